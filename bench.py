@@ -9,7 +9,8 @@ spawned before this process touches the GPU) and relays rank 0's line.  A *step*
 hot path (model call + argmax + class counts, models.py:269-270,324-331) over one batch of synthetic
 frames that are already resident in HBM.  W untimed warm-up steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize() on both sides; the time is the MAX over ranks; rank 0 prints ONE
-JSON line.
+JSON line.  ``--dump-outputs DIR`` also writes what the headline's last timed step returned (labels, class counts)
+as .npy files, so that two builds can be compared output for output on the same seeded frames.
 
 Headline (``value``, ``dtype`` "f16x2"): BASELINE.json configs[1] -- 1 x MI355X per rank, batch 1,
 synthetic 1024x1024x3 frames, in the f32-GRADE mode NBC_PREC_F16X2: every f32 value (activation or weight) is kept as
@@ -94,6 +95,11 @@ def parse(argv=None):
                          "(auto: throughput when several forwards are in flight)")
     ap.add_argument("--tune-reps", type=int, default=3, help="timed launches per tile and layer in nbc_autotune")
     ap.add_argument("--dump-ops", default=None, help="write the headline run's per-launch records (JSON) to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step returned (rank 0's labels and class counts) as "
+                         "DIR/labels.npy (float32) and DIR/counts.npy (float64), at most 64 MB: a larger label map is "
+                         "written as a fixed seeded sample of its pixels (labels.npy) with their flat indices "
+                         "(labels_index.npy); the frames and weights are seeded, so equal arguments give equal inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-bf16-leg", action="store_true", help="skip the configs[2] object (batch 8, bf16)")
@@ -110,7 +116,10 @@ def parse(argv=None):
     ap.add_argument("--tiles-file", default=None,
                     help="install the tile choices of an earlier run instead of measuring them (profiling runs: the trace "
                          "then holds no autotune launches)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -160,6 +169,30 @@ def kernel_source_id():
             h.update(f.encode())
             h.update(open(os.path.join(csrc, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 64 << 20                           # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: the (labels [N,H,W], counts int64 [N,3]) a caller of the timed path received from its last step,
+    as DIR/labels.npy (float32) and DIR/counts.npy (float64).  Labels that would not fit in DUMP_BYTES are written as a
+    sample of pixels drawn without replacement by a fixed seed (the same pixels for the same shape), in flat-index order,
+    with those indices as DIR/labels_index.npy (float64, exact)."""
+    import numpy as np
+    labels, counts = (t.cpu().numpy() for t in outputs)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), counts.astype(np.float64))
+    room = DUMP_BYTES - counts.size * 8 - 3 * 4096              # 4 KiB per file for its header
+    flat = labels.reshape(-1).astype(np.float32)
+    if flat.size * 4 <= room:
+        np.save(os.path.join(out_dir, "labels.npy"), flat.reshape(labels.shape))
+        if os.path.exists(os.path.join(out_dir, "labels_index.npy")):     # left by an earlier, larger dump
+            os.remove(os.path.join(out_dir, "labels_index.npy"))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, size=room // 12, replace=False))
+    np.save(os.path.join(out_dir, "labels.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "labels_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -290,14 +323,17 @@ def main():
             with torch.cuda.stream(streams[k]):
                 return models[k].predict_labels(batches[i % len(batches)], labels_dtype=torch.uint8)
 
+        last = {}
+
         def timed_region(n_steps, k=None):
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(n_steps):
-                step(i, k)
+                out = step(i, k)                      # a reference to the step's result tensors: nothing is copied
             torch.cuda.synchronize()
             barrier()
+            last["out"] = out
             return max_over_ranks(time.perf_counter() - t0)
 
         for i in range(warmup):
@@ -306,12 +342,11 @@ def main():
         dt = timed_region(steps)                      # (1) the contract's region: nothing but the hot path in it
         # the same region again (each with its own barrier + synchronize bracket): the spread of the line itself
         leg["dt_repeats"] = [dt] + [timed_region(steps) for _ in range(max(1, repeats) - 1)]
+        leg["last_outputs"] = last["out"]             # (labels, counts) of the last timed step, for --dump-outputs
         leg.update(dt=dt, steps=steps, warmup=warmup, batch=batch, nstreams=nstreams, tiles=tiles,
                    model=model, precision=precision)
         # per-image rows (global_idx, H, W, count_1, count_2) of this rank's last step, as the folder driver gathers them
-        labels, counts = step(steps - 1, 0)
-        torch.cuda.synchronize()
-        leg["last_counts"] = counts.cpu().numpy()
+        leg["last_counts"] = last["out"][1].cpu().numpy()
         # (2) instrumented region: the same K steps on ONE stream with a HIP event between launches
         # (recorded on the forward's stream) and tiles tuned for a launch running alone.  RAW durations.
         if instrument:
@@ -429,6 +464,8 @@ def main():
         gather_s = max_over_ranks(time.perf_counter() - t0)
         assert len(allrows) == world * args.batch
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["last_outputs"])
     if rank == 0 and args.save_tiles:
         saved = {}
         for leg in (head, legf, leg8):

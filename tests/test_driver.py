@@ -312,3 +312,32 @@ def test_abandon_marker_is_a_file_every_rank_of_the_node_can_see(tmp_path):
     a.set()                                                               # twice is fine
     a.clear()
     assert not b.is_set()
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: labels as float32 and counts as float64, exactly what the step returned; a label map over
+    the 64 MB budget becomes the same seeded sample of pixels on every call, with their flat indices."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    for n in (2, 17):                                   # 8 MB: whole; 68 MB of float32: sampled
+        g = torch.Generator().manual_seed(n)
+        labels = torch.randint(0, 3, (n, 1024, 1024), dtype=torch.uint8, generator=g)
+        counts = torch.stack([torch.bincount(l.reshape(-1).long(), minlength=3) for l in labels])
+        d = str(tmp_path / ("n%d" % n))
+        bench.dump_outputs(d, (labels, counts))
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= bench.DUMP_BYTES
+        got_l, got_c = np.load(os.path.join(d, "labels.npy")), np.load(os.path.join(d, "counts.npy"))
+        assert got_l.dtype == np.float32 and got_c.dtype == np.float64
+        assert np.array_equal(got_c, counts.numpy().astype(np.float64))
+        if n == 2:
+            assert sorted(os.listdir(d)) == ["counts.npy", "labels.npy"]
+            assert np.array_equal(got_l, labels.numpy().astype(np.float32))
+        else:
+            idx = np.load(os.path.join(d, "labels_index.npy"))
+            assert idx.dtype == np.float64 and idx.shape == got_l.shape and (np.diff(idx) > 0).all()
+            assert np.array_equal(got_l, labels.numpy().reshape(-1)[idx.astype(np.int64)].astype(np.float32))
+            bench.dump_outputs(str(tmp_path / "again"), (labels, counts))
+            assert np.array_equal(np.load(str(tmp_path / "again" / "labels_index.npy")), idx)
+    bench.dump_outputs(d, (labels[:2], counts[:2]))     # a smaller dump into the same folder drops the stale index
+    assert sorted(os.listdir(d)) == ["counts.npy", "labels.npy"]

@@ -96,3 +96,28 @@ def test_gpus_mismatch_is_an_error(built_lib):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr and not p.stdout.strip()
+
+
+def test_dump_outputs_of_the_last_timed_step(built_lib, sd_np, tmp_path):
+    """`--dump-outputs DIR`: the labels and class counts of the headline's last timed step (step 3 of 3 over 4 frames:
+    frame 2), equal from run to run and equal to what the model returns for that frame."""
+    import numpy as np
+    import torch
+    from neuralbarkcalculator_amd import synth
+    from neuralbarkcalculator_amd.model import FCNResNet50
+    flags = ("--steps", "3", "--warmup", "1", "--frames", "4", "--repeats", "1", "--no-op-events", "--no-f32-leg",
+             "--no-bf16-leg", "--no-cpu-baseline", "--no-parity")
+    dumps = []
+    for run in ("a", "b"):
+        d = run_bench(*flags, "--dump-outputs", str(tmp_path / run))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["counts.npy", "labels.npy"]
+        dumps.append((np.load(tmp_path / run / "labels.npy"), np.load(tmp_path / run / "counts.npy")))
+    (la, ca), (lb, cb) = dumps
+    assert la.dtype == np.float32 and la.shape == (1, 1024, 1024) and ca.dtype == np.float64 and ca.shape == (1, 3)
+    assert np.array_equal(la, lb) and np.array_equal(ca, cb)
+    assert np.array_equal(ca[0], np.bincount(la.reshape(-1).astype(np.int64), minlength=3).astype(np.float64))
+    m = FCNResNet50("f16x2").load_state_dict(sd_np).to("cuda:0")
+    labels, counts = m.predict_labels(torch.from_numpy(synth.make_input(2, 1024, 1024))[None].to("cuda:0"))
+    assert np.array_equal(la, labels.cpu().numpy().astype(np.float32))
+    assert np.array_equal(ca, counts.cpu().numpy().astype(np.float64))
