@@ -23,8 +23,6 @@
 //
 // D[n][m] orientation: weights are the MFMA A operand, pixels the B operand, so a lane
 // ends up holding one pixel (column) and groups of four consecutive output channels (rows).
-#include <cstdlib>
-
 #include <atomic>
 
 #include "nbc_kernels.hpp"
@@ -83,7 +81,15 @@ __device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned l
 }
 
 // Diagnostic build (tools/conv_timeline.hip, -DNBC_STAMPS): thread 0 of every block writes the 100 MHz
-// wall clock at phase boundaries into a buffer nothing else reads.  The library build has no stamps.
+// wall clock at phase boundaries into a buffer nothing else reads, and every wave counts the shader
+// cycles it spends in the K loop's vm-wait and barrier.  The kernel only calls these hooks; in the
+// library build every one of them expands to nothing.
+//   NBC_STAMP(i) / NBC_STAMP_CLK(i)   wall clock / shader clock into stamp slot i of the block
+//   NBC_WAIT_COUNTERS()               declares the wave's two wait counters
+//   NBC_WAIT_BEGIN() / NBC_WAIT_MID() in front of the vm-wait / between it and the barrier
+//   NBC_WAIT_END(count)               behind the barrier: adds both waits to the counters when `count`
+//   NBC_STAMP_WAVE_WAITS()            lane 0 of every wave stores its counters (slots 16 + wave, 32 + wave)
+//   NBC_STAMP_BLOCK_END()             when wave 0's stores were issued and acknowledged, and where the block ran
 #ifdef NBC_STAMPS
 #define NBC_STAMP(i)                                                                                   \
   do {                                                                                                 \
@@ -93,9 +99,35 @@ __device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned l
   do {                                                                                                 \
     if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 64 + (i)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
+#define NBC_WAIT_COUNTERS() unsigned long long st_vm = 0, st_bar = 0
+#define NBC_WAIT_BEGIN() const unsigned long long st0 = __builtin_amdgcn_s_memtime()
+#define NBC_WAIT_MID() const unsigned long long st1 = __builtin_amdgcn_s_memtime()
+#define NBC_WAIT_END(count)                                                                            \
+  do {                                                                                                 \
+    if (count) { st_vm += st1 - st0; st_bar += __builtin_amdgcn_s_memtime() - st1; }                  \
+  } while (0)
+#define NBC_STAMP_WAVE_WAITS()                                                                         \
+  do {                                                                                                 \
+    if (p.stamps && lane == 0) { p.stamps[(size_t)blockIdx.x * 64 + 16 + wave] = st_vm; p.stamps[(size_t)blockIdx.x * 64 + 32 + wave] = st_bar; } \
+  } while (0)
+#define NBC_STAMP_BLOCK_END()                                                                          \
+  do {                                                                                                 \
+    NBC_STAMP(5);                                   /* wave 0's stores issued */                       \
+    wait_vmcnt<0>();                                                                                   \
+    NBC_STAMP(6);                                   /* wave 0's stores acknowledged */                 \
+    if (p.stamps && threadIdx.x == 0)               /* XCC_ID (reg 20) << 32 | HW_ID (reg 4) */        \
+      p.stamps[(size_t)blockIdx.x * 64 + 7] =                                                          \
+          ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11)); \
+  } while (0)
 #else
 #define NBC_STAMP(i) do { } while (0)
 #define NBC_STAMP_CLK(i) do { } while (0)
+#define NBC_WAIT_COUNTERS()
+#define NBC_WAIT_BEGIN()
+#define NBC_WAIT_MID()
+#define NBC_WAIT_END(count) do { } while (0)
+#define NBC_STAMP_WAVE_WAITS() do { } while (0)
+#define NBC_STAMP_BLOCK_END() do { } while (0)
 #endif
 
 template <int N>
@@ -116,15 +148,20 @@ constexpr int min_waves_per_simd(int prec, int wm, int wn, int mt, int nt, int s
   return (wm * wn >= 8 && (wm * wn >= 16 || ring_bytes(prec, wm, wn, mt, nt, s) + 2048 <= 80 * 1024)) ? 4 : 2;
 }
 
+// Kernel variants (the VAR template argument; its values are part of the mangled kernel names that rocprof tables quote).
+constexpr int kVarDefault = 0;        // f32, f16x2, and bf16 on v_mfma_f32_16x16x32_bf16
+constexpr int kVarBf16Mfma32 = 1;     // bf16 on v_mfma_f32_32x32x16_bf16 (the residual layers: see launch_conv_dma)
+constexpr int kVarLoaderWaves = 8;    // f16x2 with loader waves (below)
+
 // Tile = (WM*MT*32) pixels x (WN*NT*32) channels, WM*WN waves, S LDS stages.
-// VAR 8 (f16x2): four more waves that do nothing but issue the LDS-DMAs of the ring ("loader waves"), while the WM*WN
+// kVarLoaderWaves (f16x2): four more waves that do nothing but issue the LDS-DMAs of the ring ("loader waves"), while the WM*WN
 // others only read fragments and issue MFMAs.  An LDS-DMA costs the wave that issues it 60-185 cycles
 // (MI355X_MICROARCH.md, cycle constants); an f16x2 K-step is 384 MFMA cycles per wave, so four to six DMAs per wave
 // and step in the MFMA waves' own instruction stream cost more than the arithmetic.
 typedef unsigned nt_u32x4 __attribute__((ext_vector_type(4)));   // what __builtin_nontemporal_load accepts
-constexpr int loader_waves(int var) { return var == 8 ? 4 : 0; }
+constexpr int loader_waves(int var) { return var == kVarLoaderWaves ? 4 : 0; }
 template <int PREC, int WM, int WN, int MT, int NT, int S, bool STEM, int VAR, bool BIGW>
-__global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM * WN + loader_waves(VAR)) / 4 : min_waves_per_simd(PREC, WM, WN, MT, NT, S)) void conv_dma_kernel(const ConvArgs p) {
+__global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoaderWaves ? (WM * WN + loader_waves(VAR)) / 4 : min_waves_per_simd(PREC, WM, WN, MT, NT, S)) void conv_dma_kernel(const ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int EB = PREC == 1 ? 2 : 4;           // f16x2: two f16 pieces per element, the f32 mode's geometry
   constexpr bool X2 = (PREC == 2);
@@ -257,12 +294,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   auto issue_one = [&](int d, int t, unsigned sa) __attribute__((always_inline)) {
     if (d < A_PASSES) {
       const int i = d;
-#if defined(NBC_ABLATE) && (NBC_ABLATE == 5)
-      if (X2 && !STEM && ld_kw != 0) return;           // tool builds only: pixel rows fetched for one tap column in three (timing of a
-#endif                                                 // 3x3 K loop whose rows stay in LDS across the kernel's columns)
-#if defined(NBC_ABLATE) && (NBC_ABLATE == 6)
-      if (X2 && !STEM) return;                         // tool builds only: no pixel-row DMAs at all (weights only)
-#endif
       if constexpr (!STEM) {
         dma16_buf(a_off[i], xrsrc, sa + (unsigned)(ROWS_PER_PASS * 128 * i), (unsigned)ld_cb * 128u);
       } else {
@@ -283,10 +314,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   // The L DMAs of a K-step are issued in four parts so that the main loop can slot one part behind
   // each MFMA cluster (their SALU/VMEM issue then runs in the shadow of the matrix pipe).
   auto issue_part = [&](int part, int t, int stage) __attribute__((always_inline)) {
-    if constexpr (VAR == 4 || VAR == 7) return;      // timing-only ablations: no refill DMAs in the loop
-#if defined(NBC_ABLATE) && (NBC_ABLATE == 2)
-    if constexpr (X2) return;                        // tool builds only (tools/build_variant.sh): f16x2 K loop without refill DMAs
-#endif
     const unsigned sa = smem_base + (unsigned)stage * STAGE_BYTES + wave_off;
 #pragma unroll
     for (int d = 0; d < L; ++d)
@@ -312,10 +339,10 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   // ---- MFMA geometry
   const int r = lane & 31, h = lane >> 5;
   const int wm = wave % WM, wn = wave / WM;
-  // bf16 uses v_mfma_f32_16x16x32_bf16 (VAR 0): same cycles per FLOP as 32x32x16 but the chip holds a
-  // higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back item 7); VAR 1 keeps the
-  // 32x32x16 form for A/B runs.  f32 always uses 32x32x2.
-  constexpr bool M16 = (PREC == 1 && (VAR == 0 || VAR == 4)) || X2;
+  // bf16 uses v_mfma_f32_16x16x32_bf16 (kVarDefault): same cycles per FLOP as 32x32x16 but the chip holds a
+  // higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back item 7); kVarBf16Mfma32 keeps the
+  // 32x32x16 form.  f32 always uses 32x32x2.
+  constexpr bool M16 = (PREC == 1 && VAR == kVarDefault) || X2;
   constexpr int MT16 = 2 * MT, NT16 = 2 * NT;
   const int r16 = lane & 15, q16 = lane >> 4;
   // f32 (parity mode) sums in two levels: the 32 products of a K-step go through the MFMA's own fma chain
@@ -361,9 +388,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
         for (int e = 0; e < 16; ++e) acc[j][i][e] = 0.f;
   }
 
-#ifdef NBC_STAMPS
-  unsigned long long st_vm = 0, st_bar = 0;         // diagnostic build: cycles each wave spends in the two waits
-#endif
+  NBC_WAIT_COUNTERS();                              // diagnostic build: cycles each wave spends in the two waits
   // ---- f32 K-step (64 * MT*NT/4 MFMAs of 64 cycles each per wave; two waves share a SIMD's matrix pipe).
   // With three or more ring slots (PREFETCH) the ONE barrier of a K-step sits in its middle:
   //   * ks 0,1 run on fragments that were read before the barrier (the first ones at the end of the
@@ -422,18 +447,12 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         if (PREFETCH && ks == 2 && more) {                   // wave-uniform
-#ifdef NBC_STAMPS
-          const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
+          NBC_WAIT_BEGIN();
           if (S > 3 && all_issued) wait_vmcnt<(S - 3) * L>();      // step t+1 has landed (own share)
           else wait_vmcnt<0>();
-#ifdef NBC_STAMPS
-          const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-#endif
+          NBC_WAIT_MID();
           __builtin_amdgcn_s_barrier();
-#ifdef NBC_STAMPS
-          st_vm += st1 - st0; st_bar += __builtin_amdgcn_s_memtime() - st1;
-#endif
+          NBC_WAIT_END(true);
         }
         if (ks + 1 < 4) load_frags32(stage, ks + 1, fpf[(ks + 1) & 1], fwf[(ks + 1) & 1]);
         else if (PREFETCH && more) load_frags32(next_stage, 0, fpf[0], fwf[0]);
@@ -482,14 +501,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   };
   auto x2_read = [&](int stage, uint4 (&xp0)[XM], uint4 (&xp1)[XM], uint4 (&xw0)[XN], uint4 (&xw1)[XN]) __attribute__((always_inline)) {
     if constexpr (X2F) {
-#if defined(NBC_ABLATE) && (NBC_ABLATE == 3 || NBC_ABLATE == 4)
-      // tool builds only: no fragment reads (the registers are marked written so that the MFMAs stay)
-#pragma unroll
-      for (int i = 0; i < XM; ++i) { asm volatile("" : "+v"(xp0[i].x), "+v"(xp0[i].y), "+v"(xp0[i].z), "+v"(xp0[i].w)); asm volatile("" : "+v"(xp1[i].x), "+v"(xp1[i].y), "+v"(xp1[i].z), "+v"(xp1[i].w)); }
-#pragma unroll
-      for (int j = 0; j < XN; ++j) { asm volatile("" : "+v"(xw0[j].x), "+v"(xw0[j].y), "+v"(xw0[j].z), "+v"(xw0[j].w)); asm volatile("" : "+v"(xw1[j].x), "+v"(xw1[j].y), "+v"(xw1[j].z), "+v"(xw1[j].w)); }
-      return;
-#endif
       // lane (r16, q16) reads, of row r16 of every 16-row block, chunk q16 (high pieces of channels 8*q16..) and chunk
       // 4 + q16 (their low pieces)
       const unsigned char* sa = smem + stage * STAGE_BYTES;
@@ -510,18 +521,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
       __attribute__((always_inline)) {
     if constexpr (X2F) {
       constexpr int NTI = NT16 * MT16;
-#if defined(NBC_ABLATE) && (NBC_ABLATE == 1 || NBC_ABLATE == 4)
-      // tool builds only: fragments consumed, no MFMA
-#pragma unroll
-      for (int i = 0; i < XM; ++i) { asm volatile("" :: "v"(xp0[i].x), "v"(xp0[i].y), "v"(xp0[i].z), "v"(xp0[i].w)); asm volatile("" :: "v"(xp1[i].x), "v"(xp1[i].y), "v"(xp1[i].z), "v"(xp1[i].w)); }
-#pragma unroll
-      for (int j = 0; j < XN; ++j) { asm volatile("" :: "v"(xw0[j].x), "v"(xw0[j].y), "v"(xw0[j].z), "v"(xw0[j].w)); asm volatile("" :: "v"(xw1[j].x), "v"(xw1[j].y), "v"(xw1[j].z), "v"(xw1[j].w)); }
-      if (do_issue) {
-#pragma unroll
-        for (int part = 0; part < 4; ++part) issue_part(part, t_issue, issue_stage);
-      }
-      return;
-#endif
       const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
       // product-major: two MFMAs on one accumulator are NTI instructions apart; the scaled high pieces of a weight
       // block are formed right in front of the block's third products (four v_pk_mul_f16; hoisting them cost 0-3 %,
@@ -581,13 +580,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
       }
       return;
     }
-    if constexpr (VAR == 6) {                        // timing-only ablation: DMA + barriers only
-      if (do_issue) {
-#pragma unroll
-        for (int part = 0; part < 4; ++part) issue_part(part, t_issue, issue_stage);
-      }
-      return;
-    }
     if constexpr (M16) {
       // two 32-deep halves per K-step; lane (r16, q16) reads row r16 of each 16-row tile, chunk 4*half+q16
       constexpr bool DBUF = (MT16 + NT16) * 8 <= 64;      // both halves' fragments in <= 64 VGPRs
@@ -630,28 +622,10 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
       for (int j = 0; j < NT; ++j)
         wfr[j] = *reinterpret_cast<const uint4*>(sb + lds_off((wn * NT + j) * 32 + r, chunk));
     };
-    if constexpr (VAR == 7) {                        // timing-only ablation: MFMAs on constant fragments
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) pf[b][i] = make_uint4(0x3f803f80u + lane, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) wf[b][j] = make_uint4(0x3f803f80u, 0x3f803f80u + lane, 0x3f803f80u, 0x3f803f80u);
-      }
-    } else {
-      load_frags(0, pf[0], wf[0]);
-    }
+    load_frags(0, pf[0], wf[0]);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      if (VAR != 7 && ks + 1 < 4) load_frags(ks + 1, pf[(ks + 1) & 1], wf[(ks + 1) & 1]);
-      if constexpr (VAR == 3) {                        // timing-only ablation: fragments read, no MFMA
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-          asm volatile("" ::"v"(pf[ks & 1][i].x), "v"(pf[ks & 1][i].y), "v"(pf[ks & 1][i].z), "v"(pf[ks & 1][i].w));
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          asm volatile("" ::"v"(wf[ks & 1][j].x), "v"(wf[ks & 1][j].y), "v"(wf[ks & 1][j].z), "v"(wf[ks & 1][j].w));
-      } else
+      if (ks + 1 < 4) load_frags(ks + 1, pf[(ks + 1) & 1], wf[(ks + 1) & 1]);
 #pragma unroll
       for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -673,7 +647,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   constexpr int PASSES = 32 / PIX_PER_PASS;
   // identity prefetch: <= 64 VGPRs per lane, and not on the 128x64 wave tile of the 16x16 path
   // (128 accumulators + 48 fragment registers leave no room: it spilled)
-  constexpr bool RES_PREFETCH = (MT * PASSES <= 16) && !(PREC == 1 && (VAR == 0 || VAR == 4) && MT * NT >= 8) && !X2;
+  constexpr bool RES_PREFETCH = (MT * PASSES <= 16) && !(PREC == 1 && VAR == kVarDefault && MT * NT >= 8) && !X2;
   static_assert(WM * WN * 32 * PITCH <= TABLE_OFF, "epilogue scratch must fit below the scale/shift table");
   // Output addressing: a wave-uniform 64-bit base (first pixel of the tile, first channel of the wave's
   // slab) plus a 32-bit per-lane offset (row inside the tile x row pitch + the lane's 16-byte chunk).
@@ -738,27 +712,19 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
       step32(t, t % S, true, t + S - 2 < T, (t + 1) % S, t + S - 1 < T, t + S - 1, (t + S - 1) % S);
     NBC_STAMP(3);
     NBC_STAMP_CLK(12);
-#ifdef NBC_STAMPS
-    if (p.stamps && lane == 0) { p.stamps[(size_t)blockIdx.x * 64 + 16 + wave] = st_vm; p.stamps[(size_t)blockIdx.x * 64 + 32 + wave] = st_bar; }
-#endif
+    NBC_STAMP_WAVE_WAITS();
     prefetch_identity();                                         // no DMA is outstanding any more
     step32(T - 1, (T - 1) % S, false, false, 0, false, 0, 0);
   } else {
   // top of K-step t: own DMAs of step t have landed when at most (S-2) younger steps' DMAs are outstanding; the
   // barrier makes every wave's share visible and retires the reads of the slot about to be refilled
   auto loop_top = [&](int t) __attribute__((always_inline)) {
-#ifdef NBC_STAMPS
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
+    NBC_WAIT_BEGIN();
     if (t + (S - 2) < T) wait_vmcnt<(S - 2) * L>();
     else wait_vmcnt<0>();
-#ifdef NBC_STAMPS
-    const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-#endif
+    NBC_WAIT_MID();
     __builtin_amdgcn_s_barrier();
-#ifdef NBC_STAMPS
-    if (t > 0) { st_vm += st1 - st0; st_bar += __builtin_amdgcn_s_memtime() - st1; }
-#endif
+    NBC_WAIT_END(t > 0);
     if (t == 0) { NBC_STAMP(2); NBC_STAMP_CLK(11); }   // first K-step landed
   };
   if constexpr (STAGGER) {
@@ -833,9 +799,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
   __builtin_amdgcn_s_barrier();
   NBC_STAMP(3);                                     // last K-step landed (main loop done but for its MFMAs)
   NBC_STAMP_CLK(12);
-#ifdef NBC_STAMPS
-  if (p.stamps && lane == 0) { p.stamps[(size_t)blockIdx.x * 64 + 16 + wave] = st_vm; p.stamps[(size_t)blockIdx.x * 64 + 32 + wave] = st_bar; }
-#endif
+  NBC_STAMP_WAVE_WAITS();
   if (computes) prefetch_identity();                 // (loader waves own no output rows: their row / channel indices lie outside the tile)
   if constexpr (F32) step32(T - 1, (T - 1) % S, false, false, 0, false, 0, 0);
   else if constexpr (STAGGER) {
@@ -1014,17 +978,10 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == 8 ? (WM 
     }
     if (i == 0) NBC_STAMP(10);                      // first slab's stores issued
   }
-#ifdef NBC_STAMPS
-  NBC_STAMP(5);                                     // wave 0's stores issued
-  wait_vmcnt<0>();
-  NBC_STAMP(6);                                     // wave 0's stores acknowledged
-  if (p.stamps && threadIdx.x == 0)                 // where the block ran: XCC_ID (reg 20) << 32 | HW_ID (reg 4)
-    p.stamps[(size_t)blockIdx.x * 64 + 7] =
-        ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));
-#endif
+  NBC_STAMP_BLOCK_END();
 }
 
-template <int PREC, int WM, int WN, int MT, int NT, int S, bool STEM, int VAR = 0, bool BIGW = false>
+template <int PREC, int WM, int WN, int MT, int NT, int S, bool STEM, int VAR = kVarDefault, bool BIGW = false>
 hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
   constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
   constexpr int smem = ring_bytes(PREC, WM, WN, MT, NT, S) + 2048;     // ring (or scratch) + scale/shift table
@@ -1063,7 +1020,7 @@ hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
 //                                                               long-K layers, 2-5 % faster epilogue-heavy 1x1 layers)
 //   13  128x128   2x4            64x32      3       96 KiB   1   (8 waves)
 //   f16x2 only (9, 10 there with three stages):
-//   14  128x128   2x4 + 4        64x32      3       96 KiB   1   (13 with four loader waves, VAR 8: the tile of a layer whose
+//   14  128x128   2x4 + 4        64x32      3       96 KiB   1   (13 with four loader waves, kVarLoaderWaves: the tile of a layer whose
 //                                                               128x128 tiles number 256 or fewer, one per CU: layer3 at batch 1)
 //   15  128x64    4x2 + 4        32x32      3       72 KiB   1   (10 with four loader waves; layer2's 3x3 at batch 1)
 //   16  128x128   2x2 + 4        64x64      3       96 KiB   1   (four MFMA waves of 64x64 + four loader waves: ties 14)
@@ -1080,14 +1037,14 @@ hipError_t launch_tile(const ConvArgs& a, int tile, hipStream_t s) {
       if (a.res != nullptr && a.w_bytes >= (3u << 20)) {
         if (tile == 17) return launch_cfg<PREC, 2, 4, 2, 1, 2, false, VAR, true>(a, s);
         if (tile == 1) return launch_cfg<PREC, 2, 2, 2, 2, 2, false, VAR, true>(a, s);
-        if (tile == 14) return launch_cfg<PREC, 2, 4, 2, 1, 3, false, 8, true>(a, s);
+        if (tile == 14) return launch_cfg<PREC, 2, 4, 2, 1, 3, false, kVarLoaderWaves, true>(a, s);
       }
     }
     switch (tile) {
       case 0: return launch_cfg<PREC, 2, 2, 2, 1, 3, STEM, VAR>(a, s);
       case 1: return launch_cfg<PREC, 2, 2, 2, 2, 2, STEM, VAR>(a, s);
       case 5: return launch_cfg<PREC, 2, 4, 2, 2, 3, STEM, VAR>(a, s);
-      case 16: return launch_cfg<PREC, 2, 2, 2, 2, 3, STEM, STEM ? VAR : 8>(a, s);    // 128x128 of 64x64 wave tiles + four loader waves
+      case 16: return launch_cfg<PREC, 2, 2, 2, 2, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);    // 128x128 of 64x64 wave tiles + four loader waves
       case 17: return launch_cfg<PREC, 2, 4, 2, 1, 2, STEM, VAR>(a, s);               // 13 with two stages: two blocks per CU
       case 6: return launch_cfg<PREC, 4, 2, 2, 1, 3, STEM, VAR>(a, s);
       case 7: return launch_cfg<PREC, 2, 2, 2, 1, 2, STEM, VAR>(a, s);
@@ -1095,12 +1052,8 @@ hipError_t launch_tile(const ConvArgs& a, int tile, hipStream_t s) {
       case 9: return launch_cfg<PREC, 4, 2, 1, 2, 3, STEM, VAR>(a, s);
       case 10: return launch_cfg<PREC, 4, 2, 1, 1, 3, STEM, VAR>(a, s);
       case 13: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, VAR>(a, s);
-#ifdef NBC_TILE14_S4
-      case 14: return launch_cfg<PREC, 2, 4, 2, 1, 4, STEM, STEM ? VAR : 8>(a, s);     // tool builds only: four ring slots
-#else
-      case 14: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, STEM ? VAR : 8>(a, s);     // 13 with four loader waves
-#endif
-      case 15: return launch_cfg<PREC, 4, 2, 1, 1, 3, STEM, STEM ? VAR : 8>(a, s);     // 10 with four loader waves
+      case 14: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);     // 13 with four loader waves
+      case 15: return launch_cfg<PREC, 4, 2, 1, 1, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);     // 10 with four loader waves
       default: return hipErrorInvalidValue;
     }
   } else
@@ -1129,7 +1082,7 @@ hipError_t launch_tile(const ConvArgs& a, int tile, hipStream_t s) {
 
 //   18  128x128   row-step kernel (conv3x3_rows.hip: ONE image row x 128 channels, eight 64x32 MFMA waves + four loader waves, the
 //                                row in LDS for its three taps, one barrier per (channel block, kh)): the 3x3 layers of
-//                                128-pixel-wide maps with 256 output channels or more run on it and on nothing else
+//                                128-pixel-wide maps with 256 output channels or more run on it or on tile 20
 //   19  128x64    row-step kernel (one image row x 64 channels, four MFMA + four loader waves): likewise those with 64 / 128
 //                                output channels (layer2.1-3 conv2; conv_rows_kind)
 //   20  256x64    row-step kernel (TWO image rows, a dilation apart, x 64 channels; eight MFMA + four loader waves): the layers of
@@ -1145,8 +1098,9 @@ int conv_tile_cols(int tile) { return tile >= 0 && tile < CONV_TILE_COUNT ? kTil
 // Whether tile id `tile` exists for this precision and divides the layer's output channels.
 bool conv_tile_ok(int precision, int tile, int Co, int rows_kind) {
   if (tile < 0 || tile >= CONV_TILE_COUNT) return false;
-  // the row-resident 3x3 kernel's tiles and the generic ones: never mixed (kind 1: 18; kind 2: 19; kind 0: 0 .. 17)
-  const int tile_kind = tile < CONV_TILE_ROWS_FIRST ? 0 : tile == 19 ? 2 : 1;      // (kind 1: tiles 18 and 20)
+  // the row-resident 3x3 kernel's tiles and the generic ones: never mixed (kind 1: tiles 18 or 20, same K order and bits;
+  // kind 2: tile 19; kind 0: 0 .. 17)
+  const int tile_kind = tile < CONV_TILE_ROWS_FIRST ? 0 : tile == 19 ? 2 : 1;
   if (rows_kind != tile_kind) return false;
   if (rows_kind != 0) return precision == 2 && Co % kTileCols[tile] == 0;
   if (precision == 0 && (tile == 3 || tile == 12)) return false;   // the f32 kernel keeps two accumulator sets
@@ -1249,36 +1203,16 @@ hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream
   if (tile < 0) tile = choose_conv_tile(a.M, a.Co, a.ksteps * (128 / eb), precision, rows);
   if (!conv_tile_ok(precision, tile, a.Co, rows)) return hipErrorInvalidValue;
   if (rows != 0) return launch_conv3x3_rows(a, tile - CONV_TILE_ROWS_FIRST, s);
-#ifdef NBC_DIAG
-  // measurement builds only (tools/build_tools.sh): the library never reads these variables
-  // NBC_CONV_ABLATE=1 (no MFMA) / 2 (no refill DMA): timing-only builds of the bf16 256x256 and
-  // 128x256 tiles, results are garbage.  Never set outside an experiment.
-  static const int ablate = [] { const char* e = getenv("NBC_CONV_ABLATE"); return e ? atoi(e) : 0; }();
-  if (ablate && precision == 1 && !a.stem && (tile == 3 || tile == 5)) {
-    // 1: no MFMA (DMA + fragment reads)  2: no refill DMA (MFMA + fragment reads)
-    // 3: DMA + barriers only             4: MFMA on constant fragments, no DMA, no fragment reads
-    switch (ablate) {
-      case 1: return tile == 3 ? launch_cfg<1, 2, 4, 4, 2, 2, false, 3>(a, s) : launch_cfg<1, 2, 4, 2, 2, 3, false, 3>(a, s);
-      case 2: return tile == 3 ? launch_cfg<1, 2, 4, 4, 2, 2, false, 4>(a, s) : launch_cfg<1, 2, 4, 2, 2, 3, false, 4>(a, s);
-      case 3: return tile == 3 ? launch_cfg<1, 2, 4, 4, 2, 2, false, 6>(a, s) : launch_cfg<1, 2, 4, 2, 2, 3, false, 6>(a, s);
-      default: return tile == 3 ? launch_cfg<1, 2, 4, 4, 2, 2, false, 7>(a, s) : launch_cfg<1, 2, 4, 2, 2, 3, false, 7>(a, s);
-    }
-  }
-#endif
-  if (precision == 0) return a.stem ? launch_tile<0, true, 0>(a, tile, s) : launch_tile<0, false, 0>(a, tile, s);
-  if (precision == 2) return a.stem ? launch_tile<2, true, 0>(a, tile, s) : launch_tile<2, false, 0>(a, tile, s);
-  if (a.stem) return launch_tile<1, true, 0>(a, tile, s);
-  // bf16: the MFMA-heavy layers run on v_mfma_f32_16x16x32_bf16 (VAR 0: +4-5 % measured on the
+  if (precision == 0) return a.stem ? launch_tile<0, true, kVarDefault>(a, tile, s) : launch_tile<0, false, kVarDefault>(a, tile, s);
+  if (precision == 2) return a.stem ? launch_tile<2, true, kVarDefault>(a, tile, s) : launch_tile<2, false, kVarDefault>(a, tile, s);
+  if (a.stem) return launch_tile<1, true, kVarDefault>(a, tile, s);
+  // bf16: the MFMA-heavy layers run on v_mfma_f32_16x16x32_bf16 (kVarDefault: +4-5 % measured on the
   // head and layer4 3x3 convs, the chip holds a higher clock on it); the residual 1x1 layers keep
-  // v_mfma_f32_32x32x16_bf16 (VAR 1), whose fragment registers leave room for the identity prefetch
+  // v_mfma_f32_32x32x16_bf16 (kVarBf16Mfma32), whose fragment registers leave room for the identity prefetch
   // on the 256x256 tile.  The choice depends on the layer only, never on the tile, so the
   // tile-invariance of the results holds.
-#ifdef NBC_DIAG
-  static const int mfma32 = [] { const char* e = getenv("NBC_CONV_MFMA32"); return e ? atoi(e) : 0; }();   // A/B runs
-  if (mfma32) return launch_tile<1, false, 1>(a, tile, s);
-#endif
-  if (a.res != nullptr) return launch_tile<1, false, 1>(a, tile, s);
-  return launch_tile<1, false, 0>(a, tile, s);
+  if (a.res != nullptr) return launch_tile<1, false, kVarBf16Mfma32>(a, tile, s);
+  return launch_tile<1, false, kVarDefault>(a, tile, s);
 }
 
 }  // namespace nbc

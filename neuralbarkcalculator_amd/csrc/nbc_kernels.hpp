@@ -39,7 +39,7 @@ constexpr int CONV_TILE_ROWS_FIRST = 18;   // (conv3x3_rows.hip: one image row x
 int conv_tile_rows(int tile);
 int conv_tile_cols(int tile);
 // Whether a convolution runs on the row-resident 3x3 kernels (conv3x3_rows.hip; f16x2, 3x3, stride 1, no identity): 0 no;
-// 1: 128-pixel-wide maps, >= 256 output channels: tile 18 ONLY; 2: 128-pixel-wide maps, 64 / 128 output channels: tile 19 ONLY.  A property of the layer and its shape that fixes its K order; every other convolution runs on
+// 1: 128-pixel-wide maps, >= 256 output channels: tiles 18 or 20 (same K order and bits); 2: 128-pixel-wide maps, 64 / 128 output channels: tile 19.  A property of the layer and its shape that fixes its K order; every other convolution runs on
 // tiles 0 .. 17 only.
 int conv_rows_kind(int precision, int k, int stride, int pad, int dil, int Hi, int Wi, int Ho, int Wo, int Ci, int Co, bool has_res);
 bool conv_tile_ok(int precision, int tile, int Co, int rows_kind);   // the tile exists for the precision and the kind of convolution and divides Co

@@ -271,9 +271,6 @@ int f16x2_row_exponent(const float* row, size_t n, bool* clamped) {
 // this existed, bit for bit.  classifier.4 reads the last tensor with f32 weights: they take the 2^-a.
 // out_exp[u] / in_exp[u]: power of conv unit u's output tensor / of the tensor it reads.
 static int tensor_exponent(float est) {
-#ifdef NBC_NO_ACT_EXP
-  return 0;                                           // tool builds only (scripts/act_floor_probe.py): the library before this existed
-#endif
   if (!(est > 0.f) || !std::isfinite(est)) return 0;
   if (est >= 0.03125f && est <= 128.0f) return 0;
   int e = 0;

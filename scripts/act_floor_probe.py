@@ -2,7 +2,8 @@
 """f16x2's activation floor, before and after the per-tensor powers of two of nbc_pack_weights: logit error against a float64
 evaluation (of the logit range) for the seed-7 network with its scale-free tensors moved by a power of two
 (tests/conftest.py::rescale_activations), for one or more builds of the library in one process.
-  tools/build_variant.sh noactexp "-DNBC_NO_ACT_EXP"      # the packer without the powers (round 4's behaviour)
+  mkdir -p /tmp/r05 && git archive ba884b8 neuralbarkcalculator_amd/csrc | tar -x -C /tmp/r05   # the last revision with the switch
+  tools/build_variant.sh noactexp "-DNBC_NO_ACT_EXP" /tmp/r05/neuralbarkcalculator_amd/csrc      # the packer without the powers (round 4's behaviour)
   gpurun -- 'python scripts/act_floor_probe.py tools/_bin/libnbc_noactexp.so neuralbarkcalculator_amd/libnbc_hip.so'
 (profiles/r05_small_activation_floor_before_fix.log)"""
 import ctypes as C

@@ -32,11 +32,25 @@ def test_library_exports_every_declared_symbol(built_lib):
 
 def test_library_holds_no_measurement_switches(built_lib):
     """The timing-only variants of the conv kernel (no MFMA, no refill DMA, ...) and the A/B instruction switch
-    exist in the -DNBC_DIAG builds of tools/ only: the product library neither reads their environment variables
-    nor contains those kernel instantiations."""
+    are gone from the sources (revision ba884b8 is the last that had them): the product library neither reads
+    their environment variables nor contains those kernel instantiations."""
     blob = open(_lib.LIB_PATH, "rb").read()
     for needle in (b"NBC_CONV_ABLATE", b"NBC_CONV_MFMA32", b"getenv"):
         assert needle not in blob, needle
+
+
+def test_sources_hold_no_measurement_switches():
+    """The product sources carry no ablation or diagnostic switch, and the conv kernel's only preprocessor
+    conditional is the block that defines the stamp hooks of the diagnostic build (tools/conv_timeline.hip)."""
+    csrc = os.path.join(ROOT, "neuralbarkcalculator_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".cpp")))
+    assert "conv_igemm_dma.hip" in sources
+    for f in sources:
+        text = open(os.path.join(csrc, f)).read()
+        for needle in ("NBC_ABLATE", "NBC_DIAG", "NBC_TILE14_S4", "NBC_NO_ACT_EXP", "getenv"):
+            assert needle not in text, (f, needle)
+    conv = open(os.path.join(csrc, "conv_igemm_dma.hip")).read()
+    assert len(re.findall(r"^\s*#\s*if", conv, flags=re.M)) == 1
 
 
 def test_topology_through_the_abi(built_lib):

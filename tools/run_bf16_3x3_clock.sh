@@ -2,6 +2,7 @@
 # bf16 3x3 layers: TFLOP/s next to the shader clock the chip holds in the K loop and the MFMA-busy share of
 # its cycles (diagnostic build with in-kernel stamps; random data, back-to-back launches).
 # Batch 1 shapes (M = 16384 / 65536) and batch 8 shapes (M x 8), on the tiles the autotuner picks.
+set -o pipefail                 # a failed or timed-out run ends the script, not only a grep that matched nothing
 T=tools/_bin/conv_timeline
 run() { timeout -k 5 90 $T "$@" | grep -E "^shape|K loop" | cut -c1-200 || exit 1; }
 echo "== batch 1"

@@ -1,5 +1,6 @@
 #!/bin/bash
 # f32 parity mode: shader clock and MFMA-busy share of the K loop on the layers that carry the FLOPs
+set -o pipefail                 # a failed or timed-out run ends the script, not only a grep that matched nothing
 T=tools/_bin/conv_timeline
 run() { timeout -k 5 90 $T "$@" | grep -E "^shape|K loop|per wave" || exit 1; }
 run 128 128 2048 512 3 1 0 2 1 0
