@@ -226,6 +226,17 @@ int nbc_upsample_argmax(nbc_ctx* ctx, const float* logits_lowres_dev, int N, int
 int nbc_remove_small_zones(nbc_ctx* ctx, void* labels_dev, int labels_dtype, int N, int H, int W, int min_pixels,
                            int exclude_nodes, int64_t* counts_dev, void* hip_stream);
 
+/* Per-image 3x3 confusion counts of predicted labels against a grey target mask: the pixel counting behind the evaluation
+ * loop's lovasz `iou` (lovasz_losses.py:54-73) and `PixelWiseF1` (utils.py:201-235), called at __main__.py:331-332;
+ * the ratios are host arithmetic (neuralbarkcalculator_amd/metrics.py).  No context: csrc/confusion.hip.
+ * labels_dev  uint8 or int64 [N,H,W] (NBC_LABEL_U8 / NBC_LABEL_I64), values in {0,1,2}; other values are counted nowhere
+ * target_dev  uint8 [N,H,W], grey levels as PIL 'L' gives them; class = round(2 * float32(v) / 255)
+ *             (dataset.py:189-197): 0..63 -> 0, 64..191 -> 1, 192..255 -> 2
+ * conf_dev    int64 [N,3,3], conf[n][t][p] = pixels with target class t and predicted class p; overwritten
+ * Runs on hip_stream (the caller's current device); no synchronisation.  N <= 65535, H * W < 2^31. */
+int nbc_confusion(const void* labels_dev, int labels_dtype, const uint8_t* target_dev,
+                  int N, int H, int W, int64_t* conf_dev, void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

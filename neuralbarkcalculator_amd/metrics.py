@@ -1,0 +1,107 @@
+"""The evaluation metrics of the reference, from 3x3 confusion counts (host-side float64 arithmetic).
+
+The reference's evaluation loop (/root/reference/src/bark_calculator/__main__.py:299-437) writes one tab-separated row
+per labelled image (header at ``__main__.py:307-311``).  Its two metrics are ratios of pixel counts, so they are
+computed here from ``conf[t][p]`` (pixels of target class t predicted as p; ``FCNResNet50.confusion`` counts them on the
+device):
+
+* IoU: lovasz ``iou`` (lovasz_losses.py:54-73) on the argmax of the logits (``__main__.py:331``).  ``IoU_c = tp / union``
+  as Python floats, ``EMPTY = 1.0`` when the union is empty, times 100.  The ``remove_small_zones`` the loop applies to the
+  float logits first (``__main__.py:324``) changes nothing but exact-0.0 logits, which it turns into 1.0; that quirk is
+  not reproduced: the IoU here is that of the raw argmax.
+* F1: ``PixelWiseF1('all')`` (utils.py:201-235), i.e. sklearn 0.21's ``f1_score(average=None)`` on the labels AFTER
+  ``remove_small_zones`` (150 pixels): ``p = tp / (tp + fp)``, ``r = tp / (tp + fn)`` (0 on a zero denominator),
+  ``f = 2 p r / (p + r)`` (0 when ``p + r == 0``), then the absent-class rule of utils.py:222-226 in class order on the
+  array as already updated (a class absent from target and output takes the mean of the other two scores), times 100.
+* The percent columns: float32 ``count / (H W) * 100`` with ``'{:.5f}'`` (``__main__.py:392-398``), like
+  ``predict.stats_row``; "Output" from the raw argmax, "Target" from the target.
+"""
+from __future__ import annotations
+
+from typing import List, Sequence
+
+import numpy as np
+
+CLASS_NAMES = ["nothing", "bark", "node"]
+EVAL_CSV_HEADER = ["Name", "Type", "Split", "iou_nothing", "iou_bark", "iou_node", "iou_mean", "f1_nothing", "f1_bark",
+                   "f1_node", "f1_mean", "Output Bark %", "Output Node %", "Target Bark %", "Target Node %"]   # __main__.py:307-311
+SPLIT = "all"                     # the Split column: the tool has no train / valid / test split (__main__.py:375-377)
+
+
+def target_classes(grey: np.ndarray) -> np.ndarray:
+    """Class of each grey level of a dual, as dataset.py:189-197 decodes it after ToTensor: ``round(2 * float32(v) / 255)``
+    -- 0 for 0..63, 1 for 64..191, 2 for 192..255 (no level lands on a half).  What the kernel of ``nbc_confusion`` does
+    with ``(v + 64) >> 7``."""
+    grey = np.asarray(grey)
+    if grey.dtype != np.uint8:
+        raise ValueError("grey must be uint8")
+    return ((grey.astype(np.int32) + 64) >> 7).astype(np.uint8)
+
+
+def confusion_numpy(labels: np.ndarray, target_class: np.ndarray) -> np.ndarray:
+    """conf[t][p] of one image on the host: int64 [3,3] (labels outside {0,1,2} counted nowhere)."""
+    p = np.asarray(labels).astype(np.int64).ravel()
+    t = np.asarray(target_class).astype(np.int64).ravel()
+    ok = (p >= 0) & (p < 3)
+    return np.bincount(3 * t[ok] + p[ok], minlength=9).reshape(3, 3)
+
+
+def iou(conf) -> np.ndarray:
+    """lovasz ``iou`` (lovasz_losses.py:54-73) of one image from its raw-argmax confusion: float64 [3], in percent."""
+    conf = np.asarray(conf, dtype=np.int64).reshape(3, 3)
+    out = []
+    for c in range(3):
+        inter = int(conf[c, c])
+        union = int(conf[c, :].sum() + conf[:, c].sum()) - inter
+        out.append(1.0 if union == 0 else float(inter) / float(union))
+    return 100 * np.array(out)
+
+
+def f1(conf) -> np.ndarray:
+    """``PixelWiseF1('all')`` (utils.py:201-235) of one image from its confusion after remove_small_zones: float64 [3], in
+    percent (the ``* 100`` of __main__.py:332)."""
+    conf = np.asarray(conf, dtype=np.int64).reshape(3, 3)
+    tp = np.diag(conf).astype(np.float64)
+    pred = conf.sum(axis=0).astype(np.float64)        # tp + fp
+    true = conf.sum(axis=1).astype(np.float64)        # tp + fn
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(pred > 0, tp / np.where(pred > 0, pred, 1), 0.0)
+        r = np.where(true > 0, tp / np.where(true > 0, true, 1), 0.0)
+        den = p + r
+        scores = np.where(den > 0, 2.0 * p * r / np.where(den > 0, den, 1), 0.0)
+    for i in range(3):                                # utils.py:222-226, sequential on the updated array
+        if true[i] == 0 and pred[i] == 0:
+            scores[i] = np.delete(scores, i).mean()
+    return scores * 100
+
+
+def percent(count: int, pixels: int) -> str:
+    """``'{:.5f}'.format((x == c).float().mean() * 100)`` in float32 (__main__.py:392-398)."""
+    frac = np.float32(count) / np.float32(pixels)
+    return "{:.5f}".format(float(frac * np.float32(100)))
+
+
+def eval_row(name: str, wood: str, conf_raw, conf_clean) -> List[str]:
+    """One row of the evaluation CSV (__main__.py:371-398) from the image's two confusions."""
+    raw = np.asarray(conf_raw, dtype=np.int64).reshape(3, 3)
+    ious, f1s = iou(raw), f1(conf_clean)
+    pixels = int(raw.sum())
+    row = [name, wood, SPLIT]
+    row += ["{:.3f}".format(v) for v in ious] + ["{:.3f}".format(ious.mean())]
+    row += ["{:.3f}".format(v) for v in f1s] + ["{:.3f}".format(f1s.mean())]
+    pred, true = raw.sum(axis=0), raw.sum(axis=1)
+    row += [percent(int(pred[c]), pixels) for c in (1, 2)] + [percent(int(true[c]), pixels) for c in (1, 2)]
+    return row
+
+
+def summarize(rows: Sequence[Sequence[str]], conf_raw_total, conf_clean_total) -> dict:
+    """Pooled metrics (summed confusions over every evaluated image) and the mean of each numeric CSV column."""
+    out = {"pooled": {}, "column_means": {}}
+    ious, f1s = iou(conf_raw_total), f1(conf_clean_total)
+    for c, name in enumerate(CLASS_NAMES):
+        out["pooled"]["iou_" + name] = float(ious[c])
+        out["pooled"]["f1_" + name] = float(f1s[c])
+    out["pooled"]["iou_mean"], out["pooled"]["f1_mean"] = float(ious.mean()), float(f1s.mean())
+    for j, col in enumerate(EVAL_CSV_HEADER[3:], start=3):
+        out["column_means"][col] = float(np.mean([float(r[j]) for r in rows])) if rows else None
+    return out

@@ -189,6 +189,28 @@ class FCNResNet50:
                                                         counts.data_ptr(), stream), "nbc_remove_small_zones")
         return labels, counts
 
+    def confusion(self, labels: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """Per-image 3x3 confusion counts on the device (nbc_confusion): the pixel counting behind the evaluation loop's
+        ``iou`` and ``PixelWiseF1`` (__main__.py:331-332).  ``labels``: contiguous uint8 or int64 ``[N,H,W]`` / ``[H,W]``
+        with values in {0,1,2} (others are counted nowhere); ``target``: contiguous uint8 grey mask of the same shape, class
+        ``round(2 * v / 255)`` (dataset.py:189-197); both on this model's device.  Runs on the current stream.  Returns int64
+        ``[N,3,3]``: ``conf[n, t, p]`` = pixels of target class t predicted as p."""
+        self._require_ctx()
+        if labels.device != self.device or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
+            raise ValueError("labels must be a contiguous uint8 or int64 tensor on %s" % (self.device,))
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
+            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
+        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
+            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
+        n = 1 if labels.dim() == 2 else int(labels.shape[0])
+        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        conf = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.nbc_confusion(labels.data_ptr(), _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+                                               target.data_ptr(), n, h, w, conf.data_ptr(), stream), "nbc_confusion")
+        return conf
+
     def resize_cubic_u8(self, image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """The resize of the reference's preprocessor (models.py:191-198) on the device: uint8 RGB
         ``[H,W,3]`` -> ToTensor -> ``skimage.transform.resize(order=3, mode='reflect',

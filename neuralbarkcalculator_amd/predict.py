@@ -366,14 +366,15 @@ def label_png(labels: np.ndarray) -> np.ndarray:
     return out
 
 
-def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, device=None, cap: int = None) -> np.ndarray:
+def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, device=None, cap: int = None,
+                width: int = ROW_WIDTH) -> np.ndarray:
     """all_gather of fixed-size per-rank row buffers; returns the rows sorted by global index.
-    ``local_rows``: int64 [k, ROW_WIDTH] with k <= ``cap`` (default ceil(n_total / world), the round-robin
+    ``local_rows``: int64 [k, width] with k <= ``cap`` (default ceil(n_total / world), the round-robin
     bound; pixel-balanced shards pass the largest shard's size)."""
     import torch
     if cap is None:
         cap = (n_total + world - 1) // world if n_total else 0
-    buf = torch.full((max(cap, 1), ROW_WIDTH), -1, dtype=torch.int64)
+    buf = torch.full((max(cap, 1), width), -1, dtype=torch.int64)
     if len(local_rows):
         buf[: len(local_rows)] = torch.from_numpy(np.asarray(local_rows, dtype=np.int64))
     if dist is None or world == 1:
@@ -719,8 +720,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             "distinct_shapes": len(shape_count), "autotuned_shapes": len({k for _, k in tuned}), "streams": n_streams}
 
 
-def launch_ranks(n: int, argv: Sequence[str]) -> int:
-    """``--gpus N`` without a torchrun environment: start N ranks (one per GPU) as a child process."""
+def launch_ranks(n: int, argv: Sequence[str], module: str = "neuralbarkcalculator_amd.predict") -> int:
+    """``--gpus N`` without a torchrun environment: start N ranks (one per GPU) of ``module`` as a child process."""
     import socket
     import subprocess
     import sys
@@ -735,7 +736,7 @@ def launch_ranks(n: int, argv: Sequence[str]) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "-m", "neuralbarkcalculator_amd.predict"] + list(argv)
+           "--master-port", str(port), "-m", module] + list(argv)
     return subprocess.run(cmd, env=env).returncode
 
 
