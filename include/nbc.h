@@ -90,6 +90,18 @@ enum {
   NBC_PACK_SCALE_RANGE = 2   /* a BatchNorm scale / shift left f32's normal range under the powers of two folded into it */
 };
 
+/* Networks the library runs (models.py:46-57, 127-139).  Both share the dilated ResNet-50 trunk (318 backbone.* keys)
+ * and differ in the head.  Every function without an architecture argument is architecture 0. */
+enum {
+  NBC_ARCH_FCN_RESNET50 = 0,       /* FCNHead(2048, 3): 3x3 conv 2048 -> 512, BN, ReLU, 1x1 conv 512 -> 3 (326 keys) */
+  NBC_ARCH_DEEPLABV3_RESNET50 = 1  /* DeepLabHead(2048, 3) of torchvision 0.3: ASPP(2048, [12, 24, 36]) -- 1x1 conv, three
+                                      3x3 convs at dilation 12 / 24 / 36 and global-average-pool + 1x1 conv, each 256
+                                      channels with BN + ReLU, concatenated (1280) and projected 1280 -> 256 with BN + ReLU --,
+                                      3x3 conv 256 -> 256, BN, ReLU, 1x1 conv 256 -> 3 (362 keys).  Its activations have the
+                                      conv unit names; the concat is "classifier.0.concat" and the pooled vector (one pixel per
+                                      image) "classifier.0.convs.4". */
+};
+
 /* Layout of the image handed to nbc_forward. */
 enum {
   NBC_IN_F32_NCHW = 0,  /* float32 [N,3,H,W], already normalised: exactly `batch[0]` of models.py:269 */
@@ -140,6 +152,14 @@ int nbc_num_convs(void);
 int nbc_conv_info(int index, nbc_conv_desc* out);
 int nbc_num_state_keys(void);                               /* 326 */
 int nbc_state_key(int index, const char** name, int64_t shape[4], int32_t* ndim, int32_t* dtype);
+/* The same for architecture `arch` (NBC_ARCH_*); NBC_ERR_INVALID for an unknown one. */
+int nbc_arch_num_convs(int arch);
+int nbc_arch_conv_info(int arch, int index, nbc_conv_desc* out);
+int nbc_arch_num_state_keys(int arch);                      /* 326 / 362 */
+int nbc_arch_state_key(int arch, int index, const char** name, int64_t shape[4], int32_t* ndim, int32_t* dtype);
+/* The architecture whose key set (names, shapes, dtypes) the state_dict matches exactly, or NBC_ERR_KEYS with the message
+ * strict loading into architecture 0 gives. */
+int nbc_arch_of_state_dict(const nbc_tensor* tensors, int n);
 /* Low-resolution logits size for an HxW input (three stride-2 stages). */
 int nbc_lowres_size(int H, int W, int* h, int* w);
 
@@ -160,6 +180,16 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
 /* NBC_PACK_* bits of a packed blob in HOST memory (>= 0), or a negative error.  The bits ride in the blob's trailer, so
  * a rank that received the blob by broadcast reads the same ones (nbc_weights_flags on its context). */
 int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision);
+/* The same three for architecture `arch`.  The blob's trailer records the architecture in a word every blob of architecture
+ * 0 holds as 0, so an FCN blob of nbc_pack_weights_arch(..., 0, ...) is byte for byte the one nbc_pack_weights wrote before
+ * the word had this meaning.  f16x2: the five ASPP branches write one tensor, the concat, and share one power of two (from
+ * the largest of their five BatchNorm estimates); the pooling branch keeps its weights in f32 like classifier.4. */
+size_t nbc_arch_packed_weights_bytes(int precision, int arch);
+int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int arch, void* blob, size_t blob_bytes);
+int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int precision, int arch);
+/* The architecture recorded in a packed blob in HOST memory of exactly nbc_arch_packed_weights_bytes(precision, arch)
+ * bytes, or NBC_ERR_INVALID. */
+int nbc_packed_weights_arch(const void* blob, size_t blob_bytes, int precision);
 
 /* ---- context --------------------------------------------------------------------------- */
 int nbc_create(nbc_ctx** out, int hip_device);
@@ -168,8 +198,13 @@ int nbc_destroy(nbc_ctx* ctx);
  * (e.g. a torch tensor that was the target of an RCCL broadcast).  Must outlive the context
  * or the next attach. */
 int nbc_attach_weights(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int precision);
+/* The same for a blob of architecture `arch`: a blob whose trailer names another architecture is refused
+ * (NBC_ERR_INVALID).  nbc_forward, nbc_reserve, nbc_autotune, the plan tiles, the profiling records, keep mode and the
+ * calibration guard then run that architecture. */
+int nbc_attach_weights_arch(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int precision, int arch);
 /* Convenience: pack on the host, allocate device memory owned by the context, upload. */
 int nbc_load_weights(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision);
+int nbc_load_weights_arch(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision, int arch);
 /* NBC_PACK_* bits of the attached blob (read from its trailer when it was attached: a 1-KiB device-to-host copy), >= 0,
  * or a negative error (no weights attached). */
 int nbc_weights_flags(nbc_ctx* ctx);
@@ -184,7 +219,8 @@ int nbc_activation_exponent(nbc_ctx* ctx, const char* name, int32_t* exponent);
  * predict.py:57); every other rank allocates a blob the context owns, receives into it and attaches
  * it.  The RCCL entry points are looked up in the host process at call time (the library links
  * libamdhip64 only); NBC_ERR_STATE when the process holds no RCCL.  The blob is valid once the stream
- * has been synchronised. */
+ * has been synchronised.  NBC_ARCH_FCN_RESNET50 only: NBC_ERR_STATE on a context that holds another architecture (the
+ * folder drivers broadcast the blob through torch.distributed). */
 int nbc_bcast_weights(nbc_ctx* ctx, void* rccl_comm, int root, int precision, void* hip_stream);
 /* mean/std used for NBC_IN_U8_NHWC input; defaults are models.py:208-209. */
 int nbc_set_normalization(nbc_ctx* ctx, const float mean[3], const float std[3]);
@@ -308,7 +344,8 @@ int nbc_set_keep_activations(nbc_ctx* ctx, int on);
 /* The calibration guard of NBC_PREC_F16X2 (any precision answers): after a forward with keep-activations on, the largest
  * finite |value| of every conv unit's output tensor AS STORED on the device (with the power of two nbc_pack_weights gave it),
  * one float per conv unit in nbc_conv_info order (0 for classifier.4, whose output is the logits); returns their number
- * (nbc_num_convs()) or a negative error.  nbc_pack_weights places a tensor by its BatchNorm's promise; this is what the
+ * (nbc_arch_num_convs() of the attached architecture) or a negative error.  DeepLabV3: the pooling branch's entry is its
+ * pooled vector; the concat holds exactly the five branch tensors, so its peak is the largest of theirs.  nbc_pack_weights places a tensor by its BatchNorm's promise; this is what the
  * data did.  A tensor that peaks below 2^-8 has most of its values under f16x2's 2^-12 floor (absolute error 2^-36), one
  * beyond 2^14 is a factor four from f16's range: a caller that sees either on a frame of its data runs NBC_PREC_FP32
  * (the folder driver checks its first image: neuralbarkcalculator_amd/predict.py).  Synchronises the device. */

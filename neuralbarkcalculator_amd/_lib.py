@@ -18,6 +18,7 @@ PREC_FP32, PREC_BF16, PREC_F16X2 = 0, 1, 2
 IN_F32_NCHW, IN_U8_NHWC = 0, 1
 LABEL_U8, LABEL_I64 = 0, 1
 PACK_ROW_CLAMPED, PACK_SCALE_RANGE = 1, 2      # NBC_PACK_* of include/nbc.h
+ARCH_FCN_RESNET50, ARCH_DEEPLABV3_RESNET50 = 0, 1   # NBC_ARCH_*
 
 
 class NbcTensor(C.Structure):
@@ -47,17 +48,29 @@ SIGNATURES = {
     "nbc_num_state_keys": (C.c_int, []),
     "nbc_state_key": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64 * 4),
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "nbc_arch_num_convs": (C.c_int, [C.c_int]),
+    "nbc_arch_conv_info": (C.c_int, [C.c_int, C.c_int, C.POINTER(NbcConvDesc)]),
+    "nbc_arch_num_state_keys": (C.c_int, [C.c_int]),
+    "nbc_arch_state_key": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64 * 4),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "nbc_arch_of_state_dict": (C.c_int, [C.POINTER(NbcTensor), C.c_int]),
     "nbc_lowres_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nbc_packed_weights_bytes": (C.c_size_t, [C.c_int]),
     "nbc_split_f16x2": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "nbc_pack_weights": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "nbc_packed_weights_flags": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int]),
+    "nbc_arch_packed_weights_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "nbc_pack_weights_arch": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "nbc_packed_weights_flags_arch": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "nbc_packed_weights_arch": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int]),
     "nbc_weights_flags": (C.c_int, [C.c_void_p]),
     "nbc_activation_exponent": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
     "nbc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "nbc_destroy": (C.c_int, [C.c_void_p]),
     "nbc_attach_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     "nbc_load_weights": (C.c_int, [C.c_void_p, C.POINTER(NbcTensor), C.c_int, C.c_int]),
+    "nbc_attach_weights_arch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "nbc_load_weights_arch": (C.c_int, [C.c_void_p, C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_int]),
     "nbc_set_normalization": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nbc_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "nbc_nonfinite_seen": (C.c_int, [C.c_void_p, C.c_int]),

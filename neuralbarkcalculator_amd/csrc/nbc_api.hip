@@ -29,21 +29,23 @@ namespace {
       return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
-enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE };
+enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT };
 
 struct Op {
   OpKind kind;
-  int unit;            // conv unit index (OP_CONV / OP_HEAD1X1), -1 otherwise
+  int unit;            // conv unit index (OP_CONV / OP_HEAD1X1 / OP_ASPP_POOL), -1 otherwise
   int in_buf, out_buf, res_buf;
   int Hi, Wi, Ci, Ho, Wo, Co;
   std::string name;
   double flops, bytes;
   int tile;            // OP_CONV: tile id of the LDS-DMA kernel (default choice or autotuned)
   int rows;            // OP_CONV: conv_rows_kind: 0 generic tiles, 1 / 2 the row-resident 3x3 kernel (kind 1: tiles 18 or 20; kind 2: tile 19)
+  int ws_buf;          // OP_ASPP_POOL: workspace buffer (slice partials, then the per-image means)
+  int cat_in[5];       // OP_CONCAT: the four spatial branches' buffers and the pooled vectors' buffer
 };
 
 struct Plan {
-  int N = 0, H = 0, W = 0, precision = -1;
+  int N = 0, H = 0, W = 0, precision = -1, arch = 0;
   bool keep = false;
   int h = 0, w = 0;                    // low-res logits size
   std::vector<Op> ops;
@@ -55,6 +57,7 @@ struct Plan {
 struct nbc_ctx {
   int device = 0;
   int precision = -1;
+  int arch = kArchFcn;                      // NBC_ARCH_* of the attached blob
   const unsigned char* weights = nullptr;   // device blob
   void* owned_weights = nullptr;
   PackedLayout layout;
@@ -74,6 +77,7 @@ struct nbc_ctx {
   std::vector<std::vector<hipEvent_t>> prof_sets;
   size_t prof_used = 0;
   std::vector<Op> prof_ops;
+  int prof_arch = kArchFcn;                 // architecture of prof_ops
   std::vector<nbc_op_record> records;
   std::map<std::string, int> act_of;        // conv unit name -> op index (keep mode)
   void* scratch256 = nullptr;               // 256 bytes of device scratch (min/max of the preprocessor resize)
@@ -88,11 +92,11 @@ namespace {
 
 constexpr size_t kPlanCacheEntries = 64;
 
-bool same_shape(const Plan& p, int N, int H, int W, int precision, bool keep) {
-  return p.N == N && p.H == H && p.W == W && p.precision == precision && p.keep == keep;
+bool same_shape(const Plan& p, int N, int H, int W, int precision, bool keep, int arch) {
+  return p.N == N && p.H == H && p.W == W && p.precision == precision && p.keep == keep && p.arch == arch;
 }
 bool same_plan(const Plan& p, const nbc_ctx* c, int N, int H, int W) {
-  return same_shape(p, N, H, W, c->precision, c->keep);
+  return same_shape(p, N, H, W, c->precision, c->keep, c->arch);
 }
 
 // Park the current plan (folders of height-trimmed images alternate between a few shapes: each keeps
@@ -101,7 +105,7 @@ void stash_plan(nbc_ctx* c) {
   Plan& cur = c->plan;
   if (cur.N == 0) return;
   for (Plan& p : c->plan_cache)
-    if (same_shape(p, cur.N, cur.H, cur.W, cur.precision, cur.keep)) {
+    if (same_shape(p, cur.N, cur.H, cur.W, cur.precision, cur.keep, cur.arch)) {
       p = cur; cur = Plan(); return;
     }
   if (c->plan_cache.size() >= kPlanCacheEntries) c->plan_cache.erase(c->plan_cache.begin());
@@ -113,9 +117,9 @@ void stash_plan(nbc_ctx* c) {
 // unless `keep` asks for one buffer per op (layer-by-layer parity tests).
 int build_plan(nbc_ctx* c, int N, int H, int W) {
   Plan P;
-  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep;
+  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch;
   const int eb = elem_bytes(c->precision);
-  const auto& units = conv_units();
+  const auto& units = conv_units(c->arch);
   const auto& L = c->layout;
 
   std::vector<bool> in_use;
@@ -201,13 +205,47 @@ int build_plan(nbc_ctx* c, int N, int H, int W) {
   }
   // head
   {
-    int oH, oW;
-    const int t = add_conv((int)ui, cur, curH, curW, curC, -1, &oH, &oW);   // classifier.0
-    release(cur);
+    int oH, oW, t, cls = (int)ui + 1;                                        // classifier.4's unit
+    if (c->arch == kArchDeepLab) {
+      // ASPP: four convolutions and the pooling branch all read layer4's output (`cur`), which stays acquired until the
+      // last of them; the concat then copies the five into one [M][1280] tensor.  Then project, classifier.1.
+      int br[4];
+      for (int b = 0; b < 4; ++b) br[b] = add_conv((int)ui + b, cur, curH, curW, curC, -1, &oH, &oW);
+      const int hw = curH * curW, B = units[ui + 4].cout;
+      const int ws = acquire(((size_t)N * aspp_pool_slices(hw) + N) * curC * sizeof(float));
+      Op po{};
+      po.kind = OP_ASPP_POOL; po.unit = (int)ui + 4; po.in_buf = cur; po.res_buf = -1; po.ws_buf = ws;
+      po.Hi = curH; po.Wi = curW; po.Ci = curC; po.Ho = 1; po.Wo = 1; po.Co = B;
+      po.name = "classifier.0.convs.4";                                      // the pooled vector: one pixel per image
+      po.out_buf = acquire((size_t)N * B * eb);
+      po.flops = 2.0 * N * B * curC + (double)N * hw * curC;
+      po.bytes = (double)N * hw * curC * eb + (double)B * curC * 4 + (double)N * B * eb;
+      P.ops.push_back(po);
+      release(ws);
+      release(cur);
+      Op co{};
+      co.kind = OP_CONCAT; co.unit = -1; co.in_buf = -1; co.res_buf = -1;
+      for (int b = 0; b < 4; ++b) co.cat_in[b] = br[b];
+      co.cat_in[4] = po.out_buf;
+      co.Hi = oH; co.Wi = oW; co.Ci = 5 * B; co.Ho = oH; co.Wo = oW; co.Co = 5 * B;
+      co.name = "classifier.0.concat";
+      co.out_buf = acquire((size_t)N * hw * 5 * B * eb);
+      co.bytes = 2.0 * N * hw * 5 * B * eb;
+      P.ops.push_back(co);
+      for (int b = 0; b < 5; ++b) release(co.cat_in[b]);
+      const int pj = add_conv((int)ui + 5, co.out_buf, oH, oW, 5 * B, -1, &oH, &oW);   // classifier.0.project
+      release(co.out_buf);
+      t = add_conv((int)ui + 6, pj, oH, oW, B, -1, &oH, &oW);                 // classifier.1
+      release(pj);
+      cls = (int)ui + 7;
+    } else {
+      t = add_conv((int)ui, cur, curH, curW, curC, -1, &oH, &oW);            // classifier.0
+      release(cur);
+    }
     Op o{};
-    o.kind = OP_HEAD1X1; o.unit = (int)ui + 1; o.in_buf = t; o.out_buf = -1; o.res_buf = -1;
-    o.Hi = oH; o.Wi = oW; o.Ci = units[ui].cout; o.Ho = oH; o.Wo = oW; o.Co = kNumClasses;
-    o.name = units[ui + 1].name;
+    o.kind = OP_HEAD1X1; o.unit = cls; o.in_buf = t; o.out_buf = -1; o.res_buf = -1;
+    o.Hi = oH; o.Wi = oW; o.Ci = units[cls].cin; o.Ho = oH; o.Wo = oW; o.Co = kNumClasses;
+    o.name = units[cls].name;
     o.flops = 2.0 * N * oH * oW * o.Ci * kNumClasses;
     o.bytes = (double)N * oH * oW * o.Ci * eb + (double)N * oH * oW * kNumClasses * 4;
     P.ops.push_back(o);
@@ -263,7 +301,7 @@ int ensure_buffers(nbc_ctx* c) {
 
 // One convolution launch of the plan (shared by nbc_forward and nbc_autotune).
 int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipError_t* err) {
-  const auto& units = conv_units();
+  const auto& units = conv_units(c->arch);
   const ConvUnit& u = units[o.unit];
   const PackedConv& pc = c->layout.convs[o.unit];
   const int prec = c->precision;
@@ -305,6 +343,8 @@ const char* kernel_name(OpKind k) {
     case OP_CONV: return "conv_dma";
     case OP_MAXPOOL: return "maxpool";
     case OP_HEAD1X1: return "head1x1";
+    case OP_ASPP_POOL: return "aspp_pool";
+    case OP_CONCAT: return "concat";
     default: return "upsample_argmax";
   }
 }
@@ -345,10 +385,11 @@ int nbc_destroy(nbc_ctx* c) {
   return NBC_OK;
 }
 
-int nbc_attach_weights(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision) {
+int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision, int arch) {
   if (!c || !dev_blob) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: null argument");
   if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown precision");
-  PackedLayout L = packed_layout(precision);
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown architecture");
+  PackedLayout L = packed_layout(precision, arch);
   if (bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: blob smaller than the packed layout");
   if (reinterpret_cast<uintptr_t>(dev_blob) % 256 != 0)
     return set_error(NBC_ERR_INVALID, "nbc_attach_weights: blob must be 256-byte aligned");
@@ -356,25 +397,31 @@ int nbc_attach_weights(nbc_ctx* c, const void* dev_blob, size_t bytes, int preci
   int32_t meta[kMetaWords];
   NBC_HIP(hipSetDevice(c->device));
   NBC_HIP(hipMemcpy(meta, static_cast<const unsigned char*>(dev_blob) + L.meta_off, sizeof(meta), hipMemcpyDeviceToHost));
-  const int nunits = (int)conv_units().size();
-  if (meta[0] != kMetaMagic || meta[2] != nunits)
-    return set_error(NBC_ERR_INVALID, "nbc_attach_weights: not a blob of this library's nbc_pack_weights (trailer mismatch)");
+  const int nunits = (int)conv_units(arch).size();
+  if (meta[0] != kMetaMagic || meta[2] != nunits || meta[kMetaArch] != arch)
+    return set_error(NBC_ERR_INVALID, "nbc_attach_weights: not a blob of this library's nbc_pack_weights for this architecture "
+                                      "(trailer mismatch)");
   if (c->owned_weights && c->owned_weights != dev_blob) { (void)hipFree(c->owned_weights); c->owned_weights = nullptr; }
   c->pack_flags = meta[1];
   c->act_exp.assign(meta + kMetaExpBase, meta + kMetaExpBase + nunits);
   c->weights = static_cast<const unsigned char*>(dev_blob);
   c->layout = L;
-  if (c->precision != precision) stash_plan(c);      // element size changed: another plan
+  if (c->precision != precision || c->arch != arch) stash_plan(c);      // element size or network changed: another plan
   c->precision = precision;
+  c->arch = arch;
   return NBC_OK;
 }
 
-int nbc_load_weights(nbc_ctx* c, const nbc_tensor* tensors, int n, int precision) {
+int nbc_attach_weights(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision) {
+  return nbc_attach_weights_arch(c, dev_blob, bytes, precision, kArchFcn);
+}
+
+int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int precision, int arch) {
   if (!c) return set_error(NBC_ERR_INVALID, "nbc_load_weights: null context");
-  const size_t bytes = nbc_packed_weights_bytes(precision);
-  if (bytes == 0) return set_error(NBC_ERR_INVALID, "nbc_load_weights: unknown precision");
+  const size_t bytes = nbc_arch_packed_weights_bytes(precision, arch);
+  if (bytes == 0) return set_error(NBC_ERR_INVALID, "nbc_load_weights: unknown precision or architecture");
   std::vector<unsigned char> host(bytes);
-  int rc = nbc_pack_weights(tensors, n, precision, host.data(), bytes);
+  int rc = nbc_pack_weights_arch(tensors, n, precision, arch, host.data(), bytes);
   if (rc != NBC_OK) return rc;
   NBC_HIP(hipSetDevice(c->device));
   void* dev = nullptr;
@@ -383,10 +430,14 @@ int nbc_load_weights(nbc_ctx* c, const nbc_tensor* tensors, int n, int precision
   if (e != hipSuccess) { (void)hipFree(dev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(weights): ") + hipGetErrorString(e)); }
   if (c->owned_weights) (void)hipFree(c->owned_weights);
   c->owned_weights = nullptr;
-  rc = nbc_attach_weights(c, dev, bytes, precision);
+  rc = nbc_attach_weights_arch(c, dev, bytes, precision, arch);
   if (rc != NBC_OK) { (void)hipFree(dev); return rc; }
   c->owned_weights = dev;
   return NBC_OK;
+}
+
+int nbc_load_weights(nbc_ctx* c, const nbc_tensor* tensors, int n, int precision) {
+  return nbc_load_weights_arch(c, tensors, n, precision, kArchFcn);
 }
 
 // RCCL is resolved at call time from the host process (the library itself links libamdhip64 only):
@@ -408,6 +459,9 @@ void* rccl_symbol(const char* name) {
 
 int nbc_bcast_weights(nbc_ctx* c, void* rccl_comm, int root, int precision, void* hip_stream) {
   if (!c || !rccl_comm) return set_error(NBC_ERR_INVALID, "nbc_bcast_weights: null argument");
+  if (c->arch != kArchFcn)
+    return set_error(NBC_ERR_STATE, "nbc_bcast_weights: FCN-ResNet-50 only; broadcast the blob of another architecture yourself "
+                                    "and attach it with nbc_attach_weights_arch");
   const size_t bytes = nbc_packed_weights_bytes(precision);
   if (bytes == 0) return set_error(NBC_ERR_INVALID, "nbc_bcast_weights: unknown precision");
   auto bcast = reinterpret_cast<nccl_bcast_fn>(rccl_symbol("ncclBroadcast"));
@@ -451,9 +505,13 @@ int nbc_weights_flags(nbc_ctx* c) {
 namespace {
 // power of two the output of plan op `name` is stored with: a conv unit's own, the max-pool keeps the stem's, the image has none
 bool stored_exponent(const nbc_ctx* c, const std::string& name, int* e) {
-  const auto& units = conv_units();
+  const auto& units = conv_units(c->arch);
   if (name == "ingest") { *e = 0; return true; }
   if (name == "backbone.maxpool") { *e = c->act_exp.empty() ? 0 : c->act_exp[0]; return true; }
+  if (c->arch == kArchDeepLab && (name == "classifier.0.concat" || name == "classifier.0.convs.4")) {
+    // the concat and the pooled vector: the power the five ASPP branches share (that of convs.0)
+    return stored_exponent(c, "classifier.0.convs.0.0", e);
+  }
   for (size_t u = 0; u < units.size(); ++u)
     if (units[u].name == name) { *e = u < c->act_exp.size() ? c->act_exp[u] : 0; return true; }
   return false;
@@ -573,6 +631,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
       evs->push_back(ev);
     }
     c->prof_ops = P.ops;
+    c->prof_arch = P.arch;
   }
   float* lowres = logits_lowres_dev ? logits_lowres_dev : c->lowres;
 
@@ -601,12 +660,32 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         break;
       case OP_HEAD1X1: {
         const PackedConv& pc = c->layout.convs[o.unit];
-        if (o.Ci != 512) return set_error(NBC_ERR_STATE, "classifier.4 expects 512 input channels");
+        if (o.Ci != 512 && o.Ci != 256) return set_error(NBC_ERR_STATE, "classifier.4 expects 512 or 256 input channels");
         // also clears this launch's share of the counters (3 per image) when the batch has at most 256 of them
         unsigned long long* cz = counts_dev && 3 * N <= 256 ? reinterpret_cast<unsigned long long*>(counts_dev) : nullptr;
-        e = launch_head1x1(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
-                           reinterpret_cast<const float*>(c->weights + pc.shift_off),
-                           lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+        if (o.Ci == 512)
+          e = launch_head1x1(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
+                             reinterpret_cast<const float*>(c->weights + pc.shift_off),
+                             lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+        else
+          e = launch_head1x1_c256(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
+                                  reinterpret_cast<const float*>(c->weights + pc.shift_off),
+                                  lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+        break;
+      }
+      case OP_ASPP_POOL: {
+        const PackedConv& pc = c->layout.convs[o.unit];
+        float* partial = static_cast<float*>(c->bufs[o.ws_buf]);
+        float* mean = partial + (size_t)N * aspp_pool_slices(o.Hi * o.Wi) * o.Ci;
+        e = launch_aspp_pool(c->bufs[o.in_buf], N, o.Hi * o.Wi, o.Ci, reinterpret_cast<const float*>(c->weights + pc.w_off),
+                             reinterpret_cast<const float*>(c->weights + pc.scale_off),
+                             reinterpret_cast<const float*>(c->weights + pc.shift_off), o.Co, partial, mean, c->bufs[o.out_buf],
+                             prec, s);
+        break;
+      }
+      case OP_CONCAT: {
+        const void* br[4] = {c->bufs[o.cat_in[0]], c->bufs[o.cat_in[1]], c->bufs[o.cat_in[2]], c->bufs[o.cat_in[3]]};
+        e = launch_aspp_concat(br, c->bufs[o.cat_in[4]], c->bufs[o.out_buf], N, o.Ho * o.Wo, prec, s);
         break;
       }
       case OP_UPSAMPLE:
@@ -633,7 +712,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
 // Average the event sets recorded since the last call (synchronises on the last one), then reset.
 static int collect_profile(nbc_ctx* c) {
   if (c->prof_used == 0) return NBC_OK;
-  const auto& units = conv_units();
+  const auto& units = conv_units(c->prof_arch);
   const size_t nops = c->prof_ops.size();
   NBC_HIP(hipEventSynchronize(c->prof_sets[c->prof_used - 1][nops]));
   c->records.assign(nops, nbc_op_record{});
@@ -651,7 +730,7 @@ static int collect_profile(nbc_ctx* c) {
     std::snprintf(r.kernel, sizeof(r.kernel), "%s", kernel_name(o.kind));
     r.ms = (float)(sum[i] / (double)c->prof_used);
     r.calls = (int32_t)c->prof_used;
-    r.launches = 1;
+    r.launches = o.kind == OP_ASPP_POOL ? 3 : 1;              // partial sums, their sum, the 1x1 conv
     r.flops = o.flops;
     r.bytes = o.bytes;
     r.kh = r.kw = (o.kind == OP_CONV || o.kind == OP_HEAD1X1) ? units[o.unit].k : 0;
@@ -820,8 +899,8 @@ int nbc_get_op_record(nbc_ctx* c, int index, nbc_op_record* out) {
 int nbc_activation_peaks(nbc_ctx* c, float* peaks_host, int capacity) {
   if (!c || !peaks_host) return set_error(NBC_ERR_INVALID, "nbc_activation_peaks: null argument");
   if (!c->plan.keep) return set_error(NBC_ERR_STATE, "nbc_activation_peaks: keep-activations is off (nbc_set_keep_activations, then a forward)");
-  const int nunits = (int)conv_units().size();
-  if (capacity < nunits) return set_error(NBC_ERR_INVALID, "nbc_activation_peaks: need room for nbc_num_convs() values");
+  const int nunits = (int)conv_units(c->plan.arch).size();
+  if (capacity < nunits) return set_error(NBC_ERR_INVALID, "nbc_activation_peaks: need room for nbc_arch_num_convs() values");
   NBC_HIP(hipSetDevice(c->device));
   unsigned* dev = nullptr;
   NBC_HIP(hipMalloc((void**)&dev, sizeof(unsigned) * nunits));
@@ -829,7 +908,7 @@ int nbc_activation_peaks(nbc_ctx* c, float* peaks_host, int capacity) {
   const int N = c->plan.N;
   for (const Op& o : c->plan.ops) {
     if (e != hipSuccess) break;
-    if (o.kind != OP_CONV || o.out_buf < 0) continue;
+    if ((o.kind != OP_CONV && o.kind != OP_ASPP_POOL) || o.out_buf < 0) continue;   // the pooling branch: its pooled vector
     e = launch_absmax(c->bufs[o.out_buf], (size_t)N * o.Ho * o.Wo * o.Co, o.Co, c->precision, dev + o.unit, nullptr);
   }
   std::vector<unsigned> bits(nunits, 0u);

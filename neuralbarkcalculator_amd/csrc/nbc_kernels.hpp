@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip and small_zones.hip).
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip and aspp.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +62,18 @@ hipError_t launch_maxpool3x3s2(const void* x, void* y, int N, int Hi, int Wi, in
 // nonfinite (nullable): one device word that gets bit 0 set when a logit is NaN or infinite.
 hipError_t launch_head1x1(const void* x, const float* w, const float* bias, float* y, int N, int hw,
                           int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
+// classifier.4 of DeepLabHead: the same with 256 input channels
+hipError_t launch_head1x1_c256(const void* x, const float* w, const float* bias, float* y, int N, int hw,
+                               int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
+// ASPP pooling branch (aspp.hip), per image: mean over hw pixels of x [N][hw][cin = 2048] (stored elements), the 1x1 conv
+// with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout] elements.  Workspaces: partial
+// N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.
+int aspp_pool_slices(int hw);
+hipError_t launch_aspp_pool(const void* x, int N, int hw, int cin, const float* w, const float* scale, const float* shift, int cout,
+                            float* partial, float* mean, void* y, int precision, hipStream_t s);
+// ASPP concat: y [N*hw][1280] elements = the four branches [N*hw][256] then the image's pooled vector [N][256], per pixel.
+hipError_t launch_aspp_concat(const void* const branch[4], const void* pooled, void* y, int N, int hw, int precision,
+                              hipStream_t s);
 // Bicubic (A=-0.75, align_corners=False) upsample of f32 NCHW [N,3,h,w] to HxW, fused with the
 // per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,

@@ -17,7 +17,7 @@
 
 namespace nbc {
 
-static std::vector<ConvUnit> build_units() {
+static std::vector<ConvUnit> build_units(int arch) {
   std::vector<ConvUnit> u;
   u.push_back({"backbone.conv1", "backbone.bn1", 3, 64, 7, 2, 3, 1, true, false, false, 0});
   int inplanes = 64, dilation = 1;
@@ -42,20 +42,37 @@ static std::vector<ConvUnit> build_units() {
       inplanes = planes * 4;
     }
   }
+  if (arch == kArchDeepLab) {
+    // DeepLabHead(2048, 3) of torchvision 0.3 (models.py:46-57): ASPP(2048, [12, 24, 36]) -- four spatial branches and the
+    // pooling branch, each 256 channels with BatchNorm + ReLU, concatenated in this order and projected 1280 -> 256 --, then
+    // a 3x3 conv 256 -> 256 with BatchNorm + ReLU and the 1x1 classifier.  No conv but classifier.4 has a bias.
+    const int B = kAsppBranchCh;
+    u.push_back({"classifier.0.convs.0.0", "classifier.0.convs.0.1", 2048, B, 1, 1, 0, 1, true, false, false, 0});
+    const int rates[3] = {12, 24, 36};
+    for (int i = 0; i < 3; ++i) {
+      const std::string p = "classifier.0.convs." + std::to_string(i + 1);
+      u.push_back({p + ".0", p + ".1", 2048, B, 3, 1, rates[i], rates[i], true, false, false, 0});
+    }
+    u.push_back({"classifier.0.convs.4.1", "classifier.0.convs.4.2", 2048, B, 1, 1, 0, 1, true, false, false, 0, true});
+    u.push_back({"classifier.0.project.0", "classifier.0.project.1", 5 * B, B, 1, 1, 0, 1, true, false, false, 0});
+    u.push_back({"classifier.1", "classifier.2", B, B, 3, 1, 1, 1, true, false, false, 0});
+    u.push_back({"classifier.4", "", B, kNumClasses, 1, 1, 0, 1, false, true, false, 0});
+    return u;
+  }
   u.push_back({"classifier.0", "classifier.1", 2048, 512, 3, 1, 1, 1, true, false, false, 0});
   u.push_back({"classifier.4", "", 512, kNumClasses, 1, 1, 0, 1, false, true, false, 0});
   return u;
 }
 
-const std::vector<ConvUnit>& conv_units() {
-  static const std::vector<ConvUnit> u = build_units();
-  return u;
+const std::vector<ConvUnit>& conv_units(int arch) {
+  static const std::vector<ConvUnit> u[kNumArchs] = {build_units(kArchFcn), build_units(kArchDeepLab)};
+  return u[arch == kArchDeepLab ? kArchDeepLab : kArchFcn];
 }
 
-static std::vector<StateKey> build_keys() {
+static std::vector<StateKey> build_keys(int arch) {
   // nn.Module.state_dict() order: inside a Bottleneck conv1,bn1,conv2,bn2,conv3,bn3,downsample.
   std::vector<StateKey> keys;
-  const auto& units = conv_units();
+  const auto& units = conv_units(arch);
   std::vector<const ConvUnit*> ordered;
   for (size_t i = 0; i < units.size(); ++i) {
     const ConvUnit& c = units[i];
@@ -91,22 +108,32 @@ static std::vector<StateKey> build_keys() {
   return keys;
 }
 
-const std::vector<StateKey>& state_keys() {
-  static const std::vector<StateKey> k = build_keys();
-  return k;
+const std::vector<StateKey>& state_keys(int arch) {
+  static const std::vector<StateKey> k[kNumArchs] = {build_keys(kArchFcn), build_keys(kArchDeepLab)};
+  return k[arch == kArchDeepLab ? kArchDeepLab : kArchFcn];
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-PackedLayout packed_layout(int precision) {
+PackedLayout packed_layout(int precision, int arch) {
   PackedLayout L;
   const int eb = elem_bytes(precision);
   size_t off = 0;
-  for (const ConvUnit& c : conv_units()) {
+  for (const ConvUnit& c : conv_units(arch)) {
     PackedConv p{};
     p.stem = (c.cin == 3);
     p.head = c.bn.empty();
-    if (p.head) {                      // f32 [3][512] + bias
+    p.pooled = c.pooled;
+    if (p.pooled) {                    // f32 [cout][cin], f32 scale and shift (the pooled vector is one pixel per image)
+      p.cin_pad = c.cin;
+      p.ksteps = 0;
+      p.w_off = off;
+      off = align_up(off + (size_t)c.cout * c.cin * 4, 256);
+      p.scale_off = off;
+      off = align_up(off + (size_t)c.cout * 4, 256);
+      p.shift_off = off;
+      off = align_up(off + (size_t)c.cout * 4, 256);
+    } else if (p.head) {               // f32 [3][cin] + bias
       p.cin_pad = c.cin;
       p.ksteps = 0;
       p.w_off = off;
@@ -291,9 +318,9 @@ static float bn_estimate(const float* gamma, const float* beta, const float* var
   return m;
 }
 
-static void activation_exponents(const std::vector<const float*>& gamma, const std::vector<const float*>& beta,
+static void activation_exponents(int arch, const std::vector<const float*>& gamma, const std::vector<const float*>& beta,
                           const std::vector<const float*>& var, std::vector<int>& out_exp, std::vector<int>& in_exp) {
-  const auto& units = conv_units();
+  const auto& units = conv_units(arch);
   const size_t n = units.size();
   out_exp.assign(n, 0);
   in_exp.assign(n, 0);
@@ -330,6 +357,21 @@ static void activation_exponents(const std::vector<const float*>& gamma, const s
     cur = a_stream;
     ui = end;
   }
+  if (arch == kArchDeepLab) {
+    // ASPP: the five branches write ONE tensor (the concat), so they share one power, from the largest of their five
+    // estimates; the pooling branch reads layer4's output like the four convolutions (its f32 scale takes the 2^-a)
+    float cat = 0.f;
+    for (size_t b = 0; b < 5; ++b) cat = std::max(cat, est(ui + b));
+    const int a_cat = tensor_exponent(cat);
+    for (size_t b = 0; b < 5; ++b) { in_exp[ui + b] = cur; out_exp[ui + b] = a_cat; }
+    in_exp[ui + 5] = a_cat;                           // classifier.0.project
+    out_exp[ui + 5] = tensor_exponent(est(ui + 5));
+    in_exp[ui + 6] = out_exp[ui + 5];                 // classifier.1
+    out_exp[ui + 6] = tensor_exponent(est(ui + 6));
+    in_exp[ui + 7] = out_exp[ui + 6];                 // classifier.4: f32 weights, no BatchNorm
+    out_exp[ui + 7] = 0;
+    return;
+  }
   in_exp[ui] = cur;                                   // classifier.0
   out_exp[ui] = tensor_exponent(est(ui));
   in_exp[ui + 1] = out_exp[ui];                       // classifier.4: f32 weights, no BatchNorm
@@ -361,10 +403,15 @@ extern "C" {
 const char* nbc_last_error(void) { return g_last_error.c_str(); }
 const char* nbc_version(void) { return "nbc-hip 0.1 (gfx950)"; }
 
-int nbc_num_convs(void) { return (int)conv_units().size(); }
+int nbc_arch_num_convs(int arch) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_arch_num_convs: unknown architecture");
+  return (int)conv_units(arch).size();
+}
+int nbc_num_convs(void) { return nbc_arch_num_convs(kArchFcn); }
 
-int nbc_conv_info(int index, nbc_conv_desc* out) {
-  const auto& u = conv_units();
+int nbc_arch_conv_info(int arch, int index, nbc_conv_desc* out) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_conv_info: unknown architecture");
+  const auto& u = conv_units(arch);
   if (!out || index < 0 || index >= (int)u.size()) return set_error(NBC_ERR_INVALID, "nbc_conv_info: bad index");
   const ConvUnit& c = u[index];
   std::memset(out, 0, sizeof(*out));
@@ -375,17 +422,26 @@ int nbc_conv_info(int index, nbc_conv_desc* out) {
   out->relu = c.relu; out->bias = c.bias; out->residual = c.residual;
   return NBC_OK;
 }
+int nbc_conv_info(int index, nbc_conv_desc* out) { return nbc_arch_conv_info(kArchFcn, index, out); }
 
-int nbc_num_state_keys(void) { return (int)state_keys().size(); }
+int nbc_arch_num_state_keys(int arch) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_arch_num_state_keys: unknown architecture");
+  return (int)state_keys(arch).size();
+}
+int nbc_num_state_keys(void) { return nbc_arch_num_state_keys(kArchFcn); }
 
-int nbc_state_key(int index, const char** name, int64_t shape[4], int32_t* ndim, int32_t* dtype) {
-  const auto& k = state_keys();
+int nbc_arch_state_key(int arch, int index, const char** name, int64_t shape[4], int32_t* ndim, int32_t* dtype) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_state_key: unknown architecture");
+  const auto& k = state_keys(arch);
   if (index < 0 || index >= (int)k.size()) return set_error(NBC_ERR_INVALID, "nbc_state_key: bad index");
   if (name) *name = k[index].name.c_str();
   if (shape) for (int i = 0; i < 4; ++i) shape[i] = k[index].shape[i];
   if (ndim) *ndim = k[index].ndim;
   if (dtype) *dtype = k[index].dtype;
   return NBC_OK;
+}
+int nbc_state_key(int index, const char** name, int64_t shape[4], int32_t* ndim, int32_t* dtype) {
+  return nbc_arch_state_key(kArchFcn, index, name, shape, ndim, dtype);
 }
 
 int nbc_lowres_size(int H, int W, int* h, int* w) {
@@ -402,28 +458,32 @@ int nbc_split_f16x2(const float* x, size_t n, uint16_t* h0, uint16_t* h1) {
   return NBC_OK;
 }
 
-size_t nbc_packed_weights_bytes(int precision) {
-  if (!known_precision(precision)) return 0;
-  return packed_layout(precision).total_bytes;
+size_t nbc_arch_packed_weights_bytes(int precision, int arch) {
+  if (!known_precision(precision) || !known_arch(arch)) return 0;
+  return packed_layout(precision, arch).total_bytes;
 }
+size_t nbc_packed_weights_bytes(int precision) { return nbc_arch_packed_weights_bytes(precision, kArchFcn); }
 
-int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob, size_t blob_bytes) {
-  if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: unknown precision");
-  if (!tensors || n < 0 || !blob) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: null argument");
-  const PackedLayout L = packed_layout(precision);
-  if (blob_bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: blob too small");
+}  // extern "C"
 
-  // --- strict key / shape check, in the manner of nn.Module.load_state_dict (models.py:222)
+namespace nbc {
+
+const char* arch_name(int arch) { return arch == kArchDeepLab ? "deeplabv3_resnet50" : "fcn_resnet50"; }
+
+// The strict key / shape check of nn.Module.load_state_dict (models.py:222) against architecture `arch`: NBC_OK and the
+// tensors by name, or NBC_ERR_KEYS with the missing / unexpected / mis-shaped entries (NBC_ERR_INVALID for a nameless one).
+static int check_state_dict(const nbc_tensor* tensors, int n, int arch, std::map<std::string, const nbc_tensor*>* given_out,
+                            std::string* msg_out) {
   std::map<std::string, const nbc_tensor*> given;
   std::string unexpected, missing, badshape;
   std::set<std::string> expected;
-  for (const StateKey& k : state_keys()) expected.insert(k.name);
+  for (const StateKey& k : state_keys(arch)) expected.insert(k.name);
   for (int i = 0; i < n; ++i) {
-    if (!tensors[i].name) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: tensor without a name");
+    if (!tensors[i].name) { *msg_out = "tensor without a name"; return NBC_ERR_INVALID; }
     if (!expected.count(tensors[i].name)) unexpected += std::string(" \"") + tensors[i].name + "\"";
     given[tensors[i].name] = &tensors[i];
   }
-  for (const StateKey& k : state_keys()) {
+  for (const StateKey& k : state_keys(arch)) {
     auto it = given.find(k.name);
     if (it == given.end()) { missing += " \"" + k.name + "\""; continue; }
     const nbc_tensor* t = it->second;
@@ -432,17 +492,39 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
     if (!ok) badshape += " \"" + k.name + "\"";
   }
   if (!missing.empty() || !unexpected.empty() || !badshape.empty()) {
-    std::string msg = "Error(s) in loading state_dict for fcn_resnet50:";
+    std::string msg = std::string("Error(s) in loading state_dict for ") + arch_name(arch) + ":";
     if (!missing.empty()) msg += " Missing key(s) in state_dict:" + missing + ".";
     if (!unexpected.empty()) msg += " Unexpected key(s) in state_dict:" + unexpected + ".";
     if (!badshape.empty()) msg += " size or dtype mismatch for:" + badshape + ".";
-    return set_error(NBC_ERR_KEYS, msg);
+    *msg_out = msg;
+    return NBC_ERR_KEYS;
   }
+  if (given_out) *given_out = std::move(given);
+  return NBC_OK;
+}
+
+}  // namespace nbc
+
+extern "C" {
+
+int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int arch, void* blob, size_t blob_bytes) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: unknown architecture");
+  if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: unknown precision");
+  if (!tensors || n < 0 || !blob) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: null argument");
+  const PackedLayout L = packed_layout(precision, arch);
+  if (blob_bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: blob too small");
+
+  // --- strict key / shape check, in the manner of nn.Module.load_state_dict (models.py:222)
+  std::map<std::string, const nbc_tensor*> given;
+  std::string msg;
+  const int krc = check_state_dict(tensors, n, arch, &given, &msg);
+  if (krc == NBC_ERR_INVALID) return set_error(krc, "nbc_pack_weights: " + msg);
+  if (krc != NBC_OK) return set_error(krc, msg);
 
   std::memset(blob, 0, L.total_bytes);
   unsigned char* base = static_cast<unsigned char*>(blob);
   const int eb = elem_bytes(precision);
-  const auto& units = conv_units();
+  const auto& units = conv_units(arch);
   int flags = 0;
   std::vector<int> out_exp(units.size(), 0), in_exp(units.size(), 0);
   if (precision == NBC_PREC_F16X2) {
@@ -454,7 +536,7 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
       bet[ui] = static_cast<const float*>(given[c.bn + ".bias"]->data);
       var[ui] = static_cast<const float*>(given[c.bn + ".running_var"]->data);
     }
-    activation_exponents(gam, bet, var, out_exp, in_exp);
+    activation_exponents(arch, gam, bet, var, out_exp, in_exp);
   }
   for (size_t ui = 0; ui < units.size(); ++ui) {
     const ConvUnit& c = units[ui];
@@ -467,7 +549,9 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
       continue;
     }
     const size_t row_bytes = (size_t)p.ksteps * kKStepBytes;
-    for (int o = 0; o < c.cout; ++o) {
+    if (p.pooled)                                                       // f32 [cout][cin] as the checkpoint holds it; the
+      std::memcpy(base + p.w_off, w, (size_t)c.cout * c.cin * 4);      // powers of two go into the f32 scale below
+    for (int o = 0; !p.pooled && o < c.cout; ++o) {
       unsigned char* row = base + p.w_off + (size_t)o * row_bytes;
       for (int kh = 0; kh < c.k; ++kh)
         for (int kw = 0; kw < c.k; ++kw)
@@ -487,8 +571,8 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
     // the activation's pieces, X1 carrying 2^11), and the channel's f32 BatchNorm scale takes the 2^-k below -- exact:
     // the epilogue's fma(acc, scale, shift) sees 2^k acc * 2^-k scale.  What remains is relative to the row: a weight
     // below 2^-15 of its row's largest loses low bits (an absolute error of 2^-39 of that largest weight).
-    std::vector<int> row_exp(precision == NBC_PREC_F16X2 ? c.cout : 0, 0);
-    if (precision == NBC_PREC_F16X2) {
+    std::vector<int> row_exp(precision == NBC_PREC_F16X2 && !p.pooled ? c.cout : 0, 0);
+    if (precision == NBC_PREC_F16X2 && !p.pooled) {
       const size_t row_floats = row_bytes / 4;
       for (int o = 0; o < c.cout; ++o) {
         float* row = reinterpret_cast<float*>(base + p.w_off + (size_t)o * row_bytes);
@@ -523,8 +607,38 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
   meta[0] = kMetaMagic;
   meta[1] = flags;
   meta[2] = (int32_t)units.size();
+  meta[kMetaArch] = arch;                                               // 0 for FCN: what the word always held
   for (size_t ui = 0; ui < units.size(); ++ui) meta[kMetaExpBase + ui] = out_exp[ui];
   return NBC_OK;
+}
+
+int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob, size_t blob_bytes) {
+  return nbc_pack_weights_arch(tensors, n, precision, kArchFcn, blob, blob_bytes);
+}
+
+int nbc_arch_of_state_dict(const nbc_tensor* tensors, int n) {
+  if (!tensors || n < 0) return set_error(NBC_ERR_INVALID, "nbc_arch_of_state_dict: null argument");
+  std::string msg;
+  for (int arch = 0; arch < kNumArchs; ++arch) {
+    const int rc = check_state_dict(tensors, n, arch, nullptr, &msg);
+    if (rc == NBC_OK) return arch;
+    if (rc == NBC_ERR_INVALID) return set_error(rc, "nbc_arch_of_state_dict: " + msg);
+  }
+  // no architecture matches: the message strict loading into the default one (FCN) gives
+  (void)check_state_dict(tensors, n, kArchFcn, nullptr, &msg);
+  return set_error(NBC_ERR_KEYS, msg);
+}
+
+int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int precision, int arch) {
+  if (!known_precision(precision) || !known_arch(arch) || !blob)
+    return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: bad argument");
+  const PackedLayout L = packed_layout(precision, arch);
+  if (blob_bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: blob too small");
+  const int32_t* meta = reinterpret_cast<const int32_t*>(static_cast<const unsigned char*>(blob) + L.meta_off);
+  if (meta[0] != kMetaMagic) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: not a blob of nbc_pack_weights (this version)");
+  if (meta[kMetaArch] != arch || meta[2] != (int32_t)conv_units(arch).size())
+    return set_error(NBC_ERR_INVALID, std::string("nbc_packed_weights_flags: not a blob of ") + arch_name(arch));
+  return meta[1];
 }
 
 int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision) {
@@ -534,6 +648,17 @@ int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision)
   const int32_t* meta = reinterpret_cast<const int32_t*>(static_cast<const unsigned char*>(blob) + L.meta_off);
   if (meta[0] != kMetaMagic) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: not a blob of nbc_pack_weights (this version)");
   return meta[1];
+}
+
+int nbc_packed_weights_arch(const void* blob, size_t blob_bytes, int precision) {
+  if (!known_precision(precision) || !blob) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_arch: bad argument");
+  for (int arch = 0; arch < kNumArchs; ++arch) {
+    const PackedLayout L = packed_layout(precision, arch);
+    if (blob_bytes != L.total_bytes) continue;
+    const int32_t* meta = reinterpret_cast<const int32_t*>(static_cast<const unsigned char*>(blob) + L.meta_off);
+    if (meta[0] == kMetaMagic && meta[kMetaArch] == arch && meta[2] == (int32_t)conv_units(arch).size()) return arch;
+  }
+  return set_error(NBC_ERR_INVALID, "nbc_packed_weights_arch: not a blob of nbc_pack_weights of this precision");
 }
 
 }  // extern "C"

@@ -143,48 +143,51 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x
   static_cast<uint4*>(y)[(((size_t)img * Ho + oy) * Wo + ox) * chunks + ch] = o;
 }
 
-// classifier.4 (models.py:121): 1x1 conv 512 -> 3 with bias.  One wave per pixel: lane l owns
-// channels 8l..8l+7 (an f32 fma chain in channel order), then a 64-lane xor-tree.
-template <int PREC>
-__global__ __launch_bounds__(256) void head1x1_kernel(const void* __restrict__ x,
-                                                      const float* __restrict__ w,
-                                                      const float* __restrict__ bias,
-                                                      float* __restrict__ y, int M, int hw,
-                                                      unsigned long long* __restrict__ counts_zero, int ncounts,
-                                                      unsigned* __restrict__ nonfinite) {
-  constexpr int CIN = 512;
-  constexpr int PIX_PER_WAVE = 8;
+// classifier.4 (models.py:121): 1x1 conv CIN -> 3 with bias.  CIN = 512 (FCNHead): one wave per pixel, lane l owns
+// channels 8l..8l+7 (an f32 fma chain in channel order), then a 64-lane xor-tree.  CIN = 256 (DeepLabHead): the same
+// with a half-wave per pixel, two pixels per wave-wide load, a 32-lane tree.
+template <int PREC, int CIN>
+__device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
+                                             const float* __restrict__ w,
+                                             const float* __restrict__ bias,
+                                             float* __restrict__ y, int M, int hw,
+                                             unsigned long long* __restrict__ counts_zero, int ncounts,
+                                             unsigned* __restrict__ nonfinite) {
+  constexpr int LPP = CIN / 8;                            // lanes per pixel: 64 or 32
+  constexpr int PPL = 64 / LPP;                           // pixels per wave-wide load: 1 or 2
+  constexpr int PIX_PER_WAVE = 8 * PPL;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
+  const int cl = lane % LPP, sub = lane / LPP;            // CIN = 512: cl = lane, sub = 0
   float wr[3][8];
 #pragma unroll
   for (int c = 0; c < 3; ++c)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) wr[c][e] = w[c * CIN + lane * 8 + e];
+    for (int e = 0; e < 8; ++e) wr[c][e] = w[c * CIN + cl * 8 + e];
   const float b0 = bias[0], b1 = bias[1], b2 = bias[2];
   const int first = (blockIdx.x * 4 + wave) * PIX_PER_WAVE;
   if (counts_zero && blockIdx.x == 0 && threadIdx.x < ncounts) counts_zero[threadIdx.x] = 0ull;   // for the next launch
-  // the wave's 8 pixel rows are requested together (one memory round trip), then reduced one by one
+  // the wave's 8 pixel rows (loads) are requested together (one memory round trip), then reduced one by one
   constexpr int VPP = PREC == 1 ? 1 : 2;                  // 16-byte loads per lane and pixel
-  uint4 raw[PIX_PER_WAVE][VPP];
+  uint4 raw[8][VPP];
 #pragma unroll
-  for (int q = 0; q < PIX_PER_WAVE; ++q) {
-    const int m = min(first + q, M - 1);
+  for (int q = 0; q < 8; ++q) {
+    const int m = min(first + q * PPL + sub, M - 1);
     if constexpr (PREC == 2) {      // channels 8l .. 8l+7: h0 chunk l % 4 of group l / 4, and its h1 chunk 64 bytes on
       const uint4* xp = reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(x) + (size_t)m * CIN * 4 +
-                                                       (lane >> 2) * 128 + (lane & 3) * 16);
+                                                       (cl >> 2) * 128 + (cl & 3) * 16);
       raw[q][0] = xp[0];
       raw[q][VPP - 1] = xp[4];
     } else {
       const uint4* xp = reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(x) +
-                                                       ((size_t)m * CIN + lane * 8) * (PREC == 0 ? 4 : 2));
+                                                       ((size_t)m * CIN + cl * 8) * (PREC == 0 ? 4 : 2));
 #pragma unroll
       for (int k = 0; k < VPP; ++k) raw[q][k] = xp[k];
     }
   }
 #pragma unroll
-  for (int q = 0; q < PIX_PER_WAVE; ++q) {
-    const int m = first + q;
+  for (int q = 0; q < 8; ++q) {
+    const int m = first + q * PPL + sub;
     float f[8];
     if constexpr (PREC == 2) {
       join16x8(raw[q][0], raw[q][VPP - 1], f);
@@ -208,10 +211,10 @@ __global__ __launch_bounds__(256) void head1x1_kernel(const void* __restrict__ x
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(f[e], wr[c][e], s[c]);
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
+    for (int off = LPP / 2; off >= 1; off >>= 1)
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += __shfl_xor(s[c], off, 64);
-    if (lane == 0 && m < M) {
+    if (cl == 0 && m < M) {
       const int img = m / hw, pix = m - img * hw;
       float* yp = y + (size_t)img * 3 * hw + pix;
       const float l0 = s[0] + b0, l1 = s[1] + b1, l2 = s[2] + b2;
@@ -223,6 +226,26 @@ __global__ __launch_bounds__(256) void head1x1_kernel(const void* __restrict__ x
       if (nonfinite && !(__builtin_isfinite(l0) && __builtin_isfinite(l1) && __builtin_isfinite(l2))) atomicOr(nonfinite, 1u);
     }
   }
+}
+
+template <int PREC>
+__global__ __launch_bounds__(256) void head1x1_kernel(const void* __restrict__ x,
+                                                      const float* __restrict__ w,
+                                                      const float* __restrict__ bias,
+                                                      float* __restrict__ y, int M, int hw,
+                                                      unsigned long long* __restrict__ counts_zero, int ncounts,
+                                                      unsigned* __restrict__ nonfinite) {
+  head1x1_body<PREC, 512>(x, w, bias, y, M, hw, counts_zero, ncounts, nonfinite);
+}
+
+template <int PREC>
+__global__ __launch_bounds__(256) void head1x1_c256_kernel(const void* __restrict__ x,
+                                                           const float* __restrict__ w,
+                                                           const float* __restrict__ bias,
+                                                           float* __restrict__ y, int M, int hw,
+                                                           unsigned long long* __restrict__ counts_zero, int ncounts,
+                                                           unsigned* __restrict__ nonfinite) {
+  head1x1_body<PREC, 256>(x, w, bias, y, M, hw, counts_zero, ncounts, nonfinite);
 }
 
 // Cubic-convolution taps, A = -0.75, exactly the expressions of ATen's
@@ -641,6 +664,17 @@ hipError_t launch_head1x1(const void* x, const float* w, const float* bias, floa
   if (precision == 0) hipLaunchKernelGGL(head1x1_kernel<0>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
   else if (precision == 2) hipLaunchKernelGGL(head1x1_kernel<2>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
   else hipLaunchKernelGGL(head1x1_kernel<1>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+  return hipGetLastError();
+}
+
+hipError_t launch_head1x1_c256(const void* x, const float* w, const float* bias, float* y, int N, int hw,
+                               int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s) {
+  if (3 * N > 256) counts_zero = nullptr;      // the caller then clears the counters itself
+  const int M = N * hw;
+  const int blocks = (M + 63) / 64;           // 4 waves x 16 pixels
+  if (precision == 0) hipLaunchKernelGGL(head1x1_c256_kernel<0>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+  else if (precision == 2) hipLaunchKernelGGL(head1x1_c256_kernel<2>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+  else hipLaunchKernelGGL(head1x1_c256_kernel<1>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
   return hipGetLastError();
 }
 

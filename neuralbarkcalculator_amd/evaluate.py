@@ -112,15 +112,17 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
 
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
-                    streams: int = None) -> dict:
+                    streams: int = None, arch: str = "auto") -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
-    the summary on rank 0.  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
+    the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
+    name).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import sys
     import time
     from collections import defaultdict, deque
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from .model import FCNResNet50
+    from .model import MODELS, FCNResNet50
+    from .predict import resolve_arch
     t_start = time.perf_counter()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -138,15 +140,20 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         batch = 8 if precision == "bf16" else 2
     n_streams = 4 if streams is None else max(1, int(streams))
 
-    model = FCNResNet50(precision).to(dev)
     marker = AbandonMarker(root)
     if rank == 0:
         os.makedirs(os.path.join(root, "results"), exist_ok=True)
         marker.clear()
     if dist is not None:
         dist.barrier()
+    state_dict = None
     if rank == 0:                                    # only one rank touches the checkpoint
-        model.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True))
+        state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
+    arch = resolve_arch(arch, state_dict, dist, dev)
+    model = MODELS[arch](precision).to(dev)
+    if rank == 0:
+        model.load_state_dict(state_dict)
+    del state_dict
     if dist is not None:
         model.broadcast_weights(src=0)
     if precision == "f16x2" and model.pack_flags:
@@ -350,6 +357,8 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
     ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2, 8 in bf16)")
     ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
+    ap.add_argument("--arch", choices=["auto", "fcn_resnet50", "deeplabv3_resnet50"], default="auto",
+                    help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
@@ -359,7 +368,7 @@ def main(argv=None):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, raw, module="neuralbarkcalculator_amd.evaluate"))
     idx = None if "WORLD_SIZE" in os.environ else 0
-    kw = dict(batch=args.batch, streams=args.streams)
+    kw = dict(batch=args.batch, streams=args.streams, arch=args.arch)
     if args.precision == "auto":
         stats = None
         try:

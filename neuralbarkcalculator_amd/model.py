@@ -2,7 +2,8 @@
 
 ``FCNResNet50`` stands where ``fcn_resnet50(pretrained=False)`` is bound to ``self.model`` in
 ``NeuralBarkCalculator.__init__`` (/root/reference/src/bark_calculator/models.py:221-223) and is
-called at ``models.py:269``.  It keeps the reference's surface -- ``load_state_dict``, ``to``,
+called at ``models.py:269``; ``DeepLabV3ResNet50`` stands for ``deeplabv3_resnet50()`` (``models.py:46-57``), the other
+network the reference's training script offers (``__main__.py:230-232``).  They keep the reference's surface -- ``load_state_dict``, ``to``,
 ``eval``, ``__call__`` -- and adds the fused ``predict_labels`` (``models.py:269-270`` plus the
 ``--exclude_nodes`` remap ``models.py:273-276`` and the per-class counts ``models.py:324-331``).
 
@@ -31,11 +32,8 @@ def _as_numpy(v) -> np.ndarray:
     return np.asarray(v)
 
 
-def pack_state_dict(state_dict: Mapping[str, object], precision: str = "fp32") -> np.ndarray:
-    """Check keys like ``nn.Module.load_state_dict`` (strict) and return the packed weight blob
-    (uint8 numpy array).  Raises ``RuntimeError`` listing missing / unexpected keys."""
-    lib = _lib.load()
-    prec = _PRECISIONS[precision]
+def _tensor_array(state_dict: Mapping[str, object]):
+    """The state_dict as an array of nbc_tensor, and what keeps its memory alive during a call."""
     items = []
     keep = []   # keep numpy arrays / byte strings alive during the call
     for name, value in state_dict.items():
@@ -59,11 +57,31 @@ def pack_state_dict(state_dict: Mapping[str, object], precision: str = "fp32") -
         t.dtype = dt
         items.append(t)
         keep.append((a, bname))
-    arr = (_lib.NbcTensor * len(items))(*items)
-    nbytes = lib.nbc_packed_weights_bytes(prec)
+    return (_lib.NbcTensor * len(items))(*items), len(items), keep
+
+
+def pack_state_dict(state_dict: Mapping[str, object], precision: str = "fp32", arch="fcn_resnet50") -> np.ndarray:
+    """Check keys like ``nn.Module.load_state_dict`` (strict) against architecture ``arch`` and return the packed weight
+    blob (uint8 numpy array).  Raises ``RuntimeError`` listing missing / unexpected keys."""
+    lib = _lib.load()
+    prec = _PRECISIONS[precision]
+    a = topology.arch_index(arch)
+    arr, n, _keep = _tensor_array(state_dict)
+    nbytes = lib.nbc_arch_packed_weights_bytes(prec, a)
     blob = np.zeros(nbytes, dtype=np.uint8)
-    _lib.check(lib.nbc_pack_weights(arr, len(items), prec, blob.ctypes.data, nbytes), "load_state_dict")
+    _lib.check(lib.nbc_pack_weights_arch(arr, n, prec, a, blob.ctypes.data, nbytes), "load_state_dict")
     return blob
+
+
+def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
+    """The architecture (``topology.ARCHS``) whose key set the state_dict matches exactly (nbc_arch_of_state_dict);
+    ``RuntimeError`` with the strict-load message of fcn_resnet50 when none does."""
+    lib = _lib.load()
+    arr, n, _keep = _tensor_array(state_dict)
+    rc = lib.nbc_arch_of_state_dict(arr, n)
+    if rc < 0:
+        _lib.check(rc, "load_state_dict")
+    return topology.ARCHS[rc]
 
 
 class FCNResNet50:
@@ -75,6 +93,8 @@ class FCNResNet50:
     two-level sums (include/nbc.h, NBC_PREC_F16X2; same tolerances as "fp32" in the tests); ``"bf16"`` -- bf16 MFMA with
     f32 accumulation and f32 BatchNorm epilogue, the throughput mode.
     """
+
+    ARCH = "fcn_resnet50"                  # topology.ARCHS entry (NBC_ARCH_*) of the network this class runs
 
     def __init__(self, precision: str = "fp32"):
         if precision not in _PRECISIONS:
@@ -92,7 +112,7 @@ class FCNResNet50:
     def load_state_dict(self, state_dict: Mapping[str, object], strict: bool = True):
         if not strict:
             raise NotImplementedError("only strict=True is supported (the reference never passes strict=False)")
-        self._blob_host = pack_state_dict(state_dict, self.precision)
+        self._blob_host = pack_state_dict(state_dict, self.precision, self.ARCH)
         if self.device is not None:
             self._upload()
         return self
@@ -283,7 +303,7 @@ class FCNResNet50:
         in HBM) but owns its own context and activation workspace, so the two can run concurrently
         on different HIP streams (pipelined batch-1 serving)."""
         self._require_weights()
-        other = FCNResNet50(self.precision)
+        other = type(self)(self.precision)
         other.to(self.device)
         other._attach(self._blob_dev)
         return other
@@ -295,7 +315,7 @@ class FCNResNet50:
         import torch.distributed as dist
         if self.device is None:
             raise RuntimeError("call .to(device) before broadcast_weights")
-        nbytes = self._lib.nbc_packed_weights_bytes(self._prec)
+        nbytes = self._lib.nbc_arch_packed_weights_bytes(self._prec, topology.arch_index(self.ARCH))
         if dist.get_rank(group) == src:
             self._require_weights()
             blob = self._blob_dev
@@ -336,7 +356,8 @@ class FCNResNet50:
             return int(rc)
         if self._blob_host is None:
             raise RuntimeError("no weights loaded")
-        rc = self._lib.nbc_packed_weights_flags(self._blob_host.ctypes.data, self._blob_host.size, self._prec)
+        rc = self._lib.nbc_packed_weights_flags_arch(self._blob_host.ctypes.data, self._blob_host.size, self._prec,
+                                                     topology.arch_index(self.ARCH))
         if rc < 0:
             _lib.check(rc, "nbc_packed_weights_flags")
         return int(rc)
@@ -358,14 +379,14 @@ class FCNResNet50:
         try:
             self._forward(x, n, h, w, lowres=torch.empty((n, NUM_CLASSES) + out_hw(h, w), dtype=torch.float32, device=self.device))
             torch.cuda.synchronize(self.device)
-            k = int(self._lib.nbc_num_convs())
+            k = int(self._lib.nbc_arch_num_convs(topology.arch_index(self.ARCH)))
             buf = (C.c_float * k)()
             rc = self._lib.nbc_activation_peaks(self._require_ctx(), buf, k)
             if rc < 0:
                 _lib.check(rc, "nbc_activation_peaks")
         finally:
             self.set_keep_activations(False)
-        names = [u.name for u in topology.conv_units()]
+        names = [u.name for u in topology.conv_units(self.ARCH)]
         return {names[i]: float(buf[i]) for i in range(k) if names[i] != "classifier.4"}
 
     @staticmethod
@@ -456,8 +477,8 @@ class FCNResNet50:
 
     def _attach(self, blob: torch.Tensor):
         assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.device == self.device
-        _lib.check(self._lib.nbc_attach_weights(self._require_ctx(), blob.data_ptr(), blob.numel(), self._prec),
-                   "nbc_attach_weights")
+        _lib.check(self._lib.nbc_attach_weights_arch(self._require_ctx(), blob.data_ptr(), blob.numel(), self._prec,
+                                                     topology.arch_index(self.ARCH)), "nbc_attach_weights")
         self._blob_dev = blob    # keep the device memory alive as long as it is attached
 
     def _check_input(self, x: torch.Tensor) -> Tuple[int, int, int]:
@@ -512,3 +533,22 @@ def fcn_resnet50(pretrained: bool = False, dropout: float = 0.1, precision: str 
         raise RuntimeError("pretrained=True needs a download; load a local state_dict instead (predict.py:57)")
     del dropout  # identity in eval mode
     return FCNResNet50(precision=precision)
+
+
+class DeepLabV3ResNet50(FCNResNet50):
+    """MI355X-native ``deeplabv3_resnet50`` (models.py:46-57): the same trunk and surface as ``FCNResNet50`` with
+    torchvision 0.3's DeepLabHead -- ASPP(2048, [12, 24, 36]) (a 1x1 conv, three 3x3 convs at dilation 12 / 24 / 36 and a
+    global-average-pool branch, concatenated and projected to 256 channels), a 3x3 conv and the 1x1 classifier -- then the
+    same bicubic x8 upsample and argmax.  Strict loading takes exactly its 362 keys; an FCN checkpoint raises, like the
+    reference's ``load_state_dict``.  ``broadcast_weights`` uses ``torch.distributed`` like the FCN model."""
+
+    ARCH = "deeplabv3_resnet50"
+
+
+MODELS = {"fcn_resnet50": FCNResNet50, "deeplabv3_resnet50": DeepLabV3ResNet50}
+
+
+def deeplabv3_resnet50(precision: str = "fp32") -> DeepLabV3ResNet50:
+    """Factory with the reference's name (models.py:46).  The reference builds its trunk with ImageNet weights, which the
+    checkpoint's load_state_dict then replaces in full; here the weights come from load_state_dict alone."""
+    return DeepLabV3ResNet50(precision=precision)

@@ -390,6 +390,37 @@ def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, dev
     return allrows[np.argsort(allrows[:, 0], kind="stable")]
 
 
+def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
+    """The network a folder driver runs (``--arch``).  ``"auto"``: rank 0, the one rank that read the checkpoint, picks
+    the architecture whose key set ``state_dict`` matches (``model.arch_of_state_dict``) and broadcasts its NBC_ARCH_*
+    index, so that every other rank sizes its blob for it.  A checkpoint no architecture matches raises on every rank
+    alike (rank 0 with the strict-load message of fcn_resnet50).  A named architecture is taken as it stands: strict
+    loading then refuses a checkpoint of the other one."""
+    from . import topology
+    if arch != "auto":
+        return topology.ARCHS[topology.arch_index(arch)]
+    rank = dist.get_rank() if dist is not None else 0
+    code, err = -1, None
+    if rank == 0:
+        from .model import arch_of_state_dict
+        try:
+            code = topology.arch_index(arch_of_state_dict(state_dict))
+        except RuntimeError as e:
+            err = e
+    if dist is not None:
+        import torch
+        t = torch.tensor([code], dtype=torch.int32)
+        if dist.get_backend() == "nccl":
+            t = t.to(device)
+        dist.broadcast(t, src=0)
+        code = int(t.cpu()[0])
+    if err is not None:
+        raise err
+    if code < 0:
+        raise RuntimeError("rank 0 found no architecture matching the checkpoint's keys")
+    return topology.ARCHS[code]
+
+
 def plan_items(root: str) -> List[dict]:
     """What the reference's two passes end up predicting, in its order: every file that will exist under
     processed/samples/<wood>/ once the preprocessor has run (models.py:173-189 writes
@@ -414,7 +445,7 @@ def plan_items(root: str) -> List[dict]:
 def predict_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32",
                    exclude_nodes: bool = False, small_zones: bool = True, device_index: int = None,
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
-                   streams: int = None) -> dict:
+                   streams: int = None, arch: str = "auto") -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -431,6 +462,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     shape.  In "f16x2" mode ``calibrate`` (default) runs the first image once with every activation kept and leaves with
     ``NonFiniteLogits`` -- before any batch -- when a stored tensor lies outside the range the f16 pieces hold at f32 grade
     (``FCNResNet50.activation_peaks``: the silent counterpart of the non-finite word, which still rides back with every batch).
+    ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -438,7 +470,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     from concurrent.futures import ThreadPoolExecutor
     import threading
     from PIL import Image
-    from .model import FCNResNet50
+    from .model import MODELS, FCNResNet50
     from .pngio import write_png
     t_start = time.perf_counter()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -457,8 +489,6 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         batch = 8 if precision == "bf16" else 2
     n_streams = 4 if streams is None else max(1, int(streams))
 
-    model = FCNResNet50(precision)
-    model.to(dev)
     pre_model = FCNResNet50(precision).to(dev)      # its own context: the pool's device resizes never touch the predictor's
     marker = AbandonMarker(root)
     if rank == 0:
@@ -466,8 +496,15 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         marker.clear()
     if dist is not None:
         dist.barrier()
+    state_dict = None
     if rank == 0:                                    # only one rank touches the checkpoint
-        model.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True))
+        state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
+    arch = resolve_arch(arch, state_dict, dist, dev)
+    model = MODELS[arch](precision)
+    model.to(dev)
+    if rank == 0:
+        model.load_state_dict(state_dict)
+    del state_dict
     if dist is not None:
         model.broadcast_weights(src=0)
     if precision == "f16x2" and model.pack_flags:
@@ -756,6 +793,8 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
     ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2 in fp32, 8 in bf16)")
     ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
+    ap.add_argument("--arch", choices=["auto", "fcn_resnet50", "deeplabv3_resnet50"], default="auto",
+                    help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--autotune", action="store_true",
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
     raw = list(sys.argv[1:] if argv is None else argv)
@@ -772,7 +811,7 @@ def main(argv=None):
     idx = None
     if "WORLD_SIZE" not in os.environ and ":" in args.device:
         idx = int(args.device.split(":")[1])
-    kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams)
+    kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch)
     if args.precision == "auto":
         stats = None
         try:

@@ -12,7 +12,9 @@ any machine and numpy version.  Shapes follow SURVEY.md section 8(d):
   ``"random_init"`` (torchvision's initialisation: Kaiming-normal fan_out convs, BN identity)
   or ``"trained_like"`` (perturbed BN statistics and a calibrated classifier so that the three
   classes all appear in the label mask; random-init gives an all-"Nothing" mask, which would
-  make a label-parity test vacuous).
+  make a label-parity test vacuous);
+* ``arch="deeplabv3_resnet50"``: the 362-entry state_dict of ``deeplabv3_resnet50`` (``models.py:46-57``), the same
+  trunk (same numbers for the same seed) and a DeepLabHead.
 """
 from __future__ import annotations
 
@@ -65,13 +67,16 @@ def normal(seed: int, stream: int, n: int) -> np.ndarray:
 TRAINED_LIKE_HEAD_BIAS = (0.0, 0.0, 0.0)
 
 
-def make_state_dict(kind: str = "trained_like", seed: int = 7) -> Dict[str, np.ndarray]:
-    """The 326-entry state_dict as numpy arrays (float32; ``num_batches_tracked`` int64)."""
+def make_state_dict(kind: str = "trained_like", seed: int = 7, arch: str = "fcn_resnet50") -> Dict[str, np.ndarray]:
+    """The state_dict of ``arch`` (326 entries for fcn_resnet50, 362 for deeplabv3_resnet50) as numpy arrays (float32;
+    ``num_batches_tracked`` int64)."""
     if kind not in ("trained_like", "random_init"):
         raise ValueError(f"unknown weight kind {kind!r}")
-    units = {u.name: u for u in conv_units()}
+    units = {u.name: u for u in conv_units(arch)}
+    aspp_head = {u.name for u in conv_units(arch) if u.name.startswith("classifier.") and u.bn is not None} \
+        if arch == "deeplabv3_resnet50" else set()
     sd: Dict[str, np.ndarray] = {}
-    for stream, (key, shape, dtype) in enumerate(state_dict_spec()):
+    for stream, (key, shape, dtype) in enumerate(state_dict_spec(arch)):
         n = int(np.prod(shape)) if shape else 1
         if key.endswith("num_batches_tracked"):
             sd[key] = np.zeros((), dtype=np.int64)
@@ -82,6 +87,10 @@ def make_state_dict(kind: str = "trained_like", seed: int = 7) -> Dict[str, np.n
             if u.bn is None:  # classifier.4: nn.Conv2d default init ~ U(-1/sqrt(fan_in), +)
                 bound = 1.0 / np.sqrt(u.cin * u.k * u.k)
                 v = (uniform01(seed, stream, n) * 2.0 - 1.0) * bound
+            elif kind == "trained_like" and prefix in aspp_head:
+                # DeepLabHead's convs read 2048 / 1280 channels into 256: at fan_out scale a tensor's variance would grow
+                # 16x / 10x per layer against running statistics near 1; a fan_in scale keeps the head's activations O(1)
+                v = normal(seed, stream, n) * np.sqrt(1.0 / (u.cin * u.k * u.k))
             else:             # torchvision: kaiming_normal_(mode="fan_out", nonlinearity="relu")
                 v = normal(seed, stream, n) * np.sqrt(2.0 / (u.cout * u.k * u.k))
         elif prefix in units and leaf == "bias":
