@@ -102,6 +102,17 @@ enum {
                                       image) "classifier.0.convs.4". */
 };
 
+/* BatchNorm statistics (nbc_set_bn_statistics). */
+enum {
+  NBC_BN_RUNNING = 0,   /* eval mode (the default): the running statistics, folded into each conv's epilogue at pack time */
+  NBC_BN_PER_IMAGE = 1  /* every BatchNorm normalises each image by that image's own per-channel mean and BIASED variance
+                           over its H x W pixels (eps 1e-5) and applies the checkpoint's gamma and beta: F.batch_norm(training=
+                           True) on a batch of one, what the shipped tool's forward does (models.py:212-250 never calls .eval()
+                           and feeds one image at a time).  Running statistics are read by nothing and updated by nothing;
+                           Dropout stays the identity (its expectation: live Dropout noise is what remains different from the
+                           shipped tool).  NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50 only. */
+};
+
 /* Layout of the image handed to nbc_forward. */
 enum {
   NBC_IN_F32_NCHW = 0,  /* float32 [N,3,H,W], already normalised: exactly `batch[0]` of models.py:269 */
@@ -191,6 +202,14 @@ int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int preci
  * bytes, or NBC_ERR_INVALID. */
 int nbc_packed_weights_arch(const void* blob, size_t blob_bytes, int precision);
 
+/* The per-image BatchNorm affine array (NBC_BN_PER_IMAGE): gamma then beta of every conv unit that has a BatchNorm, in
+ * conv-unit order (nbc_arch_conv_info), as f32.  It travels beside the blob, not in it (a blob's bytes do not depend on the
+ * BatchNorm mode).  nbc_arch_bn_affine_floats: its length (2 x the summed cout of those units), 0 for an unknown
+ * architecture.  nbc_pack_bn_affine: the strict key / shape check of nbc_pack_weights (same errors and messages), then the
+ * array into `out` (at least that many floats). */
+size_t nbc_arch_bn_affine_floats(int arch);
+int nbc_pack_bn_affine(const nbc_tensor* tensors, int n, int arch, float* out, size_t count);
+
 /* ---- context --------------------------------------------------------------------------- */
 int nbc_create(nbc_ctx** out, int hip_device);
 int nbc_destroy(nbc_ctx* ctx);
@@ -202,7 +221,8 @@ int nbc_attach_weights(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int pre
  * (NBC_ERR_INVALID).  nbc_forward, nbc_reserve, nbc_autotune, the plan tiles, the profiling records, keep mode and the
  * calibration guard then run that architecture. */
 int nbc_attach_weights_arch(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int precision, int arch);
-/* Convenience: pack on the host, allocate device memory owned by the context, upload. */
+/* Convenience: pack on the host, allocate device memory owned by the context, upload; the BatchNorm affine array
+ * (nbc_pack_bn_affine) of the same tensors is uploaded and attached as well. */
 int nbc_load_weights(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision);
 int nbc_load_weights_arch(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision, int arch);
 /* NBC_PACK_* bits of the attached blob (read from its trailer when it was attached: a 1-KiB device-to-host copy), >= 0,
@@ -222,6 +242,21 @@ int nbc_activation_exponent(nbc_ctx* ctx, const char* name, int32_t* exponent);
  * has been synchronised.  NBC_ARCH_FCN_RESNET50 only: NBC_ERR_STATE on a context that holds another architecture (the
  * folder drivers broadcast the blob through torch.distributed). */
 int nbc_bcast_weights(nbc_ctx* ctx, void* rccl_comm, int root, int precision, void* hip_stream);
+/* Attach a per-image BatchNorm affine array (nbc_pack_bn_affine) that lives in DEVICE memory and stays owned by the caller
+ * (must outlive the context or the next attach); `count` floats, nbc_arch_bn_affine_floats of the attached architecture.
+ * nbc_bcast_weights does not carry it: a multi-rank caller broadcasts it itself and attaches it on each rank. */
+int nbc_attach_bn_affine(nbc_ctx* ctx, const float* dev_affine, size_t count);
+/* NBC_BN_RUNNING (default) or NBC_BN_PER_IMAGE.  NBC_ERR_STATE for NBC_BN_PER_IMAGE unless the attached weights are
+ * NBC_PREC_FP32 of NBC_ARCH_FCN_RESNET50 (f16x2 folds powers of two into the BatchNorm pairs at pack time; bf16 rounds the
+ * raw pre-BatchNorm values; DeepLabV3's pooling-branch BatchNorm sees one value per channel, which batch statistics refuse).
+ * The mode is part of the plan key, like the precision.  In NBC_BN_PER_IMAGE every BatchNorm'd convolution runs raw on the
+ * same conv kernels and tiles (nbc_autotune, nbc_set_plan_tiles: the same list), followed by two plan ops named after the
+ * BatchNorm: "<bn>.stats" (kernel "bn_stats": per-image sums over fixed pixel slices, f64, no atomics, so an image's bits do
+ * not depend on its batch) and "<bn>.apply" (kernel "bn_apply": in place, with the identity and ReLU of the unit).  Keep
+ * mode returns each unit's post-BatchNorm (post-ReLU) tensor under the unit's name.  nbc_forward / nbc_reserve then return
+ * NBC_ERR_STATE without an affine array attached, and NBC_ERR_INVALID ("Expected more than 1 value per channel when
+ * training") for an image whose low-resolution map is 1 x 1 (e.g. 8 x 8), which batch statistics cannot normalise. */
+int nbc_set_bn_statistics(nbc_ctx* ctx, int mode);
 /* mean/std used for NBC_IN_U8_NHWC input; defaults are models.py:208-209. */
 int nbc_set_normalization(nbc_ctx* ctx, const float mean[3], const float std[3]);
 /* Pre-size the workspace for an (N,H,W) so that the first nbc_forward does not allocate.  Buffers only grow, and a

@@ -19,6 +19,7 @@ IN_F32_NCHW, IN_U8_NHWC = 0, 1
 LABEL_U8, LABEL_I64 = 0, 1
 PACK_ROW_CLAMPED, PACK_SCALE_RANGE = 1, 2      # NBC_PACK_* of include/nbc.h
 ARCH_FCN_RESNET50, ARCH_DEEPLABV3_RESNET50 = 0, 1   # NBC_ARCH_*
+BN_RUNNING, BN_PER_IMAGE = 0, 1                     # NBC_BN_*
 
 
 class NbcTensor(C.Structure):
@@ -63,6 +64,10 @@ SIGNATURES = {
     "nbc_pack_weights_arch": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "nbc_packed_weights_flags_arch": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "nbc_packed_weights_arch": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int]),
+    "nbc_arch_bn_affine_floats": (C.c_size_t, [C.c_int]),
+    "nbc_pack_bn_affine": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "nbc_attach_bn_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "nbc_set_bn_statistics": (C.c_int, [C.c_void_p, C.c_int]),
     "nbc_weights_flags": (C.c_int, [C.c_void_p]),
     "nbc_activation_exponent": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
     "nbc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),

@@ -29,7 +29,7 @@ namespace {
       return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
-enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT };
+enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT, OP_BN_STATS, OP_BN_APPLY };
 
 struct Op {
   OpKind kind;
@@ -42,11 +42,16 @@ struct Op {
   int rows;            // OP_CONV: conv_rows_kind: 0 generic tiles, 1 / 2 the row-resident 3x3 kernel (kind 1: tiles 18 or 20; kind 2: tile 19)
   int ws_buf;          // OP_ASPP_POOL: workspace buffer (slice partials, then the per-image means)
   int cat_in[5];       // OP_CONCAT: the four spatial branches' buffers and the pooled vectors' buffer
+  bool raw;            // OP_CONV in NBC_BN_PER_IMAGE: unit scale, zero shift, no ReLU, no identity (the raw conv output)
+  int relu;            // OP_BN_APPLY: the unit's ReLU
+  size_t affine_off;   // OP_BN_STATS: floats before the unit's (gamma, beta) in the affine array
 };
 
 struct Plan {
   int N = 0, H = 0, W = 0, precision = -1, arch = 0;
   bool keep = false;
+  int bn = NBC_BN_RUNNING;             // NBC_BN_*
+  size_t bn_ws_bytes = 0;              // NBC_BN_PER_IMAGE: slice partials + [N][C] scale and shift of the largest BatchNorm
   int h = 0, w = 0;                    // low-res logits size
   std::vector<Op> ops;
   std::vector<size_t> buf_bytes;       // per activation buffer
@@ -86,17 +91,24 @@ struct nbc_ctx {
   unsigned* nonfinite = nullptr;            // one device word: bit 0 = a forward produced a NaN / infinite logit (sticky)
   void* zones_ws = nullptr;                 // remove_small_zones workspace: bg bytes, parent ints, size ints
   size_t zones_px = 0;                      // pixels it is sized for
+  int bn_mode = NBC_BN_RUNNING;             // NBC_BN_*
+  const float* bn_affine = nullptr;         // device: gamma, beta per BatchNorm unit (nbc_pack_bn_affine)
+  size_t bn_affine_count = 0;
+  void* owned_affine = nullptr;             // the affine array nbc_load_weights uploaded
+  float* bn_unit = nullptr;                 // device: 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
+  void* bn_ws = nullptr;                    // per-image BatchNorm workspace (Plan::bn_ws_bytes)
+  size_t bn_ws_cap = 0;
 };
 
 namespace {
 
 constexpr size_t kPlanCacheEntries = 64;
 
-bool same_shape(const Plan& p, int N, int H, int W, int precision, bool keep, int arch) {
-  return p.N == N && p.H == H && p.W == W && p.precision == precision && p.keep == keep && p.arch == arch;
+bool same_shape(const Plan& p, int N, int H, int W, int precision, bool keep, int arch, int bn) {
+  return p.N == N && p.H == H && p.W == W && p.precision == precision && p.keep == keep && p.arch == arch && p.bn == bn;
 }
 bool same_plan(const Plan& p, const nbc_ctx* c, int N, int H, int W) {
-  return same_shape(p, N, H, W, c->precision, c->keep, c->arch);
+  return same_shape(p, N, H, W, c->precision, c->keep, c->arch, c->bn_mode);
 }
 
 // Park the current plan (folders of height-trimmed images alternate between a few shapes: each keeps
@@ -105,7 +117,7 @@ void stash_plan(nbc_ctx* c) {
   Plan& cur = c->plan;
   if (cur.N == 0) return;
   for (Plan& p : c->plan_cache)
-    if (same_shape(p, cur.N, cur.H, cur.W, cur.precision, cur.keep, cur.arch)) {
+    if (same_shape(p, cur.N, cur.H, cur.W, cur.precision, cur.keep, cur.arch, cur.bn)) {
       p = cur; cur = Plan(); return;
     }
   if (c->plan_cache.size() >= kPlanCacheEntries) c->plan_cache.erase(c->plan_cache.begin());
@@ -117,10 +129,14 @@ void stash_plan(nbc_ctx* c) {
 // unless `keep` asks for one buffer per op (layer-by-layer parity tests).
 int build_plan(nbc_ctx* c, int N, int H, int W) {
   Plan P;
-  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch;
+  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch; P.bn = c->bn_mode;
   const int eb = elem_bytes(c->precision);
   const auto& units = conv_units(c->arch);
   const auto& L = c->layout;
+  const bool per_image = P.bn == NBC_BN_PER_IMAGE;
+  std::vector<size_t> affine_off(units.size(), 0);     // per unit: floats of the affine array before its (gamma, beta)
+  for (size_t u = 0, off = 0; u < units.size(); ++u)
+    if (!units[u].bn.empty()) { affine_off[u] = off; off += 2 * (size_t)units[u].cout; }
 
   std::vector<bool> in_use;
   auto acquire = [&](size_t bytes) {
@@ -146,12 +162,16 @@ int build_plan(nbc_ctx* c, int N, int H, int W) {
   }
   int curH = H, curW = W, curC = cin_img;
 
+  std::string refused;                                  // per image: the first BatchNorm that would see one value per channel
   auto add_conv = [&](int ui, int in_buf, int inH, int inW, int inC, int res_buf, int* oH, int* oW) {
     const ConvUnit& u = units[ui];
     const int Ho = conv_out(inH, u.k, u.stride, u.pad, u.dil);
     const int Wo = conv_out(inW, u.k, u.stride, u.pad, u.dil);
+    const bool bn_ops = per_image && !u.bn.empty();     // raw conv, then <bn>.stats and <bn>.apply (with the identity)
+    const int idt = res_buf;
+    if (bn_ops) res_buf = -1;
     Op o{};
-    o.kind = OP_CONV; o.unit = ui; o.in_buf = in_buf; o.res_buf = res_buf;
+    o.kind = OP_CONV; o.unit = ui; o.in_buf = in_buf; o.res_buf = res_buf; o.raw = bn_ops;
     o.Hi = inH; o.Wi = inW; o.Ci = inC; o.Ho = Ho; o.Wo = Wo; o.Co = u.cout; o.name = u.name;
     o.out_buf = acquire((size_t)N * Ho * Wo * u.cout * eb);
     o.rows = conv_rows_kind(c->precision, u.k, u.stride, u.pad, u.dil, inH, inW, Ho, Wo, inC, u.cout, res_buf >= 0);
@@ -161,6 +181,26 @@ int build_plan(nbc_ctx* c, int N, int H, int W) {
     o.bytes = ((double)N * inH * inW * u.cin + (double)u.cout * u.cin * u.k * u.k + M * u.cout +
                (res_buf >= 0 ? M * u.cout : 0.0)) * eb;
     P.ops.push_back(o);
+    if (bn_ops) {
+      // F.batch_norm(training=True) of a batch of one refuses a map of one pixel; so does this mode, for every image
+      if (Ho * Wo == 1 && refused.empty())
+        refused = "Expected more than 1 value per channel when training, got input size [1, " + std::to_string(u.cout) +
+                  ", 1, 1] (" + u.bn + " of a " + std::to_string(H) + "x" + std::to_string(W) + " image; per-image BatchNorm)";
+      const int hw = Ho * Wo;
+      Op st = o;
+      st.kind = OP_BN_STATS; st.in_buf = o.out_buf; st.res_buf = -1; st.raw = false; st.name = u.bn + ".stats";
+      st.affine_off = affine_off[ui];
+      st.flops = 3.0 * M * u.cout;
+      st.bytes = M * u.cout * 4.0 + (double)N * bn_stats_slices(hw) * u.cout * 16.0;
+      P.ops.push_back(st);
+      Op ap = o;
+      ap.kind = OP_BN_APPLY; ap.in_buf = o.out_buf; ap.res_buf = idt; ap.raw = false; ap.name = u.bn + ".apply";
+      ap.relu = u.relu ? 1 : 0;
+      ap.flops = 2.0 * M * u.cout;
+      ap.bytes = (2.0 + (idt >= 0 ? 1.0 : 0.0)) * M * u.cout * 4.0;
+      P.ops.push_back(ap);
+      P.bn_ws_bytes = std::max(P.bn_ws_bytes, bn_stats_workspace_bytes(N, hw, u.cout));
+    }
     *oH = Ho; *oW = Wo;
     return o.out_buf;
   };
@@ -259,6 +299,7 @@ int build_plan(nbc_ctx* c, int N, int H, int W) {
     P.ops.push_back(up);
   }
   (void)L;
+  if (!refused.empty()) return set_error(NBC_ERR_INVALID, refused);
 
   c->plan = P;
   return NBC_OK;
@@ -287,6 +328,20 @@ int ensure_buffers(nbc_ctx* c) {
       c->buf_cap[i] = want;
     }
   }
+  if (P.bn == NBC_BN_PER_IMAGE) {
+    if (!c->bn_unit) {
+      std::vector<float> unit(4096, 0.f);
+      std::fill(unit.begin(), unit.begin() + 2048, 1.f);
+      NBC_HIP(hipMalloc((void**)&c->bn_unit, unit.size() * sizeof(float)));
+      NBC_HIP(hipMemcpy(c->bn_unit, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (c->bn_ws_cap < P.bn_ws_bytes) {
+      if (c->bn_ws) NBC_HIP(hipFree(c->bn_ws));
+      c->bn_ws = nullptr; c->bn_ws_cap = 0;
+      NBC_HIP(hipMalloc(&c->bn_ws, P.bn_ws_bytes));
+      c->bn_ws_cap = P.bn_ws_bytes;
+    }
+  }
   const size_t lr = (size_t)P.N * kNumClasses * P.h * P.w * sizeof(float);
   if (c->lowres_cap < lr) {
     if (c->lowres) NBC_HIP(hipFree(c->lowres));
@@ -312,13 +367,19 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
   a.scale = reinterpret_cast<const float*>(c->weights + pc.scale_off);
   a.shift = reinterpret_cast<const float*>(c->weights + pc.shift_off);
   a.res = o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr;
+  if (o.raw) {                                         // per-image BatchNorm follows: fma(acc, 1, 0) = acc in f32
+    if (o.Co > 2048) return set_error(NBC_ERR_STATE, "raw convolution wider than the unit table at " + o.name);
+    a.scale = c->bn_unit;
+    a.shift = c->bn_unit + 2048;
+    a.res = nullptr;
+  }
   a.y = c->bufs[o.out_buf];
   a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.Ci = o.Ci;
   a.Ho = o.Ho; a.Wo = o.Wo; a.Co = o.Co;
   a.KH = u.k; a.KW = u.k; a.stride = u.stride; a.pad = u.pad; a.dil = u.dil;
   a.M = N * o.Ho * o.Wo;
   a.ksteps = pc.ksteps;
-  a.relu = u.relu ? 1 : 0;
+  a.relu = u.relu && !o.raw ? 1 : 0;
   a.stem = pc.stem ? 1 : 0;
   a.wo_shift = -1;
   a.hw_shift = -1;
@@ -345,6 +406,8 @@ const char* kernel_name(OpKind k) {
     case OP_HEAD1X1: return "head1x1";
     case OP_ASPP_POOL: return "aspp_pool";
     case OP_CONCAT: return "concat";
+    case OP_BN_STATS: return "bn_stats";
+    case OP_BN_APPLY: return "bn_apply";
     default: return "upsample_argmax";
   }
 }
@@ -380,6 +443,9 @@ int nbc_destroy(nbc_ctx* c) {
   if (c->scratch256) (void)hipFree(c->scratch256);
   if (c->nonfinite) (void)hipFree(c->nonfinite);
   if (c->owned_weights) (void)hipFree(c->owned_weights);
+  if (c->owned_affine) (void)hipFree(c->owned_affine);
+  if (c->bn_unit) (void)hipFree(c->bn_unit);
+  if (c->bn_ws) (void)hipFree(c->bn_ws);
   for (auto& set : c->prof_sets) for (hipEvent_t ev : set) (void)hipEventDestroy(ev);
   delete c;
   return NBC_OK;
@@ -433,6 +499,43 @@ int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int prec
   rc = nbc_attach_weights_arch(c, dev, bytes, precision, arch);
   if (rc != NBC_OK) { (void)hipFree(dev); return rc; }
   c->owned_weights = dev;
+  // the per-image BatchNorm affine array of the same tensors (already checked by the pack above)
+  std::vector<float> affine(nbc_arch_bn_affine_floats(arch));
+  rc = nbc_pack_bn_affine(tensors, n, arch, affine.data(), affine.size());
+  if (rc != NBC_OK) return rc;
+  void* adev = nullptr;
+  NBC_HIP(hipMalloc(&adev, affine.size() * sizeof(float)));
+  e = hipMemcpy(adev, affine.data(), affine.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(adev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn affine): ") + hipGetErrorString(e)); }
+  if (c->owned_affine) (void)hipFree(c->owned_affine);
+  c->owned_affine = adev;
+  c->bn_affine = static_cast<const float*>(adev);
+  c->bn_affine_count = affine.size();
+  return NBC_OK;
+}
+
+int nbc_attach_bn_affine(nbc_ctx* c, const float* dev_affine, size_t count) {
+  if (!c || !dev_affine) return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: null argument");
+  if (count != nbc_arch_bn_affine_floats(kArchFcn) && count != nbc_arch_bn_affine_floats(kArchDeepLab))
+    return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: count is nbc_arch_bn_affine_floats of no architecture");
+  if (c->owned_affine && c->owned_affine != dev_affine) {
+    NBC_HIP(hipSetDevice(c->device));
+    (void)hipFree(c->owned_affine);                    // synchronises: nothing of the old array is in flight
+    c->owned_affine = nullptr;
+  }
+  c->bn_affine = dev_affine;
+  c->bn_affine_count = count;
+  return NBC_OK;
+}
+
+int nbc_set_bn_statistics(nbc_ctx* c, int mode) {
+  if (!c) return set_error(NBC_ERR_INVALID, "null context");
+  if (mode != NBC_BN_RUNNING && mode != NBC_BN_PER_IMAGE) return set_error(NBC_ERR_INVALID, "nbc_set_bn_statistics: unknown mode");
+  if (mode == NBC_BN_PER_IMAGE && (c->precision != NBC_PREC_FP32 || c->arch != kArchFcn))
+    return set_error(NBC_ERR_STATE, "nbc_set_bn_statistics: per-image BatchNorm statistics need NBC_PREC_FP32 weights of "
+                                    "NBC_ARCH_FCN_RESNET50 attached");
+  if (c->bn_mode != mode) stash_plan(c);               // another launch list: park this one, like a precision change
+  c->bn_mode = mode;
   return NBC_OK;
 }
 
@@ -585,6 +688,13 @@ int nbc_reserve(nbc_ctx* c, int N, int H, int W) {
   if (!c) return set_error(NBC_ERR_INVALID, "null context");
   if (c->precision < 0) return set_error(NBC_ERR_STATE, "nbc_reserve: no weights attached");
   if (N < 1 || H < 8 || W < 8) return set_error(NBC_ERR_INVALID, "nbc_reserve: need N>=1, H>=8, W>=8");
+  if (c->bn_mode == NBC_BN_PER_IMAGE) {
+    if (c->precision != NBC_PREC_FP32 || c->arch != kArchFcn)
+      return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics need NBC_PREC_FP32 weights of NBC_ARCH_FCN_RESNET50 attached");
+    if (!c->bn_affine || c->bn_affine_count != nbc_arch_bn_affine_floats(c->arch))
+      return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics: no affine array of this architecture attached "
+                                      "(nbc_attach_bn_affine)");
+  }
   NBC_HIP(hipSetDevice(c->device));
   if (same_plan(c->plan, c, N, H, W)) return NBC_OK;
   stash_plan(c);
@@ -688,6 +798,23 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         e = launch_aspp_concat(br, c->bufs[o.cat_in[4]], c->bufs[o.out_buf], N, o.Ho * o.Wo, prec, s);
         break;
       }
+      case OP_BN_STATS:
+      case OP_BN_APPLY: {
+        // the workspace: slice partials, then the [N][C] scale and shift tables of this BatchNorm (stats writes, apply reads)
+        const int hw = o.Ho * o.Wo;
+        float* scale = reinterpret_cast<float*>(static_cast<unsigned char*>(c->bn_ws) +
+                                                (size_t)N * bn_stats_slices(hw) * o.Co * 2 * sizeof(double));
+        float* shift = scale + (size_t)N * o.Co;
+        if (o.kind == OP_BN_STATS) {
+          const float* gamma = c->bn_affine + o.affine_off;
+          e = launch_bn_stats(static_cast<const float*>(c->bufs[o.out_buf]), N, hw, o.Co, gamma, gamma + o.Co, c->bn_ws, scale,
+                              shift, s);
+        } else {
+          e = launch_bn_apply(static_cast<float*>(c->bufs[o.out_buf]), o.res_buf >= 0 ? static_cast<const float*>(c->bufs[o.res_buf]) : nullptr,
+                              N, hw, o.Co, scale, shift, o.relu, s);
+        }
+        break;
+      }
       case OP_UPSAMPLE:
         if (counts_dev && 3 * N > 256) {             // more counters than classifier.4's launch clears
           e = hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 3 * N, s);
@@ -730,7 +857,8 @@ static int collect_profile(nbc_ctx* c) {
     std::snprintf(r.kernel, sizeof(r.kernel), "%s", kernel_name(o.kind));
     r.ms = (float)(sum[i] / (double)c->prof_used);
     r.calls = (int32_t)c->prof_used;
-    r.launches = o.kind == OP_ASPP_POOL ? 3 : 1;              // partial sums, their sum, the 1x1 conv
+    r.launches = o.kind == OP_ASPP_POOL ? 3 : (o.kind == OP_BN_STATS ? 2 : 1);   // aspp: partial sums, their sum, the 1x1 conv;
+                                                                                   // bn_stats: partial sums, their sum + the table
     r.flops = o.flops;
     r.bytes = o.bytes;
     r.kh = r.kw = (o.kind == OP_CONV || o.kind == OP_HEAD1X1) ? units[o.unit].k : 0;

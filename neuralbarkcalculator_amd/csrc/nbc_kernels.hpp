@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip and aspp.hip).
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip, aspp.hip and bn_stats.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +74,17 @@ hipError_t launch_aspp_pool(const void* x, int N, int hw, int cin, const float* 
 // ASPP concat: y [N*hw][1280] elements = the four branches [N*hw][256] then the image's pooled vector [N][256], per pixel.
 hipError_t launch_aspp_concat(const void* const branch[4], const void* pooled, void* y, int N, int hw, int precision,
                               hipStream_t s);
+// Per-image BatchNorm (bn_stats.hip), f32 NHWC y [N][hw][C], C a power of two in [64, 2048].  bn_stats: per (image,
+// channel) mean and biased variance over hw pixels in two levels over bn_stats_slices(hw) fixed slices (f64), then
+// scale[n][c] = gamma[c] / sqrt(var + 1e-5), shift[n][c] = beta[c] - mean * scale.  ws: bn_stats_workspace_bytes(N, hw, C)
+// bytes, of which the slice partials are the first N * slices * C * 16.  bn_apply: in place, y = relu?(fma(y, scale, shift)
+// (+ res)), res nullable.
+int bn_stats_slices(int hw);
+size_t bn_stats_workspace_bytes(int N, int hw, int C);
+hipError_t launch_bn_stats(const float* y, int N, int hw, int C, const float* gamma, const float* beta, void* ws, float* scale,
+                           float* shift, hipStream_t s);
+hipError_t launch_bn_apply(float* y, const float* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
+                           hipStream_t s);
 // Bicubic (A=-0.75, align_corners=False) upsample of f32 NCHW [N,3,h,w] to HxW, fused with the
 // per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,

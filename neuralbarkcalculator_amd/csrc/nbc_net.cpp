@@ -113,6 +113,13 @@ const std::vector<StateKey>& state_keys(int arch) {
   return k[arch == kArchDeepLab ? kArchDeepLab : kArchFcn];
 }
 
+size_t bn_affine_floats(int arch) {
+  size_t n = 0;
+  for (const ConvUnit& c : conv_units(arch))
+    if (!c.bn.empty()) n += 2 * (size_t)c.cout;
+  return n;
+}
+
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 PackedLayout packed_layout(int precision, int arch) {
@@ -639,6 +646,30 @@ int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int preci
   if (meta[kMetaArch] != arch || meta[2] != (int32_t)conv_units(arch).size())
     return set_error(NBC_ERR_INVALID, std::string("nbc_packed_weights_flags: not a blob of ") + arch_name(arch));
   return meta[1];
+}
+
+size_t nbc_arch_bn_affine_floats(int arch) {
+  if (!known_arch(arch)) return 0;
+  return bn_affine_floats(arch);
+}
+
+int nbc_pack_bn_affine(const nbc_tensor* tensors, int n, int arch, float* out, size_t count) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_affine: unknown architecture");
+  if (!tensors || n < 0 || !out) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_affine: null argument");
+  if (count < bn_affine_floats(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_affine: out holds fewer than nbc_arch_bn_affine_floats() floats");
+  std::map<std::string, const nbc_tensor*> given;
+  std::string msg;
+  const int krc = check_state_dict(tensors, n, arch, &given, &msg);  // the strict check of nbc_pack_weights
+  if (krc == NBC_ERR_INVALID) return set_error(krc, "nbc_pack_bn_affine: " + msg);
+  if (krc != NBC_OK) return set_error(krc, msg);
+  size_t off = 0;
+  for (const ConvUnit& c : conv_units(arch)) {
+    if (c.bn.empty()) continue;
+    std::memcpy(out + off, given[c.bn + ".weight"]->data, (size_t)c.cout * 4);
+    std::memcpy(out + off + c.cout, given[c.bn + ".bias"]->data, (size_t)c.cout * 4);
+    off += 2 * (size_t)c.cout;
+  }
+  return NBC_OK;
 }
 
 int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision) {

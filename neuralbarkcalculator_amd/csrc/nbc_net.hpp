@@ -42,6 +42,10 @@ struct StateKey {
 const std::vector<ConvUnit>& conv_units(int arch = kArchFcn);
 const std::vector<StateKey>& state_keys(int arch = kArchFcn);
 
+// Floats of the per-image BatchNorm affine array (nbc_pack_bn_affine): gamma then beta of every conv unit with a BatchNorm,
+// in conv-unit order; the unit's pair sits at the running sum of 2 * cout over the units before it.
+size_t bn_affine_floats(int arch);
+
 // bytes per activation / weight element: f32 4, bf16 2, f16x2 4 (two f16 pieces; a 128-byte group holds 32 channels:
 // [h0 x 32][h1 x 32], so tensors, K-steps and LDS rows have the f32 mode's geometry)
 inline int elem_bytes(int precision) { return precision == 1 ? 2 : 4; }

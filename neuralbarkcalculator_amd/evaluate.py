@@ -44,8 +44,8 @@ from typing import List, Tuple
 import numpy as np
 
 from . import metrics
-from .predict import (AbandonMarker, NonFiniteLogits, _decode_rgb, _host_workers, gather_rows, launch_ranks, list_images,
-                      shard_by_pixels)
+from .predict import (BN_STATS, AbandonMarker, NonFiniteLogits, _decode_rgb, _host_workers, gather_rows, launch_ranks,
+                      list_images, resolve_bn_stats, shard_by_pixels)
 
 ROW_WIDTH = 22                                   # (global_idx, H, W, status, conf_raw[9], conf_clean[9])
 STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
@@ -90,7 +90,8 @@ def write_stats_csv(path: str, rows) -> None:
         csv.writer(f, delimiter="\t").writerows([metrics.EVAL_CSV_HEADER] + [list(r) for r in rows])
 
 
-def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str) -> Tuple[List[List[str]], dict]:
+def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
+           bn_stats: str = "running") -> Tuple[List[List[str]], dict]:
     """CSV rows and summary from the gathered rank rows (rank 0)."""
     rows, skipped = [], {r: [] for r in SKIP_REASONS.values()}
     raw_total, clean_total = np.zeros((3, 3), np.int64), np.zeros((3, 3), np.int64)
@@ -103,7 +104,7 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
         raw_total += raw
         clean_total += clean
         rows.append(metrics.eval_row(d["name"], d["wood"], raw, clean))
-    summary = {"precision": precision, "model_path": model_path, "images_evaluated": len(rows),
+    summary = {"precision": precision, "bn_statistics": bn_stats, "model_path": model_path, "images_evaluated": len(rows),
                "images_skipped": sum(len(v) for v in skipped.values()), "skipped": skipped}
     if rows:
         summary.update(metrics.summarize(rows, raw_total, clean_total))
@@ -112,17 +113,18 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
 
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
-                    streams: int = None, arch: str = "auto") -> dict:
+                    streams: int = None, arch: str = "auto", bn_stats: str = "running") -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
-    name).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
+    name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
+    ("fp32", FCN only; ``predict.resolve_bn_stats``).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import sys
     import time
     from collections import defaultdict, deque
     from concurrent.futures import ThreadPoolExecutor
     import torch
     from .model import MODELS, FCNResNet50
-    from .predict import resolve_arch
+    from .predict import check_bn_stats_arch, resolve_arch
     t_start = time.perf_counter()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -150,7 +152,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if rank == 0:                                    # only one rank touches the checkpoint
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
     arch = resolve_arch(arch, state_dict, dist, dev)
-    model = MODELS[arch](precision).to(dev)
+    check_bn_stats_arch(bn_stats, arch)
+    model = MODELS[arch](precision).set_bn_statistics(bn_stats).to(dev)
     if rank == 0:
         model.load_state_dict(state_dict)
     del state_dict
@@ -320,7 +323,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     summary = gathered = None
     if rank == 0:
         gathered = allrows.tolist()
-        csv_rows, summary = report(items, allrows, precision, model_path)
+        csv_rows, summary = report(items, allrows, precision, model_path, bn_stats)
         write_stats_csv(os.path.join(root, STATS_CSV), csv_rows)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
@@ -335,8 +338,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
 
 
 def format_summary(summary: dict) -> str:
-    lines = ["evaluated %d images in %s (checkpoint %s), skipped %d%s" % (
-        summary["images_evaluated"], summary["precision"], summary["model_path"], summary["images_skipped"],
+    lines = ["evaluated %d images in %s%s (checkpoint %s), skipped %d%s" % (
+        summary["images_evaluated"], summary["precision"],
+        ", per-image BatchNorm statistics" if summary.get("bn_statistics") == "image" else "", summary["model_path"],
+        summary["images_skipped"],
         "".join("; %s: %s" % (r, ", ".join(v)) for r, v in summary["skipped"].items() if v))]
     if "pooled" in summary:
         p = summary["pooled"]
@@ -359,16 +364,23 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
     ap.add_argument("--arch", choices=["auto", "fcn_resnet50", "deeplabv3_resnet50"], default="auto",
                     help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
+    ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
+                    help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
+                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
+    try:
+        args.precision = resolve_bn_stats(args.bn_stats, args.precision)
+    except ValueError as e:
+        ap.error(str(e))
     if args.exclude_nodes:
         raise SystemExit("evaluate: --exclude_nodes is not supported: IoU and F1 are defined on the three classes "
                          "(nothing, bark, node) of the duals")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, raw, module="neuralbarkcalculator_amd.evaluate"))
     idx = None if "WORLD_SIZE" in os.environ else 0
-    kw = dict(batch=args.batch, streams=args.streams, arch=args.arch)
+    kw = dict(batch=args.batch, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
     if args.precision == "auto":
         stats = None
         try:

@@ -24,6 +24,7 @@ from .topology import NUM_CLASSES, out_hw
 
 _PRECISIONS = {"fp32": _lib.PREC_FP32, "f32": _lib.PREC_FP32, "float32": _lib.PREC_FP32,
                "bf16": _lib.PREC_BF16, "bfloat16": _lib.PREC_BF16, "f16x2": _lib.PREC_F16X2}
+BN_STATISTICS = {"running": _lib.BN_RUNNING, "image": _lib.BN_PER_IMAGE}   # NBC_BN_*
 
 
 def _as_numpy(v) -> np.ndarray:
@@ -73,6 +74,37 @@ def pack_state_dict(state_dict: Mapping[str, object], precision: str = "fp32", a
     return blob
 
 
+def pack_bn_affine(state_dict: Mapping[str, object], arch="fcn_resnet50") -> np.ndarray:
+    """The per-image BatchNorm affine array of ``state_dict`` (nbc_pack_bn_affine): float32, gamma then beta of every conv
+    unit with a BatchNorm, in ``topology.conv_units`` order.  Same strict key check and ``RuntimeError`` as
+    ``pack_state_dict``."""
+    lib = _lib.load()
+    a = topology.arch_index(arch)
+    arr, n, _keep = _tensor_array(state_dict)
+    count = lib.nbc_arch_bn_affine_floats(a)
+    out = np.zeros(count, dtype=np.float32)
+    _lib.check(lib.nbc_pack_bn_affine(arr, n, a, out.ctypes.data, count), "load_state_dict")
+    return out
+
+
+def broadcast_bn_affine(affine: Optional[np.ndarray], arch="fcn_resnet50", src: int = 0, group=None, device=None) -> np.ndarray:
+    """``torch.distributed`` broadcast of the per-image BatchNorm affine array from rank ``src`` (which passes it; the
+    other ranks pass None and get its copy).  ``device``: where the collective's tensor lives (an RCCL group needs the
+    GPU; None = the host, for gloo)."""
+    import torch.distributed as dist
+    count = int(_lib.load().nbc_arch_bn_affine_floats(topology.arch_index(arch)))
+    if dist.get_rank(group) == src:
+        if affine is None or affine.size != count:
+            raise RuntimeError("broadcast_bn_affine: the source rank holds no affine array of %s" % arch)
+        t = torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float32))
+    else:
+        t = torch.empty(count, dtype=torch.float32)
+    if device is not None:
+        t = t.to(device)
+    dist.broadcast(t, src=src, group=group)
+    return t.cpu().numpy()
+
+
 def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
     """The architecture (``topology.ARCHS``) whose key set the state_dict matches exactly (nbc_arch_of_state_dict);
     ``RuntimeError`` with the strict-load message of fcn_resnet50 when none does."""
@@ -92,6 +124,11 @@ class FCNResNet50:
     a power of two per output channel, so their magnitude does not matter), three exact f16 products per product, f32
     two-level sums (include/nbc.h, NBC_PREC_F16X2; same tolerances as "fp32" in the tests); ``"bf16"`` -- bf16 MFMA with
     f32 accumulation and f32 BatchNorm epilogue, the throughput mode.
+
+    bn_statistics (``set_bn_statistics``): ``"running"`` (default) -- eval mode, BatchNorm on the running statistics;
+    ``"image"`` -- every BatchNorm normalises each image by its own per-channel mean and biased variance, as the shipped
+    tool's forward does (it never calls ``.eval()`` and feeds one image at a time); "fp32" only.  Dropout is the identity
+    in both (live Dropout noise is all that stays different from the shipped tool).
     """
 
     ARCH = "fcn_resnet50"                  # topology.ARCHS entry (NBC_ARCH_*) of the network this class runs
@@ -102,8 +139,11 @@ class FCNResNet50:
         self._lib = _lib.load()            # fails loudly when libnbc_hip.so is not built
         self.precision = precision
         self._prec = _PRECISIONS[precision]
+        self.bn_statistics = "running"
         self._blob_host: Optional[np.ndarray] = None
         self._blob_dev: Optional[torch.Tensor] = None
+        self._affine_host: Optional[np.ndarray] = None     # per-image BatchNorm gamma / beta (pack_bn_affine)
+        self._affine_dev: Optional[torch.Tensor] = None
         self._ctx = C.c_void_p()
         self.device: Optional[torch.device] = None
         self.training = False
@@ -113,6 +153,7 @@ class FCNResNet50:
         if not strict:
             raise NotImplementedError("only strict=True is supported (the reference never passes strict=False)")
         self._blob_host = pack_state_dict(state_dict, self.precision, self.ARCH)
+        self._affine_host = pack_bn_affine(state_dict, self.ARCH)
         if self.device is not None:
             self._upload()
         return self
@@ -138,7 +179,29 @@ class FCNResNet50:
         return self.to(torch.device("cuda", index if index is not None else torch.cuda.current_device()))
 
     def eval(self):
-        """No-op: the path is eval-only (BN running stats, Dropout identity)."""
+        """No-op: the path is eval-only (BN running stats, Dropout identity); see ``set_bn_statistics`` for the
+        per-image BatchNorm statistics of the shipped tool."""
+        return self
+
+    def set_bn_statistics(self, mode: str):
+        """``"running"`` (default): BatchNorm on the checkpoint's running statistics, folded into the convolutions.
+        ``"image"``: every BatchNorm uses the statistics of the image being run -- per-channel mean and biased variance over
+        its H x W pixels, eps 1e-5, the checkpoint's gamma and beta: ``F.batch_norm(training=True)`` on a batch of one, what
+        the shipped tool computes.  Nothing is updated (this is not training: ``train(True)`` stays refused), and an image's
+        result does not depend on the batch it runs in.  "fp32" FCN-ResNet-50 only (``ValueError`` otherwise, before the
+        device is touched); an image whose low-resolution map is 1 x 1 (e.g. 8 x 8) raises ``ValueError`` like torch does."""
+        if mode not in BN_STATISTICS:
+            raise ValueError(f"bn_statistics must be one of {sorted(BN_STATISTICS)}, got {mode!r}")
+        if mode == "image":
+            if self.ARCH != "fcn_resnet50":
+                raise ValueError("per-image BatchNorm statistics are refused for %s: its ASPP pooling branch's BatchNorm sees a "
+                                 "[1, 256, 1, 1] tensor, which batch statistics cannot normalise (torch raises, and so would "
+                                 "the reference)" % self.ARCH)
+            if self._prec != _lib.PREC_FP32:
+                raise ValueError("per-image BatchNorm statistics run in precision 'fp32' only, not %r" % self.precision)
+        self.bn_statistics = mode
+        if self._ctx:
+            _lib.check(self._lib.nbc_set_bn_statistics(self._ctx, BN_STATISTICS[mode]), "nbc_set_bn_statistics")
         return self
 
     def train(self, mode: bool = True):
@@ -304,8 +367,9 @@ class FCNResNet50:
         on different HIP streams (pipelined batch-1 serving)."""
         self._require_weights()
         other = type(self)(self.precision)
+        other.bn_statistics = self.bn_statistics
         other.to(self.device)
-        other._attach(self._blob_dev)
+        other._attach(self._blob_dev, self._affine_dev)
         return other
 
     # ---- multi-GPU: one process per GPU, weights read by one rank only ---------------------
@@ -322,7 +386,11 @@ class FCNResNet50:
         else:
             blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         dist.broadcast(blob, src=src, group=group)
-        self._attach(blob)
+        # the per-image BatchNorm affine array travels beside the blob (one more collective, every rank alike)
+        affine = broadcast_bn_affine(self._affine_host if dist.get_rank(group) == src else None, self.ARCH, src, group,
+                                     self.device)
+        self._affine_host = affine
+        self._attach(blob, torch.from_numpy(affine).to(self.device))
         return self
 
     # ---- measurement / debugging ------------------------------------------------------------
@@ -473,13 +541,19 @@ class FCNResNet50:
 
     def _upload(self):
         blob = torch.from_numpy(self._blob_host).to(self.device, non_blocking=False)
-        self._attach(blob)
+        affine = torch.from_numpy(self._affine_host).to(self.device) if self._affine_host is not None else None
+        self._attach(blob, affine)
 
-    def _attach(self, blob: torch.Tensor):
+    def _attach(self, blob: torch.Tensor, affine: Optional[torch.Tensor] = None):
         assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.device == self.device
         _lib.check(self._lib.nbc_attach_weights_arch(self._require_ctx(), blob.data_ptr(), blob.numel(), self._prec,
                                                      topology.arch_index(self.ARCH)), "nbc_attach_weights")
         self._blob_dev = blob    # keep the device memory alive as long as it is attached
+        if affine is not None:
+            assert affine.dtype == torch.float32 and affine.is_contiguous() and affine.device == self.device
+            _lib.check(self._lib.nbc_attach_bn_affine(self._ctx, affine.data_ptr(), affine.numel()), "nbc_attach_bn_affine")
+            self._affine_dev = affine
+        _lib.check(self._lib.nbc_set_bn_statistics(self._ctx, BN_STATISTICS[self.bn_statistics]), "nbc_set_bn_statistics")
 
     def _check_input(self, x: torch.Tensor) -> Tuple[int, int, int]:
         self._require_weights()
@@ -499,6 +573,9 @@ class FCNResNet50:
             raise RuntimeError(f"unsupported input dtype {x.dtype}")
         if h < 8 or w < 8:
             raise RuntimeError("H and W must be >= 8")
+        if self.bn_statistics == "image" and out_hw(int(h), int(w)) == (1, 1):
+            raise ValueError("Expected more than 1 value per channel when training: a %dx%d image has a 1x1 low-resolution "
+                             "map, which per-image BatchNorm statistics cannot normalise" % (h, w))
         return int(n), int(h), int(w)
 
     def _forward(self, x, n, h, w, logits_full=None, labels=None, counts=None, lowres=None,
@@ -526,13 +603,15 @@ class FCNResNet50:
             pass
 
 
-def fcn_resnet50(pretrained: bool = False, dropout: float = 0.1, precision: str = "fp32") -> FCNResNet50:
+def fcn_resnet50(pretrained: bool = False, dropout: float = 0.1, precision: str = "fp32",
+                 bn_statistics: str = "running") -> FCNResNet50:
     """Factory with the reference's name and arguments (models.py:127).  ``pretrained=True``
-    would download ImageNet weights in the reference; there is no network here."""
+    would download ImageNet weights in the reference; there is no network here.  ``bn_statistics``:
+    ``FCNResNet50.set_bn_statistics``."""
     if pretrained:
         raise RuntimeError("pretrained=True needs a download; load a local state_dict instead (predict.py:57)")
-    del dropout  # identity in eval mode
-    return FCNResNet50(precision=precision)
+    del dropout  # identity in eval mode (and its expectation in train mode)
+    return FCNResNet50(precision=precision).set_bn_statistics(bn_statistics)
 
 
 class DeepLabV3ResNet50(FCNResNet50):

@@ -421,6 +421,31 @@ def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
     return topology.ARCHS[code]
 
 
+BN_STATS = ("running", "image")
+
+
+def resolve_bn_stats(bn_stats: str, precision: str) -> str:
+    """The precision a folder driver runs with ``--bn_stats`` (``FCNResNet50.set_bn_statistics``).  ``"running"`` leaves
+    ``precision`` as it is.  ``"image"`` (the shipped tool's per-image BatchNorm statistics) runs the f32 MFMA only:
+    ``"auto"`` means ``"fp32"`` (no f16x2 run, no calibration), ``"f16x2"`` and ``"bf16"`` raise ``ValueError``."""
+    if bn_stats not in BN_STATS:
+        raise ValueError("--bn_stats must be one of %s, got %r" % (", ".join(BN_STATS), bn_stats))
+    if bn_stats == "running":
+        return precision
+    if precision in ("auto", "fp32"):
+        return "fp32"
+    raise ValueError("--bn_stats image runs in --precision fp32 (or auto) only, not %s: raw pre-BatchNorm values do not fit "
+                     "the f16x2 pieces' pack-time scaling, and bf16 rounds them too coarsely for the mean subtraction" % precision)
+
+
+def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
+    """``ValueError`` for ``--bn_stats image`` on a network other than FCN-ResNet-50.  Called with the architecture
+    ``resolve_arch`` returned, which every rank holds alike, so every rank refuses alike."""
+    if bn_stats == "image" and arch != "fcn_resnet50":
+        raise ValueError("--bn_stats image is refused for %s: its ASPP pooling branch's BatchNorm sees a [1, 256, 1, 1] tensor, "
+                         "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
+
+
 def plan_items(root: str) -> List[dict]:
     """What the reference's two passes end up predicting, in its order: every file that will exist under
     processed/samples/<wood>/ once the preprocessor has run (models.py:173-189 writes
@@ -445,7 +470,7 @@ def plan_items(root: str) -> List[dict]:
 def predict_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32",
                    exclude_nodes: bool = False, small_zones: bool = True, device_index: int = None,
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
-                   streams: int = None, arch: str = "auto") -> dict:
+                   streams: int = None, arch: str = "auto", bn_stats: str = "running") -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -462,7 +487,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     shape.  In "f16x2" mode ``calibrate`` (default) runs the first image once with every activation kept and leaves with
     ``NonFiniteLogits`` -- before any batch -- when a stored tensor lies outside the range the f16 pieces hold at f32 grade
     (``FCNResNet50.activation_peaks``: the silent counterpart of the non-finite word, which still rides back with every batch).
-    ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.
+    ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.  ``bn_stats``: ``"running"``
+    (eval mode) or ``"image"``, the per-image BatchNorm statistics the shipped tool ran with ("fp32", FCN only:
+    ``resolve_bn_stats``, ``check_bn_stats_arch``).
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -500,7 +527,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     if rank == 0:                                    # only one rank touches the checkpoint
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
     arch = resolve_arch(arch, state_dict, dist, dev)
-    model = MODELS[arch](precision)
+    check_bn_stats_arch(bn_stats, arch)
+    model = MODELS[arch](precision).set_bn_statistics(bn_stats)
     model.to(dev)
     if rank == 0:
         model.load_state_dict(state_dict)
@@ -797,8 +825,15 @@ def main(argv=None):
                     help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--autotune", action="store_true",
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
+    ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
+                    help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
+                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
+    try:
+        args.precision = resolve_bn_stats(args.bn_stats, args.precision)
+    except ValueError as e:
+        ap.error(str(e))
     if not args.device.startswith("cuda"):
         raise SystemExit("this package is the MI355X path; run the reference for --device=cpu")
     if args.only_preprocess:                             # predict.py:53-55: the resize runs on the device here too
@@ -811,7 +846,7 @@ def main(argv=None):
     idx = None
     if "WORLD_SIZE" not in os.environ and ":" in args.device:
         idx = int(args.device.split(":")[1])
-    kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch)
+    kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
     if args.precision == "auto":
         stats = None
         try:
