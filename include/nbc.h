@@ -94,12 +94,25 @@ enum {
  * and differ in the head.  Every function without an architecture argument is architecture 0. */
 enum {
   NBC_ARCH_FCN_RESNET50 = 0,       /* FCNHead(2048, 3): 3x3 conv 2048 -> 512, BN, ReLU, 1x1 conv 512 -> 3 (326 keys) */
-  NBC_ARCH_DEEPLABV3_RESNET50 = 1  /* DeepLabHead(2048, 3) of torchvision 0.3: ASPP(2048, [12, 24, 36]) -- 1x1 conv, three
+  NBC_ARCH_DEEPLABV3_RESNET50 = 1, /* DeepLabHead(2048, 3) of torchvision 0.3: ASPP(2048, [12, 24, 36]) -- 1x1 conv, three
                                       3x3 convs at dilation 12 / 24 / 36 and global-average-pool + 1x1 conv, each 256
                                       channels with BN + ReLU, concatenated (1280) and projected 1280 -> 256 with BN + ReLU --,
                                       3x3 conv 256 -> 256, BN, ReLU, 1x1 conv 256 -> 3 (362 keys).  Its activations have the
                                       conv unit names; the concat is "classifier.0.concat" and the pooled vector (one pixel per
                                       image) "classifier.0.convs.4". */
+  /* 2 is not an architecture.  EfficientNet-b{n}, n = 0..7 (models.py:60-110): the trunk of efficientnet_pytorch 0.7
+     (EfficientNet.from_pretrained('efficientnet-b{n}').extract_features, keys "backbone.model.*", its unused ImageNet
+     classifier "backbone.model._fc.*" included) under FCNHead(inplanes, 3) / DeepLabHead(inplanes, 3), inplanes = 1280 ..
+     2560.  NBC_PREC_FP32 only, running statistics only.  Output stride 32 (nbc_arch_lowres_size), bicubic x32.  Every
+     BatchNorm of the trunk has eps 1e-3 (the heads' 1e-5); every convolution pads TF-"same" for the variant's native image
+     size (nbc_arch_conv_ext).  Activations are stored NHWC f32 with their channels zero-padded to a multiple of 64; keep
+     mode and nbc_read_activation return the real channels.  Keep-mode names are the torch module names:
+     "<block>._expand_conv" and "_conv_stem" hold the BatchNorm output BEFORE its swish (the depthwise kernel applies it as
+     it reads them), "<block>._depthwise_conv" the swish output before the SE gate, "<block>._se_expand" the gate
+     (sigmoid, one pixel per image), "<block>._project_conv" the block's output, "_conv_head" the trunk's output (after its
+     swish). */
+  NBC_ARCH_FCN_EFFICIENTNET_B0 = 16,        /* + n: fcn_efficientnet(n) */
+  NBC_ARCH_DEEPLABV3_EFFICIENTNET_B0 = 24   /* + n: deeplabv3_efficientnet(n) */
 };
 
 /* BatchNorm statistics (nbc_set_bn_statistics). */
@@ -142,6 +155,19 @@ typedef struct {
   int32_t relu, bias, residual;
 } nbc_conv_desc;
 
+/* What nbc_conv_desc does not say about a unit (EfficientNet; for the ResNet-50 networks: kind 0, pad_after = pad, cin_pad /
+ * cout_pad = cin / cout, block -1, eps 1e-5). */
+typedef struct {
+  int32_t kind;        /* 0 convolution, 1 depthwise (groups = channels; its weight is [C,1,k,k]), 2 SE reduce, 3 SE expand */
+  int32_t pad_before;  /* top / left pad (= nbc_conv_desc.pad) */
+  int32_t pad_after;   /* bottom / right pad */
+  int32_t act;         /* after the BatchNorm (or the bias): 0 none, 1 ReLU, 2 swish (SE expand: its sigmoid is the gate) */
+  int32_t cin_pad, cout_pad;   /* channels of the stored input / output tensors */
+  int32_t block;       /* MBConv block index, -1 outside the blocks */
+  int32_t in_swish;    /* depthwise: applies the swish its stored input was written without */
+  float eps;           /* BatchNorm eps */
+} nbc_conv_ext;
+
 /* Per-op record of the last profiled forwards (nbc_set_profiling). */
 typedef struct {
   char name[64];      /* conv unit name, or "ingest" / "maxpool" / "upsample_argmax" */
@@ -173,6 +199,10 @@ int nbc_arch_state_key(int arch, int index, const char** name, int64_t shape[4],
 int nbc_arch_of_state_dict(const nbc_tensor* tensors, int n);
 /* Low-resolution logits size for an HxW input (three stride-2 stages). */
 int nbc_lowres_size(int H, int W, int* h, int* w);
+/* The same for architecture `arch`: the ResNet-50 networks as nbc_lowres_size; EfficientNet through its five stride-2
+ * convolutions with their fixed pads, floor((H + before + after - k) / 2) + 1 each (not always ceil(H / 2)). */
+int nbc_arch_lowres_size(int arch, int H, int W, int* h, int* w);
+int nbc_arch_conv_ext(int arch, int index, nbc_conv_ext* out);
 
 /* ---- weights (host side; no GPU needed) ------------------------------------------------ */
 /* The two f16 pieces NBC_PREC_F16X2 keeps of each of n f32 ACTIVATION values (host arithmetic, bit patterns of IEEE
@@ -195,7 +225,7 @@ int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision)
  * 0 holds as 0, so an FCN blob of nbc_pack_weights_arch(..., 0, ...) is byte for byte the one nbc_pack_weights wrote before
  * the word had this meaning.  f16x2: the five ASPP branches write one tensor, the concat, and share one power of two (from
  * the largest of their five BatchNorm estimates); the pooling branch keeps its weights in f32 like classifier.4. */
-size_t nbc_arch_packed_weights_bytes(int precision, int arch);
+size_t nbc_arch_packed_weights_bytes(int precision, int arch);   /* 0 for an EfficientNet network outside NBC_PREC_FP32 */
 int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int arch, void* blob, size_t blob_bytes);
 int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int precision, int arch);
 /* The architecture recorded in a packed blob in HOST memory of exactly nbc_arch_packed_weights_bytes(precision, arch)

@@ -19,6 +19,7 @@ IN_F32_NCHW, IN_U8_NHWC = 0, 1
 LABEL_U8, LABEL_I64 = 0, 1
 PACK_ROW_CLAMPED, PACK_SCALE_RANGE = 1, 2      # NBC_PACK_* of include/nbc.h
 ARCH_FCN_RESNET50, ARCH_DEEPLABV3_RESNET50 = 0, 1   # NBC_ARCH_*
+ARCH_FCN_EFFICIENTNET_B0, ARCH_DEEPLABV3_EFFICIENTNET_B0 = 16, 24   # + n, n = 0..7
 BN_RUNNING, BN_PER_IMAGE = 0, 1                     # NBC_BN_*
 
 
@@ -32,6 +33,12 @@ class NbcConvDesc(C.Structure):
                 ("cin", C.c_int32), ("cout", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32),
                 ("pad", C.c_int32), ("dil", C.c_int32),
                 ("relu", C.c_int32), ("bias", C.c_int32), ("residual", C.c_int32)]
+
+
+class NbcConvExt(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad_before", C.c_int32), ("pad_after", C.c_int32), ("act", C.c_int32),
+                ("cin_pad", C.c_int32), ("cout_pad", C.c_int32), ("block", C.c_int32), ("in_swish", C.c_int32),
+                ("eps", C.c_float)]
 
 
 class NbcOpRecord(C.Structure):
@@ -56,6 +63,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nbc_arch_of_state_dict": (C.c_int, [C.POINTER(NbcTensor), C.c_int]),
     "nbc_lowres_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nbc_arch_lowres_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nbc_arch_conv_ext": (C.c_int, [C.c_int, C.c_int, C.POINTER(NbcConvExt)]),
     "nbc_packed_weights_bytes": (C.c_size_t, [C.c_int]),
     "nbc_split_f16x2": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "nbc_pack_weights": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

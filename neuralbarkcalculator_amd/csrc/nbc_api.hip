@@ -29,7 +29,8 @@ namespace {
       return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
-enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT, OP_BN_STATS, OP_BN_APPLY };
+enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT, OP_BN_STATS, OP_BN_APPLY,
+              OP_DWCONV, OP_SE_EXCITE, OP_GATE_WEIGHTS, OP_SWISH, OP_POOL_ANY };
 
 struct Op {
   OpKind kind;
@@ -45,6 +46,13 @@ struct Op {
   bool raw;            // OP_CONV in NBC_BN_PER_IMAGE: unit scale, zero shift, no ReLU, no identity (the raw conv output)
   int relu;            // OP_BN_APPLY: the unit's ReLU
   size_t affine_off;   // OP_BN_STATS: floats before the unit's (gamma, beta) in the affine array
+  // EfficientNet
+  int gate_buf = -1;   // OP_CONV: per-image weights [N][Co][Ci] (the SE-gated project conv: one launch per image);
+                       // OP_SE_EXCITE / OP_GATE_WEIGHTS: the gate [N][C]
+  int creal = 0;       // channels of the tensor the network defines (0 = Co): nbc_read_activation drops the pad channels
+  int launches = 1;    // launches of the op per forward (profiling records)
+  int tiles = 0;       // OP_DWCONV / OP_SE_EXCITE: SE squeeze partials per image
+  int aux_unit = -1;   // OP_SE_EXCITE: the _se_expand unit (unit = _se_reduce); OP_GATE_WEIGHTS: the project unit
 };
 
 struct Plan {
@@ -127,7 +135,10 @@ void stash_plan(nbc_ctx* c) {
 
 // Build the launch list for an (N,H,W).  Activation buffers are recycled through a small pool
 // unless `keep` asks for one buffer per op (layer-by-layer parity tests).
+int build_plan_effnet(nbc_ctx* c, int N, int H, int W);
+
 int build_plan(nbc_ctx* c, int N, int H, int W) {
+  if (is_effnet(c->arch)) return build_plan_effnet(c, N, H, W);
   Plan P;
   P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch; P.bn = c->bn_mode;
   const int eb = elem_bytes(c->precision);
@@ -305,6 +316,183 @@ int build_plan(nbc_ctx* c, int N, int H, int W) {
   return NBC_OK;
 }
 
+// EfficientNet (fp32): ingest, the stem on conv_dma (its swish deferred), per MBConv block [expand conv (swish deferred)],
+// depthwise conv (+ BN, swish, SE squeeze partials), SE excite (gate), gated project weights, project conv per image
+// (+ identity), then the head conv with a swish pass and the FCN / DeepLab head.  Channels padded (ConvUnit::outc).
+int build_plan_effnet(nbc_ctx* c, int N, int H, int W) {
+  Plan P;
+  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch; P.bn = c->bn_mode;
+  const auto& units = conv_units(c->arch);
+  std::vector<bool> in_use;
+  auto acquire = [&](size_t bytes) {
+    if (!P.keep)
+      for (size_t i = 0; i < in_use.size(); ++i)
+        if (!in_use[i]) { in_use[i] = true; P.buf_bytes[i] = std::max(P.buf_bytes[i], bytes); return (int)i; }
+    in_use.push_back(true);
+    P.buf_bytes.push_back(bytes);
+    return (int)in_use.size() - 1;
+  };
+  auto release = [&](int b) { if (b >= 0 && !P.keep) in_use[b] = false; };
+  std::string err;
+  // a conv_dma launch of unit ui; gate_buf >= 0: per image on the gated weights
+  auto add_conv = [&](int ui, int in_buf, int inH, int inW, int res_buf, int gate_buf, int* oH, int* oW) {
+    const ConvUnit& u = units[ui];
+    const int keff = u.dil * (u.k - 1) + 1;                          // the dilated extent (ASPP)
+    const int Ho = same_out(inH, keff, u.stride, u.pad, u.pad_end());
+    const int Wo = same_out(inW, keff, u.stride, u.pad, u.pad_end());
+    if ((Ho < 1 || Wo < 1) && err.empty())
+      err = "nbc_forward: a " + std::to_string(H) + "x" + std::to_string(W) + " image is too small for " + arch_name(c->arch) +
+            " (" + u.name + " has no output pixel)";
+    Op o{};
+    o.kind = OP_CONV; o.unit = ui; o.in_buf = in_buf; o.res_buf = res_buf; o.gate_buf = gate_buf;
+    o.Hi = inH; o.Wi = inW; o.Ci = u.inc(); o.Ho = Ho; o.Wo = Wo; o.Co = u.outc(); o.creal = u.cout; o.name = u.name;
+    o.out_buf = acquire((size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * u.outc() * 4);
+    o.rows = 0;
+    const int Mt = (gate_buf >= 0 ? 1 : N) * std::max(Ho * Wo, 1);
+    o.tile = choose_conv_tile(Mt, u.outc(), u.inc() * u.k * u.k, c->precision, 0);
+    o.launches = gate_buf >= 0 ? N : 1;
+    const double M = (double)N * Ho * Wo;
+    o.flops = 2.0 * M * u.cout * u.cin * u.k * u.k;
+    o.bytes = ((double)N * inH * inW * u.inc() + (double)u.outc() * u.inc() * u.k * u.k * (gate_buf >= 0 ? N : 1) + M * u.outc() +
+               (res_buf >= 0 ? M * u.outc() : 0.0)) * 4;
+    P.ops.push_back(o);
+    *oH = Ho; *oW = Wo;
+    return o.out_buf;
+  };
+
+  int cur = acquire((size_t)N * H * W * kChunkBytes);
+  {
+    Op o{};
+    o.kind = OP_INGEST; o.unit = -1; o.in_buf = -1; o.out_buf = cur; o.res_buf = -1;
+    o.Hi = H; o.Wi = W; o.Ci = 3; o.Ho = H; o.Wo = W; o.Co = kChunkBytes / 4; o.creal = 3; o.name = "ingest";
+    P.ops.push_back(o);
+  }
+  int curH = H, curW = W;
+  {
+    int oH, oW;
+    const int b = add_conv(0, cur, curH, curW, -1, -1, &oH, &oW);   // _conv_stem: BN, swish deferred
+    release(cur);
+    cur = b; curH = oH; curW = oW;
+  }
+  size_t ui = 1;
+  while (ui < units.size() && units[ui].block >= 0) {
+    const int in = cur, inH = curH, inW = curW;
+    int e = in, eH = inH, eW = inW;
+    if (units[ui].kind == kUnitConv) {                                // _expand_conv
+      e = add_conv((int)ui, in, inH, inW, -1, -1, &eH, &eW);
+      ++ui;
+    }
+    const ConvUnit& dw = units[ui];
+    const int C = dw.outc();
+    const int Ho = same_out(eH, dw.k, dw.stride, dw.pad, dw.pad_end()), Wo = same_out(eW, dw.k, dw.stride, dw.pad, dw.pad_end());
+    if ((Ho < 1 || Wo < 1) && err.empty())
+      err = "nbc_forward: a " + std::to_string(H) + "x" + std::to_string(W) + " image is too small for " + arch_name(c->arch) +
+            " (" + dw.name + " has no output pixel)";
+    const int tiles = dwconv_tiles(dw.stride, std::max(Ho, 1), std::max(Wo, 1));
+    const int ws = acquire((size_t)N * tiles * C * 4);
+    Op d{};
+    d.kind = OP_DWCONV; d.unit = (int)ui; d.in_buf = e; d.res_buf = -1; d.ws_buf = ws; d.tiles = tiles;
+    d.Hi = eH; d.Wi = eW; d.Ci = C; d.Ho = Ho; d.Wo = Wo; d.Co = C; d.creal = dw.cout; d.name = dw.name;
+    d.out_buf = acquire((size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * C * 4);
+    d.flops = 2.0 * N * Ho * Wo * dw.cout * dw.k * dw.k;
+    d.bytes = ((double)N * eH * eW * C + (double)N * Ho * Wo * C) * 4;
+    P.ops.push_back(d);
+    if (e != in) release(e);
+    const ConvUnit& red = units[ui + 1];
+    const ConvUnit& exc = units[ui + 2];
+    const ConvUnit& prj = units[ui + 3];
+    const int gate = acquire((size_t)N * C * 4);
+    Op se{};
+    se.kind = OP_SE_EXCITE; se.unit = (int)ui + 1; se.aux_unit = (int)ui + 2; se.in_buf = ws; se.res_buf = -1; se.tiles = tiles;
+    se.out_buf = gate; se.gate_buf = gate;
+    se.Hi = Ho; se.Wi = Wo; se.Ci = C; se.Ho = 1; se.Wo = 1; se.Co = C; se.creal = exc.cout; se.name = exc.name;
+    se.flops = 4.0 * N * C * red.cout;
+    se.bytes = ((double)N * tiles * C + 2.0 * C * red.cout + (double)N * C) * 4;
+    P.ops.push_back(se);
+    release(ws);
+    const int wg = acquire((size_t)N * prj.outc() * prj.inc() * 4);
+    Op gw{};
+    gw.kind = OP_GATE_WEIGHTS; gw.unit = (int)ui + 3; gw.in_buf = -1; gw.out_buf = -1; gw.res_buf = -1; gw.ws_buf = wg;
+    gw.gate_buf = gate; gw.Ci = prj.inc(); gw.Co = prj.outc(); gw.name = prj.name + ".gated_weights";
+    gw.flops = (double)N * prj.outc() * prj.inc();
+    gw.bytes = ((double)prj.outc() * prj.inc() * (1 + N) + (double)N * C) * 4;
+    P.ops.push_back(gw);
+    release(gate);
+    int pH, pW;
+    const int out = add_conv((int)ui + 3, d.out_buf, Ho, Wo, prj.residual ? in : -1, wg, &pH, &pW);
+    release(d.out_buf);
+    release(wg);
+    release(in);
+    cur = out; curH = pH; curW = pW;
+    ui += 4;
+  }
+  {
+    int oH, oW;
+    const int h = add_conv((int)ui, cur, curH, curW, -1, -1, &oH, &oW);   // _conv_head, then its swish in place
+    release(cur);
+    Op sw{};
+    sw.kind = OP_SWISH; sw.unit = (int)ui; sw.in_buf = h; sw.out_buf = h; sw.res_buf = -1;
+    sw.Hi = oH; sw.Wi = oW; sw.Ci = units[ui].outc(); sw.Ho = oH; sw.Wo = oW; sw.Co = units[ui].outc(); sw.creal = units[ui].cout;
+    sw.name = units[ui].name + ".swish";
+    sw.flops = (double)N * oH * oW * units[ui].cout * 4;
+    sw.bytes = 2.0 * N * oH * oW * units[ui].outc() * 4;
+    P.ops.push_back(sw);
+    cur = h; curH = oH; curW = oW;
+    ++ui;
+  }
+  int oH = curH, oW = curW, t, cls = (int)ui + 1;
+  if (is_deeplab_head(c->arch)) {
+    int br[4];
+    for (int b = 0; b < 4; ++b) br[b] = add_conv((int)ui + b, cur, curH, curW, -1, -1, &oH, &oW);
+    const ConvUnit& pu = units[ui + 4];
+    const int hw = curH * curW, B = pu.cout;
+    const int ws = acquire((size_t)N * pool_any_slices(std::max(hw, 1)) * pu.cin * 4);
+    Op po{};
+    po.kind = OP_POOL_ANY; po.unit = (int)ui + 4; po.in_buf = cur; po.res_buf = -1; po.ws_buf = ws;
+    po.Hi = curH; po.Wi = curW; po.Ci = pu.cin; po.Ho = 1; po.Wo = 1; po.Co = B; po.name = "classifier.0.convs.4";
+    po.out_buf = acquire((size_t)N * B * 4);
+    po.launches = 2;
+    po.flops = 2.0 * N * B * pu.cin + (double)N * hw * pu.cin;
+    po.bytes = (double)N * hw * pu.cin * 4 + (double)B * pu.cin * 4 + (double)N * B * 4;
+    P.ops.push_back(po);
+    release(ws);
+    release(cur);
+    Op co{};
+    co.kind = OP_CONCAT; co.unit = -1; co.in_buf = -1; co.res_buf = -1;
+    for (int b = 0; b < 4; ++b) co.cat_in[b] = br[b];
+    co.cat_in[4] = po.out_buf;
+    co.Hi = oH; co.Wi = oW; co.Ci = 5 * B; co.Ho = oH; co.Wo = oW; co.Co = 5 * B; co.name = "classifier.0.concat";
+    co.out_buf = acquire((size_t)N * hw * 5 * B * 4);
+    co.bytes = 2.0 * N * hw * 5 * B * 4;
+    P.ops.push_back(co);
+    for (int b = 0; b < 5; ++b) release(co.cat_in[b]);
+    const int pj = add_conv((int)ui + 5, co.out_buf, oH, oW, -1, -1, &oH, &oW);
+    release(co.out_buf);
+    t = add_conv((int)ui + 6, pj, oH, oW, -1, -1, &oH, &oW);
+    release(pj);
+    cls = (int)ui + 7;
+  } else {
+    t = add_conv((int)ui, cur, curH, curW, -1, -1, &oH, &oW);             // classifier.0
+    release(cur);
+  }
+  Op o{};
+  o.kind = OP_HEAD1X1; o.unit = cls; o.in_buf = t; o.out_buf = -1; o.res_buf = -1;
+  o.Hi = oH; o.Wi = oW; o.Ci = units[cls].inc(); o.Ho = oH; o.Wo = oW; o.Co = kNumClasses; o.name = units[cls].name;
+  o.flops = 2.0 * N * oH * oW * units[cls].cin * kNumClasses;
+  o.bytes = (double)N * oH * oW * o.Ci * 4 + (double)N * oH * oW * kNumClasses * 4;
+  P.ops.push_back(o);
+  release(t);
+  P.h = oH; P.w = oW;
+  Op up{};
+  up.kind = OP_UPSAMPLE; up.unit = -1; up.in_buf = -1; up.out_buf = -1; up.res_buf = -1;
+  up.Hi = oH; up.Wi = oW; up.Ci = kNumClasses; up.Ho = H; up.Wo = W; up.Co = kNumClasses; up.name = "upsample_argmax";
+  up.bytes = (double)N * oH * oW * kNumClasses * 4 + (double)N * H * W;
+  P.ops.push_back(up);
+  if (!err.empty()) return set_error(NBC_ERR_INVALID, err);
+  c->plan = P;
+  return NBC_OK;
+}
+
 // Workspace of the current plan: buffers only ever grow, so a plan taken back from the cache finds
 // them large enough unless a later, smaller-indexed plan never needed that slot.  A buffer that has to grow
 // grows by at least half (hipFree synchronises the device: shapes that rise one after the other then reallocate
@@ -394,6 +582,21 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     return set_error(NBC_ERR_INVALID, "activation of " + o.name + " exceeds 2 GiB: lower the batch size");
   a.x_bytes = (unsigned)xb;
   a.w_bytes = (unsigned)wbts;
+  if (o.gate_buf >= 0) {                               // EfficientNet's project conv: image n on its SE-gated weights
+    const size_t xi = (size_t)o.Hi * o.Wi * o.Ci * eb, yi = (size_t)o.Ho * o.Wo * o.Co * eb;
+    a.N = 1;
+    a.M = o.Ho * o.Wo;
+    a.x_bytes = (unsigned)xi;
+    for (int n = 0; n < N; ++n) {
+      a.x = static_cast<const unsigned char*>(c->bufs[o.in_buf]) + n * xi;
+      a.w = static_cast<const unsigned char*>(c->bufs[o.gate_buf]) + n * wbts;
+      a.res = o.res_buf >= 0 ? static_cast<const unsigned char*>(c->bufs[o.res_buf]) + n * yi : nullptr;
+      a.y = static_cast<unsigned char*>(c->bufs[o.out_buf]) + n * yi;
+      *err = launch_conv_dma(a, prec, tile, s);
+      if (*err != hipSuccess) break;
+    }
+    return NBC_OK;
+  }
   *err = launch_conv_dma(a, prec, tile, s);
   return NBC_OK;
 }
@@ -408,6 +611,11 @@ const char* kernel_name(OpKind k) {
     case OP_CONCAT: return "concat";
     case OP_BN_STATS: return "bn_stats";
     case OP_BN_APPLY: return "bn_apply";
+    case OP_DWCONV: return "dwconv";
+    case OP_SE_EXCITE: return "se_excite";
+    case OP_GATE_WEIGHTS: return "gate_weights";
+    case OP_SWISH: return "swish";
+    case OP_POOL_ANY: return "pool";
     default: return "upsample_argmax";
   }
 }
@@ -455,6 +663,8 @@ int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int 
   if (!c || !dev_blob) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: null argument");
   if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown precision");
   if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown architecture");
+  if (is_effnet(arch) && precision != NBC_PREC_FP32)
+    return set_error(NBC_ERR_INVALID, std::string("nbc_attach_weights: ") + arch_name(arch) + " runs in NBC_PREC_FP32 (fp32) only");
   PackedLayout L = packed_layout(precision, arch);
   if (bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: blob smaller than the packed layout");
   if (reinterpret_cast<uintptr_t>(dev_blob) % 256 != 0)
@@ -469,7 +679,10 @@ int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int 
                                       "(trailer mismatch)");
   if (c->owned_weights && c->owned_weights != dev_blob) { (void)hipFree(c->owned_weights); c->owned_weights = nullptr; }
   c->pack_flags = meta[1];
-  c->act_exp.assign(meta + kMetaExpBase, meta + kMetaExpBase + nunits);
+  const int nexp = std::min(nunits, kMetaWords - kMetaExpBase);         // EfficientNet's trailer holds no exponents (f32)
+  c->act_exp.assign(meta + kMetaExpBase, meta + kMetaExpBase + nexp);
+  c->act_exp.resize(nunits, 0);
+  if (is_effnet(arch)) std::fill(c->act_exp.begin(), c->act_exp.end(), 0);
   c->weights = static_cast<const unsigned char*>(dev_blob);
   c->layout = L;
   if (c->precision != precision || c->arch != arch) stash_plan(c);      // element size or network changed: another plan
@@ -516,7 +729,9 @@ int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int prec
 
 int nbc_attach_bn_affine(nbc_ctx* c, const float* dev_affine, size_t count) {
   if (!c || !dev_affine) return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: null argument");
-  if (count != nbc_arch_bn_affine_floats(kArchFcn) && count != nbc_arch_bn_affine_floats(kArchDeepLab))
+  bool any = false;
+  for (int a = 0; a < kArchDeepLabEffB0 + 8; ++a) any = any || (known_arch(a) && count == nbc_arch_bn_affine_floats(a));
+  if (!any)
     return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: count is nbc_arch_bn_affine_floats of no architecture");
   if (c->owned_affine && c->owned_affine != dev_affine) {
     NBC_HIP(hipSetDevice(c->device));
@@ -770,10 +985,15 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         break;
       case OP_HEAD1X1: {
         const PackedConv& pc = c->layout.convs[o.unit];
-        if (o.Ci != 512 && o.Ci != 256) return set_error(NBC_ERR_STATE, "classifier.4 expects 512 or 256 input channels");
+        if (o.Ci != 512 && o.Ci != 256 && !is_effnet(c->arch))
+          return set_error(NBC_ERR_STATE, "classifier.4 expects 512 or 256 input channels");
         // also clears this launch's share of the counters (3 per image) when the batch has at most 256 of them
         unsigned long long* cz = counts_dev && 3 * N <= 256 ? reinterpret_cast<unsigned long long*>(counts_dev) : nullptr;
-        if (o.Ci == 512)
+        if (is_effnet(c->arch) && o.Ci != 256)             // FCNHead(inplanes, 3): inplanes / 4 channels, padded
+          e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf]), reinterpret_cast<const float*>(c->weights + pc.w_off),
+                                 reinterpret_cast<const float*>(c->weights + pc.shift_off), lowres, N, o.Ho * o.Wo, o.Ci, cz,
+                                 c->nonfinite, s);
+        else if (o.Ci == 512)
           e = launch_head1x1(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
                              reinterpret_cast<const float*>(c->weights + pc.shift_off),
                              lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
@@ -813,6 +1033,48 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
           e = launch_bn_apply(static_cast<float*>(c->bufs[o.out_buf]), o.res_buf >= 0 ? static_cast<const float*>(c->bufs[o.res_buf]) : nullptr,
                               N, hw, o.Co, scale, shift, o.relu, s);
         }
+        break;
+      }
+      case OP_DWCONV: {
+        const PackedConv& pc = c->layout.convs[o.unit];
+        const ConvUnit& u = conv_units(c->arch)[o.unit];
+        DwArgs a{};
+        a.x = static_cast<const float*>(c->bufs[o.in_buf]);
+        a.w = reinterpret_cast<const float*>(c->weights + pc.w_off);
+        a.scale = reinterpret_cast<const float*>(c->weights + pc.scale_off);
+        a.shift = reinterpret_cast<const float*>(c->weights + pc.shift_off);
+        a.y = static_cast<float*>(c->bufs[o.out_buf]);
+        a.partial = static_cast<float*>(c->bufs[o.ws_buf]);
+        a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.C = o.Co; a.Ho = o.Ho; a.Wo = o.Wo;
+        a.k = u.k; a.stride = u.stride; a.pad_t = u.pad; a.pad_l = u.pad; a.in_swish = u.in_swish ? 1 : 0;
+        e = launch_dwconv(a, s);
+        break;
+      }
+      case OP_SE_EXCITE: {
+        const PackedConv& pr = c->layout.convs[o.unit];
+        const PackedConv& pe = c->layout.convs[o.aux_unit];
+        const ConvUnit& ur = conv_units(c->arch)[o.unit];
+        e = launch_se_excite(static_cast<const float*>(c->bufs[o.in_buf]), N, o.tiles, o.Co, o.Hi * o.Wi,
+                             reinterpret_cast<const float*>(c->weights + pr.w_off), reinterpret_cast<const float*>(c->weights + pr.shift_off),
+                             ur.cout, reinterpret_cast<const float*>(c->weights + pe.w_off),
+                             reinterpret_cast<const float*>(c->weights + pe.shift_off), static_cast<float*>(c->bufs[o.out_buf]), s);
+        break;
+      }
+      case OP_GATE_WEIGHTS: {
+        const PackedConv& pc = c->layout.convs[o.unit];
+        e = launch_gate_weights(reinterpret_cast<const float*>(c->weights + pc.w_off), static_cast<const float*>(c->bufs[o.gate_buf]),
+                                static_cast<float*>(c->bufs[o.ws_buf]), N, o.Co, o.Ci, s);
+        break;
+      }
+      case OP_SWISH:
+        e = launch_swish(static_cast<float*>(c->bufs[o.out_buf]), (size_t)N * o.Ho * o.Wo * o.Co, s);
+        break;
+      case OP_POOL_ANY: {
+        const PackedConv& pc = c->layout.convs[o.unit];
+        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf]), N, o.Hi * o.Wi, o.Ci,
+                            reinterpret_cast<const float*>(c->weights + pc.w_off), reinterpret_cast<const float*>(c->weights + pc.scale_off),
+                            reinterpret_cast<const float*>(c->weights + pc.shift_off), o.Co, static_cast<float*>(c->bufs[o.ws_buf]),
+                            static_cast<float*>(c->bufs[o.out_buf]), s);
         break;
       }
       case OP_UPSAMPLE:
@@ -857,7 +1119,7 @@ static int collect_profile(nbc_ctx* c) {
     std::snprintf(r.kernel, sizeof(r.kernel), "%s", kernel_name(o.kind));
     r.ms = (float)(sum[i] / (double)c->prof_used);
     r.calls = (int32_t)c->prof_used;
-    r.launches = o.kind == OP_ASPP_POOL ? 3 : (o.kind == OP_BN_STATS ? 2 : 1);   // aspp: partial sums, their sum, the 1x1 conv;
+    r.launches = o.kind == OP_ASPP_POOL ? 3 : (o.kind == OP_BN_STATS ? 2 : o.launches);   // aspp: partial sums, their sum, the 1x1 conv;
                                                                                    // bn_stats: partial sums, their sum + the table
     r.flops = o.flops;
     r.bytes = o.bytes;
@@ -1055,19 +1317,32 @@ int nbc_read_activation(nbc_ctx* c, const char* name, float* dst_host, size_t ca
   const Op& o = c->plan.ops[it->second];
   if (o.out_buf < 0) return set_error(NBC_ERR_INVALID, "nbc_read_activation: op has no activation buffer");
   const int N = c->plan.N;
-  const size_t elems = (size_t)N * o.Ho * o.Wo * o.Co;
+  const int creal = o.creal > 0 ? o.creal : o.Co;     // EfficientNet: the pad channels stay behind
+  const size_t elems = (size_t)N * o.Ho * o.Wo * creal;
   if (capacity < elems) return set_error(NBC_ERR_INVALID, "nbc_read_activation: destination too small");
   NBC_HIP(hipSetDevice(c->device));
   float* tmp = nullptr;
   NBC_HIP(hipMalloc((void**)&tmp, elems * sizeof(float)));
-  hipError_t e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf], tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(dst_host, tmp, elems * sizeof(float), hipMemcpyDeviceToHost);
+  hipError_t e = hipSuccess;
+  if (creal == o.Co) {
+    e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf], tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(dst_host, tmp, elems * sizeof(float), hipMemcpyDeviceToHost);
+  } else {                                             // NCHW of the padded tensor, then each image's first creal channels
+    (void)hipFree(tmp);
+    tmp = nullptr;
+    const size_t img = (size_t)o.Ho * o.Wo * o.Co;
+    NBC_HIP(hipMalloc((void**)&tmp, (size_t)N * img * sizeof(float)));
+    e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf], tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
+    for (int n = 0; n < N && e == hipSuccess; ++n)
+      e = hipMemcpy(dst_host + (size_t)n * o.Ho * o.Wo * creal, tmp + n * img, (size_t)o.Ho * o.Wo * creal * sizeof(float),
+                    hipMemcpyDeviceToHost);
+  }
   (void)hipFree(tmp);
   if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_read_activation: ") + hipGetErrorString(e));
   int a = 0;
   if (stored_exponent(c, o.name, &a) && a != 0)        // f16x2: the tensor as the network defines it (power of two taken off, exact)
     for (size_t i = 0; i < elems; ++i) dst_host[i] = std::ldexp(dst_host[i], -a);
-  if (shape) { shape[0] = N; shape[1] = o.Co; shape[2] = o.Ho; shape[3] = o.Wo; }
+  if (shape) { shape[0] = N; shape[1] = creal; shape[2] = o.Ho; shape[3] = o.Wo; }
   return NBC_OK;
 }
 

@@ -1,4 +1,5 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip, aspp.hip and bn_stats.hip).
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
+// efficientnet.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,6 +86,38 @@ hipError_t launch_bn_stats(const float* y, int N, int hw, int C, const float* ga
                            float* shift, hipStream_t s);
 hipError_t launch_bn_apply(float* y, const float* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
                            hipStream_t s);
+// EfficientNet (efficientnet.hip), f32 NHWC, C a multiple of 64.
+// Depthwise k x k conv (k 3 / 5, stride 1 / 2) of x [N][Hi][Wi][C] with weights [k*k][C], top / left pads pad_t / pad_l
+// (a tap outside the image reads 0), y [N][Ho][Wo][C] = swish(fma(acc, scale, shift)); in_swish: x is stored before its
+// swish, applied as it is read.  partial [N][dwconv_tiles(stride, Ho, Wo)][C]: per tile the sum of its outputs (the SE
+// squeeze's first level).
+struct DwArgs {
+  const float* x;
+  const float* w;
+  const float* scale;
+  const float* shift;
+  float* y;
+  float* partial;
+  int N, Hi, Wi, C, Ho, Wo, k, stride, pad_t, pad_l, in_swish;
+};
+int dwconv_tiles_x(int Wo);
+int dwconv_tiles(int stride, int Ho, int Wo);
+hipError_t launch_dwconv(const DwArgs& a, hipStream_t s);
+// Per image: mean = (sum of the tiles' partials in tile order) / hw, r = swish(wr [cse][C] . mean + br),
+// gate [N][C] = sigmoid(we [C][cse] . r + be).
+hipError_t launch_se_excite(const float* partial, int N, int tiles, int C, int hw, const float* wr, const float* br, int cse,
+                            const float* we, const float* be, float* gate, hipStream_t s);
+// wg [N][Co][Ci] = w [Co][Ci] * gate [N][Ci] (the project conv's weights, gated per image)
+hipError_t launch_gate_weights(const float* w, const float* gate, float* wg, int N, int Co, int Ci, hipStream_t s);
+// y = swish(y) in place, elems a multiple of 4
+hipError_t launch_swish(float* y, size_t elems, hipStream_t s);
+// DeepLabHead's pooling branch for any cin: partial N * pool_any_slices(hw) * cin floats; y [N][cout] f32
+int pool_any_slices(int hw);
+hipError_t launch_pool_any(const float* x, int N, int hw, int cin, const float* w, const float* scale, const float* shift, int cout,
+                           float* partial, float* y, hipStream_t s);
+// classifier.4 with cin a multiple of 64, f32 (the contract of launch_head1x1)
+hipError_t launch_head1x1_any(const float* x, const float* w, const float* bias, float* y, int N, int hw, int cin,
+                              unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
 // Bicubic (A=-0.75, align_corners=False) upsample of f32 NCHW [N,3,h,w] to HxW, fused with the
 // per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,

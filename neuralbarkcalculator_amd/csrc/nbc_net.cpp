@@ -17,7 +17,107 @@
 
 namespace nbc {
 
+// EfficientNet-b{n} as efficientnet_pytorch 0.7 builds it (EfficientNet.from_pretrained, extract_features), under the
+// heads of models.py (FCNHead / DeepLabHead on efficientnet_inplanes[n]).  Stages (repeats, k, stride, expand, in, out), SE
+// ratio 0.25 everywhere; per variant (width, depth, native size).  Every convolution pads TF-"same" for the NATIVE image
+// size, fixed when the model is built (Conv2dStaticSamePadding): pad = max((ceil(i/s) - 1) s + k - i, 0), pad // 2 before,
+// the rest after, i the native size at that conv (ceil-divided by every stride before it).
+namespace {
+struct EffStage { int repeats, k, stride, expand, cin, cout; };
+constexpr EffStage kEffStages[7] = {{1, 3, 1, 1, 32, 16},  {2, 3, 2, 6, 16, 24},   {2, 5, 2, 6, 24, 40},  {3, 3, 2, 6, 40, 80},
+                                    {3, 5, 1, 6, 80, 112}, {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
+struct EffParams { double width, depth; int native; };
+constexpr EffParams kEffParams[8] = {{1.0, 1.0, 224}, {1.0, 1.1, 240}, {1.1, 1.2, 260}, {1.2, 1.4, 300},
+                                     {1.4, 1.8, 380}, {1.6, 2.2, 456}, {1.8, 2.6, 528}, {2.0, 3.1, 600}};
+int eff_round_filters(int f, double width) {
+  const double x = f * width;
+  int nf = std::max(8, (int)(x + 4) / 8 * 8);
+  if (nf < 0.9 * x) nf += 8;
+  return nf;
+}
+int pad64(int c) { return (c + kEffChannelPad - 1) / kEffChannelPad * kEffChannelPad; }
+// TF "same" pads for an input of native size i: (before, after)
+void same_pads(int i, int k, int s, int* before, int* after) {
+  const int o = (i + s - 1) / s;
+  const int p = std::max((o - 1) * s + k - i, 0);
+  *before = p / 2;
+  *after = p - p / 2;
+}
+}  // namespace
+
+static void build_effnet_units(int arch, std::vector<ConvUnit>& u) {
+  const EffParams P = kEffParams[effnet_variant(arch)];
+  const std::string m = "backbone.model.";
+  auto unit = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int s, int pb, int pa, int kind,
+                  bool swish, bool bias, bool residual, int block) {
+    ConvUnit c{name, bn, cin, cout, k, s, pb, 1, false, bias, residual, 0};
+    c.kind = kind; c.pad_after = pa; c.swish = swish; c.eps = kBnEpsEffNet; c.block = block;
+    c.cin_pad = kind == kUnitSeExpand ? cin : pad64(cin);
+    c.cout_pad = kind == kUnitSeReduce ? cout : pad64(cout);
+    if (cin == 3) c.cin_pad = 4;                          // the ingested image: one 16-byte pixel
+    u.push_back(c);
+  };
+  int size = P.native, pb, pa;
+  const int stem = eff_round_filters(32, P.width);
+  same_pads(size, 3, 2, &pb, &pa);
+  unit(m + "_conv_stem", m + "_bn0", 3, stem, 3, 2, pb, pa, kUnitConv, true, false, false, -1);
+  size = (size + 1) / 2;
+  int bi = 0;
+  bool prev_swish = true;                                 // the tensor the next block reads is stored before its swish
+  for (const EffStage& st : kEffStages) {
+    const int reps = (int)std::ceil(P.depth * st.repeats);
+    for (int r = 0; r < reps; ++r, ++bi) {
+      const int cin = eff_round_filters(r == 0 ? st.cin : st.cout, P.width), cout = eff_round_filters(st.cout, P.width);
+      const int s = r == 0 ? st.stride : 1, cexp = cin * st.expand;
+      const std::string b = m + "_blocks." + std::to_string(bi) + ".";
+      if (st.expand != 1) unit(b + "_expand_conv", b + "_bn0", cin, cexp, 1, 1, 0, 0, kUnitConv, true, false, false, bi);
+      same_pads(size, st.k, s, &pb, &pa);
+      unit(b + "_depthwise_conv", b + "_bn1", cexp, cexp, st.k, s, pb, pa, kUnitDepthwise, true, false, false, bi);
+      u.back().in_swish = st.expand != 1 || prev_swish;
+      size = (size + s - 1) / s;
+      const int cse = std::max(1, (int)(cin * 0.25));
+      unit(b + "_se_reduce", "", cexp, cse, 1, 1, 0, 0, kUnitSeReduce, true, true, false, bi);
+      unit(b + "_se_expand", "", cse, cexp, 1, 1, 0, 0, kUnitSeExpand, false, true, false, bi);
+      unit(b + "_project_conv", b + "_bn2", cexp, cout, 1, 1, 0, 0, kUnitConv, false, false, s == 1 && cin == cout, bi);
+      prev_swish = false;
+    }
+  }
+  const int inplanes = eff_round_filters(1280, P.width);
+  unit(m + "_conv_head", m + "_bn1", eff_round_filters(320, P.width), inplanes, 1, 1, 0, 0, kUnitConv, true, false, false, -1);
+  // the heads: torchvision's modules, BatchNorm eps 1e-5, channels padded like the trunk's
+  auto head = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int pad, bool relu, bool bias,
+                  bool pooled) {
+    ConvUnit c{name, bn, cin, cout, k, 1, pad, k == 3 ? pad : 1, relu, bias, false, 0, pooled};   // the 3x3s: dilation = pad
+    c.cin_pad = pad64(cin);
+    c.cout_pad = bn.empty() || pooled ? cout : pad64(cout);
+    u.push_back(c);
+  };
+  if (is_deeplab_head(arch)) {
+    const int B = kAsppBranchCh;
+    head("classifier.0.convs.0.0", "classifier.0.convs.0.1", inplanes, B, 1, 0, true, false, false);
+    const int rates[3] = {12, 24, 36};
+    for (int i = 0; i < 3; ++i) {
+      const std::string p = "classifier.0.convs." + std::to_string(i + 1);
+      head(p + ".0", p + ".1", inplanes, B, 3, rates[i], true, false, false);
+    }
+    head("classifier.0.convs.4.1", "classifier.0.convs.4.2", inplanes, B, 1, 0, true, false, true);
+    head("classifier.0.project.0", "classifier.0.project.1", 5 * B, B, 1, 0, true, false, false);
+    head("classifier.1", "classifier.2", B, B, 3, 1, true, false, false);
+    head("classifier.4", "", B, kNumClasses, 1, 0, false, true, false);
+    return;
+  }
+  head("classifier.0", "classifier.1", inplanes, inplanes / 4, 3, 1, true, false, false);
+  head("classifier.4", "", inplanes / 4, kNumClasses, 1, 0, false, true, false);
+}
+
+int effnet_inplanes(int arch) { return is_effnet(arch) ? eff_round_filters(1280, kEffParams[effnet_variant(arch)].width) : 0; }
+
 static std::vector<ConvUnit> build_units(int arch) {
+  if (is_effnet(arch)) {
+    std::vector<ConvUnit> e;
+    build_effnet_units(arch, e);
+    return e;
+  }
   std::vector<ConvUnit> u;
   u.push_back({"backbone.conv1", "backbone.bn1", 3, 64, 7, 2, 3, 1, true, false, false, 0});
   int inplanes = 64, dilation = 1;
@@ -64,9 +164,15 @@ static std::vector<ConvUnit> build_units(int arch) {
   return u;
 }
 
+static int arch_of_slot(int slot) { return slot < kNumArchs ? slot : kArchFcnEffB0 + (slot - kNumArchs); }
+
 const std::vector<ConvUnit>& conv_units(int arch) {
-  static const std::vector<ConvUnit> u[kNumArchs] = {build_units(kArchFcn), build_units(kArchDeepLab)};
-  return u[arch == kArchDeepLab ? kArchDeepLab : kArchFcn];
+  static const std::vector<std::vector<ConvUnit>> u = [] {
+    std::vector<std::vector<ConvUnit>> t;
+    for (int slot = 0; slot < kArchSlots; ++slot) t.push_back(build_units(arch_of_slot(slot)));
+    return t;
+  }();
+  return u[known_arch(arch) ? arch_slot(arch) : 0];
 }
 
 static std::vector<StateKey> build_keys(int arch) {
@@ -95,7 +201,12 @@ static std::vector<StateKey> build_keys(int arch) {
     keys.push_back(k);
   };
   for (const ConvUnit* c : ordered) {
-    add(c->name + ".weight", {c->cout, c->cin, c->k, c->k}, 0);
+    if (c->name == "classifier.0.convs.0.0" && is_effnet(arch))
+      for (const StateKey& k : unused_keys(arch)) keys.push_back(k);   // the trunk's last entries: _fc (state_dict order)
+    if (c->name == "classifier.0" && is_effnet(arch))
+      for (const StateKey& k : unused_keys(arch)) keys.push_back(k);
+    if (c->kind == kUnitDepthwise) add(c->name + ".weight", {c->cout, 1, c->k, c->k}, 0);   // groups = channels
+    else add(c->name + ".weight", {c->cout, c->cin, c->k, c->k}, 0);
     if (c->bias) add(c->name + ".bias", {c->cout}, 0);
     if (!c->bn.empty()) {
       add(c->bn + ".weight", {c->cout}, 0);
@@ -109,8 +220,31 @@ static std::vector<StateKey> build_keys(int arch) {
 }
 
 const std::vector<StateKey>& state_keys(int arch) {
-  static const std::vector<StateKey> k[kNumArchs] = {build_keys(kArchFcn), build_keys(kArchDeepLab)};
-  return k[arch == kArchDeepLab ? kArchDeepLab : kArchFcn];
+  static const std::vector<std::vector<StateKey>> k = [] {
+    std::vector<std::vector<StateKey>> t;
+    for (int slot = 0; slot < kArchSlots; ++slot) t.push_back(build_keys(arch_of_slot(slot)));
+    return t;
+  }();
+  return k[known_arch(arch) ? arch_slot(arch) : 0];
+}
+
+const std::vector<StateKey>& unused_keys(int arch) {
+  // EfficientNet's ImageNet classifier: Linear(inplanes, 1000), in the checkpoint but read by nothing (extract_features)
+  static const std::vector<std::vector<StateKey>> k = [] {
+    std::vector<std::vector<StateKey>> t;
+    for (int slot = 0; slot < kArchSlots; ++slot) {
+      const int arch = arch_of_slot(slot);
+      std::vector<StateKey> v;
+      if (is_effnet(arch)) {
+        const int c = effnet_inplanes(arch);
+        v.push_back({"backbone.model._fc.weight", {1000, c, 1, 1}, 2, 0});
+        v.push_back({"backbone.model._fc.bias", {1000, 1, 1, 1}, 1, 0});
+      }
+      t.push_back(v);
+    }
+    return t;
+  }();
+  return k[known_arch(arch) ? arch_slot(arch) : 0];
 }
 
 size_t bn_affine_floats(int arch) {
@@ -129,9 +263,20 @@ PackedLayout packed_layout(int precision, int arch) {
   for (const ConvUnit& c : conv_units(arch)) {
     PackedConv p{};
     p.stem = (c.cin == 3);
-    p.head = c.bn.empty();
+    p.head = c.bn.empty() && c.kind == kUnitConv;
     p.pooled = c.pooled;
-    if (p.pooled) {                    // f32 [cout][cin], f32 scale and shift (the pooled vector is one pixel per image)
+    p.kind = c.kind;
+    if (c.kind != kUnitConv) {         // EfficientNet, f32 only: depthwise [k*k][cout_pad] + (scale, shift); SE [rows][cols] + bias
+      p.cin_pad = c.inc();
+      p.ksteps = 0;
+      p.w_off = off;
+      off = align_up(off + (size_t)(c.kind == kUnitDepthwise ? c.k * c.k : c.outc()) *
+                               (c.kind == kUnitDepthwise ? c.outc() : c.inc()) * 4, 256);
+      p.scale_off = off;
+      if (c.kind == kUnitDepthwise) off = align_up(off + (size_t)c.outc() * 4, 256);
+      p.shift_off = off;
+      off = align_up(off + (size_t)c.outc() * 4, 256);
+    } else if (p.pooled) {                    // f32 [cout][cin], f32 scale and shift (the pooled vector is one pixel per image)
       p.cin_pad = c.cin;
       p.ksteps = 0;
       p.w_off = off;
@@ -140,11 +285,11 @@ PackedLayout packed_layout(int precision, int arch) {
       off = align_up(off + (size_t)c.cout * 4, 256);
       p.shift_off = off;
       off = align_up(off + (size_t)c.cout * 4, 256);
-    } else if (p.head) {               // f32 [3][cin] + bias
-      p.cin_pad = c.cin;
+    } else if (p.head) {               // f32 [3][cin] + bias (EfficientNet: [3][cin_pad], zero beyond cin)
+      p.cin_pad = c.inc();
       p.ksteps = 0;
       p.w_off = off;
-      off = align_up(off + (size_t)c.cout * c.cin * 4, 256);
+      off = align_up(off + (size_t)c.cout * p.cin_pad * 4, 256);
       p.scale_off = off;               // unused
       p.shift_off = off;               // bias
       off = align_up(off + (size_t)c.cout * 4, 256);
@@ -155,15 +300,15 @@ PackedLayout packed_layout(int precision, int arch) {
         p.cin_pad = kChunkBytes / eb;
         p.ksteps = c.k;
       } else {
-        p.cin_pad = c.cin;
-        p.ksteps = c.k * c.k * c.cin * eb / kKStepBytes;
+        p.cin_pad = c.inc();
+        p.ksteps = c.k * c.k * p.cin_pad * eb / kKStepBytes;
       }
       p.w_off = off;
-      off = align_up(off + (size_t)c.cout * p.ksteps * kKStepBytes, 256);
+      off = align_up(off + (size_t)c.outc() * p.ksteps * kKStepBytes, 256);
       p.scale_off = off;
-      off = align_up(off + (size_t)c.cout * 4, 256);
+      off = align_up(off + (size_t)c.outc() * 4, 256);
       p.shift_off = off;
-      off = align_up(off + (size_t)c.cout * 4, 256);
+      off = align_up(off + (size_t)c.outc() * 4, 256);
     }
     L.convs.push_back(p);
   }
@@ -465,8 +610,48 @@ int nbc_split_f16x2(const float* x, size_t n, uint16_t* h0, uint16_t* h1) {
   return NBC_OK;
 }
 
+// The low-resolution size of an EfficientNet network: its five stride-2 convolutions with their fixed pads
+static void effnet_lowres(int arch, int* H, int* W) {
+  for (const ConvUnit& c : conv_units(arch))
+    if (c.stride == 2) {
+      *H = same_out(*H, c.k, 2, c.pad, c.pad_end());
+      *W = same_out(*W, c.k, 2, c.pad, c.pad_end());
+    }
+}
+
+int nbc_arch_lowres_size(int arch, int H, int W, int* h, int* w) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_arch_lowres_size: unknown architecture");
+  if (!is_effnet(arch)) return nbc_lowres_size(H, W, h, w);
+  if (H < 1 || W < 1) return set_error(NBC_ERR_INVALID, "nbc_arch_lowres_size: H,W must be >= 1");
+  int a = H, b = W;
+  effnet_lowres(arch, &a, &b);
+  if (a < 1 || b < 1) return set_error(NBC_ERR_INVALID, "nbc_arch_lowres_size: the image is too small for the network");
+  if (h) *h = a;
+  if (w) *w = b;
+  return NBC_OK;
+}
+
+int nbc_arch_conv_ext(int arch, int index, nbc_conv_ext* out) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_arch_conv_ext: unknown architecture");
+  const auto& u = conv_units(arch);
+  if (!out || index < 0 || index >= (int)u.size()) return set_error(NBC_ERR_INVALID, "nbc_arch_conv_ext: bad index");
+  const ConvUnit& c = u[index];
+  std::memset(out, 0, sizeof(*out));
+  out->kind = c.kind;
+  out->pad_before = c.pad;
+  out->pad_after = c.pad_end();
+  out->act = c.swish ? 2 : (c.relu ? 1 : 0);
+  out->cin_pad = c.inc();
+  out->cout_pad = c.outc();
+  out->block = c.block;
+  out->in_swish = c.in_swish;
+  out->eps = c.eps;
+  return NBC_OK;
+}
+
 size_t nbc_arch_packed_weights_bytes(int precision, int arch) {
   if (!known_precision(precision) || !known_arch(arch)) return 0;
+  if (is_effnet(arch) && precision != NBC_PREC_FP32) return 0;   // EfficientNet runs NBC_PREC_FP32 only
   return packed_layout(precision, arch).total_bytes;
 }
 size_t nbc_packed_weights_bytes(int precision) { return nbc_arch_packed_weights_bytes(precision, kArchFcn); }
@@ -475,7 +660,15 @@ size_t nbc_packed_weights_bytes(int precision) { return nbc_arch_packed_weights_
 
 namespace nbc {
 
-const char* arch_name(int arch) { return arch == kArchDeepLab ? "deeplabv3_resnet50" : "fcn_resnet50"; }
+const char* arch_name(int arch) {
+  static const std::vector<std::string> names = [] {
+    std::vector<std::string> v = {"fcn_resnet50", "deeplabv3_resnet50"};
+    for (int n = 0; n < 8; ++n) v.push_back("fcn_efficientnet_b" + std::to_string(n));
+    for (int n = 0; n < 8; ++n) v.push_back("deeplabv3_efficientnet_b" + std::to_string(n));
+    return v;
+  }();
+  return names[known_arch(arch) ? arch_slot(arch) : 0].c_str();
+}
 
 // The strict key / shape check of nn.Module.load_state_dict (models.py:222) against architecture `arch`: NBC_OK and the
 // tensors by name, or NBC_ERR_KEYS with the missing / unexpected / mis-shaped entries (NBC_ERR_INVALID for a nameless one).
@@ -485,7 +678,7 @@ static int check_state_dict(const nbc_tensor* tensors, int n, int arch, std::map
   std::string unexpected, missing, badshape;
   std::set<std::string> expected;
   for (const StateKey& k : state_keys(arch)) expected.insert(k.name);
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; i < n; ++i) {   // (state_keys holds unused_keys too: strict loading takes them, the packer skips them)
     if (!tensors[i].name) { *msg_out = "tensor without a name"; return NBC_ERR_INVALID; }
     if (!expected.count(tensors[i].name)) unexpected += std::string(" \"") + tensors[i].name + "\"";
     given[tensors[i].name] = &tensors[i];
@@ -510,6 +703,61 @@ static int check_state_dict(const nbc_tensor* tensors, int n, int arch, std::map
   return NBC_OK;
 }
 
+// EfficientNet blobs (NBC_PREC_FP32 only): every stored tensor has outc() channels, the rows and columns beyond the
+// checkpoint's channels stay zero (weights, scale, shift, bias), so pad channels hold exactly 0 through swish, the SE gate
+// and the residual.  The trailer holds no exponents (f32: all zero).
+static void pack_effnet(const std::map<std::string, const nbc_tensor*>& given, int arch, const PackedLayout& L, unsigned char* base) {
+  const auto& units = conv_units(arch);
+  auto f32 = [&](const std::string& key) { return static_cast<const float*>(given.at(key)->data); };
+  for (size_t ui = 0; ui < units.size(); ++ui) {
+    const ConvUnit& c = units[ui];
+    const PackedConv& p = L.convs[ui];
+    const float* w = f32(c.name + ".weight");
+    float* pw = reinterpret_cast<float*>(base + p.w_off);
+    if (c.kind == kUnitDepthwise) {                     // [k*k][cout_pad]: a tap's channels contiguous
+      for (int o = 0; o < c.cout; ++o)
+        for (int t = 0; t < c.k * c.k; ++t) pw[(size_t)t * c.outc() + o] = w[(size_t)o * c.k * c.k + t];
+    } else if (c.kind == kUnitSeReduce) {               // [cse][cin_pad]
+      for (int j = 0; j < c.cout; ++j)
+        for (int i = 0; i < c.cin; ++i) pw[(size_t)j * c.inc() + i] = w[(size_t)j * c.cin + i];
+    } else if (c.kind == kUnitSeExpand) {               // [cout_pad][cse]
+      std::memcpy(pw, w, (size_t)c.cout * c.cin * 4);
+    } else if (p.head) {                                // classifier.4: [3][cin_pad]
+      for (int o = 0; o < c.cout; ++o)
+        for (int i = 0; i < c.cin; ++i) pw[(size_t)o * c.inc() + i] = w[(size_t)o * c.cin + i];
+    } else if (p.pooled) {                              // [cout][cin], cin = inplanes (a multiple of 64)
+      std::memcpy(pw, w, (size_t)c.cout * c.cin * 4);
+    } else {                                            // conv_dma panels [cout_pad][ksteps * 32 floats]
+      const size_t row = (size_t)p.ksteps * kKStepBytes / 4;
+      for (int o = 0; o < c.cout; ++o)
+        for (int kh = 0; kh < c.k; ++kh)
+          for (int kw = 0; kw < c.k; ++kw)
+            for (int ci = 0; ci < c.cin; ++ci) {
+              const size_t kidx = p.stem ? (size_t)(kh * 8 + kw) * p.cin_pad + ci : (size_t)(kh * c.k + kw) * p.cin_pad + ci;
+              pw[o * row + kidx] = w[(((size_t)o * c.cin + ci) * c.k + kh) * c.k + kw];
+            }
+    }
+    if (c.bias) std::memcpy(base + p.shift_off, f32(c.name + ".bias"), (size_t)c.cout * 4);
+    if (c.bn.empty()) continue;
+    const float* g = f32(c.bn + ".weight");
+    const float* b = f32(c.bn + ".bias");
+    const float* mu = f32(c.bn + ".running_mean");
+    const float* var = f32(c.bn + ".running_var");
+    float* scale = reinterpret_cast<float*>(base + p.scale_off);
+    float* shift = reinterpret_cast<float*>(base + p.shift_off);
+    for (int o = 0; o < c.cout; ++o) {                  // eval-mode BatchNorm as ATen applies it, with the unit's eps
+      const float alpha = g[o] * (1.0f / std::sqrt(var[o] + c.eps));
+      scale[o] = alpha;
+      shift[o] = b[o] - mu[o] * alpha;
+    }
+  }
+  int32_t* meta = reinterpret_cast<int32_t*>(base + L.meta_off);
+  meta[0] = kMetaMagic;
+  meta[1] = 0;
+  meta[2] = (int32_t)units.size();
+  meta[kMetaArch] = arch;
+}
+
 }  // namespace nbc
 
 extern "C" {
@@ -518,6 +766,8 @@ int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int a
   if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: unknown architecture");
   if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: unknown precision");
   if (!tensors || n < 0 || !blob) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: null argument");
+  if (is_effnet(arch) && precision != NBC_PREC_FP32)
+    return set_error(NBC_ERR_INVALID, std::string("nbc_pack_weights: ") + arch_name(arch) + " runs in NBC_PREC_FP32 (fp32) only");
   const PackedLayout L = packed_layout(precision, arch);
   if (blob_bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_pack_weights: blob too small");
 
@@ -530,6 +780,10 @@ int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int a
 
   std::memset(blob, 0, L.total_bytes);
   unsigned char* base = static_cast<unsigned char*>(blob);
+  if (is_effnet(arch)) {
+    pack_effnet(given, arch, L, base);
+    return NBC_OK;
+  }
   const int eb = elem_bytes(precision);
   const auto& units = conv_units(arch);
   int flags = 0;
@@ -615,7 +869,7 @@ int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int a
   meta[1] = flags;
   meta[2] = (int32_t)units.size();
   meta[kMetaArch] = arch;                                               // 0 for FCN: what the word always held
-  for (size_t ui = 0; ui < units.size(); ++ui) meta[kMetaExpBase + ui] = out_exp[ui];
+  for (size_t ui = 0; ui < units.size() && kMetaExpBase + ui < (size_t)kMetaWords; ++ui) meta[kMetaExpBase + ui] = out_exp[ui];
   return NBC_OK;
 }
 
@@ -626,7 +880,8 @@ int nbc_pack_weights(const nbc_tensor* tensors, int n, int precision, void* blob
 int nbc_arch_of_state_dict(const nbc_tensor* tensors, int n) {
   if (!tensors || n < 0) return set_error(NBC_ERR_INVALID, "nbc_arch_of_state_dict: null argument");
   std::string msg;
-  for (int arch = 0; arch < kNumArchs; ++arch) {
+  for (int slot = 0; slot < kArchSlots; ++slot) {
+    const int arch = arch_of_slot(slot);
     const int rc = check_state_dict(tensors, n, arch, nullptr, &msg);
     if (rc == NBC_OK) return arch;
     if (rc == NBC_ERR_INVALID) return set_error(rc, "nbc_arch_of_state_dict: " + msg);
@@ -637,7 +892,7 @@ int nbc_arch_of_state_dict(const nbc_tensor* tensors, int n) {
 }
 
 int nbc_packed_weights_flags_arch(const void* blob, size_t blob_bytes, int precision, int arch) {
-  if (!known_precision(precision) || !known_arch(arch) || !blob)
+  if (!known_precision(precision) || !known_arch(arch) || !blob || (is_effnet(arch) && precision != NBC_PREC_FP32))
     return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: bad argument");
   const PackedLayout L = packed_layout(precision, arch);
   if (blob_bytes < L.total_bytes) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_flags: blob too small");
@@ -683,7 +938,9 @@ int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision)
 
 int nbc_packed_weights_arch(const void* blob, size_t blob_bytes, int precision) {
   if (!known_precision(precision) || !blob) return set_error(NBC_ERR_INVALID, "nbc_packed_weights_arch: bad argument");
-  for (int arch = 0; arch < kNumArchs; ++arch) {
+  for (int slot = 0; slot < kArchSlots; ++slot) {
+    const int arch = arch_of_slot(slot);
+    if (is_effnet(arch) && precision != NBC_PREC_FP32) continue;
     const PackedLayout L = packed_layout(precision, arch);
     if (blob_bytes != L.total_bytes) continue;
     const int32_t* meta = reinterpret_cast<const int32_t*>(static_cast<const unsigned char*>(blob) + L.meta_off);

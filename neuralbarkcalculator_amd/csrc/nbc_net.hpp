@@ -19,9 +19,21 @@ constexpr int kChunkBytes = 16;    // one lane-load
 // Architectures (NBC_ARCH_* of nbc.h): the trunk is shared, the head differs.
 constexpr int kArchFcn = 0;        // fcn_resnet50: FCNHead(2048, 3)
 constexpr int kArchDeepLab = 1;    // deeplabv3_resnet50: DeepLabHead(2048, 3) = ASPP(2048, [12, 24, 36]) + 3x3 conv
-constexpr int kNumArchs = 2;
-inline bool known_arch(int arch) { return arch >= 0 && arch < kNumArchs; }
+constexpr int kNumArchs = 2;       // the ResNet-50 pair; the EfficientNet ids follow (2 stays unused)
+// EfficientNet trunks (efficientnet_pytorch 0.7 extract_features) under FCNHead / DeepLabHead(inplanes, 3): n = 0..7.
+constexpr int kArchFcnEffB0 = 16;       // fcn_efficientnet(n): 16 + n
+constexpr int kArchDeepLabEffB0 = 24;   // deeplabv3_efficientnet(n): 24 + n
+inline bool is_effnet(int arch) { return arch >= kArchFcnEffB0 && arch < kArchDeepLabEffB0 + 8; }
+inline int effnet_variant(int arch) { return arch & 7; }
+inline bool is_deeplab_head(int arch) { return arch == kArchDeepLab || (arch >= kArchDeepLabEffB0 && arch < kArchDeepLabEffB0 + 8); }
+inline bool known_arch(int arch) { return (arch >= 0 && arch < kNumArchs) || is_effnet(arch); }
+constexpr int kArchSlots = kNumArchs + 16;   // table slots: the two ResNet-50 networks, then 16 + n, 24 + n
+inline int arch_slot(int arch) { return is_effnet(arch) ? kNumArchs + (arch - kArchFcnEffB0) : (arch == kArchDeepLab ? 1 : 0); }
+constexpr float kBnEpsEffNet = 1e-3f;   // every BatchNorm of the EfficientNet trunk (the heads keep torch's 1e-5)
+constexpr int kEffChannelPad = 64;      // EfficientNet tensors: channels zero-padded to a multiple of this
 constexpr int kAsppBranchCh = 256;  // channels of every ASPP branch; the concat holds five of them
+
+enum { kUnitConv = 0, kUnitDepthwise = 1, kUnitSeReduce = 2, kUnitSeExpand = 3 };
 
 struct ConvUnit {
   std::string name;      // "backbone.layer1.0.conv1"
@@ -30,6 +42,17 @@ struct ConvUnit {
   bool relu, bias, residual;
   int block_first;       // 1 when this is conv1 of a bottleneck (plan building)
   bool pooled = false;   // the ASPP pooling branch: global average pool, then this 1x1 conv in f32 (aspp.hip)
+  // EfficientNet (all defaults for the ResNet-50 networks)
+  int kind = kUnitConv;  // kUnit*
+  int pad_after = -1;    // bottom / right pad (TF "same": may differ from `pad`, the top / left one); -1 = pad
+  bool swish = false;    // BatchNorm, then swish (stem and expand: deferred into the depthwise kernel's staging)
+  float eps = kBnEps;
+  int cin_pad = 0, cout_pad = 0;   // channels of the stored tensors (0 = cin / cout)
+  int block = -1;        // MBConv block index
+  bool in_swish = false; // depthwise: its input is a stored pre-swish tensor (stem or expand output)
+  int inc() const { return cin_pad ? cin_pad : cin; }
+  int outc() const { return cout_pad ? cout_pad : cout; }
+  int pad_end() const { return pad_after < 0 ? pad : pad_after; }
 };
 
 struct StateKey {
@@ -41,6 +64,19 @@ struct StateKey {
 
 const std::vector<ConvUnit>& conv_units(int arch = kArchFcn);
 const std::vector<StateKey>& state_keys(int arch = kArchFcn);
+
+// The trunk's extra keys that no unit reads (EfficientNet: the ImageNet classifier _fc.weight / _fc.bias).
+const std::vector<StateKey>& unused_keys(int arch);
+// Channels of the EfficientNet trunk's output (models.py efficientnet_inplanes), 0 for another architecture.
+int effnet_inplanes(int arch);
+const char* arch_name(int arch);
+
+// Output size of a convolution with pads (before, after) on an x-pixel input, floor((x + before + after - k) / s) + 1; 0 when the
+// padded input is smaller than the kernel
+inline int same_out(int x, int k, int s, int before, int after) {
+  const int t = x + before + after - k;
+  return t < 0 ? 0 : t / s + 1;
+}
 
 // Floats of the per-image BatchNorm affine array (nbc_pack_bn_affine): gamma then beta of every conv unit with a BatchNorm,
 // in conv-unit order; the unit's pair sits at the running sum of 2 * cout over the units before it.
@@ -61,6 +97,8 @@ struct PackedConv {
   bool stem;             // one 16-byte chunk per tap (cin_pad*elem = 16 bytes)
   bool head;             // classifier.4: weights kept f32 [3][cin], shift = bias
   bool pooled;           // ASPP pooling branch: weights kept f32 [cout][cin], f32 (scale, shift)
+  int kind;              // kUnit*: depthwise [k*k][cout_pad] f32 + (scale, shift); SE reduce [cout][cin_pad] f32 + bias at
+                         // shift_off; SE expand [cout_pad][cin] f32 + bias at shift_off
 };
 
 // Trailer of the blob: what a rank that receives the blob by broadcast must know besides the panels.

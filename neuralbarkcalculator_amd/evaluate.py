@@ -44,8 +44,8 @@ from typing import List, Tuple
 import numpy as np
 
 from . import metrics
-from .predict import (BN_STATS, AbandonMarker, NonFiniteLogits, _decode_rgb, _host_workers, gather_rows, launch_ranks,
-                      list_images, resolve_bn_stats, shard_by_pixels)
+from .predict import (ARCH_CHOICES, BN_STATS, AbandonMarker, NonFiniteLogits, _decode_rgb, _host_workers, check_bn_stats_arch,
+                      gather_rows, launch_ranks, list_images, resolve_arch_precision, resolve_bn_stats, shard_by_pixels)
 
 ROW_WIDTH = 22                                   # (global_idx, H, W, status, conf_raw[9], conf_clean[9])
 STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
@@ -113,7 +113,7 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
 
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
-                    streams: int = None, arch: str = "auto", bn_stats: str = "running") -> dict:
+                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -124,7 +124,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     from concurrent.futures import ThreadPoolExecutor
     import torch
     from .model import MODELS, FCNResNet50
-    from .predict import check_bn_stats_arch, resolve_arch
+    from .predict import check_bn_stats_arch, resolve_arch, resolve_arch_precision
     t_start = time.perf_counter()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -153,6 +153,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
     arch = resolve_arch(arch, state_dict, dist, dev)
     check_bn_stats_arch(bn_stats, arch)
+    precision = resolve_arch_precision(arch, precision, precision_auto)   # EfficientNet: fp32
     model = MODELS[arch](precision).set_bn_statistics(bn_stats).to(dev)
     if rank == 0:
         model.load_state_dict(state_dict)
@@ -362,7 +363,7 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
     ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2, 8 in bf16)")
     ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
-    ap.add_argument("--arch", choices=["auto", "fcn_resnet50", "deeplabv3_resnet50"], default="auto",
+    ap.add_argument("--arch", choices=["auto"] + list(ARCH_CHOICES), default="auto",
                     help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
                     help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
@@ -372,6 +373,9 @@ def main(argv=None):
     args = ap.parse_args(raw)
     try:
         args.precision = resolve_bn_stats(args.bn_stats, args.precision)
+        if args.arch != "auto":
+            check_bn_stats_arch(args.bn_stats, args.arch)
+        args.precision = resolve_arch_precision(args.arch, args.precision)
     except ValueError as e:
         ap.error(str(e))
     if args.exclude_nodes:
@@ -384,7 +388,7 @@ def main(argv=None):
     if args.precision == "auto":
         stats = None
         try:
-            stats = evaluate_folder(args.root_path, args.model_path, "f16x2", idx, **kw)
+            stats = evaluate_folder(args.root_path, args.model_path, "f16x2", idx, precision_auto=True, **kw)
         except NonFiniteLogits as e:                 # raised on every rank alike
             if int(os.environ.get("RANK", "0")) == 0:
                 print("evaluate: %s -- evaluating the folder again on the f32 MFMA" % e, flush=True)

@@ -113,7 +113,7 @@ def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
     rc = lib.nbc_arch_of_state_dict(arr, n)
     if rc < 0:
         _lib.check(rc, "load_state_dict")
-    return topology.ARCHS[rc]
+    return topology.arch_name(rc)
 
 
 class FCNResNet50:
@@ -136,6 +136,9 @@ class FCNResNet50:
     def __init__(self, precision: str = "fp32"):
         if precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
+        if topology.is_efficientnet(self.ARCH) and _PRECISIONS[precision] != _lib.PREC_FP32:
+            raise ValueError("%s runs in precision 'fp32' only, not %r: swish and the SE gate are not positively homogeneous, "
+                             "so f16x2's powers of two cannot be folded into its BatchNorm pairs" % (self.ARCH, precision))
         self._lib = _lib.load()            # fails loudly when libnbc_hip.so is not built
         self.precision = precision
         self._prec = _PRECISIONS[precision]
@@ -193,6 +196,9 @@ class FCNResNet50:
         if mode not in BN_STATISTICS:
             raise ValueError(f"bn_statistics must be one of {sorted(BN_STATISTICS)}, got {mode!r}")
         if mode == "image":
+            if topology.is_efficientnet(self.ARCH):
+                raise ValueError("per-image BatchNorm statistics are refused for %s: they are implemented for fcn_resnet50 "
+                                 "only" % self.ARCH)
             if self.ARCH != "fcn_resnet50":
                 raise ValueError("per-image BatchNorm statistics are refused for %s: its ASPP pooling branch's BatchNorm sees a "
                                  "[1, 256, 1, 1] tensor, which batch statistics cannot normalise (torch raises, and so would "
@@ -234,7 +240,7 @@ class FCNResNet50:
         counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
         lowres = None
         if return_lowres:
-            lh, lw = out_hw(h, w)
+            lh, lw = out_hw(h, w, self.ARCH)
             lowres = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
         self._forward(x, n, h, w, labels=labels, counts=counts, lowres=lowres,
                       exclude_nodes=exclude_nodes and not small_zones)
@@ -245,7 +251,7 @@ class FCNResNet50:
     def lowres_logits(self, x: torch.Tensor) -> torch.Tensor:
         """Output of ``classifier.4`` (models.py:121) before the upsample: f32 ``[N,3,h,w]``."""
         n, h, w = self._check_input(x)
-        lh, lw = out_hw(h, w)
+        lh, lw = out_hw(h, w, self.ARCH)
         lowres = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
         self._forward(x, n, h, w, lowres=lowres)
         return lowres
@@ -366,11 +372,15 @@ class FCNResNet50:
         in HBM) but owns its own context and activation workspace, so the two can run concurrently
         on different HIP streams (pipelined batch-1 serving)."""
         self._require_weights()
-        other = type(self)(self.precision)
+        other = self._like()
         other.bn_statistics = self.bn_statistics
         other.to(self.device)
         other._attach(self._blob_dev, self._affine_dev)
         return other
+
+    def _like(self) -> "FCNResNet50":
+        """A fresh model object of this network and precision."""
+        return type(self)(self.precision)
 
     # ---- multi-GPU: one process per GPU, weights read by one rank only ---------------------
     def broadcast_weights(self, src: int = 0, group=None):
@@ -445,7 +455,7 @@ class FCNResNet50:
         n, h, w = self._check_input(x)
         self.set_keep_activations(True)
         try:
-            self._forward(x, n, h, w, lowres=torch.empty((n, NUM_CLASSES) + out_hw(h, w), dtype=torch.float32, device=self.device))
+            self._forward(x, n, h, w, lowres=torch.empty((n, NUM_CLASSES) + out_hw(h, w, self.ARCH), dtype=torch.float32, device=self.device))
             torch.cuda.synchronize(self.device)
             k = int(self._lib.nbc_arch_num_convs(topology.arch_index(self.ARCH)))
             buf = (C.c_float * k)()
@@ -573,6 +583,8 @@ class FCNResNet50:
             raise RuntimeError(f"unsupported input dtype {x.dtype}")
         if h < 8 or w < 8:
             raise RuntimeError("H and W must be >= 8")
+        if min(out_hw(int(h), int(w), self.ARCH)) < 1:
+            raise RuntimeError("a %dx%d image is too small for %s" % (h, w, self.ARCH))
         if self.bn_statistics == "image" and out_hw(int(h), int(w)) == (1, 1):
             raise ValueError("Expected more than 1 value per channel when training: a %dx%d image has a 1x1 low-resolution "
                              "map, which per-image BatchNorm statistics cannot normalise" % (h, w))
@@ -624,7 +636,49 @@ class DeepLabV3ResNet50(FCNResNet50):
     ARCH = "deeplabv3_resnet50"
 
 
+class FCNEfficientNet(FCNResNet50):
+    """MI355X-native ``fcn_efficientnet(n, dropout)`` (models.py:95-101): the trunk of efficientnet_pytorch 0.7's
+    ``EfficientNet.from_pretrained('efficientnet-b{n}').extract_features`` -- stem, MBConv blocks with depthwise convolutions,
+    swish and squeeze-and-excitation, head conv, output stride 32 -- under ``FCNHead(inplanes, 3)``, then the bicubic x32
+    upsample and argmax.  "fp32" only (``ValueError`` otherwise), running BatchNorm statistics only.  Strict loading takes
+    exactly the variant's keys, the trunk's unused ImageNet classifier (``backbone.model._fc.*``) included."""
+
+    HEAD = "fcn"
+
+    def __init__(self, n: int = 0, precision: str = "fp32"):
+        if int(n) not in range(8):
+            raise ValueError("EfficientNet variant n must be 0..7, got %r" % (n,))
+        self.n = int(n)
+        self.ARCH = "%s_efficientnet_b%d" % ("deeplabv3" if self.HEAD == "deeplab" else "fcn", self.n)
+        super().__init__(precision)
+
+    def _like(self):
+        return type(self)(self.n, self.precision)
+
+
+class DeepLabV3EfficientNet(FCNEfficientNet):
+    """MI355X-native ``deeplabv3_efficientnet(n)`` (models.py:81-87): the EfficientNet-b{n} trunk of ``FCNEfficientNet``
+    under ``DeepLabHead(inplanes, 3)``.  "fp32" only."""
+
+    HEAD = "deeplab"
+
+
+def fcn_efficientnet(n: int, dropout: float = 0.1, precision: str = "fp32") -> FCNEfficientNet:
+    """Factory with the reference's name and arguments (models.py:95).  The reference starts from ImageNet weights that the
+    checkpoint's load_state_dict replaces in full; here the weights come from load_state_dict alone."""
+    del dropout  # identity in eval mode
+    return FCNEfficientNet(n, precision=precision)
+
+
+def deeplabv3_efficientnet(n: int, precision: str = "fp32") -> DeepLabV3EfficientNet:
+    """Factory with the reference's name (models.py:81)."""
+    return DeepLabV3EfficientNet(n, precision=precision)
+
+
 MODELS = {"fcn_resnet50": FCNResNet50, "deeplabv3_resnet50": DeepLabV3ResNet50}
+for _n in range(8):
+    MODELS["fcn_efficientnet_b%d" % _n] = (lambda n: lambda precision="fp32": FCNEfficientNet(n, precision))(_n)
+    MODELS["deeplabv3_efficientnet_b%d" % _n] = (lambda n: lambda precision="fp32": DeepLabV3EfficientNet(n, precision))(_n)
 
 
 def deeplabv3_resnet50(precision: str = "fp32") -> DeepLabV3ResNet50:

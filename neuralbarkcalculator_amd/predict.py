@@ -398,7 +398,7 @@ def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
     loading then refuses a checkpoint of the other one."""
     from . import topology
     if arch != "auto":
-        return topology.ARCHS[topology.arch_index(arch)]
+        return topology.arch_name(topology.arch_index(arch))
     rank = dist.get_rank() if dist is not None else 0
     code, err = -1, None
     if rank == 0:
@@ -418,10 +418,26 @@ def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
         raise err
     if code < 0:
         raise RuntimeError("rank 0 found no architecture matching the checkpoint's keys")
-    return topology.ARCHS[code]
+    return topology.arch_name(code)
+
+
+def resolve_arch_precision(arch: str, precision: str, precision_auto: bool = False) -> str:
+    """The precision a folder driver runs ``arch`` in.  EfficientNet networks run "fp32" only: ``--precision auto`` means
+    "fp32" for them (``precision_auto``: the precision came from auto), an explicit "f16x2" or "bf16" raises ``ValueError``
+    naming fp32.  Every other network keeps ``precision``.  Called with the architecture ``resolve_arch`` returned (every
+    rank alike), or at argument time with a named one."""
+    from . import topology
+    if arch == "auto" or not topology.is_efficientnet(arch) or precision in ("fp32", "auto"):
+        return "fp32" if arch != "auto" and topology.is_efficientnet(arch) else precision
+    if precision_auto:
+        return "fp32"
+    raise ValueError("%s runs in --precision fp32 (or auto) only, not %s: swish and the SE gate are not positively "
+                     "homogeneous, so f16x2's powers of two cannot be folded into its BatchNorm pairs" % (arch, precision))
 
 
 BN_STATS = ("running", "image")
+ARCH_CHOICES = ("fcn_resnet50", "deeplabv3_resnet50") + tuple("fcn_efficientnet_b%d" % n for n in range(8)) + \
+    tuple("deeplabv3_efficientnet_b%d" % n for n in range(8))
 
 
 def resolve_bn_stats(bn_stats: str, precision: str) -> str:
@@ -441,6 +457,10 @@ def resolve_bn_stats(bn_stats: str, precision: str) -> str:
 def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
     """``ValueError`` for ``--bn_stats image`` on a network other than FCN-ResNet-50.  Called with the architecture
     ``resolve_arch`` returned, which every rank holds alike, so every rank refuses alike."""
+    from . import topology
+    if bn_stats == "image" and topology.is_efficientnet(arch):
+        raise ValueError("--bn_stats image is refused for %s: per-image BatchNorm statistics are implemented for fcn_resnet50 "
+                         "only" % arch)
     if bn_stats == "image" and arch != "fcn_resnet50":
         raise ValueError("--bn_stats image is refused for %s: its ASPP pooling branch's BatchNorm sees a [1, 256, 1, 1] tensor, "
                          "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
@@ -470,7 +490,7 @@ def plan_items(root: str) -> List[dict]:
 def predict_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32",
                    exclude_nodes: bool = False, small_zones: bool = True, device_index: int = None,
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
-                   streams: int = None, arch: str = "auto", bn_stats: str = "running") -> dict:
+                   streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -489,7 +509,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     (``FCNResNet50.activation_peaks``: the silent counterpart of the non-finite word, which still rides back with every batch).
     ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.  ``bn_stats``: ``"running"``
     (eval mode) or ``"image"``, the per-image BatchNorm statistics the shipped tool ran with ("fp32", FCN only:
-    ``resolve_bn_stats``, ``check_bn_stats_arch``).
+    ``resolve_bn_stats``, ``check_bn_stats_arch``).  EfficientNet networks run "fp32" (``resolve_arch_precision``;
+    ``precision_auto``: ``precision`` came from ``--precision auto``).
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -528,6 +549,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
     arch = resolve_arch(arch, state_dict, dist, dev)
     check_bn_stats_arch(bn_stats, arch)
+    precision = resolve_arch_precision(arch, precision, precision_auto)
     model = MODELS[arch](precision).set_bn_statistics(bn_stats)
     model.to(dev)
     if rank == 0:
@@ -821,7 +843,7 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
     ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2 in fp32, 8 in bf16)")
     ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
-    ap.add_argument("--arch", choices=["auto", "fcn_resnet50", "deeplabv3_resnet50"], default="auto",
+    ap.add_argument("--arch", choices=["auto"] + list(ARCH_CHOICES), default="auto",
                     help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--autotune", action="store_true",
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
@@ -832,6 +854,9 @@ def main(argv=None):
     args = ap.parse_args(raw)
     try:
         args.precision = resolve_bn_stats(args.bn_stats, args.precision)
+        if args.arch != "auto":
+            check_bn_stats_arch(args.bn_stats, args.arch)
+        args.precision = resolve_arch_precision(args.arch, args.precision)
     except ValueError as e:
         ap.error(str(e))
     if not args.device.startswith("cuda"):
@@ -850,7 +875,8 @@ def main(argv=None):
     if args.precision == "auto":
         stats = None
         try:
-            stats = predict_folder(args.root_path, args.model_path, "f16x2", args.exclude_nodes, not args.no_small_zones, idx, **kw)
+            stats = predict_folder(args.root_path, args.model_path, "f16x2", args.exclude_nodes, not args.no_small_zones, idx,
+                                   precision_auto=True, **kw)
         except NonFiniteLogits as e:                 # raised on every rank alike
             if int(os.environ.get("RANK", "0")) == 0:
                 print("predict: %s -- running the folder again on the f32 MFMA" % e, flush=True)

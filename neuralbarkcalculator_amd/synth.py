@@ -14,7 +14,9 @@ any machine and numpy version.  Shapes follow SURVEY.md section 8(d):
   classes all appear in the label mask; random-init gives an all-"Nothing" mask, which would
   make a label-parity test vacuous);
 * ``arch="deeplabv3_resnet50"``: the 362-entry state_dict of ``deeplabv3_resnet50`` (``models.py:46-57``), the same
-  trunk (same numbers for the same seed) and a DeepLabHead.
+  trunk (same numbers for the same seed) and a DeepLabHead;
+* ``arch="fcn_efficientnet_b{n}"`` / ``"deeplabv3_efficientnet_b{n}"``: an EfficientNet trunk (``topology``) under the
+  same heads; "trained_like" scales every weight by its fan-in so that activations stay O(1) through the deep trunks.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ from typing import Dict
 
 import numpy as np
 
-from .topology import conv_units, state_dict_spec
+from .topology import conv_units, is_efficientnet, state_dict_spec
 
 DEFAULT_MEAN = (0.7399, 0.6139, 0.4401)   # models.py:208
 DEFAULT_STD = (0.1068, 0.1272, 0.1271)    # models.py:209
@@ -76,12 +78,17 @@ def make_state_dict(kind: str = "trained_like", seed: int = 7, arch: str = "fcn_
     aspp_head = {u.name for u in conv_units(arch) if u.name.startswith("classifier.") and u.bn is not None} \
         if arch == "deeplabv3_resnet50" else set()
     sd: Dict[str, np.ndarray] = {}
+    eff = is_efficientnet(arch)
     for stream, (key, shape, dtype) in enumerate(state_dict_spec(arch)):
         n = int(np.prod(shape)) if shape else 1
         if key.endswith("num_batches_tracked"):
             sd[key] = np.zeros((), dtype=np.int64)
             continue
         prefix, leaf = key.rsplit(".", 1)
+        if eff and (prefix.endswith("._fc") or (prefix in units and units[prefix].kind != "conv")
+                    or (prefix in units and leaf == "weight" and units[prefix].bn is not None)):
+            sd[key] = _efficientnet_leaf(units.get(prefix), prefix, leaf, shape, kind, seed, stream, n)
+            continue
         if prefix in units and leaf == "weight":
             u = units[prefix]
             if u.bn is None:  # classifier.4: nn.Conv2d default init ~ U(-1/sqrt(fan_in), +)
@@ -105,7 +112,7 @@ def make_state_dict(kind: str = "trained_like", seed: int = 7, arch: str = "fcn_
                 v = np.ones(n) if leaf in ("weight", "running_var") else np.zeros(n)
             elif leaf == "weight":
                 v = 0.5 + uniform01(seed, stream, n)
-                if prefix.endswith(".bn3"):   # trained nets keep the residual branch small
+                if prefix.endswith(".bn3") or (eff and prefix.endswith("._bn2")):   # trained nets keep the residual branch small
                     v = v * 0.35
             elif leaf == "running_var":
                 v = 0.5 + uniform01(seed, stream, n)
@@ -113,6 +120,23 @@ def make_state_dict(kind: str = "trained_like", seed: int = 7, arch: str = "fcn_
                 v = normal(seed, stream, n) * 0.1
         sd[key] = v.astype(np.float32).reshape(shape)
     return sd
+
+
+def _efficientnet_leaf(u, prefix, leaf, shape, kind, seed, stream, n) -> np.ndarray:
+    """EfficientNet weights: every convolution (depthwise and SE too) ~ N(0, 1 / fan_in), the SE convolutions with
+    biases ~ N(0, 0.1^2) (the expand bias centred at +1, so that the gates open), the unused _fc ~ N(0, 0.01^2)."""
+    if u is None:                                        # backbone.model._fc
+        v = normal(seed, stream, n) * 0.01
+    elif leaf == "bias":
+        v = normal(seed, stream, n) * 0.1 + (1.0 if u.kind == "se_expand" else 0.0)
+    else:
+        fan_in = (1 if u.kind == "dw" else u.cin) * u.k * u.k
+        gain = 1.0
+        if kind == "random_init":                         # torch's default conv init bound, uniform
+            v = (uniform01(seed, stream, n) * 2.0 - 1.0) / np.sqrt(fan_in)
+        else:
+            v = normal(seed, stream, n) * np.sqrt(gain / fan_in)
+    return v.astype(np.float32).reshape(shape)
 
 
 def _smooth_field(seed: int, stream: int, h: int, w: int, cells: int) -> np.ndarray:
