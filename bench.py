@@ -12,6 +12,10 @@ barrier + torch.cuda.synchronize() on both sides; the time is the MAX over ranks
 JSON line.  ``--dump-outputs DIR`` also writes what the headline's last timed step returned (labels, class counts)
 as .npy files, so that two builds can be compared output for output on the same seeded frames.
 
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the dump
+if asked for, the line.  Everything else the bench measures or checks (the extra objects below, the
+repeats of the headline's region, the row gather of a multi-rank run) runs with ``--full`` only.
+
 Headline (``value``, ``dtype`` "f16x2"): BASELINE.json configs[1] -- 1 x MI355X per rank, batch 1,
 synthetic 1024x1024x3 frames, in the f32-GRADE mode NBC_PREC_F16X2: every f32 value (activation or weight) is kept as
 two f16 pieces (to 2^-23 relative for |x| >= 2^-12; weight rows normalised by a power of two per output channel), a
@@ -23,9 +27,9 @@ profiles/r04_fp64_adjudication_*).  The f32 MFMA mode (v_mfma_f32_32x32x2_f32),
 round 2's headline, rides along as ``f32_mfma_batch1``.
 Images are independent: N GPUs = N shards of the folder, no data-path collective,
 weak scaling; the collectives are the one-off RCCL broadcast of the packed weights (``setup``) and
-the all_gather of the per-image rows at the end (``gather_s``), both outside the timed region.
+the all_gather of the per-image rows at the end (``gather_s``, ``--full``), both outside the timed region.
 
-Extra objects on the same line:
+Extra objects on the same line (``--full``):
   ``roofline``      dominant kernel of the headline run (the implicit-GEMM convolution, MFMA-bound):
                     algorithmic FLOPs / RAW HIP-event durations of its launches, measured in a second
                     region of K steps on one stream with an event between launches (nothing subtracted)
@@ -67,6 +71,10 @@ DTYPE_NOTE = {
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: its region repeated (--repeats), the instrumented "
+                         "region (roofline), the f32 MFMA and bf16 batch-8 legs, the CPU baseline, parity against the CPU "
+                         "oracle, the row gather of a multi-rank run; the --no-* switches below leave parts of it out")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--precision", choices=["bf16", "fp32", "f16x2"], default="f16x2",
@@ -109,9 +117,10 @@ def parse(argv=None):
     ap.add_argument("--bf16-steps", type=int, default=0, help="steps of the configs[2] leg (default: max(10, K/5))")
     ap.add_argument("--bf16-streams", type=int, default=2)
     ap.add_argument("--no-op-events", action="store_true", help="no instrumented region (no roofline object)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="how often the headline's bracketed K-step region is run: `value` is the FIRST (the contract's region), "
-                         "`value_repeats` lists all of them, `value_median` their median (the line's own spread)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how often the headline's bracketed K-step region is run (default 5 with --full, else 1): `value` is "
+                         "the FIRST (the contract's region), `value_repeats` lists all of them, `value_median` their median "
+                         "(the line's own spread)")
     ap.add_argument("--save-tiles", default=None, help="write the measured per-layer tile choices (JSON) to this file")
     ap.add_argument("--tiles-file", default=None,
                     help="install the tile choices of an earlier run instead of measuring them (profiling runs: the trace "
@@ -119,6 +128,12 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops needs --full: the per-launch records come from the instrumented region")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:       # a plain run: the headline alone
+        args.no_op_events = args.no_f32_leg = args.no_bf16_leg = args.no_cpu_baseline = args.no_parity = True
     return args
 
 
@@ -454,7 +469,7 @@ def main():
 
     # ---- the gather of the per-image rows (one all_gather of int64 rows, predict.py's collective)
     gather_s = None
-    if dist is not None:
+    if dist is not None and args.full:
         from neuralbarkcalculator_amd.predict import gather_rows
         rows = np.array([[rank + world * j, H, W, int(head["last_counts"][j, 1]), int(head["last_counts"][j, 2])]
                          for j in range(args.batch)], dtype=np.int64)

@@ -6,7 +6,7 @@ out=$root/gpurun_out/matrix; mkdir -p $out
 i=0
 for flags in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python $root/bench.py --no-cpu-baseline --no-parity $flags > $out/run$i.json 2> $out/run$i.err || { echo "run $i failed"; tail -3 $out/run$i.err; exit 1; }
+  timeout -k 10 300 python $root/bench.py --full --no-cpu-baseline --no-parity $flags > $out/run$i.json 2> $out/run$i.err || { echo "run $i failed"; tail -3 $out/run$i.err; exit 1; }
   python3 - "$out/run$i.json" "$flags" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d.get("roofline",{}); b=d.get("bf16_batch8")

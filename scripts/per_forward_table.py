@@ -149,7 +149,7 @@ def main():
                                                                     "head" if n.startswith("classifier") else n)
         stages.setdefault(st, []).append(r)
     out = {
-        "source": "rocprofv3 --kernel-trace of `python3 bench.py --precision %s --batch %d --streams 1 --steps %d --warmup %d --no-bf16-leg "
+        "source": "rocprofv3 --kernel-trace of `python3 bench.py --full --precision %s --batch %d --streams 1 --steps %d --warmup %d --no-bf16-leg "
                   "--no-cpu-baseline --no-parity`; medians over the %d forwards of bench.py's timed region (autotune launches excluded)"
                   % (a.precision, a.batch, a.steps, a.warmup, a.steps),
         "precision": a.precision, "batch": a.batch, "kernel_source_id": kernel_source_id(),

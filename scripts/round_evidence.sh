@@ -13,8 +13,8 @@ timeout -k 10 600 python -m pytest tests -m gpu -q -s > $out/gpu_tests.log 2>&1 
 tail -1 $out/gpu_tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -5 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err || { tail -5 $out/bench_default.err; exit 1; }
-timeout -k 10 300 python bench.py --gpus 2 --share-gpu --steps 20 --warmup 3 --no-bf16-leg > $out/bench_2ranks_one_gpu_gloo.json 2> $out/bench_2ranks.err || { tail -5 $out/bench_2ranks.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err || { tail -5 $out/bench_default.err; exit 1; }
+timeout -k 10 300 python bench.py --full --gpus 2 --share-gpu --steps 20 --warmup 3 --no-bf16-leg > $out/bench_2ranks_one_gpu_gloo.json 2> $out/bench_2ranks.err || { tail -5 $out/bench_2ranks.err; exit 1; }
 timeout -k 10 300 python scripts/time_folder.py 1000 f16x2,bf16,fp32 > $out/time_folder.log 2>&1 || { tail -5 $out/time_folder.log; exit 1; }
 grep -E "run 1" $out/time_folder.log
 timeout -k 10 200 python scripts/time_folder.py 1000 f16x2,fp32 ragged > $out/time_folder_ragged.log 2>&1 || { tail -5 $out/time_folder_ragged.log; exit 1; }

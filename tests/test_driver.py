@@ -341,3 +341,22 @@ def test_bench_dump_outputs_files(tmp_path):
             assert np.array_equal(np.load(str(tmp_path / "again" / "labels_index.npy")), idx)
     bench.dump_outputs(d, (labels[:2], counts[:2]))     # a smaller dump into the same folder drops the stale index
     assert sorted(os.listdir(d)) == ["counts.npy", "labels.npy"]
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """bench.py without --full: the contract's region once and no other leg, region or check; --full switches them on
+    (the --no-* switches still leave parts out), and --dump-ops, which needs the instrumented region, asks for it."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    extras = ("no_op_events", "no_f32_leg", "no_bf16_leg", "no_cpu_baseline", "no_parity")
+    a = bench.parse(["--steps", "20", "--warmup", "3"])
+    assert not a.full and a.repeats == 1 and all(getattr(a, k) for k in extras)
+    assert (a.steps, a.warmup, a.precision, a.batch, a.streams, a.frames) == (20, 3, "f16x2", 1, 2, 100)
+    assert bench.parse(["--repeats", "3"]).repeats == 3
+    f = bench.parse(["--full"])
+    assert f.full and f.repeats == 5 and not any(getattr(f, k) for k in extras)
+    assert bench.parse(["--full", "--no-bf16-leg"]).no_bf16_leg
+    with pytest.raises(SystemExit):
+        bench.parse(["--dump-ops", "ops.json"])
+    assert bench.parse(["--full", "--dump-ops", "ops.json"]).dump_ops == "ops.json"

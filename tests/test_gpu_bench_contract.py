@@ -39,10 +39,25 @@ def check_roofline(r, peak):
         assert "frac_rocprof_table" not in r and "table" not in r and "head_conv_rocprof_table" not in r
 
 
-def test_default_bench_line(built_lib):
-    """The driver's command shape: the headline is configs[1] in the f32-grade f16x2 mode (same parity bounds as the f32
-    MFMA mode, which rides along as its own object), configs[2] (bf16, batch 8) as another."""
+def test_plain_bench_line(built_lib):
+    """The driver's command shape: the headline alone -- configs[1] in the f32-grade f16x2 mode, the contract's region
+    once -- and nothing that --full adds."""
     d = run_bench("--steps", "8", "--warmup", "2")
+    assert d["metric"].startswith("1024x1024 images/sec") and d["unit"] == "images/s"
+    assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["rccl_ranks"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]      # batch 1, one rank
+    assert d["value_repeats"] == [d["value"]] and d["value_median"] == d["value"]
+    assert d["higher_is_better"] is True and d["dtype"] == "f16x2" and "f32-grade" in d["dtype_note"]
+    assert d["config"]["workload"].startswith("configs[1]") and d["config"]["frames"] == 100
+    assert d["gather_s"] is None
+    for key in ("roofline", "top_ops", "cpu_baseline", "parity", "f32_mfma_batch1", "bf16_batch8"):
+        assert key not in d, key
+
+
+def test_default_bench_line(built_lib):
+    """`--full`: the headline is configs[1] in the f32-grade f16x2 mode (same parity bounds as the f32 MFMA mode, which
+    rides along as its own object), configs[2] (bf16, batch 8) as another."""
+    d = run_bench("--full", "--steps", "8", "--warmup", "2")
     assert d["metric"].startswith("1024x1024 images/sec") and d["unit"] == "images/s"
     assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["rccl_ranks"] == 1
     assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]      # batch 1, one rank
@@ -83,7 +98,7 @@ def test_bench_starts_its_own_ranks(built_lib):
     """`bench.py --gpus 2` with no torchrun environment starts two ranks itself (here both on cuda:0 over
     gloo: a one-GPU box) and prints one line for the two-rank job: weight broadcast, sharded frames,
     max-over-ranks timing, the row gather."""
-    d = run_bench("--gpus", "2", "--share-gpu", "--steps", "4", "--warmup", "1", "--no-bf16-leg", "--frames", "4")
+    d = run_bench("--full", "--gpus", "2", "--share-gpu", "--steps", "4", "--warmup", "1", "--no-bf16-leg", "--frames", "4")
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["dist_backend"] == "gloo"
     assert d["steps"] == 4 and abs(d["value"] - 2 * 4 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"]
     assert d["setup"]["weight_broadcast_s"] > 0 and d["setup"]["process_group_init_s"] > 0
