@@ -338,6 +338,32 @@ int nbc_remove_small_zones(nbc_ctx* ctx, void* labels_dev, int labels_dtype, int
 int nbc_confusion(const void* labels_dev, int labels_dtype, const uint8_t* target_dev,
                   int N, int H, int W, int64_t* conf_dev, void* hip_stream);
 
+/* Per-image Lovasz-Softmax loss terms: `LovaszSoftmax()(logits, target)` (lovasz_losses.py:162-223: softmax over the classes,
+ * then lovasz_softmax_flat with classes='present', ignore=None) of each image as a batch of one -- the training objective of
+ * __main__.py:236-239, which exp.test / test_model_on_checkpoint print as test_loss (__main__.py:179-197).  No context:
+ * csrc/lovasz.hip.  Per image n and class c, with fg = (target class == c), p_c = softmax(logits)_c in f32 and
+ * e = |fg - p_c| sorted descending (fg carried along), G = sum fg, I_i = G - sum_{k<=i} fg_(k), U_i = G + sum_{k<=i} (1 - fg_(k)),
+ * J_i = 1 - I_i / U_i (f64), J_{-1} = 0:  terms[n][c] = sum_i e_(i) (J_i - J_{i-1})  (lovasz_grad, lovasz_losses.py:19-31),
+ * summed in f64 in a fixed order.  The loss of an image is the mean of the terms of its present classes (fg_counts > 0) in
+ * class order, a host division (neuralbarkcalculator_amd/metrics.py: lovasz_loss).
+ * logits_full_dev  float32 [N,3,H,W], what nbc_forward writes to logits_full_dev (after the bicubic upsample)
+ * target_dev       uint8 [N,H,W] grey levels; class = round(2 * float32(v) / 255) as nbc_confusion derives it
+ * workspace_dev    at least nbc_lovasz_workspace_bytes(N, H, W) bytes of device memory, 256-byte aligned; contents scratch
+ * terms_dev        float64 [N,3]: the term of each class; 0 for an absent class; NaN for every present class of an image
+ *                  in which some pixel's softmax is not finite (a NaN or +inf logit, or all three -inf), as torch gives
+ * fg_counts_dev    int64 [N,3]: G, the target pixels of each class (0 tells the caller the class is absent)
+ * The sort is exact (keys-only LSD radix sort of the f32 errors, no binning) and every sum has a fixed order: an image's
+ * terms are bit-identical alone, in any batch and on any stream.  Runs on hip_stream; no synchronisation.
+ * NBC_ERR_INVALID: a null pointer, N < 1 or N > 65535, H or W < 1, H * W >= 2^31, or a workspace too small or misaligned.
+ * With P = H * W, S = 3 N, T = ceil(P / 8192) and A(x) = x rounded up to a multiple of 256, the workspace is
+ *   2 A(4 S P) + A(1024 S T) + A(1024 S) + A(4 S T) + A(8 S T) + A(4 N) bytes
+ * (two key arrays, per-tile digit histograms, digit bases, per-tile foreground counts, per-tile f64 partials, non-finite
+ * flags); nbc_lovasz_workspace_bytes returns 0 for a shape nbc_lovasz_softmax refuses. */
+size_t nbc_lovasz_workspace_bytes(int N, int H, int W);
+int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
+                       void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev,
+                       void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

@@ -1,0 +1,445 @@
+// Per-image Lovasz-Softmax loss terms on the device: `LovaszSoftmax()(logits, target)` of
+// the reference's bark_calculator/lovasz_losses.py:162-223 (softmax, then lovasz_softmax_flat with classes='present',
+// ignore=None) for a batch of one, the objective the training script builds its Experiment with (__main__.py:236-239).
+// One f64 term per (image, class) and the class's foreground count leave the device; the mean over the present classes
+// is host arithmetic (neuralbarkcalculator_amd/metrics.py, lovasz_loss).
+//
+// Per (image, class) "segment" of P = H * W pixels:
+//   lovasz_keys     reads the logits [3,H,W] and the u8 grey target once; writes one u32 key per (class, pixel),
+//                   key = bits(e) << 1 | fg with e = |fg - softmax_c| in [0, 1] (so bits(e) <= 0x3F800000 is monotone in
+//                   e and the key fits in 31 bits), the foreground count G of every class (integer atomics: their order
+//                   reaches nothing) and a per-image flag when a pixel's softmax is not finite.
+//   lovasz_hist / lovasz_scan / lovasz_scatter
+//                   a keys-only LSD radix sort, descending, 8-bit digits in 4 passes, tiles of 8192 keys: per-tile digit
+//                   histograms, their exclusive scan per segment, and a stable scatter (ranks from wave ballots, the tile
+//                   sorted in LDS, then written out in runs).  Keys-only: any correct sort gives the same array.
+//   lovasz_tile_fg  foreground keys per sorted tile (exact integers).
+//   lovasz_partial  per tile: running fg / bg counts, J_i = 1 - I_i / U_i and J_{i-1} in f64, sum of e_(i) (J_i - J_{i-1})
+//                   in f64 in a fixed order (lane, wave butterfly, waves in order).
+//   lovasz_finish   one thread per segment adds the tile partials in tile order.
+// Every sum has a fixed order and every count is exact, so an image's terms are bit-identical whatever batch or stream
+// it runs in.  A segment whose class is absent (G = 0) or whose image has a non-finite softmax is not sorted: its term is
+// 0 or NaN.  No library besides the HIP runtime.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/nbc.h"
+#include "nbc_internal.hpp"
+
+using namespace nbc;
+
+namespace {
+
+constexpr int kClasses = 3;
+constexpr int kSortThreads = 512;                       // 8 waves
+constexpr int kWaves = kSortThreads / 64;
+constexpr int kItems = 16;                              // keys per lane and tile
+constexpr int kTile = kSortThreads * kItems;            // 8192 keys per tile
+constexpr int kRadix = 256;
+constexpr int kPasses = 4;                              // 4 x 8 bits cover the 31-bit keys
+constexpr int kKeyThreads = 256;
+constexpr int kScanThreads = 1024;                      // 4 groups of 256 digit lanes
+
+using u32 = unsigned;
+using u64 = unsigned long long;
+
+// descending order: the digit of ~key, so that the ascending LSD sort puts large keys first
+__device__ __forceinline__ u32 digit_of(u32 key, int shift) { return ((~key) >> shift) & (kRadix - 1u); }
+
+__device__ __forceinline__ u64 lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
+// the lanes of this wave that hold the same 8-bit digit (and are valid)
+__device__ __forceinline__ u64 digit_peers(u32 d, bool valid) {
+  u64 peers = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const u64 vote = __ballot(bit);
+    peers &= bit ? vote : ~vote;
+  }
+  return peers;
+}
+
+// exclusive scan of v over threads 0..255; every thread of the block calls it (threads >= 256 pass anything and get garbage)
+__device__ __forceinline__ u32 excl_scan_256(u32 v, u32* wsum /* LDS [4] */) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  u32 x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u32 y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (w < 4 && lane == 63) wsum[w] = x;
+  __syncthreads();
+  u32 pre = 0;
+  for (int k = 0; k < 4 && k < w; ++k) pre += wsum[k];
+  return pre + x - v;
+}
+
+__device__ __forceinline__ bool segment_idle(const u64* G, const u32* flag, int n, int seg) { return G[seg] == 0 || flag[n] != 0; }
+
+__global__ __launch_bounds__(kKeyThreads) void lovasz_keys(const float* __restrict__ logits, const unsigned char* __restrict__ target,
+                                                           long long P, u32* __restrict__ keys, u64* __restrict__ G,
+                                                           u32* __restrict__ flag) {
+  const int n = blockIdx.y, tid = threadIdx.x;
+  const float* lg = logits + (size_t)n * kClasses * P;
+  const unsigned char* tg = target + (size_t)n * P;
+  u32* k0 = keys + (size_t)n * kClasses * P;
+  u32 cnt[kClasses] = {0, 0, 0};
+  bool bad = false;
+  for (long long i = (long long)blockIdx.x * kKeyThreads + tid; i < P; i += (long long)gridDim.x * kKeyThreads) {
+    const float a = lg[i], b = lg[P + i], c = lg[2 * P + i];
+    const float m = fmaxf(fmaxf(a, b), c);                 // a NaN logit is skipped here and poisons its exp below
+    const float ea = expf(a - m), eb = expf(b - m), ec = expf(c - m);
+    const float s = ea + eb + ec;
+    const float p[kClasses] = {ea / s, eb / s, ec / s};
+    const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+    bad |= !finite;
+    const u32 t = ((u32)tg[i] + 64u) >> 7;                 // round(2 v / 255), as nbc_confusion
+#pragma unroll
+    for (int cl = 0; cl < kClasses; ++cl) {
+      const u32 fg = t == (u32)cl;
+      const float e = finite ? fabsf((float)fg - p[cl]) : 0.f;
+      k0[(size_t)cl * P + i] = (__float_as_uint(e) << 1) | fg;
+      cnt[cl] += fg;
+    }
+  }
+  __shared__ u32 part[kKeyThreads / 64][kClasses];
+#pragma unroll
+  for (int cl = 0; cl < kClasses; ++cl) {
+    u32 v = cnt[cl];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((tid & 63) == 0) part[tid >> 6][cl] = v;
+  }
+  if (__syncthreads_or(bad) && tid == 0) flag[n] = 1u;
+  if (tid < kClasses) {
+    u64 s = 0;
+#pragma unroll
+    for (int w = 0; w < kKeyThreads / 64; ++w) s += part[w][tid];
+    if (s) atomicAdd(&G[(size_t)n * kClasses + tid], s);
+  }
+}
+
+// per-tile digit histogram: hist[seg][t][d]
+__global__ __launch_bounds__(kSortThreads) void lovasz_hist(const u32* __restrict__ keys, long long P, int T, int shift,
+                                                            u32* __restrict__ hist, const u64* __restrict__ G,
+                                                            const u32* __restrict__ flag) {
+  const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
+  if (segment_idle(G, flag, n, seg)) return;
+  __shared__ u32 h[kRadix];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid < kRadix) h[tid] = 0;
+  __syncthreads();
+  const long long start = (long long)t * kTile;
+  const int nt = (int)min((long long)kTile, P - start);
+  const u32* src = keys + (size_t)seg * P + start;
+#pragma unroll 4
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    const bool valid = idx < nt;
+    const u32 d = valid ? digit_of(src[idx], shift) : 0u;
+    const u64 peers = digit_peers(d, valid);
+    if (valid && (peers & lanes_below(lane)) == 0) atomicAdd(&h[d], (u32)__popcll(peers));
+  }
+  __syncthreads();
+  if (tid < kRadix) hist[((size_t)seg * T + t) * kRadix + tid] = h[tid];
+}
+
+// per segment: hist[seg][t][d] <- sum over t' < t of hist[seg][t'][d]; base[seg][d] <- keys of the segment with a digit below d
+__global__ __launch_bounds__(kScanThreads) void lovasz_scan(u32* __restrict__ hist, int T, u32* __restrict__ base,
+                                                            const u64* __restrict__ G, const u32* __restrict__ flag) {
+  const int n = blockIdx.x, seg = n * kClasses + blockIdx.y;
+  if (segment_idle(G, flag, n, seg)) return;
+  __shared__ u32 gsum[kScanThreads / kRadix][kRadix];
+  __shared__ u32 wsum[4];
+  const int tid = threadIdx.x, d = tid & (kRadix - 1), g = tid / kRadix;
+  constexpr int kGroups = kScanThreads / kRadix;
+  const int per = (T + kGroups - 1) / kGroups;
+  const int t0 = min(T, g * per), t1 = min(T, t0 + per);
+  u32* h = hist + (size_t)seg * T * kRadix + d;
+  u32 sum = 0;
+  for (int t = t0; t < t1; ++t) sum += h[(size_t)t * kRadix];
+  gsum[g][d] = sum;
+  __syncthreads();
+  u32 run = 0, total = 0;
+#pragma unroll
+  for (int k = 0; k < kGroups; ++k) {
+    if (k < g) run += gsum[k][d];
+    total += gsum[k][d];
+  }
+  for (int t = t0; t < t1; ++t) {
+    const u32 v = h[(size_t)t * kRadix];
+    h[(size_t)t * kRadix] = run;
+    run += v;
+  }
+  const u32 ex = excl_scan_256(total, wsum);
+  if (tid < kRadix) base[(size_t)seg * kRadix + d] = ex;
+}
+
+// one stable LSD pass of one tile: rank by wave ballots, sort the tile in LDS, write it out in runs of equal digits
+__global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __restrict__ in, u32* __restrict__ out, long long P, int T,
+                                                               int shift, const u32* __restrict__ hist, const u32* __restrict__ base,
+                                                               const u64* __restrict__ G, const u32* __restrict__ flag) {
+  const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
+  if (segment_idle(G, flag, n, seg)) return;
+  __shared__ u32 sorted[kTile];
+  __shared__ u32 cnt[kWaves][kRadix];                 // per wave: digit counts, then the wave's start inside the digit
+  __shared__ u32 dstart[kRadix];                      // start of each digit in the sorted tile
+  __shared__ u32 gofs[kRadix];                        // segment position of sorted[i] = gofs[digit] + i
+  __shared__ u32 wsum[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int k = lane; k < kRadix; k += 64) cnt[w][k] = 0;
+  __builtin_amdgcn_wave_barrier();
+  const long long start = (long long)t * kTile;
+  const int nt = (int)min((long long)kTile, P - start);
+  const u32* src = in + (size_t)seg * P + start;
+
+  u32 key[kItems], rank[kItems];
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    key[j] = idx < nt ? src[idx] : 0u;
+  }
+  // input order inside the tile: wave, then item j, then lane -- ranks follow it, so the pass is stable
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    const bool valid = idx < nt;
+    const u32 d = digit_of(key[j], shift);
+    const u64 peers = digit_peers(d, valid);
+    const u32 below = (u32)__popcll(peers & lanes_below(lane));
+    const u32 old = cnt[w][d];
+    __builtin_amdgcn_wave_barrier();
+    if (valid && below == 0) cnt[w][d] = old + (u32)__popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+    rank[j] = old + below;
+  }
+  __syncthreads();
+  u32 total = 0;
+  if (tid < kRadix) {
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+      const u32 v = cnt[k][tid];
+      cnt[k][tid] = total;
+      total += v;
+    }
+  }
+  const u32 ds = excl_scan_256(total, wsum);
+  if (tid < kRadix) {
+    dstart[tid] = ds;
+    gofs[tid] = base[(size_t)seg * kRadix + tid] + hist[((size_t)seg * T + t) * kRadix + tid] - ds;   // mod 2^32, >= 0 once i is added
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    if (idx < nt) {
+      const u32 d = digit_of(key[j], shift);
+      sorted[dstart[d] + cnt[w][d] + rank[j]] = key[j];
+    }
+  }
+  __syncthreads();
+  u32* dst = out + (size_t)seg * P;
+  for (int i = tid; i < nt; i += kSortThreads) {
+    const u32 k = sorted[i];
+    dst[gofs[digit_of(k, shift)] + (u32)i] = k;
+  }
+}
+
+__device__ __forceinline__ void block_sum_to(u32 v, u32* red /* LDS [kWaves] */, u32* out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) {
+    u32 s = 0;
+    for (int k = 0; k < kWaves; ++k) s += red[k];
+    *out = s;
+  }
+}
+
+// foreground keys per tile of the sorted segment
+__global__ __launch_bounds__(kSortThreads) void lovasz_tile_fg(const u32* __restrict__ keys, long long P, int T,
+                                                               u32* __restrict__ tile_fg, const u64* __restrict__ G,
+                                                               const u32* __restrict__ flag) {
+  const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
+  if (segment_idle(G, flag, n, seg)) return;
+  __shared__ u32 red[kWaves];
+  const long long start = (long long)t * kTile;
+  const int nt = (int)min((long long)kTile, P - start);
+  const u32* src = keys + (size_t)seg * P + start;
+  u32 c = 0;
+  for (int i = threadIdx.x; i < nt; i += kSortThreads) c += src[i] & 1u;
+  block_sum_to(c, red, &tile_fg[(size_t)seg * T + t]);
+}
+
+// f64 partial sum of e_(i) (J_i - J_{i-1}) over one tile of the sorted segment
+__global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __restrict__ keys, long long P, int T,
+                                                               const u32* __restrict__ tile_fg, const u64* __restrict__ G,
+                                                               const u32* __restrict__ flag, double* __restrict__ partial) {
+  const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
+  if (segment_idle(G, flag, n, seg)) return;
+  __shared__ u32 red[kWaves];
+  __shared__ u32 wfg[kWaves];
+  __shared__ u32 fg_before_tile;
+  __shared__ double dred[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  u32 c = 0;
+  for (int u = tid; u < t; u += kSortThreads) c += tile_fg[(size_t)seg * T + u];
+  block_sum_to(c, red, &fg_before_tile);
+
+  const long long start = (long long)t * kTile;
+  const int nt = (int)min((long long)kTile, P - start);
+  const u32* src = keys + (size_t)seg * P + start;
+  u32 key[kItems];
+  u32 mine = 0;
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    key[j] = idx < nt ? src[idx] : 0u;              // 0: not foreground, e = 0
+    mine += key[j] & 1u;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if (lane == 0) wfg[w] = mine;
+  __syncthreads();
+  long long run = fg_before_tile;                    // foreground keys before this wave's first key
+  for (int k = 0; k < w; ++k) run += wfg[k];
+  const long long g_all = (long long)G[seg];
+  const double gd = (double)g_all;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    const u32 g = key[j] & 1u;
+    const u64 m = __ballot(g != 0);
+    if (idx < nt) {
+      const long long i = start + idx;              // position in the sorted segment
+      const long long fg_before = run + __popcll(m & lanes_below(lane));
+      const long long cum_fg = fg_before + g;
+      const double J = 1.0 - (double)(g_all - cum_fg) / (gd + (double)(i + 1 - cum_fg));
+      const double Jp = i == 0 ? 0.0 : 1.0 - (double)(g_all - fg_before) / (gd + (double)(i - fg_before));
+      acc += (double)__uint_as_float(key[j] >> 1) * (J - Jp);
+    }
+    run += __popcll(m);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) dred[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int k = 0; k < kWaves; ++k) s += dred[k];
+    partial[(size_t)seg * T + t] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ partial, int T, int S, const u64* __restrict__ G,
+                                                    const u32* __restrict__ flag, double* __restrict__ terms) {
+  const int seg = blockIdx.x * 64 + threadIdx.x;
+  if (seg >= S) return;
+  double s = 0.0;
+  if (G[seg] == 0)
+    s = 0.0;
+  else if (flag[seg / kClasses])
+    s = __builtin_nan("");
+  else {
+    const double* p = partial + (size_t)seg * T;
+    int t = 0;
+    for (; t + 8 <= T; t += 8) {                     // eight loads in flight, added in tile order
+      double v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = p[t + k];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += v[k];
+    }
+    for (; t < T; ++t) s += p[t];
+  }
+  terms[seg] = s;
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Layout {
+  size_t keys_a, keys_b, hist, base, tile_fg, partial, flag, total;
+};
+
+// byte offsets of the workspace regions (include/nbc.h states the sum); false for a shape the call refuses
+bool layout(int N, int H, int W, Layout* L) {
+  if (N < 1 || N > 65535 || H < 1 || W < 1) return false;
+  const size_t P = (size_t)H * (size_t)W;
+  if (P >= ((size_t)1 << 31)) return false;
+  const size_t S = (size_t)kClasses * N, T = (P + kTile - 1) / kTile;
+  size_t o = 0;
+  L->keys_a = o;  o += align256(4 * S * P);
+  L->keys_b = o;  o += align256(4 * S * P);
+  L->hist = o;    o += align256(4 * S * T * kRadix);
+  L->base = o;    o += align256(4 * S * kRadix);
+  L->tile_fg = o; o += align256(4 * S * T);
+  L->partial = o; o += align256(8 * S * T);
+  L->flag = o;    o += align256(4 * (size_t)N);
+  L->total = o;
+  return true;
+}
+
+int fail(int code, const std::string& msg) { return set_error(code, "nbc_lovasz_softmax: " + msg); }
+
+}  // namespace
+
+extern "C" size_t nbc_lovasz_workspace_bytes(int N, int H, int W) {
+  Layout L;
+  return layout(N, H, W, &L) ? L.total : 0;
+}
+
+extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, void* workspace_dev,
+                                  size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
+  if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(NBC_ERR_INVALID, "null argument");
+  Layout L;
+  if (!layout(N, H, W, &L)) return fail(NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H, W >= 1 and H * W < 2^31");
+  if (workspace_bytes < L.total)
+    return fail(NBC_ERR_INVALID, "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(L.total) + " needed");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) & 255u) return fail(NBC_ERR_INVALID, "workspace must be 256-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  char* ws = static_cast<char*>(workspace_dev);
+  u32* keys[2] = {reinterpret_cast<u32*>(ws + L.keys_a), reinterpret_cast<u32*>(ws + L.keys_b)};
+  u32* hist = reinterpret_cast<u32*>(ws + L.hist);
+  u32* base = reinterpret_cast<u32*>(ws + L.base);
+  u32* tile_fg = reinterpret_cast<u32*>(ws + L.tile_fg);
+  double* partial = reinterpret_cast<double*>(ws + L.partial);
+  u32* flag = reinterpret_cast<u32*>(ws + L.flag);
+  u64* G = reinterpret_cast<u64*>(fg_counts_dev);
+  const long long P = (long long)H * W;
+  const int S = kClasses * N, T = (int)((P + kTile - 1) / kTile);
+
+  hipError_t e = hipMemsetAsync(G, 0, sizeof(u64) * (size_t)S, s);
+  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(u32) * (size_t)N, s);
+  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  // about 4 pixels per thread and at most ~4096 blocks over the batch
+  long long bx = (P + 4 * kKeyThreads - 1) / (4 * kKeyThreads);
+  const long long cap = (4096 + N - 1) / N;
+  if (bx > cap) bx = cap;
+  if (bx < 1) bx = 1;
+  hipLaunchKernelGGL(lovasz_keys, dim3((unsigned)bx, (unsigned)N), dim3(kKeyThreads), 0, s, logits_full_dev, target_dev, P, keys[0], G,
+                     flag);
+  const dim3 tiles((unsigned)T, (unsigned)N, (unsigned)kClasses);
+  for (int pass = 0; pass < kPasses; ++pass) {
+    const int shift = 8 * pass;
+    const u32* in = keys[pass & 1];
+    u32* out = keys[(pass & 1) ^ 1];
+    hipLaunchKernelGGL(lovasz_hist, tiles, dim3(kSortThreads), 0, s, in, P, T, shift, hist, G, flag);
+    hipLaunchKernelGGL(lovasz_scan, dim3((unsigned)N, (unsigned)kClasses), dim3(kScanThreads), 0, s, hist, T, base, G, flag);
+    hipLaunchKernelGGL(lovasz_scatter, tiles, dim3(kSortThreads), 0, s, in, out, P, T, shift, hist, base, G, flag);
+  }
+  const u32* sorted = keys[kPasses & 1];             // an even number of passes ends where the keys started
+  hipLaunchKernelGGL(lovasz_tile_fg, tiles, dim3(kSortThreads), 0, s, sorted, P, T, tile_fg, G, flag);
+  hipLaunchKernelGGL(lovasz_partial, tiles, dim3(kSortThreads), 0, s, sorted, P, T, tile_fg, G, flag, partial);
+  hipLaunchKernelGGL(lovasz_finish, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, partial, T, S, G, flag, terms_dev);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  return NBC_OK;
+}

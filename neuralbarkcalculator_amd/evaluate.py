@@ -26,6 +26,13 @@ Deliberate departures from the reference:
 * ``--exclude_nodes`` is refused: the metrics are defined on three classes;
 * no label PNGs and no matplotlib figures are written.
 
+``--loss`` (``loss=True``) adds the training objective: each batch also writes its full-resolution logits, and
+``FCNResNet50.lovasz_softmax`` turns them and the duals into per-class Lovasz-Softmax terms on the batch's stream
+(``LovaszSoftmax()`` of lovasz_losses.py:162-223 per image, the loss of __main__.py:236-239; the batch-pooled loss of
+``exp.test`` is not computed).  The ``[n,3]`` float64 terms ride back beside the confusions; each rank keeps them in rows
+``(global_idx, 3 terms as int64 bit patterns)`` that a second ``all_gather`` brings to rank 0.  The CSV gains the four
+columns of ``metrics.LOSS_CSV_COLUMNS`` and the summary a ``"lovasz_softmax"`` entry.  Without the flag nothing changes.
+
 The machinery is the predict driver's: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -48,6 +55,7 @@ from .predict import (ARCH_CHOICES, BN_STATS, AbandonMarker, NonFiniteLogits, _d
                       gather_rows, launch_ranks, list_images, resolve_arch_precision, resolve_bn_stats, shard_by_pixels)
 
 ROW_WIDTH = 22                                   # (global_idx, H, W, status, conf_raw[9], conf_clean[9])
+LOSS_ROW_WIDTH = 4                               # --loss: (global_idx, 3 float64 terms viewed as int64)
 STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
 SKIP_REASONS = {STATUS_NO_DUAL: "no_dual", STATUS_SHAPE_MISMATCH: "shape_mismatch", STATUS_TOO_LARGE: "too_large"}
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
@@ -85,14 +93,22 @@ def decode_dual(path: str) -> np.ndarray:
         return np.array(im.convert("L"))
 
 
-def write_stats_csv(path: str, rows) -> None:
+def csv_header(loss: bool = False) -> List[str]:
+    return metrics.EVAL_CSV_HEADER + (metrics.LOSS_CSV_COLUMNS if loss else [])
+
+
+def write_stats_csv(path: str, rows, loss: bool = False) -> None:
     with open(path, "w") as f:                   # __main__.py:433-437
-        csv.writer(f, delimiter="\t").writerows([metrics.EVAL_CSV_HEADER] + [list(r) for r in rows])
+        csv.writer(f, delimiter="\t").writerows([csv_header(loss)] + [list(r) for r in rows])
 
 
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
-           bn_stats: str = "running") -> Tuple[List[List[str]], dict]:
-    """CSV rows and summary from the gathered rank rows (rank 0)."""
+           bn_stats: str = "running", loss_rows: np.ndarray = None) -> Tuple[List[List[str]], dict]:
+    """CSV rows and summary from the gathered rank rows (rank 0); ``loss_rows``: the gathered ``LOSS_ROW_WIDTH`` rows of
+    ``--loss`` (None without it)."""
+    terms = None
+    if loss_rows is not None:
+        terms = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in loss_rows}
     rows, skipped = [], {r: [] for r in SKIP_REASONS.values()}
     raw_total, clean_total = np.zeros((3, 3), np.int64), np.zeros((3, 3), np.int64)
     for r in allrows:
@@ -103,21 +119,28 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
         raw, clean = r[4:13].reshape(3, 3), r[13:22].reshape(3, 3)
         raw_total += raw
         clean_total += clean
-        rows.append(metrics.eval_row(d["name"], d["wood"], raw, clean))
+        row = metrics.eval_row(d["name"], d["wood"], raw, clean)
+        if terms is not None:                    # a class is present where its target row of the confusion is not empty
+            row += metrics.loss_cells(terms[int(r[0])], raw.sum(axis=1))
+        rows.append(row)
     summary = {"precision": precision, "bn_statistics": bn_stats, "model_path": model_path, "images_evaluated": len(rows),
                "images_skipped": sum(len(v) for v in skipped.values()), "skipped": skipped}
     if rows:
         summary.update(metrics.summarize(rows, raw_total, clean_total))
+    if terms is not None:
+        summary["lovasz_softmax"] = metrics.summarize_loss(rows, len(metrics.EVAL_CSV_HEADER))
     return rows, summary
 
 
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
-                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False) -> dict:
+                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
+                    loss: bool = False) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
-    ("fp32", FCN only; ``predict.resolve_bn_stats``).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
+    ("fp32", FCN only; ``predict.resolve_bn_stats``).  ``loss``: also the per-image Lovasz-Softmax loss (module
+    docstring).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import sys
     import time
     from collections import defaultdict, deque
@@ -170,6 +193,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     for m in models:                                 # the largest workspaces once (a context's buffers only grow)
         m.reserve(batch, target_size, target_size)
         m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if loss:                                     # and the loss workspace
+            m.lovasz_softmax(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
+                             torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
     torch.cuda.synchronize(dev)
     t_ready = time.perf_counter()
 
@@ -181,6 +207,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     shards = shard_by_pixels([h * w for h, w in sizes], world)
     mine = shards[rank]
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
+    loss_rows = np.zeros((len(mine), LOSS_ROW_WIDTH), dtype=np.int64) if loss else None
+    if loss:
+        loss_rows[:, 0] = mine
 
     def prepare(k):
         """Pool: status, and for an image that can be evaluated the RGB frame and the grey dual."""
@@ -200,6 +229,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
               "ev": torch.cuda.Event()} for _ in range(depth)]
     ring = [torch.empty((2, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(depth)]   # raw, clean
     ring_ev = [torch.cuda.Event() for _ in range(depth)]
+    loss_ring = [torch.empty((batch, 3), dtype=torch.float64).pin_memory() for _ in range(depth)] if loss else None
+    logits_buf = [torch.empty(batch * 3 * target_size * target_size, dtype=torch.float32, device=dev)
+                  for _ in range(n_streams)] if loss else None
     flag_host = torch.zeros(depth, dtype=torch.int32).pin_memory()
     check_flag = precision == "f16x2"
     bad_seen = [False]
@@ -219,6 +251,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             h, w = sizes[mine[k]]
             rows[k, :4] = (mine[k], h, w, STATUS_OK)
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
+            if loss:
+                loss_rows[k, 1:] = loss_ring[slot][j].numpy().view(np.int64)
 
     # f16x2 calibration guard (predict.predict_folder): rank 0 runs its first image that fits once with every activation kept
     if check_flag and calibrate:
@@ -283,8 +317,12 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                         x = xb.to(dev, non_blocking=True)     # uint8 NHWC; normalised on the device
                         tgt = tb.to(dev, non_blocking=True)
                         st["ev"].record()
-                        labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8)   # __main__.py:323
+                        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss else None
+                        labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
                         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
+                        if loss:                                                      # LovaszSoftmax (:236-239)
+                            terms, _ = mdl.lovasz_softmax(lg, tgt)
+                            loss_ring[slot][:n].copy_(terms, non_blocking=True)
                         mdl.remove_small_zones(labels)                                # PixelWiseF1 (utils.py:213)
                         conf_clean = mdl.confusion(labels, tgt)
                         ring[slot][0, :n].copy_(conf_raw, non_blocking=True)
@@ -321,21 +359,26 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     cap = max(len(s) for s in shards) if shards else 0
     gather_dev = dev if dist is not None and dist.get_backend() == "nccl" else None
     allrows = gather_rows(rows, n_total, world, dist, gather_dev, cap=cap, width=ROW_WIDTH)
+    all_loss = gather_rows(loss_rows, n_total, world, dist, gather_dev, cap=cap, width=LOSS_ROW_WIDTH) if loss else None
     summary = gathered = None
     if rank == 0:
         gathered = allrows.tolist()
-        csv_rows, summary = report(items, allrows, precision, model_path, bn_stats)
-        write_stats_csv(os.path.join(root, STATS_CSV), csv_rows)
+        csv_rows, summary = report(items, allrows, precision, model_path, bn_stats, loss_rows=all_loss)
+        write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     if dist is not None:
         dist.barrier()
     t_end = time.perf_counter()
     n_eval = int(sum(1 for k in range(len(mine)) if rows[k, 3] == STATUS_OK))
-    return {"rank": rank, "world": world, "images_total": n_total, "images_this_rank": len(mine),
-            "images_evaluated_this_rank": n_eval, "batches": n_batches, "batch": batch, "streams": n_streams,
-            "setup_s": t_ready - t_start, "loop_s": t_done - t_loop, "total_s": t_end - t_start,
-            "images_per_s_loop": len(mine) / max(t_done - t_loop, 1e-9), "summary": summary, "rows": gathered}
+    out = {"rank": rank, "world": world, "images_total": n_total, "images_this_rank": len(mine),
+           "images_evaluated_this_rank": n_eval, "batches": n_batches, "batch": batch, "streams": n_streams,
+           "setup_s": t_ready - t_start, "loop_s": t_done - t_loop, "total_s": t_end - t_start,
+           "images_per_s_loop": len(mine) / max(t_done - t_loop, 1e-9), "summary": summary, "rows": gathered}
+    if loss:                                     # rank 0: {global_idx: float64 [3] terms}
+        out["loss_terms"] = None if all_loss is None or rank != 0 else {
+            int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64).copy() for r in all_loss}
+    return out
 
 
 def format_summary(summary: dict) -> str:
@@ -349,6 +392,11 @@ def format_summary(summary: dict) -> str:
         lines.append("pooled over all pixels: " + ", ".join("%s %.3f" % (k, p[k]) for k in p))
         m = summary["column_means"]
         lines.append("mean over images: " + ", ".join("%s %.3f" % (k, m[k]) for k in m))
+    if summary.get("lovasz_softmax"):
+        ls = summary["lovasz_softmax"]
+        fmt = lambda v: "-" if v is None else "%.6f" % v
+        lines.append("lovasz_softmax loss: mean over images %s (per class, over the images where it is present: %s)" % (
+            fmt(ls["mean_over_images"]), ", ".join("%s %s" % (k, fmt(v)) for k, v in ls["per_class_mean"].items())))
     return "\n".join(lines)
 
 
@@ -368,6 +416,8 @@ def main(argv=None):
     ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
                     help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
                          "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
+    ap.add_argument("--loss", action="store_true",
+                    help="also the per-image Lovasz-Softmax loss, the training objective (four more CSV columns, computed on the GPU)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
@@ -385,6 +435,8 @@ def main(argv=None):
         raise SystemExit(launch_ranks(args.gpus, raw, module="neuralbarkcalculator_amd.evaluate"))
     idx = None if "WORLD_SIZE" in os.environ else 0
     kw = dict(batch=args.batch, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
+    if args.loss:
+        kw["loss"] = True
     if args.precision == "auto":
         stats = None
         try:

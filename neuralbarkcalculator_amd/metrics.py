@@ -13,6 +13,10 @@ device):
   ``remove_small_zones`` (150 pixels): ``p = tp / (tp + fp)``, ``r = tp / (tp + fn)`` (0 on a zero denominator),
   ``f = 2 p r / (p + r)`` (0 when ``p + r == 0``), then the absent-class rule of utils.py:222-226 in class order on the
   array as already updated (a class absent from target and output takes the mean of the other two scores), times 100.
+* The loss (``evaluate --loss``): ``LovaszSoftmax()`` (lovasz_losses.py:162-223) of each image as a batch of one, the
+  objective of __main__.py:236-239.  ``FCNResNet50.lovasz_softmax`` computes one term per class on the device;
+  ``lovasz_loss`` is the mean over the present classes (lovasz_losses.py:258-276).  Four trailing CSV columns
+  (``LOSS_CSV_COLUMNS``), written with ``repr`` so that they carry every bit of the float64 values.
 * The percent columns: float32 ``count / (H W) * 100`` with ``'{:.5f}'`` (``__main__.py:392-398``), like
   ``predict.stats_row``; "Output" from the raw argmax, "Target" from the target.
 """
@@ -25,6 +29,7 @@ import numpy as np
 CLASS_NAMES = ["nothing", "bark", "node"]
 EVAL_CSV_HEADER = ["Name", "Type", "Split", "iou_nothing", "iou_bark", "iou_node", "iou_mean", "f1_nothing", "f1_bark",
                    "f1_node", "f1_mean", "Output Bark %", "Output Node %", "Target Bark %", "Target Node %"]   # __main__.py:307-311
+LOSS_CSV_COLUMNS = ["loss_nothing", "loss_bark", "loss_node", "lovasz_softmax"]   # evaluate --loss: after the 15 above
 SPLIT = "all"                     # the Split column: the tool has no train / valid / test split (__main__.py:375-377)
 
 
@@ -105,3 +110,44 @@ def summarize(rows: Sequence[Sequence[str]], conf_raw_total, conf_clean_total) -
     for j, col in enumerate(EVAL_CSV_HEADER[3:], start=3):
         out["column_means"][col] = float(np.mean([float(r[j]) for r in rows])) if rows else None
     return out
+
+
+def lovasz_loss(terms, fg_counts) -> np.ndarray:
+    """The Lovasz-Softmax loss of each image from its per-class terms (``FCNResNet50.lovasz_softmax``): the terms of the
+    classes with ``fg_counts > 0``, added in class order and divided once by their number, as the reference's ``mean``
+    (lovasz_losses.py:258-276) takes it over the present classes.  ``terms`` float [N,3] or [3], ``fg_counts`` int of the
+    same shape; returns float64 [N] (or a float for one image).  An image with no present class (no pixel) gives 0, the
+    reference's ``empty`` value; a NaN term gives NaN."""
+    terms = np.asarray(terms, dtype=np.float64)
+    counts = np.asarray(fg_counts)
+    if terms.shape != counts.shape or terms.shape[-1] != 3:
+        raise ValueError("terms and fg_counts must both be [N,3] or [3]")
+    t2, c2 = terms.reshape(-1, 3), counts.reshape(-1, 3)
+    out = np.zeros(len(t2), dtype=np.float64)
+    for i, (t, c) in enumerate(zip(t2, c2)):
+        present = [float(t[k]) for k in range(3) if c[k] > 0]
+        if present:
+            acc = 0.0
+            for v in present:
+                acc += v
+            out[i] = acc / len(present)
+    return float(out[0]) if terms.ndim == 1 else out
+
+
+def loss_cells(terms, fg_counts) -> List[str]:
+    """The four loss cells of one CSV row: each class's term (empty for an absent class), then the image's loss."""
+    terms = np.asarray(terms, dtype=np.float64).reshape(3)
+    counts = np.asarray(fg_counts).reshape(3)
+    return [repr(float(terms[k])) if counts[k] > 0 else "" for k in range(3)] + [repr(lovasz_loss(terms, counts))]
+
+
+def summarize_loss(rows: Sequence[Sequence[str]], first: int) -> dict:
+    """``{"mean_over_images", "per_class_mean"}`` from the loss cells of the CSV rows (columns ``first`` .. ``first + 3``):
+    the mean of the image losses, and per class the mean of its term over the images where the class is present (None
+    when it is present nowhere)."""
+    per_class = {}
+    for k, name in enumerate(CLASS_NAMES):
+        vals = [float(r[first + k]) for r in rows if r[first + k] != ""]
+        per_class[name] = float(np.mean(vals)) if vals else None
+    losses = [float(r[first + 3]) for r in rows]
+    return {"mean_over_images": float(np.mean(losses)) if losses else None, "per_class_mean": per_class}

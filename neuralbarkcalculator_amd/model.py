@@ -148,6 +148,7 @@ class FCNResNet50:
         self._affine_host: Optional[np.ndarray] = None     # per-image BatchNorm gamma / beta (pack_bn_affine)
         self._affine_dev: Optional[torch.Tensor] = None
         self._ctx = C.c_void_p()
+        self._lovasz_ws: Optional[torch.Tensor] = None     # nbc_lovasz_softmax's workspace (grows, never shrinks)
         self.device: Optional[torch.device] = None
         self.training = False
 
@@ -227,22 +228,30 @@ class FCNResNet50:
     # ---- fused extras ---------------------------------------------------------------------
     def predict_labels(self, x: torch.Tensor, exclude_nodes: bool = False,
                        labels_dtype: torch.dtype = torch.int64,
-                       return_lowres: bool = False, small_zones: bool = False):
+                       return_lowres: bool = False, small_zones: bool = False,
+                       logits_full: Optional[torch.Tensor] = None):
         """Model call + argmax (+ optional 2->1 remap) + per-class pixel counts in one pass.
         ``small_zones=True`` also applies ``remove_small_zones`` (models.py:271) on the device, before
         the remap like the reference does (models.py:271-276); the counts are those of the final labels.
+        ``logits_full``: an optional contiguous f32 ``[N,3,H,W]`` tensor on this model's device that receives the logits
+        ``self(x)`` returns, from the same forward (what ``lovasz_softmax`` reads).
 
         Returns ``(labels [N,H,W], counts int64 [N,3])`` (+ ``lowres f32 [N,3,h,w]``)."""
         n, h, w = self._check_input(x)
         if labels_dtype not in (torch.int64, torch.uint8):
             raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
+        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
+                                        or not logits_full.is_contiguous()
+                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
+            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
+                                                                                                    self.device))
         labels = torch.empty((n, h, w), dtype=labels_dtype, device=self.device)
         counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
         lowres = None
         if return_lowres:
             lh, lw = out_hw(h, w, self.ARCH)
             lowres = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
-        self._forward(x, n, h, w, labels=labels, counts=counts, lowres=lowres,
+        self._forward(x, n, h, w, labels=labels, counts=counts, lowres=lowres, logits_full=logits_full,
                       exclude_nodes=exclude_nodes and not small_zones)
         if small_zones:
             labels, counts = self.remove_small_zones(labels, exclude_nodes=exclude_nodes)
@@ -299,6 +308,39 @@ class FCNResNet50:
             _lib.check(self._lib.nbc_confusion(labels.data_ptr(), _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
                                                target.data_ptr(), n, h, w, conf.data_ptr(), stream), "nbc_confusion")
         return conf
+
+    def lovasz_softmax(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per-image Lovasz-Softmax terms on the device (nbc_lovasz_softmax): ``LovaszSoftmax()(logits, target)``
+        (lovasz_losses.py:162-223), the training objective of __main__.py:236-239, for each image as a batch of one.
+        ``logits_full``: contiguous f32 ``[N,3,H,W]`` (``self(x)``, or ``predict_labels(..., logits_full=)``); ``target``:
+        contiguous uint8 grey mask ``[N,H,W]``, class ``round(2 * v / 255)`` as ``confusion`` reads it; both on this model's
+        device.  Runs on the current stream; the workspace is cached on this object and only grows.  Returns
+        ``(terms f64 [N,3], fg_counts int64 [N,3])``: the term of each class (0 for an absent class, whose fg_count is 0;
+        NaN for every present class of an image whose softmax is not finite somewhere); ``metrics.lovasz_loss`` takes the
+        mean over the present classes."""
+        self._require_ctx()
+        if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
+                or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES:
+            raise ValueError("logits_full must be a contiguous float32 [N,3,H,W] tensor on %s" % (self.device,))
+        n, _, h, w = (int(v) for v in logits_full.shape)
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous() \
+                or tuple(target.shape) != (n, h, w) or target.numel() == 0:
+            raise ValueError("target must be a contiguous uint8 [%d,%d,%d] tensor on %s" % (n, h, w, self.device))
+        need = int(self._lib.nbc_lovasz_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_lovasz_softmax refuses a [%d,3,%d,%d] batch (N <= 65535, H * W < 2^31)" % (n, h, w))
+        if self._lovasz_ws is None or self._lovasz_ws.numel() < need:
+            self._lovasz_ws = None
+            self._lovasz_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        terms = torch.empty((n, NUM_CLASSES), dtype=torch.float64, device=self.device)
+        fg_counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            self._lovasz_ws.record_stream(cur)       # the cached workspace may be used on several streams
+            _lib.check(self._lib.nbc_lovasz_softmax(logits_full.data_ptr(), target.data_ptr(), n, h, w, self._lovasz_ws.data_ptr(),
+                                                    self._lovasz_ws.numel(), terms.data_ptr(), fg_counts.data_ptr(),
+                                                    cur.cuda_stream), "nbc_lovasz_softmax")
+        return terms, fg_counts
 
     def resize_cubic_u8(self, image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """The resize of the reference's preprocessor (models.py:191-198) on the device: uint8 RGB
@@ -607,6 +649,7 @@ class FCNResNet50:
             self._lib.nbc_destroy(self._ctx)
             self._ctx = C.c_void_p()
         self._blob_dev = None
+        self._lovasz_ws = None
 
     def __del__(self):
         try:
