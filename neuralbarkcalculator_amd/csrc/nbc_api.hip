@@ -1,4 +1,4 @@
-// Context, launch plan and the forward entry point of libnbc_hip.so.
+// Context, plan cache, forward entry point and autotune of libnbc_hip.so; the launch plan itself is built in nbc_plan.cpp.
 //
 // nbc_forward replaces, at the C ABI, `outputs = self.model(batch[0].to(self.device))` followed
 // by `torch.argmax(outputs, dim=1)` (/root/reference/src/bark_calculator/models.py:269-270).
@@ -17,10 +17,9 @@
 #include "nbc_internal.hpp"
 #include "nbc_kernels.hpp"
 #include "nbc_net.hpp"
+#include "nbc_plan.hpp"
 
 using namespace nbc;
-
-namespace {
 
 #define NBC_HIP(expr)                                                                         \
   do {                                                                                        \
@@ -28,44 +27,6 @@ namespace {
     if (_e != hipSuccess)                                                                     \
       return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
-
-enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT, OP_BN_STATS, OP_BN_APPLY,
-              OP_DWCONV, OP_SE_EXCITE, OP_GATE_WEIGHTS, OP_SWISH, OP_POOL_ANY };
-
-struct Op {
-  OpKind kind;
-  int unit;            // conv unit index (OP_CONV / OP_HEAD1X1 / OP_ASPP_POOL), -1 otherwise
-  int in_buf, out_buf, res_buf;
-  int Hi, Wi, Ci, Ho, Wo, Co;
-  std::string name;
-  double flops, bytes;
-  int tile;            // OP_CONV: tile id of the LDS-DMA kernel (default choice or autotuned)
-  int rows;            // OP_CONV: conv_rows_kind: 0 generic tiles, 1 / 2 the row-resident 3x3 kernel (kind 1: tiles 18 or 20; kind 2: tile 19)
-  int ws_buf;          // OP_ASPP_POOL: workspace buffer (slice partials, then the per-image means)
-  int cat_in[5];       // OP_CONCAT: the four spatial branches' buffers and the pooled vectors' buffer
-  bool raw;            // OP_CONV in NBC_BN_PER_IMAGE: unit scale, zero shift, no ReLU, no identity (the raw conv output)
-  int relu;            // OP_BN_APPLY: the unit's ReLU
-  size_t affine_off;   // OP_BN_STATS: floats before the unit's (gamma, beta) in the affine array
-  // EfficientNet
-  int gate_buf = -1;   // OP_CONV: per-image weights [N][Co][Ci] (the SE-gated project conv: one launch per image);
-                       // OP_SE_EXCITE / OP_GATE_WEIGHTS: the gate [N][C]
-  int creal = 0;       // channels of the tensor the network defines (0 = Co): nbc_read_activation drops the pad channels
-  int launches = 1;    // launches of the op per forward (profiling records)
-  int tiles = 0;       // OP_DWCONV / OP_SE_EXCITE: SE squeeze partials per image
-  int aux_unit = -1;   // OP_SE_EXCITE: the _se_expand unit (unit = _se_reduce); OP_GATE_WEIGHTS: the project unit
-};
-
-struct Plan {
-  int N = 0, H = 0, W = 0, precision = -1, arch = 0;
-  bool keep = false;
-  int bn = NBC_BN_RUNNING;             // NBC_BN_*
-  size_t bn_ws_bytes = 0;              // NBC_BN_PER_IMAGE: slice partials + [N][C] scale and shift of the largest BatchNorm
-  int h = 0, w = 0;                    // low-res logits size
-  std::vector<Op> ops;
-  std::vector<size_t> buf_bytes;       // per activation buffer
-};
-
-}  // namespace
 
 struct nbc_ctx {
   int device = 0;
@@ -112,11 +73,10 @@ namespace {
 
 constexpr size_t kPlanCacheEntries = 64;
 
-bool same_shape(const Plan& p, int N, int H, int W, int precision, bool keep, int arch, int bn) {
-  return p.N == N && p.H == H && p.W == W && p.precision == precision && p.keep == keep && p.arch == arch && p.bn == bn;
-}
-bool same_plan(const Plan& p, const nbc_ctx* c, int N, int H, int W) {
-  return same_shape(p, N, H, W, c->precision, c->keep, c->arch, c->bn_mode);
+PlanKey plan_key(const nbc_ctx* c, int N, int H, int W) {
+  PlanKey k;
+  k.N = N; k.H = H; k.W = W; k.precision = c->precision; k.arch = c->arch; k.keep = c->keep; k.bn = c->bn_mode;
+  return k;
 }
 
 // Park the current plan (folders of height-trimmed images alternate between a few shapes: each keeps
@@ -125,372 +85,12 @@ void stash_plan(nbc_ctx* c) {
   Plan& cur = c->plan;
   if (cur.N == 0) return;
   for (Plan& p : c->plan_cache)
-    if (same_shape(p, cur.N, cur.H, cur.W, cur.precision, cur.keep, cur.arch, cur.bn)) {
+    if (same_shape(p, cur)) {
       p = cur; cur = Plan(); return;
     }
   if (c->plan_cache.size() >= kPlanCacheEntries) c->plan_cache.erase(c->plan_cache.begin());
   c->plan_cache.push_back(cur);
   cur = Plan();
-}
-
-// Build the launch list for an (N,H,W).  Activation buffers are recycled through a small pool
-// unless `keep` asks for one buffer per op (layer-by-layer parity tests).
-int build_plan_effnet(nbc_ctx* c, int N, int H, int W);
-
-int build_plan(nbc_ctx* c, int N, int H, int W) {
-  if (is_effnet(c->arch)) return build_plan_effnet(c, N, H, W);
-  Plan P;
-  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch; P.bn = c->bn_mode;
-  const int eb = elem_bytes(c->precision);
-  const auto& units = conv_units(c->arch);
-  const auto& L = c->layout;
-  const bool per_image = P.bn == NBC_BN_PER_IMAGE;
-  std::vector<size_t> affine_off(units.size(), 0);     // per unit: floats of the affine array before its (gamma, beta)
-  for (size_t u = 0, off = 0; u < units.size(); ++u)
-    if (!units[u].bn.empty()) { affine_off[u] = off; off += 2 * (size_t)units[u].cout; }
-
-  std::vector<bool> in_use;
-  auto acquire = [&](size_t bytes) {
-    if (!P.keep)
-      for (size_t i = 0; i < in_use.size(); ++i)
-        if (!in_use[i]) { in_use[i] = true; P.buf_bytes[i] = std::max(P.buf_bytes[i], bytes); return (int)i; }
-    in_use.push_back(true);
-    P.buf_bytes.push_back(bytes);
-    return (int)in_use.size() - 1;
-  };
-  auto release = [&](int b) { if (b >= 0 && !P.keep) in_use[b] = false; };
-
-  auto conv_out = [](int x, int k, int s, int p, int d) { return (x + 2 * p - d * (k - 1) - 1) / s + 1; };
-
-  // ingest: image -> NHWC with one 16-byte pixel
-  const int cin_img = kChunkBytes / eb;
-  int cur = acquire((size_t)N * H * W * kChunkBytes);
-  {
-    Op o{};
-    o.kind = OP_INGEST; o.unit = -1; o.in_buf = -1; o.out_buf = cur; o.res_buf = -1;
-    o.Hi = H; o.Wi = W; o.Ci = 3; o.Ho = H; o.Wo = W; o.Co = cin_img; o.name = "ingest";
-    P.ops.push_back(o);
-  }
-  int curH = H, curW = W, curC = cin_img;
-
-  std::string refused;                                  // per image: the first BatchNorm that would see one value per channel
-  auto add_conv = [&](int ui, int in_buf, int inH, int inW, int inC, int res_buf, int* oH, int* oW) {
-    const ConvUnit& u = units[ui];
-    const int Ho = conv_out(inH, u.k, u.stride, u.pad, u.dil);
-    const int Wo = conv_out(inW, u.k, u.stride, u.pad, u.dil);
-    const bool bn_ops = per_image && !u.bn.empty();     // raw conv, then <bn>.stats and <bn>.apply (with the identity)
-    const int idt = res_buf;
-    if (bn_ops) res_buf = -1;
-    Op o{};
-    o.kind = OP_CONV; o.unit = ui; o.in_buf = in_buf; o.res_buf = res_buf; o.raw = bn_ops;
-    o.Hi = inH; o.Wi = inW; o.Ci = inC; o.Ho = Ho; o.Wo = Wo; o.Co = u.cout; o.name = u.name;
-    o.out_buf = acquire((size_t)N * Ho * Wo * u.cout * eb);
-    o.rows = conv_rows_kind(c->precision, u.k, u.stride, u.pad, u.dil, inH, inW, Ho, Wo, inC, u.cout, res_buf >= 0);
-    o.tile = choose_conv_tile(N * Ho * Wo, u.cout, u.cin * u.k * u.k, c->precision, o.rows);
-    const double M = (double)N * Ho * Wo;
-    o.flops = 2.0 * M * u.cout * u.cin * u.k * u.k;
-    o.bytes = ((double)N * inH * inW * u.cin + (double)u.cout * u.cin * u.k * u.k + M * u.cout +
-               (res_buf >= 0 ? M * u.cout : 0.0)) * eb;
-    P.ops.push_back(o);
-    if (bn_ops) {
-      // F.batch_norm(training=True) of a batch of one refuses a map of one pixel; so does this mode, for every image
-      if (Ho * Wo == 1 && refused.empty())
-        refused = "Expected more than 1 value per channel when training, got input size [1, " + std::to_string(u.cout) +
-                  ", 1, 1] (" + u.bn + " of a " + std::to_string(H) + "x" + std::to_string(W) + " image; per-image BatchNorm)";
-      const int hw = Ho * Wo;
-      Op st = o;
-      st.kind = OP_BN_STATS; st.in_buf = o.out_buf; st.res_buf = -1; st.raw = false; st.name = u.bn + ".stats";
-      st.affine_off = affine_off[ui];
-      st.flops = 3.0 * M * u.cout;
-      st.bytes = M * u.cout * 4.0 + (double)N * bn_stats_slices(hw) * u.cout * 16.0;
-      P.ops.push_back(st);
-      Op ap = o;
-      ap.kind = OP_BN_APPLY; ap.in_buf = o.out_buf; ap.res_buf = idt; ap.raw = false; ap.name = u.bn + ".apply";
-      ap.relu = u.relu ? 1 : 0;
-      ap.flops = 2.0 * M * u.cout;
-      ap.bytes = (2.0 + (idt >= 0 ? 1.0 : 0.0)) * M * u.cout * 4.0;
-      P.ops.push_back(ap);
-      P.bn_ws_bytes = std::max(P.bn_ws_bytes, bn_stats_workspace_bytes(N, hw, u.cout));
-    }
-    *oH = Ho; *oW = Wo;
-    return o.out_buf;
-  };
-
-  size_t ui = 0;
-  // stem
-  {
-    int oH, oW;
-    const int b = add_conv(0, cur, curH, curW, curC, -1, &oH, &oW);
-    release(cur);
-    cur = b; curH = oH; curW = oW; curC = units[0].cout;
-    const int pH = (curH - 1) / 2 + 1, pW = (curW - 1) / 2 + 1;
-    Op o{};
-    o.kind = OP_MAXPOOL; o.unit = -1; o.in_buf = cur; o.res_buf = -1;
-    o.Hi = curH; o.Wi = curW; o.Ci = curC; o.Ho = pH; o.Wo = pW; o.Co = curC; o.name = "backbone.maxpool";
-    o.out_buf = acquire((size_t)N * pH * pW * curC * eb);
-    o.bytes = ((double)N * curH * curW * curC + (double)N * pH * pW * curC) * eb;
-    P.ops.push_back(o);
-    release(cur);
-    cur = o.out_buf; curH = pH; curW = pW;
-    ui = 1;
-  }
-  // bottlenecks
-  while (ui < units.size() && units[ui].block_first) {
-    int h1, w1, h2, w2, h3, w3;
-    const int t1 = add_conv((int)ui, cur, curH, curW, curC, -1, &h1, &w1);
-    const int t2 = add_conv((int)ui + 1, t1, h1, w1, units[ui].cout, -1, &h2, &w2);
-    release(t1);
-    int idt = cur;
-    size_t c3 = ui + 2;
-    if (!units[ui + 2].residual) {      // downsample present
-      int hd, wd;
-      idt = add_conv((int)ui + 2, cur, curH, curW, curC, -1, &hd, &wd);
-      release(cur);
-      c3 = ui + 3;
-    }
-    const int out = add_conv((int)c3, t2, h2, w2, units[ui + 1].cout, idt, &h3, &w3);
-    release(t2);
-    release(idt);
-    cur = out; curH = h3; curW = w3; curC = units[c3].cout;
-    ui = c3 + 1;
-  }
-  // head
-  {
-    int oH, oW, t, cls = (int)ui + 1;                                        // classifier.4's unit
-    if (c->arch == kArchDeepLab) {
-      // ASPP: four convolutions and the pooling branch all read layer4's output (`cur`), which stays acquired until the
-      // last of them; the concat then copies the five into one [M][1280] tensor.  Then project, classifier.1.
-      int br[4];
-      for (int b = 0; b < 4; ++b) br[b] = add_conv((int)ui + b, cur, curH, curW, curC, -1, &oH, &oW);
-      const int hw = curH * curW, B = units[ui + 4].cout;
-      const int ws = acquire(((size_t)N * aspp_pool_slices(hw) + N) * curC * sizeof(float));
-      Op po{};
-      po.kind = OP_ASPP_POOL; po.unit = (int)ui + 4; po.in_buf = cur; po.res_buf = -1; po.ws_buf = ws;
-      po.Hi = curH; po.Wi = curW; po.Ci = curC; po.Ho = 1; po.Wo = 1; po.Co = B;
-      po.name = "classifier.0.convs.4";                                      // the pooled vector: one pixel per image
-      po.out_buf = acquire((size_t)N * B * eb);
-      po.flops = 2.0 * N * B * curC + (double)N * hw * curC;
-      po.bytes = (double)N * hw * curC * eb + (double)B * curC * 4 + (double)N * B * eb;
-      P.ops.push_back(po);
-      release(ws);
-      release(cur);
-      Op co{};
-      co.kind = OP_CONCAT; co.unit = -1; co.in_buf = -1; co.res_buf = -1;
-      for (int b = 0; b < 4; ++b) co.cat_in[b] = br[b];
-      co.cat_in[4] = po.out_buf;
-      co.Hi = oH; co.Wi = oW; co.Ci = 5 * B; co.Ho = oH; co.Wo = oW; co.Co = 5 * B;
-      co.name = "classifier.0.concat";
-      co.out_buf = acquire((size_t)N * hw * 5 * B * eb);
-      co.bytes = 2.0 * N * hw * 5 * B * eb;
-      P.ops.push_back(co);
-      for (int b = 0; b < 5; ++b) release(co.cat_in[b]);
-      const int pj = add_conv((int)ui + 5, co.out_buf, oH, oW, 5 * B, -1, &oH, &oW);   // classifier.0.project
-      release(co.out_buf);
-      t = add_conv((int)ui + 6, pj, oH, oW, B, -1, &oH, &oW);                 // classifier.1
-      release(pj);
-      cls = (int)ui + 7;
-    } else {
-      t = add_conv((int)ui, cur, curH, curW, curC, -1, &oH, &oW);            // classifier.0
-      release(cur);
-    }
-    Op o{};
-    o.kind = OP_HEAD1X1; o.unit = cls; o.in_buf = t; o.out_buf = -1; o.res_buf = -1;
-    o.Hi = oH; o.Wi = oW; o.Ci = units[cls].cin; o.Ho = oH; o.Wo = oW; o.Co = kNumClasses;
-    o.name = units[cls].name;
-    o.flops = 2.0 * N * oH * oW * o.Ci * kNumClasses;
-    o.bytes = (double)N * oH * oW * o.Ci * eb + (double)N * oH * oW * kNumClasses * 4;
-    P.ops.push_back(o);
-    release(t);
-    P.h = oH; P.w = oW;
-    Op up{};
-    up.kind = OP_UPSAMPLE; up.unit = -1; up.in_buf = -1; up.out_buf = -1; up.res_buf = -1;
-    up.Hi = oH; up.Wi = oW; up.Ci = kNumClasses; up.Ho = H; up.Wo = W; up.Co = kNumClasses;
-    up.name = "upsample_argmax";
-    up.bytes = (double)N * oH * oW * kNumClasses * 4 + (double)N * H * W;
-    P.ops.push_back(up);
-  }
-  (void)L;
-  if (!refused.empty()) return set_error(NBC_ERR_INVALID, refused);
-
-  c->plan = P;
-  return NBC_OK;
-}
-
-// EfficientNet (fp32): ingest, the stem on conv_dma (its swish deferred), per MBConv block [expand conv (swish deferred)],
-// depthwise conv (+ BN, swish, SE squeeze partials), SE excite (gate), gated project weights, project conv per image
-// (+ identity), then the head conv with a swish pass and the FCN / DeepLab head.  Channels padded (ConvUnit::outc).
-int build_plan_effnet(nbc_ctx* c, int N, int H, int W) {
-  Plan P;
-  P.N = N; P.H = H; P.W = W; P.precision = c->precision; P.keep = c->keep; P.arch = c->arch; P.bn = c->bn_mode;
-  const auto& units = conv_units(c->arch);
-  std::vector<bool> in_use;
-  auto acquire = [&](size_t bytes) {
-    if (!P.keep)
-      for (size_t i = 0; i < in_use.size(); ++i)
-        if (!in_use[i]) { in_use[i] = true; P.buf_bytes[i] = std::max(P.buf_bytes[i], bytes); return (int)i; }
-    in_use.push_back(true);
-    P.buf_bytes.push_back(bytes);
-    return (int)in_use.size() - 1;
-  };
-  auto release = [&](int b) { if (b >= 0 && !P.keep) in_use[b] = false; };
-  std::string err;
-  // a conv_dma launch of unit ui; gate_buf >= 0: per image on the gated weights
-  auto add_conv = [&](int ui, int in_buf, int inH, int inW, int res_buf, int gate_buf, int* oH, int* oW) {
-    const ConvUnit& u = units[ui];
-    const int keff = u.dil * (u.k - 1) + 1;                          // the dilated extent (ASPP)
-    const int Ho = same_out(inH, keff, u.stride, u.pad, u.pad_end());
-    const int Wo = same_out(inW, keff, u.stride, u.pad, u.pad_end());
-    if ((Ho < 1 || Wo < 1) && err.empty())
-      err = "nbc_forward: a " + std::to_string(H) + "x" + std::to_string(W) + " image is too small for " + arch_name(c->arch) +
-            " (" + u.name + " has no output pixel)";
-    Op o{};
-    o.kind = OP_CONV; o.unit = ui; o.in_buf = in_buf; o.res_buf = res_buf; o.gate_buf = gate_buf;
-    o.Hi = inH; o.Wi = inW; o.Ci = u.inc(); o.Ho = Ho; o.Wo = Wo; o.Co = u.outc(); o.creal = u.cout; o.name = u.name;
-    o.out_buf = acquire((size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * u.outc() * 4);
-    o.rows = 0;
-    const int Mt = (gate_buf >= 0 ? 1 : N) * std::max(Ho * Wo, 1);
-    o.tile = choose_conv_tile(Mt, u.outc(), u.inc() * u.k * u.k, c->precision, 0);
-    o.launches = gate_buf >= 0 ? N : 1;
-    const double M = (double)N * Ho * Wo;
-    o.flops = 2.0 * M * u.cout * u.cin * u.k * u.k;
-    o.bytes = ((double)N * inH * inW * u.inc() + (double)u.outc() * u.inc() * u.k * u.k * (gate_buf >= 0 ? N : 1) + M * u.outc() +
-               (res_buf >= 0 ? M * u.outc() : 0.0)) * 4;
-    P.ops.push_back(o);
-    *oH = Ho; *oW = Wo;
-    return o.out_buf;
-  };
-
-  int cur = acquire((size_t)N * H * W * kChunkBytes);
-  {
-    Op o{};
-    o.kind = OP_INGEST; o.unit = -1; o.in_buf = -1; o.out_buf = cur; o.res_buf = -1;
-    o.Hi = H; o.Wi = W; o.Ci = 3; o.Ho = H; o.Wo = W; o.Co = kChunkBytes / 4; o.creal = 3; o.name = "ingest";
-    P.ops.push_back(o);
-  }
-  int curH = H, curW = W;
-  {
-    int oH, oW;
-    const int b = add_conv(0, cur, curH, curW, -1, -1, &oH, &oW);   // _conv_stem: BN, swish deferred
-    release(cur);
-    cur = b; curH = oH; curW = oW;
-  }
-  size_t ui = 1;
-  while (ui < units.size() && units[ui].block >= 0) {
-    const int in = cur, inH = curH, inW = curW;
-    int e = in, eH = inH, eW = inW;
-    if (units[ui].kind == kUnitConv) {                                // _expand_conv
-      e = add_conv((int)ui, in, inH, inW, -1, -1, &eH, &eW);
-      ++ui;
-    }
-    const ConvUnit& dw = units[ui];
-    const int C = dw.outc();
-    const int Ho = same_out(eH, dw.k, dw.stride, dw.pad, dw.pad_end()), Wo = same_out(eW, dw.k, dw.stride, dw.pad, dw.pad_end());
-    if ((Ho < 1 || Wo < 1) && err.empty())
-      err = "nbc_forward: a " + std::to_string(H) + "x" + std::to_string(W) + " image is too small for " + arch_name(c->arch) +
-            " (" + dw.name + " has no output pixel)";
-    const int tiles = dwconv_tiles(dw.stride, std::max(Ho, 1), std::max(Wo, 1));
-    const int ws = acquire((size_t)N * tiles * C * 4);
-    Op d{};
-    d.kind = OP_DWCONV; d.unit = (int)ui; d.in_buf = e; d.res_buf = -1; d.ws_buf = ws; d.tiles = tiles;
-    d.Hi = eH; d.Wi = eW; d.Ci = C; d.Ho = Ho; d.Wo = Wo; d.Co = C; d.creal = dw.cout; d.name = dw.name;
-    d.out_buf = acquire((size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * C * 4);
-    d.flops = 2.0 * N * Ho * Wo * dw.cout * dw.k * dw.k;
-    d.bytes = ((double)N * eH * eW * C + (double)N * Ho * Wo * C) * 4;
-    P.ops.push_back(d);
-    if (e != in) release(e);
-    const ConvUnit& red = units[ui + 1];
-    const ConvUnit& exc = units[ui + 2];
-    const ConvUnit& prj = units[ui + 3];
-    const int gate = acquire((size_t)N * C * 4);
-    Op se{};
-    se.kind = OP_SE_EXCITE; se.unit = (int)ui + 1; se.aux_unit = (int)ui + 2; se.in_buf = ws; se.res_buf = -1; se.tiles = tiles;
-    se.out_buf = gate; se.gate_buf = gate;
-    se.Hi = Ho; se.Wi = Wo; se.Ci = C; se.Ho = 1; se.Wo = 1; se.Co = C; se.creal = exc.cout; se.name = exc.name;
-    se.flops = 4.0 * N * C * red.cout;
-    se.bytes = ((double)N * tiles * C + 2.0 * C * red.cout + (double)N * C) * 4;
-    P.ops.push_back(se);
-    release(ws);
-    const int wg = acquire((size_t)N * prj.outc() * prj.inc() * 4);
-    Op gw{};
-    gw.kind = OP_GATE_WEIGHTS; gw.unit = (int)ui + 3; gw.in_buf = -1; gw.out_buf = -1; gw.res_buf = -1; gw.ws_buf = wg;
-    gw.gate_buf = gate; gw.Ci = prj.inc(); gw.Co = prj.outc(); gw.name = prj.name + ".gated_weights";
-    gw.flops = (double)N * prj.outc() * prj.inc();
-    gw.bytes = ((double)prj.outc() * prj.inc() * (1 + N) + (double)N * C) * 4;
-    P.ops.push_back(gw);
-    release(gate);
-    int pH, pW;
-    const int out = add_conv((int)ui + 3, d.out_buf, Ho, Wo, prj.residual ? in : -1, wg, &pH, &pW);
-    release(d.out_buf);
-    release(wg);
-    release(in);
-    cur = out; curH = pH; curW = pW;
-    ui += 4;
-  }
-  {
-    int oH, oW;
-    const int h = add_conv((int)ui, cur, curH, curW, -1, -1, &oH, &oW);   // _conv_head, then its swish in place
-    release(cur);
-    Op sw{};
-    sw.kind = OP_SWISH; sw.unit = (int)ui; sw.in_buf = h; sw.out_buf = h; sw.res_buf = -1;
-    sw.Hi = oH; sw.Wi = oW; sw.Ci = units[ui].outc(); sw.Ho = oH; sw.Wo = oW; sw.Co = units[ui].outc(); sw.creal = units[ui].cout;
-    sw.name = units[ui].name + ".swish";
-    sw.flops = (double)N * oH * oW * units[ui].cout * 4;
-    sw.bytes = 2.0 * N * oH * oW * units[ui].outc() * 4;
-    P.ops.push_back(sw);
-    cur = h; curH = oH; curW = oW;
-    ++ui;
-  }
-  int oH = curH, oW = curW, t, cls = (int)ui + 1;
-  if (is_deeplab_head(c->arch)) {
-    int br[4];
-    for (int b = 0; b < 4; ++b) br[b] = add_conv((int)ui + b, cur, curH, curW, -1, -1, &oH, &oW);
-    const ConvUnit& pu = units[ui + 4];
-    const int hw = curH * curW, B = pu.cout;
-    const int ws = acquire((size_t)N * pool_any_slices(std::max(hw, 1)) * pu.cin * 4);
-    Op po{};
-    po.kind = OP_POOL_ANY; po.unit = (int)ui + 4; po.in_buf = cur; po.res_buf = -1; po.ws_buf = ws;
-    po.Hi = curH; po.Wi = curW; po.Ci = pu.cin; po.Ho = 1; po.Wo = 1; po.Co = B; po.name = "classifier.0.convs.4";
-    po.out_buf = acquire((size_t)N * B * 4);
-    po.launches = 2;
-    po.flops = 2.0 * N * B * pu.cin + (double)N * hw * pu.cin;
-    po.bytes = (double)N * hw * pu.cin * 4 + (double)B * pu.cin * 4 + (double)N * B * 4;
-    P.ops.push_back(po);
-    release(ws);
-    release(cur);
-    Op co{};
-    co.kind = OP_CONCAT; co.unit = -1; co.in_buf = -1; co.res_buf = -1;
-    for (int b = 0; b < 4; ++b) co.cat_in[b] = br[b];
-    co.cat_in[4] = po.out_buf;
-    co.Hi = oH; co.Wi = oW; co.Ci = 5 * B; co.Ho = oH; co.Wo = oW; co.Co = 5 * B; co.name = "classifier.0.concat";
-    co.out_buf = acquire((size_t)N * hw * 5 * B * 4);
-    co.bytes = 2.0 * N * hw * 5 * B * 4;
-    P.ops.push_back(co);
-    for (int b = 0; b < 5; ++b) release(co.cat_in[b]);
-    const int pj = add_conv((int)ui + 5, co.out_buf, oH, oW, -1, -1, &oH, &oW);
-    release(co.out_buf);
-    t = add_conv((int)ui + 6, pj, oH, oW, -1, -1, &oH, &oW);
-    release(pj);
-    cls = (int)ui + 7;
-  } else {
-    t = add_conv((int)ui, cur, curH, curW, -1, -1, &oH, &oW);             // classifier.0
-    release(cur);
-  }
-  Op o{};
-  o.kind = OP_HEAD1X1; o.unit = cls; o.in_buf = t; o.out_buf = -1; o.res_buf = -1;
-  o.Hi = oH; o.Wi = oW; o.Ci = units[cls].inc(); o.Ho = oH; o.Wo = oW; o.Co = kNumClasses; o.name = units[cls].name;
-  o.flops = 2.0 * N * oH * oW * units[cls].cin * kNumClasses;
-  o.bytes = (double)N * oH * oW * o.Ci * 4 + (double)N * oH * oW * kNumClasses * 4;
-  P.ops.push_back(o);
-  release(t);
-  P.h = oH; P.w = oW;
-  Op up{};
-  up.kind = OP_UPSAMPLE; up.unit = -1; up.in_buf = -1; up.out_buf = -1; up.res_buf = -1;
-  up.Hi = oH; up.Wi = oW; up.Ci = kNumClasses; up.Ho = H; up.Wo = W; up.Co = kNumClasses; up.name = "upsample_argmax";
-  up.bytes = (double)N * oH * oW * kNumClasses * 4 + (double)N * H * W;
-  P.ops.push_back(up);
-  if (!err.empty()) return set_error(NBC_ERR_INVALID, err);
-  c->plan = P;
-  return NBC_OK;
 }
 
 // Workspace of the current plan: buffers only ever grow, so a plan taken back from the cache finds
@@ -542,18 +142,30 @@ int ensure_buffers(nbc_ctx* c) {
   return NBC_OK;
 }
 
+// A conv unit's arrays in the attached blob: f32 but for w of a conv_dma unit (panels of the precision's elements).
+struct UnitPtrs {
+  const float* w;
+  const float* scale;
+  const float* shift;
+};
+UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
+  const PackedConv& pc = c->layout.convs[unit];
+  return {reinterpret_cast<const float*>(c->weights + pc.w_off), reinterpret_cast<const float*>(c->weights + pc.scale_off),
+          reinterpret_cast<const float*>(c->weights + pc.shift_off)};
+}
+
 // One convolution launch of the plan (shared by nbc_forward and nbc_autotune).
 int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipError_t* err) {
-  const auto& units = conv_units(c->arch);
-  const ConvUnit& u = units[o.unit];
+  const ConvUnit& u = conv_units(c->arch)[o.unit];
   const PackedConv& pc = c->layout.convs[o.unit];
+  const UnitPtrs p = unit_ptrs(c, o.unit);
   const int prec = c->precision;
   const size_t eb = elem_bytes(prec);
   ConvArgs a{};
   a.x = c->bufs[o.in_buf];
-  a.w = c->weights + pc.w_off;
-  a.scale = reinterpret_cast<const float*>(c->weights + pc.scale_off);
-  a.shift = reinterpret_cast<const float*>(c->weights + pc.shift_off);
+  a.w = p.w;
+  a.scale = p.scale;
+  a.shift = p.shift;
   a.res = o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr;
   if (o.raw) {                                         // per-image BatchNorm follows: fma(acc, 1, 0) = acc in f32
     if (o.Co > 2048) return set_error(NBC_ERR_STATE, "raw convolution wider than the unit table at " + o.name);
@@ -911,14 +523,15 @@ int nbc_reserve(nbc_ctx* c, int N, int H, int W) {
                                       "(nbc_attach_bn_affine)");
   }
   NBC_HIP(hipSetDevice(c->device));
-  if (same_plan(c->plan, c, N, H, W)) return NBC_OK;
+  const PlanKey key = plan_key(c, N, H, W);
+  if (same_shape(c->plan, key)) return NBC_OK;
   stash_plan(c);
   bool found = false;
   for (const Plan& p : c->plan_cache)
-    if (same_plan(p, c, N, H, W)) { c->plan = p; found = true; break; }
+    if (same_shape(p, key)) { c->plan = p; found = true; break; }
   if (!found) {
-    int rc = build_plan(c, N, H, W);
-    if (rc != NBC_OK) return rc;
+    const std::string refused = build_plan(key, &c->plan);
+    if (!refused.empty()) return set_error(NBC_ERR_INVALID, refused);
   }
   int rc = ensure_buffers(c);
   if (rc != NBC_OK) c->plan = Plan();
@@ -943,14 +556,13 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   }
 
   const size_t nops = P.ops.size();
-  const size_t nl = nops;                              // one launch per op
   constexpr size_t kMaxProfSets = 4096;
   std::vector<hipEvent_t>* evs = nullptr;
   if (c->profiling && c->prof_used < kMaxProfSets) {
     if (c->prof_used > 0 && c->prof_ops.size() != nops) c->prof_used = 0;   // plan changed: restart
     if (c->prof_sets.size() <= c->prof_used) c->prof_sets.emplace_back();
     evs = &c->prof_sets[c->prof_used];
-    while (evs->size() < nl + 1) {
+    while (evs->size() < nops + 1) {
       hipEvent_t ev;
       NBC_HIP(hipEventCreate(&ev));
       evs->push_back(ev);
@@ -961,7 +573,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   float* lowres = logits_lowres_dev ? logits_lowres_dev : c->lowres;
 
   if (evs) NBC_HIP(hipEventRecord((*evs)[0], s));
-  for (size_t l = 0; l < nl; ++l) {
+  for (size_t l = 0; l < nops; ++l) {
     const Op& o = P.ops[l];
     hipError_t e = hipSuccess;
     int rc = NBC_OK;
@@ -984,32 +596,25 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         e = launch_maxpool3x3s2(c->bufs[o.in_buf], c->bufs[o.out_buf], N, o.Hi, o.Wi, o.Ci, o.Ho, o.Wo, prec, s);
         break;
       case OP_HEAD1X1: {
-        const PackedConv& pc = c->layout.convs[o.unit];
+        const UnitPtrs p = unit_ptrs(c, o.unit);
         if (o.Ci != 512 && o.Ci != 256 && !is_effnet(c->arch))
           return set_error(NBC_ERR_STATE, "classifier.4 expects 512 or 256 input channels");
         // also clears this launch's share of the counters (3 per image) when the batch has at most 256 of them
         unsigned long long* cz = counts_dev && 3 * N <= 256 ? reinterpret_cast<unsigned long long*>(counts_dev) : nullptr;
         if (is_effnet(c->arch) && o.Ci != 256)             // FCNHead(inplanes, 3): inplanes / 4 channels, padded
-          e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf]), reinterpret_cast<const float*>(c->weights + pc.w_off),
-                                 reinterpret_cast<const float*>(c->weights + pc.shift_off), lowres, N, o.Ho * o.Wo, o.Ci, cz,
+          e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf]), p.w, p.shift, lowres, N, o.Ho * o.Wo, o.Ci, cz,
                                  c->nonfinite, s);
         else if (o.Ci == 512)
-          e = launch_head1x1(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
-                             reinterpret_cast<const float*>(c->weights + pc.shift_off),
-                             lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+          e = launch_head1x1(c->bufs[o.in_buf], p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
         else
-          e = launch_head1x1_c256(c->bufs[o.in_buf], reinterpret_cast<const float*>(c->weights + pc.w_off),
-                                  reinterpret_cast<const float*>(c->weights + pc.shift_off),
-                                  lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+          e = launch_head1x1_c256(c->bufs[o.in_buf], p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
         break;
       }
       case OP_ASPP_POOL: {
-        const PackedConv& pc = c->layout.convs[o.unit];
+        const UnitPtrs p = unit_ptrs(c, o.unit);
         float* partial = static_cast<float*>(c->bufs[o.ws_buf]);
         float* mean = partial + (size_t)N * aspp_pool_slices(o.Hi * o.Wi) * o.Ci;
-        e = launch_aspp_pool(c->bufs[o.in_buf], N, o.Hi * o.Wi, o.Ci, reinterpret_cast<const float*>(c->weights + pc.w_off),
-                             reinterpret_cast<const float*>(c->weights + pc.scale_off),
-                             reinterpret_cast<const float*>(c->weights + pc.shift_off), o.Co, partial, mean, c->bufs[o.out_buf],
+        e = launch_aspp_pool(c->bufs[o.in_buf], N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co, partial, mean, c->bufs[o.out_buf],
                              prec, s);
         break;
       }
@@ -1036,13 +641,13 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         break;
       }
       case OP_DWCONV: {
-        const PackedConv& pc = c->layout.convs[o.unit];
+        const UnitPtrs p = unit_ptrs(c, o.unit);
         const ConvUnit& u = conv_units(c->arch)[o.unit];
         DwArgs a{};
         a.x = static_cast<const float*>(c->bufs[o.in_buf]);
-        a.w = reinterpret_cast<const float*>(c->weights + pc.w_off);
-        a.scale = reinterpret_cast<const float*>(c->weights + pc.scale_off);
-        a.shift = reinterpret_cast<const float*>(c->weights + pc.shift_off);
+        a.w = p.w;
+        a.scale = p.scale;
+        a.shift = p.shift;
         a.y = static_cast<float*>(c->bufs[o.out_buf]);
         a.partial = static_cast<float*>(c->bufs[o.ws_buf]);
         a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.C = o.Co; a.Ho = o.Ho; a.Wo = o.Wo;
@@ -1051,30 +656,23 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         break;
       }
       case OP_SE_EXCITE: {
-        const PackedConv& pr = c->layout.convs[o.unit];
-        const PackedConv& pe = c->layout.convs[o.aux_unit];
+        const UnitPtrs pr = unit_ptrs(c, o.unit), pe = unit_ptrs(c, o.aux_unit);
         const ConvUnit& ur = conv_units(c->arch)[o.unit];
-        e = launch_se_excite(static_cast<const float*>(c->bufs[o.in_buf]), N, o.tiles, o.Co, o.Hi * o.Wi,
-                             reinterpret_cast<const float*>(c->weights + pr.w_off), reinterpret_cast<const float*>(c->weights + pr.shift_off),
-                             ur.cout, reinterpret_cast<const float*>(c->weights + pe.w_off),
-                             reinterpret_cast<const float*>(c->weights + pe.shift_off), static_cast<float*>(c->bufs[o.out_buf]), s);
+        e = launch_se_excite(static_cast<const float*>(c->bufs[o.in_buf]), N, o.tiles, o.Co, o.Hi * o.Wi, pr.w, pr.shift, ur.cout,
+                             pe.w, pe.shift, static_cast<float*>(c->bufs[o.out_buf]), s);
         break;
       }
-      case OP_GATE_WEIGHTS: {
-        const PackedConv& pc = c->layout.convs[o.unit];
-        e = launch_gate_weights(reinterpret_cast<const float*>(c->weights + pc.w_off), static_cast<const float*>(c->bufs[o.gate_buf]),
+      case OP_GATE_WEIGHTS:
+        e = launch_gate_weights(unit_ptrs(c, o.unit).w, static_cast<const float*>(c->bufs[o.gate_buf]),
                                 static_cast<float*>(c->bufs[o.ws_buf]), N, o.Co, o.Ci, s);
         break;
-      }
       case OP_SWISH:
         e = launch_swish(static_cast<float*>(c->bufs[o.out_buf]), (size_t)N * o.Ho * o.Wo * o.Co, s);
         break;
       case OP_POOL_ANY: {
-        const PackedConv& pc = c->layout.convs[o.unit];
-        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf]), N, o.Hi * o.Wi, o.Ci,
-                            reinterpret_cast<const float*>(c->weights + pc.w_off), reinterpret_cast<const float*>(c->weights + pc.scale_off),
-                            reinterpret_cast<const float*>(c->weights + pc.shift_off), o.Co, static_cast<float*>(c->bufs[o.ws_buf]),
-                            static_cast<float*>(c->bufs[o.out_buf]), s);
+        const UnitPtrs p = unit_ptrs(c, o.unit);
+        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf]), N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co,
+                            static_cast<float*>(c->bufs[o.ws_buf]), static_cast<float*>(c->bufs[o.out_buf]), s);
         break;
       }
       case OP_UPSAMPLE:
@@ -1148,16 +746,15 @@ int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W
   for (size_t oi = 0; oi < P.ops.size(); ++oi) {
     Op& o = P.ops[oi];
     if (o.kind != OP_CONV) continue;
-    const int NB = N;
     float best_ms = 1e30f;
     int best = o.tile;
     for (int tile = 0; tile < CONV_TILE_COUNT; ++tile) {
       if (!conv_tile_ok(c->precision, tile, o.Co, o.rows)) continue;
       hipError_t e = hipSuccess;
-      rc = launch_conv_op(c, o, NB, tile, s, &e);                         // warm-up (and attribute set-up)
+      rc = launch_conv_op(c, o, N, tile, s, &e);                         // warm-up (and attribute set-up)
       if (rc != NBC_OK || e != hipSuccess) continue;
       (void)hipEventRecord(e0, s);
-      for (int k = 0; k < reps; ++k) (void)launch_conv_op(c, o, NB, tile, s, &e);
+      for (int k = 0; k < reps; ++k) (void)launch_conv_op(c, o, N, tile, s, &e);
       (void)hipEventRecord(e1, s);
       if (hipEventSynchronize(e1) != hipSuccess) continue;
       float ms = 0.f;
@@ -1165,7 +762,7 @@ int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W
       if (objective == 1) {
         // throughput objective: several forwards run concurrently on other streams, so a launch that
         // fills only part of the chip costs only that part: weigh the time by the fraction of CUs used
-        const int tiles = ((NB * o.Ho * o.Wo + conv_tile_rows(tile) - 1) / conv_tile_rows(tile)) * (o.Co / conv_tile_cols(tile));
+        const int tiles = ((N * o.Ho * o.Wo + conv_tile_rows(tile) - 1) / conv_tile_rows(tile)) * (o.Co / conv_tile_cols(tile));
         if (tiles < 256) ms *= (float)tiles / 256.0f;
       }
       if (ms < best_ms) { best_ms = ms; best = tile; }

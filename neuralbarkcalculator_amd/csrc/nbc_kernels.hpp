@@ -1,5 +1,6 @@
 // Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
-// efficientnet.hip).
+// efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
+// bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.
 #pragma once
 #include <hip/hip_runtime.h>
 
