@@ -1,0 +1,531 @@
+"""The folder-run engine under the predict and evaluate drivers: everything that must be the same on every rank and in
+both tools, written once.
+
+A driver (``predict.predict_folder``, ``evaluate.evaluate_folder``) calls, in this order:
+
+* ``open_run``: the rank context (rank, world, ``dist`` or None, device, the batch and stream defaults);
+* ``bring_up``: rank 0's folders and the start barrier, the checkpoint on rank 0 alone, architecture (one broadcast under
+  ``--arch auto``) and precision, the weight broadcast, the ``pack_flags`` refusal, one model object and side stream per
+  batch in flight, the largest workspaces once (``warm``: the driver's own);
+* ``shard``: the host pool and this rank's contiguous, pixel-balanced share of the driver's item list;
+* ``run_loop``: the f16x2 calibration guard (one verdict broadcast), the batch loop, and the non-finite settlement (one MAX
+  all-reduce in f16x2).  The driver supplies ``prepare(k)`` (pool: the arrays of local image k, or None to skip it),
+  ``launch`` (the device work of one batch, on its stream) and ``consume`` (one finished slot, on the host);
+* ``gather`` (once per row kind) and ``finish`` (the final barrier and the statistics every driver returns).
+
+No collective sits in the per-image path: ranks with different numbers of windows tell each other of an abandoned f16x2
+run through ``AbandonMarker``.  ``run_precision``, ``add_shared_arguments`` and ``resolve_arguments`` are the drivers'
+shared command-line tail.
+"""
+from __future__ import annotations
+
+import os
+from types import SimpleNamespace
+from typing import List, Sequence
+
+import numpy as np
+
+
+class NonFiniteLogits(RuntimeError):
+    """A forward produced NaN / infinite logits: in f16x2 mode an activation beyond f16's range (or NaN/inf weights) -- or the
+    packer reported weights the f16 pieces cannot carry at f32 grade (``FCNResNet50.pack_flags``), before any forward ran."""
+
+    def __init__(self, text: str, batches_run: int = 0, images_this_rank: int = 0):
+        super().__init__(text)
+        self.batches_run, self.images_this_rank = batches_run, images_this_rank
+
+
+class AbandonMarker:
+    """How the ranks of one node tell each other that an f16x2 run is being abandoned: a file under ``results/`` that the
+    rank that sees the non-finite word creates and every rank looks for once per window of images (``os.path.exists``: no
+    collective, so ranks with different numbers of windows cannot wait for each other).  The folder driver's ranks share a
+    node (``--gpus N`` starts them on this one) and the folder's file system with it.  Rank 0 clears a stale marker before
+    the start barrier and the final one after the flag all-reduce."""
+
+    def __init__(self, root: str):
+        self.path = os.path.join(root, "results", ".f16x2_abandoned")
+
+    def set(self):
+        try:
+            os.makedirs(os.path.dirname(self.path), exist_ok=True)
+            open(self.path, "w").close()
+        except OSError:
+            pass                                         # the flag all-reduce at the end still tells every rank
+
+    def is_set(self) -> bool:
+        return os.path.exists(self.path)
+
+    def clear(self):
+        try:
+            os.remove(self.path)
+        except OSError:
+            pass
+
+
+def _host_workers() -> int:
+    return max(1, min(32, int(os.environ.get("NBC_HOST_WORKERS", "16"))))
+
+
+def shard_indices(n: int, rank: int, world: int) -> List[int]:
+    """Round-robin shard: images r, r+W, r+2W, ... (frames of equal size: bench.py)."""
+    return list(range(rank, n, world))
+
+
+def shard_by_pixels(pixels: Sequence[int], world: int) -> List[List[int]]:
+    """Contiguous, pixel-balanced shards of the sorted image list (folders of height-trimmed
+    or differently sized scans): image i goes to the rank whose share of the total pixel count contains the
+    midpoint of i's own span.  Every rank gets a contiguous range; ranges are empty only when there are
+    fewer images than ranks."""
+    total = float(sum(pixels))
+    shards: List[List[int]] = [[] for _ in range(world)]
+    acc = 0.0
+    for i, p in enumerate(pixels):
+        mid = acc + 0.5 * p
+        r = min(world - 1, int(mid * world / total)) if total > 0 else i % world
+        shards[r].append(i)
+        acc += p
+    return shards
+
+
+def windows(n: int, window: int) -> List[List[int]]:
+    """The local images 0..n-1 in windows of ``window``, in order: the pool works one window ahead of the GPU."""
+    return [list(range(a, min(a + window, n))) for a in range(0, n, window)]
+
+
+def batches_of(win: Sequence[int], shapes: dict, batch: int) -> List[tuple]:
+    """The batches of one window, in the order they run: ``(shape, [k, ...])`` with the window's images grouped by frame
+    shape (``shapes[k]``; None: image k is skipped), shapes in sorted order, each group cut into runs of up to ``batch``."""
+    groups = {}
+    for k in win:
+        if shapes[k] is not None:
+            groups.setdefault(shapes[k], []).append(k)
+    return [(shape, ks[a:a + batch]) for shape, ks in sorted(groups.items()) for a in range(0, len(ks), batch)]
+
+
+def collective_device(dist, device):
+    """Where a collective's tensors live: RCCL takes device tensors (``device``); a gloo group (one-GPU rehearsals of the
+    multi-rank path) and a single rank take host tensors (None)."""
+    return device if dist is not None and dist.get_backend() == "nccl" else None
+
+
+def _on_wire(t, wire_dev):
+    return t if wire_dev is None else t.to(wire_dev)
+
+
+def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, device=None, cap: int = None,
+                width: int = 5) -> np.ndarray:
+    """all_gather of fixed-size per-rank row buffers; returns the rows sorted by global index.
+    ``local_rows``: int64 [k, width] with k <= ``cap`` (default ceil(n_total / world), the round-robin
+    bound; pixel-balanced shards pass the largest shard's size)."""
+    import torch
+    if cap is None:
+        cap = (n_total + world - 1) // world if n_total else 0
+    buf = torch.full((max(cap, 1), width), -1, dtype=torch.int64)
+    if len(local_rows):
+        buf[: len(local_rows)] = torch.from_numpy(np.asarray(local_rows, dtype=np.int64))
+    if dist is None or world == 1:
+        allrows = buf
+    else:
+        if device is not None:
+            buf = buf.to(device)
+        parts = [torch.empty_like(buf) for _ in range(world)]
+        dist.all_gather(parts, buf)
+        allrows = torch.cat(parts).cpu()
+    allrows = allrows.numpy()
+    allrows = allrows[allrows[:, 0] >= 0]
+    return allrows[np.argsort(allrows[:, 0], kind="stable")]
+
+
+def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
+    """The network a folder driver runs (``--arch``).  ``"auto"``: rank 0, the one rank that read the checkpoint, picks
+    the architecture whose key set ``state_dict`` matches (``model.arch_of_state_dict``) and broadcasts its NBC_ARCH_*
+    index, so that every other rank sizes its blob for it.  A checkpoint no architecture matches raises on every rank
+    alike (rank 0 with the strict-load message of fcn_resnet50).  A named architecture is taken as it stands: strict
+    loading then refuses a checkpoint of the other one."""
+    from . import topology
+    if arch != "auto":
+        return topology.arch_name(topology.arch_index(arch))
+    rank = dist.get_rank() if dist is not None else 0
+    code, err = -1, None
+    if rank == 0:
+        from .model import arch_of_state_dict
+        try:
+            code = topology.arch_index(arch_of_state_dict(state_dict))
+        except RuntimeError as e:
+            err = e
+    if dist is not None:
+        import torch
+        t = _on_wire(torch.tensor([code], dtype=torch.int32), collective_device(dist, device))
+        dist.broadcast(t, src=0)
+        code = int(t.cpu()[0])
+    if err is not None:
+        raise err
+    if code < 0:
+        raise RuntimeError("rank 0 found no architecture matching the checkpoint's keys")
+    return topology.arch_name(code)
+
+
+def resolve_arch_precision(arch: str, precision: str, precision_auto: bool = False) -> str:
+    """The precision a folder driver runs ``arch`` in.  EfficientNet networks run "fp32" only: ``--precision auto`` means
+    "fp32" for them (``precision_auto``: the precision came from auto), an explicit "f16x2" or "bf16" raises ``ValueError``
+    naming fp32.  Every other network keeps ``precision``.  Called with the architecture ``resolve_arch`` returned (every
+    rank alike), or at argument time with a named one."""
+    from . import topology
+    if arch == "auto" or not topology.is_efficientnet(arch) or precision in ("fp32", "auto"):
+        return "fp32" if arch != "auto" and topology.is_efficientnet(arch) else precision
+    if precision_auto:
+        return "fp32"
+    raise ValueError("%s runs in --precision fp32 (or auto) only, not %s: swish and the SE gate are not positively "
+                     "homogeneous, so f16x2's powers of two cannot be folded into its BatchNorm pairs" % (arch, precision))
+
+
+BN_STATS = ("running", "image")
+ARCH_CHOICES = ("fcn_resnet50", "deeplabv3_resnet50") + tuple("fcn_efficientnet_b%d" % n for n in range(8)) + \
+    tuple("deeplabv3_efficientnet_b%d" % n for n in range(8))
+
+
+def resolve_bn_stats(bn_stats: str, precision: str) -> str:
+    """The precision a folder driver runs with ``--bn_stats`` (``FCNResNet50.set_bn_statistics``).  ``"running"`` leaves
+    ``precision`` as it is.  ``"image"`` (the shipped tool's per-image BatchNorm statistics) runs the f32 MFMA only:
+    ``"auto"`` means ``"fp32"`` (no f16x2 run, no calibration), ``"f16x2"`` and ``"bf16"`` raise ``ValueError``."""
+    if bn_stats not in BN_STATS:
+        raise ValueError("--bn_stats must be one of %s, got %r" % (", ".join(BN_STATS), bn_stats))
+    if bn_stats == "running":
+        return precision
+    if precision in ("auto", "fp32"):
+        return "fp32"
+    raise ValueError("--bn_stats image runs in --precision fp32 (or auto) only, not %s: raw pre-BatchNorm values do not fit "
+                     "the f16x2 pieces' pack-time scaling, and bf16 rounds them too coarsely for the mean subtraction" % precision)
+
+
+def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
+    """``ValueError`` for ``--bn_stats image`` on a network other than FCN-ResNet-50.  Called with the architecture
+    ``resolve_arch`` returned, which every rank holds alike, so every rank refuses alike."""
+    from . import topology
+    if bn_stats == "image" and topology.is_efficientnet(arch):
+        raise ValueError("--bn_stats image is refused for %s: per-image BatchNorm statistics are implemented for fcn_resnet50 "
+                         "only" % arch)
+    if bn_stats == "image" and arch != "fcn_resnet50":
+        raise ValueError("--bn_stats image is refused for %s: its ASPP pooling branch's BatchNorm sees a [1, 256, 1, 1] tensor, "
+                         "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
+
+
+def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
+             target_size: int = 1024) -> SimpleNamespace:
+    """The rank context of one folder run, and the state its later steps fill in.  An already initialised process group (gloo
+    in the one-GPU rehearsals) is used as it is; ``wire_dev`` is where its collectives' tensors live (``collective_device``)."""
+    import time
+    from collections import defaultdict
+    import torch
+    r = SimpleNamespace(root=root, tool=tool, precision=precision, target_size=target_size, t_start=time.perf_counter(),
+                        world=int(os.environ.get("WORLD_SIZE", "1")), rank=int(os.environ.get("RANK", "0")), dist=None)
+    local_rank = int(os.environ.get("LOCAL_RANK", "0")) if device_index is None else device_index
+    if r.world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.cuda.set_device(local_rank)
+        if not dist.is_initialized():
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+        r.dist = dist
+    r.dev = torch.device("cuda", local_rank)
+    torch.cuda.set_device(r.dev)
+    r.wire_dev = collective_device(r.dist, r.dev)
+    r.batch = (8 if precision == "bf16" else 2) if batch is None else batch
+    r.n_streams = 4 if streams is None else max(1, int(streams))
+    r.depth = r.n_streams + 1                        # slots of the pinned rings: one more than batches in flight
+    r.marker = AbandonMarker(root)
+    r.prof = defaultdict(float)                      # seconds per stage, summed over threads
+    r.shape_count = defaultdict(int)                 # images seen per frame shape, the running window included
+    r.n_batches = 0
+    return r
+
+
+def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool, make_dirs, warm=None) -> None:
+    """Rank 0's ``make_dirs(root)`` and the start barrier, then ``r.models`` (``r.n_streams`` objects on one copy of the
+    weights), ``r.gpu_streams``, and the resolved ``r.arch`` / ``r.precision``.  ``warm(model)``: the driver's own workspaces, grown
+    to their largest size once like the forward's."""
+    import time
+    import torch
+    from .model import MODELS
+    if r.rank == 0:
+        make_dirs(r.root)
+        r.marker.clear()
+    if r.dist is not None:
+        r.dist.barrier()
+    state_dict = None
+    if r.rank == 0:                                  # only one rank touches the checkpoint
+        state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
+    r.arch = resolve_arch(arch, state_dict, r.dist, r.dev)
+    check_bn_stats_arch(bn_stats, r.arch)
+    r.precision = resolve_arch_precision(r.arch, r.precision, precision_auto)   # EfficientNet: fp32
+    model = MODELS[r.arch](r.precision).set_bn_statistics(bn_stats).to(r.dev)
+    if r.rank == 0:
+        model.load_state_dict(state_dict)
+    del state_dict
+    if r.dist is not None:
+        model.broadcast_weights(src=0)
+    if r.precision == "f16x2" and model.pack_flags:
+        # what the packer had to give up rides in the blob's trailer: every rank reads the same bits and leaves here alike
+        raise NonFiniteLogits("the packed weights carry NBC_PACK flags %d (a weight row beyond the reach of the f16x2 row "
+                              "normalisation, or a BatchNorm scale outside f32's normal range under its powers of two): f16x2 "
+                              "would not be f32 grade on this checkpoint; rerun with --precision fp32" % model.pack_flags)
+    r.models = [model] + [model.clone_shared() for _ in range(r.n_streams - 1)]
+    # side streams only: the default stream stays with whatever else the driver runs on the device
+    r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
+    for m in r.models:                               # the largest workspace once: a context's buffers only grow, and a folder of
+        m.reserve(r.batch, r.target_size, r.target_size)   # rising heights would otherwise free and reallocate them shape after shape
+        if warm is not None:
+            warm(m)
+    torch.cuda.synchronize(r.dev)                    # weights uploaded / received before any side stream reads them
+    r.t_ready = time.perf_counter()
+
+
+def shard(r, items: Sequence, size_of) -> list:
+    """Starts the host pool (``r.pool``) and cuts ``items`` into contiguous, pixel-balanced shards by ``size_of(item)`` ->
+    ``(h, w)`` (a header read, on the pool); ``r.mine``: this rank's global indices.  Returns every item's size."""
+    from concurrent.futures import ThreadPoolExecutor
+    r.workers = _host_workers()
+    r.pool = ThreadPoolExecutor(max_workers=r.workers)
+    sizes = list(r.pool.map(size_of, items))
+    shards = shard_by_pixels([h * w for h, w in sizes], r.world)
+    r.n_total, r.mine, r.cap = len(items), shards[r.rank], max(len(s) for s in shards)
+    return sizes
+
+
+def _calibration_guard(r, first_frame) -> None:
+    """f16x2: nbc_pack_weights places every tensor by its BatchNorm's promise (|beta| + 3 |gamma|); whether the DATA keeps that
+    promise shows on the first image: rank 0 runs it once with every activation kept and looks at each stored tensor's
+    largest value.  One below 2^-8 sits mostly under the f16 pieces' 2^-12 floor -- finite logits, nothing for the
+    non-finite flag to see --, one beyond 2^14 is a factor four from f16's range: either way the folder belongs on the f32
+    MFMA, and every rank leaves here alike (one scalar broadcast), before any batch has run."""
+    import torch
+    from .model import FCNResNet50
+    verdict = torch.zeros(1, dtype=torch.int32)
+    offenders = {}
+    first = first_frame() if r.rank == 0 else None
+    if first is not None:
+        peaks = r.models[0].activation_peaks(torch.from_numpy(np.ascontiguousarray(first[None])).to(r.dev))
+        ok, offenders = FCNResNet50.f16x2_range_ok(peaks)
+        verdict[0] = 0 if ok else 1
+    if r.dist is not None:
+        verdict = _on_wire(verdict, r.wire_dev)
+        r.dist.broadcast(verdict, src=0)
+    if int(verdict.cpu()[0]) != 0:
+        r.pool.shutdown(wait=True, cancel_futures=True)
+        worst = ", ".join("%s %.3g" % kv for kv in sorted(offenders.items(), key=lambda kv: kv[1])[:4])
+        raise NonFiniteLogits("calibration on the first image: an activation tensor lies outside the range the f16 pieces hold "
+                              "at f32 grade (stored peak below 2^-8 or beyond 2^14%s): f16x2 would lose bits silently on this "
+                              "checkpoint; rerun with --precision fp32" % ((": " + worst) if worst else ""), 0, len(r.mine))
+
+
+def run_loop(r, window: int, prepare, launch, consume, first_frame, calibrate: bool = True,
+             bytes_per_pixel: Sequence[int] = (3,), on_abandon=None, abandon_note: str = "") -> None:
+    """The calibration guard, the batch loop over ``r.mine`` and the non-finite settlement.
+
+    Local image k (global ``r.mine[k]``) is prepared on the pool one window ahead: ``prepare(k)`` returns a tuple of uint8
+    arrays, the ``[h, w, 3]`` frame first, or None for an image that is skipped.  A window's frames are grouped by shape
+    (``batches_of``); batch number b takes stream and model ``b % n_streams`` and slot ``b % depth`` of the pinned staging
+    buffers (``bytes_per_pixel``: one buffer per array of the tuple), which an event guards against the copy that last read
+    them.  On its stream, ``launch(slot, sid, part, *device_arrays)`` queues the driver's work and the copies into the
+    driver's own result ring; the context's sticky non-finite word rides back behind them (f16x2: nbc_nonfinite_peek_async,
+    no synchronisation) and an event closes the slot.  Once more than ``n_streams`` batches are pending the oldest is waited
+    for and ``consume(slot, part, n, h, w)`` takes its results; the futures it returns are waited for before the pool
+    closes.  A non-zero word abandons the run at that batch: nothing of it is consumed, the other ranks of the node learn of it
+    through the marker at their next window, and after the MAX all-reduce every rank raises ``NonFiniteLogits`` alike
+    (``on_abandon()`` first: the driver's clean-up; ``abandon_note``: what the message says of it).
+    ``first_frame()``: rank 0's first frame for the calibration guard, or None."""
+    import sys
+    import time
+    from collections import deque
+    import torch
+    clock, prof, mine, pool = time.perf_counter, r.prof, r.mine, r.pool
+    dev, models, n_streams, depth, batch = r.dev, r.models, r.n_streams, r.depth, r.batch
+    check_flag = r.precision == "f16x2"
+    if check_flag and calibrate:
+        _calibration_guard(r, first_frame)
+    # pinned staging, allocated once for the largest batch: pinning memory costs milliseconds, and a folder of rising
+    # heights would otherwise re-pin at every new shape
+    full = batch * r.target_size * r.target_size
+    stage = [[torch.empty(full * c, dtype=torch.uint8).pin_memory() for c in bytes_per_pixel] for _ in range(depth)]
+    stage_ev = [torch.cuda.Event() for _ in range(depth)]
+    ring_ev = [torch.cuda.Event() for _ in range(depth)]
+    flag_host = torch.zeros(depth, dtype=torch.int32).pin_memory()
+    bad = False
+    pending = deque()                                # (slot, [k], n, h, w), oldest first
+    done = []
+
+    def settle(p):
+        nonlocal bad
+        ring_ev[p[0]].synchronize()
+        if check_flag and int(flag_host[p[0]]) != 0:
+            bad = True                               # this batch's results (and every later one's) are not valid: none is consumed
+            if r.world > 1:
+                r.marker.set()                       # the other ranks of the node stop at their next window
+            return
+        done.extend(consume(*p) or ())
+
+    # the GPU loop runs in this thread next to up to 32 busy pool threads: a short switch interval keeps it
+    # from waiting 5 ms for the interpreter lock at every step (restored below)
+    switch = sys.getswitchinterval()
+    sys.setswitchinterval(2e-4)
+    try:
+        wins = windows(len(mine), window)
+        futs = {k: pool.submit(prepare, k) for k in (wins[0] if wins else [])}
+        r.t_loop = clock()
+        for wi, win in enumerate(wins):
+            if check_flag and r.world > 1 and not bad and r.marker.is_set():
+                bad = True                               # another rank of the node saw the word
+            if bad:                                      # f16x2 cannot carry these weights: the run is abandoned here
+                break
+            if wi + 1 < len(wins):                       # the pool starts on the next window before the GPU gets this one
+                for k in wins[wi + 1]:
+                    futs[k] = pool.submit(prepare, k)
+            t0 = clock()
+            got = {k: futs.pop(k).result() for k in win}
+            prof["main.wait_for_frames"] += clock() - t0
+            parts = batches_of(win, {k: None if g is None else g[0].shape for k, g in got.items()}, batch)
+            for shape, part in parts:
+                r.shape_count[shape] += len(part)
+            for shape, part in parts:
+                if bad:
+                    break
+                n, (h, w) = len(part), shape[:2]
+                t0 = clock()
+                slot, sid = r.n_batches % depth, r.n_batches % n_streams   # free: at most n_streams batches are pending, on other slots
+                bufs = stage[slot]                            # frames are packed while the GPU runs the batches before
+                for i, c in enumerate(bytes_per_pixel):       # a stale file under processed/ with no sample is predicted as it
+                    if bufs[i].numel() < n * h * w * c:       # is, at any size: the one frame larger than target_size
+                        bufs[i] = torch.empty(n * h * w * c, dtype=torch.uint8).pin_memory()
+                stage_ev[slot].synchronize()                  # the copies that last read these buffers have finished
+                host = [b[: n * h * w * c].view((n,) + a.shape) for b, c, a in zip(bufs, bytes_per_pixel, got[part[0]])]
+                views = [t.numpy() for t in host]
+                for j, k in enumerate(part):
+                    for v, a in zip(views, got[k]):
+                        v[j] = a
+                t1 = clock()
+                with torch.cuda.stream(r.gpu_streams[sid]):
+                    on_dev = [t.to(dev, non_blocking=True) for t in host]   # uint8, the frame NHWC; normalised on the device
+                    stage_ev[slot].record()
+                    launch(slot, sid, part, *on_dev)
+                    if check_flag:
+                        models[sid].nonfinite_peek_async(flag_host[slot:slot + 1])
+                    ring_ev[slot].record()
+                t2 = clock()
+                pending.append((slot, part, n, h, w))
+                while len(pending) > n_streams:               # the oldest batch's results, while the newer ones run
+                    settle(pending.popleft())
+                prof["main.pack"] += t1 - t0; prof["main.h2d_and_launch"] += t2 - t1; prof["main.consume"] += clock() - t2
+                r.n_batches += 1
+            got.clear()
+        while pending:
+            settle(pending.popleft())
+        for f in done:
+            f.result()
+    finally:                                         # also on an exception from a worker: no stray threads, switch interval restored
+        pool.shutdown(wait=True, cancel_futures=True)
+        sys.setswitchinterval(switch)
+    torch.cuda.synchronize()
+    r.t_done = clock()
+    if check_flag:
+        # f16x2 keeps every value as two f16 pieces: an activation beyond +-65504 cannot be represented and turns into NaN
+        # (never into a silently wrong number).  Unknown weights that do this belong in the f32 MFMA mode.  Every rank
+        # learns of it (one more tiny collective) so that all of them leave before the row gather, none waits in it.
+        # The word rides back with every batch (settle), so a rank that sees it stops at that batch instead of finishing its
+        # shard; the contexts are all read (and reset) here once more, whatever the first one says.
+        bad = any([m.nonfinite_seen() for m in models]) or bad
+        if r.dist is not None:
+            flag = _on_wire(torch.tensor([int(bad)], dtype=torch.int32), r.wire_dev)
+            r.dist.all_reduce(flag, op=r.dist.ReduceOp.MAX)
+            bad = bool(int(flag.item()))
+            if r.rank == 0:
+                r.marker.clear()                     # every rank is past its loop (the all-reduce above)
+        if bad:
+            if on_abandon is not None:
+                on_abandon()
+            raise NonFiniteLogits("a forward produced non-finite logits in f16x2 mode (an activation beyond f16's range, or NaN/inf "
+                                  "in the weights): the %s run was abandoned after %d of this rank's %d images%s; rerun with "
+                                  "--precision fp32" % (r.tool, min(r.n_batches * batch, len(mine)), len(mine), abandon_note),
+                                  r.n_batches, len(mine))
+
+
+def gather(r, rows: np.ndarray, width: int) -> np.ndarray:
+    """One ``all_gather`` of this rank's rows, the largest shard as the cap."""
+    return gather_rows(rows, r.n_total, r.world, r.dist, r.wire_dev, cap=r.cap, width=width)
+
+
+def finish(r) -> dict:
+    """The final barrier, and the statistics of this rank that every driver returns."""
+    import time
+    if r.dist is not None:
+        r.dist.barrier()
+    loop_s = r.t_done - r.t_loop
+    return {"rank": r.rank, "world": r.world, "images_total": r.n_total, "images_this_rank": len(r.mine), "batches": r.n_batches,
+            "batch": r.batch, "streams": r.n_streams, "setup_s": r.t_ready - r.t_start, "loop_s": loop_s,
+            "total_s": time.perf_counter() - r.t_start, "images_per_s_loop": len(r.mine) / max(loop_s, 1e-9)}
+
+
+def launch_ranks(n: int, argv: Sequence[str], module: str = "neuralbarkcalculator_amd.predict") -> int:
+    """``--gpus N`` without a torchrun environment: start N ranks (one per GPU) of ``module`` as a child process."""
+    import socket
+    import subprocess
+    import sys
+    import torch
+    if torch.cuda.device_count() < n:                # counts devices without initialising HIP
+        print("predict: --gpus %d but this node shows %d GPU(s)" % (n, torch.cuda.device_count()), file=sys.stderr)
+        return 2
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+           "--master-port", str(port), "-m", module] + list(argv)
+    return subprocess.run(cmd, env=env).returncode
+
+
+def add_shared_arguments(ap) -> None:
+    """The options both drivers take."""
+    ap.add_argument("--model_path", default="./best_model.pt")       # predict.py:57
+    ap.add_argument("--precision", choices=["auto", "fp32", "f16x2", "bf16"], default="auto",
+                    help="auto (default): the f32-grade f16x2 mode, 2.4x faster than the f32 MFMA at the same tolerances, and a "
+                         "second run in fp32 if the weights drive an activation beyond f16's range (the library says so); fp32: "
+                         "f32 MFMA; bf16: throughput mode, not f32 grade")
+    ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
+    ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2, 8 in bf16)")
+    ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
+    ap.add_argument("--arch", choices=["auto"] + list(ARCH_CHOICES), default="auto",
+                    help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
+    ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
+                    help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
+                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
+
+
+def resolve_arguments(ap, args) -> None:
+    """``args.precision`` as ``--bn_stats`` and a named ``--arch`` leave it; what they refuse ends in ``ap.error``."""
+    try:
+        args.precision = resolve_bn_stats(args.bn_stats, args.precision)
+        if args.arch != "auto":
+            check_bn_stats_arch(args.bn_stats, args.arch)
+        args.precision = resolve_arch_precision(args.arch, args.precision)
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def run_precision(tool: str, run, precision: str) -> dict:
+    """``run(precision)``; for ``"auto"``, ``run("f16x2", precision_auto=True)`` and, when that mode cannot carry the weights
+    (``NonFiniteLogits``, raised on every rank alike), the folder again as ``run("fp32")``."""
+    if precision != "auto":
+        return run(precision)
+    try:
+        return run("f16x2", precision_auto=True)
+    except NonFiniteLogits as e:
+        if int(os.environ.get("RANK", "0")) == 0:
+            print("%s: %s -- running the folder again on the f32 MFMA" % (tool, e), flush=True)
+    # outside the except block: the exception's traceback holds the first run's frame (the model contexts with their
+    # workspaces, the pinned rings, the streams) for as long as the block lasts
+    import gc
+    import torch
+    gc.collect()
+    torch.cuda.empty_cache()
+    return run("fp32")

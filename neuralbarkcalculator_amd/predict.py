@@ -19,7 +19,8 @@ accelerated model call:
 Multi-GPU (one process per GPU, ``torch.distributed`` over RCCL; ``--gpus N`` starts the ranks): the
 sorted list is cut into contiguous, pixel-balanced shards; rank 0 alone reads the checkpoint and
 broadcasts the packed weights; every rank fills int64 rows ``(global_idx, H, W, count_1, count_2)``
-which one ``all_gather`` brings to rank 0 for the CSV.  No collective sits in the per-image path.
+which one ``all_gather`` brings to rank 0 for the CSV.  No collective sits in the per-image path.  The ranks, the model
+bring-up, the batch loop and the f16x2 guards are ``folder_run``'s, shared with the evaluate driver.
 """
 from __future__ import annotations
 
@@ -30,6 +31,11 @@ import threading
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
+
+from . import folder_run
+from .folder_run import (ARCH_CHOICES, BN_STATS, AbandonMarker, NonFiniteLogits, _host_workers, check_bn_stats_arch,  # noqa: F401
+                         gather_rows, launch_ranks, resolve_arch, resolve_arch_precision, resolve_bn_stats, shard_by_pixels,
+                         shard_indices)      # the folder-run engine's helpers, under the names they have always had here
 
 WOOD_TYPES = ["epinette_gelee", "epinette_non_gelee", "sapin"]            # dataset.py:50
 IMG_EXTENSIONS = [".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", "webp"]  # dataset.py:77-79
@@ -254,10 +260,6 @@ def preprocess_bmp_scan_on_device(path: str, target_size: int, model, lock) -> O
     return np.ascontiguousarray(out[first:last])
 
 
-def _host_workers() -> int:
-    return max(1, min(32, int(os.environ.get("NBC_HOST_WORKERS", "16"))))
-
-
 def _png_level(kind: str) -> int:
     """zlib level of the PNGs the driver writes.  The files carry pixel values (models.py:203,349-356 pin
     values, not bytes): processed frames default to stored (level 0: noise-like photographs barely
@@ -289,59 +291,6 @@ def preprocess_images(root: str, target_size: int = 1024, model=None) -> None:
         list(pool.map(one, list_images(root)))
 
 
-class NonFiniteLogits(RuntimeError):
-    """A forward produced NaN / infinite logits: in f16x2 mode an activation beyond f16's range (or NaN/inf weights) -- or the
-    packer reported weights the f16 pieces cannot carry at f32 grade (``FCNResNet50.pack_flags``), before any forward ran."""
-
-
-class AbandonMarker:
-    """How the ranks of one node tell each other that an f16x2 run is being abandoned: a file under ``results/`` that the
-    rank that sees the non-finite word creates and every rank looks for once per window of images (``os.path.exists``: no
-    collective, so ranks with different numbers of windows cannot wait for each other).  The folder driver's ranks share a
-    node (``--gpus N`` starts them on this one) and the folder's file system with it.  Rank 0 clears a stale marker before
-    the start barrier and the final one after the flag all-reduce."""
-
-    def __init__(self, root: str):
-        self.path = os.path.join(root, "results", ".f16x2_abandoned")
-
-    def set(self):
-        try:
-            os.makedirs(os.path.dirname(self.path), exist_ok=True)
-            open(self.path, "w").close()
-        except OSError:
-            pass                                         # the flag all-reduce at the end still tells every rank
-
-    def is_set(self) -> bool:
-        return os.path.exists(self.path)
-
-    def clear(self):
-        try:
-            os.remove(self.path)
-        except OSError:
-            pass
-
-
-def shard_indices(n: int, rank: int, world: int) -> List[int]:
-    """Round-robin shard: images r, r+W, r+2W, ... (frames of equal size: bench.py)."""
-    return list(range(rank, n, world))
-
-
-def shard_by_pixels(pixels: Sequence[int], world: int) -> List[List[int]]:
-    """Contiguous, pixel-balanced shards of the sorted image list (folders of height-trimmed
-    or differently sized scans): image i goes to the rank whose share of the total pixel count contains the
-    midpoint of i's own span.  Every rank gets a contiguous range; ranges are empty only when there are
-    fewer images than ranks."""
-    total = float(sum(pixels))
-    shards: List[List[int]] = [[] for _ in range(world)]
-    acc = 0.0
-    for i, p in enumerate(pixels):
-        mid = acc + 0.5 * p
-        r = min(world - 1, int(mid * world / total)) if total > 0 else i % world
-        shards[r].append(i)
-        acc += p
-    return shards
-
-
 def stats_row(name: str, wood: str, h: int, w: int, count_1: int, count_2: int) -> List[str]:
     """One CSV row, float32 arithmetic and '{:.5f}' formatting of models.py:321-332."""
     row = [name, wood]
@@ -364,106 +313,6 @@ def label_png(labels: np.ndarray) -> np.ndarray:
     out[labels == 1] = 127
     out[labels == 2] = 255
     return out
-
-
-def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, device=None, cap: int = None,
-                width: int = ROW_WIDTH) -> np.ndarray:
-    """all_gather of fixed-size per-rank row buffers; returns the rows sorted by global index.
-    ``local_rows``: int64 [k, width] with k <= ``cap`` (default ceil(n_total / world), the round-robin
-    bound; pixel-balanced shards pass the largest shard's size)."""
-    import torch
-    if cap is None:
-        cap = (n_total + world - 1) // world if n_total else 0
-    buf = torch.full((max(cap, 1), width), -1, dtype=torch.int64)
-    if len(local_rows):
-        buf[: len(local_rows)] = torch.from_numpy(np.asarray(local_rows, dtype=np.int64))
-    if dist is None or world == 1:
-        allrows = buf
-    else:
-        if device is not None:
-            buf = buf.to(device)
-        parts = [torch.empty_like(buf) for _ in range(world)]
-        dist.all_gather(parts, buf)
-        allrows = torch.cat(parts).cpu()
-    allrows = allrows.numpy()
-    allrows = allrows[allrows[:, 0] >= 0]
-    return allrows[np.argsort(allrows[:, 0], kind="stable")]
-
-
-def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
-    """The network a folder driver runs (``--arch``).  ``"auto"``: rank 0, the one rank that read the checkpoint, picks
-    the architecture whose key set ``state_dict`` matches (``model.arch_of_state_dict``) and broadcasts its NBC_ARCH_*
-    index, so that every other rank sizes its blob for it.  A checkpoint no architecture matches raises on every rank
-    alike (rank 0 with the strict-load message of fcn_resnet50).  A named architecture is taken as it stands: strict
-    loading then refuses a checkpoint of the other one."""
-    from . import topology
-    if arch != "auto":
-        return topology.arch_name(topology.arch_index(arch))
-    rank = dist.get_rank() if dist is not None else 0
-    code, err = -1, None
-    if rank == 0:
-        from .model import arch_of_state_dict
-        try:
-            code = topology.arch_index(arch_of_state_dict(state_dict))
-        except RuntimeError as e:
-            err = e
-    if dist is not None:
-        import torch
-        t = torch.tensor([code], dtype=torch.int32)
-        if dist.get_backend() == "nccl":
-            t = t.to(device)
-        dist.broadcast(t, src=0)
-        code = int(t.cpu()[0])
-    if err is not None:
-        raise err
-    if code < 0:
-        raise RuntimeError("rank 0 found no architecture matching the checkpoint's keys")
-    return topology.arch_name(code)
-
-
-def resolve_arch_precision(arch: str, precision: str, precision_auto: bool = False) -> str:
-    """The precision a folder driver runs ``arch`` in.  EfficientNet networks run "fp32" only: ``--precision auto`` means
-    "fp32" for them (``precision_auto``: the precision came from auto), an explicit "f16x2" or "bf16" raises ``ValueError``
-    naming fp32.  Every other network keeps ``precision``.  Called with the architecture ``resolve_arch`` returned (every
-    rank alike), or at argument time with a named one."""
-    from . import topology
-    if arch == "auto" or not topology.is_efficientnet(arch) or precision in ("fp32", "auto"):
-        return "fp32" if arch != "auto" and topology.is_efficientnet(arch) else precision
-    if precision_auto:
-        return "fp32"
-    raise ValueError("%s runs in --precision fp32 (or auto) only, not %s: swish and the SE gate are not positively "
-                     "homogeneous, so f16x2's powers of two cannot be folded into its BatchNorm pairs" % (arch, precision))
-
-
-BN_STATS = ("running", "image")
-ARCH_CHOICES = ("fcn_resnet50", "deeplabv3_resnet50") + tuple("fcn_efficientnet_b%d" % n for n in range(8)) + \
-    tuple("deeplabv3_efficientnet_b%d" % n for n in range(8))
-
-
-def resolve_bn_stats(bn_stats: str, precision: str) -> str:
-    """The precision a folder driver runs with ``--bn_stats`` (``FCNResNet50.set_bn_statistics``).  ``"running"`` leaves
-    ``precision`` as it is.  ``"image"`` (the shipped tool's per-image BatchNorm statistics) runs the f32 MFMA only:
-    ``"auto"`` means ``"fp32"`` (no f16x2 run, no calibration), ``"f16x2"`` and ``"bf16"`` raise ``ValueError``."""
-    if bn_stats not in BN_STATS:
-        raise ValueError("--bn_stats must be one of %s, got %r" % (", ".join(BN_STATS), bn_stats))
-    if bn_stats == "running":
-        return precision
-    if precision in ("auto", "fp32"):
-        return "fp32"
-    raise ValueError("--bn_stats image runs in --precision fp32 (or auto) only, not %s: raw pre-BatchNorm values do not fit "
-                     "the f16x2 pieces' pack-time scaling, and bf16 rounds them too coarsely for the mean subtraction" % precision)
-
-
-def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
-    """``ValueError`` for ``--bn_stats image`` on a network other than FCN-ResNet-50.  Called with the architecture
-    ``resolve_arch`` returned, which every rank holds alike, so every rank refuses alike."""
-    from . import topology
-    if bn_stats == "image" and topology.is_efficientnet(arch):
-        raise ValueError("--bn_stats image is refused for %s: per-image BatchNorm statistics are implemented for fcn_resnet50 "
-                         "only" % arch)
-    if bn_stats == "image" and arch != "fcn_resnet50":
-        raise ValueError("--bn_stats image is refused for %s: its ASPP pooling branch's BatchNorm sees a [1, 256, 1, 1] tensor, "
-                         "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
 
 
 def plan_items(root: str) -> List[dict]:
@@ -514,91 +363,36 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     Returns timing / count statistics of this rank."""
     import time
     import torch
-    from collections import defaultdict, deque
-    from concurrent.futures import ThreadPoolExecutor
-    import threading
     from PIL import Image
-    from .model import MODELS, FCNResNet50
+    from .model import FCNResNet50
     from .pngio import write_png
-    t_start = time.perf_counter()
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0")) if device_index is None else device_index
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        torch.cuda.set_device(local_rank)
-        if not dist.is_initialized():
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    dev = torch.device("cuda", local_rank)
-    torch.cuda.set_device(dev)
-    if batch is None:
-        batch = 8 if precision == "bf16" else 2
-    n_streams = 4 if streams is None else max(1, int(streams))
-
+    r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size)
+    dev, batch, prof, clock = r.dev, r.batch, r.prof, time.perf_counter
     pre_model = FCNResNet50(precision).to(dev)      # its own context: the pool's device resizes never touch the predictor's
-    marker = AbandonMarker(root)
-    if rank == 0:
-        generate_folders(root)
-        marker.clear()
-    if dist is not None:
-        dist.barrier()
-    state_dict = None
-    if rank == 0:                                    # only one rank touches the checkpoint
-        state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
-    arch = resolve_arch(arch, state_dict, dist, dev)
-    check_bn_stats_arch(bn_stats, arch)
-    precision = resolve_arch_precision(arch, precision, precision_auto)
-    model = MODELS[arch](precision).set_bn_statistics(bn_stats)
-    model.to(dev)
-    if rank == 0:
-        model.load_state_dict(state_dict)
-    del state_dict
-    if dist is not None:
-        model.broadcast_weights(src=0)
-    if precision == "f16x2" and model.pack_flags:
-        # what the packer had to give up rides in the blob's trailer: every rank reads the same bits and leaves here alike
-        err = NonFiniteLogits("the packed weights carry NBC_PACK flags %d (a weight row beyond the reach of the f16x2 row "
-                              "normalisation, or a BatchNorm scale outside f32's normal range under its powers of two): f16x2 "
-                              "would not be f32 grade on this checkpoint; rerun with --precision fp32" % model.pack_flags)
-        err.batches_run, err.images_this_rank = 0, 0
-        raise err
-    models = [model] + [model.clone_shared() for _ in range(n_streams - 1)]
-    # side streams only: the default stream stays with the pool's device resizes (pre_model)
-    gpu_streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
-    for m in models:                                 # the largest workspace once: a context's buffers only grow, and a folder of
-        m.reserve(batch, target_size, target_size)   # rising heights would otherwise free and reallocate them shape after shape
-        if small_zones:                              # likewise the remove_small_zones workspace (9 bytes per pixel)
+
+    def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel)
+        if small_zones:
             m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
-    torch.cuda.synchronize(dev)                      # weights uploaded / received before any side stream reads them
-    t_ready = time.perf_counter()
+    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, generate_folders, warm)
 
     items = plan_items(root)
-    n_total = len(items)
-    workers = _host_workers()
-    pool = ThreadPoolExecutor(max_workers=workers)
 
-    def header_pixels(d):
+    def header_size(d):
         with open(d["src"] or d["processed"], "rb") as f:
             w, h = Image.open(f).size                # header only: nothing is decoded
-        return w * h
-    pixels = list(pool.map(header_pixels, items))
-    shards = shard_by_pixels(pixels, world)
-    mine = shards[rank]
+        return h, w
+    folder_run.shard(r, items, header_size)
+    mine, pool = r.mine, r.pool
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
-    resize_lock = threading.Lock()
+    resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
     lvl_proc, lvl_lab = _png_level("processed"), _png_level("labels")
 
-    prof = defaultdict(float)                        # seconds per stage, summed over threads (NBC_FOLDER_PROFILE=1 prints them)
-    clock = time.perf_counter
-
-    def prepare(gi):
+    def prepare(k):
         """Pool: decode + preprocess + write processed/ -> the uint8 frame the model sees."""
-        d = items[gi]
+        d = items[mine[k]]
         t0 = clock()
         if d["src"] is None:
-            return _decode_rgb(d["processed"])
+            return (_decode_rgb(d["processed"]),)
         out = preprocess_bmp_scan_on_device(d["src"], target_size, pre_model, resize_lock)     # raw scans: no host decode
         t1 = t2 = clock()
         if out is None:
@@ -613,218 +407,64 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         write_png(d["processed"], out, lvl_proc)
         t3 = clock()
         prof["pool.decode"] += t1 - t0; prof["pool.preprocess"] += t2 - t1; prof["pool.write_processed"] += t3 - t2
-        return out
+        return (out,)
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, gi, lab, c1, c2):
+    def finish(k, lab, c1, c2):
         """Pool: label PNG (models.py:349-356) + the image's row."""
-        d = items[gi]
+        d = items[mine[k]]
         t0 = clock()
         path = os.path.join(root, "results", "outputs", d["wood"], d["name"])
         label_paths.append(path)
         write_png(path, label_png(lab), lvl_lab)
-        rows[k] = (gi, lab.shape[0], lab.shape[1], c1, c2)
+        rows[k] = (mine[k], lab.shape[0], lab.shape[1], c1, c2)
         prof["pool.write_labels"] += clock() - t0
 
-    # pinned rings, one slot more than batches in flight: frames going up, labels + counts coming back
-    # (allocated once for the largest batch: pinning memory costs milliseconds, and a folder of rising heights would
-    # otherwise re-pin at every new shape)
-    depth = n_streams + 1
+    # the result ring, one slot per staging slot: labels + counts coming back (pinned once for the largest batch)
     full = batch * target_size * target_size
     ring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, 3), dtype=torch.int64).pin_memory())
-            for _ in range(depth)]
-    ring_ev = [torch.cuda.Event() for _ in range(depth)]
-    # f16x2: the context's sticky non-finite word rides back with every batch (nbc_nonfinite_peek_async: no synchronisation)
-    flag_host = torch.zeros(depth, dtype=torch.int32).pin_memory()
-    check_flag = precision == "f16x2"
-    bad_seen = [False]
-    stage = [{"buf": torch.empty(full * 3, dtype=torch.uint8).pin_memory(), "ev": torch.cuda.Event()} for _ in range(depth)]
-    pending = deque()                                # (slot, [(k, gi)], n, h, w), oldest first
-    done = []
+            for _ in range(r.depth)]
     tuned = set()
-    shape_count = defaultdict(int)
-    n_batches = 0
 
-    def consume(p):
-        slot, members, n, h, w = p
-        ring_ev[slot].synchronize()
-        if check_flag and int(flag_host[slot]) != 0:
-            bad_seen[0] = True                       # this batch's labels (and every later one's) are not valid: nothing is written
-            if world > 1:
-                marker.set()                         # the other ranks of the node stop at their next window
-            return
+    def launch(slot, sid, part, x):
+        (n, h, w), mdl = x.shape[:3], r.models[sid]
+        need = n * h * w
+        if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:   # an oversized stale processed frame (run_loop)
+            ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
+        if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
+            mdl.autotune(x)                          # once per distinct full-batch shape and model object
+            tuned.add((sid, (n, h, w)))
+        labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
+                                            small_zones=small_zones)   # models.py:269-276 on the device
+        ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
+        ring[slot][1][:n].copy_(counts, non_blocking=True)
+
+    def consume(slot, part, n, h, w):
         lab_host, cnt_host = ring[slot]
         labs = lab_host[: n * h * w].numpy().reshape(n, h, w).copy()
         cnts = cnt_host[:n].numpy().copy()
-        for j, (k, gi) in enumerate(members):
-            done.append(pool.submit(finish, k, gi, labs[j], int(cnts[j, 1]), int(cnts[j, 2])))
+        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2])) for j, k in enumerate(part)]
 
-    # f16x2, calibration guard: nbc_pack_weights places every tensor by its BatchNorm's promise (|beta| + 3 |gamma|); whether the
-    # DATA keeps that promise shows on the first image: rank 0 runs it once with every activation kept and looks at each
-    # stored tensor's largest value.  One below 2^-8 sits mostly under the f16 pieces' 2^-12 floor -- finite logits, nothing
-    # for the non-finite flag to see --, one beyond 2^14 is a factor four from f16's range: either way the folder belongs on
-    # the f32 MFMA, and every rank leaves here alike (one scalar broadcast), before any batch has run.
-    if check_flag and calibrate:
-        verdict = torch.zeros(1, dtype=torch.int32)
-        offenders = {}
-        if rank == 0 and len(mine) > 0:
-            first = prepare(mine[0])                     # (decoded once more inside the loop: one image's host work)
-            peaks = models[0].activation_peaks(torch.from_numpy(np.ascontiguousarray(first[None])).to(dev))
-            ok, offenders = FCNResNet50.f16x2_range_ok(peaks)
-            verdict[0] = 0 if ok else 1
-        if dist is not None:
-            vd = verdict.to(dev) if dist.get_backend() == "nccl" else verdict
-            dist.broadcast(vd, src=0)
-            verdict = vd.cpu()
-        if int(verdict[0]) != 0:
-            pool.shutdown(wait=True, cancel_futures=True)
-            worst = ", ".join("%s %.3g" % kv for kv in sorted(offenders.items(), key=lambda kv: kv[1])[:4])
-            err = NonFiniteLogits("calibration on the first image: an activation tensor lies outside the range the f16 pieces hold "
-                                  "at f32 grade (stored peak below 2^-8 or beyond 2^14%s): f16x2 would lose bits silently on this "
-                                  "checkpoint; rerun with --precision fp32" % ((": " + worst) if worst else ""))
-            err.batches_run, err.images_this_rank = 0, len(mine)
-            raise err
+    def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
+        for path in label_paths:                     # must not leave them behind (the processed/ images do not depend on
+            try:                                     # the arithmetic and stay)
+                os.remove(path)
+            except OSError:
+                pass
 
-    # the GPU loop runs in this thread next to up to 32 busy pool threads: a short switch interval keeps it
-    # from waiting 5 ms for the interpreter lock at every step (restored below)
-    import sys
-    switch = sys.getswitchinterval()
-    sys.setswitchinterval(2e-4)
-    try:
-        windows = [list(range(a, min(a + window, len(mine)))) for a in range(0, len(mine), window)]
-        futs = {k: pool.submit(prepare, mine[k]) for k in (windows[0] if windows else [])}
-        t_loop = time.perf_counter()
-        for wi, win in enumerate(windows):
-            if check_flag and world > 1 and not bad_seen[0] and marker.is_set():
-                bad_seen[0] = True                       # another rank of the node saw the word
-            if bad_seen[0]:                              # f16x2 cannot carry these weights: the run is abandoned here
-                break
-            if wi + 1 < len(windows):                    # the pool starts on the next window before the GPU gets this one
-                for k in windows[wi + 1]:
-                    futs[k] = pool.submit(prepare, mine[k])
-            t0 = clock()
-            frames = {k: futs.pop(k).result() for k in win}
-            prof["main.wait_for_frames"] += clock() - t0
-            groups = defaultdict(list)
-            for k in win:
-                groups[frames[k].shape].append(k)
-            for shape, ks in sorted(groups.items()):
-                shape_count[shape] += len(ks)
-                for a in range(0, len(ks), batch):
-                    if bad_seen[0]:
-                        break
-                    part = ks[a:a + batch]
-                    n, (h, w) = len(part), shape[:2]
-                    t0 = clock()
-                    slot = n_batches % depth                  # free: at most n_streams batches are pending, on other slots
-                    sid = n_batches % n_streams
-                    mdl = models[sid]
-                    st = stage[slot]                          # frames are packed while the GPU runs the batches before
-                    if st["buf"].numel() < n * h * w * 3:       # cannot happen after the preprocessor (h, w <= target_size)
-                        st["buf"] = torch.empty(n * h * w * 3, dtype=torch.uint8).pin_memory()
-                    st["ev"].synchronize()                    # the copy that last read this buffer has finished
-                    xb = st["buf"][: n * h * w * 3].view(n, h, w, 3)
-                    xnp = xb.numpy()
-                    for j, k in enumerate(part):
-                        xnp[j] = frames[k]
-                    need = n * h * w
-                    if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:
-                        ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
-                    t1 = clock()
-                    with torch.cuda.stream(gpu_streams[sid]):
-                        x = xb.to(dev, non_blocking=True)     # uint8 NHWC; normalised on the device
-                        st["ev"].record()
-                        key = (n, h, w)
-                        if autotune and (sid, key) not in tuned and n == batch and shape_count[shape] >= 2 * batch:
-                            mdl.autotune(x)                  # once per distinct full-batch shape and model object
-                            tuned.add((sid, key))
-                        labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                            small_zones=small_zones)   # models.py:269-276 on the device
-                        ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
-                        ring[slot][1][:n].copy_(counts, non_blocking=True)
-                        if check_flag:
-                            mdl.nonfinite_peek_async(flag_host[slot:slot + 1])
-                        ring_ev[slot].record()
-                    t2 = clock()
-                    pending.append((slot, [(k, mine[k]) for k in part], n, h, w))
-                    while len(pending) > n_streams:           # the oldest batch's labels, while the newer ones run
-                        consume(pending.popleft())
-                    prof["main.pack"] += t1 - t0; prof["main.h2d_and_launch"] += t2 - t1; prof["main.consume"] += clock() - t2
-                    n_batches += 1
-            frames.clear()
-        while pending:
-            consume(pending.popleft())
-        for f in done:
-            f.result()
-    finally:                                         # also on an exception from a worker: no stray threads, switch interval restored
-        pool.shutdown(wait=True, cancel_futures=True)
-        sys.setswitchinterval(switch)
-    torch.cuda.synchronize()
-    t_done = time.perf_counter()
-    if precision == "f16x2":
-        # f16x2 keeps every value as two f16 pieces: an activation beyond +-65504 cannot be represented and turns into NaN
-        # (never into a silently wrong number).  Unknown weights that do this belong in the f32 MFMA mode.  Every rank
-        # learns of it (one more tiny collective) so that all of them leave before the row gather, none waits in it.
-        # The word rides back with every batch (consume), so a rank that sees it stops at that batch instead of finishing its
-        # shard; the contexts are all read (and reset) here once more, whatever the first one says.
-        bad = any([m.nonfinite_seen() for m in models]) or bad_seen[0]
-        if dist is not None:
-            flag = torch.tensor([int(bad)], dtype=torch.int32, device=dev if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-            bad = bool(int(flag.item()))
-            if rank == 0:
-                marker.clear()                       # every rank is past its loop (the all-reduce above)
-        if bad:
-            for path in label_paths:                 # this rank's label PNGs of the invalid run: a crash before the rerun
-                try:                                 # must not leave them behind (the processed/ images do not depend on
-                    os.remove(path)                  # the arithmetic and stay)
-                except OSError:
-                    pass
-            err = NonFiniteLogits("a forward produced non-finite logits in f16x2 mode (an activation beyond f16's range, or NaN/inf "
-                                  "in the weights): the run was abandoned after %d of this rank's %d images and its label PNGs "
-                                  "removed; rerun with --precision fp32" % (min(n_batches * batch, len(mine)), len(mine)))
-            err.batches_run, err.images_this_rank = n_batches, len(mine)
-            raise err
-
+    folder_run.run_loop(r, window, prepare, launch, consume, lambda: prepare(0)[0] if mine else None, calibrate,
+                        on_abandon=remove_labels, abandon_note=" and its label PNGs removed")
     if os.environ.get("NBC_FOLDER_PROFILE"):
         print("rank %d stage seconds (pool stages summed over %d threads): %s; loop wall %.2f s" %
-              (rank, workers, ", ".join("%s %.2f" % kv for kv in sorted(prof.items())), t_done - t_loop), flush=True)
-    cap = max(len(s) for s in shards) if shards else 0
-    # RCCL gathers device tensors; a gloo group (one-GPU rehearsals of the multi-rank path) gathers on the host
-    gather_dev = dev if dist is not None and dist.get_backend() == "nccl" else None
-    allrows = gather_rows(rows, n_total, world, dist, gather_dev, cap=cap)
-    if rank == 0:
+              (r.rank, r.workers, ", ".join("%s %.2f" % kv for kv in sorted(prof.items())), r.t_done - r.t_loop), flush=True)
+    allrows = folder_run.gather(r, rows, ROW_WIDTH)
+    if r.rank == 0:
         write_stats_csv(os.path.join(root, "results", "final_stats.csv"),
-                        [stats_row(items[int(r[0])]["name"], items[int(r[0])]["wood"], int(r[1]), int(r[2]), int(r[3]), int(r[4]))
-                         for r in allrows])
-    if dist is not None:
-        dist.barrier()
-    t_end = time.perf_counter()
-    return {"rank": rank, "world": world, "images_total": n_total, "images_this_rank": len(mine), "batches": n_batches,
-            "batch": batch, "host_workers": workers, "setup_s": t_ready - t_start, "loop_s": t_done - t_loop,
-            "total_s": t_end - t_start, "images_per_s_loop": len(mine) / max(t_done - t_loop, 1e-9),
-            "distinct_shapes": len(shape_count), "autotuned_shapes": len({k for _, k in tuned}), "streams": n_streams}
-
-
-def launch_ranks(n: int, argv: Sequence[str], module: str = "neuralbarkcalculator_amd.predict") -> int:
-    """``--gpus N`` without a torchrun environment: start N ranks (one per GPU) of ``module`` as a child process."""
-    import socket
-    import subprocess
-    import sys
-    import torch
-    if torch.cuda.device_count() < n:                # counts devices without initialising HIP
-        print("predict: --gpus %d but this node shows %d GPU(s)" % (n, torch.cuda.device_count()), file=sys.stderr)
-        return 2
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "-m", module] + list(argv)
-    return subprocess.run(cmd, env=env).returncode
+                        [stats_row(items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), int(g[3]), int(g[4]))
+                         for g in allrows])
+    return dict(folder_run.finish(r), host_workers=r.workers, distinct_shapes=len(r.shape_count),
+                autotuned_shapes=len({k for _, k in tuned}))
 
 
 def main(argv=None):
@@ -834,31 +474,13 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0", help="cuda:N (the CPU path is the reference itself)")
     ap.add_argument("--exclude_nodes", action="store_true")
     ap.add_argument("--only_preprocess", action="store_true")
-    ap.add_argument("--model_path", default="./best_model.pt")       # predict.py:57
-    ap.add_argument("--precision", choices=["auto", "fp32", "f16x2", "bf16"], default="auto",
-                    help="auto (default): the f32-grade f16x2 mode, 2.4x faster than the f32 MFMA at the same tolerances, and a "
-                         "second run in fp32 if the weights drive an activation beyond f16's range (the library says so); fp32: "
-                         "f32 MFMA; bf16: throughput mode, not f32 grade")
     ap.add_argument("--no_small_zones", action="store_true")
-    ap.add_argument("--gpus", type=int, default=1, help="shard the folder over N GPUs of this node (one process each, RCCL)")
-    ap.add_argument("--batch", type=int, default=None, help="frames of equal size per forward (default 2 in fp32, 8 in bf16)")
-    ap.add_argument("--streams", type=int, default=None, help="batches in flight, each on its own HIP stream (default 4)")
-    ap.add_argument("--arch", choices=["auto"] + list(ARCH_CHOICES), default="auto",
-                    help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--autotune", action="store_true",
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
-    ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
-                    help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
-                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
+    folder_run.add_shared_arguments(ap)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
-    try:
-        args.precision = resolve_bn_stats(args.bn_stats, args.precision)
-        if args.arch != "auto":
-            check_bn_stats_arch(args.bn_stats, args.arch)
-        args.precision = resolve_arch_precision(args.arch, args.precision)
-    except ValueError as e:
-        ap.error(str(e))
+    folder_run.resolve_arguments(ap, args)
     if not args.device.startswith("cuda"):
         raise SystemExit("this package is the MI355X path; run the reference for --device=cpu")
     if args.only_preprocess:                             # predict.py:53-55: the resize runs on the device here too
@@ -872,25 +494,8 @@ def main(argv=None):
     if "WORLD_SIZE" not in os.environ and ":" in args.device:
         idx = int(args.device.split(":")[1])
     kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
-    if args.precision == "auto":
-        stats = None
-        try:
-            stats = predict_folder(args.root_path, args.model_path, "f16x2", args.exclude_nodes, not args.no_small_zones, idx,
-                                   precision_auto=True, **kw)
-        except NonFiniteLogits as e:                 # raised on every rank alike
-            if int(os.environ.get("RANK", "0")) == 0:
-                print("predict: %s -- running the folder again on the f32 MFMA" % e, flush=True)
-        if stats is None:
-            # outside the except block: the exception's traceback holds the first run's frame (four model contexts with
-            # their workspaces, the pinned rings, the streams) for as long as the block lasts
-            import gc
-            import torch
-            gc.collect()
-            torch.cuda.empty_cache()
-            stats = predict_folder(args.root_path, args.model_path, "fp32", args.exclude_nodes, not args.no_small_zones, idx, **kw)
-    else:
-        stats = predict_folder(args.root_path, args.model_path, args.precision, args.exclude_nodes,
-                               not args.no_small_zones, idx, **kw)
+    stats = folder_run.run_precision("predict", lambda precision, **auto: predict_folder(
+        args.root_path, args.model_path, precision, args.exclude_nodes, not args.no_small_zones, idx, **auto, **kw), args.precision)
     if stats["rank"] == 0:
         print("predicted %(images_total)d images (%(images_this_rank)d on rank 0, %(batches)d batches): %(total_s).2f s, "
               "%(images_per_s_loop).1f images/s in the loop on this rank" % stats)

@@ -3,7 +3,7 @@
 
 No 8-GPU node is available to this builder, so the GPU stage of predict.predict_folder is REPLACED BY A SLEEP of the
 measured per-batch time and everything the host does per image runs for real, in R processes of T pool threads each
-(the driver's shape: one process per GPU, NBC_HOST_WORKERS threads, predict.py:464-492):
+(the driver's shape: one process per GPU, NBC_HOST_WORKERS threads, the loop of folder_run.run_loop):
     prepare:  read the .bmp, decode (24-bit BMP fast path), preprocess (a 1024 x 1024 frame passes through),
               write processed/<wood>/<name>.png
     (sleep):  one batch of `batch` frames every `gpu_ms_per_batch`

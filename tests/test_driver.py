@@ -170,6 +170,37 @@ def test_gather_of_unequal_pixel_balanced_shards_over_gloo(tmp_path):
         np.testing.assert_array_equal(np.load(os.path.join(str(tmp_path), f"prow{r}.npy")), want)
 
 
+def test_windows_and_batches_partition_a_shard():
+    """The folder loop's partition of a shard: windows in order, inside a window the frames grouped by shape (sorted) and
+    cut into batches of up to `batch`; every local image runs exactly once, a skipped one (shape None) never."""
+    from neuralbarkcalculator_amd import folder_run as fr
+    assert fr.windows(0, 64) == [] and fr.windows(1, 64) == [[0]]                  # an empty shard, one image
+    assert fr.batches_of([0], {0: (8, 8, 3)}, 2) == [((8, 8, 3), [0])]
+    assert fr.windows(7, 3) == [[0, 1, 2], [3, 4, 5], [6]]
+    rng = np.random.default_rng(5)
+    for n, window, batch in ((1, 64, 2), (10, 4, 2), (23, 7, 3), (64, 64, 8), (65, 64, 1)):
+        heights = rng.integers(0, 3, size=n)
+        shapes = {k: None if k % 11 == 5 else (520 + int(heights[k]), 1024, 3) for k in range(n)}
+        wins = fr.windows(n, window)
+        assert sum(wins, []) == list(range(n)) and all(0 < len(w) <= window for w in wins)
+        ran = []
+        for win in wins:
+            parts = fr.batches_of(win, shapes, batch)
+            assert [s for s, _ in parts] == sorted(s for s, _ in parts)            # one shape after the other
+            for shape, part in parts:
+                assert 0 < len(part) <= batch and part == sorted(part) and set(part) <= set(win)
+                assert all(shapes[k] == shape for k in part)
+            for shape in {s for s, _ in parts}:                                    # only a group's last batch is short
+                sizes = [len(p) for s, p in parts if s == shape]
+                assert all(m == batch for m in sizes[:-1])
+            ran += [k for _, part in parts for k in part]
+        assert sorted(ran) == [k for k in range(n) if shapes[k] is not None] and len(set(ran)) == len(ran)
+    # a window whose groups do not divide by the batch: 5 frames of one shape and 2 of another, batch 2
+    shapes = {k: (600, 1024, 3) if k in (1, 4) else (528, 1024, 3) for k in range(7)}
+    assert fr.batches_of(range(7), shapes, 2) == [((528, 1024, 3), [0, 2]), ((528, 1024, 3), [3, 5]), ((528, 1024, 3), [6]),
+                                                  ((600, 1024, 3), [1, 4])]
+
+
 def test_png_writer_round_trips_through_pil():
     import io
     from PIL import Image
