@@ -338,6 +338,26 @@ int nbc_remove_small_zones(nbc_ctx* ctx, void* labels_dev, int labels_dtype, int
 int nbc_confusion(const void* labels_dev, int labels_dtype, const uint8_t* target_dev,
                   int N, int H, int W, int64_t* conf_dev, void* hip_stream);
 
+/* Exact per-image, per-channel integer moments of uint8 RGB frames: what compute_mean_std (utils.py:23-39: ToTensor, then
+ * .mean(2) and .std(2) of every image's [3, H*W] view) needs from the pixels.  With S1 and S2 the two sums of a channel and
+ * P = H * W, the image's mean is S1 / (255 P) and its unbiased standard deviation sqrt((P S2 - S1^2) / (P (P - 1) 65025)):
+ * host arithmetic (neuralbarkcalculator_amd/stats.py).  No context: csrc/dataset_stats.hip.
+ * x_dev        uint8 [N,H,W,3], the layout of NBC_IN_U8_NHWC; any alignment
+ * moments_dev  uint64 [N,3,2]: moments[n][c] = { sum of v, sum of v*v } over the H*W pixels of channel c; overwritten
+ * Integer sums: an image's six numbers are the same alone, in any batch and on any stream.  Runs on hip_stream (the caller's
+ * current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null pointer, N < 1 or N > 65535, H or
+ * W < 1, H * W >= 2^31.  Every sum stays below 2^47. */
+int nbc_image_moments(const uint8_t* x_dev, int N, int H, int W, uint64_t* moments_dev, void* hip_stream);
+
+/* Per-image class counts of grey target masks: what compute_pos_weight (utils.py:51-69) counts with (targets == y).sum(), and
+ * what get_splits' sample_weight (utils.py:94-95: the pixels that are not class 0) is made of.  No context:
+ * csrc/dataset_stats.hip.
+ * target_dev  uint8 [N,H,W]; class = round(2 * float32(v) / 255) exactly as nbc_confusion derives it
+ * counts_dev  int64 [N,4]: pixels of class 0, 1, 2, and the pixels whose grey level is none of 0, 127, 255 (they are counted
+ *             in their class as well; the fourth cell only reports them); overwritten
+ * Runs on hip_stream; no synchronisation.  Limits and errors as nbc_image_moments. */
+int nbc_target_counts(const uint8_t* target_dev, int N, int H, int W, int64_t* counts_dev, void* hip_stream);
+
 /* Per-image Lovasz-Softmax loss terms: `LovaszSoftmax()(logits, target)` (lovasz_losses.py:162-223: softmax over the classes,
  * then lovasz_softmax_flat with classes='present', ignore=None) of each image as a batch of one -- the training objective of
  * __main__.py:236-239, which exp.test / test_model_on_checkpoint print as test_loss (__main__.py:179-197).  No context:

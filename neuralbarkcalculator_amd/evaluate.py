@@ -7,9 +7,11 @@ was selected by.
 * input: ``ROOT/samples/<wood_type>/<name>`` listed as ``predict.list_images`` lists them (dataset.py:41-68), each with its
   dual ``ROOT/duals/<wood_type>/<name.replace("bmp", "png")>`` (every ``bmp`` replaced, dataset.py:58), decoded with PIL
   ``convert('L')``;
-* the network sees each sample as it is, through the uint8 ingest and the default mean / std of the predict driver: the
-  reference's evaluation never runs the preprocessor, its labelled folder is already at model resolution.  Nothing is
-  written under ``processed/``;
+* the network sees each sample as it is, through the uint8 ingest and, by default, the default mean / std of the predict
+  driver (models.py:208-209); ``--mean R G B --std R G B`` or ``--stats PATH`` (``normalization=``) name another pair, as
+  the reference's loop does with the ``compute_mean_std`` of its folder (__main__.py:204; ``python -m
+  neuralbarkcalculator_amd.stats`` computes it), and the summary then says which.  The reference's evaluation never runs
+  the preprocessor, its labelled folder is already at model resolution.  Nothing is written under ``processed/``;
 * on the device, per batch of equal-sized frames: forward -> argmax labels -> ``confusion`` (raw) -> ``remove_small_zones``
   (150 pixels) -> ``confusion`` (clean).  Only the two int64 ``[N,3,3]`` results come back; ``metrics.py`` turns them into
   the row of ``__main__.py:371-398`` (IoU from the raw argmax, F1 after remove_small_zones, see there);
@@ -103,9 +105,11 @@ def write_stats_csv(path: str, rows, loss: bool = False) -> None:
 
 
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
-           bn_stats: str = "running", loss_rows: np.ndarray = None) -> Tuple[List[List[str]], dict]:
+           bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
+           normalization_source: str = "arguments") -> Tuple[List[List[str]], dict]:
     """CSV rows and summary from the gathered rank rows (rank 0); ``loss_rows``: the gathered ``LOSS_ROW_WIDTH`` rows of
-    ``--loss`` (None without it)."""
+    ``--loss`` (None without it); ``normalization``: the ``(mean, std)`` the run was given (None: the defaults, and no entry
+    in the summary)."""
     terms = None
     if loss_rows is not None:
         terms = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in loss_rows}
@@ -129,18 +133,23 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
         summary.update(metrics.summarize(rows, raw_total, clean_total))
     if terms is not None:
         summary["lovasz_softmax"] = metrics.summarize_loss(rows, len(metrics.EVAL_CSV_HEADER))
+    if normalization is not None:
+        summary["normalization"] = {"mean": list(normalization[0]), "std": list(normalization[1]),
+                                    "source": normalization_source}
     return rows, summary
 
 
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
                     streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
-                    loss: bool = False) -> dict:
+                    loss: bool = False, normalization=None, normalization_source: str = "arguments") -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
     ("fp32", FCN only; ``predict.resolve_bn_stats``).  ``loss``: also the per-image Lovasz-Softmax loss (module
-    docstring).  Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
+    docstring).  ``normalization``: the ``(mean, std)`` of the ingest (``folder_run.resolve_normalization``; None: the
+    defaults), set on every stream's model object; ``normalization_source``: what the summary says of where it came from.
+    Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size)
     dev, batch = r.dev, r.batch
@@ -151,7 +160,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             m.lovasz_softmax(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                              torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
-                        lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm)
+                        lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
+                        normalization=normalization)
 
     items = list_labelled(root)
     sizes = folder_run.shard(r, items, lambda d: image_hw(d["src"]))
@@ -210,7 +220,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
-        csv_rows, summary = report(items, allrows, r.precision, model_path, bn_stats, loss_rows=all_loss)
+        csv_rows, summary = report(items, allrows, r.precision, model_path, bn_stats, loss_rows=all_loss,
+                                   normalization=normalization, normalization_source=normalization_source)
         write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
@@ -228,6 +239,9 @@ def format_summary(summary: dict) -> str:
         ", per-image BatchNorm statistics" if summary.get("bn_statistics") == "image" else "", summary["model_path"],
         summary["images_skipped"],
         "".join("; %s: %s" % (r, ", ".join(v)) for r, v in summary["skipped"].items() if v))]
+    if "normalization" in summary:
+        nm = summary["normalization"]
+        lines.append("normalised with mean %s, std %s (%s)" % (nm["mean"], nm["std"], nm["source"]))
     if "pooled" in summary:
         p = summary["pooled"]
         lines.append("pooled over all pixels: " + ", ".join("%s %.3f" % (k, p[k]) for k in p))
@@ -262,6 +276,10 @@ def main(argv=None):
     kw = dict(batch=args.batch, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
     if args.loss:
         kw["loss"] = True
+    if args.normalization is not None:
+        kw["normalization"] = args.normalization
+        if args.stats is not None:
+            kw["normalization_source"] = args.stats
     stats = folder_run.run_precision("evaluate", lambda precision, **auto: evaluate_folder(
         args.root_path, args.model_path, precision, idx, **auto, **kw), args.precision)
     if stats["rank"] == 0:

@@ -6,7 +6,8 @@ A driver (``predict.predict_folder``, ``evaluate.evaluate_folder``) calls, in th
 * ``open_run``: the rank context (rank, world, ``dist`` or None, device, the batch and stream defaults);
 * ``bring_up``: rank 0's folders and the start barrier, the checkpoint on rank 0 alone, architecture (one broadcast under
   ``--arch auto``) and precision, the weight broadcast, the ``pack_flags`` refusal, one model object and side stream per
-  batch in flight, the largest workspaces once (``warm``: the driver's own);
+  batch in flight, the ingest's mean / std on every one of them (``normalization``), the largest workspaces once (``warm``:
+  the driver's own); ``bring_up_without_model`` for a driver that runs no network (``stats``);
 * ``shard``: the host pool and this rank's contiguous, pixel-balanced share of the driver's item list;
 * ``run_loop``: the f16x2 calibration guard (one verdict broadcast), the batch loop, and the non-finite settlement (one MAX
   all-reduce in f16x2).  The driver supplies ``prepare(k)`` (pool: the arrays of local image k, or None to skip it),
@@ -14,8 +15,8 @@ A driver (``predict.predict_folder``, ``evaluate.evaluate_folder``) calls, in th
 * ``gather`` (once per row kind) and ``finish`` (the final barrier and the statistics every driver returns).
 
 No collective sits in the per-image path: ranks with different numbers of windows tell each other of an abandoned f16x2
-run through ``AbandonMarker``.  ``run_precision``, ``add_shared_arguments`` and ``resolve_arguments`` are the drivers'
-shared command-line tail.
+run through ``AbandonMarker``.  ``run_precision``, ``add_shared_arguments``, ``resolve_arguments`` and
+``resolve_normalization`` are the predict and evaluate drivers' shared command-line tail.
 """
 from __future__ import annotations
 
@@ -240,18 +241,41 @@ def open_run(root: str, tool: str, precision: str, device_index: int = None, bat
     return r
 
 
-def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool, make_dirs, warm=None) -> None:
-    """Rank 0's ``make_dirs(root)`` and the start barrier, then ``r.models`` (``r.n_streams`` objects on one copy of the
-    weights), ``r.gpu_streams``, and the resolved ``r.arch`` / ``r.precision``.  ``warm(model)``: the driver's own workspaces, grown
-    to their largest size once like the forward's."""
-    import time
-    import torch
-    from .model import MODELS
+def _start(r, make_dirs) -> None:
+    """Rank 0's ``make_dirs(root)`` and the start barrier."""
     if r.rank == 0:
         make_dirs(r.root)
         r.marker.clear()
     if r.dist is not None:
         r.dist.barrier()
+
+
+def bring_up_without_model(r, make_dirs) -> None:
+    """``bring_up`` for a driver that reads no checkpoint and runs no network (``stats``): rank 0's ``make_dirs(root)``, the
+    start barrier and the side streams.  ``r.models`` holds no object, one None per stream: ``run_loop`` touches a model only
+    for the f16x2 guards, which ``r.precision`` = "fp32" (required here) never runs."""
+    import time
+    import torch
+    if r.precision != "fp32":
+        raise ValueError("a run without a model has no arithmetic mode: precision must be 'fp32', not %r" % (r.precision,))
+    _start(r, make_dirs)
+    r.arch = None
+    r.models = [None] * r.n_streams
+    r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
+    r.t_ready = time.perf_counter()
+
+
+def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool, make_dirs, warm=None,
+             normalization=None) -> None:
+    """Rank 0's ``make_dirs(root)`` and the start barrier, then ``r.models`` (``r.n_streams`` objects on one copy of the
+    weights), ``r.gpu_streams``, and the resolved ``r.arch`` / ``r.precision``.  ``warm(model)``: the driver's own workspaces, grown
+    to their largest size once like the forward's.  ``normalization``: the ``(mean, std)`` of the uint8 ingest
+    (``resolve_normalization``), set on every model object before anything runs (a clone owns its context and would start on
+    the defaults); None leaves the defaults of models.py:208-209."""
+    import time
+    import torch
+    from .model import MODELS
+    _start(r, make_dirs)
     state_dict = None
     if r.rank == 0:                                  # only one rank touches the checkpoint
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
@@ -270,6 +294,9 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
                               "normalisation, or a BatchNorm scale outside f32's normal range under its powers of two): f16x2 "
                               "would not be f32 grade on this checkpoint; rerun with --precision fp32" % model.pack_flags)
     r.models = [model] + [model.clone_shared() for _ in range(r.n_streams - 1)]
+    if normalization is not None:                    # every rank parsed the same arguments: no collective
+        for m in r.models:
+            m.set_normalization(*normalization)
     # side streams only: the default stream stays with whatever else the driver runs on the device
     r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
     for m in r.models:                               # the largest workspace once: a context's buffers only grow, and a folder of
@@ -485,7 +512,7 @@ def launch_ranks(n: int, argv: Sequence[str], module: str = "neuralbarkcalculato
 
 
 def add_shared_arguments(ap) -> None:
-    """The options both drivers take."""
+    """The options the predict and evaluate drivers take."""
     ap.add_argument("--model_path", default="./best_model.pt")       # predict.py:57
     ap.add_argument("--precision", choices=["auto", "fp32", "f16x2", "bf16"], default="auto",
                     help="auto (default): the f32-grade f16x2 mode, 2.4x faster than the f32 MFMA at the same tolerances, and a "
@@ -499,11 +526,56 @@ def add_shared_arguments(ap) -> None:
     ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
                     help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
                          "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
+    ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
+                    help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
+                         "(with --std; default: the constants of the reference's model class)")
+    ap.add_argument("--std", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
+                    help="per-channel standard deviation that goes with --mean")
+    ap.add_argument("--stats", metavar="PATH", default=None,
+                    help="take mean and std from this JSON (results/dataset_stats.json of python -m neuralbarkcalculator_amd.stats) "
+                         "instead of --mean / --std")
+
+
+def resolve_normalization(mean=None, std=None, stats: str = None):
+    """The ``(mean, std)`` pair (two tuples of three floats) the drivers' ``--mean R G B --std R G B`` or ``--stats PATH``
+    name, or None when none of them is given.  ``ValueError``: one of ``mean`` / ``std`` without the other, ``stats`` beside
+    them, a file that cannot be read as JSON or lacks one of the two keys, a value count other than three, a mean that is not
+    finite, a std that is not finite and positive."""
+    import json
+    import math
+    if stats is not None:
+        if mean is not None or std is not None:
+            raise ValueError("--stats names the mean and std: --mean / --std cannot be given beside it")
+        try:
+            with open(stats) as f:
+                doc = json.load(f)
+        except (OSError, ValueError) as e:
+            raise ValueError("--stats %s: %s" % (stats, e))
+        if not isinstance(doc, dict) or "mean" not in doc or "std" not in doc:
+            raise ValueError("--stats %s: the file holds no \"mean\" and \"std\"" % stats)
+        mean, std = doc["mean"], doc["std"]
+    if mean is None and std is None:
+        return None
+    if mean is None or std is None:
+        raise ValueError("--mean and --std go together: both or neither")
+    try:
+        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    except (TypeError, ValueError):
+        raise ValueError("mean and std must be three numbers each")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must be three numbers each")
+    if not all(math.isfinite(v) for v in mean):
+        raise ValueError("mean must be finite, got %r" % (mean,))
+    if not all(math.isfinite(v) and v > 0 for v in std):
+        raise ValueError("std must be finite and positive, got %r" % (std,))
+    return mean, std
 
 
 def resolve_arguments(ap, args) -> None:
-    """``args.precision`` as ``--bn_stats`` and a named ``--arch`` leave it; what they refuse ends in ``ap.error``."""
+    """``args.precision`` as ``--bn_stats`` and a named ``--arch`` leave it, and ``args.normalization``
+    (``resolve_normalization``: the pair, or None); what they refuse ends in ``ap.error``."""
     try:
+        args.normalization = resolve_normalization(args.mean, args.std, args.stats)
         args.precision = resolve_bn_stats(args.bn_stats, args.precision)
         if args.arch != "auto":
             check_bn_stats_arch(args.bn_stats, args.arch)

@@ -339,7 +339,8 @@ def plan_items(root: str) -> List[dict]:
 def predict_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32",
                    exclude_nodes: bool = False, small_zones: bool = True, device_index: int = None,
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
-                   streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False) -> dict:
+                   streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
+                   normalization=None) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -359,7 +360,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.  ``bn_stats``: ``"running"``
     (eval mode) or ``"image"``, the per-image BatchNorm statistics the shipped tool ran with ("fp32", FCN only:
     ``resolve_bn_stats``, ``check_bn_stats_arch``).  EfficientNet networks run "fp32" (``resolve_arch_precision``;
-    ``precision_auto``: ``precision`` came from ``--precision auto``).
+    ``precision_auto``: ``precision`` came from ``--precision auto``).  ``normalization``: the ``(mean, std)`` the frames are
+    normalised with (``--mean`` / ``--std`` / ``--stats``, ``folder_run.resolve_normalization``), set on every stream's model
+    object, the calibration guard's included; None: the defaults of models.py:208-209.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -373,7 +376,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel)
         if small_zones:
             m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
-    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, generate_folders, warm)
+    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, generate_folders, warm, normalization=normalization)
 
     items = plan_items(root)
 
@@ -494,6 +497,11 @@ def main(argv=None):
     if "WORLD_SIZE" not in os.environ and ":" in args.device:
         idx = int(args.device.split(":")[1])
     kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
+    if args.normalization is not None:
+        kw["normalization"] = args.normalization
+        if int(os.environ.get("RANK", "0")) == 0:
+            print("predict: frames normalised with mean %s, std %s (%s)" % (
+                list(args.normalization[0]), list(args.normalization[1]), args.stats or "arguments"), flush=True)
     stats = folder_run.run_precision("predict", lambda precision, **auto: predict_folder(
         args.root_path, args.model_path, precision, args.exclude_nodes, not args.no_small_zones, idx, **auto, **kw), args.precision)
     if stats["rank"] == 0:
