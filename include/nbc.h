@@ -384,6 +384,36 @@ int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, 
                        void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev,
                        void* hip_stream);
 
+/* Per-image pixel-wise cross-entropy sums: what CustomWeightedCrossEntropy (utils.py:151-165: F.cross_entropy with
+ * reduction='none', times the class weight at max(argmax, target), mean over the pixels), the plain cross-entropy (xloss,
+ * lovasz_losses.py:246-251) and MixedLoss (utils.py:185-192) need from the pixels of each image as a batch of one, with the
+ * weights (compute_pos_weight, utils.py:51-69; get_pos_weight, utils.py:72-73) left to the host.  No context:
+ * csrc/pixel_ce.hip.  Per image n and pixel: t = target class, p = argmax of the three logits (first maximum wins, a NaN
+ * counts as the maximum: torch.argmax and nbc_forward's labels), ce = logsumexp(x) - x[t], evaluated in f64 from the f32
+ * logits as log(sum_c exp(x_c - m)) - (x_t - m) with m = max_c x_c:
+ *   sums[n][t][p] = sum of ce over the pixels of cell (t, p), counts[n][t][p] = their number.
+ * Then cross_entropy = sum(sums) / P, CustomWeightedCrossEntropy(w) = sum(w[max(t, p)] sums[t][p]) / P, and MixedLoss is that
+ * / 4 plus the Lovasz-Softmax loss: host arithmetic (neuralbarkcalculator_amd/metrics.py).
+ * logits_full_dev  float32 [N,3,H,W], what nbc_forward writes to logits_full_dev; any 4-byte alignment (an image whose three
+ *                  planes start on 16-byte boundaries, i.e. H * W a multiple of 4 in an aligned buffer, is read by 16-byte loads)
+ * target_dev       uint8 [N,H,W] grey levels; class = round(2 * float32(v) / 255) as nbc_confusion derives it
+ * workspace_dev    at least nbc_pixel_ce_workspace_bytes(N, H, W) bytes of device memory, 256-byte aligned; contents scratch
+ * sums_dev         float64 [N,3,3]; overwritten.  A pixel whose entropy is not finite reaches its own cell only: NaN for a
+ *                  NaN or +inf logit or three -inf, +inf for -inf at the target class alone, as F.cross_entropy gives
+ * counts_dev       int64 [N,3,3]; overwritten.  Equal to nbc_confusion's conf of the labels of the same forward
+ * Every float sum has a fixed order that depends on H * W alone (pixels of a lane in order, lanes, waves, per-tile partials
+ * in the workspace, tiles by a second launch) and there are no atomics: an image's 18 numbers are bit-identical alone,
+ * anywhere in a batch and on any stream.  Runs on hip_stream (the caller's current device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer, N < 1 or N > 65535, H or W < 1, H * W >= 2^31, or a workspace too
+ * small or misaligned.  With P = H * W, T = ceil(P / 4096) and A(x) = x rounded up to a multiple of 256, the workspace is
+ *   A(72 N T) + A(36 N T) bytes
+ * (an f64 and a u32 partial per image, cell and tile); nbc_pixel_ce_workspace_bytes returns 0 for a shape
+ * nbc_pixel_cross_entropy refuses. */
+size_t nbc_pixel_ce_workspace_bytes(int N, int H, int W);
+int nbc_pixel_cross_entropy(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
+                            void* workspace_dev, size_t workspace_bytes, double* sums_dev, int64_t* counts_dev,
+                            void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

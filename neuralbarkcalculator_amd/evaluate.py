@@ -35,6 +35,18 @@ Deliberate departures from the reference:
 ``(global_idx, 3 terms as int64 bit patterns)`` that a second ``all_gather`` brings to rank 0.  The CSV gains the four
 columns of ``metrics.LOSS_CSV_COLUMNS`` and the summary a ``"lovasz_softmax"`` entry.  Without the flag nothing changes.
 
+``--ce`` (``ce=True``) adds the loss the shipped checkpoint was trained on: each batch writes its full-resolution logits as
+under ``--loss`` (one buffer per stream serves both flags), and ``FCNResNet50.pixel_cross_entropy`` sums the pixel entropies
+per (target class, argmax class) cell on the batch's stream.  The ``[n,9]`` float64 sums ride back beside the confusions; each
+rank keeps rows ``(global_idx, 9 sums as int64 bit patterns)`` that one more ``all_gather`` brings to rank 0 (the kernel's
+counts are not gathered: they are the raw confusion of the rank rows).  ``metrics.py`` turns them into the plain
+cross-entropy, ``CustomWeightedCrossEntropy`` (utils.py:151-165) for the class weights of ``--class_weights W0 W1 W2`` or
+``--class_weights_from PATH`` (the ``pos_weight`` of a ``stats`` run; default ``metrics.REFERENCE_CLASS_WEIGHTS``, the
+reference's ``get_pos_weight()``) and, with ``--loss`` too, ``MixedLoss`` (utils.py:185-192).  The CSV gains the columns of
+``metrics.CE_CSV_COLUMNS`` (and ``mixed_loss``) after those of ``--loss``, the summary a ``"cross_entropy"`` entry that also
+holds the cell sums and pixel counts of the whole folder, so that it can be re-weighted without another run.  The
+reference's ``JaccardLoss`` is not computed.  Without the flag nothing changes.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -58,6 +70,7 @@ from .predict import _decode_rgb, list_images
 
 ROW_WIDTH = 22                                   # (global_idx, H, W, status, conf_raw[9], conf_clean[9])
 LOSS_ROW_WIDTH = 4                               # --loss: (global_idx, 3 float64 terms viewed as int64)
+CE_ROW_WIDTH = 10                                # --ce: (global_idx, 9 float64 cell sums viewed as int64)
 STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
 SKIP_REASONS = {STATUS_NO_DUAL: "no_dual", STATUS_SHAPE_MISMATCH: "shape_mismatch", STATUS_TOO_LARGE: "too_large"}
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
@@ -95,24 +108,55 @@ def decode_dual(path: str) -> np.ndarray:
         return np.array(im.convert("L"))
 
 
-def csv_header(loss: bool = False) -> List[str]:
-    return metrics.EVAL_CSV_HEADER + (metrics.LOSS_CSV_COLUMNS if loss else [])
+def csv_header(loss: bool = False, ce: bool = False) -> List[str]:
+    return metrics.EVAL_CSV_HEADER + (metrics.LOSS_CSV_COLUMNS if loss else []) + (metrics.CE_CSV_COLUMNS if ce else []) + \
+        ([metrics.MIXED_CSV_COLUMN] if ce and loss else [])
 
 
-def write_stats_csv(path: str, rows, loss: bool = False) -> None:
+def write_stats_csv(path: str, rows, loss: bool = False, ce: bool = False) -> None:
     with open(path, "w") as f:                   # __main__.py:433-437
-        csv.writer(f, delimiter="\t").writerows([csv_header(loss)] + [list(r) for r in rows])
+        csv.writer(f, delimiter="\t").writerows([csv_header(loss, ce)] + [list(r) for r in rows])
+
+
+def class_weights_from(path: str) -> Tuple[float, float, float]:
+    """The ``pos_weight`` of a ``results/dataset_stats.json`` (``python -m neuralbarkcalculator_amd.stats``) as class weights;
+    ValueError when the file has none, or a null in it (a class without a pixel has no weight)."""
+    with open(path) as f:
+        doc = json.load(f)
+    w = doc.get("pos_weight") if isinstance(doc, dict) else None
+    if not isinstance(w, list) or len(w) != 3:
+        raise ValueError("%s holds no pos_weight of three classes" % path)
+    if any(v is None for v in w):
+        raise ValueError("%s: pos_weight has a null: a class without a pixel has no weight" % path)
+    return check_class_weights(w)
+
+
+def check_class_weights(weights) -> Tuple[float, float, float]:
+    """Three finite weights >= 0 as floats; ValueError otherwise."""
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError("class weights must be three numbers")
+    if len(w) != 3 or not all(np.isfinite(v) and v >= 0 for v in w):
+        raise ValueError("class weights must be three finite numbers >= 0, got %r" % (list(weights),))
+    return w
 
 
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
-           normalization_source: str = "arguments") -> Tuple[List[List[str]], dict]:
+           normalization_source: str = "arguments", ce_rows: np.ndarray = None,
+           class_weights=metrics.REFERENCE_CLASS_WEIGHTS,
+           class_weights_source: str = "reference") -> Tuple[List[List[str]], dict]:
     """CSV rows and summary from the gathered rank rows (rank 0); ``loss_rows``: the gathered ``LOSS_ROW_WIDTH`` rows of
     ``--loss`` (None without it); ``normalization``: the ``(mean, std)`` the run was given (None: the defaults, and no entry
-    in the summary)."""
-    terms = None
+    in the summary); ``ce_rows``: the gathered ``CE_ROW_WIDTH`` rows of ``--ce`` (None without it), weighted with
+    ``class_weights``."""
+    terms = ce_sums = None
     if loss_rows is not None:
         terms = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in loss_rows}
+    if ce_rows is not None:
+        ce_sums = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in ce_rows}
+    ce_cells_of = [[] for _ in range(9)]             # per cell: the sums of the evaluated images
     rows, skipped = [], {r: [] for r in SKIP_REASONS.values()}
     raw_total, clean_total = np.zeros((3, 3), np.int64), np.zeros((3, 3), np.int64)
     for r in allrows:
@@ -126,6 +170,11 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
         row = metrics.eval_row(d["name"], d["wood"], raw, clean)
         if terms is not None:                    # a class is present where its target row of the confusion is not empty
             row += metrics.loss_cells(terms[int(r[0])], raw.sum(axis=1))
+        if ce_sums is not None:
+            cells = ce_sums[int(r[0])]
+            for k in range(9):
+                ce_cells_of[k].append(float(cells[k]))
+            row += metrics.ce_cells(cells, int(raw.sum()), class_weights, float(row[-1]) if terms is not None else None)
         rows.append(row)
     summary = {"precision": precision, "bn_statistics": bn_stats, "model_path": model_path, "images_evaluated": len(rows),
                "images_skipped": sum(len(v) for v in skipped.values()), "skipped": skipped}
@@ -133,6 +182,10 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
         summary.update(metrics.summarize(rows, raw_total, clean_total))
     if terms is not None:
         summary["lovasz_softmax"] = metrics.summarize_loss(rows, len(metrics.EVAL_CSV_HEADER))
+    if ce_sums is not None:
+        first = len(metrics.EVAL_CSV_HEADER) + (len(metrics.LOSS_CSV_COLUMNS) if terms is not None else 0)
+        summary["cross_entropy"] = metrics.summarize_ce(rows, first, [metrics._fsum(v) for v in ce_cells_of], raw_total,
+                                                        class_weights, class_weights_source, mixed=terms is not None)
     if normalization is not None:
         summary["normalization"] = {"mean": list(normalization[0]), "std": list(normalization[1]),
                                     "source": normalization_source}
@@ -142,23 +195,31 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
 def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: str = "fp32", device_index: int = None,
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
                     streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
-                    loss: bool = False, normalization=None, normalization_source: str = "arguments") -> dict:
+                    loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
+                    class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference") -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
     ("fp32", FCN only; ``predict.resolve_bn_stats``).  ``loss``: also the per-image Lovasz-Softmax loss (module
     docstring).  ``normalization``: the ``(mean, std)`` of the ingest (``folder_run.resolve_normalization``; None: the
     defaults), set on every stream's model object; ``normalization_source``: what the summary says of where it came from.
+    ``ce``: also the cross-entropy family (module docstring), weighted with ``class_weights`` (three finite values >= 0);
+    ``class_weights_source``: what the summary says of where they came from.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
+    if ce:
+        class_weights = check_class_weights(class_weights)
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size)
     dev, batch = r.dev, r.batch
 
-    def warm(m):                                     # the remove_small_zones workspace and, with ``loss``, the loss's
+    def warm(m):                                     # the remove_small_zones workspace and, with ``loss`` / ``ce``, theirs
         m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
         if loss:
             m.lovasz_softmax(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                              torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if ce:
+            m.pixel_cross_entropy(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
+                                  torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
                         normalization=normalization)
@@ -170,6 +231,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     loss_rows = np.zeros((len(mine), LOSS_ROW_WIDTH), dtype=np.int64) if loss else None
     if loss:
         loss_rows[:, 0] = mine
+    ce_rows = np.zeros((len(mine), CE_ROW_WIDTH), dtype=np.int64) if ce else None
+    if ce:
+        ce_rows[:, 0] = mine
 
     def prepare(k):
         """Pool: the RGB frame and the grey dual of an image that can be evaluated; its status row and None otherwise."""
@@ -187,13 +251,17 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ring = [torch.empty((2, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)]   # raw, clean
     loss_ring = [torch.empty((batch, 3), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if loss else None
     logits_buf = [torch.empty(batch * 3 * target_size * target_size, dtype=torch.float32, device=dev)
-                  for _ in range(r.n_streams)] if loss else None
+                  for _ in range(r.n_streams)] if loss or ce else None
+    ce_ring = [torch.empty((batch, 9), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if ce else None
 
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
-        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss else None
+        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce else None
         labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
+        if ce:                                                        # CustomWeightedCrossEntropy (utils.py:151-165)
+            sums, _ = mdl.pixel_cross_entropy(lg, tgt)
+            ce_ring[slot][:n].copy_(sums.view(n, 9), non_blocking=True)
         if loss:                                                      # LovaszSoftmax (:236-239)
             terms, _ = mdl.lovasz_softmax(lg, tgt)
             loss_ring[slot][:n].copy_(terms, non_blocking=True)
@@ -209,6 +277,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
             if loss:
                 loss_rows[k, 1:] = loss_ring[slot][j].numpy().view(np.int64)
+            if ce:
+                ce_rows[k, 1:] = ce_ring[slot][j].numpy().view(np.int64)
 
     def first_frame():                               # the calibration guard's: this rank's first image that fits
         first = next((gi for gi in mine if max(sizes[gi]) <= target_size), None)
@@ -217,12 +287,15 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     folder_run.run_loop(r, window, prepare, launch, consume, first_frame, calibrate, bytes_per_pixel=(3, 1))
     allrows = folder_run.gather(r, rows, ROW_WIDTH)
     all_loss = folder_run.gather(r, loss_rows, LOSS_ROW_WIDTH) if loss else None
+    all_ce = folder_run.gather(r, ce_rows, CE_ROW_WIDTH) if ce else None
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
         csv_rows, summary = report(items, allrows, r.precision, model_path, bn_stats, loss_rows=all_loss,
-                                   normalization=normalization, normalization_source=normalization_source)
-        write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss)
+                                   normalization=normalization, normalization_source=normalization_source,
+                                   **(dict(ce_rows=all_ce, class_weights=class_weights,
+                                           class_weights_source=class_weights_source) if ce else {}))
+        write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss, **(dict(ce=True) if ce else {}))
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -230,6 +303,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if loss:                                     # rank 0: {global_idx: float64 [3] terms}
         out["loss_terms"] = None if r.rank != 0 else {
             int(g[0]): np.ascontiguousarray(g[1:]).view(np.float64).copy() for g in all_loss}
+    if ce:                                       # rank 0: {global_idx: float64 [3,3] cell sums}
+        out["ce_sums"] = None if r.rank != 0 else {
+            int(g[0]): np.ascontiguousarray(g[1:]).view(np.float64).reshape(3, 3).copy() for g in all_ce}
     return out
 
 
@@ -252,6 +328,12 @@ def format_summary(summary: dict) -> str:
         fmt = lambda v: "-" if v is None else "%.6f" % v
         lines.append("lovasz_softmax loss: mean over images %s (per class, over the images where it is present: %s)" % (
             fmt(ls["mean_over_images"]), ", ".join("%s %s" % (k, fmt(v)) for k, v in ls["per_class_mean"].items())))
+    if summary.get("cross_entropy"):
+        ce = summary["cross_entropy"]
+        fmt = lambda v: "-" if v is None else "%.6f" % v
+        lines.append("cross-entropy: mean over images %s; class weights %s (%s)" % (
+            ", ".join("%s %s" % (k, fmt(v)) for k, v in ce["mean_over_images"].items()),
+            " ".join(repr(v) for v in ce["class_weights"]), ce["class_weights_source"]))
     return "\n".join(lines)
 
 
@@ -263,6 +345,14 @@ def main(argv=None):
     folder_run.add_shared_arguments(ap)
     ap.add_argument("--loss", action="store_true",
                     help="also the per-image Lovasz-Softmax loss, the training objective (four more CSV columns, computed on the GPU)")
+    ap.add_argument("--ce", action="store_true",
+                    help="also the cross-entropy the shipped checkpoint was trained on: cross_entropy and weighted_cross_entropy "
+                         "columns (and mixed_loss with --loss), summed on the GPU")
+    ap.add_argument("--class_weights", type=float, nargs=3, metavar=("W0", "W1", "W2"), default=None,
+                    help="--ce: the class weights (default: the reference's 0.4004 2.0334 93.1921)")
+    ap.add_argument("--class_weights_from", metavar="PATH", default=None,
+                    help="--ce: take the class weights from the pos_weight of a dataset_stats.json (python -m "
+                         "neuralbarkcalculator_amd.stats)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
@@ -270,12 +360,28 @@ def main(argv=None):
     if args.exclude_nodes:
         raise SystemExit("evaluate: --exclude_nodes is not supported: IoU and F1 are defined on the three classes "
                          "(nothing, bark, node) of the duals")
+    if args.class_weights is not None and args.class_weights_from is not None:
+        ap.error("--class_weights and --class_weights_from exclude each other")
+    if (args.class_weights is not None or args.class_weights_from is not None) and not args.ce:
+        ap.error("--class_weights and --class_weights_from need --ce")
+    ce_kw = {}
+    if args.ce:
+        try:
+            if args.class_weights is not None:
+                ce_kw = dict(class_weights=check_class_weights(args.class_weights), class_weights_source="arguments")
+            elif args.class_weights_from is not None:
+                ce_kw = dict(class_weights=class_weights_from(args.class_weights_from),
+                             class_weights_source=args.class_weights_from)
+        except (OSError, ValueError) as e:
+            ap.error(str(e))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, raw, module="neuralbarkcalculator_amd.evaluate"))
     idx = None if "WORLD_SIZE" in os.environ else 0
     kw = dict(batch=args.batch, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
     if args.loss:
         kw["loss"] = True
+    if args.ce:
+        kw.update(ce=True, **ce_kw)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

@@ -17,11 +17,17 @@ device):
   objective of __main__.py:236-239.  ``FCNResNet50.lovasz_softmax`` computes one term per class on the device;
   ``lovasz_loss`` is the mean over the present classes (lovasz_losses.py:258-276).  Four trailing CSV columns
   (``LOSS_CSV_COLUMNS``), written with ``repr`` so that they carry every bit of the float64 values.
+* The cross-entropy family (``evaluate --ce``): ``FCNResNet50.pixel_cross_entropy`` sums each image's pixel entropies per
+  (target class, argmax class) cell on the device; from the nine float64 sums ``cross_entropy`` is ``F.cross_entropy`` (xloss,
+  lovasz_losses.py:246-251), ``weighted_cross_entropy`` is ``CustomWeightedCrossEntropy`` (utils.py:151-165: each pixel's
+  entropy times the class weight at ``max(argmax, target)``, mean over the pixels) for any weights, and ``mixed_loss`` is
+  ``MixedLoss`` (utils.py:185-192).  Two or three trailing CSV columns, written with ``repr``.
 * The percent columns: float32 ``count / (H W) * 100`` with ``'{:.5f}'`` (``__main__.py:392-398``), like
   ``predict.stats_row``; "Output" from the raw argmax, "Target" from the target.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Sequence
 
 import numpy as np
@@ -30,6 +36,9 @@ CLASS_NAMES = ["nothing", "bark", "node"]
 EVAL_CSV_HEADER = ["Name", "Type", "Split", "iou_nothing", "iou_bark", "iou_node", "iou_mean", "f1_nothing", "f1_bark",
                    "f1_node", "f1_mean", "Output Bark %", "Output Node %", "Target Bark %", "Target Node %"]   # __main__.py:307-311
 LOSS_CSV_COLUMNS = ["loss_nothing", "loss_bark", "loss_node", "lovasz_softmax"]   # evaluate --loss: after the 15 above
+CE_CSV_COLUMNS = ["cross_entropy", "weighted_cross_entropy"]                      # evaluate --ce: after those
+MIXED_CSV_COLUMN = "mixed_loss"                                                   # --ce and --loss together: the last one
+REFERENCE_CLASS_WEIGHTS = (0.4004, 2.0334, 93.1921)   # get_pos_weight(), utils.py:72-73: compute_pos_weight of its dataset, frozen
 SPLIT = "all"                     # the Split column: the tool has no train / valid / test split (__main__.py:375-377)
 
 
@@ -151,3 +160,69 @@ def summarize_loss(rows: Sequence[Sequence[str]], first: int) -> dict:
         per_class[name] = float(np.mean(vals)) if vals else None
     losses = [float(r[first + 3]) for r in rows]
     return {"mean_over_images": float(np.mean(losses)) if losses else None, "per_class_mean": per_class}
+
+
+def _ce_sums(sums) -> np.ndarray:
+    s = np.asarray(sums, dtype=np.float64)
+    if s.size != 9:
+        raise ValueError("sums must hold the 9 cells of one image")
+    return s.reshape(3, 3)
+
+
+def _fsum(values) -> float:
+    """``math.fsum``, and what IEEE addition gives where it refuses (an infinity beside a NaN or the other infinity)."""
+    values = [float(v) for v in values]
+    if all(math.isfinite(v) for v in values):
+        return math.fsum(values)
+    return float(np.sum(np.array(values, dtype=np.float64)))
+
+
+def cross_entropy(sums, pixels: int) -> float:
+    """``F.cross_entropy(logits, target)`` of one image from its cell sums (``FCNResNet50.pixel_cross_entropy``): the nine
+    sums added exactly, one division by the number of pixels."""
+    return _fsum(_ce_sums(sums).ravel()) / float(pixels)
+
+
+def weighted_cross_entropy(sums, pixels: int, weights) -> float:
+    """``CustomWeightedCrossEntropy(weights)`` (utils.py:151-165) of one image as a batch of one: the cell of target class a
+    and argmax class b carries the weight of class ``max(a, b)``.  ``0 * inf`` is NaN, as in torch."""
+    s = _ce_sums(sums)
+    w = [float(v) for v in weights]
+    if len(w) != 3:
+        raise ValueError("weights must hold one value per class")
+    with np.errstate(invalid="ignore"):
+        products = [float(np.float64(w[max(a, b)]) * s[a, b]) for a in range(3) for b in range(3)]
+    return _fsum(products) / float(pixels)
+
+
+def mixed_loss(weighted: float, lovasz: float) -> float:
+    """``MixedLoss`` (utils.py:185-192): the weighted cross-entropy over four plus the Lovasz-Softmax loss."""
+    return float(weighted) / 4 + float(lovasz)
+
+
+def ce_cells(sums, pixels: int, weights, lovasz: float = None) -> List[str]:
+    """The cross-entropy cells of one CSV row (``repr``: every bit); with ``lovasz`` (the image's Lovasz-Softmax loss) the
+    mixed loss as well."""
+    wce = weighted_cross_entropy(sums, pixels, weights)
+    cells = [repr(cross_entropy(sums, pixels)), repr(wce)]
+    if lovasz is not None:
+        cells.append(repr(mixed_loss(wce, lovasz)))
+    return cells
+
+
+def summarize_ce(rows: Sequence[Sequence[str]], first: int, sums_total, pixels_total, weights, weights_source: str,
+                 mixed: bool = False) -> dict:
+    """The summary's ``"cross_entropy"`` entry: the means of the CSV cells (columns from ``first``), and the same formulas on
+    the cell sums and pixel counts added over every evaluated image (``pooled``), with the totals themselves so that a
+    reader can re-weight the folder.  ``mixed``: the rows carry the mixed loss as well (it has no pooled value:
+    the Lovasz-Softmax loss does not pool)."""
+    names = CE_CSV_COLUMNS + ([MIXED_CSV_COLUMN] if mixed else [])
+    mean = {name: (float(np.mean([float(r[first + k]) for r in rows])) if rows else None) for k, name in enumerate(names)}
+    total = _ce_sums(sums_total)
+    pixels = np.asarray(pixels_total, dtype=np.int64).reshape(3, 3)
+    p = int(pixels.sum())
+    pooled = {}
+    if p:
+        pooled = {"cross_entropy": cross_entropy(total, p), "weighted_cross_entropy": weighted_cross_entropy(total, p, weights)}
+    return {"class_weights": [float(v) for v in weights], "class_weights_source": weights_source, "mean_over_images": mean,
+            "pooled": pooled, "sums": total.tolist(), "pixels": pixels.tolist()}

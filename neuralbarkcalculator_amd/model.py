@@ -149,6 +149,7 @@ class FCNResNet50:
         self._affine_dev: Optional[torch.Tensor] = None
         self._ctx = C.c_void_p()
         self._lovasz_ws: Optional[torch.Tensor] = None     # nbc_lovasz_softmax's workspace (grows, never shrinks)
+        self._pixel_ce_ws: Optional[torch.Tensor] = None   # nbc_pixel_cross_entropy's, likewise
         self.device: Optional[torch.device] = None
         self.training = False
 
@@ -341,6 +342,38 @@ class FCNResNet50:
                                                     self._lovasz_ws.numel(), terms.data_ptr(), fg_counts.data_ptr(),
                                                     cur.cuda_stream), "nbc_lovasz_softmax")
         return terms, fg_counts
+
+    def pixel_cross_entropy(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per-image cross-entropy sums on the device (nbc_pixel_cross_entropy): what ``CustomWeightedCrossEntropy``
+        (utils.py:151-165), the plain cross-entropy and ``MixedLoss`` (utils.py:185-192) need from the pixels, for each image
+        as a batch of one.  ``logits_full`` and ``target`` as ``lovasz_softmax`` takes them.  Runs on the current stream; the
+        workspace is cached on this object and only grows.  Returns ``(sums f64 [N,3,3], counts int64 [N,3,3])``:
+        ``sums[n, t, p]`` = the sum of ``logsumexp(x) - x[t]`` over the pixels of target class t whose argmax is p,
+        ``counts[n, t, p]`` their number (the raw ``confusion`` of the same forward).  ``metrics.cross_entropy``,
+        ``weighted_cross_entropy`` and ``mixed_loss`` turn them into the losses, for any class weights."""
+        self._require_ctx()
+        if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
+                or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES:
+            raise ValueError("logits_full must be a contiguous float32 [N,3,H,W] tensor on %s" % (self.device,))
+        n, _, h, w = (int(v) for v in logits_full.shape)
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous() \
+                or tuple(target.shape) != (n, h, w) or target.numel() == 0:
+            raise ValueError("target must be a contiguous uint8 [%d,%d,%d] tensor on %s" % (n, h, w, self.device))
+        need = int(self._lib.nbc_pixel_ce_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_pixel_cross_entropy refuses a [%d,3,%d,%d] batch (N <= 65535, H * W < 2^31)" % (n, h, w))
+        if self._pixel_ce_ws is None or self._pixel_ce_ws.numel() < need:
+            self._pixel_ce_ws = None
+            self._pixel_ce_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        sums = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.float64, device=self.device)
+        counts = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            self._pixel_ce_ws.record_stream(cur)
+            _lib.check(self._lib.nbc_pixel_cross_entropy(logits_full.data_ptr(), target.data_ptr(), n, h, w,
+                                                         self._pixel_ce_ws.data_ptr(), self._pixel_ce_ws.numel(), sums.data_ptr(),
+                                                         counts.data_ptr(), cur.cuda_stream), "nbc_pixel_cross_entropy")
+        return sums, counts
 
     def resize_cubic_u8(self, image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """The resize of the reference's preprocessor (models.py:191-198) on the device: uint8 RGB
@@ -650,6 +683,7 @@ class FCNResNet50:
             self._ctx = C.c_void_p()
         self._blob_dev = None
         self._lovasz_ws = None
+        self._pixel_ce_ws = None
 
     def __del__(self):
         try:
