@@ -22,7 +22,8 @@
  * allocation in steady state).  Work is enqueued on the caller's stream; outputs are valid
  * once that stream has been synchronised.
  *
- * Eval-mode only: BatchNorm uses running statistics, Dropout is the identity.
+ * Eval mode by default: BatchNorm uses running statistics, Dropout is the identity.  The shipped tool's
+ * per-image BatchNorm statistics and its live Dropout are opt-in: nbc_set_bn_statistics, nbc_dropout_draws.
  */
 #ifndef NBC_H
 #define NBC_H
@@ -123,7 +124,7 @@ enum {
                            True) on a batch of one, what the shipped tool's forward does (models.py:212-250 never calls .eval()
                            and feeds one image at a time).  Running statistics are read by nothing and updated by nothing;
                            Dropout stays the identity (its expectation: live Dropout noise is what remains different from the
-                           shipped tool).  NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50 only. */
+                           shipped tool; nbc_dropout_draws samples it).  NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50 only. */
 };
 
 /* Layout of the image handed to nbc_forward. */
@@ -413,6 +414,58 @@ size_t nbc_pixel_ce_workspace_bytes(int N, int H, int W);
 int nbc_pixel_cross_entropy(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
                             void* workspace_dev, size_t workspace_bytes, double* sums_dev, int64_t* counts_dev,
                             void* hip_stream);
+
+/* ---- the shipped tool's live Dropout --------------------------------------------------------
+ * FCNHead's Dropout(0.1) (models.py:113-124) sits behind the 3x3 head convolution and in front of classifier.4, and the
+ * shipped predict.py never calls .eval(): every number it wrote is one random draw of that mask.  torch's CPU random stream
+ * is not reproduced; these calls sample the SAME distribution with a generator of the library's own, so that the spread
+ * the shipped tool puts on a number can be measured.  The definition of a draw:
+ *
+ * For image n of the batch with 64-bit identity id, 64-bit seed S, draw number d >= 0 and probability p in [0, 1):
+ *   X        the stored input of classifier.4 as the last nbc_forward left it: [h*w][512] per image, post-BatchNorm and
+ *            post-ReLU (in NBC_BN_PER_IMAGE the in-place "<bn>.apply" has run on it)
+ *   e        element index pixel * 512 + c, pixel = y * w + x; quad q = e >> 2, lane e & 3; h * w * 128 < 2^32
+ *   r        Philox4x32-10(counter = (q, d, id & 0xffffffff, id >> 32), key = (S & 0xffffffff, S >> 32))[lane]
+ *            (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds; counter and key
+ *            all zero give 6627e8d5 e169c58d bc57ac4c 9b00dbd8)
+ *   keep     r >= T, T = floor(p * 2^32) evaluated in double (p = 0.1: T = 429496729)
+ *   m        float32(1) / float32(1.0 - p): what nn.Dropout multiplies a kept element by
+ *   logits_d[k][pixel] = bias[k] + sum_c w[k][c] * (X[pixel][c] * (m * keep)), through the weights and in the summation
+ *            order of the forward's classifier.4 launch (lane l owns channels 8l .. 8l+7, an f32 fma chain, a 64-lane xor
+ *            tree, then the bias): with p = 0 a draw is BITWISE the forward's low-resolution logits.  A logit that is not
+ *            finite raises the context's sticky word (nbc_nonfinite_seen).
+ * then, as the forward and the folder driver do: bicubic upsample + argmax, remove_small_zones(min_pixels) unless 0, the
+ * optional 2 -> 1 remap, per-class pixel counts.  A draw of an image depends on (X, id, S, d, p) alone: not on the batch
+ * it runs in, its place in it, the stream, the context, or how many draws share a pass. */
+
+/* Host only, no context, no device: keep_host[i] = 1 when element first_element + i of draw `draw` is kept, else 0
+ * (count flags).  NBC_ERR_INVALID: p outside [0, 1), draw < 0, a null keep_host with count > 0, elements beyond 2^34. */
+int nbc_dropout_mask(uint64_t seed, uint64_t image_id, int draw, double p, uint64_t first_element, size_t count,
+                     uint8_t* keep_host);
+/* Bytes of device workspace that let nbc_dropout_draws run draws_per_pass draws of an [N,3,H,W] forward in one pass.
+ * With (h, w) = nbc_lowres_size(H, W), I = draws_per_pass * N and A(x) = x rounded up to a multiple of 256:
+ *   A(12 I h w) + A(I H W) + 2 A(4 I H W) + A(I H W)
+ * (low-resolution logits, uint8 labels, and remove_small_zones' parent / size ints and background bytes).  0 for what
+ * nbc_dropout_draws refuses: N < 1, H or W < 8, draws_per_pass < 1, I > 65535, H > 65535, H * W >= 2^31, h * w >= 2^25. */
+size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass);
+/* Draws first_draw .. first_draw + draws - 1 of every image of the context's last forward.
+ * image_ids_host     HOST memory, N identities (read before the call returns)
+ * logits_lowres_dev  nullable, float32 [draws][N][3][h][w]
+ * counts_dev         int64 [draws][N][3]: pixels per class of each draw's final labels; overwritten
+ * min_pixels         remove_small_zones' threshold (the reference: 150), 0 = none;  exclude_nodes: the 2 -> 1 remap
+ * workspace_dev      256-byte aligned device memory, at least nbc_dropout_workspace_bytes(N, H, W, 1); contents scratch.  As
+ *                    many draws share a pass (one read of X, the draws stacked as images on the upsample and
+ *                    remove_small_zones launchers) as it has room for; results do not depend on that number.
+ * Enqueues on hip_stream -- the stream of the forward, or one ordered behind it -- and does not synchronise; the context's
+ * activations are read, nothing of the context is written but the sticky non-finite word.
+ * NBC_ERR_INVALID: p outside [0, 1), draws < 1 or > 1024, first_draw < 0 or first_draw + draws > 2^31 - 1, min_pixels < 0,
+ * a null context, identity, count or workspace pointer, a misaligned workspace or one too small for one draw per pass.
+ * NBC_ERR_STATE: unless the context's last forward was an NBC_ARCH_FCN_RESNET50 forward of exactly this (N, H, W) and
+ * nothing has touched its plan since (nbc_reserve of another shape, nbc_autotune, keep mode, BatchNorm mode, new weights).
+ * Both BatchNorm modes and all three precisions are served. */
+int nbc_dropout_draws(nbc_ctx* ctx, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed,
+                      int first_draw, int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev,
+                      int64_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
 
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',

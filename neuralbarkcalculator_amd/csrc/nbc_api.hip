@@ -18,6 +18,7 @@
 #include "nbc_kernels.hpp"
 #include "nbc_net.hpp"
 #include "nbc_plan.hpp"
+#include "philox.hpp"
 
 using namespace nbc;
 
@@ -67,6 +68,10 @@ struct nbc_ctx {
   float* bn_unit = nullptr;                 // device: 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
   void* bn_ws = nullptr;                    // per-image BatchNorm workspace (Plan::bn_ws_bytes)
   size_t bn_ws_cap = 0;
+  // the (N, H, W) of the last completed nbc_forward while its activations and plan stand untouched (nbc_dropout_draws reads
+  // the stored input of classifier.4): cleared by whatever parks the plan, retunes it or attaches other weights
+  bool fwd_valid = false;
+  int fwd_N = 0, fwd_H = 0, fwd_W = 0;
 };
 
 namespace {
@@ -83,6 +88,7 @@ PlanKey plan_key(const nbc_ctx* c, int N, int H, int W) {
 // its launch list and its measured tile choice instead of being rebuilt on every change).
 void stash_plan(nbc_ctx* c) {
   Plan& cur = c->plan;
+  c->fwd_valid = false;
   if (cur.N == 0) return;
   for (Plan& p : c->plan_cache)
     if (same_shape(p, cur)) {
@@ -297,6 +303,7 @@ int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int 
   if (is_effnet(arch)) std::fill(c->act_exp.begin(), c->act_exp.end(), 0);
   c->weights = static_cast<const unsigned char*>(dev_blob);
   c->layout = L;
+  c->fwd_valid = false;
   if (c->precision != precision || c->arch != arch) stash_plan(c);      // element size or network changed: another plan
   c->precision = precision;
   c->arch = arch;
@@ -545,6 +552,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   if (!c->weights) return set_error(NBC_ERR_STATE, "nbc_forward: no weights attached (load_state_dict first)");
   if (x_dtype != NBC_IN_F32_NCHW && x_dtype != NBC_IN_U8_NHWC) return set_error(NBC_ERR_INVALID, "nbc_forward: bad x_dtype");
   if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_forward: bad labels_dtype");
+  c->fwd_valid = false;
   int rc = nbc_reserve(c, N, H, W);
   if (rc != NBC_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -691,6 +699,8 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
     if (evs) NBC_HIP(hipEventRecord((*evs)[l + 1], s));
   }
   if (evs) ++c->prof_used;
+  c->fwd_valid = true;
+  c->fwd_N = N; c->fwd_H = H; c->fwd_W = W;
   return NBC_OK;
 }
 
@@ -739,6 +749,7 @@ int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W
   int rc = nbc_forward(c, x_dev, x_dtype, N, H, W, nullptr, nullptr, nullptr, NBC_LABEL_U8, nullptr, 0, hip_stream);
   if (rc != NBC_OK) return rc;
   NBC_HIP(hipStreamSynchronize(s));
+  c->fwd_valid = false;                    // the timed launches below rewrite activations (raw ones in NBC_BN_PER_IMAGE)
   hipEvent_t e0, e1;
   NBC_HIP(hipEventCreate(&e0));
   NBC_HIP(hipEventCreate(&e1));
@@ -844,6 +855,80 @@ int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N
   NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, exclude_nodes, bg,
                                     parent, size, reinterpret_cast<unsigned long long*>(counts_dev),
                                     static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
+}
+
+size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
+  if (N < 1 || H < 8 || W < 8 || H > 65535 || draws_per_pass < 1 || (long long)H * W > 0x7fffffffLL) return 0;
+  const unsigned long long I = (unsigned long long)draws_per_pass * (unsigned long long)N;
+  if (I > 65535ull) return 0;
+  int h = 0, w = 0;
+  if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1 || (unsigned long long)h * w >= (1ull << 25)) return 0;
+  const auto A = [](unsigned long long x) { return (x + 255ull) & ~255ull; };
+  const unsigned long long px = I * (unsigned long long)H * W;
+  return (size_t)(A(12ull * I * h * w) + A(px) + 2 * A(4 * px) + A(px));
+}
+
+int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
+                      int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev, int64_t* counts_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+  if (!dropout_p_ok(p)) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: p must lie in [0, 1)");
+  if (draws < 1 || draws > 1024) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: draws must lie in 1..1024");
+  if (first_draw < 0 || first_draw > 0x7fffffff - draws)
+    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: first_draw must not be negative (and first_draw + draws < 2^31)");
+  if (min_pixels < 0) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: min_pixels must not be negative");
+  if (!c || !image_ids_host || !counts_dev || !workspace_dev) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: null argument");
+  if (c->arch != kArchFcn)
+    return set_error(NBC_ERR_STATE, std::string("nbc_dropout_draws: NBC_ARCH_FCN_RESNET50 only, the context holds ") +
+                                        arch_name(c->arch) + " (DeepLabHead's Dropout sits inside ASPP; the EfficientNet heads are "
+                                        "left out)");
+  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
+    return set_error(NBC_ERR_STATE, "nbc_dropout_draws: the context's last forward was not one of this (N, H, W), or its plan has "
+                                    "been touched since: run nbc_forward first");
+  const size_t one = nbc_dropout_workspace_bytes(N, H, W, 1);
+  if (one == 0) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: shape beyond the limits (N <= 65535, H * W < 2^31, h * w < 2^25)");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) % 256 != 0)
+    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: the workspace must be 256-byte aligned");
+  if (workspace_bytes < one)
+    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: the workspace is smaller than nbc_dropout_workspace_bytes(N, H, W, 1)");
+  const Plan& P = c->plan;
+  const Op* head = nullptr;
+  for (const Op& o : P.ops)
+    if (o.kind == OP_HEAD1X1) head = &o;
+  if (!head || head->Ci != 512 || head->in_buf < 0 || !c->nonfinite)
+    return set_error(NBC_ERR_STATE, "nbc_dropout_draws: the plan holds no classifier.4 of 512 input channels");
+  int pass = std::min(draws, 65535 / N);
+  while (pass > 1 && nbc_dropout_workspace_bytes(N, H, W, pass) > workspace_bytes) --pass;
+  NBC_HIP(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const UnitPtrs up = unit_ptrs(c, head->unit);
+  const int hw = P.h * P.w;
+  const auto A = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const uint32_t T = dropout_threshold(p);
+  const float m = dropout_scale(p);
+  for (int d0 = 0; d0 < draws; d0 += pass) {
+    const int D = std::min(pass, draws - d0);
+    const int I = D * N;
+    const size_t px = (size_t)I * H * W;
+    // the pass's slice of the workspace, sized for THIS pass (the last one may be shorter)
+    unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws);
+    ws += A((size_t)12 * I * hw);
+    unsigned char* labels = ws; ws += A(px);
+    int* parent = reinterpret_cast<int*>(ws); ws += A(4 * px);
+    int* size = reinterpret_cast<int*>(ws); ws += A(4 * px);
+    unsigned char* bg = ws;
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
+    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf], up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
+                                   first_draw + d0, D, c->nonfinite, s));
+    if (min_pixels > 0) {
+      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, nullptr, 0, s));
+      NBC_HIP(launch_remove_small_zones(labels, 0, I, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s));
+    } else {
+      NBC_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * kNumClasses * I, s));
+      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, counts, exclude_nodes, s));
+    }
+  }
   return NBC_OK;
 }
 

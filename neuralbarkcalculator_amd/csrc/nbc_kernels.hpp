@@ -67,6 +67,17 @@ hipError_t launch_head1x1(const void* x, const float* w, const float* bias, floa
 // classifier.4 of DeepLabHead: the same with 256 input channels
 hipError_t launch_head1x1_c256(const void* x, const float* w, const float* bias, float* y, int N, int hw,
                                int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
+// classifier.4 of FCNHead behind a live Dropout (dropout_head.hip; the definition: include/nbc.h, nbc_dropout_draws): the
+// low-resolution logits y [draws][N][3][hw] of draws first_draw .. first_draw + draws - 1 from one read of x [N][hw][512]
+// stored elements.  ids_host: the N image identities, HOST memory, handed to the kernel by value (64 per launch: no copy,
+// no synchronisation).  threshold / keep_scale: dropout_threshold(p) / dropout_scale(p) of philox.hpp.  hw * 128 < 2^32.
+constexpr int kDropoutIdsPerLaunch = 64;
+struct DropoutIds {
+  unsigned long long id[kDropoutIdsPerLaunch];
+};
+hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bias, float* y, int N, int hw, int precision,
+                                  const uint64_t* ids_host, uint64_t seed, uint32_t threshold, float keep_scale, int first_draw,
+                                  int draws, unsigned* nonfinite, hipStream_t s);
 // ASPP pooling branch (aspp.hip), per image: mean over hw pixels of x [N][hw][cin = 2048] (stored elements), the 1x1 conv
 // with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout] elements.  Workspaces: partial
 // N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.

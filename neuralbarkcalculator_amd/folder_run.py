@@ -211,6 +211,144 @@ def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
                          "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
 
 
+# ---- the shipped tool's live Dropout (--dropout_draws): identities, argument checks, the report -----------------------
+DROPOUT_MAX_DRAWS = 1024
+DROPOUT_COLUMNS = ["Name", "Type", "Output Bark %", "Output Node %", "bark_mean", "bark_std", "bark_min", "bark_max",
+                   "node_mean", "node_std", "node_min", "node_max", "draws"]
+DROPOUT_COMPARE_COLUMNS = ["old_bark", "old_node", "bark_inside", "node_inside", "bark_z", "node_z"]
+
+
+def image_id(wood: str, name: str) -> int:
+    """The 64-bit identity of a folder image for ``FCNResNet50.dropout_draws``: FNV-1a-64 (offset 0xcbf29ce484222325, prime
+    0x100000001b3) of the UTF-8 bytes of ``wood + "/" + name``.  An image's draws therefore depend neither on what else is in
+    the folder, nor on batch, streams or ranks."""
+    h = 0xcbf29ce484222325
+    for b in (wood + "/" + name).encode("utf-8"):
+        h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
+    return h
+
+
+def check_dropout_arguments(draws, p=None, seed=None, compare=None, arch: str = "auto", only_preprocess: bool = False) -> None:
+    """``ValueError`` for what ``--dropout_draws`` and its companions refuse before any device is touched.  ``draws``: None =
+    the flag is off, and then ``p``, ``seed`` and ``compare`` must be None too.  On: ``draws`` in 1..1024, ``p`` in [0, 1),
+    ``seed`` an unsigned 64-bit integer, a named ``arch`` fcn_resnet50 (``check_dropout_arch`` once ``"auto"`` is resolved),
+    and not ``only_preprocess``."""
+    if draws is None:
+        given = [n for n, v in (("--dropout_p", p), ("--dropout_seed", seed), ("--dropout_compare", compare)) if v is not None]
+        if given:
+            raise ValueError("%s needs --dropout_draws" % ", ".join(given))
+        return
+    if not 1 <= int(draws) <= DROPOUT_MAX_DRAWS:
+        raise ValueError("--dropout_draws must lie in 1..%d, got %r" % (DROPOUT_MAX_DRAWS, draws))
+    if p is not None and not (0.0 <= float(p) < 1.0):
+        raise ValueError("--dropout_p must lie in [0, 1), got %r" % (p,))
+    if seed is not None and not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("--dropout_seed must be an unsigned 64-bit integer, got %r" % (seed,))
+    if only_preprocess:
+        raise ValueError("--dropout_draws runs the network: it cannot go with --only_preprocess")
+    if arch != "auto":
+        check_dropout_arch(arch)
+
+
+def check_dropout_arch(arch: str) -> None:
+    """``ValueError`` for ``--dropout_draws`` on a network other than FCN-ResNet-50 (every rank holds the resolved architecture
+    alike, so every rank refuses alike)."""
+    from . import topology
+    if topology.is_efficientnet(arch):
+        raise ValueError("--dropout_draws is refused for %s: EfficientNet's FCN head is left out" % arch)
+    if arch != "fcn_resnet50":
+        raise ValueError("--dropout_draws is refused for %s: DeepLabHead's Dropout sits inside ASPP" % arch)
+
+
+def percent_string(count: int, pixels: int) -> str:
+    """A class percentage as ``final_stats.csv`` prints it: float32 arithmetic and '{:.5f}' (models.py:321-332)."""
+    return "{:.5f}".format(float(np.float32(count) / np.float32(pixels) * np.float32(100)))
+
+
+def draw_statistics(counts: Sequence[int], pixels: int) -> dict:
+    """mean, unbiased std (None for one draw), min and max of the percentages ``100 * count / pixels`` of one class over the
+    draws, from the integer counts: sums and the variance's numerator are exact integers, each figure one correctly rounded
+    division (and one square root) away from them."""
+    import math
+    cs = [int(c) for c in counts]
+    d, s1, s2 = len(cs), sum(cs), sum(c * c for c in cs)
+    out = {"mean": (100 * s1) / (d * pixels), "min": (100 * min(cs)) / pixels, "max": (100 * max(cs)) / pixels, "std": None}
+    if d > 1:
+        out["std"] = math.sqrt((10000 * (d * s2 - s1 * s1)) / (d * (d - 1) * pixels * pixels))
+    return out
+
+
+def read_shipped_stats(path: str) -> dict:
+    """``{(name, type): (bark %, node %)}`` of a ``final_stats.csv`` as the shipped tool writes it: tab separated, seven header
+    names over SIX columns per row (models.py:252-255 against :321-332), so rows are read by position -- name, type, bark %
+    at 2, node % at 4.  ``ValueError`` for a file that cannot be read that way."""
+    import csv
+    old = {}
+    try:
+        with open(path, newline="") as f:
+            for i, row in enumerate(csv.reader(f, delimiter="\t")):
+                if i == 0 or not row:
+                    continue
+                if len(row) < 5:
+                    raise ValueError("row %d has %d columns, not the six of the shipped tool" % (i + 1, len(row)))
+                old[(row[0], row[1])] = (float(row[2]), float(row[4]))
+    except OSError as e:
+        raise ValueError("--dropout_compare %s: %s" % (path, e))
+    except ValueError as e:
+        raise ValueError("--dropout_compare %s: %s" % (path, e))
+    return old
+
+
+def dropout_report(images: Sequence[tuple], draws: int, old: dict = None):
+    """The rows of ``dropout_stats.csv`` (header first) and the folder summary.  ``images``: per image
+    ``(name, wood, h, w, count_1, count_2, draw_counts)`` with the deterministic forward's bark / node pixels and
+    ``draw_counts`` int ``[draws][3]``.  Figures are formatted '{:.5f}'; the std is empty for one draw.  ``old``
+    (``read_shipped_stats``): adds the old file's two percentages, whether each lies within [min, max] of the draws -- the
+    bounds taken as the shipped tool prints them (``percent_string`` of the extreme counts), since the old value went through
+    that rounding -- and its z score (empty when the std is 0 or absent, or the image is missing from the old file)."""
+    fmt = lambda v: "" if v is None else "{:.5f}".format(v)
+    header = list(DROPOUT_COLUMNS) + (list(DROPOUT_COMPARE_COLUMNS) if old is not None else [])
+    rows, sums, nstd = [header], {}, 0
+    inside = {"bark": 0, "node": 0}
+    missing, compared = [], 0
+    for name, wood, h, w, c1, c2, dc in images:
+        px = h * w
+        dc = [[int(v) for v in d3] for d3 in dc]
+        assert len(dc) == draws
+        st = {"bark": draw_statistics([d3[1] for d3 in dc], px), "node": draw_statistics([d3[2] for d3 in dc], px)}
+        row = [name, wood, percent_string(c1, px), percent_string(c2, px)]
+        for cls in ("bark", "node"):
+            row += [fmt(st[cls][k]) for k in ("mean", "std", "min", "max")]
+            for k in ("mean", "std", "min", "max"):
+                if st[cls][k] is not None:
+                    sums[cls + "_" + k] = sums.get(cls + "_" + k, 0.0) + st[cls][k]
+        row.append(str(draws))
+        if old is not None:
+            o = old.get((name, wood))
+            if o is None:
+                missing.append("%s/%s" % (wood, name))
+                row += [""] * len(DROPOUT_COMPARE_COLUMNS)
+            else:
+                compared += 1
+                ins, zs = [], []
+                for cls, col, v in (("bark", 1, o[0]), ("node", 2, o[1])):
+                    lo = float(percent_string(min(d3[col] for d3 in dc), px))
+                    hi = float(percent_string(max(d3[col] for d3 in dc), px))
+                    ok = lo <= v <= hi
+                    inside[cls] += int(ok)
+                    ins.append("1" if ok else "0")
+                    zs.append(fmt((v - st[cls]["mean"]) / st[cls]["std"]) if st[cls]["std"] else "")
+                row += [fmt(o[0]), fmt(o[1])] + ins + zs
+        rows.append(row)
+    n = len(images)
+    summary = {"draws": draws, "images": n,
+               "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}}
+    if old is not None:
+        summary["compare"] = {"images_compared": compared, "bark_inside": inside["bark"], "node_inside": inside["node"],
+                              "missing_from_old": missing}
+    return rows, summary
+
+
 def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
              target_size: int = 1024) -> SimpleNamespace:
     """The rank context of one folder run, and the state its later steps fill in.  An already initialised process group (gloo
@@ -534,6 +672,17 @@ def add_shared_arguments(ap) -> None:
     ap.add_argument("--stats", metavar="PATH", default=None,
                     help="take mean and std from this JSON (results/dataset_stats.json of python -m neuralbarkcalculator_amd.stats) "
                          "instead of --mean / --std")
+
+
+def add_dropout_arguments(ap) -> None:
+    """``--dropout_draws`` and its companions (the predict driver)."""
+    ap.add_argument("--dropout_draws", type=int, default=None, metavar="D",
+                    help="also sample D random draws (1..1024) of the live Dropout the shipped tool ran with, per image, and write "
+                         "results/dropout_stats.csv and dropout_summary.json (fcn_resnet50 only)")
+    ap.add_argument("--dropout_p", type=float, default=None, help="the Dropout probability (default 0.1, FCNHead's)")
+    ap.add_argument("--dropout_seed", type=int, default=None, help="64-bit seed of the draws (default 0)")
+    ap.add_argument("--dropout_compare", metavar="OLD_final_stats.csv", default=None,
+                    help="a final_stats.csv of the shipped tool: report where its numbers lie within the draws")
 
 
 def resolve_normalization(mean=None, std=None, stats: str = None):

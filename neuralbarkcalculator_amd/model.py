@@ -128,7 +128,7 @@ class FCNResNet50:
     bn_statistics (``set_bn_statistics``): ``"running"`` (default) -- eval mode, BatchNorm on the running statistics;
     ``"image"`` -- every BatchNorm normalises each image by its own per-channel mean and biased variance, as the shipped
     tool's forward does (it never calls ``.eval()`` and feeds one image at a time); "fp32" only.  Dropout is the identity
-    in both (live Dropout noise is all that stays different from the shipped tool).
+    in both (live Dropout noise is all that stays different from the shipped tool; ``dropout_draws`` samples it).
     """
 
     ARCH = "fcn_resnet50"                  # topology.ARCHS entry (NBC_ARCH_*) of the network this class runs
@@ -150,6 +150,8 @@ class FCNResNet50:
         self._ctx = C.c_void_p()
         self._lovasz_ws: Optional[torch.Tensor] = None     # nbc_lovasz_softmax's workspace (grows, never shrinks)
         self._pixel_ce_ws: Optional[torch.Tensor] = None   # nbc_pixel_cross_entropy's, likewise
+        self._dropout_ws: Optional[torch.Tensor] = None    # nbc_dropout_draws', likewise
+        self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self.device: Optional[torch.device] = None
         self.training = False
 
@@ -374,6 +376,69 @@ class FCNResNet50:
                                                          self._pixel_ce_ws.data_ptr(), self._pixel_ce_ws.numel(), sums.data_ptr(),
                                                          counts.data_ptr(), cur.cuda_stream), "nbc_pixel_cross_entropy")
         return sums, counts
+
+    def dropout_draws(self, draws: int, image_ids, p: float = 0.1, seed: int = 0, first_draw: int = 0,
+                      small_zones: bool = True, exclude_nodes: bool = False, return_lowres: bool = False, *,
+                      min_pixels: int = 150, draws_per_pass: int = 8):
+        """Random draws of the shipped tool's live ``Dropout(p)`` (``FCNHead``, models.py:113-124; its predict.py never calls
+        ``.eval()``) on the images of the LAST forward of this object (``predict_labels`` / ``lowres_logits`` / ``__call__``),
+        on the current stream (nbc_dropout_draws; the definition of a draw: include/nbc.h).  The trunk and the
+        head convolution are not run again: each draw is a masked ``classifier.4`` on the stored features, the bicubic upsample
+        + argmax, ``remove_small_zones`` (``small_zones``, threshold ``min_pixels``) and the ``exclude_nodes`` remap.
+        ``image_ids``: one 64-bit identity per image of that forward (``folder_run.image_id``); an image's draws depend on its
+        features, its identity, ``seed``, the draw number (``first_draw`` + 0 .. ``draws`` - 1) and ``p`` alone -- not on its
+        batch, the stream, the object (``clone_shared``) or ``draws_per_pass`` (how many draws share one read of the features;
+        it sizes the workspace cached on this object).  ``p = 0`` gives the forward's own logits bit for bit.
+        Returns int64 ``[draws, N, 3]`` pixels per class (+ f32 ``[draws, N, 3, h, w]`` low-resolution logits with
+        ``return_lowres``).  ``ValueError``: another network than fcn_resnet50, ``draws`` outside 1..1024, ``p`` outside
+        [0, 1), a negative ``first_draw``, an id count other than the last forward's batch."""
+        if topology.is_efficientnet(self.ARCH):
+            raise ValueError("dropout draws are refused for %s: EfficientNet's FCN head is left out (its Dropout is not "
+                             "implemented)" % self.ARCH)
+        if self.ARCH != "fcn_resnet50":
+            raise ValueError("dropout draws are refused for %s: DeepLabHead's Dropout sits inside ASPP, in front of convolutions "
+                             "that would have to run again for every draw" % self.ARCH)
+        draws, first_draw, seed = int(draws), int(first_draw), int(seed)
+        if not 1 <= draws <= 1024:
+            raise ValueError("draws must lie in 1..1024, got %d" % draws)
+        if not (0.0 <= float(p) < 1.0):
+            raise ValueError("p must lie in [0, 1), got %r" % (p,))
+        if first_draw < 0 or first_draw + draws > 2 ** 31 - 1:
+            raise ValueError("first_draw must not be negative, got %d" % first_draw)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an unsigned 64-bit integer, got %d" % seed)
+        if int(min_pixels) < 0 or int(draws_per_pass) < 1:
+            raise ValueError("min_pixels must not be negative and draws_per_pass must be positive")
+        self._require_weights()
+        if self._last_shape is None:
+            raise RuntimeError("dropout_draws follows a forward (predict_labels / lowres_logits) of this object: none has run")
+        n, h, w = self._last_shape
+        ids = [int(v) for v in image_ids]
+        if len(ids) != n or any(not 0 <= v < 2 ** 64 for v in ids):
+            raise ValueError("image_ids must hold one unsigned 64-bit identity per image of the last forward (%d), got %d"
+                             % (n, len(ids)))
+        ids_arr = (C.c_uint64 * n)(*ids)
+        per_pass = max(1, min(draws, int(draws_per_pass), 65535 // n))
+        need = int(self._lib.nbc_dropout_workspace_bytes(n, h, w, per_pass))
+        if need == 0:
+            raise ValueError("nbc_dropout_draws refuses a [%d,3,%d,%d] batch (draws x N <= 65535 per pass, H * W < 2^31)" % (n, h, w))
+        if self._dropout_ws is None or self._dropout_ws.numel() < need:
+            self._dropout_ws = None
+            self._dropout_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        counts = torch.empty((draws, n, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        lowres = None
+        if return_lowres:
+            lowres = torch.empty((draws, n, NUM_CLASSES) + out_hw(h, w, self.ARCH), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            self._dropout_ws.record_stream(cur)
+            # the workspace handed over is exactly what per_pass draws need: a larger cached one must not change the pass
+            rc = self._lib.nbc_dropout_draws(self._ctx, n, h, w, ids_arr, float(p), seed, first_draw, draws,
+                                             int(min_pixels) if small_zones else 0, int(bool(exclude_nodes)),
+                                             lowres.data_ptr() if lowres is not None else None, counts.data_ptr(),
+                                             self._dropout_ws.data_ptr(), need, cur.cuda_stream)
+        _lib.check(rc, "nbc_dropout_draws")
+        return (counts, lowres) if return_lowres else counts
 
     def resize_cubic_u8(self, image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """The resize of the reference's preprocessor (models.py:191-198) on the device: uint8 RGB
@@ -676,6 +741,7 @@ class FCNResNet50:
             rc = self._lib.nbc_forward(self._ctx, x.data_ptr(), x_dtype, n, h, w, ptr(lowres), ptr(logits_full),
                                        ptr(labels), ldt, ptr(counts), int(bool(exclude_nodes)), stream)
         _lib.check(rc, "nbc_forward")
+        self._last_shape = (n, h, w)
 
     def _destroy(self):
         if self._ctx:
@@ -684,6 +750,8 @@ class FCNResNet50:
         self._blob_dev = None
         self._lovasz_ws = None
         self._pixel_ce_ws = None
+        self._dropout_ws = None
+        self._last_shape = None
 
     def __del__(self):
         try:

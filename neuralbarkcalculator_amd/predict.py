@@ -307,6 +307,26 @@ def write_stats_csv(path: str, rows: Sequence[Sequence[str]]) -> None:
         csv.writer(f, delimiter="\t").writerows([CSV_HEADER] + [list(r) for r in rows])
 
 
+def write_dropout_report(results_dir: str, items, allrows, alld, draws: int, p: float, seed: int, precision: str, bn_stats: str,
+                         old_stats=None, compare_path: str = None) -> dict:
+    """``dropout_stats.csv`` (tab separated) and ``dropout_summary.json`` from the gathered rows: ``allrows`` as
+    ``final_stats.csv`` is written from, ``alld`` the ``(global_idx, D x 3 counts)`` rows of the draws.  Returns the summary."""
+    import json
+    by_idx = {int(g[0]): g[1:].reshape(draws, 3) for g in alld}
+    images = [(items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), int(g[3]), int(g[4]), by_idx[int(g[0])])
+              for g in allrows]
+    table, summary = folder_run.dropout_report(images, draws, old_stats)
+    with open(os.path.join(results_dir, "dropout_stats.csv"), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    summary = dict({"p": float(p), "seed": int(seed), "precision": precision, "bn_stats": bn_stats}, **summary)
+    if compare_path is not None:
+        summary["compare"]["file"] = os.path.basename(compare_path)
+    with open(os.path.join(results_dir, "dropout_summary.json"), "w") as f:
+        json.dump(summary, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return summary
+
+
 def label_png(labels: np.ndarray) -> np.ndarray:
     """models.py:349-353: uint8 map with Bark = 127, Node = 255."""
     out = np.zeros(labels.shape, dtype=np.uint8)
@@ -340,7 +360,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    exclude_nodes: bool = False, small_zones: bool = True, device_index: int = None,
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
-                   normalization=None) -> dict:
+                   normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
+                   dropout_compare: str = None) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -363,12 +384,24 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     ``precision_auto``: ``precision`` came from ``--precision auto``).  ``normalization``: the ``(mean, std)`` the frames are
     normalised with (``--mean`` / ``--std`` / ``--stats``, ``folder_run.resolve_normalization``), set on every stream's model
     object, the calibration guard's included; None: the defaults of models.py:208-209.
+    ``dropout_draws`` = D > 0 (fcn_resnet50 only): after each batch's forward, on its stream and model object, D draws of the
+    live ``Dropout(dropout_p)`` the shipped tool ran with (``FCNResNet50.dropout_draws`` under ``dropout_seed``, each image
+    under its ``folder_run.image_id``, with this run's ``small_zones`` and ``exclude_nodes``); their counts ride back beside
+    the labels and rank 0 writes ``results/dropout_stats.csv`` and ``results/dropout_summary.json``
+    (``folder_run.dropout_report``; ``dropout_compare``: a ``final_stats.csv`` of the shipped tool to place within the draws).
+    Everything else the run writes is byte for byte what it writes without the draws.
     Returns timing / count statistics of this rank."""
     import time
     import torch
     from PIL import Image
     from .model import FCNResNet50
     from .pngio import write_png
+    D = int(dropout_draws or 0)
+    old_stats = None
+    if D:                                            # refusals first: nothing has touched a device yet
+        folder_run.check_dropout_arguments(D, dropout_p, dropout_seed, dropout_compare, arch)
+        if dropout_compare is not None:
+            old_stats = folder_run.read_shipped_stats(dropout_compare)
     r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size)
     dev, batch, prof, clock = r.dev, r.batch, r.prof, time.perf_counter
     pre_model = FCNResNet50(precision).to(dev)      # its own context: the pool's device resizes never touch the predictor's
@@ -377,6 +410,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if small_zones:
             m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, generate_folders, warm, normalization=normalization)
+    if D:
+        folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
 
     items = plan_items(root)
 
@@ -387,6 +422,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     folder_run.shard(r, items, header_size)
     mine, pool = r.mine, r.pool
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
+    drows = np.zeros((len(mine), 1 + 3 * D), dtype=np.int64)     # (global_idx, D x 3 counts) of the Dropout draws
     resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
     lvl_proc, lvl_lab = _png_level("processed"), _png_level("labels")
 
@@ -414,7 +450,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2):
+    def finish(k, lab, c1, c2, draws=None):
         """Pool: label PNG (models.py:349-356) + the image's row."""
         d = items[mine[k]]
         t0 = clock()
@@ -422,12 +458,15 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         label_paths.append(path)
         write_png(path, label_png(lab), lvl_lab)
         rows[k] = (mine[k], lab.shape[0], lab.shape[1], c1, c2)
+        if draws is not None:
+            drows[k, 0], drows[k, 1:] = mine[k], draws.reshape(-1)
         prof["pool.write_labels"] += clock() - t0
 
     # the result ring, one slot per staging slot: labels + counts coming back (pinned once for the largest batch)
     full = batch * target_size * target_size
     ring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, 3), dtype=torch.int64).pin_memory())
             for _ in range(r.depth)]
+    dring = [torch.empty(D * batch * 3, dtype=torch.int64).pin_memory() for _ in range(r.depth)] if D else None
     tuned = set()
 
     def launch(slot, sid, part, x):
@@ -442,11 +481,21 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                                             small_zones=small_zones)   # models.py:269-276 on the device
         ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
         ring[slot][1][:n].copy_(counts, non_blocking=True)
+        if D:                                        # the draws read the features this forward left, on the same stream
+            if dring[slot].numel() < D * n * 3:
+                dring[slot] = torch.empty(D * n * 3, dtype=torch.int64).pin_memory()
+            ids = [folder_run.image_id(items[mine[k]]["wood"], items[mine[k]]["name"]) for k in part]
+            dcounts = mdl.dropout_draws(D, ids, p=dropout_p, seed=dropout_seed, small_zones=small_zones,
+                                        exclude_nodes=exclude_nodes)
+            dring[slot][: D * n * 3].copy_(dcounts.reshape(-1), non_blocking=True)
 
     def consume(slot, part, n, h, w):
         lab_host, cnt_host = ring[slot]
         labs = lab_host[: n * h * w].numpy().reshape(n, h, w).copy()
         cnts = cnt_host[:n].numpy().copy()
+        if D:
+            dc = dring[slot][: D * n * 3].numpy().reshape(D, n, 3).copy()
+            return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j]) for j, k in enumerate(part)]
         return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2])) for j, k in enumerate(part)]
 
     def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
@@ -466,6 +515,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         write_stats_csv(os.path.join(root, "results", "final_stats.csv"),
                         [stats_row(items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), int(g[3]), int(g[4]))
                          for g in allrows])
+    if D:
+        alld = folder_run.gather(r, drows, 1 + 3 * D)       # one more all_gather, as evaluate's --loss rows take
+        if r.rank == 0:
+            write_dropout_report(os.path.join(root, "results"), items, allrows, alld, D, dropout_p, dropout_seed, r.precision,
+                                 bn_stats, old_stats, dropout_compare)
     return dict(folder_run.finish(r), host_workers=r.workers, distinct_shapes=len(r.shape_count),
                 autotuned_shapes=len({k for _, k in tuned}))
 
@@ -481,9 +535,17 @@ def main(argv=None):
     ap.add_argument("--autotune", action="store_true",
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
     folder_run.add_shared_arguments(ap)
+    folder_run.add_dropout_arguments(ap)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
+    try:                                                 # refused as argument errors, before any device is touched
+        folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
+                                           args.only_preprocess)
+        if args.dropout_compare is not None:
+            folder_run.read_shipped_stats(args.dropout_compare)
+    except ValueError as e:
+        ap.error(str(e))
     if not args.device.startswith("cuda"):
         raise SystemExit("this package is the MI355X path; run the reference for --device=cpu")
     if args.only_preprocess:                             # predict.py:53-55: the resize runs on the device here too
@@ -497,6 +559,9 @@ def main(argv=None):
     if "WORLD_SIZE" not in os.environ and ":" in args.device:
         idx = int(args.device.split(":")[1])
     kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
+    if args.dropout_draws:
+        kw.update(dropout_draws=args.dropout_draws, dropout_p=0.1 if args.dropout_p is None else args.dropout_p,
+                  dropout_seed=args.dropout_seed or 0, dropout_compare=args.dropout_compare)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if int(os.environ.get("RANK", "0")) == 0:
