@@ -15,6 +15,7 @@
 // Bounds: (1) reads N * hw * 2048 elements and writes N * kPoolSlices * 2048 floats; (2) reads those; (3) reads 2 MiB of
 // weights per image (L2-resident after the first image); concat reads 5/4 x M x 256 x 4 elements' bytes and writes the same.
 #include "nbc_kernels.hpp"
+#include "reduce.hpp"
 #include "split16.hpp"
 
 namespace nbc {
@@ -103,8 +104,7 @@ __global__ __launch_bounds__(256) void aspp_pool_conv_kernel(const float* __rest
   float acc = 0.f;
 #pragma unroll 8
   for (int i = 0; i < kPoolCin / 64; ++i) acc = __builtin_fmaf(wr[lane + 64 * i], m[lane + 64 * i], acc);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum(acc);
   if (lane != 0) return;
   const float v = __builtin_fmaxf(__builtin_fmaf(acc, scale[o], shift[o]), 0.f);
   const size_t at = (size_t)img * cout + o;

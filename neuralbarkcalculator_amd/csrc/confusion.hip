@@ -1,21 +1,15 @@
 // Per-image 3x3 confusion counts of predicted labels against a grey target mask: what the evaluation loop of
-// /root/reference/src/bark_calculator/__main__.py:331-332 (lovasz `iou`, `PixelWiseF1`) counts on the host, pixel by
+// the reference's bark_calculator/__main__.py:331-332 (lovasz `iou`, `PixelWiseF1`) counts on the host, pixel by
 // pixel, before it divides.  Only the 9 integers per image leave the device; the ratios are host arithmetic
 // (neuralbarkcalculator_amd/metrics.py).
 //
-// A byte stream: 2 B per pixel with uint8 labels, 9 B with int64 labels, nothing reused.  Each thread walks
-// 16-pixel chunks (one 16-B load of target bytes, one 16-B load of u8 labels or eight of int64 labels), counts the
-// chunk into a packed 64-bit word (7 bits per cell: at most 16 per chunk), unpacks it into 9 register counters, and
-// the block reduces them per wave (shuffles) and across waves (LDS) before one 64-bit atomic per cell and block.
-// Blocks of 1024 threads, about 128 of them per call, each thread walking its chunks with a grid stride.
-// Integer sums do not depend on order: the result is bit-reproducible.  The grid is (slices of an image) x N.
+// A byte stream (reduce.hpp): 2 B per pixel with uint8 labels, 9 B with int64 labels, nothing reused.  A chunk is 16 pixels
+// (one 16-B load of target bytes, one 16-B load of u8 labels or eight of int64 labels), counted into a packed 64-bit word
+// (7 bits per cell: at most 16 per chunk) and unpacked into 9 register counters, which block_add sums into the image's cells.
+// Blocks of 1024 threads, about 128 of them per call.  The grid is (slices of an image) x N.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
-
-#include "../../include/nbc.h"
-#include "nbc_internal.hpp"
+#include "reduce.hpp"
 
 using namespace nbc;
 
@@ -24,11 +18,12 @@ namespace {
 constexpr int kThreads = 1024;                  // 16 waves: few blocks, so few atomics on the 9 cells of an image
 constexpr int kChunk = 16;                      // pixels per thread and step (16 target bytes)
 constexpr int kCells = 9;
+constexpr int kBlocksPerCall = 128;
+constexpr const char* kWho = "nbc_confusion";
 
-// target class of a grey level: round(2 * float32(v) / 255) (dataset.py:189-197) is 0 for 0..63, 1 for 64..191, 2 for
-// 192..255, which is (v + 64) >> 7 on the integer.  Cell 3 t + p; a label outside {0,1,2} is counted nowhere.
+// cell 3 t + p; a label outside {0,1,2} is counted nowhere
 __device__ __forceinline__ unsigned long long cell_bit(unsigned grey, unsigned long long label) {
-  const unsigned cell = ((grey + 64u) >> 7) * 3u + (unsigned)label;
+  const unsigned cell = target_class(grey) * 3u + (unsigned)label;
   return label < 3ull ? (1ull << (7u * cell)) : 0ull;
 }
 
@@ -73,73 +68,43 @@ __global__ __launch_bounds__(kThreads) void confusion_kernel(const LabelT* __res
   const long long stride = (long long)gridDim.x * kThreads;
   unsigned cnt[kCells] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-  // scalar head up to the first pixel whose target byte is 16-B aligned; the vector body needs the label there aligned too
+  // the vector body starts at the first pixel whose target byte is 16-B aligned and needs the label there aligned too
   // (always so for buffers that start 16-B aligned: then the label's offset is a multiple of 16 elements as well)
-  long long head = (long long)((16u - ((unsigned)reinterpret_cast<uintptr_t>(tgt) & 15u)) & 15u);
-  if (head > P) head = P;
-  const bool vec = ((reinterpret_cast<uintptr_t>(lab + head)) & 15u) == 0;
-  const long long chunks = vec ? (P - head) / kChunk : 0;
-  const long long body_end = head + chunks * kChunk;
+  ByteStream st(tgt, P, kChunk);
+  if ((reinterpret_cast<uintptr_t>(lab + st.head)) & 15u) st.drop_body();
 
-  for (long long c = (long long)blockIdx.x * kThreads + tid; c < chunks; c += stride)
-    unpack(chunk_bits(lab, tgt, head + c * kChunk), cnt);
+  const long long g = (long long)blockIdx.x * kThreads + tid;
+  for (long long c = g; c < st.chunks; c += stride) unpack(chunk_bits(lab, tgt, st.head + c * kChunk), cnt);
 
   // the pixels outside the body (head and tail, or every pixel of an image the body cannot reach), one per thread
   unsigned long long packed = 0;
   int in_packed = 0;
-  auto scalar = [&](long long q) {
+  st.for_each_outside(g, stride, [&](long long q) {
     packed += cell_bit(tgt[q], (unsigned long long)lab[q]);
     if (++in_packed == 127) { unpack(packed, cnt); packed = 0; in_packed = 0; }
-  };
-  const long long g = (long long)blockIdx.x * kThreads + tid;
-  for (long long q = g; q < (vec ? head : P); q += stride) scalar(q);
-  if (vec)
-    for (long long q = body_end + g; q < P; q += stride) scalar(q);
+  });
   unpack(packed, cnt);
 
-  // per wave, then per block: one 64-bit atomic per non-zero cell
-  __shared__ unsigned part[kThreads / 64][kCells];
-#pragma unroll
-  for (int k = 0; k < kCells; ++k) {
-    unsigned v = cnt[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((tid & 63) == 0) part[tid >> 6][k] = v;
-  }
-  __syncthreads();
-  if (tid < kCells) {
-    unsigned long long s = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s += part[w][tid];
-    if (s) atomicAdd(&conf[(size_t)blockIdx.y * kCells + tid], s);
-  }
+  block_add<kThreads, kCells>(cnt, conf + (size_t)blockIdx.y * kCells);
 }
-
-int fail(int code, const std::string& msg) { return set_error(code, "nbc_confusion: " + msg); }
 
 }  // namespace
 
 extern "C" int nbc_confusion(const void* labels_dev, int labels_dtype, const uint8_t* target_dev, int N, int H, int W,
                              int64_t* conf_dev, void* hip_stream) {
-  if (!labels_dev || !target_dev || !conf_dev) return fail(NBC_ERR_INVALID, "null argument");
-  if (N < 1 || N > 65535 || H < 1 || W < 1) return fail(NBC_ERR_INVALID, "bad shape");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(NBC_ERR_INVALID, "bad labels_dtype");
+  if (!labels_dev || !target_dev || !conf_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!per_image_shape_ok(N, H, W)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
   const long long P = (long long)H * W;
-  if (P > 0x7fffffffLL) return fail(NBC_ERR_INVALID, "H * W must stay below 2^31");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   unsigned long long* conf = reinterpret_cast<unsigned long long*>(conf_dev);
   hipError_t e = hipMemsetAsync(conf, 0, sizeof(unsigned long long) * kCells * (size_t)N, s);
-  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
-  // slices per image: at most one chunk per thread and step, and about 128 blocks over the batch.  Every block of an image
-  // adds into the same 9 cells, and atomics on one address serialise: per 1024^2 x 2 call inside the evaluation run
-  // (rocprofv3, other streams' forwards beside it) 512 blocks of 256 threads took 11.4 us (median), these 128 blocks of
-  // 1024 threads 8.7 us; the 4 MB read alone would take under 1 us at HBM rate.
-  const long long per_block = (long long)kThreads * kChunk;
-  long long slices = (P + per_block - 1) / per_block;
-  const long long want = (128 + N - 1) / N;
-  if (slices > want) slices = want;
-  if (slices < 1) slices = 1;
-  const dim3 grid((unsigned)slices, (unsigned)N);
+  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
+  // about 128 blocks over the batch.  Every block of an image adds into the same 9 cells, and atomics on one address
+  // serialise: per 1024^2 x 2 call inside the evaluation run (rocprofv3, other streams' forwards beside it) 512 blocks of
+  // 256 threads took 11.4 us (median), these 128 blocks of 1024 threads 8.7 us; the 4 MB read alone would take under 1 us
+  // at HBM rate.
+  const dim3 grid(slices_for(P, kChunk, kThreads, kBlocksPerCall, N), (unsigned)N);
   if (labels_dtype == NBC_LABEL_I64)
     hipLaunchKernelGGL(confusion_kernel<long long>, grid, dim3(kThreads), 0, s, static_cast<const long long*>(labels_dev), target_dev,
                        P, conf);
@@ -147,6 +112,6 @@ extern "C" int nbc_confusion(const void* labels_dev, int labels_dtype, const uin
     hipLaunchKernelGGL(confusion_kernel<unsigned char>, grid, dim3(kThreads), 0, s, static_cast<const unsigned char*>(labels_dev),
                        target_dev, P, conf);
   e = hipGetLastError();
-  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
 }

@@ -6,10 +6,8 @@
 // Only 6 + 4 integers per image leave the device; the divisions and the square root are host arithmetic
 // (neuralbarkcalculator_amd/stats.py).
 //
-// Both are byte streams with nothing reused, built like csrc/confusion.hip: 16-byte loads, a scalar head / tail for
-// unaligned starts and odd sizes, per-wave shuffles, then LDS, then one 64-bit atomic per cell and block on cells a memset
-// zeroed.  Integer sums do not depend on order: the results are bit-reproducible, and an image's numbers do not depend
-// on its batch or stream.  The grid is (slices of an image) x N, blocks of 1024 threads walking their chunks with a grid stride.
+// Both are byte streams with nothing reused, walked and summed by reduce.hpp's ByteStream and block_add.  The grid is
+// (slices of an image) x N, blocks of 1024 threads.
 //
 // Moments: interleaved RGB, so 48 bytes (three 16-byte loads) hold 16 whole pixels and byte j of a 48-byte chunk always
 // belongs to "slot" j % 3.  The body starts at the image's first 16-byte boundary, `head` bytes in, so slot s is channel
@@ -18,16 +16,12 @@
 // v_dot4_u32_u8 of the dword with the mask, its sum of squares one of the masked dword with the dword.  A chunk adds at most
 // 16 x 255 to a sum and 16 x 65025 to a sum of squares: they are taken per chunk in 32 bits and accumulated in 64.
 //
-// Counts: class = (v + 64) >> 7 (round(2 * float32(v) / 255), as nbc_confusion), so with a = bytes >= 64 and b = bytes >= 192
+// Counts: target_class is (v + 64) >> 7, so with a = bytes >= 64 and b = bytes >= 192
 // of a dword (bit 7 | bit 6, bit 7 & bit 6: one popcount each) the classes hold 4 - a, a - b and b of its pixels; the bytes
 // equal to 0, 127 or 255 are found with the exact zero-byte test ~(((x & 0x7f..) + 0x7f..) | x | 0x7f..) on v, v ^ 0x7f.. and ~v.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
-
-#include "../../include/nbc.h"
-#include "nbc_internal.hpp"
+#include "reduce.hpp"
 
 using namespace nbc;
 
@@ -50,27 +44,6 @@ __device__ __forceinline__ constexpr unsigned slot_mask(int k, int s, unsigned o
   return m;
 }
 
-// Block-wide sum of `cells` 64-bit values per thread into out[cells]: shuffles, LDS, one atomic per non-zero cell.
-template <int kCells>
-__device__ __forceinline__ void block_add(const u64 (&v)[kCells], u64* __restrict__ out) {
-  __shared__ u64 part[kThreads / 64][kCells];
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < kCells; ++k) {
-    u64 x = v[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    if ((tid & 63) == 0) part[tid >> 6][k] = x;
-  }
-  __syncthreads();
-  if (tid < kCells) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) s += part[w][tid];
-    if (s) atomicAdd(&out[tid], s);
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void image_moments_kernel(const unsigned char* __restrict__ x, long long B,
                                                                  u64* __restrict__ moments) {
   const unsigned char* img = x + (long long)blockIdx.y * B;      // B = 3 H W bytes per image
@@ -78,14 +51,11 @@ __global__ __launch_bounds__(kThreads) void image_moments_kernel(const unsigned 
   const long long g = (long long)blockIdx.x * kThreads + tid;
   const long long stride = (long long)gridDim.x * kThreads;
 
-  long long head = (long long)((16u - ((unsigned)reinterpret_cast<uintptr_t>(img) & 15u)) & 15u);
-  if (head > B) head = B;
-  const long long chunks = (B - head) / kMomentChunk;
-  const long long body_end = head + chunks * kMomentChunk;
+  const ByteStream st(img, B, kMomentChunk);
 
   u64 s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};     // per slot
-  for (long long c = g; c < chunks; c += stride) {
-    const uint4* p = reinterpret_cast<const uint4*>(img + head + c * kMomentChunk);
+  for (long long c = g; c < st.chunks; c += stride) {
+    const uint4* p = reinterpret_cast<const uint4*>(img + st.head + c * kMomentChunk);
     const uint4 a = p[0], b = p[1], d = p[2];
     const unsigned w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
     unsigned c1[3] = {0, 0, 0}, c2[3] = {0, 0, 0};
@@ -102,7 +72,7 @@ __global__ __launch_bounds__(kThreads) void image_moments_kernel(const unsigned 
   }
 
   // slot s is channel (head + s) % 3; then the bytes outside the body (at most 15 + 47 of them), one per thread
-  const int ph = (int)(head % 3);
+  const int ph = (int)(st.head % 3);
   u64 acc[kMomentCells];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
@@ -110,17 +80,15 @@ __global__ __launch_bounds__(kThreads) void image_moments_kernel(const unsigned 
     acc[2 * ch] = s == 0 ? s1[0] : s == 1 ? s1[1] : s1[2];
     acc[2 * ch + 1] = s == 0 ? s2[0] : s == 1 ? s2[1] : s2[2];
   }
-  auto scalar = [&](long long q) {
+  st.for_each_outside(g, stride, [&](long long q) {
     const unsigned v = img[q];
     const int ch = (int)(q % 3);
 #pragma unroll
     for (int k = 0; k < 3; ++k)
       if (ch == k) { acc[2 * k] += v; acc[2 * k + 1] += v * v; }
-  };
-  for (long long q = g; q < head; q += stride) scalar(q);
-  for (long long q = body_end + g; q < B; q += stride) scalar(q);
+  });
 
-  block_add<kMomentCells>(acc, moments + (size_t)blockIdx.y * kMomentCells);
+  block_add<kThreads, kMomentCells>(acc, moments + (size_t)blockIdx.y * kMomentCells);
 }
 
 // 0x80 in every byte of x that is zero, 0 elsewhere (exact: no carry crosses a byte)
@@ -135,14 +103,11 @@ __global__ __launch_bounds__(kThreads) void target_counts_kernel(const unsigned 
   const long long g = (long long)blockIdx.x * kThreads + tid;
   const long long stride = (long long)gridDim.x * kThreads;
 
-  long long head = (long long)((16u - ((unsigned)reinterpret_cast<uintptr_t>(tgt) & 15u)) & 15u);
-  if (head > P) head = P;
-  const long long chunks = (P - head) / kCountChunk;
-  const long long body_end = head + chunks * kCountChunk;
+  const ByteStream st(tgt, P, kCountChunk);
 
   unsigned cnt[kCountCells] = {0, 0, 0, 0};     // at most 2^31 / 1024 pixels per thread
-  for (long long c = g; c < chunks; c += stride) {
-    const uint4 t = *reinterpret_cast<const uint4*>(tgt + head + c * kCountChunk);
+  for (long long c = g; c < st.chunks; c += stride) {
+    const uint4 t = *reinterpret_cast<const uint4*>(tgt + st.head + c * kCountChunk);
     const unsigned w[4] = {t.x, t.y, t.z, t.w};
     unsigned ge64 = 0, ge192 = 0, on = 0;
 #pragma unroll
@@ -153,61 +118,40 @@ __global__ __launch_bounds__(kThreads) void target_counts_kernel(const unsigned 
     }
     cnt[0] += 16u - ge64; cnt[1] += ge64 - ge192; cnt[2] += ge192; cnt[3] += 16u - on;
   }
-  auto scalar = [&](long long q) {
+  st.for_each_outside(g, stride, [&](long long q) {
     const unsigned v = tgt[q];
-    const unsigned cls = (v + 64u) >> 7;
+    const unsigned cls = target_class(v);
     cnt[0] += cls == 0u; cnt[1] += cls == 1u; cnt[2] += cls == 2u;
     cnt[3] += (v != 0u && v != 127u && v != 255u);
-  };
-  for (long long q = g; q < head; q += stride) scalar(q);
-  for (long long q = body_end + g; q < P; q += stride) scalar(q);
+  });
 
   const u64 acc[kCountCells] = {cnt[0], cnt[1], cnt[2], cnt[3]};
-  block_add<kCountCells>(acc, counts + (size_t)blockIdx.y * kCountCells);
+  block_add<kThreads, kCountCells>(acc, counts + (size_t)blockIdx.y * kCountCells);
 }
 
-// what both entry points refuse, decided before any HIP call
-int check_shape(const char* who, const void* in, const void* out, int N, int H, int W) {
-  const std::string name(who);
-  if (!in || !out) return set_error(NBC_ERR_INVALID, name + ": null argument");
-  if (N < 1 || N > 65535 || H < 1 || W < 1) return set_error(NBC_ERR_INVALID, name + ": bad shape");
-  if ((long long)H * W > 0x7fffffffLL) return set_error(NBC_ERR_INVALID, name + ": H * W must stay below 2^31");
+// what both entry points refuse, decided before any HIP call; then the memset of the cells and the launch
+template <typename Kernel>
+int run(const char* who, Kernel kernel, const uint8_t* in, int channels, int chunk, int cells, int N, int H, int W, void* out_dev,
+        void* hip_stream) {
+  if (!in || !out_dev) return fail(who, NBC_ERR_INVALID, "null argument");
+  if (!per_image_shape_ok(N, H, W)) return fail(who, NBC_ERR_INVALID, kPerImageShape);
+  const long long bytes = (long long)channels * H * W;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  u64* out = static_cast<u64*>(out_dev);
+  hipError_t e = hipMemsetAsync(out, 0, sizeof(u64) * cells * (size_t)N, s);
+  if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
+  hipLaunchKernelGGL(kernel, dim3(slices_for(bytes, chunk, kThreads, kBlocksPerCall, N), (unsigned)N), dim3(kThreads), 0, s, in, bytes, out);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
-}
-
-// slices per image: no more than its chunks fill, and about kBlocksPerCall blocks over the batch
-unsigned slices_for(long long bytes, int chunk, int N) {
-  const long long per_block = (long long)kThreads * chunk;
-  long long slices = (bytes + per_block - 1) / per_block;
-  const long long want = (kBlocksPerCall + N - 1) / N;
-  if (slices > want) slices = want;
-  return (unsigned)(slices < 1 ? 1 : slices);
 }
 
 }  // namespace
 
 extern "C" int nbc_image_moments(const uint8_t* x_dev, int N, int H, int W, uint64_t* moments_dev, void* hip_stream) {
-  if (int rc = check_shape("nbc_image_moments", x_dev, moments_dev, N, H, W)) return rc;
-  const long long B = 3LL * H * W;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  u64* out = reinterpret_cast<u64*>(moments_dev);
-  hipError_t e = hipMemsetAsync(out, 0, sizeof(u64) * kMomentCells * (size_t)N, s);
-  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_image_moments: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(image_moments_kernel, dim3(slices_for(B, kMomentChunk, N), (unsigned)N), dim3(kThreads), 0, s, x_dev, B, out);
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_image_moments: ") + hipGetErrorString(e));
-  return NBC_OK;
+  return run("nbc_image_moments", image_moments_kernel, x_dev, 3, kMomentChunk, kMomentCells, N, H, W, moments_dev, hip_stream);
 }
 
 extern "C" int nbc_target_counts(const uint8_t* target_dev, int N, int H, int W, int64_t* counts_dev, void* hip_stream) {
-  if (int rc = check_shape("nbc_target_counts", target_dev, counts_dev, N, H, W)) return rc;
-  const long long P = (long long)H * W;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  u64* out = reinterpret_cast<u64*>(counts_dev);
-  hipError_t e = hipMemsetAsync(out, 0, sizeof(u64) * kCountCells * (size_t)N, s);
-  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_target_counts: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(target_counts_kernel, dim3(slices_for(P, kCountChunk, N), (unsigned)N), dim3(kThreads), 0, s, target_dev, P, out);
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_target_counts: ") + hipGetErrorString(e));
-  return NBC_OK;
+  return run("nbc_target_counts", target_counts_kernel, target_dev, 1, kCountChunk, kCountCells, N, H, W, counts_dev, hip_stream);
 }

@@ -3,15 +3,14 @@
 // of the mask from ONE read of the stored input of classifier.4.  The definition of a draw is in include/nbc.h
 // (nbc_dropout_draws); the generator is csrc/philox.hpp, shared with the host entry point nbc_dropout_mask below.
 //
-// The arithmetic is head1x1_body's (pointwise.hip) with one multiplication in front of it: one wave per pixel, lane l
-// owns channels 8l .. 8l+7 -- elements 512 pixel + 8l .. + 7, i.e. quads 128 pixel + 2l and + 1: two Philox calls per
-// lane, pixel and draw --, an f32 fma chain in channel order, then the 64-lane xor tree and the bias.  With p = 0 the
-// factor is 1.0f for every element and the logits are bit for bit the forward's.
-#include "../../include/nbc.h"
-#include "nbc_internal.hpp"
+// The arithmetic is head1x1_body's (pointwise.hip; the operands come in through the same head1x1.hpp) with one
+// multiplication in front of it: one wave per pixel, lane l owns channels 8l .. 8l+7 -- elements 512 pixel + 8l .. + 7,
+// i.e. quads 128 pixel + 2l and + 1: two Philox calls per lane, pixel and draw --, an f32 fma chain in channel order, then
+// wave_sum and the bias.  With p = 0 the factor is 1.0f for every element and the logits are bit for bit the forward's.
+#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "philox.hpp"
-#include "split16.hpp"
+#include "reduce.hpp"
 
 namespace nbc {
 namespace {
@@ -36,43 +35,16 @@ __global__ __launch_bounds__(256) void head1x1_dropout_kernel(const void* __rest
   const float b0 = bias[0], b1 = bias[1], b2 = bias[2];
   const int first = (blockIdx.x * 4 + wave) * 8;
   if (first >= hw) return;                                // wave-uniform: the shuffles below see whole waves
-  constexpr int VPP = PREC == 1 ? 1 : 2;                  // 16-byte loads per lane and pixel
   const unsigned char* xi = static_cast<const unsigned char*>(x) + (size_t)img * hw * CIN * (PREC == 1 ? 2 : 4);
-  uint4 raw[8][VPP];
+  Head1x1Raw<PREC> raw[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int m = min(first + q, hw - 1);
-    if constexpr (PREC == 2) {      // channels 8l .. 8l+7: h0 chunk l % 4 of group l / 4, and its h1 chunk 64 bytes on
-      const uint4* xp = reinterpret_cast<const uint4*>(xi + (size_t)m * CIN * 4 + (lane >> 2) * 128 + (lane & 3) * 16);
-      raw[q][0] = xp[0];
-      raw[q][VPP - 1] = xp[4];
-    } else {
-      const uint4* xp = reinterpret_cast<const uint4*>(xi + ((size_t)m * CIN + lane * 8) * (PREC == 0 ? 4 : 2));
-#pragma unroll
-      for (int k = 0; k < VPP; ++k) raw[q][k] = xp[k];
-    }
-  }
+  for (int q = 0; q < 8; ++q) raw[q] = head1x1_load<PREC, CIN>(xi, min(first + q, hw - 1), lane);
   bool bad = false;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int pix = first + q;
     float f[8];
-    if constexpr (PREC == 2) {
-      join16x8(raw[q][0], raw[q][VPP - 1], f);
-    } else if constexpr (PREC == 0) {
-      const uint4 a = raw[q][0], b = raw[q][VPP - 1];
-      f[0] = __builtin_bit_cast(float, a.x); f[1] = __builtin_bit_cast(float, a.y);
-      f[2] = __builtin_bit_cast(float, a.z); f[3] = __builtin_bit_cast(float, a.w);
-      f[4] = __builtin_bit_cast(float, b.x); f[5] = __builtin_bit_cast(float, b.y);
-      f[6] = __builtin_bit_cast(float, b.z); f[7] = __builtin_bit_cast(float, b.w);
-    } else {
-      const unsigned u[4] = {raw[q][0].x, raw[q][0].y, raw[q][0].z, raw[q][0].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-        f[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xffff0000u);
-      }
-    }
+    head1x1_decode(raw[q], f);
     const unsigned quad = (unsigned)pix * 128u + 2u * (unsigned)lane;   // hw * 128 < 2^32 (checked by the caller)
     for (int d = 0; d < draws; ++d) {
       const Philox4 r0 = dropout_words(quad, (unsigned)(first_draw + d), id, seed);
@@ -85,10 +57,7 @@ __global__ __launch_bounds__(256) void head1x1_dropout_kernel(const void* __rest
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(g, wr[c][e], s[c]);
       }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += __shfl_xor(s[c], off, 64);
+      wave_sum(s);
       if (lane == 0 && pix < hw) {
         float* yp = y + ((size_t)d * N + img) * 3 * hw + pix;
         const float l0 = s[0] + b0, l1 = s[1] + b1, l2 = s[2] + b2;

@@ -17,6 +17,7 @@
 //     pixel slices, then the 1x1 conv with BatchNorm and ReLU.
 //   head1x1: classifier.4 for any cin (a multiple of 64): FCNHead's inplanes / 4 channels, padded.
 #include "nbc_kernels.hpp"
+#include "reduce.hpp"
 
 namespace nbc {
 namespace {
@@ -115,8 +116,7 @@ __global__ __launch_bounds__(256) void se_excite_kernel(const float* __restrict_
     const float* row = wr + (size_t)j * C;
     float acc = 0.f;
     for (int i = lane; i < C; i += 64) acc = __builtin_fmaf(row[i], mean[i], acc);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum(acc);
     if (lane == 0) red[j] = swish_f(acc + br[j]);
   }
   __syncthreads();
@@ -184,8 +184,7 @@ __global__ __launch_bounds__(256) void pool_conv_kernel(const float* __restrict_
   const float* wr = w + (size_t)o * C;
   float acc = 0.f;
   for (int i = lane; i < C; i += 64) acc = __builtin_fmaf(wr[i], m[i], acc);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum(acc);
   if (lane == 0) y[(size_t)img * cout + o] = __builtin_fmaxf(__builtin_fmaf(acc, scale[o], shift[o]), 0.f);
 }
 

@@ -15,19 +15,15 @@
 //                   sorted in LDS, then written out in runs).  Keys-only: any correct sort gives the same array.
 //   lovasz_tile_fg  foreground keys per sorted tile (exact integers).
 //   lovasz_partial  per tile: running fg / bg counts, J_i = 1 - I_i / U_i and J_{i-1} in f64, sum of e_(i) (J_i - J_{i-1})
-//                   in f64 in a fixed order (lane, wave butterfly, waves in order).
+//                   in f64 in the fixed order of reduce.hpp.
 //   lovasz_finish   one thread per segment adds the tile partials in tile order.
-// Every sum has a fixed order and every count is exact, so an image's terms are bit-identical whatever batch or stream
-// it runs in.  A segment whose class is absent (G = 0) or whose image has a non-finite softmax is not sorted: its term is
+// A segment whose class is absent (G = 0) or whose image has a non-finite softmax is not sorted: its term is
 // 0 or NaN.  No library besides the HIP runtime.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
-#include <string>
 
-#include "../../include/nbc.h"
-#include "nbc_internal.hpp"
+#include "reduce.hpp"
 
 using namespace nbc;
 
@@ -42,6 +38,7 @@ constexpr int kRadix = 256;
 constexpr int kPasses = 4;                              // 4 x 8 bits cover the 31-bit keys
 constexpr int kKeyThreads = 256;
 constexpr int kScanThreads = 1024;                      // 4 groups of 256 digit lanes
+constexpr const char* kWho = "nbc_lovasz_softmax";
 
 using u32 = unsigned;
 using u64 = unsigned long long;
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(kKeyThreads) void lovasz_keys(const float* __restri
     const float p[kClasses] = {ea / s, eb / s, ec / s};
     const bool finite = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
     bad |= !finite;
-    const u32 t = ((u32)tg[i] + 64u) >> 7;                 // round(2 v / 255), as nbc_confusion
+    const u32 t = target_class(tg[i]);
 #pragma unroll
     for (int cl = 0; cl < kClasses; ++cl) {
       const u32 fg = t == (u32)cl;
@@ -107,21 +104,9 @@ __global__ __launch_bounds__(kKeyThreads) void lovasz_keys(const float* __restri
       cnt[cl] += fg;
     }
   }
-  __shared__ u32 part[kKeyThreads / 64][kClasses];
-#pragma unroll
-  for (int cl = 0; cl < kClasses; ++cl) {
-    u32 v = cnt[cl];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((tid & 63) == 0) part[tid >> 6][cl] = v;
-  }
-  if (__syncthreads_or(bad) && tid == 0) flag[n] = 1u;
-  if (tid < kClasses) {
-    u64 s = 0;
-#pragma unroll
-    for (int w = 0; w < kKeyThreads / 64; ++w) s += part[w][tid];
-    if (s) atomicAdd(&G[(size_t)n * kClasses + tid], s);
-  }
+  block_add<kKeyThreads, kClasses>(cnt, G + (size_t)n * kClasses, [&] {
+    if (__syncthreads_or(bad) && tid == 0) flag[n] = 1u;
+  });
 }
 
 // per-tile digit histogram: hist[seg][t][d]
@@ -252,8 +237,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __rest
 
 __device__ __forceinline__ void block_sum_to(u32 v, u32* red /* LDS [kWaves] */, u32* out) {
   const int tid = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = wave_sum(v);
   if ((tid & 63) == 0) red[tid >> 6] = v;
   __syncthreads();
   if (tid == 0) {
@@ -304,8 +288,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __rest
     key[j] = idx < nt ? src[idx] : 0u;              // 0: not foreground, e = 0
     mine += key[j] & 1u;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  mine = wave_sum(mine);
   if (lane == 0) wfg[w] = mine;
   __syncthreads();
   long long run = fg_before_tile;                    // foreground keys before this wave's first key
@@ -328,8 +311,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __rest
     }
     run += __popcll(m);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  acc = wave_sum(acc);
   if (lane == 0) dred[w] = acc;
   __syncthreads();
   if (tid == 0) {
@@ -363,31 +345,26 @@ __global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ p
   terms[seg] = s;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
   size_t keys_a, keys_b, hist, base, tile_fg, partial, flag, total;
 };
 
 // byte offsets of the workspace regions (include/nbc.h states the sum); false for a shape the call refuses
 bool layout(int N, int H, int W, Layout* L) {
-  if (N < 1 || N > 65535 || H < 1 || W < 1) return false;
+  if (!per_image_shape_ok(N, H, W)) return false;
   const size_t P = (size_t)H * (size_t)W;
-  if (P >= ((size_t)1 << 31)) return false;
   const size_t S = (size_t)kClasses * N, T = (P + kTile - 1) / kTile;
-  size_t o = 0;
-  L->keys_a = o;  o += align256(4 * S * P);
-  L->keys_b = o;  o += align256(4 * S * P);
-  L->hist = o;    o += align256(4 * S * T * kRadix);
-  L->base = o;    o += align256(4 * S * kRadix);
-  L->tile_fg = o; o += align256(4 * S * T);
-  L->partial = o; o += align256(8 * S * T);
-  L->flag = o;    o += align256(4 * (size_t)N);
-  L->total = o;
+  Carver ws;
+  L->keys_a = ws.take(4 * S * P);
+  L->keys_b = ws.take(4 * S * P);
+  L->hist = ws.take(4 * S * T * kRadix);
+  L->base = ws.take(4 * S * kRadix);
+  L->tile_fg = ws.take(4 * S * T);
+  L->partial = ws.take(8 * S * T);
+  L->flag = ws.take(4 * (size_t)N);
+  L->total = ws.offset;
   return true;
 }
-
-int fail(int code, const std::string& msg) { return set_error(code, "nbc_lovasz_softmax: " + msg); }
 
 }  // namespace
 
@@ -398,12 +375,10 @@ extern "C" size_t nbc_lovasz_workspace_bytes(int N, int H, int W) {
 
 extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, void* workspace_dev,
                                   size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
-  if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(NBC_ERR_INVALID, "null argument");
+  if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
   Layout L;
-  if (!layout(N, H, W, &L)) return fail(NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H, W >= 1 and H * W < 2^31");
-  if (workspace_bytes < L.total)
-    return fail(NBC_ERR_INVALID, "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(L.total) + " needed");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) & 255u) return fail(NBC_ERR_INVALID, "workspace must be 256-byte aligned");
+  if (!layout(N, H, W, &L)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, L.total)) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   char* ws = static_cast<char*>(workspace_dev);
   u32* keys[2] = {reinterpret_cast<u32*>(ws + L.keys_a), reinterpret_cast<u32*>(ws + L.keys_b)};
@@ -418,7 +393,7 @@ extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* t
 
   hipError_t e = hipMemsetAsync(G, 0, sizeof(u64) * (size_t)S, s);
   if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(u32) * (size_t)N, s);
-  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
   // about 4 pixels per thread and at most ~4096 blocks over the batch
   long long bx = (P + 4 * kKeyThreads - 1) / (4 * kKeyThreads);
   const long long cap = (4096 + N - 1) / N;
@@ -440,6 +415,6 @@ extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* t
   hipLaunchKernelGGL(lovasz_partial, tiles, dim3(kSortThreads), 0, s, sorted, P, T, tile_fg, G, flag, partial);
   hipLaunchKernelGGL(lovasz_finish, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, partial, T, S, G, flag, terms_dev);
   e = hipGetLastError();
-  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
 }

@@ -19,6 +19,7 @@
 #include "nbc_net.hpp"
 #include "nbc_plan.hpp"
 #include "philox.hpp"
+#include "reduce.hpp"
 
 using namespace nbc;
 
@@ -738,6 +739,19 @@ static int collect_profile(nbc_ctx* c) {
   return NBC_OK;
 }
 
+// One pass of nbc_dropout_draws over `draws` draws of N images: its regions of the workspace.  nbc_dropout_workspace_bytes
+// publishes `total` (include/nbc.h states the formula), the pass loop takes the offsets.
+struct DropoutLayout {
+  size_t lowres, labels, parent, size, bg, total;
+};
+static DropoutLayout dropout_layout(int N, int H, int W, int h, int w, int draws) {
+  const size_t I = (size_t)draws * N, px = I * H * W;
+  Carver ws;
+  const size_t lowres = ws.take(12 * I * h * w), labels = ws.take(px);                        // f32 [I][3][h][w], u8 [I][H][W]
+  const size_t parent = ws.take(4 * px), size = ws.take(4 * px), bg = ws.take(px);           // remove_small_zones' int, int, u8
+  return {lowres, labels, parent, size, bg, ws.offset};
+}
+
 extern "C" {
 
 int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W, int reps, int objective,
@@ -864,9 +878,7 @@ size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
   if (I > 65535ull) return 0;
   int h = 0, w = 0;
   if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1 || (unsigned long long)h * w >= (1ull << 25)) return 0;
-  const auto A = [](unsigned long long x) { return (x + 255ull) & ~255ull; };
-  const unsigned long long px = I * (unsigned long long)H * W;
-  return (size_t)(A(12ull * I * h * w) + A(px) + 2 * A(4 * px) + A(px));
+  return dropout_layout(N, H, W, h, w, draws_per_pass).total;
 }
 
 int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
@@ -903,21 +915,19 @@ int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const UnitPtrs up = unit_ptrs(c, head->unit);
   const int hw = P.h * P.w;
-  const auto A = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const uint32_t T = dropout_threshold(p);
   const float m = dropout_scale(p);
   for (int d0 = 0; d0 < draws; d0 += pass) {
     const int D = std::min(pass, draws - d0);
     const int I = D * N;
-    const size_t px = (size_t)I * H * W;
     // the pass's slice of the workspace, sized for THIS pass (the last one may be shorter)
+    const DropoutLayout L = dropout_layout(N, H, W, P.h, P.w, D);
     unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
-    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws);
-    ws += A((size_t)12 * I * hw);
-    unsigned char* labels = ws; ws += A(px);
-    int* parent = reinterpret_cast<int*>(ws); ws += A(4 * px);
-    int* size = reinterpret_cast<int*>(ws); ws += A(4 * px);
-    unsigned char* bg = ws;
+    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws + L.lowres);
+    unsigned char* labels = ws + L.labels;
+    int* parent = reinterpret_cast<int*>(ws + L.parent);
+    int* size = reinterpret_cast<int*>(ws + L.size);
+    unsigned char* bg = ws + L.bg;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
     NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf], up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
                                    first_draw + d0, D, c->nonfinite, s));

@@ -17,10 +17,10 @@
 //                     4-byte and 1-byte loads.  How a pixel was loaded reaches nothing: the entropy is evaluated in f64 from
 //                     the f32 logits, m = max, log(sum exp(x_c - m)) - (x_t - m), and added to the thread's accumulator
 //                     of its cell (a select, not a multiplication by 0: a non-finite entropy reaches its own cell only)
-//                     in pixel order; then lanes (xor butterfly), then the four waves in order through LDS.  One f64 and one
+//                     in pixel order; then lanes (wave_sum), then the four waves in order through LDS.  One f64 and one
 //                     u32 partial per (image, cell, tile) go to the workspace.  No atomics, no memset.
-//   pixel_ce_finish   one wave per (image, cell): lane l adds the partials of tiles l, l + 64, ... in tile order, then the
-//                     xor butterfly over the lanes.
+//   pixel_ce_finish   one wave per (image, cell): lane l adds the partials of tiles l, l + 64, ... in tile order, then
+//                     wave_sum.
 // The tile size and both orders depend on H * W alone, so an image's 18 numbers are bit-identical alone, anywhere in a
 // batch and on any stream.  IEEE arithmetic gives torch's answers on non-finite input by itself: a NaN or +inf logit, or three
 // -inf, make x_c - m NaN and with it the entropy; -inf at the target class alone makes it +inf.
@@ -28,11 +28,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
-#include <string>
 
-#include "../../include/nbc.h"
-#include "nbc_internal.hpp"
+#include "reduce.hpp"
 
 using namespace nbc;
 
@@ -45,6 +42,7 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kGroup = 4;                               // consecutive pixels per load group
 constexpr int kGroups = 4;                              // groups per thread and tile
 constexpr int kTile = kThreads * kGroup * kGroups;      // 4096 pixels per tile
+constexpr const char* kWho = "nbc_pixel_cross_entropy";
 
 using u32 = unsigned;
 using u64 = unsigned long long;
@@ -55,14 +53,10 @@ __device__ __forceinline__ void add_pixel(float a, float b, float c, u32 grey, d
   const double x0 = (double)a, x1 = (double)b, x2 = (double)c;
   const double m = fmax(fmax(x0, x1), x2);              // skips a NaN, which poisons its own difference below
   const double s = exp(x0 - m) + exp(x1 - m) + exp(x2 - m);
-  const u32 t = (grey + 64u) >> 7;                      // round(2 v / 255), as nbc_confusion
+  const u32 t = target_class(grey);
   const double xt = t == 0u ? x0 : t == 1u ? x1 : x2;
   const double ce = log(s) - (xt - m);
-  // torch.argmax: first maximum wins, NaN counts as the maximum (as upsample_argmax_kernel)
-  u32 best = 0;
-  float bv = a;
-  if ((b > bv) || (b != b && bv == bv)) { best = 1; bv = b; }
-  if ((c > bv) || (c != c && bv == bv)) { best = 2; bv = c; }
+  const u32 best = argmax3(a, b, c);                    // the forward's own labels (upsample_argmax_kernel)
   const u32 cell = t * 3u + best;
   packed += 1ull << (7u * cell);
 #pragma unroll
@@ -108,13 +102,8 @@ __global__ __launch_bounds__(kThreads) void pixel_ce_partial(const float* __rest
   __shared__ u32 cred[kWaves][kCells];
 #pragma unroll
   for (int k = 0; k < kCells; ++k) {
-    double v = acc[k];
-    u32 c = (u32)(packed >> (7 * k)) & 127u;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      v += __shfl_xor(v, off, 64);
-      c += __shfl_xor(c, off, 64);
-    }
+    const double v = wave_sum(acc[k]);
+    const u32 c = wave_sum((u32)(packed >> (7 * k)) & 127u);
     if (lane == 0) { dred[w][k] = v; cred[w][k] = c; }
   }
   __syncthreads();
@@ -138,15 +127,10 @@ __global__ __launch_bounds__(64) void pixel_ce_finish(const double* __restrict__
   double s = 0.0;
   u64 c = 0;
   for (int t = lane; t < T; t += 64) { s += ps[t]; c += pc[t]; }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s += __shfl_xor(s, off, 64);
-    c += __shfl_xor(c, off, 64);
-  }
+  s = wave_sum(s);
+  c = wave_sum(c);
   if (lane == 0) { sums[seg] = s; counts[seg] = c; }
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
   size_t part_sum, part_cnt, total;
@@ -155,19 +139,16 @@ struct Layout {
 
 // byte offsets of the workspace regions (include/nbc.h states the sum); false for a shape the call refuses
 bool layout(int N, int H, int W, Layout* L) {
-  if (N < 1 || N > 65535 || H < 1 || W < 1) return false;
+  if (!per_image_shape_ok(N, H, W)) return false;
   const size_t P = (size_t)H * (size_t)W;
-  if (P >= ((size_t)1 << 31)) return false;
   const size_t T = (P + kTile - 1) / kTile, S = (size_t)kCells * N;
-  size_t o = 0;
-  L->part_sum = o; o += align256(8 * S * T);
-  L->part_cnt = o; o += align256(4 * S * T);
-  L->total = o;
+  Carver ws;
+  L->part_sum = ws.take(8 * S * T);
+  L->part_cnt = ws.take(4 * S * T);
+  L->total = ws.offset;
   L->T = (int)T;
   return true;
 }
-
-int fail(int code, const std::string& msg) { return set_error(code, "nbc_pixel_cross_entropy: " + msg); }
 
 }  // namespace
 
@@ -178,12 +159,10 @@ extern "C" size_t nbc_pixel_ce_workspace_bytes(int N, int H, int W) {
 
 extern "C" int nbc_pixel_cross_entropy(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, void* workspace_dev,
                                        size_t workspace_bytes, double* sums_dev, int64_t* counts_dev, void* hip_stream) {
-  if (!logits_full_dev || !target_dev || !workspace_dev || !sums_dev || !counts_dev) return fail(NBC_ERR_INVALID, "null argument");
+  if (!logits_full_dev || !target_dev || !workspace_dev || !sums_dev || !counts_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
   Layout L;
-  if (!layout(N, H, W, &L)) return fail(NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H, W >= 1 and H * W < 2^31");
-  if (workspace_bytes < L.total)
-    return fail(NBC_ERR_INVALID, "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(L.total) + " needed");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) & 255u) return fail(NBC_ERR_INVALID, "workspace must be 256-byte aligned");
+  if (!layout(N, H, W, &L)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, L.total)) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   char* ws = static_cast<char*>(workspace_dev);
   double* part_sum = reinterpret_cast<double*>(ws + L.part_sum);
@@ -194,6 +173,6 @@ extern "C" int nbc_pixel_cross_entropy(const float* logits_full_dev, const uint8
   hipLaunchKernelGGL(pixel_ce_finish, dim3((unsigned)(kCells * N)), dim3(64), 0, s, part_sum, part_cnt, L.T, sums_dev,
                      reinterpret_cast<u64*>(counts_dev));
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NBC_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
 }

@@ -3,7 +3,9 @@
 // lane accesses, no MFMA.
 #include <cstdlib>
 
+#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
+#include "reduce.hpp"
 #include "split16.hpp"
 
 namespace nbc {
@@ -168,43 +170,14 @@ __device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
   const int first = (blockIdx.x * 4 + wave) * PIX_PER_WAVE;
   if (counts_zero && blockIdx.x == 0 && threadIdx.x < ncounts) counts_zero[threadIdx.x] = 0ull;   // for the next launch
   // the wave's 8 pixel rows (loads) are requested together (one memory round trip), then reduced one by one
-  constexpr int VPP = PREC == 1 ? 1 : 2;                  // 16-byte loads per lane and pixel
-  uint4 raw[8][VPP];
+  Head1x1Raw<PREC> raw[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int m = min(first + q * PPL + sub, M - 1);
-    if constexpr (PREC == 2) {      // channels 8l .. 8l+7: h0 chunk l % 4 of group l / 4, and its h1 chunk 64 bytes on
-      const uint4* xp = reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(x) + (size_t)m * CIN * 4 +
-                                                       (cl >> 2) * 128 + (cl & 3) * 16);
-      raw[q][0] = xp[0];
-      raw[q][VPP - 1] = xp[4];
-    } else {
-      const uint4* xp = reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(x) +
-                                                       ((size_t)m * CIN + cl * 8) * (PREC == 0 ? 4 : 2));
-#pragma unroll
-      for (int k = 0; k < VPP; ++k) raw[q][k] = xp[k];
-    }
-  }
+  for (int q = 0; q < 8; ++q) raw[q] = head1x1_load<PREC, CIN>(x, min(first + q * PPL + sub, M - 1), cl);
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int m = first + q * PPL + sub;
     float f[8];
-    if constexpr (PREC == 2) {
-      join16x8(raw[q][0], raw[q][VPP - 1], f);
-    } else if constexpr (PREC == 0) {
-      const uint4 a = raw[q][0], b = raw[q][VPP - 1];
-      f[0] = __builtin_bit_cast(float, a.x); f[1] = __builtin_bit_cast(float, a.y);
-      f[2] = __builtin_bit_cast(float, a.z); f[3] = __builtin_bit_cast(float, a.w);
-      f[4] = __builtin_bit_cast(float, b.x); f[5] = __builtin_bit_cast(float, b.y);
-      f[6] = __builtin_bit_cast(float, b.z); f[7] = __builtin_bit_cast(float, b.w);
-    } else {
-      const unsigned u[4] = {raw[q][0].x, raw[q][0].y, raw[q][0].z, raw[q][0].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-        f[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xffff0000u);
-      }
-    }
+    head1x1_decode(raw[q], f);
     float s[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -314,14 +287,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(
       v[c] = out;
       if (logits_full) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = out;
     }
-    // torch.argmax: first maximum wins, NaN counts as the maximum.
-    int best = 0;
-    float bv = v[0];
-#pragma unroll
-    for (int c = 1; c < 3; ++c) {
-      const bool take = (v[c] > bv) || (v[c] != v[c] && bv == bv);
-      if (take) { best = c; bv = v[c]; }
-    }
+    int best = argmax3(v[0], v[1], v[2]);
     if (exclude_nodes && best == 2) best = 1;
     label = best;
     if (labels) {
@@ -408,7 +374,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
       hsum[c][rr][tid] = t;                        // read back by this thread only
     }
   }
-  unsigned cnt0 = 0, cnt1 = 0, cnt2 = 0;
+  unsigned cnt[3] = {0, 0, 0};
   for (int row = 0; row < UP_ROWS; ++row) {
     const int oy = oy0 + row;
     if (oy >= H) break;                        // block-uniform
@@ -427,16 +393,10 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
       v[c] = out;
       if (logits_full && live_x) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = out;
     }
-    int best = 0;
-    float bv = v[0];
-#pragma unroll
-    for (int c = 1; c < 3; ++c) {
-      const bool take = (v[c] > bv) || (v[c] != v[c] && bv == bv);
-      if (take) { best = c; bv = v[c]; }
-    }
+    int best = argmax3(v[0], v[1], v[2]);
     if (exclude_nodes && best == 2) best = 1;
     if (live_x) {
-      cnt0 += best == 0; cnt1 += best == 1; cnt2 += best == 2;
+      cnt[0] += best == 0; cnt[1] += best == 1; cnt[2] += best == 2;
       if (labels) {
         const size_t o = ((size_t)img * H + oy) * W + ox;
         if (labels_i64) static_cast<long long*>(labels)[o] = best;
@@ -445,16 +405,11 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
     }
   }
   if (counts) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      cnt0 += __shfl_xor(cnt0, off, 64);
-      cnt1 += __shfl_xor(cnt1, off, 64);
-      cnt2 += __shfl_xor(cnt2, off, 64);
-    }
+    wave_sum(cnt);
     if ((tid & 63) == 0) {
-      if (cnt0) atomicAdd(&blk_counts[0], cnt0);
-      if (cnt1) atomicAdd(&blk_counts[1], cnt1);
-      if (cnt2) atomicAdd(&blk_counts[2], cnt2);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (cnt[c]) atomicAdd(&blk_counts[c], cnt[c]);
     }
     __syncthreads();
     if (tid < 3 && blk_counts[tid])

@@ -13,6 +13,7 @@ runs, ``torch.distributed`` (RCCL) for the one-off weight broadcast.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Mapping, Optional, Tuple
 
@@ -275,19 +276,17 @@ class FCNResNet50:
         (class 0 <-> class 1).  ``exclude_nodes`` applies the 2 -> 1 remap of models.py:273-276
         afterwards.  Returns ``(labels, counts int64 [N,3])`` with the pixels per class of the result."""
         self._require_ctx()
-        if labels.device != self.device or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
-            raise ValueError("labels must be a contiguous uint8 or int64 tensor on %s" % (self.device,))
+        self._check_labels(labels)
         if labels.dim() not in (2, 3):
             raise ValueError("labels must be [H,W] or [N,H,W]")
         n = 1 if labels.dim() == 2 else int(labels.shape[0])
         h, w = int(labels.shape[-2]), int(labels.shape[-1])
         counts = torch.empty((n, 3), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             _lib.check(self._lib.nbc_remove_small_zones(self._ctx, labels.data_ptr(),
                                                         _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
                                                         n, h, w, int(min_pixels), int(bool(exclude_nodes)),
-                                                        counts.data_ptr(), stream), "nbc_remove_small_zones")
+                                                        counts.data_ptr(), cur.cuda_stream), "nbc_remove_small_zones")
         return labels, counts
 
     def confusion(self, labels: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -297,8 +296,7 @@ class FCNResNet50:
         ``round(2 * v / 255)`` (dataset.py:189-197); both on this model's device.  Runs on the current stream.  Returns int64
         ``[N,3,3]``: ``conf[n, t, p]`` = pixels of target class t predicted as p."""
         self._require_ctx()
-        if labels.device != self.device or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
-            raise ValueError("labels must be a contiguous uint8 or int64 tensor on %s" % (self.device,))
+        self._check_labels(labels)
         if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
             raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
         if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
@@ -306,10 +304,9 @@ class FCNResNet50:
         n = 1 if labels.dim() == 2 else int(labels.shape[0])
         h, w = int(labels.shape[-2]), int(labels.shape[-1])
         conf = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             _lib.check(self._lib.nbc_confusion(labels.data_ptr(), _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
-                                               target.data_ptr(), n, h, w, conf.data_ptr(), stream), "nbc_confusion")
+                                               target.data_ptr(), n, h, w, conf.data_ptr(), cur.cuda_stream), "nbc_confusion")
         return conf
 
     def lovasz_softmax(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -322,27 +319,16 @@ class FCNResNet50:
         NaN for every present class of an image whose softmax is not finite somewhere); ``metrics.lovasz_loss`` takes the
         mean over the present classes."""
         self._require_ctx()
-        if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
-                or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES:
-            raise ValueError("logits_full must be a contiguous float32 [N,3,H,W] tensor on %s" % (self.device,))
-        n, _, h, w = (int(v) for v in logits_full.shape)
-        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous() \
-                or tuple(target.shape) != (n, h, w) or target.numel() == 0:
-            raise ValueError("target must be a contiguous uint8 [%d,%d,%d] tensor on %s" % (n, h, w, self.device))
+        n, h, w = self._check_logits_target(logits_full, target)
         need = int(self._lib.nbc_lovasz_workspace_bytes(n, h, w))
         if need == 0:
             raise ValueError("nbc_lovasz_softmax refuses a [%d,3,%d,%d] batch (N <= 65535, H * W < 2^31)" % (n, h, w))
-        if self._lovasz_ws is None or self._lovasz_ws.numel() < need:
-            self._lovasz_ws = None
-            self._lovasz_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         terms = torch.empty((n, NUM_CLASSES), dtype=torch.float64, device=self.device)
         fg_counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            self._lovasz_ws.record_stream(cur)       # the cached workspace may be used on several streams
-            _lib.check(self._lib.nbc_lovasz_softmax(logits_full.data_ptr(), target.data_ptr(), n, h, w, self._lovasz_ws.data_ptr(),
-                                                    self._lovasz_ws.numel(), terms.data_ptr(), fg_counts.data_ptr(),
-                                                    cur.cuda_stream), "nbc_lovasz_softmax")
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_lovasz_ws", need, cur)
+            _lib.check(self._lib.nbc_lovasz_softmax(logits_full.data_ptr(), target.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(),
+                                                    terms.data_ptr(), fg_counts.data_ptr(), cur.cuda_stream), "nbc_lovasz_softmax")
         return terms, fg_counts
 
     def pixel_cross_entropy(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -354,27 +340,17 @@ class FCNResNet50:
         ``counts[n, t, p]`` their number (the raw ``confusion`` of the same forward).  ``metrics.cross_entropy``,
         ``weighted_cross_entropy`` and ``mixed_loss`` turn them into the losses, for any class weights."""
         self._require_ctx()
-        if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
-                or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES:
-            raise ValueError("logits_full must be a contiguous float32 [N,3,H,W] tensor on %s" % (self.device,))
-        n, _, h, w = (int(v) for v in logits_full.shape)
-        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous() \
-                or tuple(target.shape) != (n, h, w) or target.numel() == 0:
-            raise ValueError("target must be a contiguous uint8 [%d,%d,%d] tensor on %s" % (n, h, w, self.device))
+        n, h, w = self._check_logits_target(logits_full, target)
         need = int(self._lib.nbc_pixel_ce_workspace_bytes(n, h, w))
         if need == 0:
             raise ValueError("nbc_pixel_cross_entropy refuses a [%d,3,%d,%d] batch (N <= 65535, H * W < 2^31)" % (n, h, w))
-        if self._pixel_ce_ws is None or self._pixel_ce_ws.numel() < need:
-            self._pixel_ce_ws = None
-            self._pixel_ce_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         sums = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.float64, device=self.device)
         counts = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            self._pixel_ce_ws.record_stream(cur)
-            _lib.check(self._lib.nbc_pixel_cross_entropy(logits_full.data_ptr(), target.data_ptr(), n, h, w,
-                                                         self._pixel_ce_ws.data_ptr(), self._pixel_ce_ws.numel(), sums.data_ptr(),
-                                                         counts.data_ptr(), cur.cuda_stream), "nbc_pixel_cross_entropy")
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_pixel_ce_ws", need, cur)
+            _lib.check(self._lib.nbc_pixel_cross_entropy(logits_full.data_ptr(), target.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(),
+                                                         sums.data_ptr(), counts.data_ptr(), cur.cuda_stream),
+                       "nbc_pixel_cross_entropy")
         return sums, counts
 
     def dropout_draws(self, draws: int, image_ids, p: float = 0.1, seed: int = 0, first_draw: int = 0,
@@ -422,21 +398,17 @@ class FCNResNet50:
         need = int(self._lib.nbc_dropout_workspace_bytes(n, h, w, per_pass))
         if need == 0:
             raise ValueError("nbc_dropout_draws refuses a [%d,3,%d,%d] batch (draws x N <= 65535 per pass, H * W < 2^31)" % (n, h, w))
-        if self._dropout_ws is None or self._dropout_ws.numel() < need:
-            self._dropout_ws = None
-            self._dropout_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         counts = torch.empty((draws, n, NUM_CLASSES), dtype=torch.int64, device=self.device)
         lowres = None
         if return_lowres:
             lowres = torch.empty((draws, n, NUM_CLASSES) + out_hw(h, w, self.ARCH), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            self._dropout_ws.record_stream(cur)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_dropout_ws", need, cur)
             # the workspace handed over is exactly what per_pass draws need: a larger cached one must not change the pass
             rc = self._lib.nbc_dropout_draws(self._ctx, n, h, w, ids_arr, float(p), seed, first_draw, draws,
                                              int(min_pixels) if small_zones else 0, int(bool(exclude_nodes)),
                                              lowres.data_ptr() if lowres is not None else None, counts.data_ptr(),
-                                             self._dropout_ws.data_ptr(), need, cur.cuda_stream)
+                                             ws.data_ptr(), need, cur.cuda_stream)
         _lib.check(rc, "nbc_dropout_draws")
         return (counts, lowres) if return_lowres else counts
 
@@ -446,14 +418,11 @@ class FCNResNet50:
         anti_aliasing=False)`` -> float32 ``[out_h,out_w,3]``; bit-identical to
         ``predict.resize_bicubic_reflect(image.astype(float32) / 255, out_h, out_w)``."""
         self._require_ctx()
-        if image.device != self.device or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 \
-                or not image.is_contiguous():
-            raise ValueError("image must be a contiguous uint8 [H,W,3] tensor on %s" % (self.device,))
+        self._check_rgb_u8(image)
         out = torch.empty((int(out_h), int(out_w), 3), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             _lib.check(self._lib.nbc_resize_cubic_u8(self._ctx, image.data_ptr(), int(image.shape[0]), int(image.shape[1]),
-                                                     out.data_ptr(), int(out_h), int(out_w), stream), "nbc_resize_cubic_u8")
+                                                     out.data_ptr(), int(out_h), int(out_w), cur.cuda_stream), "nbc_resize_cubic_u8")
         return out
 
     def preprocess_u8(self, image: torch.Tensor, out_h: int, out_w: int):
@@ -461,15 +430,12 @@ class FCNResNet50:
         and ``trim_black``'s per-row lit-pixel counts (models.py:158-161), all on the device.  Returns
         ``(uint8 [out_h,out_w,3], int32 [out_h])``."""
         self._require_ctx()
-        if image.device != self.device or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 \
-                or not image.is_contiguous():
-            raise ValueError("image must be a contiguous uint8 [H,W,3] tensor on %s" % (self.device,))
+        self._check_rgb_u8(image)
         out = torch.empty((int(out_h), int(out_w), 3), dtype=torch.uint8, device=self.device)
         lit = torch.empty((int(out_h),), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             _lib.check(self._lib.nbc_preprocess_u8(self._ctx, image.data_ptr(), int(image.shape[0]), int(image.shape[1]),
-                                                   out.data_ptr(), lit.data_ptr(), int(out_h), int(out_w), stream), "nbc_preprocess_u8")
+                                                   out.data_ptr(), lit.data_ptr(), int(out_h), int(out_w), cur.cuda_stream), "nbc_preprocess_u8")
         return out, lit
 
     def upsample_argmax(self, lowres: torch.Tensor, size: Tuple[int, int], exclude_nodes: bool = False,
@@ -486,12 +452,11 @@ class FCNResNet50:
         counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
         logits = torch.empty((n, NUM_CLASSES, H, W), dtype=torch.float32, device=self.device) if return_logits else None
         ldt = _lib.LABEL_I64 if labels_dtype == torch.int64 else _lib.LABEL_U8
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             rc = self._lib.nbc_upsample_argmax(self._ctx, lowres.data_ptr(), n, lh, lw, H, W,
                                                logits.data_ptr() if logits is not None else None,
                                                labels.data_ptr(), ldt, counts.data_ptr(),
-                                               int(bool(exclude_nodes)), stream)
+                                               int(bool(exclude_nodes)), cur.cuda_stream)
         _lib.check(rc, "nbc_upsample_argmax")
         return (labels, counts, logits) if return_logits else (labels, counts)
 
@@ -627,9 +592,8 @@ class FCNResNet50:
         ahead of the copy produced a NaN / infinite logit."""
         if host_word.dtype != torch.int32 or host_word.numel() != 1 or host_word.is_cuda or not host_word.is_pinned():
             raise ValueError("host_word must be a pinned int32 CPU tensor with one element")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self._lib.nbc_nonfinite_peek_async(self._require_ctx(), host_word.data_ptr(), stream), "nbc_nonfinite_peek_async")
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_nonfinite_peek_async(self._require_ctx(), host_word.data_ptr(), cur.cuda_stream), "nbc_nonfinite_peek_async")
 
     def set_conv_tile(self, tile: int = -1):
         """Tuning/test knob: tile -1 = per-layer choice, 0..20 = one tile shape of the conv kernel (18 / 19 / 20: the row-resident 3x3
@@ -647,10 +611,9 @@ class FCNResNet50:
         n, h, w = self._check_input(x)
         x = x.contiguous()
         x_dtype = _lib.IN_F32_NCHW if x.dtype == torch.float32 else _lib.IN_U8_NHWC
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             _lib.check(self._lib.nbc_autotune(self._ctx, x.data_ptr(), x_dtype, n, h, w, int(reps),
-                                              1 if objective == "throughput" else 0, stream),
+                                              1 if objective == "throughput" else 0, cur.cuda_stream),
                        "nbc_autotune")
         return self.plan_tiles()
 
@@ -679,6 +642,42 @@ class FCNResNet50:
         return buf[: int(np.prod(shp))].reshape(shp)
 
     # ---- internals --------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _on_stream(self):
+        """Enters this model's device and yields the current stream there."""
+        with torch.cuda.device(self.device):
+            yield torch.cuda.current_stream(self.device)
+
+    def _grown_workspace(self, attr: str, need: int, stream) -> torch.Tensor:
+        """The workspace cached as ``self.<attr>``, grown (never shrunk) to ``need`` bytes; it may be used on several streams."""
+        ws = getattr(self, attr)
+        if ws is None or ws.numel() < need:
+            setattr(self, attr, None)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            setattr(self, attr, ws)
+        ws.record_stream(stream)
+        return ws
+
+    def _check_labels(self, labels: torch.Tensor):
+        if labels.device != self.device or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
+            raise ValueError("labels must be a contiguous uint8 or int64 tensor on %s" % (self.device,))
+
+    def _check_rgb_u8(self, image: torch.Tensor):
+        if image.device != self.device or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 \
+                or not image.is_contiguous():
+            raise ValueError("image must be a contiguous uint8 [H,W,3] tensor on %s" % (self.device,))
+
+    def _check_logits_target(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[int, int, int]:
+        """(N, H, W) of a contiguous f32 ``[N,3,H,W]`` and its contiguous uint8 ``[N,H,W]`` grey mask, both on this device."""
+        if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
+                or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES:
+            raise ValueError("logits_full must be a contiguous float32 [N,3,H,W] tensor on %s" % (self.device,))
+        n, _, h, w = (int(v) for v in logits_full.shape)
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous() \
+                or tuple(target.shape) != (n, h, w) or target.numel() == 0:
+            raise ValueError("target must be a contiguous uint8 [%d,%d,%d] tensor on %s" % (n, h, w, self.device))
+        return n, h, w
+
     def _require_ctx(self):
         if not self._ctx:
             raise RuntimeError("call .to('cuda[:i]') first")
@@ -736,10 +735,9 @@ class FCNResNet50:
         x_dtype = _lib.IN_F32_NCHW if x.dtype == torch.float32 else _lib.IN_U8_NHWC
         ldt = _lib.LABEL_I64 if (labels is None or labels.dtype == torch.int64) else _lib.LABEL_U8
         ptr = lambda t: (t.data_ptr() if t is not None else None)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with self._on_stream() as cur:
             rc = self._lib.nbc_forward(self._ctx, x.data_ptr(), x_dtype, n, h, w, ptr(lowres), ptr(logits_full),
-                                       ptr(labels), ldt, ptr(counts), int(bool(exclude_nodes)), stream)
+                                       ptr(labels), ldt, ptr(counts), int(bool(exclude_nodes)), cur.cuda_stream)
         _lib.check(rc, "nbc_forward")
         self._last_shape = (n, h, w)
 

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Do two builds of libnbc_hip.so compute the same bits from the same plan?  Per network, precision and BatchNorm mode, on a few
 seeded frames: full-resolution logits and labels, and what each build planned (op records without their timings, plan tiles).
-Exit status 1 on any difference.
+Then the per-image reduction passes on the same seeded inputs, every output buffer byte for byte: nbc_confusion (u8 and i64
+labels), nbc_image_moments and nbc_target_counts -- these three also on views that start 1, 5 and 17 bytes off a 16-byte
+boundary --, nbc_pixel_cross_entropy, nbc_lovasz_softmax, and dropout_draws (p = 0.1, low-resolution logits, small zones on
+and off, a short last pass) in the three precisions.  Exit status 1 on any difference.
   gpurun -- 'python scripts/ab_equal.py neuralbarkcalculator_amd/libnbc_hip.so tools/_bin/libnbc_x.so'"""
 import ctypes as C
 import os
@@ -24,11 +27,16 @@ CASES += [("fcn_efficientnet_b0", "fp32", "running", TWO), ("deeplabv3_efficient
 state_dicts = {}
 
 
-def model_on(path, arch, precision, bn):
+def lib_of(path):
     lib = C.CDLL(os.path.abspath(path))
     for name, (res, argtypes) in _lib.SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, argtypes
+    return lib
+
+
+def model_on(path, arch, precision, bn):
+    lib = lib_of(path)
     if arch not in state_dicts:
         state_dicts[arch] = synth.make_state_dict("trained_like", seed=7, arch=arch)
     keep = _lib._lib
@@ -59,6 +67,106 @@ for arch, precision, bn, shapes in CASES:
         print("%s %s bn=%s %s x %dx%d: %s (max |logit difference| %.3e), plans %s (%d ops, %d tiles)" %
               (arch, precision, bn, idx, h, w, "identical" if same else "DIFFERENT", float((la - lb).abs().max()),
                "equal" if pa == pb else "DIFFERENT", len(pa[0]), len(pa[1])), flush=True)
+    a._destroy()
+    b._destroy()
+
+# ---- the per-image reduction passes ----------------------------------------------------------------------------------
+PASS_SHAPES = ((2, 1024, 1024), (1, 520, 1024), (3, 203, 317))      # 203 x 317 is odd: planes off a 16-byte boundary
+OFFSETS = (0, 1, 5, 17)                                             # bytes (elements of the labels) off a 16-byte boundary
+gen = torch.Generator(device=dev).manual_seed(11)
+
+
+def off_view(t, off):
+    """A contiguous copy of `t` that starts `off` elements behind a 512-byte aligned allocation."""
+    buf = torch.empty(t.numel() + off, dtype=t.dtype, device=dev)
+    assert buf.data_ptr() % 16 == 0
+    v = buf[off:].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+def ok(lib, rc, what):
+    if rc != _lib.NBC_OK:
+        raise RuntimeError("%s: %s" % (what, lib.nbc_last_error().decode()))
+
+
+def byte_stream_passes(lib, n, h, w, off, rgb, grey, lab8, lab64, stream):
+    """outputs of the three byte-stream calls on inputs `off` bytes off; the last confusion has aligned targets and labels 3 off"""
+    out = {}
+    x, t, l8, l64 = off_view(rgb, off), off_view(grey, off), off_view(lab8, off), off_view(lab64, off)
+    for name, labels, dtype, target in (("confusion u8", l8, _lib.LABEL_U8, t), ("confusion i64", l64, _lib.LABEL_I64, t),
+                                        ("confusion u8, labels alone off", off_view(lab8, 3), _lib.LABEL_U8, off_view(grey, 0))):
+        conf = torch.full((n, 3, 3), -1, dtype=torch.int64, device=dev)
+        ok(lib, lib.nbc_confusion(labels.data_ptr(), dtype, target.data_ptr(), n, h, w, conf.data_ptr(), stream), name)
+        out[name] = conf
+    moments = torch.full((n, 6), -1, dtype=torch.int64, device=dev)
+    ok(lib, lib.nbc_image_moments(x.data_ptr(), n, h, w, moments.data_ptr(), stream), "nbc_image_moments")
+    counts = torch.full((n, 4), -1, dtype=torch.int64, device=dev)
+    ok(lib, lib.nbc_target_counts(t.data_ptr(), n, h, w, counts.data_ptr(), stream), "nbc_target_counts")
+    out["image_moments"], out["target_counts"] = moments, counts
+    return out
+
+
+def loss_passes(lib, n, h, w, logits, grey, stream):
+    out = {}
+    need = lib.nbc_pixel_ce_workspace_bytes(n, h, w)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    sums = torch.zeros((n, 3, 3), dtype=torch.float64, device=dev)
+    counts = torch.full((n, 3, 3), -1, dtype=torch.int64, device=dev)
+    ok(lib, lib.nbc_pixel_cross_entropy(logits.data_ptr(), grey.data_ptr(), n, h, w, ws.data_ptr(), need, sums.data_ptr(),
+                                        counts.data_ptr(), stream), "nbc_pixel_cross_entropy")
+    out["pixel_ce workspace bytes"], out["pixel_ce sums"], out["pixel_ce counts"] = torch.tensor([need]), sums, counts
+    need = lib.nbc_lovasz_workspace_bytes(n, h, w)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    terms = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    fg = torch.full((n, 3), -1, dtype=torch.int64, device=dev)
+    ok(lib, lib.nbc_lovasz_softmax(logits.data_ptr(), grey.data_ptr(), n, h, w, ws.data_ptr(), need, terms.data_ptr(), fg.data_ptr(),
+                                   stream), "nbc_lovasz_softmax")
+    out["lovasz workspace bytes"], out["lovasz terms"], out["lovasz fg_counts"] = torch.tensor([need]), terms, fg
+    return out
+
+
+def same_bytes(p, q):
+    return p.shape == q.shape and p.dtype == q.dtype and torch.equal(p.contiguous().view(torch.uint8), q.contiguous().view(torch.uint8))
+
+
+def compare(what, outs_a, outs_b):
+    diff = [k for k in outs_a if not same_bytes(outs_a[k], outs_b[k])]
+    print("%s: %s" % (what, "identical (%d buffers)" % len(outs_a) if not diff else "DIFFERENT in " + ", ".join(diff)), flush=True)
+    return len(diff)
+
+
+libs = [lib_of(p) for p in sys.argv[1:3]]
+stream = torch.cuda.current_stream(dev).cuda_stream
+for n, h, w in PASS_SHAPES:
+    rgb = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device=dev, generator=gen)
+    grey = torch.randint(0, 256, (n, h, w), dtype=torch.uint8, device=dev, generator=gen)
+    lab8 = torch.randint(0, 4, (n, h, w), dtype=torch.uint8, device=dev, generator=gen)      # 3: a label counted nowhere
+    lab64 = lab8.to(torch.int64)
+    logits = torch.randn((n, 3, h, w), device=dev, generator=gen) * 3
+    for off in OFFSETS:
+        outs = [byte_stream_passes(lib, n, h, w, off, rgb, grey, lab8, lab64, stream) for lib in libs]
+        torch.cuda.synchronize()
+        bad += compare("byte streams %dx%dx%d, %d off" % (n, h, w, off), *outs)
+    outs = [loss_passes(lib, n, h, w, logits, grey, stream) for lib in libs]
+    torch.cuda.synchronize()
+    bad += compare("losses %dx%dx%d" % (n, h, w), *outs)
+
+for precision in ("f16x2", "fp32", "bf16"):
+    a, b = (model_on(p, "fcn_resnet50", precision, "running") for p in sys.argv[1:3])
+    for n, h, w in PASS_SHAPES:
+        x = torch.from_numpy(np.stack([synth.make_input(i, h, w) for i in range(n)])).to(dev)
+        outs = []
+        for m in (a, b):
+            m.predict_labels(x, labels_dtype=torch.uint8)
+            o = {}
+            for zones in (True, False):                  # 5 draws in passes of 2: the last pass is shorter
+                counts, lowres = m.dropout_draws(5, [1000 + i for i in range(n)], p=0.1, seed=42, first_draw=3, small_zones=zones,
+                                                 return_lowres=True, draws_per_pass=2)
+                o["counts, small zones %s" % zones], o["lowres, small zones %s" % zones] = counts, lowres
+            outs.append(o)
+        torch.cuda.synchronize()
+        bad += compare("dropout_draws %s %dx%dx%d" % (precision, n, h, w), *outs)
     a._destroy()
     b._destroy()
 sys.exit(1 if bad else 0)
