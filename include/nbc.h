@@ -532,6 +532,14 @@ int nbc_nonfinite_seen(nbc_ctx* ctx, int reset);
 int nbc_nonfinite_peek_async(nbc_ctx* ctx, uint32_t* host_dst, void* hip_stream);
 
 /* ---- debugging / measurement ----------------------------------------------------------- */
+/* NBC_PREC_F16X2: the first bottleneck of a ResNet stage computes its downsample.0 inside the launch of the conv3 that
+ * adds it (one launch instead of two; the tensor between them is never written or read back) wherever conv3 has at most
+ * 8 K-steps (layer1.0, layer2.0, layer3.0) and runs on a tile that has the dual-branch form (17, 8, 10).  Same bits either way.
+ * On by default; off: two launches, as with keep-activations, profiling or NBC_BN_PER_IMAGE, and as in every other
+ * precision.  A switch for tests and A/B runs. */
+int nbc_set_fuse_downsample(nbc_ctx* ctx, int on);
+/* (downsample.0, conv3) pairs the last nbc_forward ran as one launch. */
+int nbc_fused_pairs(nbc_ctx* ctx);
 /* Copy the activation written by conv unit `name` during the last forward to `dst_host` as
  * float32 NCHW.  `capacity` is in elements.  Only valid when keep-activations is on. */
 int nbc_set_keep_activations(nbc_ctx* ctx, int on);

@@ -37,6 +37,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     headers.append(os.path.join(os.path.dirname(PKG), "include", "nbc.h"))
+    if not force and not _deps_newer(LIB, [os.path.join(CSRC, src) for src in SOURCES] + headers):
+        return LIB                      # the library is newer than every source and header: nothing to do, objects or not
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 
     def compile_one(src: str) -> str:

@@ -46,6 +46,8 @@ struct nbc_ctx {
   float* lowres = nullptr;
   size_t lowres_cap = 0;
   int conv_tile = -1;                       // tile override, -1 = per-layer choice
+  bool fuse_downsample = true;              // nbc_set_fuse_downsample
+  int fused_pairs = 0;                      // (downsample.0, conv3) pairs the last forward ran as one launch
   bool keep = false;
   bool profiling = false;
   // profiling: one event set (nops+1 events) per profiled forward, read back lazily so that the
@@ -100,6 +102,8 @@ void stash_plan(nbc_ctx* c) {
   cur = Plan();
 }
 
+bool downsample_pair(const nbc_ctx* c, const Plan& P, size_t l);
+
 // Workspace of the current plan: buffers only ever grow, so a plan taken back from the cache finds
 // them large enough unless a later, smaller-indexed plan never needed that slot.  A buffer that has to grow
 // grows by at least half (hipFree synchronises the device: shapes that rise one after the other then reallocate
@@ -107,16 +111,28 @@ void stash_plan(nbc_ctx* c) {
 int ensure_buffers(nbc_ctx* c) {
   const Plan& P = c->plan;
   if (c->bufs.size() < P.buf_bytes.size()) { c->bufs.resize(P.buf_bytes.size(), nullptr); c->buf_cap.resize(P.buf_bytes.size(), 0); }
+  // A fused (downsample.0, conv3) launch writes conv3's output where the plan put the downsample's -- the plan hands conv3 the
+  // buffer the downsample read, free by then in two launches and still being read in one -- and the two buffers then change
+  // places (nbc_forward).  The buffers that can change places are therefore all as large as the largest of them.
+  std::vector<size_t> need(P.buf_bytes);
+  {
+    std::vector<int> group;
+    size_t most = 0;
+    for (size_t l = 0; l + 1 < P.ops.size(); ++l)
+      if (downsample_pair(c, P, l))
+        for (int b : {P.ops[l].out_buf, P.ops[l + 1].out_buf}) { group.push_back(b); most = std::max(most, need[b]); }
+    for (int b : group) need[b] = most;
+  }
   for (size_t i = 0; i < P.buf_bytes.size(); ++i) {
-    if (c->buf_cap[i] < P.buf_bytes[i]) {
+    if (c->buf_cap[i] < need[i]) {
       const size_t grown = c->buf_cap[i] + c->buf_cap[i] / 2;
       if (c->bufs[i]) NBC_HIP(hipFree(c->bufs[i]));
       c->bufs[i] = nullptr; c->buf_cap[i] = 0;
-      size_t want = std::max(P.buf_bytes[i], grown);
+      size_t want = std::max(need[i], grown);
       hipError_t e = hipMalloc(&c->bufs[i], want);
-      if (e != hipSuccess && want > P.buf_bytes[i]) {          // no room for the margin: the exact size
+      if (e != hipSuccess && want > need[i]) {          // no room for the margin: the exact size
         (void)hipGetLastError();
-        want = P.buf_bytes[i];
+        want = need[i];
         e = hipMalloc(&c->bufs[i], want);
       }
       if (e != hipSuccess) return set_error(NBC_ERR_NOMEM, std::string("hipMalloc(workspace): ") + hipGetErrorString(e));
@@ -161,8 +177,9 @@ UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
           reinterpret_cast<const float*>(c->weights + pc.shift_off)};
 }
 
-// One convolution launch of the plan (shared by nbc_forward and nbc_autotune).
-int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipError_t* err) {
+// One convolution launch of the plan (shared by nbc_forward and nbc_autotune).  ds: the downsample.0 op whose output is this
+// op's identity, to be computed inside this launch (fusable_downsample below), or nullptr.
+int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipError_t* err, const Op* ds = nullptr) {
   const ConvUnit& u = conv_units(c->arch)[o.unit];
   const PackedConv& pc = c->layout.convs[o.unit];
   const UnitPtrs p = unit_ptrs(c, o.unit);
@@ -201,6 +218,25 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     return set_error(NBC_ERR_INVALID, "activation of " + o.name + " exceeds 2 GiB: lower the batch size");
   a.x_bytes = (unsigned)xb;
   a.w_bytes = (unsigned)wbts;
+  if (ds) {                                            // the identity branch's operands; the tensor between the two is never stored
+    const ConvUnit& u2 = conv_units(c->arch)[ds->unit];
+    const PackedConv& pc2 = c->layout.convs[ds->unit];
+    const UnitPtrs p2 = unit_ptrs(c, ds->unit);
+    const size_t xb2 = (size_t)N * ds->Hi * ds->Wi * ds->Ci * eb;
+    const size_t wb2 = (size_t)ds->Co * pc2.ksteps * kKStepBytes;
+    if (ds->Ci != pc2.cin_pad) return set_error(NBC_ERR_STATE, "plan/channel mismatch at " + ds->name);
+    if (xb2 >= 0x80000000ull || wb2 >= 0x80000000ull)
+      return set_error(NBC_ERR_INVALID, "activation of " + ds->name + " exceeds 2 GiB: lower the batch size");
+    a.res = nullptr;
+    a.y = c->bufs[ds->out_buf];                        // (the caller swaps the two buffers afterwards: see ensure_buffers)
+    a.x2 = c->bufs[ds->in_buf];
+    a.w2 = p2.w;
+    a.scale2 = p2.scale;
+    a.shift2 = p2.shift;
+    a.x2_bytes = (unsigned)xb2;
+    a.w2_bytes = (unsigned)wb2;
+    a.Ci2 = ds->Ci; a.Hi2 = ds->Hi; a.Wi2 = ds->Wi; a.stride2 = u2.stride; a.ksteps2 = pc2.ksteps;
+  }
   if (o.gate_buf >= 0) {                               // EfficientNet's project conv: image n on its SE-gated weights
     const size_t xi = (size_t)o.Hi * o.Wi * o.Ci * eb, yi = (size_t)o.Ho * o.Wo * o.Co * eb;
     a.N = 1;
@@ -218,6 +254,33 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
   }
   *err = launch_conv_dma(a, prec, tile, s);
   return NBC_OK;
+}
+
+// Whether op l of the plan is a stage-entry downsample.0 and op l + 1 the conv3 that reads its output as identity and could
+// compute it inside its own launch (the dual-branch form of the f16x2 kernel, conv_igemm_dma.hip): BatchNorm folded, nothing
+// else reading the tensor (keep-activations off), conv3 short enough to leave its second accumulator set free (<= 8 K-steps).
+bool downsample_pair(const nbc_ctx* c, const Plan& P, size_t l) {
+  if (c->precision != NBC_PREC_F16X2 || P.bn != NBC_BN_RUNNING || P.keep || l + 1 >= P.ops.size()) return false;
+  const Op& d = P.ops[l];
+  const Op& o = P.ops[l + 1];
+  if (d.kind != OP_CONV || o.kind != OP_CONV || d.raw || o.raw || d.gate_buf >= 0 || o.gate_buf >= 0) return false;
+  if (d.res_buf >= 0 || o.res_buf < 0 || o.res_buf != d.out_buf || o.rows != 0 || d.rows != 0) return false;
+  if (d.out_buf == d.in_buf || d.out_buf == o.in_buf || d.out_buf == o.out_buf) return false;
+  const auto& units = conv_units(c->arch);
+  const ConvUnit& ud = units[d.unit];
+  const ConvUnit& uo = units[o.unit];
+  static const std::string kSuffix = ".downsample.0";
+  if (ud.name.size() <= kSuffix.size() || ud.name.compare(ud.name.size() - kSuffix.size(), kSuffix.size(), kSuffix) != 0) return false;
+  if (ud.k != 1 || ud.pad != 0 || ud.relu || uo.k != 1 || uo.stride != 1 || uo.pad != 0) return false;
+  if (d.Ho != o.Ho || d.Wo != o.Wo || d.Co != o.Co || o.Hi != o.Ho || o.Wi != o.Wo) return false;
+  const PackedConv& pd = c->layout.convs[d.unit];
+  const PackedConv& po = c->layout.convs[o.unit];
+  return !pd.stem && !po.stem && po.ksteps <= 8;
+}
+// ... and does so in this forward: fusion on, one timed launch per op not asked for (profiling off), conv3 on a tile (`tile3`)
+// that has the form.
+bool fusable_downsample(const nbc_ctx* c, const Plan& P, size_t l, int tile3) {
+  return c->fuse_downsample && !c->profiling && downsample_pair(c, P, l) && conv_tile_has_dual(c->precision, tile3);
 }
 
 const char* kernel_name(OpKind k) {
@@ -478,6 +541,17 @@ int nbc_set_conv_tile(nbc_ctx* c, int tile) {
   return NBC_OK;
 }
 
+int nbc_set_fuse_downsample(nbc_ctx* c, int on) {
+  if (!c) return set_error(NBC_ERR_INVALID, "null context");
+  c->fuse_downsample = on != 0;
+  return NBC_OK;
+}
+
+int nbc_fused_pairs(nbc_ctx* c) {
+  if (!c) return set_error(NBC_ERR_INVALID, "null context");
+  return c->fused_pairs;
+}
+
 int nbc_set_keep_activations(nbc_ctx* c, int on) {
   if (!c) return set_error(NBC_ERR_INVALID, "null context");
   if (c->keep != (on != 0)) stash_plan(c);
@@ -581,6 +655,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   }
   float* lowres = logits_lowres_dev ? logits_lowres_dev : c->lowres;
 
+  c->fused_pairs = 0;
   if (evs) NBC_HIP(hipEventRecord((*evs)[0], s));
   for (size_t l = 0; l < nops; ++l) {
     const Op& o = P.ops[l];
@@ -594,11 +669,20 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
           e = launch_ingest_u8(static_cast<const uint8_t*>(x_dev), c->bufs[o.out_buf], N, H, W, c->mean, c->stdv, prec, s);
         break;
       case OP_CONV: {
-        int tile = c->conv_tile;
-        if (!conv_tile_ok(prec, tile, o.Co, o.rows)) tile = o.tile;   // no override, or it does not fit (a generic tile on a
-                                                                      // layer of the row-resident kernel, or the reverse): planned tile
-        rc = launch_conv_op(c, o, N, tile, s, &e);
+        const auto tile_of = [&](const Op& q) {
+          // no override, or it does not fit (a generic tile on a layer of the row-resident kernel, or the reverse): planned tile
+          return conv_tile_ok(prec, c->conv_tile, q.Co, q.rows) ? c->conv_tile : q.tile;
+        };
+        if (l + 1 < nops && P.ops[l + 1].kind == OP_CONV && fusable_downsample(c, P, l, tile_of(P.ops[l + 1])))
+          break;                                       // downsample.0: the next op's launch computes it
+        const Op* ds = l > 0 && fusable_downsample(c, P, l - 1, tile_of(o)) ? &P.ops[l - 1] : nullptr;
+        rc = launch_conv_op(c, o, N, tile_of(o), s, &e, ds);
         if (rc != NBC_OK) return rc;
+        if (ds && e == hipSuccess) {
+          ++c->fused_pairs;
+          std::swap(c->bufs[o.out_buf], c->bufs[ds->out_buf]);
+          std::swap(c->buf_cap[o.out_buf], c->buf_cap[ds->out_buf]);
+        }
         break;
       }
       case OP_MAXPOOL:

@@ -28,6 +28,15 @@ struct ConvArgs {
   int stem;             // one 16-byte chunk per tap (Ci*elem == 16 bytes)
   int wo_shift;         // log2(Wo) when Wo is a power of two, else -1
   int hw_shift;         // log2(Ho*Wo) when it is a power of two, else -1 (batches: image index without a division)
+  // Dual-branch launch (f16x2; x2 != nullptr): this convolution is a 1x1, stride 1, unpadded conv3 of at most 8 K-steps with
+  // res == nullptr, and its identity is computed in the same block by a 1x1 convolution (padding 0, no ReLU: downsample.0)
+  // of x2 onto the same Ho x Wo x Co map -- see kVarDualBranch in conv_igemm_dma.hip.
+  const void* x2;       // [N][Hi2][Wi2][Ci2] elements
+  const void* w2;       // [Co][ksteps2*128 bytes]
+  const float* scale2;  // [Co]
+  const float* shift2;  // [Co]
+  unsigned x2_bytes, w2_bytes;
+  int Ci2, Hi2, Wi2, stride2, ksteps2;
 #ifdef NBC_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/conv_timeline.hip): 8 stamps per block
 #endif
@@ -45,6 +54,7 @@ int conv_tile_cols(int tile);
 // tiles 0 .. 17 only.
 int conv_rows_kind(int precision, int k, int stride, int pad, int dil, int Hi, int Wi, int Ho, int Wo, int Ci, int Co, bool has_res);
 bool conv_tile_ok(int precision, int tile, int Co, int rows_kind);   // the tile exists for the precision and the kind of convolution and divides Co
+bool conv_tile_has_dual(int precision, int tile);   // the tile has the dual-branch form (ConvArgs::x2)
 // K = Cin*kh*kw; the default tile of a layer (cost model); rows_kind: conv_rows_kind
 int choose_conv_tile(int M, int Co, int K, int precision, int rows_kind);
 hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream_t s);

@@ -595,6 +595,18 @@ class FCNResNet50:
         with self._on_stream() as cur:
             _lib.check(self._lib.nbc_nonfinite_peek_async(self._require_ctx(), host_word.data_ptr(), cur.cuda_stream), "nbc_nonfinite_peek_async")
 
+    def set_fuse_downsample(self, on: bool = True):
+        """Test / A-B switch (f16x2): whether downsample.0 of a stage's first bottleneck runs inside the launch of the conv3
+        that adds it (include/nbc.h, nbc_set_fuse_downsample; default on, same bits either way)."""
+        _lib.check(self._lib.nbc_set_fuse_downsample(self._require_ctx(), int(on)), "nbc_set_fuse_downsample")
+
+    def fused_pairs(self) -> int:
+        """(downsample.0, conv3) pairs the last forward ran as one launch."""
+        n = self._lib.nbc_fused_pairs(self._require_ctx())
+        if n < 0:
+            _lib.check(n, "nbc_fused_pairs")
+        return int(n)
+
     def set_conv_tile(self, tile: int = -1):
         """Tuning/test knob: tile -1 = per-layer choice, 0..20 = one tile shape of the conv kernel (18 / 19 / 20: the row-resident 3x3
         kernel of f16x2, which its layers never leave; the menu:
