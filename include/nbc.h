@@ -294,6 +294,16 @@ int nbc_set_normalization(nbc_ctx* ctx, const float mean[3], const float std[3])
  * growth frees and reallocates (which synchronises the device): a caller that will see many shapes reserves the
  * largest one first, as the folder driver does. */
 int nbc_reserve(nbc_ctx* ctx, int N, int H, int W);
+/* The launch plan nbc_reserve would build for such a context, as text (host only, no context, no device call), one line per
+ * op in launch order and then one per activation buffer:
+ *   op <name> <kernel> [in=B] [out=B] [res=B] [ws=B] [gate=B] [cat=B x 5] [tile=T] launches=L [ds=<name>]
+ *   buf <index> <bytes> [identity]
+ * B: buffer indices (a field the op does not use is left out); ds: on the conv3 of a (downsample.0, conv3) pair, the
+ * downsample op in front of it (nbc_set_fuse_downsample); identity: the buffer outside the recycled pool that the downsamples
+ * of the pairs write when they run in a launch of their own.  Returns the bytes the text needs with its terminating 0; at
+ * most `capacity` are written (text may be null).  NBC_ERR_INVALID for what nbc_attach_weights_arch, nbc_set_bn_statistics or
+ * nbc_reserve refuse, with nbc_reserve's message for an image the network cannot run on. */
+int nbc_describe_plan(int arch, int precision, int N, int H, int W, int keep, int bn_mode, char* text, size_t capacity);
 
 /* ---- the hot path ------------------------------------------------------------------------
  * x_dev                 device pointer, layout per x_dtype
@@ -536,7 +546,9 @@ int nbc_nonfinite_peek_async(nbc_ctx* ctx, uint32_t* host_dst, void* hip_stream)
  * adds it (one launch instead of two; the tensor between them is never written or read back) wherever conv3 has at most
  * 8 K-steps (layer1.0, layer2.0, layer3.0) and runs on a tile that has the dual-branch form (17, 8, 10).  Same bits either way.
  * On by default; off: two launches, as with keep-activations, profiling or NBC_BN_PER_IMAGE, and as in every other
- * precision.  A switch for tests and A/B runs. */
+ * precision.  The plan marks the pairs and gives them buffers that serve both forms (nbc_describe_plan); the identity buffer,
+ * which only the two-launch form uses, is allocated by the first forward that runs a pair that way (that forward
+ * synchronises the device, as one of a larger shape does).  A switch for tests and A/B runs. */
 int nbc_set_fuse_downsample(nbc_ctx* ctx, int on);
 /* (downsample.0, conv3) pairs the last nbc_forward ran as one launch. */
 int nbc_fused_pairs(nbc_ctx* ctx);

@@ -102,43 +102,37 @@ void stash_plan(nbc_ctx* c) {
   cur = Plan();
 }
 
-bool downsample_pair(const nbc_ctx* c, const Plan& P, size_t l);
+// Room for buffer i of the current plan.  Buffers only ever grow; one that has to grow grows by at least half (hipFree
+// synchronises the device: shapes that rise one after the other then reallocate O(log) times, not once per shape).
+int ensure_buffer(nbc_ctx* c, int i) {
+  const size_t need = c->plan.buf_bytes[i];
+  if (c->buf_cap[i] >= need) return NBC_OK;
+  const size_t grown = c->buf_cap[i] + c->buf_cap[i] / 2;
+  if (c->bufs[i]) NBC_HIP(hipFree(c->bufs[i]));
+  c->bufs[i] = nullptr; c->buf_cap[i] = 0;
+  size_t want = std::max(need, grown);
+  hipError_t e = hipMalloc(&c->bufs[i], want);
+  if (e != hipSuccess && want > need) {                // no room for the margin: the exact size
+    (void)hipGetLastError();
+    want = need;
+    e = hipMalloc(&c->bufs[i], want);
+  }
+  if (e != hipSuccess) return set_error(NBC_ERR_NOMEM, std::string("hipMalloc(workspace): ") + hipGetErrorString(e));
+  c->buf_cap[i] = want;
+  return NBC_OK;
+}
 
-// Workspace of the current plan: buffers only ever grow, so a plan taken back from the cache finds
-// them large enough unless a later, smaller-indexed plan never needed that slot.  A buffer that has to grow
-// grows by at least half (hipFree synchronises the device: shapes that rise one after the other then reallocate
-// O(log) times, not once per shape); a caller that knows its largest shape reserves it first (nbc_reserve).
+// Workspace of the current plan: a plan taken back from the cache finds its buffers large enough unless a later,
+// smaller-indexed plan never needed that slot; a caller that knows its largest shape reserves it first (nbc_reserve).  The
+// identity buffer is left to the first launch that writes it (launch_conv_op): the default path never does.
 int ensure_buffers(nbc_ctx* c) {
   const Plan& P = c->plan;
   if (c->bufs.size() < P.buf_bytes.size()) { c->bufs.resize(P.buf_bytes.size(), nullptr); c->buf_cap.resize(P.buf_bytes.size(), 0); }
-  // A fused (downsample.0, conv3) launch writes conv3's output where the plan put the downsample's -- the plan hands conv3 the
-  // buffer the downsample read, free by then in two launches and still being read in one -- and the two buffers then change
-  // places (nbc_forward).  The buffers that can change places are therefore all as large as the largest of them.
-  std::vector<size_t> need(P.buf_bytes);
-  {
-    std::vector<int> group;
-    size_t most = 0;
-    for (size_t l = 0; l + 1 < P.ops.size(); ++l)
-      if (downsample_pair(c, P, l))
-        for (int b : {P.ops[l].out_buf, P.ops[l + 1].out_buf}) { group.push_back(b); most = std::max(most, need[b]); }
-    for (int b : group) need[b] = most;
-  }
-  for (size_t i = 0; i < P.buf_bytes.size(); ++i) {
-    if (c->buf_cap[i] < need[i]) {
-      const size_t grown = c->buf_cap[i] + c->buf_cap[i] / 2;
-      if (c->bufs[i]) NBC_HIP(hipFree(c->bufs[i]));
-      c->bufs[i] = nullptr; c->buf_cap[i] = 0;
-      size_t want = std::max(need[i], grown);
-      hipError_t e = hipMalloc(&c->bufs[i], want);
-      if (e != hipSuccess && want > need[i]) {          // no room for the margin: the exact size
-        (void)hipGetLastError();
-        want = need[i];
-        e = hipMalloc(&c->bufs[i], want);
-      }
-      if (e != hipSuccess) return set_error(NBC_ERR_NOMEM, std::string("hipMalloc(workspace): ") + hipGetErrorString(e));
-      c->buf_cap[i] = want;
+  for (int i = 0; i < (int)P.buf_bytes.size(); ++i)
+    if (i != P.identity_buf) {
+      const int rc = ensure_buffer(c, i);
+      if (rc != NBC_OK) return rc;
     }
-  }
   if (P.bn == NBC_BN_PER_IMAGE) {
     if (!c->bn_unit) {
       std::vector<float> unit(4096, 0.f);
@@ -178,7 +172,10 @@ UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
 }
 
 // One convolution launch of the plan (shared by nbc_forward and nbc_autotune).  ds: the downsample.0 op whose output is this
-// op's identity, to be computed inside this launch (fusable_downsample below), or nullptr.
+// op's identity, to be computed inside this launch (fusable_downsample below), or nullptr.  A downsample.0 of a pair that runs
+// in a launch of its own finds the identity buffer here, allocated or grown on first use: that frees and allocates, so it
+// synchronises the device as a change of shape does -- once per context and size, and only where the pair runs as two
+// launches (the A/B switch, profiling, autotune, a forced or tuned tile without the dual-branch form).
 int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipError_t* err, const Op* ds = nullptr) {
   const ConvUnit& u = conv_units(c->arch)[o.unit];
   const PackedConv& pc = c->layout.convs[o.unit];
@@ -196,6 +193,10 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     a.scale = c->bn_unit;
     a.shift = c->bn_unit + 2048;
     a.res = nullptr;
+  }
+  if (o.out_buf == c->plan.identity_buf) {
+    const int rc = ensure_buffer(c, o.out_buf);
+    if (rc != NBC_OK) return rc;
   }
   a.y = c->bufs[o.out_buf];
   a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.Ci = o.Ci;
@@ -228,7 +229,6 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     if (xb2 >= 0x80000000ull || wb2 >= 0x80000000ull)
       return set_error(NBC_ERR_INVALID, "activation of " + ds->name + " exceeds 2 GiB: lower the batch size");
     a.res = nullptr;
-    a.y = c->bufs[ds->out_buf];                        // (the caller swaps the two buffers afterwards: see ensure_buffers)
     a.x2 = c->bufs[ds->in_buf];
     a.w2 = p2.w;
     a.scale2 = p2.scale;
@@ -256,31 +256,11 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
   return NBC_OK;
 }
 
-// Whether op l of the plan is a stage-entry downsample.0 and op l + 1 the conv3 that reads its output as identity and could
-// compute it inside its own launch (the dual-branch form of the f16x2 kernel, conv_igemm_dma.hip): BatchNorm folded, nothing
-// else reading the tensor (keep-activations off), conv3 short enough to leave its second accumulator set free (<= 8 K-steps).
-bool downsample_pair(const nbc_ctx* c, const Plan& P, size_t l) {
-  if (c->precision != NBC_PREC_F16X2 || P.bn != NBC_BN_RUNNING || P.keep || l + 1 >= P.ops.size()) return false;
-  const Op& d = P.ops[l];
-  const Op& o = P.ops[l + 1];
-  if (d.kind != OP_CONV || o.kind != OP_CONV || d.raw || o.raw || d.gate_buf >= 0 || o.gate_buf >= 0) return false;
-  if (d.res_buf >= 0 || o.res_buf < 0 || o.res_buf != d.out_buf || o.rows != 0 || d.rows != 0) return false;
-  if (d.out_buf == d.in_buf || d.out_buf == o.in_buf || d.out_buf == o.out_buf) return false;
-  const auto& units = conv_units(c->arch);
-  const ConvUnit& ud = units[d.unit];
-  const ConvUnit& uo = units[o.unit];
-  static const std::string kSuffix = ".downsample.0";
-  if (ud.name.size() <= kSuffix.size() || ud.name.compare(ud.name.size() - kSuffix.size(), kSuffix.size(), kSuffix) != 0) return false;
-  if (ud.k != 1 || ud.pad != 0 || ud.relu || uo.k != 1 || uo.stride != 1 || uo.pad != 0) return false;
-  if (d.Ho != o.Ho || d.Wo != o.Wo || d.Co != o.Co || o.Hi != o.Ho || o.Wi != o.Wo) return false;
-  const PackedConv& pd = c->layout.convs[d.unit];
-  const PackedConv& po = c->layout.convs[o.unit];
-  return !pd.stem && !po.stem && po.ksteps <= 8;
-}
-// ... and does so in this forward: fusion on, one timed launch per op not asked for (profiling off), conv3 on a tile (`tile3`)
-// that has the form.
-bool fusable_downsample(const nbc_ctx* c, const Plan& P, size_t l, int tile3) {
-  return c->fuse_downsample && !c->profiling && downsample_pair(c, P, l) && conv_tile_has_dual(c->precision, tile3);
+// Whether `conv3` is the conv3 of a (downsample.0, conv3) pair of the plan (Op::ds_op) that computes the downsample inside its
+// own launch in this forward: fusion on, one timed launch per op not asked for (profiling off), conv3 on a tile (`tile3`) that
+// has the dual-branch form.
+bool fusable_downsample(const nbc_ctx* c, const Op& conv3, int tile3) {
+  return conv3.ds_op >= 0 && c->fuse_downsample && !c->profiling && conv_tile_has_dual(c->precision, tile3);
 }
 
 const char* kernel_name(OpKind k) {
@@ -620,6 +600,38 @@ int nbc_reserve(nbc_ctx* c, int N, int H, int W) {
   return rc;
 }
 
+int nbc_describe_plan(int arch, int precision, int N, int H, int W, int keep, int bn_mode, char* text, size_t capacity) {
+  if (!known_arch(arch) || !known_precision(precision) || (is_effnet(arch) && precision != NBC_PREC_FP32))
+    return set_error(NBC_ERR_INVALID, "nbc_describe_plan: unknown architecture or precision, or one the architecture does not run in");
+  if (N < 1 || H < 8 || W < 8) return set_error(NBC_ERR_INVALID, "nbc_describe_plan: need N>=1, H>=8, W>=8");
+  if (bn_mode != NBC_BN_RUNNING && (bn_mode != NBC_BN_PER_IMAGE || precision != NBC_PREC_FP32 || arch != kArchFcn))
+    return set_error(NBC_ERR_INVALID, "nbc_describe_plan: per-image BatchNorm statistics need NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50");
+  PlanKey key;
+  key.N = N; key.H = H; key.W = W; key.precision = precision; key.arch = arch; key.keep = keep != 0; key.bn = bn_mode;
+  Plan P;
+  const std::string refused = build_plan(key, &P);
+  if (!refused.empty()) return set_error(NBC_ERR_INVALID, refused);
+  std::string out;
+  const auto field = [&](const char* what, int v) { if (v >= 0) out += std::string(" ") + what + "=" + std::to_string(v); };
+  for (const Op& o : P.ops) {
+    out += "op " + o.name + " " + kernel_name(o.kind);
+    field("in", o.in_buf); field("out", o.out_buf); field("res", o.res_buf); field("ws", o.ws_buf); field("gate", o.gate_buf);
+    for (int b : o.cat_in) field("cat", b);
+    if (o.kind == OP_CONV) field("tile", o.tile);
+    field("launches", o.launches);
+    if (o.ds_op >= 0) out += " ds=" + P.ops[o.ds_op].name;
+    out += "\n";
+  }
+  for (size_t i = 0; i < P.buf_bytes.size(); ++i)
+    out += "buf " + std::to_string(i) + " " + std::to_string(P.buf_bytes[i]) + ((int)i == P.identity_buf ? " identity\n" : "\n");
+  if (text && capacity > 0) {
+    const size_t n = std::min(out.size(), capacity - 1);
+    std::memcpy(text, out.data(), n);
+    text[n] = 0;
+  }
+  return (int)out.size() + 1;
+}
+
 int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
                 float* logits_lowres_dev, float* logits_full_dev, void* labels_dev, int labels_dtype,
                 int64_t* counts_dev, int exclude_nodes, void* hip_stream) {
@@ -673,16 +685,12 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
           // no override, or it does not fit (a generic tile on a layer of the row-resident kernel, or the reverse): planned tile
           return conv_tile_ok(prec, c->conv_tile, q.Co, q.rows) ? c->conv_tile : q.tile;
         };
-        if (l + 1 < nops && P.ops[l + 1].kind == OP_CONV && fusable_downsample(c, P, l, tile_of(P.ops[l + 1])))
+        if (l + 1 < nops && P.ops[l + 1].ds_op == (int)l && fusable_downsample(c, P.ops[l + 1], tile_of(P.ops[l + 1])))
           break;                                       // downsample.0: the next op's launch computes it
-        const Op* ds = l > 0 && fusable_downsample(c, P, l - 1, tile_of(o)) ? &P.ops[l - 1] : nullptr;
+        const Op* ds = fusable_downsample(c, o, tile_of(o)) ? &P.ops[o.ds_op] : nullptr;
         rc = launch_conv_op(c, o, N, tile_of(o), s, &e, ds);
         if (rc != NBC_OK) return rc;
-        if (ds && e == hipSuccess) {
-          ++c->fused_pairs;
-          std::swap(c->bufs[o.out_buf], c->bufs[ds->out_buf]);
-          std::swap(c->buf_cap[o.out_buf], c->buf_cap[ds->out_buf]);
-        }
+        if (ds && e == hipSuccess) ++c->fused_pairs;
         break;
       }
       case OP_MAXPOOL:
@@ -812,8 +820,7 @@ static int collect_profile(nbc_ctx* c) {
     std::snprintf(r.kernel, sizeof(r.kernel), "%s", kernel_name(o.kind));
     r.ms = (float)(sum[i] / (double)c->prof_used);
     r.calls = (int32_t)c->prof_used;
-    r.launches = o.kind == OP_ASPP_POOL ? 3 : (o.kind == OP_BN_STATS ? 2 : o.launches);   // aspp: partial sums, their sum, the 1x1 conv;
-                                                                                   // bn_stats: partial sums, their sum + the table
+    r.launches = o.launches;
     r.flops = o.flops;
     r.bytes = o.bytes;
     r.kh = r.kw = (o.kind == OP_CONV || o.kind == OP_HEAD1X1) ? units[o.unit].k : 0;

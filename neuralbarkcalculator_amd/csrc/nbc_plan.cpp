@@ -38,6 +38,13 @@ struct Builder {
     return (int)in_use.size() - 1;
   }
   void release(int b) { if (b >= 0 && !P.keep) in_use[b] = false; }
+  // The one buffer outside the pool, which the pairs of a plan share: the identity between downsample.0 and the conv3 of its
+  // pair when the two run as two launches (resnet50_trunk).  Never released, so no other op is given it.
+  int identity(size_t bytes) {
+    if (P.identity_buf < 0) { in_use.push_back(true); P.buf_bytes.push_back(0); P.identity_buf = (int)in_use.size() - 1; }
+    P.buf_bytes[P.identity_buf] = std::max(P.buf_bytes[P.identity_buf], bytes);
+    return P.identity_buf;
+  }
 
   // image -> NHWC with one 16-byte pixel
   Tensor ingest(int creal) {
@@ -61,8 +68,8 @@ struct Builder {
   }
 
   // A conv_dma launch of unit ui; gate_buf >= 0: per image on the gated weights.  In NBC_BN_PER_IMAGE a unit with a BatchNorm
-  // is the raw conv, then <bn>.stats and <bn>.apply (with the identity).
-  Tensor add_conv(int ui, const Tensor& in, int res_buf = -1, int gate_buf = -1) {
+  // is the raw conv, then <bn>.stats and <bn>.apply (with the identity).  to_identity: the output goes to the identity buffer.
+  Tensor add_conv(int ui, const Tensor& in, int res_buf = -1, int gate_buf = -1, bool to_identity = false) {
     const ConvUnit& u = units[ui];
     int Ho, Wo;
     out_size(u, in, &Ho, &Wo);
@@ -73,7 +80,8 @@ struct Builder {
     o.kind = OP_CONV; o.unit = ui; o.in_buf = in.buf; o.res_buf = res_buf; o.gate_buf = gate_buf; o.raw = bn_ops;
     o.Hi = in.H; o.Wi = in.W; o.Ci = in.C; o.Ho = Ho; o.Wo = Wo; o.Co = u.outc(); o.name = u.name;
     o.creal = u.cout_pad ? u.cout : 0;                               // EfficientNet pads its channels, ResNet-50 does not
-    o.out_buf = acquire((size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * u.outc() * eb);
+    const size_t out_bytes = (size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * u.outc() * eb;
+    o.out_buf = to_identity ? identity(out_bytes) : acquire(out_bytes);
     o.rows = conv_rows_kind(P.precision, u.k, u.stride, u.pad, u.dil, in.H, in.W, Ho, Wo, in.C, u.outc(), res_buf >= 0);
     // the tile's K and the bytes count the unit's channels (ResNet-50's stem: the 3 real ones of the 16-byte pixel)
     const int images = gate_buf >= 0 ? 1 : N;                        // per launch
@@ -93,6 +101,7 @@ struct Builder {
       Op st = o;
       st.kind = OP_BN_STATS; st.in_buf = o.out_buf; st.res_buf = -1; st.raw = false; st.name = u.bn + ".stats";
       st.affine_off = affine_off[ui];
+      st.launches = 2;                                                 // partial sums, then their sum and the table
       st.flops = 3.0 * M * u.cout;
       st.bytes = M * u.cout * 4.0 + (double)N * bn_stats_slices(hw) * u.cout * 16.0;
       P.ops.push_back(st);
@@ -130,14 +139,23 @@ struct Builder {
       const Tensor t2 = add_conv(ui + 1, t1);
       release(t1.buf);
       int idt = cur.buf, c3 = ui + 2;
+      bool pair = false;
       if (!units[ui + 2].residual) {      // downsample present
-        idt = add_conv(ui + 2, cur).buf;
-        release(cur.buf);
         c3 = ui + 3;
+        // A (downsample.0, conv3) pair, which a forward may run as one launch (the dual-branch form of the f16x2 kernel,
+        // conv_igemm_dma.hip): BatchNorm folded, nothing else reading the identity (keep-activations off), conv3 short enough
+        // to leave its second accumulator set free (<= 8 K-steps).  Its buffers serve both forms: the block's input, which
+        // the one launch reads, stays acquired until conv3 has its output buffer, and the identity, which only the two
+        // launches write and read, lies outside the pool.
+        const ConvUnit& u3 = units[c3];
+        pair = P.precision == NBC_PREC_F16X2 && P.bn == NBC_BN_RUNNING && !P.keep && u3.inc() * u3.k * u3.k * eb / kKStepBytes <= 8;
+        idt = add_conv(ui + 2, cur, -1, -1, pair).buf;
+        if (!pair) release(cur.buf);
       }
       const Tensor out = add_conv(c3, t2, idt);
+      if (pair) P.ops.back().ds_op = (int)P.ops.size() - 2;
       release(t2.buf);
-      release(idt);
+      release(pair ? cur.buf : idt);
       cur = out;
       ui = c3 + 1;
     }
@@ -237,7 +255,7 @@ struct Builder {
       po.Hi = cur.H; po.Wi = cur.W; po.Ci = pu.cin; po.Ho = 1; po.Wo = 1; po.Co = B;
       po.name = "classifier.0.convs.4";                                      // the pooled vector: one pixel per image
       po.out_buf = acquire((size_t)N * B * eb);
-      po.launches = pool == OP_POOL_ANY ? 2 : 1;
+      po.launches = pool == OP_POOL_ANY ? 2 : 3;                             // OP_ASPP_POOL: partial sums, their sum, the 1x1 conv
       po.flops = 2.0 * N * B * pu.cin + (double)N * hw * pu.cin;
       po.bytes = (double)N * hw * pu.cin * eb + (double)B * pu.cin * 4 + (double)N * B * eb;
       P.ops.push_back(po);

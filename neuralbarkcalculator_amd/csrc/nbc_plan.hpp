@@ -34,6 +34,7 @@ struct Op {
   int launches = 1;    // launches of the op per forward (profiling records)
   int tiles = 0;       // OP_DWCONV / OP_SE_EXCITE: SE squeeze partials per image
   int aux_unit = -1;   // OP_SE_EXCITE: the _se_expand unit (unit = _se_reduce); OP_GATE_WEIGHTS: the project unit
+  int ds_op = -1;      // OP_CONV, conv3 of a (downsample.0, conv3) pair: index of the downsample op, which is the op before it
 };
 
 // Everything a plan depends on.
@@ -52,6 +53,7 @@ struct Plan : PlanKey {
   int h = 0, w = 0;                    // low-res logits size
   std::vector<Op> ops;
   std::vector<size_t> buf_bytes;       // per activation buffer
+  int identity_buf = -1;               // the buffer outside the pool that the downsample of every pair writes (-1: no pair)
 };
 
 // The launch list of `key` into *out, or the reason why this network cannot run on such an image (*out is then left alone).

@@ -117,6 +117,19 @@ def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
     return topology.arch_name(rc)
 
 
+def describe_plan(arch: str, precision: str, n: int, h: int, w: int, keep: bool = False, bn_statistics: str = "running") -> str:
+    """The launch plan of an [n, 3, h, w] forward as text (nbc_describe_plan; host only: no context, no GPU); ``RuntimeError``
+    for what the library refuses."""
+    lib = _lib.load()
+    args = (topology.arch_index(arch), _PRECISIONS[precision], n, h, w, int(keep), BN_STATISTICS[bn_statistics])
+    need = lib.nbc_describe_plan(*args, None, 0)
+    if need < 0:
+        _lib.check(need, "nbc_describe_plan")
+    buf = C.create_string_buffer(need)
+    lib.nbc_describe_plan(*args, buf, need)
+    return buf.value.decode()
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 

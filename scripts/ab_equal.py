@@ -30,7 +30,9 @@ state_dicts = {}
 def lib_of(path):
     lib = C.CDLL(os.path.abspath(path))
     for name, (res, argtypes) in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:                                   # a build of an older revision: calls added since are not made here
+            continue
         fn.restype, fn.argtypes = res, argtypes
     return lib
 

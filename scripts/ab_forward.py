@@ -2,6 +2,8 @@
 """Whole-forward A/B of library builds in ONE process on one box: images/s of the headline configuration (f16x2, batch 1,
 `--streams` forwards in flight, default tiles) for two or more builds of libnbc_hip.so, rounds interleaved, every
 measurement on models of its own (scripts/ab_tiles.py measures per layer on one stream; this is the bench's region).
+--memory: afterwards, per build, the device bytes one fresh context takes with its first forward (torch.cuda.mem_get_info
+around it, weights uploaded before), and what a following forward with set_fuse_downsample(False) adds.
   gpurun -- 'python scripts/ab_forward.py --libs tools/_bin/libnbc_base.so neuralbarkcalculator_amd/libnbc_hip.so'"""
 import argparse
 import ctypes as C
@@ -23,13 +25,14 @@ ap.add_argument("--streams", type=int, default=2)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--steps", type=int, default=60)
 ap.add_argument("--frames", type=int, default=8)
+ap.add_argument("--memory", action="store_true")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 sd = synth.make_state_dict("trained_like", seed=7)
 xs = [torch.from_numpy(np.stack([synth.make_input(i * args.batch + j, 1024, 1024) for j in range(args.batch)])).to(dev) for i in range(args.frames)]
 
 
-def models_on(path):
+def models_on(path, reserve=True):
     lib = C.CDLL(os.path.abspath(path))
     for name, (res, argtypes) in _lib.SIGNATURES.items():
         fn = getattr(lib, name, None)
@@ -44,7 +47,8 @@ def models_on(path):
     finally:
         _lib._lib = keep if keep is not None else lib
     for q in ms:
-        q.reserve(args.batch, 1024, 1024)
+        if reserve:
+            q.reserve(args.batch, 1024, 1024)
     return ms
 
 
@@ -74,3 +78,24 @@ for k, p in enumerate(args.libs):
 base = float(np.median(res[0]))
 for k in range(1, len(args.libs)):
     print("%s vs %s: %+.2f %%" % (os.path.basename(args.libs[k]), os.path.basename(args.libs[0]), 100 * (float(np.median(res[k])) / base - 1)))
+
+if args.memory:
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(dev)[0]
+
+    for p in args.libs:
+        ms = models_on(p, reserve=False)
+        for q in ms[1:]:
+            q._destroy()
+        m = ms[0]
+        before = free_bytes()
+        m.predict_labels(xs[0], labels_dtype=torch.uint8)
+        pairs = m.fused_pairs()
+        first = free_bytes()
+        m.set_fuse_downsample(False)
+        m.predict_labels(xs[0], labels_dtype=torch.uint8)
+        unfused = free_bytes()
+        print("%-28s device bytes one context takes with its first forward: %d; more with a set_fuse_downsample(False) "
+              "forward: %d  (the first forward fused %d pairs)" % (os.path.basename(p), before - first, first - unfused, pairs))
+        m._destroy()

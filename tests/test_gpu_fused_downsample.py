@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from neuralbarkcalculator_amd import synth
-from neuralbarkcalculator_amd.model import FCNResNet50
+from neuralbarkcalculator_amd.model import FCNResNet50, describe_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -67,8 +67,8 @@ def test_fused_equals_two_launches_bit_for_bit(model, shape, nan_pixel):
 def test_fused_at_the_full_size_tile(model, shape):
     """Tile 17 (the three layers' tile at 1024x1024) forced: fused and two-launch forms agree on a small batch and on an
     image with more blocks than the chip holds at once (layer1: 520 tiles), where a block finishes while others have not
-    started -- the fused launch must not write where a later block still reads (the plan gives conv3 the buffer the
-    downsample read)."""
+    started -- the fused launch must not write where a later block still reads (the plan gives conv3 a buffer that is
+    neither its own input nor the downsample's)."""
     n, h, w = shape
     x = frames(range(61, 61 + n), h, w).to(DEV)
     model.set_conv_tile(17)
@@ -155,3 +155,70 @@ def test_two_fused_forwards_at_once_are_deterministic(model):
         labels, counts, lowres = outs[k]
         assert torch.equal(labels, alone[k][0]) and torch.equal(counts, alone[k][1])
         assert torch.equal(bits(lowres), bits(alone[k][2])), f"stream {k} differs from the same frame alone"
+
+
+DUAL_TILES = (17, 8, 10)     # conv_tile_has_dual of the f16x2 kernel (csrc/conv_igemm_dma.hip)
+
+
+def test_the_two_forms_alternate_across_shapes_and_the_plan_cache(model):
+    """One context, three shapes, each in both forms and out of the plan cache in the other one; whatever form ran before,
+    every result is that of a fresh context in the default form.  The identity buffer, which only the two-launch form uses,
+    is first allocated in the second step (1.25 MB, enough for the next two two-launch steps) and has to grow in the last
+    one (3 x 6 x 256 pixels x 256 channels: 4.7 MB)."""
+    steps = [((1, 40, 72), True), ((2, 72, 136), False), ((1, 40, 72), False), ((1, 128, 128), True), ((2, 72, 136), True),
+             ((1, 128, 128), False), ((3, 24, 1024), False)]
+    xs = {shape: frames(range(80, 80 + shape[0]), *shape[1:]).to(DEV) for shape, _ in steps}
+    want = {}
+    for shape, x in xs.items():
+        fresh = model.clone_shared()
+        want[shape] = run(fresh, x)
+        fresh._destroy()
+        assert want[shape][3] == 3 and torch.isfinite(want[shape][2]).all()
+    m = model.clone_shared()
+    try:
+        for shape, fuse in steps:
+            m.set_fuse_downsample(fuse)
+            labels, counts, lowres, pairs = run(m, xs[shape])
+            assert pairs == (3 if fuse else 0), (shape, fuse)
+            assert torch.equal(bits(lowres), bits(want[shape][2])), (shape, fuse)
+            assert torch.equal(labels, want[shape][0]) and torch.equal(counts, want[shape][1]), (shape, fuse)
+    finally:
+        m._destroy()
+
+
+def test_autotune_on_a_context_that_only_ran_fused_then_a_forward(model):
+    """nbc_autotune times downsample.0 and conv3 one by one, so it is the first to need the identity buffer here; the forward
+    on the tuned tiles fuses the pairs whose conv3 got a tile with the dual-branch form."""
+    x = frames([3], 128, 128).to(DEV)
+    m = model.clone_shared()
+    try:
+        _, _, want, pairs = run(m, x)
+        assert pairs == 3
+        tiles = m.autotune(x, reps=1)
+        assert tiles == m.plan_tiles()
+        convs = [line.split()[1] for line in describe_plan("fcn_resnet50", "f16x2", 1, 128, 128).splitlines() if " conv_dma " in line]
+        assert len(convs) == len(tiles) == 54
+        conv3 = [tiles[convs.index("backbone.layer%d.0.conv3" % s)] for s in (1, 2, 3)]
+        _, _, tuned, pairs = run(m, x)
+        assert pairs == sum(t in DUAL_TILES for t in conv3), conv3
+        assert torch.equal(bits(tuned), bits(want))
+    finally:
+        m._destroy()
+
+
+def test_profiling_runs_the_pairs_as_two_timed_launches(model):
+    x = frames([3], 128, 128).to(DEV)
+    m = model.clone_shared()
+    try:
+        _, _, want, pairs = run(m, x)
+        assert pairs == 3
+        m.set_profiling(True)
+        _, _, low, pairs = run(m, x)
+        records = m.op_records()
+        m.set_profiling(False)
+        assert pairs == 0 and len(records) == 58
+        assert all(r["ms"] > 0 for r in records), [r["name"] for r in records if not r["ms"] > 0]
+        assert torch.equal(bits(low), bits(want))
+        assert run(m, x)[3] == 3
+    finally:
+        m._destroy()

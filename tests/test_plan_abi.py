@@ -1,0 +1,296 @@
+"""The launch plan without a GPU (nbc_describe_plan): which (downsample.0, conv3) pairs the builder marks and the buffers it
+gives them, that no op writes a buffer it reads, that every read finds the tensor the topology implies -- with the pairs as
+two launches and as one --, the pool's sizes, and the launches of an op."""
+import pytest
+
+from neuralbarkcalculator_amd import topology
+from neuralbarkcalculator_amd.model import describe_plan
+
+FCN, DL, EFF = "fcn_resnet50", "deeplabv3_resnet50", "fcn_efficientnet_b0"
+SHAPES = [(n, h, w) for n in (1, 2, 3) for h, w in ((8, 8), (24, 1024), (40, 72), (72, 136), (128, 128), (520, 1024), (1024, 1024))]
+# (architecture, precision, BatchNorm statistics): every precision a network runs in, both modes where per-image is allowed
+MODES = ([(FCN, p, "running") for p in ("fp32", "bf16", "f16x2")] + [(FCN, "fp32", "image")] +
+         [(DL, p, "running") for p in ("fp32", "bf16", "f16x2")] + [(EFF, "fp32", "running")])
+CASES = [m + (keep,) + s for m in MODES for keep in (False, True) for s in SHAPES]
+
+
+def refused(arch, bn, h, w):
+    """Per-image statistics refuse a 1x1 low-resolution map; EfficientNet-B0 has no output pixel left on 8 or 24 rows."""
+    return (bn == "image" and (h, w) == (8, 8)) or (arch == EFF and h < 40)
+
+
+def parse(text):
+    ops, bufs, identity = [], [], None
+    for line in text.splitlines():
+        f = line.split()
+        if f[0] == "op":
+            o = {"name": f[1], "kernel": f[2], "cat": []}
+            for key, v in (x.split("=") for x in f[3:]):
+                if key == "cat":
+                    o["cat"].append(int(v))
+                else:
+                    o[key] = v if key == "ds" else int(v)
+            ops.append(o)
+        else:
+            assert f[0] == "buf" and int(f[1]) == len(bufs)
+            bufs.append(int(f[2]))
+            if f[3:] == ["identity"]:
+                assert identity is None, "one identity buffer per plan"
+                identity = int(f[1])
+    return ops, bufs, identity
+
+
+@pytest.fixture(scope="module")
+def plans(built_lib):
+    out = {}
+    for case in CASES:
+        arch, prec, bn, keep, n, h, w = case
+        if refused(arch, bn, h, w):
+            with pytest.raises(RuntimeError, match="Expected more than 1 value per channel" if bn == "image" else "too small"):
+                describe_plan(arch, prec, n, h, w, keep, bn)
+        else:
+            out[case] = parse(describe_plan(arch, prec, n, h, w, keep, bn))
+    return out
+
+
+# what an op reads and writes, by kernel, as fields of its line.  bn_stats names the tensor it reads as `out` as well and
+# writes the BatchNorm workspace only; aspp_pool / pool write their workspace before they read it; se_excite's `gate` is its
+# output once more; bn_apply and swish work in place.
+IO = {"ingest": ((), ("out",)), "conv_dma": (("in", "res", "gate"), ("out",)), "maxpool": (("in",), ("out",)),
+      "head1x1": (("in",), ()), "upsample_argmax": ((), ()), "aspp_pool": (("in",), ("ws", "out")), "pool": (("in",), ("ws", "out")),
+      "concat": (("cat",), ("out",)), "bn_stats": (("in",), ()), "bn_apply": (("in", "res"), ("out",)),
+      "dwconv": (("in",), ("ws", "out")), "se_excite": (("in",), ("out",)), "gate_weights": (("gate",), ("ws",)),
+      "swish": (("in",), ("out",))}
+IN_PLACE = ("bn_apply", "swish")
+
+
+def fields(o, names):
+    """[(field, buffer)] of the named fields the op has; the concat's five inputs as cat0 .. cat4"""
+    out = []
+    for f in names:
+        if f == "cat":
+            out += [("cat%d" % i, b) for i, b in enumerate(o["cat"])]
+        elif f in o:
+            out.append((f, o[f]))
+    return out
+
+
+def pairs_of(ops):
+    return [(ops[i - 1], o) for i, o in enumerate(ops) if "ds" in o]
+
+
+def test_three_pairs_in_f16x2_with_running_statistics_and_none_elsewhere(plans):
+    for (arch, prec, bn, keep, n, h, w), (ops, bufs, identity) in plans.items():
+        case = (arch, prec, bn, keep, n, h, w)
+        got = [(d["name"], o["name"], o["ds"]) for d, o in pairs_of(ops)]
+        if arch in (FCN, DL) and prec == "f16x2" and bn == "running" and not keep:
+            want = [("backbone.layer%d.0.downsample.0" % s, "backbone.layer%d.0.conv3" % s, "backbone.layer%d.0.downsample.0" % s)
+                    for s in (1, 2, 3)]                      # the op in front of conv3 is the one it names; layer4.0: no pair
+            assert got == want and identity is not None, case
+        else:
+            assert got == [] and identity is None, case
+
+
+def test_a_pair_s_buffers_serve_both_launch_forms(plans):
+    seen = 0
+    for case, (ops, bufs, identity) in plans.items():
+        for d, o in pairs_of(ops):
+            seen += 1
+            assert o["out"] not in (o["in"], d["in"]), case      # the one launch reads both while it writes
+            assert d["out"] == identity and o["res"] == identity, case
+            assert "res" not in d and len({d["in"], o["in"], o["out"], identity}) == 4, case
+        users = [o["name"] for o in ops if identity is not None and identity in [b for _, b in fields(o, ("in", "out", "res", "ws", "gate", "cat"))]]
+        assert users == [x["name"] for p in pairs_of(ops) for x in p], case   # nobody else names the identity buffer
+    assert seen == 3 * 2 * len(SHAPES)
+
+
+def test_no_op_writes_a_buffer_it_reads(plans):
+    for case, (ops, bufs, identity) in plans.items():
+        for o in ops:
+            reads, writes = IO[o["kernel"]]
+            if o["kernel"] in IN_PLACE:
+                assert o["in"] == o["out"], (case, o)
+                continue
+            r, w = fields(o, reads), fields(o, writes)
+            assert not {b for _, b in r} & {b for _, b in w}, (case, o)
+            assert len({b for _, b in w}) == len(w), (case, o)
+            for _, b in r + w:
+                assert 0 <= b < len(bufs), (case, o)
+
+
+def expected_reads(arch, bn, names, fused):
+    """{(op, field): the op whose output that read must find}, from the networks' topology (the op names carry it).  fused:
+    the conv3 of a pair reads the downsample's input (as x2) instead of the identity, and the downsample reads nothing."""
+    units = {u.name: u for u in topology.conv_units(arch)}
+    image = bn == "image"
+
+    def out_of(unit):                                       # the op that leaves `unit`'s tensor as its readers want it
+        return units[unit].bn + ".apply" if image and units[unit].bn else unit
+
+    want, stream, block_in, have = {}, None, None, set(names)
+    for name in names:
+        u = units.get(name)
+        if image and name.endswith((".stats", ".apply")):
+            unit = next(x.name for x in units.values() if x.bn == name[:-6])
+            want[(name, "in")] = unit                        # the raw convolution
+            if name.endswith(".apply") and units[unit].residual:
+                blk = unit[:-len(".conv3")]
+                want[(name, "res")] = out_of(blk + ".downsample.0") if blk + ".downsample.0" in have else block_in
+        elif name == "ingest":
+            stream = name
+        elif name in ("backbone.conv1", "backbone.maxpool", "backbone.model._conv_stem", "backbone.model._conv_head"):
+            want[(name, "in")] = stream
+            stream = out_of(name) if u else name
+        elif name.endswith(".swish"):
+            want[(name, "in")] = stream
+            stream = name
+        elif name.endswith(".conv1") and ".layer" in name:
+            block_in = stream
+            want[(name, "in")] = stream
+        elif name.endswith(".conv2") and ".layer" in name:
+            want[(name, "in")] = out_of(name[:-1] + "1")
+        elif name.endswith(".downsample.0"):
+            if not (fused and name in fused):
+                want[(name, "in")] = block_in
+        elif name.endswith(".conv3") and ".layer" in name:
+            blk = name[:-len(".conv3")]
+            want[(name, "in")] = out_of(blk + ".conv2")
+            if fused and name in fused.values():
+                want[(name, "x2")] = block_in
+            elif not image:
+                want[(name, "res")] = blk + ".downsample.0" if blk + ".downsample.0" in have else block_in
+            stream = out_of(name)
+        elif name.endswith("._expand_conv"):
+            block_in = stream
+            want[(name, "in")] = stream
+        elif name.endswith("._depthwise_conv"):
+            blk = name[:-len("._depthwise_conv")]
+            if blk + "._expand_conv" not in have:
+                block_in = stream
+            want[(name, "in")] = blk + "._expand_conv" if blk + "._expand_conv" in have else stream
+        elif name.endswith("._se_expand"):
+            want[(name, "in")] = name[:-len("._se_expand")] + "._depthwise_conv"     # its squeeze partials
+        elif name.endswith(".gated_weights"):
+            want[(name, "gate")] = name[:-len("._project_conv.gated_weights")] + "._se_expand"
+        elif name.endswith("._project_conv"):
+            want[(name, "in")] = name[:-len("._project_conv")] + "._depthwise_conv"
+            want[(name, "gate")] = name + ".gated_weights"
+            if u.residual:
+                want[(name, "res")] = block_in
+            stream = name
+        elif name in ("classifier.0", "classifier.0.convs.4") or name.startswith("classifier.0.convs."):
+            want[(name, "in")] = stream                     # the head reads the trunk
+        elif name == "classifier.0.concat":
+            for i, b in enumerate(["classifier.0.convs.%d.0" % k for k in range(4)] + ["classifier.0.convs.4"]):
+                want[(name, "cat%d" % i)] = b
+        elif name == "classifier.0.project.0":
+            want[(name, "in")] = "classifier.0.concat"
+        elif name == "classifier.1":
+            want[(name, "in")] = "classifier.0.project.0"
+        elif name == "classifier.4":
+            want[(name, "in")] = "classifier.1" if "classifier.1" in units else out_of("classifier.0")
+        else:
+            assert name == "upsample_argmax", name
+    return want
+
+
+def replay(ops, fused):
+    """{(op, field): the op that last wrote the buffer read there}, the ops taken in order"""
+    by_name = {o["name"]: o for o in ops}
+    last, got = {}, {}
+    for o in ops:
+        if fused and o["name"] in fused:
+            continue                                        # the next op's launch computes it and stores nothing
+        reads, writes = IO[o["kernel"]]
+        r = fields(o, reads)
+        if fused and o["name"] in fused.values():
+            r = [(f, b) for f, b in r if f != "res"] + [("x2", by_name[o["ds"]]["in"])]
+        for f, b in r:
+            got[(o["name"], f)] = last.get(b)
+        for _, b in fields(o, writes):
+            last[b] = o["name"]
+    return got
+
+
+def test_every_read_finds_its_producer_in_both_launch_forms(plans):
+    for case, (ops, bufs, identity) in plans.items():
+        arch, bn = case[0], case[2]
+        names = [o["name"] for o in ops]
+        pairs = {d["name"]: o["name"] for d, o in pairs_of(ops)}
+        for fused in ([None, pairs] if pairs else [None]):
+            got, want = replay(ops, fused), expected_reads(arch, bn, names, fused)
+            assert got == want, (case, "fused" if fused else "two launches",
+                                 {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)})
+
+
+def pool_and_identity(plan):
+    ops, bufs, identity = plan
+    return [b for i, b in enumerate(bufs) if i != identity], None if identity is None else bufs[identity]
+
+
+def test_pool_and_identity_bytes_of_the_flagship_plan(plans):
+    # the pool of the revision that paired at run time: its Plan::buf_bytes for the same key
+    assert pool_and_identity(plans[(FCN, "f16x2", "running", False, 1, 1024, 1024)]) == ([134217728, 134217728, 33554432], 67108864)
+    # 65 x 128 x 1024 x 4: layer3.0.downsample.0's output, that revision's buf_bytes for it with keep-activations on
+    assert pool_and_identity(plans[(FCN, "f16x2", "running", False, 1, 520, 1024)]) == ([68157440, 68157440, 17039360], 34078720)
+    assert 34078720 == 65 * 128 * 1024 * 4
+
+
+# Plan::buf_bytes of the plans that hold no pair, dumped once from the revision before the builder marked the pairs
+# (the commit "Run downsample.0 inside conv3's launch in f16x2"), its build_plan called from a host program.
+M = 1 << 20
+KEEP_F16X2_1024 = [16, 64, 16, 16, 16, 64, 64, 16, 16, 64, 16, 16, 64, 32, 8, 32, 32, 8, 8, 32, 8, 8, 32, 8, 8, 32, 16, 16, 64, 64, 16,
+                   16, 64, 16, 16, 64, 16, 16, 64, 16, 16, 64, 16, 16, 64, 32, 32, 128, 128, 32, 32, 128, 32, 32, 128, 32]
+UNCHANGED = {
+    (FCN, "fp32", "running", False, 1, 1024, 1024): [128 * M, 128 * M, 32 * M],
+    (FCN, "fp32", "image", False, 1, 1024, 1024): [128 * M, 128 * M, 32 * M],
+    (FCN, "bf16", "running", False, 1, 1024, 1024): [64 * M, 64 * M, 16 * M],
+    (DL, "fp32", "running", False, 1, 1024, 1024): [128 * M, 128 * M, 32 * M, 16 * M, 16 * M, 2105344, 1024],
+    (DL, "bf16", "running", False, 1, 1024, 1024): [64 * M, 64 * M, 16 * M, 8 * M, 8 * M, 2105344, 512],
+    (EFF, "fp32", "running", False, 1, 1024, 1024): [128 * M, 64 * M, 64 * M, 64 * M],
+    (FCN, "f16x2", "running", True, 1, 1024, 1024): [k * M for k in KEEP_F16X2_1024],
+    (FCN, "fp32", "running", True, 1, 1024, 1024): [k * M for k in KEEP_F16X2_1024],
+}
+
+
+@pytest.mark.parametrize("case", list(UNCHANGED), ids=lambda c: "-".join(str(x) for x in c))
+def test_plans_without_a_pair_keep_their_buffers(plans, case):
+    ops, bufs, identity = plans[case]
+    assert identity is None and bufs == UNCHANGED[case]
+
+
+def test_launches_of_an_op(plans):
+    for case, (ops, bufs, identity) in plans.items():
+        arch, n = case[0], case[4]
+        for o in ops:
+            if o["kernel"] == "aspp_pool":
+                want = 3                                    # partial sums, their sum, the 1x1 conv
+                assert arch == DL and o["name"] == "classifier.0.convs.4", case
+            elif o["kernel"] in ("bn_stats", "pool"):
+                want = 2
+            elif o["kernel"] == "conv_dma" and "gate" in o:
+                want = n                                    # the SE-gated project conv: one launch per image
+            else:
+                want = 1
+            assert o["launches"] == want, (case, o)
+        assert [o["name"] for o in ops if o["name"].endswith(".stats")] == (
+            [u.bn + ".stats" for u in topology.conv_units(arch) if u.bn] if case[2] == "image" else []), case
+        if arch == DL:
+            assert sum(o["kernel"] == "aspp_pool" for o in ops) == 1, case
+    dl_eff = parse(describe_plan("deeplabv3_efficientnet_b0", "fp32", 2, 72, 136))[0]
+    assert [(o["name"], o["launches"]) for o in dl_eff if o["kernel"] == "pool"] == [("classifier.0.convs.4", 2)]
+
+
+def test_the_text_is_cut_to_the_capacity_and_bad_keys_are_refused(built_lib):
+    import ctypes as C
+    args = (topology.arch_index(FCN), 2, 1, 40, 72, 0, 0)
+    need = built_lib.nbc_describe_plan(*args, None, 0)
+    full, short = C.create_string_buffer(need), C.create_string_buffer(b"\xff" * 64, 64)
+    assert built_lib.nbc_describe_plan(*args, full, need) == need and len(full.value) == need - 1
+    assert built_lib.nbc_describe_plan(*args, short, 32) == need
+    assert short.raw[:32] == full.raw[:31] + b"\0" and short.raw[32:] == b"\xff" * 32
+    for bad in ((FCN, "f16x2", 0, 40, 72), (FCN, "f16x2", 1, 7, 72), (EFF, "bf16", 1, 40, 72)):
+        with pytest.raises(RuntimeError):
+            describe_plan(*bad)
+    with pytest.raises(RuntimeError, match="per-image"):
+        describe_plan(DL, "fp32", 1, 40, 72, False, "image")
