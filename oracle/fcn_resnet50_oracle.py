@@ -22,15 +22,18 @@ dilation).  The arithmetic itself is torch's own ATen CPU ops (conv2d, batch_nor
 relu, max_pool2d, interpolate(bicubic), argmax), i.e. the same library the
 reference runs on ``--device=cpu``.
 
-Pinning status: the reference ships no tests, golden vectors or weights for this
-path, and its modules cannot be imported here (ordinary
-``ModuleNotFoundError: torchvision``).  **parity unpinned** by reference fixtures; the
-independent pins are (tests/test_oracle.py): the 326 state_dict key names, the
-32 947 779 parameter count, the feature-map shapes, and the closed-form bicubic
-weights, and ``oracle/numpy_restatement.py`` — the same forward written again in
-float64 numpy from the published formulas, sharing no code with this file — which
-agrees with this file to 2e-5 of the logit range on a ragged 40x56 input.  Goldens
-under tests/golden/ are produced by THIS file (drift guards).
+Pinning status: pinned to executed reference code where the reference can run.  Its modules import once the packages
+they never call on these paths (torchvision, skimage, poutyne, efficientnet_pytorch) are stood in for by empty modules;
+``oracle/record_reference.py`` then runs the reference's ``SimpleSegmentationModel.forward`` (models.py:33-43) around the
+reference's ``FCNHead(2048, 3)`` (models.py:113-124) in ``eval()`` and records the logits and the head's ``state_dict`` keys
+(tests/golden/ref_head_*.npz); tests/test_reference_pins.py holds ``OracleFCNResNet50.forward`` and the key list to them,
+tests/test_gpu_reference_pins.py the HIP path.  The recipe refuses to record a forward that differs from this file's by a
+bit.  **Still restated**: the trunk -- torchvision itself is absent, so the recorded forward runs on
+``DilatedResNet50Trunk`` below -- whose independent pins are (tests/test_oracle.py) the 326 state_dict key names, the
+32 947 779 parameter count, the feature-map shapes, and ``oracle/numpy_restatement.py`` -- the same forward written again
+in float64 numpy from the published formulas, sharing no code with this file -- which agrees with this file to 2e-5 of the
+logit range on a ragged 40x56 input; ``DeepLabHead`` and EfficientNet (tests/helpers/) likewise.  The other goldens under
+tests/golden/ are produced by THIS file (drift guards).
 
 Decision D1: the oracle runs in eval mode (BN running stats,
 Dropout identity).  ``predict.py`` as shipped never calls ``.eval()`` and is therefore

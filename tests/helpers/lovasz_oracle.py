@@ -6,8 +6,16 @@ carrying fg along; with the running foreground count F_i and background count B_
 J_i = 1 - (G - F_i) / (G + B_i), and the class's term is sum_i e_(i) (J_i - J_{i-1}) with J_{-1} = 0.  The loss is the
 mean of the present classes' terms.  An absent class has term 0 and count 0.
 
-* ``terms_torch_f32``: what the training code evaluates -- torch.sort descending, float32 cumulative sums, float32 dot.
+* ``terms_torch_f32``: what the training code evaluates -- torch.sort descending, float32 cumulative sums and Jaccard
+  steps -- except that the last dot product adds its float32 products in float64: a float32 ``torch.dot`` adds them in an
+  order that depends on the CPU (the constant-logits image of tests/golden/ref_loss_65x127 moves by 9e-7 between two
+  machines), and a restatement must say the same thing everywhere.
 * ``terms_float64``: numpy in float64 from the same float32 errors (the adjudicating value).
+
+Both are pinned to executed reference code: tests/test_reference_pins.py holds them (and ``target_classes``) to what
+``LovaszSoftmax``, ``lovasz_softmax_flat(classes=[c])`` and the decode of dataset.py:188-198 returned on the images of
+tests/golden/ref_loss_*.npz (oracle/record_reference.py), the ``'present'`` rule included, within the recorded float32
+rounding ``d_ref`` + 1e-7.
 """
 from __future__ import annotations
 
@@ -33,7 +41,7 @@ def errors_f32(probs: np.ndarray, classes: np.ndarray, c: int) -> Tuple[np.ndarr
 
 
 def terms_torch_f32(logits: np.ndarray, grey: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """(terms float64 [3] holding the float32 results, fg counts int64 [3]) for one image, the float32 torch way."""
+    """(terms float64 [3], fg counts int64 [3]) for one image, the float32 torch way up to the final sum."""
     probs = softmax_f32(logits)
     classes = target_classes(grey)
     terms, counts = np.zeros(3), np.zeros(3, np.int64)
@@ -49,7 +57,7 @@ def terms_torch_f32(logits: np.ndarray, grey: np.ndarray) -> Tuple[np.ndarray, n
         jac = 1.0 - (total - g.cumsum(0)) / (total + (1 - g).cumsum(0))
         if len(jac) > 1:
             jac[1:] = jac[1:] - jac[:-1].clone()
-        terms[c] = float(torch.dot(e_sorted, jac))
+        terms[c] = float(torch.dot(e_sorted.double(), jac.double()))
     return terms, counts
 
 

@@ -9,6 +9,11 @@ the pixels, which is sum(w[max(a, b)] S[a][b]) / P.
 * ``sums_float64``: S and K in float64 from the float32 logits (the adjudicating value).
 * ``reference_procedure_f32``: the weighted loss the training code's way, step by step in float32 torch.
 * ``weighted_float64``: the same expression evaluated in float64 torch, pixel by pixel (no S in between).
+
+All three are pinned to executed reference code: tests/test_reference_pins.py holds them (and ``target_classes``) to what
+``CrossEntropyLoss``, ``CustomWeightedCrossEntropy`` (two weight vectors: the ``max(argmax, target)`` index) and ``MixedLoss``
+returned on the images of tests/golden/ref_loss_*.npz (oracle/record_reference.py), a NaN image included, within the
+recorded float32 rounding ``d_ref`` + 1e-7 relative.
 """
 from __future__ import annotations
 

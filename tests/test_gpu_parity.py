@@ -300,6 +300,78 @@ def test_upsample_argmax_known_answers(gpu_fp32):
     assert bool((lab == 1).all())
 
 
+def _tiled_upsample_fits(h, w, H, W):
+    """`fits` of launch_upsample_argmax (csrc/pointwise.hip), in the same float32 arithmetic: the tap window of a 256 x 8
+    output block against the tiled kernel's 9 x 72 LDS image.  False: the one-pixel-per-thread kernel runs."""
+    sy, sx = np.float32(h) / np.float32(H), np.float32(w) / np.float32(W)
+    return int(sx * np.float32(255.0)) + 6 <= 72 and int(sy * np.float32(7.0)) + 6 <= 9
+
+
+def _upsample_logits_vs_torch(model, lr, size):
+    labels, counts, logits = model.upsample_argmax(lr.to(DEV), size, return_logits=True)
+    ref = torch.nn.functional.interpolate(lr, size=size, mode="bicubic", align_corners=False)
+    err = float((logits.cpu() - ref).abs().max())
+    assert err <= 2e-6 * float(ref.abs().max()), (tuple(lr.shape), size, err)
+    return labels, counts, ref, err
+
+
+@pytest.mark.parametrize("shape,size", [((2, 3, 20, 150), (40, 300)), ((1, 3, 7, 9), (9, 13)), ((1, 3, 16, 16), (16, 16)),
+                                        ((1, 3, 12, 20), (5, 9))])
+def test_upsample_argmax_one_pixel_per_thread_kernel(gpu_fp32, shape, size):
+    """Geometries whose tap window does not fit the tiled kernel, so that nbc_upsample_argmax runs upsample_argmax_kernel:
+    scale 0.5 both ways with two blocks along W and a tail, a non-integer scale, the identity, a downscale.  Logits against
+    torch's CPU bicubic, labels, counts, both label types, exclude_nodes, and the tie and NaN rules."""
+    n, _, h, w = shape
+    H, W = size
+    assert not _tiled_upsample_fits(h, w, H, W)
+    dev = torch.device(DEV)
+    lr = torch.randn(shape, generator=torch.Generator().manual_seed(h * 1000 + w))
+    labels, counts, ref, err = _upsample_logits_vs_torch(gpu_fp32, lr, size)
+    assert labels.dtype == torch.int64 and tuple(labels.shape) == (n, H, W)
+    check_labels(labels, torch.argmax(ref, 1), ref, max(err, 1e-7))
+    want_counts = torch.stack([(labels == c).flatten(1).sum(1) for c in range(3)], 1)
+    assert torch.equal(counts, want_counts) and int(counts.sum()) == n * H * W
+    lab8, cnt8 = gpu_fp32.upsample_argmax(lr.to(dev), size, labels_dtype=torch.uint8)
+    assert lab8.dtype == torch.uint8 and torch.equal(lab8.long(), labels) and torch.equal(cnt8, counts)
+    labx, cntx = gpu_fp32.upsample_argmax(lr.to(dev), size, exclude_nodes=True)
+    remapped = labels.clone()
+    remapped[remapped == 2] = 1
+    assert torch.equal(labx, remapped)
+    assert torch.equal(cntx, torch.stack([counts[:, 0], counts[:, 1] + counts[:, 2], torch.zeros_like(counts[:, 2])], 1))
+    # ties -> lowest index; NaN wins (the first one); constant planes stay constant
+    px = H * W
+    c = torch.zeros(shape, device=dev)
+    lab, cnt = gpu_fp32.upsample_argmax(c, size)
+    assert int(lab.sum()) == 0 and cnt.tolist() == [[px, 0, 0]] * n
+    c[:, 0] = 1.0
+    c[:, 1] = 2.0
+    c[:, 2] = 2.0
+    lab, cnt = gpu_fp32.upsample_argmax(c, size)
+    assert bool((lab == 1).all()) and cnt.tolist() == [[0, px, 0]] * n
+    c[:, 2] = float("nan")
+    lab, cnt = gpu_fp32.upsample_argmax(c, size)
+    assert bool((lab == 2).all()) and cnt.tolist() == [[0, 0, px]] * n
+    c[:, 1] = float("nan")
+    lab, _ = gpu_fp32.upsample_argmax(c, size, labels_dtype=torch.uint8)
+    assert bool((lab == 1).all())
+    lab, cnt = gpu_fp32.upsample_argmax(c, size, exclude_nodes=True)
+    assert bool((lab == 1).all()) and cnt.tolist() == [[0, px, 0]] * n
+
+
+@pytest.mark.parametrize("inside,outside,size", [((1, 3, 6, 133), (1, 3, 6, 135), (24, 510)),
+                                                 ((1, 3, 15, 40), (1, 3, 17, 40), (28, 160))])
+def test_upsample_argmax_at_the_boundary_between_its_two_kernels(gpu_fp32, inside, outside, size):
+    """One geometry just inside the tiled kernel's window and one just outside, along W (int(255 w / W) = 66 and 67 against
+    the 66 that fit) and along H (int(7 h / H) = 3 and 4 against 3): the same bound on the logits on both sides."""
+    H, W = size
+    assert _tiled_upsample_fits(inside[2], inside[3], H, W) and not _tiled_upsample_fits(outside[2], outside[3], H, W)
+    for shape in (inside, outside):
+        lr = torch.randn(shape, generator=torch.Generator().manual_seed(shape[2] * 1000 + shape[3]))
+        labels, counts, ref, err = _upsample_logits_vs_torch(gpu_fp32, lr, size)
+        check_labels(labels, torch.argmax(ref, 1), ref, max(err, 1e-7))
+        assert torch.equal(counts, torch.stack([(labels == c).flatten(1).sum(1) for c in range(3)], 1))
+
+
 def test_full_size_properties_1024(gpu_fp32, gpu_bf16):
     """Size-independent properties at BASELINE.json's full frame size."""
     x = frames([20, 21], 1024, 1024).to(DEV)
