@@ -33,6 +33,28 @@
 // LDS: three row slots (slot = kh: a channel block's three kernel rows; tile 20: four, its four input rows) of 144 pixels x 128 bytes, their 16-byte chunks
 // rotated by the pixel index so that a fragment block may start at ANY pixel without bank conflicts (row_off), and two or
 // three stages of three weight panels (one per kw).
+//
+// The tile walk (tiles 18 and 20).  A block of tile 20 takes 124 KiB of LDS and twelve waves: a compute unit holds ONE, and nothing
+// becomes resident beside it.  With more tiles than compute units (the head conv and layer4's conv2 at 1024 x 1024: 512 tiles, two
+// per unit) the epilogue of a unit's first tile, the exit of its waves, the dispatch of the next block, its index arithmetic, its
+// table and the round trip of its first row-step ran strictly one after the other, no MFMA in flight.  So a launch has
+// min(tiles, compute units) blocks, and block b computes tiles b, b + blocks, b + 2 blocks, ... -- each through the same
+// XCD-aware index map, each exactly as a block of its own would (image, row pair, segment, channel tile, K order): which block
+// computes which tile changes no bit.  After the barrier that ends a tile's K loop the loader waves do not leave: they request
+// the next tile's scale/shift table and its first row-step (pixel slots 0 [and 1], weight stage 0) at once and go on with the
+// usual protocol, while the MFMA waves run the epilogue and meet them at the next tile's first barrier with zeroed accumulators.
+// The last tile of a block, or the only one, ends as before: the loaders leave after its K loop.
+//   LDS of a walking block, tile 20 (tile 18): bytes
+//          0 ..  73 728 ( 55 296)  four (three) pixel slots of 18 432; the epilogue scratch (eight waves x 32 rows x 144 bytes =
+//                                  36 864) lies on the LAST TWO, from 36 864 (18 432): the next tile's first row-step does not
+//                                  touch them, and its second is requested after that tile's first barrier, which every MFMA
+//                                  wave reaches with its last scratch read behind it;
+//     73 728 .. 122 880 (153 600)  two weight stages of 3 x 64 (128) x 128;
+//    122 880 .. 126 976 (157 696)  two scale/shift tables of 2 048, one per tile in flight, used in turn: 124 KiB (154 KiB).
+//   Waits.  Every LDS-DMA of the next tile, table included, is issued by the loader waves, which count their own vmcnt alone and
+//   have nothing else in flight: the waits stay exact.  The MFMA waves still issue no load in the loop and wait for no vmcnt;
+//   their epilogue's stores count on THEIR vmcnt, which no loader wave waits on, and are left to retire under the next K loop.
+//   Registers of the MFMA waves: as a block of one tile (each tile computes its fragment and epilogue addressing anew).
 #include <atomic>
 
 #include "nbc_kernels.hpp"
@@ -80,6 +102,14 @@ __host__ __device__ inline int rowstep_pairs(int Ho, int dil) {
   return groups * dil + (rem < dil ? rem : dil);
 }
 
+// Tiles 18 and 20 (SB 2) WALK: a launch has one block per compute unit at the most, and block b computes tiles b, b + blocks, ...
+// (the kernel's comment).  LDS of a launch: the pixel slots, SB weight stages and a 2-KiB scale/shift table, two for a walking kernel.
+constexpr bool rowstep_walks(int SB) { return SB == 2; }
+constexpr int rowstep_tables(int SB) { return rowstep_walks(SB) ? 2 : 1; }
+constexpr int rowstep_lds_bytes(int BN, int SB, int OR) { return (OR == 2 ? 4 : 3) * kRowBytes + SB * 3 * BN * 128 + rowstep_tables(SB) * 2048; }
+static_assert(rowstep_lds_bytes(64, 2, 2) == 124 * 1024 && rowstep_lds_bytes(128, 2, 1) == 154 * 1024 && rowstep_lds_bytes(64, 3, 1) == 128 * 1024,
+              "tile 20: 124 KiB, tile 18: 154 KiB, tile 19: 128 KiB of the CU's 160");
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -88,16 +118,16 @@ __device__ __forceinline__ void wait_vmcnt() {
 // Epilogue (conv_igemm_dma.hip's f16x2 path without identity, instruction for instruction): BN on the
 // accumulators into a per-wave f32 scratch in the idle ring, read back row-wise, ReLU, split, whole row segments stored.
 // acc16[j][i]: lane (r16, q16) holds pixel i*16 + r16 and channels j*16 + 4*q16 .. +3 of the wave's (MT*32) x (NT*32) tile.
-template <int CW, int MT, int NT, int TABLE_OFF>
-__device__ __forceinline__ void rows_epilogue(const ConvArgs& p, unsigned char* smem, f32x4 (&acc16)[2 * NT][2 * MT], int wave, int lane,
-                                              int wm, int wn, int m0, int n0) {
+// scratch: the block's scratch in LDS (CW x 32 x PITCH bytes, a slab per wave); table: the tile's scale/shift table.
+template <int CW, int MT, int NT>
+__device__ __forceinline__ void rows_epilogue(const ConvArgs& p, unsigned char* scratch, const unsigned char* table_base, f32x4 (&acc16)[2 * NT][2 * MT],
+                                              int wave, int lane, int wm, int wn, int m0, int n0) {
   constexpr int NT16 = 2 * NT;
   constexpr int SLAB_CH = NT * 32;
   constexpr int PITCH = SLAB_CH * 4 + 16;
   constexpr int CPR = SLAB_CH / 8;                  // lanes per pixel row: 8 channels (an h0 chunk and an h1 chunk) each
   constexpr int PIX_PER_PASS = 64 / CPR;
   constexpr int PASSES = 32 / PIX_PER_PASS;
-  static_assert(CW * 32 * PITCH <= TABLE_OFF, "epilogue scratch must fit below the scale/shift table");
   const int r16 = lane & 15, q16 = lane >> 4;
   const int o_pix = lane / CPR, o_chunk = lane % CPR;
   const int n_slab = n0 + wn * SLAB_CH;
@@ -106,8 +136,8 @@ __device__ __forceinline__ void rows_epilogue(const ConvArgs& p, unsigned char* 
   const int rows_valid = p.M - m0;
   const int row0 = wm * MT * 32 + o_pix;
   const unsigned lane_chunk = (unsigned)(o_chunk >> 2) * 128u + (unsigned)(o_chunk & 3) * 16u;
-  unsigned char* scr = smem + wave * (32 * PITCH);
-  const unsigned char* table = smem + TABLE_OFF + wn * SLAB_CH * 4;
+  unsigned char* scr = scratch + wave * (32 * PITCH);
+  const unsigned char* table = table_base + wn * SLAB_CH * 4;
   const bool relu = p.relu != 0;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
@@ -165,11 +195,11 @@ __device__ __forceinline__ void rows_epilogue(const ConvArgs& p, unsigned char* 
 // 128 pixels (an image row; a 128-pixel segment of a wider one) x BN = WN * NT * 32 channels per block: 2 x WN MFMA waves of
 // 64 x (NT * 32) and four loader waves; three row slots of 18 KiB and SB stages of 3 x BN x 128 bytes of weights: a stage is
 // refilled a whole row-step (three K-steps of MFMAs) ahead.
-//   tile 18: WN 4 -> 128 channels, eight MFMA waves, SB 2 (150 KiB): 256 output channels or more;
-//   tile 19: WN 2 ->  64 channels, four MFMA waves,  SB 3 (126 KiB): the 64 / 128-channel layers, whose K loop ran at one
+//   tile 18: WN 4 -> 128 channels, eight MFMA waves, SB 2 (150 KiB + tables): 256 output channels or more;
+//   tile 19: WN 2 ->  64 channels, four MFMA waves,  SB 3 (126 KiB + table): the 64 / 128-channel layers, whose K loop ran at one
 //            LDS-DMA round trip per K-step (DMA and barriers alone: 19-21 of their 21-25 us).
 //   tile 20: OR 2, WN 2 -> TWO output rows (oy and oy + dilation: four input rows between them instead of six) x 64 channels,
-//            eight MFMA waves (output row x pixel half x channel half), SB 2 (122 KiB): per output row and channel block 72 KiB
+//            eight MFMA waves (output row x pixel half x channel half), SB 2 (120 KiB + tables): per output row and channel block 72 KiB
 //            of pixels and weights where tile 18 moves 99; the same K order per output, so the same bits as tile 18.
 template <int WN, int NT, int SB, int OR>
 __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void conv3x3_rowstep_kernel(const ConvArgs p) {
@@ -177,6 +207,7 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
   static_assert(OR == 1 || (OR == 2 && SB == 2), "two output rows per block: every row-step's DMAs are waited for in full");
   constexpr int WM = 2, MT = 2, CW = WM * WN * OR, NW = 4;   // 2 x WN (x OR) MFMA waves of 64 x (NT * 32), four loader waves
   constexpr int BN = WN * NT * 32;
+  constexpr bool WALK = rowstep_walks(SB);
   // pixel-row slots.  OR 1: slot = kh.  OR 2: slot k = input row oy + (k - 1) dil; row-step kh reads slots kh (first output row) and
   // kh + 1 (second): slots 0 and 1 are requested with kh 0's weights, 2 with kh 1's, 3 with kh 2's, each a row-step ahead, into a slot
   // last read two row-steps before.  (Rows requested TWO row-steps ahead through a ring of six slots: the same times,
@@ -185,6 +216,16 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
   constexpr int A_SLOT = kRowBytes, A_REGION = NSLOT * A_SLOT;
   constexpr int B_TAP = BN * 128, B_STEP = 3 * B_TAP;
   constexpr int TABLE_OFF = A_REGION + SB * B_STEP;   // the ring; the epilogue scratch (18 / 36 KiB) lies inside it
+  // The epilogue scratch.  A walking block's loaders fill the next tile's first row-step (pixel slots 0 [and 1], weight stage 0) and
+  // its table while the MFMA waves are in this tile's epilogue: the scratch lies on the LAST two pixel slots, which the next tile
+  // requests only after its first barrier, and each of two tiles in flight has a table of its own.
+  constexpr int SCRATCH = CW * 32 * (NT * 32 * 4 + 16);
+  constexpr int SCRATCH_OFF = WALK ? (NSLOT - 2) * A_SLOT : 0;
+  constexpr int FIRST_SLOTS = OR == 2 ? 2 : 1;        // pixel slots of a tile's first row-step
+  static_assert(!WALK || SB == 2, "a walking block runs one row-step ahead: weight stage 0 and the first row-step's slots");
+  static_assert(SCRATCH_OFF >= (WALK ? FIRST_SLOTS * A_SLOT : 0), "the scratch must not lie on the next tile's first row-step");
+  static_assert(SCRATCH_OFF + SCRATCH <= A_REGION, "the scratch lies on pixel slots, below the weight stages and the tables");
+  static_assert(TABLE_OFF + rowstep_tables(SB) * 2048 == rowstep_lds_bytes(BN, SB, OR), "the launch's LDS size is this layout");
   constexpr int NA = kRowPx / 8;                       // 18 pixel DMAs per row-step
   constexpr int LA_HI = (NA + NW - 1) / NW, LA_LO = NA / NW;
   constexpr int NBW = (BN / 8) / NW;                  // weight DMAs per loading wave and tap
@@ -205,16 +246,16 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
   const int tiles_n = p.Co / BN;
   const int tiles_m = NH * segs;
   const int nblk = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-  }
-  const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
-  const int n0 = tile_n * BN;
-  const int R = tile_m / segs, seg = tile_m - R * segs;
-  const int img = R / pairs, pr = R - img * pairs;
-  const int oy = OR == 2 ? (pr / dil) * 2 * dil + pr % dil : pr;    // the (first) output row
+  // tile tl of the launch (block b: tl = b, b + gridDim.x, ...): channel tile, image, (first) output row and segment
+  struct Tile { int n0, img, oy, seg; };
+  auto tile_at = [&](int tl) __attribute__((always_inline)) {
+    const int q = nblk >> 3, rr = nblk & 7, xcd = tl & 7;
+    const int bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (tl >> 3);
+    const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
+    const int R = tile_m / segs, seg = tile_m - R * segs;
+    const int img = R / pairs, pr = R - img * pairs;
+    return Tile{tile_n * BN, img, OR == 2 ? (pr / dil) * 2 * dil + pr % dil : pr, seg};
+  };
 
   const rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
   const rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
@@ -226,157 +267,185 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
   typedef __attribute__((address_space(3))) unsigned char lds_u8;
   const unsigned smem_base = (unsigned)(size_t)(lds_u8*)smem;
 
-  if (wave == CW && lane < BN / 4) {
-    dma16(p.scale + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF);
-    dma16(p.shift + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF + 1024u);
-  }
   if (is_loader) {
     const int lp = lane >> 3, ps = lane & 7;
-    unsigned w_off[NBW], a_col[LA_HI];
-#pragma unroll
-    for (int i = 0; i < NBW; ++i) {
-      const int row = (lw + NW * i) * 8 + lp;
-      w_off[i] = (unsigned)(n0 + row) * wrow_bytes + (unsigned)(ps ^ ((row >> 1) & 7)) * 16u;
-    }
-#pragma unroll
-    for (int d = 0; d < LA_HI; ++d) {
-      const int pp = (lw + NW * d) * 8 + lp;            // slot pixel
-      const int ix = seg * 128 + pp - dil;
-      const unsigned chunk = (unsigned)((ps - 2 * ((pp >> 1) & 3)) & 7) * 16u;
-      a_col[d] = (unsigned)ix < (unsigned)p.Wi ? (unsigned)ix * (unsigned)pix_bytes + chunk : kOutOfRange;
-    }
     const int la = la_hi ? LA_HI : LA_LO;
-    int i_cb = 0, i_kh = 0, i_sb = 0;                   // the row-step issued next: channel block, kh (= its pixel slot), weight stage
-    auto issue_row = [&](int k, int cb, int slot) __attribute__((always_inline)) {     // input row oy + (k - 1) dil of channel block cb
-      const int iy = oy + (k - 1) * dil;
-      const bool rowok = (unsigned)iy < (unsigned)p.Hi;
-      const unsigned rowoff = (unsigned)((img * p.Hi + iy) * p.Wi) * (unsigned)pix_bytes;
+    // Tile after tile.  The barrier that ends a tile's K loop retires every read of the ring, so the next tile's table and first
+    // row-step go out at once, beside the MFMA waves' epilogue; the last tile's loaders leave there.
+    for (int tl = blockIdx.x, table = TABLE_OFF;;) {
+      const Tile c = tile_at(tl);
+      const int n0 = c.n0, img = c.img, oy = c.oy, seg = c.seg;
+      if (wave == CW && lane < BN / 4) {
+        dma16(p.scale + n0 + lane * 4, smem_base + (unsigned)table);
+        dma16(p.shift + n0 + lane * 4, smem_base + (unsigned)table + 1024u);
+      }
+      unsigned w_off[NBW], a_col[LA_HI];
 #pragma unroll
-      for (int d = 0; d < LA_HI; ++d)
-        if (d < la)
-          dma16_buf(rowok ? a_col[d] + rowoff : kOutOfRange, xrsrc, smem_base + (unsigned)(slot * A_SLOT) + (unsigned)(lw + NW * d) * 1024u,
-                    (unsigned)cb * 128u);
-    };
-    auto issue_rowstep = [&]() __attribute__((always_inline)) {
-      if constexpr (OR == 1) issue_row(i_kh, i_cb, i_kh);
-      else if (i_kh == 0) { issue_row(0, i_cb, 0); issue_row(1, i_cb, 1); }
-      else issue_row(i_kh + 1, i_cb, i_kh + 1);
-      const unsigned soff = ((unsigned)(3 * i_kh) * (unsigned)cblocks + (unsigned)i_cb) * 128u;
+      for (int i = 0; i < NBW; ++i) {
+        const int row = (lw + NW * i) * 8 + lp;
+        w_off[i] = (unsigned)(n0 + row) * wrow_bytes + (unsigned)(ps ^ ((row >> 1) & 7)) * 16u;
+      }
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
+      for (int d = 0; d < LA_HI; ++d) {
+        const int pp = (lw + NW * d) * 8 + lp;            // slot pixel
+        const int ix = seg * 128 + pp - dil;
+        const unsigned chunk = (unsigned)((ps - 2 * ((pp >> 1) & 3)) & 7) * 16u;
+        a_col[d] = (unsigned)ix < (unsigned)p.Wi ? (unsigned)ix * (unsigned)pix_bytes + chunk : kOutOfRange;
+      }
+      int i_cb = 0, i_kh = 0, i_sb = 0;                   // the row-step issued next: channel block, kh (= its pixel slot), weight stage
+      auto issue_row = [&](int k, int cb, int slot) __attribute__((always_inline)) {     // input row oy + (k - 1) dil of channel block cb
+        const int iy = oy + (k - 1) * dil;
+        const bool rowok = (unsigned)iy < (unsigned)p.Hi;
+        const unsigned rowoff = (unsigned)((img * p.Hi + iy) * p.Wi) * (unsigned)pix_bytes;
 #pragma unroll
-        for (int i = 0; i < NBW; ++i)
-          dma16_buf(w_off[i], wrsrc, smem_base + (unsigned)(A_REGION + i_sb * B_STEP + kw * B_TAP) + (unsigned)(lw + NW * i) * 1024u,
-                    soff + (unsigned)kw * tap_stride);
-      if (++i_kh == 3) { i_kh = 0; ++i_cb; }
-      if (++i_sb == SB) i_sb = 0;
-    };
-    // SB - 1 row-steps ahead (the pixel slots, three of them, never run short)
-    int issued = 0;
+        for (int d = 0; d < LA_HI; ++d)
+          if (d < la)
+            dma16_buf(rowok ? a_col[d] + rowoff : kOutOfRange, xrsrc, smem_base + (unsigned)(slot * A_SLOT) + (unsigned)(lw + NW * d) * 1024u,
+                      (unsigned)cb * 128u);
+      };
+      auto issue_rowstep = [&]() __attribute__((always_inline)) {
+        if constexpr (OR == 1) issue_row(i_kh, i_cb, i_kh);
+        else if (i_kh == 0) { issue_row(0, i_cb, 0); issue_row(1, i_cb, 1); }
+        else issue_row(i_kh + 1, i_cb, i_kh + 1);
+        const unsigned soff = ((unsigned)(3 * i_kh) * (unsigned)cblocks + (unsigned)i_cb) * 128u;
 #pragma unroll
-    for (int k = 0; k < SB - 1; ++k)
-      if (issued < RS) { issue_rowstep(); ++issued; }
-    for (int rs = 0; rs < RS; ++rs) {
-      // this wave's DMAs of row-step rs have landed when only the younger row-steps' (SB - 2 of them) are outstanding
-      const int younger = issued - rs - 1;
-      if (younger <= 0) wait_vmcnt<0>();
-      else if (SB == 3 && younger == 1) { if (la_hi) wait_vmcnt<LB + LA_HI>(); else wait_vmcnt<LB + LA_LO>(); }
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      if (issued < RS) { issue_rowstep(); ++issued; }   // into the stage row-step rs-1 used: its reads retired at this barrier
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+          for (int i = 0; i < NBW; ++i)
+            dma16_buf(w_off[i], wrsrc, smem_base + (unsigned)(A_REGION + i_sb * B_STEP + kw * B_TAP) + (unsigned)(lw + NW * i) * 1024u,
+                      soff + (unsigned)kw * tap_stride);
+        if (++i_kh == 3) { i_kh = 0; ++i_cb; }
+        if (++i_sb == SB) i_sb = 0;
+      };
+      // SB - 1 row-steps ahead (the pixel slots, three of them, never run short)
+      int issued = 0;
+#pragma unroll
+      for (int k = 0; k < SB - 1; ++k)
+        if (issued < RS) { issue_rowstep(); ++issued; }
+      for (int rs = 0; rs < RS; ++rs) {
+        // this wave's DMAs of row-step rs have landed when only the younger row-steps' (SB - 2 of them) are outstanding
+        const int younger = issued - rs - 1;
+        if (younger <= 0) wait_vmcnt<0>();
+        else if (SB == 3 && younger == 1) { if (la_hi) wait_vmcnt<LB + LA_HI>(); else wait_vmcnt<LB + LA_LO>(); }
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        if (issued < RS) { issue_rowstep(); ++issued; }   // into the stage row-step rs-1 used: its reads retired at this barrier
+      }
+      __syncthreads();
+      if (!WALK) return;
+      tl += gridDim.x;
+      if (tl >= nblk) return;
+      table ^= TABLE_OFF ^ (TABLE_OFF + 2048);
     }
-    __syncthreads();
-    return;
   }
 
   // ---- MFMA waves
-  const int r16 = lane & 15, q16 = lane >> 4;
+  // Every tile of the walk runs the code of a block of one tile, its fragment and epilogue addressing included.  That addressing is
+  // the same for every tile, and computed once, ahead of the tile loop, it would stay in some forty registers through the K loop and
+  // the epilogue where a one-tile block computes it next to its use.  So the lane index is opaque to the compiler at a tile's start.
   const int wm = wave % WM, orow = OR == 2 ? (wave / WM) & 1 : 0, wn = wave / (WM * OR);
   auto row_off = [](int pix, int chunk) { return pix * 128 + (((chunk + 2 * ((pix >> 1) & 3)) & 7) << 4); };
-  unsigned a_rd[3][2];
+  for (int tl = blockIdx.x, table = TABLE_OFF;;) {
+    const Tile c = tile_at(tl);
+    int tlane = lane;
+    if constexpr (WALK) asm volatile("" : "+v"(tlane));
+    const int r16 = tlane & 15, q16 = tlane >> 4;
+    unsigned a_rd[3][2];
 #pragma unroll
-  for (int kw = 0; kw < 3; ++kw) {
-    const int pix = wm * 64 + kw * dil + r16;
-    a_rd[kw][0] = (unsigned)row_off(pix, q16);
-    a_rd[kw][1] = (unsigned)row_off(pix, 4 + q16);
-  }
-  const unsigned b_rd0 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, q16));
-  const unsigned b_rd1 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, 4 + q16));
-  f32x4 acc16[NT16][MT16], accI2[NT16][MT16];
-#pragma unroll
-  for (int j = 0; j < NT16; ++j)
-#pragma unroll
-    for (int i = 0; i < MT16; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { acc16[j][i][e] = 0.f; accI2[j][i][e] = 0.f; }
-  const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
-  unsigned a_off = (unsigned)(orow * A_SLOT), b_off = 0;   // byte offsets of the row-step's pixel slot (kh [+ 1]) and weight stage
-  int t = 0;
-  for (int rs = 0; rs < RS; ++rs) {
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw, ++t) {
-      if (t > 0 && (t & 7) == 0) {                     // the chain of the last eight K-steps joins the sum
-#pragma unroll
-        for (int n = 0; n < NT16 * MT16; ++n) {
-          acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) accI2[n / MT16][n % MT16][e] = 0.f;
-        }
-      }
-      uint4 xp0[MT16], xp1[MT16], xw0[NT16], xw1[NT16];
-#pragma unroll
-      for (int i = 0; i < MT16; ++i) {
-        xp0[i] = *reinterpret_cast<const uint4*>(smem + (a_rd[kw][0] + a_off) + i * 2048);
-        xp1[i] = *reinterpret_cast<const uint4*>(smem + (a_rd[kw][1] + a_off) + i * 2048);
-      }
-#pragma unroll
-      for (int j = 0; j < NT16; ++j) {
-        xw0[j] = *reinterpret_cast<const uint4*>(smem + (b_rd0 + b_off) + (kw * B_TAP + j * 2048));
-        xw1[j] = *reinterpret_cast<const uint4*>(smem + (b_rd1 + b_off) + (kw * B_TAP + j * 2048));
-      }
-      constexpr int NTI = NT16 * MT16;
-#pragma unroll
-      for (int idx = 0; idx < 3 * NTI; ++idx) {
-        const int prod = idx / NTI, n = idx % NTI, j = n / MT16, i = n % MT16;
-        if (prod == 0)
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-        else if (prod == 1)
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw1[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-        else {
-          if (i == 0) xw0[j] = __builtin_bit_cast(uint4, __builtin_bit_cast(f16x8, xw0[j]) * kLow);
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp1[i]), accI2[j][i], 0, 0, 0);
-        }
-      }
+    for (int kw = 0; kw < 3; ++kw) {
+      const int pix = wm * 64 + kw * dil + r16;
+      a_rd[kw][0] = (unsigned)row_off(pix, q16);
+      a_rd[kw][1] = (unsigned)row_off(pix, 4 + q16);
     }
-    a_off = a_off == (unsigned)((2 + orow) * A_SLOT) ? (unsigned)(orow * A_SLOT) : a_off + (unsigned)A_SLOT;
-    b_off = b_off == (unsigned)(SB - 1) * B_STEP ? 0u : b_off + (unsigned)B_STEP;
-  }
+    const unsigned b_rd0 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, q16));
+    const unsigned b_rd1 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, 4 + q16));
+    const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
+    f32x4 acc16[NT16][MT16], accI2[NT16][MT16];
 #pragma unroll
-  for (int n = 0; n < NT16 * MT16; ++n) acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
-  __syncthreads();
-  const int oyw = oy + orow * dil;                     // this wave's output row
-  if (oyw < p.Ho)                                      // (the second row of a last, odd pair lies below the image: nothing to store)
-    rows_epilogue<CW, MT, NT, TABLE_OFF>(p, smem, acc16, wave, lane, wm, wn, ((img * p.Ho + oyw) * segs + seg) * 128, n0);
+    for (int j = 0; j < NT16; ++j)
+#pragma unroll
+      for (int i = 0; i < MT16; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { acc16[j][i][e] = 0.f; accI2[j][i][e] = 0.f; }
+    unsigned a_off = (unsigned)(orow * A_SLOT), b_off = 0;   // byte offsets of the row-step's pixel slot (kh [+ 1]) and weight stage
+    int t = 0;
+    for (int rs = 0; rs < RS; ++rs) {
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw, ++t) {
+        if (t > 0 && (t & 7) == 0) {                     // the chain of the last eight K-steps joins the sum
+#pragma unroll
+          for (int n = 0; n < NT16 * MT16; ++n) {
+            acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) accI2[n / MT16][n % MT16][e] = 0.f;
+          }
+        }
+        uint4 xp0[MT16], xp1[MT16], xw0[NT16], xw1[NT16];
+#pragma unroll
+        for (int i = 0; i < MT16; ++i) {
+          xp0[i] = *reinterpret_cast<const uint4*>(smem + (a_rd[kw][0] + a_off) + i * 2048);
+          xp1[i] = *reinterpret_cast<const uint4*>(smem + (a_rd[kw][1] + a_off) + i * 2048);
+        }
+#pragma unroll
+        for (int j = 0; j < NT16; ++j) {
+          xw0[j] = *reinterpret_cast<const uint4*>(smem + (b_rd0 + b_off) + (kw * B_TAP + j * 2048));
+          xw1[j] = *reinterpret_cast<const uint4*>(smem + (b_rd1 + b_off) + (kw * B_TAP + j * 2048));
+        }
+        constexpr int NTI = NT16 * MT16;
+#pragma unroll
+        for (int idx = 0; idx < 3 * NTI; ++idx) {
+          const int prod = idx / NTI, n = idx % NTI, j = n / MT16, i = n % MT16;
+          if (prod == 0)
+            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
+          else if (prod == 1)
+            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw1[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
+          else {
+            if (i == 0) xw0[j] = __builtin_bit_cast(uint4, __builtin_bit_cast(f16x8, xw0[j]) * kLow);
+            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp1[i]), accI2[j][i], 0, 0, 0);
+          }
+        }
+      }
+      a_off = a_off == (unsigned)((2 + orow) * A_SLOT) ? (unsigned)(orow * A_SLOT) : a_off + (unsigned)A_SLOT;
+      b_off = b_off == (unsigned)(SB - 1) * B_STEP ? 0u : b_off + (unsigned)B_STEP;
+    }
+#pragma unroll
+    for (int n = 0; n < NT16 * MT16; ++n) acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
+    __syncthreads();
+    const int oyw = c.oy + orow * dil;                   // this wave's output row
+    if (oyw < p.Ho)                                      // (the second row of a last, odd pair lies below the image: nothing to store)
+      rows_epilogue<CW, MT, NT>(p, smem + SCRATCH_OFF, smem + table, acc16, wave, tlane, wm, wn, ((c.img * p.Ho + oyw) * segs + c.seg) * 128, c.n0);
+    if (!WALK) return;
+    tl += gridDim.x;
+    if (tl >= nblk) return;
+    table ^= TABLE_OFF ^ (TABLE_OFF + 2048);
+  }
 }
 
 template <int WN, int NT, int SB, int OR = 1>
 hipError_t launch_rowstep_cfg(const ConvArgs& a, hipStream_t s) {
   constexpr int BN = WN * NT * 32;
-  constexpr int smem = (OR == 2 ? 4 : 3) * kRowBytes + SB * 3 * BN * 128 + 2048;
+  constexpr int smem = rowstep_lds_bytes(BN, SB, OR);
   static std::atomic<unsigned long long> attr_done{0};
+  static int cus[64];                                  // compute units per device: a walking launch has a block for each
   auto kern = &conv3x3_rowstep_kernel<WN, NT, SB, OR>;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
   if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1ull)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return e;
+    int n = 0;
+    e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    if (n < 1) return hipErrorInvalidDevice;
+    cus[dev] = n;
     attr_done.fetch_or(1ull << dev, std::memory_order_release);
   }
   if (a.Co % BN != 0 || a.Wo % 128 != 0) return hipErrorInvalidValue;
   const int pairs = OR == 2 ? rowstep_pairs(a.Ho, a.dil) : a.Ho;
   const int tiles = a.N * pairs * (a.Wo / 128) * (a.Co / BN);
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3((2 * WN * OR + 4) * 64), smem, s, a);
+  const int blocks = rowstep_walks(SB) && tiles > cus[dev] ? cus[dev] : tiles;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3((2 * WN * OR + 4) * 64), smem, s, a);
   return hipGetLastError();
 }
 
