@@ -118,6 +118,7 @@ SIGNATURES = {
     "nbc_get_plan_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "nbc_set_plan_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "nbc_default_conv_tile": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nbc_conv_tile_info": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 4),
     "nbc_bcast_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nbc_set_conv_tile": (C.c_int, [C.c_void_p, C.c_int]),
     "nbc_set_keep_activations": (C.c_int, [C.c_void_p, C.c_int]),

@@ -55,45 +55,18 @@
 //   have nothing else in flight: the waits stay exact.  The MFMA waves still issue no load in the loop and wait for no vmcnt;
 //   their epilogue's stores count on THEIR vmcnt, which no loader wave waits on, and are left to retire under the next K loop.
 //   Registers of the MFMA waves: as a block of one tile (each tile computes its fragment and epilogue addressing anew).
-#include <atomic>
-
+#include "lds_dma.hpp"
 #include "nbc_kernels.hpp"
 #include "split16.hpp"
 
 namespace nbc {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr unsigned kOutOfRange = 0x80000000u;
 constexpr int kRowPx = 144;                         // pixels of a row slot: 128 + 2 * dil, dil <= 8, in whole 8-pixel DMAs
 constexpr int kRowBytes = kRowPx * 128;
 constexpr int kRowParts = kRowPx / 8 / 3;           // LDS-DMAs (8 pixels each) of one row per K-step: a row in three parts
 static_assert(kRowParts * 24 == kRowPx && kRowParts % 2 == 0, "a row slot is three even parts of whole 8-pixel DMAs");
 
-__device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned lds_base, unsigned soff) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %1, %3 offen lds"
-      :
-      : "v"(voff), "s"(rsrc), "s"(lds_base), "s"(soff)
-      : "memory");
-}
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
 // Tile 20: the output rows of an image in pairs (oy, oy + dil): whole groups of 2 dil rows hold dil pairs each (pair q of group g: rows
 // g 2 dil + q and + dil), a last group of fewer rows one pair per row of its first half (the second row of such a pair may lie below
 // the image: computed on zero rows, not stored).  Pair index -> first row: (pr / dil) 2 dil + pr % dil in both cases.
@@ -109,11 +82,6 @@ constexpr int rowstep_tables(int SB) { return rowstep_walks(SB) ? 2 : 1; }
 constexpr int rowstep_lds_bytes(int BN, int SB, int OR) { return (OR == 2 ? 4 : 3) * kRowBytes + SB * 3 * BN * 128 + rowstep_tables(SB) * 2048; }
 static_assert(rowstep_lds_bytes(64, 2, 2) == 124 * 1024 && rowstep_lds_bytes(128, 2, 1) == 154 * 1024 && rowstep_lds_bytes(64, 3, 1) == 128 * 1024,
               "tile 20: 124 KiB, tile 18: 154 KiB, tile 19: 128 KiB of the CU's 160");
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Epilogue (conv_igemm_dma.hip's f16x2 path without identity, instruction for instruction): BN on the
 // accumulators into a per-wave f32 scratch in the idle ring, read back row-wise, ReLU, split, whole row segments stored.
@@ -430,17 +398,7 @@ hipError_t launch_rowstep_cfg(const ConvArgs& a, hipStream_t s) {
   static int cus[64];                                  // compute units per device: a walking launch has a block for each
   auto kern = &conv3x3_rowstep_kernel<WN, NT, SB, OR>;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return e;
-    int n = 0;
-    e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    if (n < 1) return hipErrorInvalidDevice;
-    cus[dev] = n;
-    attr_done.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (hipError_t e = raise_lds_limit_once(attr_done, reinterpret_cast<const void*>(kern), smem, &dev, cus); e != hipSuccess) return e;
   if (a.Co % BN != 0 || a.Wo % 128 != 0) return hipErrorInvalidValue;
   const int pairs = OR == 2 ? rowstep_pairs(a.Ho, a.dil) : a.Ho;
   const int tiles = a.N * pairs * (a.Wo / 128) * (a.Co / BN);
@@ -449,34 +407,27 @@ hipError_t launch_rowstep_cfg(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-}  // namespace
-
-// Whether a convolution runs on the kernels of this file (f16x2): 3x3, stride 1, padding = dilation <= 8, no identity, and
-//   kind 1: 128-pixel-wide maps, 256 output channels or more (layer3 / layer4 conv2, classifier.0 of a 1024-pixel-wide image):
-//           tile 18 or tile 20 (the same K order and bits; the cost model's default is 20);
-//   kind 2: 128-pixel-wide maps, 64 or 128 output channels (layer2.1-3 conv2): tile 19;
-//   0: neither (the generic kernel).  A property of the layer and its shape: the K order follows from it (the head of this file).
-int conv_rows_kind(int precision, int k, int stride, int pad, int dil, int Hi, int Wi, int Ho, int Wo, int Ci, int Co, bool has_res) {
-  if (!(precision == 2 && k == 3 && stride == 1 && pad == dil && dil >= 1 && dil <= 8 && Ho == Hi && Wo == Wi && Ci % 32 == 0 && !has_res)) return 0;
-  if (Wi == 128 && Co >= 256 && Co % 128 == 0) return 1;
-  // (maps of 256 pixels -- layer1's conv2, two segments per row -- run on this kernel as well, and no faster than on the generic
-  // tiles, which keep two blocks per CU there: profiles/r05_rowstep_kernel_layer1_layer2.log; left to them)
-  if (Wi == 128 && Co % 64 == 0 && Co < 256) return 2;
-  return 0;
+// The row-step tile `tile` of the menu (conv_tiles.hpp) for a convolution of its kind: <WN, NT, SB, OR> from the row
+template <int I = 0>
+hipError_t launch_rows_tile(const ConvArgs& a, int tile, int kind, hipStream_t s) {
+  if constexpr (I == CONV_TILE_COUNT) return hipErrorInvalidValue;
+  else {
+    constexpr ConvTile t = kConvTiles[I];
+    if constexpr (t.kind != 0) {
+      if (tile == I && kind == t.kind) return launch_rowstep_cfg<t.wn, t.nt, t.s[2], t.wm / 2>(a, s);
+    }
+    return launch_rows_tile<I + 1>(a, tile, kind, s);
+  }
 }
 
-// rows_tile (tile id - 18): 0 = one image row x 128 channels (eight 64x32 MFMA waves + four loader waves; kind 1),
-// 1 = one image row x 64 channels (four MFMA + four loader waves; kind 2), 2 = two image rows x 64 channels (eight + four; kind 1)
-hipError_t launch_conv3x3_rows(const ConvArgs& a, int rows_tile, hipStream_t s) {
+}  // namespace
+
+hipError_t launch_conv3x3_rows(const ConvArgs& a, int tile, hipStream_t s) {
   if (a.x_bytes == 0 || a.x_bytes >= kOutOfRange || a.w_bytes == 0 || a.w_bytes >= kOutOfRange) return hipErrorInvalidValue;
   if (a.stem || a.KH != 3 || a.KW != 3 || a.ksteps != 9 * (a.Ci * 4 / 128) ||
       a.M != a.N * a.Ho * a.Wo)
     return hipErrorInvalidValue;
-  const int kind = conv_rows_kind(2, a.KH, a.stride, a.pad, a.dil, a.Hi, a.Wi, a.Ho, a.Wo, a.Ci, a.Co, a.res != nullptr);
-  if (rows_tile == 0 && kind == 1) return launch_rowstep_cfg<4, 1, 2>(a, s);
-  if (rows_tile == 1 && kind == 2) return launch_rowstep_cfg<2, 1, 3>(a, s);
-  if (rows_tile == 2 && kind == 1) return launch_rowstep_cfg<2, 1, 2, 2>(a, s);
-  return hipErrorInvalidValue;
+  return launch_rows_tile(a, tile, conv_rows_kind(2, a.KH, a.stride, a.pad, a.dil, a.Hi, a.Wi, a.Ho, a.Wo, a.Ci, a.Co, a.res != nullptr), s);
 }
 
 }  // namespace nbc

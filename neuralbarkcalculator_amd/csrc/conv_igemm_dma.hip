@@ -23,8 +23,7 @@
 //
 // D[n][m] orientation: weights are the MFMA A operand, pixels the B operand, so a lane
 // ends up holding one pixel (column) and groups of four consecutive output channels (rows).
-#include <atomic>
-
+#include "lds_dma.hpp"
 #include "nbc_kernels.hpp"
 #include "split16.hpp"
 
@@ -33,51 +32,13 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-  return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
   return __builtin_bit_cast(float, (unsigned)b << 16);
 }
 __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
   __bf16 b = (__bf16)f;
   return __builtin_bit_cast(unsigned short, b);
-}
-
-// One LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses to lds_base .. lds_base+1023.
-// M0 carries the wave-uniform LDS base; it is compiler-reserved, so it is saved, written and
-// restored inside the one statement that uses it.
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
-
-// The same through a buffer resource: 64 lanes x 16 bytes from `rsrc` base + per-lane 32-bit offset + a
-// wave-uniform scalar offset.  Three instructions per DMA instead of seven (no 64-bit pointer per row to
-// advance, no M0 save/restore): every instruction a SIMD issues beside its MFMAs costs the matrix pipe
-// about its own issue time (tools/mfma_f32_probe.hip).  A lane whose offset lies outside the resource
-// (halo and tail lanes: kOutOfRange) gets zeros from the hardware's range check: no zero page.
-// M0 is written and left: nothing else in this kernel reads it (the scale/shift DMAs above restore it).
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr unsigned kOutOfRange = 0x80000000u;      // >= every resource size (activations and weights stay below 2 GiB)
-__device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned lds_base, unsigned soff) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %1, %3 offen lds"
-      :
-      : "v"(voff), "s"(rsrc), "s"(lds_base), "s"(soff)
-      : "memory");
 }
 
 // Diagnostic build (tools/conv_timeline.hip, -DNBC_STAMPS): thread 0 of every block writes the 100 MHz
@@ -129,11 +90,6 @@ __device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned l
 #define NBC_STAMP_WAVE_WAITS() do { } while (0)
 #define NBC_STAMP_BLOCK_END() do { } while (0)
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // LDS bytes of the ring (it also hosts the epilogue's per-wave transpose scratch, which is larger than
 // the ring on the 8-wave 128x128 tile); the scale/shift table sits right behind it.
@@ -1093,223 +1049,42 @@ template <int PREC, int WM, int WN, int MT, int NT, int S, bool STEM, int VAR = 
 hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
   constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
   constexpr int smem = ring_bytes(PREC, WM, WN, MT, NT, S) + (VAR == kVarDualBranch ? 4096 : 2048);     // ring (or scratch) + scale/shift table(s)
-  static std::atomic<unsigned long long> attr_done{0};     // bit d: attribute set on device d (one context per device)
+  static std::atomic<unsigned long long> attr_done{0};
   auto kern = &conv_dma_kernel<PREC, WM, WN, MT, NT, S, STEM, VAR, BIGW>;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return hipErrorInvalidDevice;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1ull)) {   // setting it twice from two threads is harmless
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (hipError_t e = raise_lds_limit_once(attr_done, reinterpret_cast<const void*>(kern), smem, &dev); e != hipSuccess) return e;
   if (a.Co % BN != 0) return hipErrorInvalidValue;
   const int tiles = ((a.M + BM - 1) / BM) * (a.Co / BN);
   hipLaunchKernelGGL(kern, dim3(tiles), dim3((WM * WN + loader_waves(VAR)) * 64), smem, s, a);
   return hipGetLastError();
 }
 
-// The tile menu.  rows x cols = pixels x channels; "blocks/CU" is what the LDS ring (and the registers) allow.
-//   id  tile      waves (m x n)  wave tile  stages  LDS      blocks/CU
-//   0   128x64    2x2            64x32      3       72 KiB   2
-//   1   128x128   2x2            64x64      2       64 KiB   2
-//   2   256x128   4x2            64x64      3       144 KiB  1   (no f16x2 form: it spills)
-//   3   256x256   2x4            128x64     2       128 KiB  1   (bf16 only)
-//   4   128x128   2x2            64x64      4       128 KiB  1   (deeper prefetch; f32 / bf16)
-//   5   128x256   2x4            64x64      3       144 KiB  1
-//   6   256x64    4x2            64x32      3       120 KiB  1
-//   7   128x64    2x2            64x32      2       48 KiB   3   (short-K layers: K fits two stages)
-//   8   64x128    1x4            64x32      2       48 KiB   3
-//   9   128x128   4x2            32x64      2       70 KiB   2   (8 waves: short-K layers, where the
-//   10  128x64    4x2            32x32      2       48 KiB   3    serial prologue/epilogue code dominates
-//   11  256x128   4x4            64x32      2       96 KiB   1    and more waves run it in parallel)
-//   12  256x256   4x4            64x64      2       128 KiB  1   (bf16: short-K layers at batch >= 2; the matrix pipe is
-//                                                               busier than with 8 waves, the clock lower: same TFLOP/s on
-//                                                               long-K layers, 2-5 % faster epilogue-heavy 1x1 layers)
-//   13  128x128   2x4            64x32      3       96 KiB   1   (8 waves)
-//   f16x2 only (9, 10 there with three stages):
-//   14  128x128   2x4 + 4        64x32      3       96 KiB   1   (13 with four loader waves, kVarLoaderWaves: the tile of a layer whose
-//                                                               128x128 tiles number 256 or fewer, one per CU: layer3 at batch 1)
-//   15  128x64    4x2 + 4        32x32      3       72 KiB   1   (10 with four loader waves; layer2's 3x3 at batch 1)
-//   16  128x128   2x2 + 4        64x64      3       96 KiB   1   (four MFMA waves of 64x64 + four loader waves: ties 14)
-//   17  128x128   2x4            64x32      2       64 KiB   2   (13 with two stages at 128 registers: TWO blocks per CU, one's
-//                                                               barrier waits, prologue and epilogue under the other's MFMAs;
-//                                                               the tile of every layer with two or more 128x128 tiles per
-//                                                               CU: 0.51 of the mode's peak on the head conv and layer4's
-//                                                               3x3 against 0.45 for tile 14)
-template <int PREC, bool STEM, int VAR>
+// Tile `tile` of the menu (conv_tiles.hpp) for this precision: a compile-time walk over the table instantiates, per row that has
+// the precision, the plain form and the forms the row is flagged for.
+//   BIGW: f16x2 identity layers with 3 MiB of weights or more (layer4's conv3) on the 128-channel tiles they run on: see BIGW in the kernel
+//   dual: ConvArgs::x2 (kVarDualBranch in the kernel)
+template <int PREC, bool STEM, int VAR, int I = 0>
 hipError_t launch_tile(const ConvArgs& a, int tile, hipStream_t s) {
-  if constexpr (PREC == 2) {             // f16x2 (two accumulator sets: 64x64 wave tiles at most)
-    // identity layers with 3 MiB of weights or more (layer4's conv3) on the 128-channel tiles they run on: see BIGW in the kernel
-    if constexpr (!STEM) {
-      if (a.res != nullptr && a.w_bytes >= (3u << 20)) {
-        if (tile == 17) return launch_cfg<PREC, 2, 4, 2, 1, 2, false, VAR, true>(a, s);
-        if (tile == 1) return launch_cfg<PREC, 2, 2, 2, 2, 2, false, VAR, true>(a, s);
-        if (tile == 14) return launch_cfg<PREC, 2, 4, 2, 1, 3, false, kVarLoaderWaves, true>(a, s);
+  if constexpr (I == CONV_TILE_COUNT) return hipErrorInvalidValue;
+  else {
+    constexpr ConvTile t = kConvTiles[I];
+    if constexpr (t.kind == 0 && t.s[PREC] != 0) {
+      if (tile == I) {
+        constexpr int V = ((t.flags & kTileLoaderWaves) && !STEM) ? kVarLoaderWaves : VAR;
+        if constexpr (PREC == 2 && !STEM && (t.flags & kTileBigW) != 0) {
+          if (a.res != nullptr && a.w_bytes >= (3u << 20)) return launch_cfg<PREC, t.wm, t.wn, t.mt, t.nt, t.s[PREC], false, V, true>(a, s);
+        }
+        if constexpr (PREC == 2 && !STEM && (t.flags & kTileDual) != 0) {
+          if (a.x2 != nullptr) return launch_cfg<PREC, t.wm, t.wn, t.mt, t.nt, t.s[PREC], false, kVarDualBranch>(a, s);
+        }
+        return launch_cfg<PREC, t.wm, t.wn, t.mt, t.nt, t.s[PREC], STEM, V>(a, s);
       }
     }
-    switch (tile) {
-      case 0: return launch_cfg<PREC, 2, 2, 2, 1, 3, STEM, VAR>(a, s);
-      case 1: return launch_cfg<PREC, 2, 2, 2, 2, 2, STEM, VAR>(a, s);
-      case 5: return launch_cfg<PREC, 2, 4, 2, 2, 3, STEM, VAR>(a, s);
-      case 16: return launch_cfg<PREC, 2, 2, 2, 2, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);    // 128x128 of 64x64 wave tiles + four loader waves
-      case 17:                                                                          // 13 with two stages: two blocks per CU
-        if constexpr (!STEM) {
-          if (a.x2 != nullptr) return launch_cfg<PREC, 2, 4, 2, 1, 2, false, kVarDualBranch>(a, s);
-        }
-        return launch_cfg<PREC, 2, 4, 2, 1, 2, STEM, VAR>(a, s);
-      case 6: return launch_cfg<PREC, 4, 2, 2, 1, 3, STEM, VAR>(a, s);
-      case 7: return launch_cfg<PREC, 2, 2, 2, 1, 2, STEM, VAR>(a, s);
-      case 8:
-        if constexpr (!STEM) {
-          if (a.x2 != nullptr) return launch_cfg<PREC, 1, 4, 2, 1, 2, false, kVarDualBranch>(a, s);
-        }
-        return launch_cfg<PREC, 1, 4, 2, 1, 2, STEM, VAR>(a, s);
-      case 9: return launch_cfg<PREC, 4, 2, 1, 2, 3, STEM, VAR>(a, s);
-      case 10:
-        if constexpr (!STEM) {
-          if (a.x2 != nullptr) return launch_cfg<PREC, 4, 2, 1, 1, 3, false, kVarDualBranch>(a, s);
-        }
-        return launch_cfg<PREC, 4, 2, 1, 1, 3, STEM, VAR>(a, s);
-      case 13: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, VAR>(a, s);
-      case 14: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);     // 13 with four loader waves
-      case 15: return launch_cfg<PREC, 4, 2, 1, 1, 3, STEM, STEM ? VAR : kVarLoaderWaves>(a, s);     // 10 with four loader waves
-      default: return hipErrorInvalidValue;
-    }
-  } else
-  switch (tile) {
-    case 0: return launch_cfg<PREC, 2, 2, 2, 1, 3, STEM, VAR>(a, s);
-    case 1: return launch_cfg<PREC, 2, 2, 2, 2, 2, STEM, VAR>(a, s);
-    case 2: return launch_cfg<PREC, 4, 2, 2, 2, 3, STEM, VAR>(a, s);
-    case 3:
-      if constexpr (PREC == 0) return hipErrorInvalidValue;   // 2 x 128 accumulator registers: no f32 form
-      else return launch_cfg<PREC, 2, 4, 4, 2, 2, STEM, VAR>(a, s);
-    case 4: return launch_cfg<PREC, 2, 2, 2, 2, 4, STEM, VAR>(a, s);
-    case 5: return launch_cfg<PREC, 2, 4, 2, 2, 3, STEM, VAR>(a, s);
-    case 6: return launch_cfg<PREC, 4, 2, 2, 1, 3, STEM, VAR>(a, s);
-    case 7: return launch_cfg<PREC, 2, 2, 2, 1, 2, STEM, VAR>(a, s);
-    case 8: return launch_cfg<PREC, 1, 4, 2, 1, 2, STEM, VAR>(a, s);
-    case 9: return launch_cfg<PREC, 4, 2, 1, 2, PREC == 0 ? 3 : 2, STEM, VAR>(a, s);    // f32: three slots (96 KiB, fragment prefetch)
-    case 10: return launch_cfg<PREC, 4, 2, 1, 1, PREC == 0 ? 3 : 2, STEM, VAR>(a, s);   // f32: 72 KiB, two blocks per CU
-    case 11: return launch_cfg<PREC, 4, 4, 2, 1, 2, STEM, VAR>(a, s);
-    case 12:
-      if constexpr (PREC == 0) return hipErrorInvalidValue;
-      else return launch_cfg<PREC, 4, 4, 2, 2, 2, STEM, VAR>(a, s);   // bf16 only (f32: 128-register budget)
-    case 13: return launch_cfg<PREC, 2, 4, 2, 1, 3, STEM, VAR>(a, s);
-    default: return hipErrorInvalidValue;
+    return launch_tile<PREC, STEM, VAR, I + 1>(a, tile, s);
   }
 }
 
-//   18  128x128   row-step kernel (conv3x3_rows.hip: ONE image row x 128 channels, eight 64x32 MFMA waves + four loader waves, the
-//                                row in LDS for its three taps, one barrier per (channel block, kh)): the 3x3 layers of
-//                                128-pixel-wide maps with 256 output channels or more run on it or on tile 20
-//   19  128x64    row-step kernel (one image row x 64 channels, four MFMA + four loader waves): likewise those with 64 / 128
-//                                output channels (layer2.1-3 conv2; conv_rows_kind)
-//   20  256x64    row-step kernel (TWO image rows, a dilation apart, x 64 channels; eight MFMA + four loader waves): the layers of
-//                                tile 18, same K order and bits, 27 % fewer bytes into LDS per product: their default
-constexpr int kTileRows[CONV_TILE_COUNT] = {128, 128, 256, 256, 128, 128, 256, 128, 64, 128, 128, 256, 256, 128, 128, 128, 128, 128, 128, 128, 256};
-constexpr int kTileCols[CONV_TILE_COUNT] = {64, 128, 128, 256, 128, 256, 64, 64, 128, 128, 64, 128, 256, 128, 128, 64, 128, 128, 128, 64, 64};
-
 }  // namespace
-
-int conv_tile_rows(int tile) { return tile >= 0 && tile < CONV_TILE_COUNT ? kTileRows[tile] : 0; }
-int conv_tile_cols(int tile) { return tile >= 0 && tile < CONV_TILE_COUNT ? kTileCols[tile] : 0; }
-
-// Whether tile id `tile` exists for this precision and divides the layer's output channels.
-bool conv_tile_ok(int precision, int tile, int Co, int rows_kind) {
-  if (tile < 0 || tile >= CONV_TILE_COUNT) return false;
-  // the row-resident 3x3 kernel's tiles and the generic ones: never mixed (kind 1: tiles 18 or 20, same K order and bits;
-  // kind 2: tile 19; kind 0: 0 .. 17)
-  const int tile_kind = tile < CONV_TILE_ROWS_FIRST ? 0 : tile == 19 ? 2 : 1;
-  if (rows_kind != tile_kind) return false;
-  if (rows_kind != 0) return precision == 2 && Co % kTileCols[tile] == 0;
-  if (precision == 0 && (tile == 3 || tile == 12)) return false;   // the f32 kernel keeps two accumulator sets
-  if (precision == 2 && (tile == 2 || tile == 3 || tile == 4 || tile == 11 || tile == 12)) return false;   // f16x2: no wave tiles of 128x64, no
-                                                                   // 16-wave blocks; the 256x128 tile of 64x64 wave tiles spills
-  if (precision != 2 && tile >= 14) return false;                  // the loader-wave tile is f16x2's (in bf16 a 256x128 tile
-                                                                   // with loader waves ties the one without: section 6.4)
-  return Co % kTileCols[tile] == 0;
-}
-
-// 17: conv3 of layer1.0, layer2.0 and layer3.0 at full size; 8 and 10: the same layers on small images
-bool conv_tile_has_dual(int precision, int tile) { return precision == 2 && (tile == 17 || tile == 8 || tile == 10); }
-
-// Default tile of a layer (what runs unless nbc_autotune has measured): the cheapest under a small cost model.
-// A launch takes as long as the CU with the most blocks: b = ceil(blocks / 256) of them, run in groups of cap[t] -- the
-// blocks of that tile a CU holds at once (LDS and registers): they share its matrix pipes, and their prologues and
-// epilogues overlap -- that is g = b / cap full groups and a rest of r = b % cap blocks:
-//   (g * cap / eff[t] + r / eff_r) * tile FLOPs / per-CU matrix rate  +  b * tile bytes * cb[t] / (50 GB/s)  +  ceil(b / cap) * ovh[t]
-// (K = Cin*kh*kw products per output; tile bytes = the (rows + cols) x K operand panels + twice the output tile; eff_r
-// lies between eff1[t], one block alone on its CU, and eff[t], cap blocks together).  What matters most is the block
-// count: a 640x1024 image has 10 240 pixels at stride 8, so the head conv on 128x128 tiles is 320 blocks = two rounds of
-// which the second is a quarter full, on 64x128 tiles 640 blocks = three per CU, a third faster; and whether a tile's
-// blocks come in pairs: the f16x2 128x128 tile of eight waves at two blocks per CU runs the long-K layers at 0.51 of
-// the mode's peak when every CU has two (or four) of them and at 0.33 when it has one, where the one-block-per-CU tiles
-// (14 with loader waves, 5 with 64x64 wave tiles) reach 0.40-0.55.  Constants fitted to per-layer timings of every tile (scripts/tile_model_probe.py,
-// scripts/fit_tile_model.py): f32 and bf16 on 28 (precision, batch, height) cases (profiles/r02_tile_model_fit.log:
-// within 0.1-0.5 % (f32) / 0.4-4.4 % (bf16) of the per-layer best, which is where nbc_autotune lands too); f16x2 on
-// eight cases (profiles/r04_tile_model_fit_f16x2.log: 0.2-1.6 % from the per-layer best, 0.9 % on average, and the same when
-// every constant is perturbed by +-2 %: no choice sits on a knife edge).
-namespace {
-struct TileModel {
-  double cu_flops_per_us;              // per-CU matrix rate the efficiencies refer to
-  double eff[CONV_TILE_COUNT], eff1[CONV_TILE_COUNT], ovh_us[CONV_TILE_COUNT], cb[CONV_TILE_COUNT];
-  int cap[CONV_TILE_COUNT];
-};
-constexpr TileModel kTileModel[3] = {
-    // f32: 157.3 TF / 256 CUs
-    {157.3e6 / 256.0,
-     {0.85, 0.85, 0.85, 0.85, 0.85, 0.896, 0.722, 0.811, 0.894, 0.85, 0.85, 0.85, 0.85, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80},
-     {0.85, 0.85, 0.85, 0.85, 0.85, 0.896, 0.722, 0.811, 0.894, 0.85, 0.85, 0.85, 0.85, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80},
-     {4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 5.08, 3.14, 0.76, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0},
-     {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-     {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}},
-    // bf16: against the 1 400 TF/s the chip sustains on this kernel (power-limited), / 256 CUs
-    {1400.0e6 / 256.0,
-     {0.888, 0.85, 0.85, 0.897, 0.85, 0.911, 0.85, 0.85, 0.85, 0.754, 0.85, 0.85, 0.85, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80},
-     {0.888, 0.85, 0.85, 0.897, 0.85, 0.911, 0.85, 0.85, 0.85, 0.754, 0.85, 0.85, 0.85, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80, 0.80},
-     {1.19, 4.0, 4.0, 2.78, 4.0, 4.0, 4.0, 0.0, 4.0, 0.5, 4.0, 4.0, 3.61, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0, 4.0},
-     {0.91, 1.0, 1.0, 1.07, 1.0, 0.78, 1.0, 1.03, 1.0, 0.68, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0},
-     {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}},
-    // f16x2: f32-equivalent FLOPs against the 839 TF/s three f16 MFMAs per product allow (2 517 / 3), / 256 CUs
-    {839.0e6 / 256.0,
-     {0.421, 0.52, 0.5, 0.5, 0.5, 0.535, 0.42, 0.476, 0.42, 0.42, 0.455, 0.5, 0.5, 0.44, 0.47, 0.4, 0.448, 0.501, 0.50, 0.45, 0.515},
-     {0.38, 0.36, 0.5, 0.5, 0.5, 0.535, 0.42, 0.383, 0.36, 0.42, 0.392, 0.5, 0.5, 0.44, 0.47, 0.4, 0.448, 0.36, 0.50, 0.45, 0.515},
-     {3, 3, 3, 3, 3, 3.45, 3.007, 3, 2.746, 3, 2.868, 3, 3, 2.518, 3.874, 3, 3, 3.321, 4.0, 3.0, 4.0},
-     {0.3, 0.3, 0.3, 0.3, 0.3, 0.3, 0.309, 0.31, 0.272, 0.3, 0.3, 0.3, 0.3, 0.3, 0.3, 0.3, 0.3, 0.195, 0.2, 0.3, 0.2},
-     {2, 2, 1, 1, 1, 1, 1, 3, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1}}};
-}  // namespace
-
-int choose_conv_tile(int M, int Co, int K, int precision, int rows_kind) {
-  if (precision < 0 || precision > 2) return -1;
-  const TileModel& tm = kTileModel[precision];
-  const double eb = precision == 1 ? 2.0 : 4.0;
-  int best = -1;
-  double best_cost = 0.0;
-  for (int t = 0; t < CONV_TILE_COUNT; ++t) {
-    if (!conv_tile_ok(precision, t, Co, rows_kind)) continue;
-    const double trows = kTileRows[t], cols = kTileCols[t];
-    const long long blocks = (long long)((M + kTileRows[t] - 1) / kTileRows[t]) * (Co / kTileCols[t]);
-    const long long b = (blocks + 255) / 256;
-    const int cap = tm.cap[t];
-    const long long g = b / cap, rest = b % cap;
-    const double eff_r = cap > 1 && rest > 0 ? tm.eff1[t] + (tm.eff[t] - tm.eff1[t]) * (double)(rest - 1) / (double)(cap - 1) : tm.eff[t];
-    const double flops = trows * cols * 2.0 * K;
-    // operand panels per block: the row-resident kernel fetches a pixel row (144 pixels for 128) once for the three taps of a kernel
-    // row, its two-row tile four rows per channel block for the six (row, kernel row) pairs
-    const double prows = t == 20 ? trows / 4.0 * 1.125 : t >= CONV_TILE_ROWS_FIRST ? trows / 3.0 * 1.125 : trows;
-    const double bytes = (prows + cols) * K * eb + trows * cols * eb * 2.0;
-    const double cost = ((double)(g * cap) / tm.eff[t] + (double)rest / eff_r) * flops / tm.cu_flops_per_us +
-                        (double)b * bytes * tm.cb[t] / 50.0e3 + (double)((b + cap - 1) / cap) * tm.ovh_us[t];
-    // ties (to 1e-9 relative) go to the larger tile: fewer L2 -> LDS bytes per FLOP
-    if (best < 0 || cost < best_cost * (1.0 - 1e-9) ||
-        (cost <= best_cost * (1.0 + 1e-9) && trows * cols > (double)kTileRows[best] * kTileCols[best])) {
-      best = t;
-      best_cost = cost;
-    }
-  }
-  return best;
-}
 
 hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream_t s) {
   const int eb = precision == 1 ? 2 : 4;
@@ -1334,7 +1109,7 @@ hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream
                        ? conv_rows_kind(precision, a.KH, a.stride, a.pad, a.dil, a.Hi, a.Wi, a.Ho, a.Wo, a.Ci, a.Co, a.res != nullptr) : 0;
   if (tile < 0) tile = choose_conv_tile(a.M, a.Co, a.ksteps * (128 / eb), precision, rows);
   if (!conv_tile_ok(precision, tile, a.Co, rows)) return hipErrorInvalidValue;
-  if (rows != 0) return launch_conv3x3_rows(a, tile - CONV_TILE_ROWS_FIRST, s);
+  if (rows != 0) return launch_conv3x3_rows(a, tile, s);
   if (precision == 0) return a.stem ? launch_tile<0, true, kVarDefault>(a, tile, s) : launch_tile<0, false, kVarDefault>(a, tile, s);
   if (precision == 2) return a.stem ? launch_tile<2, true, kVarDefault>(a, tile, s) : launch_tile<2, false, kVarDefault>(a, tile, s);
   if (a.stem) return launch_tile<1, true, kVarDefault>(a, tile, s);

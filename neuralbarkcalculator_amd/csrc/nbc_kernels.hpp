@@ -1,10 +1,12 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
 // efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "conv_tiles.hpp"
 
 namespace nbc {
 
@@ -45,20 +47,20 @@ struct ConvArgs {
 // precision: 0 = f32 (v_mfma_f32_32x32x2_f32), 1 = bf16 (v_mfma_f32_16x16x32_bf16 / v_mfma_f32_32x32x16_bf16),
 // 2 = f16x2 (two f16 pieces per f32 value, three v_mfma_f32_16x16x32_f16 per product: split16.hpp)
 // LDS-DMA ring (conv_igemm_dma.hip).  tile < 0 = choose_conv_tile(M, Co, K, precision).
-constexpr int CONV_TILE_COUNT = 21;   // tile menu: see launch_tile() in conv_igemm_dma.hip; 18, 19, 20 = the row-resident 3x3 kernel
-constexpr int CONV_TILE_ROWS_FIRST = 18;   // (conv3x3_rows.hip: one image row x 128 / 64 channels; 20: two rows x 64 channels)
+// The tile menu -- ids, shapes, precisions, forms, cost-model constants, CONV_TILE_COUNT -- is the one table of conv_tiles.hpp; the host
+// functions below (conv_tiles.cpp) read it.
 int conv_tile_rows(int tile);
 int conv_tile_cols(int tile);
 // Whether a convolution runs on the row-resident 3x3 kernels (conv3x3_rows.hip; f16x2, 3x3, stride 1, no identity): 0 no;
-// 1: 128-pixel-wide maps, >= 256 output channels: tiles 18 or 20 (same K order and bits); 2: 128-pixel-wide maps, 64 / 128 output channels: tile 19.  A property of the layer and its shape that fixes its K order; every other convolution runs on
-// tiles 0 .. 17 only.
+// 1: 128-pixel-wide maps, >= 256 output channels; 2: 128-pixel-wide maps, 64 / 128 output channels.  A property of the layer and its
+// shape that fixes its K order: it runs on the menu's tiles of its kind only, every other convolution on those of kind 0.
 int conv_rows_kind(int precision, int k, int stride, int pad, int dil, int Hi, int Wi, int Ho, int Wo, int Ci, int Co, bool has_res);
 bool conv_tile_ok(int precision, int tile, int Co, int rows_kind);   // the tile exists for the precision and the kind of convolution and divides Co
 bool conv_tile_has_dual(int precision, int tile);   // the tile has the dual-branch form (ConvArgs::x2)
 // K = Cin*kh*kw; the default tile of a layer (cost model); rows_kind: conv_rows_kind
 int choose_conv_tile(int M, int Co, int K, int precision, int rows_kind);
 hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream_t s);
-hipError_t launch_conv3x3_rows(const ConvArgs& a, int rows_tile, hipStream_t s);   // rows_tile: tile id - CONV_TILE_ROWS_FIRST
+hipError_t launch_conv3x3_rows(const ConvArgs& a, int tile, hipStream_t s);   // tile: a row-step tile of the convolution's kind
 
 // float32 NCHW [N,3,H,W] -> NHWC elements padded to 16 bytes per pixel.
 hipError_t launch_ingest_f32(const float* x, void* y, int N, int H, int W, int precision, hipStream_t s);

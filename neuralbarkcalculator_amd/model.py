@@ -130,6 +130,15 @@ def describe_plan(arch: str, precision: str, n: int, h: int, w: int, keep: bool 
     return buf.value.decode()
 
 
+def conv_tile_info(precision: str, tile: int):
+    """(rows, cols, kind, has_dual) of a tile id of the convolution menu (nbc_conv_tile_info; host only), or None where the
+    precision has no such tile."""
+    v = [C.c_int32() for _ in range(4)]
+    if not _lib.load().nbc_conv_tile_info(_PRECISIONS[precision], tile, *[C.byref(x) for x in v]):
+        return None
+    return tuple(x.value for x in v)
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 

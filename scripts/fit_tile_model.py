@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fits the default-tile cost model of csrc/conv_igemm_dma.hip (choose_conv_tile) to the output of
+"""Fits the default-tile cost model of csrc/conv_tiles.cpp (choose_conv_tile; constants: the table of csrc/conv_tiles.hpp) to the output of
 scripts/tile_model_probe.py and reports, per case, how far the model's choice, the rule it replaced and
 nbc_autotune's pick are from the per-layer best.   python scripts/fit_tile_model.py a.json b.json [--fit]
 Without --fit it evaluates the constants below (the ones compiled into the library).
@@ -15,11 +15,16 @@ fixed set of +-2 % perturbations of every constant (a choice that flips under su
 fit lost 16 % when its constants were rounded), then cross-validated between the two files."""
 import json
 import math
+import os
 import random
 import sys
 
-ROWS = [128, 128, 256, 256, 128, 128, 256, 128, 64, 128, 128, 256, 256, 128, 128, 128, 128, 128]
-COLS = [64, 128, 128, 256, 128, 256, 64, 64, 128, 128, 64, 128, 256, 128, 128, 64, 128, 128]
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from neuralbarkcalculator_amd.model import conv_tile_info
+
+# the generic tiles of the menu (kind 0: the row-step kernel's are not a choice), per precision: {tile: (rows, cols, kind, dual)}
+MENU = {p: {t: i for t in range(18) for i in [conv_tile_info(p, t)] if i and i[2] == 0} for p in ("fp32", "bf16", "f16x2")}
+ROWS, COLS = ([next(m[t][k] for m in MENU.values() if t in m) for t in range(18)] for k in (0, 1))
 CAP = {"fp32": [1] * 18, "bf16": [1] * 18,
        "f16x2": [2, 2, 1, 1, 1, 1, 1, 3, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2]}      # blocks per CU (LDS and registers)
 NT = len(ROWS)
@@ -41,15 +46,10 @@ MODEL = {
 }
 for _m in MODEL.values():
     _m.setdefault("eff1", list(_m["eff"]))
-F16X2_TILES = (0, 1, 5, 6, 7, 8, 9, 10, 13, 14, 15, 16, 17)
 
 
 def tile_ok(prec, t, co):
-    if prec == "f16x2" and t not in F16X2_TILES:
-        return False
-    if prec != "f16x2" and t >= 14:
-        return False
-    return not (prec == "fp32" and t in (3, 12)) and co % COLS[t] == 0
+    return t in MENU[prec] and co % COLS[t] == 0
 
 
 def out_hw(name, h, w=1024):

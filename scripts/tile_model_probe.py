@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-layer duration of EVERY conv tile shape on a list of (precision, batch, height) cases: the data behind the
-default-tile cost model of csrc/conv_igemm_dma.hip (choose_conv_tile).  Width is 1024 (the preprocessor's output).
+default-tile cost model of csrc/conv_tiles.cpp (choose_conv_tile).  Width is 1024 (the preprocessor's output).
   gpurun -- 'python scripts/tile_model_probe.py gpurun_out/tiles_a.json "fp32:1:1024 fp32:1:640 bf16:8:1024 ..."'
-For each case: the plan's default tiles and their per-launch times, the times with each of the 13 tiles forced
+For each case: the plan's default tiles and their per-launch times, the times with each generic tile of the menu forced
 wherever it fits the layer (HIP events between launches, mean of 8 forwards), and what nbc_autotune picks."""
 import json
 import os
@@ -12,9 +12,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import numpy as np
 import torch
 from neuralbarkcalculator_amd import synth
-from neuralbarkcalculator_amd.model import FCNResNet50
+from neuralbarkcalculator_amd.model import FCNResNet50, conv_tile_info
 
-N_TILES = 18
 out_path = sys.argv[1]
 cases = [(p, int(b), int(h)) for p, b, h in (c.split(":") for c in sys.argv[2].split())]
 dev = torch.device("cuda", 0)
@@ -39,7 +38,7 @@ for prec, batch, h in cases:
     m.reserve(batch, h, 1024)
     default_tiles = m.plan_tiles()
     per_tile = {}
-    for tile in range(N_TILES):
+    for tile in (t for t in range(64) if (conv_tile_info(prec, t) or (0, 0, 1))[2] == 0):   # the generic tiles this precision has
         m.set_conv_tile(tile)            # forced wherever it fits the layer; elsewhere the planned tile runs
         per_tile[tile] = [q["ms"] for q in records()]
     m.set_conv_tile(-1)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from neuralbarkcalculator_amd import _lib, synth, topology
-from neuralbarkcalculator_amd.model import FCNResNet50, pack_state_dict
+from neuralbarkcalculator_amd.model import FCNResNet50, conv_tile_info, pack_state_dict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -281,10 +281,13 @@ def test_missing_library_is_an_error(monkeypatch, tmp_path):
 
 
 def test_default_conv_tile_cost_model(built_lib):
-    """Host logic of the per-layer default tile (csrc/conv_igemm_dma.hip, choose_conv_tile): a valid tile for the
+    """Host logic of the per-layer default tile (csrc/conv_tiles.cpp, choose_conv_tile): a valid tile for the
     precision and channel count, and the choices that matter most, where whole rounds of blocks on 256 CUs decide."""
-    rows = [128, 128, 256, 256, 128, 128, 256, 128, 64, 128, 128, 256, 256, 128, 128, 128, 128, 128]
-    cols = [64, 128, 128, 256, 128, 256, 64, 64, 128, 128, 64, 128, 256, 128, 128, 64, 128, 128]
+    rows = [128, 128, 256, 256, 128, 128, 256, 128, 64, 128, 128, 256, 256, 128, 128, 128, 128, 128, 128, 128, 256]
+    cols = [64, 128, 128, 256, 128, 256, 64, 64, 128, 128, 64, 128, 256, 128, 128, 64, 128, 128, 128, 64, 64]
+    for t in range(21):                   # the literals are the pin; the menu (csrc/conv_tiles.hpp) has to say the same
+        assert [(rows[t], cols[t])] == list({conv_tile_info(p, t)[:2] for p in ("fp32", "bf16", "f16x2") if conv_tile_info(p, t)}), t
+    assert conv_tile_info("f16x2", 21) is None and conv_tile_info("f16x2", -1) is None
     f = built_lib.nbc_default_conv_tile
     for prec in (0, 1, 2):
         for co in (64, 128, 256, 512, 1024, 2048):

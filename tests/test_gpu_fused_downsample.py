@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from neuralbarkcalculator_amd import synth
-from neuralbarkcalculator_amd.model import FCNResNet50, describe_plan
+from neuralbarkcalculator_amd.model import FCNResNet50, conv_tile_info, describe_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -157,7 +157,7 @@ def test_two_fused_forwards_at_once_are_deterministic(model):
         assert torch.equal(bits(lowres), bits(alone[k][2])), f"stream {k} differs from the same frame alone"
 
 
-DUAL_TILES = (17, 8, 10)     # conv_tile_has_dual of the f16x2 kernel (csrc/conv_igemm_dma.hip)
+DUAL_TILES = (17, 8, 10)     # the tiles flagged kTileDual in the menu (csrc/conv_tiles.hpp), written out: the independent pin
 
 
 def test_the_two_forms_alternate_across_shapes_and_the_plan_cache(model):
@@ -200,6 +200,7 @@ def test_autotune_on_a_context_that_only_ran_fused_then_a_forward(model):
         assert len(convs) == len(tiles) == 54
         conv3 = [tiles[convs.index("backbone.layer%d.0.conv3" % s)] for s in (1, 2, 3)]
         _, _, tuned, pairs = run(m, x)
+        assert sorted(DUAL_TILES) == [t for t in range(21) if (conv_tile_info("f16x2", t) or (0, 0, 0, 0))[3]]
         assert pairs == sum(t in DUAL_TILES for t in conv3), conv3
         assert torch.equal(bits(tuned), bits(want))
     finally:

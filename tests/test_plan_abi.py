@@ -1,10 +1,13 @@
 """The launch plan without a GPU (nbc_describe_plan): which (downsample.0, conv3) pairs the builder marks and the buffers it
 gives them, that no op writes a buffer it reads, that every read finds the tensor the topology implies -- with the pairs as
 two launches and as one --, the pool's sizes, and the launches of an op."""
+import json
+import os
+
 import pytest
 
 from neuralbarkcalculator_amd import topology
-from neuralbarkcalculator_amd.model import describe_plan
+from neuralbarkcalculator_amd.model import conv_tile_info, describe_plan
 
 FCN, DL, EFF = "fcn_resnet50", "deeplabv3_resnet50", "fcn_efficientnet_b0"
 SHAPES = [(n, h, w) for n in (1, 2, 3) for h, w in ((8, 8), (24, 1024), (40, 72), (72, 136), (128, 128), (520, 1024), (1024, 1024))]
@@ -51,6 +54,25 @@ def plans(built_lib):
         else:
             out[case] = parse(describe_plan(arch, prec, n, h, w, keep, bn))
     return out
+
+
+def test_tiles_are_those_recorded_before_the_menu_became_one_table(built_lib, plans):
+    """tests/golden/plan_tiles.json, recorded from the revision whose tile menu was still spread over switches, id lists and
+    parallel arrays: the planned tile of every conv launch of every plan (recorded without keep-activations, which changed no
+    tile then and may change none now), nbc_default_conv_tile over the grid test_abi.py walks, and which precision has which
+    of the 21 tiles."""
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "plan_tiles.json")))
+    assert len(plans) == 2 * len(gold["plans"]) == 318
+    for (arch, prec, bn, keep, n, h, w), (ops, bufs, identity) in plans.items():
+        want = gold["plans"][" ".join(str(x) for x in (arch, prec, bn, n, h, w))]
+        assert [o["tile"] for o in ops if o["kernel"] == "conv_dma"] == want, (arch, prec, bn, keep, n, h, w)
+    g = gold["default_tile"]
+    got = [built_lib.nbc_default_conv_tile(m, co, k, p) for p in g["precision"] for co in g["cout"] for m in g["m"] for k in g["k"]]
+    assert len(got) == 3 * 6 * 8 * 4 and got == g["tile"]
+    exists = [[int(conv_tile_info(p, t) is not None) for t in range(21)] for p in ("fp32", "bf16", "f16x2")]
+    assert exists == gold["exists"]
+    kinds = {conv_tile_info("f16x2", t)[2] for t in (18, 20)}, conv_tile_info("f16x2", 19)[2], {conv_tile_info(p, t)[2] for p in ("fp32", "bf16", "f16x2") for t in range(18) if conv_tile_info(p, t)}
+    assert kinds == ({1}, 2, {0})
 
 
 # what an op reads and writes, by kernel, as fields of its line.  bn_stats names the tensor it reads as `out` as well and
