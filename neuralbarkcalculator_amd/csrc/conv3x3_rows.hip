@@ -26,9 +26,9 @@
 // K order.  (channel block, kh, kw) -- the generic kernel walks (kh, kw, channel block).  The order is a property of the
 // LAYER AND SHAPE, never of the tile: a convolution these kernels take (conv_rows_kind) runs on its one tile whatever the
 // caller forces or the autotuner measures, so logits stay bit-identical across tiles.  Everything else is the generic f16x2
-// arithmetic, instruction for instruction: per 16x16 tile and K-step P.X0, Q.X0, (P 2^-11).X1 on v_mfma_f32_16x16x32_f16
-// into one chain that joins the running f32 sum every eighth K-step; f32 BN + ReLU epilogue through a per-wave LDS
-// transpose, whole 256-byte row segments stored.
+// arithmetic, the same functions (f16x2_mma.hpp): per 16x16 tile and K-step P.X0, Q.X0, (P 2^-11).X1 on
+// v_mfma_f32_16x16x32_f16 into one chain that joins the running f32 sum every eighth K-step; f32 BN + ReLU epilogue through a
+// per-wave LDS transpose, whole 256-byte row segments stored.  This file reads the fragments and walks the tiles.
 //
 // LDS: three row slots (slot = kh: a channel block's three kernel rows; tile 20: four, its four input rows) of 144 pixels x 128 bytes, their 16-byte chunks
 // rotated by the pixel index so that a fragment block may start at ANY pixel without bank conflicts (row_off), and two or
@@ -55,9 +55,8 @@
 //   have nothing else in flight: the waits stay exact.  The MFMA waves still issue no load in the loop and wait for no vmcnt;
 //   their epilogue's stores count on THEIR vmcnt, which no loader wave waits on, and are left to retire under the next K loop.
 //   Registers of the MFMA waves: as a block of one tile (each tile computes its fragment and epilogue addressing anew).
-#include "lds_dma.hpp"
+#include "f16x2_mma.hpp"
 #include "nbc_kernels.hpp"
-#include "split16.hpp"
 
 namespace nbc {
 namespace {
@@ -83,79 +82,30 @@ constexpr int rowstep_lds_bytes(int BN, int SB, int OR) { return (OR == 2 ? 4 : 
 static_assert(rowstep_lds_bytes(64, 2, 2) == 124 * 1024 && rowstep_lds_bytes(128, 2, 1) == 154 * 1024 && rowstep_lds_bytes(64, 3, 1) == 128 * 1024,
               "tile 20: 124 KiB, tile 18: 154 KiB, tile 19: 128 KiB of the CU's 160");
 
-// Epilogue (conv_igemm_dma.hip's f16x2 path without identity, instruction for instruction): BN on the
-// accumulators into a per-wave f32 scratch in the idle ring, read back row-wise, ReLU, split, whole row segments stored.
+// Epilogue: the pieces of f16x2_mma.hpp, as conv_igemm_dma.hip's f16x2 path calls them, without identity: BN on the accumulators
+// into a per-wave f32 scratch in the idle ring, read back row-wise, ReLU, split, whole row segments stored.
 // acc16[j][i]: lane (r16, q16) holds pixel i*16 + r16 and channels j*16 + 4*q16 .. +3 of the wave's (MT*32) x (NT*32) tile.
 // scratch: the block's scratch in LDS (CW x 32 x PITCH bytes, a slab per wave); table: the tile's scale/shift table.
 template <int CW, int MT, int NT>
 __device__ __forceinline__ void rows_epilogue(const ConvArgs& p, unsigned char* scratch, const unsigned char* table_base, f32x4 (&acc16)[2 * NT][2 * MT],
                                               int wave, int lane, int wm, int wn, int m0, int n0) {
-  constexpr int NT16 = 2 * NT;
-  constexpr int SLAB_CH = NT * 32;
-  constexpr int PITCH = SLAB_CH * 4 + 16;
-  constexpr int CPR = SLAB_CH / 8;                  // lanes per pixel row: 8 channels (an h0 chunk and an h1 chunk) each
-  constexpr int PIX_PER_PASS = 64 / CPR;
-  constexpr int PASSES = 32 / PIX_PER_PASS;
-  const int r16 = lane & 15, q16 = lane >> 4;
-  const int o_pix = lane / CPR, o_chunk = lane % CPR;
-  const int n_slab = n0 + wn * SLAB_CH;
-  const unsigned row_bytes = (unsigned)p.Co * 4u;
-  unsigned char* ytile = static_cast<unsigned char*>(p.y) + ((size_t)m0 * p.Co + n_slab) * 4;
+  typedef EpiGeom<NT, 2> G;
+  const int o_pix = lane / G::CPR, o_chunk = lane % G::CPR;
+  const unsigned row_bytes = (unsigned)p.Co * 4u, lane_chunk = G::lane_chunk(o_chunk);
+  unsigned char* ytile = static_cast<unsigned char*>(p.y) + ((size_t)m0 * p.Co + n0 + wn * G::SLAB_CH) * 4;
   const int rows_valid = p.M - m0;
-  const int row0 = wm * MT * 32 + o_pix;
-  const unsigned lane_chunk = (unsigned)(o_chunk >> 2) * 128u + (unsigned)(o_chunk & 3) * 16u;
-  unsigned char* scr = scratch + wave * (32 * PITCH);
-  const unsigned char* table = table_base + wn * SLAB_CH * 4;
+  unsigned char* scr = scratch + wave * (32 * G::PITCH);
+  const unsigned char* table = table_base + wn * G::SLAB_CH * 4;
   const bool relu = p.relu != 0;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
+    bn16_to_scratch<G::PITCH, false>(scr, table, acc16, acc16, i, lane & 15, lane >> 4);
+    float v[G::PASSES][8];
+    epi_read_rows<G>(scr, o_pix, o_chunk, v);
 #pragma unroll
-    for (int j0 = 0; j0 < NT16; j0 += 4) {
-      float4 sc[4], sh[4];
-#pragma unroll
-      for (int jj = 0; jj < 4 && j0 + jj < NT16; ++jj) {
-        const int nl = (j0 + jj) * 16 + 4 * q16;
-        sc[jj] = *reinterpret_cast<const float4*>(table + nl * 4);
-        sh[jj] = *reinterpret_cast<const float4*>(table + 1024 + nl * 4);
-      }
-#pragma unroll
-      for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-        for (int jj = 0; jj < 4 && j0 + jj < NT16; ++jj) {
-          const int nl = (j0 + jj) * 16 + 4 * q16;
-          const f32x4 a = acc16[j0 + jj][2 * i + i2];
-          float4 v;
-          v.x = __builtin_fmaf(a[0], sc[jj].x, sh[jj].x);
-          v.y = __builtin_fmaf(a[1], sc[jj].y, sh[jj].y);
-          v.z = __builtin_fmaf(a[2], sc[jj].z, sh[jj].z);
-          v.w = __builtin_fmaf(a[3], sc[jj].w, sh[jj].w);
-          *reinterpret_cast<float4*>(scr + (i2 * 16 + r16) * PITCH + nl * 4) = v;
-        }
-    }
-    float v[PASSES][8];
-#pragma unroll
-    for (int ps2 = 0; ps2 < PASSES; ++ps2) {
-      const float4* sp = reinterpret_cast<const float4*>(scr + (ps2 * PIX_PER_PASS + o_pix) * PITCH + o_chunk * 32);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const float4 t4 = sp[q];
-        v[ps2][4 * q] = t4.x; v[ps2][4 * q + 1] = t4.y; v[ps2][4 * q + 2] = t4.z; v[ps2][4 * q + 3] = t4.w;
-      }
-    }
-#pragma unroll
-    for (int ps2 = 0; ps2 < PASSES; ++ps2) {
-      const int row = row0 + i * 32 + ps2 * PIX_PER_PASS;
-      const unsigned loff = (unsigned)row * row_bytes + lane_chunk;
-      if (relu) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[ps2][e] = __builtin_elementwise_maximum(v[ps2][e], 0.f);
-      }
-      uint4 o, o1;
-      split16x8(v[ps2], o, o1);
-      if (row < rows_valid) {
-        *reinterpret_cast<uint4*>(ytile + loff + 64) = o1;
-        *reinterpret_cast<uint4*>(ytile + loff) = o;
-      }
+    for (int ps2 = 0; ps2 < G::PASSES; ++ps2) {
+      const int row = wm * MT * 32 + o_pix + i * 32 + ps2 * G::PIX_PER_PASS;
+      x2_store(v[ps2], relu, ytile + ((unsigned)row * row_bytes + lane_chunk), row < rows_valid);
     }
   }
 }
@@ -217,8 +167,7 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
   // tile tl of the launch (block b: tl = b, b + gridDim.x, ...): channel tile, image, (first) output row and segment
   struct Tile { int n0, img, oy, seg; };
   auto tile_at = [&](int tl) __attribute__((always_inline)) {
-    const int q = nblk >> 3, rr = nblk & 7, xcd = tl & 7;
-    const int bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (tl >> 3);
+    const int bid = xcd_tile(tl, nblk);
     const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
     const int R = tile_m / segs, seg = tile_m - R * segs;
     const int img = R / pairs, pr = R - img * pairs;
@@ -243,10 +192,7 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
     for (int tl = blockIdx.x, table = TABLE_OFF;;) {
       const Tile c = tile_at(tl);
       const int n0 = c.n0, img = c.img, oy = c.oy, seg = c.seg;
-      if (wave == CW && lane < BN / 4) {
-        dma16(p.scale + n0 + lane * 4, smem_base + (unsigned)table);
-        dma16(p.shift + n0 + lane * 4, smem_base + (unsigned)table + 1024u);
-      }
+      if (wave == CW && lane < BN / 4) dma_scale_shift(p.scale, p.shift, n0, lane, smem_base + (unsigned)table);
       unsigned w_off[NBW], a_col[LA_HI];
 #pragma unroll
       for (int i = 0; i < NBW; ++i) {
@@ -327,7 +273,6 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
     }
     const unsigned b_rd0 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, q16));
     const unsigned b_rd1 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, 4 + q16));
-    const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
     f32x4 acc16[NT16][MT16], accI2[NT16][MT16];
 #pragma unroll
     for (int j = 0; j < NT16; ++j)
@@ -341,14 +286,7 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
       __builtin_amdgcn_s_barrier();
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw, ++t) {
-        if (t > 0 && (t & 7) == 0) {                     // the chain of the last eight K-steps joins the sum
-#pragma unroll
-          for (int n = 0; n < NT16 * MT16; ++n) {
-            acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) accI2[n / MT16][n % MT16][e] = 0.f;
-          }
-        }
+        x2_flush(t, acc16, accI2);
         uint4 xp0[MT16], xp1[MT16], xw0[NT16], xw1[NT16];
 #pragma unroll
         for (int i = 0; i < MT16; ++i) {
@@ -360,25 +298,12 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
           xw0[j] = *reinterpret_cast<const uint4*>(smem + (b_rd0 + b_off) + (kw * B_TAP + j * 2048));
           xw1[j] = *reinterpret_cast<const uint4*>(smem + (b_rd1 + b_off) + (kw * B_TAP + j * 2048));
         }
-        constexpr int NTI = NT16 * MT16;
-#pragma unroll
-        for (int idx = 0; idx < 3 * NTI; ++idx) {
-          const int prod = idx / NTI, n = idx % NTI, j = n / MT16, i = n % MT16;
-          if (prod == 0)
-            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-          else if (prod == 1)
-            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw1[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-          else {
-            if (i == 0) xw0[j] = __builtin_bit_cast(uint4, __builtin_bit_cast(f16x8, xw0[j]) * kLow);
-            accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp1[i]), accI2[j][i], 0, 0, 0);
-          }
-        }
+        x2_products(xp0, xp1, xw0, xw1, accI2);
       }
       a_off = a_off == (unsigned)((2 + orow) * A_SLOT) ? (unsigned)(orow * A_SLOT) : a_off + (unsigned)A_SLOT;
       b_off = b_off == (unsigned)(SB - 1) * B_STEP ? 0u : b_off + (unsigned)B_STEP;
     }
-#pragma unroll
-    for (int n = 0; n < NT16 * MT16; ++n) acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
+    x2_join<false>(acc16, accI2);
     __syncthreads();
     const int oyw = c.oy + orow * dil;                   // this wave's output row
     if (oyw < p.Ho)                                      // (the second row of a last, odd pair lies below the image: nothing to store)

@@ -23,9 +23,10 @@
 //
 // D[n][m] orientation: weights are the MFMA A operand, pixels the B operand, so a lane
 // ends up holding one pixel (column) and groups of four consecutive output channels (rows).
-#include "lds_dma.hpp"
+// f16x2: the K-step's products, the chain's joins and the epilogue's pieces are f16x2_mma.hpp, the same functions the row-step
+// kernel (conv3x3_rows.hip) calls; only the stem's two-product form is written here.
+#include "f16x2_mma.hpp"
 #include "nbc_kernels.hpp"
-#include "split16.hpp"
 
 namespace nbc {
 namespace {
@@ -170,11 +171,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   const int tiles_n = p.Co / BN;
   const int tiles_m = (p.M + BM - 1) / BM;
   const int nblk = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, rr = nblk & 7, xcd = bid & 7;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-  }
+  const int bid = xcd_tile(blockIdx.x, nblk);
   int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
   // BIGW (f16x2 identity layers whose weights alone fill an XCD's 4 MiB L2 -- layer4's conv3: 2048 x 512 x 4 B; chosen by
   // launch_tile): a 4 x 2 grid of XCDs over (pixel tiles, channel tiles) halves the weights an XCD walks, and the identity
@@ -202,8 +199,10 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   const int pix_bytes = p.Ci * EB;
   const unsigned wrow_bytes = (unsigned)(DUAL ? p.ksteps2 : p.ksteps) * 128u;
 
+  // (dual-branch form: phase A is this loader on the second operand set, a 1x1 convolution of x2 [N][Hi2][Wi2][Ci2] with stride2
+  // and no padding onto the same output pixels: the selects on DUAL in this loop and in set_tap, constants in every other form.)
   int a_iy0[A_PASSES], a_ix0[A_PASSES], a_img[A_PASSES], a_coff[A_PASSES];
-  if constexpr (!DUAL) {
+  {
     const int hw = p.Ho * p.Wo;
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i) {
@@ -217,9 +216,9 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
         const int rem = m - img * hw;
         const int oy = p.wo_shift >= 0 ? (rem >> p.wo_shift) : rem / p.Wo;
         const int ox = rem - oy * p.Wo;
-        a_iy0[i] = oy * p.stride - p.pad;
-        a_ix0[i] = ox * p.stride - p.pad;
-        a_img[i] = img * p.Hi * p.Wi;
+        a_iy0[i] = oy * (DUAL ? p.stride2 : p.stride) - (DUAL ? 0 : p.pad);
+        a_ix0[i] = ox * (DUAL ? p.stride2 : p.stride) - (DUAL ? 0 : p.pad);
+        a_img[i] = img * (DUAL ? p.Hi2 : p.Hi) * (DUAL ? p.Wi2 : p.Wi);
       } else {
         a_iy0[i] = -(1 << 24);
         a_ix0[i] = 0;
@@ -252,30 +251,12 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i) {
       const int iy = a_iy0[i] + dy, ix = a_ix0[i] + dx;
-      const bool ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-      const unsigned off = (unsigned)(a_img[i] + iy * p.Wi + ix) * (unsigned)pix_bytes + (unsigned)a_coff[i];
+      const bool ok = (unsigned)iy < (unsigned)(DUAL ? p.Hi2 : p.Hi) && (unsigned)ix < (unsigned)(DUAL ? p.Wi2 : p.Wi);
+      const unsigned off = (unsigned)(a_img[i] + iy * (DUAL ? p.Wi2 : p.Wi) + ix) * (unsigned)(DUAL ? p.Ci2 * EB : pix_bytes) + (unsigned)a_coff[i];
       a_off[i] = ok ? off : kOutOfRange;
     }
   };
-  if constexpr (DUAL) {
-    // phase A, the identity branch: a 1x1 convolution of x2 [N][Hi2][Wi2][Ci2] with stride2 and no padding onto the same
-    // output pixels; tail rows (and whatever the stride would push outside) carry an offset outside the resource: zeros
-    const int hw = p.Ho * p.Wo;
-    const unsigned pix2 = (unsigned)p.Ci2 * EB;
-#pragma unroll
-    for (int i = 0; i < A_PASSES; ++i) {
-      const int row = lr + ROWS_PER_PASS * i;
-      const int m = m0 + row;
-      const int img = p.N == 1 ? 0 : (p.hw_shift >= 0 ? (m >> p.hw_shift) : m / hw);
-      const int rem = m - img * hw;
-      const int oy = p.wo_shift >= 0 ? (rem >> p.wo_shift) : rem / p.Wo;
-      const int ox = rem - oy * p.Wo;
-      const int iy = oy * p.stride2, ix = ox * p.stride2;
-      const bool ok = m < p.M && (unsigned)iy < (unsigned)p.Hi2 && (unsigned)ix < (unsigned)p.Wi2;
-      const unsigned off = (unsigned)((img * p.Hi2 + iy) * p.Wi2 + ix) * pix2 + (unsigned)(ps ^ ((row >> 1) & 7)) * 16u;
-      a_off[i] = ok ? off : kOutOfRange;
-    }
-  } else if constexpr (!STEM) set_tap(0, 0);
+  if constexpr (!STEM) set_tap(0, 0);
 
   // DMA d (0..L-1: activation passes first, then weight passes) of K-step t into ring slot `stage`.
   auto issue_one = [&](int d, int t, unsigned sa) __attribute__((always_inline)) {
@@ -476,18 +457,6 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   // staggered tiles: the late half's fragments live across the loop's barrier (elsewhere they are locals of a K-step)
   constexpr bool X2_STAG = STAGGER;                 // ONE predicate: which tiles stagger and whose fragments cross the barrier
   uint4 sp0[X2_STAG ? XM : 1], sp1[X2_STAG ? XM : 1], sw0[X2_STAG ? XN : 1], sw1[X2_STAG ? XN : 1];
-  auto x2_flush = [&](int t) __attribute__((always_inline)) {
-    if constexpr (X2) {
-      if (t > 0 && (t & 7) == 0) {                     // wave-uniform: the chain of the last eight K-steps joins the sum
-#pragma unroll
-        for (int n = 0; n < NT16 * MT16; ++n) {
-          acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) accI2[n / MT16][n % MT16][e] = 0.f;
-        }
-      }
-    }
-  };
   auto x2_read = [&](int stage, uint4 (&xp0)[XM], uint4 (&xp1)[XM], uint4 (&xw0)[XN], uint4 (&xw1)[XN]) __attribute__((always_inline)) {
     if constexpr (X2F) {
       // lane (r16, q16) reads, of row r16 of every 16-row block, chunk q16 (high pieces of channels 8*q16..) and chunk
@@ -509,24 +478,11 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   auto x2_mfma = [&](int t, bool do_issue, int t_issue, int issue_stage, uint4 (&xp0)[XM], uint4 (&xp1)[XM], uint4 (&xw0)[XN], uint4 (&xw1)[XN])
       __attribute__((always_inline)) {
     if constexpr (X2F) {
-      constexpr int NTI = NT16 * MT16;
-      const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
-      // product-major: two MFMAs on one accumulator are NTI instructions apart; the scaled high pieces of a weight
-      // block are formed right in front of the block's third products (four v_pk_mul_f16; hoisting them cost 0-3 %,
-      // profiles/r04_f16x2_kloop_schedule_variants_rejected.log)
-#pragma unroll
-      for (int idx = 0; idx < 3 * NTI; ++idx) {
-        const int prod = idx / NTI, n = idx % NTI, j = n / MT16, i = n % MT16;
-        if (prod == 0)
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-        else if (prod == 1)
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw1[j]), __builtin_bit_cast(f16x8, xp0[i]), accI2[j][i], 0, 0, 0);
-        else {
-          if (i == 0) xw0[j] = __builtin_bit_cast(uint4, __builtin_bit_cast(f16x8, xw0[j]) * kLow);      // P -> P 2^-11, in place
-          accI2[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp1[i]), accI2[j][i], 0, 0, 0);
-        }
-        if (do_issue && (idx + 1) % (3 * NTI / 4) == 0) issue_part((idx + 1) / (3 * NTI / 4) - 1, t_issue, issue_stage);   // wave-uniform
-      }
+      // the refill's four parts, one behind each quarter of the step's MFMAs (wave-uniform)
+      constexpr int QUARTER = 3 * NT16 * MT16 / 4;
+      x2_products(xp0, xp1, xw0, xw1, accI2, [&](int idx) __attribute__((always_inline)) {
+        if (do_issue && (idx + 1) % QUARTER == 0) issue_part((idx + 1) / QUARTER - 1, t_issue, issue_stage);
+      });
     }
   };
 
@@ -539,12 +495,11 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
       constexpr int NTI = NT16 * MT16;
       if constexpr (!STEM) {
         uint4 p0[XM], p1[XM], w0[XN], w1[XN];
-        x2_flush(t);
+        x2_flush(t, acc16, accI2);
         x2_read(stage, p0, p1, w0, w1);
         x2_mfma(t, do_issue, t_issue, issue_stage, p0, p1, w0, w1);
       } else {
-        x2_flush(t);
-        const f16x8 kLow = {kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH, kH1UnscaleH};
+        x2_flush(t, acc16, accI2);
         // stem: a chunk is one tap, pixel [X0 x 4][X1 x 4] (3 channels + a zero), weight [P x 4][Q x 4].  With the weight
         // chunk as (P, P 2^-11) the MFMA sums P.X0 + (P 2^-11).X1, as (Q, 0) it sums Q.X0: two MFMAs per tile and half
 #pragma unroll
@@ -628,19 +583,14 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   };
 
   // ---- epilogue geometry (needed before the last K-step: the identity tile is prefetched there)
-  constexpr int SLAB_CH = NT * 32;                  // channels of the wave's slab
-  constexpr int PITCH = SLAB_CH * 4 + 16;           // f32 scratch row, padded against bank conflicts
-  constexpr int OUT_CH = X2 ? 8 : 16 / EB;          // channels per lane and pass: 16 output bytes (f16x2: an h0 chunk and an h1 chunk)
-  constexpr int CPR = SLAB_CH / OUT_CH;             // 16-byte output chunks per pixel row
-  constexpr int PIX_PER_PASS = 64 / CPR;
-  constexpr int PASSES = 32 / PIX_PER_PASS;
+  typedef EpiGeom<NT, PREC> G;
+  constexpr int SLAB_CH = G::SLAB_CH, PITCH = G::PITCH, OUT_CH = G::OUT_CH, PIX_PER_PASS = G::PIX_PER_PASS, PASSES = G::PASSES;
   // identity prefetch: <= 64 VGPRs per lane, and not on the 128x64 wave tile of the 16x16 path
   // (128 accumulators + 48 fragment registers leave no room: it spilled)
   constexpr bool RES_PREFETCH = (MT * PASSES <= 16) && !(PREC == 1 && VAR == kVarDefault && MT * NT >= 8) && !X2;
   static_assert(WM * WN * 32 * PITCH <= TABLE_OFF, "epilogue scratch must fit below the scale/shift table");
-  // Output addressing: a wave-uniform 64-bit base (first pixel of the tile, first channel of the wave's
-  // slab) plus a 32-bit per-lane offset (row inside the tile x row pitch + the lane's 16-byte chunk).
-  const int o_pix = lane / CPR, o_chunk = lane % CPR;
+  // Output addressing (EpiGeom): wave-uniform base + 32-bit per-lane offset
+  const int o_pix = lane / G::CPR, o_chunk = lane % G::CPR;
   const int n_slab = n0 + wn * SLAB_CH;
   const unsigned row_bytes = (unsigned)p.Co * EB;
   const size_t tile_off = ((size_t)m0 * p.Co + n_slab) * EB;
@@ -648,8 +598,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   const unsigned char* rtile = p.res ? static_cast<const unsigned char*>(p.res) + tile_off : nullptr;
   const int rows_valid = p.M - m0;                  // rows of this tile inside the image batch (>= 1)
   const int row0 = wm * MT * 32 + o_pix;            // + i*32 + pass*PIX_PER_PASS
-  // byte offset of the lane's chunk behind the slab's first channel (f16x2: the h0 chunk; its h1 chunk is 64 bytes on)
-  const unsigned lane_chunk = X2 ? (unsigned)(o_chunk >> 2) * 128u + (unsigned)(o_chunk & 3) * 16u : (unsigned)o_chunk * 16u;
+  const unsigned lane_chunk = G::lane_chunk(o_chunk);
   uint4 rpre[RES_PREFETCH ? MT : 1][RES_PREFETCH ? PASSES : 1];
   // f16x2: the identity tile (an h0 and an h1 chunk per lane and pass) is requested right BEHIND the last K-step's
   // MFMAs -- its fragment registers are free by then -- and arrives under the accumulator sums, the block barrier and
@@ -665,11 +614,8 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-          for (int ps2 = 0; ps2 < PASSES; ++ps2) {
-            int row = row0 + i * 32 + ps2 * PIX_PER_PASS;
-            row = row < rows_valid ? row : rows_valid - 1;   // tail rows read a valid row; never stored
-            rpre[i][ps2] = *reinterpret_cast<const uint4*>(rtile + ((unsigned)row * row_bytes + lane_chunk));
-          }
+          for (int ps2 = 0; ps2 < PASSES; ++ps2)
+            rpre[i][ps2] = *reinterpret_cast<const uint4*>(rtile + ((unsigned)G::id_row(row0 + i * 32 + ps2 * PIX_PER_PASS, rows_valid) * row_bytes + lane_chunk));
       }
     }
   };
@@ -681,16 +627,14 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   // LDS-DMAs of wave 0, older than every ring DMA, so the first counted wait covers them): the
   // epilogue then reads them from LDS instead of paying an L2 round trip per 32-pixel slab.
   if (wave == (SPEC ? CW : 0) && lane < BN / 4) {
-    dma16(p.scale + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF);
-    dma16(p.shift + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF + 1024u);
-    if constexpr (DUAL) {                           // the identity branch's pairs: a second table behind the first
-      dma16(p.scale2 + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF + 2048u);
-      dma16(p.shift2 + n0 + lane * 4, smem_base + (unsigned)TABLE_OFF + 3072u);
-    }
+    dma_scale_shift(p.scale, p.shift, n0, lane, smem_base + (unsigned)TABLE_OFF);
+    // (dual-branch form) the identity branch's pairs: a second table behind the first
+    if constexpr (DUAL) dma_scale_shift(p.scale2, p.shift2, n0, lane, smem_base + (unsigned)TABLE_OFF + 2048u);
   }
   if constexpr (DUAL) {
     static_assert(!DUAL || (!SPEC && !STAGGER && !PREFETCH), "dual-branch form: every wave loads and computes, in lock step");
-    // ---- phase A: the identity branch's K loop, the pipeline below word for word on the second operand set (T2 >= 1 steps)
+    // ---- phase A: the identity branch's K loop, the lock-step pipeline below on the second operand set (T2 >= 1 steps).  A copy:
+    // as one lambda with the main loop it changed the bf16 kernels' machine code
     const int T2 = p.ksteps2;
 #pragma unroll
     for (int s = 0; s < S - 1; ++s)
@@ -805,7 +749,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
       for (int t = 0; t < T - 1; ++t) {
         loop_top(t);
         if constexpr (!SPEC && S == 2) { if (t + S - 1 < T) issue_step(t + S - 1, (t + S - 1) % S); }
-        x2_flush(t);
+        x2_flush(t, acc16, accI2);
         x2_read(t % S, sp0, sp1, sw0, sw1);
         x2_mfma(t, !SPEC && S > 2 && t + S - 1 < T, t + S - 1, (t + S - 1) % S, sp0, sp1, sw0, sw1);
       }
@@ -825,7 +769,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
       for (int t = 1; t < T - 1; ++t) {
         loop_top(t);
         if constexpr (!SPEC && S == 2) { if (t + S - 1 < T) issue_step(t + S - 1, (t + S - 1) % S); }
-        x2_flush(t - 1);
+        x2_flush(t - 1, acc16, accI2);
         x2_mfma(t - 1, !SPEC && S > 2 && t + S - 1 < T, t + S - 1, (t + S - 1) % S, sp0, sp1, sw0, sw1);
         x2_read(t % S, sp0, sp1, sw0, sw1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -861,8 +805,8 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   if constexpr (F32) step32(T - 1, (T - 1) % S, false, false, 0, false, 0, 0);
   else if constexpr (STAGGER) {
     if (computes) {
-      if (late_half && T > 1) { x2_flush(T - 2); x2_mfma(T - 2, false, 0, 0, sp0, sp1, sw0, sw1); }       // the late half catches up
-      x2_flush(T - 1);
+      if (late_half && T > 1) { x2_flush(T - 2, acc16, accI2); x2_mfma(T - 2, false, 0, 0, sp0, sp1, sw0, sw1); }       // the late half catches up
+      x2_flush(T - 1, acc16, accI2);
       x2_read((T - 1) % S, sp0, sp1, sw0, sw1);
       x2_mfma(T - 1, false, 0, 0, sp0, sp1, sw0, sw1);
     }
@@ -874,9 +818,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int ps2 = 0; ps2 < PASSES; ++ps2) {
-          int row = row0 + i * 32 + ps2 * PIX_PER_PASS;
-          row = row < rows_valid ? row : rows_valid - 1;     // tail rows read a valid row; never stored
-          const unsigned char* rp = rtile + ((unsigned)row * row_bytes + lane_chunk);
+          const unsigned char* rp = rtile + ((unsigned)G::id_row(row0 + i * 32 + ps2 * PIX_PER_PASS, rows_valid) * row_bytes + lane_chunk);
           if constexpr (BIGW) {
             rpre2[i][ps2][0] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4*>(rp)));
             rpre2[i][ps2][1] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4*>(rp + 64)));
@@ -893,8 +835,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
     for (int n = 0; n < NTILES; ++n) acc[n / MT][n % MT] += accI[n / MT][n % MT];
   }
   if constexpr (X2 && !DUAL) {                        // likewise (dual-branch form: acc16 holds the identity; see the epilogue)
-#pragma unroll
-    for (int n = 0; n < NT16 * MT16; ++n) acc16[n / MT16][n % MT16] += accI2[n / MT16][n % MT16];
+    x2_join<false>(acc16, accI2);
   }
 
   // ---- epilogue.
@@ -914,41 +855,10 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
   typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    // (a) BN on the accumulators, into the scratch.  The scale/shift reads of a channel group are all
-    // issued before its scratch writes (LDS operations of a wave complete in order, so a table read
-    // behind a scratch write would wait for it).
+    // (a) BN on the accumulators, into the scratch (f16x2_mma.hpp; dual-branch form: acc16 holds the identity, the chain is the sum)
     if constexpr (M16) {
-      // 16x16 D layout: lane (r16, q16) holds pixel r16 and channels 4*q16..4*q16+3 of each tile
-#pragma unroll
-      for (int j0 = 0; j0 < NT16; j0 += 4) {
-        float4 sc[4], sh[4];
-#pragma unroll
-        for (int jj = 0; jj < 4 && j0 + jj < NT16; ++jj) {
-          const int nl = (j0 + jj) * 16 + 4 * q16;
-          sc[jj] = *reinterpret_cast<const float4*>(table + nl * 4);
-          sh[jj] = *reinterpret_cast<const float4*>(table + 1024 + nl * 4);
-        }
-#pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-          for (int jj = 0; jj < 4 && j0 + jj < NT16; ++jj) {
-            const int nl = (j0 + jj) * 16 + 4 * q16;
-            // dual-branch form: the sum is 0 + chain, as in a launch of its own that never joined; the identity is added
-            // here, value for value what the row-wise `+ identity` below adds in the two-launch form
-            const f32x4 kZero = {0.f, 0.f, 0.f, 0.f};
-            const f32x4 a = DUAL ? kZero + accI2[X2 ? j0 + jj : 0][X2 ? 2 * i + i2 : 0] : acc16[j0 + jj][2 * i + i2];
-            float4 v;
-            v.x = __builtin_fmaf(a[0], sc[jj].x, sh[jj].x);
-            v.y = __builtin_fmaf(a[1], sc[jj].y, sh[jj].y);
-            v.z = __builtin_fmaf(a[2], sc[jj].z, sh[jj].z);
-            v.w = __builtin_fmaf(a[3], sc[jj].w, sh[jj].w);
-            if constexpr (DUAL) {
-              const f32x4 idv = acc16[j0 + jj][2 * i + i2];
-              v.x += idv[0]; v.y += idv[1]; v.z += idv[2]; v.w += idv[3];
-            }
-            *reinterpret_cast<float4*>(scr + (i2 * 16 + r16) * PITCH + nl * 4) = v;
-          }
-      }
+      if constexpr (DUAL) bn16_to_scratch<PITCH, true>(scr, table, accI2, acc16, i, r16, q16);
+      else bn16_to_scratch<PITCH, false>(scr, table, acc16, acc16, i, r16, q16);
     } else {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
@@ -972,39 +882,31 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
       }
     }
     if (i == 0) NBC_STAMP(9);                       // first slab in scratch
-    // (b) read the slab back row-wise: every lane gets 16 output bytes of one pixel per pass.  All
-    // reads of the slab are issued before the first use (the scratch is wave-private).
+    // (b) read the slab back row-wise
     float v[PASSES][OUT_CH];
-#pragma unroll
-    for (int ps2 = 0; ps2 < PASSES; ++ps2) {
-      const float4* sp = reinterpret_cast<const float4*>(scr + (ps2 * PIX_PER_PASS + o_pix) * PITCH + o_chunk * OUT_CH * 4);
-#pragma unroll
-      for (int q = 0; q < OUT_CH / 4; ++q) {
-        const float4 t4 = sp[q];
-        v[ps2][4 * q] = t4.x; v[ps2][4 * q + 1] = t4.y; v[ps2][4 * q + 2] = t4.z; v[ps2][4 * q + 3] = t4.w;
-      }
-    }
+    epi_read_rows<G>(scr, o_pix, o_chunk, v);
     // (c) + identity, ReLU (NaN-propagating: v_maximum3_f32), rounding, 16-byte stores in whole row segments
 #pragma unroll
     for (int ps2 = 0; ps2 < PASSES; ++ps2) {
       const int row = row0 + i * 32 + ps2 * PIX_PER_PASS;
       const unsigned loff = (unsigned)row * row_bytes + lane_chunk;
       if constexpr (X2) {
+        uint4 id0 = {}, id1 = {};                     // the identity's h0 and h1 chunks
         if (rtile) {
-          float idv[8];
           if constexpr (RES_PREFETCH2) {
-            join16x8(rpre2[i][ps2][0], rpre2[i][ps2][1], idv);
+            id0 = rpre2[i][ps2][0]; id1 = rpre2[i][ps2][1];
           } else {
-            const unsigned char* rp = rtile + ((unsigned)(row < rows_valid ? row : rows_valid - 1) * row_bytes + lane_chunk);
-            join16x8(*reinterpret_cast<const uint4*>(rp), *reinterpret_cast<const uint4*>(rp + 64), idv);
+            const unsigned char* rp = rtile + ((unsigned)G::id_row(row, rows_valid) * row_bytes + lane_chunk);
+            id0 = *reinterpret_cast<const uint4*>(rp); id1 = *reinterpret_cast<const uint4*>(rp + 64);
           }
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[ps2][q] += idv[q];
         }
-      } else if (rtile) {
+        x2_store(v[ps2], relu, ytile + loff, row < rows_valid, rtile != nullptr, id0, id1);
+        continue;
+      }
+      if (rtile) {
         uint4 rv;
         if constexpr (RES_PREFETCH) rv = rpre[i][ps2];
-        else rv = *reinterpret_cast<const uint4*>(rtile + ((unsigned)(row < rows_valid ? row : rows_valid - 1) * row_bytes + lane_chunk));
+        else rv = *reinterpret_cast<const uint4*>(rtile + ((unsigned)G::id_row(row, rows_valid) * row_bytes + lane_chunk));
         const unsigned u[4] = {rv.x, rv.y, rv.z, rv.w};
         if constexpr (PREC == 0) {
 #pragma unroll
@@ -1022,11 +924,7 @@ __global__ __launch_bounds__((WM * WN + loader_waves(VAR)) * 64, VAR == kVarLoad
         for (int e = 0; e < OUT_CH; ++e) v[ps2][e] = __builtin_elementwise_maximum(v[ps2][e], 0.f);
       }
       uint4 o;
-      if constexpr (X2) {
-        uint4 o1;
-        split16x8(v[ps2], o, o1);
-        if (row < rows_valid) *reinterpret_cast<uint4*>(ytile + loff + 64) = o1;
-      } else if constexpr (PREC == 0) {
+      if constexpr (PREC == 0) {
         o.x = __builtin_bit_cast(unsigned, v[ps2][0]); o.y = __builtin_bit_cast(unsigned, v[ps2][1]);
         o.z = __builtin_bit_cast(unsigned, v[ps2][2]); o.w = __builtin_bit_cast(unsigned, v[ps2][3]);
       } else {

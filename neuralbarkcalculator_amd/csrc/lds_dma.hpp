@@ -1,5 +1,6 @@
 // What the two LDS-DMA convolution kernels (conv_igemm_dma.hip, conv3x3_rows.hip) share: the swizzled LDS row, the DMA
-// instructions, the counted wait, and the once-per-device raise of a kernel's dynamic-LDS limit.
+// instructions, the counted wait, the scale/shift table's DMA, the XCD-aware block -> tile map, and the once-per-device raise
+// of a kernel's dynamic-LDS limit.  (The f16x2 arithmetic they share: f16x2_mma.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +54,20 @@ __device__ __forceinline__ void dma16_buf(unsigned voff, rsrc_t rsrc, unsigned l
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// A block's BN scale/shift pairs (four channels from n0 on per lane of the calling wave) into a 2 KiB LDS table at `lds`, the
+// shifts 1024 bytes behind the scales: the epilogue reads them from there, no L2 round trip per 32-pixel slab.
+__device__ __forceinline__ void dma_scale_shift(const float* scale, const float* shift, int n0, int lane, unsigned lds) {
+  dma16(scale + n0 + lane * 4, lds);
+  dma16(shift + n0 + lane * 4, lds + 1024u);
+}
+
+// XCD-aware block -> tile map: blocks that share an XCD (block % 8) take a contiguous range of the launch's nblk tiles, so the
+// channel tiles of a pixel tile and the halo rows of neighbouring pixel tiles meet in one L2.
+__device__ __forceinline__ int xcd_tile(int block, int nblk) {
+  const int q = nblk >> 3, rr = nblk & 7, xcd = block & 7;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (block >> 3);
 }
 
 // A kernel that asks for more than 64 KiB of dynamic LDS has hipFuncAttributeMaxDynamicSharedMemorySize raised once per device

@@ -171,6 +171,19 @@ UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
           reinterpret_cast<const float*>(c->weights + pc.shift_off)};
 }
 
+// Checks a conv op's operand set against its packed unit and sizes it for the buffer resources (activations and weights stay
+// below 2 GiB: kOutOfRange).
+int conv_operand_bytes(const Op& o, const PackedConv& pc, int N, size_t eb, unsigned* x_bytes, unsigned* w_bytes) {
+  if (o.Ci != pc.cin_pad) return set_error(NBC_ERR_STATE, "plan/channel mismatch at " + o.name);
+  const size_t xb = (size_t)N * o.Hi * o.Wi * o.Ci * eb;
+  const size_t wb = (size_t)o.Co * pc.ksteps * kKStepBytes;
+  if (xb >= 0x80000000ull || wb >= 0x80000000ull)
+    return set_error(NBC_ERR_INVALID, "activation of " + o.name + " exceeds 2 GiB: lower the batch size");
+  *x_bytes = (unsigned)xb;
+  *w_bytes = (unsigned)wb;
+  return NBC_OK;
+}
+
 // One convolution launch of the plan (shared by nbc_forward and nbc_autotune).  ds: the downsample.0 op whose output is this
 // op's identity, to be computed inside this launch (fusable_downsample below), or nullptr.  A downsample.0 of a pair that runs
 // in a launch of its own finds the identity buffer here, allocated or grown on first use: that frees and allocates, so it
@@ -212,29 +225,17 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     if ((1 << sft) == o.Wo) a.wo_shift = sft;
     if ((1 << sft) == o.Ho * o.Wo) a.hw_shift = sft;
   }
-  if (o.Ci != pc.cin_pad) return set_error(NBC_ERR_STATE, "plan/channel mismatch at " + o.name);
-  const size_t xb = (size_t)N * o.Hi * o.Wi * o.Ci * eb;
-  const size_t wbts = (size_t)o.Co * pc.ksteps * kKStepBytes;
-  if (xb >= 0x80000000ull || wbts >= 0x80000000ull)
-    return set_error(NBC_ERR_INVALID, "activation of " + o.name + " exceeds 2 GiB: lower the batch size");
-  a.x_bytes = (unsigned)xb;
-  a.w_bytes = (unsigned)wbts;
+  if (const int rc = conv_operand_bytes(o, pc, N, eb, &a.x_bytes, &a.w_bytes); rc != NBC_OK) return rc;
   if (ds) {                                            // the identity branch's operands; the tensor between the two is never stored
     const ConvUnit& u2 = conv_units(c->arch)[ds->unit];
     const PackedConv& pc2 = c->layout.convs[ds->unit];
     const UnitPtrs p2 = unit_ptrs(c, ds->unit);
-    const size_t xb2 = (size_t)N * ds->Hi * ds->Wi * ds->Ci * eb;
-    const size_t wb2 = (size_t)ds->Co * pc2.ksteps * kKStepBytes;
-    if (ds->Ci != pc2.cin_pad) return set_error(NBC_ERR_STATE, "plan/channel mismatch at " + ds->name);
-    if (xb2 >= 0x80000000ull || wb2 >= 0x80000000ull)
-      return set_error(NBC_ERR_INVALID, "activation of " + ds->name + " exceeds 2 GiB: lower the batch size");
+    if (const int rc = conv_operand_bytes(*ds, pc2, N, eb, &a.x2_bytes, &a.w2_bytes); rc != NBC_OK) return rc;
     a.res = nullptr;
     a.x2 = c->bufs[ds->in_buf];
     a.w2 = p2.w;
     a.scale2 = p2.scale;
     a.shift2 = p2.shift;
-    a.x2_bytes = (unsigned)xb2;
-    a.w2_bytes = (unsigned)wb2;
     a.Ci2 = ds->Ci; a.Hi2 = ds->Hi; a.Wi2 = ds->Wi; a.stride2 = u2.stride; a.ksteps2 = pc2.ksteps;
   }
   if (o.gate_buf >= 0) {                               // EfficientNet's project conv: image n on its SE-gated weights
@@ -244,7 +245,7 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     a.x_bytes = (unsigned)xi;
     for (int n = 0; n < N; ++n) {
       a.x = static_cast<const unsigned char*>(c->bufs[o.in_buf]) + n * xi;
-      a.w = static_cast<const unsigned char*>(c->bufs[o.gate_buf]) + n * wbts;
+      a.w = static_cast<const unsigned char*>(c->bufs[o.gate_buf]) + n * (size_t)a.w_bytes;
       a.res = o.res_buf >= 0 ? static_cast<const unsigned char*>(c->bufs[o.res_buf]) + n * yi : nullptr;
       a.y = static_cast<unsigned char*>(c->bufs[o.out_buf]) + n * yi;
       *err = launch_conv_dma(a, prec, tile, s);
