@@ -82,14 +82,27 @@ def adjudicated_flips(labels_gpu, logits_ref, err, oracle, x):
     return n
 
 
+_HEAD_REF = {}
+
+
+def _head_reference(oracle, size):
+    """The frame and the oracle's head tensors at `size`: computed once, shared by the three modes."""
+    if size not in _HEAD_REF:
+        x = frames([5], *size)
+        _HEAD_REF[size] = (x, deeplab_oracle.head_outputs(oracle, x))
+    return _HEAD_REF[size]
+
+
+@pytest.mark.parametrize("size", [(256, 256), (640, 640)], ids=lambda s: "%dx%d" % s)
 @pytest.mark.parametrize("mode", MODES)
-def test_head_layer_by_layer_against_oracle(oracle, models, mode):
-    """Keep mode at 256 x 256 (a 32 x 32 map: dilation 24 and 36 reach mostly padding): every head tensor, including the
-    pooled vector and the concat, and the logits."""
+def test_head_layer_by_layer_against_oracle(oracle, models, mode, size):
+    """Keep mode: every head tensor, including the pooled vector and the concat, and the logits.  At 256 x 256 (a 32 x 32
+    map) a tap of dilation 24 lands inside the image for only 8 of a row's 32 pixels on either side and a tap of dilation 36
+    for none: those two branches are their centre tap plus, at dilation 24, a fringe.  At 640 x 640 (an 80 x 80 map) pixels
+    36..43 in each direction have all nine taps of every dilation inside the image, and every other pixel a proper subset."""
     m = models[mode]
     rl, rlog = RTOL[mode]
-    x = frames([5], 256, 256)
-    ref = deeplab_oracle.head_outputs(oracle, x)
+    x, ref = _head_reference(oracle, size)
     m.set_keep_activations(True)
     try:
         lowres = m.lowres_logits(x.to(DEV))
@@ -107,7 +120,7 @@ def test_head_layer_by_layer_against_oracle(oracle, models, mode):
             err = float(np.abs(got - want).max())
             report[name] = err / scale
             assert err <= (rlog if name == "classifier.4" else rl) * scale, f"{name}: max err {err} vs scale {scale} ({mode})"
-        print(mode, "head rel err", {k: "%.2e" % v for k, v in report.items()})
+        print(mode, "%dx%d" % size, "head rel err", {k: "%.2e" % v for k, v in report.items()})
         # the calibration guard and the stored powers cover the new tensors by name
         peaks = m.activation_peaks(x.to(DEV))
         assert len(peaks) == len(topology.conv_units(DL)) - 1 and "classifier.0.convs.4.1" in peaks
