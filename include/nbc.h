@@ -124,7 +124,17 @@ enum {
                            True) on a batch of one, what the shipped tool's forward does (models.py:212-250 never calls .eval()
                            and feeds one image at a time).  Running statistics are read by nothing and updated by nothing;
                            Dropout stays the identity (its expectation: live Dropout noise is what remains different from the
-                           shipped tool; nbc_dropout_draws samples it).  NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50 only. */
+                           shipped tool; nbc_dropout_draws samples it).  NBC_ARCH_FCN_RESNET50 in NBC_PREC_FP32 or
+                           NBC_PREC_F16X2 (see nbc_set_bn_statistics for the arithmetic on pieces). */
+};
+
+/* Bits of the context's sticky word (nbc_nonfinite_seen, nbc_nonfinite_peek_async). */
+enum {
+  NBC_NONFINITE_LOGIT = 1,     /* classifier.4 produced a logit that is NaN or infinite */
+  NBC_NONFINITE_BN_RANGE = 2   /* NBC_BN_PER_IMAGE in NBC_PREC_F16X2: a channel's stored raw convolution output lies outside
+                                  the range the pieces hold to 2^-23 (its rms over the image is not finite, above 2^12, or
+                                  positive and below 2^-10): the running statistics misjudge the channel.  Raised by nothing
+                                  outside that mode */
 };
 
 /* Layout of the image handed to nbc_forward. */
@@ -241,6 +251,18 @@ int nbc_packed_weights_arch(const void* blob, size_t blob_bytes, int precision);
 size_t nbc_arch_bn_affine_floats(int arch);
 int nbc_pack_bn_affine(const nbc_tensor* tensors, int n, int arch, float* out, size_t count);
 
+/* The second side array of NBC_BN_PER_IMAGE, read in NBC_PREC_F16X2 only: per conv unit that has a BatchNorm, in conv-unit
+ * order, cout values 2^(r_o - k_o - a_in) and then cout values 2^-r_o, as f32 (the layout and length of the affine array).
+ * k_o is the weight row's power of two and a_in the power of the tensor the unit reads, the very ones nbc_pack_weights folds
+ * into the blob; r_o is the power of two that brings |running_mean_o| + 3 sqrt(max(running_var_o, 0)) into [2, 4) (0 for an
+ * estimate that is 0 or not finite, clamped to [-100, 100]).  The raw convolution runs with the first as its scale table, so
+ * what it stores is 2^r_o conv_o, where the pieces hold it to 2^-23; the statistics kernel takes 2^r_o off with the second.
+ * nbc_arch_bn_raw_floats: the length, 0 for an unknown architecture or one without f16x2.  nbc_pack_bn_raw: the strict key /
+ * shape check of nbc_pack_weights (same errors and messages), then the array into `out`; returns NBC_PACK_* bits (>= 0):
+ * NBC_PACK_SCALE_RANGE when a power leaves f32's normal range, NBC_PACK_ROW_CLAMPED as nbc_pack_weights raises it. */
+size_t nbc_arch_bn_raw_floats(int arch);
+int nbc_pack_bn_raw(const nbc_tensor* tensors, int n, int arch, float* out, size_t count);
+
 /* ---- context --------------------------------------------------------------------------- */
 int nbc_create(nbc_ctx** out, int hip_device);
 int nbc_destroy(nbc_ctx* ctx);
@@ -253,7 +275,8 @@ int nbc_attach_weights(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int pre
  * calibration guard then run that architecture. */
 int nbc_attach_weights_arch(nbc_ctx* ctx, const void* dev_blob, size_t bytes, int precision, int arch);
 /* Convenience: pack on the host, allocate device memory owned by the context, upload; the BatchNorm affine array
- * (nbc_pack_bn_affine) of the same tensors is uploaded and attached as well. */
+ * (nbc_pack_bn_affine) of the same tensors is uploaded and attached as well, and in NBC_PREC_F16X2 the raw-convolution array
+ * (nbc_pack_bn_raw), whose NBC_PACK_* bits join those nbc_weights_flags reports. */
 int nbc_load_weights(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision);
 int nbc_load_weights_arch(nbc_ctx* ctx, const nbc_tensor* tensors, int n, int precision, int arch);
 /* NBC_PACK_* bits of the attached blob (read from its trailer when it was attached: a 1-KiB device-to-host copy), >= 0,
@@ -277,15 +300,25 @@ int nbc_bcast_weights(nbc_ctx* ctx, void* rccl_comm, int root, int precision, vo
  * (must outlive the context or the next attach); `count` floats, nbc_arch_bn_affine_floats of the attached architecture.
  * nbc_bcast_weights does not carry it: a multi-rank caller broadcasts it itself and attaches it on each rank. */
 int nbc_attach_bn_affine(nbc_ctx* ctx, const float* dev_affine, size_t count);
+/* The same for the raw-convolution array (nbc_pack_bn_raw), `count` = nbc_arch_bn_raw_floats of the attached architecture. */
+int nbc_attach_bn_raw(nbc_ctx* ctx, const float* dev_raw, size_t count);
 /* NBC_BN_RUNNING (default) or NBC_BN_PER_IMAGE.  NBC_ERR_STATE for NBC_BN_PER_IMAGE unless the attached weights are
- * NBC_PREC_FP32 of NBC_ARCH_FCN_RESNET50 (f16x2 folds powers of two into the BatchNorm pairs at pack time; bf16 rounds the
- * raw pre-BatchNorm values; DeepLabV3's pooling-branch BatchNorm sees one value per channel, which batch statistics refuse).
+ * NBC_PREC_FP32 or NBC_PREC_F16X2 of NBC_ARCH_FCN_RESNET50 (bf16 rounds the raw pre-BatchNorm values; DeepLabV3's
+ * pooling-branch BatchNorm sees one value per channel, which batch statistics refuse).
+ * NBC_PREC_F16X2, unit u, output channel o: the raw launch's table is scale[o] = 2^(r_o - k_o - a_in), shift 0 (nbc_pack_bn_raw),
+ * exact in fma(acc, 2^e, 0), so the buffer holds 2^r_o conv_o as pieces.  "<bn>.stats" sums the joined stored values and their
+ * squares in f64 and finishes mean = (S / hw) 2^-r_o, var = max(SS / hw - (S / hw)^2, 0) 2^-2 r_o (exact scalings),
+ * sc = gamma / sqrt(var + 1e-5), table scale = f32(sc) 2^(a_out - r_o), shift = f32(beta - mean sc) 2^a_out, a_out the power
+ * the blob records for the unit's output (nbc_activation_exponent); it raises NBC_NONFINITE_BN_RANGE from the channel's stored
+ * rms sqrt(SS / hw).  "<bn>.apply" joins, fma(x, scale, shift), adds the joined identity (stored with the same a_out: a
+ * residual stream is one tensor), applies the ReLU (NaN-propagating) and splits again, in place.  Every reader of the
+ * tensor is the one of NBC_BN_RUNNING.
  * The mode is part of the plan key, like the precision.  In NBC_BN_PER_IMAGE every BatchNorm'd convolution runs raw on the
  * same conv kernels and tiles (nbc_autotune, nbc_set_plan_tiles: the same list), followed by two plan ops named after the
  * BatchNorm: "<bn>.stats" (kernel "bn_stats": per-image sums over fixed pixel slices, f64, no atomics, so an image's bits do
  * not depend on its batch) and "<bn>.apply" (kernel "bn_apply": in place, with the identity and ReLU of the unit).  Keep
  * mode returns each unit's post-BatchNorm (post-ReLU) tensor under the unit's name.  nbc_forward / nbc_reserve then return
- * NBC_ERR_STATE without an affine array attached, and NBC_ERR_INVALID ("Expected more than 1 value per channel when
+ * NBC_ERR_STATE without an affine array (in NBC_PREC_F16X2: or without a raw-convolution array) attached, and NBC_ERR_INVALID ("Expected more than 1 value per channel when
  * training") for an image whose low-resolution map is 1 x 1 (e.g. 8 x 8), which batch statistics cannot normalise. */
 int nbc_set_bn_statistics(nbc_ctx* ctx, int mode);
 /* mean/std used for NBC_IN_U8_NHWC input; defaults are models.py:208-209. */
@@ -528,8 +561,9 @@ int nbc_conv_tile_info(int precision, int tile, int32_t* rows, int32_t* cols, in
  * e.g. one measured in an earlier process: NBC_ERR_INVALID when the count or a tile does not fit. */
 int nbc_set_plan_tiles(nbc_ctx* ctx, const int32_t* tiles, int n);
 
-/* 1 when a forward of this context since the last reset produced a logit that is NaN or infinite, else 0 (negative:
- * error).  Sticky, raised by classifier.4's launch at no measurable cost.  NaN / inf in the input or the weights do
+/* 1 when a forward of this context since the last reset raised a bit of the sticky word (NBC_NONFINITE_*), else 0 (negative:
+ * error): a logit that is NaN or infinite, raised by classifier.4's launch at no measurable cost, or, in NBC_BN_PER_IMAGE on
+ * NBC_PREC_F16X2, a channel outside the pieces' range (NBC_NONFINITE_BN_RANGE).  Either way the f16x2 run is not to be trusted.  NaN / inf in the input or the weights do
  * that in every mode, like in the reference; in NBC_PREC_F16X2 so does an activation beyond f16's range (+-65504), which
  * that mode cannot represent: a caller that runs unknown weights in f16x2 checks this after its last forward and falls
  * back to NBC_PREC_FP32 when it is raised (the folder driver does).  Synchronises the device. */

@@ -76,6 +76,9 @@ SIGNATURES = {
     "nbc_arch_bn_affine_floats": (C.c_size_t, [C.c_int]),
     "nbc_pack_bn_affine": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "nbc_attach_bn_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "nbc_arch_bn_raw_floats": (C.c_size_t, [C.c_int]),
+    "nbc_pack_bn_raw": (C.c_int, [C.POINTER(NbcTensor), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "nbc_attach_bn_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "nbc_set_bn_statistics": (C.c_int, [C.c_void_p, C.c_int]),
     "nbc_weights_flags": (C.c_int, [C.c_void_p]),
     "nbc_activation_exponent": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),

@@ -61,13 +61,17 @@ struct nbc_ctx {
   void* scratch256 = nullptr;               // 256 bytes of device scratch (min/max of the preprocessor resize)
   int pack_flags = 0;                       // NBC_PACK_* of the attached blob (its trailer)
   std::vector<int> act_exp;                 // per conv unit: power of two its output tensor is stored with (trailer)
-  unsigned* nonfinite = nullptr;            // one device word: bit 0 = a forward produced a NaN / infinite logit (sticky)
+  unsigned* nonfinite = nullptr;            // one device word, sticky: bit 0 = a forward produced a NaN / infinite logit,
+                                            // NBC_NONFINITE_BN_RANGE = a per-image BatchNorm saw a channel outside the pieces' range
   void* zones_ws = nullptr;                 // remove_small_zones workspace: bg bytes, parent ints, size ints
   size_t zones_px = 0;                      // pixels it is sized for
   int bn_mode = NBC_BN_RUNNING;             // NBC_BN_*
   const float* bn_affine = nullptr;         // device: gamma, beta per BatchNorm unit (nbc_pack_bn_affine)
   size_t bn_affine_count = 0;
   void* owned_affine = nullptr;             // the affine array nbc_load_weights uploaded
+  const float* bn_raw = nullptr;            // device, f16x2: 2^(r - k - a_in), 2^-r per BatchNorm unit (nbc_pack_bn_raw)
+  size_t bn_raw_count = 0;
+  void* owned_raw = nullptr;                // the raw array nbc_load_weights uploaded
   float* bn_unit = nullptr;                 // device: 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
   void* bn_ws = nullptr;                    // per-image BatchNorm workspace (Plan::bn_ws_bytes)
   size_t bn_ws_cap = 0;
@@ -206,6 +210,8 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     a.scale = c->bn_unit;
     a.shift = c->bn_unit + 2048;
     a.res = nullptr;
+    // f16x2: the channel's power of two 2^(r - k - a_in) (nbc_pack_bn_raw), so that the pieces hold 2^r conv: exact in the fma
+    if (prec == NBC_PREC_F16X2) a.scale = c->bn_raw + o.affine_off;
   }
   if (o.out_buf == c->plan.identity_buf) {
     const int rc = ensure_buffer(c, o.out_buf);
@@ -255,6 +261,11 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
   }
   *err = launch_conv_dma(a, prec, tile, s);
   return NBC_OK;
+}
+
+// Per-image BatchNorm statistics run on f32 activations and on f16x2 pieces of NBC_ARCH_FCN_RESNET50.
+bool bn_per_image_ok(int precision, int arch) {
+  return arch == kArchFcn && (precision == NBC_PREC_FP32 || precision == NBC_PREC_F16X2);
 }
 
 // Whether `conv3` is the conv3 of a (downsample.0, conv3) pair of the plan (Op::ds_op) that computes the downsample inside its
@@ -315,6 +326,7 @@ int nbc_destroy(nbc_ctx* c) {
   if (c->nonfinite) (void)hipFree(c->nonfinite);
   if (c->owned_weights) (void)hipFree(c->owned_weights);
   if (c->owned_affine) (void)hipFree(c->owned_affine);
+  if (c->owned_raw) (void)hipFree(c->owned_raw);
   if (c->bn_unit) (void)hipFree(c->bn_unit);
   if (c->bn_ws) (void)hipFree(c->bn_ws);
   for (auto& set : c->prof_sets) for (hipEvent_t ev : set) (void)hipEventDestroy(ev);
@@ -388,6 +400,20 @@ int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int prec
   c->owned_affine = adev;
   c->bn_affine = static_cast<const float*>(adev);
   c->bn_affine_count = affine.size();
+  if (precision == NBC_PREC_F16X2 && !is_effnet(arch)) {   // and the raw convolutions' powers of two (NBC_BN_PER_IMAGE on pieces)
+    std::vector<float> raw(nbc_arch_bn_raw_floats(arch));
+    rc = nbc_pack_bn_raw(tensors, n, arch, raw.data(), raw.size());
+    if (rc < 0) return rc;
+    c->pack_flags |= rc;
+    void* rdev = nullptr;
+    NBC_HIP(hipMalloc(&rdev, raw.size() * sizeof(float)));
+    e = hipMemcpy(rdev, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(rdev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn raw): ") + hipGetErrorString(e)); }
+    if (c->owned_raw) (void)hipFree(c->owned_raw);
+    c->owned_raw = rdev;
+    c->bn_raw = static_cast<const float*>(rdev);
+    c->bn_raw_count = raw.size();
+  }
   return NBC_OK;
 }
 
@@ -407,10 +433,26 @@ int nbc_attach_bn_affine(nbc_ctx* c, const float* dev_affine, size_t count) {
   return NBC_OK;
 }
 
+int nbc_attach_bn_raw(nbc_ctx* c, const float* dev_raw, size_t count) {
+  if (!c || !dev_raw) return set_error(NBC_ERR_INVALID, "nbc_attach_bn_raw: null argument");
+  bool any = false;
+  for (int a = 0; a < kNumArchs; ++a) any = any || (count > 0 && count == nbc_arch_bn_raw_floats(a));
+  if (!any)
+    return set_error(NBC_ERR_INVALID, "nbc_attach_bn_raw: count is nbc_arch_bn_raw_floats of no architecture");
+  if (c->owned_raw && c->owned_raw != dev_raw) {
+    NBC_HIP(hipSetDevice(c->device));
+    (void)hipFree(c->owned_raw);                       // synchronises: nothing of the old array is in flight
+    c->owned_raw = nullptr;
+  }
+  c->bn_raw = dev_raw;
+  c->bn_raw_count = count;
+  return NBC_OK;
+}
+
 int nbc_set_bn_statistics(nbc_ctx* c, int mode) {
   if (!c) return set_error(NBC_ERR_INVALID, "null context");
   if (mode != NBC_BN_RUNNING && mode != NBC_BN_PER_IMAGE) return set_error(NBC_ERR_INVALID, "nbc_set_bn_statistics: unknown mode");
-  if (mode == NBC_BN_PER_IMAGE && (c->precision != NBC_PREC_FP32 || c->arch != kArchFcn))
+  if (mode == NBC_BN_PER_IMAGE && !bn_per_image_ok(c->precision, c->arch))
     return set_error(NBC_ERR_STATE, "nbc_set_bn_statistics: per-image BatchNorm statistics need NBC_PREC_FP32 weights of "
                                     "NBC_ARCH_FCN_RESNET50 attached");
   if (c->bn_mode != mode) stash_plan(c);               // another launch list: park this one, like a precision change
@@ -579,11 +621,14 @@ int nbc_reserve(nbc_ctx* c, int N, int H, int W) {
   if (c->precision < 0) return set_error(NBC_ERR_STATE, "nbc_reserve: no weights attached");
   if (N < 1 || H < 8 || W < 8) return set_error(NBC_ERR_INVALID, "nbc_reserve: need N>=1, H>=8, W>=8");
   if (c->bn_mode == NBC_BN_PER_IMAGE) {
-    if (c->precision != NBC_PREC_FP32 || c->arch != kArchFcn)
+    if (!bn_per_image_ok(c->precision, c->arch))
       return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics need NBC_PREC_FP32 weights of NBC_ARCH_FCN_RESNET50 attached");
     if (!c->bn_affine || c->bn_affine_count != nbc_arch_bn_affine_floats(c->arch))
       return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics: no affine array of this architecture attached "
                                       "(nbc_attach_bn_affine)");
+    if (c->precision == NBC_PREC_F16X2 && (!c->bn_raw || c->bn_raw_count != nbc_arch_bn_raw_floats(c->arch)))
+      return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics in NBC_PREC_F16X2: no raw-convolution array of this "
+                                      "architecture attached (nbc_attach_bn_raw)");
   }
   NBC_HIP(hipSetDevice(c->device));
   const PlanKey key = plan_key(c, N, H, W);
@@ -605,7 +650,7 @@ int nbc_describe_plan(int arch, int precision, int N, int H, int W, int keep, in
   if (!known_arch(arch) || !known_precision(precision) || (is_effnet(arch) && precision != NBC_PREC_FP32))
     return set_error(NBC_ERR_INVALID, "nbc_describe_plan: unknown architecture or precision, or one the architecture does not run in");
   if (N < 1 || H < 8 || W < 8) return set_error(NBC_ERR_INVALID, "nbc_describe_plan: need N>=1, H>=8, W>=8");
-  if (bn_mode != NBC_BN_RUNNING && (bn_mode != NBC_BN_PER_IMAGE || precision != NBC_PREC_FP32 || arch != kArchFcn))
+  if (bn_mode != NBC_BN_RUNNING && (bn_mode != NBC_BN_PER_IMAGE || !bn_per_image_ok(precision, arch)))
     return set_error(NBC_ERR_INVALID, "nbc_describe_plan: per-image BatchNorm statistics need NBC_PREC_FP32 and NBC_ARCH_FCN_RESNET50");
   PlanKey key;
   key.N = N; key.H = H; key.W = W; key.precision = precision; key.arch = arch; key.keep = keep != 0; key.bn = bn_mode;
@@ -734,8 +779,15 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         float* shift = scale + (size_t)N * o.Co;
         if (o.kind == OP_BN_STATS) {
           const float* gamma = c->bn_affine + o.affine_off;
-          e = launch_bn_stats(static_cast<const float*>(c->bufs[o.out_buf]), N, hw, o.Co, gamma, gamma + o.Co, c->bn_ws, scale,
-                              shift, s);
+          if (prec == NBC_PREC_F16X2)                  // the unit's 2^-r follows its raw scales; the table carries the tensor's 2^a_out
+            e = launch_bn_stats_f16x2(c->bufs[o.out_buf], N, hw, o.Co, gamma, gamma + o.Co, c->bn_raw + o.affine_off + o.Co,
+                                      c->act_exp[o.unit], c->bn_ws, scale, shift, c->nonfinite, s);
+          else
+            e = launch_bn_stats(static_cast<const float*>(c->bufs[o.out_buf]), N, hw, o.Co, gamma, gamma + o.Co, c->bn_ws, scale,
+                                shift, s);
+        } else if (prec == NBC_PREC_F16X2) {
+          e = launch_bn_apply_f16x2(c->bufs[o.out_buf], o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr, N, hw, o.Co, scale, shift,
+                                    o.relu, s);
         } else {
           e = launch_bn_apply(static_cast<float*>(c->bufs[o.out_buf]), o.res_buf >= 0 ? static_cast<const float*>(c->bufs[o.res_buf]) : nullptr,
                               N, hw, o.Co, scale, shift, o.relu, s);

@@ -110,6 +110,15 @@ hipError_t launch_bn_stats(const float* y, int N, int hw, int C, const float* ga
                            float* shift, hipStream_t s);
 hipError_t launch_bn_apply(float* y, const float* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
                            hipStream_t s);
+// The same on f16x2 pieces (NBC_PREC_F16X2; same slices, lane and slice orders, workspace).  y holds 2^r_c x per channel c,
+// inv_r[c] = 2^-r_c (nbc_pack_bn_raw); the statistics are those of x, the table is for the stored value and carries the power
+// 2^a_out the normalised tensor is stored with: scale = f32(sc) 2^(a_out - r_c), shift = f32(beta - mean sc) 2^a_out.  word
+// (nullable) gets bit NBC_NONFINITE_BN_RANGE when a channel's stored rms is not finite, above 2^12 or positive and below 2^-10.
+// bn_apply: in place on pieces, res (pieces, stored with 2^a_out) nullable.
+hipError_t launch_bn_stats_f16x2(const void* y, int N, int hw, int C, const float* gamma, const float* beta, const float* inv_r,
+                                 int a_out, void* ws, float* scale, float* shift, unsigned* word, hipStream_t s);
+hipError_t launch_bn_apply_f16x2(void* y, const void* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
+                                 hipStream_t s);
 // EfficientNet (efficientnet.hip), f32 NHWC, C a multiple of 64.
 // Depthwise k x k conv (k 3 / 5, stride 1 / 2) of x [N][Hi][Wi][C] with weights [k*k][C], top / left pads pad_t / pad_l
 // (a tap outside the image reads 0), y [N][Ho][Wo][C] = swish(fma(acc, scale, shift)); in_swish: x is stored before its

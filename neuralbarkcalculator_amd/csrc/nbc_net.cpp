@@ -449,13 +449,17 @@ int f16x2_row_exponent(const float* row, size_t n, bool* clamped) {
 // it): one power per stage.  Tensors of ordinary size keep a = 0, so an ordinary checkpoint computes what it computed before
 // this existed, bit for bit.  classifier.4 reads the last tensor with f32 weights: they take the 2^-a.
 // out_exp[u] / in_exp[u]: power of conv unit u's output tensor / of the tensor it reads.
-static int tensor_exponent(float est) {
-  if (!(est > 0.f) || !std::isfinite(est)) return 0;
-  if (est >= 0.03125f && est <= 128.0f) return 0;
+// The power of two that brings est into [2, 4), clamped to [-100, 100]; 0 for an estimate that is 0 or not finite.
+static int range_exponent(double est) {
+  if (!(est > 0.0) || !std::isfinite(est)) return 0;
   int e = 0;
   (void)std::frexp(est, &e);                          // est = f * 2^e, f in [0.5, 1)
   const int a = 2 - e;                                // est * 2^a in [2, 4)
   return a > 100 ? 100 : (a < -100 ? -100 : a);
+}
+static int tensor_exponent(float est) {
+  if (est >= 0.03125f && est <= 128.0f) return 0;
+  return range_exponent(est);
 }
 
 // gamma counts with the share of the normalised value that is data: a channel whose running variance lies below eps comes
@@ -528,6 +532,21 @@ static void activation_exponents(int arch, const std::vector<const float*>& gamm
   out_exp[ui] = tensor_exponent(est(ui));
   in_exp[ui + 1] = out_exp[ui];                       // classifier.4: f32 weights, no BatchNorm
   out_exp[ui + 1] = 0;
+}
+
+// activation_exponents of the tensors of a state dict that check_state_dict has passed (f16x2; ResNet-50 trunks)
+static void activation_exponents_of(int arch, const std::map<std::string, const nbc_tensor*>& given, std::vector<int>& out_exp,
+                                    std::vector<int>& in_exp) {
+  const auto& units = conv_units(arch);
+  std::vector<const float*> gam(units.size(), nullptr), bet(units.size(), nullptr), var(units.size(), nullptr);
+  for (size_t ui = 0; ui < units.size(); ++ui) {
+    const ConvUnit& c = units[ui];
+    if (c.bn.empty()) continue;                                           // classifier.4: never asked for an estimate
+    gam[ui] = static_cast<const float*>(given.at(c.bn + ".weight")->data);
+    bet[ui] = static_cast<const float*>(given.at(c.bn + ".bias")->data);
+    var[ui] = static_cast<const float*>(given.at(c.bn + ".running_var")->data);
+  }
+  activation_exponents(arch, gam, bet, var, out_exp, in_exp);
 }
 
 // v * 2^e for a BatchNorm scale / shift; NBC_PACK_SCALE_RANGE when that leaves f32's normal range (the product is then no
@@ -788,17 +807,7 @@ int nbc_pack_weights_arch(const nbc_tensor* tensors, int n, int precision, int a
   const auto& units = conv_units(arch);
   int flags = 0;
   std::vector<int> out_exp(units.size(), 0), in_exp(units.size(), 0);
-  if (precision == NBC_PREC_F16X2) {
-    std::vector<const float*> gam(units.size(), nullptr), bet(units.size(), nullptr), var(units.size(), nullptr);
-    for (size_t ui = 0; ui < units.size(); ++ui) {
-      const ConvUnit& c = units[ui];
-      if (c.bn.empty()) continue;                                           // classifier.4: never asked for an estimate
-      gam[ui] = static_cast<const float*>(given[c.bn + ".weight"]->data);
-      bet[ui] = static_cast<const float*>(given[c.bn + ".bias"]->data);
-      var[ui] = static_cast<const float*>(given[c.bn + ".running_var"]->data);
-    }
-    activation_exponents(arch, gam, bet, var, out_exp, in_exp);
-  }
+  if (precision == NBC_PREC_F16X2) activation_exponents_of(arch, given, out_exp, in_exp);
   for (size_t ui = 0; ui < units.size(); ++ui) {
     const ConvUnit& c = units[ui];
     const PackedConv& p = L.convs[ui];
@@ -925,6 +934,49 @@ int nbc_pack_bn_affine(const nbc_tensor* tensors, int n, int arch, float* out, s
     off += 2 * (size_t)c.cout;
   }
   return NBC_OK;
+}
+
+size_t nbc_arch_bn_raw_floats(int arch) {
+  if (!known_arch(arch) || is_effnet(arch)) return 0;
+  return bn_affine_floats(arch);
+}
+
+int nbc_pack_bn_raw(const nbc_tensor* tensors, int n, int arch, float* out, size_t count) {
+  if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_raw: unknown architecture");
+  if (is_effnet(arch))
+    return set_error(NBC_ERR_INVALID, std::string("nbc_pack_bn_raw: ") + arch_name(arch) + " runs in NBC_PREC_FP32 (fp32) only");
+  if (!tensors || n < 0 || !out) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_raw: null argument");
+  if (count < bn_affine_floats(arch)) return set_error(NBC_ERR_INVALID, "nbc_pack_bn_raw: out holds fewer than nbc_arch_bn_raw_floats() floats");
+  std::map<std::string, const nbc_tensor*> given;
+  std::string msg;
+  const int krc = check_state_dict(tensors, n, arch, &given, &msg);  // the strict check of nbc_pack_weights
+  if (krc == NBC_ERR_INVALID) return set_error(krc, "nbc_pack_bn_raw: " + msg);
+  if (krc != NBC_OK) return set_error(krc, msg);
+  const auto& units = conv_units(arch);
+  const PackedLayout L = packed_layout(NBC_PREC_F16X2, arch);
+  std::vector<int> out_exp, in_exp;
+  activation_exponents_of(arch, given, out_exp, in_exp);
+  int flags = 0;
+  size_t off = 0;
+  for (size_t ui = 0; ui < units.size(); ++ui) {
+    const ConvUnit& c = units[ui];
+    if (c.bn.empty()) continue;
+    const float* w = static_cast<const float*>(given[c.name + ".weight"]->data);
+    const float* mu = static_cast<const float*>(given[c.bn + ".running_mean"]->data);
+    const float* var = static_cast<const float*>(given[c.bn + ".running_var"]->data);
+    const size_t row_floats = (size_t)c.cin * c.k * c.k;                // the packed row holds these and zeros: the same largest |w|
+    for (int o = 0; o < c.cout; ++o) {
+      bool clamped = false;
+      const int k = L.convs[ui].pooled ? 0 : f16x2_row_exponent(w + (size_t)o * row_floats, row_floats, &clamped);
+      if (clamped) flags |= NBC_PACK_ROW_CLAMPED;
+      const double sd = var[o] > 0.f ? std::sqrt((double)var[o]) : 0.0;
+      const int r = range_exponent(std::fabs((double)mu[o]) + 3.0 * sd);
+      out[off + o] = ldexp_flagged(1.0f, r - k - in_exp[ui], &flags);
+      out[off + c.cout + o] = ldexp_flagged(1.0f, -r, &flags);
+    }
+    off += 2 * (size_t)c.cout;
+  }
+  return flags;
 }
 
 int nbc_packed_weights_flags(const void* blob, size_t blob_bytes, int precision) {

@@ -78,6 +78,7 @@ struct Builder {
     if (bn_ops) res_buf = -1;
     Op o;
     o.kind = OP_CONV; o.unit = ui; o.in_buf = in.buf; o.res_buf = res_buf; o.gate_buf = gate_buf; o.raw = bn_ops;
+    o.affine_off = affine_off[ui];                                   // a raw f16x2 launch reads its scales from the raw array
     o.Hi = in.H; o.Wi = in.W; o.Ci = in.C; o.Ho = Ho; o.Wo = Wo; o.Co = u.outc(); o.name = u.name;
     o.creal = u.cout_pad ? u.cout : 0;                               // EfficientNet pads its channels, ResNet-50 does not
     const size_t out_bytes = (size_t)N * std::max(Ho, 1) * std::max(Wo, 1) * u.outc() * eb;

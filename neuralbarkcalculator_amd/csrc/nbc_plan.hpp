@@ -26,7 +26,7 @@ struct Op {
   int cat_in[5] = {-1, -1, -1, -1, -1};   // OP_CONCAT: the four spatial branches' buffers and the pooled vectors' buffer
   bool raw = false;    // OP_CONV in NBC_BN_PER_IMAGE: unit scale, zero shift, no ReLU, no identity (the raw conv output)
   int relu = 0;        // OP_BN_APPLY: the unit's ReLU
-  size_t affine_off = 0;   // OP_BN_STATS: floats before the unit's (gamma, beta) in the affine array
+  size_t affine_off = 0;   // OP_BN_STATS, raw OP_CONV: floats before the unit's pair in the affine array and in the raw array
   // EfficientNet
   int gate_buf = -1;   // OP_CONV: per-image weights [N][Co][Ci] (the SE-gated project conv: one launch per image);
                        // OP_SE_EXCITE / OP_GATE_WEIGHTS: the gate [N][C]
@@ -58,7 +58,7 @@ struct Plan : PlanKey {
 
 // The launch list of `key` into *out, or the reason why this network cannot run on such an image (*out is then left alone).
 // The key must name a known architecture in a precision it runs in, N >= 1 and H, W >= 8, and NBC_BN_PER_IMAGE only for
-// NBC_ARCH_FCN_RESNET50 in NBC_PREC_FP32 (nbc_set_bn_statistics and nbc_reserve refuse the rest before they come here).
+// NBC_ARCH_FCN_RESNET50 in NBC_PREC_FP32 or NBC_PREC_F16X2 (nbc_set_bn_statistics and nbc_reserve refuse the rest before they come here).
 std::string build_plan(const PlanKey& key, Plan* out);
 
 }  // namespace nbc

@@ -200,7 +200,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
-    ("fp32", FCN only; ``predict.resolve_bn_stats``).  ``loss``: also the per-image Lovasz-Softmax loss (module
+    ("fp32", FCN only; ``predict.resolve_bn_stats``), or ``"image_f16x2"``, the same on the f16x2 pipe ("f16x2" only).  ``loss``: also the per-image Lovasz-Softmax loss (module
     docstring).  ``normalization``: the ``(mean, std)`` of the ingest (``folder_run.resolve_normalization``; None: the
     defaults), set on every stream's model object; ``normalization_source``: what the summary says of where it came from.
     ``ce``: also the cross-entropy family (module docstring), weighted with ``class_weights`` (three finite values >= 0);
@@ -312,7 +312,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
 def format_summary(summary: dict) -> str:
     lines = ["evaluated %d images in %s%s (checkpoint %s), skipped %d%s" % (
         summary["images_evaluated"], summary["precision"],
-        ", per-image BatchNorm statistics" if summary.get("bn_statistics") == "image" else "", summary["model_path"],
+        ", per-image BatchNorm statistics" if summary.get("bn_statistics") in ("image", "image_f16x2") else "", summary["model_path"],
         summary["images_skipped"],
         "".join("; %s: %s" % (r, ", ".join(v)) for r, v in summary["skipped"].items() if v))]
     if "normalization" in summary:
@@ -386,8 +386,8 @@ def main(argv=None):
         kw["normalization"] = args.normalization
         if args.stats is not None:
             kw["normalization_source"] = args.stats
-    stats = folder_run.run_precision("evaluate", lambda precision, **auto: evaluate_folder(
-        args.root_path, args.model_path, precision, idx, **auto, **kw), args.precision)
+    stats = folder_run.run_precision("evaluate", lambda precision, **over: evaluate_folder(
+        args.root_path, args.model_path, precision, idx, **dict(kw, **over)), args.precision, args.bn_stats)
     if stats["rank"] == 0:
         print(format_summary(stats["summary"]))
         print("%(images_total)d images (%(images_this_rank)d on rank 0, %(batches)d batches): %(total_s).2f s, "

@@ -180,7 +180,7 @@ def resolve_arch_precision(arch: str, precision: str, precision_auto: bool = Fal
                      "homogeneous, so f16x2's powers of two cannot be folded into its BatchNorm pairs" % (arch, precision))
 
 
-BN_STATS = ("running", "image")
+BN_STATS = ("running", "image", "image_f16x2")
 ARCH_CHOICES = ("fcn_resnet50", "deeplabv3_resnet50") + tuple("fcn_efficientnet_b%d" % n for n in range(8)) + \
     tuple("deeplabv3_efficientnet_b%d" % n for n in range(8))
 
@@ -188,25 +188,35 @@ ARCH_CHOICES = ("fcn_resnet50", "deeplabv3_resnet50") + tuple("fcn_efficientnet_
 def resolve_bn_stats(bn_stats: str, precision: str) -> str:
     """The precision a folder driver runs with ``--bn_stats`` (``FCNResNet50.set_bn_statistics``).  ``"running"`` leaves
     ``precision`` as it is.  ``"image"`` (the shipped tool's per-image BatchNorm statistics) runs the f32 MFMA only:
-    ``"auto"`` means ``"fp32"`` (no f16x2 run, no calibration), ``"f16x2"`` and ``"bf16"`` raise ``ValueError``."""
+    ``"auto"`` means ``"fp32"`` (no f16x2 run, no calibration), ``"f16x2"`` and ``"bf16"`` raise ``ValueError``.
+    ``"image_f16x2"`` is the same statistics on the f16x2 pipe: ``"f16x2"`` runs it, ``"auto"`` stays ``"auto"`` (f16x2
+    under its guards, and ``--bn_stats image`` in fp32 when one of them speaks: ``run_precision``), ``"fp32"`` and ``"bf16"``
+    raise ``ValueError``."""
     if bn_stats not in BN_STATS:
         raise ValueError("--bn_stats must be one of %s, got %r" % (", ".join(BN_STATS), bn_stats))
     if bn_stats == "running":
         return precision
+    if bn_stats == "image_f16x2":
+        if precision in ("auto", "f16x2"):
+            return precision
+        raise ValueError("--bn_stats image_f16x2 runs in --precision f16x2 (or auto) only, not %s: --bn_stats image is the "
+                         "fp32 mode" % precision)
     if precision in ("auto", "fp32"):
         return "fp32"
-    raise ValueError("--bn_stats image runs in --precision fp32 (or auto) only, not %s: raw pre-BatchNorm values do not fit "
-                     "the f16x2 pieces' pack-time scaling, and bf16 rounds them too coarsely for the mean subtraction" % precision)
+    raise ValueError("--bn_stats image runs in --precision fp32 (or auto) only, not %s: the f16x2 form of the mode is "
+                     "--bn_stats image_f16x2, and bf16 rounds raw pre-BatchNorm values too coarsely for the mean "
+                     "subtraction" % precision)
 
 
 def check_bn_stats_arch(bn_stats: str, arch: str) -> None:
-    """``ValueError`` for ``--bn_stats image`` on a network other than FCN-ResNet-50.  Called with the architecture
+    """``ValueError`` for ``--bn_stats image`` (or ``image_f16x2``) on a network other than FCN-ResNet-50.  Called with the architecture
     ``resolve_arch`` returned, which every rank holds alike, so every rank refuses alike."""
     from . import topology
-    if bn_stats == "image" and topology.is_efficientnet(arch):
+    image = bn_stats in ("image", "image_f16x2")
+    if image and topology.is_efficientnet(arch):
         raise ValueError("--bn_stats image is refused for %s: per-image BatchNorm statistics are implemented for fcn_resnet50 "
                          "only" % arch)
-    if bn_stats == "image" and arch != "fcn_resnet50":
+    if image and arch != "fcn_resnet50":
         raise ValueError("--bn_stats image is refused for %s: its ASPP pooling branch's BatchNorm sees a [1, 256, 1, 1] tensor, "
                          "which batch statistics cannot normalise (torch raises, and so would the reference)" % arch)
 
@@ -663,7 +673,9 @@ def add_shared_arguments(ap) -> None:
                     help="the network of the checkpoint; auto (default): the one whose state_dict keys it holds")
     ap.add_argument("--bn_stats", choices=list(BN_STATS), default="running",
                     help="running (default): BatchNorm on the running statistics (eval mode); image: each image's own statistics, "
-                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32)")
+                         "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32); image_f16x2: "
+                         "the same statistics on the f16x2 pipe (--precision f16x2, or auto: f16x2 under its guards, else image "
+                         "in fp32)")
     ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
                     help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
                          "(with --std; default: the constants of the reference's model class)")
@@ -733,9 +745,10 @@ def resolve_arguments(ap, args) -> None:
         ap.error(str(e))
 
 
-def run_precision(tool: str, run, precision: str) -> dict:
+def run_precision(tool: str, run, precision: str, bn_stats: str = "running") -> dict:
     """``run(precision)``; for ``"auto"``, ``run("f16x2", precision_auto=True)`` and, when that mode cannot carry the weights
-    (``NonFiniteLogits``, raised on every rank alike), the folder again as ``run("fp32")``."""
+    (``NonFiniteLogits``, raised on every rank alike), the folder again as ``run("fp32")``.  ``bn_stats`` "image_f16x2" has no
+    fp32 form of its own: the second run is ``run("fp32", bn_stats="image")``, the same statistics on the f32 MFMA."""
     if precision != "auto":
         return run(precision)
     try:
@@ -749,4 +762,6 @@ def run_precision(tool: str, run, precision: str) -> dict:
     import torch
     gc.collect()
     torch.cuda.empty_cache()
+    if bn_stats == "image_f16x2":
+        return run("fp32", bn_stats="image")
     return run("fp32")

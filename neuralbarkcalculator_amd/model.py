@@ -25,7 +25,9 @@ from .topology import NUM_CLASSES, out_hw
 
 _PRECISIONS = {"fp32": _lib.PREC_FP32, "f32": _lib.PREC_FP32, "float32": _lib.PREC_FP32,
                "bf16": _lib.PREC_BF16, "bfloat16": _lib.PREC_BF16, "f16x2": _lib.PREC_F16X2}
-BN_STATISTICS = {"running": _lib.BN_RUNNING, "image": _lib.BN_PER_IMAGE}   # NBC_BN_*
+# NBC_BN_*; "image" is per-image statistics on the f32 MFMA, "image_f16x2" the same mode on an "f16x2" model
+BN_STATISTICS = {"running": _lib.BN_RUNNING, "image": _lib.BN_PER_IMAGE, "image_f16x2": _lib.BN_PER_IMAGE}
+PER_IMAGE_MODES = ("image", "image_f16x2")
 
 
 def _as_numpy(v) -> np.ndarray:
@@ -106,6 +108,47 @@ def broadcast_bn_affine(affine: Optional[np.ndarray], arch="fcn_resnet50", src: 
     return t.cpu().numpy()
 
 
+def pack_bn_raw(state_dict: Mapping[str, object], arch="fcn_resnet50"):
+    """``(array, flags)``: the raw-convolution array of ``state_dict`` for per-image BatchNorm statistics in "f16x2"
+    (nbc_pack_bn_raw): float32 powers of two, per conv unit with a BatchNorm ``2^(r - k - a_in)`` then ``2^-r`` per channel,
+    in ``topology.conv_units`` order, and its NBC_PACK_* bits.  Same strict key check and ``RuntimeError`` as
+    ``pack_state_dict``."""
+    lib = _lib.load()
+    a = topology.arch_index(arch)
+    arr, n, _keep = _tensor_array(state_dict)
+    count = lib.nbc_arch_bn_raw_floats(a)
+    out = np.zeros(count, dtype=np.float32)
+    rc = lib.nbc_pack_bn_raw(arr, n, a, out.ctypes.data, count)
+    if rc < 0:
+        _lib.check(rc, "load_state_dict")
+    return out, int(rc)
+
+
+def bn_raw_flags(raw: np.ndarray) -> int:
+    """``_lib.PACK_SCALE_RANGE`` when an entry of a raw-convolution array is not a normal f32 (a power of two that left the
+    range), else 0: what a rank that received the array by broadcast can still tell."""
+    a = np.abs(np.asarray(raw, dtype=np.float32))
+    ok = np.isfinite(a) & (a >= np.finfo(np.float32).tiny)
+    return 0 if bool(ok.all()) else _lib.PACK_SCALE_RANGE
+
+
+def broadcast_bn_raw(raw: Optional[np.ndarray], arch="fcn_resnet50", src: int = 0, group=None, device=None) -> np.ndarray:
+    """``torch.distributed`` broadcast of the raw-convolution array (``pack_bn_raw``) from rank ``src``, as
+    ``broadcast_bn_affine`` sends the affine array."""
+    import torch.distributed as dist
+    count = int(_lib.load().nbc_arch_bn_raw_floats(topology.arch_index(arch)))
+    if dist.get_rank(group) == src:
+        if raw is None or raw.size != count:
+            raise RuntimeError("broadcast_bn_raw: the source rank holds no raw-convolution array of %s" % arch)
+        t = torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32))
+    else:
+        t = torch.empty(count, dtype=torch.float32)
+    if device is not None:
+        t = t.to(device)
+    dist.broadcast(t, src=src, group=group)
+    return t.cpu().numpy()
+
+
 def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
     """The architecture (``topology.ARCHS``) whose key set the state_dict matches exactly (nbc_arch_of_state_dict);
     ``RuntimeError`` with the strict-load message of fcn_resnet50 when none does."""
@@ -150,7 +193,8 @@ class FCNResNet50:
 
     bn_statistics (``set_bn_statistics``): ``"running"`` (default) -- eval mode, BatchNorm on the running statistics;
     ``"image"`` -- every BatchNorm normalises each image by its own per-channel mean and biased variance, as the shipped
-    tool's forward does (it never calls ``.eval()`` and feeds one image at a time); "fp32" only.  Dropout is the identity
+    tool's forward does (it never calls ``.eval()`` and feeds one image at a time), "fp32" only; ``"image_f16x2"`` -- the
+    same statistics on an "f16x2" model, the raw convolution outputs kept as pieces.  Dropout is the identity
     in both (live Dropout noise is all that stays different from the shipped tool; ``dropout_draws`` samples it).
     """
 
@@ -170,6 +214,8 @@ class FCNResNet50:
         self._blob_dev: Optional[torch.Tensor] = None
         self._affine_host: Optional[np.ndarray] = None     # per-image BatchNorm gamma / beta (pack_bn_affine)
         self._affine_dev: Optional[torch.Tensor] = None
+        self._raw_host: Optional[np.ndarray] = None        # "f16x2": the raw convolutions' powers of two (pack_bn_raw)
+        self._raw_dev: Optional[torch.Tensor] = None
         self._ctx = C.c_void_p()
         self._lovasz_ws: Optional[torch.Tensor] = None     # nbc_lovasz_softmax's workspace (grows, never shrinks)
         self._pixel_ce_ws: Optional[torch.Tensor] = None   # nbc_pixel_cross_entropy's, likewise
@@ -184,6 +230,7 @@ class FCNResNet50:
             raise NotImplementedError("only strict=True is supported (the reference never passes strict=False)")
         self._blob_host = pack_state_dict(state_dict, self.precision, self.ARCH)
         self._affine_host = pack_bn_affine(state_dict, self.ARCH)
+        self._raw_host = pack_bn_raw(state_dict, self.ARCH)[0] if self._has_bn_raw() else None
         if self.device is not None:
             self._upload()
         return self
@@ -219,10 +266,13 @@ class FCNResNet50:
         its H x W pixels, eps 1e-5, the checkpoint's gamma and beta: ``F.batch_norm(training=True)`` on a batch of one, what
         the shipped tool computes.  Nothing is updated (this is not training: ``train(True)`` stays refused), and an image's
         result does not depend on the batch it runs in.  "fp32" FCN-ResNet-50 only (``ValueError`` otherwise, before the
-        device is touched); an image whose low-resolution map is 1 x 1 (e.g. 8 x 8) raises ``ValueError`` like torch does."""
+        device is touched); an image whose low-resolution map is 1 x 1 (e.g. 8 x 8) raises ``ValueError`` like torch does.
+        ``"image_f16x2"``: the same statistics on an "f16x2" FCN-ResNet-50 (``ValueError`` on another precision): each raw
+        convolution output is stored as pieces, normalised per channel by a power of two taken from the running statistics;
+        ``nonfinite_seen`` is raised when an image's channel falls outside the range the pieces hold."""
         if mode not in BN_STATISTICS:
             raise ValueError(f"bn_statistics must be one of {sorted(BN_STATISTICS)}, got {mode!r}")
-        if mode == "image":
+        if mode in PER_IMAGE_MODES:
             if topology.is_efficientnet(self.ARCH):
                 raise ValueError("per-image BatchNorm statistics are refused for %s: they are implemented for fcn_resnet50 "
                                  "only" % self.ARCH)
@@ -230,8 +280,11 @@ class FCNResNet50:
                 raise ValueError("per-image BatchNorm statistics are refused for %s: its ASPP pooling branch's BatchNorm sees a "
                                  "[1, 256, 1, 1] tensor, which batch statistics cannot normalise (torch raises, and so would "
                                  "the reference)" % self.ARCH)
-            if self._prec != _lib.PREC_FP32:
+            if mode == "image" and self._prec != _lib.PREC_FP32:
                 raise ValueError("per-image BatchNorm statistics run in precision 'fp32' only, not %r" % self.precision)
+            if mode == "image_f16x2" and self._prec != _lib.PREC_F16X2:
+                raise ValueError("bn_statistics 'image_f16x2' runs in precision 'f16x2' only, not %r ('image' is the fp32 "
+                                 "mode)" % self.precision)
         self.bn_statistics = mode
         if self._ctx:
             _lib.check(self._lib.nbc_set_bn_statistics(self._ctx, BN_STATISTICS[mode]), "nbc_set_bn_statistics")
@@ -502,7 +555,7 @@ class FCNResNet50:
         other = self._like()
         other.bn_statistics = self.bn_statistics
         other.to(self.device)
-        other._attach(self._blob_dev, self._affine_dev)
+        other._attach(self._blob_dev, self._affine_dev, self._raw_dev)
         return other
 
     def _like(self) -> "FCNResNet50":
@@ -527,7 +580,12 @@ class FCNResNet50:
         affine = broadcast_bn_affine(self._affine_host if dist.get_rank(group) == src else None, self.ARCH, src, group,
                                      self.device)
         self._affine_host = affine
-        self._attach(blob, torch.from_numpy(affine).to(self.device))
+        raw = None
+        if self._has_bn_raw():                             # and so does the f16x2 raw-convolution array
+            self._raw_host = broadcast_bn_raw(self._raw_host if dist.get_rank(group) == src else None, self.ARCH, src, group,
+                                              self.device)
+            raw = torch.from_numpy(self._raw_host).to(self.device)
+        self._attach(blob, torch.from_numpy(affine).to(self.device), raw)
         return self
 
     # ---- measurement / debugging ------------------------------------------------------------
@@ -553,19 +611,21 @@ class FCNResNet50:
         """NBC_PACK_* bits of the weights this model holds (0 = nothing given up): in "f16x2" mode a weight row beyond the
         reach of the row normalisation (``_lib.PACK_ROW_CLAMPED``) or a BatchNorm scale / shift pushed out of f32's normal
         range by the powers of two folded into it (``_lib.PACK_SCALE_RANGE``) -- run such a checkpoint in "fp32".  Read from
-        the packed blob's trailer, so a rank that received the blob by broadcast sees the same bits."""
+        the packed blob's trailer, so a rank that received the blob by broadcast sees the same bits.  In bn_statistics
+        "image_f16x2" the bits of the raw-convolution array (``bn_raw_flags``) join them."""
+        extra = bn_raw_flags(self._raw_host) if self.bn_statistics == "image_f16x2" and self._raw_host is not None else 0
         if self._ctx and self._blob_dev is not None:
             rc = self._lib.nbc_weights_flags(self._ctx)
             if rc < 0:
                 _lib.check(rc, "nbc_weights_flags")
-            return int(rc)
+            return int(rc) | extra
         if self._blob_host is None:
             raise RuntimeError("no weights loaded")
         rc = self._lib.nbc_packed_weights_flags_arch(self._blob_host.ctypes.data, self._blob_host.size, self._prec,
                                                      topology.arch_index(self.ARCH))
         if rc < 0:
             _lib.check(rc, "nbc_packed_weights_flags")
-        return int(rc)
+        return int(rc) | extra
 
     def activation_exponent(self, name: str) -> int:
         """Power of two the output tensor of op ``name`` is stored with on the device (0 outside "f16x2" and for every
@@ -602,7 +662,8 @@ class FCNResNet50:
 
     def nonfinite_seen(self, reset: bool = True) -> bool:
         """True when a forward since the last reset produced a NaN / infinite logit (nbc_nonfinite_seen; synchronises).
-        In "f16x2" mode that also means an activation left f16's range: rerun such weights in "fp32"."""
+        In "f16x2" mode that also means an activation left f16's range, and in bn_statistics "image_f16x2" a channel
+        whose raw values left the range the pieces hold (bit 2 of the word): rerun such weights in "fp32"."""
         rc = self._lib.nbc_nonfinite_seen(self._require_ctx(), int(reset))
         if rc < 0:
             _lib.check(rc, "nbc_nonfinite_seen")
@@ -725,9 +786,14 @@ class FCNResNet50:
     def _upload(self):
         blob = torch.from_numpy(self._blob_host).to(self.device, non_blocking=False)
         affine = torch.from_numpy(self._affine_host).to(self.device) if self._affine_host is not None else None
-        self._attach(blob, affine)
+        raw = torch.from_numpy(self._raw_host).to(self.device) if self._raw_host is not None else None
+        self._attach(blob, affine, raw)
 
-    def _attach(self, blob: torch.Tensor, affine: Optional[torch.Tensor] = None):
+    def _has_bn_raw(self) -> bool:
+        """Whether this model carries the raw-convolution array: an "f16x2" ResNet-50 network."""
+        return self._prec == _lib.PREC_F16X2 and not topology.is_efficientnet(self.ARCH)
+
+    def _attach(self, blob: torch.Tensor, affine: Optional[torch.Tensor] = None, raw: Optional[torch.Tensor] = None):
         assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.device == self.device
         _lib.check(self._lib.nbc_attach_weights_arch(self._require_ctx(), blob.data_ptr(), blob.numel(), self._prec,
                                                      topology.arch_index(self.ARCH)), "nbc_attach_weights")
@@ -736,6 +802,10 @@ class FCNResNet50:
             assert affine.dtype == torch.float32 and affine.is_contiguous() and affine.device == self.device
             _lib.check(self._lib.nbc_attach_bn_affine(self._ctx, affine.data_ptr(), affine.numel()), "nbc_attach_bn_affine")
             self._affine_dev = affine
+        if raw is not None:
+            assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.device == self.device
+            _lib.check(self._lib.nbc_attach_bn_raw(self._ctx, raw.data_ptr(), raw.numel()), "nbc_attach_bn_raw")
+            self._raw_dev = raw
         _lib.check(self._lib.nbc_set_bn_statistics(self._ctx, BN_STATISTICS[self.bn_statistics]), "nbc_set_bn_statistics")
 
     def _check_input(self, x: torch.Tensor) -> Tuple[int, int, int]:
@@ -758,7 +828,7 @@ class FCNResNet50:
             raise RuntimeError("H and W must be >= 8")
         if min(out_hw(int(h), int(w), self.ARCH)) < 1:
             raise RuntimeError("a %dx%d image is too small for %s" % (h, w, self.ARCH))
-        if self.bn_statistics == "image" and out_hw(int(h), int(w)) == (1, 1):
+        if self.bn_statistics in PER_IMAGE_MODES and out_hw(int(h), int(w)) == (1, 1):
             raise ValueError("Expected more than 1 value per channel when training: a %dx%d image has a 1x1 low-resolution "
                              "map, which per-image BatchNorm statistics cannot normalise" % (h, w))
         return int(n), int(h), int(w)

@@ -379,7 +379,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     ``NonFiniteLogits`` -- before any batch -- when a stored tensor lies outside the range the f16 pieces hold at f32 grade
     (``FCNResNet50.activation_peaks``: the silent counterpart of the non-finite word, which still rides back with every batch).
     ``arch`` (``resolve_arch``): the network, ``"auto"`` = the one the checkpoint's keys name.  ``bn_stats``: ``"running"``
-    (eval mode) or ``"image"``, the per-image BatchNorm statistics the shipped tool ran with ("fp32", FCN only:
+    (eval mode), ``"image"``, the per-image BatchNorm statistics the shipped tool ran with ("fp32", FCN only) or
+    ``"image_f16x2"``, the same on the f16x2 pipe ("f16x2", FCN only:
     ``resolve_bn_stats``, ``check_bn_stats_arch``).  EfficientNet networks run "fp32" (``resolve_arch_precision``;
     ``precision_auto``: ``precision`` came from ``--precision auto``).  ``normalization``: the ``(mean, std)`` the frames are
     normalised with (``--mean`` / ``--std`` / ``--stats``, ``folder_run.resolve_normalization``), set on every stream's model
@@ -567,8 +568,9 @@ def main(argv=None):
         if int(os.environ.get("RANK", "0")) == 0:
             print("predict: frames normalised with mean %s, std %s (%s)" % (
                 list(args.normalization[0]), list(args.normalization[1]), args.stats or "arguments"), flush=True)
-    stats = folder_run.run_precision("predict", lambda precision, **auto: predict_folder(
-        args.root_path, args.model_path, precision, args.exclude_nodes, not args.no_small_zones, idx, **auto, **kw), args.precision)
+    stats = folder_run.run_precision("predict", lambda precision, **over: predict_folder(
+        args.root_path, args.model_path, precision, args.exclude_nodes, not args.no_small_zones, idx, **dict(kw, **over)),
+        args.precision, args.bn_stats)
     if stats["rank"] == 0:
         print("predicted %(images_total)d images (%(images_this_rank)d on rank 0, %(batches)d batches): %(total_s).2f s, "
               "%(images_per_s_loop).1f images/s in the loop on this rank" % stats)
