@@ -16,7 +16,7 @@
 // weights per image (L2-resident after the first image); concat reads 5/4 x M x 256 x 4 elements' bytes and writes the same.
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
-#include "split16.hpp"
+#include "stored.hpp"
 
 namespace nbc {
 namespace {
@@ -24,31 +24,6 @@ namespace {
 constexpr int kPoolCin = 2048;
 constexpr int kPoolThreads = kPoolCin / 8;      // a thread owns eight channels of every pixel
 constexpr int kPoolSlices = 256;                // pixel slices per image (fewer when hw is smaller)
-
-// eight consecutive channels [c8, c8 + 8) of stored pixel `pix` (C channels) as f32
-template <int PREC>
-__device__ __forceinline__ void load8(const void* __restrict__ x, size_t pix, int C, int c8, float (&f)[8]) {
-  if constexpr (PREC == 0) {
-    const uint4* p = reinterpret_cast<const uint4*>(static_cast<const float*>(x) + pix * C + c8);
-    const uint4 a = p[0], b = p[1];
-    f[0] = __builtin_bit_cast(float, a.x); f[1] = __builtin_bit_cast(float, a.y);
-    f[2] = __builtin_bit_cast(float, a.z); f[3] = __builtin_bit_cast(float, a.w);
-    f[4] = __builtin_bit_cast(float, b.x); f[5] = __builtin_bit_cast(float, b.y);
-    f[6] = __builtin_bit_cast(float, b.z); f[7] = __builtin_bit_cast(float, b.w);
-  } else if constexpr (PREC == 2) {             // h0 chunk (c8 % 32) / 8 of group c8 / 32, its h1 chunk 64 bytes on
-    const uint4* p = reinterpret_cast<const uint4*>(static_cast<const unsigned char*>(x) + pix * C * 4 + (c8 >> 5) * 128 +
-                                                    (c8 & 31) * 2);
-    join16x8(p[0], p[4], f);
-  } else {
-    const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(x) + pix * C + c8);
-    const unsigned u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-      f[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xffff0000u);
-    }
-  }
-}
 
 // (1) grid (slices, N), 256 threads: partial[img][slice][c] = sum over the slice's pixels, in pixel order
 template <int PREC>
@@ -63,7 +38,7 @@ __global__ __launch_bounds__(kPoolThreads) void aspp_pool_partial_kernel(const v
   for (; p + 4 <= p1; p += 4) {                 // four pixels' loads in flight, summed in pixel order
     float f[4][8];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) load8<PREC>(x, base + p + q, kPoolCin, c8, f[q]);
+    for (int q = 0; q < 4; ++q) read8<PREC>(x, base + p + q, kPoolCin, c8, f[q]);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -71,7 +46,7 @@ __global__ __launch_bounds__(kPoolThreads) void aspp_pool_partial_kernel(const v
   }
   for (; p < p1; ++p) {
     float f[8];
-    load8<PREC>(x, base + p, kPoolCin, c8, f);
+    read8<PREC>(x, base + p, kPoolCin, c8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s[e] += f[e];
   }
@@ -107,18 +82,7 @@ __global__ __launch_bounds__(256) void aspp_pool_conv_kernel(const float* __rest
   acc = wave_sum(acc);
   if (lane != 0) return;
   const float v = __builtin_fmaxf(__builtin_fmaf(acc, scale[o], shift[o]), 0.f);
-  const size_t at = (size_t)img * cout + o;
-  if constexpr (PREC == 0) {
-    static_cast<float*>(y)[at] = v;
-  } else if constexpr (PREC == 2) {
-    _Float16 h0, h1;
-    split16(v, h0, h1);
-    _Float16* yp = static_cast<_Float16*>(y) + (size_t)img * cout * 2 + (o >> 5) * 64 + (o & 31);
-    yp[0] = h0;
-    yp[32] = h1;
-  } else {
-    static_cast<__bf16*>(y)[at] = (__bf16)v;
-  }
+  store_elem<PREC>(y, (size_t)img * cout + o, img, cout, o, v);
 }
 
 struct ConcatSrc {

@@ -34,14 +34,6 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
-  return __builtin_bit_cast(float, (unsigned)b << 16);
-}
-__device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-
 // Diagnostic build (tools/conv_timeline.hip, -DNBC_STAMPS): thread 0 of every block writes the 100 MHz
 // wall clock at phase boundaries into a buffer nothing else reads, and every wave counts the shader
 // cycles it spends in the K loop's vm-wait and barrier.  The kernel only calls these hooks; in the

@@ -3,14 +3,14 @@
 // of the mask from ONE read of the stored input of classifier.4.  The definition of a draw is in include/nbc.h
 // (nbc_dropout_draws); the generator is csrc/philox.hpp, shared with the host entry point nbc_dropout_mask below.
 //
-// The arithmetic is head1x1_body's (pointwise.hip; the operands come in through the same head1x1.hpp) with one
+// The arithmetic is head1x1_body's (pointwise.hip; the operands come in through the same load8 / decode8 of stored.hpp) with one
 // multiplication in front of it: one wave per pixel, lane l owns channels 8l .. 8l+7 -- elements 512 pixel + 8l .. + 7,
 // i.e. quads 128 pixel + 2l and + 1: two Philox calls per lane, pixel and draw --, an f32 fma chain in channel order, then
 // wave_sum and the bias.  With p = 0 the factor is 1.0f for every element and the logits are bit for bit the forward's.
-#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "philox.hpp"
 #include "reduce.hpp"
+#include "stored.hpp"
 
 namespace nbc {
 namespace {
@@ -36,15 +36,15 @@ __global__ __launch_bounds__(256) void head1x1_dropout_kernel(const void* __rest
   const int first = (blockIdx.x * 4 + wave) * 8;
   if (first >= hw) return;                                // wave-uniform: the shuffles below see whole waves
   const unsigned char* xi = static_cast<const unsigned char*>(x) + (size_t)img * hw * CIN * (PREC == 1 ? 2 : 4);
-  Head1x1Raw<PREC> raw[8];
+  Eight<PREC> raw[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) raw[q] = head1x1_load<PREC, CIN>(xi, min(first + q, hw - 1), lane);
+  for (int q = 0; q < 8; ++q) raw[q] = load8<PREC>(eight_at<PREC>(xi + (size_t)min(first + q, hw - 1) * CIN * stored_elem_bytes(PREC), lane * 8));
   bool bad = false;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int pix = first + q;
     float f[8];
-    head1x1_decode(raw[q], f);
+    decode8(raw[q], f);
     const unsigned quad = (unsigned)pix * 128u + 2u * (unsigned)lane;   // hw * 128 < 2^32 (checked by the caller)
     for (int d = 0; d < draws; ++d) {
       const Philox4 r0 = dropout_words(quad, (unsigned)(first_draw + d), id, seed);

@@ -770,30 +770,17 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         e = launch_aspp_concat(br, c->bufs[o.cat_in[4]], c->bufs[o.out_buf], N, o.Ho * o.Wo, prec, s);
         break;
       }
-      case OP_BN_STATS:
-      case OP_BN_APPLY: {
-        // the workspace: slice partials, then the [N][C] scale and shift tables of this BatchNorm (stats writes, apply reads)
-        const int hw = o.Ho * o.Wo;
-        float* scale = reinterpret_cast<float*>(static_cast<unsigned char*>(c->bn_ws) +
-                                                (size_t)N * bn_stats_slices(hw) * o.Co * 2 * sizeof(double));
-        float* shift = scale + (size_t)N * o.Co;
-        if (o.kind == OP_BN_STATS) {
-          const float* gamma = c->bn_affine + o.affine_off;
-          if (prec == NBC_PREC_F16X2)                  // the unit's 2^-r follows its raw scales; the table carries the tensor's 2^a_out
-            e = launch_bn_stats_f16x2(c->bufs[o.out_buf], N, hw, o.Co, gamma, gamma + o.Co, c->bn_raw + o.affine_off + o.Co,
-                                      c->act_exp[o.unit], c->bn_ws, scale, shift, c->nonfinite, s);
-          else
-            e = launch_bn_stats(static_cast<const float*>(c->bufs[o.out_buf]), N, hw, o.Co, gamma, gamma + o.Co, c->bn_ws, scale,
-                                shift, s);
-        } else if (prec == NBC_PREC_F16X2) {
-          e = launch_bn_apply_f16x2(c->bufs[o.out_buf], o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr, N, hw, o.Co, scale, shift,
-                                    o.relu, s);
-        } else {
-          e = launch_bn_apply(static_cast<float*>(c->bufs[o.out_buf]), o.res_buf >= 0 ? static_cast<const float*>(c->bufs[o.res_buf]) : nullptr,
-                              N, hw, o.Co, scale, shift, o.relu, s);
-        }
+      case OP_BN_STATS: {                              // f16x2: the unit's 2^-r follows its raw scales; the table carries the tensor's 2^a_out
+        const float* gamma = c->bn_affine + o.affine_off;
+        const bool x2 = prec == NBC_PREC_F16X2;
+        e = launch_bn_stats(c->bufs[o.out_buf], N, o.Ho * o.Wo, o.Co, gamma, gamma + o.Co, x2 ? c->bn_raw + o.affine_off + o.Co : nullptr,
+                            x2 ? c->act_exp[o.unit] : 0, c->bn_ws, c->nonfinite, prec, s);
         break;
       }
+      case OP_BN_APPLY:                                // with the tables the statistics op left in the workspace
+        e = launch_bn_apply(c->bufs[o.out_buf], o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr, N, o.Ho * o.Wo, o.Co, c->bn_ws, o.relu, prec,
+                            s);
+        break;
       case OP_DWCONV: {
         const UnitPtrs p = unit_ptrs(c, o.unit);
         const ConvUnit& u = conv_units(c->arch)[o.unit];

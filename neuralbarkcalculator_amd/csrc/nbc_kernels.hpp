@@ -99,26 +99,26 @@ hipError_t launch_aspp_pool(const void* x, int N, int hw, int cin, const float* 
 // ASPP concat: y [N*hw][1280] elements = the four branches [N*hw][256] then the image's pooled vector [N][256], per pixel.
 hipError_t launch_aspp_concat(const void* const branch[4], const void* pooled, void* y, int N, int hw, int precision,
                               hipStream_t s);
-// Per-image BatchNorm (bn_stats.hip), f32 NHWC y [N][hw][C], C a power of two in [64, 2048].  bn_stats: per (image,
-// channel) mean and biased variance over hw pixels in two levels over bn_stats_slices(hw) fixed slices (f64), then
-// scale[n][c] = gamma[c] / sqrt(var + 1e-5), shift[n][c] = beta[c] - mean * scale.  ws: bn_stats_workspace_bytes(N, hw, C)
-// bytes, of which the slice partials are the first N * slices * C * 16.  bn_apply: in place, y = relu?(fma(y, scale, shift)
-// (+ res)), res nullable.
+// Per-image BatchNorm (bn_stats.hip) of NHWC y [N][hw][C], C a power of two in [64, 2048], precision 0 or 2 (1: invalid value).
+// bn_stats: per (image, channel) mean and biased variance over hw pixels in two levels over bn_stats_slices(hw) fixed slices
+// (f64), then scale[n][c] = gamma[c] / sqrt(var + 1e-5), shift[n][c] = beta[c] - mean * scale.  ws: bn_stats_workspace_bytes(N,
+// hw, C) bytes: the slice partials (N * slices * C * 16 bytes), then the two [N][C] tables, where bn_stats_tables finds them.
+// bn_apply: in place, y = relu?(fma(y, scale, shift) (+ res)) with the tables bn_stats left in ws, res nullable.
+// f16x2 (same slices, lane and slice orders, workspace): y holds 2^r_c x per channel c, inv_r[c] = 2^-r_c (nbc_pack_bn_raw); the
+// statistics are those of x, the table is for the stored value and carries the power 2^a_out the normalised tensor (and res) is
+// stored with: scale = f32(sc) 2^(a_out - r_c), shift = f32(beta - mean sc) 2^a_out.  word (nullable) gets bit
+// NBC_NONFINITE_BN_RANGE when a channel's stored rms is not finite, above 2^12 or positive and below 2^-10.  f32 reads none of
+// inv_r, a_out and word.
+struct BnTables {
+  float* scale;   // [N][C]
+  float* shift;   // [N][C]
+};
 int bn_stats_slices(int hw);
 size_t bn_stats_workspace_bytes(int N, int hw, int C);
-hipError_t launch_bn_stats(const float* y, int N, int hw, int C, const float* gamma, const float* beta, void* ws, float* scale,
-                           float* shift, hipStream_t s);
-hipError_t launch_bn_apply(float* y, const float* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
-                           hipStream_t s);
-// The same on f16x2 pieces (NBC_PREC_F16X2; same slices, lane and slice orders, workspace).  y holds 2^r_c x per channel c,
-// inv_r[c] = 2^-r_c (nbc_pack_bn_raw); the statistics are those of x, the table is for the stored value and carries the power
-// 2^a_out the normalised tensor is stored with: scale = f32(sc) 2^(a_out - r_c), shift = f32(beta - mean sc) 2^a_out.  word
-// (nullable) gets bit NBC_NONFINITE_BN_RANGE when a channel's stored rms is not finite, above 2^12 or positive and below 2^-10.
-// bn_apply: in place on pieces, res (pieces, stored with 2^a_out) nullable.
-hipError_t launch_bn_stats_f16x2(const void* y, int N, int hw, int C, const float* gamma, const float* beta, const float* inv_r,
-                                 int a_out, void* ws, float* scale, float* shift, unsigned* word, hipStream_t s);
-hipError_t launch_bn_apply_f16x2(void* y, const void* res, int N, int hw, int C, const float* scale, const float* shift, int relu,
-                                 hipStream_t s);
+BnTables bn_stats_tables(void* ws, int N, int hw, int C);
+hipError_t launch_bn_stats(const void* y, int N, int hw, int C, const float* gamma, const float* beta, const float* inv_r, int a_out,
+                           void* ws, unsigned* word, int precision, hipStream_t s);
+hipError_t launch_bn_apply(void* y, const void* res, int N, int hw, int C, void* ws, int relu, int precision, hipStream_t s);
 // EfficientNet (efficientnet.hip), f32 NHWC, C a multiple of 64.
 // Depthwise k x k conv (k 3 / 5, stride 1 / 2) of x [N][Hi][Wi][C] with weights [k*k][C], top / left pads pad_t / pad_l
 // (a tap outside the image reads 0), y [N][Ho][Wo][C] = swish(fma(acc, scale, shift)); in_swish: x is stored before its

@@ -3,21 +3,12 @@
 // lane accesses, no MFMA.
 #include <cstdlib>
 
-#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
-#include "split16.hpp"
+#include "stored.hpp"
 
 namespace nbc {
 namespace {
-
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
-  return __builtin_bit_cast(float, (unsigned)b << 16);
-}
-__device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
 
 // One pixel's three normalised channels -> one 16-byte NHWC pixel (f32x4 or bf16x8, zero padded).
 template <int PREC>
@@ -76,7 +67,8 @@ __global__ void ingest_u8_kernel(const uint8_t* __restrict__ x, void* __restrict
 // MaxPool2d(kernel 3, stride 2, padding 1): padding is -inf, i.e. out-of-range taps do not count;
 // NaN propagates like ATen's max_pool2d (a NaN tap wins): v_maximum3_f32.
 // grid = (ceil(Wo*chunks / 256), Ho, N); a thread owns one 16-byte channel chunk of one output pixel,
-// consecutive threads consecutive chunks (whole 128/256-byte pixel rows per 8/16 lanes).
+// consecutive threads consecutive chunks (whole 128/256-byte pixel rows per 8/16 lanes).  It keeps its own address
+// arithmetic and decode (the unit of stored.hpp gives its f16x2 form other machine code).
 template <int PREC>
 __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x, void* __restrict__ y, int Hi, int Wi,
                                                       int chunk_shift, int Ho, int Wo) {
@@ -170,14 +162,15 @@ __device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
   const int first = (blockIdx.x * 4 + wave) * PIX_PER_WAVE;
   if (counts_zero && blockIdx.x == 0 && threadIdx.x < ncounts) counts_zero[threadIdx.x] = 0ull;   // for the next launch
   // the wave's 8 pixel rows (loads) are requested together (one memory round trip), then reduced one by one
-  Head1x1Raw<PREC> raw[8];
+  const unsigned char* xb = static_cast<const unsigned char*>(x);
+  Eight<PREC> raw[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) raw[q] = head1x1_load<PREC, CIN>(x, min(first + q * PPL + sub, M - 1), cl);
+  for (int q = 0; q < 8; ++q) raw[q] = load8<PREC>(eight_at<PREC>(xb + (size_t)min(first + q * PPL + sub, M - 1) * CIN * stored_elem_bytes(PREC), cl * 8));
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int m = first + q * PPL + sub;
     float f[8];
-    head1x1_decode(raw[q], f);
+    decode8(raw[q], f);
     float s[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -425,13 +418,7 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ x, float* __restric
     const int c = (int)(i % C);
     const size_t pix = i / C;                 // img*HW + p
     const size_t img = pix / HW, p = pix - img * HW;
-    float v;
-    if constexpr (PREC == 0) v = static_cast<const float*>(x)[i];
-    else if constexpr (PREC == 2) {
-      const _Float16* hp = static_cast<const _Float16*>(x) + pix * (size_t)C * 2 + (c >> 5) * 64 + (c & 31);
-      v = join16(hp[0], hp[32]);
-    } else v = bf16_bits_to_f32(static_cast<const unsigned short*>(x)[i]);
-    y[(img * C + c) * (size_t)HW + p] = v;
+    y[(img * C + c) * (size_t)HW + p] = load_elem<PREC>(x, i, pix, C, c);
   }
 }
 
@@ -441,15 +428,9 @@ template <int PREC>
 __global__ void absmax_kernel(const void* __restrict__ x, size_t elems, int C, unsigned* __restrict__ out) {
   float m = 0.f;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < elems; i += (size_t)gridDim.x * blockDim.x) {
-    float v;
-    if constexpr (PREC == 0) v = static_cast<const float*>(x)[i];
-    else if constexpr (PREC == 2) {
-      const size_t pix = i / C;
-      const int c = (int)(i - pix * C);
-      const _Float16* hp = static_cast<const _Float16*>(x) + pix * (size_t)C * 2 + (c >> 5) * 64 + (c & 31);
-      v = join16(hp[0], hp[32]);
-    } else v = bf16_bits_to_f32(static_cast<const unsigned short*>(x)[i]);
-    v = __builtin_fabsf(v);
+    const size_t pix = i / C;
+    const int c = (int)(i - pix * C);
+    const float v = __builtin_fabsf(load_elem<PREC>(x, i, pix, C, c));
     if (v < __builtin_inff() && v > m) m = v;          // NaN and infinity do not count (the non-finite flag reports those)
   }
 #pragma unroll

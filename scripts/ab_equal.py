@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Do two builds of libnbc_hip.so compute the same bits from the same plan?  Per network, precision and BatchNorm mode, on a few
-seeded frames: full-resolution logits and labels, and what each build planned (op records without their timings, plan tiles).
+seeded frames: full-resolution logits and labels, and what each build planned (op records without their timings, plan tiles);
+for the ResNet-50 networks also keep-mode reads of a few activations (the max-pool, one unit each of 64, 128, 256 and 2048
+channels, DeepLab's pooled vector and concat) and the calibration guard's peaks, byte for byte, on one small batch.
 Then the per-image reduction passes on the same seeded inputs, every output buffer byte for byte: nbc_confusion (u8 and i64
 labels), nbc_image_moments and nbc_target_counts -- these three also on views that start 1, 5 and 17 bytes off a 16-byte
 boundary --, nbc_pixel_cross_entropy, nbc_lovasz_softmax, and dropout_draws (p = 0.1, low-resolution logits, small zones on
@@ -23,7 +25,15 @@ TWO = (([5], 520, 1024), ([3, 4], 200, 328))                     # batch 1 and b
 CASES = [("fcn_resnet50", p, "running", THREE) for p in ("f16x2", "fp32", "bf16")]
 CASES += [("deeplabv3_resnet50", p, "running", TWO) for p in ("f16x2", "fp32", "bf16")]
 CASES += [("fcn_efficientnet_b0", "fp32", "running", TWO), ("deeplabv3_efficientnet_b0", "fp32", "running", TWO),
-          ("fcn_resnet50", "fp32", "image", TWO)]
+          ("fcn_resnet50", "fp32", "image", TWO), ("fcn_resnet50", "f16x2", "image_f16x2", TWO)]
+# keep-mode reads, (name, channels): their maps are at most a quarter of the image each way
+KEEP_SHAPE = ([3, 4], 200, 328)
+KEPT = {"fcn_resnet50": [("backbone.maxpool", 64), ("backbone.layer1.0.conv1", 64), ("backbone.layer2.0.conv1", 128),
+                         ("backbone.layer1.0.conv3", 256), ("backbone.layer4.2.conv3", 2048)]}
+KEPT["deeplabv3_resnet50"] = KEPT["fcn_resnet50"] + [("classifier.0.convs.4", 256), ("classifier.0.concat", 1280)]
+KEEP_CASES = {("fcn_resnet50", p, "running") for p in ("f16x2", "fp32", "bf16")} | {
+    ("deeplabv3_resnet50", "f16x2", "running"), ("deeplabv3_resnet50", "bf16", "running"),
+    ("fcn_resnet50", "fp32", "image"), ("fcn_resnet50", "f16x2", "image_f16x2")}
 state_dicts = {}
 
 
@@ -58,8 +68,35 @@ def run(m, x):
     return logits, m.predict_labels(x, labels_dtype=torch.uint8)[0], (plan, m.plan_tiles())
 
 
+def kept(m, arch, x):
+    """keep-mode reads of one forward, and the stored peaks of another"""
+    n, _, h, w = x.shape
+    m.set_keep_activations(True)
+    m(x)
+    out = {name: torch.from_numpy(m.read_activation(name, n * ch * ((h + 3) // 4) * ((w + 3) // 4)).copy()) for name, ch in KEPT[arch]}
+    m.set_keep_activations(False)
+    peaks = m.activation_peaks(x)
+    out["activation_peaks"] = torch.tensor([peaks[k] for k in sorted(peaks)], dtype=torch.float32)
+    return out
+
+
+def same_bytes(p, q):
+    return p.shape == q.shape and p.dtype == q.dtype and torch.equal(p.contiguous().view(torch.uint8), q.contiguous().view(torch.uint8))
+
+
+def compare(what, outs_a, outs_b):
+    diff = [k for k in outs_a if not same_bytes(outs_a[k], outs_b[k])]
+    print("%s: %s" % (what, "identical (%d buffers)" % len(outs_a) if not diff else "DIFFERENT in " + ", ".join(diff)), flush=True)
+    return len(diff)
+
+
+KEEP_CALLS_OK = all(hasattr(lib_of(p), name) for p in sys.argv[1:3]
+                    for name in ("nbc_set_keep_activations", "nbc_read_activation", "nbc_activation_peaks"))
 bad = 0
 for arch, precision, bn, shapes in CASES:
+    if bn == "image_f16x2" and not all(hasattr(lib_of(p), "nbc_attach_bn_raw") for p in sys.argv[1:3]):
+        print("%s %s bn=%s: skipped, a library lacks nbc_attach_bn_raw" % (arch, precision, bn), flush=True)
+        continue
     a, b = model_on(sys.argv[1], arch, precision, bn), model_on(sys.argv[2], arch, precision, bn)
     for idx, h, w in shapes:
         x = torch.from_numpy(np.stack([synth.make_input(i, h, w) for i in idx])).to(dev)
@@ -69,6 +106,12 @@ for arch, precision, bn, shapes in CASES:
         print("%s %s bn=%s %s x %dx%d: %s (max |logit difference| %.3e), plans %s (%d ops, %d tiles)" %
               (arch, precision, bn, idx, h, w, "identical" if same else "DIFFERENT", float((la - lb).abs().max()),
                "equal" if pa == pb else "DIFFERENT", len(pa[0]), len(pa[1])), flush=True)
+    if (arch, precision, bn) in KEEP_CASES and not KEEP_CALLS_OK:
+        print("%s %s bn=%s kept activations and peaks: skipped, a library lacks a keep-mode call" % (arch, precision, bn), flush=True)
+    elif (arch, precision, bn) in KEEP_CASES:
+        idx, h, w = KEEP_SHAPE
+        x = torch.from_numpy(np.stack([synth.make_input(i, h, w) for i in idx])).to(dev)
+        bad += compare("%s %s bn=%s %s x %dx%d kept activations and peaks" % (arch, precision, bn, idx, h, w), kept(a, arch, x), kept(b, arch, x))
     a._destroy()
     b._destroy()
 
@@ -126,16 +169,6 @@ def loss_passes(lib, n, h, w, logits, grey, stream):
                                    stream), "nbc_lovasz_softmax")
     out["lovasz workspace bytes"], out["lovasz terms"], out["lovasz fg_counts"] = torch.tensor([need]), terms, fg
     return out
-
-
-def same_bytes(p, q):
-    return p.shape == q.shape and p.dtype == q.dtype and torch.equal(p.contiguous().view(torch.uint8), q.contiguous().view(torch.uint8))
-
-
-def compare(what, outs_a, outs_b):
-    diff = [k for k in outs_a if not same_bytes(outs_a[k], outs_b[k])]
-    print("%s: %s" % (what, "identical (%d buffers)" % len(outs_a) if not diff else "DIFFERENT in " + ", ".join(diff)), flush=True)
-    return len(diff)
 
 
 libs = [lib_of(p) for p in sys.argv[1:3]]
