@@ -510,6 +510,43 @@ int nbc_dropout_draws(nbc_ctx* ctx, int N, int H, int W, const uint64_t* image_i
                       int first_draw, int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev,
                       int64_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
 
+/* ---- per-pixel votes of the draws ------------------------------------------------------------
+ * Where in the image the draws disagree.  The definition (csrc/votes.hpp), for D draws, 1 <= D <= 65535:
+ *   vote word  one uint32 per pixel: bits 0..15 = n1, the draws whose final label is 1; bits 16..31 = n2, the draws whose
+ *              final label is 2; n0 = D - n1 - n2.  A label outside {0,1,2} votes nowhere, as nbc_confusion counts it nowhere.
+ *   winner     the class with the most votes; a tie goes to the lowest class index (torch.argmax's first maximum)
+ *   support    floor(255 * n_win / D) in integer arithmetic: 255 exactly when the draws are unanimous, never below 85
+ *   invalid    a word with n1 + n2 > D cannot come from D draws: label 0, support 0, and of the statistics below it reaches
+ *              slot 7 alone
+ *   statistics int64 [NBC_VOTE_STATS] per image: 0..2 pixels per winning class, 3..5 unanimous pixels per class, 6 the sum
+ *              of n_win, 7 invalid words, 8 the sum of n1, 9 the sum of n2 */
+#define NBC_VOTE_STATS 10
+/* Host only, no context, no device: the winner and the support byte of one word under `draws` draws (either pointer may be
+ * null).  NBC_ERR_INVALID: draws outside 1..65535. */
+int nbc_vote_decode(uint32_t word, int draws, uint8_t* label, uint8_t* support);
+/* nbc_dropout_draws -- the same arguments, workspace, refusals, stream semantics, and bit for bit the same logits and counts
+ * -- which also counts each pass's final labels into the vote words before the next pass overwrites them.
+ * votes_dev   uint32 [N][H][W], 16-byte aligned
+ * accumulate  0: the words are overwritten (the first pass stores them; no memset is needed); 1: the draws are added to what
+ *             the words hold.  The caller keeps the total of the draws added into a word at or below 65535.
+ * NBC_ERR_INVALID as nbc_dropout_draws (draws > 1024 among them), and a null or misaligned votes_dev.  NBC_ERR_STATE as
+ * nbc_dropout_draws.  Messages begin "nbc_dropout_votes:". */
+int nbc_dropout_votes(nbc_ctx* ctx, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed,
+                      int first_draw, int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev,
+                      int64_t* counts_dev, uint32_t* votes_dev, int accumulate, void* workspace_dev, size_t workspace_bytes,
+                      void* hip_stream);
+/* The decision on every word and the statistics of every image.  No context: csrc/dropout_votes.hip.
+ * votes_dev    uint32 [N][H][W], any 4-byte alignment (a 16-byte aligned buffer is read by 16-byte loads)
+ * draws        D, the draws the words hold
+ * labels_dev   nullable, uint8 [N][H][W]: the winner
+ * support_dev  nullable, uint8 [N][H][W]: the support byte
+ * stats_dev    int64 [N][NBC_VOTE_STATS]; overwritten
+ * Integer sums: an image's numbers are the same alone, in any batch and on any stream.  Runs on hip_stream (the caller's
+ * current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null votes_dev or stats_dev, N < 1 or
+ * N > 65535, H or W < 1, H * W >= 2^31, draws outside 1..65535, a votes_dev that is not 4-byte aligned. */
+int nbc_vote_summary(const uint32_t* votes_dev, int N, int H, int W, int draws, uint8_t* labels_dev, uint8_t* support_dev,
+                     int64_t* stats_dev, void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

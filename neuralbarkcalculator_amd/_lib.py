@@ -21,6 +21,7 @@ PACK_ROW_CLAMPED, PACK_SCALE_RANGE = 1, 2      # NBC_PACK_* of include/nbc.h
 ARCH_FCN_RESNET50, ARCH_DEEPLABV3_RESNET50 = 0, 1   # NBC_ARCH_*
 ARCH_FCN_EFFICIENTNET_B0, ARCH_DEEPLABV3_EFFICIENTNET_B0 = 16, 24   # + n, n = 0..7
 BN_RUNNING, BN_PER_IMAGE = 0, 1                     # NBC_BN_*
+VOTE_STATS = 10                                     # NBC_VOTE_STATS
 
 
 class NbcTensor(C.Structure):
@@ -113,6 +114,11 @@ SIGNATURES = {
     "nbc_dropout_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nbc_dropout_draws": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nbc_vote_decode": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "nbc_dropout_votes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "nbc_vote_summary": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbc_resize_cubic_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nbc_preprocess_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p]),

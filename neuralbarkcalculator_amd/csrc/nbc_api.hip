@@ -883,6 +883,73 @@ static DropoutLayout dropout_layout(int N, int H, int W, int h, int w, int draws
   return {lowres, labels, parent, size, bg, ws.offset};
 }
 
+// The pass loop behind nbc_dropout_draws and nbc_dropout_votes (`who` prefixes the error messages): the masked classifier,
+// the upsample + argmax, remove_small_zones and the counts of each pass; with `with_votes`, the pass's final labels are
+// counted into votes_dev before the next pass overwrites them.
+static int dropout_passes(const char* who, nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed,
+                          int first_draw, int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev,
+                          int64_t* counts_dev, bool with_votes, uint32_t* votes_dev, int accumulate, void* workspace_dev,
+                          size_t workspace_bytes, void* hip_stream) {
+  const auto refuse = [who](int code, const std::string& msg) { return set_error(code, std::string(who) + ": " + msg); };
+  if (!dropout_p_ok(p)) return refuse(NBC_ERR_INVALID, "p must lie in [0, 1)");
+  if (draws < 1 || draws > 1024) return refuse(NBC_ERR_INVALID, "draws must lie in 1..1024");
+  if (first_draw < 0 || first_draw > 0x7fffffff - draws)
+    return refuse(NBC_ERR_INVALID, "first_draw must not be negative (and first_draw + draws < 2^31)");
+  if (min_pixels < 0) return refuse(NBC_ERR_INVALID, "min_pixels must not be negative");
+  if (!c || !image_ids_host || !counts_dev || !workspace_dev || (with_votes && !votes_dev)) return refuse(NBC_ERR_INVALID, "null argument");
+  if (with_votes && reinterpret_cast<uintptr_t>(votes_dev) % 16 != 0) return refuse(NBC_ERR_INVALID, "votes_dev must be 16-byte aligned");
+  if (c->arch != kArchFcn)
+    return refuse(NBC_ERR_STATE, std::string("NBC_ARCH_FCN_RESNET50 only, the context holds ") + arch_name(c->arch) +
+                                     " (DeepLabHead's Dropout sits inside ASPP; the EfficientNet heads are left out)");
+  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
+    return refuse(NBC_ERR_STATE, "the context's last forward was not one of this (N, H, W), or its plan has been touched since: run "
+                                 "nbc_forward first");
+  const size_t one = nbc_dropout_workspace_bytes(N, H, W, 1);
+  if (one == 0) return refuse(NBC_ERR_INVALID, "shape beyond the limits (N <= 65535, H * W < 2^31, h * w < 2^25)");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) % 256 != 0) return refuse(NBC_ERR_INVALID, "the workspace must be 256-byte aligned");
+  if (workspace_bytes < one)
+    return refuse(NBC_ERR_INVALID, "the workspace is smaller than nbc_dropout_workspace_bytes(N, H, W, 1)");
+  const Plan& P = c->plan;
+  const Op* head = nullptr;
+  for (const Op& o : P.ops)
+    if (o.kind == OP_HEAD1X1) head = &o;
+  if (!head || head->Ci != 512 || head->in_buf < 0 || !c->nonfinite)
+    return refuse(NBC_ERR_STATE, "the plan holds no classifier.4 of 512 input channels");
+  int pass = std::min(draws, 65535 / N);
+  while (pass > 1 && nbc_dropout_workspace_bytes(N, H, W, pass) > workspace_bytes) --pass;
+  NBC_HIP(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const UnitPtrs up = unit_ptrs(c, head->unit);
+  const int hw = P.h * P.w;
+  const uint32_t T = dropout_threshold(p);
+  const float m = dropout_scale(p);
+  for (int d0 = 0; d0 < draws; d0 += pass) {
+    const int D = std::min(pass, draws - d0);
+    const int I = D * N;
+    // the pass's slice of the workspace, sized for THIS pass (the last one may be shorter)
+    const DropoutLayout L = dropout_layout(N, H, W, P.h, P.w, D);
+    unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws + L.lowres);
+    unsigned char* labels = ws + L.labels;
+    int* parent = reinterpret_cast<int*>(ws + L.parent);
+    int* size = reinterpret_cast<int*>(ws + L.size);
+    unsigned char* bg = ws + L.bg;
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
+    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf], up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
+                                   first_draw + d0, D, c->nonfinite, s));
+    if (min_pixels > 0) {
+      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, nullptr, 0, s));
+      NBC_HIP(launch_remove_small_zones(labels, 0, I, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s));
+    } else {
+      NBC_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * kNumClasses * I, s));
+      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, counts, exclude_nodes, s));
+    }
+    if (with_votes)                                 // the first pass of a call that does not accumulate stores the words
+      NBC_HIP(launch_vote_accumulate(labels, D, N, (long long)H * W, votes_dev, !accumulate && d0 == 0, s));
+  }
+  return NBC_OK;
+}
+
 extern "C" {
 
 int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W, int reps, int objective,
@@ -1015,62 +1082,15 @@ size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
 int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
                       int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev, int64_t* counts_dev,
                       void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
-  if (!dropout_p_ok(p)) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: p must lie in [0, 1)");
-  if (draws < 1 || draws > 1024) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: draws must lie in 1..1024");
-  if (first_draw < 0 || first_draw > 0x7fffffff - draws)
-    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: first_draw must not be negative (and first_draw + draws < 2^31)");
-  if (min_pixels < 0) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: min_pixels must not be negative");
-  if (!c || !image_ids_host || !counts_dev || !workspace_dev) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: null argument");
-  if (c->arch != kArchFcn)
-    return set_error(NBC_ERR_STATE, std::string("nbc_dropout_draws: NBC_ARCH_FCN_RESNET50 only, the context holds ") +
-                                        arch_name(c->arch) + " (DeepLabHead's Dropout sits inside ASPP; the EfficientNet heads are "
-                                        "left out)");
-  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
-    return set_error(NBC_ERR_STATE, "nbc_dropout_draws: the context's last forward was not one of this (N, H, W), or its plan has "
-                                    "been touched since: run nbc_forward first");
-  const size_t one = nbc_dropout_workspace_bytes(N, H, W, 1);
-  if (one == 0) return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: shape beyond the limits (N <= 65535, H * W < 2^31, h * w < 2^25)");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) % 256 != 0)
-    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: the workspace must be 256-byte aligned");
-  if (workspace_bytes < one)
-    return set_error(NBC_ERR_INVALID, "nbc_dropout_draws: the workspace is smaller than nbc_dropout_workspace_bytes(N, H, W, 1)");
-  const Plan& P = c->plan;
-  const Op* head = nullptr;
-  for (const Op& o : P.ops)
-    if (o.kind == OP_HEAD1X1) head = &o;
-  if (!head || head->Ci != 512 || head->in_buf < 0 || !c->nonfinite)
-    return set_error(NBC_ERR_STATE, "nbc_dropout_draws: the plan holds no classifier.4 of 512 input channels");
-  int pass = std::min(draws, 65535 / N);
-  while (pass > 1 && nbc_dropout_workspace_bytes(N, H, W, pass) > workspace_bytes) --pass;
-  NBC_HIP(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  const UnitPtrs up = unit_ptrs(c, head->unit);
-  const int hw = P.h * P.w;
-  const uint32_t T = dropout_threshold(p);
-  const float m = dropout_scale(p);
-  for (int d0 = 0; d0 < draws; d0 += pass) {
-    const int D = std::min(pass, draws - d0);
-    const int I = D * N;
-    // the pass's slice of the workspace, sized for THIS pass (the last one may be shorter)
-    const DropoutLayout L = dropout_layout(N, H, W, P.h, P.w, D);
-    unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
-    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws + L.lowres);
-    unsigned char* labels = ws + L.labels;
-    int* parent = reinterpret_cast<int*>(ws + L.parent);
-    int* size = reinterpret_cast<int*>(ws + L.size);
-    unsigned char* bg = ws + L.bg;
-    unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
-    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf], up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
-                                   first_draw + d0, D, c->nonfinite, s));
-    if (min_pixels > 0) {
-      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, nullptr, 0, s));
-      NBC_HIP(launch_remove_small_zones(labels, 0, I, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s));
-    } else {
-      NBC_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * kNumClasses * I, s));
-      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, counts, exclude_nodes, s));
-    }
-  }
-  return NBC_OK;
+  return dropout_passes("nbc_dropout_draws", c, N, H, W, image_ids_host, p, seed, first_draw, draws, min_pixels, exclude_nodes,
+                        logits_lowres_dev, counts_dev, false, nullptr, 0, workspace_dev, workspace_bytes, hip_stream);
+}
+
+int nbc_dropout_votes(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
+                      int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev, int64_t* counts_dev,
+                      uint32_t* votes_dev, int accumulate, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+  return dropout_passes("nbc_dropout_votes", c, N, H, W, image_ids_host, p, seed, first_draw, draws, min_pixels, exclude_nodes,
+                        logits_lowres_dev, counts_dev, true, votes_dev, accumulate, workspace_dev, workspace_bytes, hip_stream);
 }
 
 int nbc_resize_cubic_u8(nbc_ctx* c, const uint8_t* src_dev, int H, int W, float* dst_dev, int out_h, int out_w,

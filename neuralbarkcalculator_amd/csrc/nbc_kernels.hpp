@@ -90,6 +90,11 @@ struct DropoutIds {
 hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bias, float* y, int N, int hw, int precision,
                                   const uint64_t* ids_host, uint64_t seed, uint32_t threshold, float keep_scale, int first_draw,
                                   int draws, unsigned* nonfinite, hipStream_t s);
+// The votes of a pass of the Dropout draws (dropout_votes.hip; the definition: votes.hpp): the final labels u8 [draws][N][P]
+// of the pass are counted into the vote words u32 [N][P] -- stored when `first`, added to what is there otherwise.
+// draws <= 65535 (a 16-bit field per class), votes 16-byte aligned for the vector path; labels at any address.
+hipError_t launch_vote_accumulate(const unsigned char* labels, int draws, int N, long long P, uint32_t* votes, bool first,
+                                  hipStream_t s);
 // ASPP pooling branch (aspp.hip), per image: mean over hw pixels of x [N][hw][cin = 2048] (stored elements), the 1x1 conv
 // with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout] elements.  Workspaces: partial
 // N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.

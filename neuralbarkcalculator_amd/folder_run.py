@@ -226,6 +226,8 @@ DROPOUT_MAX_DRAWS = 1024
 DROPOUT_COLUMNS = ["Name", "Type", "Output Bark %", "Output Node %", "bark_mean", "bark_std", "bark_min", "bark_max",
                    "node_mean", "node_std", "node_min", "node_max", "draws"]
 DROPOUT_COMPARE_COLUMNS = ["old_bark", "old_node", "bark_inside", "node_inside", "bark_z", "node_z"]
+VOTE_COLUMNS = ["Name", "Type", "draws", "Vote Bark %", "Vote Node %", "unanimous %", "mean_support", "changed_pixels"]
+VOTE_STATS = 10                                      # NBC_VOTE_STATS of include/nbc.h
 
 
 def image_id(wood: str, name: str) -> int:
@@ -238,13 +240,16 @@ def image_id(wood: str, name: str) -> int:
     return h
 
 
-def check_dropout_arguments(draws, p=None, seed=None, compare=None, arch: str = "auto", only_preprocess: bool = False) -> None:
+def check_dropout_arguments(draws, p=None, seed=None, compare=None, arch: str = "auto", only_preprocess: bool = False,
+                            votes: bool = False) -> None:
     """``ValueError`` for what ``--dropout_draws`` and its companions refuse before any device is touched.  ``draws``: None =
-    the flag is off, and then ``p``, ``seed`` and ``compare`` must be None too.  On: ``draws`` in 1..1024, ``p`` in [0, 1),
-    ``seed`` an unsigned 64-bit integer, a named ``arch`` fcn_resnet50 (``check_dropout_arch`` once ``"auto"`` is resolved),
+    the flag is off, and then ``p``, ``seed`` and ``compare`` must be None and ``votes`` (``--dropout_votes``) false too.  On:
+    ``draws`` in 1..1024, ``p`` in [0, 1), ``seed`` an unsigned 64-bit integer, a named ``arch`` fcn_resnet50 (``check_dropout_arch`` once ``"auto"`` is resolved),
     and not ``only_preprocess``."""
     if draws is None:
         given = [n for n, v in (("--dropout_p", p), ("--dropout_seed", seed), ("--dropout_compare", compare)) if v is not None]
+        if votes:
+            given.append("--dropout_votes")
         if given:
             raise ValueError("%s needs --dropout_draws" % ", ".join(given))
         return
@@ -357,6 +362,28 @@ def dropout_report(images: Sequence[tuple], draws: int, old: dict = None):
         summary["compare"] = {"images_compared": compared, "bark_inside": inside["bark"], "node_inside": inside["node"],
                               "missing_from_old": missing}
     return rows, summary
+
+
+def vote_report(images: Sequence[tuple], draws: int):
+    """The rows of ``dropout_votes.csv`` (header first) and the folder means.  ``images``: per image ``(name, wood, h, w, stats,
+    changed)`` with the ten integers of nbc_vote_summary (include/nbc.h: pixels per winning class, unanimous pixels per class,
+    the sum of n_win, invalid words, the sums of n1 and n2) and the pixels on which the vote mask differs from the
+    deterministic label.  The vote percentages are printed as ``final_stats.csv`` prints a percentage (``percent_string``);
+    the unanimous percentage ``100 (u0 + u1 + u2) / (h w)`` and the mean support ``sum n_win / (draws h w)`` are each one
+    correctly rounded division of exact integers, formatted '{:.5f}'."""
+    rows, sums = [list(VOTE_COLUMNS)], {}
+    for name, wood, h, w, st, changed in images:
+        px = h * w
+        st = [int(v) for v in st]
+        assert len(st) == VOTE_STATS
+        figures = {"vote_bark": (100 * st[1]) / px, "vote_node": (100 * st[2]) / px, "unanimous": (100 * (st[3] + st[4] + st[5])) / px,
+                   "mean_support": st[6] / (draws * px), "changed_pixels": int(changed)}
+        rows.append([name, wood, str(draws), percent_string(st[1], px), percent_string(st[2], px),
+                     "{:.5f}".format(figures["unanimous"]), "{:.5f}".format(figures["mean_support"]), str(int(changed))])
+        for k, v in figures.items():
+            sums[k] = sums.get(k, 0.0) + v
+    n = len(images)
+    return rows, {"images": n, "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}}
 
 
 def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
@@ -691,6 +718,9 @@ def add_dropout_arguments(ap) -> None:
     ap.add_argument("--dropout_draws", type=int, default=None, metavar="D",
                     help="also sample D random draws (1..1024) of the live Dropout the shipped tool ran with, per image, and write "
                          "results/dropout_stats.csv and dropout_summary.json (fcn_resnet50 only)")
+    ap.add_argument("--dropout_votes", action="store_true",
+                    help="with --dropout_draws: vote per pixel over the draws and write results/dropout_votes/ (the majority "
+                         "mask), results/dropout_support/ (grey, 255 = every draw agrees) and results/dropout_votes.csv")
     ap.add_argument("--dropout_p", type=float, default=None, help="the Dropout probability (default 0.1, FCNHead's)")
     ap.add_argument("--dropout_seed", type=int, default=None, help="64-bit seed of the draws (default 0)")
     ap.add_argument("--dropout_compare", metavar="OLD_final_stats.csv", default=None,

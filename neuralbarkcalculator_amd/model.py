@@ -443,6 +443,26 @@ class FCNResNet50:
         Returns int64 ``[draws, N, 3]`` pixels per class (+ f32 ``[draws, N, 3, h, w]`` low-resolution logits with
         ``return_lowres``).  ``ValueError``: another network than fcn_resnet50, ``draws`` outside 1..1024, ``p`` outside
         [0, 1), a negative ``first_draw``, an id count other than the last forward's batch."""
+        return self._dropout_run("dropout_draws", False, draws, image_ids, p, seed, first_draw, small_zones, exclude_nodes,
+                                 return_lowres, min_pixels, draws_per_pass)
+
+    def dropout_votes(self, draws: int, image_ids, p: float = 0.1, seed: int = 0, first_draw: int = 0,
+                      small_zones: bool = True, exclude_nodes: bool = False, return_lowres: bool = False, *,
+                      min_pixels: int = 150, draws_per_pass: int = 8, return_words: bool = False):
+        """``dropout_draws`` -- the same arguments, checks, refusals and, bit for bit, the same counts and logits -- which also
+        votes per pixel over the draws' final label maps while they are on the device (nbc_dropout_votes, nbc_vote_summary;
+        the definition: include/nbc.h).  Returns ``(counts int64 [D,N,3], vote_labels uint8 [N,H,W], support
+        uint8 [N,H,W], stats int64 [N,10])`` (+ ``lowres`` with ``return_lowres``): the class most draws give a pixel (a tie
+        goes to the lowest class), ``floor(255 * n_win / D)`` (255 = every draw agrees, never below 85), and per image the
+        pixels per winning class (0..2), the unanimous pixels per class (3..5), the sum of n_win (6), invalid words (7, always
+        0 here) and the sums of the bark and node votes (8, 9: the draws' counts summed).  ``return_words`` appends the vote
+        words themselves, ``[N,H,W]`` int32 holding the uint32 bits: n1 in the low half, n2 in the high half."""
+        return self._dropout_run("dropout_votes", True, draws, image_ids, p, seed, first_draw, small_zones, exclude_nodes,
+                                 return_lowres, min_pixels, draws_per_pass, return_words)
+
+    def _dropout_run(self, what, votes, draws, image_ids, p, seed, first_draw, small_zones, exclude_nodes, return_lowres,
+                     min_pixels, draws_per_pass, return_words=False):
+        """The checks and the call behind ``dropout_draws`` and ``dropout_votes``."""
         if topology.is_efficientnet(self.ARCH):
             raise ValueError("dropout draws are refused for %s: EfficientNet's FCN head is left out (its Dropout is not "
                              "implemented)" % self.ARCH)
@@ -462,7 +482,7 @@ class FCNResNet50:
             raise ValueError("min_pixels must not be negative and draws_per_pass must be positive")
         self._require_weights()
         if self._last_shape is None:
-            raise RuntimeError("dropout_draws follows a forward (predict_labels / lowres_logits) of this object: none has run")
+            raise RuntimeError("%s follows a forward (predict_labels / lowres_logits) of this object: none has run" % what)
         n, h, w = self._last_shape
         ids = [int(v) for v in image_ids]
         if len(ids) != n or any(not 0 <= v < 2 ** 64 for v in ids):
@@ -472,20 +492,36 @@ class FCNResNet50:
         per_pass = max(1, min(draws, int(draws_per_pass), 65535 // n))
         need = int(self._lib.nbc_dropout_workspace_bytes(n, h, w, per_pass))
         if need == 0:
-            raise ValueError("nbc_dropout_draws refuses a [%d,3,%d,%d] batch (draws x N <= 65535 per pass, H * W < 2^31)" % (n, h, w))
+            raise ValueError("nbc_%s refuses a [%d,3,%d,%d] batch (draws x N <= 65535 per pass, H * W < 2^31)" % (what, n, h, w))
         counts = torch.empty((draws, n, NUM_CLASSES), dtype=torch.int64, device=self.device)
         lowres = None
         if return_lowres:
             lowres = torch.empty((draws, n, NUM_CLASSES) + out_hw(h, w, self.ARCH), dtype=torch.float32, device=self.device)
+        min_px = int(min_pixels) if small_zones else 0
+        low_ptr = lowres.data_ptr() if lowres is not None else None
+        if not votes:
+            with self._on_stream() as cur:
+                ws = self._grown_workspace("_dropout_ws", need, cur)
+                # the workspace handed over is exactly what per_pass draws need: a larger cached one must not change the pass
+                rc = self._lib.nbc_dropout_draws(self._ctx, n, h, w, ids_arr, float(p), seed, first_draw, draws, min_px,
+                                                 int(bool(exclude_nodes)), low_ptr, counts.data_ptr(), ws.data_ptr(), need,
+                                                 cur.cuda_stream)
+            _lib.check(rc, "nbc_dropout_draws")
+            return (counts, lowres) if return_lowres else counts
+        words = torch.empty((n, h, w), dtype=torch.int32, device=self.device)       # uint32 vote words (torch has no such dtype)
+        vote_labels = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        support = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        stats = torch.empty((n, _lib.VOTE_STATS), dtype=torch.int64, device=self.device)
         with self._on_stream() as cur:
             ws = self._grown_workspace("_dropout_ws", need, cur)
-            # the workspace handed over is exactly what per_pass draws need: a larger cached one must not change the pass
-            rc = self._lib.nbc_dropout_draws(self._ctx, n, h, w, ids_arr, float(p), seed, first_draw, draws,
-                                             int(min_pixels) if small_zones else 0, int(bool(exclude_nodes)),
-                                             lowres.data_ptr() if lowres is not None else None, counts.data_ptr(),
+            rc = self._lib.nbc_dropout_votes(self._ctx, n, h, w, ids_arr, float(p), seed, first_draw, draws, min_px,
+                                             int(bool(exclude_nodes)), low_ptr, counts.data_ptr(), words.data_ptr(), 0,
                                              ws.data_ptr(), need, cur.cuda_stream)
-        _lib.check(rc, "nbc_dropout_draws")
-        return (counts, lowres) if return_lowres else counts
+            _lib.check(rc, "nbc_dropout_votes")
+            _lib.check(self._lib.nbc_vote_summary(words.data_ptr(), n, h, w, draws, vote_labels.data_ptr(), support.data_ptr(),
+                                                  stats.data_ptr(), cur.cuda_stream), "nbc_vote_summary")
+        out = (counts, vote_labels, support, stats)
+        return out + ((lowres,) if return_lowres else ()) + ((words,) if return_words else ())
 
     def resize_cubic_u8(self, image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """The resize of the reference's preprocessor (models.py:191-198) on the device: uint8 RGB

@@ -45,14 +45,14 @@ CSV_HEADER = ["Name", "Type", "Image Size", "Output Bark %", "Bark area (mm^2)",
 ROW_WIDTH = 5                                                              # (global_idx, H, W, count_1, count_2)
 
 
-def generate_folders(root: str, only_preprocess: bool = False) -> None:
-    """predict.py:10-48."""
+def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False) -> None:
+    """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well."""
     present = os.listdir(os.path.join(root, "samples"))
     wood_types = [w for w in WOOD_TYPES if w in present]
     for w in wood_types:
         os.makedirs(os.path.join(root, "processed", "samples", w), exist_ok=True)
     if not only_preprocess:
-        for level in ("combined_images", "outputs"):
+        for level in ("combined_images", "outputs") + (("dropout_votes", "dropout_support") if votes else ()):
             for w in wood_types:
                 os.makedirs(os.path.join(root, "results", level, w), exist_ok=True)
 
@@ -308,9 +308,11 @@ def write_stats_csv(path: str, rows: Sequence[Sequence[str]]) -> None:
 
 
 def write_dropout_report(results_dir: str, items, allrows, alld, draws: int, p: float, seed: int, precision: str, bn_stats: str,
-                         old_stats=None, compare_path: str = None) -> dict:
+                         old_stats=None, compare_path: str = None, allv=None) -> dict:
     """``dropout_stats.csv`` (tab separated) and ``dropout_summary.json`` from the gathered rows: ``allrows`` as
-    ``final_stats.csv`` is written from, ``alld`` the ``(global_idx, D x 3 counts)`` rows of the draws.  Returns the summary."""
+    ``final_stats.csv`` is written from, ``alld`` the ``(global_idx, D x 3 counts)`` rows of the draws.  ``allv``
+    (``--dropout_votes``): the ``(global_idx, 10 stats, changed)`` rows of the votes, which make ``dropout_votes.csv``
+    (``folder_run.vote_report``) and the summary's ``"votes"`` entry.  Returns the summary."""
     import json
     by_idx = {int(g[0]): g[1:].reshape(draws, 3) for g in alld}
     images = [(items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), int(g[3]), int(g[4]), by_idx[int(g[0])])
@@ -321,6 +323,14 @@ def write_dropout_report(results_dir: str, items, allrows, alld, draws: int, p: 
     summary = dict({"p": float(p), "seed": int(seed), "precision": precision, "bn_stats": bn_stats}, **summary)
     if compare_path is not None:
         summary["compare"]["file"] = os.path.basename(compare_path)
+    if allv is not None:
+        by_idx = {int(g[0]): g[1:] for g in allv}
+        vimages = [(items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]),
+                    by_idx[int(g[0])][:folder_run.VOTE_STATS], int(by_idx[int(g[0])][folder_run.VOTE_STATS])) for g in allrows]
+        vtable, vsummary = folder_run.vote_report(vimages, draws)
+        with open(os.path.join(results_dir, "dropout_votes.csv"), "w") as f:
+            csv.writer(f, delimiter="\t").writerows(vtable)
+        summary["votes"] = vsummary["means"]
     with open(os.path.join(results_dir, "dropout_summary.json"), "w") as f:
         json.dump(summary, f, indent=2, sort_keys=True)
         f.write("\n")
@@ -361,7 +371,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
-                   dropout_compare: str = None) -> dict:
+                   dropout_compare: str = None, dropout_votes: bool = False) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -391,6 +401,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     the labels and rank 0 writes ``results/dropout_stats.csv`` and ``results/dropout_summary.json``
     (``folder_run.dropout_report``; ``dropout_compare``: a ``final_stats.csv`` of the shipped tool to place within the draws).
     Everything else the run writes is byte for byte what it writes without the draws.
+    ``dropout_votes`` (with ``dropout_draws`` only): the draws run through ``FCNResNet50.dropout_votes``, whose per-pixel
+    majority mask and support byte ride back beside the labels: ``results/dropout_votes/<wood>/<name>`` (the mask, written as
+    the label PNGs are), ``results/dropout_support/<wood>/<name>`` (grey, 255 = every draw agrees),
+    ``results/dropout_votes.csv`` (``folder_run.vote_report``, with the pixels on which the mask differs from the label PNG)
+    and a ``"votes"`` entry in ``dropout_summary.json``; every other file stays byte for byte what it is without the flag.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -398,7 +413,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     from .model import FCNResNet50
     from .pngio import write_png
     D = int(dropout_draws or 0)
+    V = bool(dropout_votes)
     old_stats = None
+    if V and not D:
+        raise ValueError("--dropout_votes needs --dropout_draws")
     if D:                                            # refusals first: nothing has touched a device yet
         folder_run.check_dropout_arguments(D, dropout_p, dropout_seed, dropout_compare, arch)
         if dropout_compare is not None:
@@ -410,7 +428,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel)
         if small_zones:
             m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
-    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, generate_folders, warm, normalization=normalization)
+    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, lambda root_: generate_folders(root_, votes=V), warm,
+                        normalization=normalization)
     if D:
         folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
 
@@ -424,6 +443,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     mine, pool = r.mine, r.pool
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
     drows = np.zeros((len(mine), 1 + 3 * D), dtype=np.int64)     # (global_idx, D x 3 counts) of the Dropout draws
+    VROW = 2 + folder_run.VOTE_STATS
+    vrows = np.zeros((len(mine), VROW), dtype=np.int64)          # (global_idx, 10 vote statistics, changed pixels)
     resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
     lvl_proc, lvl_lab = _png_level("processed"), _png_level("labels")
 
@@ -451,8 +472,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2, draws=None):
-        """Pool: label PNG (models.py:349-356) + the image's row."""
+    def finish(k, lab, c1, c2, draws=None, votes=None):
+        """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row)."""
         d = items[mine[k]]
         t0 = clock()
         path = os.path.join(root, "results", "outputs", d["wood"], d["name"])
@@ -461,6 +482,13 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         rows[k] = (mine[k], lab.shape[0], lab.shape[1], c1, c2)
         if draws is not None:
             drows[k, 0], drows[k, 1:] = mine[k], draws.reshape(-1)
+        if votes is not None:
+            vlab, sup, vstats = votes
+            for level, img in (("dropout_votes", label_png(vlab)), ("dropout_support", sup)):
+                vpath = os.path.join(root, "results", level, d["wood"], d["name"])
+                label_paths.append(vpath)
+                write_png(vpath, img, lvl_lab)
+            vrows[k, 0], vrows[k, 1:-1], vrows[k, -1] = mine[k], vstats, int(np.count_nonzero(vlab != lab))
         prof["pool.write_labels"] += clock() - t0
 
     # the result ring, one slot per staging slot: labels + counts coming back (pinned once for the largest batch)
@@ -468,6 +496,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     ring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, 3), dtype=torch.int64).pin_memory())
             for _ in range(r.depth)]
     dring = [torch.empty(D * batch * 3, dtype=torch.int64).pin_memory() for _ in range(r.depth)] if D else None
+    # the votes' slots: the mask and the support plane, one after the other, and the ten statistics per image
+    vring = [(torch.empty(2 * full, dtype=torch.uint8).pin_memory(),
+              torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory()) for _ in range(r.depth)] if V else None
     tuned = set()
 
     def launch(slot, sid, part, x):
@@ -486,8 +517,18 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             if dring[slot].numel() < D * n * 3:
                 dring[slot] = torch.empty(D * n * 3, dtype=torch.int64).pin_memory()
             ids = [folder_run.image_id(items[mine[k]]["wood"], items[mine[k]]["name"]) for k in part]
-            dcounts = mdl.dropout_draws(D, ids, p=dropout_p, seed=dropout_seed, small_zones=small_zones,
-                                        exclude_nodes=exclude_nodes)
+            if V:
+                if vring[slot][0].numel() < 2 * need or vring[slot][1].shape[0] < n:
+                    vring[slot] = (torch.empty(2 * need, dtype=torch.uint8).pin_memory(),
+                                   torch.empty((n, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory())
+                dcounts, vlab, sup, vstats = mdl.dropout_votes(D, ids, p=dropout_p, seed=dropout_seed, small_zones=small_zones,
+                                                               exclude_nodes=exclude_nodes)
+                vring[slot][0][:need].copy_(vlab.reshape(-1), non_blocking=True)
+                vring[slot][0][need: 2 * need].copy_(sup.reshape(-1), non_blocking=True)
+                vring[slot][1][:n].copy_(vstats, non_blocking=True)
+            else:
+                dcounts = mdl.dropout_draws(D, ids, p=dropout_p, seed=dropout_seed, small_zones=small_zones,
+                                            exclude_nodes=exclude_nodes)
             dring[slot][: D * n * 3].copy_(dcounts.reshape(-1), non_blocking=True)
 
     def consume(slot, part, n, h, w):
@@ -496,6 +537,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         cnts = cnt_host[:n].numpy().copy()
         if D:
             dc = dring[slot][: D * n * 3].numpy().reshape(D, n, 3).copy()
+            if V:
+                planes = vring[slot][0][: 2 * n * h * w].numpy().reshape(2, n, h, w).copy()
+                vst = vring[slot][1][:n].numpy().copy()
+                return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j], (planes[0, j], planes[1, j], vst[j]))
+                        for j, k in enumerate(part)]
             return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j]) for j, k in enumerate(part)]
         return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2])) for j, k in enumerate(part)]
 
@@ -518,9 +564,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                          for g in allrows])
     if D:
         alld = folder_run.gather(r, drows, 1 + 3 * D)       # one more all_gather, as evaluate's --loss rows take
+        allv = folder_run.gather(r, vrows, VROW) if V else None
         if r.rank == 0:
             write_dropout_report(os.path.join(root, "results"), items, allrows, alld, D, dropout_p, dropout_seed, r.precision,
-                                 bn_stats, old_stats, dropout_compare)
+                                 bn_stats, old_stats, dropout_compare, allv)
     return dict(folder_run.finish(r), host_workers=r.workers, distinct_shapes=len(r.shape_count),
                 autotuned_shapes=len({k for _, k in tuned}))
 
@@ -542,7 +589,7 @@ def main(argv=None):
     folder_run.resolve_arguments(ap, args)
     try:                                                 # refused as argument errors, before any device is touched
         folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
-                                           args.only_preprocess)
+                                           args.only_preprocess, args.dropout_votes)
         if args.dropout_compare is not None:
             folder_run.read_shipped_stats(args.dropout_compare)
     except ValueError as e:
@@ -562,7 +609,7 @@ def main(argv=None):
     kw = dict(batch=args.batch, autotune=args.autotune, streams=args.streams, arch=args.arch, bn_stats=args.bn_stats)
     if args.dropout_draws:
         kw.update(dropout_draws=args.dropout_draws, dropout_p=0.1 if args.dropout_p is None else args.dropout_p,
-                  dropout_seed=args.dropout_seed or 0, dropout_compare=args.dropout_compare)
+                  dropout_seed=args.dropout_seed or 0, dropout_compare=args.dropout_compare, dropout_votes=args.dropout_votes)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if int(os.environ.get("RANK", "0")) == 0:
