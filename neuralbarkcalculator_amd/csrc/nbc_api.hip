@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/nbc.h"
+#include "device_mem.hpp"
 #include "nbc_internal.hpp"
 #include "nbc_kernels.hpp"
 #include "nbc_net.hpp"
@@ -30,21 +31,40 @@ using namespace nbc;
       return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
+// The memory policy of the context's owners (device_mem.hpp), and an event owned the same way.
+struct HipMem {
+  using Error = hipError_t;
+  static constexpr Error ok() { return hipSuccess; }
+  static Error allocate(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void release(void* p) { (void)hipFree(p); }          // synchronises: nothing of the block is in flight afterwards
+  static void forget_error() { (void)hipGetLastError(); }
+  static Error copy_in(void* dst, const void* host, size_t bytes) { return hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice); }
+};
+using DeviceBuffer = Buffer<HipMem>;
+template <class T> using DeviceArray = Array<T, HipMem>;
+
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : ev(std::exchange(o.ev, nullptr)) {}
+  ~Event() { if (ev) (void)hipEventDestroy(ev); }
+  hipError_t create() { return hipEventCreate(&ev); }
+  operator hipEvent_t() const { return ev; }
+};
+
+// Everything the context holds on the device is a member that releases itself: nbc_destroy deletes the context.
 struct nbc_ctx {
   int device = 0;
   int precision = -1;
   int arch = kArchFcn;                      // NBC_ARCH_* of the attached blob
-  const unsigned char* weights = nullptr;   // device blob
-  void* owned_weights = nullptr;
+  DeviceArray<unsigned char> weights;       // device blob: the caller's (nbc_attach_weights) or one loaded / received here
   PackedLayout layout;
   float mean[3] = {0.7399f, 0.6139f, 0.4401f};   // models.py:208
   float stdv[3] = {0.1068f, 0.1272f, 0.1271f};   // models.py:209
   Plan plan;                                // plan of the current (N,H,W)
   std::vector<Plan> plan_cache;             // plans (with their tuned tiles) of the other shapes seen, oldest first
-  std::vector<void*> bufs;
-  std::vector<size_t> buf_cap;
-  float* lowres = nullptr;
-  size_t lowres_cap = 0;
+  std::vector<DeviceBuffer> bufs;           // the plan's activation buffers: they only ever grow
+  DeviceBuffer lowres;
   int conv_tile = -1;                       // tile override, -1 = per-layer choice
   bool fuse_downsample = true;              // nbc_set_fuse_downsample
   int fused_pairs = 0;                      // (downsample.0, conv3) pairs the last forward ran as one launch
@@ -52,29 +72,23 @@ struct nbc_ctx {
   bool profiling = false;
   // profiling: one event set (nops+1 events) per profiled forward, read back lazily so that the
   // timed loop never synchronises; nbc_num_op_records() averages over the sets and resets.
-  std::vector<std::vector<hipEvent_t>> prof_sets;
+  std::vector<std::vector<Event>> prof_sets;
   size_t prof_used = 0;
   std::vector<Op> prof_ops;
   int prof_arch = kArchFcn;                 // architecture of prof_ops
   std::vector<nbc_op_record> records;
   std::map<std::string, int> act_of;        // conv unit name -> op index (keep mode)
-  void* scratch256 = nullptr;               // 256 bytes of device scratch (min/max of the preprocessor resize)
+  DeviceBuffer scratch256;                  // 256 bytes of device scratch (min/max of the preprocessor resize)
   int pack_flags = 0;                       // NBC_PACK_* of the attached blob (its trailer)
   std::vector<int> act_exp;                 // per conv unit: power of two its output tensor is stored with (trailer)
-  unsigned* nonfinite = nullptr;            // one device word, sticky: bit 0 = a forward produced a NaN / infinite logit,
+  DeviceBuffer nonfinite;                   // one device word, sticky: bit 0 = a forward produced a NaN / infinite logit,
                                             // NBC_NONFINITE_BN_RANGE = a per-image BatchNorm saw a channel outside the pieces' range
-  void* zones_ws = nullptr;                 // remove_small_zones workspace: bg bytes, parent ints, size ints
-  size_t zones_px = 0;                      // pixels it is sized for
+  DeviceBuffer zones_ws;                    // remove_small_zones workspace: parent ints, size ints, bg bytes
   int bn_mode = NBC_BN_RUNNING;             // NBC_BN_*
-  const float* bn_affine = nullptr;         // device: gamma, beta per BatchNorm unit (nbc_pack_bn_affine)
-  size_t bn_affine_count = 0;
-  void* owned_affine = nullptr;             // the affine array nbc_load_weights uploaded
-  const float* bn_raw = nullptr;            // device, f16x2: 2^(r - k - a_in), 2^-r per BatchNorm unit (nbc_pack_bn_raw)
-  size_t bn_raw_count = 0;
-  void* owned_raw = nullptr;                // the raw array nbc_load_weights uploaded
-  float* bn_unit = nullptr;                 // device: 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
-  void* bn_ws = nullptr;                    // per-image BatchNorm workspace (Plan::bn_ws_bytes)
-  size_t bn_ws_cap = 0;
+  DeviceArray<float> bn_affine;             // gamma, beta per BatchNorm unit (nbc_pack_bn_affine)
+  DeviceArray<float> bn_raw;                // f16x2: 2^(r - k - a_in), 2^-r per BatchNorm unit (nbc_pack_bn_raw)
+  DeviceArray<float> bn_unit;               // 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
+  DeviceBuffer bn_ws;                       // per-image BatchNorm workspace (Plan::bn_ws_bytes)
   // the (N, H, W) of the last completed nbc_forward while its activations and plan stand untouched (nbc_dropout_draws reads
   // the stored input of classifier.4): cleared by whatever parks the plan, retunes it or attaches other weights
   bool fwd_valid = false;
@@ -106,23 +120,10 @@ void stash_plan(nbc_ctx* c) {
   cur = Plan();
 }
 
-// Room for buffer i of the current plan.  Buffers only ever grow; one that has to grow grows by at least half (hipFree
-// synchronises the device: shapes that rise one after the other then reallocate O(log) times, not once per shape).
+// Room for buffer i of the current plan, grown with the margin (Buffer::reserve).
 int ensure_buffer(nbc_ctx* c, int i) {
-  const size_t need = c->plan.buf_bytes[i];
-  if (c->buf_cap[i] >= need) return NBC_OK;
-  const size_t grown = c->buf_cap[i] + c->buf_cap[i] / 2;
-  if (c->bufs[i]) NBC_HIP(hipFree(c->bufs[i]));
-  c->bufs[i] = nullptr; c->buf_cap[i] = 0;
-  size_t want = std::max(need, grown);
-  hipError_t e = hipMalloc(&c->bufs[i], want);
-  if (e != hipSuccess && want > need) {                // no room for the margin: the exact size
-    (void)hipGetLastError();
-    want = need;
-    e = hipMalloc(&c->bufs[i], want);
-  }
+  const hipError_t e = c->bufs[i].reserve(c->plan.buf_bytes[i], Grow::kMargin);
   if (e != hipSuccess) return set_error(NBC_ERR_NOMEM, std::string("hipMalloc(workspace): ") + hipGetErrorString(e));
-  c->buf_cap[i] = want;
   return NBC_OK;
 }
 
@@ -131,33 +132,21 @@ int ensure_buffer(nbc_ctx* c, int i) {
 // identity buffer is left to the first launch that writes it (launch_conv_op): the default path never does.
 int ensure_buffers(nbc_ctx* c) {
   const Plan& P = c->plan;
-  if (c->bufs.size() < P.buf_bytes.size()) { c->bufs.resize(P.buf_bytes.size(), nullptr); c->buf_cap.resize(P.buf_bytes.size(), 0); }
+  if (c->bufs.size() < P.buf_bytes.size()) c->bufs.resize(P.buf_bytes.size());
   for (int i = 0; i < (int)P.buf_bytes.size(); ++i)
     if (i != P.identity_buf) {
       const int rc = ensure_buffer(c, i);
       if (rc != NBC_OK) return rc;
     }
   if (P.bn == NBC_BN_PER_IMAGE) {
-    if (!c->bn_unit) {
+    if (!c->bn_unit.data()) {
       std::vector<float> unit(4096, 0.f);
       std::fill(unit.begin(), unit.begin() + 2048, 1.f);
-      NBC_HIP(hipMalloc((void**)&c->bn_unit, unit.size() * sizeof(float)));
-      NBC_HIP(hipMemcpy(c->bn_unit, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+      NBC_HIP(c->bn_unit.upload(unit.data(), unit.size()));
     }
-    if (c->bn_ws_cap < P.bn_ws_bytes) {
-      if (c->bn_ws) NBC_HIP(hipFree(c->bn_ws));
-      c->bn_ws = nullptr; c->bn_ws_cap = 0;
-      NBC_HIP(hipMalloc(&c->bn_ws, P.bn_ws_bytes));
-      c->bn_ws_cap = P.bn_ws_bytes;
-    }
+    NBC_HIP(c->bn_ws.reserve(P.bn_ws_bytes));
   }
-  const size_t lr = (size_t)P.N * kNumClasses * P.h * P.w * sizeof(float);
-  if (c->lowres_cap < lr) {
-    if (c->lowres) NBC_HIP(hipFree(c->lowres));
-    c->lowres = nullptr; c->lowres_cap = 0;
-    NBC_HIP(hipMalloc((void**)&c->lowres, lr));
-    c->lowres_cap = lr;
-  }
+  NBC_HIP(c->lowres.reserve((size_t)P.N * kNumClasses * P.h * P.w * sizeof(float)));
   c->act_of.clear();
   for (size_t i = 0; i < P.ops.size(); ++i) c->act_of[P.ops[i].name] = (int)i;
   return NBC_OK;
@@ -171,8 +160,9 @@ struct UnitPtrs {
 };
 UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
   const PackedConv& pc = c->layout.convs[unit];
-  return {reinterpret_cast<const float*>(c->weights + pc.w_off), reinterpret_cast<const float*>(c->weights + pc.scale_off),
-          reinterpret_cast<const float*>(c->weights + pc.shift_off)};
+  return {reinterpret_cast<const float*>(c->weights.data() + pc.w_off),
+          reinterpret_cast<const float*>(c->weights.data() + pc.scale_off),
+          reinterpret_cast<const float*>(c->weights.data() + pc.shift_off)};
 }
 
 // Checks a conv op's operand set against its packed unit and sizes it for the buffer resources (activations and weights stay
@@ -200,24 +190,24 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
   const int prec = c->precision;
   const size_t eb = elem_bytes(prec);
   ConvArgs a{};
-  a.x = c->bufs[o.in_buf];
+  a.x = c->bufs[o.in_buf].get();
   a.w = p.w;
   a.scale = p.scale;
   a.shift = p.shift;
-  a.res = o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr;
+  a.res = o.res_buf >= 0 ? c->bufs[o.res_buf].get() : nullptr;
   if (o.raw) {                                         // per-image BatchNorm follows: fma(acc, 1, 0) = acc in f32
     if (o.Co > 2048) return set_error(NBC_ERR_STATE, "raw convolution wider than the unit table at " + o.name);
-    a.scale = c->bn_unit;
-    a.shift = c->bn_unit + 2048;
+    a.scale = c->bn_unit.data();
+    a.shift = c->bn_unit.data() + 2048;
     a.res = nullptr;
     // f16x2: the channel's power of two 2^(r - k - a_in) (nbc_pack_bn_raw), so that the pieces hold 2^r conv: exact in the fma
-    if (prec == NBC_PREC_F16X2) a.scale = c->bn_raw + o.affine_off;
+    if (prec == NBC_PREC_F16X2) a.scale = c->bn_raw.data() + o.affine_off;
   }
   if (o.out_buf == c->plan.identity_buf) {
     const int rc = ensure_buffer(c, o.out_buf);
     if (rc != NBC_OK) return rc;
   }
-  a.y = c->bufs[o.out_buf];
+  a.y = c->bufs[o.out_buf].get();
   a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.Ci = o.Ci;
   a.Ho = o.Ho; a.Wo = o.Wo; a.Co = o.Co;
   a.KH = u.k; a.KW = u.k; a.stride = u.stride; a.pad = u.pad; a.dil = u.dil;
@@ -238,7 +228,7 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     const UnitPtrs p2 = unit_ptrs(c, ds->unit);
     if (const int rc = conv_operand_bytes(*ds, pc2, N, eb, &a.x2_bytes, &a.w2_bytes); rc != NBC_OK) return rc;
     a.res = nullptr;
-    a.x2 = c->bufs[ds->in_buf];
+    a.x2 = c->bufs[ds->in_buf].get();
     a.w2 = p2.w;
     a.scale2 = p2.scale;
     a.shift2 = p2.shift;
@@ -250,10 +240,10 @@ int launch_conv_op(nbc_ctx* c, const Op& o, int N, int tile, hipStream_t s, hipE
     a.M = o.Ho * o.Wo;
     a.x_bytes = (unsigned)xi;
     for (int n = 0; n < N; ++n) {
-      a.x = static_cast<const unsigned char*>(c->bufs[o.in_buf]) + n * xi;
-      a.w = static_cast<const unsigned char*>(c->bufs[o.gate_buf]) + n * (size_t)a.w_bytes;
-      a.res = o.res_buf >= 0 ? static_cast<const unsigned char*>(c->bufs[o.res_buf]) + n * yi : nullptr;
-      a.y = static_cast<unsigned char*>(c->bufs[o.out_buf]) + n * yi;
+      a.x = static_cast<const unsigned char*>(c->bufs[o.in_buf].get()) + n * xi;
+      a.w = static_cast<const unsigned char*>(c->bufs[o.gate_buf].get()) + n * (size_t)a.w_bytes;
+      a.res = o.res_buf >= 0 ? static_cast<const unsigned char*>(c->bufs[o.res_buf].get()) + n * yi : nullptr;
+      a.y = static_cast<unsigned char*>(c->bufs[o.out_buf].get()) + n * yi;
       *err = launch_conv_dma(a, prec, tile, s);
       if (*err != hipSuccess) break;
     }
@@ -319,22 +309,17 @@ int nbc_create(nbc_ctx** out, int hip_device) {
 int nbc_destroy(nbc_ctx* c) {
   if (!c) return NBC_OK;
   (void)hipSetDevice(c->device);
-  for (void* b : c->bufs) if (b) (void)hipFree(b);
-  if (c->lowres) (void)hipFree(c->lowres);
-  if (c->zones_ws) (void)hipFree(c->zones_ws);
-  if (c->scratch256) (void)hipFree(c->scratch256);
-  if (c->nonfinite) (void)hipFree(c->nonfinite);
-  if (c->owned_weights) (void)hipFree(c->owned_weights);
-  if (c->owned_affine) (void)hipFree(c->owned_affine);
-  if (c->owned_raw) (void)hipFree(c->owned_raw);
-  if (c->bn_unit) (void)hipFree(c->bn_unit);
-  if (c->bn_ws) (void)hipFree(c->bn_ws);
-  for (auto& set : c->prof_sets) for (hipEvent_t ev : set) (void)hipEventDestroy(ev);
   delete c;
   return NBC_OK;
 }
 
-int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision, int arch) {
+}  // extern "C"
+
+namespace {
+
+// nbc_attach_weights_arch.  `owned`: the block dev_blob lies in, which the context takes over once every check has passed
+// (nbc_load_weights, the receiving nbc_bcast_weights), or nullptr for the caller's memory.  A refusal changes nothing.
+int attach_weights(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision, int arch, DeviceBuffer* owned) {
   if (!c || !dev_blob) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: null argument");
   if (!known_precision(precision)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown precision");
   if (!known_arch(arch)) return set_error(NBC_ERR_INVALID, "nbc_attach_weights: unknown architecture");
@@ -352,13 +337,13 @@ int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int 
   if (meta[0] != kMetaMagic || meta[2] != nunits || meta[kMetaArch] != arch)
     return set_error(NBC_ERR_INVALID, "nbc_attach_weights: not a blob of this library's nbc_pack_weights for this architecture "
                                       "(trailer mismatch)");
-  if (c->owned_weights && c->owned_weights != dev_blob) { (void)hipFree(c->owned_weights); c->owned_weights = nullptr; }
+  if (owned) c->weights.adopt(std::move(*owned), bytes);
+  else c->weights.attach(static_cast<const unsigned char*>(dev_blob), bytes);
   c->pack_flags = meta[1];
   const int nexp = std::min(nunits, kMetaWords - kMetaExpBase);         // EfficientNet's trailer holds no exponents (f32)
   c->act_exp.assign(meta + kMetaExpBase, meta + kMetaExpBase + nexp);
   c->act_exp.resize(nunits, 0);
   if (is_effnet(arch)) std::fill(c->act_exp.begin(), c->act_exp.end(), 0);
-  c->weights = static_cast<const unsigned char*>(dev_blob);
   c->layout = L;
   c->fwd_valid = false;
   if (c->precision != precision || c->arch != arch) stash_plan(c);      // element size or network changed: another plan
@@ -367,10 +352,33 @@ int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int 
   return NBC_OK;
 }
 
+// nbc_attach_bn_affine / nbc_attach_bn_raw: `what` names the array in the messages, `floats_of` is its
+// nbc_arch_<what>_floats (0 for an architecture that has no such array).
+int attach_bn_array(nbc_ctx* c, const std::string& what, size_t (*floats_of)(int), DeviceArray<float> nbc_ctx::*array,
+                    const float* dev, size_t count) {
+  if (!c || !dev) return set_error(NBC_ERR_INVALID, "nbc_attach_" + what + ": null argument");
+  bool any = false;
+  for (int a = 0; a < kArchDeepLabEffB0 + 8; ++a) any = any || (count > 0 && count == floats_of(a));
+  if (!any)
+    return set_error(NBC_ERR_INVALID, "nbc_attach_" + what + ": count is nbc_arch_" + what + "_floats of no architecture");
+  NBC_HIP(hipSetDevice(c->device));
+  (c->*array).attach(dev, count);                      // releasing an array owned before synchronises: nothing of it is in flight
+  return NBC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbc_attach_weights_arch(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision, int arch) {
+  return attach_weights(c, dev_blob, bytes, precision, arch, nullptr);
+}
+
 int nbc_attach_weights(nbc_ctx* c, const void* dev_blob, size_t bytes, int precision) {
   return nbc_attach_weights_arch(c, dev_blob, bytes, precision, kArchFcn);
 }
 
+// Packs and uploads everything first, attaches afterwards: a refusal at any step leaves the context as it was.
 int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int precision, int arch) {
   if (!c) return set_error(NBC_ERR_INVALID, "nbc_load_weights: null context");
   const size_t bytes = nbc_arch_packed_weights_bytes(precision, arch);
@@ -378,75 +386,37 @@ int nbc_load_weights_arch(nbc_ctx* c, const nbc_tensor* tensors, int n, int prec
   std::vector<unsigned char> host(bytes);
   int rc = nbc_pack_weights_arch(tensors, n, precision, arch, host.data(), bytes);
   if (rc != NBC_OK) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  void* dev = nullptr;
-  NBC_HIP(hipMalloc(&dev, bytes));
-  hipError_t e = hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(dev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(weights): ") + hipGetErrorString(e)); }
-  if (c->owned_weights) (void)hipFree(c->owned_weights);
-  c->owned_weights = nullptr;
-  rc = nbc_attach_weights_arch(c, dev, bytes, precision, arch);
-  if (rc != NBC_OK) { (void)hipFree(dev); return rc; }
-  c->owned_weights = dev;
   // the per-image BatchNorm affine array of the same tensors (already checked by the pack above)
   std::vector<float> affine(nbc_arch_bn_affine_floats(arch));
   rc = nbc_pack_bn_affine(tensors, n, arch, affine.data(), affine.size());
   if (rc != NBC_OK) return rc;
-  void* adev = nullptr;
-  NBC_HIP(hipMalloc(&adev, affine.size() * sizeof(float)));
-  e = hipMemcpy(adev, affine.data(), affine.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(adev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn affine): ") + hipGetErrorString(e)); }
-  if (c->owned_affine) (void)hipFree(c->owned_affine);
-  c->owned_affine = adev;
-  c->bn_affine = static_cast<const float*>(adev);
-  c->bn_affine_count = affine.size();
-  if (precision == NBC_PREC_F16X2 && !is_effnet(arch)) {   // and the raw convolutions' powers of two (NBC_BN_PER_IMAGE on pieces)
-    std::vector<float> raw(nbc_arch_bn_raw_floats(arch));
-    rc = nbc_pack_bn_raw(tensors, n, arch, raw.data(), raw.size());
-    if (rc < 0) return rc;
-    c->pack_flags |= rc;
-    void* rdev = nullptr;
-    NBC_HIP(hipMalloc(&rdev, raw.size() * sizeof(float)));
-    e = hipMemcpy(rdev, raw.data(), raw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(rdev); return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn raw): ") + hipGetErrorString(e)); }
-    if (c->owned_raw) (void)hipFree(c->owned_raw);
-    c->owned_raw = rdev;
-    c->bn_raw = static_cast<const float*>(rdev);
-    c->bn_raw_count = raw.size();
-  }
+  // and, f16x2, the raw convolutions' powers of two (NBC_BN_PER_IMAGE on pieces) with their NBC_PACK_* bits
+  std::vector<float> raw(precision == NBC_PREC_F16X2 && !is_effnet(arch) ? nbc_arch_bn_raw_floats(arch) : 0);
+  const int raw_flags = raw.empty() ? 0 : nbc_pack_bn_raw(tensors, n, arch, raw.data(), raw.size());
+  if (raw_flags < 0) return raw_flags;
+  NBC_HIP(hipSetDevice(c->device));
+  DeviceBuffer blob;
+  DeviceArray<float> affine_dev, raw_dev;
+  hipError_t e = blob.reserve(bytes);
+  if (e == hipSuccess) e = HipMem::copy_in(blob.get(), host.data(), bytes);
+  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("hipMemcpy(weights): ") + hipGetErrorString(e));
+  e = affine_dev.upload(affine.data(), affine.size());
+  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn affine): ") + hipGetErrorString(e));
+  if (!raw.empty()) e = raw_dev.upload(raw.data(), raw.size());
+  if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("hipMemcpy(bn raw): ") + hipGetErrorString(e));
+  rc = attach_weights(c, blob.get(), bytes, precision, arch, &blob);
+  if (rc != NBC_OK) return rc;
+  c->bn_affine = std::move(affine_dev);                // nothing below can fail; each old block is released as it is replaced
+  if (!raw.empty()) { c->bn_raw = std::move(raw_dev); c->pack_flags |= raw_flags; }
   return NBC_OK;
 }
 
 int nbc_attach_bn_affine(nbc_ctx* c, const float* dev_affine, size_t count) {
-  if (!c || !dev_affine) return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: null argument");
-  bool any = false;
-  for (int a = 0; a < kArchDeepLabEffB0 + 8; ++a) any = any || (known_arch(a) && count == nbc_arch_bn_affine_floats(a));
-  if (!any)
-    return set_error(NBC_ERR_INVALID, "nbc_attach_bn_affine: count is nbc_arch_bn_affine_floats of no architecture");
-  if (c->owned_affine && c->owned_affine != dev_affine) {
-    NBC_HIP(hipSetDevice(c->device));
-    (void)hipFree(c->owned_affine);                    // synchronises: nothing of the old array is in flight
-    c->owned_affine = nullptr;
-  }
-  c->bn_affine = dev_affine;
-  c->bn_affine_count = count;
-  return NBC_OK;
+  return attach_bn_array(c, "bn_affine", nbc_arch_bn_affine_floats, &nbc_ctx::bn_affine, dev_affine, count);
 }
 
 int nbc_attach_bn_raw(nbc_ctx* c, const float* dev_raw, size_t count) {
-  if (!c || !dev_raw) return set_error(NBC_ERR_INVALID, "nbc_attach_bn_raw: null argument");
-  bool any = false;
-  for (int a = 0; a < kNumArchs; ++a) any = any || (count > 0 && count == nbc_arch_bn_raw_floats(a));
-  if (!any)
-    return set_error(NBC_ERR_INVALID, "nbc_attach_bn_raw: count is nbc_arch_bn_raw_floats of no architecture");
-  if (c->owned_raw && c->owned_raw != dev_raw) {
-    NBC_HIP(hipSetDevice(c->device));
-    (void)hipFree(c->owned_raw);                       // synchronises: nothing of the old array is in flight
-    c->owned_raw = nullptr;
-  }
-  c->bn_raw = dev_raw;
-  c->bn_raw_count = count;
-  return NBC_OK;
+  return attach_bn_array(c, "bn_raw", nbc_arch_bn_raw_floats, &nbc_ctx::bn_raw, dev_raw, count);
 }
 
 int nbc_set_bn_statistics(nbc_ctx* c, int mode) {
@@ -495,34 +465,25 @@ int nbc_bcast_weights(nbc_ctx* c, void* rccl_comm, int root, int precision, void
   if (user_rank(rccl_comm, &rank) != 0) return set_error(NBC_ERR_INVALID, "nbc_bcast_weights: ncclCommUserRank failed (bad communicator?)");
   NBC_HIP(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  DeviceBuffer received;                               // a receiving rank's blob: the context's once the attach has taken it
   void* blob = nullptr;
-  bool fresh = false;
   if (rank == root) {
-    if (!c->weights || c->precision != precision)
+    if (!c->weights.data() || c->precision != precision)
       return set_error(NBC_ERR_STATE, "nbc_bcast_weights: the root rank has no weights of this precision attached");
-    blob = const_cast<unsigned char*>(c->weights);
+    blob = const_cast<unsigned char*>(c->weights.data());
   } else {
-    NBC_HIP(hipMalloc(&blob, bytes));
-    fresh = true;
+    NBC_HIP(received.reserve(bytes));
+    blob = received.get();
   }
   const int rc = bcast(blob, blob, bytes, /*ncclUint8*/ 1, root, rccl_comm, s);
-  if (rc != 0) {
-    if (fresh) (void)hipFree(blob);
-    return set_error(NBC_ERR_HIP, "nbc_bcast_weights: ncclBroadcast returned " + std::to_string(rc));
-  }
-  if (fresh) {
-    if (c->owned_weights) (void)hipFree(c->owned_weights);     // synchronises: nothing of the old blob is in flight
-    c->owned_weights = nullptr;
-    const int arc = nbc_attach_weights(c, blob, bytes, precision);
-    if (arc != NBC_OK) { (void)hipFree(blob); return arc; }
-    c->owned_weights = blob;
-  }
-  return NBC_OK;
+  if (rc != 0) return set_error(NBC_ERR_HIP, "nbc_bcast_weights: ncclBroadcast returned " + std::to_string(rc));
+  // the blob held before is released by the attach (which synchronises: nothing of it is in flight), and only once it accepts
+  return rank == root ? NBC_OK : attach_weights(c, blob, bytes, precision, kArchFcn, &received);
 }
 
 int nbc_weights_flags(nbc_ctx* c) {
   if (!c) return set_error(NBC_ERR_INVALID, "null context");
-  if (!c->weights) return set_error(NBC_ERR_STATE, "nbc_weights_flags: no weights attached");
+  if (!c->weights.data()) return set_error(NBC_ERR_STATE, "nbc_weights_flags: no weights attached");
   return c->pack_flags;
 }
 
@@ -544,7 +505,7 @@ bool stored_exponent(const nbc_ctx* c, const std::string& name, int* e) {
 
 int nbc_activation_exponent(nbc_ctx* c, const char* name, int32_t* exponent) {
   if (!c || !name || !exponent) return set_error(NBC_ERR_INVALID, "nbc_activation_exponent: null argument");
-  if (!c->weights) return set_error(NBC_ERR_STATE, "nbc_activation_exponent: no weights attached");
+  if (!c->weights.data()) return set_error(NBC_ERR_STATE, "nbc_activation_exponent: no weights attached");
   int e = 0;
   if (!stored_exponent(c, name, &e)) return set_error(NBC_ERR_INVALID, std::string("nbc_activation_exponent: unknown op ") + name);
   *exponent = e;
@@ -588,8 +549,8 @@ int nbc_nonfinite_seen(nbc_ctx* c, int reset) {
   NBC_HIP(hipSetDevice(c->device));
   unsigned v = 0;
   NBC_HIP(hipDeviceSynchronize());                   // every forward on every stream (non-blocking ones too) has finished
-  NBC_HIP(hipMemcpy(&v, c->nonfinite, sizeof(v), hipMemcpyDeviceToHost));
-  if (reset && v) NBC_HIP(hipMemset(c->nonfinite, 0, sizeof(v)));
+  NBC_HIP(hipMemcpy(&v, c->nonfinite.get(), sizeof(v), hipMemcpyDeviceToHost));
+  if (reset && v) NBC_HIP(hipMemset(c->nonfinite.get(), 0, sizeof(v)));
   return v ? 1 : 0;
 }
 
@@ -606,7 +567,7 @@ int nbc_nonfinite_peek_async(nbc_ctx* c, uint32_t* host_dst, void* hip_stream) {
     }
   }
   if (!c->nonfinite) { *host_dst = 0; return NBC_OK; }   // no forward yet
-  NBC_HIP(hipMemcpyAsync(host_dst, c->nonfinite, sizeof(uint32_t), hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
+  NBC_HIP(hipMemcpyAsync(host_dst, c->nonfinite.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
   return NBC_OK;
 }
 
@@ -623,10 +584,10 @@ int nbc_reserve(nbc_ctx* c, int N, int H, int W) {
   if (c->bn_mode == NBC_BN_PER_IMAGE) {
     if (!bn_per_image_ok(c->precision, c->arch))
       return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics need NBC_PREC_FP32 weights of NBC_ARCH_FCN_RESNET50 attached");
-    if (!c->bn_affine || c->bn_affine_count != nbc_arch_bn_affine_floats(c->arch))
+    if (c->bn_affine.count() != nbc_arch_bn_affine_floats(c->arch))
       return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics: no affine array of this architecture attached "
                                       "(nbc_attach_bn_affine)");
-    if (c->precision == NBC_PREC_F16X2 && (!c->bn_raw || c->bn_raw_count != nbc_arch_bn_raw_floats(c->arch)))
+    if (c->precision == NBC_PREC_F16X2 && c->bn_raw.count() != nbc_arch_bn_raw_floats(c->arch))
       return set_error(NBC_ERR_STATE, "per-image BatchNorm statistics in NBC_PREC_F16X2: no raw-convolution array of this "
                                       "architecture attached (nbc_attach_bn_raw)");
   }
@@ -682,7 +643,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
                 float* logits_lowres_dev, float* logits_full_dev, void* labels_dev, int labels_dtype,
                 int64_t* counts_dev, int exclude_nodes, void* hip_stream) {
   if (!c || !x_dev) return set_error(NBC_ERR_INVALID, "nbc_forward: null argument");
-  if (!c->weights) return set_error(NBC_ERR_STATE, "nbc_forward: no weights attached (load_state_dict first)");
+  if (!c->weights.data()) return set_error(NBC_ERR_STATE, "nbc_forward: no weights attached (load_state_dict first)");
   if (x_dtype != NBC_IN_F32_NCHW && x_dtype != NBC_IN_U8_NHWC) return set_error(NBC_ERR_INVALID, "nbc_forward: bad x_dtype");
   if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_forward: bad labels_dtype");
   c->fwd_valid = false;
@@ -692,26 +653,26 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   const Plan& P = c->plan;
   const int prec = c->precision;
   if (!c->nonfinite) {
-    NBC_HIP(hipMalloc((void**)&c->nonfinite, 256));
-    NBC_HIP(hipMemset(c->nonfinite, 0, 256));
+    NBC_HIP(c->nonfinite.reserve(256));
+    NBC_HIP(hipMemset(c->nonfinite.get(), 0, 256));
   }
 
   const size_t nops = P.ops.size();
   constexpr size_t kMaxProfSets = 4096;
-  std::vector<hipEvent_t>* evs = nullptr;
+  std::vector<Event>* evs = nullptr;
   if (c->profiling && c->prof_used < kMaxProfSets) {
     if (c->prof_used > 0 && c->prof_ops.size() != nops) c->prof_used = 0;   // plan changed: restart
     if (c->prof_sets.size() <= c->prof_used) c->prof_sets.emplace_back();
     evs = &c->prof_sets[c->prof_used];
     while (evs->size() < nops + 1) {
-      hipEvent_t ev;
-      NBC_HIP(hipEventCreate(&ev));
-      evs->push_back(ev);
+      Event ev;
+      NBC_HIP(ev.create());
+      evs->push_back(std::move(ev));
     }
     c->prof_ops = P.ops;
     c->prof_arch = P.arch;
   }
-  float* lowres = logits_lowres_dev ? logits_lowres_dev : c->lowres;
+  float* lowres = logits_lowres_dev ? logits_lowres_dev : c->lowres.as<float>();
 
   c->fused_pairs = 0;
   if (evs) NBC_HIP(hipEventRecord((*evs)[0], s));
@@ -722,9 +683,9 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
     switch (o.kind) {
       case OP_INGEST:
         if (x_dtype == NBC_IN_F32_NCHW)
-          e = launch_ingest_f32(static_cast<const float*>(x_dev), c->bufs[o.out_buf], N, H, W, prec, s);
+          e = launch_ingest_f32(static_cast<const float*>(x_dev), c->bufs[o.out_buf].get(), N, H, W, prec, s);
         else
-          e = launch_ingest_u8(static_cast<const uint8_t*>(x_dev), c->bufs[o.out_buf], N, H, W, c->mean, c->stdv, prec, s);
+          e = launch_ingest_u8(static_cast<const uint8_t*>(x_dev), c->bufs[o.out_buf].get(), N, H, W, c->mean, c->stdv, prec, s);
         break;
       case OP_CONV: {
         const auto tile_of = [&](const Op& q) {
@@ -740,7 +701,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         break;
       }
       case OP_MAXPOOL:
-        e = launch_maxpool3x3s2(c->bufs[o.in_buf], c->bufs[o.out_buf], N, o.Hi, o.Wi, o.Ci, o.Ho, o.Wo, prec, s);
+        e = launch_maxpool3x3s2(c->bufs[o.in_buf].get(), c->bufs[o.out_buf].get(), N, o.Hi, o.Wi, o.Ci, o.Ho, o.Wo, prec, s);
         break;
       case OP_HEAD1X1: {
         const UnitPtrs p = unit_ptrs(c, o.unit);
@@ -749,48 +710,49 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         // also clears this launch's share of the counters (3 per image) when the batch has at most 256 of them
         unsigned long long* cz = counts_dev && 3 * N <= 256 ? reinterpret_cast<unsigned long long*>(counts_dev) : nullptr;
         if (is_effnet(c->arch) && o.Ci != 256)             // FCNHead(inplanes, 3): inplanes / 4 channels, padded
-          e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf]), p.w, p.shift, lowres, N, o.Ho * o.Wo, o.Ci, cz,
-                                 c->nonfinite, s);
+          e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf].get()), p.w, p.shift, lowres, N, o.Ho * o.Wo, o.Ci, cz,
+                                 c->nonfinite.as<unsigned>(), s);
         else if (o.Ci == 512)
-          e = launch_head1x1(c->bufs[o.in_buf], p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+          e = launch_head1x1(c->bufs[o.in_buf].get(), p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite.as<unsigned>(), s);
         else
-          e = launch_head1x1_c256(c->bufs[o.in_buf], p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite, s);
+          e = launch_head1x1_c256(c->bufs[o.in_buf].get(), p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite.as<unsigned>(), s);
         break;
       }
       case OP_ASPP_POOL: {
         const UnitPtrs p = unit_ptrs(c, o.unit);
-        float* partial = static_cast<float*>(c->bufs[o.ws_buf]);
+        float* partial = static_cast<float*>(c->bufs[o.ws_buf].get());
         float* mean = partial + (size_t)N * aspp_pool_slices(o.Hi * o.Wi) * o.Ci;
-        e = launch_aspp_pool(c->bufs[o.in_buf], N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co, partial, mean, c->bufs[o.out_buf],
+        e = launch_aspp_pool(c->bufs[o.in_buf].get(), N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co, partial, mean, c->bufs[o.out_buf].get(),
                              prec, s);
         break;
       }
       case OP_CONCAT: {
-        const void* br[4] = {c->bufs[o.cat_in[0]], c->bufs[o.cat_in[1]], c->bufs[o.cat_in[2]], c->bufs[o.cat_in[3]]};
-        e = launch_aspp_concat(br, c->bufs[o.cat_in[4]], c->bufs[o.out_buf], N, o.Ho * o.Wo, prec, s);
+        const void* br[4] = {c->bufs[o.cat_in[0]].get(), c->bufs[o.cat_in[1]].get(), c->bufs[o.cat_in[2]].get(), c->bufs[o.cat_in[3]].get()};
+        e = launch_aspp_concat(br, c->bufs[o.cat_in[4]].get(), c->bufs[o.out_buf].get(), N, o.Ho * o.Wo, prec, s);
         break;
       }
       case OP_BN_STATS: {                              // f16x2: the unit's 2^-r follows its raw scales; the table carries the tensor's 2^a_out
-        const float* gamma = c->bn_affine + o.affine_off;
+        const float* gamma = c->bn_affine.data() + o.affine_off;
         const bool x2 = prec == NBC_PREC_F16X2;
-        e = launch_bn_stats(c->bufs[o.out_buf], N, o.Ho * o.Wo, o.Co, gamma, gamma + o.Co, x2 ? c->bn_raw + o.affine_off + o.Co : nullptr,
-                            x2 ? c->act_exp[o.unit] : 0, c->bn_ws, c->nonfinite, prec, s);
+        e = launch_bn_stats(c->bufs[o.out_buf].get(), N, o.Ho * o.Wo, o.Co, gamma, gamma + o.Co,
+                            x2 ? c->bn_raw.data() + o.affine_off + o.Co : nullptr, x2 ? c->act_exp[o.unit] : 0, c->bn_ws.get(),
+                            c->nonfinite.as<unsigned>(), prec, s);
         break;
       }
       case OP_BN_APPLY:                                // with the tables the statistics op left in the workspace
-        e = launch_bn_apply(c->bufs[o.out_buf], o.res_buf >= 0 ? c->bufs[o.res_buf] : nullptr, N, o.Ho * o.Wo, o.Co, c->bn_ws, o.relu, prec,
-                            s);
+        e = launch_bn_apply(c->bufs[o.out_buf].get(), o.res_buf >= 0 ? c->bufs[o.res_buf].get() : nullptr, N, o.Ho * o.Wo, o.Co,
+                            c->bn_ws.get(), o.relu, prec, s);
         break;
       case OP_DWCONV: {
         const UnitPtrs p = unit_ptrs(c, o.unit);
         const ConvUnit& u = conv_units(c->arch)[o.unit];
         DwArgs a{};
-        a.x = static_cast<const float*>(c->bufs[o.in_buf]);
+        a.x = static_cast<const float*>(c->bufs[o.in_buf].get());
         a.w = p.w;
         a.scale = p.scale;
         a.shift = p.shift;
-        a.y = static_cast<float*>(c->bufs[o.out_buf]);
-        a.partial = static_cast<float*>(c->bufs[o.ws_buf]);
+        a.y = static_cast<float*>(c->bufs[o.out_buf].get());
+        a.partial = static_cast<float*>(c->bufs[o.ws_buf].get());
         a.N = N; a.Hi = o.Hi; a.Wi = o.Wi; a.C = o.Co; a.Ho = o.Ho; a.Wo = o.Wo;
         a.k = u.k; a.stride = u.stride; a.pad_t = u.pad; a.pad_l = u.pad; a.in_swish = u.in_swish ? 1 : 0;
         e = launch_dwconv(a, s);
@@ -799,21 +761,21 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
       case OP_SE_EXCITE: {
         const UnitPtrs pr = unit_ptrs(c, o.unit), pe = unit_ptrs(c, o.aux_unit);
         const ConvUnit& ur = conv_units(c->arch)[o.unit];
-        e = launch_se_excite(static_cast<const float*>(c->bufs[o.in_buf]), N, o.tiles, o.Co, o.Hi * o.Wi, pr.w, pr.shift, ur.cout,
-                             pe.w, pe.shift, static_cast<float*>(c->bufs[o.out_buf]), s);
+        e = launch_se_excite(static_cast<const float*>(c->bufs[o.in_buf].get()), N, o.tiles, o.Co, o.Hi * o.Wi, pr.w, pr.shift, ur.cout,
+                             pe.w, pe.shift, static_cast<float*>(c->bufs[o.out_buf].get()), s);
         break;
       }
       case OP_GATE_WEIGHTS:
-        e = launch_gate_weights(unit_ptrs(c, o.unit).w, static_cast<const float*>(c->bufs[o.gate_buf]),
-                                static_cast<float*>(c->bufs[o.ws_buf]), N, o.Co, o.Ci, s);
+        e = launch_gate_weights(unit_ptrs(c, o.unit).w, static_cast<const float*>(c->bufs[o.gate_buf].get()),
+                                static_cast<float*>(c->bufs[o.ws_buf].get()), N, o.Co, o.Ci, s);
         break;
       case OP_SWISH:
-        e = launch_swish(static_cast<float*>(c->bufs[o.out_buf]), (size_t)N * o.Ho * o.Wo * o.Co, s);
+        e = launch_swish(static_cast<float*>(c->bufs[o.out_buf].get()), (size_t)N * o.Ho * o.Wo * o.Co, s);
         break;
       case OP_POOL_ANY: {
         const UnitPtrs p = unit_ptrs(c, o.unit);
-        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf]), N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co,
-                            static_cast<float*>(c->bufs[o.ws_buf]), static_cast<float*>(c->bufs[o.out_buf]), s);
+        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf].get()), N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co,
+                            static_cast<float*>(c->bufs[o.ws_buf].get()), static_cast<float*>(c->bufs[o.out_buf].get()), s);
         break;
       }
       case OP_UPSAMPLE:
@@ -935,8 +897,8 @@ static int dropout_passes(const char* who, nbc_ctx* c, int N, int H, int W, cons
     int* size = reinterpret_cast<int*>(ws + L.size);
     unsigned char* bg = ws + L.bg;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
-    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf], up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
-                                   first_draw + d0, D, c->nonfinite, s));
+    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf].get(), up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
+                                   first_draw + d0, D, c->nonfinite.as<unsigned>(), s));
     if (min_pixels > 0) {
       NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, nullptr, 0, s));
       NBC_HIP(launch_remove_small_zones(labels, 0, I, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s));
@@ -962,9 +924,9 @@ int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W
   if (rc != NBC_OK) return rc;
   NBC_HIP(hipStreamSynchronize(s));
   c->fwd_valid = false;                    // the timed launches below rewrite activations (raw ones in NBC_BN_PER_IMAGE)
-  hipEvent_t e0, e1;
-  NBC_HIP(hipEventCreate(&e0));
-  NBC_HIP(hipEventCreate(&e1));
+  Event e0, e1;
+  NBC_HIP(e0.create());
+  NBC_HIP(e1.create());
   Plan& P = c->plan;
   for (size_t oi = 0; oi < P.ops.size(); ++oi) {
     Op& o = P.ops[oi];
@@ -992,8 +954,6 @@ int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W
     }
     o.tile = best;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return NBC_OK;
 }
 
@@ -1051,17 +1011,8 @@ int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N
   if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_remove_small_zones: bad labels_dtype");
   NBC_HIP(hipSetDevice(c->device));
   const size_t px = (size_t)N * H * W;
-  if (px > c->zones_px) {                             // grows by at least half, like the activation buffers
-    size_t cap = std::max(px, c->zones_px + c->zones_px / 2);
-    if (c->zones_ws) { NBC_HIP(hipFree(c->zones_ws)); c->zones_ws = nullptr; c->zones_px = 0; }
-    if (hipMalloc(&c->zones_ws, cap * 9 + 256) != hipSuccess) {
-      (void)hipGetLastError();
-      cap = px;
-      NBC_HIP(hipMalloc(&c->zones_ws, cap * 9 + 256));
-    }
-    c->zones_px = cap;
-  }
-  int* parent = static_cast<int*>(c->zones_ws);
+  NBC_HIP(c->zones_ws.reserve(px * 9 + 256, Grow::kMargin));   // grows by at least half, like the activation buffers
+  int* parent = c->zones_ws.as<int>();
   int* size = parent + px;
   unsigned char* bg = reinterpret_cast<unsigned char*>(size + px);
   NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, exclude_nodes, bg,
@@ -1098,8 +1049,8 @@ int nbc_resize_cubic_u8(nbc_ctx* c, const uint8_t* src_dev, int H, int W, float*
   if (!c || !src_dev || !dst_dev) return set_error(NBC_ERR_INVALID, "nbc_resize_cubic_u8: null argument");
   if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return set_error(NBC_ERR_INVALID, "nbc_resize_cubic_u8: bad shape");
   NBC_HIP(hipSetDevice(c->device));
-  if (!c->scratch256) NBC_HIP(hipMalloc(&c->scratch256, 256));
-  unsigned* minmax = static_cast<unsigned*>(c->scratch256);
+  NBC_HIP(c->scratch256.reserve(256));
+  unsigned* minmax = c->scratch256.as<unsigned>();
   NBC_HIP(launch_resize_cubic_u8(src_dev, H, W, dst_dev, nullptr, nullptr, out_h, out_w, minmax, static_cast<hipStream_t>(hip_stream)));
   return NBC_OK;
 }
@@ -1109,8 +1060,8 @@ int nbc_preprocess_u8(nbc_ctx* c, const uint8_t* src_dev, int H, int W, uint8_t*
   if (!c || !src_dev || !dst_u8_dev) return set_error(NBC_ERR_INVALID, "nbc_preprocess_u8: null argument");
   if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return set_error(NBC_ERR_INVALID, "nbc_preprocess_u8: bad shape");
   NBC_HIP(hipSetDevice(c->device));
-  if (!c->scratch256) NBC_HIP(hipMalloc(&c->scratch256, 256));
-  unsigned* minmax = static_cast<unsigned*>(c->scratch256);
+  NBC_HIP(c->scratch256.reserve(256));
+  unsigned* minmax = c->scratch256.as<unsigned>();
   NBC_HIP(launch_resize_cubic_u8(src_dev, H, W, nullptr, dst_u8_dev, row_lit_dev, out_h, out_w, minmax,
                                  static_cast<hipStream_t>(hip_stream)));
   return NBC_OK;
@@ -1135,18 +1086,18 @@ int nbc_activation_peaks(nbc_ctx* c, float* peaks_host, int capacity) {
   const int nunits = (int)conv_units(c->plan.arch).size();
   if (capacity < nunits) return set_error(NBC_ERR_INVALID, "nbc_activation_peaks: need room for nbc_arch_num_convs() values");
   NBC_HIP(hipSetDevice(c->device));
-  unsigned* dev = nullptr;
-  NBC_HIP(hipMalloc((void**)&dev, sizeof(unsigned) * nunits));
+  DeviceBuffer tmp;
+  NBC_HIP(tmp.reserve(sizeof(unsigned) * nunits));
+  unsigned* dev = tmp.as<unsigned>();
   hipError_t e = hipMemset(dev, 0, sizeof(unsigned) * nunits);
   const int N = c->plan.N;
   for (const Op& o : c->plan.ops) {
     if (e != hipSuccess) break;
     if ((o.kind != OP_CONV && o.kind != OP_ASPP_POOL) || o.out_buf < 0) continue;   // the pooling branch: its pooled vector
-    e = launch_absmax(c->bufs[o.out_buf], (size_t)N * o.Ho * o.Wo * o.Co, o.Co, c->precision, dev + o.unit, nullptr);
+    e = launch_absmax(c->bufs[o.out_buf].get(), (size_t)N * o.Ho * o.Wo * o.Co, o.Co, c->precision, dev + o.unit, nullptr);
   }
   std::vector<unsigned> bits(nunits, 0u);
   if (e == hipSuccess) e = hipMemcpy(bits.data(), dev, sizeof(unsigned) * nunits, hipMemcpyDeviceToHost);
-  (void)hipFree(dev);
   if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_activation_peaks: ") + hipGetErrorString(e));
   for (int u = 0; u < nunits; ++u) std::memcpy(&peaks_host[u], &bits[u], 4);
   return nunits;
@@ -1164,23 +1115,18 @@ int nbc_read_activation(nbc_ctx* c, const char* name, float* dst_host, size_t ca
   const size_t elems = (size_t)N * o.Ho * o.Wo * creal;
   if (capacity < elems) return set_error(NBC_ERR_INVALID, "nbc_read_activation: destination too small");
   NBC_HIP(hipSetDevice(c->device));
-  float* tmp = nullptr;
-  NBC_HIP(hipMalloc((void**)&tmp, elems * sizeof(float)));
-  hipError_t e = hipSuccess;
+  const size_t img = (size_t)o.Ho * o.Wo * o.Co;        // NCHW of the (padded) tensor
+  DeviceBuffer nchw;
+  NBC_HIP(nchw.reserve((size_t)N * img * sizeof(float)));
+  float* tmp = nchw.as<float>();
+  hipError_t e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf].get(), tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
   if (creal == o.Co) {
-    e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf], tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
     if (e == hipSuccess) e = hipMemcpy(dst_host, tmp, elems * sizeof(float), hipMemcpyDeviceToHost);
-  } else {                                             // NCHW of the padded tensor, then each image's first creal channels
-    (void)hipFree(tmp);
-    tmp = nullptr;
-    const size_t img = (size_t)o.Ho * o.Wo * o.Co;
-    NBC_HIP(hipMalloc((void**)&tmp, (size_t)N * img * sizeof(float)));
-    e = launch_nhwc_to_nchw_f32(c->bufs[o.out_buf], tmp, N, o.Ho, o.Wo, o.Co, c->precision, nullptr);
+  } else {                                             // each image's first creal channels
     for (int n = 0; n < N && e == hipSuccess; ++n)
       e = hipMemcpy(dst_host + (size_t)n * o.Ho * o.Wo * creal, tmp + n * img, (size_t)o.Ho * o.Wo * creal * sizeof(float),
                     hipMemcpyDeviceToHost);
   }
-  (void)hipFree(tmp);
   if (e != hipSuccess) return set_error(NBC_ERR_HIP, std::string("nbc_read_activation: ") + hipGetErrorString(e));
   int a = 0;
   if (stored_exponent(c, o.name, &a) && a != 0)        // f16x2: the tensor as the network defines it (power of two taken off, exact)

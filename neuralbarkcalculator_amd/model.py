@@ -90,22 +90,28 @@ def pack_bn_affine(state_dict: Mapping[str, object], arch="fcn_resnet50") -> np.
     return out
 
 
-def broadcast_bn_affine(affine: Optional[np.ndarray], arch="fcn_resnet50", src: int = 0, group=None, device=None) -> np.ndarray:
-    """``torch.distributed`` broadcast of the per-image BatchNorm affine array from rank ``src`` (which passes it; the
-    other ranks pass None and get its copy).  ``device``: where the collective's tensor lives (an RCCL group needs the
-    GPU; None = the host, for gloo)."""
+def _broadcast_side_array(arr: Optional[np.ndarray], count: int, who: str, what: str, arch, src: int, group, device) -> np.ndarray:
+    """``torch.distributed`` broadcast of a float32 array of ``count`` elements from rank ``src``: ``who`` and ``what`` name
+    the caller and the array in the source rank's refusal."""
     import torch.distributed as dist
-    count = int(_lib.load().nbc_arch_bn_affine_floats(topology.arch_index(arch)))
     if dist.get_rank(group) == src:
-        if affine is None or affine.size != count:
-            raise RuntimeError("broadcast_bn_affine: the source rank holds no affine array of %s" % arch)
-        t = torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float32))
+        if arr is None or arr.size != count:
+            raise RuntimeError("%s: the source rank holds no %s of %s" % (who, what, arch))
+        t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
     else:
         t = torch.empty(count, dtype=torch.float32)
     if device is not None:
         t = t.to(device)
     dist.broadcast(t, src=src, group=group)
     return t.cpu().numpy()
+
+
+def broadcast_bn_affine(affine: Optional[np.ndarray], arch="fcn_resnet50", src: int = 0, group=None, device=None) -> np.ndarray:
+    """``torch.distributed`` broadcast of the per-image BatchNorm affine array from rank ``src`` (which passes it; the
+    other ranks pass None and get its copy).  ``device``: where the collective's tensor lives (an RCCL group needs the
+    GPU; None = the host, for gloo)."""
+    count = int(_lib.load().nbc_arch_bn_affine_floats(topology.arch_index(arch)))
+    return _broadcast_side_array(affine, count, "broadcast_bn_affine", "affine array", arch, src, group, device)
 
 
 def pack_bn_raw(state_dict: Mapping[str, object], arch="fcn_resnet50"):
@@ -135,18 +141,8 @@ def bn_raw_flags(raw: np.ndarray) -> int:
 def broadcast_bn_raw(raw: Optional[np.ndarray], arch="fcn_resnet50", src: int = 0, group=None, device=None) -> np.ndarray:
     """``torch.distributed`` broadcast of the raw-convolution array (``pack_bn_raw``) from rank ``src``, as
     ``broadcast_bn_affine`` sends the affine array."""
-    import torch.distributed as dist
     count = int(_lib.load().nbc_arch_bn_raw_floats(topology.arch_index(arch)))
-    if dist.get_rank(group) == src:
-        if raw is None or raw.size != count:
-            raise RuntimeError("broadcast_bn_raw: the source rank holds no raw-convolution array of %s" % arch)
-        t = torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32))
-    else:
-        t = torch.empty(count, dtype=torch.float32)
-    if device is not None:
-        t = t.to(device)
-    dist.broadcast(t, src=src, group=group)
-    return t.cpu().numpy()
+    return _broadcast_side_array(raw, count, "broadcast_bn_raw", "raw-convolution array", arch, src, group, device)
 
 
 def arch_of_state_dict(state_dict: Mapping[str, object]) -> str:
