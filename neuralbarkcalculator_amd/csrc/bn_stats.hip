@@ -266,16 +266,18 @@ BnTables bn_stats_tables(void* ws, int N, int hw, int C) {
 hipError_t launch_bn_stats(const void* y, int N, int hw, int C, const float* gamma, const float* beta, const float* inv_r, int a_out,
                            void* ws, unsigned* word, int precision, hipStream_t s) {
   if (!bn_shape_ok(N, hw, C)) return hipErrorInvalidValue;
-  if (precision == 0) return bn_stats<0>(y, N, hw, C, gamma, beta, nullptr, 0, ws, nullptr, s);
-  if (precision == 2) return bn_stats<2>(y, N, hw, C, gamma, beta, inv_r, a_out, ws, word, s);
-  return hipErrorInvalidValue;
+  return with_precision(precision, [&](auto P) {        // f32 reads none of inv_r, a_out and word
+    if constexpr (P.value == 1) return hipErrorInvalidValue;
+    else return bn_stats<P.value>(y, N, hw, C, gamma, beta, inv_r, a_out, ws, word, s);
+  });
 }
 
 hipError_t launch_bn_apply(void* y, const void* res, int N, int hw, int C, void* ws, int relu, int precision, hipStream_t s) {
   if (!bn_shape_ok(N, hw, C)) return hipErrorInvalidValue;
-  if (precision == 0) return bn_apply<0>(y, res, N, hw, C, ws, relu, s);
-  if (precision == 2) return bn_apply<2>(y, res, N, hw, C, ws, relu, s);
-  return hipErrorInvalidValue;
+  return with_precision(precision, [&](auto P) {
+    if constexpr (P.value == 1) return hipErrorInvalidValue;
+    else return bn_apply<P.value>(y, res, N, hw, C, ws, relu, s);
+  });
 }
 
 }  // namespace nbc

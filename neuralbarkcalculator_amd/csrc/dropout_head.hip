@@ -3,10 +3,13 @@
 // of the mask from ONE read of the stored input of classifier.4.  The definition of a draw is in include/nbc.h
 // (nbc_dropout_draws); the generator is csrc/philox.hpp, shared with the host entry point nbc_dropout_mask below.
 //
-// The arithmetic is head1x1_body's (pointwise.hip; the operands come in through the same load8 / decode8 of stored.hpp) with one
-// multiplication in front of it: one wave per pixel, lane l owns channels 8l .. 8l+7 -- elements 512 pixel + 8l .. + 7,
-// i.e. quads 128 pixel + 2l and + 1: two Philox calls per lane, pixel and draw --, an f32 fma chain in channel order, then
-// wave_sum and the bias.  With p = 0 the factor is 1.0f for every element and the logits are bit for bit the forward's.
+// The arithmetic is head1x1_body's (pointwise.hip): the weight rows and the chain are the same functions of head1x1.hpp, the
+// tree and the store the functions whose text head1x1_body writes out, the operands come in through the same load8 / decode8 of
+// stored.hpp.  The one difference is the chain's
+// per-element hook, here the multiplication by the keep factor: one wave per pixel, lane l owns channels 8l .. 8l+7 -- elements
+// 512 pixel + 8l .. + 7, i.e. quads 128 pixel + 2l and + 1: two Philox calls per lane, pixel and draw.  With p = 0 the factor is
+// 1.0f for every element and the logits are bit for bit the forward's.
+#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "philox.hpp"
 #include "reduce.hpp"
@@ -28,11 +31,8 @@ __global__ __launch_bounds__(256) void head1x1_dropout_kernel(const void* __rest
   const int img = img0 + blockIdx.y;
   const unsigned long long id = ids.id[blockIdx.y];
   float wr[3][8];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) wr[c][e] = w[c * CIN + lane * 8 + e];
-  const float b0 = bias[0], b1 = bias[1], b2 = bias[2];
+  head_weight_rows(w, CIN, lane * 8, wr);
+  const float b[3] = {bias[0], bias[1], bias[2]};
   const int first = (blockIdx.x * 4 + wave) * 8;
   if (first >= hw) return;                                // wave-uniform: the shuffles below see whole waves
   const unsigned char* xi = static_cast<const unsigned char*>(x) + (size_t)img * hw * CIN * (PREC == 1 ? 2 : 4);
@@ -49,27 +49,16 @@ __global__ __launch_bounds__(256) void head1x1_dropout_kernel(const void* __rest
     for (int d = 0; d < draws; ++d) {
       const Philox4 r0 = dropout_words(quad, (unsigned)(first_draw + d), id, seed);
       const Philox4 r1 = dropout_words(quad + 1u, (unsigned)(first_draw + d), id, seed);
-      float s[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
+      float s[3];
+      head_chain(f, wr, s, [&](int e, float v) {
         const unsigned r = e < 4 ? r0.v[e] : r1.v[e - 4];
-        const float g = f[e] * (r < threshold ? 0.f : keep_scale);       // X (m keep)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(g, wr[c][e], s[c]);
-      }
-      wave_sum(s);
-      if (lane == 0 && pix < hw) {
-        float* yp = y + ((size_t)d * N + img) * 3 * hw + pix;
-        const float l0 = s[0] + b0, l1 = s[1] + b1, l2 = s[2] + b2;
-        yp[0] = l0;
-        yp[(size_t)hw] = l1;
-        yp[2 * (size_t)hw] = l2;
-        bad = bad || !(__builtin_isfinite(l0) && __builtin_isfinite(l1) && __builtin_isfinite(l2));
-      }
+        return v * (r < threshold ? 0.f : keep_scale);                   // X (m keep)
+      });
+      head_tree<64>(s);
+      if (lane == 0 && pix < hw) bad = !head_store(s, b, y + ((size_t)d * N + img) * 3 * hw + pix, hw) || bad;
     }
   }
-  // a logit that is not finite raises the context's sticky flag, as in head1x1_body
-  if (nonfinite && bad) atomicOr(nonfinite, 1u);
+  if (bad) head_raise(nonfinite);
 }
 
 }  // namespace
@@ -83,15 +72,10 @@ hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bi
     DropoutIds ids{};
     for (int i = 0; i < n; ++i) ids.id[i] = ids_host[img0 + i];
     const dim3 grid((hw + 31) / 32, n);
-    if (precision == 0)
-      hipLaunchKernelGGL(head1x1_dropout_kernel<0>, grid, dim3(256), 0, s, x, w, bias, y, N, hw, img0, ids, seed, threshold,
+    with_precision(precision, [&](auto P) {
+      hipLaunchKernelGGL(head1x1_dropout_kernel<P.value>, grid, dim3(256), 0, s, x, w, bias, y, N, hw, img0, ids, seed, threshold,
                          keep_scale, first_draw, draws, nonfinite);
-    else if (precision == 2)
-      hipLaunchKernelGGL(head1x1_dropout_kernel<2>, grid, dim3(256), 0, s, x, w, bias, y, N, hw, img0, ids, seed, threshold,
-                         keep_scale, first_draw, draws, nonfinite);
-    else
-      hipLaunchKernelGGL(head1x1_dropout_kernel<1>, grid, dim3(256), 0, s, x, w, bias, y, N, hw, img0, ids, seed, threshold,
-                         keep_scale, first_draw, draws, nonfinite);
+    });
   }
   return hipGetLastError();
 }

@@ -13,9 +13,10 @@
 //   gate_weights: the gate folded into the project conv's weights, per image: Wg[n][o][c] = W[o][c] * gate[n][c]; the
 //     project conv then runs once per image on them (no pass over the gated activation).
 //   swish: in place (the head conv's output).
-//   pool: DeepLabHead's pooling branch for any cin (aspp.hip's has cin = 2048 built in): two-level f32 mean over fixed
-//     pixel slices, then the 1x1 conv with BatchNorm and ReLU.
-//   head1x1: classifier.4 for any cin (a multiple of 64): FCNHead's inplanes / 4 channels, padded.
+//   head1x1: classifier.4 for any cin (a multiple of 64): FCNHead's inplanes / 4 channels, padded.  Its chain is its own
+//     (lane-strided channel order); the tree, the store, the flag and the counter clearing are head1x1.hpp's.
+// (DeepLabHead's pooling branch is aspp.hip's, for every trunk.)
+#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 
@@ -151,43 +152,6 @@ __global__ __launch_bounds__(256) void swish_kernel(float4* __restrict__ y, size
   }
 }
 
-constexpr int kPoolSlicesEff = 256;
-
-// grid (slices, N), 256 threads over the channels: partial[img][slice][c] = sum of the slice's pixels, in pixel order
-__global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restrict__ x, float* __restrict__ partial, int hw, int C,
-                                                           int slices) {
-  const int slice = blockIdx.x, img = blockIdx.y;
-  const int p0 = (int)(((long long)hw * slice) / slices), p1 = (int)(((long long)hw * (slice + 1)) / slices);
-  const float* xi = x + (size_t)img * hw * C;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float s = 0.f;
-    for (int p = p0; p < p1; ++p) s += xi[(size_t)p * C + c];
-    partial[((size_t)img * slices + slice) * C + c] = s;
-  }
-}
-
-// grid (cout / 4, N): the image's mean (slices in order / hw) into LDS, then one wave per output channel:
-// y = relu(fma(w . mean, scale, shift))
-__global__ __launch_bounds__(256) void pool_conv_kernel(const float* __restrict__ partial, int slices, int hw, int C,
-                                                        const float* __restrict__ w, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, float* __restrict__ y, int cout) {
-  extern __shared__ float m[];
-  const int img = blockIdx.y;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float* p = partial + (size_t)img * slices * C + c;
-    float s = 0.f;
-    for (int k = 0; k < slices; ++k) s += p[(size_t)k * C];
-    m[c] = s / (float)hw;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, o = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const float* wr = w + (size_t)o * C;
-  float acc = 0.f;
-  for (int i = lane; i < C; i += 64) acc = __builtin_fmaf(wr[i], m[i], acc);
-  acc = wave_sum(acc);
-  if (lane == 0) y[(size_t)img * cout + o] = __builtin_fmaxf(__builtin_fmaf(acc, scale[o], shift[o]), 0.f);
-}
-
 // classifier.4 for cin a multiple of 64: one wave per pixel, lane l sums channels l, l + 64, ... in order, a 64-lane tree
 __global__ __launch_bounds__(256) void head1x1_any_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y, int M, int hw,
@@ -195,36 +159,23 @@ __global__ __launch_bounds__(256) void head1x1_any_kernel(const float* __restric
                                                           unsigned* __restrict__ nonfinite) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (counts_zero && blockIdx.x == 0 && threadIdx.x < ncounts) counts_zero[threadIdx.x] = 0ull;   // for the next launch
+  head_clear_counts(counts_zero, ncounts);
   if (m >= M) return;
   const float* xp = x + (size_t)m * C;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float s[3] = {0.f, 0.f, 0.f};
   for (int i = lane; i < C; i += 64) {
     const float v = xp[i];
-    s0 = __builtin_fmaf(v, w[i], s0);
-    s1 = __builtin_fmaf(v, w[C + i], s1);
-    s2 = __builtin_fmaf(v, w[2 * C + i], s2);
-  }
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s0 += __shfl_xor(s0, off, 64);
-    s1 += __shfl_xor(s1, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
+    for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(v, w[c * C + i], s[c]);
   }
+  head_tree<64>(s);
   if (lane != 0) return;
   const int img = m / hw, pix = m - img * hw;
-  float* yp = y + (size_t)img * 3 * hw + pix;
-  const float l0 = s0 + bias[0], l1 = s1 + bias[1], l2 = s2 + bias[2];
-  yp[0] = l0;
-  yp[(size_t)hw] = l1;
-  yp[2 * (size_t)hw] = l2;
-  if (nonfinite && !(__builtin_isfinite(l0) && __builtin_isfinite(l1) && __builtin_isfinite(l2))) atomicOr(nonfinite, 1u);
+  const float b[3] = {bias[0], bias[1], bias[2]};
+  if (!head_store(s, b, y + (size_t)img * 3 * hw + pix, hw)) head_raise(nonfinite);
 }
 
-unsigned grid_stride_blocks(size_t n) {
-  size_t b = (n + 255) / 256;
-  return (unsigned)(b > 256 * 16 ? 256 * 16 : (b ? b : 1));   // 16 blocks per CU, grid-stride the rest
-}
+constexpr int kBlocksPerCu = 16;   // of this file's grid-stride kernels
 
 template <int K, int S>
 void launch_dw(const DwArgs& a, hipStream_t s) {
@@ -263,32 +214,21 @@ hipError_t launch_se_excite(const float* partial, int N, int tiles, int C, int h
 
 hipError_t launch_gate_weights(const float* w, const float* gate, float* wg, int N, int Co, int Ci, hipStream_t s) {
   if (N < 1 || Co < 1 || Ci % 64 != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gate_weights_kernel, dim3(grid_stride_blocks((size_t)N * Co * Ci / 4)), dim3(256), 0, s,
+  hipLaunchKernelGGL(gate_weights_kernel, dim3(grid_stride_blocks((size_t)N * Co * Ci / 4, 256, kBlocksPerCu)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(w), gate, reinterpret_cast<float4*>(wg), Co, Ci, N);
   return hipGetLastError();
 }
 
 hipError_t launch_swish(float* y, size_t elems, hipStream_t s) {
   if (elems % 4 != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(swish_kernel, dim3(grid_stride_blocks(elems / 4)), dim3(256), 0, s, reinterpret_cast<float4*>(y), elems / 4);
-  return hipGetLastError();
-}
-
-int pool_any_slices(int hw) { return hw < kPoolSlicesEff ? hw : kPoolSlicesEff; }
-
-hipError_t launch_pool_any(const float* x, int N, int hw, int cin, const float* w, const float* scale, const float* shift, int cout,
-                           float* partial, float* y, hipStream_t s) {
-  if (cout % 4 != 0 || N < 1 || N > 65535 || hw < 1 || cin < 1 || (size_t)cin * 4 > 64 * 1024) return hipErrorInvalidValue;
-  const int slices = pool_any_slices(hw);
-  hipLaunchKernelGGL(pool_partial_kernel, dim3(slices, N), dim3(256), 0, s, x, partial, hw, cin, slices);
-  hipLaunchKernelGGL(pool_conv_kernel, dim3(cout / 4, N), dim3(256), (size_t)cin * sizeof(float), s, partial, slices, hw, cin, w, scale,
-                     shift, y, cout);
+  hipLaunchKernelGGL(swish_kernel, dim3(grid_stride_blocks(elems / 4, 256, kBlocksPerCu)), dim3(256), 0, s, reinterpret_cast<float4*>(y), elems / 4);
   return hipGetLastError();
 }
 
 hipError_t launch_head1x1_any(const float* x, const float* w, const float* bias, float* y, int N, int hw, int cin,
                               unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s) {
   if (cin % 64 != 0 || N < 1 || hw < 1) return hipErrorInvalidValue;
+  if (!head_clears_counts(N)) counts_zero = nullptr;      // the caller then clears the counters itself
   const int M = N * hw;
   hipLaunchKernelGGL(head1x1_any_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, w, bias, y, M, hw, cin, counts_zero, 3 * N, nonfinite);
   return hipGetLastError();

@@ -279,7 +279,6 @@ const char* kernel_name(OpKind k) {
     case OP_SE_EXCITE: return "se_excite";
     case OP_GATE_WEIGHTS: return "gate_weights";
     case OP_SWISH: return "swish";
-    case OP_POOL_ANY: return "pool";
     default: return "upsample_argmax";
   }
 }
@@ -707,15 +706,13 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         const UnitPtrs p = unit_ptrs(c, o.unit);
         if (o.Ci != 512 && o.Ci != 256 && !is_effnet(c->arch))
           return set_error(NBC_ERR_STATE, "classifier.4 expects 512 or 256 input channels");
-        // also clears this launch's share of the counters (3 per image) when the batch has at most 256 of them
-        unsigned long long* cz = counts_dev && 3 * N <= 256 ? reinterpret_cast<unsigned long long*>(counts_dev) : nullptr;
-        if (is_effnet(c->arch) && o.Ci != 256)             // FCNHead(inplanes, 3): inplanes / 4 channels, padded
+        // also clears the class counters (3 per image) when the batch is small enough (head_clears_counts; else OP_UPSAMPLE does)
+        unsigned long long* cz = reinterpret_cast<unsigned long long*>(counts_dev);
+        if (is_effnet(c->arch) && o.Ci != 256)             // FCNHead(inplanes, 3): inplanes / 4 channels, padded; at 512 (b5) too
           e = launch_head1x1_any(static_cast<const float*>(c->bufs[o.in_buf].get()), p.w, p.shift, lowres, N, o.Ho * o.Wo, o.Ci, cz,
                                  c->nonfinite.as<unsigned>(), s);
-        else if (o.Ci == 512)
-          e = launch_head1x1(c->bufs[o.in_buf].get(), p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite.as<unsigned>(), s);
         else
-          e = launch_head1x1_c256(c->bufs[o.in_buf].get(), p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite.as<unsigned>(), s);
+          e = launch_head1x1(c->bufs[o.in_buf].get(), o.Ci, p.w, p.shift, lowres, N, o.Ho * o.Wo, prec, cz, c->nonfinite.as<unsigned>(), s);
         break;
       }
       case OP_ASPP_POOL: {
@@ -772,14 +769,8 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
       case OP_SWISH:
         e = launch_swish(static_cast<float*>(c->bufs[o.out_buf].get()), (size_t)N * o.Ho * o.Wo * o.Co, s);
         break;
-      case OP_POOL_ANY: {
-        const UnitPtrs p = unit_ptrs(c, o.unit);
-        e = launch_pool_any(static_cast<const float*>(c->bufs[o.in_buf].get()), N, o.Hi * o.Wi, o.Ci, p.w, p.scale, p.shift, o.Co,
-                            static_cast<float*>(c->bufs[o.ws_buf].get()), static_cast<float*>(c->bufs[o.out_buf].get()), s);
-        break;
-      }
       case OP_UPSAMPLE:
-        if (counts_dev && 3 * N > 256) {             // more counters than classifier.4's launch clears
+        if (counts_dev && !head_clears_counts(N)) {  // more counters than classifier.4's launch clears
           e = hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 3 * N, s);
           if (e != hipSuccess) break;
         }

@@ -1,10 +1,12 @@
 // Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
 // efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
-// bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.
+// bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
+// convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "conv_tiles.hpp"
 
@@ -62,6 +64,22 @@ int choose_conv_tile(int M, int Co, int K, int precision, int rows_kind);
 hipError_t launch_conv_dma(const ConvArgs& a, int precision, int tile, hipStream_t s);
 hipError_t launch_conv3x3_rows(const ConvArgs& a, int tile, hipStream_t s);   // tile: a row-step tile of the convolution's kind
 
+// f(tag) with the run-time precision as a compile-time tag.value: 0 -> f32, 2 -> f16x2, anything else -> bf16 (the numbering of
+// every `template <int PREC>` of stored.hpp's users).  The conv kernels keep their own dispatch (launch_conv_dma).
+template <typename F>
+inline auto with_precision(int precision, F&& f) {
+  if (precision == 0) return f(std::integral_constant<int, 0>{});
+  if (precision == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 1>{});
+}
+
+// Blocks of a grid-stride kernel over `items` items, one per thread and round: enough to cover them once, at most blocks_per_cu
+// on each of the 256 CUs, at least one.
+inline unsigned grid_stride_blocks(size_t items, int threads, int blocks_per_cu) {
+  const size_t blocks = (items + threads - 1) / threads, cap = (size_t)256 * blocks_per_cu;
+  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
 // float32 NCHW [N,3,H,W] -> NHWC elements padded to 16 bytes per pixel.
 hipError_t launch_ingest_f32(const float* x, void* y, int N, int H, int W, int precision, hipStream_t s);
 // uint8 NHWC [N,H,W,3] -> same, applying (u8/255 - mean)/std in f32 (dataset.py:175-186).
@@ -70,15 +88,18 @@ hipError_t launch_ingest_u8(const uint8_t* x, void* y, int N, int H, int W, cons
 // MaxPool2d(3, stride 2, padding 1) on NHWC, C a multiple of the 16-byte chunk.
 hipError_t launch_maxpool3x3s2(const void* x, void* y, int N, int Hi, int Wi, int C, int Ho, int Wo,
                                int precision, hipStream_t s);
-// classifier.4: 1x1 conv 512 -> 3 with bias; f32 weights [3][512]; output f32 NCHW [N,3,h,w].
-// counts_zero (nullable, 3*N <= 256 counters): cleared by this launch for the upsample/argmax launch
-// that follows it, which accumulates the per-class pixel counts there (saves a memset node).
-// nonfinite (nullable): one device word that gets bit 0 set when a logit is NaN or infinite.
-hipError_t launch_head1x1(const void* x, const float* w, const float* bias, float* y, int N, int hw,
-                          int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
-// classifier.4 of DeepLabHead: the same with 256 input channels
-hipError_t launch_head1x1_c256(const void* x, const float* w, const float* bias, float* y, int N, int hw,
-                               int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
+// classifier.4 (its pieces: head1x1.hpp): 1x1 conv cin -> 3 with bias; f32 weights [3][cin]; output f32 NCHW [N,3,h,w].
+// cin = 512 (FCNHead: a wave per pixel) or 256 (DeepLabHead: a half-wave per pixel), anything else is an invalid value.
+// counts_zero (nullable): the 3 * N class counters, cleared by this launch for the upsample/argmax launch that follows it,
+// which accumulates the per-class pixel counts there (saves a memset node) -- when head_clears_counts(N), else the caller
+// clears them.  nonfinite (nullable): one device word that gets bit 0 set when a logit is NaN or infinite.
+inline bool head_clears_counts(int N) { return 3 * N <= 256; }   // one thread of block 0 per counter
+hipError_t launch_head1x1(const void* x, int cin, const float* w, const float* bias, float* y, int N, int hw, int precision,
+                          unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
+// The same for f32 and any cin that is a multiple of 64, its chain in lane-strided channel order (lane l: channels l, l + 64, ...):
+// the FCN head of every EfficientNet, whatever its width -- other bits than launch_head1x1 at cin = 512.
+hipError_t launch_head1x1_any(const float* x, const float* w, const float* bias, float* y, int N, int hw, int cin,
+                              unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
 // classifier.4 of FCNHead behind a live Dropout (dropout_head.hip; the definition: include/nbc.h, nbc_dropout_draws): the
 // low-resolution logits y [draws][N][3][hw] of draws first_draw .. first_draw + draws - 1 from one read of x [N][hw][512]
 // stored elements.  ids_host: the N image identities, HOST memory, handed to the kernel by value (64 per launch: no copy,
@@ -95,9 +116,9 @@ hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bi
 // draws <= 65535 (a 16-bit field per class), votes 16-byte aligned for the vector path; labels at any address.
 hipError_t launch_vote_accumulate(const unsigned char* labels, int draws, int N, long long P, uint32_t* votes, bool first,
                                   hipStream_t s);
-// ASPP pooling branch (aspp.hip), per image: mean over hw pixels of x [N][hw][cin = 2048] (stored elements), the 1x1 conv
-// with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout] elements.  Workspaces: partial
-// N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.
+// ASPP pooling branch of every DeepLab head (aspp.hip), per image: mean over hw pixels of x [N][hw][cin] (stored elements; cin a
+// multiple of 64, at most 4096), the 1x1 conv with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout]
+// elements.  Workspaces: partial N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.
 int aspp_pool_slices(int hw);
 hipError_t launch_aspp_pool(const void* x, int N, int hw, int cin, const float* w, const float* scale, const float* shift, int cout,
                             float* partial, float* mean, void* y, int precision, hipStream_t s);
@@ -149,13 +170,6 @@ hipError_t launch_se_excite(const float* partial, int N, int tiles, int C, int h
 hipError_t launch_gate_weights(const float* w, const float* gate, float* wg, int N, int Co, int Ci, hipStream_t s);
 // y = swish(y) in place, elems a multiple of 4
 hipError_t launch_swish(float* y, size_t elems, hipStream_t s);
-// DeepLabHead's pooling branch for any cin: partial N * pool_any_slices(hw) * cin floats; y [N][cout] f32
-int pool_any_slices(int hw);
-hipError_t launch_pool_any(const float* x, int N, int hw, int cin, const float* w, const float* scale, const float* shift, int cout,
-                           float* partial, float* y, hipStream_t s);
-// classifier.4 with cin a multiple of 64, f32 (the contract of launch_head1x1)
-hipError_t launch_head1x1_any(const float* x, const float* w, const float* bias, float* y, int N, int hw, int cin,
-                              unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
 // Bicubic (A=-0.75, align_corners=False) upsample of f32 NCHW [N,3,h,w] to HxW, fused with the
 // per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,

@@ -235,10 +235,8 @@ struct Builder {
     return h;
   }
 
-  // FCNHead or DeepLabHead on the trunk's output, classifier.4, then the upsample with its argmax.  pool: the kernel of the
-  // ASPP pooling branch: OP_ASPP_POOL (2048 stored elements per pixel; its workspace also holds the per-image means) or
-  // OP_POOL_ANY (f32, any width, two launches).
-  void head(Tensor cur, int ui, OpKind pool) {
+  // FCNHead or DeepLabHead on the trunk's output, classifier.4, then the upsample with its argmax.
+  void head(Tensor cur, int ui) {
     Tensor t;
     int cls = ui + 1;                                                        // classifier.4's unit
     if (is_deeplab_head(P.arch)) {
@@ -248,15 +246,13 @@ struct Builder {
       for (int b = 0; b < 4; ++b) br[b] = add_conv(ui + b, cur);
       const ConvUnit& pu = units[ui + 4];
       const int hw = cur.H * cur.W, B = pu.cout;
-      const size_t ws_floats = pool == OP_ASPP_POOL ? ((size_t)N * aspp_pool_slices(hw) + N) * pu.cin
-                                                    : (size_t)N * pool_any_slices(std::max(hw, 1)) * pu.cin;
-      const int ws = acquire(ws_floats * sizeof(float));
+      const int ws = acquire(((size_t)N * aspp_pool_slices(hw) + N) * pu.cin * sizeof(float));   // the slices' sums, then the means
       Op po;
-      po.kind = pool; po.unit = ui + 4; po.in_buf = cur.buf; po.ws_buf = ws;
+      po.kind = OP_ASPP_POOL; po.unit = ui + 4; po.in_buf = cur.buf; po.ws_buf = ws;
       po.Hi = cur.H; po.Wi = cur.W; po.Ci = pu.cin; po.Ho = 1; po.Wo = 1; po.Co = B;
       po.name = "classifier.0.convs.4";                                      // the pooled vector: one pixel per image
       po.out_buf = acquire((size_t)N * B * eb);
-      po.launches = pool == OP_POOL_ANY ? 2 : 3;                             // OP_ASPP_POOL: partial sums, their sum, the 1x1 conv
+      po.launches = 3;                                                       // partial sums, their sum, the 1x1 conv
       po.flops = 2.0 * N * B * pu.cin + (double)N * hw * pu.cin;
       po.bytes = (double)N * hw * pu.cin * eb + (double)B * pu.cin * 4 + (double)N * B * eb;
       P.ops.push_back(po);
@@ -303,13 +299,8 @@ struct Builder {
 std::string build_plan(const PlanKey& key, Plan* out) {
   Builder b(key);
   int head_unit = 0;
-  if (is_effnet(key.arch)) {
-    const Tensor x = b.effnet_trunk(&head_unit);
-    b.head(x, head_unit, OP_POOL_ANY);
-  } else {
-    const Tensor x = b.resnet50_trunk(&head_unit);
-    b.head(x, head_unit, OP_ASPP_POOL);
-  }
+  const Tensor x = is_effnet(key.arch) ? b.effnet_trunk(&head_unit) : b.resnet50_trunk(&head_unit);
+  b.head(x, head_unit);
   if (b.refused.empty()) *out = b.P;
   return b.refused;
 }

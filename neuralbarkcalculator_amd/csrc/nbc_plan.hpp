@@ -10,7 +10,7 @@
 namespace nbc {
 
 enum OpKind { OP_INGEST, OP_CONV, OP_MAXPOOL, OP_HEAD1X1, OP_UPSAMPLE, OP_ASPP_POOL, OP_CONCAT, OP_BN_STATS, OP_BN_APPLY,
-              OP_DWCONV, OP_SE_EXCITE, OP_GATE_WEIGHTS, OP_SWISH, OP_POOL_ANY };
+              OP_DWCONV, OP_SE_EXCITE, OP_GATE_WEIGHTS, OP_SWISH };
 
 // Buffer 0 is a real buffer: an op names the buffers and units it uses, everything else stays -1.
 struct Op {

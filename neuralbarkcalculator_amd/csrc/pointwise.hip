@@ -3,6 +3,7 @@
 // lane accesses, no MFMA.
 #include <cstdlib>
 
+#include "head1x1.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 #include "stored.hpp"
@@ -137,9 +138,13 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x
   static_cast<uint4*>(y)[(((size_t)img * Ho + oy) * Wo + ox) * chunks + ch] = o;
 }
 
-// classifier.4 (models.py:121): 1x1 conv CIN -> 3 with bias.  CIN = 512 (FCNHead): one wave per pixel, lane l owns
-// channels 8l..8l+7 (an f32 fma chain in channel order), then a 64-lane xor-tree.  CIN = 256 (DeepLabHead): the same
-// with a half-wave per pixel, two pixels per wave-wide load, a 32-lane tree.
+// classifier.4 (models.py:121): 1x1 conv CIN -> 3 with bias.  CIN = 512 (FCNHead): one wave per pixel, lane l owns channels
+// 8l..8l+7 (head_chain of head1x1.hpp: an f32 fma chain in channel order), then a 64-lane xor-tree.  CIN = 256 (DeepLabHead): the
+// same with a half-wave per pixel, two pixels per wave-wide load, a 32-lane tree.  The weight rows, the chain and the counter
+// clearing are head1x1.hpp's and leave this kernel's machine code as it was.  The tree and the store are head_tree's and
+// head_store's text written out here: called as functions they compute the same bits, but the compiler then schedules the
+// kernel differently, and a build with that code missed the bf16 kernel's time margin at batch 8, which sends a kernel back
+// to its earlier form (profiles/pointwise_shared_forward_ab.log; that log also shows this form reading no faster).
 template <int PREC, int CIN>
 __device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
                                              const float* __restrict__ w,
@@ -154,13 +159,10 @@ __device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
   const int wave = threadIdx.x >> 6;
   const int cl = lane % LPP, sub = lane / LPP;            // CIN = 512: cl = lane, sub = 0
   float wr[3][8];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) wr[c][e] = w[c * CIN + cl * 8 + e];
+  head_weight_rows(w, CIN, cl * 8, wr);
   const float b0 = bias[0], b1 = bias[1], b2 = bias[2];
   const int first = (blockIdx.x * 4 + wave) * PIX_PER_WAVE;
-  if (counts_zero && blockIdx.x == 0 && threadIdx.x < ncounts) counts_zero[threadIdx.x] = 0ull;   // for the next launch
+  head_clear_counts(counts_zero, ncounts);
   // the wave's 8 pixel rows (loads) are requested together (one memory round trip), then reduced one by one
   const unsigned char* xb = static_cast<const unsigned char*>(x);
   Eight<PREC> raw[8];
@@ -171,24 +173,19 @@ __device__ __forceinline__ void head1x1_body(const void* __restrict__ x,
     const int m = first + q * PPL + sub;
     float f[8];
     decode8(raw[q], f);
-    float s[3] = {0.f, 0.f, 0.f};
+    float s[3];
+    head_chain(f, wr, s, head_identity{});
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) s[c] = __builtin_fmaf(f[e], wr[c][e], s[c]);
-#pragma unroll
-    for (int off = LPP / 2; off >= 1; off >>= 1)
+    for (int off = LPP / 2; off >= 1; off >>= 1)          // head_tree<LPP>, written out
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += __shfl_xor(s[c], off, 64);
     if (cl == 0 && m < M) {
       const int img = m / hw, pix = m - img * hw;
       float* yp = y + (size_t)img * 3 * hw + pix;
-      const float l0 = s[0] + b0, l1 = s[1] + b1, l2 = s[2] + b2;
+      const float l0 = s[0] + b0, l1 = s[1] + b1, l2 = s[2] + b2;      // head_store and head_raise, written out
       yp[0] = l0;
       yp[(size_t)hw] = l1;
       yp[2 * (size_t)hw] = l2;
-      // a logit that is not finite (NaN / inf in the input or the weights; in f16x2 mode an activation beyond f16's
-      // range) raises the context's sticky flag: nbc_nonfinite_seen
       if (nonfinite && !(__builtin_isfinite(l0) && __builtin_isfinite(l1) && __builtin_isfinite(l2))) atomicOr(nonfinite, 1u);
     }
   }
@@ -243,6 +240,44 @@ __device__ __forceinline__ void cubic_setup(int o, float scale, int in, int idx[
   }
 }
 
+// One four-tap sum of the separable bicubic filter, along a row (taps v, coefficients cx) or down a column (the four row sums,
+// cy): a product, then three fmas in tap order.
+__device__ __forceinline__ float cubic_dot4(float v0, float v1, float v2, float v3, const float (&c)[4]) {
+  float t = v0 * c[0];
+  t = __builtin_fmaf(v1, c[1], t);
+  t = __builtin_fmaf(v2, c[2], t);
+  return __builtin_fmaf(v3, c[3], t);
+}
+
+// One output pixel's label (element o of labels, nullable): models.py:273-276 (optional 2 -> 1), then, for a pixel inside the
+// image (`live`), the pixel counted into its class of cnt and the store as u8 or i64.
+__device__ __forceinline__ void emit_label(int best, int exclude_nodes, bool live, void* __restrict__ labels, int labels_i64, size_t o,
+                                           unsigned (&cnt)[3]) {
+  if (exclude_nodes && best == 2) best = 1;
+  if (live) {
+    cnt[0] += best == 0; cnt[1] += best == 1; cnt[2] += best == 2;
+    if (labels) {
+      if (labels_i64) static_cast<long long*>(labels)[o] = best;
+      else static_cast<unsigned char*>(labels)[o] = (unsigned char)best;
+    }
+  }
+}
+
+// The counting of models.py:324-331: the block's per-class pixel counts into the image's three 64-bit counters -- wave_sum, the
+// waves' sums through blk (three LDS words that the kernel zeroed before a barrier), one atomic per non-zero class.  (block_add
+// of reduce.hpp is this reduction with an LDS row per wave: 36 bytes more per block than these kernels hold.)
+__device__ __forceinline__ void add_class_counts(unsigned (&cnt)[3], unsigned (&blk)[3], unsigned long long* __restrict__ counts) {
+  const int tid = threadIdx.x;
+  wave_sum(cnt);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (cnt[c]) atomicAdd(&blk[c], cnt[c]);
+  }
+  __syncthreads();
+  if (tid < 3 && blk[tid]) atomicAdd(&counts[tid], (unsigned long long)blk[tid]);
+}
+
 // models.py:38-41 (bicubic to the input size) + models.py:270 (argmax over the 3 classes) +
 // models.py:273-276 (optional 2 -> 1) + the counting of models.py:324-331.
 // grid = (ceil(W/256), H, N), one output pixel per thread.
@@ -250,15 +285,14 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(
     const float* __restrict__ lowres, int h, int w, int H, int W, float scale_y, float scale_x,
     float* __restrict__ logits_full, void* __restrict__ labels, int labels_i64,
     unsigned long long* __restrict__ counts, int exclude_nodes) {
-  __shared__ unsigned int blk_counts[3];
+  __shared__ unsigned blk_counts[3];
   if (threadIdx.x < 3) blk_counts[threadIdx.x] = 0;
   __syncthreads();
   const int ox = blockIdx.x * 256 + threadIdx.x;
   const int oy = blockIdx.y;
   const int img = blockIdx.z;
-  const bool live = ox < W;
-  int label = -1;
-  if (live) {
+  unsigned cnt[3] = {0, 0, 0};
+  if (ox < W) {
     int iy[4], ix[4];
     float cy[4], cx[4];
     cubic_setup(oy, scale_y, h, iy, cy);
@@ -267,45 +301,29 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* src = lowres + ((size_t)img * 3 + c) * h * w;
-      float out = 0.f;
+      float t[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float* row = src + (size_t)iy[j] * w;
-        float t = row[ix[0]] * cx[0];
-        t = __builtin_fmaf(row[ix[1]], cx[1], t);
-        t = __builtin_fmaf(row[ix[2]], cx[2], t);
-        t = __builtin_fmaf(row[ix[3]], cx[3], t);
-        out = (j == 0) ? t * cy[0] : __builtin_fmaf(t, cy[j], out);
+        t[j] = cubic_dot4(row[ix[0]], row[ix[1]], row[ix[2]], row[ix[3]], cx);
       }
-      v[c] = out;
-      if (logits_full) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = out;
+      v[c] = cubic_dot4(t[0], t[1], t[2], t[3], cy);
+      if (logits_full) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = v[c];
     }
-    int best = argmax3(v[0], v[1], v[2]);
-    if (exclude_nodes && best == 2) best = 1;
-    label = best;
-    if (labels) {
-      const size_t o = ((size_t)img * H + oy) * W + ox;
-      if (labels_i64) static_cast<long long*>(labels)[o] = best;
-      else static_cast<unsigned char*>(labels)[o] = (unsigned char)best;
-    }
+    emit_label(argmax3(v[0], v[1], v[2]), exclude_nodes, true, labels, labels_i64, ((size_t)img * H + oy) * W + ox, cnt);
   }
-  if (counts) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const unsigned long long mask = __ballot(label == c);
-      if ((threadIdx.x & 63) == 0 && mask) atomicAdd(&blk_counts[c], (unsigned)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && blk_counts[threadIdx.x])
-      atomicAdd(&counts[(size_t)img * 3 + threadIdx.x], (unsigned long long)blk_counts[threadIdx.x]);
-  }
+  if (counts) add_class_counts(cnt, blk_counts, counts + (size_t)img * 3);
 }
 
 // Tiled form of the same computation: a block owns 256 columns x UP_ROWS rows of the output and
 // first copies the low-resolution window those pixels read (at most UP_WIN_R x UP_WIN_C taps per
 // class, edge-clamped) into LDS, so the 48 taps per pixel are LDS reads instead of 48 gather loads
 // (the one-pixel-per-thread kernel above was texture-address bound: 62 us per 1024^2 image).
-// Arithmetic and its order are identical to upsample_argmax_kernel.
+// Arithmetic and its order are upsample_argmax_kernel's: the row sums go through cubic_dot4, the labels through emit_label and
+// the counts through add_class_counts in both, which leaves this kernel's machine code what it was.  The column sum is
+// cubic_dot4's text written out: as a call (by value, by reference or over a callable) it gives the same bits and another
+// schedule, and a build with that code missed the kernel's time margin at batch 8, which sends a kernel back to its earlier
+// form (profiles/pointwise_shared_forward_ab.log; that log also shows this form reading no faster).
 constexpr int UP_WIN_R = 9, UP_WIN_C = 72;
 
 template <int UP_ROWS>
@@ -318,7 +336,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
   __shared__ unsigned int blk_counts[3];
   const int tid = threadIdx.x;
   const int ox0 = blockIdx.x * 256, oy0 = blockIdx.y * UP_ROWS, img = blockIdx.z;
-  if (tid < 3) blk_counts[tid] = 0;
+  if (tid < 3) blk_counts[tid] = 0;            // before the barrier behind the window copy
   int ti[4];
   float tc[4];
   cubic_setup(oy0, scale_y, h, ti, tc);
@@ -360,11 +378,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* rowp = win[c][rr];
-      float t = rowp[ix[0]] * cx[0];
-      t = __builtin_fmaf(rowp[ix[1]], cx[1], t);
-      t = __builtin_fmaf(rowp[ix[2]], cx[2], t);
-      t = __builtin_fmaf(rowp[ix[3]], cx[3], t);
-      hsum[c][rr][tid] = t;                        // read back by this thread only
+      hsum[c][rr][tid] = cubic_dot4(rowp[ix[0]], rowp[ix[1]], rowp[ix[2]], rowp[ix[3]], cx);   // read back by this thread only
     }
   }
   unsigned cnt[3] = {0, 0, 0};
@@ -377,7 +391,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float out = 0.f;
+      float out = 0.f;                             // cubic_dot4 down the column, written out (see above)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float t = hsum[c][iy[j] - wy0][tid];
@@ -386,28 +400,9 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
       v[c] = out;
       if (logits_full && live_x) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = out;
     }
-    int best = argmax3(v[0], v[1], v[2]);
-    if (exclude_nodes && best == 2) best = 1;
-    if (live_x) {
-      cnt[0] += best == 0; cnt[1] += best == 1; cnt[2] += best == 2;
-      if (labels) {
-        const size_t o = ((size_t)img * H + oy) * W + ox;
-        if (labels_i64) static_cast<long long*>(labels)[o] = best;
-        else static_cast<unsigned char*>(labels)[o] = (unsigned char)best;
-      }
-    }
+    emit_label(argmax3(v[0], v[1], v[2]), exclude_nodes, live_x, labels, labels_i64, ((size_t)img * H + oy) * W + ox, cnt);
   }
-  if (counts) {
-    wave_sum(cnt);
-    if ((tid & 63) == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        if (cnt[c]) atomicAdd(&blk_counts[c], cnt[c]);
-    }
-    __syncthreads();
-    if (tid < 3 && blk_counts[tid])
-      atomicAdd(&counts[(size_t)img * 3 + tid], (unsigned long long)blk_counts[tid]);
-  }
+  if (counts) add_class_counts(cnt, blk_counts, counts + (size_t)img * 3);
 }
 
 template <int PREC>
@@ -543,11 +538,7 @@ __global__ __launch_bounds__(256) void resize_cubic_kernel(const uint8_t* __rest
   }
 }
 
-inline int grid_for(size_t total, int block) {
-  size_t g = (total + block - 1) / block;
-  const size_t cap = 256 * 8;                 // 8 blocks per CU, grid-stride the rest
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int kBlocksPerCu = 8;               // of this file's grid-stride kernels
 
 }  // namespace
 
@@ -555,25 +546,18 @@ hipError_t launch_ingest_f32(const float* x, void* y, int N, int H, int W, int p
   if (N > 65535 || (long long)H * W > 0x7fffffffLL) return hipErrorInvalidValue;
   const int HW = H * W;
   dim3 grid((HW + 511) / 512, N);
-  if (precision == 0) hipLaunchKernelGGL(ingest_f32_kernel<0>, grid, dim3(256), 0, s, x, y, HW);
-  else if (precision == 2) hipLaunchKernelGGL(ingest_f32_kernel<2>, grid, dim3(256), 0, s, x, y, HW);
-  else hipLaunchKernelGGL(ingest_f32_kernel<1>, grid, dim3(256), 0, s, x, y, HW);
+  with_precision(precision, [&](auto P) { hipLaunchKernelGGL(ingest_f32_kernel<P.value>, grid, dim3(256), 0, s, x, y, HW); });
   return hipGetLastError();
 }
 
 hipError_t launch_ingest_u8(const uint8_t* x, void* y, int N, int H, int W, const float mean[3],
                             const float stdv[3], int precision, hipStream_t s) {
   const size_t total = (size_t)N * H * W;
-  const int g = grid_for(total, 256);
-  if (precision == 0)
-    hipLaunchKernelGGL(ingest_u8_kernel<0>, dim3(g), dim3(256), 0, s, x, y, total, mean[0], mean[1],
-                       mean[2], stdv[0], stdv[1], stdv[2]);
-  else if (precision == 2)
-    hipLaunchKernelGGL(ingest_u8_kernel<2>, dim3(g), dim3(256), 0, s, x, y, total, mean[0], mean[1],
-                       mean[2], stdv[0], stdv[1], stdv[2]);
-  else
-    hipLaunchKernelGGL(ingest_u8_kernel<1>, dim3(g), dim3(256), 0, s, x, y, total, mean[0], mean[1],
-                       mean[2], stdv[0], stdv[1], stdv[2]);
+  const unsigned g = grid_stride_blocks(total, 256, kBlocksPerCu);
+  with_precision(precision, [&](auto P) {
+    hipLaunchKernelGGL(ingest_u8_kernel<P.value>, dim3(g), dim3(256), 0, s, x, y, total, mean[0], mean[1], mean[2], stdv[0], stdv[1],
+                       stdv[2]);
+  });
   return hipGetLastError();
 }
 
@@ -586,31 +570,21 @@ hipError_t launch_maxpool3x3s2(const void* x, void* y, int N, int Hi, int Wi, in
   while ((1 << shift) < chunks) ++shift;
   if ((1 << shift) != chunks || chunks > 256 || Ho > 65535 || N > 65535) return hipErrorInvalidValue;   // C = 64 on this path
   dim3 grid((Wo * chunks + 255) / 256, Ho, N);
-  if (precision == 0) hipLaunchKernelGGL(maxpool_kernel<0>, grid, dim3(256), 0, s, x, y, Hi, Wi, shift, Ho, Wo);
-  else if (precision == 2) hipLaunchKernelGGL(maxpool_kernel<2>, grid, dim3(256), 0, s, x, y, Hi, Wi, shift, Ho, Wo);
-  else hipLaunchKernelGGL(maxpool_kernel<1>, grid, dim3(256), 0, s, x, y, Hi, Wi, shift, Ho, Wo);
+  with_precision(precision, [&](auto P) { hipLaunchKernelGGL(maxpool_kernel<P.value>, grid, dim3(256), 0, s, x, y, Hi, Wi, shift, Ho, Wo); });
   return hipGetLastError();
 }
 
-hipError_t launch_head1x1(const void* x, const float* w, const float* bias, float* y, int N, int hw,
-                          int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s) {
-  if (3 * N > 256) counts_zero = nullptr;      // the caller then clears the counters itself
+hipError_t launch_head1x1(const void* x, int cin, const float* w, const float* bias, float* y, int N, int hw, int precision,
+                          unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s) {
+  if (cin != 512 && cin != 256) return hipErrorInvalidValue;
+  if (!head_clears_counts(N)) counts_zero = nullptr;      // the caller then clears the counters itself
   const int M = N * hw;
-  const int blocks = (M + 31) / 32;           // 4 waves x 8 pixels
-  if (precision == 0) hipLaunchKernelGGL(head1x1_kernel<0>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
-  else if (precision == 2) hipLaunchKernelGGL(head1x1_kernel<2>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
-  else hipLaunchKernelGGL(head1x1_kernel<1>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
-  return hipGetLastError();
-}
-
-hipError_t launch_head1x1_c256(const void* x, const float* w, const float* bias, float* y, int N, int hw,
-                               int precision, unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s) {
-  if (3 * N > 256) counts_zero = nullptr;      // the caller then clears the counters itself
-  const int M = N * hw;
-  const int blocks = (M + 63) / 64;           // 4 waves x 16 pixels
-  if (precision == 0) hipLaunchKernelGGL(head1x1_c256_kernel<0>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
-  else if (precision == 2) hipLaunchKernelGGL(head1x1_c256_kernel<2>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
-  else hipLaunchKernelGGL(head1x1_c256_kernel<1>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+  const int per_block = cin == 512 ? 32 : 64;             // 4 waves x 8 pixels, or x 16 by half-waves
+  const dim3 grid((M + per_block - 1) / per_block);
+  with_precision(precision, [&](auto P) {
+    if (cin == 512) hipLaunchKernelGGL(head1x1_kernel<P.value>, grid, dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+    else hipLaunchKernelGGL(head1x1_c256_kernel<P.value>, grid, dim3(256), 0, s, x, w, bias, y, M, hw, counts_zero, 3 * N, nonfinite);
+  });
   return hipGetLastError();
 }
 
@@ -650,7 +624,7 @@ hipError_t launch_resize_cubic_u8(const uint8_t* src, int H, int W, float* dst, 
     if (e != hipSuccess) return e;
   }
   const size_t n = (size_t)H * W * 3;
-  hipLaunchKernelGGL(minmax_u8_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, src, n, minmax);
+  hipLaunchKernelGGL(minmax_u8_kernel, dim3(grid_stride_blocks(n, 256, kBlocksPerCu)), dim3(256), 0, s, src, n, minmax);
   hipLaunchKernelGGL(resize_cubic_kernel, dim3((out_w + 255) / 256, out_h), dim3(256), 0, s, src, H, W, dst, dst_u8, row_lit, out_h,
                      out_w, minmax);
   return hipGetLastError();
@@ -659,18 +633,14 @@ hipError_t launch_resize_cubic_u8(const uint8_t* src, int H, int W, float* dst, 
 hipError_t launch_nhwc_to_nchw_f32(const void* x, float* y, int N, int H, int W, int C, int precision,
                                    hipStream_t s) {
   const size_t total = (size_t)N * H * W * C;
-  const int g = grid_for(total, 256);
-  if (precision == 0) hipLaunchKernelGGL(nhwc_to_nchw_kernel<0>, dim3(g), dim3(256), 0, s, x, y, N, H * W, C);
-  else if (precision == 2) hipLaunchKernelGGL(nhwc_to_nchw_kernel<2>, dim3(g), dim3(256), 0, s, x, y, N, H * W, C);
-  else hipLaunchKernelGGL(nhwc_to_nchw_kernel<1>, dim3(g), dim3(256), 0, s, x, y, N, H * W, C);
+  const unsigned g = grid_stride_blocks(total, 256, kBlocksPerCu);
+  with_precision(precision, [&](auto P) { hipLaunchKernelGGL(nhwc_to_nchw_kernel<P.value>, dim3(g), dim3(256), 0, s, x, y, N, H * W, C); });
   return hipGetLastError();
 }
 
 hipError_t launch_absmax(const void* x, size_t elems, int C, int precision, unsigned* out, hipStream_t s) {
-  const int g = grid_for(elems, 256);
-  if (precision == 0) hipLaunchKernelGGL(absmax_kernel<0>, dim3(g), dim3(256), 0, s, x, elems, C, out);
-  else if (precision == 2) hipLaunchKernelGGL(absmax_kernel<2>, dim3(g), dim3(256), 0, s, x, elems, C, out);
-  else hipLaunchKernelGGL(absmax_kernel<1>, dim3(g), dim3(256), 0, s, x, elems, C, out);
+  const unsigned g = grid_stride_blocks(elems, 256, kBlocksPerCu);
+  with_precision(precision, [&](auto P) { hipLaunchKernelGGL(absmax_kernel<P.value>, dim3(g), dim3(256), 0, s, x, elems, C, out); });
   return hipGetLastError();
 }
 

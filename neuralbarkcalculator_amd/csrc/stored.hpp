@@ -1,8 +1,10 @@
 // The three forms an activation tensor [pixels][C] is stored in, and how a lane finds and decodes its channels in each.
 // PREC is the numbering of every `template <int PREC>` here: 0 = f32, 1 = bf16, 2 = f16x2 pieces (split16.hpp), whose pixel is
 // C / 32 groups of 128 bytes, [h0 x 32][h1 x 32].  Read through this header: classifier.4 and its dropout form, the ASPP pooling
-// branch, per-image BatchNorm, keep-mode reads and the calibration guard.  Not: the max-pool (pointwise.hip), the ingest kernels,
-// EfficientNet's f32 kernels, and the conv kernels' f16x2 epilogue (x2_store, f16x2_mma.hpp).
+// branch (of every DeepLab head, the EfficientNets' f32 one included), per-image BatchNorm, keep-mode reads and the calibration
+// guard.  Not: the max-pool (pointwise.hip), the ingest kernels, EfficientNet's own f32 kernels (efficientnet.hip), and the conv
+// kernels' f16x2 epilogue (x2_store, f16x2_mma.hpp).  The precision numbering is also with_precision's (nbc_kernels.hpp), which
+// turns the run-time precision into PREC for the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,7 +96,8 @@ __device__ __forceinline__ void unit_store(void* at, const Unit<PREC>& u) {
 
 // ---- eight channels [c8, c8 + 8) of pixel `pix` of a C-channel tensor (c8 a multiple of 8): two units in f32, one otherwise.
 // classifier.4 reads its operands through this one pair in the forward (head1x1_body, pointwise.hip) and behind the live
-// Dropout (head1x1_dropout_kernel, dropout_head.hip), which is what keeps "p = 0 gives the forward's logits bit for bit" true.
+// Dropout (head1x1_dropout_kernel, dropout_head.hip), and both run head_chain of head1x1.hpp on them (the header says which of
+// its other pieces each kernel calls): the two together are what makes "p = 0 gives the forward's logits bit for bit" true.
 template <int PREC>
 struct Eight {
   static constexpr int UNITS = 8 / Unit<PREC>::CH;

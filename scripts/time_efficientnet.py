@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Forward timing of the EfficientNet networks at 1024^2 in fp32 (bench.py keeps measuring fcn_resnet50): images/s of
 b0 and b5, both heads, at batch 1 and 2 (one stream, HIP events around the timed forwards), then one profiled pass per
-configuration: per kernel family the summed time, and for each new kernel (dwconv, se_excite, gate_weights, swish, pool)
+configuration: per kernel family the summed time, and for each new kernel (dwconv, se_excite, gate_weights, swish, aspp_pool)
 its achieved bytes/s against the 6.29 TB/s streaming figure of DESIGN section 3.6; the depthwise launches on tensors of
 64 MB or more are listed on their own.
 usage: python scripts/time_efficientnet.py [steps=20] [warmup=3] [out.json]   (one JSON line per configuration; all of
@@ -17,7 +17,7 @@ from neuralbarkcalculator_amd import synth
 from neuralbarkcalculator_amd.model import MODELS
 
 STREAM_TBPS = 6.29                      # DESIGN: measured streaming copy rate of the MI355X
-NEW_KERNELS = ("dwconv", "se_excite", "gate_weights", "swish", "pool")
+NEW_KERNELS = ("dwconv", "se_excite", "gate_weights", "swish", "aspp_pool")
 CONFIGS = [(arch, batch) for arch in ("fcn_efficientnet_b0", "deeplabv3_efficientnet_b0", "fcn_efficientnet_b5",
                                       "deeplabv3_efficientnet_b5") for batch in (1, 2)]
 

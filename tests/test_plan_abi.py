@@ -59,10 +59,10 @@ def test_tiles_are_those_recorded_before_the_menu_became_one_table(built_lib, pl
 
 
 # what an op reads and writes, by kernel, as fields of its line.  bn_stats names the tensor it reads as `out` as well and
-# writes the BatchNorm workspace only; aspp_pool / pool write their workspace before they read it; se_excite's `gate` is its
+# writes the BatchNorm workspace only; aspp_pool writes its workspace before it reads it; se_excite's `gate` is its
 # output once more; bn_apply and swish work in place.
 IO = {"ingest": ((), ("out",)), "conv_dma": (("in", "res", "gate"), ("out",)), "maxpool": (("in",), ("out",)),
-      "head1x1": (("in",), ()), "upsample_argmax": ((), ()), "aspp_pool": (("in",), ("ws", "out")), "pool": (("in",), ("ws", "out")),
+      "head1x1": (("in",), ()), "upsample_argmax": ((), ()), "aspp_pool": (("in",), ("ws", "out")),
       "concat": (("cat",), ("out",)), "bn_stats": (("in",), ()), "bn_apply": (("in", "res"), ("out",)),
       "dwconv": (("in",), ("ws", "out")), "se_excite": (("in",), ("out",)), "gate_weights": (("gate",), ("ws",)),
       "swish": (("in",), ("out",))}
@@ -195,7 +195,7 @@ def test_launches_of_an_op(plans):
             if o["kernel"] == "aspp_pool":
                 want = 3                                    # partial sums, their sum, the 1x1 conv
                 assert arch == DL and o["name"] == "classifier.0.convs.4", case
-            elif o["kernel"] in ("bn_stats", "pool"):
+            elif o["kernel"] == "bn_stats":
                 want = 2
             elif o["kernel"] == "conv_dma" and "gate" in o:
                 want = n                                    # the SE-gated project conv: one launch per image
@@ -207,7 +207,27 @@ def test_launches_of_an_op(plans):
         if arch == DL:
             assert sum(o["kernel"] == "aspp_pool" for o in ops) == 1, case
     dl_eff = parse(describe_plan("deeplabv3_efficientnet_b0", "fp32", 2, 72, 136))[0]
-    assert [(o["name"], o["launches"]) for o in dl_eff if o["kernel"] == "pool"] == [("classifier.0.convs.4", 2)]
+    assert [(o["name"], o["launches"]) for o in dl_eff if o["kernel"] == "aspp_pool"] == [("classifier.0.convs.4", 3)]
+
+
+# (network, precision, channels of the trunk's output as stored)
+POOL_CASES = [(DL, "fp32", 2048), (DL, "bf16", 2048), (DL, "f16x2", 2048),
+              ("deeplabv3_efficientnet_b0", "fp32", 1280), ("deeplabv3_efficientnet_b7", "fp32", 2560)]
+
+
+@pytest.mark.parametrize("arch,prec,cin", POOL_CASES, ids=lambda v: str(v))
+@pytest.mark.parametrize("n,h,w", [(2, 72, 136), (1, 1024, 1024)], ids=lambda v: str(v))
+def test_one_pooling_branch_for_every_deeplab_head(built_lib, arch, prec, cin, n, h, w):
+    """Every DeepLab head has exactly one aspp_pool op, classifier.0.convs.4 in three launches, whose workspace holds the
+    slices' partial sums (min(hw, 256) slices per image, hw the trunk output's pixels) and the per-image means, cin floats each;
+    no plan holds the `pool` op the EfficientNets had."""
+    ops, bufs, identity = parse(describe_plan(arch, prec, n, h, w))
+    pools = [o for o in ops if o["kernel"] == "aspp_pool"]
+    assert [(o["name"], o["launches"]) for o in pools] == [("classifier.0.convs.4", 3)]
+    assert not [o for o in ops if o["kernel"] == "pool"]
+    ho, wo = topology.out_hw(h, w, arch)                    # the head keeps the trunk's map: classifier.4's is the trunk's
+    hw = ho * wo
+    assert bufs[pools[0]["ws"]] == (n * min(hw, 256) + n) * cin * 4
 
 
 def test_the_text_is_cut_to_the_capacity_and_bad_keys_are_refused(built_lib):

@@ -3,6 +3,7 @@
   python tools/codegen_table.py CSRC_DIR file.hip ... > table.txt        one revision
   python tools/codegen_table.py --diff OLD.txt NEW.txt                   both side by side; exit status 1 when a kernel's
                                                                          scratch, occupancy or LDS got worse
+                                                                         or a kernel is new (a removed one is listed)
 Per kernel (hipcc -O3 -Rpass-analysis=kernel-resource-usage --save-temps): VGPRs, AGPRs, SGPRs, scratch bytes per lane,
 occupancy in waves per SIMD, LDS bytes per block, and the SHA-1 of its ISA with comments, directives and label numbers taken
 out.  Equal digests mean equal machine code.  A compile is not a run."""
@@ -80,9 +81,9 @@ def diff(old, new):
         x, y = a.get(key), b.get(key)
         fmt = lambda r: "%s/%s/%s/%s" % (r["vgpr"], r["scratch"], r["occ"], r["lds"]) if r else "-"
         worse = x and y and (int(y["scratch"]) > int(x["scratch"]) or int(y["occ"]) < int(x["occ"]) or int(y["lds"]) > int(x["lds"]))
-        bad += bool(worse) or not (x and y)
-        print("%-18s %-44s %-26s %-26s %s%s" % (key[0], key[1], fmt(x), fmt(y), "identical" if x and y and x["isa"] == y["isa"] else "CHANGED",
-                                                "  WORSE" if worse else ""))
+        bad += bool(worse) or not x                      # a kernel the new revision no longer has is not worse; one it adds has no parent row
+        print("%-18s %-44s %-26s %-26s %s%s" % (key[0], key[1], fmt(x), fmt(y),
+                                                "removed" if not y else "identical" if x and x["isa"] == y["isa"] else "CHANGED", "  WORSE" if worse else ""))
     return 1 if bad else 0
 
 
