@@ -547,6 +547,32 @@ int nbc_dropout_votes(nbc_ctx* ctx, int N, int H, int W, const uint64_t* image_i
 int nbc_vote_summary(const uint32_t* votes_dev, int N, int H, int W, int draws, uint8_t* labels_dev, uint8_t* support_dev,
                      int64_t* stats_dev, void* hip_stream);
 
+/* ---- the zones of a label map ------------------------------------------------------------------
+ * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and
+ * whether the bark is one sheet or many fragments.  The reference has no such code; the host restatement is
+ * neuralbarkcalculator_amd/zones.py (scipy.ndimage.label per class plus numpy reductions), the kernels csrc/zones.hip.
+ *
+ * Zones of a label map: the 8-connected components of each class c in {1, 2} (pixels with any other value belong to no zone).
+ * rows_dev  int64 [N, cap, NBC_ZONE_ROW], num_dev int64 [N].  num_dev[n] = the number of zones of image n (all of them, also
+ * when > cap).  Rows 0 .. min(num, cap)-1 of image n, in ascending order of first_pixel; rows beyond are not written.
+ * Row: { first_pixel (y*W+x of the zone's first pixel in raster order), class, pixels, x0, y0, x1, y1 (inclusive box),
+ *        sum_x, sum_y (over the zone's pixels), perimeter }
+ * perimeter: the number of pixel sides (4-neighbourhood) of the zone whose neighbour has another label or lies outside the
+ * image.  A 4-neighbour of the same class is in the same zone, so the figure is local to the pixel and an exact integer.
+ * labels_dev     uint8 or int64 [N,H,W] (labels_dtype NBC_LABEL_U8 / NBC_LABEL_I64); read, never written
+ * workspace_dev  at least nbc_zones_workspace_bytes(N, H, W) bytes of device memory, 256-byte aligned; contents scratch
+ * Everything is an integer sum, minimum or maximum: an image's rows are the same alone, in any batch, on any stream and from
+ * run to run.  Runs on hip_stream (on the context's device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null
+ * pointer (ctx, labels_dev, rows_dev, num_dev, workspace_dev), N < 1 or N > 65535, H or W outside 1..65535, H * W >= 2^31,
+ * cap < 1, another labels_dtype, a workspace that is too small or not 256-byte aligned. */
+#define NBC_ZONE_ROW 10
+/* With P = H * W and A(x) = x rounded up to a multiple of 256:  A(4 N P) + A(N P) + A(4 N ceil(P / 1024))
+ * (a parent int and a class byte per pixel, and a root count per 1024 pixels): 5 bytes per pixel and a little.
+ * 0 for a shape that nbc_label_zones refuses. */
+size_t nbc_zones_workspace_bytes(int N, int H, int W);
+int nbc_label_zones(nbc_ctx* ctx, const void* labels_dev, int labels_dtype, int N, int H, int W,
+                    int64_t* rows_dev, int cap, int64_t* num_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

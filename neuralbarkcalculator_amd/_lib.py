@@ -22,6 +22,7 @@ ARCH_FCN_RESNET50, ARCH_DEEPLABV3_RESNET50 = 0, 1   # NBC_ARCH_*
 ARCH_FCN_EFFICIENTNET_B0, ARCH_DEEPLABV3_EFFICIENTNET_B0 = 16, 24   # + n, n = 0..7
 BN_RUNNING, BN_PER_IMAGE = 0, 1                     # NBC_BN_*
 VOTE_STATS = 10                                     # NBC_VOTE_STATS
+ZONE_ROW = 10                                       # NBC_ZONE_ROW
 
 
 class NbcTensor(C.Structure):
@@ -119,6 +120,9 @@ SIGNATURES = {
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
     "nbc_vote_summary": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
     "nbc_resize_cubic_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nbc_preprocess_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p]),

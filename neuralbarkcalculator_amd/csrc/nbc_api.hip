@@ -1012,6 +1012,28 @@ int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N
   return NBC_OK;
 }
 
+static bool zones_shape_ok(int N, int H, int W) { return per_image_shape_ok(N, H, W) && H <= 65535 && W <= 65535; }
+
+size_t nbc_zones_workspace_bytes(int N, int H, int W) { return zones_shape_ok(N, H, W) ? zones_layout(N, H, W).total : 0; }
+
+int nbc_label_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, int N, int H, int W, int64_t* rows_dev, int cap,
+                    int64_t* num_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+  constexpr const char* kWho = "nbc_label_zones";
+  if (!c || !labels_dev || !rows_dev || !num_dev || !workspace_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!zones_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
+  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
+  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  const ZonesLayout lay = zones_layout(N, H, W);
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, lay.total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+  NBC_HIP(launch_label_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, reinterpret_cast<long long*>(rows_dev), cap,
+                             reinterpret_cast<long long*>(num_dev), reinterpret_cast<int*>(ws + lay.parent), ws + lay.cls,
+                             reinterpret_cast<int*>(ws + lay.blocks), static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
+}
+
 size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
   if (N < 1 || H < 8 || W < 8 || H > 65535 || draws_per_pass < 1 || (long long)H * W > 0x7fffffffLL) return 0;
   const unsigned long long I = (unsigned long long)draws_per_pass * (unsigned long long)N;

@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, aspp.hip, bn_stats.hip and
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, aspp.hip, bn_stats.hip and
 // efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
 // convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
@@ -180,6 +180,14 @@ hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int 
 // 2 -> 1 remap and per-class counts afterwards.  Workspaces: bg N*H*W bytes, parent and size N*H*W ints.
 hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H, int W, int min_pixels, int exclude_nodes,
                                      unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s);
+// The zones of label maps (zones.hip; the contract: nbc_label_zones in include/nbc.h): rows int64 [N][cap][10], num int64 [N].
+// zones_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size.
+struct ZonesLayout {
+  size_t parent, cls, blocks, total;         // int [N][H*W], u8 [N][H*W], int [N][ceil(H*W / 1024)]
+};
+ZonesLayout zones_layout(int N, int H, int W);
+hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, int W, long long* rows, int cap, long long* num,
+                              int* parent, unsigned char* cls, int* blocks, hipStream_t s);
 // Preprocessor (models.py:191-203): uint8 HWC [H,W,3] -> ToTensor -> skimage cubic resize with reflected borders,
 // clipped to the input range -> any of: float32 HWC [out_h,out_w,3]; its uint8 form as imsave writes it; per output
 // row the number of pixels trim_black counts as lit.  minmax: two uints of scratch.

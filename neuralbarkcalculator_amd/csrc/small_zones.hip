@@ -16,55 +16,12 @@
 // The result (which pixels flip) depends only on component sizes, which are exact integers, so the
 // output equals the CPU restatement (scipy.ndimage.label) bit for bit.
 #include "nbc_kernels.hpp"
+#include "union_find.hpp"
 
 namespace nbc {
 namespace {
 
-constexpr int TILE = 32;
-
-// Root of x with intermediate pointer jumping: every node passed is re-pointed at its grandparent.
-// Parents only ever decrease and always stay inside the node's (eventual) component, so the plain
-// stores race benignly with the atomicMin links of unite() (ECL-CC's "representative").
-__device__ __forceinline__ int find_root(int* L, int x) {
-  int curr = L[x];
-  if (curr != x) {
-    int prev = x, next;
-    while (curr > (next = L[curr])) {
-      L[prev] = next;
-      prev = curr;
-      curr = next;
-    }
-  }
-  return curr;
-}
-__device__ __forceinline__ int find_root_lds(const volatile int* L, int x) {
-  int p = L[x];
-  while (p != x) { x = p; p = L[x]; }
-  return x;
-}
-// link the larger root under the smaller one; retried when another thread re-rooted it meanwhile
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-  while (true) {
-    a = find_root(L, a);
-    b = find_root(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&L[b], a);
-    if (old == b) return;
-    b = old;
-  }
-}
-__device__ __forceinline__ void unite_lds(int* L, int a, int b) {
-  while (true) {
-    a = find_root_lds(L, a);
-    b = find_root_lds(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&L[b], a);
-    if (old == b) return;
-    b = old;
-  }
-}
+constexpr int TILE = kLabelTile;   // find_root / unite and their LDS forms: union_find.hpp
 
 // phase 0: mask = (label != 0) is labelled ("holes" of the Nothing mask); phase 1: mask = bg.
 // bg[] holds the Nothing mask (1 = background); written here in phase 0.

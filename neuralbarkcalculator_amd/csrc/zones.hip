@@ -1,0 +1,299 @@
+// The zones of a label map (nbc_label_zones, include/nbc.h): the 8-connected components of each class c in {1, 2}, one
+// record per zone -- first pixel, class, pixels, bounding box, coordinate sums, perimeter.  Integer work, exact against the
+// host restatement (neuralbarkcalculator_amd/zones.py: scipy.ndimage.label per class plus numpy reductions).
+//
+// The labelling is small_zones.hip's, made class-aware: a pixel is "set" for its neighbour only when both carry the same
+// class, so the zones of class 1 and of class 2 are labelled in one pass over one parent array.
+//   zone_tile      one 32x32 tile per block: runs of equal class per row (ballots), one LDS union per pair of touching runs of
+//                  consecutive rows, every pixel then points at its tile-local root (a pixel index of the image); the class
+//                  (0 for any label outside {1, 2}) goes to a byte plane that every later kernel reads instead of the labels
+//   zone_border_rows / _cols   unions across the tile borders, the run rule with "a same-class neighbour" for "a set one"
+//   count_roots    a root is a pixel that points at itself; unite() roots at the smaller index, so a zone's root is its
+//                  first pixel in raster order.  Roots per 1024 consecutive pixels,
+//   scan_roots     their exclusive scan per image (one block per image) and the image's zone count,
+//   assign_roots   every root's index within its image, in raster order: the root's parent becomes the code -2 - index and,
+//                  below cap, its row is initialised
+//   accumulate     one 32x32 tile per block again: every zone pixel walks to its root's code; a wave reduces its two rows per
+//                  distinct zone from ballots alone (pixel count, coordinate sums and box from the bit mask, the perimeter from
+//                  four side ballots), its leader adds that into an LDS hash slot of the tile, and every used slot issues one
+//                  set of 64-bit global atomics (4 adds, 2 mins, 2 maxes) into the zone's row.  Rows at or above cap get nothing.
+// Workspace: 4 B (parent) + 1 B (class) per pixel + 4 B per 1024 pixels.  Integer sums, mins and maxes do not depend on their
+// order: an image's rows are the same alone, in any batch, on any stream and from run to run.
+#include "nbc_kernels.hpp"
+#include "reduce.hpp"
+#include "union_find.hpp"
+
+namespace nbc {
+namespace {
+
+constexpr int TILE = kLabelTile;
+constexpr int kChunk = 1024;                 // consecutive pixels per block of the root count / scan / assign
+constexpr int kRow = NBC_ZONE_ROW;           // int64 per zone
+constexpr int kSlots = TILE * TILE;          // LDS hash slots per tile: at most 512 zones meet a tile (two per 2x2 pixels)
+
+template <typename LabelT>
+__global__ __launch_bounds__(TILE* TILE) void zone_tile_kernel(const LabelT* __restrict__ labels, unsigned char* __restrict__ cls,
+                                                                int* __restrict__ parent, int H, int W) {
+  __shared__ int s[TILE * TILE];
+  __shared__ unsigned char sc[TILE * TILE];
+  const int tx = threadIdx.x & (TILE - 1), ty = threadIdx.x >> 5;
+  const int x = blockIdx.x * TILE + tx, y = blockIdx.y * TILE + ty;
+  const size_t img = (size_t)blockIdx.z * H * W;
+  const bool inside = x < W && y < H;
+  const int p = y * W + x;
+  int c = 0;
+  if (inside) {
+    const LabelT v = labels[img + p];
+    c = v == (LabelT)1 ? 1 : (v == (LabelT)2 ? 2 : 0);
+  }
+  const int t = threadIdx.x;
+  // horizontal runs of equal class, without atomics: a pixel points at the first pixel of its run
+  const unsigned long long b1 = __ballot(c == 1), b2 = __ballot(c == 2);
+  const unsigned row_bits = (unsigned)((c == 1 ? b1 : (c == 2 ? b2 : 0ull)) >> (32 * ((t >> 5) & 1)));
+  const unsigned zeros_left = ~row_bits & ((1u << tx) - 1u);
+  const int run_start = zeros_left ? 32 - __clz((int)zeros_left) : 0;
+  s[t] = c ? (t - tx + run_start) : -1;
+  sc[t] = (unsigned char)c;
+  __syncthreads();
+  // one union per pair of touching runs of the same class in consecutive rows (small_zones.hip's rule)
+  if (c && ty > 0) {
+    const bool w = tx > 0 && ((row_bits >> (tx - 1)) & 1u), e = tx < TILE - 1 && ((row_bits >> (tx + 1)) & 1u);
+    const bool n = sc[t - TILE] == c;
+    const bool nw = tx > 0 && sc[t - TILE - 1] == c, ne = tx < TILE - 1 && sc[t - TILE + 1] == c;
+    if (n) {
+      if (!(w && nw)) unite_lds(s, t, t - TILE);
+    } else {
+      if (nw && !w) unite_lds(s, t, t - TILE - 1);
+      if (ne && !e) unite_lds(s, t, t - TILE + 1);
+    }
+  }
+  __syncthreads();
+  if (inside) {
+    int r = -1;
+    if (c) {
+      r = find_root_lds(s, t);
+      r = (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1));   // index inside the image
+    }
+    parent[img + p] = r;
+    cls[img + p] = (unsigned char)c;
+  }
+}
+
+// Unions across tile borders: small_zones.hip's border kernels with "set" read as "of this pixel's class".
+__global__ void zone_border_rows_kernel(int* __restrict__ parent, const unsigned char* __restrict__ cls, int H, int W) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = (blockIdx.y + 1) * TILE;
+  if (x >= W || y >= H) return;
+  int* L = parent + (size_t)blockIdx.z * H * W;
+  const unsigned char* C = cls + (size_t)blockIdx.z * H * W;
+  const int p = y * W + x;
+  const int c = C[p];
+  if (!c) return;
+  const bool n = C[p - W] == c;
+  const bool w = x > 0 && C[p - 1] == c, e = x < W - 1 && C[p + 1] == c;
+  const bool nw = x > 0 && C[p - W - 1] == c, ne = x < W - 1 && C[p - W + 1] == c;
+  if (n) {
+    if (!(w && nw)) unite(L, p, p - W);
+  } else {
+    if (nw && !w) unite(L, p, p - W - 1);
+    if (ne && !e) unite(L, p, p - W + 1);
+  }
+}
+__global__ void zone_border_cols_kernel(int* __restrict__ parent, const unsigned char* __restrict__ cls, int H, int W) {
+  const int y = blockIdx.x * blockDim.x + threadIdx.x, x = (blockIdx.y + 1) * TILE;      // x: first column right of a border
+  if (y >= H || x >= W) return;
+  int* L = parent + (size_t)blockIdx.z * H * W;
+  const unsigned char* C = cls + (size_t)blockIdx.z * H * W;
+  const int p = y * W + x;                    // right of the border; p - 1 is left of it
+  const bool top = (y & (TILE - 1)) == 0;     // rows on a horizontal border are handled by zone_border_rows_kernel
+  const int cr = C[p], cl = C[p - 1];
+  if (cr && cr == cl) unite(L, p, p - 1);
+  if (y == 0 || top) return;
+  // a diagonal across the border is needed only when neither the pixel's straight neighbour in its own tile (N) nor the
+  // pixel across the border in its own row has the pixel's class: otherwise that neighbour's own link joins the two
+  if (cr && cl != cr && C[p - W] != cr && C[p - W - 1] == cr) unite(L, p, p - W - 1);          // NW across the border
+  if (cl && cr != cl && C[p - 1 - W] != cl && C[p - W] == cl) unite(L, p - 1, p - W);          // NE across the border
+}
+
+__global__ __launch_bounds__(kChunk) void count_roots_kernel(const int* __restrict__ parent, int* __restrict__ blocks, int P) {
+  const long long q = (long long)blockIdx.x * kChunk + threadIdx.x;      // may pass 2^31 in the last block
+  const bool root = q < P && parent[(size_t)blockIdx.y * P + q] == q;
+  const int cnt = __syncthreads_count(root);
+  if (threadIdx.x == 0) blocks[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = cnt;
+}
+
+// blocks[n][0..nb) -> their exclusive scan, num[n] = their sum.  One block per image.
+__global__ __launch_bounds__(kChunk) void scan_roots_kernel(int* __restrict__ blocks, int nb, long long* __restrict__ num) {
+  __shared__ int wsum[kChunk / 64];
+  int* B = blocks + (size_t)blockIdx.x * nb;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int carry = 0;
+  for (int base = 0; base < nb; base += kChunk) {
+    const int i = base + t;
+    const int v = i < nb ? B[i] : 0;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int u = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += u;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < kChunk / 64; ++k) {
+      const int ws = wsum[k];
+      if (k < wave) before += ws;
+      total += ws;
+    }
+    if (i < nb) B[i] = carry + before + incl - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (t == 0) num[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(kChunk) void assign_roots_kernel(int* __restrict__ parent, const unsigned char* __restrict__ cls,
+                                                              const int* __restrict__ blocks, int P, int H, int W,
+                                                              long long* __restrict__ rows, int cap) {
+  __shared__ int wsum[kChunk / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long long q = (long long)blockIdx.x * kChunk + t;
+  const size_t img = (size_t)blockIdx.y * P;
+  const bool root = q < P && parent[img + q] == q;
+  const unsigned long long bits = __ballot(root);
+  if (lane == 0) wsum[wave] = (int)__popcll(bits);
+  __syncthreads();
+  if (!root) return;
+  int idx = blocks[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + (int)__popcll(bits & ((1ull << lane) - 1ull));
+  for (int k = 0; k < wave; ++k) idx += wsum[k];
+  parent[img + q] = -2 - idx;
+  if (idx < cap) {
+    long long* row = rows + ((size_t)blockIdx.y * cap + idx) * kRow;
+    row[0] = q;
+    row[1] = cls[img + q];
+    row[2] = 0;
+    row[3] = W;      // the box: mins start above, maxes below every coordinate
+    row[4] = H;
+    row[5] = 0;
+    row[6] = 0;
+    row[7] = 0;
+    row[8] = 0;
+    row[9] = 0;
+  }
+}
+
+// sum of the positions of the set bits of m
+__device__ __forceinline__ int bit_position_sum(unsigned m) {
+  return __popc(m & 0xAAAAAAAAu) + 2 * __popc(m & 0xCCCCCCCCu) + 4 * __popc(m & 0xF0F0F0F0u) + 8 * __popc(m & 0xFF00FF00u) +
+         16 * __popc(m & 0xFFFF0000u);
+}
+
+enum { kPixels, kSumX, kSumY, kPerimeter, kMinX, kMinY, kMaxX, kMaxY, kFields };
+
+__global__ __launch_bounds__(TILE* TILE) void accumulate_kernel(const int* __restrict__ parent, const unsigned char* __restrict__ cls,
+                                                                 int H, int W, long long* __restrict__ rows, int cap) {
+  __shared__ int key[kSlots];
+  __shared__ int acc[kFields][kSlots];
+  const int t = threadIdx.x, lane = t & 63;
+  const int tx = t & (TILE - 1), ty = t >> 5;
+  const int x = blockIdx.x * TILE + tx, y = blockIdx.y * TILE + ty;
+  const size_t img = (size_t)blockIdx.z * H * W;
+  const int* L = parent + img;
+  const unsigned char* C = cls + img;
+  key[t] = -1;
+#pragma unroll
+  for (int f = 0; f < kFields; ++f) acc[f][t] = (f == kMinX || f == kMinY) ? 0x7fffffff : (f == kMaxX || f == kMaxY ? -1 : 0);
+  __syncthreads();
+
+  int idx = -1;
+  bool dn = false, ds = false, dw = false, de = false;
+  if (x < W && y < H) {
+    const int p = y * W + x;
+    const int c = C[p];
+    if (c) {
+      int v = L[p];
+      while (v >= 0) v = L[v];            // up to the root, whose parent holds -2 - index
+      idx = -2 - v;
+      if (idx >= cap) idx = -1;
+    }
+    if (idx >= 0) {                       // sides whose neighbour has another label or lies outside the image
+      dn = y == 0 || C[p - W] != c;
+      ds = y == H - 1 || C[p + W] != c;
+      dw = x == 0 || C[p - 1] != c;
+      de = x == W - 1 || C[p + 1] != c;
+    }
+  }
+  const unsigned long long bn = __ballot(dn), bs = __ballot(ds), bw = __ballot(dw), be = __ballot(de);
+  const int x_base = blockIdx.x * TILE, y_lo = blockIdx.y * TILE + (ty & ~1);      // the wave's two rows: y_lo, y_lo + 1
+  unsigned long long todo = __ballot(idx >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int k = __shfl(idx, leader, 64);
+    const unsigned long long same = __ballot(idx == k) & todo;
+    if (lane == leader) {
+      const unsigned lo = (unsigned)same, hi = (unsigned)(same >> 32), both = lo | hi;
+      const int n_lo = __popc(lo), n_hi = __popc(hi);
+      unsigned h = ((unsigned)k * 2654435761u) >> 22;                               // 10 bits: kSlots
+      while (true) {
+        const int old = atomicCAS(&key[h], -1, k);
+        if (old == -1 || old == k) break;
+        h = (h + 1) & (kSlots - 1);
+      }
+      atomicAdd(&acc[kPixels][h], n_lo + n_hi);
+      atomicAdd(&acc[kSumX][h], (n_lo + n_hi) * x_base + bit_position_sum(lo) + bit_position_sum(hi));
+      atomicAdd(&acc[kSumY][h], n_lo * y_lo + n_hi * (y_lo + 1));
+      atomicAdd(&acc[kPerimeter][h], (int)(__popcll(same & bn) + __popcll(same & bs) + __popcll(same & bw) + __popcll(same & be)));
+      atomicMin(&acc[kMinX][h], x_base + (__ffs((int)both) - 1));
+      atomicMax(&acc[kMaxX][h], x_base + 31 - __clz((int)both));
+      atomicMin(&acc[kMinY][h], lo ? y_lo : y_lo + 1);
+      atomicMax(&acc[kMaxY][h], hi ? y_lo + 1 : y_lo);
+    }
+    todo &= ~same;
+  }
+  __syncthreads();
+  const int k = key[t];
+  if (k < 0) return;
+  unsigned long long* row = reinterpret_cast<unsigned long long*>(rows) + ((size_t)blockIdx.z * cap + k) * kRow;
+  atomicAdd(row + 2, (unsigned long long)acc[kPixels][t]);
+  atomicMin(row + 3, (unsigned long long)acc[kMinX][t]);
+  atomicMin(row + 4, (unsigned long long)acc[kMinY][t]);
+  atomicMax(row + 5, (unsigned long long)acc[kMaxX][t]);
+  atomicMax(row + 6, (unsigned long long)acc[kMaxY][t]);
+  atomicAdd(row + 7, (unsigned long long)acc[kSumX][t]);
+  atomicAdd(row + 8, (unsigned long long)acc[kSumY][t]);
+  if (acc[kPerimeter][t]) atomicAdd(row + 9, (unsigned long long)acc[kPerimeter][t]);
+}
+
+}  // namespace
+
+ZonesLayout zones_layout(int N, int H, int W) {
+  const size_t P = (size_t)H * W, nb = (P + kChunk - 1) / kChunk;
+  Carver ws;
+  const size_t parent = ws.take(4 * P * N), cls = ws.take(P * N), blocks = ws.take(4 * nb * N);
+  return {parent, cls, blocks, ws.offset};
+}
+
+hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, int W, long long* rows, int cap, long long* num,
+                              int* parent, unsigned char* cls, int* blocks, hipStream_t s) {
+  if (N < 1 || N > 65535 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)H * W > 0x7fffffffLL || cap < 1)
+    return hipErrorInvalidValue;
+  const int P = H * W, nb = (P + kChunk - 1) / kChunk;
+  const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, N);
+  if (labels_i64)
+    hipLaunchKernelGGL(zone_tile_kernel<long long>, tiles, dim3(TILE * TILE), 0, s, static_cast<const long long*>(labels), cls, parent,
+                       H, W);
+  else
+    hipLaunchKernelGGL(zone_tile_kernel<unsigned char>, tiles, dim3(TILE * TILE), 0, s, static_cast<const unsigned char*>(labels), cls,
+                       parent, H, W);
+  if (H > TILE)
+    hipLaunchKernelGGL(zone_border_rows_kernel, dim3((W + 255) / 256, (H - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
+  if (W > TILE)
+    hipLaunchKernelGGL(zone_border_cols_kernel, dim3((H + 255) / 256, (W - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
+  hipLaunchKernelGGL(count_roots_kernel, dim3(nb, N), dim3(kChunk), 0, s, parent, blocks, P);
+  hipLaunchKernelGGL(scan_roots_kernel, dim3(N), dim3(kChunk), 0, s, blocks, nb, num);
+  hipLaunchKernelGGL(assign_roots_kernel, dim3(nb, N), dim3(kChunk), 0, s, parent, cls, blocks, P, H, W, rows, cap);
+  hipLaunchKernelGGL(accumulate_kernel, tiles, dim3(TILE * TILE), 0, s, parent, cls, H, W, rows, cap);
+  return hipGetLastError();
+}
+
+}  // namespace nbc

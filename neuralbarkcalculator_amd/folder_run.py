@@ -137,6 +137,19 @@ def gather_rows(local_rows: np.ndarray, n_total: int, world: int, dist=None, dev
     return allrows[np.argsort(allrows[:, 0], kind="stable")]
 
 
+def gather_ragged(local_rows: np.ndarray, world: int, dist=None, device=None, width: int = 5) -> np.ndarray:
+    """``gather_rows`` for row sets whose per-rank length no rank can predict (several rows per image, or none, as the zone
+    rows of ``predict --zones``): one extra all_reduce of the largest per-rank count gives every rank the same ``cap``.  The
+    rows come back sorted by their first column, the global image index; the rows of one image keep their order."""
+    cap = len(local_rows)
+    if dist is not None and world > 1:
+        import torch
+        t = _on_wire(torch.tensor([cap], dtype=torch.int64), device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        cap = int(t.cpu()[0])
+    return gather_rows(np.asarray(local_rows, dtype=np.int64).reshape(-1, width), 0, world, dist, device, cap=cap, width=width)
+
+
 def resolve_arch(arch: str, state_dict=None, dist=None, device=None) -> str:
     """The network a folder driver runs (``--arch``).  ``"auto"``: rank 0, the one rank that read the checkpoint, picks
     the architecture whose key set ``state_dict`` matches (``model.arch_of_state_dict``) and broadcasts its NBC_ARCH_*
@@ -263,6 +276,22 @@ def check_dropout_arguments(draws, p=None, seed=None, compare=None, arch: str = 
         raise ValueError("--dropout_draws runs the network: it cannot go with --only_preprocess")
     if arch != "auto":
         check_dropout_arch(arch)
+
+
+ZONES_MAX_CAP = 65536
+
+
+def check_zones_arguments(zones: bool, zones_cap=None, only_preprocess: bool = False) -> None:
+    """``ValueError`` for what ``--zones`` and ``--zones_cap`` refuse before any device is touched: a cap without the flag, the
+    flag with ``--only_preprocess`` (there is no label map to inventory), a cap outside 1..65536."""
+    if not zones:
+        if zones_cap is not None:
+            raise ValueError("--zones_cap needs --zones")
+        return
+    if only_preprocess:
+        raise ValueError("--zones inventories the label maps: it is refused with --only_preprocess")
+    if zones_cap is not None and not 1 <= int(zones_cap) <= ZONES_MAX_CAP:
+        raise ValueError("--zones_cap must lie in 1..%d" % ZONES_MAX_CAP)
 
 
 def check_dropout_arch(arch: str) -> None:
@@ -711,6 +740,16 @@ def add_shared_arguments(ap) -> None:
     ap.add_argument("--stats", metavar="PATH", default=None,
                     help="take mean and std from this JSON (results/dataset_stats.json of python -m neuralbarkcalculator_amd.stats) "
                          "instead of --mean / --std")
+
+
+def add_zones_arguments(ap) -> None:
+    """``--zones`` and ``--zones_cap`` of ``predict`` (``check_zones_arguments`` holds their rules)."""
+    ap.add_argument("--zones", action="store_true",
+                    help="also inventory the bark zones and nodes of every label map (8-connected components per class, on the "
+                         "device) and write results/zones.csv, zones_summary.csv and zones_summary.json")
+    ap.add_argument("--zones_cap", type=int, default=None, metavar="ROWS",
+                    help="with --zones: zone rows per image the device pass keeps (default 1024); an image with more zones is "
+                         "inventoried on the host from its label map instead")
 
 
 def add_dropout_arguments(ap) -> None:

@@ -216,6 +216,7 @@ class FCNResNet50:
         self._lovasz_ws: Optional[torch.Tensor] = None     # nbc_lovasz_softmax's workspace (grows, never shrinks)
         self._pixel_ce_ws: Optional[torch.Tensor] = None   # nbc_pixel_cross_entropy's, likewise
         self._dropout_ws: Optional[torch.Tensor] = None    # nbc_dropout_draws', likewise
+        self._zones_ws: Optional[torch.Tensor] = None      # nbc_label_zones', likewise
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self.device: Optional[torch.device] = None
         self.training = False
@@ -359,6 +360,36 @@ class FCNResNet50:
                                                         n, h, w, int(min_pixels), int(bool(exclude_nodes)),
                                                         counts.data_ptr(), cur.cuda_stream), "nbc_remove_small_zones")
         return labels, counts
+
+    def label_zones(self, labels: torch.Tensor, cap: int = 1024) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The zones of label maps on the device (nbc_label_zones; include/nbc.h, csrc/zones.hip): the 8-connected components
+        of each class in {1, 2}, one row of ten integers per zone (``zones.ZONE_FIELDS``: first pixel ``y * W + x``, class,
+        pixels, inclusive box x0 y0 x1 y1, sum_x, sum_y, perimeter), sorted by first pixel.  ``labels``: contiguous uint8 or
+        int64 ``[N,H,W]`` / ``[H,W]`` on this model's device, read only.  Runs on the current stream; the workspace (5 bytes
+        per pixel) is cached on this object and only grows.  Returns ``(rows int64 [N,cap,10], num int64 [N])``: ``num[n]`` is
+        the number of zones of image n, also when it exceeds ``cap``; rows ``min(num[n], cap)`` onwards are not written.
+        Equal to ``zones.zones_cpu``, integer for integer; works for every architecture, since it only sees labels."""
+        self._require_ctx()
+        self._check_labels(labels)
+        if labels.dim() not in (2, 3) or labels.numel() == 0:
+            raise ValueError("labels must be a non-empty [H,W] or [N,H,W]")
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError("cap must be at least 1")
+        n = 1 if labels.dim() == 2 else int(labels.shape[0])
+        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        need = int(self._lib.nbc_zones_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_label_zones refuses a [%d,%d,%d] batch (N <= 65535, H, W <= 65535, H * W < 2^31)" % (n, h, w))
+        rows = torch.empty((n, cap, _lib.ZONE_ROW), dtype=torch.int64, device=self.device)
+        num = torch.empty((n,), dtype=torch.int64, device=self.device)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_zones_ws", need, cur)
+            _lib.check(self._lib.nbc_label_zones(self._ctx, labels.data_ptr(),
+                                                 _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8, n, h, w,
+                                                 rows.data_ptr(), cap, num.data_ptr(), ws.data_ptr(), ws.numel(), cur.cuda_stream),
+                       "nbc_label_zones")
+        return rows, num
 
     def confusion(self, labels: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """Per-image 3x3 confusion counts on the device (nbc_confusion): the pixel counting behind the evaluation loop's
@@ -885,6 +916,7 @@ class FCNResNet50:
         self._lovasz_ws = None
         self._pixel_ce_ws = None
         self._dropout_ws = None
+        self._zones_ws = None
         self._last_shape = None
 
     def __del__(self):

@@ -337,6 +337,31 @@ def write_dropout_report(results_dir: str, items, allrows, alld, draws: int, p: 
     return summary
 
 
+def write_zones_report(results_dir: str, items, allrows, allz, cap: int, host_fallbacks: int) -> dict:
+    """``zones.csv``, ``zones_summary.csv`` (tab separated, like ``final_stats.csv``) and ``zones_summary.json`` from the
+    gathered rows: ``allrows`` as ``final_stats.csv`` is written from (one per image: its size), ``allz`` the
+    ``(global_idx, 10 zone fields)`` rows of every zone, an image's rows in first-pixel order.  Returns the summary."""
+    import json
+    from . import zones as zn
+    allz = np.asarray(allz, dtype=np.int64).reshape(-1, 1 + zn.ZONE_ROW)
+    starts = np.searchsorted(allz[:, 0], [int(g[0]) for g in allrows], side="left")
+    ends = np.searchsorted(allz[:, 0], [int(g[0]) for g in allrows], side="right")
+    table, summary, figures = [list(zn.ZONE_COLUMNS)], [list(zn.SUMMARY_COLUMNS)], []
+    for g, a, b in zip(allrows, starts, ends):
+        d, h, w, z = items[int(g[0])], int(g[1]), int(g[2]), allz[a:b, 1:]
+        table += zn.zone_rows(d["name"], d["wood"], h, w, z)
+        summary += zn.summary_rows(d["name"], d["wood"], h, w, z)
+        figures.append(zn.image_figures(h, w, z))
+    for name, rows_ in (("zones.csv", table), ("zones_summary.csv", summary)):
+        with open(os.path.join(results_dir, name), "w") as f:
+            csv.writer(f, delimiter="\t").writerows(rows_)
+    doc = zn.folder_summary(figures, cap, host_fallbacks)
+    with open(os.path.join(results_dir, "zones_summary.json"), "w") as f:
+        json.dump(doc, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return doc
+
+
 def label_png(labels: np.ndarray) -> np.ndarray:
     """models.py:349-353: uint8 map with Bark = 127, Node = 255."""
     out = np.zeros(labels.shape, dtype=np.uint8)
@@ -371,7 +396,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
-                   dropout_compare: str = None, dropout_votes: bool = False) -> dict:
+                   dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -406,14 +431,25 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     the label PNGs are), ``results/dropout_support/<wood>/<name>`` (grey, 255 = every draw agrees),
     ``results/dropout_votes.csv`` (``folder_run.vote_report``, with the pixels on which the mask differs from the label PNG)
     and a ``"votes"`` entry in ``dropout_summary.json``; every other file stays byte for byte what it is without the flag.
+    ``zones``: after ``predict_labels``, on the same stream and model object, ``FCNResNet50.label_zones`` inventories the
+    final label maps (after ``remove_small_zones`` and the ``exclude_nodes`` remap): up to ``zones_cap`` (default 1024) rows
+    per image ride back beside the labels; an image with more zones gets its rows from ``zones.zones_cpu`` on the label plane
+    already on the host.  Rank 0 writes ``results/zones.csv`` (a row per zone), ``results/zones_summary.csv`` (a row per
+    image) and ``results/zones_summary.json`` (``write_zones_report``); every other file stays byte for byte what it is
+    without the flag.  The returned dict gains ``zones_host_fallbacks``, this rank's images that took the host path, and ``zones_report_s``, the
+    seconds the gather and (on rank 0) the three files took after the loop.
     Returns timing / count statistics of this rank."""
     import time
     import torch
     from PIL import Image
+    from . import zones as zn
     from .model import FCNResNet50
     from .pngio import write_png
     D = int(dropout_draws or 0)
     V = bool(dropout_votes)
+    Z = bool(zones)
+    folder_run.check_zones_arguments(Z, zones_cap)   # refusals first: nothing has touched a device yet
+    ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
     old_stats = None
     if V and not D:
         raise ValueError("--dropout_votes needs --dropout_draws")
@@ -428,6 +464,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel)
         if small_zones:
             m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if Z:                                        # and label_zones' (5 bytes per pixel)
+            m.label_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev), cap=ZCAP)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, lambda root_: generate_folders(root_, votes=V), warm,
                         normalization=normalization)
     if D:
@@ -445,6 +483,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     drows = np.zeros((len(mine), 1 + 3 * D), dtype=np.int64)     # (global_idx, D x 3 counts) of the Dropout draws
     VROW = 2 + folder_run.VOTE_STATS
     vrows = np.zeros((len(mine), VROW), dtype=np.int64)          # (global_idx, 10 vote statistics, changed pixels)
+    zrows = {}                                       # k -> the image's zone rows int64 [zones, 10] (--zones)
+    zfallbacks = []                                  # the k whose rows came from the host: more zones than ZCAP
     resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
     lvl_proc, lvl_lab = _png_level("processed"), _png_level("labels")
 
@@ -472,8 +512,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2, draws=None, votes=None):
-        """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row)."""
+    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None):
+        """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row; + the
+        zone rows: ``zone`` = (the device's rows, or None when the image has more zones than the cap: the host computes them)."""
         d = items[mine[k]]
         t0 = clock()
         path = os.path.join(root, "results", "outputs", d["wood"], d["name"])
@@ -490,6 +531,14 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                 write_png(vpath, img, lvl_lab)
             vrows[k, 0], vrows[k, 1:-1], vrows[k, -1] = mine[k], vstats, int(np.count_nonzero(vlab != lab))
         prof["pool.write_labels"] += clock() - t0
+        if zone is not None:
+            t1 = clock()
+            if zone[0] is None:
+                zfallbacks.append(k)
+                zrows[k] = zn.zones_cpu(lab)[0]
+            else:
+                zrows[k] = zone[0]
+            prof["pool.zones"] += clock() - t1
 
     # the result ring, one slot per staging slot: labels + counts coming back (pinned once for the largest batch)
     full = batch * target_size * target_size
@@ -499,6 +548,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     # the votes' slots: the mask and the support plane, one after the other, and the ten statistics per image
     vring = [(torch.empty(2 * full, dtype=torch.uint8).pin_memory(),
               torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory()) for _ in range(r.depth)] if V else None
+    # the zones' slots: ZCAP rows per image and the zone counts
+    zring = [(torch.empty((batch, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(), torch.empty(batch, dtype=torch.int64).pin_memory())
+             for _ in range(r.depth)] if Z else None
     tuned = set()
 
     def launch(slot, sid, part, x):
@@ -513,6 +565,13 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                                             small_zones=small_zones)   # models.py:269-276 on the device
         ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
         ring[slot][1][:n].copy_(counts, non_blocking=True)
+        if Z:                                        # the labels are final here: after remove_small_zones and the remap
+            if zring[slot][1].shape[0] < n:
+                zring[slot] = (torch.empty((n, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(),
+                               torch.empty(n, dtype=torch.int64).pin_memory())
+            zr, znum = mdl.label_zones(labels, cap=ZCAP)
+            zring[slot][0][:n].copy_(zr, non_blocking=True)
+            zring[slot][1][:n].copy_(znum, non_blocking=True)
         if D:                                        # the draws read the features this forward left, on the same stream
             if dring[slot].numel() < D * n * 3:
                 dring[slot] = torch.empty(D * n * 3, dtype=torch.int64).pin_memory()
@@ -535,15 +594,17 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         lab_host, cnt_host = ring[slot]
         labs = lab_host[: n * h * w].numpy().reshape(n, h, w).copy()
         cnts = cnt_host[:n].numpy().copy()
-        if D:
-            dc = dring[slot][: D * n * 3].numpy().reshape(D, n, 3).copy()
-            if V:
-                planes = vring[slot][0][: 2 * n * h * w].numpy().reshape(2, n, h, w).copy()
-                vst = vring[slot][1][:n].numpy().copy()
-                return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j], (planes[0, j], planes[1, j], vst[j]))
-                        for j, k in enumerate(part)]
-            return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j]) for j, k in enumerate(part)]
-        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2])) for j, k in enumerate(part)]
+        dc = dring[slot][: D * n * 3].numpy().reshape(D, n, 3).copy() if D else None
+        votes = zone = [None] * n
+        if V:
+            planes = vring[slot][0][: 2 * n * h * w].numpy().reshape(2, n, h, w).copy()
+            vst = vring[slot][1][:n].numpy().copy()
+            votes = [(planes[0, j], planes[1, j], vst[j]) for j in range(n)]
+        if Z:                                        # (rows,) per image; (None,) = more zones than the cap: the host's turn
+            znum = zring[slot][1][:n].numpy()
+            zone = [(zring[slot][0][j, :int(znum[j])].numpy().copy() if znum[j] <= ZCAP else None,) for j in range(n)]
+        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j])
+                for j, k in enumerate(part)]
 
     def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
         for path in label_paths:                     # must not leave them behind (the processed/ images do not depend on
@@ -568,8 +629,18 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if r.rank == 0:
             write_dropout_report(os.path.join(root, "results"), items, allrows, alld, D, dropout_p, dropout_seed, r.precision,
                                  bn_stats, old_stats, dropout_compare, allv)
+    extra = {}
+    if Z:                                            # (global_idx, 10 zone fields) rows, an image's rows together and in order
+        t_report = clock()
+        local = [np.concatenate([np.full((len(zrows[k]), 1), mine[k], dtype=np.int64), zrows[k]], axis=1) for k in sorted(zrows)]
+        local = np.concatenate(local) if local else np.zeros((0, 1 + zn.ZONE_ROW), dtype=np.int64)
+        allz = folder_run.gather_ragged(local, r.world, r.dist, r.wire_dev, width=1 + zn.ZONE_ROW)
+        fb = folder_run.gather(r, np.array([[mine[k]] for k in sorted(zfallbacks)], dtype=np.int64).reshape(-1, 1), 1)
+        if r.rank == 0:
+            write_zones_report(os.path.join(root, "results"), items, allrows, allz, ZCAP, len(fb))
+        extra.update(zones_host_fallbacks=len(zfallbacks), zones_report_s=clock() - t_report)
     return dict(folder_run.finish(r), host_workers=r.workers, distinct_shapes=len(r.shape_count),
-                autotuned_shapes=len({k for _, k in tuned}))
+                autotuned_shapes=len({k for _, k in tuned}), **extra)
 
 
 def main(argv=None):
@@ -584,6 +655,7 @@ def main(argv=None):
                     help="measure the conv tile shapes once per distinct full-batch image shape (0.5-0.9 s each) instead of the default choice")
     folder_run.add_shared_arguments(ap)
     folder_run.add_dropout_arguments(ap)
+    folder_run.add_zones_arguments(ap)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
@@ -592,6 +664,7 @@ def main(argv=None):
                                            args.only_preprocess, args.dropout_votes)
         if args.dropout_compare is not None:
             folder_run.read_shipped_stats(args.dropout_compare)
+        folder_run.check_zones_arguments(args.zones, args.zones_cap, args.only_preprocess)
     except ValueError as e:
         ap.error(str(e))
     if not args.device.startswith("cuda"):
@@ -610,6 +683,8 @@ def main(argv=None):
     if args.dropout_draws:
         kw.update(dropout_draws=args.dropout_draws, dropout_p=0.1 if args.dropout_p is None else args.dropout_p,
                   dropout_seed=args.dropout_seed or 0, dropout_compare=args.dropout_compare, dropout_votes=args.dropout_votes)
+    if args.zones:
+        kw.update(zones=True, zones_cap=args.zones_cap)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if int(os.environ.get("RANK", "0")) == 0:
