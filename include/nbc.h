@@ -573,6 +573,41 @@ size_t nbc_zones_workspace_bytes(int N, int H, int W);
 int nbc_label_zones(nbc_ctx* ctx, const void* labels_dev, int labels_dtype, int N, int H, int W,
                     int64_t* rows_dev, int cap, int64_t* num_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
 
+/* ---- output zones against target zones ----------------------------------------------------------
+ * Which zone of a label map is which zone of its labelled mask, and how well they overlap: what the per-pixel metrics of
+ * the evaluation hide (two nodes reported where the mask has one, every small node missed, three nodes glued into one).  The
+ * reference has no such code; the host restatement is zones.match_cpu (scipy.ndimage.label per class, a zone-index plane
+ * per map, numpy.unique on the joined key), the kernels csrc/zone_match.hip.
+ *
+ * out_rows_dev / out_num_dev   what nbc_label_zones gives for labels_dev: same rows, same order, same cap behaviour
+ * tgt_rows_dev / tgt_num_dev   the same of the target's class map, the class of a grey level being nbc_confusion's
+ *                              (0..63 -> 0, 64..191 -> 1, 192..255 -> 2); both int64 [N, cap, NBC_ZONE_ROW] / int64 [N]
+ * pair_rows_dev  int64 [N, pair_cap, NBC_ZONE_PAIR_ROW], pair_num_dev int64 [N].
+ * Pair row: { output zone index, target zone index, pixels }.  An index is the zone's position among its map's zones in
+ * first-pixel order (the row number in out_rows / tgt_rows; valid for every zone, also at or above cap).  pixels: the pixels
+ * that lie in both zones, > 0.  Only zones of the same class share pixels.  The rows of an image are sorted by (output index,
+ * target index).  pair_num_dev[n] = the number of distinct pairs of image n when that is <= pair_cap; otherwise exactly
+ * pair_cap + 1, and the image's pair_cap rows are unspecified.  Nothing outside an image's own rows is ever written, and
+ * rows pair_num[n] onwards are not written when pair_num[n] <= pair_cap.
+ * labels_dev / target_grey_dev  uint8 or int64 [N,H,W] / uint8 [N,H,W]; read, never written
+ * workspace_dev  at least nbc_zone_match_workspace_bytes(N, H, W, pair_cap) bytes, 256-byte aligned; contents scratch
+ * No loop of the pass depends on the data for its end: hash probes are bounded by their table's size, and an image with
+ * more than pair_cap pairs stops inserting.  Integer counts and a sorted output: an image's three outputs are the same alone,
+ * in any batch, on any stream and from run to run.  Runs on hip_stream (on the context's device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer, the shapes, cap and labels_dtype nbc_label_zones refuses, pair_cap
+ * outside 1..NBC_ZONE_PAIRS_MAX_CAP, a workspace that is too small or not 256-byte aligned. */
+#define NBC_ZONE_PAIR_ROW 3
+#define NBC_ZONE_PAIRS_MAX_CAP 4096   /* what the sort kernel's LDS holds: 4096 x (8-byte key + 4-byte count) = 48 KiB */
+/* With P = H * W, T = the power of two >= 2 * pair_cap (at least 2) and A(x) = x rounded up to a multiple of 256:
+ *   2 nbc_zones_workspace_bytes(N, H, W) + A(N P) + A(8 N T) + A(4 N T) + A(4 N)
+ * (both labellings, the target's class map, and per image the pair table's keys and counts and a claim counter): 11 bytes
+ * per pixel and a little.  0 for a shape or a pair_cap that nbc_match_zones refuses. */
+size_t nbc_zone_match_workspace_bytes(int N, int H, int W, int pair_cap);
+int nbc_match_zones(nbc_ctx* ctx, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H, int W,
+                    int64_t* out_rows_dev, int64_t* out_num_dev, int64_t* tgt_rows_dev, int64_t* tgt_num_dev, int cap,
+                    int64_t* pair_rows_dev, int64_t* pair_num_dev, int pair_cap, void* workspace_dev, size_t workspace_bytes,
+                    void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

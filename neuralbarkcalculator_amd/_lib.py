@@ -23,6 +23,8 @@ ARCH_FCN_EFFICIENTNET_B0, ARCH_DEEPLABV3_EFFICIENTNET_B0 = 16, 24   # + n, n = 0
 BN_RUNNING, BN_PER_IMAGE = 0, 1                     # NBC_BN_*
 VOTE_STATS = 10                                     # NBC_VOTE_STATS
 ZONE_ROW = 10                                       # NBC_ZONE_ROW
+ZONE_PAIR_ROW = 3                                   # NBC_ZONE_PAIR_ROW
+PAIRS_MAX_CAP = 4096                                # NBC_ZONE_PAIRS_MAX_CAP
 
 
 class NbcTensor(C.Structure):
@@ -123,6 +125,10 @@ SIGNATURES = {
     "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),
+    "nbc_zone_match_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nbc_match_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
     "nbc_resize_cubic_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nbc_preprocess_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p]),

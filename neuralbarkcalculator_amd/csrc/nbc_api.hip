@@ -1034,6 +1034,36 @@ int nbc_label_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, int N,
   return NBC_OK;
 }
 
+static bool pair_cap_ok(int pair_cap) { return pair_cap >= 1 && pair_cap <= NBC_ZONE_PAIRS_MAX_CAP; }
+
+size_t nbc_zone_match_workspace_bytes(int N, int H, int W, int pair_cap) {
+  return zones_shape_ok(N, H, W) && pair_cap_ok(pair_cap) ? zone_match_layout(N, H, W, pair_cap).total : 0;
+}
+
+int nbc_match_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H, int W,
+                    int64_t* out_rows_dev, int64_t* out_num_dev, int64_t* tgt_rows_dev, int64_t* tgt_num_dev, int cap,
+                    int64_t* pair_rows_dev, int64_t* pair_num_dev, int pair_cap, void* workspace_dev, size_t workspace_bytes,
+                    void* hip_stream) {
+  constexpr const char* kWho = "nbc_match_zones";
+  if (!c || !labels_dev || !target_grey_dev || !out_rows_dev || !out_num_dev || !tgt_rows_dev || !tgt_num_dev || !pair_rows_dev ||
+      !pair_num_dev || !workspace_dev)
+    return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!zones_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
+  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
+  if (!pair_cap_ok(pair_cap))
+    return fail(kWho, NBC_ERR_INVALID, "pair_cap must lie in 1.." + std::to_string(NBC_ZONE_PAIRS_MAX_CAP));
+  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, zone_match_layout(N, H, W, pair_cap).total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  NBC_HIP(launch_match_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, target_grey_dev, N, H, W,
+                             reinterpret_cast<long long*>(out_rows_dev), reinterpret_cast<long long*>(out_num_dev),
+                             reinterpret_cast<long long*>(tgt_rows_dev), reinterpret_cast<long long*>(tgt_num_dev), cap,
+                             reinterpret_cast<long long*>(pair_rows_dev), reinterpret_cast<long long*>(pair_num_dev), pair_cap,
+                             static_cast<unsigned char*>(workspace_dev), static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
+}
+
 size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
   if (N < 1 || H < 8 || W < 8 || H > 65535 || draws_per_pass < 1 || (long long)H * W > 0x7fffffffLL) return 0;
   const unsigned long long I = (unsigned long long)draws_per_pass * (unsigned long long)N;

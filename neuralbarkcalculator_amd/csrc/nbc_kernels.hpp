@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, aspp.hip, bn_stats.hip and
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, aspp.hip, bn_stats.hip and
 // efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
 // convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
@@ -188,6 +188,20 @@ struct ZonesLayout {
 ZonesLayout zones_layout(int N, int H, int W);
 hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, int W, long long* rows, int cap, long long* num,
                               int* parent, unsigned char* cls, int* blocks, hipStream_t s);
+// Output zones against target zones (zone_match.hip; the contract: nbc_match_zones in include/nbc.h): both inventories as
+// launch_label_zones gives them, and the pair rows int64 [N][pair_cap][3], pair_num int64 [N].  zone_match_layout: the regions
+// of the workspace (byte offsets, each 256-byte aligned) and its size -- two zones_layout regions (`zones` holds the offsets
+// inside each), the target's class map, and per image a table of `table` slots (a power of two >= 2 * pair_cap): 64-bit keys,
+// 32-bit counts, and a claim counter.  pair_cap in 1..NBC_ZONE_PAIRS_MAX_CAP; the shapes of launch_label_zones.
+struct ZoneMatchLayout {
+  ZonesLayout zones;
+  size_t out, tgt, tgt_cls, keys, counts, claimed, total;
+  int table;
+};
+ZoneMatchLayout zone_match_layout(int N, int H, int W, int pair_cap);
+hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
+                              long long* out_rows, long long* out_num, long long* tgt_rows, long long* tgt_num, int cap,
+                              long long* pair_rows, long long* pair_num, int pair_cap, unsigned char* ws, hipStream_t s);
 // Preprocessor (models.py:191-203): uint8 HWC [H,W,3] -> ToTensor -> skimage cubic resize with reflected borders,
 // clipped to the input range -> any of: float32 HWC [out_h,out_w,3]; its uint8 form as imsave writes it; per output
 // row the number of pixels trim_black counts as lit.  minmax: two uints of scratch.

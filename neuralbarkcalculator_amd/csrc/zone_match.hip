@@ -1,0 +1,242 @@
+// Which output zone is which target zone (nbc_match_zones, include/nbc.h): the zones of the label maps and of the grey duals'
+// class maps, and for every (output zone, target zone) pair of the same class that shares a pixel, the number of shared pixels.
+// Integer work, exact against the host restatement (neuralbarkcalculator_amd/zones.py: match_cpu).
+//
+// Both inventories are zones.hip's (launch_label_zones, twice, on two parent / class planes); the target's class map comes
+// from the grey levels by nbc_confusion's rule (target_class, reduce.hpp).  What launch_label_zones leaves behind is a parent
+// plane whose roots hold the code -2 - index (the zone's position in first-pixel order, valid also at or above cap).  Then
+//   target_class_plane   grey u8 -> class u8, the "labels" of the second labelling
+//   pair_clear           the per-image tables: keys empty, counts 0, the claim counters 0
+//   pair_accumulate      one 32x32 tile per block, modelled on zones.hip's accumulate: every pixel with cls_out == cls_tgt != 0
+//                        walks both parent planes to the two indices; a wave reduces its two rows per distinct pair from
+//                        ballots; its leader adds the count into an LDS hash slot of the tile (at most 512 distinct pairs meet
+//                        a tile: two same-class pixels of different pairs cannot be 8-neighbours, so a 2x2 block holds at most
+//                        one pair per class); every used slot makes one insertion into the image's table (open addressing,
+//                        the 64-bit key claimed by CAS, the count added atomically)
+//   pair_sort            one block per image: the claimed slots into LDS, a bitonic sort by key, the rows and pair_num
+// Termination does not depend on the data: every probe loop is bounded by its table's size; the image's claim counter stops
+// insertions once more than pair_cap keys are claimed; a full or overflowed table ends as pair_cap + 1; the parent walks end
+// for accumulate's reason (a parent's index is smaller than its child's, a root holds a negative code).
+// Counts are integer sums and the rows are sorted: an image's outputs are the same alone, in any batch, on any stream.
+#include "nbc_kernels.hpp"
+#include "reduce.hpp"
+#include "union_find.hpp"
+
+namespace nbc {
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr int TILE = kLabelTile;
+constexpr int kThreads = TILE * TILE;
+constexpr int kSlots = TILE * TILE;           // LDS hash slots per tile, twice the 512 pairs that can meet one
+constexpr int kPairRow = NBC_ZONE_PAIR_ROW;
+constexpr u64 kEmpty = ~0ull;                 // no key: both indices are below 2^31
+constexpr u64 kGolden = 0x9E3779B97F4A7C15ull;
+
+__global__ __launch_bounds__(256) void target_class_plane_kernel(const unsigned char* __restrict__ grey, unsigned char* __restrict__ cls,
+                                                                 size_t bytes) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // whole words where the grey plane starts on one (cls is a region of the workspace: 256-byte aligned), bytes otherwise
+  const size_t words = (reinterpret_cast<uintptr_t>(grey) & 3u) ? 0 : bytes / 4;
+  for (size_t i = g; i < words; i += stride) {
+    const unsigned v = reinterpret_cast<const unsigned*>(grey)[i];
+    reinterpret_cast<unsigned*>(cls)[i] = target_class(v & 255u) | (target_class((v >> 8) & 255u) << 8) |
+                                          (target_class((v >> 16) & 255u) << 16) | (target_class(v >> 24) << 24);
+  }
+  for (size_t i = words * 4 + g; i < bytes; i += stride) cls[i] = (unsigned char)target_class(grey[i]);
+}
+
+__global__ __launch_bounds__(256) void pair_clear_kernel(u64* __restrict__ keys, unsigned* __restrict__ counts, int* __restrict__ claimed,
+                                                         size_t slots, int N) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = g; i < slots; i += stride) {
+    keys[i] = kEmpty;
+    counts[i] = 0u;
+  }
+  if (g < (size_t)N) claimed[g] = 0;
+}
+
+__global__ __launch_bounds__(kThreads) void pair_accumulate_kernel(const int* __restrict__ parent_out, const unsigned char* __restrict__ cls_out,
+                                                                   const int* __restrict__ parent_tgt, const unsigned char* __restrict__ cls_tgt,
+                                                                   int H, int W, u64* __restrict__ keys, unsigned* __restrict__ counts,
+                                                                   int* __restrict__ claimed, int table, int table_shift, int pair_cap) {
+  __shared__ u64 skey[kSlots];
+  __shared__ int scnt[kSlots];
+  const int t = threadIdx.x, lane = t & 63;
+  const int x = blockIdx.x * TILE + (t & (TILE - 1)), y = blockIdx.y * TILE + (t >> 5);
+  const size_t img = (size_t)blockIdx.z * H * W;
+  int* const mine = claimed + blockIdx.z;
+  skey[t] = kEmpty;
+  scnt[t] = 0;
+  __syncthreads();
+
+  int io = -1, it = -1;
+  if (x < W && y < H) {
+    const int p = y * W + x;
+    const int c = cls_out[img + p];
+    if (c && c == cls_tgt[img + p]) {
+      const int* Lo = parent_out + img;
+      const int* Lt = parent_tgt + img;
+      int v = Lo[p];
+      while (v >= 0) v = Lo[v];           // up to the root, whose parent holds -2 - index
+      io = -2 - v;
+      v = Lt[p];
+      while (v >= 0) v = Lt[v];
+      it = -2 - v;
+    }
+  }
+  u64 todo = __ballot(io >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int ko = __shfl(io, leader, 64), kt = __shfl(it, leader, 64);
+    const u64 same = __ballot(io == ko && it == kt) & todo;
+    if (lane == leader) {
+      const u64 key = ((u64)(unsigned)ko << 32) | (u64)(unsigned)kt;
+      unsigned h = (unsigned)((key * kGolden) >> 54);                            // 10 bits: kSlots
+      int probe = 0;
+      for (; probe < kSlots; ++probe) {
+        const u64 old = atomicCAS(&skey[h], kEmpty, key);
+        if (old == kEmpty || old == key) {
+          atomicAdd(&scnt[h], (int)__popcll(same));
+          break;
+        }
+        h = (h + 1) & (kSlots - 1);
+      }
+      if (probe == kSlots) atomicMax(mine, pair_cap + 1);                        // cannot happen (512 pairs per tile); no spin if it did
+    }
+    todo &= ~same;
+  }
+  __syncthreads();
+  const u64 key = skey[t];
+  if (key == kEmpty) return;
+  u64* K = keys + (size_t)blockIdx.z * table;
+  unsigned* V = counts + (size_t)blockIdx.z * table;
+  unsigned h = (unsigned)((key * kGolden) >> table_shift);
+  for (int probe = 0; probe < table; ++probe) {
+    if (*reinterpret_cast<volatile int*>(mine) > pair_cap) return;               // the image has overflowed: its rows are void
+    const u64 old = atomicCAS(&K[h], kEmpty, key);
+    if (old == kEmpty) atomicAdd(mine, 1);
+    if (old == kEmpty || old == key) {
+      atomicAdd(&V[h], (unsigned)scnt[t]);
+      return;
+    }
+    h = (h + 1) & (unsigned)(table - 1);
+  }
+  atomicMax(mine, pair_cap + 1);                                                 // a full table
+}
+
+__global__ __launch_bounds__(kThreads) void pair_sort_kernel(const u64* __restrict__ keys, const unsigned* __restrict__ counts,
+                                                             const int* __restrict__ claimed, int table, int pair_cap,
+                                                             long long* __restrict__ rows, long long* __restrict__ num) {
+  __shared__ u64 sk[NBC_ZONE_PAIRS_MAX_CAP];
+  __shared__ unsigned sv[NBC_ZONE_PAIRS_MAX_CAP];
+  __shared__ int fill;
+  const int t = threadIdx.x;
+  const int c = claimed[blockIdx.x];
+  if (c > pair_cap) {                                     // uniform over the block
+    if (t == 0) num[blockIdx.x] = (long long)pair_cap + 1;
+    return;
+  }
+  int m = 1;
+  while (m < c) m <<= 1;                                  // c <= pair_cap <= NBC_ZONE_PAIRS_MAX_CAP, a power of two
+  for (int i = t; i < m; i += kThreads) {
+    sk[i] = kEmpty;                                       // sorts behind every key
+    sv[i] = 0u;
+  }
+  if (t == 0) fill = 0;
+  __syncthreads();
+  const u64* K = keys + (size_t)blockIdx.x * table;
+  const unsigned* V = counts + (size_t)blockIdx.x * table;
+  for (int i = t; i < table; i += kThreads) {
+    const u64 k = K[i];
+    if (k != kEmpty) {
+      const int j = atomicAdd(&fill, 1);
+      if (j < m) {
+        sk[j] = k;
+        sv[j] = V[i];
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = 2; k <= m; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = t; i < m; i += kThreads) {
+        const int o = i ^ j;
+        if (o > i) {
+          const u64 a = sk[i], b = sk[o];
+          if ((a > b) == ((i & k) == 0)) {
+            sk[i] = b;
+            sk[o] = a;
+            const unsigned va = sv[i];
+            sv[i] = sv[o];
+            sv[o] = va;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  long long* R = rows + (size_t)blockIdx.x * pair_cap * kPairRow;
+  for (int i = t; i < c; i += kThreads) {
+    const u64 k = sk[i];
+    R[(size_t)i * kPairRow + 0] = (long long)(k >> 32);
+    R[(size_t)i * kPairRow + 1] = (long long)(k & 0xffffffffull);
+    R[(size_t)i * kPairRow + 2] = (long long)sv[i];
+  }
+  if (t == 0) num[blockIdx.x] = c;
+}
+
+}  // namespace
+
+ZoneMatchLayout zone_match_layout(int N, int H, int W, int pair_cap) {
+  const ZonesLayout z = zones_layout(N, H, W);            // its total is a multiple of 256
+  int table = 2;
+  while (table < 2 * pair_cap) table <<= 1;
+  Carver ws;
+  ZoneMatchLayout lay;
+  lay.zones = z;
+  lay.out = ws.take(z.total);
+  lay.tgt = ws.take(z.total);
+  lay.tgt_cls = ws.take((size_t)N * H * W);
+  lay.keys = ws.take(8 * (size_t)N * table);
+  lay.counts = ws.take(4 * (size_t)N * table);
+  lay.claimed = ws.take(4 * (size_t)N);
+  lay.total = ws.offset;
+  lay.table = table;
+  return lay;
+}
+
+hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
+                              long long* out_rows, long long* out_num, long long* tgt_rows, long long* tgt_num, int cap,
+                              long long* pair_rows, long long* pair_num, int pair_cap, unsigned char* ws, hipStream_t s) {
+  if (pair_cap < 1 || pair_cap > NBC_ZONE_PAIRS_MAX_CAP) return hipErrorInvalidValue;
+  const ZoneMatchLayout lay = zone_match_layout(N, H, W, pair_cap);
+  const ZonesLayout& z = lay.zones;
+  int* parent_out = reinterpret_cast<int*>(ws + lay.out + z.parent);
+  int* parent_tgt = reinterpret_cast<int*>(ws + lay.tgt + z.parent);
+  unsigned char* cls_out = ws + lay.out + z.cls;
+  unsigned char* cls_tgt = ws + lay.tgt + z.cls;
+  unsigned char* tgt_labels = ws + lay.tgt_cls;
+  u64* keys = reinterpret_cast<u64*>(ws + lay.keys);
+  unsigned* counts = reinterpret_cast<unsigned*>(ws + lay.counts);
+  int* claimed = reinterpret_cast<int*>(ws + lay.claimed);
+
+  hipError_t e = launch_label_zones(labels, labels_i64, N, H, W, out_rows, cap, out_num, parent_out, cls_out,
+                                    reinterpret_cast<int*>(ws + lay.out + z.blocks), s);
+  if (e != hipSuccess) return e;
+  const size_t px = (size_t)N * H * W, slots = (size_t)N * lay.table;
+  hipLaunchKernelGGL(target_class_plane_kernel, dim3(grid_stride_blocks(px / 4 + 1, 256, 8)), dim3(256), 0, s, target_grey, tgt_labels, px);
+  e = launch_label_zones(tgt_labels, 0, N, H, W, tgt_rows, cap, tgt_num, parent_tgt, cls_tgt,
+                         reinterpret_cast<int*>(ws + lay.tgt + z.blocks), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pair_clear_kernel, dim3(grid_stride_blocks(slots, 256, 8)), dim3(256), 0, s, keys, counts, claimed, slots,
+                     N);                                  // slots >= 2 N: the first N threads exist
+  int log2_table = 0;
+  while ((1 << log2_table) < lay.table) ++log2_table;
+  hipLaunchKernelGGL(pair_accumulate_kernel, dim3((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, N), dim3(kThreads), 0, s, parent_out,
+                     cls_out, parent_tgt, cls_tgt, H, W, keys, counts, claimed, lay.table, 64 - log2_table, pair_cap);
+  hipLaunchKernelGGL(pair_sort_kernel, dim3(N), dim3(kThreads), 0, s, keys, counts, claimed, lay.table, pair_cap, pair_rows, pair_num);
+  return hipGetLastError();
+}
+
+}  // namespace nbc

@@ -47,6 +47,18 @@ reference's ``get_pos_weight()``) and, with ``--loss`` too, ``MixedLoss`` (utils
 holds the cell sums and pixel counts of the whole folder, so that it can be re-weighted without another run.  The
 reference's ``JaccardLoss`` is not computed.  Without the flag nothing changes.
 
+``--zones`` (``zones=True``) asks what the pixel metrics hide: which zone of the final labels is which zone of the dual, and
+how well they overlap.  After the second ``confusion``, on the labels ``PixelWiseF1`` sees, ``FCNResNet50.match_zones`` leaves
+the zone rows of both maps (``predict --zones``' inventory; the dual's classes by ``metrics.target_classes``) and the
+``(output zone, target zone, shared pixels)`` rows of every overlapping pair of the same class (csrc/zone_match.hip).  Up to
+``--zones_cap`` (1024) zone rows per map and ``--zone_pairs_cap`` (2048) pair rows per image ride back per batch; an image
+over a cap is matched by ``zones.match_cpu`` from the two planes, which ride back too, so the files do not depend on the
+caps.  Three ragged gathers (``folder_run.gather_ragged``) bring the rows to rank 0, which writes
+``results/zone_matches.csv`` (a row per target zone, ``matched`` or ``missed``, then a row per ``spurious`` output zone),
+``results/zone_evaluation.csv`` (a row per image: ``zones.match_figures`` for Bark and Node) and a ``"zones"`` entry in the
+summary (``zones.match_summary``).  Two zones match iff their IoU exceeds ``--match_iou`` (0.5 <= T < 1, default 0.5), so a
+zone has at most one partner.  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -75,6 +87,7 @@ STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
 SKIP_REASONS = {STATUS_NO_DUAL: "no_dual", STATUS_SHAPE_MISMATCH: "shape_mismatch", STATUS_TOO_LARGE: "too_large"}
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
 SUMMARY_JSON = os.path.join("results", "evaluation_summary.json")
+MATCHES_CSV, ZONE_EVALUATION_CSV = "zone_matches.csv", "zone_evaluation.csv"     # --zones, under results/
 
 
 def list_labelled(root: str) -> List[dict]:
@@ -142,6 +155,52 @@ def check_class_weights(weights) -> Tuple[float, float, float]:
     return w
 
 
+def check_zone_match_arguments(zones: bool, zones_cap=None, zone_pairs_cap=None, match_iou=None) -> None:
+    """``ValueError`` for what ``--zones`` and its options refuse before any device is touched: an option without the flag, a
+    cap out of range (``folder_run.ZONES_MAX_CAP``, ``zones.PAIRS_MAX_CAP``), a threshold outside [0.5, 1)."""
+    from . import zones as zn
+    folder_run.check_zones_arguments(zones, zones_cap)
+    if not zones:
+        if zone_pairs_cap is not None:
+            raise ValueError("--zone_pairs_cap needs --zones")
+        if match_iou is not None:
+            raise ValueError("--match_iou needs --zones")
+        return
+    if zone_pairs_cap is not None and not 1 <= int(zone_pairs_cap) <= zn.PAIRS_MAX_CAP:
+        raise ValueError("--zone_pairs_cap must lie in 1..%d" % zn.PAIRS_MAX_CAP)
+    if match_iou is not None:
+        zn.check_match_iou(match_iou)
+
+
+def _rows_of_image(allz: np.ndarray, indices) -> list:
+    """The rows of each global index of ``indices`` in gathered ``(global_idx, fields...)`` rows, without the index column."""
+    starts, ends = np.searchsorted(allz[:, 0], indices, side="left"), np.searchsorted(allz[:, 0], indices, side="right")
+    return [allz[a:b, 1:] for a, b in zip(starts, ends)]
+
+
+def write_zone_match_report(results_dir: str, items, allrows, all_out, all_tgt, all_pairs, match_iou: float, cap: int,
+                            pair_cap: int, host_fallbacks: int) -> dict:
+    """``zone_matches.csv`` and ``zone_evaluation.csv`` (tab separated, like ``evaluation_stats.csv``) from the gathered rows,
+    for the evaluated images of ``allrows`` in their order: ``all_out`` / ``all_tgt`` the ``(global_idx, 10 zone fields)`` rows
+    of the output's and the target's zones, ``all_pairs`` the ``(global_idx, 3 pair fields)`` rows.  Returns the ``"zones"``
+    entry of the summary (``zones.match_summary``)."""
+    from . import zones as zn
+    all_out = np.asarray(all_out, dtype=np.int64).reshape(-1, 1 + zn.ZONE_ROW)
+    all_tgt = np.asarray(all_tgt, dtype=np.int64).reshape(-1, 1 + zn.ZONE_ROW)
+    all_pairs = np.asarray(all_pairs, dtype=np.int64).reshape(-1, 1 + zn.PAIR_ROW)
+    done = [int(g[0]) for g in allrows if int(g[3]) == STATUS_OK]
+    matches, evaluation, figures = [list(zn.MATCH_COLUMNS)], [list(zn.EVALUATION_COLUMNS)], []
+    for gi, o, t, p in zip(done, _rows_of_image(all_out, done), _rows_of_image(all_tgt, done), _rows_of_image(all_pairs, done)):
+        d = items[gi]
+        matches += zn.match_rows(d["name"], d["wood"], o, t, p, match_iou)
+        figures.append(zn.match_figures(o, t, p, match_iou))
+        evaluation += zn.evaluation_rows(d["name"], d["wood"], figures[-1])
+    for name, rows_ in ((MATCHES_CSV, matches), (ZONE_EVALUATION_CSV, evaluation)):
+        with open(os.path.join(results_dir, name), "w") as f:
+            csv.writer(f, delimiter="\t").writerows(rows_)
+    return zn.match_summary(figures, match_iou, cap, pair_cap, host_fallbacks)
+
+
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
@@ -196,7 +255,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     batch: int = None, window: int = 64, target_size: int = 1024, calibrate: bool = True,
                     streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                     loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
-                    class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference") -> dict:
+                    class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
+                    zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -205,8 +265,18 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     defaults), set on every stream's model object; ``normalization_source``: what the summary says of where it came from.
     ``ce``: also the cross-entropy family (module docstring), weighted with ``class_weights`` (three finite values >= 0);
     ``class_weights_source``: what the summary says of where they came from.
+    ``zones``: also match the zones of the final labels against the zones of the duals (module docstring): ``zones_cap`` zone
+    rows per map and ``zone_pairs_cap`` pair rows per image stay on the device path (defaults ``zones.DEFAULT_CAP``,
+    ``zones.DEFAULT_PAIR_CAP``), ``match_iou`` is the matching threshold in [0.5, 1) (default 0.5).  The returned dict gains
+    ``zones_host_fallbacks``, this rank's images that were matched on the host.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
+    from . import zones as zn
+    Z = bool(zones)
+    check_zone_match_arguments(Z, zones_cap, zone_pairs_cap, match_iou)     # refusals first: nothing has touched a device yet
+    ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
+    PCAP = int(zone_pairs_cap) if zone_pairs_cap is not None else zn.DEFAULT_PAIR_CAP
+    IOU = zn.check_match_iou(match_iou) if match_iou is not None else zn.DEFAULT_MATCH_IOU
     if ce:
         class_weights = check_class_weights(class_weights)
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size)
@@ -220,6 +290,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if ce:
             m.pixel_cross_entropy(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                                   torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if Z:                                        # match_zones' (11 bytes per pixel)
+            plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
+            m.match_zones(plane, plane, cap=ZCAP, pair_cap=PCAP)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
                         normalization=normalization)
@@ -253,6 +326,14 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     logits_buf = [torch.empty(batch * 3 * target_size * target_size, dtype=torch.float32, device=dev)
                   for _ in range(r.n_streams)] if loss or ce else None
     ce_ring = [torch.empty((batch, 9), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if ce else None
+    # --zones: per slot the two zone inventories, the pair rows, the three counts per image, and the two planes an image over
+    # a cap is matched from on the host
+    zring = [(torch.empty((2, batch, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(),
+              torch.empty((batch, PCAP, zn.PAIR_ROW), dtype=torch.int64).pin_memory(),
+              torch.empty((3, batch), dtype=torch.int64).pin_memory(),
+              torch.empty(2 * batch * target_size * target_size, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if Z else None
+    zres = {}                                        # k -> (output zone rows, target zone rows, pair rows)
+    zfallbacks = []                                  # the k matched on the host: zones or pairs over a cap
 
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
@@ -269,9 +350,33 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         conf_clean = mdl.confusion(labels, tgt)
         ring[slot][0, :n].copy_(conf_raw, non_blocking=True)
         ring[slot][1, :n].copy_(conf_clean, non_blocking=True)
+        if Z:                                                         # the labels PixelWiseF1 sees, against the same dual
+            zr, pr, nums, planes = zring[slot]
+            o_rows, o_num, t_rows, t_num, p_rows, p_num = mdl.match_zones(labels, tgt, cap=ZCAP, pair_cap=PCAP)
+            zr[0, :n].copy_(o_rows, non_blocking=True)
+            zr[1, :n].copy_(t_rows, non_blocking=True)
+            pr[:n].copy_(p_rows, non_blocking=True)
+            for i, t in enumerate((o_num, t_num, p_num)):
+                nums[i, :n].copy_(t, non_blocking=True)
+            planes[: n * h * w].copy_(labels.reshape(-1), non_blocking=True)
+            planes[n * h * w: 2 * n * h * w].copy_(tgt.reshape(-1), non_blocking=True)
+
+    def match_on_host(k, lab, grey):                 # pool: an image over a cap, from the two planes
+        zres[k] = zn.match_cpu(lab, zn.target_classes(grey))[0]
 
     def consume(slot, part, n, h, w):
         conf = ring[slot][:, :n].numpy().reshape(2, n, 9)
+        futures = []
+        if Z:
+            zr, pr, nums, planes = (t.numpy() for t in zring[slot])
+            for j, k in enumerate(part):
+                no, nt, npairs = (int(v) for v in nums[:, j])
+                if no > ZCAP or nt > ZCAP or npairs > PCAP:
+                    zfallbacks.append(k)
+                    lab, grey = (planes[a * n * h * w:][j * h * w: (j + 1) * h * w].reshape(h, w).copy() for a in (0, 1))
+                    futures.append(r.pool.submit(match_on_host, k, lab, grey))
+                else:
+                    zres[k] = (zr[0, j, :no].copy(), zr[1, j, :nt].copy(), pr[j, :npairs].copy())
         for j, k in enumerate(part):
             rows[k, :4] = (mine[k], h, w, STATUS_OK)
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
@@ -279,6 +384,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                 loss_rows[k, 1:] = loss_ring[slot][j].numpy().view(np.int64)
             if ce:
                 ce_rows[k, 1:] = ce_ring[slot][j].numpy().view(np.int64)
+        return futures
 
     def first_frame():                               # the calibration guard's: this rank's first image that fits
         first = next((gi for gi in mine if max(sizes[gi]) <= target_size), None)
@@ -288,6 +394,15 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     allrows = folder_run.gather(r, rows, ROW_WIDTH)
     all_loss = folder_run.gather(r, loss_rows, LOSS_ROW_WIDTH) if loss else None
     all_ce = folder_run.gather(r, ce_rows, CE_ROW_WIDTH) if ce else None
+    all_zones = n_fallbacks = None
+    if Z:                                            # three ragged row sets, an image's rows together and in order
+        def local(which, width):
+            parts = [np.concatenate([np.full((len(zres[k][which]), 1), mine[k], dtype=np.int64), zres[k][which]], axis=1)
+                     for k in sorted(zres)]
+            return np.concatenate(parts) if parts else np.zeros((0, 1 + width), dtype=np.int64)
+        all_zones = [folder_run.gather_ragged(local(i, wd), r.world, r.dist, r.wire_dev, width=1 + wd)
+                     for i, wd in enumerate((zn.ZONE_ROW, zn.ZONE_ROW, zn.PAIR_ROW))]
+        n_fallbacks = len(folder_run.gather(r, np.array([[mine[k]] for k in sorted(zfallbacks)], dtype=np.int64).reshape(-1, 1), 1))
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
@@ -296,6 +411,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                                    **(dict(ce_rows=all_ce, class_weights=class_weights,
                                            class_weights_source=class_weights_source) if ce else {}))
         write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss, **(dict(ce=True) if ce else {}))
+        if Z:
+            summary["zones"] = write_zone_match_report(os.path.join(root, "results"), items, allrows, *all_zones, IOU, ZCAP, PCAP,
+                                                       n_fallbacks)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -303,6 +421,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if loss:                                     # rank 0: {global_idx: float64 [3] terms}
         out["loss_terms"] = None if r.rank != 0 else {
             int(g[0]): np.ascontiguousarray(g[1:]).view(np.float64).copy() for g in all_loss}
+    if Z:
+        out["zones_host_fallbacks"] = len(zfallbacks)
     if ce:                                       # rank 0: {global_idx: float64 [3,3] cell sums}
         out["ce_sums"] = None if r.rank != 0 else {
             int(g[0]): np.ascontiguousarray(g[1:]).view(np.float64).reshape(3, 3).copy() for g in all_ce}
@@ -334,6 +454,17 @@ def format_summary(summary: dict) -> str:
         lines.append("cross-entropy: mean over images %s; class weights %s (%s)" % (
             ", ".join("%s %s" % (k, fmt(v)) for k, v in ce["mean_over_images"].items()),
             " ".join(repr(v) for v in ce["class_weights"]), ce["class_weights_source"]))
+    if summary.get("zones"):
+        z = summary["zones"]
+        fmt = lambda v: "-" if v is None else "%.3f" % v
+        for name in ("Bark", "Node"):
+            c = z[name]
+            lines.append("%s zones at IoU > %s: %d of %d target zones matched (%d output zones, %d spurious; %d split targets, %d "
+                         "merged outputs): recall %s, precision %s, F1 %s, mean matched IoU %s" % (
+                             name, z["match_iou"], c["matched"], c["targets"], c["outputs"], c["spurious"], c["split_targets"],
+                             c["merged_outputs"], fmt(c["recall"]), fmt(c["precision"]), fmt(c["f1"]), fmt(c["mean_iou"])))
+        if z["host_fallbacks"]:
+            lines.append("%d images over a cap were matched on the host" % z["host_fallbacks"])
     return "\n".join(lines)
 
 
@@ -353,10 +484,25 @@ def main(argv=None):
     ap.add_argument("--class_weights_from", metavar="PATH", default=None,
                     help="--ce: take the class weights from the pos_weight of a dataset_stats.json (python -m "
                          "neuralbarkcalculator_amd.stats)")
+    ap.add_argument("--zones", action="store_true",
+                    help="also match the zones of the final labels against the zones of the duals on the device (which output "
+                         "zone is which target zone, and how well they overlap) and write results/zone_matches.csv, "
+                         "zone_evaluation.csv and a \"zones\" entry in the summary")
+    ap.add_argument("--zones_cap", type=int, default=None, metavar="ROWS",
+                    help="with --zones: zone rows per map the device pass keeps (default 1024); an image over a cap is matched "
+                         "on the host, the files do not depend on it")
+    ap.add_argument("--zone_pairs_cap", type=int, default=None, metavar="ROWS",
+                    help="with --zones: (output zone, target zone) rows per image the device pass keeps (default 2048, at most 4096)")
+    ap.add_argument("--match_iou", type=float, default=None, metavar="T",
+                    help="with --zones: two zones match when their IoU exceeds T, 0.5 <= T < 1 (default 0.5)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
+    try:
+        check_zone_match_arguments(args.zones, args.zones_cap, args.zone_pairs_cap, args.match_iou)
+    except ValueError as e:
+        ap.error(str(e))
     if args.exclude_nodes:
         raise SystemExit("evaluate: --exclude_nodes is not supported: IoU and F1 are defined on the three classes "
                          "(nothing, bark, node) of the duals")
@@ -382,6 +528,8 @@ def main(argv=None):
         kw["loss"] = True
     if args.ce:
         kw.update(ce=True, **ce_kw)
+    if args.zones:
+        kw.update(zones=True, zones_cap=args.zones_cap, zone_pairs_cap=args.zone_pairs_cap, match_iou=args.match_iou)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

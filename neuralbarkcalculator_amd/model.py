@@ -217,6 +217,7 @@ class FCNResNet50:
         self._pixel_ce_ws: Optional[torch.Tensor] = None   # nbc_pixel_cross_entropy's, likewise
         self._dropout_ws: Optional[torch.Tensor] = None    # nbc_dropout_draws', likewise
         self._zones_ws: Optional[torch.Tensor] = None      # nbc_label_zones', likewise
+        self._zone_match_ws: Optional[torch.Tensor] = None   # nbc_match_zones', likewise
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self.device: Optional[torch.device] = None
         self.training = False
@@ -390,6 +391,45 @@ class FCNResNet50:
                                                  rows.data_ptr(), cap, num.data_ptr(), ws.data_ptr(), ws.numel(), cur.cuda_stream),
                        "nbc_label_zones")
         return rows, num
+
+    def match_zones(self, labels: torch.Tensor, target: torch.Tensor, cap: int = 1024, pair_cap: int = 2048):
+        """The zones of label maps against the zones of their labelled masks on the device (nbc_match_zones; include/nbc.h,
+        csrc/zone_match.hip).  ``labels`` as ``label_zones`` takes them, ``target`` the contiguous uint8 grey mask of the same
+        shape as ``confusion`` takes it (class ``round(2 * v / 255)``); both read only.  Runs on the current stream; the
+        workspace (11 bytes per pixel) is cached on this object and only grows.  Returns six int64 tensors ``(out_rows [N,cap,10],
+        out_num [N], tgt_rows [N,cap,10], tgt_num [N], pair_rows [N,pair_cap,3], pair_num [N])``: both inventories as
+        ``label_zones`` gives them, and per image the rows ``(output zone index, target zone index, shared pixels)`` of every
+        pair of same-class zones that share a pixel, sorted, the indices being the zones' positions in first-pixel order
+        (valid also at or above ``cap``).  ``pair_num[n]`` is the number of pairs, or ``pair_cap + 1`` when there are more
+        (the image's pair rows are then unspecified); rows ``pair_num[n]`` onwards are not written.  Equal to
+        ``zones.match_cpu``, integer for integer; works for every architecture, since it only sees labels."""
+        self._require_ctx()
+        self._check_labels(labels)
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
+            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
+        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
+            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
+        cap, pair_cap = int(cap), int(pair_cap)
+        if cap < 1:
+            raise ValueError("cap must be at least 1")
+        if not 1 <= pair_cap <= _lib.PAIRS_MAX_CAP:
+            raise ValueError("pair_cap must lie in 1..%d" % _lib.PAIRS_MAX_CAP)
+        n = 1 if labels.dim() == 2 else int(labels.shape[0])
+        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        need = int(self._lib.nbc_zone_match_workspace_bytes(n, h, w, pair_cap))
+        if need == 0:
+            raise ValueError("nbc_match_zones refuses a [%d,%d,%d] batch (N <= 65535, H, W <= 65535, H * W < 2^31)" % (n, h, w))
+        out_rows, tgt_rows = (torch.empty((n, cap, _lib.ZONE_ROW), dtype=torch.int64, device=self.device) for _ in range(2))
+        pair_rows = torch.empty((n, pair_cap, _lib.ZONE_PAIR_ROW), dtype=torch.int64, device=self.device)
+        out_num, tgt_num, pair_num = (torch.empty((n,), dtype=torch.int64, device=self.device) for _ in range(3))
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_zone_match_ws", need, cur)
+            _lib.check(self._lib.nbc_match_zones(self._ctx, labels.data_ptr(),
+                                                 _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8, target.data_ptr(),
+                                                 n, h, w, out_rows.data_ptr(), out_num.data_ptr(), tgt_rows.data_ptr(),
+                                                 tgt_num.data_ptr(), cap, pair_rows.data_ptr(), pair_num.data_ptr(), pair_cap,
+                                                 ws.data_ptr(), ws.numel(), cur.cuda_stream), "nbc_match_zones")
+        return out_rows, out_num, tgt_rows, tgt_num, pair_rows, pair_num
 
     def confusion(self, labels: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """Per-image 3x3 confusion counts on the device (nbc_confusion): the pixel counting behind the evaluation loop's
@@ -917,6 +957,7 @@ class FCNResNet50:
         self._pixel_ce_ws = None
         self._dropout_ws = None
         self._zones_ws = None
+        self._zone_match_ws = None
         self._last_shape = None
 
     def __del__(self):
