@@ -608,6 +608,50 @@ int nbc_match_zones(nbc_ctx* ctx, const void* labels_dev, int labels_dtype, cons
                     int64_t* pair_rows_dev, int64_t* pair_num_dev, int pair_cap, void* workspace_dev, size_t workspace_bytes,
                     void* hip_stream);
 
+/* ---- contour distances against the labelled masks -------------------------------------------------
+ * How far the contours of a label map lie from the contours of its labelled mask: the error model of an area in mm^2 (a
+ * zone's area error is about its perimeter times the displacement).  The reference has no such code; the host restatement
+ * is contours.contours_cpu (scipy erosion for the contour, scipy's exact Euclidean distance transform by indices), the
+ * kernels csrc/contours.hip.
+ *
+ * Class maps: the output's class is the label, 1 or 2 (any other value belongs to no class); the target's class is
+ * nbc_confusion's (grey 0..63 -> 0, 64..191 -> 1, 192..255 -> 2).  A pixel is on the contour of class c iff it has class c
+ * and at least one 4-neighbour inside the image does not (the inner 4-contour; a neighbour outside the image is no contour
+ * side, so the frame that cuts both maps alike adds nothing).
+ * Sets: four per image, s = 2 (c - 1) + dir for c = 1 (Bark), 2 (Node); dir 0: source = the output's contour, destination =
+ * the target's; dir 1: source = the target's, destination = the output's.  For a source pixel p,
+ * d2(p) = min over the destination pixels q of (px - qx)^2 + (py - qy)^2, an exact integer.
+ * rows_dev  int64 [N, NBC_CONTOUR_SETS, NBC_CONTOUR_HEAD + bins].  Row: { n, m, sum_d2, max_d2, hist[bins] }: n the source
+ *   contour pixels, m the destination contour pixels, sum_d2 and max_d2 the sum and the maximum of d2 over the source pixels,
+ *   hist[k] for k < bins - 1 the source pixels with ceil(sqrt(d2)) == k, that is (k - 1)^2 < d2 <= k^2 (bin 0: d2 == 0), and
+ *   hist[bins - 1] those with d2 > (bins - 2)^2.  The bin is computed on the integers.  With bins >= ceil(hypot(H - 1,
+ *   W - 1)) + 1 the last bin is no overflow bin.  When n == 0 or m == 0, sum_d2, max_d2 and every bin are 0.
+ * sum_d_dev  float64 [N, NBC_CONTOUR_SETS]: the sum of sqrt(d2) over the source pixels, 0.0 when n == 0 or m == 0.  The sum
+ *   is added in an order fixed by the image alone: a row's source pixels, listed in an order their positions fix, go
+ *   round-robin over the threads of a block, then the lanes of a wave by the xor butterfly, the waves in order, then the
+ *   rows lane-strided and by the butterfly; no float atomics, and nothing in the order depends on the batch, the stream
+ *   or the timing.  The integers are sums, maxima and counts, whose order does not matter.  An image's rows and sum_d
+ *   therefore have the same bits alone, in any batch, on any stream and from run to run.
+ * labels_dev / target_grey_dev  uint8 or int64 [N,H,W] / uint8 [N,H,W]; read, never written
+ * workspace_dev  at least nbc_contours_workspace_bytes(N, H, W) bytes, 256-byte aligned; contents scratch
+ * Every word of rows_dev and sum_d_dev is written on every call, zeros included; nothing outside them (and the workspace) is
+ * written.  No loop of the pass depends on the data for its end: the row scan of a pixel takes at most W steps.
+ * Runs on hip_stream (on the context's device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer, N outside 1..65535, H or W outside 1..NBC_CONTOUR_MAX_SIDE (d2 then
+ * fits 32 bits and a row's column distances fit LDS), bins outside 2..5793 (= ceil(hypot(4095, 4095)) + 1), another
+ * labels_dtype, a workspace that is too small or not 256-byte aligned. */
+#define NBC_CONTOUR_SETS 4
+#define NBC_CONTOUR_HEAD 4          /* n, m, sum_d2, max_d2 */
+#define NBC_CONTOUR_MAX_SIDE 4096
+/* With P = H * W and A(x) = x rounded up to a multiple of 256:
+ *   A(N P) + A(8 N P) + A(8 * 4 N H)
+ * (a mark byte per pixel, four u16 column distances per pixel, an f64 partial per image, set and row): 9 bytes per pixel
+ * and N * 4 * H doubles.  0 for a shape that nbc_contour_distances refuses. */
+size_t nbc_contours_workspace_bytes(int N, int H, int W);     /* 0 for a shape the call refuses */
+int nbc_contour_distances(nbc_ctx* ctx, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev,
+                          int N, int H, int W, int64_t* rows_dev /* [N,4,NBC_CONTOUR_HEAD+bins] */, int bins,
+                          double* sum_d_dev /* [N,4] */, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+
 /* The resize of the reference's preprocessor (models.py:191-198): uint8 RGB [H,W,3] on the device ->
  * ToTensor (u8 / 255 in float32) -> skimage.transform.resize(order=3, mode='reflect',
  * anti_aliasing=False) to out_h x out_w (4-tap Catmull-Rom, all arithmetic in float32 like scikit-image's

@@ -25,6 +25,8 @@ VOTE_STATS = 10                                     # NBC_VOTE_STATS
 ZONE_ROW = 10                                       # NBC_ZONE_ROW
 ZONE_PAIR_ROW = 3                                   # NBC_ZONE_PAIR_ROW
 PAIRS_MAX_CAP = 4096                                # NBC_ZONE_PAIRS_MAX_CAP
+CONTOUR_SETS, CONTOUR_HEAD = 4, 4                   # NBC_CONTOUR_SETS, NBC_CONTOUR_HEAD
+CONTOUR_MAX_SIDE = 4096                             # NBC_CONTOUR_MAX_SIDE
 
 
 class NbcTensor(C.Structure):
@@ -129,6 +131,9 @@ SIGNATURES = {
     "nbc_match_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                   C.c_void_p]),
+    "nbc_contours_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nbc_contour_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nbc_resize_cubic_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "nbc_preprocess_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p]),

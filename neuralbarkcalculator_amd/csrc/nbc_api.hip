@@ -1064,6 +1064,31 @@ int nbc_match_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, const 
   return NBC_OK;
 }
 
+static bool contours_shape_ok(int N, int H, int W) {
+  return N >= 1 && N <= 65535 && H >= 1 && H <= NBC_CONTOUR_MAX_SIDE && W >= 1 && W <= NBC_CONTOUR_MAX_SIDE;
+}
+static constexpr int kContourMaxBins = 5793;         // ceil(hypot(4095, 4095)) + 1
+
+size_t nbc_contours_workspace_bytes(int N, int H, int W) { return contours_shape_ok(N, H, W) ? contours_layout(N, H, W).total : 0; }
+
+int nbc_contour_distances(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H, int W,
+                          int64_t* rows_dev, int bins, double* sum_d_dev, void* workspace_dev, size_t workspace_bytes,
+                          void* hip_stream) {
+  constexpr const char* kWho = "nbc_contour_distances";
+  if (!c || !labels_dev || !target_grey_dev || !rows_dev || !sum_d_dev || !workspace_dev)
+    return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!contours_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1.." + std::to_string(NBC_CONTOUR_MAX_SIDE));
+  if (bins < 2 || bins > kContourMaxBins) return fail(kWho, NBC_ERR_INVALID, "bins must lie in 2.." + std::to_string(kContourMaxBins));
+  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, contours_layout(N, H, W).total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  NBC_HIP(launch_contour_distances(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, target_grey_dev, N, H, W,
+                                   reinterpret_cast<long long*>(rows_dev), bins, sum_d_dev, static_cast<unsigned char*>(workspace_dev),
+                                   static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
+}
+
 size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
   if (N < 1 || H < 8 || W < 8 || H > 65535 || draws_per_pass < 1 || (long long)H * W > 0x7fffffffLL) return 0;
   const unsigned long long I = (unsigned long long)draws_per_pass * (unsigned long long)N;

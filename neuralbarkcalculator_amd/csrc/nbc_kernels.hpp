@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, aspp.hip, bn_stats.hip and
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, contours.hip, aspp.hip, bn_stats.hip and
 // efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
 // convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
@@ -202,6 +202,16 @@ ZoneMatchLayout zone_match_layout(int N, int H, int W, int pair_cap);
 hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
                               long long* out_rows, long long* out_num, long long* tgt_rows, long long* tgt_num, int cap,
                               long long* pair_rows, long long* pair_num, int pair_cap, unsigned char* ws, hipStream_t s);
+// Contour distances (contours.hip; the contract: nbc_contour_distances in include/nbc.h): rows int64 [N][4][NBC_CONTOUR_HEAD + bins],
+// sum_d f64 [N][4].  contours_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size -- a mark
+// byte per pixel, the four u16 column distances per pixel, and an f64 partial per (image, set, row).  N in 1..65535, H and W
+// in 1..NBC_CONTOUR_MAX_SIDE, bins >= 2.
+struct ContoursLayout {
+  size_t mark, dist, partial, total;
+};
+ContoursLayout contours_layout(int N, int H, int W);
+hipError_t launch_contour_distances(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
+                                    long long* rows, int bins, double* sum_d, unsigned char* ws, hipStream_t s);
 // Preprocessor (models.py:191-203): uint8 HWC [H,W,3] -> ToTensor -> skimage cubic resize with reflected borders,
 // clipped to the input range -> any of: float32 HWC [out_h,out_w,3]; its uint8 form as imsave writes it; per output
 // row the number of pixels trim_black counts as lit.  minmax: two uints of scratch.

@@ -59,6 +59,18 @@ caps.  Three ragged gathers (``folder_run.gather_ragged``) bring the rows to ran
 summary (``zones.match_summary``).  Two zones match iff their IoU exceeds ``--match_iou`` (0.5 <= T < 1, default 0.5), so a
 zone has at most one partner.  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
 
+``--contours`` (``contours=True``) asks how far the output's contours lie from the labelled ones, in millimetres: for a tool
+whose product is an area, contour displacement is the error model.  After the second ``confusion``, on the same labels,
+``FCNResNet50.contour_distances`` leaves per image and set (Bark and Node, output to target and back) the contour pixels, the
+sum and maximum of the squared distances, their histogram by whole pixels and the float64 sum of the distances
+(csrc/contours.hip; the host restatement is ``contours.contours_cpu``).  The rows ride back with the batch; each rank turns
+them into one fixed-width row per image (``contours.wire_rows``: the heads, the sums, the counts within ``--contour_tolerance``
+pixels -- default 2, 7.2 mm -- and the HD95 bins) and one pooled histogram, and only these travel.  Rank 0 writes
+``results/contour_evaluation.csv`` (``contours.CONTOUR_COLUMNS``: per class the contour pixels of both maps, contour
+precision, recall and F1 at the tolerance, the mean symmetric contour distance, HD95 -- whole pixels, rounded up -- and the
+Hausdorff distance in mm) and a ``"contours"`` entry in the summary (``contours.contour_summary``) with the pooled histogram,
+from which any other tolerance can be read off.  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -88,6 +100,7 @@ SKIP_REASONS = {STATUS_NO_DUAL: "no_dual", STATUS_SHAPE_MISMATCH: "shape_mismatc
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
 SUMMARY_JSON = os.path.join("results", "evaluation_summary.json")
 MATCHES_CSV, ZONE_EVALUATION_CSV = "zone_matches.csv", "zone_evaluation.csv"     # --zones, under results/
+CONTOUR_CSV = "contour_evaluation.csv"                                           # --contours, under results/
 
 
 def list_labelled(root: str) -> List[dict]:
@@ -201,6 +214,36 @@ def write_zone_match_report(results_dir: str, items, allrows, all_out, all_tgt, 
     return zn.match_summary(figures, match_iou, cap, pair_cap, host_fallbacks)
 
 
+def check_contour_arguments(contours: bool, contour_tolerance=None) -> None:
+    """``ValueError`` for what ``--contours`` and its option refuse before any device is touched: the option without the flag,
+    a tolerance that is no integer >= 0."""
+    from . import contours as ct
+    if not contours:
+        if contour_tolerance is not None:
+            raise ValueError("--contour_tolerance needs --contours")
+        return
+    if contour_tolerance is not None:
+        ct.check_tolerance(contour_tolerance)
+
+
+def write_contour_report(results_dir: str, items, allrows, all_wire, histogram, tolerance: int) -> dict:
+    """``contour_evaluation.csv`` (tab separated, like ``evaluation_stats.csv``) from the gathered ``(global_idx,
+    contours.WIRE_WIDTH fields)`` rows ``all_wire``, for the evaluated images of ``allrows`` in their order.  Returns the
+    ``"contours"`` entry of the summary (``contours.contour_summary`` of the figures and the folder's pooled ``histogram``)."""
+    from . import contours as ct
+    wire = {int(g[0]): g[1:] for g in np.asarray(all_wire, dtype=np.int64).reshape(-1, 1 + ct.WIRE_WIDTH)}
+    table, figures = [list(ct.CONTOUR_COLUMNS)], []
+    for g in allrows:
+        if int(g[3]) != STATUS_OK:
+            continue
+        d = items[int(g[0])]
+        figures.append(ct.figures_of_wire(wire[int(g[0])]))
+        table += ct.contour_rows(d["name"], d["wood"], figures[-1])
+    with open(os.path.join(results_dir, CONTOUR_CSV), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    return ct.contour_summary(figures, tolerance, histogram)
+
+
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
@@ -256,7 +299,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                     loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
                     class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
-                    zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None) -> dict:
+                    zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
+                    contour_tolerance: int = None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -269,6 +313,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     rows per map and ``zone_pairs_cap`` pair rows per image stay on the device path (defaults ``zones.DEFAULT_CAP``,
     ``zones.DEFAULT_PAIR_CAP``), ``match_iou`` is the matching threshold in [0.5, 1) (default 0.5).  The returned dict gains
     ``zones_host_fallbacks``, this rank's images that were matched on the host.
+    ``contours``: also the contour distances of the final labels against the duals (module docstring), with
+    ``contour_tolerance`` pixels (an integer >= 0, default ``contours.DEFAULT_TOLERANCE``) as the tolerance of the contour
+    precision, recall and F1.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
@@ -277,6 +324,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
     PCAP = int(zone_pairs_cap) if zone_pairs_cap is not None else zn.DEFAULT_PAIR_CAP
     IOU = zn.check_match_iou(match_iou) if match_iou is not None else zn.DEFAULT_MATCH_IOU
+    from . import contours as ct
+    K = bool(contours)
+    check_contour_arguments(K, contour_tolerance)
+    TOL = ct.check_tolerance(contour_tolerance) if contour_tolerance is not None else ct.DEFAULT_TOLERANCE
+    CBINS = ct.default_bins(target_size, target_size)   # the bins of the largest frame: the pooled histogram's
     if ce:
         class_weights = check_class_weights(class_weights)
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size)
@@ -293,6 +345,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if Z:                                        # match_zones' (11 bytes per pixel)
             plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
             m.match_zones(plane, plane, cap=ZCAP, pair_cap=PCAP)
+        if K:                                        # contour_distances' (9 bytes per pixel)
+            plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
+            m.contour_distances(plane, plane)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
                         normalization=normalization)
@@ -334,6 +389,14 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
               torch.empty(2 * batch * target_size * target_size, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if Z else None
     zres = {}                                        # k -> (output zone rows, target zone rows, pair rows)
     zfallbacks = []                                  # the k matched on the host: zones or pairs over a cap
+    # --contours: per slot the rows of a batch (flat: their width follows the batch's shape) and its sum_d; per image the row
+    # that travels; the rank's pooled histogram
+    cring = [(torch.empty(batch * ct.SETS * (ct.HEAD + CBINS), dtype=torch.int64).pin_memory(),
+              torch.empty((batch, ct.SETS), dtype=torch.float64).pin_memory()) for _ in range(r.depth)] if K else None
+    cwire = np.zeros((len(mine), 1 + ct.WIRE_WIDTH), dtype=np.int64) if K else None
+    if K:
+        cwire[:, 0] = mine
+    chist = np.zeros((ct.SETS, CBINS), dtype=np.int64) if K else None
 
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
@@ -360,6 +423,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                 nums[i, :n].copy_(t, non_blocking=True)
             planes[: n * h * w].copy_(labels.reshape(-1), non_blocking=True)
             planes[n * h * w: 2 * n * h * w].copy_(tgt.reshape(-1), non_blocking=True)
+        if K:                                                         # the same labels against the same dual
+            c_rows, c_sum = mdl.contour_distances(labels, tgt)
+            cring[slot][0][: c_rows.numel()].copy_(c_rows.reshape(-1), non_blocking=True)
+            cring[slot][1][:n].copy_(c_sum, non_blocking=True)
 
     def match_on_host(k, lab, grey):                 # pool: an image over a cap, from the two planes
         zres[k] = zn.match_cpu(lab, zn.target_classes(grey))[0]
@@ -377,6 +444,13 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     futures.append(r.pool.submit(match_on_host, k, lab, grey))
                 else:
                     zres[k] = (zr[0, j, :no].copy(), zr[1, j, :nt].copy(), pr[j, :npairs].copy())
+        if K:
+            width = ct.HEAD + ct.default_bins(h, w)
+            c_rows = cring[slot][0][: n * ct.SETS * width].numpy().reshape(n, ct.SETS, width)
+            wire = ct.wire_rows(c_rows, cring[slot][1][:n].numpy(), TOL)
+            chist[...] += ct.pooled_histogram(c_rows, CBINS)
+            for j, k in enumerate(part):
+                cwire[k, 1:] = wire[j]
         for j, k in enumerate(part):
             rows[k, :4] = (mine[k], h, w, STATUS_OK)
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
@@ -403,6 +477,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         all_zones = [folder_run.gather_ragged(local(i, wd), r.world, r.dist, r.wire_dev, width=1 + wd)
                      for i, wd in enumerate((zn.ZONE_ROW, zn.ZONE_ROW, zn.PAIR_ROW))]
         n_fallbacks = len(folder_run.gather(r, np.array([[mine[k]] for k in sorted(zfallbacks)], dtype=np.int64).reshape(-1, 1), 1))
+    all_wire = all_hist = None
+    if K:                                            # a fixed-width row per image and one pooled histogram per rank
+        all_wire = folder_run.gather(r, cwire, 1 + ct.WIRE_WIDTH)
+        all_hist = folder_run.gather_ragged(np.concatenate([[r.rank], chist.ravel()])[None], r.world, r.dist, r.wire_dev,
+                                            width=1 + chist.size)[:, 1:].sum(axis=0).reshape(chist.shape)
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
@@ -414,6 +493,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if Z:
             summary["zones"] = write_zone_match_report(os.path.join(root, "results"), items, allrows, *all_zones, IOU, ZCAP, PCAP,
                                                        n_fallbacks)
+        if K:
+            summary["contours"] = write_contour_report(os.path.join(root, "results"), items, allrows, all_wire, all_hist, TOL)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -465,6 +546,13 @@ def format_summary(summary: dict) -> str:
                              c["merged_outputs"], fmt(c["recall"]), fmt(c["precision"]), fmt(c["f1"]), fmt(c["mean_iou"])))
         if z["host_fallbacks"]:
             lines.append("%d images over a cap were matched on the host" % z["host_fallbacks"])
+    if summary.get("contours"):
+        c = summary["contours"]
+        fmt = lambda v, spec: "-" if v is None else spec % v
+        lines.append("contours within %d px (%.1f mm): " % (c["tolerance_pixels"], c["tolerance_mm"]) + "; ".join(
+            "%s precision %s, recall %s, F1 %s, mean distance %s mm (%d one-sided images)" % (
+                name, fmt(c[name]["precision"], "%.3f"), fmt(c[name]["recall"], "%.3f"), fmt(c[name]["f1"], "%.3f"),
+                fmt(c[name]["mean_distance_mm"], "%.2f"), c[name]["one_sided"]) for name in ("Bark", "Node")))
     return "\n".join(lines)
 
 
@@ -495,12 +583,20 @@ def main(argv=None):
                     help="with --zones: (output zone, target zone) rows per image the device pass keeps (default 2048, at most 4096)")
     ap.add_argument("--match_iou", type=float, default=None, metavar="T",
                     help="with --zones: two zones match when their IoU exceeds T, 0.5 <= T < 1 (default 0.5)")
+    ap.add_argument("--contours", action="store_true",
+                    help="also measure how far the contours of the final labels lie from the contours of the duals, on the "
+                         "device, and write results/contour_evaluation.csv (contour precision / recall / F1, mean contour "
+                         "distance, HD95 and Hausdorff distance in mm) and a \"contours\" entry in the summary")
+    ap.add_argument("--contour_tolerance", type=int, default=None, metavar="PX",
+                    help="with --contours: a contour pixel within PX pixels of the other contour counts as found, an integer "
+                         ">= 0 (default 2: 7.2 mm)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
     try:
         check_zone_match_arguments(args.zones, args.zones_cap, args.zone_pairs_cap, args.match_iou)
+        check_contour_arguments(args.contours, args.contour_tolerance)
     except ValueError as e:
         ap.error(str(e))
     if args.exclude_nodes:
@@ -530,6 +626,8 @@ def main(argv=None):
         kw.update(ce=True, **ce_kw)
     if args.zones:
         kw.update(zones=True, zones_cap=args.zones_cap, zone_pairs_cap=args.zone_pairs_cap, match_iou=args.match_iou)
+    if args.contours:
+        kw.update(contours=True, contour_tolerance=args.contour_tolerance)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

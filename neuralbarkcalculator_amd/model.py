@@ -218,6 +218,7 @@ class FCNResNet50:
         self._dropout_ws: Optional[torch.Tensor] = None    # nbc_dropout_draws', likewise
         self._zones_ws: Optional[torch.Tensor] = None      # nbc_label_zones', likewise
         self._zone_match_ws: Optional[torch.Tensor] = None   # nbc_match_zones', likewise
+        self._contours_ws: Optional[torch.Tensor] = None   # nbc_contour_distances', likewise
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self.device: Optional[torch.device] = None
         self.training = False
@@ -430,6 +431,41 @@ class FCNResNet50:
                                                  tgt_num.data_ptr(), cap, pair_rows.data_ptr(), pair_num.data_ptr(), pair_cap,
                                                  ws.data_ptr(), ws.numel(), cur.cuda_stream), "nbc_match_zones")
         return out_rows, out_num, tgt_rows, tgt_num, pair_rows, pair_num
+
+    def contour_distances(self, labels: torch.Tensor, target: torch.Tensor, bins: Optional[int] = None):
+        """How far the contours of label maps lie from the contours of their labelled masks, on the device
+        (nbc_contour_distances; include/nbc.h, csrc/contours.hip).  ``labels`` as ``label_zones`` takes them, ``target`` the
+        contiguous uint8 grey mask of the same shape as ``confusion`` takes it; both read only, H and W at most 4096.  Runs on
+        the current stream; the workspace (9 bytes per pixel) is cached on this object and only grows.  Returns ``(rows int64
+        [N,4,4+bins], sum_d float64 [N,4])``: per image and set (Bark output to target, Bark target to output, the same two of
+        Node) the source and destination contour pixels, the sum and the maximum of the squared distances, the histogram of
+        the distances rounded up to whole pixels, and the sum of the distances.  ``bins=None``: ``ceil(hypot(H-1, W-1)) + 1``,
+        with which the last bin is no overflow bin.  The rows equal ``contours.contours_cpu`` integer for integer; an image's
+        outputs have the same bits alone and in any batch.  Works for every architecture, since it only sees labels."""
+        from . import contours as ct
+        self._require_ctx()
+        self._check_labels(labels)
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
+            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
+        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
+            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
+        n = 1 if labels.dim() == 2 else int(labels.shape[0])
+        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        need = int(self._lib.nbc_contours_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_contour_distances refuses a [%d,%d,%d] batch (N <= 65535, H, W <= %d)" % (n, h, w, ct.MAX_SIDE))
+        bins = ct.default_bins(h, w) if bins is None else int(bins)
+        if not 2 <= bins <= ct.MAX_BINS:
+            raise ValueError("bins must lie in 2..%d" % ct.MAX_BINS)
+        rows = torch.empty((n, _lib.CONTOUR_SETS, _lib.CONTOUR_HEAD + bins), dtype=torch.int64, device=self.device)
+        sum_d = torch.empty((n, _lib.CONTOUR_SETS), dtype=torch.float64, device=self.device)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_contours_ws", need, cur)
+            _lib.check(self._lib.nbc_contour_distances(self._ctx, labels.data_ptr(),
+                                                       _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+                                                       target.data_ptr(), n, h, w, rows.data_ptr(), bins, sum_d.data_ptr(),
+                                                       ws.data_ptr(), ws.numel(), cur.cuda_stream), "nbc_contour_distances")
+        return rows, sum_d
 
     def confusion(self, labels: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """Per-image 3x3 confusion counts on the device (nbc_confusion): the pixel counting behind the evaluation loop's
@@ -958,6 +994,7 @@ class FCNResNet50:
         self._dropout_ws = None
         self._zones_ws = None
         self._zone_match_ws = None
+        self._contours_ws = None
         self._last_shape = None
 
     def __del__(self):
