@@ -546,6 +546,52 @@ int nbc_dropout_votes(nbc_ctx* ctx, int N, int H, int W, const uint64_t* image_i
  * N > 65535, H or W < 1, H * W >= 2^31, draws outside 1..65535, a votes_dev that is not 4-byte aligned. */
 int nbc_vote_summary(const uint32_t* votes_dev, int N, int H, int W, int draws, uint8_t* labels_dev, uint8_t* support_dev,
                      int64_t* stats_dev, void* hip_stream);
+/* The vote words of D label maps of each image that are on the device already, whatever made them (the flip views below, or a
+ * caller's own): the counting nbc_dropout_votes does pass by pass, on its own.  No context: csrc/dropout_votes.hip.
+ * labels_dev  uint8 [D][N][H][W], map-major like the draws of a pass; any alignment.  A label outside {0,1,2} votes nowhere.
+ * votes_dev   uint32 [N][H][W], 16-byte aligned
+ * accumulate  0: the words are overwritten (no memset is needed); 1: the D maps are added to what the words hold.  The caller
+ *             keeps the total of the maps added into a word at or below 65535.
+ * Integer sums: an image's words are the same alone, in any batch and on any stream.  Runs on hip_stream (the caller's
+ * current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null pointer, N < 1 or N > 65535, H or W < 1,
+ * H * W >= 2^31, D outside 1..65535, a votes_dev that is not 16-byte aligned. */
+int nbc_vote_tally(const uint8_t* labels_dev, int N, int D, int H, int W, uint32_t* votes_dev, int accumulate, void* hip_stream);
+
+/* ---- the flip views the training augmented over ------------------------------------------------
+ * The reference trains with RandomHorizontalFlip and RandomVerticalFlip on the sample and its mask (__main__.py:160-164) and
+ * never uses that at prediction time.  These two calls make the mirror images of a batch and bring the network's answers for
+ * them back into one orientation; the forward between them is nbc_forward on the stack, as it stands.
+ *   views    a mask of NBC_TTA_* bits, 1..15; its V views are taken in ascending bit order
+ *   stack    view-major, like [draws][N] of nbc_dropout_draws: entry j * N + i is view j of image i
+ *   aligned  the un-flipped view: a_j[i][c][y][x] = v_j[i][c][y'][x'], y' = h-1-y if view j mirrors rows, x' = w-1-x if it
+ *            mirrors columns -- consistent with interpolate(align_corners=False) for every H and W
+ *   merged   m = (((a_0 + a_1) + a_2) + a_3) / float(V): f32 adds in view order, no contraction, one IEEE f32 division; V = 1
+ *            gives the view's own bits, a NaN in any view gives NaN */
+enum {
+  NBC_TTA_IDENTITY = 1,
+  NBC_TTA_HFLIP = 2,    /* columns mirrored: x[..., W-1-j] */
+  NBC_TTA_VFLIP = 4,    /* rows mirrored */
+  NBC_TTA_HVFLIP = 8,   /* both */
+  NBC_TTA_FLIPS = 15
+};
+/* The V views of a batch in one launch.  No context: csrc/tta.hip.
+ * x_dev    NBC_IN_U8_NHWC (a pixel is 3 bytes: rows are mirrored by pixel; any alignment) or NBC_IN_F32_NCHW (per plane;
+ *          4-byte aligned)
+ * out_dev  [V][N] entries in x's layout; must not overlap x
+ * Each source row is read once and written V times: H * W * 3 * (1 + V) bytes per u8 image.  Runs on hip_stream (the caller's
+ * current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null pointer, an unknown dtype, views outside
+ * 1..15, N < 1 or V * N > 65535, H or W < 1, H * W >= 2^31, an f32 pointer that is not 4-byte aligned, out_dev overlapping
+ * x_dev. */
+int nbc_tta_views(const void* x_dev, int x_dtype, int N, int H, int W, int views, void* out_dev, void* hip_stream);
+/* The aligned views and their mean from the low-resolution logits of a stacked forward.  No context: csrc/tta.hip.
+ * lowres_views_dev  float32 [V][N][3][h][w]: view j's logits in view j's orientation
+ * merged_dev        float32 [N][3][h][w]; overwritten
+ * aligned_dev       nullable, float32 [V][N][3][h][w]; must not alias the input
+ * An element of merged depends on the V elements it is made of alone: an image's bits are the same alone, in any batch and
+ * on any stream.  NBC_ERR_INVALID, before any HIP call: as nbc_tta_views on h and w (every pointer 4-byte aligned), and an
+ * output that overlaps the input. */
+int nbc_tta_merge(const float* lowres_views_dev, int N, int h, int w, int views, float* merged_dev, float* aligned_dev,
+                  void* hip_stream);
 
 /* ---- the zones of a label map ------------------------------------------------------------------
  * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and

@@ -27,6 +27,7 @@ ZONE_PAIR_ROW = 3                                   # NBC_ZONE_PAIR_ROW
 PAIRS_MAX_CAP = 4096                                # NBC_ZONE_PAIRS_MAX_CAP
 CONTOUR_SETS, CONTOUR_HEAD = 4, 4                   # NBC_CONTOUR_SETS, NBC_CONTOUR_HEAD
 CONTOUR_MAX_SIDE = 4096                             # NBC_CONTOUR_MAX_SIDE
+TTA_IDENTITY, TTA_HFLIP, TTA_VFLIP, TTA_HVFLIP, TTA_FLIPS = 1, 2, 4, 8, 15   # NBC_TTA_*
 
 
 class NbcTensor(C.Structure):
@@ -124,6 +125,9 @@ SIGNATURES = {
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
     "nbc_vote_summary": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbc_vote_tally": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nbc_tta_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbc_tta_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

@@ -180,6 +180,17 @@ extern "C" int nbc_vote_decode(uint32_t word, int draws, uint8_t* label, uint8_t
   return NBC_OK;
 }
 
+extern "C" int nbc_vote_tally(const uint8_t* labels_dev, int N, int D, int H, int W, uint32_t* votes_dev, int accumulate, void* hip_stream) {
+  constexpr const char* who = "nbc_vote_tally";
+  if (!labels_dev || !votes_dev) return fail(who, NBC_ERR_INVALID, "null argument");
+  if (!per_image_shape_ok(N, H, W)) return fail(who, NBC_ERR_INVALID, kPerImageShape);
+  if (D < 1 || D > kVoteMaxDraws) return fail(who, NBC_ERR_INVALID, "D must lie in 1..65535");
+  if (reinterpret_cast<uintptr_t>(votes_dev) & 15u) return fail(who, NBC_ERR_INVALID, "votes_dev must be 16-byte aligned");
+  const hipError_t e = launch_vote_accumulate(labels_dev, D, N, (long long)H * W, votes_dev, accumulate == 0, static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
+  return NBC_OK;
+}
+
 extern "C" int nbc_vote_summary(const uint32_t* votes_dev, int N, int H, int W, int draws, uint8_t* labels_dev, uint8_t* support_dev,
                                 int64_t* stats_dev, void* hip_stream) {
   if (!votes_dev || !stats_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");

@@ -300,7 +300,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
                     class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
                     zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
-                    contour_tolerance: int = None) -> dict:
+                    contour_tolerance: int = None, tta="none") -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -316,6 +316,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ``contours``: also the contour distances of the final labels against the duals (module docstring), with
     ``contour_tolerance`` pixels (an integer >= 0, default ``contours.DEFAULT_TOLERANCE``) as the tolerance of the contour
     precision, recall and F1.
+    ``tta`` ("hflip", "vflip", "flips"; "none" = off): ``FCNResNet50.predict_labels_tta`` stands where ``predict_labels`` does,
+    so every row and every optional pass is about the mean of the flip views; ``batch`` keeps counting images
+    (default 1, 2 in bf16) and the summary gains ``"tta": {"views": [...]}``.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
@@ -331,7 +334,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     CBINS = ct.default_bins(target_size, target_size)   # the bins of the largest frame: the pooled histogram's
     if ce:
         class_weights = check_class_weights(class_weights)
-    r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size)
+    T = folder_run.check_tta_arguments(tta)         # the view mask, 0 = off
+    r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size,
+                            stack=max(1, len(folder_run.tta_view_names(T))))
     dev, batch = r.dev, r.batch
 
     def warm(m):                                     # the remove_small_zones workspace and, with ``loss`` / ``ce``, theirs
@@ -401,7 +406,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce else None
-        labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
+        if T:                                                         # the same call on the mean of the flip views
+            labels, _ = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg)
+        else:
+            labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
         if ce:                                                        # CustomWeightedCrossEntropy (utils.py:151-165)
             sums, _ = mdl.pixel_cross_entropy(lg, tgt)
@@ -495,6 +503,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                                                        n_fallbacks)
         if K:
             summary["contours"] = write_contour_report(os.path.join(root, "results"), items, allrows, all_wire, all_hist, TOL)
+        if T:
+            summary["tta"] = {"views": folder_run.tta_view_names(T)}
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -628,6 +638,8 @@ def main(argv=None):
         kw.update(zones=True, zones_cap=args.zones_cap, zone_pairs_cap=args.zone_pairs_cap, match_iou=args.match_iou)
     if args.contours:
         kw.update(contours=True, contour_tolerance=args.contour_tolerance)
+    if args.tta != "none":
+        kw["tta"] = args.tta
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

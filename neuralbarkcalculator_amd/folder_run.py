@@ -415,10 +415,95 @@ def vote_report(images: Sequence[tuple], draws: int):
     return rows, {"images": n, "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}}
 
 
+# ---- the flip views the training augmented over (--tta): masks, argument checks, the report -------------------------------
+TTA_CHOICES = ("none", "hflip", "vflip", "flips")
+TTA_MASKS = {"none": 0, "hflip": 3, "vflip": 5, "flips": 15}          # NBC_TTA_* bits of include/nbc.h; identity is bit 0
+TTA_VIEW_NAMES = ("identity", "hflip", "vflip", "hvflip")             # bit 0..3
+
+
+def tta_mask(tta) -> int:
+    """The view mask of ``--tta`` (0 = off): one of ``TTA_CHOICES``, None (off) or a mask in 1..15 itself."""
+    if tta is None:
+        return 0
+    if isinstance(tta, str):
+        if tta not in TTA_MASKS:
+            raise ValueError("--tta must be one of %s, got %r" % (", ".join(TTA_CHOICES), tta))
+        return TTA_MASKS[tta]
+    if isinstance(tta, bool) or not 0 <= int(tta) <= 15:
+        raise ValueError("--tta must be one of %s, got %r" % (", ".join(TTA_CHOICES), tta))
+    return int(tta)
+
+
+def tta_view_names(mask: int) -> List[str]:
+    """The names of the views of a mask, in the order of the stack (ascending bit order)."""
+    return [TTA_VIEW_NAMES[b] for b in range(4) if (int(mask) >> b) & 1]
+
+
+def check_tta_arguments(tta, tta_votes: bool = False, dropout_draws=None, only_preprocess: bool = False) -> int:
+    """``ValueError`` for what ``--tta`` and ``--tta_votes`` refuse before any device is touched: ``--tta`` with
+    ``--dropout_draws`` (the draws read the features of a plain forward) or with ``--only_preprocess`` (no network runs),
+    ``--tta_votes`` without ``--tta``.  Returns the view mask (0 = off)."""
+    mask = tta_mask(tta)
+    if not mask:
+        if tta_votes:
+            raise ValueError("--tta_votes needs --tta")
+        return 0
+    if dropout_draws:
+        raise ValueError("--tta cannot go with --dropout_draws: TTA under Dropout draws is left out (the draws read the features "
+                         "of a plain forward)")
+    if only_preprocess:
+        raise ValueError("--tta runs the network: it cannot go with --only_preprocess")
+    return mask
+
+
+def tta_columns(mask: int) -> List[str]:
+    cols = ["Name", "Type", "Views"]
+    for v in tta_view_names(mask):
+        cols += ["%s Bark %%" % v, "%s Node %%" % v]
+    return cols + ["Bark %", "Node %", "Bark % spread", "Node % spread", "Unanimous %", "Mean support"]
+
+
+def tta_report(images: Sequence[tuple], views: int):
+    """The rows of ``tta_stats.csv`` (header first) and the folder summary.  ``images``: per image ``(name, wood, h, w,
+    merged_counts [3], view_counts [V][3], stats [10])`` with the pixels per class of the merged final labels, of each view's
+    own final labels (the order of the stack) and the ten integers of nbc_vote_summary over the views (D = V).  Every
+    percentage is printed as ``final_stats.csv`` prints one (``percent_string``); the spreads ``100 (max - min) / (h w)`` over
+    the views' counts, the unanimous percentage and the mean support are each one correctly rounded division of exact
+    integers, formatted '{:.5f}' (``vote_report``'s arithmetic).  The summary's means: the merged and the identity pair (None
+    for a mask without the identity view), their mean absolute difference, the spreads and the unanimous share."""
+    names = tta_view_names(views)
+    nv = len(names)
+    has_identity = bool(int(views) & 1)
+    rows, sums = [tta_columns(views)], {}
+    for name, wood, h, w, mc, vc, st in images:
+        px = h * w
+        mc, st = [int(v) for v in mc], [int(v) for v in st]
+        vc = [[int(v) for v in c3] for c3 in vc]
+        assert len(vc) == nv and len(st) == VOTE_STATS and len(mc) == 3
+        row = [name, wood, "+".join(names)]
+        for c3 in vc:
+            row += [percent_string(c3[1], px), percent_string(c3[2], px)]
+        spread = [(100 * (max(c3[k] for c3 in vc) - min(c3[k] for c3 in vc))) / px for k in (1, 2)]
+        figures = {"merged_bark": (100 * mc[1]) / px, "merged_node": (100 * mc[2]) / px, "bark_spread": spread[0],
+                   "node_spread": spread[1], "unanimous": (100 * (st[3] + st[4] + st[5])) / px, "mean_support": st[6] / (nv * px)}
+        if has_identity:
+            figures.update(identity_bark=(100 * vc[0][1]) / px, identity_node=(100 * vc[0][2]) / px,
+                           abs_diff_bark=abs(100 * (mc[1] - vc[0][1])) / px, abs_diff_node=abs(100 * (mc[2] - vc[0][2])) / px)
+        row += [percent_string(mc[1], px), percent_string(mc[2], px), "{:.5f}".format(spread[0]), "{:.5f}".format(spread[1]),
+                "{:.5f}".format(figures["unanimous"]), "{:.5f}".format(figures["mean_support"])]
+        rows.append(row)
+        for k, v in figures.items():
+            sums[k] = sums.get(k, 0.0) + v
+    n = len(images)
+    return rows, {"images": n, "views": names, "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}}
+
+
 def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
-             target_size: int = 1024) -> SimpleNamespace:
+             target_size: int = 1024, stack: int = 1) -> SimpleNamespace:
     """The rank context of one folder run, and the state its later steps fill in.  An already initialised process group (gloo
-    in the one-GPU rehearsals) is used as it is; ``wire_dev`` is where its collectives' tensors live (``collective_device``)."""
+    in the one-GPU rehearsals) is used as it is; ``wire_dev`` is where its collectives' tensors live (``collective_device``).
+    ``stack``: the entries the forward runs per image (the V views of ``--tta``; 1 otherwise): ``batch`` keeps counting
+    images, and its default shrinks so that the stack stays at a size the forward is already run at (4, or 8 in bf16)."""
     import time
     from collections import defaultdict
     import torch
@@ -435,7 +520,11 @@ def open_run(root: str, tool: str, precision: str, device_index: int = None, bat
     r.dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(r.dev)
     r.wire_dev = collective_device(r.dist, r.dev)
-    r.batch = (8 if precision == "bf16" else 2) if batch is None else batch
+    r.stack = max(1, int(stack))
+    if r.stack > 1:
+        r.batch = (2 if precision == "bf16" else 1) if batch is None else batch
+    else:
+        r.batch = (8 if precision == "bf16" else 2) if batch is None else batch
     r.n_streams = 4 if streams is None else max(1, int(streams))
     r.depth = r.n_streams + 1                        # slots of the pinned rings: one more than batches in flight
     r.marker = AbandonMarker(root)
@@ -470,12 +559,13 @@ def bring_up_without_model(r, make_dirs) -> None:
 
 
 def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool, make_dirs, warm=None,
-             normalization=None) -> None:
+             normalization=None, stack: int = 1) -> None:
     """Rank 0's ``make_dirs(root)`` and the start barrier, then ``r.models`` (``r.n_streams`` objects on one copy of the
     weights), ``r.gpu_streams``, and the resolved ``r.arch`` / ``r.precision``.  ``warm(model)``: the driver's own workspaces, grown
     to their largest size once like the forward's.  ``normalization``: the ``(mean, std)`` of the uint8 ingest
     (``resolve_normalization``), set on every model object before anything runs (a clone owns its context and would start on
-    the defaults); None leaves the defaults of models.py:208-209."""
+    the defaults); None leaves the defaults of models.py:208-209.  ``stack``: the entries the forward runs per image (the views
+    of ``--tta``; ``open_run``'s ``stack`` counts as well): the workspace is reserved for ``stack x r.batch`` entries."""
     import time
     import torch
     from .model import MODELS
@@ -504,7 +594,7 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
     # side streams only: the default stream stays with whatever else the driver runs on the device
     r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
     for m in r.models:                               # the largest workspace once: a context's buffers only grow, and a folder of
-        m.reserve(r.batch, r.target_size, r.target_size)   # rising heights would otherwise free and reallocate them shape after shape
+        m.reserve(r.batch * max(r.stack, int(stack)), r.target_size, r.target_size)   # rising heights would otherwise free and reallocate them shape after shape
         if warm is not None:
             warm(m)
     torch.cuda.synchronize(r.dev)                    # weights uploaded / received before any side stream reads them
@@ -732,6 +822,10 @@ def add_shared_arguments(ap) -> None:
                          "as the shipped tool ran them (fp32, FCN-ResNet-50 only; --precision auto then means fp32); image_f16x2: "
                          "the same statistics on the f16x2 pipe (--precision f16x2, or auto: f16x2 under its guards, else image "
                          "in fp32)")
+    ap.add_argument("--tta", choices=list(TTA_CHOICES), default="none",
+                    help="average the flip views the training augmented over: hflip / vflip (the image and its mirror image) or "
+                         "flips (all four); the low-resolution logits of the un-flipped views are averaged and everything "
+                         "downstream is about that mean.  --batch keeps counting images (default 1, 2 in bf16)")
     ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
                     help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
                          "(with --std; default: the constants of the reference's model class)")

@@ -178,6 +178,31 @@ def conv_tile_info(precision: str, tile: int):
     return tuple(x.value for x in v)
 
 
+TTA_VIEWS = {"hflip": _lib.TTA_IDENTITY | _lib.TTA_HFLIP, "vflip": _lib.TTA_IDENTITY | _lib.TTA_VFLIP, "flips": _lib.TTA_FLIPS}
+TTA_VIEW_NAMES = ("identity", "hflip", "vflip", "hvflip")        # bit 0..3 of a view mask (NBC_TTA_*)
+
+
+def resolve_tta_views(views) -> int:
+    """The view mask (NBC_TTA_* bits, 1..15) of ``"hflip"`` (identity + hflip), ``"vflip"`` (identity + vflip), ``"flips"``
+    (all four) or of a mask itself; ``ValueError`` otherwise."""
+    if isinstance(views, str):
+        if views not in TTA_VIEWS:
+            raise ValueError("views must be one of %s or a mask in 1..15, got %r" % (", ".join(sorted(TTA_VIEWS)), views))
+        return TTA_VIEWS[views]
+    if isinstance(views, bool) or not isinstance(views, (int, np.integer)) or not 1 <= int(views) <= _lib.TTA_FLIPS:
+        raise ValueError("views must be one of %s or a mask in 1..15, got %r" % (", ".join(sorted(TTA_VIEWS)), views))
+    return int(views)
+
+
+def tta_view_count(mask: int) -> int:
+    return bin(int(mask)).count("1")
+
+
+def tta_view_names(mask: int):
+    """The names of the views of a mask, in the order of the stack."""
+    return [TTA_VIEW_NAMES[b] for b in range(4) if (int(mask) >> b) & 1]
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 
@@ -334,6 +359,121 @@ class FCNResNet50:
         if small_zones:
             labels, counts = self.remove_small_zones(labels, exclude_nodes=exclude_nodes)
         return (labels, counts, lowres) if return_lowres else (labels, counts)
+
+    # ---- the flip views the training augmented over (include/nbc.h) ---------
+    def tta_views(self, x: torch.Tensor, views="flips") -> torch.Tensor:
+        """The mirror images of a batch on the device (nbc_tta_views): ``x`` as the model takes it (f32 ``[N,3,H,W]`` or uint8
+        ``[N,H,W,3]``) -> the stack ``[V*N, ...]`` in the same layout, view-major (entry ``j * N + i`` is view j of image i), the
+        views of the mask ``views`` (``resolve_tta_views``) in ascending bit order.  Runs on the current stream."""
+        self._require_ctx()
+        mask = resolve_tta_views(views)
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 4 or x.numel() == 0 or not (
+                (x.dtype == torch.float32 and x.shape[1] == 3) or (x.dtype == torch.uint8 and x.shape[3] == 3)):
+            raise ValueError("x must be a non-empty float32 [N,3,H,W] or uint8 [N,H,W,3] tensor on %s" % (self.device,))
+        x = x.contiguous()
+        f32 = x.dtype == torch.float32
+        n, h, w = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) if f32 else (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
+        out = torch.empty((tta_view_count(mask) * n,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_tta_views(x.data_ptr(), _lib.IN_F32_NCHW if f32 else _lib.IN_U8_NHWC, n, h, w, mask,
+                                               out.data_ptr(), cur.cuda_stream), "nbc_tta_views")
+        return out
+
+    def tta_merge(self, lowres_views: torch.Tensor, n: int, views="flips", return_aligned: bool = False):
+        """The merged low-resolution logits of a stacked forward (nbc_tta_merge): ``lowres_views`` f32 ``[V*N,3,h,w]`` (or
+        ``[V,N,3,h,w]``), view j's logits in view j's orientation -> ``m`` f32 ``[N,3,h,w]``, the mean of the un-flipped views
+        (f32 adds in view order, one IEEE division); with ``return_aligned`` also the un-flipped views f32 ``[V,N,3,h,w]``."""
+        self._require_ctx()
+        mask = resolve_tta_views(views)
+        v, n = tta_view_count(mask), int(n)
+        if lowres_views.device != self.device or lowres_views.dtype != torch.float32 or lowres_views.dim() not in (4, 5) \
+                or lowres_views.numel() == 0 or lowres_views.shape[-3] != NUM_CLASSES \
+                or int(np.prod(lowres_views.shape[:-3])) != v * n or n < 1:
+            raise ValueError("lowres_views must be a non-empty float32 [%d*%d,3,h,w] tensor on %s" % (v, n, self.device))
+        lowres_views = lowres_views.contiguous()
+        lh, lw = int(lowres_views.shape[-2]), int(lowres_views.shape[-1])
+        merged = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
+        aligned = torch.empty((v, n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device) if return_aligned else None
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_tta_merge(lowres_views.data_ptr(), n, lh, lw, mask, merged.data_ptr(),
+                                               aligned.data_ptr() if aligned is not None else None, cur.cuda_stream), "nbc_tta_merge")
+        return (merged, aligned) if return_aligned else merged
+
+    def vote_tally(self, labels: torch.Tensor, n: int) -> torch.Tensor:
+        """The vote words of D label maps per image (nbc_vote_tally; the definition: csrc/votes.hpp): ``labels`` contiguous
+        uint8 ``[D*N,H,W]`` (or ``[D,N,H,W]``), map-major -> ``[N,H,W]`` int32 holding the uint32 words (n1 in the low half, n2
+        in the high half).  A label outside {0,1,2} votes nowhere.  ``nbc_vote_summary`` decides on them."""
+        self._require_ctx()
+        n = int(n)
+        if labels.device != self.device or labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.dim() not in (3, 4) \
+                or labels.numel() == 0 or n < 1 or int(np.prod(labels.shape[:-2])) % n:
+            raise ValueError("labels must be a non-empty contiguous uint8 [D*N,H,W] tensor on %s" % (self.device,))
+        d = int(np.prod(labels.shape[:-2])) // n
+        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        words = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_vote_tally(labels.data_ptr(), n, d, h, w, words.data_ptr(), 0, cur.cuda_stream), "nbc_vote_tally")
+        return words
+
+    def predict_labels_tta(self, x: torch.Tensor, views="flips", exclude_nodes: bool = False,
+                           labels_dtype: torch.dtype = torch.int64, small_zones: bool = False,
+                           logits_full: Optional[torch.Tensor] = None, return_lowres: bool = False,
+                           return_views: bool = False, min_pixels: int = 150):
+        """``predict_labels`` on the mean of the flip views the training augmented over.  A composition of
+        calls and nothing more: ``tta_views``, one forward of the V*N stack, ``tta_merge``, then today's tail on the merged
+        low-resolution logits ``m`` -- ``upsample_argmax`` (into ``logits_full`` when given), ``remove_small_zones``
+        (``small_zones``, threshold ``min_pixels``), the ``exclude_nodes`` remap, the counts.  ``views``: "hflip", "vflip",
+        "flips" or a mask of ``_lib.TTA_*`` bits; the mask 1 gives ``predict_labels``' own bits.
+
+        Returns what ``predict_labels`` returns, for ``m`` (``return_lowres`` appends ``m`` itself).  ``return_views`` appends
+        ``(view_counts int64 [V,N,3], support uint8 [N,H,W], stats int64 [N,10], aligned f32 [V,N,3,h,w])``: each un-flipped
+        view taken through the same tail on its own -- its pixels per class --, and the per-pixel vote of the V final label
+        maps (``dropout_votes``' support byte and ten statistics, D = V).  Afterwards no forward counts as the last one:
+        ``dropout_draws`` raises until a plain forward has run."""
+        n, h, w = self._check_input(x)
+        mask = resolve_tta_views(views)
+        v = tta_view_count(mask)
+        if labels_dtype not in (torch.int64, torch.uint8):
+            raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
+        if int(min_pixels) < 0:
+            raise ValueError("min_pixels must not be negative")
+        if v * n > 65535:
+            raise ValueError("the stack of %d views of %d images exceeds 65535 entries" % (v, n))
+        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
+                                        or not logits_full.is_contiguous()
+                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
+            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
+                                                                                                    self.device))
+        lh, lw = out_hw(h, w, self.ARCH)
+        stack = self.tta_views(x, mask)
+        lowres_views = torch.empty((v * n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
+        try:
+            self._forward(stack, v * n, h, w, lowres=lowres_views)
+        finally:
+            self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
+        merged = self.tta_merge(lowres_views, n, mask, return_aligned=return_views)
+        aligned = None
+        if return_views:
+            merged, aligned = merged
+        remap_late = bool(small_zones)               # remove_small_zones comes before the remap (models.py:271-276)
+        labels, counts = self.upsample_argmax(merged, (h, w), exclude_nodes=exclude_nodes and not remap_late,
+                                              labels_dtype=labels_dtype, logits_full=logits_full)
+        if small_zones:
+            labels, counts = self.remove_small_zones(labels, exclude_nodes=exclude_nodes, min_pixels=min_pixels)
+        out = (labels, counts) + ((merged,) if return_lowres else ())
+        if not return_views:
+            return out
+        vlabels, vcounts = self.upsample_argmax(aligned.view(v * n, NUM_CLASSES, lh, lw), (h, w),
+                                                exclude_nodes=exclude_nodes and not remap_late, labels_dtype=torch.uint8)
+        if small_zones:
+            vlabels, vcounts = self.remove_small_zones(vlabels, exclude_nodes=exclude_nodes, min_pixels=min_pixels)
+        words = self.vote_tally(vlabels, n)
+        support = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        stats = torch.empty((n, _lib.VOTE_STATS), dtype=torch.int64, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_vote_summary(words.data_ptr(), n, h, w, v, None, support.data_ptr(), stats.data_ptr(),
+                                                  cur.cuda_stream), "nbc_vote_summary")
+        return out + (vcounts.view(v, n, NUM_CLASSES), support, stats, aligned)
 
     def lowres_logits(self, x: torch.Tensor) -> torch.Tensor:
         """Output of ``classifier.4`` (models.py:121) before the upsample: f32 ``[N,3,h,w]``."""
@@ -653,9 +793,11 @@ class FCNResNet50:
         return out, lit
 
     def upsample_argmax(self, lowres: torch.Tensor, size: Tuple[int, int], exclude_nodes: bool = False,
-                        labels_dtype: torch.dtype = torch.int64, return_logits: bool = False):
+                        labels_dtype: torch.dtype = torch.int64, return_logits: bool = False,
+                        logits_full: Optional[torch.Tensor] = None):
         """Tail of the path on caller-supplied low-res logits f32 ``[N,3,h,w]``:
-        bicubic to ``size`` (models.py:38-41), argmax (models.py:270), remap, counts."""
+        bicubic to ``size`` (models.py:38-41), argmax (models.py:270), remap, counts.  ``logits_full``: an optional contiguous
+        f32 ``[N,3,H,W]`` tensor on this model's device that receives the upsampled logits (``return_logits`` allocates one)."""
         self._require_ctx()
         if lowres.dtype != torch.float32 or lowres.dim() != 4 or lowres.shape[1] != NUM_CLASSES:
             raise RuntimeError("expected float32 [N,3,h,w]")
@@ -664,7 +806,12 @@ class FCNResNet50:
         H, W = int(size[0]), int(size[1])
         labels = torch.empty((n, H, W), dtype=labels_dtype, device=self.device)
         counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
-        logits = torch.empty((n, NUM_CLASSES, H, W), dtype=torch.float32, device=self.device) if return_logits else None
+        logits = logits_full
+        if logits is not None and (logits.device != self.device or logits.dtype != torch.float32 or not logits.is_contiguous()
+                                   or tuple(logits.shape) != (n, NUM_CLASSES, H, W)):
+            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, H, W, self.device))
+        if logits is None and return_logits:
+            logits = torch.empty((n, NUM_CLASSES, H, W), dtype=torch.float32, device=self.device)
         ldt = _lib.LABEL_I64 if labels_dtype == torch.int64 else _lib.LABEL_U8
         with self._on_stream() as cur:
             rc = self._lib.nbc_upsample_argmax(self._ctx, lowres.data_ptr(), n, lh, lw, H, W,

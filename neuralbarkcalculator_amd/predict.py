@@ -45,14 +45,15 @@ CSV_HEADER = ["Name", "Type", "Image Size", "Output Bark %", "Bark area (mm^2)",
 ROW_WIDTH = 5                                                              # (global_idx, H, W, count_1, count_2)
 
 
-def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False) -> None:
-    """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well."""
+def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False, tta_votes: bool = False) -> None:
+    """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well; ``tta_votes``: the one of ``--tta_votes``."""
     present = os.listdir(os.path.join(root, "samples"))
     wood_types = [w for w in WOOD_TYPES if w in present]
     for w in wood_types:
         os.makedirs(os.path.join(root, "processed", "samples", w), exist_ok=True)
     if not only_preprocess:
-        for level in ("combined_images", "outputs") + (("dropout_votes", "dropout_support") if votes else ()):
+        for level in ("combined_images", "outputs") + (("dropout_votes", "dropout_support") if votes else ()) + \
+                (("tta_support",) if tta_votes else ()):
             for w in wood_types:
                 os.makedirs(os.path.join(root, "results", level, w), exist_ok=True)
 
@@ -337,6 +338,28 @@ def write_dropout_report(results_dir: str, items, allrows, alld, draws: int, p: 
     return summary
 
 
+def write_tta_report(results_dir: str, items, allrows, allt, views: int, precision: str, bn_stats: str) -> dict:
+    """``tta_stats.csv`` (tab separated) and ``tta_summary.json`` from the gathered rows: ``allrows`` as ``final_stats.csv`` is
+    written from (the merged labels' counts), ``allt`` the ``(global_idx, merged counts 3, V x 3 view counts, 10 vote
+    statistics)`` rows of ``--tta``.  Returns the summary."""
+    import json
+    nv = len(folder_run.tta_view_names(views))
+    by_idx = {int(g[0]): g[1:] for g in allt}
+    images = []
+    for g in allrows:
+        t = by_idx[int(g[0])]
+        images.append((items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), t[:3], t[3: 3 + 3 * nv].reshape(nv, 3),
+                       t[3 + 3 * nv:]))
+    table, summary = folder_run.tta_report(images, views)
+    with open(os.path.join(results_dir, "tta_stats.csv"), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    summary = dict({"precision": precision, "bn_stats": bn_stats}, **summary)
+    with open(os.path.join(results_dir, "tta_summary.json"), "w") as f:
+        json.dump(summary, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return summary
+
+
 def write_zones_report(results_dir: str, items, allrows, allz, cap: int, host_fallbacks: int) -> dict:
     """``zones.csv``, ``zones_summary.csv`` (tab separated, like ``final_stats.csv``) and ``zones_summary.json`` from the
     gathered rows: ``allrows`` as ``final_stats.csv`` is written from (one per image: its size), ``allz`` the
@@ -396,7 +419,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    batch: int = None, window: int = 64, target_size: int = 1024, autotune: bool = False, calibrate: bool = True,
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
-                   dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None) -> dict:
+                   dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None,
+                   tta="none", tta_votes: bool = False) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -438,6 +462,12 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     image) and ``results/zones_summary.json`` (``write_zones_report``); every other file stays byte for byte what it is
     without the flag.  The returned dict gains ``zones_host_fallbacks``, this rank's images that took the host path, and ``zones_report_s``, the
     seconds the gather and (on rank 0) the three files took after the loop.
+    ``tta`` ("hflip", "vflip", "flips"; "none" = off; not with ``dropout_draws``): ``FCNResNet50.predict_labels_tta`` stands where
+    ``predict_labels`` does, so the label PNGs, ``final_stats.csv`` and ``zones`` are those of the mean of the flip views
+    (DESIGN.md 3.15).  ``batch`` keeps counting images (default 1, 2 in bf16): the forward runs V x batch entries.  Each view's
+    own counts and the vote statistics over the views ride back beside the labels; rank 0 writes ``results/tta_stats.csv``
+    and ``results/tta_summary.json`` (``folder_run.tta_report``).  ``tta_votes`` (with ``tta`` only): also
+    ``results/tta_support/<wood>/<name>``, the support byte of the views' vote (grey, 255 = every view agrees).
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -450,6 +480,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     Z = bool(zones)
     folder_run.check_zones_arguments(Z, zones_cap)   # refusals first: nothing has touched a device yet
     ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
+    T = folder_run.check_tta_arguments(tta, tta_votes, D)   # the view mask, 0 = off
+    NV = len(folder_run.tta_view_names(T))
+    TS = bool(tta_votes)
     old_stats = None
     if V and not D:
         raise ValueError("--dropout_votes needs --dropout_draws")
@@ -457,16 +490,16 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         folder_run.check_dropout_arguments(D, dropout_p, dropout_seed, dropout_compare, arch)
         if dropout_compare is not None:
             old_stats = folder_run.read_shipped_stats(dropout_compare)
-    r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size)
+    r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size, stack=max(NV, 1))
     dev, batch, prof, clock = r.dev, r.batch, r.prof, time.perf_counter
     pre_model = FCNResNet50(precision).to(dev)      # its own context: the pool's device resizes never touch the predictor's
 
-    def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel)
+    def warm(m):                                     # the remove_small_zones workspace (9 bytes per pixel; --tta: of the views' stack)
         if small_zones:
-            m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+            m.remove_small_zones(torch.zeros((batch * r.stack, target_size, target_size), dtype=torch.uint8, device=dev))
         if Z:                                        # and label_zones' (5 bytes per pixel)
             m.label_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev), cap=ZCAP)
-    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, lambda root_: generate_folders(root_, votes=V), warm,
+    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, lambda root_: generate_folders(root_, votes=V, tta_votes=TS), warm,
                         normalization=normalization)
     if D:
         folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
@@ -483,6 +516,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     drows = np.zeros((len(mine), 1 + 3 * D), dtype=np.int64)     # (global_idx, D x 3 counts) of the Dropout draws
     VROW = 2 + folder_run.VOTE_STATS
     vrows = np.zeros((len(mine), VROW), dtype=np.int64)          # (global_idx, 10 vote statistics, changed pixels)
+    TROW = 1 + 3 + 3 * NV + folder_run.VOTE_STATS
+    trows = np.zeros((len(mine), TROW), dtype=np.int64)          # (global_idx, merged counts, V x 3 view counts, 10 vote statistics)
     zrows = {}                                       # k -> the image's zone rows int64 [zones, 10] (--zones)
     zfallbacks = []                                  # the k whose rows came from the host: more zones than ZCAP
     resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
@@ -512,7 +547,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None):
+    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None, views=None):
         """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row; + the
         zone rows: ``zone`` = (the device's rows, or None when the image has more zones than the cap: the host computes them)."""
         d = items[mine[k]]
@@ -530,6 +565,13 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                 label_paths.append(vpath)
                 write_png(vpath, img, lvl_lab)
             vrows[k, 0], vrows[k, 1:-1], vrows[k, -1] = mine[k], vstats, int(np.count_nonzero(vlab != lab))
+        if views is not None:                        # --tta: (merged counts, the views' counts, the vote statistics, the support plane or None)
+            mcounts, vcounts, tstats, sup = views
+            trows[k, 0], trows[k, 1:4], trows[k, 4: 4 + 3 * NV], trows[k, 4 + 3 * NV:] = mine[k], mcounts, vcounts.reshape(-1), tstats
+            if sup is not None:
+                spath = os.path.join(root, "results", "tta_support", d["wood"], d["name"])
+                label_paths.append(spath)
+                write_png(spath, sup, lvl_lab)
         prof["pool.write_labels"] += clock() - t0
         if zone is not None:
             t1 = clock()
@@ -551,6 +593,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     # the zones' slots: ZCAP rows per image and the zone counts
     zring = [(torch.empty((batch, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(), torch.empty(batch, dtype=torch.int64).pin_memory())
              for _ in range(r.depth)] if Z else None
+    # --tta: per slot the views' counts and the vote statistics per image, and (--tta_votes) the support planes
+    tring = [(torch.empty((NV, batch, 3), dtype=torch.int64).pin_memory(),
+              torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
+              torch.empty(full if TS else 0, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if T else None
     tuned = set()
 
     def launch(slot, sid, part, x):
@@ -559,10 +605,22 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:   # an oversized stale processed frame (run_loop)
             ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
         if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
-            mdl.autotune(x)                          # once per distinct full-batch shape and model object
+            mdl.autotune(mdl.tta_views(x, T) if T else x)   # once per distinct full-batch shape and model object
             tuned.add((sid, (n, h, w)))
-        labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                            small_zones=small_zones)   # models.py:269-276 on the device
+        if T:                                        # the same tail on the mean of the flip views; the views' own figures beside it
+            if tring[slot][0].shape[1] < n or (TS and tring[slot][2].numel() < need):
+                tring[slot] = (torch.empty((NV, n, 3), dtype=torch.int64).pin_memory(),
+                               torch.empty((n, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
+                               torch.empty(need if TS else 0, dtype=torch.uint8).pin_memory())
+            labels, counts, vcounts, sup, tstats, _ = mdl.predict_labels_tta(x, T, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
+                                                                             small_zones=small_zones, return_views=True)
+            tring[slot][0][:, :n].copy_(vcounts, non_blocking=True)
+            tring[slot][1][:n].copy_(tstats, non_blocking=True)
+            if TS:
+                tring[slot][2][:need].copy_(sup.reshape(-1), non_blocking=True)
+        else:
+            labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
+                                                small_zones=small_zones)   # models.py:269-276 on the device
         ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
         ring[slot][1][:n].copy_(counts, non_blocking=True)
         if Z:                                        # the labels are final here: after remove_small_zones and the remap
@@ -603,7 +661,12 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if Z:                                        # (rows,) per image; (None,) = more zones than the cap: the host's turn
             znum = zring[slot][1][:n].numpy()
             zone = [(zring[slot][0][j, :int(znum[j])].numpy().copy() if znum[j] <= ZCAP else None,) for j in range(n)]
-        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j])
+        views = [None] * n
+        if T:
+            vc, tst = tring[slot][0][:, :n].numpy().copy(), tring[slot][1][:n].numpy().copy()
+            sups = tring[slot][2][: n * h * w].numpy().reshape(n, h, w).copy() if TS else [None] * n
+            views = [(cnts[j], vc[:, j], tst[j], sups[j]) for j in range(n)]
+        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j], views[j])
                 for j, k in enumerate(part)]
 
     def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
@@ -629,6 +692,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if r.rank == 0:
             write_dropout_report(os.path.join(root, "results"), items, allrows, alld, D, dropout_p, dropout_seed, r.precision,
                                  bn_stats, old_stats, dropout_compare, allv)
+    if T:
+        allt = folder_run.gather(r, trows, TROW)             # one more all_gather, as the draws' rows take
+        if r.rank == 0:
+            write_tta_report(os.path.join(root, "results"), items, allrows, allt, T, r.precision, bn_stats)
     extra = {}
     if Z:                                            # (global_idx, 10 zone fields) rows, an image's rows together and in order
         t_report = clock()
@@ -656,10 +723,13 @@ def main(argv=None):
     folder_run.add_shared_arguments(ap)
     folder_run.add_dropout_arguments(ap)
     folder_run.add_zones_arguments(ap)
+    ap.add_argument("--tta_votes", action="store_true",
+                    help="with --tta: also write results/tta_support/ (grey, 255 = every view gives the pixel the same label)")
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
     try:                                                 # refused as argument errors, before any device is touched
+        folder_run.check_tta_arguments(args.tta, args.tta_votes, args.dropout_draws, args.only_preprocess)
         folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
                                            args.only_preprocess, args.dropout_votes)
         if args.dropout_compare is not None:
@@ -685,6 +755,8 @@ def main(argv=None):
                   dropout_seed=args.dropout_seed or 0, dropout_compare=args.dropout_compare, dropout_votes=args.dropout_votes)
     if args.zones:
         kw.update(zones=True, zones_cap=args.zones_cap)
+    if args.tta != "none":
+        kw.update(tta=args.tta, tta_votes=args.tta_votes)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if int(os.environ.get("RANK", "0")) == 0:
