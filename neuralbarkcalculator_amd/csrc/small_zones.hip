@@ -1,27 +1,25 @@
-// remove_small_zones on the GPU: /root/reference/src/bark_calculator/utils.py:135-148, called at
+// remove_small_zones on the GPU: the reference's src/bark_calculator/utils.py:135-148, called at
 // models.py:271 between the argmax and the statistics.  Byte/index work, bound by HBM/L2 traffic.
 //
 // With m = (labels == 0) (the "Nothing" mask), skimage semantics (connectivity=2 = 8-neighbourhood):
 //   1. remove_small_holes(m, 150):   8-connected components of ~m smaller than 150 px join m;
 //   2. remove_small_objects(m, 150): 8-connected components of the filled m smaller than 150 px leave m;
 //   3. pixels that left m and were class 0 become class 1; pixels that joined m become class 0.
-// Both steps are "label the 8-connected components of a binary mask, drop the small ones":
-//   tile_label     one 32x32 tile per block: union-find in LDS over the tile's mask pixels (each pixel
-//                  with its W, NW, N, NE neighbours), every pixel then points at the tile-local root
-//                  (a global pixel index), so chains in global memory only ever link tile roots;
-//   border_rows/cols  pixels on a tile border unite their root with the touching runs across it
-//                  (atomicMin union-find on global memory with intermediate pointer jumping);
+// Both steps are "label the 8-connected components of a binary mask, drop the small ones".  The labelling is
+// components.hpp's with one class (label_tile in LDS, then the border kernels on global memory); around it:
+//   tile_label     writes the Nothing mask (phase 0) and counts the pixels of every tile-local root;
 //   sum_sizes      every tile-local root adds its tile's pixel count to its final root;
 //   apply          components below the threshold flip in the mask.
 // The result (which pixels flip) depends only on component sizes, which are exact integers, so the
 // output equals the CPU restatement (scipy.ndimage.label) bit for bit.
+#include "components.hpp"
 #include "nbc_kernels.hpp"
-#include "union_find.hpp"
+#include "reduce.hpp"
 
 namespace nbc {
 namespace {
 
-constexpr int TILE = kLabelTile;   // find_root / unite and their LDS forms: union_find.hpp
+constexpr int TILE = kLabelTile;
 
 // phase 0: mask = (label != 0) is labelled ("holes" of the Nothing mask); phase 1: mask = bg.
 // bg[] holds the Nothing mask (1 = background); written here in phase 0.
@@ -31,96 +29,30 @@ __global__ __launch_bounds__(TILE* TILE) void tile_label_kernel(const LabelT* __
                                                                  int H, int W, int phase) {
   __shared__ int s[TILE * TILE];
   __shared__ int cnt[TILE * TILE];
-  const int tx = threadIdx.x & (TILE - 1), ty = threadIdx.x >> 5;
-  const int x = blockIdx.x * TILE + tx, y = blockIdx.y * TILE + ty;
+  __shared__ unsigned char sc[TILE * TILE];
+  const int t = threadIdx.x;
+  const int x = blockIdx.x * TILE + (t & (TILE - 1)), y = blockIdx.y * TILE + (t >> 5);
   const size_t img = (size_t)blockIdx.z * H * W;
   const bool inside = x < W && y < H;
   const int p = y * W + x;
-  bool m = false;
+  int m = 0;
   if (inside) {
     if (phase == 0) {
-      const bool is_bg = labels[img + p] == 0;
-      bg[img + p] = is_bg ? 1 : 0;
-      m = !is_bg;
+      m = labels[img + p] != 0;
+      bg[img + p] = m ? 0 : 1;
     } else {
       m = bg[img + p] != 0;
     }
   }
-  const int t = threadIdx.x;
-  // Horizontal runs first, without atomics: a wave holds two rows of the tile; a mask pixel points at
-  // the first pixel of its run (the position after the nearest unset bit to its left).
-  const unsigned row_bits = (unsigned)(__ballot(m) >> (32 * ((t >> 5) & 1)));
-  const unsigned zeros_left = ~row_bits & ((1u << tx) - 1u);
-  const int run_start = zeros_left ? 32 - __clz((int)zeros_left) : 0;
-  s[t] = m ? (t - tx + run_start) : -1;
   cnt[t] = 0;
-  __syncthreads();
-  // Then one union per pair of touching runs of consecutive rows: the leftmost pixel of the overlap
-  // links upwards (N, or NW / NE when only a diagonal touches); the rest of the run is already joined.
-  if (m && ty > 0) {
-    const bool w = tx > 0 && ((row_bits >> (tx - 1)) & 1u), e = tx < TILE - 1 && ((row_bits >> (tx + 1)) & 1u);
-    const bool n = s[t - TILE] >= 0;
-    const bool nw = tx > 0 && s[t - TILE - 1] >= 0, ne = tx < TILE - 1 && s[t - TILE + 1] >= 0;
-    if (n) {
-      if (!(w && nw)) unite_lds(s, t, t - TILE);
-    } else {
-      if (nw && !w) unite_lds(s, t, t - TILE - 1);
-      if (ne && !e) unite_lds(s, t, t - TILE + 1);
-    }
-  }
-  __syncthreads();
-  const int r = m ? find_root_lds(s, t) : -1;
+  const int r = label_tile(m, s, sc);
   // pixels per tile-local root, one LDS atomic per distinct root per wave
-  unsigned long long todo = __ballot(r >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int lr = __shfl(r, leader, 64);
-    const unsigned long long same = __ballot(r == lr) & todo;
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&cnt[lr], (int)__popcll(same));
-    todo &= ~same;
-  }
+  for_each_key(r >= 0, r, [&](int root, unsigned long long same) { atomicAdd(&cnt[root], (int)__popcll(same)); });
   __syncthreads();
   if (inside) {
     parent[img + p] = m ? (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1)) : -1;   // index inside the image
-    size[img + p] = (m && r == t) ? cnt[t] : 0;   // non-zero exactly at the tile-local roots
+    size[img + p] = r == t ? cnt[t] : 0;      // non-zero exactly at the tile-local roots
   }
-}
-
-// Unions across tile borders.  Only border pixels have anything to do, and the run rule of the tile
-// kernel applies across borders too, so the launch covers just them:
-//   rows  y = 32k (k >= 1): a pixel links to the row above through N unless its W neighbour already does
-//         (W and NW both set), or through NW / NE when only a diagonal touches;
-//   columns x = 32k (k >= 1): the pixel right of the border links to W; the diagonals across a vertical
-//         border are needed only when neither the straight neighbour of the pixel's own tile (N) nor
-//         the pixel across the border in its own row (W resp. E) is set: otherwise that neighbour's own
-//         W-link already joins the two.
-__global__ void border_rows_kernel(int* __restrict__ parent, int H, int W) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = (blockIdx.y + 1) * TILE;
-  if (x >= W || y >= H) return;
-  int* L = parent + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  if (L[p] < 0) return;
-  const bool n = L[p - W] >= 0;
-  const bool w = x > 0 && L[p - 1] >= 0, e = x < W - 1 && L[p + 1] >= 0;
-  const bool nw = x > 0 && L[p - W - 1] >= 0, ne = x < W - 1 && L[p - W + 1] >= 0;
-  if (n) {
-    if (!(w && nw)) unite(L, p, p - W);
-  } else {
-    if (nw && !w) unite(L, p, p - W - 1);
-    if (ne && !e) unite(L, p, p - W + 1);
-  }
-}
-__global__ void border_cols_kernel(int* __restrict__ parent, int H, int W) {
-  const int y = blockIdx.x * blockDim.x + threadIdx.x, x = (blockIdx.y + 1) * TILE;      // x: first column right of a border
-  if (y >= H || x >= W) return;
-  int* L = parent + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;                    // right of the border; p - 1 is left of it
-  const bool top = (y & (TILE - 1)) == 0;     // rows on a horizontal border are handled by border_rows_kernel
-  const bool r_set = L[p] >= 0, l_set = L[p - 1] >= 0;
-  if (r_set && l_set) unite(L, p, p - 1);
-  if (y == 0 || top) return;
-  if (r_set && !l_set && L[p - W] < 0 && L[p - W - 1] >= 0) unite(L, p, p - W - 1);          // NW across the border
-  if (l_set && !r_set && L[p - 1 - W] < 0 && L[p - W] >= 0) unite(L, p - 1, p - W);          // NE across the border
 }
 
 // Component sizes: tile_label_kernel left the pixel count of every tile-local root in size[]; a local
@@ -205,8 +137,8 @@ hipError_t run(LabelT* labels, int N, int H, int W, int min_pixels, int exclude_
   }
   for (int phase = 0; phase < 2; ++phase) {
     hipLaunchKernelGGL(tile_label_kernel<LabelT>, tiles, dim3(TILE * TILE), 0, s, labels, bg, parent, size, H, W, phase);
-    if (H > TILE) hipLaunchKernelGGL(border_rows_kernel, dim3((W + 255) / 256, (H - 1) / TILE, N), dim3(256), 0, s, parent, H, W);
-    if (W > TILE) hipLaunchKernelGGL(border_cols_kernel, dim3((H + 255) / 256, (W - 1) / TILE, N), dim3(256), 0, s, parent, H, W);
+    if (phase == 0) launch_borders(parent, ZeroIsSet{bg}, N, H, W, s);      // the mask is ~bg, then bg
+    else launch_borders(parent, ClassPlane{bg}, N, H, W, s);
     hipLaunchKernelGGL(sum_sizes_kernel, rows, dim3(256), 0, s, parent, size, H, W);
     hipLaunchKernelGGL(apply_kernel<LabelT>, rows, dim3(256), 0, s, labels, bg, parent, size, H, W, min_pixels, phase,
                        exclude_nodes, counts);
@@ -219,7 +151,7 @@ hipError_t run(LabelT* labels, int N, int H, int W, int min_pixels, int exclude_
 
 hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H, int W, int min_pixels, int exclude_nodes,
                                      unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s) {
-  if (N < 1 || N > 65535 || H < 1 || W < 1 || H > 65535 || (long long)H * W > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (!per_image_shape_ok(N, H, W) || H > 65535) return hipErrorInvalidValue;      // grid.y carries the row
   if (labels_i64) return run(static_cast<long long*>(labels), N, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s);
   return run(static_cast<unsigned char*>(labels), N, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s);
 }

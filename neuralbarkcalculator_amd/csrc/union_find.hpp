@@ -1,4 +1,4 @@
-// The union-find that small_zones.hip and zones.hip label connected components with: one int per pixel that points at a pixel
+// The union-find that components.hpp labels connected components with: one int per pixel that points at a pixel
 // of the same component with a smaller or equal index (itself: a root), in LDS inside a 32x32 tile and in global memory across
 // tiles.  unite() always roots at the smaller index, so a component's root is its first pixel in raster order.
 #pragma once

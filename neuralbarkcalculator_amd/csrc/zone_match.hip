@@ -9,18 +9,18 @@
 //   pair_clear           the per-image tables: keys empty, counts 0, the claim counters 0
 //   pair_accumulate      one 32x32 tile per block, modelled on zones.hip's accumulate: every pixel with cls_out == cls_tgt != 0
 //                        walks both parent planes to the two indices; a wave reduces its two rows per distinct pair from
-//                        ballots; its leader adds the count into an LDS hash slot of the tile (at most 512 distinct pairs meet
-//                        a tile: two same-class pixels of different pairs cannot be 8-neighbours, so a 2x2 block holds at most
-//                        one pair per class); every used slot makes one insertion into the image's table (open addressing,
+//                        ballots (for_each_key, components.hpp); its leader adds the count into an LDS hash slot of the tile
+//                        (at most 512 distinct pairs meet a tile: two same-class pixels of different pairs cannot be
+//                        8-neighbours, so a 2x2 block holds at most one pair per class); every used slot makes one insertion into the image's table (open addressing,
 //                        the 64-bit key claimed by CAS, the count added atomically)
 //   pair_sort            one block per image: the claimed slots into LDS, a bitonic sort by key, the rows and pair_num
 // Termination does not depend on the data: every probe loop is bounded by its table's size; the image's claim counter stops
-// insertions once more than pair_cap keys are claimed; a full or overflowed table ends as pair_cap + 1; the parent walks end
-// for accumulate's reason (a parent's index is smaller than its child's, a root holds a negative code).
+// insertions once more than pair_cap keys are claimed; a full or overflowed table ends as pair_cap + 1; the parent walks are
+// components.hpp's root_index (a parent's index is smaller than its child's, a root holds a negative code).
 // Counts are integer sums and the rows are sorted: an image's outputs are the same alone, in any batch, on any stream.
+#include "components.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
-#include "union_find.hpp"
 
 namespace nbc {
 namespace {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kThreads) void pair_accumulate_kernel(const int* __
                                                                    int* __restrict__ claimed, int table, int table_shift, int pair_cap) {
   __shared__ u64 skey[kSlots];
   __shared__ int scnt[kSlots];
-  const int t = threadIdx.x, lane = t & 63;
+  const int t = threadIdx.x;
   const int x = blockIdx.x * TILE + (t & (TILE - 1)), y = blockIdx.y * TILE + (t >> 5);
   const size_t img = (size_t)blockIdx.z * H * W;
   int* const mine = claimed + blockIdx.z;
@@ -71,42 +71,26 @@ __global__ __launch_bounds__(kThreads) void pair_accumulate_kernel(const int* __
   scnt[t] = 0;
   __syncthreads();
 
-  int io = -1, it = -1;
+  u64 pair = kEmpty;                        // output index << 32 | target index
   if (x < W && y < H) {
     const int p = y * W + x;
     const int c = cls_out[img + p];
-    if (c && c == cls_tgt[img + p]) {
-      const int* Lo = parent_out + img;
-      const int* Lt = parent_tgt + img;
-      int v = Lo[p];
-      while (v >= 0) v = Lo[v];           // up to the root, whose parent holds -2 - index
-      io = -2 - v;
-      v = Lt[p];
-      while (v >= 0) v = Lt[v];
-      it = -2 - v;
-    }
+    if (c && c == cls_tgt[img + p])
+      pair = ((u64)(unsigned)root_index(parent_out + img, p) << 32) | (u64)(unsigned)root_index(parent_tgt + img, p);
   }
-  u64 todo = __ballot(io >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int ko = __shfl(io, leader, 64), kt = __shfl(it, leader, 64);
-    const u64 same = __ballot(io == ko && it == kt) & todo;
-    if (lane == leader) {
-      const u64 key = ((u64)(unsigned)ko << 32) | (u64)(unsigned)kt;
-      unsigned h = (unsigned)((key * kGolden) >> 54);                            // 10 bits: kSlots
-      int probe = 0;
-      for (; probe < kSlots; ++probe) {
-        const u64 old = atomicCAS(&skey[h], kEmpty, key);
-        if (old == kEmpty || old == key) {
-          atomicAdd(&scnt[h], (int)__popcll(same));
-          break;
-        }
-        h = (h + 1) & (kSlots - 1);
+  for_each_key(pair != kEmpty, pair, [&](u64 key, u64 same) {
+    unsigned h = (unsigned)((key * kGolden) >> 54);                              // 10 bits: kSlots
+    int probe = 0;
+    for (; probe < kSlots; ++probe) {
+      const u64 old = atomicCAS(&skey[h], kEmpty, key);
+      if (old == kEmpty || old == key) {
+        atomicAdd(&scnt[h], (int)__popcll(same));
+        break;
       }
-      if (probe == kSlots) atomicMax(mine, pair_cap + 1);                        // cannot happen (512 pairs per tile); no spin if it did
+      h = (h + 1) & (kSlots - 1);
     }
-    todo &= ~same;
-  }
+    if (probe == kSlots) atomicMax(mine, pair_cap + 1);                          // cannot happen (512 pairs per tile); no spin if it did
+  });
   __syncthreads();
   const u64 key = skey[t];
   if (key == kEmpty) return;

@@ -2,12 +2,11 @@
 // record per zone -- first pixel, class, pixels, bounding box, coordinate sums, perimeter.  Integer work, exact against the
 // host restatement (neuralbarkcalculator_amd/zones.py: scipy.ndimage.label per class plus numpy reductions).
 //
-// The labelling is small_zones.hip's, made class-aware: a pixel is "set" for its neighbour only when both carry the same
-// class, so the zones of class 1 and of class 2 are labelled in one pass over one parent array.
-//   zone_tile      one 32x32 tile per block: runs of equal class per row (ballots), one LDS union per pair of touching runs of
-//                  consecutive rows, every pixel then points at its tile-local root (a pixel index of the image); the class
+// The labelling is components.hpp's: a pixel joins a neighbour only when both carry the same class, so the zones of class 1
+// and of class 2 are labelled in one pass over one parent array.
+//   zone_tile      label_tile; every pixel then points at its tile-local root (a pixel index of the image); the class
 //                  (0 for any label outside {1, 2}) goes to a byte plane that every later kernel reads instead of the labels
-//   zone_border_rows / _cols   unions across the tile borders, the run rule with "a same-class neighbour" for "a set one"
+//   border_rows / _cols   components.hpp's unions across the tile borders, on that plane
 //   count_roots    a root is a pixel that points at itself; unite() roots at the smaller index, so a zone's root is its
 //                  first pixel in raster order.  Roots per 1024 consecutive pixels,
 //   scan_roots     their exclusive scan per image (one block per image) and the image's zone count,
@@ -19,9 +18,9 @@
 //                  set of 64-bit global atomics (4 adds, 2 mins, 2 maxes) into the zone's row.  Rows at or above cap get nothing.
 // Workspace: 4 B (parent) + 1 B (class) per pixel + 4 B per 1024 pixels.  Integer sums, mins and maxes do not depend on their
 // order: an image's rows are the same alone, in any batch, on any stream and from run to run.
+#include "components.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
-#include "union_find.hpp"
 
 namespace nbc {
 namespace {
@@ -36,8 +35,8 @@ __global__ __launch_bounds__(TILE* TILE) void zone_tile_kernel(const LabelT* __r
                                                                 int* __restrict__ parent, int H, int W) {
   __shared__ int s[TILE * TILE];
   __shared__ unsigned char sc[TILE * TILE];
-  const int tx = threadIdx.x & (TILE - 1), ty = threadIdx.x >> 5;
-  const int x = blockIdx.x * TILE + tx, y = blockIdx.y * TILE + ty;
+  const int t = threadIdx.x;
+  const int x = blockIdx.x * TILE + (t & (TILE - 1)), y = blockIdx.y * TILE + (t >> 5);
   const size_t img = (size_t)blockIdx.z * H * W;
   const bool inside = x < W && y < H;
   const int p = y * W + x;
@@ -46,72 +45,11 @@ __global__ __launch_bounds__(TILE* TILE) void zone_tile_kernel(const LabelT* __r
     const LabelT v = labels[img + p];
     c = v == (LabelT)1 ? 1 : (v == (LabelT)2 ? 2 : 0);
   }
-  const int t = threadIdx.x;
-  // horizontal runs of equal class, without atomics: a pixel points at the first pixel of its run
-  const unsigned long long b1 = __ballot(c == 1), b2 = __ballot(c == 2);
-  const unsigned row_bits = (unsigned)((c == 1 ? b1 : (c == 2 ? b2 : 0ull)) >> (32 * ((t >> 5) & 1)));
-  const unsigned zeros_left = ~row_bits & ((1u << tx) - 1u);
-  const int run_start = zeros_left ? 32 - __clz((int)zeros_left) : 0;
-  s[t] = c ? (t - tx + run_start) : -1;
-  sc[t] = (unsigned char)c;
-  __syncthreads();
-  // one union per pair of touching runs of the same class in consecutive rows (small_zones.hip's rule)
-  if (c && ty > 0) {
-    const bool w = tx > 0 && ((row_bits >> (tx - 1)) & 1u), e = tx < TILE - 1 && ((row_bits >> (tx + 1)) & 1u);
-    const bool n = sc[t - TILE] == c;
-    const bool nw = tx > 0 && sc[t - TILE - 1] == c, ne = tx < TILE - 1 && sc[t - TILE + 1] == c;
-    if (n) {
-      if (!(w && nw)) unite_lds(s, t, t - TILE);
-    } else {
-      if (nw && !w) unite_lds(s, t, t - TILE - 1);
-      if (ne && !e) unite_lds(s, t, t - TILE + 1);
-    }
-  }
-  __syncthreads();
+  const int r = label_tile(c, s, sc);
   if (inside) {
-    int r = -1;
-    if (c) {
-      r = find_root_lds(s, t);
-      r = (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1));   // index inside the image
-    }
-    parent[img + p] = r;
+    parent[img + p] = c ? (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1)) : -1;   // index inside the image
     cls[img + p] = (unsigned char)c;
   }
-}
-
-// Unions across tile borders: small_zones.hip's border kernels with "set" read as "of this pixel's class".
-__global__ void zone_border_rows_kernel(int* __restrict__ parent, const unsigned char* __restrict__ cls, int H, int W) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = (blockIdx.y + 1) * TILE;
-  if (x >= W || y >= H) return;
-  int* L = parent + (size_t)blockIdx.z * H * W;
-  const unsigned char* C = cls + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  const int c = C[p];
-  if (!c) return;
-  const bool n = C[p - W] == c;
-  const bool w = x > 0 && C[p - 1] == c, e = x < W - 1 && C[p + 1] == c;
-  const bool nw = x > 0 && C[p - W - 1] == c, ne = x < W - 1 && C[p - W + 1] == c;
-  if (n) {
-    if (!(w && nw)) unite(L, p, p - W);
-  } else {
-    if (nw && !w) unite(L, p, p - W - 1);
-    if (ne && !e) unite(L, p, p - W + 1);
-  }
-}
-__global__ void zone_border_cols_kernel(int* __restrict__ parent, const unsigned char* __restrict__ cls, int H, int W) {
-  const int y = blockIdx.x * blockDim.x + threadIdx.x, x = (blockIdx.y + 1) * TILE;      // x: first column right of a border
-  if (y >= H || x >= W) return;
-  int* L = parent + (size_t)blockIdx.z * H * W;
-  const unsigned char* C = cls + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;                    // right of the border; p - 1 is left of it
-  const bool top = (y & (TILE - 1)) == 0;     // rows on a horizontal border are handled by zone_border_rows_kernel
-  const int cr = C[p], cl = C[p - 1];
-  if (cr && cr == cl) unite(L, p, p - 1);
-  if (y == 0 || top) return;
-  // a diagonal across the border is needed only when neither the pixel's straight neighbour in its own tile (N) nor the
-  // pixel across the border in its own row has the pixel's class: otherwise that neighbour's own link joins the two
-  if (cr && cl != cr && C[p - W] != cr && C[p - W - 1] == cr) unite(L, p, p - W - 1);          // NW across the border
-  if (cl && cr != cl && C[p - 1 - W] != cl && C[p - W] == cl) unite(L, p - 1, p - W);          // NE across the border
 }
 
 __global__ __launch_bounds__(kChunk) void count_roots_kernel(const int* __restrict__ parent, int* __restrict__ blocks, int P) {
@@ -194,8 +132,7 @@ __global__ __launch_bounds__(TILE* TILE) void accumulate_kernel(const int* __res
                                                                  int H, int W, long long* __restrict__ rows, int cap) {
   __shared__ int key[kSlots];
   __shared__ int acc[kFields][kSlots];
-  const int t = threadIdx.x, lane = t & 63;
-  const int tx = t & (TILE - 1), ty = t >> 5;
+  const int t = threadIdx.x, tx = t & (TILE - 1), ty = t >> 5;
   const int x = blockIdx.x * TILE + tx, y = blockIdx.y * TILE + ty;
   const size_t img = (size_t)blockIdx.z * H * W;
   const int* L = parent + img;
@@ -210,12 +147,8 @@ __global__ __launch_bounds__(TILE* TILE) void accumulate_kernel(const int* __res
   if (x < W && y < H) {
     const int p = y * W + x;
     const int c = C[p];
-    if (c) {
-      int v = L[p];
-      while (v >= 0) v = L[v];            // up to the root, whose parent holds -2 - index
-      idx = -2 - v;
-      if (idx >= cap) idx = -1;
-    }
+    if (c) idx = root_index(L, p);
+    if (idx >= cap) idx = -1;
     if (idx >= 0) {                       // sides whose neighbour has another label or lies outside the image
       dn = y == 0 || C[p - W] != c;
       ds = y == H - 1 || C[p + W] != c;
@@ -225,31 +158,24 @@ __global__ __launch_bounds__(TILE* TILE) void accumulate_kernel(const int* __res
   }
   const unsigned long long bn = __ballot(dn), bs = __ballot(ds), bw = __ballot(dw), be = __ballot(de);
   const int x_base = blockIdx.x * TILE, y_lo = blockIdx.y * TILE + (ty & ~1);      // the wave's two rows: y_lo, y_lo + 1
-  unsigned long long todo = __ballot(idx >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int k = __shfl(idx, leader, 64);
-    const unsigned long long same = __ballot(idx == k) & todo;
-    if (lane == leader) {
-      const unsigned lo = (unsigned)same, hi = (unsigned)(same >> 32), both = lo | hi;
-      const int n_lo = __popc(lo), n_hi = __popc(hi);
-      unsigned h = ((unsigned)k * 2654435761u) >> 22;                               // 10 bits: kSlots
-      while (true) {
-        const int old = atomicCAS(&key[h], -1, k);
-        if (old == -1 || old == k) break;
-        h = (h + 1) & (kSlots - 1);
-      }
-      atomicAdd(&acc[kPixels][h], n_lo + n_hi);
-      atomicAdd(&acc[kSumX][h], (n_lo + n_hi) * x_base + bit_position_sum(lo) + bit_position_sum(hi));
-      atomicAdd(&acc[kSumY][h], n_lo * y_lo + n_hi * (y_lo + 1));
-      atomicAdd(&acc[kPerimeter][h], (int)(__popcll(same & bn) + __popcll(same & bs) + __popcll(same & bw) + __popcll(same & be)));
-      atomicMin(&acc[kMinX][h], x_base + (__ffs((int)both) - 1));
-      atomicMax(&acc[kMaxX][h], x_base + 31 - __clz((int)both));
-      atomicMin(&acc[kMinY][h], lo ? y_lo : y_lo + 1);
-      atomicMax(&acc[kMaxY][h], hi ? y_lo + 1 : y_lo);
+  for_each_key(idx >= 0, idx, [&](int k, unsigned long long same) {
+    const unsigned lo = (unsigned)same, hi = (unsigned)(same >> 32), both = lo | hi;
+    const int n_lo = __popc(lo), n_hi = __popc(hi);
+    unsigned h = ((unsigned)k * 2654435761u) >> 22;                                 // 10 bits: kSlots
+    while (true) {
+      const int old = atomicCAS(&key[h], -1, k);
+      if (old == -1 || old == k) break;
+      h = (h + 1) & (kSlots - 1);
     }
-    todo &= ~same;
-  }
+    atomicAdd(&acc[kPixels][h], n_lo + n_hi);
+    atomicAdd(&acc[kSumX][h], (n_lo + n_hi) * x_base + bit_position_sum(lo) + bit_position_sum(hi));
+    atomicAdd(&acc[kSumY][h], n_lo * y_lo + n_hi * (y_lo + 1));
+    atomicAdd(&acc[kPerimeter][h], (int)(__popcll(same & bn) + __popcll(same & bs) + __popcll(same & bw) + __popcll(same & be)));
+    atomicMin(&acc[kMinX][h], x_base + (__ffs((int)both) - 1));
+    atomicMax(&acc[kMaxX][h], x_base + 31 - __clz((int)both));
+    atomicMin(&acc[kMinY][h], lo ? y_lo : y_lo + 1);
+    atomicMax(&acc[kMaxY][h], hi ? y_lo + 1 : y_lo);
+  });
   __syncthreads();
   const int k = key[t];
   if (k < 0) return;
@@ -275,8 +201,7 @@ ZonesLayout zones_layout(int N, int H, int W) {
 
 hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, int W, long long* rows, int cap, long long* num,
                               int* parent, unsigned char* cls, int* blocks, hipStream_t s) {
-  if (N < 1 || N > 65535 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)H * W > 0x7fffffffLL || cap < 1)
-    return hipErrorInvalidValue;
+  if (!per_image_shape_ok(N, H, W) || H > 65535 || W > 65535 || cap < 1) return hipErrorInvalidValue;
   const int P = H * W, nb = (P + kChunk - 1) / kChunk;
   const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, N);
   if (labels_i64)
@@ -285,10 +210,7 @@ hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, 
   else
     hipLaunchKernelGGL(zone_tile_kernel<unsigned char>, tiles, dim3(TILE * TILE), 0, s, static_cast<const unsigned char*>(labels), cls,
                        parent, H, W);
-  if (H > TILE)
-    hipLaunchKernelGGL(zone_border_rows_kernel, dim3((W + 255) / 256, (H - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
-  if (W > TILE)
-    hipLaunchKernelGGL(zone_border_cols_kernel, dim3((H + 255) / 256, (W - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
+  launch_borders(parent, ClassPlane{cls}, N, H, W, s);
   hipLaunchKernelGGL(count_roots_kernel, dim3(nb, N), dim3(kChunk), 0, s, parent, blocks, P);
   hipLaunchKernelGGL(scan_roots_kernel, dim3(N), dim3(kChunk), 0, s, blocks, nb, num);
   hipLaunchKernelGGL(assign_roots_kernel, dim3(nb, N), dim3(kChunk), 0, s, parent, cls, blocks, P, H, W, rows, cap);

@@ -4,7 +4,7 @@
                 remove_small_zones on the same maps and zones.zones_cpu on this host: 1024x1024 and 520x1024 maps, batches of
                 1 and 8, `blobs()`-style maps (thresholded smoothed noise plus salt: a few hundred zones of every size), the
                 label maps of the network on synthetic frames, and the two extremes (all one zone; salt only).  Under
-                `rocprofv3 --kernel-trace --stats` the launches are zone_tile_kernel, zone_border_rows / _cols_kernel,
+                `rocprofv3 --kernel-trace --stats` the launches are zone_tile_kernel, border_rows / _cols_kernel<ClassPlane>,
                 count_roots / scan_roots / assign_roots_kernel and accumulate_kernel.
   --folder N    predict_folder on a synthetic folder of N 1024x1024 samples (scripts/time_evaluate.py's folder) without and
                 with zones, alternated, twice each: images/s end to end and in the loop.
