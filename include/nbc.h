@@ -458,6 +458,54 @@ int nbc_pixel_cross_entropy(const float* logits_full_dev, const uint8_t* target_
                             void* workspace_dev, size_t workspace_bytes, double* sums_dev, int64_t* counts_dev,
                             void* hip_stream);
 
+/* Per-image census of the softmax confidence: what a reliability table, the expected calibration error, the Brier score,
+ * one-vs-rest precision / recall curves of each class probability and the soft Jaccard need from the pixels -- the soft
+ * Jaccard being the quantity the reference's JaccardLoss (utils.py:168-182) is named after, which its code does not compute
+ * on the [B,H,W] targets it is given -- and the confidence plane of the plain forward.  The softmax
+ * is the one of lovasz_losses.py:162-167 / F.cross_entropy; the class weights that pushed it off the class priors are
+ * get_pos_weight (utils.py:72-73).  No context: csrc/softmax_census.hip.  The definition is integer from the quantisation
+ * on, so nothing in the result depends on an order of addition.  Per pixel of image n:
+ *   a pixel with a NaN or infinite logit adds 1 to `nonfinite`, takes part in nothing else and gets confidence byte 0;
+ *   otherwise, in f64 from the f32 logits: m = max_c x_c, e_c = exp(x_c - m), s = (e_0 + e_1) + e_2, p_c = e_c / s,
+ *   q_c = min(65535, floor(p_c * 65536));  k = argmax of the three logits (first maximum wins: nbc_forward's labels);
+ *   t = the target class, hit = (k == t); without a target t = 0 and hit = 1;  the confidence byte is q_k >> 8.
+ * The row of an image, NBC_CENSUS_WORDS unsigned 64-bit words:
+ *   H[t][c][b]  at NBC_CENSUS_H + (t * 3 + c) * 256 + b:  pixels of target class t with q_c >> 8 == b
+ *   R[hit][b]   at NBC_CENSUS_R + hit * 256 + b:          pixels with q_k >> 8 == b (the reliability counts)
+ *   RS[hit][b]  at NBC_CENSUS_RS + hit * 256 + b:         the sum of q_k over those pixels (the exact confidence sums)
+ *   M[t][c]     at NBC_CENSUS_M + t * 3 + c:              the sum of q_c over the pixels of target class t (the soft
+ *                                                         confusion, in expected pixels x 65536)
+ *   B[t]        at NBC_CENSUS_B + t:                      the sum of sum_c (q_c - 65536 [c == t])^2 (the Brier numerators)
+ *   nonfinite   at NBC_CENSUS_NONFINITE
+ * A pixel adds less than 2^33 to B[t] (its q sum to at most 65536, so (65536 - q_t)^2 and the two other squares together
+ * stay below 2 * 65536^2), so with H * W < 2^31 every word stays below 2^64: u64 holds every shape the call admits.
+ * logits_full_dev  float32 [N,3,H,W], what nbc_forward writes to logits_full_dev; any 4-byte alignment (16-byte loads where
+ *                  an image's planes start on 16-byte boundaries, as nbc_pixel_cross_entropy reads them)
+ * target_dev       nullable, uint8 [N,H,W] grey levels; class = round(2 * float32(v) / 255) as nbc_confusion derives it
+ * workspace_dev    at least nbc_softmax_census_workspace_bytes(N, H, W) bytes of device memory, 256-byte aligned; scratch
+ * rows_dev         uint64 [N][NBC_CENSUS_WORDS]; overwritten
+ * confidence_dev   nullable, uint8 [N,H,W]; overwritten
+ * Integer sums only (LDS integer atomics inside a tile, per-tile partials in the workspace, tiles added by a second launch;
+ * no float atomics, no memset): an image's row and confidence plane are bit-identical alone, anywhere in a batch and on any
+ * stream.  Runs on hip_stream (the caller's current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a
+ * null logits, workspace or rows pointer, N < 1 or N > 65535, H or W < 1, H * W >= 2^31, or a workspace too small or
+ * misaligned.  With P = H * W, T = ceil(P / 4096) and A(x) = x rounded up to a multiple of 256, the workspace is
+ *   A(5632 N T) + A(2088 N T) + A(24 N T) bytes
+ * (per image and tile: 2816 16-bit counts, 522 32-bit sums, 3 64-bit Brier sums); nbc_softmax_census_workspace_bytes
+ * returns 0 for a shape nbc_softmax_census refuses. */
+#define NBC_CENSUS_BINS 256
+#define NBC_CENSUS_H 0
+#define NBC_CENSUS_R 2304
+#define NBC_CENSUS_RS 2816
+#define NBC_CENSUS_M 3328
+#define NBC_CENSUS_B 3337
+#define NBC_CENSUS_NONFINITE 3340
+#define NBC_CENSUS_WORDS 3341
+size_t nbc_softmax_census_workspace_bytes(int N, int H, int W);
+int nbc_softmax_census(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
+                       void* workspace_dev, size_t workspace_bytes, uint64_t* rows_dev, uint8_t* confidence_dev,
+                       void* hip_stream);
+
 /* ---- the shipped tool's live Dropout --------------------------------------------------------
  * FCNHead's Dropout(0.1) (models.py:113-124) sits behind the 3x3 head convolution and in front of classifier.4, and the
  * shipped predict.py never calls .eval(): every number it wrote is one random draw of that mask.  torch's CPU random stream

@@ -27,6 +27,8 @@ ZONE_PAIR_ROW = 3                                   # NBC_ZONE_PAIR_ROW
 PAIRS_MAX_CAP = 4096                                # NBC_ZONE_PAIRS_MAX_CAP
 CONTOUR_SETS, CONTOUR_HEAD = 4, 4                   # NBC_CONTOUR_SETS, NBC_CONTOUR_HEAD
 CONTOUR_MAX_SIDE = 4096                             # NBC_CONTOUR_MAX_SIDE
+CENSUS_BINS, CENSUS_WORDS = 256, 3341               # NBC_CENSUS_BINS, NBC_CENSUS_WORDS
+CENSUS_H, CENSUS_R, CENSUS_RS, CENSUS_M, CENSUS_B, CENSUS_NONFINITE = 0, 2304, 2816, 3328, 3337, 3340   # NBC_CENSUS_*
 TTA_IDENTITY, TTA_HFLIP, TTA_VFLIP, TTA_HVFLIP, TTA_FLIPS = 1, 2, 4, 8, 15   # NBC_TTA_*
 
 
@@ -116,6 +118,9 @@ SIGNATURES = {
     "nbc_pixel_ce_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_pixel_cross_entropy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "nbc_softmax_census_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nbc_softmax_census": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "nbc_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_double, C.c_uint64, C.c_size_t, C.c_void_p]),
     "nbc_dropout_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nbc_dropout_draws": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int,

@@ -45,7 +45,8 @@ cross-entropy, ``CustomWeightedCrossEntropy`` (utils.py:151-165) for the class w
 reference's ``get_pos_weight()``) and, with ``--loss`` too, ``MixedLoss`` (utils.py:185-192).  The CSV gains the columns of
 ``metrics.CE_CSV_COLUMNS`` (and ``mixed_loss``) after those of ``--loss``, the summary a ``"cross_entropy"`` entry that also
 holds the cell sums and pixel counts of the whole folder, so that it can be re-weighted without another run.  The
-reference's ``JaccardLoss`` is not computed.  Without the flag nothing changes.
+reference's ``JaccardLoss`` is not computed as its code runs; ``--calibration`` reports the soft Jaccard
+its name means.  Without the flag nothing changes.
 
 ``--zones`` (``zones=True``) asks what the pixel metrics hide: which zone of the final labels is which zone of the dual, and
 how well they overlap.  After the second ``confusion``, on the labels ``PixelWiseF1`` sees, ``FCNResNet50.match_zones`` leaves
@@ -70,6 +71,22 @@ pixels -- default 2, 7.2 mm -- and the HD95 bins) and one pooled histogram, and 
 precision, recall and F1 at the tolerance, the mean symmetric contour distance, HD95 -- whole pixels, rounded up -- and the
 Hausdorff distance in mm) and a ``"contours"`` entry in the summary (``contours.contour_summary``) with the pooled histogram,
 from which any other tolerance can be read off.  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
+
+``--calibration`` (``calibration=True``) asks whether the network's confidence is worth anything.  Each batch writes its
+full-resolution logits as under ``--loss`` / ``--ce`` (one buffer per stream serves all three flags), and after the raw
+``confusion``, on the batch's stream, ``FCNResNet50.softmax_census`` tallies the softmax against the dual
+(csrc/softmax_census.hip; the host restatement is ``calibration.census_cpu``): the census describes the *raw* softmax, before
+``remove_small_zones`` -- with ``--tta`` the softmax of the merged logits.  The rows ride back with the batch; each rank turns
+them into one fixed-width row per image (``calibration.wire_rows``: the reliability counts and confidence sums at
+``--ece_bins`` bins -- default 16 --, the soft confusion, the Brier numerators) and one pooled census, and only these travel:
+integer sums are exact in any order.  Rank 0 writes ``results/calibration_evaluation.csv``
+(``calibration.CALIBRATION_COLUMNS``: ECE and MCE with the mean confidence of each bin from its exact sum, accuracy, mean
+confidence, the Brier score, the soft Jaccard per class and the ``JaccardLoss`` value with the sums its name means, expected
+beside hard Bark / Node %, the non-finite pixels), ``results/calibration_curves.csv`` from the pooled folder (per class and
+threshold j / 256 the one-vs-rest precision, recall and F1 of "p_c >= threshold", and the reliability table of the 256 bins)
+and a ``"calibration"`` entry in the summary (``calibration.calibration_summary``: the pooled figures, per class AP, AUROC,
+the best-F1 threshold and the F1 there beside the F1 at argmax, and the pooled ``H``, ``R`` and ``RS``, from which any other
+bin count can be read off).  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
 
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
@@ -101,6 +118,7 @@ STATS_CSV = os.path.join("results", "evaluation_stats.csv")
 SUMMARY_JSON = os.path.join("results", "evaluation_summary.json")
 MATCHES_CSV, ZONE_EVALUATION_CSV = "zone_matches.csv", "zone_evaluation.csv"     # --zones, under results/
 CONTOUR_CSV = "contour_evaluation.csv"                                           # --contours, under results/
+CALIBRATION_CSV, CURVES_CSV = "calibration_evaluation.csv", "calibration_curves.csv"   # --calibration, under results/
 
 
 def list_labelled(root: str) -> List[dict]:
@@ -244,6 +262,40 @@ def write_contour_report(results_dir: str, items, allrows, all_wire, histogram, 
     return ct.contour_summary(figures, tolerance, histogram)
 
 
+def check_calibration_arguments(calibration: bool, ece_bins=None) -> None:
+    """``ValueError`` for what ``--calibration`` and its option refuse before any device is touched: the option without the
+    flag, a bin count that is no power of two in 1..256."""
+    from . import calibration as cal
+    if not calibration:
+        if ece_bins is not None:
+            raise ValueError("--ece_bins needs --calibration")
+        return
+    if ece_bins is not None:
+        cal.check_ece_bins(ece_bins)
+
+
+def write_calibration_report(results_dir: str, items, allrows, all_wire, pooled, ece_bins: int) -> dict:
+    """``calibration_evaluation.csv`` and ``calibration_curves.csv`` (tab separated, like ``evaluation_stats.csv``) from the
+    gathered ``(global_idx, calibration.wire_width(ece_bins) fields)`` rows ``all_wire`` and the folder's pooled census row, for
+    the evaluated images of ``allrows`` in their order.  Returns the ``"calibration"`` entry of the summary
+    (``calibration.calibration_summary``)."""
+    from . import calibration as cal
+    width = cal.wire_width(ece_bins)
+    wire = {int(g[0]): g[1:] for g in np.asarray(all_wire, dtype=np.int64).reshape(-1, 1 + width)}
+    table, raw_total, images = [list(cal.CALIBRATION_COLUMNS)], np.zeros((3, 3), np.int64), 0
+    for g in allrows:
+        if int(g[3]) != STATUS_OK:
+            continue
+        d, raw = items[int(g[0])], np.asarray(g[4:13], dtype=np.int64).reshape(3, 3)
+        raw_total += raw
+        images += 1
+        table += cal.calibration_rows(d["name"], d["wood"], cal.figures_of_wire(wire[int(g[0])], ece_bins), raw.sum(axis=0))
+    for name, rows_ in ((CALIBRATION_CSV, table), (CURVES_CSV, [list(cal.CURVE_COLUMNS)] + cal.curve_rows(pooled))):
+        with open(os.path.join(results_dir, name), "w") as f:
+            csv.writer(f, delimiter="\t").writerows(rows_)
+    return cal.calibration_summary(pooled, images, ece_bins, raw_total)
+
+
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
@@ -300,7 +352,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
                     class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
                     zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
-                    contour_tolerance: int = None, tta="none") -> dict:
+                    contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -319,6 +371,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ``tta`` ("hflip", "vflip", "flips"; "none" = off): ``FCNResNet50.predict_labels_tta`` stands where ``predict_labels`` does,
     so every row and every optional pass is about the mean of the flip views; ``batch`` keeps counting images
     (default 1, 2 in bf16) and the summary gains ``"tta": {"views": [...]}``.
+    ``calibration``: also the census of the softmax confidence (module docstring), with ``ece_bins`` bins (a power of two in
+    1..256, default ``calibration.DEFAULT_ECE_BINS``) under the expected calibration error.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
@@ -332,6 +386,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     check_contour_arguments(K, contour_tolerance)
     TOL = ct.check_tolerance(contour_tolerance) if contour_tolerance is not None else ct.DEFAULT_TOLERANCE
     CBINS = ct.default_bins(target_size, target_size)   # the bins of the largest frame: the pooled histogram's
+    from . import calibration as cal
+    CAL = bool(calibration)
+    check_calibration_arguments(CAL, ece_bins)
+    EB = cal.check_ece_bins(ece_bins) if ece_bins is not None else cal.DEFAULT_ECE_BINS
     if ce:
         class_weights = check_class_weights(class_weights)
     T = folder_run.check_tta_arguments(tta)         # the view mask, 0 = off
@@ -347,6 +405,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if ce:
             m.pixel_cross_entropy(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                                   torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if CAL:
+            m.softmax_census(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
+                             torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
         if Z:                                        # match_zones' (11 bytes per pixel)
             plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
             m.match_zones(plane, plane, cap=ZCAP, pair_cap=PCAP)
@@ -384,7 +445,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ring = [torch.empty((2, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)]   # raw, clean
     loss_ring = [torch.empty((batch, 3), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if loss else None
     logits_buf = [torch.empty(batch * 3 * target_size * target_size, dtype=torch.float32, device=dev)
-                  for _ in range(r.n_streams)] if loss or ce else None
+                  for _ in range(r.n_streams)] if loss or ce or CAL else None
     ce_ring = [torch.empty((batch, 9), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if ce else None
     # --zones: per slot the two zone inventories, the pair rows, the three counts per image, and the two planes an image over
     # a cap is matched from on the host
@@ -402,10 +463,16 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if K:
         cwire[:, 0] = mine
     chist = np.zeros((ct.SETS, CBINS), dtype=np.int64) if K else None
+    # --calibration: per slot the census rows of a batch; per image the row that travels; the rank's pooled census
+    cal_ring = [torch.empty((batch, cal.WORDS), dtype=torch.int64).pin_memory() for _ in range(r.depth)] if CAL else None
+    cal_wire = np.zeros((len(mine), 1 + cal.wire_width(EB)), dtype=np.int64) if CAL else None
+    if CAL:
+        cal_wire[:, 0] = mine
+    cal_pool = np.zeros(cal.WORDS, dtype=np.uint64) if CAL else None
 
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
-        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce else None
+        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
         if T:                                                         # the same call on the mean of the flip views
             labels, _ = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg)
         else:
@@ -414,6 +481,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if ce:                                                        # CustomWeightedCrossEntropy (utils.py:151-165)
             sums, _ = mdl.pixel_cross_entropy(lg, tgt)
             ce_ring[slot][:n].copy_(sums.view(n, 9), non_blocking=True)
+        if CAL:                                                       # the raw softmax, before remove_small_zones
+            census, _ = mdl.softmax_census(lg, tgt)
+            cal_ring[slot][:n].copy_(census.view(torch.int64), non_blocking=True)
         if loss:                                                      # LovaszSoftmax (:236-239)
             terms, _ = mdl.lovasz_softmax(lg, tgt)
             loss_ring[slot][:n].copy_(terms, non_blocking=True)
@@ -459,6 +529,12 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             chist[...] += ct.pooled_histogram(c_rows, CBINS)
             for j, k in enumerate(part):
                 cwire[k, 1:] = wire[j]
+        if CAL:
+            census = cal_ring[slot][:n].numpy()
+            cal_pool[...] += cal.pool(census)
+            wire = cal.wire_rows(census, EB)
+            for j, k in enumerate(part):
+                cal_wire[k, 1:] = wire[j]
         for j, k in enumerate(part):
             rows[k, :4] = (mine[k], h, w, STATUS_OK)
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
@@ -490,6 +566,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         all_wire = folder_run.gather(r, cwire, 1 + ct.WIRE_WIDTH)
         all_hist = folder_run.gather_ragged(np.concatenate([[r.rank], chist.ravel()])[None], r.world, r.dist, r.wire_dev,
                                             width=1 + chist.size)[:, 1:].sum(axis=0).reshape(chist.shape)
+    all_cal = all_census = None
+    if CAL:                                          # a fixed-width row per image and one pooled census per rank
+        all_cal = folder_run.gather(r, cal_wire, 1 + cal.wire_width(EB))
+        all_census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cal_pool.view(np.int64)])[None], r.world, r.dist,
+                                                       r.wire_dev, width=1 + cal.WORDS)[:, 1:])
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
@@ -503,6 +584,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                                                        n_fallbacks)
         if K:
             summary["contours"] = write_contour_report(os.path.join(root, "results"), items, allrows, all_wire, all_hist, TOL)
+        if CAL:
+            summary["calibration"] = write_calibration_report(os.path.join(root, "results"), items, allrows, all_cal, all_census, EB)
         if T:
             summary["tta"] = {"views": folder_run.tta_view_names(T)}
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
@@ -556,6 +639,15 @@ def format_summary(summary: dict) -> str:
                              c["merged_outputs"], fmt(c["recall"]), fmt(c["precision"]), fmt(c["f1"]), fmt(c["mean_iou"])))
         if z["host_fallbacks"]:
             lines.append("%d images over a cap were matched on the host" % z["host_fallbacks"])
+    if summary.get("calibration"):
+        c = summary["calibration"]
+        fmt = lambda v, spec="%.4f": "-" if v is None else spec % v
+        p = c["pooled"]
+        lines.append("calibration over %d bins: ECE %s, MCE %s, accuracy %s, mean confidence %s, Brier %s; " % (
+            c["ece_bins"], fmt(p["ece"]), fmt(p["mce"]), fmt(p["accuracy"]), fmt(p["mean_confidence"]), fmt(p["brier"])) + "; ".join(
+            "%s AP %s, AUROC %s, best F1 %s at p >= %s (argmax: %s)" % (
+                name, fmt(c[name]["average_precision"]), fmt(c[name]["auroc"]), fmt(c[name]["best_f1"]),
+                fmt(c[name]["best_f1_threshold"], "%.3f"), fmt(c[name]["f1_at_argmax"])) for name in ("Bark", "Node")))
     if summary.get("contours"):
         c = summary["contours"]
         fmt = lambda v, spec: "-" if v is None else spec % v
@@ -600,6 +692,13 @@ def main(argv=None):
     ap.add_argument("--contour_tolerance", type=int, default=None, metavar="PX",
                     help="with --contours: a contour pixel within PX pixels of the other contour counts as found, an integer "
                          ">= 0 (default 2: 7.2 mm)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="also tally the softmax confidence against the duals on the device (raw softmax, before "
+                         "remove_small_zones) and write results/calibration_evaluation.csv (ECE, MCE, accuracy, mean confidence, "
+                         "Brier score, soft Jaccard, expected class shares), results/calibration_curves.csv (precision / recall / "
+                         "F1 per class and threshold, the reliability table) and a \"calibration\" entry in the summary")
+    ap.add_argument("--ece_bins", type=int, default=None, metavar="BINS",
+                    help="with --calibration: the bins under ECE and MCE, a power of two in 1..256 (default 16)")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
@@ -607,6 +706,7 @@ def main(argv=None):
     try:
         check_zone_match_arguments(args.zones, args.zones_cap, args.zone_pairs_cap, args.match_iou)
         check_contour_arguments(args.contours, args.contour_tolerance)
+        check_calibration_arguments(args.calibration, args.ece_bins)
     except ValueError as e:
         ap.error(str(e))
     if args.exclude_nodes:
@@ -638,6 +738,8 @@ def main(argv=None):
         kw.update(zones=True, zones_cap=args.zones_cap, zone_pairs_cap=args.zone_pairs_cap, match_iou=args.match_iou)
     if args.contours:
         kw.update(contours=True, contour_tolerance=args.contour_tolerance)
+    if args.calibration:
+        kw.update(calibration=True, ece_bins=args.ece_bins)
     if args.tta != "none":
         kw["tta"] = args.tta
     if args.normalization is not None:

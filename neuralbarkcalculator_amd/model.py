@@ -244,6 +244,7 @@ class FCNResNet50:
         self._zones_ws: Optional[torch.Tensor] = None      # nbc_label_zones', likewise
         self._zone_match_ws: Optional[torch.Tensor] = None   # nbc_match_zones', likewise
         self._contours_ws: Optional[torch.Tensor] = None   # nbc_contour_distances', likewise
+        self._census_ws: Optional[torch.Tensor] = None     # nbc_softmax_census', likewise
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self.device: Optional[torch.device] = None
         self.training = False
@@ -670,6 +671,37 @@ class FCNResNet50:
                                                          sums.data_ptr(), counts.data_ptr(), cur.cuda_stream),
                        "nbc_pixel_cross_entropy")
         return sums, counts
+
+    def softmax_census(self, logits_full: torch.Tensor, target: Optional[torch.Tensor] = None,
+                       confidence: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Per-image census of the softmax confidence on the device (nbc_softmax_census; the definition: include/nbc.h,
+        ``calibration.census_cpu``): the histograms of every class probability by target class, the reliability counts and
+        exact confidence sums of the winning class, the soft confusion, the Brier numerators and the non-finite pixels.
+        ``logits_full``: contiguous f32 ``[N,3,H,W]`` as ``lovasz_softmax`` takes it; ``target``: contiguous uint8 grey mask
+        ``[N,H,W]`` or None (every pixel then counts as target class 0 and as a hit); ``confidence``: also the uint8
+        ``[N,H,W]`` plane of ``q_k >> 8``, the winning class's probability in 1/256.  Runs on the current stream; the
+        workspace is cached on this object and only grows.  Returns ``(rows uint64 [N, NBC_CENSUS_WORDS], plane or None)``;
+        ``calibration.figures`` and ``calibration.curves`` turn a row into the numbers."""
+        self._require_ctx()
+        if target is None:
+            if logits_full.device != self.device or logits_full.dtype != torch.float32 or not logits_full.is_contiguous() \
+                    or logits_full.dim() != 4 or logits_full.shape[1] != NUM_CLASSES or logits_full.numel() == 0:
+                raise ValueError("logits_full must be a contiguous non-empty float32 [N,3,H,W] tensor on %s" % (self.device,))
+            n, _, h, w = (int(v) for v in logits_full.shape)
+        else:
+            n, h, w = self._check_logits_target(logits_full, target)
+        need = int(self._lib.nbc_softmax_census_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_softmax_census refuses a [%d,3,%d,%d] batch (N <= 65535, H * W < 2^31)" % (n, h, w))
+        rows = torch.empty((n, _lib.CENSUS_WORDS), dtype=torch.uint64, device=self.device)
+        plane = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if confidence else None
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_census_ws", need, cur)
+            _lib.check(self._lib.nbc_softmax_census(logits_full.data_ptr(), None if target is None else target.data_ptr(), n, h, w,
+                                                    ws.data_ptr(), ws.numel(), rows.data_ptr(),
+                                                    None if plane is None else plane.data_ptr(), cur.cuda_stream),
+                       "nbc_softmax_census")
+        return rows, plane
 
     def dropout_draws(self, draws: int, image_ids, p: float = 0.1, seed: int = 0, first_draw: int = 0,
                       small_zones: bool = True, exclude_nodes: bool = False, return_lowres: bool = False, *,
@@ -1142,6 +1174,7 @@ class FCNResNet50:
         self._zones_ws = None
         self._zone_match_ws = None
         self._contours_ws = None
+        self._census_ws = None
         self._last_shape = None
 
     def __del__(self):

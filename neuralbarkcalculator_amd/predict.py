@@ -45,15 +45,17 @@ CSV_HEADER = ["Name", "Type", "Image Size", "Output Bark %", "Bark area (mm^2)",
 ROW_WIDTH = 5                                                              # (global_idx, H, W, count_1, count_2)
 
 
-def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False, tta_votes: bool = False) -> None:
-    """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well; ``tta_votes``: the one of ``--tta_votes``."""
+def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False, tta_votes: bool = False,
+                     confidence: bool = False) -> None:
+    """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well; ``tta_votes``: the one of ``--tta_votes``;
+    ``confidence``: the one of ``--confidence``."""
     present = os.listdir(os.path.join(root, "samples"))
     wood_types = [w for w in WOOD_TYPES if w in present]
     for w in wood_types:
         os.makedirs(os.path.join(root, "processed", "samples", w), exist_ok=True)
     if not only_preprocess:
         for level in ("combined_images", "outputs") + (("dropout_votes", "dropout_support") if votes else ()) + \
-                (("tta_support",) if tta_votes else ()):
+                (("tta_support",) if tta_votes else ()) + (("confidence",) if confidence else ()):
             for w in wood_types:
                 os.makedirs(os.path.join(root, "results", level, w), exist_ok=True)
 
@@ -385,6 +387,45 @@ def write_zones_report(results_dir: str, items, allrows, allz, cap: int, host_fa
     return doc
 
 
+def check_confidence_arguments(confidence: bool, confidence_threshold=None, dropout_draws=None, only_preprocess: bool = False) -> None:
+    """``ValueError`` for what ``--confidence`` and its option refuse before any device is touched: the threshold without the
+    flag or outside (0, 1], and the flag with ``--dropout_draws`` or ``--only_preprocess``."""
+    from . import calibration as cal
+    if not confidence:
+        if confidence_threshold is not None:
+            raise ValueError("--confidence_threshold needs --confidence")
+        return
+    if dropout_draws:
+        raise ValueError("--confidence describes the plain forward: it does not go with --dropout_draws")
+    if only_preprocess:
+        raise ValueError("--confidence needs the forward: it does not go with --only_preprocess")
+    if confidence_threshold is not None:
+        cal.check_confidence_threshold(confidence_threshold)
+
+
+def write_confidence_report(results_dir: str, items, allrows, all_wire, pooled, threshold: float, precision: str, bn_stats: str) -> dict:
+    """``confidence_stats.csv`` (tab separated) and ``confidence_summary.json`` from the gathered rows: ``allrows`` as
+    ``final_stats.csv`` is written from, ``all_wire`` the ``(global_idx, pixels below the threshold, calibration.wire_rows
+    fields)`` rows, ``pooled`` the folder's census row.  Returns the summary."""
+    import json
+    from . import calibration as cal
+    width = cal.wire_width()
+    wire = {int(g[0]): g[1:] for g in np.asarray(all_wire, dtype=np.int64).reshape(-1, 2 + width)}
+    table, hard_total = [list(cal.CONFIDENCE_COLUMNS)], [0, 0, 0]
+    for g in allrows:
+        d, pixels, c1, c2 = items[int(g[0])], int(g[1]) * int(g[2]), int(g[3]), int(g[4])
+        hard = [pixels - c1 - c2, c1, c2]
+        hard_total = [a + b for a, b in zip(hard_total, hard)]
+        w = wire[int(g[0])]
+        table += cal.confidence_rows_of_wire(d["name"], d["wood"], cal.figures_of_wire(w[1:]), int(w[0]), hard)
+    with open(os.path.join(results_dir, "confidence_stats.csv"), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    summary = dict(cal.confidence_summary(pooled, len(allrows), threshold, hard_total), precision=precision, bn_statistics=bn_stats)
+    with open(os.path.join(results_dir, "confidence_summary.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
 def label_png(labels: np.ndarray) -> np.ndarray:
     """models.py:349-353: uint8 map with Bark = 127, Node = 255."""
     out = np.zeros(labels.shape, dtype=np.uint8)
@@ -420,7 +461,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
                    dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None,
-                   tta="none", tta_votes: bool = False) -> dict:
+                   tta="none", tta_votes: bool = False, confidence: bool = False, confidence_threshold: float = None) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -468,6 +509,13 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     own counts and the vote statistics over the views ride back beside the labels; rank 0 writes ``results/tta_stats.csv``
     and ``results/tta_summary.json`` (``folder_run.tta_report``).  ``tta_votes`` (with ``tta`` only): also
     ``results/tta_support/<wood>/<name>``, the support byte of the views' vote (grey, 255 = every view agrees).
+    ``confidence`` (not with ``dropout_draws``): the forward also writes its full-resolution logits, and
+    ``FCNResNet50.softmax_census`` (no target, the plane on) leaves the softmax confidence of the plain forward, which costs no
+    further forward: ``results/confidence/<wood>/<name>`` (grey, the winning class's probability in 1/256: the raw softmax,
+    before ``remove_small_zones`` and the ``exclude_nodes`` remap), ``results/confidence_stats.csv``
+    (``calibration.CONFIDENCE_COLUMNS``: the mean confidence, the share and mm2 of the pixels below ``confidence_threshold``
+    -- default 0.9 --, expected Bark / Node % and mm2 beside the hard ones) and ``results/confidence_summary.json``.
+    ``final_stats.csv`` and the label PNGs stay byte for byte what they are without the flag.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -483,6 +531,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     T = folder_run.check_tta_arguments(tta, tta_votes, D)   # the view mask, 0 = off
     NV = len(folder_run.tta_view_names(T))
     TS = bool(tta_votes)
+    from . import calibration as cal
+    C = bool(confidence)
+    check_confidence_arguments(C, confidence_threshold, D)
+    CT = cal.check_confidence_threshold(confidence_threshold) if confidence_threshold is not None else cal.DEFAULT_CONFIDENCE_THRESHOLD
     old_stats = None
     if V and not D:
         raise ValueError("--dropout_votes needs --dropout_draws")
@@ -499,8 +551,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             m.remove_small_zones(torch.zeros((batch * r.stack, target_size, target_size), dtype=torch.uint8, device=dev))
         if Z:                                        # and label_zones' (5 bytes per pixel)
             m.label_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev), cap=ZCAP)
-    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto, lambda root_: generate_folders(root_, votes=V, tta_votes=TS), warm,
-                        normalization=normalization)
+        if C:
+            m.softmax_census(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev), confidence=True)
+    folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
+                        lambda root_: generate_folders(root_, votes=V, tta_votes=TS, confidence=C), warm, normalization=normalization)
     if D:
         folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
 
@@ -518,6 +572,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     vrows = np.zeros((len(mine), VROW), dtype=np.int64)          # (global_idx, 10 vote statistics, changed pixels)
     TROW = 1 + 3 + 3 * NV + folder_run.VOTE_STATS
     trows = np.zeros((len(mine), TROW), dtype=np.int64)          # (global_idx, merged counts, V x 3 view counts, 10 vote statistics)
+    CROW = 2 + cal.wire_width()
+    crows = np.zeros((len(mine), CROW), dtype=np.int64)          # (global_idx, pixels below the threshold, calibration.wire_rows)
+    cpool = np.zeros(cal.WORDS, dtype=np.uint64)                 # this rank's pooled census (--confidence)
     zrows = {}                                       # k -> the image's zone rows int64 [zones, 10] (--zones)
     zfallbacks = []                                  # the k whose rows came from the host: more zones than ZCAP
     resize_lock = threading.Lock()                   # the default stream is the pool's: its device resizes are serialised
@@ -547,9 +604,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None, views=None):
+    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None, views=None, conf=None):
         """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row; + the
-        zone rows: ``zone`` = (the device's rows, or None when the image has more zones than the cap: the host computes them)."""
+        zone rows: ``zone`` = (the device's rows, or None when the image has more zones than the cap: the host computes them);
+        + the confidence PNG: ``conf`` = the plane)."""
         d = items[mine[k]]
         t0 = clock()
         path = os.path.join(root, "results", "outputs", d["wood"], d["name"])
@@ -572,6 +630,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                 spath = os.path.join(root, "results", "tta_support", d["wood"], d["name"])
                 label_paths.append(spath)
                 write_png(spath, sup, lvl_lab)
+        if conf is not None:
+            cpath = os.path.join(root, "results", "confidence", d["wood"], d["name"])
+            label_paths.append(cpath)
+            write_png(cpath, conf, lvl_lab)
         prof["pool.write_labels"] += clock() - t0
         if zone is not None:
             t1 = clock()
@@ -597,6 +659,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     tring = [(torch.empty((NV, batch, 3), dtype=torch.int64).pin_memory(),
               torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
               torch.empty(full if TS else 0, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if T else None
+    # --confidence: per stream the full-resolution logits; per slot the confidence planes and the census rows
+    logits_buf = [torch.empty(3 * full, dtype=torch.float32, device=dev) for _ in range(r.n_streams)] if C else None
+    cring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, cal.WORDS), dtype=torch.int64).pin_memory())
+             for _ in range(r.depth)] if C else None
     tuned = set()
 
     def launch(slot, sid, part, x):
@@ -607,22 +673,34 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
             mdl.autotune(mdl.tta_views(x, T) if T else x)   # once per distinct full-batch shape and model object
             tuned.add((sid, (n, h, w)))
-        if T:                                        # the same tail on the mean of the flip views; the views' own figures beside it
+        lg = None
+        if C:                                        # the forward writes its full-resolution logits as well
+            lg = (logits_buf[sid][: 3 * need] if 3 * need <= logits_buf[sid].numel() else
+                  torch.empty(3 * need, dtype=torch.float32, device=dev)).view(n, 3, h, w)
+        if T:                                       # the same tail on the mean of the flip views; the views' own figures beside it
             if tring[slot][0].shape[1] < n or (TS and tring[slot][2].numel() < need):
                 tring[slot] = (torch.empty((NV, n, 3), dtype=torch.int64).pin_memory(),
                                torch.empty((n, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
                                torch.empty(need if TS else 0, dtype=torch.uint8).pin_memory())
             labels, counts, vcounts, sup, tstats, _ = mdl.predict_labels_tta(x, T, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                                             small_zones=small_zones, return_views=True)
+                                                                             small_zones=small_zones, return_views=True,
+                                                                             **(dict(logits_full=lg) if C else {}))
             tring[slot][0][:, :n].copy_(vcounts, non_blocking=True)
             tring[slot][1][:n].copy_(tstats, non_blocking=True)
             if TS:
                 tring[slot][2][:need].copy_(sup.reshape(-1), non_blocking=True)
         else:
             labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                small_zones=small_zones)   # models.py:269-276 on the device
+                                                small_zones=small_zones,   # models.py:269-276 on the device
+                                                **(dict(logits_full=lg) if C else {}))
         ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
         ring[slot][1][:n].copy_(counts, non_blocking=True)
+        if C:                                        # the raw softmax of the forward: no target, the plane on
+            if cring[slot][0].numel() < need or cring[slot][1].shape[0] < n:
+                cring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, cal.WORDS), dtype=torch.int64).pin_memory())
+            census, plane = mdl.softmax_census(lg, None, confidence=True)
+            cring[slot][0][:need].copy_(plane.reshape(-1), non_blocking=True)
+            cring[slot][1][:n].copy_(census.view(torch.int64), non_blocking=True)
         if Z:                                        # the labels are final here: after remove_small_zones and the remap
             if zring[slot][1].shape[0] < n:
                 zring[slot] = (torch.empty((n, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(),
@@ -666,8 +744,16 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             vc, tst = tring[slot][0][:, :n].numpy().copy(), tring[slot][1][:n].numpy().copy()
             sups = tring[slot][2][: n * h * w].numpy().reshape(n, h, w).copy() if TS else [None] * n
             views = [(cnts[j], vc[:, j], tst[j], sups[j]) for j in range(n)]
-        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j], views[j])
-                for j, k in enumerate(part)]
+        confs = [None] * n
+        if C:
+            confs = cring[slot][0][: n * h * w].numpy().reshape(n, h, w).copy()
+            census = cring[slot][1][:n].numpy()
+            cpool[...] += cal.pool(census)
+            wire = cal.wire_rows(census)
+            for j, k in enumerate(part):
+                crows[k, 0], crows[k, 1], crows[k, 2:] = mine[k], cal.below_threshold(census[j], CT), wire[j]
+        return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j], views[j],
+                            confs[j]) for j, k in enumerate(part)]
 
     def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
         for path in label_paths:                     # must not leave them behind (the processed/ images do not depend on
@@ -696,8 +782,14 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         allt = folder_run.gather(r, trows, TROW)             # one more all_gather, as the draws' rows take
         if r.rank == 0:
             write_tta_report(os.path.join(root, "results"), items, allrows, allt, T, r.precision, bn_stats)
+    if C:                                            # a fixed-width row per image and one pooled census per rank
+        allc = folder_run.gather(r, crows, CROW)
+        census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cpool.view(np.int64)])[None], r.world, r.dist, r.wire_dev,
+                                                   width=1 + cal.WORDS)[:, 1:])
+        if r.rank == 0:
+            write_confidence_report(os.path.join(root, "results"), items, allrows, allc, census, CT, r.precision, bn_stats)
     extra = {}
-    if Z:                                            # (global_idx, 10 zone fields) rows, an image's rows together and in order
+    if Z:                                          # (global_idx, 10 zone fields) rows, an image's rows together and in order
         t_report = clock()
         local = [np.concatenate([np.full((len(zrows[k]), 1), mine[k], dtype=np.int64), zrows[k]], axis=1) for k in sorted(zrows)]
         local = np.concatenate(local) if local else np.zeros((0, 1 + zn.ZONE_ROW), dtype=np.int64)
@@ -725,10 +817,18 @@ def main(argv=None):
     folder_run.add_zones_arguments(ap)
     ap.add_argument("--tta_votes", action="store_true",
                     help="with --tta: also write results/tta_support/ (grey, 255 = every view gives the pixel the same label)")
+    ap.add_argument("--confidence", action="store_true",
+                    help="also write the softmax confidence of the plain forward: results/confidence/ (grey, the winning class's "
+                         "probability in 1/256, before remove_small_zones), results/confidence_stats.csv and "
+                         "results/confidence_summary.json; no further forward")
+    ap.add_argument("--confidence_threshold", type=float, default=None, metavar="P",
+                    help="with --confidence: the pixels whose confidence lies below P are reported as a share and in mm2, "
+                         "0 < P <= 1 (default 0.9)")
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
     folder_run.resolve_arguments(ap, args)
     try:                                                 # refused as argument errors, before any device is touched
+        check_confidence_arguments(args.confidence, args.confidence_threshold, args.dropout_draws, args.only_preprocess)
         folder_run.check_tta_arguments(args.tta, args.tta_votes, args.dropout_draws, args.only_preprocess)
         folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
                                            args.only_preprocess, args.dropout_votes)
@@ -757,6 +857,8 @@ def main(argv=None):
         kw.update(zones=True, zones_cap=args.zones_cap)
     if args.tta != "none":
         kw.update(tta=args.tta, tta_votes=args.tta_votes)
+    if args.confidence:
+        kw.update(confidence=True, confidence_threshold=args.confidence_threshold)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if int(os.environ.get("RANK", "0")) == 0:
