@@ -641,6 +641,54 @@ int nbc_tta_views(const void* x_dev, int x_dtype, int N, int H, int W, int views
 int nbc_tta_merge(const float* lowres_views_dev, int N, int h, int w, int views, float* merged_dev, float* aligned_dev,
                   void* hip_stream);
 
+/* ---- the colour-jitter views the training augmented over ---------------------------------------
+ * The reference trains with ColorJitter(saturation=0.2, brightness=0.1) on the sample (__main__.py:160) and never uses that at
+ * prediction time.  These calls make the colour views of a batch and average the network's answers for them;
+ * the forward between them is nbc_forward on the stack, as it stands.
+ *   view     a triple of float32 factors (b, c, s), each finite and in [0, 4].  A view set is V triples, 1 <= V <=
+ *            NBC_JITTER_MAX_VIEWS, taken in the order given.
+ *   image    the view of a uint8 RGB frame is saturation_s(contrast_c(brightness_b(frame))); every step yields a uint8 image, as
+ *            the PIL chain torchvision 0.3 runs does.  A step whose factor is exactly 1.0f is the identity.  The order
+ *            brightness -> contrast -> saturation is this library's: torchvision shuffles the order per sample.
+ *   step     blend(degenerate, image, f) per byte: t = float(d) + f * float(i - d) with d, i the degenerate and image bytes as
+ *            ints -- one f32 multiply and one f32 add, no contraction; the result is 0 if t <= 0, 255 if t >= 255, else t
+ *            truncated toward zero.
+ *   degenerates  brightness: 0.  saturation: the pixel's grey L = (19595 R + 38470 G + 7471 B + 32768) >> 16 in all three
+ *            channels.  contrast: every byte = m, the rounded mean grey of the image the step receives (after brightness): with
+ *            S the sum of L over that image, m = floor((2 S + H W) / (2 H W)) -- PIL's int(mean + 0.5) for every H W < 2^31, an
+ *            exact half rounds up.  m is per image and per view, never per batch.
+ *   stack    view-major, like nbc_tta_views': entry j * N + i is view j of image i
+ *   mean     m = (((v_0 + v_1) + v_2) + ...) / float(V): f32 adds in view order, no contraction, one IEEE f32 division; V = 1
+ *            gives the view's own bits (-0 included), a NaN in any view gives NaN: nbc_tta_merge's rule without the un-flip,
+ *            for V up to NBC_JITTER_MAX_VIEWS.
+ * Left out: hue (the reference never jitters it), float32 NCHW input (torchvision's tensor path is other arithmetic), products
+ * of colour and flip views, and the Gaussian sampling of the reference's NormColorJitter (a caller passes any factors). */
+enum { NBC_JITTER_MAX_VIEWS = 16 };
+/* The bytes nbc_jitter_views' workspace needs for N images and V views (8 V N), into *bytes.  NBC_ERR_INVALID: a null pointer,
+ * V outside 1..16, N < 1 or V * N > 65535. */
+int nbc_jitter_workspace_bytes(int N, int V, size_t* bytes);
+/* The V views of a batch.  No context: csrc/jitter.hip.
+ * x_dev          NBC_IN_U8_NHWC [N][H][W][3], any alignment
+ * factors        HOST memory, float32 [V][3]: (b, c, s) per view; they travel as kernel arguments (no copy, no synchronisation)
+ * out_dev        [V][N][H][W][3], any alignment; must not overlap x
+ * workspace_dev  nbc_jitter_workspace_bytes(N, V) bytes, 8-byte aligned; cleared by the call on the stream.  Used when a view has
+ *                c != 1: a pass before the views takes the uint64 grey sums (integer sums: they do not depend on arrival order;
+ *                views with the same b share one).
+ * The source is read once and every view written once: H * W * 3 * (1 + V) bytes per image (+ H * W * 3 per distinct b of the
+ * contrast pass).  An image's bytes are the same alone, in any batch and on any stream.  Runs on hip_stream (the caller's
+ * current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a null pointer, V outside 1..16, N < 1 or
+ * V * N > 65535, H or W < 1, H * W >= 2^31, a factor that is NaN, negative or above 4, overlapping buffers, a workspace that is
+ * not 8-byte aligned. */
+int nbc_jitter_views(const uint8_t* x_dev, int N, int H, int W, const float* factors, int V, uint8_t* out_dev, void* workspace_dev,
+                     void* hip_stream);
+/* The mean of the low-resolution logits of a stacked forward.  No context: csrc/jitter.hip.
+ * lowres_views_dev  float32 [V][N][3][h][w]
+ * mean_dev          float32 [N][3][h][w]; overwritten
+ * An element of the mean depends on the V elements it is made of alone.  NBC_ERR_INVALID, before any HIP call: a null pointer,
+ * V outside 1..16, N < 1 or V * N > 65535, h or w < 1, h * w >= 2^31, a pointer that is not 4-byte aligned, mean_dev
+ * overlapping the input. */
+int nbc_views_mean(const float* lowres_views_dev, int N, int V, int h, int w, float* mean_dev, void* hip_stream);
+
 /* ---- the zones of a label map ------------------------------------------------------------------
  * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and
  * whether the bark is one sheet or many fragments.  The reference has no such code; the host restatement is

@@ -30,6 +30,7 @@ CONTOUR_MAX_SIDE = 4096                             # NBC_CONTOUR_MAX_SIDE
 CENSUS_BINS, CENSUS_WORDS = 256, 3341               # NBC_CENSUS_BINS, NBC_CENSUS_WORDS
 CENSUS_H, CENSUS_R, CENSUS_RS, CENSUS_M, CENSUS_B, CENSUS_NONFINITE = 0, 2304, 2816, 3328, 3337, 3340   # NBC_CENSUS_*
 TTA_IDENTITY, TTA_HFLIP, TTA_VFLIP, TTA_HVFLIP, TTA_FLIPS = 1, 2, 4, 8, 15   # NBC_TTA_*
+JITTER_MAX_VIEWS = 16                               # NBC_JITTER_MAX_VIEWS
 
 
 class NbcTensor(C.Structure):
@@ -133,6 +134,9 @@ SIGNATURES = {
     "nbc_vote_tally": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "nbc_tta_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbc_tta_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbc_jitter_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "nbc_jitter_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nbc_views_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

@@ -15,6 +15,7 @@
 
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
+#include "views_mean.hpp"
 
 using namespace nbc;
 
@@ -117,7 +118,6 @@ __global__ __launch_bounds__(kMergeThreads) void tta_merge_kernel(const float* _
                                                                  int views, float* __restrict__ merged, float* __restrict__ aligned) {
   const long long hw = (long long)h * w, total = planes * hw;            // planes = 3 N
   const int V = count_views(views);
-  const float fv = (float)V;
   const long long stride = (long long)gridDim.x * kMergeThreads;
   for (long long e = (long long)blockIdx.x * kMergeThreads + threadIdx.x; e < total; e += stride) {
     const long long pl = e / hw;
@@ -131,10 +131,10 @@ __global__ __launch_bounds__(kMergeThreads) void tta_merge_kernel(const float* _
       const int yy = mirrors_rows(b) ? h - 1 - y : y, xx = mirrors_cols(b) ? w - 1 - x : x;
       const float a = in[((long long)vj * planes + pl) * hw + (long long)yy * w + xx];
       if (aligned) aligned[(long long)vj * total + e] = a;
-      sum = vj == 0 ? a : sum + a;                 // the first view starts the sum: V = 1 keeps its bits, -0 included
+      sum = views_mean_add(sum, a, vj);            // the first view starts the sum: V = 1 keeps its bits, -0 included
       ++vj;
     }
-    merged[e] = V == 1 ? sum : __fdiv_rn(sum, fv);
+    merged[e] = views_mean_finish(sum, V);
   }
 }
 

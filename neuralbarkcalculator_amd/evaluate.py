@@ -88,6 +88,14 @@ and a ``"calibration"`` entry in the summary (``calibration.calibration_summary`
 the best-F1 threshold and the F1 there beside the F1 at argmax, and the pooled ``H``, ``R`` and ``RS``, from which any other
 bin count can be read off).  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
 
+``--jitter training`` / ``--jitter_views "b,c,s;..."`` scores the mean of the colour-jitter views the training augmented over
+ in every metric and option above, as ``--tta`` scores the mean of the flip views, and asks how far one view
+moves the answer: each view's own final labels (after ``remove_small_zones``) go through ``confusion`` against the dual on the
+batch's stream, their nine counts ride back with the batch, and rank 0 writes ``results/jitter_evaluation.csv``
+(``jitter_evaluation``: a row per view pooled over the folder -- IoU and F1 per class with their means, Bark % and Node %, and
+each figure's difference from the ``identity`` view's) and a ``"jitter"`` entry in the summary.  ``evaluation_stats.csv``
+keeps its columns.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -296,6 +304,51 @@ def write_calibration_report(results_dir: str, items, allrows, all_wire, pooled,
     return cal.calibration_summary(pooled, images, ece_bins, raw_total)
 
 
+JITTER_EVALUATION_CSV = "jitter_evaluation.csv"                                  # --jitter, under results/
+JITTER_FIGURES = ["iou_nothing", "iou_bark", "iou_node", "iou_mean", "f1_nothing", "f1_bark", "f1_node", "f1_mean", "Bark %", "Node %"]
+
+
+def jitter_evaluation(names, confusions) -> Tuple[List[List[str]], dict]:
+    """The robustness table of ``--jitter``: one row per view from the confusion ``conf[t][p]`` of its final labels (after
+    ``remove_small_zones``) against the duals, pooled over the folder.  Per view: ``metrics.iou`` and ``metrics.f1`` of the
+    pooled counts with their means, and the share of the pixels labelled bark and node, ``100 count / pixels`` in float64; where
+    the set has an ``identity`` view, each figure's difference from that view's (the view's minus the identity's, of the
+    unrounded figures).  IoU and F1 are printed '{:.3f}' as ``evaluation_stats.csv`` prints them, the shares '{:.5f}'.  Returns
+    the CSV rows (header first) and ``{name: {"figures": {...}, "difference": {...} or None}}`` in the order of the stack."""
+    names = list(names)
+    figures = []
+    for conf in confusions:
+        conf = np.asarray(conf, dtype=np.int64).reshape(3, 3)
+        ious, f1s = metrics.iou(conf), metrics.f1(conf)
+        pixels, pred = int(conf.sum()), conf.sum(axis=0)
+        shares = [(100 * int(pred[c])) / pixels if pixels else 0.0 for c in (1, 2)]
+        figures.append([float(v) for v in ious] + [float(ious.mean())] + [float(v) for v in f1s] + [float(f1s.mean())] + shares)
+    identity = names.index("identity") if "identity" in names else None
+    spec = ["{:.3f}"] * 8 + ["{:.5f}"] * 2
+    rows = [["View"] + JITTER_FIGURES + (["d " + k for k in JITTER_FIGURES] if identity is not None else [])]
+    doc = {}
+    for name, f in zip(names, figures):
+        diff = [a - b for a, b in zip(f, figures[identity])] if identity is not None else None
+        rows.append([name] + [s.format(v) for s, v in zip(spec, f)] + ([s.format(v) for s, v in zip(spec, diff)] if diff is not None else []))
+        doc[name] = {"figures": dict(zip(JITTER_FIGURES, f)), "difference": dict(zip(JITTER_FIGURES, diff)) if diff is not None else None}
+    return rows, doc
+
+
+def write_jitter_evaluation(results_dir: str, allrows, all_views, factors) -> dict:
+    """``jitter_evaluation.csv`` (tab separated, like ``evaluation_stats.csv``) from the gathered ``(global_idx, V x 9 confusion
+    cells)`` rows ``all_views``, summed over the evaluated images of ``allrows``.  Returns the ``"jitter"`` entry of the summary."""
+    names = folder_run.jitter_view_names(factors)
+    done = {int(g[0]) for g in allrows if int(g[3]) == STATUS_OK}
+    total = np.zeros((len(names), 3, 3), dtype=np.int64)
+    for g in np.asarray(all_views, dtype=np.int64).reshape(-1, 1 + 9 * len(names)):
+        if int(g[0]) in done:
+            total += g[1:].reshape(len(names), 3, 3)
+    table, doc = jitter_evaluation(names, total)
+    with open(os.path.join(results_dir, JITTER_EVALUATION_CSV), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    return {"views": names, "factors": [[float(v) for v in t] for t in factors], "evaluation": doc}
+
+
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
@@ -352,7 +405,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     loss: bool = False, normalization=None, normalization_source: str = "arguments", ce: bool = False,
                     class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
                     zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
-                    contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None) -> dict:
+                    contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None,
+                    jitter=None, jitter_views=None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -373,6 +427,12 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     (default 1, 2 in bf16) and the summary gains ``"tta": {"views": [...]}``.
     ``calibration``: also the census of the softmax confidence (module docstring), with ``ece_bins`` bins (a power of two in
     1..256, default ``calibration.DEFAULT_ECE_BINS``) under the expected calibration error.
+    ``jitter`` ("training") or ``jitter_views`` (1..16 (brightness, contrast, saturation) triples, or the string of
+    ``--jitter_views``; not with ``tta``): ``FCNResNet50.predict_labels_jitter`` stands where ``predict_labels`` does, so every
+    row and every optional pass is about the mean of the colour-jitter views; ``batch`` keeps counting images
+    (default 1, 2 in bf16).  Each view's own final labels (after ``remove_small_zones``) go through ``confusion`` against the
+    dual as well: rank 0 writes ``results/jitter_evaluation.csv`` (``jitter_evaluation``: a row per view, pooled over the
+    folder) and the summary gains ``"jitter": {"views": [...], "factors": [...], "evaluation": {...}}``.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
@@ -393,12 +453,14 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if ce:
         class_weights = check_class_weights(class_weights)
     T = folder_run.check_tta_arguments(tta)         # the view mask, 0 = off
+    J = folder_run.check_jitter_arguments(jitter, jitter_views, tta=tta)   # the colour views' factors, None = off
+    NV = len(J) if J is not None else 0
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size,
-                            stack=max(1, len(folder_run.tta_view_names(T))))
+                            stack=max(1, NV, len(folder_run.tta_view_names(T))))
     dev, batch = r.dev, r.batch
 
-    def warm(m):                                     # the remove_small_zones workspace and, with ``loss`` / ``ce``, theirs
-        m.remove_small_zones(torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+    def warm(m):                                     # the remove_small_zones workspace (--jitter: of the views' stack) and, with ``loss`` / ``ce``, theirs
+        m.remove_small_zones(torch.zeros((batch * max(1, NV), target_size, target_size), dtype=torch.uint8, device=dev))
         if loss:
             m.lovasz_softmax(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                              torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
@@ -469,12 +531,22 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if CAL:
         cal_wire[:, 0] = mine
     cal_pool = np.zeros(cal.WORDS, dtype=np.uint64) if CAL else None
+    # --jitter: per slot the confusion of each view's final labels; per image the row that travels
+    jring = [torch.empty((NV, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)] if NV else None
+    jrows = np.zeros((len(mine), 1 + 9 * NV), dtype=np.int64) if NV else None
+    if NV:
+        jrows[:, 0] = -1                                              # a skipped image has no row
 
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
         if T:                                                         # the same call on the mean of the flip views
             labels, _ = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg)
+        elif NV:                                                      # or of the colour views; each view's own final labels beside it
+            labels, _, _, _, _, vlow = mdl.predict_labels_jitter(x, J, labels_dtype=torch.uint8, logits_full=lg, return_views=True)
+            vlab, _ = mdl.upsample_argmax(vlow.view((NV * n,) + tuple(vlow.shape[2:])), (h, w), labels_dtype=torch.uint8)
+            mdl.remove_small_zones(vlab)
+            jring[slot][:, :n].copy_(mdl.confusion(vlab, tgt.repeat(NV, 1, 1)).view(NV, n, 3, 3), non_blocking=True)
         else:
             labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
@@ -542,6 +614,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                 loss_rows[k, 1:] = loss_ring[slot][j].numpy().view(np.int64)
             if ce:
                 ce_rows[k, 1:] = ce_ring[slot][j].numpy().view(np.int64)
+            if NV:
+                jrows[k, 0], jrows[k, 1:] = mine[k], jring[slot][:, j].numpy().reshape(-1)
         return futures
 
     def first_frame():                               # the calibration guard's: this rank's first image that fits
@@ -571,6 +645,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         all_cal = folder_run.gather(r, cal_wire, 1 + cal.wire_width(EB))
         all_census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cal_pool.view(np.int64)])[None], r.world, r.dist,
                                                        r.wire_dev, width=1 + cal.WORDS)[:, 1:])
+    all_views = folder_run.gather(r, jrows, 1 + 9 * NV) if NV else None
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
@@ -588,6 +663,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             summary["calibration"] = write_calibration_report(os.path.join(root, "results"), items, allrows, all_cal, all_census, EB)
         if T:
             summary["tta"] = {"views": folder_run.tta_view_names(T)}
+        if NV:
+            summary["jitter"] = write_jitter_evaluation(os.path.join(root, "results"), allrows, all_views, J)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -648,6 +725,11 @@ def format_summary(summary: dict) -> str:
             "%s AP %s, AUROC %s, best F1 %s at p >= %s (argmax: %s)" % (
                 name, fmt(c[name]["average_precision"]), fmt(c[name]["auroc"]), fmt(c[name]["best_f1"]),
                 fmt(c[name]["best_f1_threshold"], "%.3f"), fmt(c[name]["f1_at_argmax"])) for name in ("Bark", "Node")))
+    if summary.get("jitter"):
+        for name, entry in summary["jitter"]["evaluation"].items():
+            f, d = entry["figures"], entry["difference"]
+            lines.append("view %s (its own final labels, pooled): " % name + ", ".join(
+                "%s %.3f%s" % (k, f[k], "" if d is None else " (%+.3f)" % d[k]) for k in ("iou_mean", "f1_mean", "Bark %", "Node %")))
     if summary.get("contours"):
         c = summary["contours"]
         fmt = lambda v, spec: "-" if v is None else spec % v
@@ -707,6 +789,7 @@ def main(argv=None):
         check_zone_match_arguments(args.zones, args.zones_cap, args.zone_pairs_cap, args.match_iou)
         check_contour_arguments(args.contours, args.contour_tolerance)
         check_calibration_arguments(args.calibration, args.ece_bins)
+        folder_run.check_jitter_arguments(args.jitter, args.jitter_views, tta=args.tta)
     except ValueError as e:
         ap.error(str(e))
     if args.exclude_nodes:
@@ -742,6 +825,8 @@ def main(argv=None):
         kw.update(calibration=True, ece_bins=args.ece_bins)
     if args.tta != "none":
         kw["tta"] = args.tta
+    if args.jitter is not None or args.jitter_views is not None:
+        kw.update(jitter=args.jitter, jitter_views=args.jitter_views)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

@@ -457,10 +457,7 @@ def check_tta_arguments(tta, tta_votes: bool = False, dropout_draws=None, only_p
 
 
 def tta_columns(mask: int) -> List[str]:
-    cols = ["Name", "Type", "Views"]
-    for v in tta_view_names(mask):
-        cols += ["%s Bark %%" % v, "%s Node %%" % v]
-    return cols + ["Bark %", "Node %", "Bark % spread", "Node % spread", "Unanimous %", "Mean support"]
+    return view_columns(tta_view_names(mask))
 
 
 def tta_report(images: Sequence[tuple], views: int):
@@ -471,10 +468,23 @@ def tta_report(images: Sequence[tuple], views: int):
     the views' counts, the unanimous percentage and the mean support are each one correctly rounded division of exact
     integers, formatted '{:.5f}' (``vote_report``'s arithmetic).  The summary's means: the merged and the identity pair (None
     for a mask without the identity view), their mean absolute difference, the spreads and the unanimous share."""
-    names = tta_view_names(views)
+    return views_report(images, tta_view_names(views), 0 if int(views) & 1 else None)
+
+
+def view_columns(names: Sequence[str]) -> List[str]:
+    cols = ["Name", "Type", "Views"]
+    for v in names:
+        cols += ["%s Bark %%" % v, "%s Node %%" % v]
+    return cols + ["Bark %", "Node %", "Bark % spread", "Node % spread", "Unanimous %", "Mean support"]
+
+
+def views_report(images: Sequence[tuple], names: Sequence[str], identity: int = None):
+    """``tta_report``'s and ``jitter_report``'s rows and summary for views called ``names``, in the order of the stack;
+    ``identity``: the position of the identity view in it, None for a set without one (no identity pair in the summary)."""
+    names = list(names)
     nv = len(names)
-    has_identity = bool(int(views) & 1)
-    rows, sums = [tta_columns(views)], {}
+    has_identity = identity is not None
+    rows, sums = [view_columns(names)], {}
     for name, wood, h, w, mc, vc, st in images:
         px = h * w
         mc, st = [int(v) for v in mc], [int(v) for v in st]
@@ -487,8 +497,9 @@ def tta_report(images: Sequence[tuple], views: int):
         figures = {"merged_bark": (100 * mc[1]) / px, "merged_node": (100 * mc[2]) / px, "bark_spread": spread[0],
                    "node_spread": spread[1], "unanimous": (100 * (st[3] + st[4] + st[5])) / px, "mean_support": st[6] / (nv * px)}
         if has_identity:
-            figures.update(identity_bark=(100 * vc[0][1]) / px, identity_node=(100 * vc[0][2]) / px,
-                           abs_diff_bark=abs(100 * (mc[1] - vc[0][1])) / px, abs_diff_node=abs(100 * (mc[2] - vc[0][2])) / px)
+            ic = vc[identity]
+            figures.update(identity_bark=(100 * ic[1]) / px, identity_node=(100 * ic[2]) / px,
+                           abs_diff_bark=abs(100 * (mc[1] - ic[1])) / px, abs_diff_node=abs(100 * (mc[2] - ic[2])) / px)
         row += [percent_string(mc[1], px), percent_string(mc[2], px), "{:.5f}".format(spread[0]), "{:.5f}".format(spread[1]),
                 "{:.5f}".format(figures["unanimous"]), "{:.5f}".format(figures["mean_support"])]
         rows.append(row)
@@ -498,11 +509,96 @@ def tta_report(images: Sequence[tuple], views: int):
     return rows, {"images": n, "views": names, "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}}
 
 
+# ---- the colour-jitter views the training augmented over (--jitter): view sets, argument checks, the report ------------------
+JITTER_CHOICES = ("training",)
+
+
+def parse_jitter_views(text: str) -> List[tuple]:
+    """The triples of ``--jitter_views "b,c,s;b,c,s;..."`` (brightness, contrast, saturation per view); ``ValueError`` for
+    anything that is not 1..16 triples of numbers."""
+    views = []
+    for part in str(text).split(";"):
+        fields = part.split(",")
+        try:
+            triple = tuple(float(f) for f in fields)
+        except ValueError:
+            triple = ()
+        if len(fields) != 3 or len(triple) != 3:
+            raise ValueError("--jitter_views takes triples \"b,c,s;b,c,s;...\" of numbers, got %r" % (text,))
+        views.append(triple)
+    return views
+
+
+def jitter_factors(jitter=None, jitter_views=None):
+    """The float32 ``[V,3]`` factors of ``--jitter NAME`` or ``--jitter_views`` (its string, or a sequence of triples), None
+    when neither is given; ``ValueError`` for both at once, an unknown name, or triples ``model.resolve_jitter_views``
+    refuses (malformed, more than 16, a factor outside [0, 4])."""
+    if jitter in (None, "none") and jitter_views is None:
+        return None
+    if jitter not in (None, "none") and jitter_views is not None:
+        raise ValueError("--jitter and --jitter_views exclude each other: name a view set or spell one out")
+    from .model import resolve_jitter_views
+    if jitter_views is None:
+        if not isinstance(jitter, str) or jitter not in JITTER_CHOICES:
+            raise ValueError("--jitter must be one of %s, got %r" % (", ".join(JITTER_CHOICES), jitter))
+        return resolve_jitter_views(jitter)
+    try:
+        return resolve_jitter_views(parse_jitter_views(jitter_views) if isinstance(jitter_views, str) else jitter_views)
+    except ValueError as e:
+        raise ValueError("--jitter_views: %s" % e)
+
+
+def jitter_view_names(factors) -> List[str]:
+    """The names of the views of a factor array, in the order of the stack (``model.jitter_view_names``)."""
+    from .model import jitter_view_names as names
+    return names(factors)
+
+
+def check_jitter_arguments(jitter=None, jitter_views=None, jitter_votes: bool = False, tta=None, dropout_draws=None,
+                           only_preprocess: bool = False):
+    """``ValueError`` for what ``--jitter``, ``--jitter_views`` and ``--jitter_votes`` refuse before any device is touched: both
+    view options at once, malformed or out-of-range triples, a view set with ``--tta`` (products of colour and flip views are
+    left out), with ``--dropout_draws`` (the draws read the features of a plain forward) or with ``--only_preprocess`` (no
+    network runs), ``--jitter_votes`` without a view set.  Returns the float32 ``[V,3]`` factors, None = off."""
+    factors = jitter_factors(jitter, jitter_views)
+    if factors is None:
+        if jitter_votes:
+            raise ValueError("--jitter_votes needs --jitter or --jitter_views")
+        return None
+    if tta_mask(tta):
+        raise ValueError("--jitter cannot go with --tta: products of colour and flip views are left out")
+    if dropout_draws:
+        raise ValueError("--jitter cannot go with --dropout_draws: colour views under Dropout draws are left out (the draws read "
+                         "the features of a plain forward)")
+    if only_preprocess:
+        raise ValueError("--jitter runs the network: it cannot go with --only_preprocess")
+    return factors
+
+
+def jitter_report(images: Sequence[tuple], factors):
+    """The rows of ``jitter_stats.csv`` (header first) and the folder summary: ``tta_report``'s columns and entries
+    (``views_report``) under the names of the colour views.  ``images``: per image ``(name, wood, h, w, mean_counts [3],
+    view_counts [V][3], stats [10])``."""
+    names = jitter_view_names(factors)
+    return views_report(images, names, names.index("identity") if "identity" in names else None)
+
+
+def add_jitter_arguments(ap) -> None:
+    """``--jitter`` and ``--jitter_views`` of the predict and evaluate drivers (``check_jitter_arguments`` holds their rules)."""
+    ap.add_argument("--jitter", choices=list(JITTER_CHOICES), default=None,
+                    help="average the colour-jitter views the training augmented over: training = the image, brightness 0.9 and "
+                         "1.1, saturation 0.8 and 1.2; the low-resolution logits of the views are averaged and everything "
+                         "downstream is about that mean.  --batch keeps counting images (default 1, 2 in bf16)")
+    ap.add_argument("--jitter_views", metavar="\"B,C,S;B,C,S;...\"", default=None,
+                    help="the same with views spelled out: 1..16 triples of brightness, contrast and saturation factors in "
+                         "[0, 4], applied in that order (not with --jitter)")
+
+
 def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
              target_size: int = 1024, stack: int = 1) -> SimpleNamespace:
     """The rank context of one folder run, and the state its later steps fill in.  An already initialised process group (gloo
     in the one-GPU rehearsals) is used as it is; ``wire_dev`` is where its collectives' tensors live (``collective_device``).
-    ``stack``: the entries the forward runs per image (the V views of ``--tta``; 1 otherwise): ``batch`` keeps counting
+    ``stack``: the entries the forward runs per image (the V views of ``--tta`` or ``--jitter``; 1 otherwise): ``batch`` keeps counting
     images, and its default shrinks so that the stack stays at a size the forward is already run at (4, or 8 in bf16)."""
     import time
     from collections import defaultdict
@@ -826,6 +922,7 @@ def add_shared_arguments(ap) -> None:
                     help="average the flip views the training augmented over: hflip / vflip (the image and its mirror image) or "
                          "flips (all four); the low-resolution logits of the un-flipped views are averaged and everything "
                          "downstream is about that mean.  --batch keeps counting images (default 1, 2 in bf16)")
+    add_jitter_arguments(ap)
     ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
                     help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
                          "(with --std; default: the constants of the reference's model class)")

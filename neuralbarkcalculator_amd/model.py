@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Mapping, Optional, Tuple
+from typing import List, Mapping, Optional, Tuple
 
 import numpy as np
 import torch
@@ -201,6 +201,43 @@ def tta_view_count(mask: int) -> int:
 def tta_view_names(mask: int):
     """The names of the views of a mask, in the order of the stack."""
     return [TTA_VIEW_NAMES[b] for b in range(4) if (int(mask) >> b) & 1]
+
+
+# the star of the training's amplitudes, ColorJitter(saturation=0.2, brightness=0.1) (__main__.py:160), identity first:
+# (brightness, contrast, saturation) per view
+JITTER_TRAINING = ((1.0, 1.0, 1.0), (0.9, 1.0, 1.0), (1.1, 1.0, 1.0), (1.0, 1.0, 0.8), (1.0, 1.0, 1.2))
+JITTER_VIEWS = {"training": JITTER_TRAINING}
+
+
+def resolve_jitter_views(views) -> np.ndarray:
+    """The float32 ``[V,3]`` factors (brightness, contrast, saturation) of ``"training"`` (``JITTER_TRAINING``) or of a sequence
+    of 1..16 triples, each factor finite and in [0, 4] (include/nbc.h, nbc_jitter_views); ``ValueError`` otherwise."""
+    what = "views must be one of %s or a sequence of 1..%d (brightness, contrast, saturation) triples with every factor in " \
+           "[0, 4], got %r" % (", ".join(sorted(JITTER_VIEWS)), _lib.JITTER_MAX_VIEWS, views)
+    if isinstance(views, str):
+        if views not in JITTER_VIEWS:
+            raise ValueError(what)
+        views = JITTER_VIEWS[views]
+    if isinstance(views, (bytes, dict, set)) or views is None:
+        raise ValueError(what)
+    try:
+        with np.errstate(over="ignore"):             # a factor beyond float32 becomes inf and is refused below
+            f = np.array(views, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(what)
+    if f.ndim != 2 or f.shape[1] != 3 or not 1 <= f.shape[0] <= _lib.JITTER_MAX_VIEWS or not bool(np.all((f >= 0) & (f <= 4))):
+        raise ValueError(what)
+    return np.ascontiguousarray(f)
+
+
+def jitter_view_names(factors) -> List[str]:
+    """The names of the views of a factor array, in the order of the stack: the non-unit factors joined by ``_`` (``b0.9``,
+    ``b1.1_s0.8``; ``%g`` of the factor), ``identity`` for (1, 1, 1)."""
+    names = []
+    for triple in resolve_jitter_views(factors):
+        parts = ["%s%g" % (tag, float(v)) for tag, v in zip("bcs", triple) if v != np.float32(1)]
+        names.append("_".join(parts) if parts else "identity")
+    return names
 
 
 class FCNResNet50:
@@ -456,6 +493,18 @@ class FCNResNet50:
         aligned = None
         if return_views:
             merged, aligned = merged
+        return self._views_tail(merged, aligned, n, h, w, exclude_nodes, labels_dtype, small_zones, logits_full, return_lowres,
+                                min_pixels)
+
+    def _views_tail(self, merged: torch.Tensor, aligned: Optional[torch.Tensor], n: int, h: int, w: int, exclude_nodes: bool,
+                    labels_dtype: torch.dtype, small_zones: bool, logits_full: Optional[torch.Tensor], return_lowres: bool,
+                    min_pixels: int):
+        """What ``predict_labels_tta`` and ``predict_labels_jitter`` do once the views' low-resolution logits are merged: today's
+        tail on ``merged`` f32 ``[N,3,h,w]`` and, when ``aligned`` f32 ``[V,N,3,h,w]`` is given, the same tail on each view and
+        the vote of the V final label maps."""
+        lh, lw = int(merged.shape[-2]), int(merged.shape[-1])
+        v = int(aligned.shape[0]) if aligned is not None else 0
+        return_views = aligned is not None
         remap_late = bool(small_zones)               # remove_small_zones comes before the remap (models.py:271-276)
         labels, counts = self.upsample_argmax(merged, (h, w), exclude_nodes=exclude_nodes and not remap_late,
                                               labels_dtype=labels_dtype, logits_full=logits_full)
@@ -475,6 +524,93 @@ class FCNResNet50:
             _lib.check(self._lib.nbc_vote_summary(words.data_ptr(), n, h, w, v, None, support.data_ptr(), stats.data_ptr(),
                                                   cur.cuda_stream), "nbc_vote_summary")
         return out + (vcounts.view(v, n, NUM_CLASSES), support, stats, aligned)
+
+    # ---- the colour-jitter views the training augmented over (include/nbc.h) ---------
+    def jitter_views(self, x_u8: torch.Tensor, views="training") -> torch.Tensor:
+        """The colour views of a batch on the device (nbc_jitter_views): ``x_u8`` uint8 ``[N,H,W,3]`` -> the stack uint8
+        ``[V*N,H,W,3]``, view-major (entry ``j * N + i`` is view j of image i), the views of ``views``
+        (``resolve_jitter_views``) in the order given.  Runs on the current stream."""
+        factors = resolve_jitter_views(views)
+        if isinstance(x_u8, torch.Tensor) and x_u8.dtype == torch.float32:
+            raise ValueError("the colour views are made of uint8 [N,H,W,3] frames: a float32 input is refused (torchvision's "
+                             "tensor path is other arithmetic)")
+        self._require_ctx()
+        if not isinstance(x_u8, torch.Tensor) or x_u8.device != self.device or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 \
+                or x_u8.numel() == 0 or x_u8.shape[3] != 3:
+            raise ValueError("x must be a non-empty uint8 [N,H,W,3] tensor on %s" % (self.device,))
+        x_u8 = x_u8.contiguous()
+        n, h, w = int(x_u8.shape[0]), int(x_u8.shape[1]), int(x_u8.shape[2])
+        v = int(factors.shape[0])
+        if v * n > 65535:
+            raise ValueError("the stack of %d views of %d images exceeds 65535 entries" % (v, n))
+        out = torch.empty((v * n, h, w, 3), dtype=torch.uint8, device=self.device)
+        ws = torch.empty((v * n,), dtype=torch.int64, device=self.device)      # nbc_jitter_workspace_bytes: 8 V N
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_jitter_views(x_u8.data_ptr(), n, h, w, factors.ctypes.data, v, out.data_ptr(), ws.data_ptr(),
+                                                  cur.cuda_stream), "nbc_jitter_views")
+        return out
+
+    def views_mean(self, lowres_views: torch.Tensor, n: int) -> torch.Tensor:
+        """The mean of the low-resolution logits of a stacked forward (nbc_views_mean): ``lowres_views`` f32 ``[V*N,3,h,w]`` (or
+        ``[V,N,3,h,w]``) -> ``m`` f32 ``[N,3,h,w]``: f32 adds in view order, one IEEE division; V = 1 keeps the view's bits."""
+        self._require_ctx()
+        n = int(n)
+        if not isinstance(lowres_views, torch.Tensor) or lowres_views.device != self.device or lowres_views.dtype != torch.float32 \
+                or lowres_views.dim() not in (4, 5) or lowres_views.numel() == 0 or lowres_views.shape[-3] != NUM_CLASSES \
+                or n < 1 or int(np.prod(lowres_views.shape[:-3])) % n \
+                or not 1 <= int(np.prod(lowres_views.shape[:-3])) // n <= _lib.JITTER_MAX_VIEWS:
+            raise ValueError("lowres_views must be a non-empty float32 [V*%d,3,h,w] tensor on %s, V in 1..%d" % (
+                n, self.device, _lib.JITTER_MAX_VIEWS))
+        lowres_views = lowres_views.contiguous()
+        v = int(np.prod(lowres_views.shape[:-3])) // n
+        lh, lw = int(lowres_views.shape[-2]), int(lowres_views.shape[-1])
+        mean = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_views_mean(lowres_views.data_ptr(), n, v, lh, lw, mean.data_ptr(), cur.cuda_stream),
+                       "nbc_views_mean")
+        return mean
+
+    def predict_labels_jitter(self, x: torch.Tensor, views="training", exclude_nodes: bool = False,
+                              labels_dtype: torch.dtype = torch.int64, small_zones: bool = False,
+                              logits_full: Optional[torch.Tensor] = None, return_lowres: bool = False,
+                              return_views: bool = False, min_pixels: int = 150):
+        """``predict_labels`` on the mean of the colour-jitter views the training augmented over.  A
+        composition of calls and nothing more: ``jitter_views``, one forward of the V*N stack, ``views_mean``, then today's tail
+        on the mean ``m`` of the low-resolution logits, as ``predict_labels_tta`` runs it.  ``x``: uint8 ``[N,H,W,3]`` (a
+        float32 input is a ``ValueError``); ``views``: "training" or 1..16 (brightness, contrast, saturation) triples; the set
+        ``[(1, 1, 1)]`` gives ``predict_labels``' own bits.
+
+        Returns what ``predict_labels_tta`` returns: ``(labels, counts)`` for ``m`` (``return_lowres`` appends ``m``), and with
+        ``return_views`` also ``(view_counts int64 [V,N,3], support uint8 [N,H,W], stats int64 [N,10], the views' low-resolution
+        logits f32 [V,N,3,h,w])``.  Afterwards no forward counts as the last one: ``dropout_draws`` raises until a plain forward
+        has run."""
+        factors = resolve_jitter_views(views)
+        if isinstance(x, torch.Tensor) and x.dtype == torch.float32:
+            raise ValueError("predict_labels_jitter takes uint8 [N,H,W,3] frames: a float32 input is refused (torchvision's "
+                             "tensor path is other arithmetic)")
+        n, h, w = self._check_input(x)
+        v = int(factors.shape[0])
+        if labels_dtype not in (torch.int64, torch.uint8):
+            raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
+        if int(min_pixels) < 0:
+            raise ValueError("min_pixels must not be negative")
+        if v * n > 65535:
+            raise ValueError("the stack of %d views of %d images exceeds 65535 entries" % (v, n))
+        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
+                                        or not logits_full.is_contiguous()
+                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
+            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
+                                                                                                    self.device))
+        lh, lw = out_hw(h, w, self.ARCH)
+        stack = self.jitter_views(x, factors)
+        lowres_views = torch.empty((v, n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
+        try:
+            self._forward(stack, v * n, h, w, lowres=lowres_views)
+        finally:
+            self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
+        mean = self.views_mean(lowres_views, n)
+        return self._views_tail(mean, lowres_views if return_views else None, n, h, w, exclude_nodes, labels_dtype, small_zones,
+                                logits_full, return_lowres, min_pixels)
 
     def lowres_logits(self, x: torch.Tensor) -> torch.Tensor:
         """Output of ``classifier.4`` (models.py:121) before the upsample: f32 ``[N,3,h,w]``."""

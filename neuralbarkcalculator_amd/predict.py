@@ -46,16 +46,17 @@ ROW_WIDTH = 5                                                              # (gl
 
 
 def generate_folders(root: str, only_preprocess: bool = False, votes: bool = False, tta_votes: bool = False,
-                     confidence: bool = False) -> None:
+                     confidence: bool = False, jitter_votes: bool = False) -> None:
     """predict.py:10-48.  ``votes``: the two directories of ``--dropout_votes`` as well; ``tta_votes``: the one of ``--tta_votes``;
-    ``confidence``: the one of ``--confidence``."""
+    ``confidence``: the one of ``--confidence``; ``jitter_votes``: the one of ``--jitter_votes``."""
     present = os.listdir(os.path.join(root, "samples"))
     wood_types = [w for w in WOOD_TYPES if w in present]
     for w in wood_types:
         os.makedirs(os.path.join(root, "processed", "samples", w), exist_ok=True)
     if not only_preprocess:
         for level in ("combined_images", "outputs") + (("dropout_votes", "dropout_support") if votes else ()) + \
-                (("tta_support",) if tta_votes else ()) + (("confidence",) if confidence else ()):
+                (("tta_support",) if tta_votes else ()) + (("confidence",) if confidence else ()) + \
+                (("jitter_support",) if jitter_votes else ()):
             for w in wood_types:
                 os.makedirs(os.path.join(root, "results", level, w), exist_ok=True)
 
@@ -344,19 +345,32 @@ def write_tta_report(results_dir: str, items, allrows, allt, views: int, precisi
     """``tta_stats.csv`` (tab separated) and ``tta_summary.json`` from the gathered rows: ``allrows`` as ``final_stats.csv`` is
     written from (the merged labels' counts), ``allt`` the ``(global_idx, merged counts 3, V x 3 view counts, 10 vote
     statistics)`` rows of ``--tta``.  Returns the summary."""
+    return _write_views_report(results_dir, "tta", items, allrows, allt, len(folder_run.tta_view_names(views)),
+                               lambda images: folder_run.tta_report(images, views), precision, bn_stats)
+
+
+def write_jitter_report(results_dir: str, items, allrows, allt, factors, precision: str, bn_stats: str) -> dict:
+    """``jitter_stats.csv`` (tab separated) and ``jitter_summary.json`` from the gathered rows, as ``write_tta_report`` writes
+    its two files: ``allt`` the ``(global_idx, the mean's counts 3, V x 3 view counts, 10 vote statistics)`` rows of ``--jitter``,
+    ``factors`` the float32 ``[V,3]`` view set.  Returns the summary."""
+    return _write_views_report(results_dir, "jitter", items, allrows, allt, len(factors),
+                               lambda images: folder_run.jitter_report(images, factors), precision, bn_stats)
+
+
+def _write_views_report(results_dir: str, stem: str, items, allrows, allt, nv: int, report, precision: str, bn_stats: str) -> dict:
+    """``<stem>_stats.csv`` and ``<stem>_summary.json`` of a run over ``nv`` views; ``report(images)``: the table and summary."""
     import json
-    nv = len(folder_run.tta_view_names(views))
     by_idx = {int(g[0]): g[1:] for g in allt}
     images = []
     for g in allrows:
         t = by_idx[int(g[0])]
         images.append((items[int(g[0])]["name"], items[int(g[0])]["wood"], int(g[1]), int(g[2]), t[:3], t[3: 3 + 3 * nv].reshape(nv, 3),
                        t[3 + 3 * nv:]))
-    table, summary = folder_run.tta_report(images, views)
-    with open(os.path.join(results_dir, "tta_stats.csv"), "w") as f:
+    table, summary = report(images)
+    with open(os.path.join(results_dir, stem + "_stats.csv"), "w") as f:
         csv.writer(f, delimiter="\t").writerows(table)
     summary = dict({"precision": precision, "bn_stats": bn_stats}, **summary)
-    with open(os.path.join(results_dir, "tta_summary.json"), "w") as f:
+    with open(os.path.join(results_dir, stem + "_summary.json"), "w") as f:
         json.dump(summary, f, indent=2, sort_keys=True)
         f.write("\n")
     return summary
@@ -461,7 +475,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    streams: int = None, arch: str = "auto", bn_stats: str = "running", precision_auto: bool = False,
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
                    dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None,
-                   tta="none", tta_votes: bool = False, confidence: bool = False, confidence_threshold: float = None) -> dict:
+                   tta="none", tta_votes: bool = False, confidence: bool = False, confidence_threshold: float = None,
+                   jitter=None, jitter_views=None, jitter_votes: bool = False) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -516,6 +531,12 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     (``calibration.CONFIDENCE_COLUMNS``: the mean confidence, the share and mm2 of the pixels below ``confidence_threshold``
     -- default 0.9 --, expected Bark / Node % and mm2 beside the hard ones) and ``results/confidence_summary.json``.
     ``final_stats.csv`` and the label PNGs stay byte for byte what they are without the flag.
+    ``jitter`` ("training") or ``jitter_views`` (1..16 (brightness, contrast, saturation) triples, or the string of
+    ``--jitter_views``; not with ``tta`` or ``dropout_draws``): ``FCNResNet50.predict_labels_jitter`` stands where
+    ``predict_labels`` does, so the label PNGs, ``final_stats.csv`` and ``zones`` are those of the mean of the colour-jitter views
+    (DESIGN.md 3.17).  ``batch`` keeps counting images (default 1, 2 in bf16).  Rank 0 writes ``results/jitter_stats.csv`` and
+    ``results/jitter_summary.json`` (``folder_run.jitter_report``: ``tta_stats.csv``'s columns under the views' names).
+    ``jitter_votes`` (with a view set only): also ``results/jitter_support/<wood>/<name>``, the support byte of the views' vote.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -529,8 +550,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     folder_run.check_zones_arguments(Z, zones_cap)   # refusals first: nothing has touched a device yet
     ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
     T = folder_run.check_tta_arguments(tta, tta_votes, D)   # the view mask, 0 = off
-    NV = len(folder_run.tta_view_names(T))
-    TS = bool(tta_votes)
+    J = folder_run.check_jitter_arguments(jitter, jitter_views, jitter_votes, tta, D)   # the colour views' factors, None = off
+    NV = len(J) if J is not None else len(folder_run.tta_view_names(T))
+    TS = bool(tta_votes) or bool(jitter_votes)
+    VIEWS = bool(T) or J is not None                 # the forward runs a stack of views: the flip views or the colour views
+    SUPPORT = "jitter_support" if J is not None else "tta_support"
     from . import calibration as cal
     C = bool(confidence)
     check_confidence_arguments(C, confidence_threshold, D)
@@ -554,7 +578,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if C:
             m.softmax_census(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev), confidence=True)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
-                        lambda root_: generate_folders(root_, votes=V, tta_votes=TS, confidence=C), warm, normalization=normalization)
+                        lambda root_: generate_folders(root_, votes=V, tta_votes=bool(tta_votes), confidence=C,
+                                                       jitter_votes=bool(jitter_votes)), warm, normalization=normalization)
     if D:
         folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
 
@@ -623,11 +648,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                 label_paths.append(vpath)
                 write_png(vpath, img, lvl_lab)
             vrows[k, 0], vrows[k, 1:-1], vrows[k, -1] = mine[k], vstats, int(np.count_nonzero(vlab != lab))
-        if views is not None:                        # --tta: (merged counts, the views' counts, the vote statistics, the support plane or None)
+        if views is not None:                        # --tta / --jitter: (merged counts, the views' counts, the vote statistics, the support plane or None)
             mcounts, vcounts, tstats, sup = views
             trows[k, 0], trows[k, 1:4], trows[k, 4: 4 + 3 * NV], trows[k, 4 + 3 * NV:] = mine[k], mcounts, vcounts.reshape(-1), tstats
             if sup is not None:
-                spath = os.path.join(root, "results", "tta_support", d["wood"], d["name"])
+                spath = os.path.join(root, "results", SUPPORT, d["wood"], d["name"])
                 label_paths.append(spath)
                 write_png(spath, sup, lvl_lab)
         if conf is not None:
@@ -655,10 +680,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     # the zones' slots: ZCAP rows per image and the zone counts
     zring = [(torch.empty((batch, ZCAP, zn.ZONE_ROW), dtype=torch.int64).pin_memory(), torch.empty(batch, dtype=torch.int64).pin_memory())
              for _ in range(r.depth)] if Z else None
-    # --tta: per slot the views' counts and the vote statistics per image, and (--tta_votes) the support planes
+    # --tta / --jitter: per slot the views' counts and the vote statistics per image, and (--tta_votes, --jitter_votes) the support planes
     tring = [(torch.empty((NV, batch, 3), dtype=torch.int64).pin_memory(),
               torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
-              torch.empty(full if TS else 0, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if T else None
+              torch.empty(full if TS else 0, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if VIEWS else None
     # --confidence: per stream the full-resolution logits; per slot the confidence planes and the census rows
     logits_buf = [torch.empty(3 * full, dtype=torch.float32, device=dev) for _ in range(r.n_streams)] if C else None
     cring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, cal.WORDS), dtype=torch.int64).pin_memory())
@@ -671,20 +696,21 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:   # an oversized stale processed frame (run_loop)
             ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
         if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
-            mdl.autotune(mdl.tta_views(x, T) if T else x)   # once per distinct full-batch shape and model object
+            mdl.autotune(mdl.tta_views(x, T) if T else (mdl.jitter_views(x, J) if J is not None else x))   # once per distinct full-batch shape and model object
             tuned.add((sid, (n, h, w)))
         lg = None
         if C:                                        # the forward writes its full-resolution logits as well
             lg = (logits_buf[sid][: 3 * need] if 3 * need <= logits_buf[sid].numel() else
                   torch.empty(3 * need, dtype=torch.float32, device=dev)).view(n, 3, h, w)
-        if T:                                       # the same tail on the mean of the flip views; the views' own figures beside it
+        if VIEWS:                                   # the same tail on the mean of the views; the views' own figures beside it
             if tring[slot][0].shape[1] < n or (TS and tring[slot][2].numel() < need):
                 tring[slot] = (torch.empty((NV, n, 3), dtype=torch.int64).pin_memory(),
                                torch.empty((n, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
                                torch.empty(need if TS else 0, dtype=torch.uint8).pin_memory())
-            labels, counts, vcounts, sup, tstats, _ = mdl.predict_labels_tta(x, T, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                                             small_zones=small_zones, return_views=True,
-                                                                             **(dict(logits_full=lg) if C else {}))
+            on_views = (lambda **k: mdl.predict_labels_tta(x, T, **k)) if T else (lambda **k: mdl.predict_labels_jitter(x, J, **k))
+            labels, counts, vcounts, sup, tstats, _ = on_views(exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
+                                                               small_zones=small_zones, return_views=True,
+                                                               **(dict(logits_full=lg) if C else {}))
             tring[slot][0][:, :n].copy_(vcounts, non_blocking=True)
             tring[slot][1][:n].copy_(tstats, non_blocking=True)
             if TS:
@@ -740,7 +766,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             znum = zring[slot][1][:n].numpy()
             zone = [(zring[slot][0][j, :int(znum[j])].numpy().copy() if znum[j] <= ZCAP else None,) for j in range(n)]
         views = [None] * n
-        if T:
+        if VIEWS:
             vc, tst = tring[slot][0][:, :n].numpy().copy(), tring[slot][1][:n].numpy().copy()
             sups = tring[slot][2][: n * h * w].numpy().reshape(n, h, w).copy() if TS else [None] * n
             views = [(cnts[j], vc[:, j], tst[j], sups[j]) for j in range(n)]
@@ -778,10 +804,12 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if r.rank == 0:
             write_dropout_report(os.path.join(root, "results"), items, allrows, alld, D, dropout_p, dropout_seed, r.precision,
                                  bn_stats, old_stats, dropout_compare, allv)
-    if T:
+    if VIEWS:
         allt = folder_run.gather(r, trows, TROW)             # one more all_gather, as the draws' rows take
-        if r.rank == 0:
+        if r.rank == 0 and T:
             write_tta_report(os.path.join(root, "results"), items, allrows, allt, T, r.precision, bn_stats)
+        if r.rank == 0 and J is not None:
+            write_jitter_report(os.path.join(root, "results"), items, allrows, allt, J, r.precision, bn_stats)
     if C:                                            # a fixed-width row per image and one pooled census per rank
         allc = folder_run.gather(r, crows, CROW)
         census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cpool.view(np.int64)])[None], r.world, r.dist, r.wire_dev,
@@ -817,6 +845,9 @@ def main(argv=None):
     folder_run.add_zones_arguments(ap)
     ap.add_argument("--tta_votes", action="store_true",
                     help="with --tta: also write results/tta_support/ (grey, 255 = every view gives the pixel the same label)")
+    ap.add_argument("--jitter_votes", action="store_true",
+                    help="with --jitter or --jitter_views: also write results/jitter_support/ (grey, 255 = every view gives the "
+                         "pixel the same label)")
     ap.add_argument("--confidence", action="store_true",
                     help="also write the softmax confidence of the plain forward: results/confidence/ (grey, the winning class's "
                          "probability in 1/256, before remove_small_zones), results/confidence_stats.csv and "
@@ -830,6 +861,8 @@ def main(argv=None):
     try:                                                 # refused as argument errors, before any device is touched
         check_confidence_arguments(args.confidence, args.confidence_threshold, args.dropout_draws, args.only_preprocess)
         folder_run.check_tta_arguments(args.tta, args.tta_votes, args.dropout_draws, args.only_preprocess)
+        folder_run.check_jitter_arguments(args.jitter, args.jitter_views, args.jitter_votes, args.tta, args.dropout_draws,
+                                          args.only_preprocess)
         folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
                                            args.only_preprocess, args.dropout_votes)
         if args.dropout_compare is not None:
@@ -857,6 +890,8 @@ def main(argv=None):
         kw.update(zones=True, zones_cap=args.zones_cap)
     if args.tta != "none":
         kw.update(tta=args.tta, tta_votes=args.tta_votes)
+    if args.jitter is not None or args.jitter_views is not None:
+        kw.update(jitter=args.jitter, jitter_views=args.jitter_views, jitter_votes=args.jitter_votes)
     if args.confidence:
         kw.update(confidence=True, confidence_threshold=args.confidence_threshold)
     if args.normalization is not None:
