@@ -689,6 +689,62 @@ int nbc_jitter_views(const uint8_t* x_dev, int N, int H, int W, const float* fac
  * overlapping the input. */
 int nbc_views_mean(const float* lowres_views_dev, int N, int V, int h, int w, float* mean_dev, void* hip_stream);
 
+/* ---- the crop windows the training augmented over ----------------------------------------------
+ * The reference trains on RandomCrop(crop_size) windows of a frame with crop_size = 512 (__main__.py:158-165, 260) and then
+ * predicts from whole 1024-wide frames.  These calls cut a batch into windows of the training's size and blend the network's
+ * answers for them back into the frame's grid; the forward between them is nbc_forward on the stack.
+ *   S, T     the window side and the stride: S a multiple of 8 in 32..2048, T a multiple of 8 with 8 <= T <= S <= 8 T.  The
+ *            cell is NBC_WINDOW_CELL = 8 pixels, the trunk's output stride.
+ *   grid     per axis of length L >= 8 (H or W): L8 = 8 ceil(L / 8), the extent E = min(S, L8).  L8 <= S: one window at offset
+ *            0.  Otherwise the offsets k T for every k with k T + S < L8, then a last offset L8 - S: n = 1 + ceil((L8 - S) / T)
+ *            windows.  Every offset is a multiple of 8 (a window's stride-2 layers sample the frame's own pixel phase), every
+ *            window of an image has the shape E_y x E_x, window k = r n_x + c has the offsets (oy_r, ox_c).  K = n_y n_x <=
+ *            NBC_WINDOW_MAX_K and K N <= 65535.
+ *   fill     rows L .. L8 - 1 (at most 7; columns alike) are filled by reflection without repeating the edge: index i reads
+ *            index 2 (L - 1) - i -- padding_mode='reflect' of the training's pad_resize (utils.py:242-247), numpy.pad(mode=
+ *            "reflect").  The reach stays inside the frame for every L >= 8.
+ *   stack    window-major, like nbc_tta_views' stack: entry k N + i is window k of image i
+ *   merged   on the low-resolution logits, a grid of h x w = L8_y / 8 x L8_x / 8 cells -- ceil(H / 8) x ceil(W / 8), the shape of
+ *            the plain forward's own low-resolution logits.  Window k gives its cell (y - oy / 8, x - ox / 8) to frame cell
+ *            (y, x).  With e = E / 8 and cap = max(1, e / 2) (integer division) the per-axis weight of window cell j is t(j) =
+ *            min(dl, dr, cap): dl = j + 1 if the window's offset is > 0, dr = e - j if offset + E < L8, each unbounded
+ *            otherwise (a window border that is the frame's own border is not down-weighted).  A window's weight at a cell is
+ *            w = t_y t_x, an integer <= 16384 (NBC_BLEND_TENT), or 1 everywhere (NBC_BLEND_UNIFORM).  A cell that one window
+ *            covers: m = v, the window's own bits (-0 included).  Otherwise acc = float(w_0) v_0, then acc = acc + float(w_k)
+ *            v_k over the covering windows in ascending k -- every multiply and add a rounded f32 operation of its own, no
+ *            contraction -- and m = acc / float(sum of w_k), one IEEE f32 division; the sum is an exact integer below 2^24.  A
+ *            NaN in any covering window gives NaN.
+ * The tail upsamples the h x w grid to H x W as interpolate(align_corners=False) does for the plain forward: where H is no
+ * multiple of 8 that is the stretch of less than one cell the plain path has always made.
+ * Left out: the EfficientNet networks (output stride 32 and fixed asymmetric pads: a grid of their own), per-image BatchNorm
+ * statistics (a window's statistics are not the frame's), products with the flip or colour views, per-window votes (the number of
+ * windows over a pixel varies) and the training's exact 1024 x 1024 pad_resize frame. */
+enum { NBC_WINDOW_CELL = 8, NBC_WINDOW_MAX_K = 1024 };
+enum { NBC_BLEND_TENT = 0, NBC_BLEND_UNIFORM = 1 };
+/* The window grid of an H x W frame: the one place Python and the kernels take it from.  Host only, no HIP call.
+ * dims       int [4]: E_y, E_x, n_y, n_x
+ * offsets_y  nullable, int [n_y] (NBC_WINDOW_MAX_K entries always suffice); offsets_x likewise, [n_x]
+ * NBC_ERR_INVALID: a null dims, S or T outside the rules above, H or W < 8, H * W >= 2^31, K > NBC_WINDOW_MAX_K. */
+int nbc_window_grid(int H, int W, int S, int T, int* dims, int* offsets_y, int* offsets_x);
+/* The K windows of every image of a batch in one launch.  No context: csrc/windows.hip.
+ * x_dev    NBC_IN_U8_NHWC [N][H][W][3] at any alignment, or NBC_IN_F32_NCHW [N][3][H][W], 4-byte aligned
+ * out_dev  [K][N] entries of E_y x E_x in x's layout; must not overlap x
+ * Each source row is read once and every window written once: 3 H W + 3 K E_y E_x bytes per u8 image.  An image's windows are
+ * the same alone, in any batch and on any stream.  Runs on hip_stream (the caller's current device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer, an unknown dtype, what nbc_window_grid refuses, N < 1 or K N > 65535, an
+ * f32 pointer that is not 4-byte aligned, out_dev overlapping x_dev. */
+int nbc_window_views(const void* x_dev, int x_dtype, int N, int H, int W, int S, int T, void* out_dev, void* hip_stream);
+/* The merged low-resolution logits of a stacked forward of nbc_window_views' stack.  No context: csrc/windows.hip.
+ * lowres_windows_dev  float32 [K][N][3][E_y / 8][E_x / 8]
+ * H, W                the frame's size in pixels, as nbc_window_views took it
+ * blend               NBC_BLEND_TENT or NBC_BLEND_UNIFORM
+ * merged_dev          float32 [N][3][h][w]; overwritten
+ * An element of merged depends on the window cells that cover it alone: an image's bits are the same alone, in any batch and
+ * on any stream.  NBC_ERR_INVALID, before any HIP call: as nbc_window_views, an unknown blend, a pointer that is not 4-byte
+ * aligned, merged_dev overlapping the input. */
+int nbc_window_merge(const float* lowres_windows_dev, int N, int H, int W, int S, int T, int blend, float* merged_dev,
+                     void* hip_stream);
+
 /* ---- the zones of a label map ------------------------------------------------------------------
  * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and
  * whether the bark is one sheet or many fragments.  The reference has no such code; the host restatement is

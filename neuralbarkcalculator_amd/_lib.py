@@ -31,6 +31,8 @@ CENSUS_BINS, CENSUS_WORDS = 256, 3341               # NBC_CENSUS_BINS, NBC_CENSU
 CENSUS_H, CENSUS_R, CENSUS_RS, CENSUS_M, CENSUS_B, CENSUS_NONFINITE = 0, 2304, 2816, 3328, 3337, 3340   # NBC_CENSUS_*
 TTA_IDENTITY, TTA_HFLIP, TTA_VFLIP, TTA_HVFLIP, TTA_FLIPS = 1, 2, 4, 8, 15   # NBC_TTA_*
 JITTER_MAX_VIEWS = 16                               # NBC_JITTER_MAX_VIEWS
+WINDOW_CELL, WINDOW_MAX_K = 8, 1024                 # NBC_WINDOW_CELL, NBC_WINDOW_MAX_K
+BLEND_TENT, BLEND_UNIFORM = 0, 1                    # NBC_BLEND_*
 
 
 class NbcTensor(C.Structure):
@@ -137,6 +139,9 @@ SIGNATURES = {
     "nbc_jitter_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "nbc_jitter_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nbc_views_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbc_window_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nbc_window_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbc_window_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

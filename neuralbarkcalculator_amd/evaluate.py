@@ -96,6 +96,12 @@ batch's stream, their nine counts ride back with the batch, and rank 0 writes ``
 each figure's difference from the ``identity`` view's) and a ``"jitter"`` entry in the summary.  ``evaluation_stats.csv``
 keeps its columns.
 
+``--windows S`` (with ``--windows_stride``, ``--windows_blend``) scores sliding-window inference at the training's crop size
+ in every metric and option above: ``predict_labels_windows`` stands where ``predict_labels`` does and the
+summary notes ``"windows": {window, stride, blend}``.  ``--windows_compare`` also runs the plain forward of each frame; the
+confusion of its final labels rides back with the batch and rank 0 writes ``results/windows_evaluation.csv``
+(``jitter_evaluation`` on the rows ``identity`` -- the frame -- and ``windows``, pooled over the folder).
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -349,6 +355,26 @@ def write_jitter_evaluation(results_dir: str, allrows, all_views, factors) -> di
     return {"views": names, "factors": [[float(v) for v in t] for t in factors], "evaluation": doc}
 
 
+WINDOWS_EVALUATION_CSV = "windows_evaluation.csv"                                # --windows_compare, under results/
+WINDOWS_EVALUATION_ROWS = ["identity", "windows"]                                # the plain forward of the frame, the blend of its windows
+
+
+def write_windows_evaluation(results_dir: str, allrows, all_win) -> dict:
+    """``windows_evaluation.csv`` (tab separated, like ``jitter_evaluation.csv``) from the gathered ``(global_idx, the plain
+    forward's 9 confusion cells, the windows' 9)`` rows ``all_win`` (final labels, after ``remove_small_zones``), summed over the
+    evaluated images of ``allrows``: ``jitter_evaluation`` on the two pooled confusions, the windows' row with its difference
+    from the frame's.  Returns the ``"evaluation"`` entry of the summary's ``"windows"``."""
+    done = {int(g[0]) for g in allrows if int(g[3]) == STATUS_OK}
+    total = np.zeros((2, 3, 3), dtype=np.int64)
+    for g in np.asarray(all_win, dtype=np.int64).reshape(-1, 1 + 9 * 2):
+        if int(g[0]) in done:
+            total += g[1:].reshape(2, 3, 3)
+    table, doc = jitter_evaluation(WINDOWS_EVALUATION_ROWS, total)
+    with open(os.path.join(results_dir, WINDOWS_EVALUATION_CSV), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    return doc
+
+
 def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: str,
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
@@ -406,7 +432,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     class_weights=metrics.REFERENCE_CLASS_WEIGHTS, class_weights_source: str = "reference", zones: bool = False,
                     zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
                     contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None,
-                    jitter=None, jitter_views=None) -> dict:
+                    jitter=None, jitter_views=None, windows: int = None, windows_stride: int = None, windows_blend: str = None,
+                    windows_compare: bool = False) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -433,6 +460,14 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     (default 1, 2 in bf16).  Each view's own final labels (after ``remove_small_zones``) go through ``confusion`` against the
     dual as well: rank 0 writes ``results/jitter_evaluation.csv`` (``jitter_evaluation``: a row per view, pooled over the
     folder) and the summary gains ``"jitter": {"views": [...], "factors": [...], "evaluation": {...}}``.
+    ``windows`` = S (with ``windows_stride``, default S / 2 rounded down to a multiple of 8, and ``windows_blend`` "tent" or
+    "uniform"; not with ``tta``, ``jitter`` or per-image ``bn_stats``; ResNet-50 networks only):
+    ``FCNResNet50.predict_labels_windows`` stands where ``predict_labels`` does, so every row and every optional pass is about
+    the blend of the S x S windows; ``batch`` keeps counting images (default 1, 2 in bf16) and the summary gains
+    ``"windows": {"window", "stride", "blend"}``.  ``windows_compare``: the plain forward of each frame runs as well and the
+    confusion of its final labels (after ``remove_small_zones``) rides back; rank 0 writes ``results/windows_evaluation.csv``
+    (``jitter_evaluation`` on the rows "identity" -- the frame -- and "windows", pooled over the folder) and the summary's entry
+    gains ``"evaluation"``.
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
@@ -455,8 +490,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     T = folder_run.check_tta_arguments(tta)         # the view mask, 0 = off
     J = folder_run.check_jitter_arguments(jitter, jitter_views, tta=tta)   # the colour views' factors, None = off
     NV = len(J) if J is not None else 0
+    WN = folder_run.check_windows_arguments(windows, windows_stride, windows_blend, windows_compare, tta, jitter, jitter_views,
+                                            bn_stats=bn_stats, arch=arch)   # the crop windows, None = off
+    WC = WN is not None and WN.compare
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size,
-                            stack=max(1, NV, len(folder_run.tta_view_names(T))))
+                            stack=max(1, NV, len(folder_run.tta_view_names(T))), windows=WN)
     dev, batch = r.dev, r.batch
 
     def warm(m):                                     # the remove_small_zones workspace (--jitter: of the views' stack) and, with ``loss`` / ``ce``, theirs
@@ -537,6 +575,12 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if NV:
         jrows[:, 0] = -1                                              # a skipped image has no row
 
+    # --windows_compare: per slot the confusion of the plain forward's final labels; per image the row that travels
+    wring = [torch.empty((batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)] if WC else None
+    wrows = np.zeros((len(mine), 1 + 9 * 2), dtype=np.int64) if WC else None
+    if WC:
+        wrows[:, 0] = -1                                              # a skipped image has no row
+
     def launch(slot, sid, part, x, tgt):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
@@ -547,6 +591,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             vlab, _ = mdl.upsample_argmax(vlow.view((NV * n,) + tuple(vlow.shape[2:])), (h, w), labels_dtype=torch.uint8)
             mdl.remove_small_zones(vlab)
             jring[slot][:, :n].copy_(mdl.confusion(vlab, tgt.repeat(NV, 1, 1)).view(NV, n, 3, 3), non_blocking=True)
+        elif WN is not None:                                          # or on the blend of the crop windows
+            labels, _ = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, labels_dtype=torch.uint8, logits_full=lg)
+            if WC:                                                    # the plain forward's final labels beside it
+                plab, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, small_zones=True)
+                wring[slot][:n].copy_(mdl.confusion(plab, tgt), non_blocking=True)
         else:
             labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
@@ -616,6 +665,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                 ce_rows[k, 1:] = ce_ring[slot][j].numpy().view(np.int64)
             if NV:
                 jrows[k, 0], jrows[k, 1:] = mine[k], jring[slot][:, j].numpy().reshape(-1)
+            if WC:                                                    # the frame's confusion, then the windows' (the clean one)
+                wrows[k, 0], wrows[k, 1:10], wrows[k, 10:] = mine[k], wring[slot][j].numpy().reshape(-1), conf[1, j]
         return futures
 
     def first_frame():                               # the calibration guard's: this rank's first image that fits
@@ -646,6 +697,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         all_census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cal_pool.view(np.int64)])[None], r.world, r.dist,
                                                        r.wire_dev, width=1 + cal.WORDS)[:, 1:])
     all_views = folder_run.gather(r, jrows, 1 + 9 * NV) if NV else None
+    all_win = folder_run.gather(r, wrows, 1 + 9 * 2) if WC else None
     summary = gathered = None
     if r.rank == 0:
         gathered = allrows.tolist()
@@ -665,6 +717,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             summary["tta"] = {"views": folder_run.tta_view_names(T)}
         if NV:
             summary["jitter"] = write_jitter_evaluation(os.path.join(root, "results"), allrows, all_views, J)
+        if WN is not None:
+            summary["windows"] = {"window": WN.window, "stride": WN.stride, "blend": WN.blend}
+            if WC:
+                summary["windows"]["evaluation"] = write_windows_evaluation(os.path.join(root, "results"), allrows, all_win)
         with open(os.path.join(root, SUMMARY_JSON), "w") as f:
             json.dump(summary, f, indent=1)
     out = dict(folder_run.finish(r), images_evaluated_this_rank=int((rows[:, 3] == STATUS_OK).sum()), summary=summary,
@@ -730,6 +786,13 @@ def format_summary(summary: dict) -> str:
             f, d = entry["figures"], entry["difference"]
             lines.append("view %s (its own final labels, pooled): " % name + ", ".join(
                 "%s %.3f%s" % (k, f[k], "" if d is None else " (%+.3f)" % d[k]) for k in ("iou_mean", "f1_mean", "Bark %", "Node %")))
+    if summary.get("windows"):
+        wn = summary["windows"]
+        lines.append("crop windows of %d pixels every %d, %s blend" % (wn["window"], wn["stride"], wn["blend"]))
+        for name, entry in (wn.get("evaluation") or {}).items():
+            f, d = entry["figures"], entry["difference"]
+            lines.append("%s (final labels, pooled): " % ("the frame" if name == "identity" else "the windows") + ", ".join(
+                "%s %.3f (%+.3f)" % (k, f[k], d[k]) for k in ("iou_mean", "f1_mean", "Bark %", "Node %")))
     if summary.get("contours"):
         c = summary["contours"]
         fmt = lambda v, spec: "-" if v is None else spec % v
@@ -790,6 +853,8 @@ def main(argv=None):
         check_contour_arguments(args.contours, args.contour_tolerance)
         check_calibration_arguments(args.calibration, args.ece_bins)
         folder_run.check_jitter_arguments(args.jitter, args.jitter_views, tta=args.tta)
+        folder_run.check_windows_arguments(args.windows, args.windows_stride, args.windows_blend, args.windows_compare, args.tta,
+                                           args.jitter, args.jitter_views, bn_stats=args.bn_stats, arch=args.arch)
     except ValueError as e:
         ap.error(str(e))
     if args.exclude_nodes:
@@ -827,6 +892,9 @@ def main(argv=None):
         kw["tta"] = args.tta
     if args.jitter is not None or args.jitter_views is not None:
         kw.update(jitter=args.jitter, jitter_views=args.jitter_views)
+    if args.windows is not None:
+        kw.update(windows=args.windows, windows_stride=args.windows_stride, windows_blend=args.windows_blend,
+                  windows_compare=args.windows_compare)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

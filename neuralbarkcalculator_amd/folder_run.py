@@ -594,12 +594,128 @@ def add_jitter_arguments(ap) -> None:
                          "[0, 4], applied in that order (not with --jitter)")
 
 
+# ---- the crop windows the training augmented over (--windows): argument checks, the grid, the report ------------------------
+WINDOW_BLENDS = ("tent", "uniform")
+WINDOW_COLUMNS = ["Name", "Type", "Height", "Width", "Window", "Grid", "Bark %", "Node %"]
+WINDOW_COMPARE_COLUMNS = ["Plain Bark %", "Plain Node %", "Bark % difference", "Node % difference", "Changed pixels %"]
+
+
+def default_window_stride(window: int) -> int:
+    """``--windows_stride`` when it is not given: half the window, rounded down to a multiple of 8."""
+    return int(window) // 2 // 8 * 8
+
+
+def check_windows_arguments(windows=None, windows_stride=None, windows_blend=None, windows_compare: bool = False, tta=None,
+                            jitter=None, jitter_views=None, dropout_draws=None, only_preprocess: bool = False,
+                            bn_stats: str = None, arch: str = None):
+    """``ValueError`` for what ``--windows`` and its companions refuse before any device is touched: a companion without
+    ``--windows``; a window that is no multiple of 8 in 32..2048, a stride that is no multiple of 8 with 8 <= stride <= window
+    <= 8 stride, an unknown blend (include/nbc.h, nbc_window_grid); ``--windows`` with ``--tta``, ``--jitter`` /
+    ``--jitter_views`` (products of views are left out), ``--dropout_draws`` (the draws read the features of a plain forward),
+    ``--only_preprocess`` (no network runs), ``--bn_stats image*`` (statistics per window are not the frame's) or a named
+    EfficientNet ``arch`` (``check_windows_arch`` once ``"auto"`` is resolved).  Returns ``SimpleNamespace(window, stride, blend,
+    compare)``, None = off."""
+    if windows is None:
+        given = [n for n, v in (("--windows_stride", windows_stride), ("--windows_blend", windows_blend)) if v is not None]
+        if windows_compare:
+            given.append("--windows_compare")
+        if given:
+            raise ValueError("%s needs --windows" % ", ".join(given))
+        return None
+    if isinstance(windows, bool) or int(windows) != windows or int(windows) % 8 or not 32 <= int(windows) <= 2048:
+        raise ValueError("--windows must be a multiple of 8 in 32..2048, got %r" % (windows,))
+    window = int(windows)
+    stride = default_window_stride(window) if windows_stride is None else windows_stride
+    if isinstance(stride, bool) or int(stride) != stride or int(stride) % 8 or not 8 <= int(stride) <= window <= 8 * int(stride):
+        raise ValueError("--windows_stride must be a multiple of 8 with 8 <= stride <= window <= 8 * stride, got %r for "
+                         "--windows %d" % (stride, window))
+    blend = "tent" if windows_blend is None else windows_blend
+    if blend not in WINDOW_BLENDS:
+        raise ValueError("--windows_blend must be one of %s, got %r" % (", ".join(WINDOW_BLENDS), blend))
+    if tta_mask(tta):
+        raise ValueError("--windows cannot go with --tta: products of crop windows and flip views are left out")
+    if jitter not in (None, "none") or jitter_views is not None:
+        raise ValueError("--windows cannot go with --jitter or --jitter_views: products of crop windows and colour views are left out")
+    if dropout_draws:
+        raise ValueError("--windows cannot go with --dropout_draws: the draws read the features of a plain forward")
+    if only_preprocess:
+        raise ValueError("--windows runs the network: it cannot go with --only_preprocess")
+    if bn_stats in ("image", "image_f16x2"):
+        raise ValueError("--windows cannot go with --bn_stats %s: statistics per window are not the shipped tool's per-frame "
+                         "statistics" % bn_stats)
+    if arch not in (None, "auto"):
+        check_windows_arch(arch)
+    return SimpleNamespace(window=window, stride=int(stride), blend=blend, compare=bool(windows_compare))
+
+
+def check_windows_arch(arch: str) -> None:
+    """``ValueError`` for ``--windows`` on an EfficientNet network (every rank holds the resolved architecture alike, so every
+    rank refuses alike)."""
+    from . import topology
+    if topology.is_efficientnet(arch):
+        raise ValueError("--windows is refused for %s: its output stride is 32 and its fixed asymmetric pads need a window grid "
+                         "of their own" % arch)
+
+
+def windows_report(images: Sequence[tuple], window: int, stride: int, blend: str, compare: bool = False):
+    """The rows of ``windows_stats.csv`` (header first) and the folder summary.  ``images``: per image ``(name, wood, h, w,
+    (E_y, E_x, n_y, n_x), merged_counts [3], plain_counts [3] or None, changed pixels or None)`` with the pixels per class of the
+    merged final labels and -- ``compare`` -- of the plain forward's, and the pixels on which the two label maps differ.  Every
+    percentage is printed as ``final_stats.csv`` prints one (``percent_string``); a difference (merged minus plain) and the
+    changed share are each one correctly rounded division of exact integers, formatted '{:.5f}'.  The summary: the folder means
+    of the merged pair (with ``compare``: of the plain pair, of the absolute differences and of the changed share) and the
+    images per grid shape."""
+    rows, sums, grids = [WINDOW_COLUMNS + (WINDOW_COMPARE_COLUMNS if compare else [])], {}, {}
+    for name, wood, h, w, grid, mc, pc, changed in images:
+        px = int(h) * int(w)
+        ey, ex, ny, nx = (int(v) for v in grid)
+        mc = [int(v) for v in mc]
+        shape = "%dx%d %dx%d" % (ey, ex, ny, nx)
+        grids[shape] = grids.get(shape, 0) + 1
+        row = [name, wood, str(int(h)), str(int(w)), "%dx%d" % (ey, ex), "%dx%d" % (ny, nx), percent_string(mc[1], px),
+               percent_string(mc[2], px)]
+        figures = {"merged_bark": (100 * mc[1]) / px, "merged_node": (100 * mc[2]) / px}
+        if compare:
+            pc = [int(v) for v in pc]
+            diff = [(100 * (mc[c] - pc[c])) / px for c in (1, 2)]
+            figures.update(plain_bark=(100 * pc[1]) / px, plain_node=(100 * pc[2]) / px, abs_diff_bark=abs(diff[0]),
+                           abs_diff_node=abs(diff[1]), changed=(100 * int(changed)) / px)
+            row += [percent_string(pc[1], px), percent_string(pc[2], px), "{:.5f}".format(diff[0]), "{:.5f}".format(diff[1]),
+                    "{:.5f}".format(figures["changed"])]
+        rows.append(row)
+        for k, v in figures.items():
+            sums[k] = sums.get(k, 0.0) + v
+    n = len(rows) - 1
+    return rows, {"images": n, "window": int(window), "stride": int(stride), "blend": blend,
+                  "means": {k: (v / n if n else None) for k, v in sorted(sums.items())}, "grids": dict(sorted(grids.items()))}
+
+
+def add_windows_arguments(ap) -> None:
+    """``--windows`` and its companions of the predict and evaluate drivers (``check_windows_arguments`` holds their rules)."""
+    ap.add_argument("--windows", type=int, default=None, metavar="S",
+                    help="sliding-window inference at the training's crop size: every frame is cut into S x S windows (S a "
+                         "multiple of 8 in 32..2048; the training used 512), one stacked forward runs them, their "
+                         "low-resolution logits are blended over the overlaps and everything downstream is about that blend.  "
+                         "--batch keeps counting images (default 1, 2 in bf16)")
+    ap.add_argument("--windows_stride", type=int, default=None, metavar="T",
+                    help="with --windows: the distance between windows, a multiple of 8 with 8 <= T <= S <= 8 T (default: S / 2 "
+                         "rounded down to a multiple of 8)")
+    ap.add_argument("--windows_blend", choices=list(WINDOW_BLENDS), default=None,
+                    help="with --windows: tent (default) weighs a window cell by its distance from the window's inner borders, "
+                         "uniform weighs every covering window alike")
+    ap.add_argument("--windows_compare", action="store_true",
+                    help="with --windows: also run the plain forward of each frame and report how far the two differ")
+
+
 def open_run(root: str, tool: str, precision: str, device_index: int = None, batch: int = None, streams: int = None,
-             target_size: int = 1024, stack: int = 1) -> SimpleNamespace:
+             target_size: int = 1024, stack: int = 1, windows=None) -> SimpleNamespace:
     """The rank context of one folder run, and the state its later steps fill in.  An already initialised process group (gloo
     in the one-GPU rehearsals) is used as it is; ``wire_dev`` is where its collectives' tensors live (``collective_device``).
     ``stack``: the entries the forward runs per image (the V views of ``--tta`` or ``--jitter``; 1 otherwise): ``batch`` keeps counting
-    images, and its default shrinks so that the stack stays at a size the forward is already run at (4, or 8 in bf16)."""
+    images, and its default shrinks so that the stack stays at a size the forward is already run at (4, or 8 in bf16).
+    ``windows``: what ``check_windows_arguments`` returned (None = ``--windows`` is off): the forward runs the windows of
+    ``batch`` images, so the default batch shrinks likewise, and ``bring_up`` reserves for the window stack of the largest
+    frame (``K(target_size, target_size) x batch`` entries of ``E x E``; with ``--windows_compare`` for the plain frame too)."""
     import time
     from collections import defaultdict
     import torch
@@ -617,7 +733,8 @@ def open_run(root: str, tool: str, precision: str, device_index: int = None, bat
     torch.cuda.set_device(r.dev)
     r.wire_dev = collective_device(r.dist, r.dev)
     r.stack = max(1, int(stack))
-    if r.stack > 1:
+    r.windows = windows
+    if r.stack > 1 or windows is not None:
         r.batch = (2 if precision == "bf16" else 1) if batch is None else batch
     else:
         r.batch = (8 if precision == "bf16" else 2) if batch is None else batch
@@ -671,6 +788,8 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
         state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
     r.arch = resolve_arch(arch, state_dict, r.dist, r.dev)
     check_bn_stats_arch(bn_stats, r.arch)
+    if r.windows is not None:
+        check_windows_arch(r.arch)                   # --arch auto: the checkpoint's keys have named the network by now
     r.precision = resolve_arch_precision(r.arch, r.precision, precision_auto)   # EfficientNet: fp32
     model = MODELS[r.arch](r.precision).set_bn_statistics(bn_stats).to(r.dev)
     if r.rank == 0:
@@ -690,7 +809,12 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
     # side streams only: the default stream stays with whatever else the driver runs on the device
     r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
     for m in r.models:                               # the largest workspace once: a context's buffers only grow, and a folder of
-        m.reserve(r.batch * max(r.stack, int(stack)), r.target_size, r.target_size)   # rising heights would otherwise free and reallocate them shape after shape
+        if r.windows is not None:                    # --windows: the window stack of the largest frame
+            from .model import window_grid
+            ey, ex, ny, nx, _, _ = window_grid(r.target_size, r.target_size, r.windows.window, r.windows.stride)
+            m.reserve(r.batch * ny * nx, ey, ex)
+        if r.windows is None or r.windows.compare:
+            m.reserve(r.batch * max(r.stack, int(stack)), r.target_size, r.target_size)   # rising heights would otherwise free and reallocate them shape after shape
         if warm is not None:
             warm(m)
     torch.cuda.synchronize(r.dev)                    # weights uploaded / received before any side stream reads them
@@ -923,6 +1047,7 @@ def add_shared_arguments(ap) -> None:
                          "flips (all four); the low-resolution logits of the un-flipped views are averaged and everything "
                          "downstream is about that mean.  --batch keeps counting images (default 1, 2 in bf16)")
     add_jitter_arguments(ap)
+    add_windows_arguments(ap)
     ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
                     help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
                          "(with --std; default: the constants of the reference's model class)")

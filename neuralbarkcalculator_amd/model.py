@@ -240,6 +240,35 @@ def jitter_view_names(factors) -> List[str]:
     return names
 
 
+WINDOW_BLENDS = {"tent": _lib.BLEND_TENT, "uniform": _lib.BLEND_UNIFORM}
+
+
+def resolve_window_blend(blend) -> int:
+    """``NBC_BLEND_*`` of "tent" or "uniform"; ``ValueError`` otherwise."""
+    if not isinstance(blend, str) or blend not in WINDOW_BLENDS:
+        raise ValueError("blend must be one of %s, got %r" % (", ".join(sorted(WINDOW_BLENDS)), blend))
+    return WINDOW_BLENDS[blend]
+
+
+def window_grid(h: int, w: int, window: int = 512, stride: int = 256):
+    """The window grid of an ``h x w`` frame (nbc_window_grid, the one place it is computed; include/nbc.h): ``(E_y, E_x, n_y,
+    n_x, offsets_y, offsets_x)`` -- every window is ``E_y x E_x``, window ``k = r * n_x + c`` starts at ``(offsets_y[r],
+    offsets_x[c])``.  ``ValueError`` for a window or stride outside the rules, a side below 8 or more than 1024 windows.  No
+    device is touched."""
+    lib = _lib.load()
+    dims = (C.c_int * 4)()
+    oy, ox = (C.c_int * _lib.WINDOW_MAX_K)(), (C.c_int * _lib.WINDOW_MAX_K)()
+    try:
+        args = [int(v) for v in (h, w, window, stride)]
+    except (TypeError, ValueError):
+        raise ValueError("window_grid takes integers, got %r" % ((h, w, window, stride),))
+    if any(abs(v) >= 2 ** 31 for v in args):
+        raise ValueError("window_grid: an argument beyond 32 bits in %r" % (args,))
+    if lib.nbc_window_grid(args[0], args[1], args[2], args[3], dims, oy, ox) != 0:
+        raise ValueError(_lib.last_error())
+    return dims[0], dims[1], dims[2], dims[3], list(oy[:dims[2]]), list(ox[:dims[3]])
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 
@@ -611,6 +640,101 @@ class FCNResNet50:
         mean = self.views_mean(lowres_views, n)
         return self._views_tail(mean, lowres_views if return_views else None, n, h, w, exclude_nodes, labels_dtype, small_zones,
                                 logits_full, return_lowres, min_pixels)
+
+    # ---- the crop windows the training augmented over (include/nbc.h) ---------
+    def window_grid(self, h: int, w: int, window: int = 512, stride: int = 256):
+        """``model.window_grid``: ``(E_y, E_x, n_y, n_x, offsets_y, offsets_x)`` of an ``h x w`` frame."""
+        return window_grid(h, w, window, stride)
+
+    def _check_windows_served(self):
+        if topology.is_efficientnet(self.ARCH):
+            raise ValueError("the crop windows are refused for %s: its output stride is 32 and its fixed asymmetric pads need a "
+                             "window grid of their own (left out, DESIGN.md 3.18)" % self.ARCH)
+        if self.bn_statistics in PER_IMAGE_MODES:
+            raise ValueError("the crop windows are refused under bn_statistics %r: statistics per window are not the shipped "
+                             "tool's per-frame statistics" % self.bn_statistics)
+
+    def window_views(self, x: torch.Tensor, window: int = 512, stride: int = 256) -> torch.Tensor:
+        """The windows of a batch on the device (nbc_window_views): ``x`` as the model takes it (f32 ``[N,3,H,W]`` or uint8
+        ``[N,H,W,3]``) -> the stack ``[K*N, ...]`` of ``E_y x E_x`` windows in the same layout, window-major (entry ``k * N + i``
+        is window k of image i), rows and columns beyond the frame filled by reflection.  Runs on the current stream."""
+        self._require_ctx()
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 4 or x.numel() == 0 or not (
+                (x.dtype == torch.float32 and x.shape[1] == 3) or (x.dtype == torch.uint8 and x.shape[3] == 3)):
+            raise ValueError("x must be a non-empty float32 [N,3,H,W] or uint8 [N,H,W,3] tensor on %s" % (self.device,))
+        x = x.contiguous()
+        f32 = x.dtype == torch.float32
+        n, h, w = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) if f32 else (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
+        ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
+        if ny * nx * n > 65535:
+            raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (ny * nx, n))
+        out = torch.empty((ny * nx * n,) + ((3, ey, ex) if f32 else (ey, ex, 3)), dtype=x.dtype, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_window_views(x.data_ptr(), _lib.IN_F32_NCHW if f32 else _lib.IN_U8_NHWC, n, h, w, int(window),
+                                                  int(stride), out.data_ptr(), cur.cuda_stream), "nbc_window_views")
+        return out
+
+    def window_merge(self, lowres_windows: torch.Tensor, n: int, h: int, w: int, window: int = 512, stride: int = 256,
+                     blend: str = "tent") -> torch.Tensor:
+        """The merged low-resolution logits of a stacked forward (nbc_window_merge): ``lowres_windows`` f32
+        ``[K*N,3,E_y/8,E_x/8]`` (or ``[K,N,...]``) of the windows of ``n`` frames of ``h x w`` pixels -> ``m`` f32
+        ``[N,3,ceil(h/8),ceil(w/8)]``, per cell the weighted mean of the windows that cover it (``blend``: "tent" or "uniform")
+        in ascending window order; a cell one window covers keeps that window's bits."""
+        self._require_ctx()
+        b = resolve_window_blend(blend)
+        n, h, w = int(n), int(h), int(w)
+        ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
+        k = ny * nx
+        if not isinstance(lowres_windows, torch.Tensor) or lowres_windows.device != self.device \
+                or lowres_windows.dtype != torch.float32 or lowres_windows.dim() not in (4, 5) or n < 1 \
+                or tuple(lowres_windows.shape[-3:]) != (NUM_CLASSES, ey // 8, ex // 8) \
+                or int(np.prod(lowres_windows.shape[:-3])) != k * n:
+            raise ValueError("lowres_windows must be a float32 [%d*%d,3,%d,%d] tensor on %s" % (k, n, ey // 8, ex // 8, self.device))
+        if k * n > 65535:
+            raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (k, n))
+        lowres_windows = lowres_windows.contiguous()
+        merged = torch.empty((n, NUM_CLASSES, (h + 7) // 8, (w + 7) // 8), dtype=torch.float32, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_window_merge(lowres_windows.data_ptr(), n, h, w, int(window), int(stride), b,
+                                                  merged.data_ptr(), cur.cuda_stream), "nbc_window_merge")
+        return merged
+
+    def predict_labels_windows(self, x: torch.Tensor, window: int = 512, stride: int = 256, blend: str = "tent",
+                               exclude_nodes: bool = False, labels_dtype: torch.dtype = torch.int64, small_zones: bool = False,
+                               logits_full: Optional[torch.Tensor] = None, return_lowres: bool = False, min_pixels: int = 150):
+        """``predict_labels`` on sliding windows of the training's crop size, blended over their overlaps.  A
+        composition of calls and nothing more: ``window_views``, one forward of the K*N stack at ``E_y x E_x``,
+        ``window_merge``, then today's tail on the merged low-resolution logits ``m``, as ``predict_labels_tta`` runs it.  A frame
+        whose sides are multiples of 8 and no longer than ``window`` gives ``predict_labels``' own bits.
+
+        Returns what ``predict_labels`` returns, for ``m`` (``return_lowres`` appends ``m`` itself).  Refused (``ValueError``):
+        the EfficientNet networks and per-image BatchNorm statistics.  Afterwards no forward counts as the last one:
+        ``dropout_draws`` raises until a plain forward has run."""
+        self._check_windows_served()
+        resolve_window_blend(blend)
+        n, h, w = self._check_input(x)
+        ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
+        k = ny * nx
+        if labels_dtype not in (torch.int64, torch.uint8):
+            raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
+        if int(min_pixels) < 0:
+            raise ValueError("min_pixels must not be negative")
+        if k * n > 65535:
+            raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (k, n))
+        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
+                                        or not logits_full.is_contiguous()
+                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
+            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
+                                                                                                    self.device))
+        stack = self.window_views(x, window, stride)
+        lowres_windows = torch.empty((k * n, NUM_CLASSES, ey // 8, ex // 8), dtype=torch.float32, device=self.device)
+        try:
+            self._forward(stack, k * n, ey, ex, lowres=lowres_windows)
+        finally:
+            self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
+        merged = self.window_merge(lowres_windows, n, h, w, window, stride, blend)
+        return self._views_tail(merged, None, n, h, w, exclude_nodes, labels_dtype, small_zones, logits_full, return_lowres,
+                                min_pixels)
 
     def lowres_logits(self, x: torch.Tensor) -> torch.Tensor:
         """Output of ``classifier.4`` (models.py:121) before the upsample: f32 ``[N,3,h,w]``."""

@@ -376,6 +376,29 @@ def _write_views_report(results_dir: str, stem: str, items, allrows, allt, nv: i
     return summary
 
 
+def write_windows_report(results_dir: str, items, allrows, allw, windows, precision: str) -> dict:
+    """``windows_stats.csv`` (tab separated) and ``windows_summary.json`` from the gathered rows: ``allrows`` as
+    ``final_stats.csv`` is written from (the merged labels' counts), ``allw`` the ``(global_idx, merged counts 3, the plain
+    forward's counts 3, changed pixels)`` rows of ``--windows``; ``windows``: what ``folder_run.check_windows_arguments``
+    returned.  Returns the summary."""
+    import json
+    from .model import window_grid
+    by_idx = {int(g[0]): g[1:] for g in allw}
+    images = []
+    for g in allrows:
+        t, h, w = by_idx[int(g[0])], int(g[1]), int(g[2])
+        images.append((items[int(g[0])]["name"], items[int(g[0])]["wood"], h, w, window_grid(h, w, windows.window, windows.stride)[:4],
+                       t[:3], t[3:6] if windows.compare else None, int(t[6]) if windows.compare else None))
+    table, summary = folder_run.windows_report(images, windows.window, windows.stride, windows.blend, windows.compare)
+    with open(os.path.join(results_dir, "windows_stats.csv"), "w") as f:
+        csv.writer(f, delimiter="\t").writerows(table)
+    summary = dict({"precision": precision}, **summary)
+    with open(os.path.join(results_dir, "windows_summary.json"), "w") as f:
+        json.dump(summary, f, indent=2, sort_keys=True)
+        f.write("\n")
+    return summary
+
+
 def write_zones_report(results_dir: str, items, allrows, allz, cap: int, host_fallbacks: int) -> dict:
     """``zones.csv``, ``zones_summary.csv`` (tab separated, like ``final_stats.csv``) and ``zones_summary.json`` from the
     gathered rows: ``allrows`` as ``final_stats.csv`` is written from (one per image: its size), ``allz`` the
@@ -476,7 +499,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    normalization=None, dropout_draws: int = 0, dropout_p: float = 0.1, dropout_seed: int = 0,
                    dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None,
                    tta="none", tta_votes: bool = False, confidence: bool = False, confidence_threshold: float = None,
-                   jitter=None, jitter_views=None, jitter_votes: bool = False) -> dict:
+                   jitter=None, jitter_views=None, jitter_votes: bool = False, windows: int = None, windows_stride: int = None,
+                   windows_blend: str = None, windows_compare: bool = False) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -537,6 +561,13 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     (DESIGN.md 3.17).  ``batch`` keeps counting images (default 1, 2 in bf16).  Rank 0 writes ``results/jitter_stats.csv`` and
     ``results/jitter_summary.json`` (``folder_run.jitter_report``: ``tta_stats.csv``'s columns under the views' names).
     ``jitter_votes`` (with a view set only): also ``results/jitter_support/<wood>/<name>``, the support byte of the views' vote.
+    ``windows`` = S (with ``windows_stride``, default S / 2 rounded down to a multiple of 8, and ``windows_blend`` "tent" or
+    "uniform"; not with ``tta``, ``jitter``, ``dropout_draws`` or per-image ``bn_stats``; ResNet-50 networks only):
+    ``FCNResNet50.predict_labels_windows`` stands where ``predict_labels`` does, so the label PNGs, ``final_stats.csv`` and
+    ``zones`` are those of the blended S x S windows.  ``batch`` keeps counting images (default 1, 2 in bf16).
+    Rank 0 writes ``results/windows_stats.csv`` and ``results/windows_summary.json`` (``folder_run.windows_report``).
+    ``windows_compare``: the plain forward of each frame runs as well; its counts and the pixels on which the two final label
+    maps differ (the off-diagonal of ``FCNResNet50.confusion``) ride back and fill the report's comparison columns.
     Returns timing / count statistics of this rank."""
     import time
     import torch
@@ -555,6 +586,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     TS = bool(tta_votes) or bool(jitter_votes)
     VIEWS = bool(T) or J is not None                 # the forward runs a stack of views: the flip views or the colour views
     SUPPORT = "jitter_support" if J is not None else "tta_support"
+    WN = folder_run.check_windows_arguments(windows, windows_stride, windows_blend, windows_compare, tta, jitter, jitter_views, D,
+                                            bn_stats=bn_stats, arch=arch)   # the crop windows, None = off
     from . import calibration as cal
     C = bool(confidence)
     check_confidence_arguments(C, confidence_threshold, D)
@@ -566,7 +599,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         folder_run.check_dropout_arguments(D, dropout_p, dropout_seed, dropout_compare, arch)
         if dropout_compare is not None:
             old_stats = folder_run.read_shipped_stats(dropout_compare)
-    r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size, stack=max(NV, 1))
+    r = folder_run.open_run(root, "predict", precision, device_index, batch, streams, target_size, stack=max(NV, 1), windows=WN)
     dev, batch, prof, clock = r.dev, r.batch, r.prof, time.perf_counter
     pre_model = FCNResNet50(precision).to(dev)      # its own context: the pool's device resizes never touch the predictor's
 
@@ -599,6 +632,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     trows = np.zeros((len(mine), TROW), dtype=np.int64)          # (global_idx, merged counts, V x 3 view counts, 10 vote statistics)
     CROW = 2 + cal.wire_width()
     crows = np.zeros((len(mine), CROW), dtype=np.int64)          # (global_idx, pixels below the threshold, calibration.wire_rows)
+    WROW = 1 + 3 + 3 + 1
+    wrows = np.zeros((len(mine), WROW), dtype=np.int64)          # (global_idx, merged counts, the plain forward's counts, changed pixels)
     cpool = np.zeros(cal.WORDS, dtype=np.uint64)                 # this rank's pooled census (--confidence)
     zrows = {}                                       # k -> the image's zone rows int64 [zones, 10] (--zones)
     zfallbacks = []                                  # the k whose rows came from the host: more zones than ZCAP
@@ -629,7 +664,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
 
     label_paths = []                                 # label PNGs this rank has written (removed again if the run turns out invalid)
 
-    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None, views=None, conf=None):
+    def finish(k, lab, c1, c2, draws=None, votes=None, zone=None, views=None, conf=None, win=None):
         """Pool: label PNG (models.py:349-356) + the image's row (+ the vote mask and support PNGs and the votes' row; + the
         zone rows: ``zone`` = (the device's rows, or None when the image has more zones than the cap: the host computes them);
         + the confidence PNG: ``conf`` = the plane)."""
@@ -655,6 +690,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                 spath = os.path.join(root, "results", SUPPORT, d["wood"], d["name"])
                 label_paths.append(spath)
                 write_png(spath, sup, lvl_lab)
+        if win is not None:                          # --windows: (merged counts, the plain forward's counts, changed pixels)
+            wrows[k, 0], wrows[k, 1:4], wrows[k, 4:7], wrows[k, 7] = mine[k], win[0], win[1], win[2]
         if conf is not None:
             cpath = os.path.join(root, "results", "confidence", d["wood"], d["name"])
             label_paths.append(cpath)
@@ -684,6 +721,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     tring = [(torch.empty((NV, batch, 3), dtype=torch.int64).pin_memory(),
               torch.empty((batch, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
               torch.empty(full if TS else 0, dtype=torch.uint8).pin_memory()) for _ in range(r.depth)] if VIEWS else None
+    # --windows_compare: per slot the plain forward's counts and the confusion of the two final label maps per image
+    wring = [(torch.empty((batch, 3), dtype=torch.int64).pin_memory(), torch.empty((batch, 3, 3), dtype=torch.int64).pin_memory())
+             for _ in range(r.depth)] if WN is not None and WN.compare else None
     # --confidence: per stream the full-resolution logits; per slot the confidence planes and the census rows
     logits_buf = [torch.empty(3 * full, dtype=torch.float32, device=dev) for _ in range(r.n_streams)] if C else None
     cring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, cal.WORDS), dtype=torch.int64).pin_memory())
@@ -696,7 +736,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:   # an oversized stale processed frame (run_loop)
             ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
         if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
-            mdl.autotune(mdl.tta_views(x, T) if T else (mdl.jitter_views(x, J) if J is not None else x))   # once per distinct full-batch shape and model object
+            mdl.autotune(mdl.tta_views(x, T) if T else (mdl.jitter_views(x, J) if J is not None else
+                                                          (mdl.window_views(x, WN.window, WN.stride) if WN is not None else x)))   # once per distinct full-batch shape and model object
             tuned.add((sid, (n, h, w)))
         lg = None
         if C:                                        # the forward writes its full-resolution logits as well
@@ -715,6 +756,16 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             tring[slot][1][:n].copy_(tstats, non_blocking=True)
             if TS:
                 tring[slot][2][:need].copy_(sup.reshape(-1), non_blocking=True)
+        elif WN is not None:                         # the same tail on the blend of the windows
+            labels, counts = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, exclude_nodes=exclude_nodes,
+                                                        labels_dtype=torch.uint8, small_zones=small_zones,
+                                                        **(dict(logits_full=lg) if C else {}))
+            if WN.compare:                           # the plain forward beside it: its counts and where its labels differ
+                if wring[slot][0].shape[0] < n:
+                    wring[slot] = (torch.empty((n, 3), dtype=torch.int64).pin_memory(), torch.empty((n, 3, 3), dtype=torch.int64).pin_memory())
+                plabels, pcounts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8, small_zones=small_zones)
+                wring[slot][0][:n].copy_(pcounts, non_blocking=True)
+                wring[slot][1][:n].copy_(mdl.confusion(labels, plabels * 127), non_blocking=True)   # grey 0 / 127 / 254: classes 0 / 1 / 2
         else:
             labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
                                                 small_zones=small_zones,   # models.py:269-276 on the device
@@ -770,6 +821,11 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             vc, tst = tring[slot][0][:, :n].numpy().copy(), tring[slot][1][:n].numpy().copy()
             sups = tring[slot][2][: n * h * w].numpy().reshape(n, h, w).copy() if TS else [None] * n
             views = [(cnts[j], vc[:, j], tst[j], sups[j]) for j in range(n)]
+        wins = [None] * n
+        if WN is not None:
+            pc = wring[slot][0][:n].numpy().copy() if WN.compare else np.zeros((n, 3), dtype=np.int64)
+            cf = wring[slot][1][:n].numpy().copy() if WN.compare else np.zeros((n, 3, 3), dtype=np.int64)
+            wins = [(cnts[j], pc[j], int(cf[j].sum() - np.trace(cf[j]))) for j in range(n)]
         confs = [None] * n
         if C:
             confs = cring[slot][0][: n * h * w].numpy().reshape(n, h, w).copy()
@@ -779,7 +835,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             for j, k in enumerate(part):
                 crows[k, 0], crows[k, 1], crows[k, 2:] = mine[k], cal.below_threshold(census[j], CT), wire[j]
         return [pool.submit(finish, k, labs[j], int(cnts[j, 1]), int(cnts[j, 2]), dc[:, j] if D else None, votes[j], zone[j], views[j],
-                            confs[j]) for j, k in enumerate(part)]
+                            confs[j], wins[j]) for j, k in enumerate(part)]
 
     def remove_labels():                             # this rank's label PNGs of the invalid run: a crash before the rerun
         for path in label_paths:                     # must not leave them behind (the processed/ images do not depend on
@@ -810,6 +866,10 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             write_tta_report(os.path.join(root, "results"), items, allrows, allt, T, r.precision, bn_stats)
         if r.rank == 0 and J is not None:
             write_jitter_report(os.path.join(root, "results"), items, allrows, allt, J, r.precision, bn_stats)
+    if WN is not None:
+        allw = folder_run.gather(r, wrows, WROW)             # one more all_gather, as the views' rows take
+        if r.rank == 0:
+            write_windows_report(os.path.join(root, "results"), items, allrows, allw, WN, r.precision)
     if C:                                            # a fixed-width row per image and one pooled census per rank
         allc = folder_run.gather(r, crows, CROW)
         census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cpool.view(np.int64)])[None], r.world, r.dist, r.wire_dev,
@@ -863,6 +923,9 @@ def main(argv=None):
         folder_run.check_tta_arguments(args.tta, args.tta_votes, args.dropout_draws, args.only_preprocess)
         folder_run.check_jitter_arguments(args.jitter, args.jitter_views, args.jitter_votes, args.tta, args.dropout_draws,
                                           args.only_preprocess)
+        folder_run.check_windows_arguments(args.windows, args.windows_stride, args.windows_blend, args.windows_compare, args.tta,
+                                           args.jitter, args.jitter_views, args.dropout_draws, args.only_preprocess, args.bn_stats,
+                                           args.arch)
         folder_run.check_dropout_arguments(args.dropout_draws, args.dropout_p, args.dropout_seed, args.dropout_compare, args.arch,
                                            args.only_preprocess, args.dropout_votes)
         if args.dropout_compare is not None:
@@ -892,6 +955,9 @@ def main(argv=None):
         kw.update(tta=args.tta, tta_votes=args.tta_votes)
     if args.jitter is not None or args.jitter_views is not None:
         kw.update(jitter=args.jitter, jitter_views=args.jitter_views, jitter_votes=args.jitter_votes)
+    if args.windows is not None:
+        kw.update(windows=args.windows, windows_stride=args.windows_stride, windows_blend=args.windows_blend,
+                  windows_compare=args.windows_compare)
     if args.confidence:
         kw.update(confidence=True, confidence_threshold=args.confidence_threshold)
     if args.normalization is not None:
