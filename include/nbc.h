@@ -717,8 +717,8 @@ int nbc_views_mean(const float* lowres_views_dev, int N, int V, int h, int w, fl
  * The tail upsamples the h x w grid to H x W as interpolate(align_corners=False) does for the plain forward: where H is no
  * multiple of 8 that is the stretch of less than one cell the plain path has always made.
  * Left out: the EfficientNet networks (output stride 32 and fixed asymmetric pads: a grid of their own), per-image BatchNorm
- * statistics (a window's statistics are not the frame's), products with the flip or colour views, per-window votes (the number of
- * windows over a pixel varies) and the training's exact 1024 x 1024 pad_resize frame. */
+ * statistics (a window's statistics are not the frame's), products with the flip or colour views and per-window votes (the
+ * number of windows over a pixel varies).  The training's 1024 x 1024 pad_resize frame is nbc_training_frame, below. */
 enum { NBC_WINDOW_CELL = 8, NBC_WINDOW_MAX_K = 1024 };
 enum { NBC_BLEND_TENT = 0, NBC_BLEND_UNIFORM = 1 };
 /* The window grid of an H x W frame: the one place Python and the kernels take it from.  Host only, no HIP call.
@@ -744,6 +744,51 @@ int nbc_window_views(const void* x_dev, int x_dtype, int N, int H, int W, int S,
  * aligned, merged_dev overlapping the input. */
 int nbc_window_merge(const float* lowres_windows_dev, int N, int H, int W, int S, int T, int blend, float* merged_dev,
                      void* hip_stream);
+
+/* ---- the training run's own frame --------------------------------------------------------------
+ * The reference's test_dataset -- the one val_miou, ReduceLROnPlateau, EarlyStopping, the choice of checkpoint and the test_*
+ * figures of exp.test read (__main__.py:209-228) -- passes every sample and its dual through pad_resize(img, 1024, 1024)
+ * (utils.py:242-247), and RandomCrop(512) cuts the training's crops from the same frame (__main__.py:158-165).  These calls make
+ * that frame on the device (the host restatement is neuralbarkcalculator_amd/training_frame.py).  Per axis, with L
+ * the source length and Lt the frame's:
+ *   pad       p = ceil((Lt - L) / 2) on both sides, Lp = L + 2 p, which is Lt or Lt + 1.  Padded index i reads source index
+ *             r(i - p) with r(j) = -j for j < 0, r(j) = 2 (L - 1) - j for j >= L, else j: torchvision's pad(padding_mode=
+ *             'reflect'), numpy.pad(mode="reflect").  L > Lt and p > L - 1 are refused: one reflection must reach.
+ *   Lp == Lt  the axis is a pure index map.
+ *   Lp == Lt + 1  PIL's 8-bit ImagingResample with the bilinear filter (what torchvision's resize ran): output o reads the
+ *             padded indices first[o] .. first[o] + NBC_FRAME_TAPS - 1 with the integer coefficients k[o][.] in 22-bit fixed
+ *             point (an unused tap is 0 and reads nothing) and is clip8((2^21 + sum v k) >> 22), >> arithmetic, clip8 to 0..255.
+ *   order     the horizontal pass first, rounded to bytes, then the vertical pass on those bytes: PIL's order and its intermediate
+ *             image.  Neither the padded nor the intermediate image is written: an output byte recomputes its at most 3 x 3 reads.
+ * Left out: predict on the frame (a resampled axis has no integer map back to the scan's own rows), the batch-pooled Lovasz loss
+ * of exp.test (it needs all images of a group on one device at once; the engine shards by image), remove_small_zones on a
+ * [B,H,W] batch as the reference's code runs it (connectivity=2 on a 3-D array links zones of neighbouring images through the
+ * batch axis; here zones are per image), frames that shrink an axis. */
+enum { NBC_FRAME_TAPS = 3 };
+/* PIL's table of the bilinear filter for in_size -> out_size (Resample.c: precompute_coeffs, then normalize_coeffs_8bpc), in
+ * doubles in PIL's order, no contraction: support = scale = in / out, center = (o + 0.5) scale, xmin = (int)(center - support +
+ * 0.5) clamped at 0, xmax = (int)(center + support + 0.5) clamped at in, weights 1 - |(x + xmin - center + 0.5) (1 / scale)| divided
+ * by their sequential sum, then (int)(0.5 + w 2^22).  Host only, no HIP call.
+ * first  int32 [out_size]; coeff  int32 [out_size][NBC_FRAME_TAPS]
+ * NBC_ERR_INVALID: a null pointer, anything but in_size == out_size + 1 >= 2 (all that pad_resize can produce). */
+int nbc_bilinear_taps(int in_size, int out_size, int32_t* first, int32_t* coeff);
+/* pad_resize of a batch of equal-shape uint8 images in one launch.  No context: csrc/training_frame.hip.
+ * x_dev         channels = 3: NBC_IN_U8_NHWC frames [N][H][W][3]; channels = 1: grey duals [N][H][W]; at any alignment
+ * Ht, Wt        the frame's size
+ * row_taps_dev  the table of the vertical pass, needed (and read) only where H + 2 p_y == Ht + 1: int32 [Ht][4] on the device,
+ *               entry o = { first[o], coeff[o][0], coeff[o][1], coeff[o][2] } of nbc_bilinear_taps(Ht + 1, Ht); 4-byte aligned.
+ *               The caller uploads it: the library makes no hidden copy and does not synchronise.  An index a foreign table
+ *               names beyond the padded axis is clamped into it.
+ * col_taps_dev  likewise for the horizontal pass, [Wt][4], where W + 2 p_x == Wt + 1
+ * out_dev       uint8 [N][Ht][Wt][channels] at any alignment; must not overlap x.  A lane makes four consecutive bytes and stores
+ *               the aligned dword they are; the bytes before the first and after the last aligned dword go singly.
+ * About channels H W bytes are read and channels Ht Wt written per image.  An image's bytes are the same alone, in any batch and
+ * on any stream.  Runs on hip_stream (the caller's current device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null x_dev or out_dev, channels not 1 or 3, N < 1 or N > 65535, a length < 1, H > Ht or
+ * W > Wt, p > L - 1 on either axis, Ht * Wt >= 2^31, a missing table for a resampled axis, a table that is not 4-byte aligned,
+ * out_dev overlapping x_dev. */
+int nbc_training_frame(const void* x_dev, int channels, int N, int H, int W, int Ht, int Wt, const int32_t* row_taps_dev,
+                       const int32_t* col_taps_dev, void* out_dev, void* hip_stream);
 
 /* ---- the zones of a label map ------------------------------------------------------------------
  * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and

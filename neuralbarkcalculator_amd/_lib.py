@@ -33,6 +33,7 @@ TTA_IDENTITY, TTA_HFLIP, TTA_VFLIP, TTA_HVFLIP, TTA_FLIPS = 1, 2, 4, 8, 15   # N
 JITTER_MAX_VIEWS = 16                               # NBC_JITTER_MAX_VIEWS
 WINDOW_CELL, WINDOW_MAX_K = 8, 1024                 # NBC_WINDOW_CELL, NBC_WINDOW_MAX_K
 BLEND_TENT, BLEND_UNIFORM = 0, 1                    # NBC_BLEND_*
+FRAME_TAPS = 3                                      # NBC_FRAME_TAPS
 
 
 class NbcTensor(C.Structure):
@@ -142,6 +143,9 @@ SIGNATURES = {
     "nbc_window_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nbc_window_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "nbc_window_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nbc_bilinear_taps": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "nbc_training_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "nbc_zones_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_label_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

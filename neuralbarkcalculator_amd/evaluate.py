@@ -102,6 +102,18 @@ summary notes ``"windows": {window, stride, blend}``.  ``--windows_compare`` als
 confusion of its final labels rides back with the batch and rank 0 writes ``results/windows_evaluation.csv``
 (``jitter_evaluation`` on the rows ``identity`` -- the frame -- and ``windows``, pooled over the folder).
 
+``--frame training`` (with ``--frame_size T``, ``--pool B``) scores the checkpoint on the frames it was selected on
+(DESIGN.md 3.19): ``val_miou`` -- what ``ReduceLROnPlateau``, ``EarlyStopping`` and the choice of checkpoint read -- and the
+``test_*`` figures of ``exp.test`` come from ``test_dataset`` (__main__.py:209-228), where every sample and its dual go through
+``pad_resize(img, 1024, 1024)`` (utils.py:242-247).  At the top of each batch the scans and their duals are replaced by that
+frame (``FCNResNet50.training_frame``, csrc/training_frame.hip); everything above then runs on the frame, in the training's own
+order frame -> jitter / flips / windows (__main__.py:158-165).  A scan whose pad one reflection does not reach is skipped
+(``too_small``).  The summary gains ``"frame"``: the images resampled per axis and the batch-pooled ``miou`` and
+``pixelwise_f1`` over consecutive groups of B evaluated images in list order (``metrics.pooled_over_groups``; default 8, the
+reference's validation batch), the figures a training log holds.  ``--subset PATH`` (one ``wood_type/name`` per line) evaluates
+only the named samples, in the file's order: the pooled figures mean ``val_miou`` only on the split they were logged for.
+Without the flags nothing changes.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -128,6 +140,10 @@ LOSS_ROW_WIDTH = 4                               # --loss: (global_idx, 3 float6
 CE_ROW_WIDTH = 10                                # --ce: (global_idx, 9 float64 cell sums viewed as int64)
 STATUS_OK, STATUS_NO_DUAL, STATUS_SHAPE_MISMATCH, STATUS_TOO_LARGE = 0, 1, 2, 3
 SKIP_REASONS = {STATUS_NO_DUAL: "no_dual", STATUS_SHAPE_MISMATCH: "shape_mismatch", STATUS_TOO_LARGE: "too_large"}
+STATUS_TOO_SMALL = 4                             # --frame training: a pad that one reflection of the scan does not reach
+TOO_SMALL = "too_small"                          # its reason: a key of summary["skipped"] only with the flag
+FRAMES = ("scan", "training")                    # --frame
+DEFAULT_POOL, MAX_POOL = 8, 64                   # --pool: the reference's valid_loader batches its test_dataset by 8
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
 SUMMARY_JSON = os.path.join("results", "evaluation_summary.json")
 MATCHES_CSV, ZONE_EVALUATION_CSV = "zone_matches.csv", "zone_evaluation.csv"     # --zones, under results/
@@ -288,6 +304,78 @@ def check_calibration_arguments(calibration: bool, ece_bins=None) -> None:
         cal.check_ece_bins(ece_bins)
 
 
+def check_frame_arguments(frame="scan", frame_size=None, pool=None, target_size: int = 1024):
+    """``ValueError`` for what ``--frame`` and its options refuse before any device is touched: an unknown frame,
+    ``--frame_size`` or ``--pool`` without ``--frame training``, a frame size outside ``8 .. target_size``, a pool outside
+    ``1 .. MAX_POOL``.  Returns ``(T, B)``: the side of the training frame and the images per pooled group, or ``(None, None)``
+    for ``frame="scan"``, today's behaviour."""
+    if frame is None:
+        frame = "scan"
+    if frame not in FRAMES:
+        raise ValueError("--frame must be one of %s, got %r" % (", ".join(FRAMES), frame))
+    if frame == "scan":
+        given = [n for n, v in (("--frame_size", frame_size), ("--pool", pool)) if v is not None]
+        if given:
+            raise ValueError("%s needs --frame training" % ", ".join(given))
+        return None, None
+    size = target_size if frame_size is None else frame_size
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 8 <= int(size) <= int(target_size):
+        raise ValueError("--frame_size must be an integer in 8..%d, got %r" % (target_size, size))
+    b = DEFAULT_POOL if pool is None else pool
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 1 <= int(b) <= MAX_POOL:
+        raise ValueError("--pool must be an integer in 1..%d, got %r" % (MAX_POOL, b))
+    return int(size), int(b)
+
+
+def frame_status(h: int, w: int, size: int) -> int:
+    """What ``--frame training`` says of a scan of ``h x w`` pixels that could otherwise be evaluated: STATUS_TOO_LARGE where a
+    side exceeds the frame's, STATUS_TOO_SMALL where nbc_training_frame would refuse an axis (its pad needs more than one
+    reflection), else STATUS_OK."""
+    from .training_frame import frame_geometry
+    if max(h, w) > size:
+        return STATUS_TOO_LARGE
+    try:
+        frame_geometry(h, size), frame_geometry(w, size)
+    except ValueError:
+        return STATUS_TOO_SMALL
+    return STATUS_OK
+
+
+def read_subset(path: str) -> List[str]:
+    """The lines of a ``--subset`` file: one ``wood_type/name`` per line, blank lines dropped."""
+    with open(path) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def apply_subset(items: List[dict], lines) -> List[dict]:
+    """The listed samples that ``lines`` (``wood_type/name`` each) name, in the order of the lines: the file's order becomes the
+    list order, and so the grouping of ``--pool``.  ``ValueError`` quoting the first line that names no listed sample, or one
+    named twice."""
+    by_key = {d["wood"] + "/" + d["name"]: d for d in items}
+    out, seen = [], set()
+    for line in lines:
+        if line not in by_key:
+            raise ValueError("--subset: %r names no listed sample" % line)
+        if line in seen:
+            raise ValueError("--subset: %r is named twice" % line)
+        seen.add(line)
+        out.append(by_key[line])
+    return out
+
+
+def frame_report(allrows, size: int, pool: int) -> dict:
+    """The ``"frame"`` entry of the summary from the gathered rows: the evaluated images whose padded height (width) came out
+    at ``size + 1``, so that the axis was resampled, and the batch-pooled figures of ``metrics.pooled_over_groups`` over the
+    evaluated images in list order."""
+    from .training_frame import frame_geometry
+    done = [g for g in allrows if int(g[3]) == STATUS_OK]
+    doc = {"kind": "training", "size": int(size),
+           "resampled_rows": sum(1 for g in done if frame_geometry(int(g[1]), size)[1] != size),
+           "resampled_cols": sum(1 for g in done if frame_geometry(int(g[2]), size)[1] != size)}
+    doc.update(metrics.pooled_over_groups([g[4:13] for g in done], [g[13:22] for g in done], pool))
+    return doc
+
+
 def write_calibration_report(results_dir: str, items, allrows, all_wire, pooled, ece_bins: int) -> dict:
     """``calibration_evaluation.csv`` and ``calibration_curves.csv`` (tab separated, like ``evaluation_stats.csv``) from the
     gathered ``(global_idx, calibration.wire_width(ece_bins) fields)`` rows ``all_wire`` and the folder's pooled census row, for
@@ -379,23 +467,26 @@ def report(items: List[dict], allrows: np.ndarray, precision: str, model_path: s
            bn_stats: str = "running", loss_rows: np.ndarray = None, normalization=None,
            normalization_source: str = "arguments", ce_rows: np.ndarray = None,
            class_weights=metrics.REFERENCE_CLASS_WEIGHTS,
-           class_weights_source: str = "reference") -> Tuple[List[List[str]], dict]:
+           class_weights_source: str = "reference", frame: bool = False) -> Tuple[List[List[str]], dict]:
     """CSV rows and summary from the gathered rank rows (rank 0); ``loss_rows``: the gathered ``LOSS_ROW_WIDTH`` rows of
     ``--loss`` (None without it); ``normalization``: the ``(mean, std)`` the run was given (None: the defaults, and no entry
     in the summary); ``ce_rows``: the gathered ``CE_ROW_WIDTH`` rows of ``--ce`` (None without it), weighted with
-    ``class_weights``."""
+    ``class_weights``; ``frame``: the run framed its scans (``--frame training``), so ``too_small`` is a reason to skip one."""
+    reasons = dict(SKIP_REASONS)
+    if frame:
+        reasons[STATUS_TOO_SMALL] = TOO_SMALL
     terms = ce_sums = None
     if loss_rows is not None:
         terms = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in loss_rows}
     if ce_rows is not None:
         ce_sums = {int(r[0]): np.ascontiguousarray(r[1:]).view(np.float64) for r in ce_rows}
     ce_cells_of = [[] for _ in range(9)]             # per cell: the sums of the evaluated images
-    rows, skipped = [], {r: [] for r in SKIP_REASONS.values()}
+    rows, skipped = [], {r: [] for r in reasons.values()}
     raw_total, clean_total = np.zeros((3, 3), np.int64), np.zeros((3, 3), np.int64)
     for r in allrows:
         d = items[int(r[0])]
         if int(r[3]) != STATUS_OK:
-            skipped[SKIP_REASONS[int(r[3])]].append(d["wood"] + "/" + d["name"])
+            skipped[reasons[int(r[3])]].append(d["wood"] + "/" + d["name"])
             continue
         raw, clean = r[4:13].reshape(3, 3), r[13:22].reshape(3, 3)
         raw_total += raw
@@ -433,7 +524,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     zones_cap: int = None, zone_pairs_cap: int = None, match_iou: float = None, contours: bool = False,
                     contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None,
                     jitter=None, jitter_views=None, windows: int = None, windows_stride: int = None, windows_blend: str = None,
-                    windows_compare: bool = False) -> dict:
+                    windows_compare: bool = False, frame: str = "scan", frame_size: int = None, pool: int = None,
+                    subset=None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -468,9 +560,21 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     confusion of its final labels (after ``remove_small_zones``) rides back; rank 0 writes ``results/windows_evaluation.csv``
     (``jitter_evaluation`` on the rows "identity" -- the frame -- and "windows", pooled over the folder) and the summary's entry
     gains ``"evaluation"``.
+    ``frame`` = "training" (with ``frame_size`` = T, default ``target_size``, 8 <= T <= ``target_size``): every scan and its dual
+    are replaced by the training run's own ``T x T`` frame, ``pad_resize`` of utils.py:242-247 (``FCNResNet50.training_frame``,
+    DESIGN.md 3.19), at the top of each batch; everything after that is the code above on the frame, in the training's own order
+    frame -> jitter / flips / windows (__main__.py:158-165).  The rows' ``H, W`` stay the scan's.  A scan whose pad one
+    reflection does not reach is skipped (``too_small``, a key of ``summary["skipped"]`` only here), one with a side beyond T
+    as ``too_large``.  The summary gains ``"frame": {"kind", "size", "resampled_rows", "resampled_cols", "pool", "miou",
+    "pixelwise_f1", "groups"}``: the batch-pooled figures of ``metrics.pooled_over_groups`` over consecutive groups of ``pool``
+    evaluated images in list order (default 8, 1..64), host arithmetic on rank 0 from the gathered rows.  ``frame="scan"``
+    (default) is the behaviour without it; ``frame_size`` and ``pool`` are refused then.
+    ``subset``: the path of a file with one ``wood_type/name`` per line, or such a list: only these samples are evaluated, in
+    that order (``apply_subset``).
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
+    FT, POOL = check_frame_arguments(frame, frame_size, pool, target_size)   # the training frame's side, None = off
     Z = bool(zones)
     check_zone_match_arguments(Z, zones_cap, zone_pairs_cap, match_iou)     # refusals first: nothing has touched a device yet
     ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
@@ -493,6 +597,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     WN = folder_run.check_windows_arguments(windows, windows_stride, windows_blend, windows_compare, tta, jitter, jitter_views,
                                             bn_stats=bn_stats, arch=arch)   # the crop windows, None = off
     WC = WN is not None and WN.compare
+    items = list_labelled(root)
+    if subset is not None:                           # a refusal like the others: nothing has touched a device yet
+        items = apply_subset(items, read_subset(subset) if isinstance(subset, str) else list(subset))
     r = folder_run.open_run(root, "evaluate", precision, device_index, batch, streams, target_size,
                             stack=max(1, NV, len(folder_run.tta_view_names(T))), windows=WN)
     dev, batch = r.dev, r.batch
@@ -514,11 +621,12 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if K:                                        # contour_distances' (9 bytes per pixel)
             plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
             m.contour_distances(plane, plane)
+        if FT:                                       # the coefficient table of a resampled axis, uploaded before the loop
+            m._frame_table(FT)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
                         normalization=normalization)
 
-    items = list_labelled(root)
     sizes = folder_run.shard(r, items, lambda d: image_hw(d["src"]))
     mine = r.mine
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
@@ -534,6 +642,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         gi = mine[k]
         h, w = sizes[gi]
         status = dual_status(items[gi], h, w, target_size)
+        if status == STATUS_OK and FT:
+            status = frame_status(h, w, FT)
         if status == STATUS_OK:
             frame, grey = _decode_rgb(items[gi]["src"]), decode_dual(items[gi]["dual"])
             if grey.shape == frame.shape[:2]:
@@ -582,7 +692,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         wrows[:, 0] = -1                                              # a skipped image has no row
 
     def launch(slot, sid, part, x, tgt):
-        (n, h, w), mdl = x.shape[:3], r.models[sid]
+        mdl = r.models[sid]
+        if FT:                                                        # the training's frame of the scan and of its dual
+            x, tgt = mdl.training_frame(x, (FT, FT)), mdl.training_frame(tgt, (FT, FT))
+        n, h, w = x.shape[:3]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
         if T:                                                         # the same call on the mean of the flip views
             labels, _ = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg)
@@ -633,18 +746,19 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     def consume(slot, part, n, h, w):
         conf = ring[slot][:, :n].numpy().reshape(2, n, 9)
         futures = []
+        fh, fw = (FT, FT) if FT else (h, w)          # the planes' shape: the frame's under --frame training, else the scan's
         if Z:
             zr, pr, nums, planes = (t.numpy() for t in zring[slot])
             for j, k in enumerate(part):
                 no, nt, npairs = (int(v) for v in nums[:, j])
                 if no > ZCAP or nt > ZCAP or npairs > PCAP:
                     zfallbacks.append(k)
-                    lab, grey = (planes[a * n * h * w:][j * h * w: (j + 1) * h * w].reshape(h, w).copy() for a in (0, 1))
+                    lab, grey = (planes[a * n * fh * fw:][j * fh * fw: (j + 1) * fh * fw].reshape(fh, fw).copy() for a in (0, 1))
                     futures.append(r.pool.submit(match_on_host, k, lab, grey))
                 else:
                     zres[k] = (zr[0, j, :no].copy(), zr[1, j, :nt].copy(), pr[j, :npairs].copy())
         if K:
-            width = ct.HEAD + ct.default_bins(h, w)
+            width = ct.HEAD + ct.default_bins(fh, fw)
             c_rows = cring[slot][0][: n * ct.SETS * width].numpy().reshape(n, ct.SETS, width)
             wire = ct.wire_rows(c_rows, cring[slot][1][:n].numpy(), TOL)
             chist[...] += ct.pooled_histogram(c_rows, CBINS)
@@ -670,8 +784,13 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         return futures
 
     def first_frame():                               # the calibration guard's: this rank's first image that fits
-        first = next((gi for gi in mine if max(sizes[gi]) <= target_size), None)
-        return None if first is None else _decode_rgb(items[first]["src"])
+        first = next((gi for gi in mine if max(sizes[gi]) <= target_size and (not FT or frame_status(*sizes[gi], FT) == STATUS_OK)), None)
+        if first is None:
+            return None
+        rgb = _decode_rgb(items[first]["src"])
+        if FT:                                       # framed like every batch
+            rgb = r.models[0].training_frame(torch.from_numpy(np.ascontiguousarray(rgb[None])).to(dev), (FT, FT))[0].cpu().numpy()
+        return rgb
 
     folder_run.run_loop(r, window, prepare, launch, consume, first_frame, calibrate, bytes_per_pixel=(3, 1))
     allrows = folder_run.gather(r, rows, ROW_WIDTH)
@@ -704,7 +823,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         csv_rows, summary = report(items, allrows, r.precision, model_path, bn_stats, loss_rows=all_loss,
                                    normalization=normalization, normalization_source=normalization_source,
                                    **(dict(ce_rows=all_ce, class_weights=class_weights,
-                                           class_weights_source=class_weights_source) if ce else {}))
+                                           class_weights_source=class_weights_source) if ce else {}),
+                                   **(dict(frame=True) if FT else {}))
         write_stats_csv(os.path.join(root, STATS_CSV), csv_rows, loss=loss, **(dict(ce=True) if ce else {}))
         if Z:
             summary["zones"] = write_zone_match_report(os.path.join(root, "results"), items, allrows, *all_zones, IOU, ZCAP, PCAP,
@@ -713,6 +833,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             summary["contours"] = write_contour_report(os.path.join(root, "results"), items, allrows, all_wire, all_hist, TOL)
         if CAL:
             summary["calibration"] = write_calibration_report(os.path.join(root, "results"), items, allrows, all_cal, all_census, EB)
+        if FT:
+            summary["frame"] = frame_report(allrows, FT, POOL)
         if T:
             summary["tta"] = {"views": folder_run.tta_view_names(T)}
         if NV:
@@ -781,6 +903,12 @@ def format_summary(summary: dict) -> str:
             "%s AP %s, AUROC %s, best F1 %s at p >= %s (argmax: %s)" % (
                 name, fmt(c[name]["average_precision"]), fmt(c[name]["auroc"]), fmt(c[name]["best_f1"]),
                 fmt(c[name]["best_f1_threshold"], "%.3f"), fmt(c[name]["f1_at_argmax"])) for name in ("Bark", "Node")))
+    if summary.get("frame"):
+        fr = summary["frame"]
+        fmt = lambda v: "-" if v is None else "%.3f" % v
+        lines.append("on the training's %d x %d frame (%d images resampled along rows, %d along columns); pooled over groups of "
+                     "%d: miou %s, pixelwise_f1 %s" % (fr["size"], fr["size"], fr["resampled_rows"], fr["resampled_cols"], fr["pool"],
+                                                       fmt(fr["miou"]), fmt(fr["pixelwise_f1"])))
     if summary.get("jitter"):
         for name, entry in summary["jitter"]["evaluation"].items():
             f, d = entry["figures"], entry["difference"]
@@ -844,6 +972,18 @@ def main(argv=None):
                          "F1 per class and threshold, the reliability table) and a \"calibration\" entry in the summary")
     ap.add_argument("--ece_bins", type=int, default=None, metavar="BINS",
                     help="with --calibration: the bins under ECE and MCE, a power of two in 1..256 (default 16)")
+    ap.add_argument("--frame", default="scan", metavar="{scan,training}",
+                    help="training: score every scan and its dual on the training run's own frame, pad_resize to T x T (reflection "
+                         "pad, PIL's bilinear resize where the padded length is T + 1), made on the device; everything else runs "
+                         "on that frame, and the summary gains the batch-pooled miou and pixelwise_f1 that the training log holds.  "
+                         "scan (default): each scan at its own shape")
+    ap.add_argument("--frame_size", type=int, default=None, metavar="T",
+                    help="with --frame training: the frame's side, 8 <= T <= 1024 (default 1024)")
+    ap.add_argument("--pool", type=int, default=None, metavar="B",
+                    help="with --frame training: the images per pooled group, in list order, 1..64 (default 8, the reference's "
+                         "validation batch)")
+    ap.add_argument("--subset", default=None, metavar="PATH",
+                    help="evaluate only the samples this file names, one wood_type/name per line, in the file's order")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
     raw = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(raw)
@@ -855,7 +995,10 @@ def main(argv=None):
         folder_run.check_jitter_arguments(args.jitter, args.jitter_views, tta=args.tta)
         folder_run.check_windows_arguments(args.windows, args.windows_stride, args.windows_blend, args.windows_compare, args.tta,
                                            args.jitter, args.jitter_views, bn_stats=args.bn_stats, arch=args.arch)
-    except ValueError as e:
+        check_frame_arguments(args.frame, args.frame_size, args.pool)
+        if args.subset is not None:
+            apply_subset(list_labelled(args.root_path), read_subset(args.subset))
+    except (OSError, ValueError) as e:
         ap.error(str(e))
     if args.exclude_nodes:
         raise SystemExit("evaluate: --exclude_nodes is not supported: IoU and F1 are defined on the three classes "
@@ -895,6 +1038,10 @@ def main(argv=None):
     if args.windows is not None:
         kw.update(windows=args.windows, windows_stride=args.windows_stride, windows_blend=args.windows_blend,
                   windows_compare=args.windows_compare)
+    if args.frame != "scan":
+        kw.update(frame=args.frame, frame_size=args.frame_size, pool=args.pool)
+    if args.subset is not None:
+        kw["subset"] = args.subset
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

@@ -226,3 +226,39 @@ def summarize_ce(rows: Sequence[Sequence[str]], first: int, sums_total, pixels_t
         pooled = {"cross_entropy": cross_entropy(total, p), "weighted_cross_entropy": weighted_cross_entropy(total, p, weights)}
     return {"class_weights": [float(v) for v in weights], "class_weights_source": weights_source, "mean_over_images": mean,
             "pooled": pooled, "sums": total.tolist(), "pixels": pixels.tolist()}
+
+
+def pooled_miou(confs_raw) -> float:
+    """``val_miou`` / ``test_miou`` of one batch (``iou(..., per_image=False)``, lovasz_losses.py:54-77): the mean over the three
+    classes of ``100 iou`` of the batch's *summed* raw-argmax confusions, an empty union counting as 100."""
+    total = np.asarray(confs_raw, dtype=np.int64).reshape(-1, 3, 3).sum(axis=0)
+    return float(iou(total).mean())
+
+
+def pooled_f1(confs_clean) -> float:
+    """``PixelWiseF1`` of one batch (utils.py:201-235): ``f1`` -- its absent-class rule of utils.py:219-229 included -- of the
+    batch's *summed* confusions after remove_small_zones, then the mean over the three classes."""
+    total = np.asarray(confs_clean, dtype=np.int64).reshape(-1, 3, 3).sum(axis=0)
+    return float(f1(total).mean())
+
+
+def pooled_over_groups(confs_raw, confs_clean, pool: int) -> dict:
+    """The batch-pooled figures of ``evaluate --frame training --pool B``: the images, in their order, form consecutive groups
+    of ``pool`` (the last may be shorter), as the reference's ``valid_loader`` batches its ``test_dataset`` (__main__.py:209-228);
+    each group gives ``pooled_miou`` and ``pooled_f1``, and the folder's figure is their mean weighted by group size, as the
+    trainer weights a step by its batch size.  Returns ``{"pool", "miou", "pixelwise_f1", "groups"}``; the figures are None when
+    there is no image."""
+    pool = int(pool)
+    if pool < 1:
+        raise ValueError("pool must be >= 1")
+    raw = np.asarray(confs_raw, dtype=np.int64).reshape(-1, 3, 3)
+    clean = np.asarray(confs_clean, dtype=np.int64).reshape(-1, 3, 3)
+    if len(raw) != len(clean):
+        raise ValueError("one raw and one clean confusion per image")
+    groups = []
+    for a in range(0, len(raw), pool):
+        groups.append({"images": int(len(raw[a:a + pool])), "miou": pooled_miou(raw[a:a + pool]),
+                       "pixelwise_f1": pooled_f1(clean[a:a + pool])})
+    n = len(raw)
+    mean = lambda key: (_fsum(g[key] * g["images"] for g in groups) / n) if n else None
+    return {"pool": pool, "miou": mean("miou"), "pixelwise_f1": mean("pixelwise_f1"), "groups": groups}

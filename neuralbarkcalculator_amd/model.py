@@ -269,6 +269,23 @@ def window_grid(h: int, w: int, window: int = 512, stride: int = 256):
     return dims[0], dims[1], dims[2], dims[3], list(oy[:dims[2]]), list(ox[:dims[3]])
 
 
+def bilinear_taps(n_in: int, n_out: int):
+    """PIL's 8-bit bilinear table for ``n_in == n_out + 1`` (nbc_bilinear_taps, include/nbc.h): ``(first int32 [n_out], coeff
+    int32 [n_out, 3])``.  ``ValueError`` for any other pair of sizes.  No device is touched."""
+    try:
+        n_in, n_out = int(n_in), int(n_out)
+    except (TypeError, ValueError):
+        raise ValueError("bilinear_taps takes integers, got %r" % ((n_in, n_out),))
+    if not (0 < n_out < 2 ** 30 and 0 < n_in < 2 ** 31):
+        raise ValueError("bilinear_taps: sizes out of range in %r" % ((n_in, n_out),))
+    first = np.zeros(n_out, dtype=np.int32)
+    coeff = np.zeros((n_out, _lib.FRAME_TAPS), dtype=np.int32)
+    if _lib.load().nbc_bilinear_taps(n_in, n_out, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     coeff.ctypes.data_as(C.POINTER(C.c_int32))) != 0:
+        raise ValueError(_lib.last_error())
+    return first, coeff
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 
@@ -312,6 +329,7 @@ class FCNResNet50:
         self._contours_ws: Optional[torch.Tensor] = None   # nbc_contour_distances', likewise
         self._census_ws: Optional[torch.Tensor] = None     # nbc_softmax_census', likewise
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
+        self._frame_taps: dict = {}                        # training_frame: the device table of each frame length
         self.device: Optional[torch.device] = None
         self.training = False
 
@@ -698,6 +716,51 @@ class FCNResNet50:
             _lib.check(self._lib.nbc_window_merge(lowres_windows.data_ptr(), n, h, w, int(window), int(stride), b,
                                                   merged.data_ptr(), cur.cuda_stream), "nbc_window_merge")
         return merged
+
+    # ---- the training run's own frame (include/nbc.h) ---------------------------
+    def _frame_table(self, lt: int) -> torch.Tensor:
+        """The device table of a resampled axis of frame length ``lt`` (int32 ``[lt, 4]``: first, three coefficients), built
+        through nbc_bilinear_taps and uploaded once per length."""
+        table = self._frame_taps.get(lt)
+        if table is None:
+            from .training_frame import table_of
+            table = torch.from_numpy(table_of(*bilinear_taps(lt + 1, lt))).to(self.device)
+            self._frame_taps[lt] = table
+        return table
+
+    def training_frame(self, x_u8: torch.Tensor, size=(1024, 1024)) -> torch.Tensor:
+        """The training run's frame of a batch (nbc_training_frame): ``pad_resize(img, *size)`` of utils.py:242-247 on uint8
+        ``[N,H,W,3]`` frames or ``[N,H,W]`` grey duals on the device -> uint8 ``[N,Ht,Wt,3]`` or ``[N,Ht,Wt]``, byte for byte
+        ``training_frame.pad_resize_cpu`` of each image.  Runs on the current stream; the coefficient tables of the resampled
+        axes are cached on the device per frame length.  ``ValueError`` for anything but such a tensor on the model's device, a
+        source longer than the frame on an axis, or a pad that one reflection does not reach."""
+        self._require_ctx()
+        if not isinstance(x_u8, torch.Tensor) or x_u8.device != self.device or x_u8.dtype != torch.uint8 or x_u8.numel() == 0 \
+                or not (x_u8.dim() == 3 or (x_u8.dim() == 4 and x_u8.shape[3] == 3)):
+            raise ValueError("x_u8 must be a non-empty uint8 [N,H,W,3] or [N,H,W] tensor on %s" % (self.device,))
+        from .training_frame import frame_geometry
+        try:
+            ht, wt = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError("size must be (Ht, Wt), got %r" % (size,))
+        x = x_u8.contiguous()
+        n, h, w = (int(v) for v in x.shape[:3])
+        channels = 3 if x.dim() == 4 else 1
+        if n > 65535 or ht < 1 or wt < 1 or ht * wt >= 2 ** 31:
+            raise ValueError("training_frame: N <= 65535 and Ht * Wt < 2^31, got N = %d, size %r" % (n, (ht, wt)))
+        (_, hp), (_, wp) = frame_geometry(h, ht), frame_geometry(w, wt)
+        rows = self._frame_table(ht) if hp != ht else None
+        cols = self._frame_table(wt) if wp != wt else None
+        out = torch.empty((n, ht, wt) + ((3,) if channels == 3 else ()), dtype=torch.uint8, device=self.device)
+        with self._on_stream() as cur:
+            for t in (rows, cols):
+                if t is not None:
+                    t.record_stream(cur)
+            _lib.check(self._lib.nbc_training_frame(x.data_ptr(), channels, n, h, w, ht, wt,
+                                                    rows.data_ptr() if rows is not None else None,
+                                                    cols.data_ptr() if cols is not None else None, out.data_ptr(),
+                                                    cur.cuda_stream), "nbc_training_frame")
+        return out
 
     def predict_labels_windows(self, x: torch.Tensor, window: int = 512, stride: int = 256, blend: str = "tent",
                                exclude_nodes: bool = False, labels_dtype: torch.dtype = torch.int64, small_zones: bool = False,
@@ -1435,6 +1498,7 @@ class FCNResNet50:
         self._zone_match_ws = None
         self._contours_ws = None
         self._census_ws = None
+        self._frame_taps = {}
         self._last_shape = None
 
     def __del__(self):
