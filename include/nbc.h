@@ -371,6 +371,19 @@ int nbc_upsample_argmax(nbc_ctx* ctx, const float* logits_lowres_dev, int N, int
 int nbc_remove_small_zones(nbc_ctx* ctx, void* labels_dev, int labels_dtype, int N, int H, int W, int min_pixels,
                            int exclude_nodes, int64_t* counts_dev, void* hip_stream);
 
+/* remove_small_zones on batches, as the reference's PixelWiseF1 runs it (utils.py:211-214 hands the [B,H,W] argmax of a batch
+ * to the same function): skimage's connectivity=2 on a 3-D array is generate_binary_structure(3, 2), so besides its 8
+ * neighbours inside the image a pixel (b, y, x) touches (b +- 1, y', x') with |y - y'| + |x - x'| <= 1, and min_pixels counts
+ * the pixels of the linked component over all its images.  Images n = 0 .. N-1 form consecutive groups of G
+ * (the last one may be shorter); nothing links across a group boundary.  In place; no 2 -> 1 remap.
+ * counts_dev (nullable, int64 [N,3]) receives the pixels per class of every image of the result.  With G = 1 the labels and
+ * counts are those of nbc_remove_small_zones with exclude_nodes = 0, byte for byte.  Sizes are exact integers: a group's
+ * bytes are the same alone, among other groups and on any stream.  The workspace is the context's, 9 bytes per pixel.
+ * NBC_ERR_INVALID, before any HIP call: what nbc_remove_small_zones refuses, H > 65535, H * W >= 2^31, G < 1, G > 64,
+ * g * H * W >= 2^31 for the g = min(G, N) images of a group (a parent index addresses the group's volume). */
+int nbc_remove_small_zones_groups(nbc_ctx* ctx, void* labels_dev, int labels_dtype, int N, int H, int W, int G,
+                                  int min_pixels, int64_t* counts_dev, void* hip_stream);
+
 /* Per-image 3x3 confusion counts of predicted labels against a grey target mask: the pixel counting behind the evaluation
  * loop's lovasz `iou` (lovasz_losses.py:54-73) and `PixelWiseF1` (utils.py:201-235), called at __main__.py:331-332;
  * the ratios are host arithmetic (neuralbarkcalculator_amd/metrics.py).  No context: csrc/confusion.hip.
@@ -427,6 +440,27 @@ size_t nbc_lovasz_workspace_bytes(int N, int H, int W);
 int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
                        void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev,
                        void* hip_stream);
+
+/* The Lovasz-Softmax terms of batches: `LovaszSoftmax()(logits, target)` on a batch runs with per_image=False
+ * (lovasz_losses.py:169-191), flattens the batch and sorts the errors of all its images together, per class -- val_loss and
+ * test_loss of the training log are that, per batch of 8.  Images n = 0 .. N-1 form consecutive groups of G
+ * (the last one may be shorter); there are NG = ceil(N / G) groups.  terms[group][c] and counts[group][c] are what
+ * nbc_lovasz_softmax defines for an image, the segment being the g * H * W pixels of the group's g images in image order:
+ * the pooled loss of a group is the per-image loss of its images stacked along the height, so a group's terms are bit for bit
+ * those of nbc_lovasz_softmax on the one image [1,3,g*H,W], and with G = 1 the call is nbc_lovasz_softmax.  No transposed
+ * copy of the logits is made: only the kernel that writes the keys knows about images.
+ * terms_dev   float64 [NG,3]; 0 for an absent class; NaN for every present class of a group in which some pixel's softmax is
+ *             not finite -- of that group only
+ * counts_dev  int64 [NG,3]: the target pixels of each class in the group (a class present in one image is present for the group)
+ * A group's terms are added in the same fixed order whatever else is in the call and on any stream.  Runs on hip_stream; no
+ * synchronisation.  NBC_ERR_INVALID, before any HIP call: what nbc_lovasz_softmax refuses, G < 1, G > 64, g * H * W >= 2^31
+ * for g = min(G, N).  With P = H * W, S = 3 NG, T = ceil(g P / 8192), the workspace is
+ *   2 A(12 N P) + A(1024 S T) + A(1024 S) + A(4 S T) + A(8 S T) + A(4 NG) bytes;
+ * nbc_lovasz_groups_workspace_bytes returns 0 for what nbc_lovasz_softmax_groups refuses. */
+size_t nbc_lovasz_groups_workspace_bytes(int N, int H, int W, int G);
+int nbc_lovasz_softmax_groups(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int G,
+                              void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* counts_dev,
+                              void* hip_stream);
 
 /* Per-image pixel-wise cross-entropy sums: what CustomWeightedCrossEntropy (utils.py:151-165: F.cross_entropy with
  * reduction='none', times the class weight at max(argmax, target), mean over the pixels), the plain cross-entropy (xloss,
@@ -760,10 +794,10 @@ int nbc_window_merge(const float* lowres_windows_dev, int N, int H, int W, int S
  *             point (an unused tap is 0 and reads nothing) and is clip8((2^21 + sum v k) >> 22), >> arithmetic, clip8 to 0..255.
  *   order     the horizontal pass first, rounded to bytes, then the vertical pass on those bytes: PIL's order and its intermediate
  *             image.  Neither the padded nor the intermediate image is written: an output byte recomputes its at most 3 x 3 reads.
- * Left out: predict on the frame (a resampled axis has no integer map back to the scan's own rows), the batch-pooled Lovasz loss
- * of exp.test (it needs all images of a group on one device at once; the engine shards by image), remove_small_zones on a
- * [B,H,W] batch as the reference's code runs it (connectivity=2 on a 3-D array links zones of neighbouring images through the
- * batch axis; here zones are per image), frames that shrink an axis. */
+ * Left out: predict on the frame (a resampled axis has no integer map back to the scan's own rows) and frames that shrink an
+ * axis.  The two figures of exp.test that need all images of a batch at once -- the batch-pooled Lovasz loss, and
+ * remove_small_zones on the [B,H,W] batch, whose connectivity=2 on a 3-D array links zones of neighbouring images through the
+ * batch axis -- are nbc_lovasz_softmax_groups and nbc_remove_small_zones_groups. */
 enum { NBC_FRAME_TAPS = 3 };
 /* PIL's table of the bilinear filter for in_size -> out_size (Resample.c: precompute_coeffs, then normalize_coeffs_8bpc), in
  * doubles in PIL's order, no contraction: support = scale = in / out, center = (o + 0.5) scale, xmin = (int)(center - support +

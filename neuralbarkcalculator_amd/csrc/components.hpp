@@ -7,6 +7,10 @@
 //   border_rows     link_up again for the rows y = 32k (k >= 1), on global memory;
 //   border_cols     the columns x = 32k (k >= 1): the straight link across the border, and the two diagonal ones.
 // Only border pixels have anything to do in the last two, so their launches cover just them.
+//
+// The parents of an image index its own plane, except under small_zones.hip's grouped pass: there G consecutive images form
+// one volume with one index space (Volume), their components get linked across images by that file, and everything here
+// only adds the image's offset inside its volume to the indices it writes.  G = 1 is the plain per-image labelling.
 #pragma once
 #include "union_find.hpp"
 
@@ -60,42 +64,58 @@ struct ZeroIsSet {
   __device__ int operator()(size_t q) const { return plane[q] == 0; }
 };
 
+// Image n of a batch whose consecutive groups of G images are volumes: `base` is the volume's first pixel in the batch (where
+// its parent indices count from), `off` the image's first pixel inside the volume.  G * H * W < 2^31.
+struct Volume {
+  size_t base;
+  int off;
+  __device__ Volume(int n, int G, int H, int W) {
+    const int first = n - n % G;
+    base = (size_t)first * H * W;
+    off = (n - first) * H * W;
+  }
+  __device__ size_t image() const { return base + (size_t)off; }
+};
+
 template <typename ClassOf>
-__global__ void border_rows_kernel(int* __restrict__ parent, ClassOf cls, int H, int W) {
+__global__ void border_rows_kernel(int* __restrict__ parent, ClassOf cls, int H, int W, int G) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = (blockIdx.y + 1) * kLabelTile;
   if (x >= W || y >= H) return;
-  const size_t img = (size_t)blockIdx.z * H * W;
-  int* L = parent + img;
+  const Volume vol(blockIdx.z, G, H, W);
+  const size_t img = vol.image();
+  int* L = parent + vol.base;
   const int p = y * W + x;
   const int c = cls(img + p);
   if (!c) return;
   const auto same = [&](int q) { return cls(img + q) == c; };
   link_up(x > 0 && same(p - 1), x < W - 1 && same(p + 1), same(p - W), x > 0 && same(p - W - 1), x < W - 1 && same(p - W + 1),
-          [&](int d) { unite(L, p, p - W + d); });
+          [&](int d) { unite(L, vol.off + p, vol.off + p - W + d); });
 }
 
 // The pixel right of the border links to W.  The diagonals across a vertical border are needed only when neither the
 // straight neighbour of the pixel's own tile (N) nor the pixel across the border in its own row (W resp. E) has the pixel's
 // class: otherwise that neighbour's own link already joins the two.
 template <typename ClassOf>
-__global__ void border_cols_kernel(int* __restrict__ parent, ClassOf cls, int H, int W) {
+__global__ void border_cols_kernel(int* __restrict__ parent, ClassOf cls, int H, int W, int G) {
   const int y = blockIdx.x * blockDim.x + threadIdx.x, x = (blockIdx.y + 1) * kLabelTile;   // x: first column right of a border
   if (y >= H || x >= W) return;
-  const size_t img = (size_t)blockIdx.z * H * W;
-  int* L = parent + img;
+  const Volume vol(blockIdx.z, G, H, W);
+  const size_t img = vol.image();
+  int* L = parent + vol.base;
   const int p = y * W + x;                    // right of the border; p - 1 is left of it
+  const int v = vol.off + p;                  // p as the volume counts it
   const int cr = cls(img + p), cl = cls(img + p - 1);
-  if (cr && cr == cl) unite(L, p, p - 1);
+  if (cr && cr == cl) unite(L, v, v - 1);
   if ((y & (kLabelTile - 1)) == 0) return;    // rows on a horizontal border (and row 0) are border_rows_kernel's
-  if (cr && cl != cr && cls(img + p - W) != cr && cls(img + p - W - 1) == cr) unite(L, p, p - W - 1);      // NW across the border
-  if (cl && cr != cl && cls(img + p - 1 - W) != cl && cls(img + p - W) == cl) unite(L, p - 1, p - W);      // NE across the border
+  if (cr && cl != cr && cls(img + p - W) != cr && cls(img + p - W - 1) == cr) unite(L, v, v - W - 1);      // NW across the border
+  if (cl && cr != cl && cls(img + p - 1 - W) != cl && cls(img + p - W) == cl) unite(L, v - 1, v - W);      // NE across the border
 }
 
 template <typename ClassOf>
-inline void launch_borders(int* parent, ClassOf cls, int N, int H, int W, hipStream_t s) {
+inline void launch_borders(int* parent, ClassOf cls, int N, int H, int W, hipStream_t s, int G = 1) {
   constexpr int TILE = kLabelTile;
-  if (H > TILE) hipLaunchKernelGGL(border_rows_kernel<ClassOf>, dim3((W + 255) / 256, (H - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
-  if (W > TILE) hipLaunchKernelGGL(border_cols_kernel<ClassOf>, dim3((H + 255) / 256, (W - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W);
+  if (H > TILE) hipLaunchKernelGGL(border_rows_kernel<ClassOf>, dim3((W + 255) / 256, (H - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W, G);
+  if (W > TILE) hipLaunchKernelGGL(border_cols_kernel<ClassOf>, dim3((H + 255) / 256, (W - 1) / TILE, N), dim3(256), 0, s, parent, cls, H, W, G);
 }
 
 // One leader per distinct key among the valid lanes of a wave: body(key, same) runs in the first lane that holds the key,

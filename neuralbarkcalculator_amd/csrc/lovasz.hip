@@ -19,6 +19,12 @@
 //   lovasz_finish   one thread per segment adds the tile partials in tile order.
 // A segment whose class is absent (G = 0) or whose image has a non-finite softmax is not sorted: its term is
 // 0 or NaN.  No library besides the HIP runtime.
+//
+// Pooled over groups (nbc_lovasz_softmax_groups: `LovaszSoftmax()` on a batch, per_image=False, lovasz_losses.py:169-191): the
+// segment of (group, class) is the pixels of the group's g consecutive images, one after the other -- the per-image segment
+// of the g images stacked along the height.  Only lovasz_keys knows about images: it writes the key of (image n, class c,
+// pixel i) to segment (n / G, c) at (n mod G) P + i.  Everything after it works on segments whose length Segments::pixels
+// gives (the last group may be shorter); the per-image pass is the case G = 1, same kernels, same tiles, same bits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,6 +45,8 @@ constexpr int kPasses = 4;                              // 4 x 8 bits cover the 
 constexpr int kKeyThreads = 256;
 constexpr int kScanThreads = 1024;                      // 4 groups of 256 digit lanes
 constexpr const char* kWho = "nbc_lovasz_softmax";
+constexpr const char* kWhoGroups = "nbc_lovasz_softmax_groups";
+constexpr int kMaxGroup = 64;                           // evaluate.py's MAX_POOL
 
 using u32 = unsigned;
 using u64 = unsigned long long;
@@ -76,15 +84,28 @@ __device__ __forceinline__ u32 excl_scan_256(u32 v, u32* wsum /* LDS [4] */) {
   return pre + x - v;
 }
 
+// Where the segments of a call lie: N images of P pixels in consecutive groups of `group` (the last one shorter when group
+// does not divide N).  Group n holds its three segments back to back behind the 3 * group * P keys of every group before it.
+struct Segments {
+  long long P;
+  int N, group;
+  __host__ __device__ long long pixels(int n) const { const int left = N - n * group; return (long long)(left < group ? left : group) * P; }
+  __host__ __device__ size_t keys_at(int n, int c) const { return (size_t)n * group * kClasses * P + (size_t)c * pixels(n); }
+  __host__ __device__ int tiles(int n) const { return (int)((pixels(n) + kTile - 1) / kTile); }
+};
+
 __device__ __forceinline__ bool segment_idle(const u64* G, const u32* flag, int n, int seg) { return G[seg] == 0 || flag[n] != 0; }
 
 __global__ __launch_bounds__(kKeyThreads) void lovasz_keys(const float* __restrict__ logits, const unsigned char* __restrict__ target,
-                                                           long long P, u32* __restrict__ keys, u64* __restrict__ G,
+                                                           Segments sg, u32* __restrict__ keys, u64* __restrict__ G,
                                                            u32* __restrict__ flag) {
-  const int n = blockIdx.y, tid = threadIdx.x;
+  const int n = blockIdx.y, tid = threadIdx.x;                    // n: the image; grp: its group, where it is image number n - grp * group
+  const long long P = sg.P;
+  const int grp = n / sg.group;
   const float* lg = logits + (size_t)n * kClasses * P;
   const unsigned char* tg = target + (size_t)n * P;
-  u32* k0 = keys + (size_t)n * kClasses * P;
+  u32* k0 = keys + sg.keys_at(grp, 0) + (size_t)(n - grp * sg.group) * P;
+  const size_t cstride = (size_t)sg.pixels(grp);
   u32 cnt[kClasses] = {0, 0, 0};
   bool bad = false;
   for (long long i = (long long)blockIdx.x * kKeyThreads + tid; i < P; i += (long long)gridDim.x * kKeyThreads) {
@@ -100,28 +121,29 @@ __global__ __launch_bounds__(kKeyThreads) void lovasz_keys(const float* __restri
     for (int cl = 0; cl < kClasses; ++cl) {
       const u32 fg = t == (u32)cl;
       const float e = finite ? fabsf((float)fg - p[cl]) : 0.f;
-      k0[(size_t)cl * P + i] = (__float_as_uint(e) << 1) | fg;
+      k0[cl * cstride + i] = (__float_as_uint(e) << 1) | fg;
       cnt[cl] += fg;
     }
   }
-  block_add<kKeyThreads, kClasses>(cnt, G + (size_t)n * kClasses, [&] {
-    if (__syncthreads_or(bad) && tid == 0) flag[n] = 1u;
+  block_add<kKeyThreads, kClasses>(cnt, G + (size_t)grp * kClasses, [&] {
+    if (__syncthreads_or(bad) && tid == 0) flag[grp] = 1u;
   });
 }
 
 // per-tile digit histogram: hist[seg][t][d]
-__global__ __launch_bounds__(kSortThreads) void lovasz_hist(const u32* __restrict__ keys, long long P, int T, int shift,
+__global__ __launch_bounds__(kSortThreads) void lovasz_hist(const u32* __restrict__ keys, Segments sg, int T, int shift,
                                                             u32* __restrict__ hist, const u64* __restrict__ G,
                                                             const u32* __restrict__ flag) {
   const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
-  if (segment_idle(G, flag, n, seg)) return;
+  const long long P = sg.pixels(n);
+  if (segment_idle(G, flag, n, seg) || (long long)t * kTile >= P) return;
   __shared__ u32 h[kRadix];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid < kRadix) h[tid] = 0;
   __syncthreads();
   const long long start = (long long)t * kTile;
   const int nt = (int)min((long long)kTile, P - start);
-  const u32* src = keys + (size_t)seg * P + start;
+  const u32* src = keys + sg.keys_at(n, blockIdx.z) + start;
 #pragma unroll 4
   for (int j = 0; j < kItems; ++j) {
     const int idx = w * (kItems * 64) + j * 64 + lane;
@@ -135,7 +157,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_hist(const u32* __restric
 }
 
 // per segment: hist[seg][t][d] <- sum over t' < t of hist[seg][t'][d]; base[seg][d] <- keys of the segment with a digit below d
-__global__ __launch_bounds__(kScanThreads) void lovasz_scan(u32* __restrict__ hist, int T, u32* __restrict__ base,
+__global__ __launch_bounds__(kScanThreads) void lovasz_scan(u32* __restrict__ hist, Segments sg, int T, u32* __restrict__ base,
                                                             const u64* __restrict__ G, const u32* __restrict__ flag) {
   const int n = blockIdx.x, seg = n * kClasses + blockIdx.y;
   if (segment_idle(G, flag, n, seg)) return;
@@ -143,8 +165,9 @@ __global__ __launch_bounds__(kScanThreads) void lovasz_scan(u32* __restrict__ hi
   __shared__ u32 wsum[4];
   const int tid = threadIdx.x, d = tid & (kRadix - 1), g = tid / kRadix;
   constexpr int kGroups = kScanThreads / kRadix;
-  const int per = (T + kGroups - 1) / kGroups;
-  const int t0 = min(T, g * per), t1 = min(T, t0 + per);
+  const int Tn = sg.tiles(n);                          // the segment's own tiles; T is the stride of hist
+  const int per = (Tn + kGroups - 1) / kGroups;
+  const int t0 = min(Tn, g * per), t1 = min(Tn, t0 + per);
   u32* h = hist + (size_t)seg * T * kRadix + d;
   u32 sum = 0;
   for (int t = t0; t < t1; ++t) sum += h[(size_t)t * kRadix];
@@ -166,11 +189,12 @@ __global__ __launch_bounds__(kScanThreads) void lovasz_scan(u32* __restrict__ hi
 }
 
 // one stable LSD pass of one tile: rank by wave ballots, sort the tile in LDS, write it out in runs of equal digits
-__global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __restrict__ in, u32* __restrict__ out, long long P, int T,
+__global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __restrict__ in, u32* __restrict__ out, Segments sg, int T,
                                                                int shift, const u32* __restrict__ hist, const u32* __restrict__ base,
                                                                const u64* __restrict__ G, const u32* __restrict__ flag) {
   const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
-  if (segment_idle(G, flag, n, seg)) return;
+  const long long P = sg.pixels(n);
+  if (segment_idle(G, flag, n, seg) || (long long)t * kTile >= P) return;
   __shared__ u32 sorted[kTile];
   __shared__ u32 cnt[kWaves][kRadix];                 // per wave: digit counts, then the wave's start inside the digit
   __shared__ u32 dstart[kRadix];                      // start of each digit in the sorted tile
@@ -181,7 +205,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __rest
   __builtin_amdgcn_wave_barrier();
   const long long start = (long long)t * kTile;
   const int nt = (int)min((long long)kTile, P - start);
-  const u32* src = in + (size_t)seg * P + start;
+  const u32* src = in + sg.keys_at(n, blockIdx.z) + start;
 
   u32 key[kItems], rank[kItems];
 #pragma unroll
@@ -228,7 +252,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_scatter(const u32* __rest
     }
   }
   __syncthreads();
-  u32* dst = out + (size_t)seg * P;
+  u32* dst = out + sg.keys_at(n, blockIdx.z);
   for (int i = tid; i < nt; i += kSortThreads) {
     const u32 k = sorted[i];
     dst[gofs[digit_of(k, shift)] + (u32)i] = k;
@@ -248,26 +272,28 @@ __device__ __forceinline__ void block_sum_to(u32 v, u32* red /* LDS [kWaves] */,
 }
 
 // foreground keys per tile of the sorted segment
-__global__ __launch_bounds__(kSortThreads) void lovasz_tile_fg(const u32* __restrict__ keys, long long P, int T,
+__global__ __launch_bounds__(kSortThreads) void lovasz_tile_fg(const u32* __restrict__ keys, Segments sg, int T,
                                                                u32* __restrict__ tile_fg, const u64* __restrict__ G,
                                                                const u32* __restrict__ flag) {
   const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
-  if (segment_idle(G, flag, n, seg)) return;
+  const long long P = sg.pixels(n);
+  if (segment_idle(G, flag, n, seg) || (long long)t * kTile >= P) return;
   __shared__ u32 red[kWaves];
   const long long start = (long long)t * kTile;
   const int nt = (int)min((long long)kTile, P - start);
-  const u32* src = keys + (size_t)seg * P + start;
+  const u32* src = keys + sg.keys_at(n, blockIdx.z) + start;
   u32 c = 0;
   for (int i = threadIdx.x; i < nt; i += kSortThreads) c += src[i] & 1u;
   block_sum_to(c, red, &tile_fg[(size_t)seg * T + t]);
 }
 
 // f64 partial sum of e_(i) (J_i - J_{i-1}) over one tile of the sorted segment
-__global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __restrict__ keys, long long P, int T,
+__global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __restrict__ keys, Segments sg, int T,
                                                                const u32* __restrict__ tile_fg, const u64* __restrict__ G,
                                                                const u32* __restrict__ flag, double* __restrict__ partial) {
   const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
-  if (segment_idle(G, flag, n, seg)) return;
+  const long long P = sg.pixels(n);
+  if (segment_idle(G, flag, n, seg) || (long long)t * kTile >= P) return;
   __shared__ u32 red[kWaves];
   __shared__ u32 wfg[kWaves];
   __shared__ u32 fg_before_tile;
@@ -279,7 +305,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __rest
 
   const long long start = (long long)t * kTile;
   const int nt = (int)min((long long)kTile, P - start);
-  const u32* src = keys + (size_t)seg * P + start;
+  const u32* src = keys + sg.keys_at(n, blockIdx.z) + start;
   u32 key[kItems];
   u32 mine = 0;
 #pragma unroll
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(kSortThreads) void lovasz_partial(const u32* __rest
   }
 }
 
-__global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ partial, int T, int S, const u64* __restrict__ G,
+__global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ partial, Segments sg, int T, int S, const u64* __restrict__ G,
                                                     const u32* __restrict__ flag, double* __restrict__ terms) {
   const int seg = blockIdx.x * 64 + threadIdx.x;
   if (seg >= S) return;
@@ -332,15 +358,16 @@ __global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ p
     s = __builtin_nan("");
   else {
     const double* p = partial + (size_t)seg * T;
+    const int Tn = sg.tiles(seg / kClasses);
     int t = 0;
-    for (; t + 8 <= T; t += 8) {                     // eight loads in flight, added in tile order
+    for (; t + 8 <= Tn; t += 8) {                     // eight loads in flight, added in tile order
       double v[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = p[t + k];
 #pragma unroll
       for (int k = 0; k < 8; ++k) s += v[k];
     }
-    for (; t < T; ++t) s += p[t];
+    for (; t < Tn; ++t) s += p[t];
   }
   terms[seg] = s;
 }
@@ -349,36 +376,38 @@ struct Layout {
   size_t keys_a, keys_b, hist, base, tile_fg, partial, flag, total;
 };
 
+constexpr const char* kGroupShape = "bad group: 1 <= G <= 64 and g * H * W < 2^31 for the g = min(G, N) images of a group";
+
+inline bool group_ok(int N, int H, int W, int G) {
+  return G >= 1 && G <= kMaxGroup && (long long)(G < N ? G : N) * H * W <= 0x7fffffffLL;
+}
+
 // byte offsets of the workspace regions (include/nbc.h states the sum); false for a shape the call refuses
-bool layout(int N, int H, int W, Layout* L) {
-  if (!per_image_shape_ok(N, H, W)) return false;
+bool layout(int N, int H, int W, int G, Layout* L) {
+  if (!per_image_shape_ok(N, H, W) || !group_ok(N, H, W, G)) return false;
   const size_t P = (size_t)H * (size_t)W;
-  const size_t S = (size_t)kClasses * N, T = (P + kTile - 1) / kTile;
+  const size_t NG = ((size_t)N + G - 1) / G;           // groups
+  const size_t S = (size_t)kClasses * NG, T = ((size_t)(G < N ? G : N) * P + kTile - 1) / kTile;
   Carver ws;
-  L->keys_a = ws.take(4 * S * P);
-  L->keys_b = ws.take(4 * S * P);
+  L->keys_a = ws.take(4 * kClasses * N * P);
+  L->keys_b = ws.take(4 * kClasses * N * P);
   L->hist = ws.take(4 * S * T * kRadix);
   L->base = ws.take(4 * S * kRadix);
   L->tile_fg = ws.take(4 * S * T);
   L->partial = ws.take(8 * S * T);
-  L->flag = ws.take(4 * (size_t)N);
+  L->flag = ws.take(4 * NG);
   L->total = ws.offset;
   return true;
 }
 
-}  // namespace
-
-extern "C" size_t nbc_lovasz_workspace_bytes(int N, int H, int W) {
+// the per-image pass is the grouped one with groups of one image
+int run(const char* who, const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int group, void* workspace_dev,
+        size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
+  if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(who, NBC_ERR_INVALID, "null argument");
+  if (!per_image_shape_ok(N, H, W)) return fail(who, NBC_ERR_INVALID, kPerImageShape);
   Layout L;
-  return layout(N, H, W, &L) ? L.total : 0;
-}
-
-extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, void* workspace_dev,
-                                  size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
-  if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
-  Layout L;
-  if (!layout(N, H, W, &L)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
-  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, L.total)) return rc;
+  if (!layout(N, H, W, group, &L)) return fail(who, NBC_ERR_INVALID, kGroupShape);
+  if (int rc = check_workspace(who, workspace_dev, workspace_bytes, L.total)) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   char* ws = static_cast<char*>(workspace_dev);
   u32* keys[2] = {reinterpret_cast<u32*>(ws + L.keys_a), reinterpret_cast<u32*>(ws + L.keys_b)};
@@ -388,33 +417,57 @@ extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* t
   double* partial = reinterpret_cast<double*>(ws + L.partial);
   u32* flag = reinterpret_cast<u32*>(ws + L.flag);
   u64* G = reinterpret_cast<u64*>(fg_counts_dev);
-  const long long P = (long long)H * W;
-  const int S = kClasses * N, T = (int)((P + kTile - 1) / kTile);
+  const Segments sg{(long long)H * W, N, group};
+  const long long P = sg.P;
+  const int NG = (N + group - 1) / group, S = kClasses * NG, T = sg.tiles(0);   // the first group is never the short one
 
   hipError_t e = hipMemsetAsync(G, 0, sizeof(u64) * (size_t)S, s);
-  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(u32) * (size_t)N, s);
-  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
+  if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(u32) * (size_t)NG, s);
+  if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
   // about 4 pixels per thread and at most ~4096 blocks over the batch
   long long bx = (P + 4 * kKeyThreads - 1) / (4 * kKeyThreads);
   const long long cap = (4096 + N - 1) / N;
   if (bx > cap) bx = cap;
   if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(lovasz_keys, dim3((unsigned)bx, (unsigned)N), dim3(kKeyThreads), 0, s, logits_full_dev, target_dev, P, keys[0], G,
+  hipLaunchKernelGGL(lovasz_keys, dim3((unsigned)bx, (unsigned)N), dim3(kKeyThreads), 0, s, logits_full_dev, target_dev, sg, keys[0], G,
                      flag);
-  const dim3 tiles((unsigned)T, (unsigned)N, (unsigned)kClasses);
+  const dim3 tiles((unsigned)T, (unsigned)NG, (unsigned)kClasses);
   for (int pass = 0; pass < kPasses; ++pass) {
     const int shift = 8 * pass;
     const u32* in = keys[pass & 1];
     u32* out = keys[(pass & 1) ^ 1];
-    hipLaunchKernelGGL(lovasz_hist, tiles, dim3(kSortThreads), 0, s, in, P, T, shift, hist, G, flag);
-    hipLaunchKernelGGL(lovasz_scan, dim3((unsigned)N, (unsigned)kClasses), dim3(kScanThreads), 0, s, hist, T, base, G, flag);
-    hipLaunchKernelGGL(lovasz_scatter, tiles, dim3(kSortThreads), 0, s, in, out, P, T, shift, hist, base, G, flag);
+    hipLaunchKernelGGL(lovasz_hist, tiles, dim3(kSortThreads), 0, s, in, sg, T, shift, hist, G, flag);
+    hipLaunchKernelGGL(lovasz_scan, dim3((unsigned)NG, (unsigned)kClasses), dim3(kScanThreads), 0, s, hist, sg, T, base, G, flag);
+    hipLaunchKernelGGL(lovasz_scatter, tiles, dim3(kSortThreads), 0, s, in, out, sg, T, shift, hist, base, G, flag);
   }
   const u32* sorted = keys[kPasses & 1];             // an even number of passes ends where the keys started
-  hipLaunchKernelGGL(lovasz_tile_fg, tiles, dim3(kSortThreads), 0, s, sorted, P, T, tile_fg, G, flag);
-  hipLaunchKernelGGL(lovasz_partial, tiles, dim3(kSortThreads), 0, s, sorted, P, T, tile_fg, G, flag, partial);
-  hipLaunchKernelGGL(lovasz_finish, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, partial, T, S, G, flag, terms_dev);
+  hipLaunchKernelGGL(lovasz_tile_fg, tiles, dim3(kSortThreads), 0, s, sorted, sg, T, tile_fg, G, flag);
+  hipLaunchKernelGGL(lovasz_partial, tiles, dim3(kSortThreads), 0, s, sorted, sg, T, tile_fg, G, flag, partial);
+  hipLaunchKernelGGL(lovasz_finish, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, s, partial, sg, T, S, G, flag, terms_dev);
   e = hipGetLastError();
-  if (e != hipSuccess) return fail(kWho, NBC_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t nbc_lovasz_workspace_bytes(int N, int H, int W) {
+  Layout L;
+  return layout(N, H, W, 1, &L) ? L.total : 0;
+}
+
+extern "C" int nbc_lovasz_softmax(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, void* workspace_dev,
+                                  size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
+  return run(kWho, logits_full_dev, target_dev, N, H, W, 1, workspace_dev, workspace_bytes, terms_dev, fg_counts_dev, hip_stream);
+}
+
+extern "C" size_t nbc_lovasz_groups_workspace_bytes(int N, int H, int W, int G) {
+  Layout L;
+  return layout(N, H, W, G, &L) ? L.total : 0;
+}
+
+extern "C" int nbc_lovasz_softmax_groups(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int G,
+                                         void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* counts_dev,
+                                         void* hip_stream) {
+  return run(kWhoGroups, logits_full_dev, target_dev, N, H, W, G, workspace_dev, workspace_bytes, terms_dev, counts_dev, hip_stream);
 }

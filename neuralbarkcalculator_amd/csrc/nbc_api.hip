@@ -1012,6 +1012,25 @@ int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N
   return NBC_OK;
 }
 
+int nbc_remove_small_zones_groups(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int G, int min_pixels,
+                                  int64_t* counts_dev, void* hip_stream) {
+  const char* who = "nbc_remove_small_zones_groups: ";
+  if (!c || !labels_dev) return set_error(NBC_ERR_INVALID, std::string(who) + "null argument");
+  if (!per_image_shape_ok(N, H, W) || H > 65535 || min_pixels < 0) return set_error(NBC_ERR_INVALID, std::string(who) + "bad shape");
+  if (G < 1 || G > 64 || (long long)(G < N ? G : N) * H * W > 0x7fffffffLL)
+    return set_error(NBC_ERR_INVALID, std::string(who) + "bad group: 1 <= G <= 64 and g * H * W < 2^31 for the g = min(G, N) images of a group");
+  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, std::string(who) + "bad labels_dtype");
+  NBC_HIP(hipSetDevice(c->device));
+  const size_t px = (size_t)N * H * W;
+  NBC_HIP(c->zones_ws.reserve(px * 9 + 256, Grow::kMargin));   // nbc_remove_small_zones' workspace and its carving
+  int* parent = c->zones_ws.as<int>();
+  int* size = parent + px;
+  unsigned char* bg = reinterpret_cast<unsigned char*>(size + px);
+  NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, 0, bg, parent, size,
+                                    reinterpret_cast<unsigned long long*>(counts_dev), static_cast<hipStream_t>(hip_stream), G));
+  return NBC_OK;
+}
+
 static bool zones_shape_ok(int N, int H, int W) { return per_image_shape_ok(N, H, W) && H <= 65535 && W <= 65535; }
 
 size_t nbc_zones_workspace_bytes(int N, int H, int W) { return zones_shape_ok(N, H, W) ? zones_layout(N, H, W).total : 0; }

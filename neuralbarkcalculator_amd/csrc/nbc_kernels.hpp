@@ -184,8 +184,9 @@ hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int 
 // remove_small_zones (utils.py:135-148) in place on device labels (u8 or i64, [N,H,W]): 8-connected
 // components below min_pixels of the non-background, then of the filled background, flip; optional
 // 2 -> 1 remap and per-class counts afterwards.  Workspaces: bg N*H*W bytes, parent and size N*H*W ints.
+// G > 1: consecutive groups of G images are volumes whose zones also link across images (small_zones.hip).
 hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H, int W, int min_pixels, int exclude_nodes,
-                                     unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s);
+                                     unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s, int G = 1);
 // The zones of label maps (zones.hip; the contract: nbc_label_zones in include/nbc.h): rows int64 [N][cap][10], num int64 [N].
 // zones_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size.
 struct ZonesLayout {

@@ -12,6 +12,14 @@
 //   apply          components below the threshold flip in the mask.
 // The result (which pixels flip) depends only on component sizes, which are exact integers, so the
 // output equals the CPU restatement (scipy.ndimage.label) bit for bit.
+//
+// Grouped (nbc_remove_small_zones_groups): the reference's PixelWiseF1 hands the [B,H,W] argmax of a batch to the same
+// function (utils.py:211-214), and skimage's connectivity=2 on a 3-D array is generate_binary_structure(3, 2): besides the
+// 8 neighbours inside its image, a pixel (b, y, x) touches (b +- 1, y, x) and the four edge neighbours of that pixel.  So G
+// consecutive images form one volume (components.hpp: Volume) whose parents share one index space, and
+//   link_images    one launch per phase, after the border kernels: the set pixels of an image that is not the first of
+//                  its group make the links to the image before it;
+// sum_sizes and apply then see components that span images.  G = 1 launches nothing more and is the per-image pass.
 #include "components.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
@@ -26,13 +34,14 @@ constexpr int TILE = kLabelTile;
 template <typename LabelT>
 __global__ __launch_bounds__(TILE* TILE) void tile_label_kernel(const LabelT* __restrict__ labels, unsigned char* __restrict__ bg,
                                                                  int* __restrict__ parent, int* __restrict__ size,
-                                                                 int H, int W, int phase) {
+                                                                 int H, int W, int G, int phase) {
   __shared__ int s[TILE * TILE];
   __shared__ int cnt[TILE * TILE];
   __shared__ unsigned char sc[TILE * TILE];
   const int t = threadIdx.x;
   const int x = blockIdx.x * TILE + (t & (TILE - 1)), y = blockIdx.y * TILE + (t >> 5);
-  const size_t img = (size_t)blockIdx.z * H * W;
+  const Volume vol(blockIdx.z, G, H, W);
+  const size_t img = vol.image();
   const bool inside = x < W && y < H;
   const int p = y * W + x;
   int m = 0;
@@ -50,7 +59,7 @@ __global__ __launch_bounds__(TILE* TILE) void tile_label_kernel(const LabelT* __
   for_each_key(r >= 0, r, [&](int root, unsigned long long same) { atomicAdd(&cnt[root], (int)__popcll(same)); });
   __syncthreads();
   if (inside) {
-    parent[img + p] = m ? (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1)) : -1;   // index inside the image
+    parent[img + p] = m ? vol.off + (blockIdx.y * TILE + (r >> 5)) * W + blockIdx.x * TILE + (r & (TILE - 1)) : -1;   // index inside the volume
     size[img + p] = r == t ? cnt[t] : 0;      // non-zero exactly at the tile-local roots
   }
 }
@@ -58,26 +67,60 @@ __global__ __launch_bounds__(TILE* TILE) void tile_label_kernel(const LabelT* __
 // Component sizes: tile_label_kernel left the pixel count of every tile-local root in size[]; a local
 // root that was linked under another root adds its count to its final root.  Only the (few thousand)
 // local roots do anything here; their atomics spread over as many final roots as there are components.
-__global__ void sum_sizes_kernel(int* __restrict__ parent, int* __restrict__ size, int H, int W) {
+__global__ void sum_sizes_kernel(int* __restrict__ parent, int* __restrict__ size, int H, int W, int G) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W) return;
-  int* L = parent + (size_t)blockIdx.z * H * W;
-  int* S = size + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
+  const Volume vol(blockIdx.z, G, H, W);
+  int* L = parent + vol.base;
+  int* S = size + vol.base;
+  const int p = vol.off + y * W + x;
   const int mine = S[p];
   if (mine == 0) return;                      // not a tile-local root
   const int r = find_root(L, p);              // no links change any more: r is the component's root
   if (r != p) atomicAdd(&S[r], mine);
 }
 
+// The links between consecutive images of a group, for the mask `set` (ZeroIsSet or ClassPlane of bg).  Where a pixel and
+// the pixel at its place in the image before are both set (the two "overlap"), they belong together -- but only the first
+// pixel of an overlap makes that union: one whose W or N neighbour overlaps as well is joined to that neighbour inside both
+// images, and the neighbour (or the one it defers to) makes the link.  So the unions of a large zone that stays in place
+// from image to image are as many as its overlap has upper-left corners, not as many as it has pixels.  Where the pixel
+// before is not set: for each of the four edge directions, a union with the pixel before at that neighbour's place when
+// it is set and the pixel's own neighbour there is not -- a set neighbour overlaps there and is joined to the pixel
+// inside the image already.
+template <typename ClassOf>
+__global__ void link_images_kernel(int* __restrict__ parent, ClassOf set, int H, int W, int G) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  const Volume vol(blockIdx.z, G, H, W);
+  if (x >= W || vol.off == 0) return;         // the first image of a group has none before it
+  const size_t img = vol.image(), before = img - (size_t)H * W;
+  const int p = y * W + x, P = H * W;
+  if (!set(img + p)) return;
+  int* L = parent + vol.base;
+  const int v = vol.off + p;
+  const auto overlaps = [&](int q) { return set(img + q) && set(before + q); };
+  if (set(before + p)) {
+    if (!(x > 0 && overlaps(p - 1)) && !(y > 0 && overlaps(p - W))) unite(L, v, v - P);
+    return;
+  }
+  const auto side = [&](bool in_image, int d) {
+    if (in_image && !set(img + p + d) && set(before + p + d)) unite(L, v, v - P + d);
+  };
+  side(x > 0, -1);
+  side(x < W - 1, 1);
+  side(y > 0, -W);
+  side(y < H - 1, W);
+}
+
 // phase 0: small components of ~bg join bg.  phase 1: small components of bg leave it, then the labels
 // are rewritten (utils.py:145-146), optionally remapped 2 -> 1 (models.py:273-276) and counted.
 template <typename LabelT>
 __global__ void apply_kernel(LabelT* __restrict__ labels, unsigned char* __restrict__ bg, const int* __restrict__ parent,
-                             const int* __restrict__ size, int H, int W, int min_pixels, int phase, int exclude_nodes,
+                             const int* __restrict__ size, int H, int W, int G, int min_pixels, int phase, int exclude_nodes,
                              unsigned long long* __restrict__ counts) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  const size_t img = (size_t)blockIdx.z * H * W;
+  const Volume vol(blockIdx.z, G, H, W);
+  const size_t img = vol.image();
   unsigned c1 = 0, c2 = 0;
   if (x < W) {
     const size_t q = img + (size_t)y * W + x;
@@ -85,11 +128,11 @@ __global__ void apply_kernel(LabelT* __restrict__ labels, unsigned char* __restr
     // few remaining hops to the component's root, read-only
     int r = parent[q];
     if (r >= 0) {
-      const int* L = parent + img;
+      const int* L = parent + vol.base;
       int up = L[r];
       while (up != r) { r = up; up = L[r]; }
     }
-    const bool small = r >= 0 && size[img + r] < min_pixels;
+    const bool small = r >= 0 && size[vol.base + r] < min_pixels;
     if (phase == 0) {
       if (small) bg[q] = 1;
     } else {
@@ -127,7 +170,7 @@ __global__ void finish_counts_kernel(unsigned long long* counts, int N, unsigned
 }
 
 template <typename LabelT>
-hipError_t run(LabelT* labels, int N, int H, int W, int min_pixels, int exclude_nodes, unsigned char* bg, int* parent,
+hipError_t run(LabelT* labels, int N, int H, int W, int G, int min_pixels, int exclude_nodes, unsigned char* bg, int* parent,
                int* size, unsigned long long* counts, hipStream_t s) {
   const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, N);
   const dim3 rows((W + 255) / 256, H, N);
@@ -136,11 +179,16 @@ hipError_t run(LabelT* labels, int N, int H, int W, int min_pixels, int exclude_
     if (e != hipSuccess) return e;
   }
   for (int phase = 0; phase < 2; ++phase) {
-    hipLaunchKernelGGL(tile_label_kernel<LabelT>, tiles, dim3(TILE * TILE), 0, s, labels, bg, parent, size, H, W, phase);
-    if (phase == 0) launch_borders(parent, ZeroIsSet{bg}, N, H, W, s);      // the mask is ~bg, then bg
-    else launch_borders(parent, ClassPlane{bg}, N, H, W, s);
-    hipLaunchKernelGGL(sum_sizes_kernel, rows, dim3(256), 0, s, parent, size, H, W);
-    hipLaunchKernelGGL(apply_kernel<LabelT>, rows, dim3(256), 0, s, labels, bg, parent, size, H, W, min_pixels, phase,
+    hipLaunchKernelGGL(tile_label_kernel<LabelT>, tiles, dim3(TILE * TILE), 0, s, labels, bg, parent, size, H, W, G, phase);
+    if (phase == 0) {                                                        // the mask is ~bg, then bg
+      launch_borders(parent, ZeroIsSet{bg}, N, H, W, s, G);
+      if (G > 1 && N > 1) hipLaunchKernelGGL(link_images_kernel<ZeroIsSet>, rows, dim3(256), 0, s, parent, ZeroIsSet{bg}, H, W, G);
+    } else {
+      launch_borders(parent, ClassPlane{bg}, N, H, W, s, G);
+      if (G > 1 && N > 1) hipLaunchKernelGGL(link_images_kernel<ClassPlane>, rows, dim3(256), 0, s, parent, ClassPlane{bg}, H, W, G);
+    }
+    hipLaunchKernelGGL(sum_sizes_kernel, rows, dim3(256), 0, s, parent, size, H, W, G);
+    hipLaunchKernelGGL(apply_kernel<LabelT>, rows, dim3(256), 0, s, labels, bg, parent, size, H, W, G, min_pixels, phase,
                        exclude_nodes, counts);
   }
   if (counts) hipLaunchKernelGGL(finish_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, counts, N, (unsigned long long)H * W);
@@ -150,10 +198,11 @@ hipError_t run(LabelT* labels, int N, int H, int W, int min_pixels, int exclude_
 }  // namespace
 
 hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H, int W, int min_pixels, int exclude_nodes,
-                                     unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s) {
+                                     unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s, int G) {
   if (!per_image_shape_ok(N, H, W) || H > 65535) return hipErrorInvalidValue;      // grid.y carries the row
-  if (labels_i64) return run(static_cast<long long*>(labels), N, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s);
-  return run(static_cast<unsigned char*>(labels), N, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s);
+  if (G < 1 || (long long)(G < N ? G : N) * H * W > 0x7fffffffLL) return hipErrorInvalidValue;   // a volume's index fits 31 bits
+  if (labels_i64) return run(static_cast<long long*>(labels), N, H, W, G, min_pixels, exclude_nodes, bg, parent, size, counts, s);
+  return run(static_cast<unsigned char*>(labels), N, H, W, G, min_pixels, exclude_nodes, bg, parent, size, counts, s);
 }
 
 }  // namespace nbc

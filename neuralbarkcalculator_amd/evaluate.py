@@ -114,6 +114,15 @@ reference's validation batch), the figures a training log holds.  ``--subset PAT
 only the named samples, in the file's order: the pooled figures mean ``val_miou`` only on the split they were logged for.
 Without the flags nothing changes.
 
+``--as_logged`` (with ``--frame training``) adds the other two figures of a training log as the log computed
+them: ``LovaszSoftmax()`` on a batch sorts the errors of all its images together (lovasz_losses.py:169-191), and ``PixelWiseF1``
+runs ``remove_small_zones`` on the ``[B,H,W]`` argmax, where connectivity=2 links zones of neighbouring images through the batch
+axis (utils.py:211-214).  Both need a whole group on one device: the shards are cut at group boundaries, each rank keeps the
+low-resolution logits and the framed dual of every evaluated image on its device and, after the loop, runs
+``FCNResNet50.lovasz_softmax_groups`` and ``remove_small_zones_groups`` group by group; ``summary["frame"]["as_logged"]`` holds
+``loss``, ``miou``, ``pixelwise_f1`` and the groups (``metrics.as_logged_over_groups``).  Every other file and key is what the
+run writes without the flag.
+
 The machinery is ``folder_run``'s, shared with the predict driver: equal-shape batches, ``streams`` batches in flight on their own HIP streams and
 model objects sharing one copy of the weights, contiguous pixel-balanced shards, ``--gpus N`` starting the ranks, the
 f16x2 calibration guard on the first image and the non-finite word riding back with every batch, and ``--precision auto``
@@ -127,7 +136,7 @@ import argparse
 import csv
 import json
 import os
-from typing import List, Tuple
+from typing import List, Sequence, Tuple
 
 import numpy as np
 
@@ -144,6 +153,8 @@ STATUS_TOO_SMALL = 4                             # --frame training: a pad that 
 TOO_SMALL = "too_small"                          # its reason: a key of summary["skipped"] only with the flag
 FRAMES = ("scan", "training")                    # --frame
 DEFAULT_POOL, MAX_POOL = 8, 64                   # --pool: the reference's valid_loader batches its test_dataset by 8
+GROUP_ROW_WIDTH = 17                             # --as_logged: (first global_idx, images, conf_clean[9], 3 f64 terms as int64, counts[3])
+AS_LOGGED_MAX_BYTES = 32 << 30                   # --as_logged: what a rank may hold on its device for it
 STATS_CSV = os.path.join("results", "evaluation_stats.csv")
 SUMMARY_JSON = os.path.join("results", "evaluation_summary.json")
 MATCHES_CSV, ZONE_EVALUATION_CSV = "zone_matches.csv", "zone_evaluation.csv"     # --zones, under results/
@@ -304,17 +315,17 @@ def check_calibration_arguments(calibration: bool, ece_bins=None) -> None:
         cal.check_ece_bins(ece_bins)
 
 
-def check_frame_arguments(frame="scan", frame_size=None, pool=None, target_size: int = 1024):
+def check_frame_arguments(frame="scan", frame_size=None, pool=None, target_size: int = 1024, as_logged: bool = False):
     """``ValueError`` for what ``--frame`` and its options refuse before any device is touched: an unknown frame,
-    ``--frame_size`` or ``--pool`` without ``--frame training``, a frame size outside ``8 .. target_size``, a pool outside
-    ``1 .. MAX_POOL``.  Returns ``(T, B)``: the side of the training frame and the images per pooled group, or ``(None, None)``
-    for ``frame="scan"``, today's behaviour."""
+    ``--frame_size``, ``--pool`` or ``--as_logged`` without ``--frame training``, a frame size outside ``8 .. target_size``, a
+    pool outside ``1 .. MAX_POOL``.  Returns ``(T, B)``: the side of the training frame and the images per pooled group, or
+    ``(None, None)`` for ``frame="scan"``, today's behaviour."""
     if frame is None:
         frame = "scan"
     if frame not in FRAMES:
         raise ValueError("--frame must be one of %s, got %r" % (", ".join(FRAMES), frame))
     if frame == "scan":
-        given = [n for n, v in (("--frame_size", frame_size), ("--pool", pool)) if v is not None]
+        given = [n for n, v in (("--frame_size", frame_size), ("--pool", pool), ("--as_logged", as_logged or None)) if v is not None]
         if given:
             raise ValueError("%s needs --frame training" % ", ".join(given))
         return None, None
@@ -339,6 +350,44 @@ def frame_status(h: int, w: int, size: int) -> int:
     except ValueError:
         return STATUS_TOO_SMALL
     return STATUS_OK
+
+
+def pooled_groups(ok: Sequence[bool], pool: int) -> Tuple[List[List[int]], List[int]]:
+    """The groups ``--pool`` forms, known before the loop: ``ok[i]`` says whether image i of the list passes the header checks.
+    Returns the groups (consecutive runs of ``pool`` such images, by list index) and, for ``folder_run.shard_by_units``, the
+    unit of every image of the list: its group's number, an image that is skipped going with the next group (the last one
+    when none follows)."""
+    good = [i for i, v in enumerate(ok) if v]
+    groups = [good[a:a + pool] for a in range(0, len(good), pool)]
+    unit, g = [], 0
+    for i in range(len(ok)):
+        while g + 1 < len(groups) and i > groups[g][-1]:
+            g += 1
+        unit.append(g)
+    return groups, unit
+
+
+def as_logged_bytes(images: int, size: int, pool: int) -> int:
+    """The device memory ``--as_logged`` holds on a rank whose shard has ``images`` evaluated frames of side ``size``: per image
+    the low-resolution logits (three f32 planes at the output stride of 8, an upper bound for the other networks) and the
+    framed dual, and for the pass over one group of ``pool`` frames after the loop its full logits (12 bytes per pixel), labels
+    (1), the two key arrays of ``lovasz_softmax_groups`` (24) and the workspace of ``remove_small_zones_groups`` (9)."""
+    low = (size + 7) // 8
+    return images * (12 * low * low + size * size) + min(pool, max(images, 1)) * size * size * (12 + 1 + 24 + 9)
+
+
+def as_logged_report(allrows, group_rows, pool: int) -> dict:
+    """The ``"as_logged"`` entry of the summary's ``"frame"`` from the gathered image rows and the gathered ``GROUP_ROW_WIDTH``
+    rows of the groups (in the order of their first image): ``metrics.as_logged_over_groups``, the raw confusion of a group
+    being the sum of its images' rows."""
+    done = [g for g in allrows if int(g[3]) == STATUS_OK]
+    group_rows = np.asarray(group_rows, dtype=np.int64).reshape(-1, GROUP_ROW_WIDTH)
+    raw = [np.sum([np.asarray(g[4:13], dtype=np.int64) for g in done[a:a + pool]], axis=0) for a in range(0, len(done), pool)]
+    if len(raw) != len(group_rows) or any(int(done[k * pool][0]) != int(g[0]) or len(done[k * pool:(k + 1) * pool]) != int(g[1])
+                                           for k, g in enumerate(group_rows)):
+        raise RuntimeError("--as_logged: the groups that ran are not the groups of the evaluated images")
+    return metrics.as_logged_over_groups(raw, group_rows[:, 2:11], np.ascontiguousarray(group_rows[:, 11:14]).view(np.float64),
+                                         group_rows[:, 14:17], group_rows[:, 1])
 
 
 def read_subset(path: str) -> List[str]:
@@ -525,7 +574,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None,
                     jitter=None, jitter_views=None, windows: int = None, windows_stride: int = None, windows_blend: str = None,
                     windows_compare: bool = False, frame: str = "scan", frame_size: int = None, pool: int = None,
-                    subset=None) -> dict:
+                    subset=None, as_logged: bool = False) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -569,12 +618,22 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     "pixelwise_f1", "groups"}``: the batch-pooled figures of ``metrics.pooled_over_groups`` over consecutive groups of ``pool``
     evaluated images in list order (default 8, 1..64), host arithmetic on rank 0 from the gathered rows.  ``frame="scan"``
     (default) is the behaviour without it; ``frame_size`` and ``pool`` are refused then.
+    ``as_logged`` (with ``frame="training"``; refused without): also the two figures of the training log that need a whole
+    group on one device.  The shards are cut at group boundaries (``pooled_groups``; membership is known from
+    the header reads), the rank keeps the low-resolution logits and the framed dual of every evaluated image on the device
+    (``as_logged_bytes``; a shard beyond ``AS_LOGGED_MAX_BYTES`` is refused before the loop) and, after the loop, on one stream
+    and group by group: upsample + argmax, ``lovasz_softmax_groups``, ``remove_small_zones_groups``, ``confusion``.  One
+    ``GROUP_ROW_WIDTH`` row per group travels to rank 0 and ``summary["frame"]`` gains ``"as_logged": {"loss", "miou",
+    "pixelwise_f1", "groups"}`` (``metrics.as_logged_over_groups``); everything else the run writes is what it writes without
+    the flag.  An image that passed the header checks but dropped out in the loop (a dual that decodes to another shape than
+    its header promised) would move every later group: the run then fails after the loop, on every rank alike, naming it.
     ``subset``: the path of a file with one ``wood_type/name`` per line, or such a list: only these samples are evaluated, in
     that order (``apply_subset``).
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
     import torch
     from . import zones as zn
-    FT, POOL = check_frame_arguments(frame, frame_size, pool, target_size)   # the training frame's side, None = off
+    FT, POOL = check_frame_arguments(frame, frame_size, pool, target_size, as_logged)   # the training frame's side, None = off
+    AL = bool(as_logged)
     Z = bool(zones)
     check_zone_match_arguments(Z, zones_cap, zone_pairs_cap, match_iou)     # refusals first: nothing has touched a device yet
     ZCAP = int(zones_cap) if zones_cap is not None else zn.DEFAULT_CAP
@@ -623,12 +682,37 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             m.contour_distances(plane, plane)
         if FT:                                       # the coefficient table of a resampled axis, uploaded before the loop
             m._frame_table(FT)
+        if AL and m is r.models[0]:                  # the pass after the loop runs on the first model object: its workspaces for one group
+            plane = torch.zeros((POOL, FT, FT), dtype=torch.uint8, device=dev)
+            m.remove_small_zones_groups(plane, POOL)
+            m.lovasz_softmax_groups(torch.zeros((POOL, 3, FT, FT), dtype=torch.float32, device=dev), plane, POOL)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
                         normalization=normalization)
 
-    sizes = folder_run.shard(r, items, lambda d: image_hw(d["src"]))
+    def header_status(gi, h, w):                     # what the header reads say of image gi
+        status = dual_status(items[gi], h, w, target_size)
+        if status == STATUS_OK and FT:
+            status = frame_status(h, w, FT)
+        return status
+
+    groups = header_ok = None
+    if AL:                                           # groups stay whole: the shards are cut between them
+        def units(sizes):
+            nonlocal groups, header_ok
+            header_ok = list(r.pool.map(lambda gi: header_status(gi, *sizes[gi]) == STATUS_OK, range(len(items))))
+            groups, unit = pooled_groups(header_ok, POOL)
+            return unit
+        sizes = folder_run.shard(r, items, lambda d: image_hw(d["src"]), units=units)
+        held = max(as_logged_bytes(sum(1 for gi in sh if header_ok[gi]), FT, POOL) for sh in r.shards)
+        if held > AS_LOGGED_MAX_BYTES:               # every rank sees every shard: all refuse alike, before any batch
+            r.pool.shutdown(wait=True, cancel_futures=True)
+            raise ValueError("--as_logged would hold %d bytes on one device (the bound is %d): use more ranks or a --subset"
+                             % (held, AS_LOGGED_MAX_BYTES))
+    else:
+        sizes = folder_run.shard(r, items, lambda d: image_hw(d["src"]))
     mine = r.mine
+    kept = {}                                        # --as_logged: k -> (low-resolution logits, framed dual) on the device
     rows = np.zeros((len(mine), ROW_WIDTH), dtype=np.int64)
     loss_rows = np.zeros((len(mine), LOSS_ROW_WIDTH), dtype=np.int64) if loss else None
     if loss:
@@ -641,9 +725,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         """Pool: the RGB frame and the grey dual of an image that can be evaluated; its status row and None otherwise."""
         gi = mine[k]
         h, w = sizes[gi]
-        status = dual_status(items[gi], h, w, target_size)
-        if status == STATUS_OK and FT:
-            status = frame_status(h, w, FT)
+        status = header_status(gi, h, w)
         if status == STATUS_OK:
             frame, grey = _decode_rgb(items[gi]["src"]), decode_dual(items[gi]["dual"])
             if grey.shape == frame.shape[:2]:
@@ -697,20 +779,26 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             x, tgt = mdl.training_frame(x, (FT, FT)), mdl.training_frame(tgt, (FT, FT))
         n, h, w = x.shape[:3]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
+        low_kw = dict(return_lowres=True) if AL else {}               # --as_logged: the merged low-resolution logits as well
         if T:                                                         # the same call on the mean of the flip views
-            labels, _ = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg)
+            labels, _, *low = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg, **low_kw)
         elif NV:                                                      # or of the colour views; each view's own final labels beside it
-            labels, _, _, _, _, vlow = mdl.predict_labels_jitter(x, J, labels_dtype=torch.uint8, logits_full=lg, return_views=True)
+            labels, _, *low, _, _, _, vlow = mdl.predict_labels_jitter(x, J, labels_dtype=torch.uint8, logits_full=lg,
+                                                                      return_views=True, **low_kw)
             vlab, _ = mdl.upsample_argmax(vlow.view((NV * n,) + tuple(vlow.shape[2:])), (h, w), labels_dtype=torch.uint8)
             mdl.remove_small_zones(vlab)
             jring[slot][:, :n].copy_(mdl.confusion(vlab, tgt.repeat(NV, 1, 1)).view(NV, n, 3, 3), non_blocking=True)
         elif WN is not None:                                          # or on the blend of the crop windows
-            labels, _ = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, labels_dtype=torch.uint8, logits_full=lg)
+            labels, _, *low = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, labels_dtype=torch.uint8, logits_full=lg,
+                                                         **low_kw)
             if WC:                                                    # the plain forward's final labels beside it
                 plab, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, small_zones=True)
                 wring[slot][:n].copy_(mdl.confusion(plab, tgt), non_blocking=True)
         else:
-            labels, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg)   # __main__.py:323
+            labels, _, *low = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg, **low_kw)   # __main__.py:323
+        if AL:                                                        # copies of their own: nothing of the batch stays alive for them
+            for j, k in enumerate(part):
+                kept[k] = (low[0][j].clone(), tgt[j].clone())
         conf_raw = mdl.confusion(labels, tgt)                         # iou: the raw argmax (:331)
         if ce:                                                        # CustomWeightedCrossEntropy (utils.py:151-165)
             sums, _ = mdl.pixel_cross_entropy(lg, tgt)
@@ -793,7 +881,39 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         return rgb
 
     folder_run.run_loop(r, window, prepare, launch, consume, first_frame, calibrate, bytes_per_pixel=(3, 1))
+    group_rows = None
+    if AL:                                           # the loop has drained (run_loop synchronises): one stream from here on
+        local = {gi: k for k, gi in enumerate(mine)}
+        whole = all(rows[k, 3] == STATUS_OK for k, gi in enumerate(mine) if header_ok[gi])
+        todo = [g for g in groups if g[0] in local] if whole else []   # a drop-out moves the groups: the run fails below
+        group_rows = np.zeros((len(todo), GROUP_ROW_WIDTH), dtype=np.int64)
+        mdl = r.models[0]
+        with torch.cuda.stream(r.gpu_streams[0]):
+            for i, g in enumerate(todo):
+                low = torch.stack([kept[local[gi]][0] for gi in g])
+                tgt = torch.stack([kept[local[gi]][1] for gi in g])
+                lg = torch.empty((len(g), 3, FT, FT), dtype=torch.float32, device=dev)
+                labels, _ = mdl.upsample_argmax(low, (FT, FT), labels_dtype=torch.uint8, logits_full=lg)   # the loop's own bits
+                terms, counts = mdl.lovasz_softmax_groups(lg, tgt, len(g))                                 # LovaszSoftmax on the batch
+                mdl.remove_small_zones_groups(labels, len(g))                                             # PixelWiseF1 (utils.py:211-214)
+                clean = mdl.confusion(labels, tgt).sum(dim=0)
+                group_rows[i, 0], group_rows[i, 1] = g[0], len(g)
+                group_rows[i, 2:11] = clean.reshape(-1).cpu().numpy()
+                group_rows[i, 11:14] = terms[0].cpu().numpy().view(np.int64)
+                group_rows[i, 14:17] = counts[0].cpu().numpy()
+        torch.cuda.synchronize(dev)
+        kept.clear()
     allrows = folder_run.gather(r, rows, ROW_WIDTH)
+    if AL:                                           # every rank holds every row: all of them fail alike
+        dropped = [int(g[0]) for g in allrows if header_ok[int(g[0])] and int(g[3]) != STATUS_OK]
+        all_groups = folder_run.gather_ragged(group_rows, r.world, r.dist, r.wire_dev, width=GROUP_ROW_WIDTH)
+        if dropped:
+            if r.dist is not None:
+                r.dist.barrier()
+            raise RuntimeError("--as_logged: %s passed the header checks but could not be evaluated (%s): every later group "
+                               "would move; take the sample out with --subset" % (
+                                   ", ".join(items[gi]["wood"] + "/" + items[gi]["name"] for gi in dropped),
+                                   ", ".join(sorted({SKIP_REASONS.get(int(g[3]), TOO_SMALL) for g in allrows if int(g[0]) in dropped}))))
     all_loss = folder_run.gather(r, loss_rows, LOSS_ROW_WIDTH) if loss else None
     all_ce = folder_run.gather(r, ce_rows, CE_ROW_WIDTH) if ce else None
     all_zones = n_fallbacks = None
@@ -835,6 +955,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             summary["calibration"] = write_calibration_report(os.path.join(root, "results"), items, allrows, all_cal, all_census, EB)
         if FT:
             summary["frame"] = frame_report(allrows, FT, POOL)
+        if AL:
+            summary["frame"]["as_logged"] = as_logged_report(allrows, all_groups, POOL)
         if T:
             summary["tta"] = {"views": folder_run.tta_view_names(T)}
         if NV:
@@ -909,6 +1031,10 @@ def format_summary(summary: dict) -> str:
         lines.append("on the training's %d x %d frame (%d images resampled along rows, %d along columns); pooled over groups of "
                      "%d: miou %s, pixelwise_f1 %s" % (fr["size"], fr["size"], fr["resampled_rows"], fr["resampled_cols"], fr["pool"],
                                                        fmt(fr["miou"]), fmt(fr["pixelwise_f1"])))
+        if fr.get("as_logged"):
+            al = fr["as_logged"]
+            lines.append("as the training logged it (the loss and the small zones of each group as one batch): loss %s, miou %s, "
+                         "pixelwise_f1 %s" % ("-" if al["loss"] is None else "%.6f" % al["loss"], fmt(al["miou"]), fmt(al["pixelwise_f1"])))
     if summary.get("jitter"):
         for name, entry in summary["jitter"]["evaluation"].items():
             f, d = entry["figures"], entry["difference"]
@@ -982,6 +1108,13 @@ def main(argv=None):
     ap.add_argument("--pool", type=int, default=None, metavar="B",
                     help="with --frame training: the images per pooled group, in list order, 1..64 (default 8, the reference's "
                          "validation batch)")
+    ap.add_argument("--as_logged", action="store_true",
+                    help="with --frame training: also the loss and the PixelWiseF1 exactly as a training run logged them, each group "
+                         "of --pool frames as one batch (the Lovasz-Softmax loss sorts the errors of the whole group; "
+                         "remove_small_zones links zones of neighbouring frames of a group); summary[\"frame\"][\"as_logged\"].  Holds "
+                         "the low-resolution logits and the framed dual of every evaluated frame of a rank's shard on its device "
+                         "until the loop ends (1.2 MB per frame at T = 1024) and about 46 bytes per pixel of one group after it "
+                         "(0.4 GB at --pool 8, 3.1 GB at 64); a shard that would need more than 32 GiB is refused")
     ap.add_argument("--subset", default=None, metavar="PATH",
                     help="evaluate only the samples this file names, one wood_type/name per line, in the file's order")
     ap.add_argument("--exclude_nodes", action="store_true", help=argparse.SUPPRESS)
@@ -995,7 +1128,7 @@ def main(argv=None):
         folder_run.check_jitter_arguments(args.jitter, args.jitter_views, tta=args.tta)
         folder_run.check_windows_arguments(args.windows, args.windows_stride, args.windows_blend, args.windows_compare, args.tta,
                                            args.jitter, args.jitter_views, bn_stats=args.bn_stats, arch=args.arch)
-        check_frame_arguments(args.frame, args.frame_size, args.pool)
+        check_frame_arguments(args.frame, args.frame_size, args.pool, as_logged=args.as_logged)
         if args.subset is not None:
             apply_subset(list_labelled(args.root_path), read_subset(args.subset))
     except (OSError, ValueError) as e:
@@ -1040,6 +1173,8 @@ def main(argv=None):
                   windows_compare=args.windows_compare)
     if args.frame != "scan":
         kw.update(frame=args.frame, frame_size=args.frame_size, pool=args.pool)
+        if args.as_logged:
+            kw["as_logged"] = True
     if args.subset is not None:
         kw["subset"] = args.subset
     if args.normalization is not None:

@@ -88,6 +88,22 @@ def shard_by_pixels(pixels: Sequence[int], world: int) -> List[List[int]]:
     return shards
 
 
+def shard_by_units(pixels: Sequence[int], unit_of: Sequence[int], world: int) -> List[List[int]]:
+    """``shard_by_pixels`` in units that must not be cut: ``unit_of[i]`` is the unit of image i, non-decreasing along the list.
+    The units are balanced by their summed pixels; every rank gets a contiguous range of whole units."""
+    if len(pixels) != len(unit_of) or any(b < a for a, b in zip(unit_of, unit_of[1:])):
+        raise ValueError("one unit per image, non-decreasing along the list")
+    members = {}
+    for i, u in enumerate(unit_of):
+        members.setdefault(u, []).append(i)
+    order = sorted(members)
+    shards: List[List[int]] = [[] for _ in range(world)]
+    for rank, units in enumerate(shard_by_pixels([sum(pixels[i] for i in members[u]) for u in order], world)):
+        for j in units:
+            shards[rank].extend(members[order[j]])
+    return shards
+
+
 def windows(n: int, window: int) -> List[List[int]]:
     """The local images 0..n-1 in windows of ``window``, in order: the pool works one window ahead of the GPU."""
     return [list(range(a, min(a + window, n))) for a in range(0, n, window)]
@@ -821,15 +837,20 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
     r.t_ready = time.perf_counter()
 
 
-def shard(r, items: Sequence, size_of) -> list:
+def shard(r, items: Sequence, size_of, units=None) -> list:
     """Starts the host pool (``r.pool``) and cuts ``items`` into contiguous, pixel-balanced shards by ``size_of(item)`` ->
-    ``(h, w)`` (a header read, on the pool); ``r.mine``: this rank's global indices.  Returns every item's size."""
+    ``(h, w)`` (a header read, on the pool); ``r.mine``: this rank's global indices; ``r.shards``: every rank's.  ``units``:
+    ``units(sizes)`` -> the unit of every item (``shard_by_units``: a unit stays on one rank), called once the pool runs and
+    the sizes are known.  Returns every item's size."""
     from concurrent.futures import ThreadPoolExecutor
     r.workers = _host_workers()
     r.pool = ThreadPoolExecutor(max_workers=r.workers)
     sizes = list(r.pool.map(size_of, items))
-    shards = shard_by_pixels([h * w for h, w in sizes], r.world)
-    r.n_total, r.mine, r.cap = len(items), shards[r.rank], max(len(s) for s in shards)
+    if units is None:
+        shards = shard_by_pixels([h * w for h, w in sizes], r.world)
+    else:
+        shards = shard_by_units([h * w for h, w in sizes], units(sizes), r.world)
+    r.n_total, r.mine, r.cap, r.shards = len(items), shards[r.rank], max(len(s) for s in shards), shards
     return sizes
 
 

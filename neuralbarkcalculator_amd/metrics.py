@@ -24,6 +24,10 @@ device):
   ``MixedLoss`` (utils.py:185-192).  Two or three trailing CSV columns, written with ``repr``.
 * The percent columns: float32 ``count / (H W) * 100`` with ``'{:.5f}'`` (``__main__.py:392-398``), like
   ``predict.stats_row``; "Output" from the raw argmax, "Target" from the target.
+* The figures of a training log (``evaluate --frame training --pool B [--as_logged]``): ``pooled_over_groups`` from per-image
+  confusions; ``as_logged_over_groups`` from per-group rows, where the loss is ``lovasz_loss`` of the group's pooled terms
+  (``FCNResNet50.lovasz_softmax_groups``) and the clean confusion comes from ``remove_small_zones`` on the group's ``[B,H,W]``
+  array (``remove_small_zones_groups``).
 """
 from __future__ import annotations
 
@@ -262,3 +266,31 @@ def pooled_over_groups(confs_raw, confs_clean, pool: int) -> dict:
     n = len(raw)
     mean = lambda key: (_fsum(g[key] * g["images"] for g in groups) / n) if n else None
     return {"pool": pool, "miou": mean("miou"), "pixelwise_f1": mean("pixelwise_f1"), "groups": groups}
+
+
+def as_logged_over_groups(confs_raw, confs_clean, terms, counts, sizes) -> dict:
+    """The three figures a training run of the reference logs per epoch (loss, ``miou``, ``PixelWiseF1``; ``evaluate --frame
+    training --pool B --as_logged``), from one row per group: the group's summed raw-argmax confusion, the confusion of its
+    labels after ``remove_small_zones`` on the group's ``[B,H,W]`` array (``remove_small_zones_groups``), the three Lovasz terms
+    and class counts of the group (``lovasz_softmax_groups``) and its number of images.  A group's loss is ``lovasz_loss`` of
+    its terms and counts -- a class present in one image of the group is present for the group --, its ``miou`` is
+    ``pooled_miou`` and its ``pixelwise_f1`` is ``pooled_f1``.  Each figure of the folder is the mean over the groups weighted
+    by group size, as ``pooled_over_groups`` weights.  Returns ``{"loss", "miou", "pixelwise_f1", "groups"}``; the figures
+    are None when there is no group."""
+    raw = np.asarray(confs_raw, dtype=np.int64).reshape(-1, 3, 3)
+    clean = np.asarray(confs_clean, dtype=np.int64).reshape(-1, 3, 3)
+    terms = np.asarray(terms, dtype=np.float64).reshape(-1, 3)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 3)
+    sizes = [int(v) for v in np.asarray(sizes).reshape(-1)]
+    if not (len(raw) == len(clean) == len(terms) == len(counts) == len(sizes)):
+        raise ValueError("one raw confusion, clean confusion, terms, counts and size per group")
+    if any(v < 1 for v in sizes):
+        raise ValueError("a group holds at least one image")
+    groups = []
+    for g in range(len(sizes)):
+        groups.append({"images": sizes[g], "loss": float(lovasz_loss(terms[g], counts[g])),
+                       "loss_terms": [float(v) for v in terms[g]], "present": [bool(v > 0) for v in counts[g]],
+                       "miou": pooled_miou(raw[g]), "pixelwise_f1": pooled_f1(clean[g])})
+    n = sum(sizes)
+    mean = lambda key: (_fsum(g[key] * g["images"] for g in groups) / n) if n else None
+    return {"loss": mean("loss"), "miou": mean("miou"), "pixelwise_f1": mean("pixelwise_f1"), "groups": groups}

@@ -827,6 +827,39 @@ class FCNResNet50:
                                                         counts.data_ptr(), cur.cuda_stream), "nbc_remove_small_zones")
         return labels, counts
 
+    def remove_small_zones_groups(self, labels: torch.Tensor, group: int, min_pixels: int = 150):
+        """``utils.remove_small_zones`` on batches as the reference's ``PixelWiseF1`` runs it (utils.py:211-214) on the device
+        (nbc_remove_small_zones_groups), IN PLACE on ``labels`` (contiguous uint8 or int64 ``[N,H,W]`` on this model's
+        device): consecutive groups of ``group`` images (the last may be shorter) are volumes in which a pixel also touches
+        the pixel at its place in the image before and after and that pixel's four edge neighbours (skimage's
+        ``connectivity=2`` on a 3-D array), and ``min_pixels`` counts a zone over all its images.  ``group`` in 1..64 with
+        ``min(group, N) * H * W < 2^31``; 1 is ``remove_small_zones``.  Runs on the current stream; the workspace is the
+        context's.  Returns ``(labels, counts int64 [N,3])`` with the pixels per class of every image of the result."""
+        self._require_ctx()
+        self._check_labels(labels)
+        if labels.dim() != 3 or labels.numel() == 0:
+            raise ValueError("labels must be a non-empty [N,H,W]")
+        n, h, w = (int(v) for v in labels.shape)
+        group = self._check_group(group, n, h, w)
+        if int(min_pixels) < 0:
+            raise ValueError("min_pixels must be >= 0, got %r" % (min_pixels,))
+        counts = torch.empty((n, 3), dtype=torch.int64, device=self.device)
+        with self._on_stream() as cur:
+            _lib.check(self._lib.nbc_remove_small_zones_groups(self._ctx, labels.data_ptr(),
+                                                               _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+                                                               n, h, w, group, int(min_pixels), counts.data_ptr(), cur.cuda_stream),
+                       "nbc_remove_small_zones_groups")
+        return labels, counts
+
+    @staticmethod
+    def _check_group(group, n: int, h: int, w: int) -> int:
+        """``group`` as the grouped passes take it: an int in 1..64 whose volume of ``min(group, n)`` images is indexable."""
+        if isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= 64:
+            raise ValueError("group must be an int in 1..64, got %r" % (group,))
+        if min(group, n) * h * w >= 2 ** 31:
+            raise ValueError("a group of %d [%d,%d] images has 2^31 pixels or more" % (min(group, n), h, w))
+        return group
+
     def label_zones(self, labels: torch.Tensor, cap: int = 1024) -> Tuple[torch.Tensor, torch.Tensor]:
         """The zones of label maps on the device (nbc_label_zones; include/nbc.h, csrc/zones.hip): the 8-connected components
         of each class in {1, 2}, one row of ten integers per zone (``zones.ZONE_FIELDS``: first pixel ``y * W + x``, class,
@@ -972,6 +1005,32 @@ class FCNResNet50:
             _lib.check(self._lib.nbc_lovasz_softmax(logits_full.data_ptr(), target.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(),
                                                     terms.data_ptr(), fg_counts.data_ptr(), cur.cuda_stream), "nbc_lovasz_softmax")
         return terms, fg_counts
+
+    def lovasz_softmax_groups(self, logits_full: torch.Tensor, target: torch.Tensor, group: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The Lovasz-Softmax terms of batches on the device (nbc_lovasz_softmax_groups): ``LovaszSoftmax()`` on a batch runs
+        with ``per_image=False`` (lovasz_losses.py:169-191) and sorts the errors of all its images together, per class --
+        ``val_loss`` / ``test_loss`` of the training log.  ``logits_full`` and ``target`` as ``lovasz_softmax`` takes them;
+        images form consecutive groups of ``group`` (1..64, the last may be shorter).  Runs on the current stream; shares
+        ``lovasz_softmax``'s cached workspace.  Returns ``(terms f64 [NG,3], counts int64 [NG,3])`` for the ``NG =
+        ceil(N / group)`` groups: a group's terms are bit for bit ``lovasz_softmax`` of its images stacked along the height; a
+        class present in one image is present for its group; a non-finite softmax makes its own group's terms NaN.
+        ``metrics.lovasz_loss`` takes a group's mean over the present classes."""
+        self._require_ctx()
+        n, h, w = self._check_logits_target(logits_full, target)
+        group = self._check_group(group, n, h, w)
+        need = int(self._lib.nbc_lovasz_groups_workspace_bytes(n, h, w, group))
+        if need == 0:
+            raise ValueError("nbc_lovasz_softmax_groups refuses a [%d,3,%d,%d] batch in groups of %d (N <= 65535, g * H * W < 2^31)"
+                             % (n, h, w, group))
+        ng = (n + group - 1) // group
+        terms = torch.empty((ng, NUM_CLASSES), dtype=torch.float64, device=self.device)
+        counts = torch.empty((ng, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_lovasz_ws", need, cur)
+            _lib.check(self._lib.nbc_lovasz_softmax_groups(logits_full.data_ptr(), target.data_ptr(), n, h, w, group, ws.data_ptr(),
+                                                           ws.numel(), terms.data_ptr(), counts.data_ptr(), cur.cuda_stream),
+                       "nbc_lovasz_softmax_groups")
+        return terms, counts
 
     def pixel_cross_entropy(self, logits_full: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Per-image cross-entropy sums on the device (nbc_pixel_cross_entropy): what ``CustomWeightedCrossEntropy``
