@@ -540,6 +540,41 @@ int nbc_softmax_census(const float* logits_full_dev, const uint8_t* target_dev, 
                        void* workspace_dev, size_t workspace_bytes, uint64_t* rows_dev, uint8_t* confidence_dev,
                        void* hip_stream);
 
+/* The operating-point sweep: the 3 x 3 confusion of the label map at every point of a grid of (bark offset, node offset)
+ * pairs, from one pass over the full-resolution logits.  The checkpoints were trained with class weights (get_pos_weight,
+ * utils.py:72-73); the standard correction is a constant per class added to the logits before the argmax, and this call
+ * counts what every such pair would label.  No context: csrc/offset_sweep.hip.  The definition, per pixel of image n with
+ * f32 logits x0, x1, x2 and target class t (round(2 * float32(v) / 255) of its grey level, as nbc_confusion derives it):
+ *   the decision at (i, j) is k = argmax(x0, x1 (+) bark_offsets[i], x2 (+) node_offsets[j]), (+) one f32 addition, the
+ *   argmax nbc_forward's (the first maximum wins, a NaN counts as the maximum); class 0's logit is never touched;
+ *   conf[n][i][j][t][p] counts the pixels of target class t whose decision at (i, j) is p.
+ * Non-finite logits decide like any other, so the nine cells of every grid point sum to H * W; at a point with both offsets
+ * 0 the table is nbc_confusion of the labels nbc_forward made from the same logits.  The row layout: conf_dev is
+ * uint64 [N][G1][G2][3][3], cell (t, p) of point (i, j) of image n at ((n * G1 + i) * G2 + j) * 9 + t * 3 + p.
+ * logits_full_dev    float32 [N,3,H,W], what nbc_forward writes to logits_full_dev; any 4-byte alignment (16-byte loads
+ *                    where an image's planes start on 16-byte boundaries)
+ * target_dev         uint8 [N,H,W] grey levels
+ * bark_offsets_host  G1 finite f32 values, strictly ascending, host memory, read before the call returns; 1 <= G1 <= 33
+ * node_offsets_host  G2 of the same; 1 <= G2 <= 33.  The values travel as kernel arguments.
+ * workspace_dev      at least nbc_offset_sweep_workspace_bytes(N, H, W, G1, G2) bytes of device memory, 256-byte aligned
+ * conf_dev           overwritten
+ * For a pixel and an i the decision along j is argmax(x0, x1 (+) bark_offsets[i]) up to some index and 2 from there on (f32
+ * addition is monotone in the addend; class 2 wins on a strict > only); the kernel counts that one switch index per
+ * (pixel, i).  Integer sums only (LDS integer atomics inside a tile, per-tile partials in the workspace, tiles added by a
+ * second launch; no float atomics, no memset): an image's table is bit-identical alone, anywhere in a batch and on any
+ * stream.  Runs on hip_stream (the caller's current device); no synchronisation.  NBC_ERR_INVALID, before any HIP call: a
+ * null pointer, N < 1 or N > 65535, H or W < 1, H * W >= 2^31, G1 or G2 outside 1..33, an offset that is not finite, a list
+ * that is not strictly ascending, or a workspace too small or misaligned.  With P = H * W, T = ceil(P / 4096) and A(x) = x
+ * rounded up to a multiple of 256, the workspace is
+ *   A(12 G1 (G2 + 1) N T) bytes
+ * (per image and tile: G1 * 6 * (G2 + 1) 16-bit counts); nbc_offset_sweep_workspace_bytes returns 0 for a shape or a grid
+ * nbc_offset_sweep refuses.  Messages begin "nbc_offset_sweep:". */
+#define NBC_SWEEP_MAX_GRID 33
+size_t nbc_offset_sweep_workspace_bytes(int N, int H, int W, int G1, int G2);
+int nbc_offset_sweep(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W,
+                     const float* bark_offsets_host, int G1, const float* node_offsets_host, int G2,
+                     void* workspace_dev, size_t workspace_bytes, uint64_t* conf_dev, void* hip_stream);
+
 /* ---- the shipped tool's live Dropout --------------------------------------------------------
  * FCNHead's Dropout(0.1) (models.py:113-124) sits behind the 3x3 head convolution and in front of classifier.4, and the
  * shipped predict.py never calls .eval(): every number it wrote is one random draw of that mask.  torch's CPU random stream
@@ -993,6 +1028,16 @@ int nbc_nonfinite_seen(nbc_ctx* ctx, int reset);
  * memory is staged and may block, which is what this call exists to avoid -- NBC_ERR_INVALID otherwise.  The folder driver sends it along with every batch's labels, so that an f16x2 run of
  * weights that mode cannot carry is abandoned at the first batch that shows it, not after the last. */
 int nbc_nonfinite_peek_async(nbc_ctx* ctx, uint32_t* host_dst, void* hip_stream);
+
+/* ---- the operating point ----------------------------------------------------------------- */
+/* Logit offsets: with (bark, node) set, the upsample + argmax launch of nbc_forward and nbc_upsample_argmax decides by
+ * k = argmax(x0, x1 (+) bark, x2 (+) node) -- the decision nbc_offset_sweep counts, (+) one f32 addition -- instead of the plain
+ * argmax; the launch counts and remaps (exclude_nodes) after the decision, and everything downstream sees it.  Only the
+ * decision moves: logits_lowres_dev and logits_full_dev receive the values they receive without offsets, and class 0's
+ * logit is never touched.  (0, 0) is off, the default: the context then launches exactly the kernels it launched before
+ * (the offset forms are kernels of their own).  Finite values only (NBC_ERR_INVALID otherwise).  nbc_dropout_draws and
+ * nbc_dropout_votes answer NBC_ERR_INVALID on a context with offsets on: the draws have a tail of their own. */
+int nbc_set_logit_offsets(nbc_ctx* ctx, float bark, float node);
 
 /* ---- debugging / measurement ----------------------------------------------------------- */
 /* NBC_PREC_F16X2: the first bottleneck of a ResNet stage computes its downsample.0 inside the launch of the conv3 that

@@ -34,6 +34,7 @@ JITTER_MAX_VIEWS = 16                               # NBC_JITTER_MAX_VIEWS
 WINDOW_CELL, WINDOW_MAX_K = 8, 1024                 # NBC_WINDOW_CELL, NBC_WINDOW_MAX_K
 BLEND_TENT, BLEND_UNIFORM = 0, 1                    # NBC_BLEND_*
 FRAME_TAPS = 3                                      # NBC_FRAME_TAPS
+SWEEP_MAX_GRID = 33                                 # NBC_SWEEP_MAX_GRID
 
 
 class NbcTensor(C.Structure):
@@ -130,6 +131,10 @@ SIGNATURES = {
     "nbc_softmax_census_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_softmax_census": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "nbc_offset_sweep_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nbc_offset_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                   C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "nbc_set_logit_offsets": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "nbc_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_double, C.c_uint64, C.c_size_t, C.c_void_p]),
     "nbc_dropout_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nbc_dropout_draws": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int,

@@ -68,6 +68,8 @@ struct nbc_ctx {
   int conv_tile = -1;                       // tile override, -1 = per-layer choice
   bool fuse_downsample = true;              // nbc_set_fuse_downsample
   int fused_pairs = 0;                      // (downsample.0, conv3) pairs the last forward ran as one launch
+  float logit_offsets[2] = {0.f, 0.f};      // nbc_set_logit_offsets: added to the bark and node logits of the decision alone
+  bool offsets_on = false;                  // either one is not zero: the upsample + argmax launch takes its offset kernels
   bool keep = false;
   bool profiling = false;
   // profiling: one event set (nops+1 events) per profiled forward, read back lazily so that the
@@ -530,6 +532,15 @@ int nbc_set_fuse_downsample(nbc_ctx* c, int on) {
   return NBC_OK;
 }
 
+int nbc_set_logit_offsets(nbc_ctx* c, float bark, float node) {
+  if (!std::isfinite(bark) || !std::isfinite(node)) return set_error(NBC_ERR_INVALID, "nbc_set_logit_offsets: the offsets must be finite");
+  if (!c) return set_error(NBC_ERR_INVALID, "nbc_set_logit_offsets: null context");
+  c->logit_offsets[0] = bark;
+  c->logit_offsets[1] = node;
+  c->offsets_on = bark != 0.f || node != 0.f;
+  return NBC_OK;
+}
+
 int nbc_fused_pairs(nbc_ctx* c) {
   if (!c) return set_error(NBC_ERR_INVALID, "null context");
   return c->fused_pairs;
@@ -777,7 +788,8 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
         if (logits_full_dev || labels_dev || counts_dev)
           e = launch_upsample_argmax(lowres, N, P.h, P.w, H, W, logits_full_dev, labels_dev,
                                      labels_dtype == NBC_LABEL_I64 ? 1 : 0,
-                                     reinterpret_cast<unsigned long long*>(counts_dev), exclude_nodes, s);
+                                     reinterpret_cast<unsigned long long*>(counts_dev), exclude_nodes, s,
+                                     c->offsets_on ? c->logit_offsets : nullptr);
         break;
     }
     if (e != hipSuccess)
@@ -851,6 +863,8 @@ static int dropout_passes(const char* who, nbc_ctx* c, int N, int H, int W, cons
   if (min_pixels < 0) return refuse(NBC_ERR_INVALID, "min_pixels must not be negative");
   if (!c || !image_ids_host || !counts_dev || !workspace_dev || (with_votes && !votes_dev)) return refuse(NBC_ERR_INVALID, "null argument");
   if (with_votes && reinterpret_cast<uintptr_t>(votes_dev) % 16 != 0) return refuse(NBC_ERR_INVALID, "votes_dev must be 16-byte aligned");
+  if (c->offsets_on)
+    return refuse(NBC_ERR_INVALID, "the context holds logit offsets (nbc_set_logit_offsets); the draws decide by the plain argmax");
   if (c->arch != kArchFcn)
     return refuse(NBC_ERR_STATE, std::string("NBC_ARCH_FCN_RESNET50 only, the context holds ") + arch_name(c->arch) +
                                      " (DeepLabHead's Dropout sits inside ASPP; the EfficientNet heads are left out)");
@@ -991,7 +1005,8 @@ int nbc_upsample_argmax(nbc_ctx* c, const float* lowres, int N, int h, int w, in
   if (counts_dev) NBC_HIP(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 3 * N, s));
   NBC_HIP(launch_upsample_argmax(lowres, N, h, w, H, W, logits_full_dev, labels_dev,
                                  labels_dtype == NBC_LABEL_I64 ? 1 : 0,
-                                 reinterpret_cast<unsigned long long*>(counts_dev), exclude_nodes, s));
+                                 reinterpret_cast<unsigned long long*>(counts_dev), exclude_nodes, s,
+                                 c->offsets_on ? c->logit_offsets : nullptr));
   return NBC_OK;
 }
 

@@ -177,10 +177,11 @@ hipError_t launch_gate_weights(const float* w, const float* gate, float* wg, int
 // y = swish(y) in place, elems a multiple of 4
 hipError_t launch_swish(float* y, size_t elems, hipStream_t s);
 // Bicubic (A=-0.75, align_corners=False) upsample of f32 NCHW [N,3,h,w] to HxW, fused with the
-// per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.
+// per-pixel argmax, the optional 2->1 remap and the per-class pixel counts.  `offsets` (null = the plain argmax and the plain
+// kernels): the pair nbc_set_logit_offsets holds, added to the bark and the node logit of the decision alone.
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,
                                   float* logits_full, void* labels, int labels_i64,
-                                  unsigned long long* counts, int exclude_nodes, hipStream_t s);
+                                  unsigned long long* counts, int exclude_nodes, hipStream_t s, const float* offsets = nullptr);
 // remove_small_zones (utils.py:135-148) in place on device labels (u8 or i64, [N,H,W]): 8-connected
 // components below min_pixels of the non-background, then of the filled background, flip; optional
 // 2 -> 1 remap and per-class counts afterwards.  Workspaces: bg N*H*W bytes, parent and size N*H*W ints.

@@ -405,6 +405,123 @@ __global__ __launch_bounds__(256) void upsample_argmax_tiled_kernel(
   if (counts) add_class_counts(cnt, blk_counts, counts + (size_t)img * 3);
 }
 
+// ---- the same launch with the decision moved (nbc_set_logit_offsets): k = argmax3(x0, x1 + bark, x2 + node), one f32 addition
+// each, class 0 never touched.  logits_full receives the values it receives above; the remap and the counts follow the
+// decision.  These are kernels of their own, their text the two kernels' above with `decide_offsets` for the argmax: as one
+// template over the decision, the plain forms came out of the compiler with other machine code (the schedule moved as it does
+// for the calls described above), and a context without offsets must launch what it launched before.
+__device__ __forceinline__ int decide_offsets(float x0, float x1, float x2, float bark, float node) {
+  return argmax3(x0, __fadd_rn(x1, bark), __fadd_rn(x2, node));
+}
+
+__global__ __launch_bounds__(256) void upsample_argmax_offsets_kernel(
+    const float* __restrict__ lowres, int h, int w, int H, int W, float scale_y, float scale_x,
+    float* __restrict__ logits_full, void* __restrict__ labels, int labels_i64,
+    unsigned long long* __restrict__ counts, int exclude_nodes, float bark, float node) {
+  __shared__ unsigned blk_counts[3];
+  if (threadIdx.x < 3) blk_counts[threadIdx.x] = 0;
+  __syncthreads();
+  const int ox = blockIdx.x * 256 + threadIdx.x;
+  const int oy = blockIdx.y;
+  const int img = blockIdx.z;
+  unsigned cnt[3] = {0, 0, 0};
+  if (ox < W) {
+    int iy[4], ix[4];
+    float cy[4], cx[4];
+    cubic_setup(oy, scale_y, h, iy, cy);
+    cubic_setup(ox, scale_x, w, ix, cx);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* src = lowres + ((size_t)img * 3 + c) * h * w;
+      float t[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float* row = src + (size_t)iy[j] * w;
+        t[j] = cubic_dot4(row[ix[0]], row[ix[1]], row[ix[2]], row[ix[3]], cx);
+      }
+      v[c] = cubic_dot4(t[0], t[1], t[2], t[3], cy);
+      if (logits_full) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = v[c];
+    }
+    emit_label(decide_offsets(v[0], v[1], v[2], bark, node), exclude_nodes, true, labels, labels_i64, ((size_t)img * H + oy) * W + ox, cnt);
+  }
+  if (counts) add_class_counts(cnt, blk_counts, counts + (size_t)img * 3);
+}
+
+template <int UP_ROWS>
+__global__ __launch_bounds__(256) void upsample_argmax_tiled_offsets_kernel(
+    const float* __restrict__ lowres, int h, int w, int H, int W, float scale_y, float scale_x,
+    float* __restrict__ logits_full, void* __restrict__ labels, int labels_i64,
+    unsigned long long* __restrict__ counts, int exclude_nodes, float bark, float node) {
+  __shared__ float win[3][UP_WIN_R][UP_WIN_C];
+  __shared__ float hsum[3][UP_WIN_R][256];
+  __shared__ unsigned int blk_counts[3];
+  const int tid = threadIdx.x;
+  const int ox0 = blockIdx.x * 256, oy0 = blockIdx.y * UP_ROWS, img = blockIdx.z;
+  if (tid < 3) blk_counts[tid] = 0;
+  int ti[4];
+  float tc[4];
+  cubic_setup(oy0, scale_y, h, ti, tc);
+  const int wy0 = ti[0];
+  cubic_setup(ox0, scale_x, w, ti, tc);
+  const int wx0 = ti[0];
+  constexpr int WIN_ELEMS = 3 * UP_WIN_R * UP_WIN_C, WIN_ITERS = (WIN_ELEMS + 255) / 256;
+  float wv[WIN_ITERS];
+#pragma unroll
+  for (int it = 0; it < WIN_ITERS; ++it) {
+    const int e = min(tid + it * 256, WIN_ELEMS - 1);
+    const int c = e / (UP_WIN_R * UP_WIN_C);
+    const int rem = e - c * (UP_WIN_R * UP_WIN_C);
+    const int rr = rem / UP_WIN_C, cc = rem - rr * UP_WIN_C;
+    const int sy = min(wy0 + rr, h - 1), sx = min(wx0 + cc, w - 1);
+    wv[it] = lowres[(((size_t)img * 3 + c) * h + sy) * w + sx];
+  }
+#pragma unroll
+  for (int it = 0; it < WIN_ITERS; ++it) {
+    const int e = tid + it * 256;
+    if (e < WIN_ELEMS) (&win[0][0][0])[e] = wv[it];
+  }
+  __syncthreads();
+  const int ox = ox0 + tid;
+  const bool live_x = ox < W;
+  int ix[4];
+  float cx[4];
+  cubic_setup(live_x ? ox : W - 1, scale_x, w, ix, cx);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ix[k] -= wx0;
+  cubic_setup(min(oy0 + UP_ROWS - 1, H - 1), scale_y, h, ti, tc);
+  const int nrows = ti[3] - wy0 + 1;
+  for (int rr = 0; rr < nrows; ++rr) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* rowp = win[c][rr];
+      hsum[c][rr][tid] = cubic_dot4(rowp[ix[0]], rowp[ix[1]], rowp[ix[2]], rowp[ix[3]], cx);
+    }
+  }
+  unsigned cnt[3] = {0, 0, 0};
+  for (int row = 0; row < UP_ROWS; ++row) {
+    const int oy = oy0 + row;
+    if (oy >= H) break;
+    int iy[4];
+    float cy[4];
+    cubic_setup(oy, scale_y, h, iy, cy);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float out = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t = hsum[c][iy[j] - wy0][tid];
+        out = (j == 0) ? t * cy[0] : __builtin_fmaf(t, cy[j], out);
+      }
+      v[c] = out;
+      if (logits_full && live_x) logits_full[(((size_t)img * 3 + c) * H + oy) * W + ox] = out;
+    }
+    emit_label(decide_offsets(v[0], v[1], v[2], bark, node), exclude_nodes, live_x, labels, labels_i64, ((size_t)img * H + oy) * W + ox, cnt);
+  }
+  if (counts) add_class_counts(cnt, blk_counts, counts + (size_t)img * 3);
+}
+
 template <int PREC>
 __global__ void nhwc_to_nchw_kernel(const void* __restrict__ x, float* __restrict__ y, int N, int HW, int C) {
   const size_t total = (size_t)N * HW * C;
@@ -590,7 +707,7 @@ hipError_t launch_head1x1(const void* x, int cin, const float* w, const float* b
 
 hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int H, int W,
                                   float* logits_full, void* labels, int labels_i64,
-                                  unsigned long long* counts, int exclude_nodes, hipStream_t s) {
+                                  unsigned long long* counts, int exclude_nodes, hipStream_t s, const float* offsets) {
   if (H > 65535 || N > 65535) return hipErrorInvalidValue;
   // ATen area_pixel_compute_scale<float>(in, out, align_corners=false, scales=nullopt)
   const float scale_y = (float)h / (float)H;
@@ -599,6 +716,19 @@ hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int 
   // path's own x8 geometry: 36 x 5 taps); anything else takes the one-pixel-per-thread kernel
   constexpr int up_rows = 8;                       // output rows per block (4 and 16 measured slower)
   const bool fits = (int)(scale_x * 255.0f) + 6 <= UP_WIN_C && (int)(scale_y * (up_rows - 1)) + 6 <= UP_WIN_R;
+  if (offsets) {                                   // the same geometry and choice of form, the offset kernels
+    const float bark = offsets[0], node = offsets[1];
+    if (fits) {
+      dim3 grid((W + 255) / 256, (H + up_rows - 1) / up_rows, N);
+      hipLaunchKernelGGL(upsample_argmax_tiled_offsets_kernel<up_rows>, grid, dim3(256), 0, s, lowres, h, w, H, W, scale_y,
+                         scale_x, logits_full, labels, labels_i64, counts, exclude_nodes, bark, node);
+    } else {
+      dim3 grid((W + 255) / 256, H, N);
+      hipLaunchKernelGGL(upsample_argmax_offsets_kernel, grid, dim3(256), 0, s, lowres, h, w, H, W, scale_y, scale_x,
+                         logits_full, labels, labels_i64, counts, exclude_nodes, bark, node);
+    }
+    return hipGetLastError();
+  }
   if (fits) {
     dim3 grid((W + 255) / 256, (H + up_rows - 1) / up_rows, N);
     hipLaunchKernelGGL(upsample_argmax_tiled_kernel<up_rows>, grid, dim3(256), 0, s, lowres, h, w, H, W, scale_y,

@@ -72,6 +72,15 @@ precision, recall and F1 at the tolerance, the mean symmetric contour distance, 
 Hausdorff distance in mm) and a ``"contours"`` entry in the summary (``contours.contour_summary``) with the pooled histogram,
 from which any other tolerance can be read off.  ``evaluation_stats.csv`` does not change, and without the flag nothing does.
 
+``--operating_points`` (``operating_points=True``) sweeps the operating point: beside ``confusion``, on the batch's stream and on
+the same full-resolution logits, ``FCNResNet50.offset_sweep`` counts the 3 x 3 confusion of ``argmax(x0, x1 + b1, x2 + b2)`` at
+every point of a grid of (bark, node) offsets (csrc/offset_sweep.hip; the host restatement is ``operating.sweep_cpu``).  The
+tables ride back in a pinned ring and rank 0 writes ``results/operating_points.csv``, ``results/operating_evaluation.csv`` and
+the summary's ``"operating_points"`` entry (``operating.write_report``).  ``--logit_offsets BARK NODE`` (``logit_offsets=``)
+applies one pair: every stream's model decides by that rule in the forward's own upsample + argmax launch, so both confusions
+and every pass on the labels are of the offset labels; the passes on the logits (``--loss``, ``--ce``, ``--calibration``, the
+sweep itself) do not change.
+
 ``--calibration`` (``calibration=True``) asks whether the network's confidence is worth anything.  Each batch writes its
 full-resolution logits as under ``--loss`` / ``--ce`` (one buffer per stream serves all three flags), and after the raw
 ``confusion``, on the batch's stream, ``FCNResNet50.softmax_census`` tallies the softmax against the dual
@@ -425,6 +434,19 @@ def frame_report(allrows, size: int, pool: int) -> dict:
     return doc
 
 
+def write_operating_report(results_dir: str, items, allrows, all_op, grids, logit_offsets=None) -> dict:
+    """``operating_points.csv`` and ``operating_evaluation.csv`` from the gathered ``(global_idx, G1 G2 9 counts)`` rows
+    ``all_op``, for the evaluated images of ``allrows`` in their order.  Returns the ``"operating_points"`` entry of the summary
+    (``operating.write_report``)."""
+    from . import operating as opm
+    b1, b2 = grids
+    shape = (b1.size, b2.size, 3, 3)
+    tables = {int(g[0]): g[1:] for g in np.asarray(all_op, dtype=np.int64).reshape(-1, 1 + b1.size * b2.size * 9)}
+    images = [(items[int(g[0])]["name"], items[int(g[0])]["wood"], tables[int(g[0])].reshape(shape))
+              for g in allrows if int(g[3]) == STATUS_OK]
+    return opm.write_report(results_dir, images, b1, b2, logit_offsets)
+
+
 def write_calibration_report(results_dir: str, items, allrows, all_wire, pooled, ece_bins: int) -> dict:
     """``calibration_evaluation.csv`` and ``calibration_curves.csv`` (tab separated, like ``evaluation_stats.csv``) from the
     gathered ``(global_idx, calibration.wire_width(ece_bins) fields)`` rows ``all_wire`` and the folder's pooled census row, for
@@ -574,7 +596,8 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
                     contour_tolerance: int = None, tta="none", calibration: bool = False, ece_bins: int = None,
                     jitter=None, jitter_views=None, windows: int = None, windows_stride: int = None, windows_blend: str = None,
                     windows_compare: bool = False, frame: str = "scan", frame_size: int = None, pool: int = None,
-                    subset=None, as_logged: bool = False) -> dict:
+                    subset=None, as_logged: bool = False, logit_offsets=None, operating_points: bool = False,
+                    bark_offsets=None, node_offsets=None) -> dict:
     """Evaluate the checkpoint on the labelled folder ``root`` (module docstring); returns this rank's statistics, with
     the summary on rank 0.  ``arch``: the network (``predict.resolve_arch``; ``"auto"`` = the one the checkpoint's keys
     name).  ``bn_stats``: ``"running"`` (eval mode) or ``"image"``, the shipped tool's per-image BatchNorm statistics
@@ -627,6 +650,15 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     "pixelwise_f1", "groups"}`` (``metrics.as_logged_over_groups``); everything else the run writes is what it writes without
     the flag.  An image that passed the header checks but dropped out in the loop (a dual that decodes to another shape than
     its header promised) would move every later group: the run then fails after the loop, on every rank alike, naming it.
+    ``logit_offsets`` = ``(bark, node)``: every stream's model decides by ``argmax(x0, x1 + bark, x2 + node)``
+    (``FCNResNet50.set_logit_offsets``), so the raw and the clean confusion, ``zones``, ``contours`` and the views' merges are
+    all of the offset labels; ``loss``, ``ce`` and ``calibration`` describe the logits and do not change.  The summary gains
+    ``"logit_offsets"``.
+    ``operating_points`` (with ``bark_offsets`` / ``node_offsets``: ``"LO:HI:STEP"`` or a list, default ``-8:8:0.5``; refused
+    without the flag): beside ``confusion``, on the batch's stream, ``FCNResNet50.offset_sweep`` counts the 3 x 3 confusion of
+    the raw decision at every point of the grid (``operating``; it ignores ``logit_offsets``); a table of ``G1 G2 9`` int64 per
+    image rides back, and rank 0 writes ``results/operating_points.csv``, ``results/operating_evaluation.csv`` and the
+    summary's ``"operating_points"`` entry (``operating.write_report``).
     ``subset``: the path of a file with one ``wood_type/name`` per line, or such a list: only these samples are evaluated, in
     that order (``apply_subset``).
     Raises ``NonFiniteLogits`` on every rank alike when f16x2 cannot carry the weights."""
@@ -648,6 +680,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     CAL = bool(calibration)
     check_calibration_arguments(CAL, ece_bins)
     EB = cal.check_ece_bins(ece_bins) if ece_bins is not None else cal.DEFAULT_ECE_BINS
+    from . import operating as opm
+    LO = folder_run.check_logit_offsets(logit_offsets)
+    OPS = opm.check_arguments(operating_points, bark_offsets, node_offsets)   # the two grids, None = off
+    OPW = OPS[0].size * OPS[1].size * 9 if OPS else 0                         # int64 per image
     if ce:
         class_weights = check_class_weights(class_weights)
     T = folder_run.check_tta_arguments(tta)         # the view mask, 0 = off
@@ -674,6 +710,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if CAL:
             m.softmax_census(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
                              torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev))
+        if OPS:
+            m.offset_sweep(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev),
+                           torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev), *OPS)
         if Z:                                        # match_zones' (11 bytes per pixel)
             plane = torch.zeros((batch, target_size, target_size), dtype=torch.uint8, device=dev)
             m.match_zones(plane, plane, cap=ZCAP, pair_cap=PCAP)
@@ -688,7 +727,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             m.lovasz_softmax_groups(torch.zeros((POOL, 3, FT, FT), dtype=torch.float32, device=dev), plane, POOL)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root: os.makedirs(os.path.join(root, "results"), exist_ok=True), warm,
-                        normalization=normalization)
+                        normalization=normalization, logit_offsets=LO)
 
     def header_status(gi, h, w):                     # what the header reads say of image gi
         status = dual_status(items[gi], h, w, target_size)
@@ -737,7 +776,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     ring = [torch.empty((2, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)]   # raw, clean
     loss_ring = [torch.empty((batch, 3), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if loss else None
     logits_buf = [torch.empty(batch * 3 * target_size * target_size, dtype=torch.float32, device=dev)
-                  for _ in range(r.n_streams)] if loss or ce or CAL else None
+                  for _ in range(r.n_streams)] if loss or ce or CAL or OPS else None
     ce_ring = [torch.empty((batch, 9), dtype=torch.float64).pin_memory() for _ in range(r.depth)] if ce else None
     # --zones: per slot the two zone inventories, the pair rows, the three counts per image, and the two planes an image over
     # a cap is matched from on the host
@@ -761,6 +800,11 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if CAL:
         cal_wire[:, 0] = mine
     cal_pool = np.zeros(cal.WORDS, dtype=np.uint64) if CAL else None
+    # --operating_points: per slot the tables of a batch; per image the table that travels
+    op_ring = [torch.empty((batch, OPW), dtype=torch.int64).pin_memory() for _ in range(r.depth)] if OPS else None
+    op_wire = np.zeros((len(mine), 1 + OPW), dtype=np.int64) if OPS else None
+    if OPS:
+        op_wire[:, 0] = mine
     # --jitter: per slot the confusion of each view's final labels; per image the row that travels
     jring = [torch.empty((NV, batch, 3, 3), dtype=torch.int64).pin_memory() for _ in range(r.depth)] if NV else None
     jrows = np.zeros((len(mine), 1 + 9 * NV), dtype=np.int64) if NV else None
@@ -778,7 +822,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if FT:                                                        # the training's frame of the scan and of its dual
             x, tgt = mdl.training_frame(x, (FT, FT)), mdl.training_frame(tgt, (FT, FT))
         n, h, w = x.shape[:3]
-        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL else None
+        lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL or OPS else None
         low_kw = dict(return_lowres=True) if AL else {}               # --as_logged: the merged low-resolution logits as well
         if T:                                                         # the same call on the mean of the flip views
             labels, _, *low = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg, **low_kw)
@@ -806,6 +850,9 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         if CAL:                                                       # the raw softmax, before remove_small_zones
             census, _ = mdl.softmax_census(lg, tgt)
             cal_ring[slot][:n].copy_(census.view(torch.int64), non_blocking=True)
+        if OPS:                                                       # the raw decision at every grid point, like the census
+            tables = mdl.offset_sweep(lg, tgt, *OPS)
+            op_ring[slot][:n].copy_(tables.view(torch.int64).view(n, OPW), non_blocking=True)
         if loss:                                                      # LovaszSoftmax (:236-239)
             terms, _ = mdl.lovasz_softmax(lg, tgt)
             loss_ring[slot][:n].copy_(terms, non_blocking=True)
@@ -858,6 +905,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             wire = cal.wire_rows(census, EB)
             for j, k in enumerate(part):
                 cal_wire[k, 1:] = wire[j]
+        if OPS:
+            tables = op_ring[slot][:n].numpy()
+            for j, k in enumerate(part):
+                op_wire[k, 1:] = tables[j]
         for j, k in enumerate(part):
             rows[k, :4] = (mine[k], h, w, STATUS_OK)
             rows[k, 4:13], rows[k, 13:] = conf[0, j], conf[1, j]
@@ -935,6 +986,7 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
         all_cal = folder_run.gather(r, cal_wire, 1 + cal.wire_width(EB))
         all_census = cal.pool(folder_run.gather_ragged(np.concatenate([[r.rank], cal_pool.view(np.int64)])[None], r.world, r.dist,
                                                        r.wire_dev, width=1 + cal.WORDS)[:, 1:])
+    all_op = folder_run.gather(r, op_wire, 1 + OPW) if OPS else None
     all_views = folder_run.gather(r, jrows, 1 + 9 * NV) if NV else None
     all_win = folder_run.gather(r, wrows, 1 + 9 * 2) if WC else None
     summary = gathered = None
@@ -953,6 +1005,10 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
             summary["contours"] = write_contour_report(os.path.join(root, "results"), items, allrows, all_wire, all_hist, TOL)
         if CAL:
             summary["calibration"] = write_calibration_report(os.path.join(root, "results"), items, allrows, all_cal, all_census, EB)
+        if LO is not None:
+            summary["logit_offsets"] = list(LO)
+        if OPS:
+            summary["operating_points"] = write_operating_report(os.path.join(root, "results"), items, allrows, all_op, OPS, LO)
         if FT:
             summary["frame"] = frame_report(allrows, FT, POOL)
         if AL:
@@ -1025,6 +1081,15 @@ def format_summary(summary: dict) -> str:
             "%s AP %s, AUROC %s, best F1 %s at p >= %s (argmax: %s)" % (
                 name, fmt(c[name]["average_precision"]), fmt(c[name]["auroc"]), fmt(c[name]["best_f1"]),
                 fmt(c[name]["best_f1_threshold"], "%.3f"), fmt(c[name]["f1_at_argmax"])) for name in ("Bark", "Node")))
+    if summary.get("logit_offsets"):
+        lines.append("labels decided by argmax(x0, x1 + %r, x2 + %r) (--logit_offsets)" % tuple(summary["logit_offsets"]))
+    if summary.get("operating_points"):
+        for name, p in summary["operating_points"]["points"].items():
+            f = p["figures"]
+            lines.append("operating point %s: %s%s: miou %.3f, f1_mean %.3f, f1_node %.3f, Output Bark %% %s (target %s), Output "
+                         "Node %% %s (target %s)" % (name, p["arguments"], " (on the grid's edge: widen it)" if p["on_edge"] else "",
+                                                     f["miou"], f["f1_mean"], f["f1_node"], f["Output Bark %"], f["Target Bark %"],
+                                                     f["Output Node %"], f["Target Node %"]))
     if summary.get("frame"):
         fr = summary["frame"]
         fmt = lambda v: "-" if v is None else "%.3f" % v
@@ -1098,6 +1163,16 @@ def main(argv=None):
                          "F1 per class and threshold, the reliability table) and a \"calibration\" entry in the summary")
     ap.add_argument("--ece_bins", type=int, default=None, metavar="BINS",
                     help="with --calibration: the bins under ECE and MCE, a power of two in 1..256 (default 16)")
+    ap.add_argument("--operating_points", action="store_true",
+                    help="also sweep the operating point on the device: the 3 x 3 confusion of argmax(x0, x1 + b1, x2 + b2) of the "
+                         "raw logits (before remove_small_zones; --logit_offsets does not reach it) at every point of a grid of "
+                         "(bark, node) offsets, and write results/operating_points.csv, results/operating_evaluation.csv and an "
+                         "\"operating_points\" entry in the summary that names the best-mIoU, best-F1 and area-unbiased points as "
+                         "ready --logit_offsets arguments.  G1 * G2 * 9 int64 per image ride back: 78 408 bytes at the default grid")
+    ap.add_argument("--bark_offsets", default=None, metavar="LO:HI:STEP",
+                    help="with --operating_points: the grid of the bark offset, at most 33 values (default -8:8:0.5)")
+    ap.add_argument("--node_offsets", default=None, metavar="LO:HI:STEP",
+                    help="with --operating_points: the grid of the node offset, at most 33 values (default -8:8:0.5)")
     ap.add_argument("--frame", default="scan", metavar="{scan,training}",
                     help="training: score every scan and its dual on the training run's own frame, pad_resize to T x T (reflection "
                          "pad, PIL's bilinear resize where the padded length is T + 1), made on the device; everything else runs "
@@ -1129,6 +1204,9 @@ def main(argv=None):
         folder_run.check_windows_arguments(args.windows, args.windows_stride, args.windows_blend, args.windows_compare, args.tta,
                                            args.jitter, args.jitter_views, bn_stats=args.bn_stats, arch=args.arch)
         check_frame_arguments(args.frame, args.frame_size, args.pool, as_logged=args.as_logged)
+        from . import operating as opm
+        opm.check_arguments(args.operating_points, args.bark_offsets, args.node_offsets)
+        args.logit_offsets = folder_run.check_logit_offsets(args.logit_offsets)
         if args.subset is not None:
             apply_subset(list_labelled(args.root_path), read_subset(args.subset))
     except (OSError, ValueError) as e:
@@ -1177,6 +1255,10 @@ def main(argv=None):
             kw["as_logged"] = True
     if args.subset is not None:
         kw["subset"] = args.subset
+    if args.logit_offsets is not None:
+        kw["logit_offsets"] = args.logit_offsets
+    if args.operating_points:
+        kw.update(operating_points=True, bark_offsets=args.bark_offsets, node_offsets=args.node_offsets)
     if args.normalization is not None:
         kw["normalization"] = args.normalization
         if args.stats is not None:

@@ -788,13 +788,15 @@ def bring_up_without_model(r, make_dirs) -> None:
 
 
 def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool, make_dirs, warm=None,
-             normalization=None, stack: int = 1) -> None:
+             normalization=None, stack: int = 1, logit_offsets=None) -> None:
     """Rank 0's ``make_dirs(root)`` and the start barrier, then ``r.models`` (``r.n_streams`` objects on one copy of the
     weights), ``r.gpu_streams``, and the resolved ``r.arch`` / ``r.precision``.  ``warm(model)``: the driver's own workspaces, grown
     to their largest size once like the forward's.  ``normalization``: the ``(mean, std)`` of the uint8 ingest
     (``resolve_normalization``), set on every model object before anything runs (a clone owns its context and would start on
     the defaults); None leaves the defaults of models.py:208-209.  ``stack``: the entries the forward runs per image (the views
-    of ``--tta``; ``open_run``'s ``stack`` counts as well): the workspace is reserved for ``stack x r.batch`` entries."""
+    of ``--tta``; ``open_run``'s ``stack`` counts as well): the workspace is reserved for ``stack x r.batch`` entries.
+    ``logit_offsets``: the ``(bark, node)`` pair of ``--logit_offsets`` (``check_logit_offsets``), set on every model object
+    like the normalisation; None leaves the plain argmax."""
     import time
     import torch
     from .model import MODELS
@@ -822,6 +824,9 @@ def bring_up(r, model_path: str, arch: str, bn_stats: str, precision_auto: bool,
     if normalization is not None:                    # every rank parsed the same arguments: no collective
         for m in r.models:
             m.set_normalization(*normalization)
+    if logit_offsets is not None:
+        for m in r.models:
+            m.set_logit_offsets(*logit_offsets)
     # side streams only: the default stream stays with whatever else the driver runs on the device
     r.gpu_streams = [torch.cuda.Stream(r.dev) for _ in range(r.n_streams)]
     for m in r.models:                               # the largest workspace once: a context's buffers only grow, and a folder of
@@ -1069,6 +1074,11 @@ def add_shared_arguments(ap) -> None:
                          "downstream is about that mean.  --batch keeps counting images (default 1, 2 in bf16)")
     add_jitter_arguments(ap)
     add_windows_arguments(ap)
+    ap.add_argument("--logit_offsets", type=float, nargs=2, metavar=("BARK", "NODE"), default=None,
+                    help="move the operating point: the label of a pixel is argmax(x0, x1 + BARK, x2 + NODE) of its logits "
+                         "instead of the plain argmax, decided in the forward's own upsample + argmax launch; everything "
+                         "downstream sees that decision, the logits themselves (--loss, --ce, --calibration) do not change.  "
+                         "evaluate --operating_points proposes pairs")
     ap.add_argument("--mean", type=float, nargs=3, metavar=("R", "G", "B"), default=None,
                     help="per-channel mean of the training folder, on the [0, 1] scale, that the frames are normalised with "
                          "(with --std; default: the constants of the reference's model class)")
@@ -1101,6 +1111,28 @@ def add_dropout_arguments(ap) -> None:
     ap.add_argument("--dropout_seed", type=int, default=None, help="64-bit seed of the draws (default 0)")
     ap.add_argument("--dropout_compare", metavar="OLD_final_stats.csv", default=None,
                     help="a final_stats.csv of the shipped tool: report where its numbers lie within the draws")
+
+
+def check_logit_offsets(logit_offsets, dropout_draws=None, confidence: bool = False):
+    """``ValueError`` for what ``--logit_offsets BARK NODE`` refuses before any device is touched: a pair that is not two finite
+    numbers, ``--dropout_draws`` (the draws have a tail of their own, which decides by the plain argmax) and ``predict
+    --confidence`` (the confidence byte is the raw argmax's probability).  Returns the pair as float32-exact floats, or None
+    when the option is not given."""
+    import math
+    if logit_offsets is None:
+        return None
+    try:
+        pair = tuple(float(np.float32(v)) for v in logit_offsets)
+    except (TypeError, ValueError):
+        raise ValueError("--logit_offsets takes two numbers, BARK and NODE")
+    if len(pair) != 2 or not all(math.isfinite(v) for v in pair):
+        raise ValueError("--logit_offsets takes two finite numbers, BARK and NODE, got %r" % (logit_offsets,))
+    if dropout_draws:
+        raise ValueError("--logit_offsets cannot go with --dropout_draws: offsets under the Dropout draws are left out (the draws "
+                         "decide by the plain argmax)")
+    if confidence:
+        raise ValueError("--logit_offsets cannot go with --confidence: the confidence byte is the raw argmax's probability")
+    return pair
 
 
 def resolve_normalization(mean=None, std=None, stats: str = None):

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import List, Mapping, Optional, Tuple
 
 import numpy as np
@@ -328,6 +329,8 @@ class FCNResNet50:
         self._zone_match_ws: Optional[torch.Tensor] = None   # nbc_match_zones', likewise
         self._contours_ws: Optional[torch.Tensor] = None   # nbc_contour_distances', likewise
         self._census_ws: Optional[torch.Tensor] = None     # nbc_softmax_census', likewise
+        self._sweep_ws: Optional[torch.Tensor] = None      # nbc_offset_sweep's, likewise
+        self._logit_offsets: Tuple[float, float] = (0.0, 0.0)   # set_logit_offsets: (bark, node), (0, 0) = off
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self._frame_taps: dict = {}                        # training_frame: the device table of each frame length
         self.device: Optional[torch.device] = None
@@ -356,6 +359,8 @@ class FCNResNet50:
             ctx = C.c_void_p()
             _lib.check(self._lib.nbc_create(C.byref(ctx), index), "nbc_create")
             self._ctx = ctx
+            if self._logit_offsets != (0.0, 0.0):
+                _lib.check(self._lib.nbc_set_logit_offsets(self._ctx, *self._logit_offsets), "nbc_set_logit_offsets")
         self.device = device
         if self._blob_host is not None:
             self._upload()
@@ -1085,6 +1090,50 @@ class FCNResNet50:
                        "nbc_softmax_census")
         return rows, plane
 
+    def set_logit_offsets(self, bark: float = 0.0, node: float = 0.0):
+        """Move the operating point (nbc_set_logit_offsets): the upsample + argmax launch of every forward and of
+        ``upsample_argmax`` decides by ``argmax(x0, x1 + bark, x2 + node)``, one float32 addition each, instead of the plain
+        argmax; the counts, ``exclude_nodes`` and everything downstream follow that decision.  The logits the model returns
+        are never offset.  ``(0, 0)`` is off, the default: the model then launches exactly the kernels it launched before.
+        Finite values only (``ValueError``).  ``clone_shared`` carries the setting over; ``dropout_draws`` and
+        ``dropout_votes`` refuse a model with offsets on.  ``operating.select`` proposes pairs from ``offset_sweep``."""
+        bark, node = float(np.float32(bark)), float(np.float32(node))
+        if not (math.isfinite(bark) and math.isfinite(node)):
+            raise ValueError("logit offsets must be finite, got (%r, %r)" % (bark, node))
+        if self._ctx:
+            _lib.check(self._lib.nbc_set_logit_offsets(self._ctx, bark, node), "nbc_set_logit_offsets")
+        self._logit_offsets = (bark + 0.0, node + 0.0)
+        return self
+
+    def logit_offsets(self) -> Tuple[float, float]:
+        """The ``(bark, node)`` pair ``set_logit_offsets`` holds; ``(0.0, 0.0)`` when off."""
+        return self._logit_offsets
+
+    def offset_sweep(self, logits_full: torch.Tensor, target: torch.Tensor, bark_offsets, node_offsets) -> torch.Tensor:
+        """The operating-point sweep on the device (nbc_offset_sweep; the definition: include/nbc.h, ``operating.sweep_cpu``):
+        the 3 x 3 confusion of the label map ``argmax(x0, x1 + bark_offsets[i], x2 + node_offsets[j])`` against the target at
+        every point of the grid.  ``logits_full``: contiguous f32 ``[N,3,H,W]``; ``target``: contiguous uint8 grey mask
+        ``[N,H,W]``; the offsets: 1..33 finite float32 values each, strictly ascending.  Runs on the current stream; the
+        workspace is cached on this object and only grows.  It ignores ``set_logit_offsets``: it describes the logits.
+        Returns uint64 ``[N, G1, G2, 3, 3]`` on the device, cell ``[t][p]`` the pixels of target class t decided as p."""
+        self._require_ctx()
+        n, h, w = self._check_logits_target(logits_full, target)
+        b1 = np.ascontiguousarray(np.asarray(bark_offsets, dtype=np.float32).reshape(-1))
+        b2 = np.ascontiguousarray(np.asarray(node_offsets, dtype=np.float32).reshape(-1))
+        g1, g2 = int(b1.size), int(b2.size)
+        need = int(self._lib.nbc_offset_sweep_workspace_bytes(n, h, w, g1, g2))
+        if need == 0:
+            raise ValueError("nbc_offset_sweep refuses a [%d,3,%d,%d] batch on a %d x %d grid (N <= 65535, H * W < 2^31, 1..%d "
+                             "offsets each)" % (n, h, w, g1, g2, _lib.SWEEP_MAX_GRID))
+        conf = torch.empty((n, g1, g2, NUM_CLASSES, NUM_CLASSES), dtype=torch.uint64, device=self.device)
+        fp = C.POINTER(C.c_float)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_sweep_ws", need, cur)
+            _lib.check(self._lib.nbc_offset_sweep(logits_full.data_ptr(), target.data_ptr(), n, h, w, b1.ctypes.data_as(fp), g1,
+                                                  b2.ctypes.data_as(fp), g2, ws.data_ptr(), ws.numel(), conf.data_ptr(),
+                                                  cur.cuda_stream), "nbc_offset_sweep")
+        return conf
+
     def dropout_draws(self, draws: int, image_ids, p: float = 0.1, seed: int = 0, first_draw: int = 0,
                       small_zones: bool = True, exclude_nodes: bool = False, return_lowres: bool = False, *,
                       min_pixels: int = 150, draws_per_pass: int = 8):
@@ -1254,6 +1303,7 @@ class FCNResNet50:
         self._require_weights()
         other = self._like()
         other.bn_statistics = self.bn_statistics
+        other._logit_offsets = self._logit_offsets      # applied when `to` creates the context
         other.to(self.device)
         other._attach(self._blob_dev, self._affine_dev, self._raw_dev)
         return other
@@ -1557,6 +1607,7 @@ class FCNResNet50:
         self._zone_match_ws = None
         self._contours_ws = None
         self._census_ws = None
+        self._sweep_ws = None
         self._frame_taps = {}
         self._last_shape = None
 

@@ -500,7 +500,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
                    dropout_compare: str = None, dropout_votes: bool = False, zones: bool = False, zones_cap: int = None,
                    tta="none", tta_votes: bool = False, confidence: bool = False, confidence_threshold: float = None,
                    jitter=None, jitter_views=None, jitter_votes: bool = False, windows: int = None, windows_stride: int = None,
-                   windows_blend: str = None, windows_compare: bool = False) -> dict:
+                   windows_blend: str = None, windows_compare: bool = False, logit_offsets=None) -> dict:
     """predict.py:51-58 + models.py:230-364 with the model call on the MI355X path.
 
     One pass per image instead of the reference's two (preprocess everything, then predict everything):
@@ -548,6 +548,9 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     own counts and the vote statistics over the views ride back beside the labels; rank 0 writes ``results/tta_stats.csv``
     and ``results/tta_summary.json`` (``folder_run.tta_report``).  ``tta_votes`` (with ``tta`` only): also
     ``results/tta_support/<wood>/<name>``, the support byte of the views' vote (grey, 255 = every view agrees).
+    ``logit_offsets`` = ``(bark, node)`` (not with ``dropout_draws`` or ``confidence``): every stream's model decides by
+    ``argmax(x0, x1 + bark, x2 + node)`` (``FCNResNet50.set_logit_offsets``); the label PNGs, the percentages, ``--zones`` and the
+    views' merges all see that decision.
     ``confidence`` (not with ``dropout_draws``): the forward also writes its full-resolution logits, and
     ``FCNResNet50.softmax_census`` (no target, the plane on) leaves the softmax confidence of the plain forward, which costs no
     further forward: ``results/confidence/<wood>/<name>`` (grey, the winning class's probability in 1/256: the raw softmax,
@@ -591,6 +594,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     from . import calibration as cal
     C = bool(confidence)
     check_confidence_arguments(C, confidence_threshold, D)
+    LO = folder_run.check_logit_offsets(logit_offsets, D, C)
     CT = cal.check_confidence_threshold(confidence_threshold) if confidence_threshold is not None else cal.DEFAULT_CONFIDENCE_THRESHOLD
     old_stats = None
     if V and not D:
@@ -612,7 +616,8 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
             m.softmax_census(torch.zeros((batch, 3, target_size, target_size), dtype=torch.float32, device=dev), confidence=True)
     folder_run.bring_up(r, model_path, arch, bn_stats, precision_auto,
                         lambda root_: generate_folders(root_, votes=V, tta_votes=bool(tta_votes), confidence=C,
-                                                       jitter_votes=bool(jitter_votes)), warm, normalization=normalization)
+                                                       jitter_votes=bool(jitter_votes)), warm, normalization=normalization,
+                        logit_offsets=LO)
     if D:
         folder_run.check_dropout_arch(r.arch)        # --arch auto: the checkpoint's keys have named the network by now
 
@@ -931,6 +936,7 @@ def main(argv=None):
         if args.dropout_compare is not None:
             folder_run.read_shipped_stats(args.dropout_compare)
         folder_run.check_zones_arguments(args.zones, args.zones_cap, args.only_preprocess)
+        args.logit_offsets = folder_run.check_logit_offsets(args.logit_offsets, args.dropout_draws, args.confidence)
     except ValueError as e:
         ap.error(str(e))
     if not args.device.startswith("cuda"):
@@ -965,6 +971,10 @@ def main(argv=None):
         if int(os.environ.get("RANK", "0")) == 0:
             print("predict: frames normalised with mean %s, std %s (%s)" % (
                 list(args.normalization[0]), list(args.normalization[1]), args.stats or "arguments"), flush=True)
+    if args.logit_offsets is not None:
+        kw["logit_offsets"] = args.logit_offsets
+        if int(os.environ.get("RANK", "0")) == 0:
+            print("predict: labels decided by argmax(x0, x1 + %r, x2 + %r) (--logit_offsets)" % args.logit_offsets, flush=True)
     stats = folder_run.run_precision("predict", lambda precision, **over: predict_folder(
         args.root_path, args.model_path, precision, args.exclude_nodes, not args.no_small_zones, idx, **dict(kw, **over)),
         args.precision, args.bn_stats)
