@@ -992,7 +992,9 @@ int nbc_set_conv_tile(nbc_ctx* ctx, int tile);
 /* Per-layer tile choice by measurement: runs one forward on x (so that the workspace holds real
  * activations), then times every tile shape of the LDS-DMA kernel on every convolution of the
  * current (N,H,W) plan (`reps` launches each, HIP events) and keeps the fastest.  Results do not
- * depend on the tile (same K order, one accumulator per output), only speed does.  Without this call a
+ * depend on the tile, only speed does: every tile a layer may run on walks K in the same order with the same sums per
+ * output (one accumulator; in f16x2 on the row-step tiles 18 / 19 / 20 two: the low-piece products have a sum of their
+ * own, joined once behind the K loop -- on 18 and 20 alike).  Without this call a
  * plan runs on per-layer defaults from a cost model (rounds of blocks per CU x per-block time, fitted to
  * measurements), within 0.1-0.6 % (f32) / 0.5-4.4 % (bf16) of the measured best at any image height; the
  * measurement costs 0.5-0.9 s per shape.  The choice is

@@ -25,10 +25,21 @@
 //
 // K order.  (channel block, kh, kw) -- the generic kernel walks (kh, kw, channel block).  The order is a property of the
 // LAYER AND SHAPE, never of the tile: a convolution these kernels take (conv_rows_kind) runs on its one tile whatever the
-// caller forces or the autotuner measures, so logits stay bit-identical across tiles.  Everything else is the generic f16x2
-// arithmetic, the same functions (f16x2_mma.hpp): per 16x16 tile and K-step P.X0, Q.X0, (P 2^-11).X1 on
-// v_mfma_f32_16x16x32_f16 into one chain that joins the running f32 sum every eighth K-step; f32 BN + ReLU epilogue through a
-// per-wave LDS transpose, whole 256-byte row segments stored.  This file reads the fragments and walks the tiles.
+// caller forces or the autotuner measures, so logits stay bit-identical across tiles.
+//
+// The sums.  Per 16x16 tile and K-step the same three products on v_mfma_f32_16x16x32_f16 as the generic kernel's, from the same
+// fragments in the same order (f16x2_mma.hpp): P.X0 and Q.X0 into the chain that joins the running f32 sum every eighth K-step --
+// and the low-piece product as P.X1, P AS STORED, into a third set `low` that runs over the tile's whole K loop and joins once
+// behind it, sum = fma(low, 2^-11, sum) (x2_products_low, x2_join_low).  The generic kernel forms P 2^-11 in every K-step, eight
+// v_pk_mul_f16 per 24 MFMAs, because its third products share the chain: its tiles have no registers for a third set.  A block
+// here is alone on its compute unit with twelve waves, three per SIMD (tile 19: eight, two), which may take 168 registers each; the
+// kernel takes 144-146 (116 before), no spill, no scratch, and its MFMA waves issue nothing in the loop but fragment reads and
+// MFMAs.  Measured (profiles/rowstep_low_sum_*, one stream traced ... one process untraced): head conv -1.5 ... -3 %, layer4's
+// conv2 -1 ... -2.5 %, layer3's -1 ... -2 %, layer2.1-3's -5 ... -8 %; the forward with two forwards in flight +1.0 %, all that a
+// timing-only build without the multiply gave.  `low` is zeroed with the other two sets at a tile's
+// start, a walking block's every tile included, and x2_flush never touches it; its K additions round at 2^-11 of the chain's
+// scale.  f32 BN + ReLU epilogue through a per-wave LDS transpose, whole 256-byte row segments stored, as the generic
+// kernel's.  This file reads the fragments and walks the tiles.
 //
 // LDS: three row slots (slot = kh: a channel block's three kernel rows; tile 20: four, its four input rows) of 144 pixels x 128 bytes, their 16-byte chunks
 // rotated by the pixel index so that a fragment block may start at ANY pixel without bank conflicts (row_off), and two or
@@ -273,13 +284,15 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
     }
     const unsigned b_rd0 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, q16));
     const unsigned b_rd1 = (unsigned)(A_REGION + lds_off(wn * NT * 32 + r16, 4 + q16));
-    f32x4 acc16[NT16][MT16], accI2[NT16][MT16];
+    // the running sum, the chain of P.X0 and Q.X0 that joins it every eighth K-step, and the sum of the unscaled low-piece products
+    // P.X1, which runs over the tile's whole K loop and joins once, scaled, behind it: all three start every tile from zero
+    f32x4 acc16[NT16][MT16], accI2[NT16][MT16], low[NT16][MT16];
 #pragma unroll
     for (int j = 0; j < NT16; ++j)
 #pragma unroll
       for (int i = 0; i < MT16; ++i)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { acc16[j][i][e] = 0.f; accI2[j][i][e] = 0.f; }
+        for (int e = 0; e < 4; ++e) { acc16[j][i][e] = 0.f; accI2[j][i][e] = 0.f; low[j][i][e] = 0.f; }
     unsigned a_off = (unsigned)(orow * A_SLOT), b_off = 0;   // byte offsets of the row-step's pixel slot (kh [+ 1]) and weight stage
     int t = 0;
     for (int rs = 0; rs < RS; ++rs) {
@@ -298,12 +311,13 @@ __global__ __launch_bounds__((2 * WN * OR + 4) * 64, (2 * WN * OR + 4) / 4) void
           xw0[j] = *reinterpret_cast<const uint4*>(smem + (b_rd0 + b_off) + (kw * B_TAP + j * 2048));
           xw1[j] = *reinterpret_cast<const uint4*>(smem + (b_rd1 + b_off) + (kw * B_TAP + j * 2048));
         }
-        x2_products(xp0, xp1, xw0, xw1, accI2);
+        x2_products_low(xp0, xp1, xw0, xw1, accI2, low);
       }
       a_off = a_off == (unsigned)((2 + orow) * A_SLOT) ? (unsigned)(orow * A_SLOT) : a_off + (unsigned)A_SLOT;
       b_off = b_off == (unsigned)(SB - 1) * B_STEP ? 0u : b_off + (unsigned)B_STEP;
     }
     x2_join<false>(acc16, accI2);
+    x2_join_low(acc16, low);
     __syncthreads();
     const int oyw = c.oy + orow * dil;                   // this wave's output row
     if (oyw < p.Ho)                                      // (the second row of a last, odd pair lies below the image: nothing to store)

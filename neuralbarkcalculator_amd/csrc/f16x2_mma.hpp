@@ -53,6 +53,35 @@ __device__ __forceinline__ void x2_products(const uint4 (&xp0)[NI], const uint4 
   }
 }
 
+// The row-step kernel's form of the K-step (conv3x3_rows.hip): the same fragments in the same product-major order, but the third
+// products take P AS STORED and go into a set of their own: chain += P.X0, Q.X0; low += P.X1.  The factor 2^-11 is a constant and
+// commutes with the sum, so it is applied once per output behind the K loop (x2_join_low) where x2_products multiplies 2 NJ
+// registers in every K-step; the weight fragments are not modified.  `low` runs over a tile's whole K loop: x2_flush never
+// touches it.  (Its additions round at its own scale, 2^-11 of the chain's: DESIGN 1.)
+template <int NJ, int NI>
+__device__ __forceinline__ void x2_products_low(const uint4 (&xp0)[NI], const uint4 (&xp1)[NI], const uint4 (&xw0)[NJ], const uint4 (&xw1)[NJ],
+                                                f32x4 (&chain)[NJ][NI], f32x4 (&low)[NJ][NI]) {
+  constexpr int NTI = NJ * NI;
+#pragma unroll
+  for (int idx = 0; idx < 3 * NTI; ++idx) {
+    const int prod = idx / NTI, n = idx % NTI, j = n / NI, i = n % NI;
+    if (prod == 0)
+      chain[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp0[i]), chain[j][i], 0, 0, 0);
+    else if (prod == 1)
+      chain[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw1[j]), __builtin_bit_cast(f16x8, xp0[i]), chain[j][i], 0, 0, 0);
+    else
+      low[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xw0[j]), __builtin_bit_cast(f16x8, xp1[i]), low[j][i], 0, 0, 0);
+  }
+}
+// Behind the last x2_join<false> of a tile: sum = fma(low, 2^-11, sum), one rounding per output.
+template <int NJ, int NI>
+__device__ __forceinline__ void x2_join_low(f32x4 (&sum)[NJ][NI], const f32x4 (&low)[NJ][NI]) {
+#pragma unroll
+  for (int n = 0; n < NJ * NI; ++n)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sum[n / NI][n % NI][e] = __builtin_fmaf(low[n / NI][n % NI][e], kH1Unscale, sum[n / NI][n % NI][e]);
+}
+
 // ---- epilogue.  Each wave takes one 32-pixel x (NT*32)-channel slab at a time through a private f32 scratch in LDS: BN on the
 // way in (a); on the way out (b) lane l owns chunk l % CPR (16 output bytes) of pixel l / CPR of a pass, so identity loads and
 // stores (c) are whole row segments.  Geometry of such slabs in precision PREC.  (Constants and functions of plain values: with
