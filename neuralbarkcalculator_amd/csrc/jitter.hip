@@ -208,19 +208,14 @@ __global__ __launch_bounds__(kThreads) void views_mean_kernel(const float* __res
   }
 }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // what the entry points refuse of (N, V) and of (H, W); nullptr when the shape is served
 const char* bad_stack(int N, int V) {
   if (V < 1 || V > kMaxViews) return "V must lie in 1..16";
-  if (N < 1 || (long long)V * N > 65535) return "bad shape: N >= 1 and V * N <= 65535";
+  if (!stack_entries_ok(N, V)) return "bad shape: N >= 1 and V * N <= 65535";
   return nullptr;
 }
 const char* bad_frame(int H, int W) {
-  if (H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return "bad shape: H, W >= 1 and H * W < 2^31";
+  if (!frame_shape_ok(H, W)) return "bad shape: H, W >= 1 and H * W < 2^31";
   return nullptr;
 }
 
@@ -255,8 +250,8 @@ extern "C" int nbc_jitter_views(const uint8_t* x_dev, int N, int H, int W, const
   if (reinterpret_cast<uintptr_t>(workspace_dev) & 7u) return fail(kWho, NBC_ERR_INVALID, "workspace_dev must be 8-byte aligned");
   const long long P = (long long)H * W;
   const size_t bytes = (size_t)N * P * 3, ws_bytes = (size_t)V * N * sizeof(unsigned long long);
-  if (overlap(x_dev, bytes, out_dev, bytes * V)) return fail(kWho, NBC_ERR_INVALID, "out_dev must not overlap x_dev");
-  if (overlap(workspace_dev, ws_bytes, x_dev, bytes) || overlap(workspace_dev, ws_bytes, out_dev, bytes * V))
+  if (ranges_overlap(x_dev, bytes, out_dev, bytes * V)) return fail(kWho, NBC_ERR_INVALID, "out_dev must not overlap x_dev");
+  if (ranges_overlap(workspace_dev, ws_bytes, x_dev, bytes) || ranges_overlap(workspace_dev, ws_bytes, out_dev, bytes * V))
     return fail(kWho, NBC_ERR_INVALID, "workspace_dev must not overlap x_dev or out_dev");
 
   JitterArgs a;
@@ -303,10 +298,9 @@ extern "C" int nbc_views_mean(const float* lowres_views_dev, int N, int V, int h
   if (!lowres_views_dev || !mean_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
   if (const char* why = bad_stack(N, V)) return fail(kWho, NBC_ERR_INVALID, why);
   if (const char* why = bad_frame(h, w)) return fail(kWho, NBC_ERR_INVALID, why);
-  if ((reinterpret_cast<uintptr_t>(lowres_views_dev) | reinterpret_cast<uintptr_t>(mean_dev)) & 3u)
-    return fail(kWho, NBC_ERR_INVALID, "float32 pointers must be 4-byte aligned");
+  if (!aligned4(lowres_views_dev, mean_dev)) return fail(kWho, NBC_ERR_INVALID, "float32 pointers must be 4-byte aligned");
   const size_t total = (size_t)N * 3 * h * w, bytes = total * sizeof(float);
-  if (overlap(lowres_views_dev, bytes * V, mean_dev, bytes)) return fail(kWho, NBC_ERR_INVALID, "mean_dev must not overlap the input");
+  if (ranges_overlap(lowres_views_dev, bytes * V, mean_dev, bytes)) return fail(kWho, NBC_ERR_INVALID, "mean_dev must not overlap the input");
   hipLaunchKernelGGL(views_mean_kernel, dim3(grid_stride_blocks(total, kThreads, kBlocksPerCu)), dim3(kThreads), 0,
                      static_cast<hipStream_t>(hip_stream), lowres_views_dev, (long long)total, V, mean_dev);
   const hipError_t e = hipGetLastError();

@@ -116,12 +116,6 @@ hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bi
 // draws <= 65535 (a 16-bit field per class), votes 16-byte aligned for the vector path; labels at any address.
 hipError_t launch_vote_accumulate(const unsigned char* labels, int draws, int N, long long P, uint32_t* votes, bool first,
                                   hipStream_t s);
-// The flip views of a batch and the merge of their low-resolution logits (tta.hip; the definition: include/nbc.h, nbc_tta_views /
-// nbc_tta_merge).  views: a mask of NBC_TTA_* bits in 1..15, V of them set; x / out in the layout of x_dtype (NBC_IN_*), out
-// [V][N] entries; lowres_views f32 [V][N][3][h][w], merged f32 [N][3][h][w], aligned nullable f32 [V][N][3][h][w].  The entry
-// points' checks (shape, alignment, no overlap) are the caller's.
-hipError_t launch_tta_views(const void* x, int x_dtype, int N, int H, int W, int views, void* out, hipStream_t s);
-hipError_t launch_tta_merge(const float* lowres_views, int N, int h, int w, int views, float* merged, float* aligned, hipStream_t s);
 // ASPP pooling branch of every DeepLab head (aspp.hip), per image: mean over hw pixels of x [N][hw][cin] (stored elements; cin a
 // multiple of 64, at most 4096), the 1x1 conv with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout]
 // elements.  Workspaces: partial N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.

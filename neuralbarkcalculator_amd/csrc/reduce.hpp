@@ -98,6 +98,22 @@ inline bool per_image_shape_ok(int N, int H, int W) {
   return N >= 1 && N <= 65535 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL;
 }
 constexpr const char* kPerImageShape = "bad shape: 1 <= N <= 65535, H, W >= 1 and H * W < 2^31";
+// the same for a stack of `per_image` views or windows of each of N images, and for the frame alone; the entry points word
+// their own messages
+inline bool stack_entries_ok(int N, long long per_image) { return N >= 1 && per_image * N <= 65535; }
+inline bool frame_shape_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL; }
+
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// every pointer of the list is 4-byte aligned (a null one is)
+template <typename... P>
+inline bool aligned4(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & 3u) == 0;
+}
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -144,11 +144,6 @@ __global__ __launch_bounds__(kThreads) void training_frame_kernel(const unsigned
   }
 }
 
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // the pad of an axis, or what the call refuses of it (why != nullptr)
 int axis_pad(int L, int Lt, const char** why) {
   *why = nullptr;
@@ -215,12 +210,11 @@ extern "C" int nbc_training_frame(const void* x_dev, int channels, int N, int H,
   if (why) return fail(kWho, NBC_ERR_INVALID, why);
   const int px = axis_pad(W, Wt, &why);
   if (why) return fail(kWho, NBC_ERR_INVALID, why);
-  if ((long long)Ht * Wt > 0x7fffffffLL) return fail(kWho, NBC_ERR_INVALID, "bad shape: Ht * Wt < 2^31");
+  if (!frame_shape_ok(Ht, Wt)) return fail(kWho, NBC_ERR_INVALID, "bad shape: Ht * Wt < 2^31");
   const bool rows = H + 2 * py != Ht, cols = W + 2 * px != Wt;   // the padded length is one too long
   if ((rows && !row_taps_dev) || (cols && !col_taps_dev))
     return fail(kWho, NBC_ERR_INVALID, "an axis whose padded length is the frame's + 1 needs its table (nbc_bilinear_taps)");
-  if ((reinterpret_cast<uintptr_t>(row_taps_dev) | reinterpret_cast<uintptr_t>(col_taps_dev)) & 3u)
-    return fail(kWho, NBC_ERR_INVALID, "the tables must be 4-byte aligned");
+  if (!aligned4(row_taps_dev, col_taps_dev)) return fail(kWho, NBC_ERR_INVALID, "the tables must be 4-byte aligned");
   const size_t in_bytes = (size_t)N * H * W * channels, out_bytes = (size_t)N * Ht * Wt * channels;
   if (ranges_overlap(x_dev, in_bytes, out_dev, out_bytes)) return fail(kWho, NBC_ERR_INVALID, "out_dev must not overlap x_dev");
 

@@ -3,14 +3,12 @@
 //
 // One rule for the grid (Axis, on the host and on the device) and two kernels, both without a context:
 //   window_views_kernel  a batch -> the K windows of every image, window-major, the rows and columns beyond the frame filled by
-//                        reflection.  A row is a run of units (a 3-byte pixel of uint8 NHWC, a 4-byte element of a float32 NCHW
-//                        plane) and is moved in granules (a byte, a 32-bit word).  A block takes a segment of a SOURCE row: 16-B
-//                        loads put it into LDS at the row's own alignment, then every window row that is made of it -- the
-//                        windows that cover the row, and those that cover the row beyond the frame that reflects it -- is put
-//                        together out of LDS in the destination's own 16-B vectors.  Heads, tails and the at most 7 reflected
-//                        units of a window row go granule by granule, so no access leaves [row start, row end) of either
-//                        buffer, at any alignment.  The source is read once, every window written once: 3 H W + 3 K E_y E_x
-//                        bytes per uint8 image.
+//                        reflection.  The row mover of row_views.hpp (its header states the units, the granules and the bounds
+//                        it keeps at any alignment): a block stages a segment of a SOURCE row, then emits its part of every
+//                        window row that is made of it -- the windows that cover the row, and those that cover the row beyond
+//                        the frame that reflects it.  The at most 7 reflected units of a window row go granule by granule, inside
+//                        the window row.  The source is read once, every window written once: 3 H W + 3 K E_y E_x bytes per
+//                        uint8 image.
 //   window_merge_kernel  the low-resolution logits [K][N][3][e_y][e_x] of the stacked forward -> [N][3][h][w], the weighted
 //                        mean of the windows that cover a cell in ascending window order.  A thread per output element;
 //                        contraction off, one IEEE division.
@@ -18,6 +16,7 @@
 
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
+#include "row_views.hpp"
 
 using namespace nbc;
 
@@ -72,41 +71,23 @@ Axis make_axis(int L, int S, int T, int unit) {
 }
 
 // ---- views ---------------------------------------------------------------------------------------------------------------
-constexpr int kViewThreads = 256;
-constexpr int kSegUnits = 4096;                   // units of a row per block and round: 12 KiB of pixels, 16 KiB of floats
-constexpr int kViewBlocksPerCu = 8;
-
-// GT: the granule (unsigned char / uint32_t); UG: granules per unit (3 / 1).  planes * H source rows of W units; ay / ax in pixels.
+// GT / UG: row_views.hpp.  planes * H source rows of W units; ay / ax in pixels.
 template <typename GT, int UG>
 __global__ __launch_bounds__(kViewThreads) void window_views_kernel(const GT* __restrict__ x, GT* __restrict__ out, long long planes,
                                                                    int H, int W, Axis ay, Axis ax) {
-  constexpr int kPerVec = 16 / (int)sizeof(GT);   // granules of a 16-B vector
-  __shared__ __attribute__((aligned(16))) GT seg[kSegUnits * UG + kPerVec];
+  __shared__ __attribute__((aligned(16))) GT seg[kSegGranules<GT, UG>];
   const int tid = threadIdx.x;
-  const int segs = (W + kSegUnits - 1) / kSegUnits;
-  const long long rows = planes * H, tasks = rows * segs;
+  const int segs = row_segments(W);
+  const long long tasks = planes * H * segs;
   const long long row_g = (long long)W * UG;      // granules of a source row
   const long long wrow_g = (long long)ax.e * UG;  // granules of a window row
 
   for (long long task = blockIdx.x; task < tasks; task += gridDim.x) {
-    const long long r = task / segs;
-    const int u0 = (int)(task % segs) * kSegUnits;
-    const int nu = (W - u0 < kSegUnits) ? W - u0 : kSegUnits;
-    const int ng = nu * UG;                       // granules of this segment
-    const long long p = r / H;
-    const int y = (int)(r % H);
-
-    // ---- the segment into LDS, granule i at seg[a0 + i]: a 16-B aligned global vector is a 16-B aligned LDS vector
-    const GT* src = x + r * row_g + (long long)u0 * UG;
-    const int a0 = (int)((reinterpret_cast<uintptr_t>(src) & 15u) / sizeof(GT));
-    int head = (kPerVec - a0) % kPerVec;
-    if (head > ng) head = ng;
-    const int vecs = (ng - head) / kPerVec;
-    for (int i = tid; i < head; i += kViewThreads) seg[a0 + i] = src[i];
-    for (int v = tid; v < vecs; v += kViewThreads)
-      *reinterpret_cast<uint4*>(&seg[a0 + head + v * kPerVec]) = *reinterpret_cast<const uint4*>(src + head + v * kPerVec);
-    for (int i = head + vecs * kPerVec + tid; i < ng; i += kViewThreads) seg[a0 + i] = src[i];
-    __syncthreads();
+    const RowSegment t = row_segment(task, segs, W);
+    const int u0 = t.u0, nu = t.nu;
+    const long long p = t.row / H;
+    const int y = (int)(t.row % H);
+    const int a0 = stage_segment(x + t.row * row_g + (long long)u0 * UG, nu * UG, seg);
 
     // ---- the rows of the padded frame this source row is: itself, and row 2 (H - 1) - y when that lies in [H, L8)
     for (int pass = 0; pass < 2; ++pass) {
@@ -122,31 +103,7 @@ __global__ __launch_bounds__(kViewThreads) void window_views_kernel(const GT* __
           // the units of the window row that are units of the frame row and lie in the segment: [s0, s1) of the source row
           const int s0 = ox > u0 ? ox : u0;
           int s1 = ox + ax.e < u0 + nu ? ox + ax.e : u0 + nu;   // u0 + nu <= W
-          if (s1 > s0) {
-            const int cg = (s1 - s0) * UG;        // granules to copy
-            const GT* from = &seg[a0 + (s0 - u0) * UG];
-            GT* dst = wrow + (long long)(s0 - ox) * UG;
-            int dhead = (int)(((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) / sizeof(GT));
-            if (dhead > cg) dhead = cg;
-            const int dvecs = (cg - dhead) / kPerVec;
-            for (int i = tid; i < dhead; i += kViewThreads) dst[i] = from[i];
-            for (int v = tid; v < dvecs; v += kViewThreads) {
-              const int t0 = dhead + v * kPerVec;
-              uint32_t w4[4];
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                if constexpr (sizeof(GT) == 4) {
-                  w4[q] = (uint32_t)from[t0 + q];
-                } else {
-                  w4[q] = 0u;
-#pragma unroll
-                  for (int e = 0; e < 4; ++e) w4[q] |= (uint32_t)from[t0 + 4 * q + e] << (8 * e);
-                }
-              }
-              *reinterpret_cast<uint4*>(dst + t0) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-            }
-            for (int i = dhead + dvecs * kPerVec + tid; i < cg; i += kViewThreads) dst[i] = from[i];
-          }
+          if (s1 > s0) emit_run<GT, UG>(wrow + (long long)(s0 - ox) * UG, seg, a0 + (s0 - u0) * UG, s1 - s0, false);
           // the units beyond the frame, [max(ox, W), min(ox + e, L8)): unit xx is unit 2 (W - 1) - xx of the source row
           const int x0 = ox > W ? ox : W;
           const int x1 = ox + ax.e < ax.l ? ox + ax.e : ax.l;
@@ -202,18 +159,13 @@ __global__ __launch_bounds__(kMergeThreads) void window_merge_kernel(const float
   }
 }
 
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // what every entry point refuses of (H, W, S, T); nullptr when the grid is served
 const char* bad_grid(int H, int W, int S, int T) {
   if (S < 32 || S > 2048 || S % NBC_WINDOW_CELL) return "window must be a multiple of 8 in 32..2048";
   if (T < NBC_WINDOW_CELL || T % NBC_WINDOW_CELL || T > S || S > 8 * T)
     return "stride must be a multiple of 8 with 8 <= stride <= window <= 8 * stride";
   if (H < 8 || W < 8) return "bad shape: H, W >= 8";
-  if ((long long)H * W > 0x7fffffffLL) return "bad shape: H * W < 2^31";
+  if (!frame_shape_ok(H, W)) return "bad shape: H * W < 2^31";
   if ((long long)make_axis(H, S, T, 1).n * make_axis(W, S, T, 1).n > NBC_WINDOW_MAX_K) return "more than 1024 windows per image";
   return nullptr;
 }
@@ -221,7 +173,7 @@ const char* bad_grid(int H, int W, int S, int T) {
 const char* bad_stack(int N, int H, int W, int S, int T) {
   if (N < 1) return "bad shape: N >= 1";
   if (const char* why = bad_grid(H, W, S, T)) return why;
-  if ((long long)make_axis(H, S, T, 1).n * make_axis(W, S, T, 1).n * N > 65535) return "bad shape: K * N <= 65535";
+  if (!stack_entries_ok(N, (long long)make_axis(H, S, T, 1).n * make_axis(W, S, T, 1).n)) return "bad shape: K * N <= 65535";
   return nullptr;
 }
 
@@ -244,16 +196,14 @@ extern "C" int nbc_window_views(const void* x_dev, int x_dtype, int N, int H, in
   if (x_dtype != NBC_IN_F32_NCHW && x_dtype != NBC_IN_U8_NHWC) return fail(kWho, NBC_ERR_INVALID, "bad x_dtype");
   if (const char* why = bad_stack(N, H, W, S, T)) return fail(kWho, NBC_ERR_INVALID, why);
   const bool f32 = x_dtype == NBC_IN_F32_NCHW;
-  if (f32 && ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3u))
-    return fail(kWho, NBC_ERR_INVALID, "float32 x_dev and out_dev must be 4-byte aligned");
+  if (f32 && !aligned4(x_dev, out_dev)) return fail(kWho, NBC_ERR_INVALID, "float32 x_dev and out_dev must be 4-byte aligned");
   const Axis ay = make_axis(H, S, T, 1), ax = make_axis(W, S, T, 1);
   const size_t unit = 3 * (f32 ? 4 : 1);
   const size_t in_bytes = (size_t)N * H * W * unit, out_bytes = (size_t)ay.n * ax.n * N * ay.e * ax.e * unit;
   if (ranges_overlap(x_dev, in_bytes, out_dev, out_bytes)) return fail(kWho, NBC_ERR_INVALID, "out_dev must not overlap x_dev");
   const hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const long long planes = (long long)N * (f32 ? 3 : 1);
-  const long long tasks = planes * H * ((W + kSegUnits - 1) / kSegUnits);
-  const dim3 grid(grid_stride_blocks((size_t)tasks, 1, kViewBlocksPerCu));
+  const dim3 grid(row_view_blocks(planes * H, W));
   if (f32)
     hipLaunchKernelGGL((window_views_kernel<uint32_t, 1>), grid, dim3(kViewThreads), 0, s, static_cast<const uint32_t*>(x_dev),
                        static_cast<uint32_t*>(out_dev), planes, H, W, ay, ax);
@@ -271,8 +221,7 @@ extern "C" int nbc_window_merge(const float* lowres_windows_dev, int N, int H, i
   if (!lowres_windows_dev || !merged_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
   if (blend != NBC_BLEND_TENT && blend != NBC_BLEND_UNIFORM) return fail(kWho, NBC_ERR_INVALID, "bad blend");
   if (const char* why = bad_stack(N, H, W, S, T)) return fail(kWho, NBC_ERR_INVALID, why);
-  if ((reinterpret_cast<uintptr_t>(lowres_windows_dev) | reinterpret_cast<uintptr_t>(merged_dev)) & 3u)
-    return fail(kWho, NBC_ERR_INVALID, "float32 pointers must be 4-byte aligned");
+  if (!aligned4(lowres_windows_dev, merged_dev)) return fail(kWho, NBC_ERR_INVALID, "float32 pointers must be 4-byte aligned");
   const Axis ay = make_axis(H, S, T, NBC_WINDOW_CELL), ax = make_axis(W, S, T, NBC_WINDOW_CELL);
   const size_t out_bytes = (size_t)N * 3 * ay.l * ax.l * sizeof(float);
   const size_t in_bytes = (size_t)ay.n * ax.n * N * 3 * ay.e * ax.e * sizeof(float);

@@ -817,29 +817,26 @@ def evaluate_folder(root: str, model_path: str = "./best_model.pt", precision: s
     if WC:
         wrows[:, 0] = -1                                              # a skipped image has no row
 
+    forward, _ = folder_run.stacked_call(T, J, WN)                    # the run's forward: plain, or on its views or windows
+
     def launch(slot, sid, part, x, tgt):
         mdl = r.models[sid]
         if FT:                                                        # the training's frame of the scan and of its dual
             x, tgt = mdl.training_frame(x, (FT, FT)), mdl.training_frame(tgt, (FT, FT))
         n, h, w = x.shape[:3]
         lg = logits_buf[sid][: n * 3 * h * w].view(n, 3, h, w) if loss or ce or CAL or OPS else None
-        low_kw = dict(return_lowres=True) if AL else {}               # --as_logged: the merged low-resolution logits as well
-        if T:                                                         # the same call on the mean of the flip views
-            labels, _, *low = mdl.predict_labels_tta(x, T, labels_dtype=torch.uint8, logits_full=lg, **low_kw)
-        elif NV:                                                      # or of the colour views; each view's own final labels beside it
-            labels, _, *low, _, _, _, vlow = mdl.predict_labels_jitter(x, J, labels_dtype=torch.uint8, logits_full=lg,
-                                                                      return_views=True, **low_kw)
+        kw = dict(labels_dtype=torch.uint8, logits_full=lg,           # __main__.py:323
+                  **(dict(return_lowres=True) if AL else {}))         # --as_logged: the merged low-resolution logits as well
+        if NV:                                                        # the colour views; each view's own final labels beside the mean's
+            labels, _, *low, _, _, _, vlow = forward(mdl, x, return_views=True, **kw)
             vlab, _ = mdl.upsample_argmax(vlow.view((NV * n,) + tuple(vlow.shape[2:])), (h, w), labels_dtype=torch.uint8)
             mdl.remove_small_zones(vlab)
             jring[slot][:, :n].copy_(mdl.confusion(vlab, tgt.repeat(NV, 1, 1)).view(NV, n, 3, 3), non_blocking=True)
-        elif WN is not None:                                          # or on the blend of the crop windows
-            labels, _, *low = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, labels_dtype=torch.uint8, logits_full=lg,
-                                                         **low_kw)
-            if WC:                                                    # the plain forward's final labels beside it
+        else:                                                         # the plain call, or the same on the flip views or the crop windows
+            labels, _, *low = forward(mdl, x, **kw)
+            if WC:                                                    # the plain forward's final labels beside the windows'
                 plab, _ = mdl.predict_labels(x, labels_dtype=torch.uint8, small_zones=True)
                 wring[slot][:n].copy_(mdl.confusion(plab, tgt), non_blocking=True)
-        else:
-            labels, _, *low = mdl.predict_labels(x, labels_dtype=torch.uint8, logits_full=lg, **low_kw)   # __main__.py:323
         if AL:                                                        # copies of their own: nothing of the batch stays alive for them
             for j, k in enumerate(part):
                 kept[k] = (low[0][j].clone(), tgt[j].clone())

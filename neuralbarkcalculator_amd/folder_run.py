@@ -434,7 +434,6 @@ def vote_report(images: Sequence[tuple], draws: int):
 # ---- the flip views the training augmented over (--tta): masks, argument checks, the report -------------------------------
 TTA_CHOICES = ("none", "hflip", "vflip", "flips")
 TTA_MASKS = {"none": 0, "hflip": 3, "vflip": 5, "flips": 15}          # NBC_TTA_* bits of include/nbc.h; identity is bit 0
-TTA_VIEW_NAMES = ("identity", "hflip", "vflip", "hvflip")             # bit 0..3
 
 
 def tta_mask(tta) -> int:
@@ -451,8 +450,9 @@ def tta_mask(tta) -> int:
 
 
 def tta_view_names(mask: int) -> List[str]:
-    """The names of the views of a mask, in the order of the stack (ascending bit order)."""
-    return [TTA_VIEW_NAMES[b] for b in range(4) if (int(mask) >> b) & 1]
+    """``model.tta_view_names``: the names of the views of a mask, in the order of the stack (ascending bit order)."""
+    from .model import tta_view_names as names
+    return names(mask)
 
 
 def check_tta_arguments(tta, tta_votes: bool = False, dropout_draws=None, only_preprocess: bool = False) -> int:
@@ -671,6 +671,21 @@ def check_windows_arch(arch: str) -> None:
     if topology.is_efficientnet(arch):
         raise ValueError("--windows is refused for %s: its output stride is 32 and its fixed asymmetric pads need a window grid "
                          "of their own" % arch)
+
+
+def stacked_call(views_mask: int = 0, factors=None, windows=None):
+    """The forward of a run, picked once from what the three ``check_*_arguments`` returned (at most one is on): ``(predict,
+    make_stack)``.  ``predict(mdl, x, **kw)`` is ``mdl.predict_labels`` or its form on the flip views, the colour views or the
+    crop windows; ``make_stack(mdl, x)`` is the batch that forward runs the network on (what ``autotune`` tunes for)."""
+    if views_mask:
+        return (lambda mdl, x, **kw: mdl.predict_labels_tta(x, views_mask, **kw)), (lambda mdl, x: mdl.tta_views(x, views_mask))
+    if factors is not None:
+        return (lambda mdl, x, **kw: mdl.predict_labels_jitter(x, factors, **kw)), (lambda mdl, x: mdl.jitter_views(x, factors))
+    if windows is not None:
+        wn = windows
+        return ((lambda mdl, x, **kw: mdl.predict_labels_windows(x, wn.window, wn.stride, wn.blend, **kw)),
+                (lambda mdl, x: mdl.window_views(x, wn.window, wn.stride)))
+    return (lambda mdl, x, **kw: mdl.predict_labels(x, **kw)), (lambda mdl, x: x)
 
 
 def windows_report(images: Sequence[tuple], window: int, stride: int, blend: str, compare: bool = False):

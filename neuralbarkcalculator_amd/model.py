@@ -457,12 +457,7 @@ class FCNResNet50:
         views of the mask ``views`` (``resolve_tta_views``) in ascending bit order.  Runs on the current stream."""
         self._require_ctx()
         mask = resolve_tta_views(views)
-        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 4 or x.numel() == 0 or not (
-                (x.dtype == torch.float32 and x.shape[1] == 3) or (x.dtype == torch.uint8 and x.shape[3] == 3)):
-            raise ValueError("x must be a non-empty float32 [N,3,H,W] or uint8 [N,H,W,3] tensor on %s" % (self.device,))
-        x = x.contiguous()
-        f32 = x.dtype == torch.float32
-        n, h, w = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) if f32 else (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
+        x, f32, n, h, w = self._check_model_input(x)
         out = torch.empty((tta_view_count(mask) * n,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.device)
         with self._on_stream() as cur:
             _lib.check(self._lib.nbc_tta_views(x.data_ptr(), _lib.IN_F32_NCHW if f32 else _lib.IN_U8_NHWC, n, h, w, mask,
@@ -476,9 +471,7 @@ class FCNResNet50:
         self._require_ctx()
         mask = resolve_tta_views(views)
         v, n = tta_view_count(mask), int(n)
-        if lowres_views.device != self.device or lowres_views.dtype != torch.float32 or lowres_views.dim() not in (4, 5) \
-                or lowres_views.numel() == 0 or lowres_views.shape[-3] != NUM_CLASSES \
-                or int(np.prod(lowres_views.shape[:-3])) != v * n or n < 1:
+        if self._stack_entries(lowres_views, n) != v:
             raise ValueError("lowres_views must be a non-empty float32 [%d*%d,3,h,w] tensor on %s" % (v, n, self.device))
         lowres_views = lowres_views.contiguous()
         lh, lw = int(lowres_views.shape[-2]), int(lowres_views.shape[-1])
@@ -522,31 +515,42 @@ class FCNResNet50:
         ``dropout_draws`` raises until a plain forward has run."""
         n, h, w = self._check_input(x)
         mask = resolve_tta_views(views)
-        v = tta_view_count(mask)
+
+        def merge(lowres_views):
+            return self.tta_merge(lowres_views, n, mask, True) if return_views else (self.tta_merge(lowres_views, n, mask), None)
+        return self._predict_stacked((n, h, w), tta_view_count(mask), "views", lambda: self.tta_views(x, mask), merge,
+                                     exclude_nodes=exclude_nodes, labels_dtype=labels_dtype, small_zones=small_zones,
+                                     logits_full=logits_full, return_lowres=return_lowres, min_pixels=min_pixels)
+
+    def _predict_stacked(self, shape, count: int, what: str, make_stack, merge, frame=None, *, labels_dtype, min_pixels, logits_full,
+                         **tail):
+        """What ``predict_labels_tta``, ``predict_labels_jitter`` and ``predict_labels_windows`` share, for a checked batch of
+        ``shape = (n, h, w)``: the checks of the arguments they have in common, ``make_stack()`` -- ``count`` views or windows
+        (``what``) of every image, entry-major, each a ``frame`` (default ``h x w``) --, one forward of the ``count * n`` stack,
+        ``merge(lowres f32 [count,n,3,lh,lw])`` -> ``(merged f32 [n,3,.,.], the views to take through the tail one by one or
+        None)``, then ``_views_tail``."""
+        n, h, w = shape
         if labels_dtype not in (torch.int64, torch.uint8):
             raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
         if int(min_pixels) < 0:
             raise ValueError("min_pixels must not be negative")
-        if v * n > 65535:
-            raise ValueError("the stack of %d views of %d images exceeds 65535 entries" % (v, n))
+        if count * n > 65535:
+            raise ValueError("the stack of %d %s of %d images exceeds 65535 entries" % (count, what, n))
         if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
                                         or not logits_full.is_contiguous()
                                         or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
             raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
                                                                                                     self.device))
-        lh, lw = out_hw(h, w, self.ARCH)
-        stack = self.tta_views(x, mask)
-        lowres_views = torch.empty((v * n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
+        fh, fw = frame or (h, w)
+        stack = make_stack()
+        lowres = torch.empty((count, n, NUM_CLASSES) + out_hw(fh, fw, self.ARCH), dtype=torch.float32, device=self.device)
         try:
-            self._forward(stack, v * n, h, w, lowres=lowres_views)
+            self._forward(stack, count * n, fh, fw, lowres=lowres)
         finally:
             self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
-        merged = self.tta_merge(lowres_views, n, mask, return_aligned=return_views)
-        aligned = None
-        if return_views:
-            merged, aligned = merged
-        return self._views_tail(merged, aligned, n, h, w, exclude_nodes, labels_dtype, small_zones, logits_full, return_lowres,
-                                min_pixels)
+        merged, aligned = merge(lowres)
+        return self._views_tail(merged, aligned, n, h, w, labels_dtype=labels_dtype, min_pixels=min_pixels,
+                                logits_full=logits_full, **tail)
 
     def _views_tail(self, merged: torch.Tensor, aligned: Optional[torch.Tensor], n: int, h: int, w: int, exclude_nodes: bool,
                     labels_dtype: torch.dtype, small_zones: bool, logits_full: Optional[torch.Tensor], return_lowres: bool,
@@ -607,14 +611,11 @@ class FCNResNet50:
         ``[V,N,3,h,w]``) -> ``m`` f32 ``[N,3,h,w]``: f32 adds in view order, one IEEE division; V = 1 keeps the view's bits."""
         self._require_ctx()
         n = int(n)
-        if not isinstance(lowres_views, torch.Tensor) or lowres_views.device != self.device or lowres_views.dtype != torch.float32 \
-                or lowres_views.dim() not in (4, 5) or lowres_views.numel() == 0 or lowres_views.shape[-3] != NUM_CLASSES \
-                or n < 1 or int(np.prod(lowres_views.shape[:-3])) % n \
-                or not 1 <= int(np.prod(lowres_views.shape[:-3])) // n <= _lib.JITTER_MAX_VIEWS:
+        v = self._stack_entries(lowres_views, n)
+        if not 1 <= v <= _lib.JITTER_MAX_VIEWS:
             raise ValueError("lowres_views must be a non-empty float32 [V*%d,3,h,w] tensor on %s, V in 1..%d" % (
                 n, self.device, _lib.JITTER_MAX_VIEWS))
         lowres_views = lowres_views.contiguous()
-        v = int(np.prod(lowres_views.shape[:-3])) // n
         lh, lw = int(lowres_views.shape[-2]), int(lowres_views.shape[-1])
         mean = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
         with self._on_stream() as cur:
@@ -641,28 +642,10 @@ class FCNResNet50:
             raise ValueError("predict_labels_jitter takes uint8 [N,H,W,3] frames: a float32 input is refused (torchvision's "
                              "tensor path is other arithmetic)")
         n, h, w = self._check_input(x)
-        v = int(factors.shape[0])
-        if labels_dtype not in (torch.int64, torch.uint8):
-            raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
-        if int(min_pixels) < 0:
-            raise ValueError("min_pixels must not be negative")
-        if v * n > 65535:
-            raise ValueError("the stack of %d views of %d images exceeds 65535 entries" % (v, n))
-        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
-                                        or not logits_full.is_contiguous()
-                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
-            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
-                                                                                                    self.device))
-        lh, lw = out_hw(h, w, self.ARCH)
-        stack = self.jitter_views(x, factors)
-        lowres_views = torch.empty((v, n, NUM_CLASSES, lh, lw), dtype=torch.float32, device=self.device)
-        try:
-            self._forward(stack, v * n, h, w, lowres=lowres_views)
-        finally:
-            self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
-        mean = self.views_mean(lowres_views, n)
-        return self._views_tail(mean, lowres_views if return_views else None, n, h, w, exclude_nodes, labels_dtype, small_zones,
-                                logits_full, return_lowres, min_pixels)
+        return self._predict_stacked((n, h, w), int(factors.shape[0]), "views", lambda: self.jitter_views(x, factors),
+                                     lambda lowres_views: (self.views_mean(lowres_views, n), lowres_views if return_views else None),
+                                     exclude_nodes=exclude_nodes, labels_dtype=labels_dtype, small_zones=small_zones,
+                                     logits_full=logits_full, return_lowres=return_lowres, min_pixels=min_pixels)
 
     # ---- the crop windows the training augmented over (include/nbc.h) ---------
     def window_grid(self, h: int, w: int, window: int = 512, stride: int = 256):
@@ -682,12 +665,7 @@ class FCNResNet50:
         ``[N,H,W,3]``) -> the stack ``[K*N, ...]`` of ``E_y x E_x`` windows in the same layout, window-major (entry ``k * N + i``
         is window k of image i), rows and columns beyond the frame filled by reflection.  Runs on the current stream."""
         self._require_ctx()
-        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 4 or x.numel() == 0 or not (
-                (x.dtype == torch.float32 and x.shape[1] == 3) or (x.dtype == torch.uint8 and x.shape[3] == 3)):
-            raise ValueError("x must be a non-empty float32 [N,3,H,W] or uint8 [N,H,W,3] tensor on %s" % (self.device,))
-        x = x.contiguous()
-        f32 = x.dtype == torch.float32
-        n, h, w = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) if f32 else (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
+        x, f32, n, h, w = self._check_model_input(x)
         ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
         if ny * nx * n > 65535:
             raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (ny * nx, n))
@@ -708,10 +686,7 @@ class FCNResNet50:
         n, h, w = int(n), int(h), int(w)
         ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
         k = ny * nx
-        if not isinstance(lowres_windows, torch.Tensor) or lowres_windows.device != self.device \
-                or lowres_windows.dtype != torch.float32 or lowres_windows.dim() not in (4, 5) or n < 1 \
-                or tuple(lowres_windows.shape[-3:]) != (NUM_CLASSES, ey // 8, ex // 8) \
-                or int(np.prod(lowres_windows.shape[:-3])) != k * n:
+        if self._stack_entries(lowres_windows, n) != k or tuple(lowres_windows.shape[-2:]) != (ey // 8, ex // 8):
             raise ValueError("lowres_windows must be a float32 [%d*%d,3,%d,%d] tensor on %s" % (k, n, ey // 8, ex // 8, self.device))
         if k * n > 65535:
             raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (k, n))
@@ -782,27 +757,10 @@ class FCNResNet50:
         resolve_window_blend(blend)
         n, h, w = self._check_input(x)
         ey, ex, ny, nx, _, _ = window_grid(h, w, window, stride)
-        k = ny * nx
-        if labels_dtype not in (torch.int64, torch.uint8):
-            raise ValueError("labels_dtype must be torch.int64 or torch.uint8")
-        if int(min_pixels) < 0:
-            raise ValueError("min_pixels must not be negative")
-        if k * n > 65535:
-            raise ValueError("the stack of %d windows of %d images exceeds 65535 entries" % (k, n))
-        if logits_full is not None and (logits_full.device != self.device or logits_full.dtype != torch.float32
-                                        or not logits_full.is_contiguous()
-                                        or tuple(logits_full.shape) != (n, NUM_CLASSES, h, w)):
-            raise ValueError("logits_full must be a contiguous float32 [%d,%d,%d,%d] tensor on %s" % (n, NUM_CLASSES, h, w,
-                                                                                                    self.device))
-        stack = self.window_views(x, window, stride)
-        lowres_windows = torch.empty((k * n, NUM_CLASSES, ey // 8, ex // 8), dtype=torch.float32, device=self.device)
-        try:
-            self._forward(stack, k * n, ey, ex, lowres=lowres_windows)
-        finally:
-            self._last_shape = None                  # the context holds the stack's features, not a batch a caller knows
-        merged = self.window_merge(lowres_windows, n, h, w, window, stride, blend)
-        return self._views_tail(merged, None, n, h, w, exclude_nodes, labels_dtype, small_zones, logits_full, return_lowres,
-                                min_pixels)
+        return self._predict_stacked((n, h, w), ny * nx, "windows", lambda: self.window_views(x, window, stride),
+                                     lambda lowres_windows: (self.window_merge(lowres_windows, n, h, w, window, stride, blend), None),
+                                     frame=(ey, ex), exclude_nodes=exclude_nodes, labels_dtype=labels_dtype, small_zones=small_zones,
+                                     logits_full=logits_full, return_lowres=return_lowres, min_pixels=min_pixels)
 
     def lowres_logits(self, x: torch.Tensor) -> torch.Tensor:
         """Output of ``classifier.4`` (models.py:121) before the upsample: f32 ``[N,3,h,w]``."""
@@ -1582,6 +1540,23 @@ class FCNResNet50:
             raise ValueError("Expected more than 1 value per channel when training: a %dx%d image has a 1x1 low-resolution "
                              "map, which per-image BatchNorm statistics cannot normalise" % (h, w))
         return int(n), int(h), int(w)
+
+    def _check_model_input(self, x):
+        """``(x contiguous, is float32, n, h, w)`` of a batch in either layout the model takes, for the view makers."""
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dim() != 4 or x.numel() == 0 or not (
+                (x.dtype == torch.float32 and x.shape[1] == 3) or (x.dtype == torch.uint8 and x.shape[3] == 3)):
+            raise ValueError("x must be a non-empty float32 [N,3,H,W] or uint8 [N,H,W,3] tensor on %s" % (self.device,))
+        f32, s = x.dtype == torch.float32, x.shape
+        return (x.contiguous(), f32, int(s[0])) + ((int(s[2]), int(s[3])) if f32 else (int(s[1]), int(s[2])))
+
+    def _stack_entries(self, lowres, n: int) -> int:
+        """The entries per image of a low-resolution stack, a non-empty float32 ``[E*n,3,h,w]`` (or ``[E,n,3,h,w]``) tensor on
+        this model's device; 0 for anything else.  The callers word their own refusals."""
+        if not isinstance(lowres, torch.Tensor) or lowres.device != self.device or lowres.dtype != torch.float32 \
+                or lowres.dim() not in (4, 5) or lowres.numel() == 0 or lowres.shape[-3] != NUM_CLASSES or n < 1:
+            return 0
+        entries = int(np.prod(lowres.shape[:-3]))
+        return 0 if entries % n else entries // n
 
     def _forward(self, x, n, h, w, logits_full=None, labels=None, counts=None, lowres=None,
                  exclude_nodes=False):

@@ -734,6 +734,7 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
     cring = [(torch.empty(full, dtype=torch.uint8).pin_memory(), torch.empty((batch, cal.WORDS), dtype=torch.int64).pin_memory())
              for _ in range(r.depth)] if C else None
     tuned = set()
+    forward, make_stack = folder_run.stacked_call(T, J, WN)   # the run's forward: plain, or on its views or windows
 
     def launch(slot, sid, part, x):
         (n, h, w), mdl = x.shape[:3], r.models[sid]
@@ -741,40 +742,32 @@ def predict_folder(root: str, model_path: str = "./best_model.pt", precision: st
         if ring[slot][0].numel() < need or ring[slot][1].shape[0] < n:   # an oversized stale processed frame (run_loop)
             ring[slot] = (torch.empty(need, dtype=torch.uint8).pin_memory(), torch.empty((n, 3), dtype=torch.int64).pin_memory())
         if autotune and (sid, (n, h, w)) not in tuned and n == batch and r.shape_count[tuple(x.shape[1:])] >= 2 * batch:
-            mdl.autotune(mdl.tta_views(x, T) if T else (mdl.jitter_views(x, J) if J is not None else
-                                                          (mdl.window_views(x, WN.window, WN.stride) if WN is not None else x)))   # once per distinct full-batch shape and model object
+            mdl.autotune(make_stack(mdl, x))          # once per distinct full-batch shape and model object
             tuned.add((sid, (n, h, w)))
         lg = None
         if C:                                        # the forward writes its full-resolution logits as well
             lg = (logits_buf[sid][: 3 * need] if 3 * need <= logits_buf[sid].numel() else
                   torch.empty(3 * need, dtype=torch.float32, device=dev)).view(n, 3, h, w)
+        kw = dict(exclude_nodes=exclude_nodes, labels_dtype=torch.uint8, small_zones=small_zones,   # models.py:269-276 on the device
+                  **(dict(logits_full=lg) if C else {}))
         if VIEWS:                                   # the same tail on the mean of the views; the views' own figures beside it
             if tring[slot][0].shape[1] < n or (TS and tring[slot][2].numel() < need):
                 tring[slot] = (torch.empty((NV, n, 3), dtype=torch.int64).pin_memory(),
                                torch.empty((n, folder_run.VOTE_STATS), dtype=torch.int64).pin_memory(),
                                torch.empty(need if TS else 0, dtype=torch.uint8).pin_memory())
-            on_views = (lambda **k: mdl.predict_labels_tta(x, T, **k)) if T else (lambda **k: mdl.predict_labels_jitter(x, J, **k))
-            labels, counts, vcounts, sup, tstats, _ = on_views(exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                               small_zones=small_zones, return_views=True,
-                                                               **(dict(logits_full=lg) if C else {}))
+            labels, counts, vcounts, sup, tstats, _ = forward(mdl, x, return_views=True, **kw)
             tring[slot][0][:, :n].copy_(vcounts, non_blocking=True)
             tring[slot][1][:n].copy_(tstats, non_blocking=True)
             if TS:
                 tring[slot][2][:need].copy_(sup.reshape(-1), non_blocking=True)
-        elif WN is not None:                         # the same tail on the blend of the windows
-            labels, counts = mdl.predict_labels_windows(x, WN.window, WN.stride, WN.blend, exclude_nodes=exclude_nodes,
-                                                        labels_dtype=torch.uint8, small_zones=small_zones,
-                                                        **(dict(logits_full=lg) if C else {}))
-            if WN.compare:                           # the plain forward beside it: its counts and where its labels differ
+        else:                                        # the plain forward, or the same tail on the blend of the windows
+            labels, counts = forward(mdl, x, **kw)
+            if WN is not None and WN.compare:        # the plain forward beside it: its counts and where its labels differ
                 if wring[slot][0].shape[0] < n:
                     wring[slot] = (torch.empty((n, 3), dtype=torch.int64).pin_memory(), torch.empty((n, 3, 3), dtype=torch.int64).pin_memory())
                 plabels, pcounts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8, small_zones=small_zones)
                 wring[slot][0][:n].copy_(pcounts, non_blocking=True)
                 wring[slot][1][:n].copy_(mdl.confusion(labels, plabels * 127), non_blocking=True)   # grey 0 / 127 / 254: classes 0 / 1 / 2
-        else:
-            labels, counts = mdl.predict_labels(x, exclude_nodes=exclude_nodes, labels_dtype=torch.uint8,
-                                                small_zones=small_zones,   # models.py:269-276 on the device
-                                                **(dict(logits_full=lg) if C else {}))
         ring[slot][0][:need].copy_(labels.reshape(-1), non_blocking=True)
         ring[slot][1][:n].copy_(counts, non_blocking=True)
         if C:                                        # the raw softmax of the forward: no target, the plane on

@@ -1,6 +1,7 @@
-"""Are the convolution kernels of two source trees the same device code?  (no GPU: hipcc --cuda-device-only -S)
-    python scripts/same_kernels.py OTHER_CSRC [THIS_CSRC]
-Compiles conv_igemm_dma.hip and conv3x3_rows.hip of both directories with build.py's flags and compares, kernel by kernel, the
+"""Are the kernels of two source trees the same device code?  (no GPU: hipcc --cuda-device-only -S)
+    python scripts/same_kernels.py OTHER_CSRC [THIS_CSRC] [--files NAME.hip ...]
+Compiles the named files (default: the convolution kernels, conv_igemm_dma.hip and conv3x3_rows.hip) of both directories with
+build.py's flags and compares, kernel by kernel, the
 text between the kernel's label and its .Lfunc_end without `;` comments and without the function number inside local labels
 (.LBB27_89 / .LBB33_89): all that a changed order of instantiation changes.  Exit status 1 when a kernel is missing or differs."""
 import os, re, subprocess, sys, tempfile
@@ -20,9 +21,12 @@ def kernels(csrc, name):
     return out
 
 
-other, this = sys.argv[1], (sys.argv[2:] + [os.path.join(os.path.dirname(__file__), "..", "neuralbarkcalculator_amd", "csrc")])[0]
+argv, files = sys.argv[1:], ["conv_igemm_dma.hip", "conv3x3_rows.hip"]
+if "--files" in argv:
+    argv, files = argv[:argv.index("--files")], argv[argv.index("--files") + 1:]
+other, this = argv[0], (argv[1:] + [os.path.join(os.path.dirname(__file__), "..", "neuralbarkcalculator_amd", "csrc")])[0]
 bad = 0
-for name in ("conv_igemm_dma.hip", "conv3x3_rows.hip"):
+for name in files:
     a, b = kernels(other, name), kernels(this, name)
     differ = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
     print(f"{name}: {len(a)} / {len(b)} kernels, {len(differ)} missing or different")

@@ -46,7 +46,8 @@ def stream():
 
 
 # ---- 1. the views kernel ---------------------------------------------------------------------------------------------------
-VIEW_SHAPES = [(1, 1, 1), (2, 5, 7), (3, 40, 72), (1, 129, 65), (1, 8, 21), (1, 8, 22)]
+# (1, 2, 4101): a row longer than the mover's segment of 4096 units -- a second segment of five units whose mirror lands at the row's start
+VIEW_SHAPES = [(1, 1, 1), (2, 5, 7), (3, 40, 72), (1, 129, 65), (1, 8, 21), (1, 8, 22), (1, 2, 4101)]
 VIEW_MASKS = [15, 3, 5, 9, 1, 10]
 
 

@@ -55,7 +55,10 @@ def same_floats(got, want):
 
 
 # ---- 1. the views kernel ---------------------------------------------------------------------------------------------------
-CASES = [(1, 8, 8, 32, 8), (2, 13, 21, 32, 16), (1, 40, 75, 32, 16), (3, 129, 65, 64, 32), (1, 64, 64, 64, 64), (1, 72, 200, 64, 24)]
+# (1, 9, 4101, 2048, 1024): a row longer than the mover's segment of 4096 units -- four windows across, a reflected row band (rows
+# 9..15 of the padded 16) and three reflected columns that fall in the short last segment
+CASES = [(1, 8, 8, 32, 8), (2, 13, 21, 32, 16), (1, 40, 75, 32, 16), (3, 129, 65, 64, 32), (1, 64, 64, 64, 64), (1, 72, 200, 64, 24),
+         (1, 9, 4101, 2048, 1024)]
 
 
 @pytest.mark.parametrize("case", CASES)

@@ -243,6 +243,40 @@ def test_library_keywords_are_refused_alike(built_lib):
         m.tta_views(torch.zeros((1, 3, 64, 64)))
 
 
+def test_stacked_predicts_refuse_their_common_arguments_alike(built_lib, monkeypatch):
+    """predict_labels_tta, predict_labels_jitter and predict_labels_windows word the refusals of the arguments they share the
+    same way, before anything reaches a device: the batch check is stood in for, so no context is needed."""
+    m = mdl.FCNResNet50("fp32")
+    m.device = torch.device("cpu")
+    x = torch.zeros((1, 64, 64, 3), dtype=torch.uint8)
+    calls = [("views", 4, lambda **kw: m.predict_labels_tta(x, "flips", **kw)),
+             ("views", 5, lambda **kw: m.predict_labels_jitter(x, "training", **kw)),
+             ("windows", 9, lambda **kw: m.predict_labels_windows(x, 32, 16, **kw))]       # 64 x 64 in windows of 32 every 16: 3 x 3
+    for what, count, call in calls:
+        monkeypatch.setattr(m, "_check_input", lambda x: (2, 64, 64))
+        for kw, text in [(dict(labels_dtype=torch.int32), "labels_dtype must be torch.int64 or torch.uint8"),
+                         (dict(min_pixels=-1), "min_pixels must not be negative"),
+                         (dict(logits_full=torch.zeros((2, 3, 64, 32))), "logits_full must be a contiguous float32 [2,3,64,64] tensor on cpu"),
+                         (dict(logits_full=torch.zeros((2, 3, 64, 64), dtype=torch.float64)),
+                          "logits_full must be a contiguous float32 [2,3,64,64] tensor on cpu"),
+                         (dict(logits_full=torch.zeros((2, 3, 64, 128))[..., ::2]),
+                          "logits_full must be a contiguous float32 [2,3,64,64] tensor on cpu")]:
+            with pytest.raises(ValueError) as e:
+                call(**kw)
+            assert str(e.value) == text, (what, kw)
+        n = 65535 // count + 1
+        monkeypatch.setattr(m, "_check_input", lambda x: (n, 64, 64))
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == "the stack of %d %s of %d images exceeds 65535 entries" % (count, what, n)
+        with pytest.raises(ValueError) as e:                          # the order of the refusals
+            call(labels_dtype=torch.float32, min_pixels=-1, logits_full=x)
+        assert str(e.value) == "labels_dtype must be torch.int64 or torch.uint8"
+        with pytest.raises(ValueError) as e:
+            call(min_pixels=-1, logits_full=x)
+        assert str(e.value) == "min_pixels must not be negative"
+
+
 def test_folders_of_the_support_only_with_the_flag(tmp_path):
     for tag, on in (("off", False), ("on", True)):
         root = tmp_path / tag
