@@ -859,6 +859,101 @@ int nbc_bilinear_taps(int in_size, int out_size, int32_t* first, int32_t* coeff)
 int nbc_training_frame(const void* x_dev, int channels, int N, int H, int W, int Ht, int Wt, const int32_t* row_taps_dev,
                        const int32_t* col_taps_dev, void* out_dev, void* hip_stream);
 
+/* ---- refit of classifier.4: the loss's gradient on the device ------------------------------------
+ * classifier.4 (models.py:121) is a 1x1 convolution 512 -> 3 with bias: 1 539 parameters, linear in the features the forward
+ * leaves on the device.  These calls evaluate the pixel-wise cross-entropy family and its gradient with respect to those
+ * parameters, through the bicubic upsample, for parameters other than the checkpoint's (the host restatement
+ * and the driver are neuralbarkcalculator_amd/refit.py; the kernels csrc/head_refit.hip).  Gradients into classifier.0 or the
+ * backbone, the Lovasz-Softmax gradient and the DeepLab / EfficientNet heads are left out.
+ *
+ * theta = (W f32 [3][512], b f32 [3]) in the state_dict's units: classifier.4.weight[:, :, 0, 0], then classifier.4.bias, 1 539
+ * floats in that order.  Per image n, with P = H * W and (h, w) = nbc_lowres_size(H, W):
+ *   1 trial logits   lowres = b + W X, X the stored input of classifier.4 as the last nbc_forward left it, through the forward's
+ *                    own classifier.4 launch (lane l owns channels 8l .. 8l+7, an f32 fma chain, a 64-lane xor tree, then the
+ *                    bias).  In NBC_PREC_F16X2 the stored X carries the power of two 2^a of its tensor
+ *                    (nbc_activation_exponent("classifier.0")) and the weights are multiplied by 2^-a on the device, exactly as
+ *                    nbc_pack_weights does: with theta the checkpoint's values the result is BITWISE nbc_forward's
+ *                    logits_lowres, in every precision.
+ *   2 full size      nbc_upsample_argmax on those logits: logits_full f32 [N,3,H,W] and the argmax p (first maximum wins).
+ *   3 loss           nbc_pixel_cross_entropy: sums[n][t][p], counts[n][t][p].  For a table T of nine doubles indexed
+ *                    [target class t][argmax class p] the objective of an image is sum T[t][p] sums[t][p]; over a folder that,
+ *                    summed over the images and divided by the sum of their P.  T = 1: the plain cross-entropy; T[t][p] = w[t]:
+ *                    the class-weighted one; T[t][p] = w[max(t, p)]: CustomWeightedCrossEntropy (utils.py:151-165).
+ *   4 pixel gradient from the f32 logits_full in f64: m = max_c x_c, q_c = exp(x_c - m) / sum_k exp(x_k - m),
+ *                    g_c = T[t][p] (q_c - [c = t]).  T[t][p] is a constant of the pixel (what autograd makes of the reference's
+ *                    index_select of the weights); t from the grey level as nbc_confusion derives it.  No special case for a
+ *                    logit that is not finite: NaN propagates.
+ *   5 upsample adjoint  with the per-axis tables of nbc_bicubic_taps (iy, cy for h -> H; ix, cx for w -> W):
+ *                    grad_lowres[n][c][i][j] = sum over (Y, a) with iy[Y][a] = i and (X, b) with ix[X][b] = j of
+ *                    (double)cy[Y][a] (double)cx[X][b] g_c[Y][X], in f64, not normalised (no 1 / P).  Evaluated as the column
+ *                    pass sum_(X, b) (double)cx g (X ascending over lo[j] .. hi[j], then b ascending), then the row pass on its
+ *                    results (Y ascending over lo[i] .. hi[i], then a ascending).
+ *   6 head gradient  grad_theta[n][c][k] = sum over the cells of grad_lowres[n][c][cell] (double)X[cell][k] for k < 512,
+ *                    grad_theta[n][c][512] = sum over the cells of grad_lowres[n][c][cell]: f64 [N][3][513] in the state_dict's
+ *                    units (the sums over the stored X times 2^-a, exact).
+ *   7 determinism    every float sum has an order fixed by (H, W, h, w) alone and nothing is added atomically: an image's
+ *                    numbers are bit-identical alone, anywhere in a batch and on any stream. */
+
+/* Trial logits (1).  theta_dev: 1 539 floats on the device, 4-byte aligned; logits_lowres_dev: float32 [N,3,h,w], overwritten.
+ * Enqueues on hip_stream -- the stream of the forward, or one ordered behind it -- and does not synchronise.  The context's
+ * activations are read; of the context only a 1 539-float scratch array (allocated by the first call) and the sticky non-finite
+ * word (a logit that is not finite raises it, as in nbc_forward) are written.
+ * NBC_ERR_INVALID, before any HIP call: a null ctx, theta_dev or logits_lowres_dev; either one not 4-byte aligned; N < 1 or
+ * N > 65535, H or W < 1, H * W >= 2^31.
+ * NBC_ERR_STATE: nbc_dropout_draws' contract -- unless the context's last forward was an NBC_ARCH_FCN_RESNET50 forward of exactly
+ * this (N, H, W) and nothing has touched its plan since.  Both BatchNorm modes and all three precisions are served. */
+int nbc_head_logits(nbc_ctx* ctx, const float* theta_dev, int N, int H, int W, float* logits_lowres_dev, void* hip_stream);
+
+/* The tap table of one axis of the bicubic upsample in_size -> out_size (align_corners = False), host only, no HIP call:
+ * cubic_setup's arithmetic (csrc/pointwise.hip) in f32 with every operation rounded on its own (no fused multiply-add, so
+ * that any host reproduces the table): scale = (float)in_size / (float)out_size, s = scale (o + 0.5) - 0.5,
+ * i0 = min(floor(s), in_size - 1), t = s - i0 clamped to [0, 1], taps i0 - 1 .. i0 + 2 clamped to [0, in_size - 1], and
+ * ATen's get_cubic_upsample_coefficients(t) with A = -0.75.
+ * idx    int32 [out_size][4]; coeff  float32 [out_size][4]
+ * lo, hi int32 [in_size]: lo[i] .. hi[i] is the range of outputs o with a tap on input i; i0 is monotone in o, so the range is
+ *        contiguous.  An input that no output touches (in_size > out_size) gets lo = 0, hi = -1.
+ * NBC_ERR_INVALID: a null pointer, in_size or out_size outside 1 .. 2^24. */
+int nbc_bicubic_taps(int in_size, int out_size, int32_t* idx, float* coeff, int32_t* lo, int32_t* hi);
+
+/* Pixel gradient and upsample adjoint (4, 5).  No context.
+ * logits_full_dev  float32 [N,3,H,W], 4-byte aligned (an image whose three planes start on 16-byte boundaries is read by 16-byte
+ *                  loads); target_dev  uint8 [N,H,W] grey levels
+ * h, w             the low-resolution size, 1 <= h <= H, 1 <= w <= W
+ * row_*_dev        nbc_bicubic_taps(h, H) on the device: idx int32 [H][4] and coeff float32 [H][4], both 16-byte aligned, lo and
+ *                  hi int32 [h].  col_*_dev: likewise nbc_bicubic_taps(w, W).  The caller uploads them: the library makes no
+ *                  hidden copy.  A foreign table's indices are only compared and its lo / hi are clamped into the axis: no read
+ *                  leaves the buffers whatever the tables hold.
+ * table9_host      HOST memory, T[t][p] as nine doubles (read before the call returns)
+ * workspace_dev    at least nbc_ce_gradient_workspace_bytes(N, H, W, h, w) bytes, 256-byte aligned; contents scratch.  With
+ *                  A(x) = x rounded up to a multiple of 256 and P' = H W rounded up to even:  A(24 N P') + A(24 N H w)
+ *                  (g as f64 planes; the column pass's result)
+ * grad_lowres_dev  float64 [N,3,h,w], 8-byte aligned; overwritten
+ * Three launches: the pixel pass reads 13 P and writes 24 P bytes per image, the column pass reads those 24 P and writes 24 H w,
+ * the row pass reads 24 H w and writes 24 h w.  Runs on hip_stream (the caller's current device); no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer (any of the fourteen); N < 1 or N > 65535, H or W < 1, H * W >= 2^31;
+ * h < 1, w < 1, h > H or w > W; an idx or coeff table that is not 16-byte aligned; logits_full_dev or a lo / hi table that is not
+ * 4-byte aligned; grad_lowres_dev not 8-byte aligned; a workspace too small or not 256-byte aligned.
+ * nbc_ce_gradient_workspace_bytes returns 0 for a shape nbc_ce_gradient refuses. */
+size_t nbc_ce_gradient_workspace_bytes(int N, int H, int W, int h, int w);
+int nbc_ce_gradient(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int h, int w,
+                    const int32_t* row_idx_dev, const float* row_coeff_dev, const int32_t* row_lo_dev, const int32_t* row_hi_dev,
+                    const int32_t* col_idx_dev, const float* col_coeff_dev, const int32_t* col_lo_dev, const int32_t* col_hi_dev,
+                    const double* table9_host, void* workspace_dev, size_t workspace_bytes, double* grad_lowres_dev,
+                    void* hip_stream);
+
+/* Head gradient (6): one read of X (2 048 bytes per cell; 1 024 in NBC_PREC_BF16), a block per 64 consecutive cells, a second
+ * launch adds the blocks' partials in block order.
+ * grad_lowres_dev  float64 [N,3,h,w], (h, w) = nbc_lowres_size(H, W); 8-byte aligned
+ * workspace_dev    at least nbc_head_gradient_workspace_bytes(N, H, W) = A(8 * 1539 N ceil(h w / 64)) bytes, 256-byte aligned
+ * grad_theta_dev   float64 [N][3][513], 8-byte aligned; overwritten
+ * Stream semantics and NBC_ERR_STATE as nbc_head_logits; nothing of the context is written.
+ * NBC_ERR_INVALID, before any HIP call: a null ctx, grad_lowres_dev, workspace_dev or grad_theta_dev; grad_lowres_dev or
+ * grad_theta_dev not 8-byte aligned; N < 1 or N > 65535, H or W < 1, H * W >= 2^31; a workspace too small or not 256-byte
+ * aligned.  nbc_head_gradient_workspace_bytes returns 0 for a shape nbc_head_gradient refuses. */
+size_t nbc_head_gradient_workspace_bytes(int N, int H, int W);
+int nbc_head_gradient(nbc_ctx* ctx, const double* grad_lowres_dev, int N, int H, int W, void* workspace_dev,
+                      size_t workspace_bytes, double* grad_theta_dev, void* hip_stream);
+
 /* ---- the zones of a label map ------------------------------------------------------------------
  * What the two percentages of an image are made of: how many nodes there are, how big each one is, where it lies, and
  * whether the bark is one sheet or many fragments.  The reference has no such code; the host restatement is

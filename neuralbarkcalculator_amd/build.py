@@ -14,7 +14,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(PKG, "libnbc_hip.so")
 SOURCES = ["nbc_net.cpp", "nbc_plan.cpp", "conv_tiles.cpp", "conv_igemm_dma.hip", "conv3x3_rows.hip", "pointwise.hip", "small_zones.hip", "nbc_api.hip", "confusion.hip",
            "aspp.hip", "bn_stats.hip", "efficientnet.hip", "lovasz.hip", "dataset_stats.hip", "pixel_ce.hip", "dropout_head.hip", "dropout_votes.hip", "zones.hip",
-           "zone_match.hip", "contours.hip", "tta.hip", "softmax_census.hip", "jitter.hip", "windows.hip", "training_frame.hip", "offset_sweep.hip"]
+           "zone_match.hip", "contours.hip", "tta.hip", "softmax_census.hip", "jitter.hip", "windows.hip", "training_frame.hip", "offset_sweep.hip", "head_refit.hip"]
 ARCH = "gfx950"
 
 

@@ -95,6 +95,7 @@ struct nbc_ctx {
   // the stored input of classifier.4): cleared by whatever parks the plan, retunes it or attaches other weights
   bool fwd_valid = false;
   int fwd_N = 0, fwd_H = 0, fwd_W = 0;
+  DeviceBuffer refit_theta;                 // nbc_head_logits: the caller's theta as classifier.4 reads it (kHeadThetaFloats)
 };
 
 namespace {
@@ -1137,6 +1138,70 @@ int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids
                       void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
   return dropout_passes("nbc_dropout_draws", c, N, H, W, image_ids_host, p, seed, first_draw, draws, min_pixels, exclude_nodes,
                         logits_lowres_dev, counts_dev, false, nullptr, 0, workspace_dev, workspace_bytes, hip_stream);
+}
+
+// What nbc_head_logits and nbc_head_gradient ask of the context (nbc_dropout_draws' contract): its last forward was an
+// NBC_ARCH_FCN_RESNET50 forward of this (N, H, W) and its plan stands untouched.  *head: the plan's classifier.4.
+static int refit_state(const char* who, nbc_ctx* c, int N, int H, int W, const Op** head) {
+  if (c->arch != kArchFcn)
+    return fail(who, NBC_ERR_STATE, std::string("NBC_ARCH_FCN_RESNET50 only, the context holds ") + arch_name(c->arch));
+  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
+    return fail(who, NBC_ERR_STATE, "the context's last forward was not one of this (N, H, W), or its plan has been touched since: run "
+                                    "nbc_forward first");
+  *head = nullptr;
+  for (const Op& o : c->plan.ops)
+    if (o.kind == OP_HEAD1X1) *head = &o;
+  if (!*head || (*head)->Ci != 512 || (*head)->in_buf < 0 || !c->nonfinite)
+    return fail(who, NBC_ERR_STATE, "the plan holds no classifier.4 of 512 input channels");
+  return NBC_OK;
+}
+
+// the power of two the stored input of classifier.4 carries (f16x2; 0 otherwise)
+static int head_input_exponent(const nbc_ctx* c) {
+  int a = 0;
+  return stored_exponent(c, "classifier.0", &a) ? a : 0;
+}
+
+int nbc_head_logits(nbc_ctx* c, const float* theta_dev, int N, int H, int W, float* logits_lowres_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_head_logits";
+  if (!c || !theta_dev || !logits_lowres_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!aligned4(theta_dev, logits_lowres_dev)) return fail(kWho, NBC_ERR_INVALID, "theta_dev and logits_lowres_dev must be 4-byte aligned");
+  if (!per_image_shape_ok(N, H, W)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  const Op* head = nullptr;
+  if (int rc = refit_state(kWho, c, N, H, W, &head)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  NBC_HIP(c->refit_theta.reserve(kHeadThetaFloats * sizeof(float)));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  float* theta = c->refit_theta.as<float>();
+  NBC_HIP(launch_head_theta(theta_dev, theta, head_input_exponent(c), s));
+  NBC_HIP(launch_head1x1(c->bufs[head->in_buf].get(), 512, theta, theta + 3 * 512, logits_lowres_dev, N, c->plan.h * c->plan.w,
+                         c->precision, nullptr, c->nonfinite.as<unsigned>(), s));
+  return NBC_OK;
+}
+
+size_t nbc_head_gradient_workspace_bytes(int N, int H, int W) {
+  if (!per_image_shape_ok(N, H, W)) return 0;
+  int h = 0, w = 0;
+  if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1) return 0;
+  return align256((size_t)8 * N * head_grad_blocks(h * w) * kHeadThetaFloats);
+}
+
+int nbc_head_gradient(nbc_ctx* c, const double* grad_lowres_dev, int N, int H, int W, void* workspace_dev, size_t workspace_bytes,
+                      double* grad_theta_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_head_gradient";
+  if (!c || !grad_lowres_dev || !workspace_dev || !grad_theta_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(grad_lowres_dev) | reinterpret_cast<uintptr_t>(grad_theta_dev)) & 7u)
+    return fail(kWho, NBC_ERR_INVALID, "grad_lowres_dev and grad_theta_dev must be 8-byte aligned");
+  const size_t need = nbc_head_gradient_workspace_bytes(N, H, W);
+  if (need == 0) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, need)) return rc;
+  const Op* head = nullptr;
+  if (int rc = refit_state(kWho, c, N, H, W, &head)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  NBC_HIP(launch_head_gradient(c->bufs[head->in_buf].get(), grad_lowres_dev, N, c->plan.h * c->plan.w, c->precision,
+                               head_input_exponent(c), static_cast<double*>(workspace_dev), grad_theta_dev,
+                               static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
 }
 
 int nbc_dropout_votes(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,

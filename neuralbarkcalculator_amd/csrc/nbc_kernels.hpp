@@ -1,5 +1,5 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, contours.hip, aspp.hip, bn_stats.hip and
-// efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
+// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, contours.hip, aspp.hip, bn_stats.hip,
+// head_refit.hip and efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
 // convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
 #pragma once
@@ -116,6 +116,17 @@ hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bi
 // draws <= 65535 (a 16-bit field per class), votes 16-byte aligned for the vector path; labels at any address.
 hipError_t launch_vote_accumulate(const unsigned char* labels, int draws, int N, long long P, uint32_t* votes, bool first,
                                   hipStream_t s);
+// The refit of classifier.4 (head_refit.hip; the definitions: include/nbc.h, nbc_head_logits / nbc_head_gradient).
+// launch_head_theta: theta f32 [3][512] then [3] in state_dict units -> out, the 1536 weights times 2^-a (exact: what
+// nbc_pack_weights stores for a tensor read at the power 2^a), the bias copied; launch_head1x1 on `out` then runs classifier.4
+// with the caller's parameters in the forward's own machine code.
+constexpr int kHeadThetaFloats = 3 * 512 + 3;
+hipError_t launch_head_theta(const float* theta, float* out, int a, hipStream_t s);
+// d theta [N][3][513] f64 = sum over the hw cells of g [N][3][hw] f64 times x [N][hw][512] stored elements (column 512: the
+// plain sum, the bias), times 2^-a on the 512 weight columns.  One read of x; part: head_grad_blocks(hw) * N * 1539 doubles.
+inline int head_grad_blocks(int hw) { return (hw + 63) / 64; }      // a block owns 64 consecutive cells
+hipError_t launch_head_gradient(const void* x, const double* g, int N, int hw, int precision, int a, double* part, double* out,
+                                hipStream_t s);
 // ASPP pooling branch of every DeepLab head (aspp.hip), per image: mean over hw pixels of x [N][hw][cin] (stored elements; cin a
 // multiple of 64, at most 4096), the 1x1 conv with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout]
 // elements.  Workspaces: partial N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.

@@ -287,6 +287,27 @@ def bilinear_taps(n_in: int, n_out: int):
     return first, coeff
 
 
+def bicubic_taps(n_in: int, n_out: int):
+    """One axis of the bicubic upsample ``n_in -> n_out`` as a table (nbc_bicubic_taps, include/nbc.h): ``(idx int32 [n_out, 4],
+    coeff float32 [n_out, 4], lo int32 [n_in], hi int32 [n_in])`` -- the four clamped taps of every output with ATen's f32
+    coefficients (A = -0.75), and per input the contiguous range of outputs that touch it.  ``ValueError`` for sizes outside
+    1 .. 2^24.  No device is touched."""
+    try:
+        n_in, n_out = int(n_in), int(n_out)
+    except (TypeError, ValueError):
+        raise ValueError("bicubic_taps takes integers, got %r" % ((n_in, n_out),))
+    if not (0 < n_in <= 2 ** 24 and 0 < n_out <= 2 ** 24):
+        raise ValueError("bicubic_taps: sizes out of range in %r" % ((n_in, n_out),))
+    idx = np.zeros((n_out, 4), dtype=np.int32)
+    coeff = np.zeros((n_out, 4), dtype=np.float32)
+    lo, hi = np.zeros(n_in, dtype=np.int32), np.zeros(n_in, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    if _lib.load().nbc_bicubic_taps(n_in, n_out, idx.ctypes.data_as(i32), coeff.ctypes.data_as(C.POINTER(C.c_float)),
+                                    lo.ctypes.data_as(i32), hi.ctypes.data_as(i32)) != 0:
+        raise ValueError(_lib.last_error())
+    return idx, coeff, lo, hi
+
+
 class FCNResNet50:
     """MI355X-native ``fcn_resnet50`` (3 classes, output stride 8, bicubic upsample), eval mode.
 
@@ -330,6 +351,9 @@ class FCNResNet50:
         self._contours_ws: Optional[torch.Tensor] = None   # nbc_contour_distances', likewise
         self._census_ws: Optional[torch.Tensor] = None     # nbc_softmax_census', likewise
         self._sweep_ws: Optional[torch.Tensor] = None      # nbc_offset_sweep's, likewise
+        self._ce_grad_ws: Optional[torch.Tensor] = None    # nbc_ce_gradient's, likewise
+        self._head_grad_ws: Optional[torch.Tensor] = None  # nbc_head_gradient's, likewise
+        self._bicubic_taps: dict = {}                      # ce_gradient: the device tables of each (n_in, n_out)
         self._logit_offsets: Tuple[float, float] = (0.0, 0.0)   # set_logit_offsets: (bark, node), (0, 0) = off
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
         self._frame_taps: dict = {}                        # training_frame: the device table of each frame length
@@ -1016,6 +1040,99 @@ class FCNResNet50:
                                                          sums.data_ptr(), counts.data_ptr(), cur.cuda_stream),
                        "nbc_pixel_cross_entropy")
         return sums, counts
+
+    # ---- the refit of classifier.4 (include/nbc.h; the driver: refit.py) -------------------------------------
+    def _refit_theta(self, theta) -> torch.Tensor:
+        """theta as 1 539 contiguous float32 on this device: ``classifier.4.weight`` [3, 512] then ``classifier.4.bias`` [3]."""
+        t = theta if isinstance(theta, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(theta))
+        if t.dtype != torch.float32 or t.numel() != NUM_CLASSES * 513:
+            raise ValueError("theta must hold 1539 float32 (classifier.4.weight [3,512], then classifier.4.bias [3])")
+        return t.reshape(-1).to(self.device).contiguous()
+
+    def _refit_last_shape(self, what: str) -> Tuple[int, int, int]:
+        self._require_weights()
+        if self._last_shape is None:
+            raise RuntimeError("%s follows a forward (predict_labels / lowres_logits) of this object: none has run" % what)
+        return self._last_shape
+
+    def head_logits(self, theta) -> torch.Tensor:
+        """``classifier.4`` with the parameters ``theta`` (1 539 float32 in the state_dict's units: the weight [3, 512], then the
+        bias) on the features the LAST forward of this object left on the device (nbc_head_logits), on the current stream.
+        Returns the low-resolution logits f32 ``[N,3,h,w]``; with the checkpoint's own values they are bit for bit the
+        forward's.  ``RuntimeError``: no forward has run, its plan has been touched since, or another network than
+        fcn_resnet50."""
+        n, h, w = self._refit_last_shape("head_logits")
+        th = self._refit_theta(theta)
+        out = torch.empty((n, NUM_CLASSES) + out_hw(h, w, self.ARCH), dtype=torch.float32, device=self.device)
+        with self._on_stream() as cur:
+            rc = self._lib.nbc_head_logits(self._ctx, th.data_ptr(), n, h, w, out.data_ptr(), cur.cuda_stream)
+        _lib.check(rc, "nbc_head_logits")
+        return out
+
+    def _taps_on_device(self, n_in: int, n_out: int):
+        key = (int(n_in), int(n_out))
+        if key not in self._bicubic_taps:
+            self._bicubic_taps[key] = tuple(torch.from_numpy(a).to(self.device) for a in bicubic_taps(*key))
+        return self._bicubic_taps[key]
+
+    def ce_gradient(self, logits_full: torch.Tensor, target: torch.Tensor, lowres_size, table) -> torch.Tensor:
+        """The gradient of ``sum T[t][p] ce`` of each image with respect to its low-resolution logits (nbc_ce_gradient):
+        ``g_c = T[t][p] (softmax_c - [c = t])`` per pixel in f64, then the adjoint of the bicubic upsample ``lowres_size`` ->
+        ``(H, W)`` with the tables of ``bicubic_taps`` (uploaded once per length).  ``logits_full`` and ``target`` as
+        ``pixel_cross_entropy`` takes them; ``table``: nine numbers ``T[target class][argmax class]``.  Returns f64
+        ``[N,3,h,w]``, not normalised; on the current stream."""
+        self._require_ctx()
+        n, h, w = self._check_logits_target(logits_full, target)
+        lh, lw = int(lowres_size[0]), int(lowres_size[1])
+        tab = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1))
+        if tab.size != 9:
+            raise ValueError("table must hold nine numbers T[target class][argmax class]")
+        need = int(self._lib.nbc_ce_gradient_workspace_bytes(n, h, w, lh, lw))
+        if need == 0:
+            raise ValueError("nbc_ce_gradient refuses a [%d,3,%d,%d] batch with a %dx%d low-resolution map (N <= 65535, H * W < 2^31, "
+                             "1 <= h <= H, 1 <= w <= W)" % (n, h, w, lh, lw))
+        rows, cols = self._taps_on_device(lh, h), self._taps_on_device(lw, w)
+        out = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float64, device=self.device)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_ce_grad_ws", need, cur)
+            rc = self._lib.nbc_ce_gradient(logits_full.data_ptr(), target.data_ptr(), n, h, w, lh, lw,
+                                           *[t.data_ptr() for t in rows + cols], tab.ctypes.data_as(C.POINTER(C.c_double)),
+                                           ws.data_ptr(), ws.numel(), out.data_ptr(), cur.cuda_stream)
+        _lib.check(rc, "nbc_ce_gradient")
+        return out
+
+    def head_gradient(self, grad_lowres: torch.Tensor) -> torch.Tensor:
+        """``grad_lowres`` f64 ``[N,3,h,w]`` (``ce_gradient``) carried onto the parameters of ``classifier.4`` through the features
+        of the LAST forward (nbc_head_gradient): f64 ``[N,3,513]`` per image, a class's 512 weight columns and then its bias, in
+        the state_dict's units.  On the current stream; the refusals of ``head_logits``."""
+        n, h, w = self._refit_last_shape("head_gradient")
+        lh, lw = out_hw(h, w, self.ARCH)
+        if not isinstance(grad_lowres, torch.Tensor) or grad_lowres.device != self.device or grad_lowres.dtype != torch.float64 \
+                or not grad_lowres.is_contiguous() or tuple(grad_lowres.shape) != (n, NUM_CLASSES, lh, lw):
+            raise ValueError("grad_lowres must be a contiguous float64 [%d,3,%d,%d] tensor on %s" % (n, lh, lw, self.device))
+        need = int(self._lib.nbc_head_gradient_workspace_bytes(n, h, w))
+        if need == 0:
+            raise ValueError("nbc_head_gradient refuses a [%d,3,%d,%d] batch" % (n, h, w))
+        out = torch.empty((n, NUM_CLASSES, 513), dtype=torch.float64, device=self.device)
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_head_grad_ws", need, cur)
+            rc = self._lib.nbc_head_gradient(self._ctx, grad_lowres.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                             cur.cuda_stream)
+        _lib.check(rc, "nbc_head_gradient")
+        return out
+
+    def head_loss_and_gradient(self, target: torch.Tensor, theta, table, logits_full: Optional[torch.Tensor] = None):
+        """The loss cells and their gradient for trial parameters ``theta`` on the images of the LAST forward: ``head_logits`` ->
+        ``upsample_argmax`` -> ``pixel_cross_entropy`` -> ``ce_gradient`` -> ``head_gradient``.  ``target``: the uint8 ``[N,H,W]``
+        grey masks of that forward's images; ``table`` as ``ce_gradient`` takes it; ``logits_full``: an optional f32
+        ``[N,3,H,W]`` buffer for the upsampled logits.  Returns ``(sums f64 [N,3,3], counts int64 [N,3,3], grad f64 [N,3,513])``
+        per image: the objective of the batch is ``sum(table * sums)`` and its gradient ``grad.sum(0)``, both not normalised."""
+        n, h, w = self._refit_last_shape("head_loss_and_gradient")
+        low = self.head_logits(theta)
+        _, _, full = self.upsample_argmax(low, (h, w), labels_dtype=torch.uint8, return_logits=True, logits_full=logits_full)
+        sums, counts = self.pixel_cross_entropy(full, target)
+        grad = self.head_gradient(self.ce_gradient(full, target, low.shape[2:], table))
+        return sums, counts, grad
 
     def softmax_census(self, logits_full: torch.Tensor, target: Optional[torch.Tensor] = None,
                        confidence: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
