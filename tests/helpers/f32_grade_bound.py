@@ -120,11 +120,15 @@ def _per_channel(v):
     return np.asarray(v, dtype=np.float64).reshape(1, -1, 1, 1)
 
 
-def conv_unit_reference(x, w, precision, alpha, beta, res, relu, stride, pad, dil):
+def conv_unit_reference(x, w, precision, alpha, beta, res, relu, stride, pad, dil, pads=None):
     """x, res: f32 arrays as read back; w: the checkpoint's f32 weights.  Returns y_ref, A = sum |w~| |x~| (both float64) and, for
-    f16x2, T = 2^-k sum_{0 < |P| < 2^-3} |x~| (None where no weight is that small, and for fp32)."""
+    f16x2, T = 2^-k sum_{0 < |P| < 2^-3} |x~| (None where no weight is that small, and for fp32).  pads = (before, after): zero
+    rows / columns before the top / left and after the bottom / right edge in place of `pad` on every side (the TF-"same" pads of
+    the EfficientNet stem)."""
     wt, k, p = held_weights(w, precision)
     xh = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if pads is not None:
+        xh, pad = F.pad(xh, (pads[0], pads[1], pads[0], pads[1])), 0
     kw = dict(stride=stride, padding=pad, dilation=dil)
     with torch.no_grad():
         z = F.conv2d(xh.double(), torch.from_numpy(wt), **kw).numpy()

@@ -18,7 +18,9 @@ def frames(idx, h, w):
 
 
 def conv_out(size, u):
-    return (size + 2 * u.pad - u.dil * (u.k - 1) - 1) // u.stride + 1
+    """a unit's output size; the EfficientNet units carry a bottom / right pad of their own (TF "same", from the native size)"""
+    after = u.pad if u.pad_after is None else u.pad_after
+    return (size + u.pad + after - u.dil * (u.k - 1) - 1) // u.stride + 1
 
 
 def plan_of(arch, precision, n, h, w):
@@ -37,7 +39,11 @@ def plan_of(arch, precision, n, h, w):
             shapes[name] = (n, 256, 1, 1)
         elif name == "classifier.0.concat":
             shapes[name] = (n, 1280) + shapes[reads[(name, "cat0")]][2:]
-        elif name in units and units[name].bn is not None:
+        elif name.endswith(".swish"):                       # in place: its producer's buffer
+            shapes[name] = src
+        elif name in units and units[name].kind == "se_expand":
+            shapes[name] = (n, units[name].cout, 1, 1)       # the gate
+        elif name in units and units[name].bn is not None:   # the depthwise convs with their two pads too
             u = units[name]
             shapes[name] = (n, u.cout, conv_out(src[2], u), conv_out(src[3], u))
     return names, reads, shapes, tiles
