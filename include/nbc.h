@@ -864,7 +864,8 @@ int nbc_training_frame(const void* x_dev, int channels, int N, int H, int W, int
  * leaves on the device.  These calls evaluate the pixel-wise cross-entropy family and its gradient with respect to those
  * parameters, through the bicubic upsample, for parameters other than the checkpoint's (the host restatement
  * and the driver are neuralbarkcalculator_amd/refit.py; the kernels csrc/head_refit.hip).  Gradients into classifier.0 or the
- * backbone, the Lovasz-Softmax gradient and the DeepLab / EfficientNet heads are left out.
+ * backbone, gradients of pooled groups (nbc_lovasz_softmax_groups) and the DeepLab / EfficientNet heads are left out.  The
+ * Lovasz-Softmax gradient and MixedLoss's (utils.py:185-192) come in at item 4 through nbc_lovasz_gradient below.
  *
  * theta = (W f32 [3][512], b f32 [3]) in the state_dict's units: classifier.4.weight[:, :, 0, 0], then classifier.4.bias, 1 539
  * floats in that order.  Per image n, with P = H * W and (h, w) = nbc_lowres_size(H, W):
@@ -940,6 +941,50 @@ int nbc_ce_gradient(const float* logits_full_dev, const uint8_t* target_dev, int
                     const int32_t* col_idx_dev, const float* col_coeff_dev, const int32_t* col_lo_dev, const int32_t* col_hi_dev,
                     const double* table9_host, void* workspace_dev, size_t workspace_bytes, double* grad_lowres_dev,
                     void* hip_stream);
+
+/* The Lovasz-Softmax gradient, alone or beside the cross-entropy family's (MixedLoss, utils.py:185-192): nbc_lovasz_softmax's
+ * terms and, in place of item 4, the pixel gradient of  sum T'[t][p] ce + lambda L,  L = (1 / C_p) sum over the present classes of
+ * terms[n][c] the image's Lovasz-Softmax loss (C_p = the classes with fg_counts > 0); then item 5 by the same two launches.  No
+ * context; csrc/lovasz.hip.  Per image and class c, on the keys nbc_lovasz_softmax sorts (key = bits(e) << 1 | fg, e = |fg - p_c| in
+ * f32, descending):
+ *   slope     J(k, F) = 1 - (G - F) / (G + k - F) with G the class's foreground count, k keys counted, F of them foreground
+ *             (J(0, 0) = 0).  A pixel's key lies in a run of identical keys that starts at position r, is R keys long and has F_r
+ *             foreground keys before it; every pixel of the run gets the run's mean slope
+ *             [J(r + R, F_r + fg R) - J(r, F_r)] / R -- on an image without ties the reference's J_i - J_(i-1) at the pixel's
+ *             position; with ties (which torch.sort leaves open) independent of the pixel order, equal e putting foreground first.
+ *   d_c       - sign(fg - p_c) slope / C_p: negative for a foreground pixel, positive for a background one, 0 where e == 0
+ *             (torch's abs'(0)) and for an absent class.  The order, the sign and the e == 0 test come from the f32 keys.
+ *   softmax   g_k = q_k (d_k - sum_c d_c q_c), c ascending, q in f64 from the f32 logits as in item 4.
+ *   pixel     g_k = T'[t][p] (q_k - [k = t]) + lambda (the above); the first term only with a table, the second only with
+ *             lambda != 0 (with lambda == 0 the planes are nbc_ce_gradient's bit for bit).
+ *   not finite  an image whose softmax is not finite somewhere has NaN terms (as nbc_lovasz_softmax) and, with lambda != 0, NaN in
+ *             every pixel and so in every cell of its grad_lowres; no other image is touched.
+ * logits_full_dev .. col_hi_dev   as nbc_ce_gradient takes them
+ * table9_host      HOST memory, T' as nine doubles, already scaled by the caller; may be null (no cross-entropy term)
+ * lovasz_weight    lambda, finite
+ * workspace_dev    at least nbc_lovasz_gradient_workspace_bytes(N, H, W, h, w) bytes, 256-byte aligned; contents scratch.  With
+ *                  A(x) = x rounded up to a multiple of 256 and P = H W:
+ *                  nbc_lovasz_workspace_bytes(N, H, W) + 2 A(12 N P) + A(24 N P) + A(24 N H w)
+ *                  (the terms' regions; the keys in pixel order and the foreground prefix; g; the column pass's result)
+ * terms_dev, fg_counts_dev   float64 / int64 [N,3], 8-byte aligned: nbc_lovasz_softmax's outputs from its own launches, bit for bit
+ * grad_lowres_dev  float64 [N,3,h,w], 8-byte aligned; overwritten, not normalised
+ * keys_dev         nullable: uint32 [N,3,H,W], 4-byte aligned, the keys in pixel order (else they live in the workspace)
+ * pixel_grad_dev   nullable: float64 [N,3,H,W], 8-byte aligned, the g planes (else they live in the workspace)
+ * After nbc_lovasz_softmax's launches (a device-to-device copy of the 12 P bytes of keys per image among them): the prefix pass
+ * reads 12 P and writes 12 P bytes per image; the pixel pass reads 13 P + 12 P, about log2(P) + 2 dependent 4-byte loads per
+ * (pixel, class) into the sorted segment and one into the prefix, and writes 24 P; then the column and row passes.  Every float
+ * sum has an order fixed by the shape, nothing is added atomically: item 7 holds.  Runs on hip_stream; no synchronisation.
+ * NBC_ERR_INVALID, before any HIP call: a null pointer other than table9_host, keys_dev and pixel_grad_dev; what nbc_ce_gradient
+ * refuses of the shape, the tables and logits_full_dev; a lovasz_weight that is not finite; terms_dev, fg_counts_dev,
+ * grad_lowres_dev or pixel_grad_dev not 8-byte aligned; keys_dev not 4-byte aligned; a workspace too small or not 256-byte
+ * aligned.  nbc_lovasz_gradient_workspace_bytes returns 0 for a shape nbc_lovasz_gradient refuses. */
+size_t nbc_lovasz_gradient_workspace_bytes(int N, int H, int W, int h, int w);
+int nbc_lovasz_gradient(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int h, int w,
+                        const int32_t* row_idx_dev, const float* row_coeff_dev, const int32_t* row_lo_dev, const int32_t* row_hi_dev,
+                        const int32_t* col_idx_dev, const float* col_coeff_dev, const int32_t* col_lo_dev, const int32_t* col_hi_dev,
+                        const double* table9_host, double lovasz_weight, void* workspace_dev, size_t workspace_bytes,
+                        double* terms_dev, int64_t* fg_counts_dev, double* grad_lowres_dev, uint32_t* keys_dev,
+                        double* pixel_grad_dev, void* hip_stream);
 
 /* Head gradient (6): one read of X (2 048 bytes per cell; 1 024 in NBC_PREC_BF16), a block per 64 consecutive cells, a second
  * launch adds the blocks' partials in block order.

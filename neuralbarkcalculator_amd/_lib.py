@@ -162,6 +162,9 @@ SIGNATURES = {
     "nbc_ce_gradient_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nbc_ce_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 +
                         [C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "nbc_lovasz_gradient_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nbc_lovasz_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 +
+                            [C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
     "nbc_head_gradient_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nbc_head_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_void_p]),

@@ -28,6 +28,7 @@
 
 #include <cmath>
 
+#include "ce_gradient.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 #include "stored.hpp"
@@ -45,29 +46,16 @@ constexpr int kCellsPerBlock = 4 * kCellsPerWave;       // = the 64 of head_grad
 
 using u32 = unsigned;
 
-struct CeTable {
-  double t[9];                                          // T[target class][argmax class]
-};
-
 __global__ __launch_bounds__(kThreads) void head_theta_scale(const float* __restrict__ theta, float* __restrict__ out, int neg_a) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i < kHeadThetaFloats) out[i] = i < kClasses * kCin ? ldexpf(theta[i], neg_a) : theta[i];
 }
 
-// g_c = T[t][p] (q_c - [c = t]) of one pixel, q = softmax in f64 from the f32 logits; p as the forward's argmax decides it
+// g_c = T[t][p] (q_c - [c = t]) of one pixel (ce_gradient.hpp), q = softmax in f64 from the f32 logits
 __device__ __forceinline__ void pixel_gradient(float a, float b, float c, u32 grey, const CeTable& T, double (&g)[3]) {
-  const double x0 = (double)a, x1 = (double)b, x2 = (double)c;
-  const double m = fmax(fmax(x0, x1), x2);
-  const double e0 = exp(x0 - m), e1 = exp(x1 - m), e2 = exp(x2 - m);
-  const double s = e0 + e1 + e2;
-  const u32 t = target_class(grey);
-  const u32 cell = t * 3u + (u32)argmax3(a, b, c);
-  double wgt = T.t[0];
-#pragma unroll
-  for (int k = 1; k < 9; ++k) wgt = cell == (u32)k ? T.t[k] : wgt;
-  g[0] = wgt * (e0 / s - (t == 0u ? 1.0 : 0.0));
-  g[1] = wgt * (e1 / s - (t == 1u ? 1.0 : 0.0));
-  g[2] = wgt * (e2 / s - (t == 2u ? 1.0 : 0.0));
+  double q[3];
+  pixel_softmax(a, b, c, q);
+  pixel_gradient(a, b, c, grey, T, q, g);
 }
 
 // grid = (ceil(P / 1024), N); gw: f64 [N][3][Pp], Pp = P rounded up to even
@@ -321,6 +309,19 @@ hipError_t launch_head_gradient(const void* x, const double* g, int N, int hw, i
   return hipGetLastError();
 }
 
+hipError_t launch_bicubic_adjoint(const double* g, long long g_plane, int N, int H, int W, int h, int w, const BicubicTaps& t,
+                                  double* cols, double* out, hipStream_t s) {
+  if (N < 1 || N > 65535 || h < 1 || w < 1 || h > H || w > W) return hipErrorInvalidValue;
+  // along the rows of the image: every full-resolution row Y is a row of W values, the planes g_plane apart
+  hipLaunchKernelGGL(ce_col_adjoint, dim3((unsigned)(((long long)H * w + kThreads - 1) / kThreads), (unsigned)N), dim3(kThreads), 0, s, g,
+                     g_plane, H, W, w, reinterpret_cast<const int4*>(t.col_idx), reinterpret_cast<const float4*>(t.col_coeff), t.col_lo,
+                     t.col_hi, cols);
+  hipLaunchKernelGGL(ce_row_adjoint, dim3((unsigned)(((long long)h * w + kThreads - 1) / kThreads), (unsigned)N), dim3(kThreads), 0, s,
+                     cols, H, w, h, reinterpret_cast<const int4*>(t.row_idx), reinterpret_cast<const float4*>(t.row_coeff), t.row_lo,
+                     t.row_hi, out);
+  return hipGetLastError();
+}
+
 }  // namespace nbc
 
 using namespace nbc;
@@ -379,12 +380,9 @@ extern "C" int nbc_ce_gradient(const float* logits_full_dev, const uint8_t* targ
   CeLayout L;
   if (!ce_layout(N, H, W, h, w, &L))
     return fail(kCeWho, NBC_ERR_INVALID, std::string(kPerImageShape) + ", 1 <= h <= H and 1 <= w <= W");
-  const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if ((addr(row_idx_dev) | addr(row_coeff_dev) | addr(col_idx_dev) | addr(col_coeff_dev)) & 15u)
-    return fail(kCeWho, NBC_ERR_INVALID, "the tap index and coefficient tables must be 16-byte aligned");
-  if (!aligned4(logits_full_dev, row_lo_dev, row_hi_dev, col_lo_dev, col_hi_dev))
-    return fail(kCeWho, NBC_ERR_INVALID, "logits_full_dev and the lo / hi tables must be 4-byte aligned");
-  if (addr(grad_lowres_dev) & 7u) return fail(kCeWho, NBC_ERR_INVALID, "grad_lowres_dev must be 8-byte aligned");
+  const BicubicTaps taps{row_idx_dev, row_coeff_dev, row_lo_dev, row_hi_dev, col_idx_dev, col_coeff_dev, col_lo_dev, col_hi_dev};
+  if (int rc = check_taps(kCeWho, logits_full_dev, taps)) return rc;
+  if (reinterpret_cast<uintptr_t>(grad_lowres_dev) & 7u) return fail(kCeWho, NBC_ERR_INVALID, "grad_lowres_dev must be 8-byte aligned");
   if (int rc = check_workspace(kCeWho, workspace_dev, workspace_bytes, L.total)) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   char* ws = static_cast<char*>(workspace_dev);
@@ -396,14 +394,7 @@ extern "C" int nbc_ce_gradient(const float* logits_full_dev, const uint8_t* targ
   const long long per_block = (long long)kThreads * kGroup;
   hipLaunchKernelGGL(ce_pixel_gradient, dim3((unsigned)((P + per_block - 1) / per_block), (unsigned)N), dim3(kThreads), 0, s,
                      logits_full_dev, target_dev, P, L.Pp, T, g);
-  // along the rows of the image: every full-resolution row Y is a row of W values, the planes L.Pp apart
-  hipLaunchKernelGGL(ce_col_adjoint, dim3((unsigned)(((long long)H * w + kThreads - 1) / kThreads), (unsigned)N), dim3(kThreads), 0, s, g,
-                     L.Pp, H, W, w, reinterpret_cast<const int4*>(col_idx_dev), reinterpret_cast<const float4*>(col_coeff_dev), col_lo_dev,
-                     col_hi_dev, cols);
-  hipLaunchKernelGGL(ce_row_adjoint, dim3((unsigned)(((long long)h * w + kThreads - 1) / kThreads), (unsigned)N), dim3(kThreads), 0, s,
-                     cols, H, w, h, reinterpret_cast<const int4*>(row_idx_dev), reinterpret_cast<const float4*>(row_coeff_dev), row_lo_dev,
-                     row_hi_dev, grad_lowres_dev);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_bicubic_adjoint(g, L.Pp, N, H, W, h, w, taps, cols, grad_lowres_dev, s);
   if (e != hipSuccess) return fail(kCeWho, NBC_ERR_HIP, hipGetErrorString(e));
   return NBC_OK;
 }

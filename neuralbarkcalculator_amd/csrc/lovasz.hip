@@ -25,10 +25,17 @@
 // of the g images stacked along the height.  Only lovasz_keys knows about images: it writes the key of (image n, class c,
 // pixel i) to segment (n / G, c) at (n mod G) P + i.  Everything after it works on segments whose length Segments::pixels
 // gives (the last group may be shorter); the per-image pass is the case G = 1, same kernels, same tiles, same bits.
+//
+// The gradient (nbc_lovasz_gradient, per image) follows the same launches: a copy of the keys in pixel order before the sort, then
+//   lovasz_fg_prefix       the foreground keys before every position of the sorted segment (lovasz_partial's running count),
+//   lovasz_pixel_gradient  per pixel and class the run of its key in the sorted segment (a binary search), the run's mean slope,
+//                          the softmax Jacobian in f64, the table's cross-entropy term beside it: three f64 planes per image,
+// and the adjoint of the bicubic upsample (launch_bicubic_adjoint, head_refit.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
+#include "ce_gradient.hpp"
 #include "reduce.hpp"
 
 using namespace nbc;
@@ -372,6 +379,135 @@ __global__ __launch_bounds__(64) void lovasz_finish(const double* __restrict__ p
   terms[seg] = s;
 }
 
+// ---- the gradient (nbc_lovasz_gradient; the definitions: include/nbc.h) ------------------------------------------------------
+// prefix[i] = foreground keys before position i of the sorted segment: lovasz_partial's running count, written out
+__global__ __launch_bounds__(kSortThreads) void lovasz_fg_prefix(const u32* __restrict__ keys, Segments sg, int T,
+                                                                 const u32* __restrict__ tile_fg, const u64* __restrict__ G,
+                                                                 const u32* __restrict__ flag, u32* __restrict__ prefix) {
+  const int n = blockIdx.y, seg = n * kClasses + blockIdx.z, t = blockIdx.x;
+  const long long P = sg.pixels(n);
+  if (segment_idle(G, flag, n, seg) || (long long)t * kTile >= P) return;
+  __shared__ u32 red[kWaves];
+  __shared__ u32 wfg[kWaves];
+  __shared__ u32 fg_before_tile;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  u32 c = 0;
+  for (int u = tid; u < t; u += kSortThreads) c += tile_fg[(size_t)seg * T + u];
+  block_sum_to(c, red, &fg_before_tile);
+
+  const long long start = (long long)t * kTile;
+  const int nt = (int)min((long long)kTile, P - start);
+  const size_t at = sg.keys_at(n, blockIdx.z) + start;
+  u32 fg[kItems];
+  u32 mine = 0;
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    fg[j] = idx < nt ? keys[at + idx] & 1u : 0u;
+    mine += fg[j];
+  }
+  mine = wave_sum(mine);
+  if (lane == 0) wfg[w] = mine;
+  __syncthreads();
+  u32 run = fg_before_tile;                          // foreground keys before this wave's first key
+  for (int k = 0; k < w; ++k) run += wfg[k];
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int idx = w * (kItems * 64) + j * 64 + lane;
+    const u64 m = __ballot(fg[j] != 0);
+    if (idx < nt) prefix[at + idx] = run + (u32)__popcll(m & lanes_below(lane));
+    run += (u32)__popcll(m);
+  }
+}
+
+// J(k, F) = 1 - (G - F) / (G + k - F): the Jaccard loss once k sorted keys are counted, F of them foreground; J(0, 0) = 0
+__device__ __forceinline__ double jaccard_at(long long G, long long k, long long F) {
+  return 1.0 - (double)(G - F) / ((double)G + (double)(k - F));
+}
+
+// One thread per pixel and image.  Per class with a live segment and e > 0: the run of the pixel's key in the sorted segment
+// (the lower bound of the three classes in lockstep, its number of rounds fixed by P; the run's end by doubling steps, since a
+// run is one key long unless errors tie), the foreground keys before it, the run's mean slope in closed form, d_c = -+ slope /
+// C_p.  Then g_k = q_k (d_k - sum_c d_c q_c) with q in f64 (ce_gradient.hpp), times lambda, beside the table's term.
+// gw: f64 [N][3][P].  A key that is not where the sort must have put it gives NaN, never a quiet number.
+__global__ __launch_bounds__(kKeyThreads) void lovasz_pixel_gradient(const float* __restrict__ logits, const unsigned char* __restrict__ target,
+                                                                     const u32* __restrict__ pixel_keys, const u32* __restrict__ sorted,
+                                                                     const u32* __restrict__ prefix, const u64* __restrict__ G,
+                                                                     const u32* __restrict__ flag, long long P, CeTable T, int has_table,
+                                                                     double lambda, double* __restrict__ gw) {
+  const long long i = (long long)blockIdx.x * kKeyThreads + threadIdx.x;
+  if (i >= P) return;
+  const int n = blockIdx.y;
+  const size_t img = (size_t)n * kClasses * P;
+  const float a = logits[img + i], b = logits[img + P + i], c = logits[img + 2 * P + i];
+  double q[3], g[3] = {0.0, 0.0, 0.0};
+  pixel_softmax(a, b, c, q);
+  if (has_table) pixel_gradient(a, b, c, target[(size_t)n * P + i], T, q, g);
+  if (lambda != 0.0) {
+    double lov[3];
+    if (flag[n]) {
+      lov[0] = lov[1] = lov[2] = __builtin_nan("");
+    } else {
+      long long Gc[kClasses];
+      u32 key[kClasses];
+      bool need[kClasses];
+      int present = 0;
+#pragma unroll
+      for (int k = 0; k < kClasses; ++k) {
+        Gc[k] = (long long)G[n * kClasses + k];
+        present += Gc[k] > 0;
+        key[k] = pixel_keys[img + (size_t)k * P + i];
+        need[k] = Gc[k] > 0 && (key[k] >> 1) != 0u;
+      }
+      // keys above the pixel's own in the descending segment: the lower bound, three searches side by side
+      long long lo[kClasses] = {0, 0, 0};
+      for (long long len = P; len > 1;) {
+        const long long half = len >> 1;
+#pragma unroll
+        for (int k = 0; k < kClasses; ++k)
+          if (need[k] && sorted[img + (size_t)k * P + lo[k] + half - 1] > key[k]) lo[k] += half;
+        len -= half;
+      }
+      double d[kClasses] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < kClasses; ++k) {
+        if (!need[k]) continue;
+        const u32* s = sorted + img + (size_t)k * P;
+        long long r = lo[k];
+        r += s[r] > key[k];
+        if (r >= P || s[r] != key[k]) {
+          d[k] = __builtin_nan("");
+          continue;
+        }
+        long long first = r + 1, last = P;            // the run's end lies in [first, last]
+        for (long long step = 1; r + step < P; step <<= 1) {
+          if (s[r + step] != key[k]) {
+            last = r + step;
+            break;
+          }
+          first = r + step + 1;
+        }
+        while (first < last) {
+          const long long mid = first + ((last - first) >> 1);
+          if (s[mid] == key[k]) first = mid + 1; else last = mid;
+        }
+        const long long run = first - r, F = (long long)prefix[img + (size_t)k * P + r];
+        const bool fg = key[k] & 1u;
+        const double slope = (jaccard_at(Gc[k], first, F + (fg ? run : 0)) - jaccard_at(Gc[k], r, F)) / (double)run / (double)present;
+        d[k] = fg ? -slope : slope;
+      }
+      const double dot = d[0] * q[0] + d[1] * q[1] + d[2] * q[2];
+#pragma unroll
+      for (int k = 0; k < kClasses; ++k) lov[k] = q[k] * (d[k] - dot);
+    }
+#pragma unroll
+    for (int k = 0; k < kClasses; ++k) g[k] = has_table ? g[k] + lambda * lov[k] : lambda * lov[k];
+  }
+  gw[img + i] = g[0];
+  gw[img + P + i] = g[1];
+  gw[img + 2 * P + i] = g[2];
+}
+
 struct Layout {
   size_t keys_a, keys_b, hist, base, tile_fg, partial, flag, total;
 };
@@ -400,9 +536,10 @@ bool layout(int N, int H, int W, int G, Layout* L) {
   return true;
 }
 
-// the per-image pass is the grouped one with groups of one image
+// the per-image pass is the grouped one with groups of one image.  pixel_keys (nullable; nbc_lovasz_gradient, group = 1): a copy of
+// the keys in pixel order [N][3][P], taken before the sort's first pass; the launches around it are the same either way.
 int run(const char* who, const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int group, void* workspace_dev,
-        size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream) {
+        size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev, void* hip_stream, u32* pixel_keys = nullptr) {
   if (!logits_full_dev || !target_dev || !workspace_dev || !terms_dev || !fg_counts_dev) return fail(who, NBC_ERR_INVALID, "null argument");
   if (!per_image_shape_ok(N, H, W)) return fail(who, NBC_ERR_INVALID, kPerImageShape);
   Layout L;
@@ -431,6 +568,10 @@ int run(const char* who, const float* logits_full_dev, const uint8_t* target_dev
   if (bx < 1) bx = 1;
   hipLaunchKernelGGL(lovasz_keys, dim3((unsigned)bx, (unsigned)N), dim3(kKeyThreads), 0, s, logits_full_dev, target_dev, sg, keys[0], G,
                      flag);
+  if (pixel_keys) {
+    e = hipMemcpyAsync(pixel_keys, keys[0], sizeof(u32) * (size_t)kClasses * N * (size_t)P, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return fail(who, NBC_ERR_HIP, hipGetErrorString(e));
+  }
   const dim3 tiles((unsigned)T, (unsigned)NG, (unsigned)kClasses);
   for (int pass = 0; pass < kPasses; ++pass) {
     const int shift = 8 * pass;
@@ -449,7 +590,83 @@ int run(const char* who, const float* logits_full_dev, const uint8_t* target_dev
   return NBC_OK;
 }
 
+struct GradLayout {
+  Layout terms;                                        // nbc_lovasz_softmax's regions, first
+  size_t pixel_keys, prefix, g, cols, total;
+};
+
+// byte offsets of nbc_lovasz_gradient's workspace regions (include/nbc.h states the sum); false for a shape the call refuses
+bool grad_layout(int N, int H, int W, int h, int w, GradLayout* L) {
+  if (!layout(N, H, W, 1, &L->terms) || h < 1 || w < 1 || h > H || w > W) return false;
+  const size_t planes = (size_t)kClasses * N * (size_t)H * (size_t)W;
+  Carver ws;
+  ws.take(L->terms.total);
+  L->pixel_keys = ws.take(4 * planes);
+  L->prefix = ws.take(4 * planes);
+  L->g = ws.take(8 * planes);
+  L->cols = ws.take((size_t)8 * kClasses * N * (size_t)H * w);
+  L->total = ws.offset;
+  return true;
+}
+
+constexpr const char* kWhoGrad = "nbc_lovasz_gradient";
+
 }  // namespace
+
+extern "C" size_t nbc_lovasz_gradient_workspace_bytes(int N, int H, int W, int h, int w) {
+  GradLayout L;
+  return grad_layout(N, H, W, h, w, &L) ? L.total : 0;
+}
+
+extern "C" int nbc_lovasz_gradient(const float* logits_full_dev, const uint8_t* target_dev, int N, int H, int W, int h, int w,
+                                   const int32_t* row_idx_dev, const float* row_coeff_dev, const int32_t* row_lo_dev,
+                                   const int32_t* row_hi_dev, const int32_t* col_idx_dev, const float* col_coeff_dev,
+                                   const int32_t* col_lo_dev, const int32_t* col_hi_dev, const double* table9_host, double lovasz_weight,
+                                   void* workspace_dev, size_t workspace_bytes, double* terms_dev, int64_t* fg_counts_dev,
+                                   double* grad_lowres_dev, uint32_t* keys_dev, double* pixel_grad_dev, void* hip_stream) {
+  if (!logits_full_dev || !target_dev || !row_idx_dev || !row_coeff_dev || !row_lo_dev || !row_hi_dev || !col_idx_dev || !col_coeff_dev ||
+      !col_lo_dev || !col_hi_dev || !workspace_dev || !terms_dev || !fg_counts_dev || !grad_lowres_dev)
+    return fail(kWhoGrad, NBC_ERR_INVALID, "null argument");
+  GradLayout L;
+  if (!grad_layout(N, H, W, h, w, &L))
+    return fail(kWhoGrad, NBC_ERR_INVALID, std::string(kPerImageShape) + ", 1 <= h <= H and 1 <= w <= W");
+  if (!std::isfinite(lovasz_weight)) return fail(kWhoGrad, NBC_ERR_INVALID, "lovasz_weight must be finite");
+  const BicubicTaps taps{row_idx_dev, row_coeff_dev, row_lo_dev, row_hi_dev, col_idx_dev, col_coeff_dev, col_lo_dev, col_hi_dev};
+  if (int rc = check_taps(kWhoGrad, logits_full_dev, taps)) return rc;
+  const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((addr(grad_lowres_dev) | addr(terms_dev) | addr(fg_counts_dev) | addr(pixel_grad_dev)) & 7u)
+    return fail(kWhoGrad, NBC_ERR_INVALID, "terms_dev, fg_counts_dev, grad_lowres_dev and pixel_grad_dev must be 8-byte aligned");
+  if (addr(keys_dev) & 3u) return fail(kWhoGrad, NBC_ERR_INVALID, "keys_dev must be 4-byte aligned");
+  if (int rc = check_workspace(kWhoGrad, workspace_dev, workspace_bytes, L.total)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  char* ws = static_cast<char*>(workspace_dev);
+  u32* pixel_keys = keys_dev ? keys_dev : reinterpret_cast<u32*>(ws + L.pixel_keys);
+  u32* prefix = reinterpret_cast<u32*>(ws + L.prefix);
+  double* g = pixel_grad_dev ? pixel_grad_dev : reinterpret_cast<double*>(ws + L.g);
+  double* cols = reinterpret_cast<double*>(ws + L.cols);
+  // the terms: nbc_lovasz_softmax's launches on the first region, the keys copied in pixel order on the way
+  if (int rc = run(kWhoGrad, logits_full_dev, target_dev, N, H, W, 1, ws, L.terms.total, terms_dev, fg_counts_dev, hip_stream, pixel_keys))
+    return rc;
+  const u32* sorted = reinterpret_cast<const u32*>(ws + L.terms.keys_a);   // where run's even number of passes ends
+  const u32* tile_fg = reinterpret_cast<const u32*>(ws + L.terms.tile_fg);
+  const u32* flag = reinterpret_cast<const u32*>(ws + L.terms.flag);
+  const u64* G = reinterpret_cast<const u64*>(fg_counts_dev);
+  const Segments sg{(long long)H * W, N, 1};
+  const long long P = sg.P;
+  const int T = sg.tiles(0);
+  CeTable tab{};
+  if (table9_host)
+    for (int k = 0; k < 9; ++k) tab.t[k] = table9_host[k];
+  if (lovasz_weight != 0.0)
+    hipLaunchKernelGGL(lovasz_fg_prefix, dim3((unsigned)T, (unsigned)N, (unsigned)kClasses), dim3(kSortThreads), 0, s, sorted, sg, T, tile_fg,
+                       G, flag, prefix);
+  hipLaunchKernelGGL(lovasz_pixel_gradient, dim3((unsigned)((P + kKeyThreads - 1) / kKeyThreads), (unsigned)N), dim3(kKeyThreads), 0, s,
+                     logits_full_dev, target_dev, pixel_keys, sorted, prefix, G, flag, P, tab, table9_host ? 1 : 0, lovasz_weight, g);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = launch_bicubic_adjoint(g, P, N, H, W, h, w, taps, cols, grad_lowres_dev, s);
+  if (e != hipSuccess) return fail(kWhoGrad, NBC_ERR_HIP, hipGetErrorString(e));
+  return NBC_OK;
+}
 
 extern "C" size_t nbc_lovasz_workspace_bytes(int N, int H, int W) {
   Layout L;

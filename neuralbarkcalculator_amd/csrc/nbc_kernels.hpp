@@ -127,6 +127,19 @@ hipError_t launch_head_theta(const float* theta, float* out, int a, hipStream_t 
 inline int head_grad_blocks(int hw) { return (hw + 63) / 64; }      // a block owns 64 consecutive cells
 hipError_t launch_head_gradient(const void* x, const double* g, int N, int hw, int precision, int a, double* part, double* out,
                                 hipStream_t s);
+// The adjoint of the bicubic upsample (h, w) -> (H, W) on three f64 planes per image (head_refit.hip: ce_col_adjoint along the rows of
+// the image, then ce_row_adjoint down them): g [N][3] planes of H * W values, g_plane apart -> cols [N][3][H][w] -> out [N][3][h][w].
+// The eight device tables are nbc_bicubic_taps' (the index and coefficient tables 16-byte aligned).  What nbc_ce_gradient and
+// nbc_lovasz_gradient both end in: the same two launches, the same order of every sum.
+struct BicubicTaps {
+  const int32_t* row_idx;
+  const float* row_coeff;
+  const int32_t *row_lo, *row_hi, *col_idx;
+  const float* col_coeff;
+  const int32_t *col_lo, *col_hi;
+};
+hipError_t launch_bicubic_adjoint(const double* g, long long g_plane, int N, int H, int W, int h, int w, const BicubicTaps& taps,
+                                  double* cols, double* out, hipStream_t s);
 // ASPP pooling branch of every DeepLab head (aspp.hip), per image: mean over hw pixels of x [N][hw][cin] (stored elements; cin a
 // multiple of 64, at most 4096), the 1x1 conv with f32 weights w [cout][cin], relu(fma(., scale, shift)), stored as y [N][cout]
 // elements.  Workspaces: partial N * aspp_pool_slices(hw) * cin floats, mean N * cin floats.

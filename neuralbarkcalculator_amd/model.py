@@ -353,6 +353,7 @@ class FCNResNet50:
         self._sweep_ws: Optional[torch.Tensor] = None      # nbc_offset_sweep's, likewise
         self._ce_grad_ws: Optional[torch.Tensor] = None    # nbc_ce_gradient's, likewise
         self._head_grad_ws: Optional[torch.Tensor] = None  # nbc_head_gradient's, likewise
+        self._lovasz_grad_ws: Optional[torch.Tensor] = None  # nbc_lovasz_gradient's, likewise
         self._bicubic_taps: dict = {}                      # ce_gradient: the device tables of each (n_in, n_out)
         self._logit_offsets: Tuple[float, float] = (0.0, 0.0)   # set_logit_offsets: (bark, node), (0, 0) = off
         self._last_shape: Optional[Tuple[int, int, int]] = None   # (N, H, W) of the last forward (dropout_draws)
@@ -1101,6 +1102,47 @@ class FCNResNet50:
         _lib.check(rc, "nbc_ce_gradient")
         return out
 
+    def lovasz_gradient(self, logits_full: torch.Tensor, target: torch.Tensor, lowres_size, table=None, lovasz_weight: float = 1.0,
+                        return_keys: bool = False, return_pixel_gradient: bool = False):
+        """The Lovasz-Softmax terms of each image and the gradient of ``sum T'[t][p] ce + lovasz_weight * L`` with respect to its
+        low-resolution logits (nbc_lovasz_gradient; the definitions: include/nbc.h, ``refit.lovasz_pixel_gradient_cpu``): ``L`` is
+        the image's Lovasz-Softmax loss (``metrics.lovasz_loss`` of the terms), ``table`` nine numbers ``T'`` already scaled by
+        the caller, or None for no cross-entropy term.  ``logits_full``, ``target`` and ``lowres_size`` as ``ce_gradient`` takes
+        them.  Returns ``(terms f64 [N,3], fg_counts int64 [N,3], grad_lowres f64 [N,3,h,w])`` -- the first two bit for bit
+        ``lovasz_softmax``'s -- then, when asked for, the keys in pixel order (int32 ``[N,3,H,W]`` holding the 31-bit keys
+        ``bits(e) << 1 | fg``) and the pixel gradient f64 ``[N,3,H,W]``.  On the current stream."""
+        self._require_ctx()
+        n, h, w = self._check_logits_target(logits_full, target)
+        lh, lw = int(lowres_size[0]), int(lowres_size[1])
+        tab = None
+        if table is not None:
+            tab = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1))
+            if tab.size != 9:
+                raise ValueError("table must hold nine numbers T[target class][argmax class]")
+        lam = float(lovasz_weight)
+        if not math.isfinite(lam):
+            raise ValueError("lovasz_weight must be finite, got %r" % (lovasz_weight,))
+        need = int(self._lib.nbc_lovasz_gradient_workspace_bytes(n, h, w, lh, lw))
+        if need == 0:
+            raise ValueError("nbc_lovasz_gradient refuses a [%d,3,%d,%d] batch with a %dx%d low-resolution map (N <= 65535, "
+                             "H * W < 2^31, 1 <= h <= H, 1 <= w <= W)" % (n, h, w, lh, lw))
+        rows, cols = self._taps_on_device(lh, h), self._taps_on_device(lw, w)
+        terms = torch.empty((n, NUM_CLASSES), dtype=torch.float64, device=self.device)
+        fg_counts = torch.empty((n, NUM_CLASSES), dtype=torch.int64, device=self.device)
+        out = torch.empty((n, NUM_CLASSES, lh, lw), dtype=torch.float64, device=self.device)
+        keys = torch.empty((n, NUM_CLASSES, h, w), dtype=torch.int32, device=self.device) if return_keys else None
+        pix = torch.empty((n, NUM_CLASSES, h, w), dtype=torch.float64, device=self.device) if return_pixel_gradient else None
+        with self._on_stream() as cur:
+            ws = self._grown_workspace("_lovasz_grad_ws", need, cur)
+            rc = self._lib.nbc_lovasz_gradient(logits_full.data_ptr(), target.data_ptr(), n, h, w, lh, lw,
+                                               *[t.data_ptr() for t in rows + cols],
+                                               None if tab is None else tab.ctypes.data_as(C.POINTER(C.c_double)), lam,
+                                               ws.data_ptr(), ws.numel(), terms.data_ptr(), fg_counts.data_ptr(), out.data_ptr(),
+                                               None if keys is None else keys.data_ptr(), None if pix is None else pix.data_ptr(),
+                                               cur.cuda_stream)
+        _lib.check(rc, "nbc_lovasz_gradient")
+        return (terms, fg_counts, out) + ((keys,) if return_keys else ()) + ((pix,) if return_pixel_gradient else ())
+
     def head_gradient(self, grad_lowres: torch.Tensor) -> torch.Tensor:
         """``grad_lowres`` f64 ``[N,3,h,w]`` (``ce_gradient``) carried onto the parameters of ``classifier.4`` through the features
         of the LAST forward (nbc_head_gradient): f64 ``[N,3,513]`` per image, a class's 512 weight columns and then its bias, in
@@ -1121,18 +1163,25 @@ class FCNResNet50:
         _lib.check(rc, "nbc_head_gradient")
         return out
 
-    def head_loss_and_gradient(self, target: torch.Tensor, theta, table, logits_full: Optional[torch.Tensor] = None):
+    def head_loss_and_gradient(self, target: torch.Tensor, theta, table, logits_full: Optional[torch.Tensor] = None,
+                               lovasz_weight: Optional[float] = None):
         """The loss cells and their gradient for trial parameters ``theta`` on the images of the LAST forward: ``head_logits`` ->
         ``upsample_argmax`` -> ``pixel_cross_entropy`` -> ``ce_gradient`` -> ``head_gradient``.  ``target``: the uint8 ``[N,H,W]``
         grey masks of that forward's images; ``table`` as ``ce_gradient`` takes it; ``logits_full``: an optional f32
         ``[N,3,H,W]`` buffer for the upsampled logits.  Returns ``(sums f64 [N,3,3], counts int64 [N,3,3], grad f64 [N,3,513])``
-        per image: the objective of the batch is ``sum(table * sums)`` and its gradient ``grad.sum(0)``, both not normalised."""
+        per image: the objective of the batch is ``sum(table * sums)`` and its gradient ``grad.sum(0)``, both not normalised.
+        With a ``lovasz_weight`` the gradient is ``lovasz_gradient``'s in place of ``ce_gradient``'s -- of ``sum table[t][p] ce +
+        lovasz_weight * L`` per image, ``table`` None for the Lovasz-Softmax loss alone -- and the image's ``(terms f64 [N,3],
+        fg_counts int64 [N,3])`` follow the three."""
         n, h, w = self._refit_last_shape("head_loss_and_gradient")
         low = self.head_logits(theta)
         _, _, full = self.upsample_argmax(low, (h, w), labels_dtype=torch.uint8, return_logits=True, logits_full=logits_full)
         sums, counts = self.pixel_cross_entropy(full, target)
-        grad = self.head_gradient(self.ce_gradient(full, target, low.shape[2:], table))
-        return sums, counts, grad
+        if lovasz_weight is None:
+            grad = self.head_gradient(self.ce_gradient(full, target, low.shape[2:], table))
+            return sums, counts, grad
+        terms, fg_counts, grad_lowres = self.lovasz_gradient(full, target, low.shape[2:], table, lovasz_weight)
+        return sums, counts, self.head_gradient(grad_lowres), terms, fg_counts
 
     def softmax_census(self, logits_full: torch.Tensor, target: Optional[torch.Tensor] = None,
                        confidence: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -1693,6 +1742,7 @@ class FCNResNet50:
             self._ctx = C.c_void_p()
         self._blob_dev = None
         self._lovasz_ws = None
+        self._lovasz_grad_ws = None
         self._pixel_ce_ws = None
         self._dropout_ws = None
         self._zones_ws = None

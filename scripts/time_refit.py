@@ -3,11 +3,12 @@
 usage: python scripts/time_refit.py --kernels [N]
            at 1, 2 and 8 x 1024x1024 (or at N alone), in fp32 and f16x2: launch loops (WARM + REPS calls, device events around the loop) of the
            forward, nbc_head_logits, nbc_upsample_argmax, nbc_pixel_cross_entropy, nbc_ce_gradient and nbc_head_gradient, all in
-           this process on the features of the same forward, each beside the bytes it must move at the streaming rate.  Run it
+           this process on the features of the same forward, each beside the bytes it must move at the streaming rate; then
+           nbc_lovasz_softmax and nbc_lovasz_gradient (Lovasz alone, and mixed with the table) on the same buffers.  Run it
            under `rocprofv3 --kernel-trace --stats -d DIR -- python ...` for per-launch kernel times, then
        python scripts/time_refit.py parse DIR
            medians per kernel from the kernel trace under DIR (every launch of the run pooled: trace one batch size)
-       python scripts/time_refit.py --folder N [--precision f16x2]
+       python scripts/time_refit.py --folder N [--precision f16x2] [--loss ce|lovasz|mixed]
            refit_folder on a synthetic folder of N 1024x1024 samples (scripts/time_evaluate.py's): seconds per objective
            evaluation and for a refit of 20 evaluations"""
 import csv
@@ -26,7 +27,8 @@ WARM, REPS = 5, 50
 BATCHES = (1, 2, 8)
 H = W = 1024
 KERNELS = ("head_theta_scale", "head1x1_kernel", "ce_pixel_gradient", "ce_col_adjoint", "ce_row_adjoint", "head_grad_partial",
-           "head_grad_finish", "pixel_ce_partial", "upsample_argmax")
+           "head_grad_finish", "pixel_ce_partial", "upsample_argmax", "lovasz_keys", "lovasz_hist", "lovasz_scan", "lovasz_scatter",
+           "lovasz_tile_fg", "lovasz_partial", "lovasz_fg_prefix", "lovasz_pixel_gradient")
 HBM_BYTES_PER_S = 6.29e12
 
 
@@ -36,7 +38,10 @@ def byte_bounds(n, precision, h=H // 8, w=W // 8):
     return {"head_logits": n * cells * (512 * eb + 12), "upsample_argmax": n * (12 * cells + 13 * P),
             "pixel_cross_entropy": n * 13 * P, "ce_gradient": n * ((13 + 24) * P + 24 * P + 24 * H * w + 24 * H * w + 24 * cells),
             "ce_gradient.pixel": n * (13 + 24) * P, "ce_gradient.columns": n * (24 * P + 24 * H * w),
-            "ce_gradient.rows": n * (24 * H * w + 24 * cells), "head_gradient": n * cells * (512 * eb + 24)}
+            "ce_gradient.rows": n * (24 * H * w + 24 * cells), "head_gradient": n * cells * (512 * eb + 24),
+            # beyond nbc_lovasz_softmax: the copy of the keys (12 + 12), the prefix pass (12 + 12), the pixel pass (13 + 12 in,
+            # 24 out, its searches apart), the two adjoint passes
+            "lovasz_gradient - lovasz_softmax": n * ((24 + 24 + 49) * P + 24 * P + 48 * H * w + 24 * cells)}
 
 
 def loop(fn):
@@ -79,6 +84,12 @@ def kernels(batches=BATCHES):
             us["ce_gradient"] = loop(lambda: m.ce_gradient(full, tgt, low.shape[2:], T))
             us["head_gradient"] = loop(lambda: m.head_gradient(gl))
             us["head_loss_and_gradient"] = loop(lambda: m.head_loss_and_gradient(tgt, theta, T, logits_full=full))
+            us["lovasz_softmax"] = loop(lambda: m.lovasz_softmax(full, tgt))
+            us["lovasz_gradient"] = loop(lambda: m.lovasz_gradient(full, tgt, low.shape[2:]))
+            us["lovasz_gradient, mixed"] = loop(lambda: m.lovasz_gradient(full, tgt, low.shape[2:], T / (4.0 * H * W), 1.0))
+            us["lovasz_gradient - lovasz_softmax"] = us["lovasz_gradient"] - us["lovasz_softmax"]
+            us["head_loss_and_gradient, mixed"] = loop(lambda: m.head_loss_and_gradient(tgt, theta, T / (4.0 * H * W), logits_full=full,
+                                                                                        lovasz_weight=1.0))
             bounds = byte_bounds(n, precision)
             print("%s, %d x %dx%d (loops of %d calls, launch gaps included):" % (precision, n, H, W, REPS), flush=True)
             for name, t in us.items():
@@ -109,7 +120,7 @@ def parse(folder):
                   % (kernel, len(us), np.median(us), np.percentile(us, 10), np.percentile(us, 90)))
 
 
-def folder(n, precision):
+def folder(n, precision, loss="ce"):
     from neuralbarkcalculator_amd import refit
     import time_evaluate
     root = tempfile.mkdtemp(prefix="nbc_refit_")
@@ -118,11 +129,11 @@ def folder(n, precision):
         out = os.path.join(root, "refit_model.pt")
         for iterations in (1, 9):                       # at most 2 x iterations + 2 evaluations: 4 and 20
             t0 = time.perf_counter()
-            st = refit.refit_folder(root, out, ckpt, loss="ce", iterations=iterations, precision=precision, device_index=0)
+            st = refit.refit_folder(root, out, ckpt, **{"image_loss" if loss in refit.LOVASZ_LOSSES else "loss": loss}, iterations=iterations, precision=precision, device_index=0)
             dt = time.perf_counter() - t0
             ev = st["summary"]["evaluations"]
-            print("refit %s, %d images, --iterations %d: %d evaluations in %.2f s end to end (%.2f s set-up), %.3f s per evaluation "
-                  "in the loops; a 20-evaluation refit at that rate %.1f s" % (precision, n, iterations, ev, dt, st["setup_s"],
+            print("refit %s --loss %s, %d images, --iterations %d: %d evaluations in %.2f s end to end (%.2f s set-up), %.3f s per evaluation "
+                  "in the loops; a 20-evaluation refit at that rate %.1f s" % (precision, loss, n, iterations, ev, dt, st["setup_s"],
                                                                              (dt - st["setup_s"]) / ev, st["setup_s"] + 20 * (dt - st["setup_s"]) / ev),
                   flush=True)
             print("  " + refit.format_summary(st["summary"]).splitlines()[0], flush=True)
@@ -137,6 +148,7 @@ if __name__ == "__main__":
     elif args[:1] == ["parse"] and len(args) == 2:
         parse(args[1])
     elif args[:1] == ["--folder"] and len(args) >= 2:
-        folder(int(args[1]), args[args.index("--precision") + 1] if "--precision" in args else "f16x2")
+        folder(int(args[1]), args[args.index("--precision") + 1] if "--precision" in args else "f16x2",
+               args[args.index("--loss") + 1] if "--loss" in args else "ce")
     else:
         raise SystemExit(__doc__)
