@@ -94,7 +94,7 @@ extern "C" int nbc_confusion(const void* labels_dev, int labels_dtype, const uin
                              int64_t* conf_dev, void* hip_stream) {
   if (!labels_dev || !target_dev || !conf_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
   if (!per_image_shape_ok(N, H, W)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
   const long long P = (long long)H * W;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   unsigned long long* conf = reinterpret_cast<unsigned long long*>(conf_dev);

@@ -29,6 +29,7 @@
 // The rows are zeroed by a memset in front: every word of an image's rows and sum_d is written on every call.  The float
 // sums' order depends on the image alone (its shape and where its contours lie), never on the batch, the stream or the
 // timing, so an image's outputs have the same bits alone, in any batch and on any stream.
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 
@@ -344,43 +345,65 @@ __global__ __launch_bounds__(64) void contour_finish_kernel(const double* __rest
   }
 }
 
-}  // namespace
-
+// The regions of the workspace (byte offsets, each 256-byte aligned) and its size: a mark byte per pixel, the four u16 column
+// distances per pixel, and an f64 partial per (image, set, row).
+struct ContoursLayout {
+  size_t mark, dist, partial, total;
+};
 ContoursLayout contours_layout(int N, int H, int W) {
   const size_t px = (size_t)N * H * W;
   Carver ws;
-  ContoursLayout lay;
-  lay.mark = ws.take(px);
-  lay.dist = ws.take(8 * px);
-  lay.partial = ws.take(8 * (size_t)N * kSets * H);
-  lay.total = ws.offset;
-  return lay;
+  const size_t mark = ws.take(px), dist = ws.take(8 * px), partial = ws.take(8 * (size_t)N * kSets * H);
+  return {mark, dist, partial, ws.offset};
 }
 
-hipError_t launch_contour_distances(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
-                                    long long* rows, int bins, double* sum_d, unsigned char* ws, hipStream_t s) {
-  if (N < 1 || N > 65535 || H < 1 || W < 1 || H > NBC_CONTOUR_MAX_SIDE || W > NBC_CONTOUR_MAX_SIDE || bins < 2)
-    return hipErrorInvalidValue;
+bool contours_shape_ok(int N, int H, int W) {
+  return N >= 1 && N <= 65535 && H >= 1 && H <= NBC_CONTOUR_MAX_SIDE && W >= 1 && W <= NBC_CONTOUR_MAX_SIDE;
+}
+constexpr int kContourMaxBins = 5793;         // ceil(hypot(4095, 4095)) + 1
+
+}  // namespace
+}  // namespace nbc
+
+using namespace nbc;
+
+extern "C" size_t nbc_contours_workspace_bytes(int N, int H, int W) {
+  return contours_shape_ok(N, H, W) ? contours_layout(N, H, W).total : 0;
+}
+
+extern "C" int nbc_contour_distances(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N,
+                                     int H, int W, int64_t* rows_dev, int bins, double* sum_d_dev, void* workspace_dev,
+                                     size_t workspace_bytes, void* hip_stream) {
+  constexpr const char* kWho = "nbc_contour_distances";
+  if (!c || !labels_dev || !target_grey_dev || !rows_dev || !sum_d_dev || !workspace_dev)
+    return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!contours_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1.." + std::to_string(NBC_CONTOUR_MAX_SIDE));
+  if (bins < 2 || bins > kContourMaxBins) return fail(kWho, NBC_ERR_INVALID, "bins must lie in 2.." + std::to_string(kContourMaxBins));
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
   const ContoursLayout lay = contours_layout(N, H, W);
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, lay.total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
   unsigned char* mark = ws + lay.mark;
   ushort4* dist = reinterpret_cast<ushort4*>(ws + lay.dist);
   double* partial = reinterpret_cast<double*>(ws + lay.partial);
-  u64* R = reinterpret_cast<u64*>(rows);
+  u64* R = reinterpret_cast<u64*>(rows_dev);
   const int row_len = kHead + bins;
-  hipError_t e = hipMemsetAsync(rows, 0, sizeof(long long) * (size_t)N * kSets * row_len, s);
-  if (e != hipSuccess) return e;
+  NBC_HIP(hipMemsetAsync(rows_dev, 0, sizeof(long long) * (size_t)N * kSets * row_len, s));
   const dim3 tiles((W + kThreads - 1) / kThreads, (H + kMarkRows - 1) / kMarkRows, N);
-  if (labels_i64)
-    hipLaunchKernelGGL(contour_mark_kernel<long long>, tiles, dim3(kThreads), 0, s, static_cast<const long long*>(labels), target_grey,
-                       H, W, mark, R, row_len);
+  if (labels_dtype == NBC_LABEL_I64)
+    hipLaunchKernelGGL(contour_mark_kernel<long long>, tiles, dim3(kThreads), 0, s, static_cast<const long long*>(labels_dev),
+                       target_grey_dev, H, W, mark, R, row_len);
   else
-    hipLaunchKernelGGL(contour_mark_kernel<unsigned char>, tiles, dim3(kThreads), 0, s, static_cast<const unsigned char*>(labels),
-                       target_grey, H, W, mark, R, row_len);
+    hipLaunchKernelGGL(contour_mark_kernel<unsigned char>, tiles, dim3(kThreads), 0, s, static_cast<const unsigned char*>(labels_dev),
+                       target_grey_dev, H, W, mark, R, row_len);
   hipLaunchKernelGGL(column_distance_kernel, dim3((W + 63) / 64, N), dim3(64, kSegs), 0, s, mark, H, W, dist);
   hipLaunchKernelGGL(row_min_kernel, dim3((H + kRowsPerBlock - 1) / kRowsPerBlock, N), dim3(kThreads),
                      sizeof(unsigned short) * (kSets + 2) * (size_t)W, s, mark, dist, H, W, R, row_len, bins, partial);
-  hipLaunchKernelGGL(contour_finish_kernel, dim3(N * kSets), dim3(64), 0, s, partial, H, R, row_len, sum_d);
-  return hipGetLastError();
+  hipLaunchKernelGGL(contour_finish_kernel, dim3(N * kSets), dim3(64), 0, s, partial, H, R, row_len, sum_d_dev);
+  NBC_HIP(hipGetLastError());
+  return NBC_OK;
 }
 
-}  // namespace nbc

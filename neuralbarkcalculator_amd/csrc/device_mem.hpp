@@ -1,4 +1,4 @@
-// Owners of the context's device memory (nbc_api.hip): a growing buffer and a "borrowed or owned" array.  Both are templated
+// Owners of the context's device memory (nbc_ctx.hpp): a growing buffer and a "borrowed or owned" array.  Both are templated
 // on a memory policy, and no HIP header is included here, so tests/host/device_mem_test.cpp runs them on malloc.  A policy has
 //   Error, ok()                              the error type and its "no error" value
 //   Error allocate(void** p, size_t bytes)   *p is read only when ok() comes back

@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "ce_gradient.hpp"
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 #include "stored.hpp"
@@ -42,7 +43,9 @@ constexpr int kRow = kCin + 1;                          // a class's row of d th
 constexpr int kThreads = 256;
 constexpr int kGroup = 4;                               // consecutive pixels per thread of ce_pixel_gradient
 constexpr int kCellsPerWave = 16;                       // head_grad_partial: two rounds of eight loads in flight
-constexpr int kCellsPerBlock = 4 * kCellsPerWave;       // = the 64 of head_grad_blocks (nbc_kernels.hpp)
+constexpr int kCellsPerBlock = 4 * kCellsPerWave;       // a block of head_grad_partial owns 64 consecutive cells
+constexpr int kHeadThetaFloats = kClasses * kRow;       // theta: f32 [3][512] in state_dict units, then the [3] of the bias
+inline int head_grad_blocks(int hw) { return (hw + kCellsPerBlock - 1) / kCellsPerBlock; }
 
 using u32 = unsigned;
 
@@ -290,24 +293,13 @@ bool ce_layout(int N, int H, int W, int h, int w, CeLayout* L) {
 constexpr const char* kCeWho = "nbc_ce_gradient";
 constexpr const char* kTapsWho = "nbc_bicubic_taps";
 
+// the power of two the stored input of classifier.4 carries (f16x2; 0 otherwise)
+int head_input_exponent(const nbc_ctx* c) {
+  int a = 0;
+  return stored_exponent(c, "classifier.0", &a) ? a : 0;
+}
+
 }  // namespace
-
-hipError_t launch_head_theta(const float* theta, float* out, int a, hipStream_t s) {
-  hipLaunchKernelGGL(head_theta_scale, dim3((kHeadThetaFloats + kThreads - 1) / kThreads), dim3(kThreads), 0, s, theta, out, -a);
-  return hipGetLastError();
-}
-
-hipError_t launch_head_gradient(const void* x, const double* g, int N, int hw, int precision, int a, double* part, double* out,
-                                hipStream_t s) {
-  if (N < 1 || N > 65535 || hw < 1) return hipErrorInvalidValue;
-  const int blocks = head_grad_blocks(hw);
-  with_precision(precision, [&](auto P) {
-    hipLaunchKernelGGL(head_grad_partial<P.value>, dim3((unsigned)blocks, (unsigned)N), dim3(kThreads), 0, s, x, g, hw, part);
-  });
-  hipLaunchKernelGGL(head_grad_finish, dim3((kClasses * kRow + kThreads - 1) / kThreads, (unsigned)N), dim3(kThreads), 0, s, part, blocks,
-                     std::ldexp(1.0, -a), out);
-  return hipGetLastError();
-}
 
 hipError_t launch_bicubic_adjoint(const double* g, long long g_plane, int N, int H, int W, int h, int w, const BicubicTaps& t,
                                   double* cols, double* out, hipStream_t s) {
@@ -396,5 +388,60 @@ extern "C" int nbc_ce_gradient(const float* logits_full_dev, const uint8_t* targ
                      logits_full_dev, target_dev, P, L.Pp, T, g);
   const hipError_t e = launch_bicubic_adjoint(g, L.Pp, N, H, W, h, w, taps, cols, grad_lowres_dev, s);
   if (e != hipSuccess) return fail(kCeWho, NBC_ERR_HIP, hipGetErrorString(e));
+  return NBC_OK;
+}
+
+// The trial logits: the caller's theta becomes what the forward's classifier.4 launch reads (the context keeps that array), and
+// launch_head1x1 on it is the forward's own machine code.
+extern "C" int nbc_head_logits(nbc_ctx* c, const float* theta_dev, int N, int H, int W, float* logits_lowres_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_head_logits";
+  if (!c || !theta_dev || !logits_lowres_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!aligned4(theta_dev, logits_lowres_dev)) return fail(kWho, NBC_ERR_INVALID, "theta_dev and logits_lowres_dev must be 4-byte aligned");
+  if (!per_image_shape_ok(N, H, W)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  const Op* head = nullptr;
+  if (int rc = last_forward_head(kWho, c, N, H, W, &head)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  NBC_HIP(c->refit_theta.reserve(kHeadThetaFloats * sizeof(float)));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  float* theta = c->refit_theta.as<float>();
+  hipLaunchKernelGGL(head_theta_scale, dim3((kHeadThetaFloats + kThreads - 1) / kThreads), dim3(kThreads), 0, s, theta_dev, theta,
+                     -head_input_exponent(c));
+  NBC_HIP(hipGetLastError());
+  NBC_HIP(launch_head1x1(c->bufs[head->in_buf].get(), 512, theta, theta + 3 * 512, logits_lowres_dev, N, c->plan.h * c->plan.w,
+                         c->precision, nullptr, c->nonfinite.as<unsigned>(), s));
+  return NBC_OK;
+}
+
+extern "C" size_t nbc_head_gradient_workspace_bytes(int N, int H, int W) {
+  if (!per_image_shape_ok(N, H, W)) return 0;
+  int h = 0, w = 0;
+  if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1) return 0;
+  return align256((size_t)8 * N * head_grad_blocks(h * w) * kHeadThetaFloats);
+}
+
+// d theta [N][3][513] f64 = sum over the hw cells of g [N][3][hw] f64 times x [N][hw][512] stored elements (column 512: the
+// plain sum, the bias), times 2^-a on the 512 weight columns.  One read of x; the workspace holds a partial per block.
+extern "C" int nbc_head_gradient(nbc_ctx* c, const double* grad_lowres_dev, int N, int H, int W, void* workspace_dev,
+                                 size_t workspace_bytes, double* grad_theta_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_head_gradient";
+  if (!c || !grad_lowres_dev || !workspace_dev || !grad_theta_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(grad_lowres_dev) | reinterpret_cast<uintptr_t>(grad_theta_dev)) & 7u)
+    return fail(kWho, NBC_ERR_INVALID, "grad_lowres_dev and grad_theta_dev must be 8-byte aligned");
+  const size_t need = nbc_head_gradient_workspace_bytes(N, H, W);
+  if (need == 0) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
+  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, need)) return rc;
+  const Op* head = nullptr;
+  if (int rc = last_forward_head(kWho, c, N, H, W, &head)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const int hw = c->plan.h * c->plan.w, blocks = head_grad_blocks(hw);
+  double* part = static_cast<double*>(workspace_dev);
+  with_precision(c->precision, [&](auto P) {
+    hipLaunchKernelGGL(head_grad_partial<P.value>, dim3((unsigned)blocks, (unsigned)N), dim3(kThreads), 0, s,
+                       c->bufs[head->in_buf].get(), grad_lowres_dev, hw, part);
+  });
+  hipLaunchKernelGGL(head_grad_finish, dim3((kClasses * kRow + kThreads - 1) / kThreads, (unsigned)N), dim3(kThreads), 0, s, part, blocks,
+                     std::ldexp(1.0, -head_input_exponent(c)), grad_theta_dev);
+  NBC_HIP(hipGetLastError());
   return NBC_OK;
 }

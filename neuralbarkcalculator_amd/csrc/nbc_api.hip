@@ -9,104 +9,18 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "../../include/nbc.h"
-#include "device_mem.hpp"
-#include "nbc_internal.hpp"
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
-#include "nbc_net.hpp"
-#include "nbc_plan.hpp"
-#include "philox.hpp"
 #include "reduce.hpp"
 
 using namespace nbc;
 
-#define NBC_HIP(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      return set_error(NBC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
-  } while (0)
-
-// The memory policy of the context's owners (device_mem.hpp), and an event owned the same way.
-struct HipMem {
-  using Error = hipError_t;
-  static constexpr Error ok() { return hipSuccess; }
-  static Error allocate(void** p, size_t bytes) { return hipMalloc(p, bytes); }
-  static void release(void* p) { (void)hipFree(p); }          // synchronises: nothing of the block is in flight afterwards
-  static void forget_error() { (void)hipGetLastError(); }
-  static Error copy_in(void* dst, const void* host, size_t bytes) { return hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice); }
-};
-using DeviceBuffer = Buffer<HipMem>;
-template <class T> using DeviceArray = Array<T, HipMem>;
-
-struct Event {
-  hipEvent_t ev = nullptr;
-  Event() = default;
-  Event(Event&& o) noexcept : ev(std::exchange(o.ev, nullptr)) {}
-  ~Event() { if (ev) (void)hipEventDestroy(ev); }
-  hipError_t create() { return hipEventCreate(&ev); }
-  operator hipEvent_t() const { return ev; }
-};
-
-// Everything the context holds on the device is a member that releases itself: nbc_destroy deletes the context.
-struct nbc_ctx {
-  int device = 0;
-  int precision = -1;
-  int arch = kArchFcn;                      // NBC_ARCH_* of the attached blob
-  DeviceArray<unsigned char> weights;       // device blob: the caller's (nbc_attach_weights) or one loaded / received here
-  PackedLayout layout;
-  float mean[3] = {0.7399f, 0.6139f, 0.4401f};   // models.py:208
-  float stdv[3] = {0.1068f, 0.1272f, 0.1271f};   // models.py:209
-  Plan plan;                                // plan of the current (N,H,W)
-  std::vector<Plan> plan_cache;             // plans (with their tuned tiles) of the other shapes seen, oldest first
-  std::vector<DeviceBuffer> bufs;           // the plan's activation buffers: they only ever grow
-  DeviceBuffer lowres;
-  int conv_tile = -1;                       // tile override, -1 = per-layer choice
-  bool fuse_downsample = true;              // nbc_set_fuse_downsample
-  int fused_pairs = 0;                      // (downsample.0, conv3) pairs the last forward ran as one launch
-  float logit_offsets[2] = {0.f, 0.f};      // nbc_set_logit_offsets: added to the bark and node logits of the decision alone
-  bool offsets_on = false;                  // either one is not zero: the upsample + argmax launch takes its offset kernels
-  bool keep = false;
-  bool profiling = false;
-  // profiling: one event set (nops+1 events) per profiled forward, read back lazily so that the
-  // timed loop never synchronises; nbc_num_op_records() averages over the sets and resets.
-  std::vector<std::vector<Event>> prof_sets;
-  size_t prof_used = 0;
-  std::vector<Op> prof_ops;
-  int prof_arch = kArchFcn;                 // architecture of prof_ops
-  std::vector<nbc_op_record> records;
-  std::map<std::string, int> act_of;        // conv unit name -> op index (keep mode)
-  DeviceBuffer scratch256;                  // 256 bytes of device scratch (min/max of the preprocessor resize)
-  int pack_flags = 0;                       // NBC_PACK_* of the attached blob (its trailer)
-  std::vector<int> act_exp;                 // per conv unit: power of two its output tensor is stored with (trailer)
-  DeviceBuffer nonfinite;                   // one device word, sticky: bit 0 = a forward produced a NaN / infinite logit,
-                                            // NBC_NONFINITE_BN_RANGE = a per-image BatchNorm saw a channel outside the pieces' range
-  DeviceBuffer zones_ws;                    // remove_small_zones workspace: parent ints, size ints, bg bytes
-  int bn_mode = NBC_BN_RUNNING;             // NBC_BN_*
-  DeviceArray<float> bn_affine;             // gamma, beta per BatchNorm unit (nbc_pack_bn_affine)
-  DeviceArray<float> bn_raw;                // f16x2: 2^(r - k - a_in), 2^-r per BatchNorm unit (nbc_pack_bn_raw)
-  DeviceArray<float> bn_unit;               // 2048 ones, then 2048 zeros (the raw convolutions' scale and shift)
-  DeviceBuffer bn_ws;                       // per-image BatchNorm workspace (Plan::bn_ws_bytes)
-  // the (N, H, W) of the last completed nbc_forward while its activations and plan stand untouched (nbc_dropout_draws reads
-  // the stored input of classifier.4): cleared by whatever parks the plan, retunes it or attaches other weights
-  bool fwd_valid = false;
-  int fwd_N = 0, fwd_H = 0, fwd_W = 0;
-  DeviceBuffer refit_theta;                 // nbc_head_logits: the caller's theta as classifier.4 reads it (kHeadThetaFloats)
-};
-
 namespace {
 
 constexpr size_t kPlanCacheEntries = 64;
-
-PlanKey plan_key(const nbc_ctx* c, int N, int H, int W) {
-  PlanKey k;
-  k.N = N; k.H = H; k.W = W; k.precision = c->precision; k.arch = c->arch; k.keep = c->keep; k.bn = c->bn_mode;
-  return k;
-}
 
 // Park the current plan (folders of height-trimmed images alternate between a few shapes: each keeps
 // its launch list and its measured tile choice instead of being rebuilt on every change).
@@ -153,19 +67,6 @@ int ensure_buffers(nbc_ctx* c) {
   c->act_of.clear();
   for (size_t i = 0; i < P.ops.size(); ++i) c->act_of[P.ops[i].name] = (int)i;
   return NBC_OK;
-}
-
-// A conv unit's arrays in the attached blob: f32 but for w of a conv_dma unit (panels of the precision's elements).
-struct UnitPtrs {
-  const float* w;
-  const float* scale;
-  const float* shift;
-};
-UnitPtrs unit_ptrs(const nbc_ctx* c, int unit) {
-  const PackedConv& pc = c->layout.convs[unit];
-  return {reinterpret_cast<const float*>(c->weights.data() + pc.w_off),
-          reinterpret_cast<const float*>(c->weights.data() + pc.scale_off),
-          reinterpret_cast<const float*>(c->weights.data() + pc.shift_off)};
 }
 
 // Checks a conv op's operand set against its packed unit and sizes it for the buffer resources (activations and weights stay
@@ -287,6 +188,24 @@ const char* kernel_name(OpKind k) {
 }
 
 }  // namespace
+
+namespace nbc {
+
+// power of two the output of plan op `name` is stored with: a conv unit's own, the max-pool keeps the stem's, the image has none
+bool stored_exponent(const nbc_ctx* c, const std::string& name, int* e) {
+  const auto& units = conv_units(c->arch);
+  if (name == "ingest") { *e = 0; return true; }
+  if (name == "backbone.maxpool") { *e = c->act_exp.empty() ? 0 : c->act_exp[0]; return true; }
+  if (c->arch == kArchDeepLab && (name == "classifier.0.concat" || name == "classifier.0.convs.4")) {
+    // the concat and the pooled vector: the power the five ASPP branches share (that of convs.0)
+    return stored_exponent(c, "classifier.0.convs.0.0", e);
+  }
+  for (size_t u = 0; u < units.size(); ++u)
+    if (units[u].name == name) { *e = u < c->act_exp.size() ? c->act_exp[u] : 0; return true; }
+  return false;
+}
+
+}  // namespace nbc
 
 extern "C" {
 
@@ -489,22 +408,6 @@ int nbc_weights_flags(nbc_ctx* c) {
   return c->pack_flags;
 }
 
-namespace {
-// power of two the output of plan op `name` is stored with: a conv unit's own, the max-pool keeps the stem's, the image has none
-bool stored_exponent(const nbc_ctx* c, const std::string& name, int* e) {
-  const auto& units = conv_units(c->arch);
-  if (name == "ingest") { *e = 0; return true; }
-  if (name == "backbone.maxpool") { *e = c->act_exp.empty() ? 0 : c->act_exp[0]; return true; }
-  if (c->arch == kArchDeepLab && (name == "classifier.0.concat" || name == "classifier.0.convs.4")) {
-    // the concat and the pooled vector: the power the five ASPP branches share (that of convs.0)
-    return stored_exponent(c, "classifier.0.convs.0.0", e);
-  }
-  for (size_t u = 0; u < units.size(); ++u)
-    if (units[u].name == name) { *e = u < c->act_exp.size() ? c->act_exp[u] : 0; return true; }
-  return false;
-}
-}  // namespace
-
 int nbc_activation_exponent(nbc_ctx* c, const char* name, int32_t* exponent) {
   if (!c || !name || !exponent) return set_error(NBC_ERR_INVALID, "nbc_activation_exponent: null argument");
   if (!c->weights.data()) return set_error(NBC_ERR_STATE, "nbc_activation_exponent: no weights attached");
@@ -656,7 +559,7 @@ int nbc_forward(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W,
   if (!c || !x_dev) return set_error(NBC_ERR_INVALID, "nbc_forward: null argument");
   if (!c->weights.data()) return set_error(NBC_ERR_STATE, "nbc_forward: no weights attached (load_state_dict first)");
   if (x_dtype != NBC_IN_F32_NCHW && x_dtype != NBC_IN_U8_NHWC) return set_error(NBC_ERR_INVALID, "nbc_forward: bad x_dtype");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_forward: bad labels_dtype");
+  if (!label_dtype_ok(labels_dtype)) return set_error(NBC_ERR_INVALID, "nbc_forward: bad labels_dtype");
   c->fwd_valid = false;
   int rc = nbc_reserve(c, N, H, W);
   if (rc != NBC_OK) return rc;
@@ -836,88 +739,6 @@ static int collect_profile(nbc_ctx* c) {
   return NBC_OK;
 }
 
-// One pass of nbc_dropout_draws over `draws` draws of N images: its regions of the workspace.  nbc_dropout_workspace_bytes
-// publishes `total` (include/nbc.h states the formula), the pass loop takes the offsets.
-struct DropoutLayout {
-  size_t lowres, labels, parent, size, bg, total;
-};
-static DropoutLayout dropout_layout(int N, int H, int W, int h, int w, int draws) {
-  const size_t I = (size_t)draws * N, px = I * H * W;
-  Carver ws;
-  const size_t lowres = ws.take(12 * I * h * w), labels = ws.take(px);                        // f32 [I][3][h][w], u8 [I][H][W]
-  const size_t parent = ws.take(4 * px), size = ws.take(4 * px), bg = ws.take(px);           // remove_small_zones' int, int, u8
-  return {lowres, labels, parent, size, bg, ws.offset};
-}
-
-// The pass loop behind nbc_dropout_draws and nbc_dropout_votes (`who` prefixes the error messages): the masked classifier,
-// the upsample + argmax, remove_small_zones and the counts of each pass; with `with_votes`, the pass's final labels are
-// counted into votes_dev before the next pass overwrites them.
-static int dropout_passes(const char* who, nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed,
-                          int first_draw, int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev,
-                          int64_t* counts_dev, bool with_votes, uint32_t* votes_dev, int accumulate, void* workspace_dev,
-                          size_t workspace_bytes, void* hip_stream) {
-  const auto refuse = [who](int code, const std::string& msg) { return set_error(code, std::string(who) + ": " + msg); };
-  if (!dropout_p_ok(p)) return refuse(NBC_ERR_INVALID, "p must lie in [0, 1)");
-  if (draws < 1 || draws > 1024) return refuse(NBC_ERR_INVALID, "draws must lie in 1..1024");
-  if (first_draw < 0 || first_draw > 0x7fffffff - draws)
-    return refuse(NBC_ERR_INVALID, "first_draw must not be negative (and first_draw + draws < 2^31)");
-  if (min_pixels < 0) return refuse(NBC_ERR_INVALID, "min_pixels must not be negative");
-  if (!c || !image_ids_host || !counts_dev || !workspace_dev || (with_votes && !votes_dev)) return refuse(NBC_ERR_INVALID, "null argument");
-  if (with_votes && reinterpret_cast<uintptr_t>(votes_dev) % 16 != 0) return refuse(NBC_ERR_INVALID, "votes_dev must be 16-byte aligned");
-  if (c->offsets_on)
-    return refuse(NBC_ERR_INVALID, "the context holds logit offsets (nbc_set_logit_offsets); the draws decide by the plain argmax");
-  if (c->arch != kArchFcn)
-    return refuse(NBC_ERR_STATE, std::string("NBC_ARCH_FCN_RESNET50 only, the context holds ") + arch_name(c->arch) +
-                                     " (DeepLabHead's Dropout sits inside ASPP; the EfficientNet heads are left out)");
-  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
-    return refuse(NBC_ERR_STATE, "the context's last forward was not one of this (N, H, W), or its plan has been touched since: run "
-                                 "nbc_forward first");
-  const size_t one = nbc_dropout_workspace_bytes(N, H, W, 1);
-  if (one == 0) return refuse(NBC_ERR_INVALID, "shape beyond the limits (N <= 65535, H * W < 2^31, h * w < 2^25)");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) % 256 != 0) return refuse(NBC_ERR_INVALID, "the workspace must be 256-byte aligned");
-  if (workspace_bytes < one)
-    return refuse(NBC_ERR_INVALID, "the workspace is smaller than nbc_dropout_workspace_bytes(N, H, W, 1)");
-  const Plan& P = c->plan;
-  const Op* head = nullptr;
-  for (const Op& o : P.ops)
-    if (o.kind == OP_HEAD1X1) head = &o;
-  if (!head || head->Ci != 512 || head->in_buf < 0 || !c->nonfinite)
-    return refuse(NBC_ERR_STATE, "the plan holds no classifier.4 of 512 input channels");
-  int pass = std::min(draws, 65535 / N);
-  while (pass > 1 && nbc_dropout_workspace_bytes(N, H, W, pass) > workspace_bytes) --pass;
-  NBC_HIP(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  const UnitPtrs up = unit_ptrs(c, head->unit);
-  const int hw = P.h * P.w;
-  const uint32_t T = dropout_threshold(p);
-  const float m = dropout_scale(p);
-  for (int d0 = 0; d0 < draws; d0 += pass) {
-    const int D = std::min(pass, draws - d0);
-    const int I = D * N;
-    // the pass's slice of the workspace, sized for THIS pass (the last one may be shorter)
-    const DropoutLayout L = dropout_layout(N, H, W, P.h, P.w, D);
-    unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
-    float* lowres = logits_lowres_dev ? logits_lowres_dev + (size_t)d0 * N * kNumClasses * hw : reinterpret_cast<float*>(ws + L.lowres);
-    unsigned char* labels = ws + L.labels;
-    int* parent = reinterpret_cast<int*>(ws + L.parent);
-    int* size = reinterpret_cast<int*>(ws + L.size);
-    unsigned char* bg = ws + L.bg;
-    unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev) + (size_t)d0 * N * kNumClasses;
-    NBC_HIP(launch_head1x1_dropout(c->bufs[head->in_buf].get(), up.w, up.shift, lowres, N, hw, c->precision, image_ids_host, seed, T, m,
-                                   first_draw + d0, D, c->nonfinite.as<unsigned>(), s));
-    if (min_pixels > 0) {
-      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, nullptr, 0, s));
-      NBC_HIP(launch_remove_small_zones(labels, 0, I, H, W, min_pixels, exclude_nodes, bg, parent, size, counts, s));
-    } else {
-      NBC_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * kNumClasses * I, s));
-      NBC_HIP(launch_upsample_argmax(lowres, I, P.h, P.w, H, W, nullptr, labels, 0, counts, exclude_nodes, s));
-    }
-    if (with_votes)                                 // the first pass of a call that does not accumulate stores the words
-      NBC_HIP(launch_vote_accumulate(labels, D, N, (long long)H * W, votes_dev, !accumulate && d0 == 0, s));
-  }
-  return NBC_OK;
-}
-
 extern "C" {
 
 int nbc_autotune(nbc_ctx* c, const void* x_dev, int x_dtype, int N, int H, int W, int reps, int objective,
@@ -1000,7 +821,7 @@ int nbc_upsample_argmax(nbc_ctx* c, const float* lowres, int N, int h, int w, in
                         int64_t* counts_dev, int exclude_nodes, void* hip_stream) {
   if (!c || !lowres) return set_error(NBC_ERR_INVALID, "nbc_upsample_argmax: null argument");
   if (N < 1 || h < 1 || w < 1 || H < 1 || W < 1) return set_error(NBC_ERR_INVALID, "nbc_upsample_argmax: bad shape");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_upsample_argmax: bad labels_dtype");
+  if (!label_dtype_ok(labels_dtype)) return set_error(NBC_ERR_INVALID, "nbc_upsample_argmax: bad labels_dtype");
   NBC_HIP(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   if (counts_dev) NBC_HIP(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 3 * N, s));
@@ -1009,206 +830,6 @@ int nbc_upsample_argmax(nbc_ctx* c, const float* lowres, int N, int h, int w, in
                                  reinterpret_cast<unsigned long long*>(counts_dev), exclude_nodes, s,
                                  c->offsets_on ? c->logit_offsets : nullptr));
   return NBC_OK;
-}
-
-int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int min_pixels,
-                           int exclude_nodes, int64_t* counts_dev, void* hip_stream) {
-  if (!c || !labels_dev) return set_error(NBC_ERR_INVALID, "nbc_remove_small_zones: null argument");
-  if (N < 1 || N > 65535 || H < 1 || W < 1 || min_pixels < 0) return set_error(NBC_ERR_INVALID, "nbc_remove_small_zones: bad shape");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, "nbc_remove_small_zones: bad labels_dtype");
-  NBC_HIP(hipSetDevice(c->device));
-  const size_t px = (size_t)N * H * W;
-  NBC_HIP(c->zones_ws.reserve(px * 9 + 256, Grow::kMargin));   // grows by at least half, like the activation buffers
-  int* parent = c->zones_ws.as<int>();
-  int* size = parent + px;
-  unsigned char* bg = reinterpret_cast<unsigned char*>(size + px);
-  NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, exclude_nodes, bg,
-                                    parent, size, reinterpret_cast<unsigned long long*>(counts_dev),
-                                    static_cast<hipStream_t>(hip_stream)));
-  return NBC_OK;
-}
-
-int nbc_remove_small_zones_groups(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int G, int min_pixels,
-                                  int64_t* counts_dev, void* hip_stream) {
-  const char* who = "nbc_remove_small_zones_groups: ";
-  if (!c || !labels_dev) return set_error(NBC_ERR_INVALID, std::string(who) + "null argument");
-  if (!per_image_shape_ok(N, H, W) || H > 65535 || min_pixels < 0) return set_error(NBC_ERR_INVALID, std::string(who) + "bad shape");
-  if (G < 1 || G > 64 || (long long)(G < N ? G : N) * H * W > 0x7fffffffLL)
-    return set_error(NBC_ERR_INVALID, std::string(who) + "bad group: 1 <= G <= 64 and g * H * W < 2^31 for the g = min(G, N) images of a group");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return set_error(NBC_ERR_INVALID, std::string(who) + "bad labels_dtype");
-  NBC_HIP(hipSetDevice(c->device));
-  const size_t px = (size_t)N * H * W;
-  NBC_HIP(c->zones_ws.reserve(px * 9 + 256, Grow::kMargin));   // nbc_remove_small_zones' workspace and its carving
-  int* parent = c->zones_ws.as<int>();
-  int* size = parent + px;
-  unsigned char* bg = reinterpret_cast<unsigned char*>(size + px);
-  NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, 0, bg, parent, size,
-                                    reinterpret_cast<unsigned long long*>(counts_dev), static_cast<hipStream_t>(hip_stream), G));
-  return NBC_OK;
-}
-
-static bool zones_shape_ok(int N, int H, int W) { return per_image_shape_ok(N, H, W) && H <= 65535 && W <= 65535; }
-
-size_t nbc_zones_workspace_bytes(int N, int H, int W) { return zones_shape_ok(N, H, W) ? zones_layout(N, H, W).total : 0; }
-
-int nbc_label_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, int N, int H, int W, int64_t* rows_dev, int cap,
-                    int64_t* num_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
-  constexpr const char* kWho = "nbc_label_zones";
-  if (!c || !labels_dev || !rows_dev || !num_dev || !workspace_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
-  if (!zones_shape_ok(N, H, W))
-    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
-  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
-  const ZonesLayout lay = zones_layout(N, H, W);
-  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, lay.total)) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
-  NBC_HIP(launch_label_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, reinterpret_cast<long long*>(rows_dev), cap,
-                             reinterpret_cast<long long*>(num_dev), reinterpret_cast<int*>(ws + lay.parent), ws + lay.cls,
-                             reinterpret_cast<int*>(ws + lay.blocks), static_cast<hipStream_t>(hip_stream)));
-  return NBC_OK;
-}
-
-static bool pair_cap_ok(int pair_cap) { return pair_cap >= 1 && pair_cap <= NBC_ZONE_PAIRS_MAX_CAP; }
-
-size_t nbc_zone_match_workspace_bytes(int N, int H, int W, int pair_cap) {
-  return zones_shape_ok(N, H, W) && pair_cap_ok(pair_cap) ? zone_match_layout(N, H, W, pair_cap).total : 0;
-}
-
-int nbc_match_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H, int W,
-                    int64_t* out_rows_dev, int64_t* out_num_dev, int64_t* tgt_rows_dev, int64_t* tgt_num_dev, int cap,
-                    int64_t* pair_rows_dev, int64_t* pair_num_dev, int pair_cap, void* workspace_dev, size_t workspace_bytes,
-                    void* hip_stream) {
-  constexpr const char* kWho = "nbc_match_zones";
-  if (!c || !labels_dev || !target_grey_dev || !out_rows_dev || !out_num_dev || !tgt_rows_dev || !tgt_num_dev || !pair_rows_dev ||
-      !pair_num_dev || !workspace_dev)
-    return fail(kWho, NBC_ERR_INVALID, "null argument");
-  if (!zones_shape_ok(N, H, W))
-    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
-  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
-  if (!pair_cap_ok(pair_cap))
-    return fail(kWho, NBC_ERR_INVALID, "pair_cap must lie in 1.." + std::to_string(NBC_ZONE_PAIRS_MAX_CAP));
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
-  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, zone_match_layout(N, H, W, pair_cap).total)) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  NBC_HIP(launch_match_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, target_grey_dev, N, H, W,
-                             reinterpret_cast<long long*>(out_rows_dev), reinterpret_cast<long long*>(out_num_dev),
-                             reinterpret_cast<long long*>(tgt_rows_dev), reinterpret_cast<long long*>(tgt_num_dev), cap,
-                             reinterpret_cast<long long*>(pair_rows_dev), reinterpret_cast<long long*>(pair_num_dev), pair_cap,
-                             static_cast<unsigned char*>(workspace_dev), static_cast<hipStream_t>(hip_stream)));
-  return NBC_OK;
-}
-
-static bool contours_shape_ok(int N, int H, int W) {
-  return N >= 1 && N <= 65535 && H >= 1 && H <= NBC_CONTOUR_MAX_SIDE && W >= 1 && W <= NBC_CONTOUR_MAX_SIDE;
-}
-static constexpr int kContourMaxBins = 5793;         // ceil(hypot(4095, 4095)) + 1
-
-size_t nbc_contours_workspace_bytes(int N, int H, int W) { return contours_shape_ok(N, H, W) ? contours_layout(N, H, W).total : 0; }
-
-int nbc_contour_distances(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H, int W,
-                          int64_t* rows_dev, int bins, double* sum_d_dev, void* workspace_dev, size_t workspace_bytes,
-                          void* hip_stream) {
-  constexpr const char* kWho = "nbc_contour_distances";
-  if (!c || !labels_dev || !target_grey_dev || !rows_dev || !sum_d_dev || !workspace_dev)
-    return fail(kWho, NBC_ERR_INVALID, "null argument");
-  if (!contours_shape_ok(N, H, W))
-    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1.." + std::to_string(NBC_CONTOUR_MAX_SIDE));
-  if (bins < 2 || bins > kContourMaxBins) return fail(kWho, NBC_ERR_INVALID, "bins must lie in 2.." + std::to_string(kContourMaxBins));
-  if (labels_dtype != NBC_LABEL_U8 && labels_dtype != NBC_LABEL_I64) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
-  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, contours_layout(N, H, W).total)) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  NBC_HIP(launch_contour_distances(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, target_grey_dev, N, H, W,
-                                   reinterpret_cast<long long*>(rows_dev), bins, sum_d_dev, static_cast<unsigned char*>(workspace_dev),
-                                   static_cast<hipStream_t>(hip_stream)));
-  return NBC_OK;
-}
-
-size_t nbc_dropout_workspace_bytes(int N, int H, int W, int draws_per_pass) {
-  if (N < 1 || H < 8 || W < 8 || H > 65535 || draws_per_pass < 1 || (long long)H * W > 0x7fffffffLL) return 0;
-  const unsigned long long I = (unsigned long long)draws_per_pass * (unsigned long long)N;
-  if (I > 65535ull) return 0;
-  int h = 0, w = 0;
-  if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1 || (unsigned long long)h * w >= (1ull << 25)) return 0;
-  return dropout_layout(N, H, W, h, w, draws_per_pass).total;
-}
-
-int nbc_dropout_draws(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
-                      int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev, int64_t* counts_dev,
-                      void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
-  return dropout_passes("nbc_dropout_draws", c, N, H, W, image_ids_host, p, seed, first_draw, draws, min_pixels, exclude_nodes,
-                        logits_lowres_dev, counts_dev, false, nullptr, 0, workspace_dev, workspace_bytes, hip_stream);
-}
-
-// What nbc_head_logits and nbc_head_gradient ask of the context (nbc_dropout_draws' contract): its last forward was an
-// NBC_ARCH_FCN_RESNET50 forward of this (N, H, W) and its plan stands untouched.  *head: the plan's classifier.4.
-static int refit_state(const char* who, nbc_ctx* c, int N, int H, int W, const Op** head) {
-  if (c->arch != kArchFcn)
-    return fail(who, NBC_ERR_STATE, std::string("NBC_ARCH_FCN_RESNET50 only, the context holds ") + arch_name(c->arch));
-  if (!c->fwd_valid || c->fwd_N != N || c->fwd_H != H || c->fwd_W != W || !same_shape(c->plan, plan_key(c, N, H, W)))
-    return fail(who, NBC_ERR_STATE, "the context's last forward was not one of this (N, H, W), or its plan has been touched since: run "
-                                    "nbc_forward first");
-  *head = nullptr;
-  for (const Op& o : c->plan.ops)
-    if (o.kind == OP_HEAD1X1) *head = &o;
-  if (!*head || (*head)->Ci != 512 || (*head)->in_buf < 0 || !c->nonfinite)
-    return fail(who, NBC_ERR_STATE, "the plan holds no classifier.4 of 512 input channels");
-  return NBC_OK;
-}
-
-// the power of two the stored input of classifier.4 carries (f16x2; 0 otherwise)
-static int head_input_exponent(const nbc_ctx* c) {
-  int a = 0;
-  return stored_exponent(c, "classifier.0", &a) ? a : 0;
-}
-
-int nbc_head_logits(nbc_ctx* c, const float* theta_dev, int N, int H, int W, float* logits_lowres_dev, void* hip_stream) {
-  constexpr const char* kWho = "nbc_head_logits";
-  if (!c || !theta_dev || !logits_lowres_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
-  if (!aligned4(theta_dev, logits_lowres_dev)) return fail(kWho, NBC_ERR_INVALID, "theta_dev and logits_lowres_dev must be 4-byte aligned");
-  if (!per_image_shape_ok(N, H, W)) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
-  const Op* head = nullptr;
-  if (int rc = refit_state(kWho, c, N, H, W, &head)) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  NBC_HIP(c->refit_theta.reserve(kHeadThetaFloats * sizeof(float)));
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  float* theta = c->refit_theta.as<float>();
-  NBC_HIP(launch_head_theta(theta_dev, theta, head_input_exponent(c), s));
-  NBC_HIP(launch_head1x1(c->bufs[head->in_buf].get(), 512, theta, theta + 3 * 512, logits_lowres_dev, N, c->plan.h * c->plan.w,
-                         c->precision, nullptr, c->nonfinite.as<unsigned>(), s));
-  return NBC_OK;
-}
-
-size_t nbc_head_gradient_workspace_bytes(int N, int H, int W) {
-  if (!per_image_shape_ok(N, H, W)) return 0;
-  int h = 0, w = 0;
-  if (nbc_lowres_size(H, W, &h, &w) != NBC_OK || h < 1 || w < 1) return 0;
-  return align256((size_t)8 * N * head_grad_blocks(h * w) * kHeadThetaFloats);
-}
-
-int nbc_head_gradient(nbc_ctx* c, const double* grad_lowres_dev, int N, int H, int W, void* workspace_dev, size_t workspace_bytes,
-                      double* grad_theta_dev, void* hip_stream) {
-  constexpr const char* kWho = "nbc_head_gradient";
-  if (!c || !grad_lowres_dev || !workspace_dev || !grad_theta_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
-  if ((reinterpret_cast<uintptr_t>(grad_lowres_dev) | reinterpret_cast<uintptr_t>(grad_theta_dev)) & 7u)
-    return fail(kWho, NBC_ERR_INVALID, "grad_lowres_dev and grad_theta_dev must be 8-byte aligned");
-  const size_t need = nbc_head_gradient_workspace_bytes(N, H, W);
-  if (need == 0) return fail(kWho, NBC_ERR_INVALID, kPerImageShape);
-  if (int rc = check_workspace(kWho, workspace_dev, workspace_bytes, need)) return rc;
-  const Op* head = nullptr;
-  if (int rc = refit_state(kWho, c, N, H, W, &head)) return rc;
-  NBC_HIP(hipSetDevice(c->device));
-  NBC_HIP(launch_head_gradient(c->bufs[head->in_buf].get(), grad_lowres_dev, N, c->plan.h * c->plan.w, c->precision,
-                               head_input_exponent(c), static_cast<double*>(workspace_dev), grad_theta_dev,
-                               static_cast<hipStream_t>(hip_stream)));
-  return NBC_OK;
-}
-
-int nbc_dropout_votes(nbc_ctx* c, int N, int H, int W, const uint64_t* image_ids_host, double p, uint64_t seed, int first_draw,
-                      int draws, int min_pixels, int exclude_nodes, float* logits_lowres_dev, int64_t* counts_dev,
-                      uint32_t* votes_dev, int accumulate, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
-  return dropout_passes("nbc_dropout_votes", c, N, H, W, image_ids_host, p, seed, first_draw, draws, min_pixels, exclude_nodes,
-                        logits_lowres_dev, counts_dev, true, votes_dev, accumulate, workspace_dev, workspace_bytes, hip_stream);
 }
 
 int nbc_resize_cubic_u8(nbc_ctx* c, const uint8_t* src_dev, int H, int W, float* dst_dev, int out_h, int out_w,

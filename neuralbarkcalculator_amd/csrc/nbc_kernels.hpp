@@ -1,5 +1,7 @@
-// Launchers of the gfx950 kernels (definitions in conv_igemm_dma.hip, conv3x3_rows.hip, pointwise.hip, small_zones.hip, zones.hip, zone_match.hip, contours.hip, aspp.hip, bn_stats.hip,
-// head_refit.hip and efficientnet.hip).  The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
+// Launchers of the gfx950 kernels that another file than their own calls: the forward's (definitions in conv_igemm_dma.hip,
+// conv3x3_rows.hip, pointwise.hip, aspp.hip, bn_stats.hip and efficientnet.hip) and the few a second pass shares (small_zones.hip,
+// zones.hip, dropout_votes.hip, head_refit.hip).  A pass whose entry point is its launcher's only caller declares nothing here.
+// The host functions among them that size a launch (conv_rows_kind, choose_conv_tile, *_slices, dwconv_tiles,
 // bn_stats_workspace_bytes) are what nbc_plan.cpp builds the launch plan from.  Two rules of the launchers that are not
 // convolutions are written here once: with_precision (the run-time precision as a template argument) and grid_stride_blocks.
 #pragma once
@@ -100,33 +102,11 @@ hipError_t launch_head1x1(const void* x, int cin, const float* w, const float* b
 // the FCN head of every EfficientNet, whatever its width -- other bits than launch_head1x1 at cin = 512.
 hipError_t launch_head1x1_any(const float* x, const float* w, const float* bias, float* y, int N, int hw, int cin,
                               unsigned long long* counts_zero, unsigned* nonfinite, hipStream_t s);
-// classifier.4 of FCNHead behind a live Dropout (dropout_head.hip; the definition: include/nbc.h, nbc_dropout_draws): the
-// low-resolution logits y [draws][N][3][hw] of draws first_draw .. first_draw + draws - 1 from one read of x [N][hw][512]
-// stored elements.  ids_host: the N image identities, HOST memory, handed to the kernel by value (64 per launch: no copy,
-// no synchronisation).  threshold / keep_scale: dropout_threshold(p) / dropout_scale(p) of philox.hpp.  hw * 128 < 2^32.
-constexpr int kDropoutIdsPerLaunch = 64;
-struct DropoutIds {
-  unsigned long long id[kDropoutIdsPerLaunch];
-};
-hipError_t launch_head1x1_dropout(const void* x, const float* w, const float* bias, float* y, int N, int hw, int precision,
-                                  const uint64_t* ids_host, uint64_t seed, uint32_t threshold, float keep_scale, int first_draw,
-                                  int draws, unsigned* nonfinite, hipStream_t s);
 // The votes of a pass of the Dropout draws (dropout_votes.hip; the definition: votes.hpp): the final labels u8 [draws][N][P]
 // of the pass are counted into the vote words u32 [N][P] -- stored when `first`, added to what is there otherwise.
 // draws <= 65535 (a 16-bit field per class), votes 16-byte aligned for the vector path; labels at any address.
 hipError_t launch_vote_accumulate(const unsigned char* labels, int draws, int N, long long P, uint32_t* votes, bool first,
                                   hipStream_t s);
-// The refit of classifier.4 (head_refit.hip; the definitions: include/nbc.h, nbc_head_logits / nbc_head_gradient).
-// launch_head_theta: theta f32 [3][512] then [3] in state_dict units -> out, the 1536 weights times 2^-a (exact: what
-// nbc_pack_weights stores for a tensor read at the power 2^a), the bias copied; launch_head1x1 on `out` then runs classifier.4
-// with the caller's parameters in the forward's own machine code.
-constexpr int kHeadThetaFloats = 3 * 512 + 3;
-hipError_t launch_head_theta(const float* theta, float* out, int a, hipStream_t s);
-// d theta [N][3][513] f64 = sum over the hw cells of g [N][3][hw] f64 times x [N][hw][512] stored elements (column 512: the
-// plain sum, the bias), times 2^-a on the 512 weight columns.  One read of x; part: head_grad_blocks(hw) * N * 1539 doubles.
-inline int head_grad_blocks(int hw) { return (hw + 63) / 64; }      // a block owns 64 consecutive cells
-hipError_t launch_head_gradient(const void* x, const double* g, int N, int hw, int precision, int a, double* part, double* out,
-                                hipStream_t s);
 // The adjoint of the bicubic upsample (h, w) -> (H, W) on three f64 planes per image (head_refit.hip: ce_col_adjoint along the rows of
 // the image, then ce_row_adjoint down them): g [N][3] planes of H * W values, g_plane apart -> cols [N][3][H][w] -> out [N][3][h][w].
 // The eight device tables are nbc_bicubic_taps' (the index and coefficient tables 16-byte aligned).  What nbc_ce_gradient and
@@ -207,37 +187,15 @@ hipError_t launch_upsample_argmax(const float* lowres, int N, int h, int w, int 
 hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H, int W, int min_pixels, int exclude_nodes,
                                      unsigned char* bg, int* parent, int* size, unsigned long long* counts, hipStream_t s, int G = 1);
 // The zones of label maps (zones.hip; the contract: nbc_label_zones in include/nbc.h): rows int64 [N][cap][10], num int64 [N].
-// zones_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size.
+// zones_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size.  zone_match.hip labels twice
+// with these, in two such regions.  zones_shape_ok: 1 <= N <= 65535, H and W in 1..65535, H * W < 2^31.
 struct ZonesLayout {
   size_t parent, cls, blocks, total;         // int [N][H*W], u8 [N][H*W], int [N][ceil(H*W / 1024)]
 };
+bool zones_shape_ok(int N, int H, int W);
 ZonesLayout zones_layout(int N, int H, int W);
 hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, int W, long long* rows, int cap, long long* num,
                               int* parent, unsigned char* cls, int* blocks, hipStream_t s);
-// Output zones against target zones (zone_match.hip; the contract: nbc_match_zones in include/nbc.h): both inventories as
-// launch_label_zones gives them, and the pair rows int64 [N][pair_cap][3], pair_num int64 [N].  zone_match_layout: the regions
-// of the workspace (byte offsets, each 256-byte aligned) and its size -- two zones_layout regions (`zones` holds the offsets
-// inside each), the target's class map, and per image a table of `table` slots (a power of two >= 2 * pair_cap): 64-bit keys,
-// 32-bit counts, and a claim counter.  pair_cap in 1..NBC_ZONE_PAIRS_MAX_CAP; the shapes of launch_label_zones.
-struct ZoneMatchLayout {
-  ZonesLayout zones;
-  size_t out, tgt, tgt_cls, keys, counts, claimed, total;
-  int table;
-};
-ZoneMatchLayout zone_match_layout(int N, int H, int W, int pair_cap);
-hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
-                              long long* out_rows, long long* out_num, long long* tgt_rows, long long* tgt_num, int cap,
-                              long long* pair_rows, long long* pair_num, int pair_cap, unsigned char* ws, hipStream_t s);
-// Contour distances (contours.hip; the contract: nbc_contour_distances in include/nbc.h): rows int64 [N][4][NBC_CONTOUR_HEAD + bins],
-// sum_d f64 [N][4].  contours_layout: the regions of the workspace (byte offsets, each 256-byte aligned) and its size -- a mark
-// byte per pixel, the four u16 column distances per pixel, and an f64 partial per (image, set, row).  N in 1..65535, H and W
-// in 1..NBC_CONTOUR_MAX_SIDE, bins >= 2.
-struct ContoursLayout {
-  size_t mark, dist, partial, total;
-};
-ContoursLayout contours_layout(int N, int H, int W);
-hipError_t launch_contour_distances(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
-                                    long long* rows, int bins, double* sum_d, unsigned char* ws, hipStream_t s);
 // Preprocessor (models.py:191-203): uint8 HWC [H,W,3] -> ToTensor -> skimage cubic resize with reflected borders,
 // clipped to the input range -> any of: float32 HWC [out_h,out_w,3]; its uint8 form as imsave writes it; per output
 // row the number of pixels trim_black counts as lit.  minmax: two uints of scratch.

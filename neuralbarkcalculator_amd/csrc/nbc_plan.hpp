@@ -1,5 +1,5 @@
 // The launch plan of a forward: the ops of one (network, precision, batch, image size) in launch order and the sizes of the
-// activation buffers they share.  Building one makes no device call (nbc_plan.cpp); nbc_api.hip caches and runs them.
+// activation buffers they share.  Building one makes no device call (nbc_plan.cpp); the context (nbc_ctx.hpp) caches them and nbc_api.hip runs them.
 #pragma once
 #include <cstddef>
 #include <string>

@@ -92,6 +92,7 @@ struct ByteStream {
 
 // ---- host: what the entry points check and carve -----------------------------------------------------------------------
 inline int fail(const char* who, int code, const std::string& msg) { return set_error(code, std::string(who) + ": " + msg); }
+inline bool label_dtype_ok(int labels_dtype) { return labels_dtype == NBC_LABEL_U8 || labels_dtype == NBC_LABEL_I64; }
 
 // the batch a per-image pass accepts: grid.y carries the image, a pixel index fits 31 bits
 inline bool per_image_shape_ok(int N, int H, int W) {

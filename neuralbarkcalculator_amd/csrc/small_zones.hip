@@ -21,6 +21,7 @@
 //                  its group make the links to the image before it;
 // sum_sizes and apply then see components that span images.  G = 1 launches nothing more and is the per-image pass.
 #include "components.hpp"
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 
@@ -205,4 +206,44 @@ hipError_t launch_remove_small_zones(void* labels, int labels_i64, int N, int H,
   return run(static_cast<unsigned char*>(labels), N, H, W, G, min_pixels, exclude_nodes, bg, parent, size, counts, s);
 }
 
+namespace {
+
+// Both entry points run in the context's workspace, 9 bytes per pixel: parent ints, size ints, bg bytes.
+int run_in_context(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int G, int min_pixels, int exclude_nodes,
+                   int64_t* counts_dev, void* hip_stream) {
+  NBC_HIP(hipSetDevice(c->device));
+  const size_t px = (size_t)N * H * W;
+  NBC_HIP(c->zones_ws.reserve(px * 9 + 256, Grow::kMargin));   // grows by at least half, like the activation buffers
+  int* parent = c->zones_ws.as<int>();
+  int* size = parent + px;
+  unsigned char* bg = reinterpret_cast<unsigned char*>(size + px);
+  NBC_HIP(launch_remove_small_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, min_pixels, exclude_nodes, bg,
+                                    parent, size, reinterpret_cast<unsigned long long*>(counts_dev),
+                                    static_cast<hipStream_t>(hip_stream), G));
+  return NBC_OK;
+}
+
+}  // namespace
 }  // namespace nbc
+
+using namespace nbc;
+
+extern "C" int nbc_remove_small_zones(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int min_pixels,
+                                      int exclude_nodes, int64_t* counts_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_remove_small_zones";
+  if (!c || !labels_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (N < 1 || N > 65535 || H < 1 || W < 1 || min_pixels < 0) return fail(kWho, NBC_ERR_INVALID, "bad shape");
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  return run_in_context(c, labels_dev, labels_dtype, N, H, W, 1, min_pixels, exclude_nodes, counts_dev, hip_stream);
+}
+
+extern "C" int nbc_remove_small_zones_groups(nbc_ctx* c, void* labels_dev, int labels_dtype, int N, int H, int W, int G,
+                                             int min_pixels, int64_t* counts_dev, void* hip_stream) {
+  constexpr const char* kWho = "nbc_remove_small_zones_groups";
+  if (!c || !labels_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!per_image_shape_ok(N, H, W) || H > 65535 || min_pixels < 0) return fail(kWho, NBC_ERR_INVALID, "bad shape");
+  if (G < 1 || G > 64 || (long long)(G < N ? G : N) * H * W > 0x7fffffffLL)
+    return fail(kWho, NBC_ERR_INVALID, "bad group: 1 <= G <= 64 and g * H * W < 2^31 for the g = min(G, N) images of a group");
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  return run_in_context(c, labels_dev, labels_dtype, N, H, W, G, min_pixels, 0, counts_dev, hip_stream);
+}

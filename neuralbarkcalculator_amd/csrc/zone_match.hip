@@ -19,6 +19,7 @@
 // components.hpp's root_index (a parent's index is smaller than its child's, a root holds a negative code).
 // Counts are integer sums and the rows are sorted: an image's outputs are the same alone, in any batch, on any stream.
 #include "components.hpp"
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 
@@ -170,31 +171,55 @@ __global__ __launch_bounds__(kThreads) void pair_sort_kernel(const u64* __restri
   if (t == 0) num[blockIdx.x] = c;
 }
 
-}  // namespace
-
+// The regions of the workspace (byte offsets, each 256-byte aligned) and its size: two zones_layout regions (`zones` holds the
+// offsets inside each), the target's class map, and per image a table of `table` slots (a power of two >= 2 * pair_cap):
+// 64-bit keys, 32-bit counts, and a claim counter.
+struct ZoneMatchLayout {
+  ZonesLayout zones;
+  size_t out, tgt, tgt_cls, keys, counts, claimed, total;
+  int table;
+};
 ZoneMatchLayout zone_match_layout(int N, int H, int W, int pair_cap) {
   const ZonesLayout z = zones_layout(N, H, W);            // its total is a multiple of 256
   int table = 2;
   while (table < 2 * pair_cap) table <<= 1;
   Carver ws;
-  ZoneMatchLayout lay;
-  lay.zones = z;
-  lay.out = ws.take(z.total);
-  lay.tgt = ws.take(z.total);
-  lay.tgt_cls = ws.take((size_t)N * H * W);
-  lay.keys = ws.take(8 * (size_t)N * table);
-  lay.counts = ws.take(4 * (size_t)N * table);
-  lay.claimed = ws.take(4 * (size_t)N);
-  lay.total = ws.offset;
-  lay.table = table;
-  return lay;
+  const size_t out = ws.take(z.total), tgt = ws.take(z.total), tgt_cls = ws.take((size_t)N * H * W);
+  const size_t keys = ws.take(8 * (size_t)N * table), counts = ws.take(4 * (size_t)N * table), claimed = ws.take(4 * (size_t)N);
+  return {z, out, tgt, tgt_cls, keys, counts, claimed, ws.offset, table};
 }
 
-hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned char* target_grey, int N, int H, int W,
-                              long long* out_rows, long long* out_num, long long* tgt_rows, long long* tgt_num, int cap,
-                              long long* pair_rows, long long* pair_num, int pair_cap, unsigned char* ws, hipStream_t s) {
-  if (pair_cap < 1 || pair_cap > NBC_ZONE_PAIRS_MAX_CAP) return hipErrorInvalidValue;
+bool pair_cap_ok(int pair_cap) { return pair_cap >= 1 && pair_cap <= NBC_ZONE_PAIRS_MAX_CAP; }
+long long* ll(int64_t* p) { return reinterpret_cast<long long*>(p); }
+
+}  // namespace
+}  // namespace nbc
+
+using namespace nbc;
+
+extern "C" size_t nbc_zone_match_workspace_bytes(int N, int H, int W, int pair_cap) {
+  return zones_shape_ok(N, H, W) && pair_cap_ok(pair_cap) ? zone_match_layout(N, H, W, pair_cap).total : 0;
+}
+
+extern "C" int nbc_match_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, const uint8_t* target_grey_dev, int N, int H,
+                               int W, int64_t* out_rows_dev, int64_t* out_num_dev, int64_t* tgt_rows_dev, int64_t* tgt_num_dev,
+                               int cap, int64_t* pair_rows_dev, int64_t* pair_num_dev, int pair_cap, void* workspace_dev,
+                               size_t workspace_bytes, void* hip_stream) {
+  constexpr const char* kWho = "nbc_match_zones";
+  if (!c || !labels_dev || !target_grey_dev || !out_rows_dev || !out_num_dev || !tgt_rows_dev || !tgt_num_dev || !pair_rows_dev ||
+      !pair_num_dev || !workspace_dev)
+    return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!zones_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
+  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
+  if (!pair_cap_ok(pair_cap))
+    return fail(kWho, NBC_ERR_INVALID, "pair_cap must lie in 1.." + std::to_string(NBC_ZONE_PAIRS_MAX_CAP));
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
   const ZoneMatchLayout lay = zone_match_layout(N, H, W, pair_cap);
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, lay.total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
   const ZonesLayout& z = lay.zones;
   int* parent_out = reinterpret_cast<int*>(ws + lay.out + z.parent);
   int* parent_tgt = reinterpret_cast<int*>(ws + lay.tgt + z.parent);
@@ -205,22 +230,21 @@ hipError_t launch_match_zones(const void* labels, int labels_i64, const unsigned
   unsigned* counts = reinterpret_cast<unsigned*>(ws + lay.counts);
   int* claimed = reinterpret_cast<int*>(ws + lay.claimed);
 
-  hipError_t e = launch_label_zones(labels, labels_i64, N, H, W, out_rows, cap, out_num, parent_out, cls_out,
-                                    reinterpret_cast<int*>(ws + lay.out + z.blocks), s);
-  if (e != hipSuccess) return e;
+  NBC_HIP(launch_label_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, ll(out_rows_dev), cap, ll(out_num_dev),
+                             parent_out, cls_out, reinterpret_cast<int*>(ws + lay.out + z.blocks), s));
   const size_t px = (size_t)N * H * W, slots = (size_t)N * lay.table;
-  hipLaunchKernelGGL(target_class_plane_kernel, dim3(grid_stride_blocks(px / 4 + 1, 256, 8)), dim3(256), 0, s, target_grey, tgt_labels, px);
-  e = launch_label_zones(tgt_labels, 0, N, H, W, tgt_rows, cap, tgt_num, parent_tgt, cls_tgt,
-                         reinterpret_cast<int*>(ws + lay.tgt + z.blocks), s);
-  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(target_class_plane_kernel, dim3(grid_stride_blocks(px / 4 + 1, 256, 8)), dim3(256), 0, s, target_grey_dev, tgt_labels, px);
+  NBC_HIP(launch_label_zones(tgt_labels, 0, N, H, W, ll(tgt_rows_dev), cap, ll(tgt_num_dev), parent_tgt, cls_tgt,
+                             reinterpret_cast<int*>(ws + lay.tgt + z.blocks), s));
   hipLaunchKernelGGL(pair_clear_kernel, dim3(grid_stride_blocks(slots, 256, 8)), dim3(256), 0, s, keys, counts, claimed, slots,
                      N);                                  // slots >= 2 N: the first N threads exist
   int log2_table = 0;
   while ((1 << log2_table) < lay.table) ++log2_table;
   hipLaunchKernelGGL(pair_accumulate_kernel, dim3((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, N), dim3(kThreads), 0, s, parent_out,
                      cls_out, parent_tgt, cls_tgt, H, W, keys, counts, claimed, lay.table, 64 - log2_table, pair_cap);
-  hipLaunchKernelGGL(pair_sort_kernel, dim3(N), dim3(kThreads), 0, s, keys, counts, claimed, lay.table, pair_cap, pair_rows, pair_num);
-  return hipGetLastError();
+  hipLaunchKernelGGL(pair_sort_kernel, dim3(N), dim3(kThreads), 0, s, keys, counts, claimed, lay.table, pair_cap, ll(pair_rows_dev),
+                     ll(pair_num_dev));
+  NBC_HIP(hipGetLastError());
+  return NBC_OK;
 }
 
-}  // namespace nbc

@@ -19,6 +19,7 @@
 // Workspace: 4 B (parent) + 1 B (class) per pixel + 4 B per 1024 pixels.  Integer sums, mins and maxes do not depend on their
 // order: an image's rows are the same alone, in any batch, on any stream and from run to run.
 #include "components.hpp"
+#include "nbc_ctx.hpp"
 #include "nbc_kernels.hpp"
 #include "reduce.hpp"
 
@@ -218,4 +219,28 @@ hipError_t launch_label_zones(const void* labels, int labels_i64, int N, int H, 
   return hipGetLastError();
 }
 
+bool zones_shape_ok(int N, int H, int W) { return per_image_shape_ok(N, H, W) && H <= 65535 && W <= 65535; }
+
 }  // namespace nbc
+
+using namespace nbc;
+
+extern "C" size_t nbc_zones_workspace_bytes(int N, int H, int W) { return zones_shape_ok(N, H, W) ? zones_layout(N, H, W).total : 0; }
+
+extern "C" int nbc_label_zones(nbc_ctx* c, const void* labels_dev, int labels_dtype, int N, int H, int W, int64_t* rows_dev, int cap,
+                               int64_t* num_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+  constexpr const char* kWho = "nbc_label_zones";
+  if (!c || !labels_dev || !rows_dev || !num_dev || !workspace_dev) return fail(kWho, NBC_ERR_INVALID, "null argument");
+  if (!zones_shape_ok(N, H, W))
+    return fail(kWho, NBC_ERR_INVALID, "bad shape: 1 <= N <= 65535, H and W in 1..65535 and H * W < 2^31");
+  if (cap < 1) return fail(kWho, NBC_ERR_INVALID, "cap must be at least 1");
+  if (!label_dtype_ok(labels_dtype)) return fail(kWho, NBC_ERR_INVALID, "bad labels_dtype");
+  const ZonesLayout lay = zones_layout(N, H, W);
+  if (const int rc = check_workspace(kWho, workspace_dev, workspace_bytes, lay.total)) return rc;
+  NBC_HIP(hipSetDevice(c->device));
+  unsigned char* ws = static_cast<unsigned char*>(workspace_dev);
+  NBC_HIP(launch_label_zones(labels_dev, labels_dtype == NBC_LABEL_I64 ? 1 : 0, N, H, W, reinterpret_cast<long long*>(rows_dev), cap,
+                             reinterpret_cast<long long*>(num_dev), reinterpret_cast<int*>(ws + lay.parent), ws + lay.cls,
+                             reinterpret_cast<int*>(ws + lay.blocks), static_cast<hipStream_t>(hip_stream)));
+  return NBC_OK;
+}

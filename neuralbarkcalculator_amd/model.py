@@ -805,12 +805,10 @@ class FCNResNet50:
         self._check_labels(labels)
         if labels.dim() not in (2, 3):
             raise ValueError("labels must be [H,W] or [N,H,W]")
-        n = 1 if labels.dim() == 2 else int(labels.shape[0])
-        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        n, h, w = self._batch_hw(labels)
         counts = torch.empty((n, 3), dtype=torch.int64, device=self.device)
         with self._on_stream() as cur:
-            _lib.check(self._lib.nbc_remove_small_zones(self._ctx, labels.data_ptr(),
-                                                        _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+            _lib.check(self._lib.nbc_remove_small_zones(self._ctx, labels.data_ptr(), self._label_code(labels),
                                                         n, h, w, int(min_pixels), int(bool(exclude_nodes)),
                                                         counts.data_ptr(), cur.cuda_stream), "nbc_remove_small_zones")
         return labels, counts
@@ -833,8 +831,7 @@ class FCNResNet50:
             raise ValueError("min_pixels must be >= 0, got %r" % (min_pixels,))
         counts = torch.empty((n, 3), dtype=torch.int64, device=self.device)
         with self._on_stream() as cur:
-            _lib.check(self._lib.nbc_remove_small_zones_groups(self._ctx, labels.data_ptr(),
-                                                               _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+            _lib.check(self._lib.nbc_remove_small_zones_groups(self._ctx, labels.data_ptr(), self._label_code(labels),
                                                                n, h, w, group, int(min_pixels), counts.data_ptr(), cur.cuda_stream),
                        "nbc_remove_small_zones_groups")
         return labels, counts
@@ -863,8 +860,7 @@ class FCNResNet50:
         cap = int(cap)
         if cap < 1:
             raise ValueError("cap must be at least 1")
-        n = 1 if labels.dim() == 2 else int(labels.shape[0])
-        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        n, h, w = self._batch_hw(labels)
         need = int(self._lib.nbc_zones_workspace_bytes(n, h, w))
         if need == 0:
             raise ValueError("nbc_label_zones refuses a [%d,%d,%d] batch (N <= 65535, H, W <= 65535, H * W < 2^31)" % (n, h, w))
@@ -872,8 +868,7 @@ class FCNResNet50:
         num = torch.empty((n,), dtype=torch.int64, device=self.device)
         with self._on_stream() as cur:
             ws = self._grown_workspace("_zones_ws", need, cur)
-            _lib.check(self._lib.nbc_label_zones(self._ctx, labels.data_ptr(),
-                                                 _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8, n, h, w,
+            _lib.check(self._lib.nbc_label_zones(self._ctx, labels.data_ptr(), self._label_code(labels), n, h, w,
                                                  rows.data_ptr(), cap, num.data_ptr(), ws.data_ptr(), ws.numel(), cur.cuda_stream),
                        "nbc_label_zones")
         return rows, num
@@ -891,17 +886,13 @@ class FCNResNet50:
         ``zones.match_cpu``, integer for integer; works for every architecture, since it only sees labels."""
         self._require_ctx()
         self._check_labels(labels)
-        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
-            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
-        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
-            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
+        self._check_target_like(labels, target)
         cap, pair_cap = int(cap), int(pair_cap)
         if cap < 1:
             raise ValueError("cap must be at least 1")
         if not 1 <= pair_cap <= _lib.PAIRS_MAX_CAP:
             raise ValueError("pair_cap must lie in 1..%d" % _lib.PAIRS_MAX_CAP)
-        n = 1 if labels.dim() == 2 else int(labels.shape[0])
-        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        n, h, w = self._batch_hw(labels)
         need = int(self._lib.nbc_zone_match_workspace_bytes(n, h, w, pair_cap))
         if need == 0:
             raise ValueError("nbc_match_zones refuses a [%d,%d,%d] batch (N <= 65535, H, W <= 65535, H * W < 2^31)" % (n, h, w))
@@ -910,8 +901,7 @@ class FCNResNet50:
         out_num, tgt_num, pair_num = (torch.empty((n,), dtype=torch.int64, device=self.device) for _ in range(3))
         with self._on_stream() as cur:
             ws = self._grown_workspace("_zone_match_ws", need, cur)
-            _lib.check(self._lib.nbc_match_zones(self._ctx, labels.data_ptr(),
-                                                 _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8, target.data_ptr(),
+            _lib.check(self._lib.nbc_match_zones(self._ctx, labels.data_ptr(), self._label_code(labels), target.data_ptr(),
                                                  n, h, w, out_rows.data_ptr(), out_num.data_ptr(), tgt_rows.data_ptr(),
                                                  tgt_num.data_ptr(), cap, pair_rows.data_ptr(), pair_num.data_ptr(), pair_cap,
                                                  ws.data_ptr(), ws.numel(), cur.cuda_stream), "nbc_match_zones")
@@ -930,12 +920,8 @@ class FCNResNet50:
         from . import contours as ct
         self._require_ctx()
         self._check_labels(labels)
-        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
-            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
-        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
-            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
-        n = 1 if labels.dim() == 2 else int(labels.shape[0])
-        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        self._check_target_like(labels, target)
+        n, h, w = self._batch_hw(labels)
         need = int(self._lib.nbc_contours_workspace_bytes(n, h, w))
         if need == 0:
             raise ValueError("nbc_contour_distances refuses a [%d,%d,%d] batch (N <= 65535, H, W <= %d)" % (n, h, w, ct.MAX_SIDE))
@@ -946,8 +932,7 @@ class FCNResNet50:
         sum_d = torch.empty((n, _lib.CONTOUR_SETS), dtype=torch.float64, device=self.device)
         with self._on_stream() as cur:
             ws = self._grown_workspace("_contours_ws", need, cur)
-            _lib.check(self._lib.nbc_contour_distances(self._ctx, labels.data_ptr(),
-                                                       _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+            _lib.check(self._lib.nbc_contour_distances(self._ctx, labels.data_ptr(), self._label_code(labels),
                                                        target.data_ptr(), n, h, w, rows.data_ptr(), bins, sum_d.data_ptr(),
                                                        ws.data_ptr(), ws.numel(), cur.cuda_stream), "nbc_contour_distances")
         return rows, sum_d
@@ -960,15 +945,11 @@ class FCNResNet50:
         ``[N,3,3]``: ``conf[n, t, p]`` = pixels of target class t predicted as p."""
         self._require_ctx()
         self._check_labels(labels)
-        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
-            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
-        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
-            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
-        n = 1 if labels.dim() == 2 else int(labels.shape[0])
-        h, w = int(labels.shape[-2]), int(labels.shape[-1])
+        self._check_target_like(labels, target)
+        n, h, w = self._batch_hw(labels)
         conf = torch.empty((n, NUM_CLASSES, NUM_CLASSES), dtype=torch.int64, device=self.device)
         with self._on_stream() as cur:
-            _lib.check(self._lib.nbc_confusion(labels.data_ptr(), _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8,
+            _lib.check(self._lib.nbc_confusion(labels.data_ptr(), self._label_code(labels),
                                                target.data_ptr(), n, h, w, conf.data_ptr(), cur.cuda_stream), "nbc_confusion")
         return conf
 
@@ -1630,6 +1611,22 @@ class FCNResNet50:
     def _check_labels(self, labels: torch.Tensor):
         if labels.device != self.device or labels.dtype not in (torch.uint8, torch.int64) or not labels.is_contiguous():
             raise ValueError("labels must be a contiguous uint8 or int64 tensor on %s" % (self.device,))
+
+    def _check_target_like(self, labels: torch.Tensor, target: torch.Tensor):
+        """``target``: the contiguous uint8 grey mask of checked ``labels``, ``[H,W]`` or ``[N,H,W]`` like them."""
+        if target.device != self.device or target.dtype != torch.uint8 or not target.is_contiguous():
+            raise ValueError("target must be a contiguous uint8 tensor on %s" % (self.device,))
+        if labels.dim() not in (2, 3) or labels.shape != target.shape or labels.numel() == 0:
+            raise ValueError("labels and target must both be [H,W] or [N,H,W] of the same non-empty shape")
+
+    @staticmethod
+    def _label_code(labels: torch.Tensor) -> int:
+        return _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8
+
+    @staticmethod
+    def _batch_hw(labels: torch.Tensor) -> Tuple[int, int, int]:
+        """(N, H, W) of ``[N,H,W]`` labels, or (1, H, W) of ``[H,W]`` ones."""
+        return 1 if labels.dim() == 2 else int(labels.shape[0]), int(labels.shape[-2]), int(labels.shape[-1])
 
     def _check_rgb_u8(self, image: torch.Tensor):
         if image.device != self.device or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 \

@@ -76,3 +76,22 @@ def test_zones_groups_refuses_before_the_device_is_touched(built_lib):
     for kw in bad:
         assert call(**kw) == _lib.NBC_ERR_INVALID, kw
         assert _lib.last_error().startswith("nbc_remove_small_zones_groups:"), kw
+    # the order of the refusals: null argument, shape, group, dtype
+    for kw, text in [(dict(labels=None, N=0, G=0, dtype=7), "null argument"), (dict(N=0, G=0, dtype=7), "bad shape"),
+                     (dict(G=0, dtype=7), "bad group: 1 <= G <= 64 and g * H * W < 2^31 for the g = min(G, N) images of a group"),
+                     (dict(dtype=7), "bad labels_dtype")]:
+        assert call(**kw) == _lib.NBC_ERR_INVALID, kw
+        assert _lib.last_error() == "nbc_remove_small_zones_groups: " + text, kw
+
+
+def test_remove_small_zones_refuses_before_the_context_is_read(built_lib):
+    """The per-image entry point with a fake context: every refusal by its whole text, in the order null argument, shape, dtype."""
+    def call(ctx=FAKE, labels=FAKE, dtype=_lib.LABEL_I64, N=2, H=64, W=64, min_pixels=150):
+        return built_lib.nbc_remove_small_zones(ctx, labels, dtype, N, H, W, min_pixels, 0, None, None)
+
+    for kw, text in [(dict(ctx=None), "null argument"), (dict(labels=None), "null argument"), (dict(labels=None, N=0, dtype=7), "null argument"),
+                     (dict(N=0), "bad shape"), (dict(N=65536), "bad shape"), (dict(H=0), "bad shape"), (dict(W=-1), "bad shape"),
+                     (dict(min_pixels=-1), "bad shape"), (dict(N=0, dtype=7), "bad shape"),
+                     (dict(dtype=7), "bad labels_dtype"), (dict(dtype=-1), "bad labels_dtype")]:
+        assert call(**kw) == _lib.NBC_ERR_INVALID, kw
+        assert _lib.last_error() == "nbc_remove_small_zones: " + text, kw
